@@ -255,9 +255,9 @@ class Counters:
 
 
 def toolchain_probe():
-    """What a pin against the real Rust prover needs, looked for on THIS host (recorded in cpu_baseline.reference_attempt)."""
+    """What a pin against the real Rust prover needs, looked for on THIS host (recorded in cpu_baseline.reference_attempt). Local
+    checks only: the benchmark never opens a connection to an outside host."""
     import shutil
-    import socket
     import subprocess
     cargo = shutil.which("cargo") is not None
     nightly = False
@@ -266,14 +266,8 @@ def toolchain_probe():
             nightly = "nightly" in subprocess.run(["rustc", "--version"], capture_output=True, text=True, timeout=10).stdout
         except Exception:
             pass
-    network = False
-    try:
-        socket.create_connection(("github.com", 443), timeout=2).close()
-        network = True
-    except Exception:
-        pass
-    return {"cargo": cargo, "rustc_nightly": nightly, "network": network, "reference_checkout": bool(os.environ.get("HYPER_GRECO")),
-            "pin": "not attempted: " + ("no cargo on this host" if not cargo else "no network for the reference's git dependencies" if not network else
+    return {"cargo": cargo, "rustc_nightly": nightly, "reference_checkout": bool(os.environ.get("HYPER_GRECO")),
+            "pin": "not attempted: " + ("no cargo on this host" if not cargo else
                                         "no reference checkout ($HYPER_GRECO)" if not os.environ.get("HYPER_GRECO") else "see rust/hg-shim/tests/proof_dump.rs")}
 
 
@@ -360,6 +354,19 @@ def max_over_ranks(elapsed, world, dist, torch, device):
 
 def witness_seed(base_seed, n, rank):
     return base_seed + n + 7919 * rank  # one independent witness per rank
+
+
+def dump_outputs(out_dir, proof):
+    """--dump-outputs: the proof a timed step returned, as DIR/proof.npy. The bytes are little-endian 64-bit field elements; they are
+    written as 32-bit words, which float64 holds exactly (a 64-bit element would not fit its 53-bit mantissa)."""
+    import numpy as np
+    if len(proof) % 4:
+        raise ValueError(f"proof of {len(proof)} bytes is not a whole number of 32-bit words")
+    words = np.frombuffer(proof, dtype="<u4").astype(np.float64)
+    if words.nbytes > 64 << 20:
+        raise ValueError(f"proof dump of {words.nbytes} bytes exceeds 64 MB")
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "proof.npy"), words)
 
 
 def selftest_dist(args, rank, world, dist, torch):
@@ -545,6 +552,9 @@ def main():
                     help="N>1: shard ONE proof over the GPUs (strong scaling, default) or one independent proof per GPU (weak)")
     ap.add_argument("--selftest-dist", action="store_true",
                     help="CPU/gloo self-test of the N>1 plumbing (rendezvous, barrier, max-over-ranks, rank-0 JSON); proves nothing")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned to DIR/proof.npy: the proof's bytes as little-endian "
+                         "32-bit words, one float64 each (exact); the inputs are seeded, so runs with the same arguments compare word for word")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -553,12 +563,12 @@ def main():
     if world != args.gpus and world > 1:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
 
-    import torch
-    import torch.distributed as dist
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.selftest_dist:
+        import torch
+        import torch.distributed as dist
         return selftest_dist(args, rank, world, dist, torch)
-    import __graft_entry__ as entry
-    hg = entry.load_package()
 
     # test hooks (single-GPU box): HG_BENCH_BACKEND=gloo reduces through host tensors, HG_BENCH_SAME_DEVICE=1 puts
     # every rank on device 0. The driver's multi-GPU runs use neither: RCCL ("nccl"), one rank per GPU.
@@ -566,7 +576,22 @@ def main():
     if os.environ.get("HG_BENCH_SAME_DEVICE") == "1":
         local_rank = 0
     shard = world > 1 and args.mode == "shard"
-    torch.cuda.set_device(local_rank)
+    # PyTorch ships its own HIP runtime under the same soname as the ROCm one the library is built against, and whichever of the two
+    # loads first serves the library. Bound to PyTorch's, the library's prove crashes (SIGSEGV), so the library is loaded BEFORE
+    # PyTorch wherever PyTorch is only plumbing: one GPU does not import it at all, N > 1 over gloo uses it for host-side collectives
+    # only. Only the RCCL path (torch_gpu) hands the device to PyTorch, and there it is imported first as before.
+    torch_gpu = world > 1 and backend == "nccl"
+    import __graft_entry__ as entry
+    hg = entry.load_package()
+    if not torch_gpu:
+        hg.lib()
+    torch = dist = None
+    if world > 1:
+        import torch
+        import torch.distributed as dist
+    hip_device_sync = hg.lib().hipDeviceSynchronize   # (dlsym on the library's handle: the HIP runtime the library is bound to)
+    if torch_gpu:
+        torch.cuda.set_device(local_rank)
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         if backend == "nccl":
@@ -578,7 +603,10 @@ def main():
     def barrier():
         if world > 1:
             dist.barrier()
-        torch.cuda.synchronize()
+        if torch_gpu:
+            torch.cuda.synchronize()
+        elif hip_device_sync() != 0:
+            raise RuntimeError("hipDeviceSynchronize failed")
 
     ctx = hg.Context(local_rank)
     bfv = hg.BfvEncrypt.new(args.n, args.k)
@@ -720,6 +748,8 @@ def main():
     gc.enable()
     for i in range(args.steps):   # every proof of region B against the walked proof of the same witness
         assert outs[i].bytes() == walked[i % NW], f"timed step {i}: the replayed proof differs from the walked proof of witness {i % NW}"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs[args.steps - 1].bytes())
     for i in range(NW):
         assert step(i).bytes() == walked[i]
     resident_all = None
