@@ -859,6 +859,17 @@ int hg_verify_bn254(const hg_pk* pk, const hg_witness* w, const uint8_t* proof, 
     HG_CATCH(-1)
 }
 
+int hg_verify_device_bn254(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, const uint8_t* proof, size_t len) {
+    HG_TRY
+    if (!ctx || !pk || !w || !proof || !pk->ctx) throw Error("hg_verify_device_bn254: needs a device context and a device prover key");
+    check_witness(pk, w, "hg_verify_device_bn254");
+    std::string why = hg::bn::verify_proof_device_bn254(ctx, pk, w->w, proof, len);
+    if (why.empty()) return 0;
+    g_last_error = why;
+    return 1;
+    HG_CATCH(-1)
+}
+
 int hg_circuit_eval(const hg_pk* pk, const hg_witness* w, uint64_t* lasso_in, size_t lasso_cap, uint64_t* sum_out, size_t sum_cap) {
     HG_TRY
     if (!pk || !w) throw Error("hg_circuit_eval: null argument");

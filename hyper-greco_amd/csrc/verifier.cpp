@@ -200,8 +200,8 @@ template <class F> struct Verifier {
         void set_mode(int mode) { c.set_mode(mode); }
     } ch;
     bool ext_memcheck = false;  // mode bit 1: gamma, tau stay in E (prover.rs:36-39 truncates them; README.md:108)
-    // the table-sized checks elsewhere (Goldilocks, mode 0): see VerifyBackend in host.hpp
-    VerifyBackend* dev = nullptr;
+    // the table-sized checks elsewhere (mode 0): see VerifyBackendT in host.hpp
+    VerifyBackendT<E>* dev = nullptr;
     std::vector<std::function<void()>> deferred;   // checks that need a ticket: run after dev->finish()
     std::function<E()> late_claim = nullptr;       // a late-bound term of the NEXT node's initial claim (the output evaluation)
     E read_e() { E v = F::read(bytes); ch.absorb(v); return v; }
@@ -349,8 +349,8 @@ template <class F> struct Verifier {
         return eqc;
     }
 
-    static VerifyBackend::ClaimOffs claim_offs(const std::vector<Claim>& cl, size_t alpha_off) {
-        VerifyBackend::ClaimOffs o;
+    static typename VerifyBackendT<E>::ClaimOffs claim_offs(const std::vector<Claim>& cl, size_t alpha_off) {
+        typename VerifyBackendT<E>::ClaimOffs o;
         for (auto& c : cl) { if (c.off == NOPOS) throw Reject("verifier: a claim point is not a run of the challenge chain"); o.point_off.push_back(c.off); }
         o.unit = cl.size() == 1; o.alpha_off = alpha_off;
         return o;
@@ -358,7 +358,7 @@ template <class F> struct Verifier {
     // the same node checks with the table sums taken from the backend (tickets), the comparisons deferred
     std::vector<std::vector<Claim>> vanilla_dev(int id, const HNode& n, const std::vector<Claim>& cl, const std::vector<E>& alpha, size_t alpha_off) {
         const int nin = n.log2_sub_in + n.log2_reps;
-        VerifyBackend* D = dev;
+        VerifyBackendT<E>* D = dev;
         D->begin_node(id, claim_offs(cl, alpha_off));
         E claim = F::zero();
         for (size_t a = 0; a < cl.size(); a++) claim = F::add(claim, F::mul(cl[a].value, alpha[a]));
@@ -389,8 +389,7 @@ template <class F> struct Verifier {
         auto r2 = sumcheck(2, nin, r1.first, n.lin.empty() ? std::function<E()>(nullptr) : lin, &y_off);
         std::vector<E> w(n.arity, F::zero());
         for (int i = 0; i < n.arity; i++) if (n.right_use[i]) { w[i] = read_e(); sub[i].push_back(Claim{r2.second, w[i], y_off}); }
-        std::vector<E2> u2(u.begin(), u.end());
-        D->set_y(y_off, u2);
+        D->set_y(y_off, u);
         const std::vector<int> tk = D->mul_terms();
         const E fin2 = r2.first;
         deferred.push_back([D, tk, w, fin2] {
@@ -402,7 +401,7 @@ template <class F> struct Verifier {
         return sub;
     }
     std::vector<std::vector<Claim>> fft_dev(int id, const HNode& n, const std::vector<Claim>& cl, const std::vector<E>& alpha, size_t alpha_off) {
-        VerifyBackend* D = dev;
+        VerifyBackendT<E>* D = dev;
         D->begin_node(id, claim_offs(cl, alpha_off));
         E claim = F::zero();
         for (size_t a = 0; a < cl.size(); a++) claim = F::add(claim, F::mul(cl[a].value, alpha[a]));
@@ -611,18 +610,19 @@ static std::string verify_impl(const Params& p, const LassoPlan& lp, const HCirc
     }
 }
 
-// The same walk with the table-sized sums taken from a backend (Goldilocks, mode 0): the host parses the proof, checks the round
-// polynomials and the Lasso scalars, and hands out tickets; the comparisons that need them run after dev.finish().
-static std::string verify_with_backend(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len) {
-    typedef GlField F;
-    typedef F::E E;
-    typedef Verifier<F>::Claim Claim;
+// The same walk with the table-sized sums taken from a backend (mode 0, either field): the host parses the proof, checks the round
+// polynomials and the Lasso scalars, and hands out tickets; the comparisons that need them run after dev.finish(). Chain offsets
+// count E challenges: two base challenges each over Goldilocks, one Fr each over BN254 (E = F there).
+template <class F>
+static std::string verify_with_backend(VerifyBackendT<typename F::E>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len) {
+    typedef typename F::E E;
+    typedef typename Verifier<F>::Claim Claim;
     try {
         Verifier<F> V;
         V.bytes = ProofBytes{proof, len};
         V.ch.set_mode(0);
         V.dev = &dev;
-        VerifyBackend* D = &dev;
+        VerifyBackendT<E>* D = &dev;
         const size_t p_off = V.ch.n;
         std::vector<E> point = V.squeeze_n(p.ct0is_log2());         // sk_encryption_circuit.rs:482
         const int t_out = D->mle_ct0is(p_off, p.ct0is_log2());      // :495 - the value itself is only known after finish()
@@ -671,7 +671,10 @@ static std::string verify_with_backend(VerifyBackend& dev, const Params& p, cons
 }  // namespace
 
 std::string verify_proof_with(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len) {
-    return verify_with_backend(dev, p, lp, c, proof, len);
+    return verify_with_backend<GlField>(dev, p, lp, c, proof, len);
+}
+std::string verify_proof_with_bn254(VerifyBackendT<bn::Fr>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len) {
+    return verify_with_backend<BnField>(dev, p, lp, c, proof, len);
 }
 
 // return "" on accept, the rejection reason otherwise

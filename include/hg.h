@@ -351,6 +351,12 @@ int hg_prove_bn254(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, uint8_t* p
 /* = BfvEncrypt::verify::<Fr, Fr> [REF sk_encryption_circuit.rs:462-517]: host side (no device needed; pk may come from
  *   hg_setup(NULL, ..)). Returns 0 accept, 1 reject (reason in hg_last_error), -1 error. */
 int hg_verify_bn254(const hg_pk* pk, const hg_witness* w, const uint8_t* proof, size_t len);
+/* The same check with the table-sized work on the device [REF sk_encryption_circuit.rs:462-517, 614-626; lasso/src/memory_checking/
+ * verifier.rs:130-176]: the host parses the proof and checks the round polynomials and the Lasso scalars; the eq tables, the
+ * wiring-predicate sums of the Vanilla nodes, the DFT rows of the FFT nodes and the MLE evaluations of the public inputs run as
+ * kernels over bn256::Fr (one stream, one synchronisation). Needs a device context and a device key (hg_setup(ctx, ..)). Same return
+ * values and the same accept / reject decisions as hg_verify_bn254; mode 0 only. */
+int hg_verify_device_bn254(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, const uint8_t* proof, size_t len);
 
 /* profiling: level 0 off, 1 = events around the selected kernel class only, 2 = every class */
 int hg_profile(hg_ctx* ctx, int level);

@@ -118,7 +118,8 @@ impl HipBfvEncrypt {
             match family {
                 // the device-side verifier (2.8 ms at n=32768 k=16 against 79 ms on the host; same accept / reject decisions)
                 Family::Goldilocks => hg_verify_device(self.ctx, self.pk, w, proof.as_ptr(), proof.len()),
-                Family::Bn254 => hg_verify_bn254(self.pk, w, proof.as_ptr(), proof.len()),
+                // the same over bn256::Fr (same accept / reject decisions as hg_verify_bn254)
+                Family::Bn254 => hg_verify_device_bn254(self.ctx, self.pk, w, proof.as_ptr(), proof.len()),
             }
         };
         unsafe { hg_witness_free(w) };
