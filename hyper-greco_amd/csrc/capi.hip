@@ -848,6 +848,18 @@ int hg_verify_device(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, const ui
     HG_CATCH(-1)
 }
 
+int hg_verify_device_mode(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, int mode, const uint8_t* proof, size_t len) {
+    HG_TRY
+    if (!ctx || !pk || !w || !proof || !pk->ctx) throw Error("hg_verify_device_mode: needs a device context and a device prover key");
+    if (mode < 0 || mode > 3) throw Error("hg_verify_device_mode: unknown mode bits");
+    check_witness(pk, w, "hg_verify_device_mode");
+    std::string why = verify_proof_device(ctx, pk, w->w, proof, len, mode);
+    if (why.empty()) return 0;
+    g_last_error = why;
+    return 1;
+    HG_CATCH(-1)
+}
+
 int hg_verify_bn254(const hg_pk* pk, const hg_witness* w, const uint8_t* proof, size_t len) {
     HG_TRY
     if (!pk || !w || !proof) throw Error("hg_verify_bn254: null argument");

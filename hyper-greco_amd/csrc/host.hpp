@@ -183,8 +183,9 @@ HCircuit build_circuit(const Params& p, const LassoPlan& lp);
 std::vector<std::vector<u64>> circuit_evaluate(const HCircuit& c, const Params& p, const Witness& w);
 // BfvEncrypt::verify on the host; "" = accept, otherwise the rejection reason (verifier.cpp)
 std::string verify_proof(const Params& p, const LassoPlan& lp, const HCircuit& c, const Witness& w, const uint8_t* proof, size_t len, int mode = 0);
-// The verifier's table-sized work done elsewhere (verifier_dev.hip, bn254_verify.inc: on the device). Mode 0 only: every evaluation
-// point is a run of the fixed challenge chain, so a point is an offset into it (in units of E challenges). Every method DEFERS: it
+// The verifier's table-sized work done elsewhere (verifier_dev.hip, bn254_verify.inc: on the device). Every evaluation point is a run
+// of the challenge chain, so a point is an offset into it (in units of E challenges): in mode 0 the fixed chain; in the protocol modes
+// (Goldilocks only) the challenges the walk squeezed, handed over by set_chain() ahead of finish(). Every method DEFERS: it
 // enqueues work and returns a ticket; value(ticket) is valid after finish(). The walk itself (proof parsing, sum-check round checks,
 // the Lasso scalar checks) stays on the host and never waits for a ticket - checks that need one are evaluated after finish().
 // E is the field the walk runs in: E2 (Goldilocks) or bn::Fr (BN254, Montgomery form).
@@ -201,11 +202,12 @@ template <class E> struct VerifyBackendT {
     virtual void end_node() = 0;
     virtual int mle_input(size_t k, size_t point_off, int nvars) = 0;   // input table k (chain_par! order) at a point
     virtual int mle_ct0is(size_t point_off, int nvars) = 0;
+    virtual void set_chain(const std::vector<E>& chain) { (void)chain; }   // modes != 0: every challenge the walk squeezed, in order
     virtual void finish() = 0;
     virtual E value(int ticket) const = 0;
 };
 typedef VerifyBackendT<E2> VerifyBackend;
-std::string verify_proof_with(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len);
+std::string verify_proof_with(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode);
 namespace bn { struct Fr; }
 std::string verify_proof_with_bn254(VerifyBackendT<bn::Fr>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len);
 // the same over bn256::Fr (F = E = Fr, 32-byte proof elements): the bn254 test family

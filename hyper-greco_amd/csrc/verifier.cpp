@@ -195,12 +195,14 @@ template <class F> struct Verifier {
     struct CountingChal {   // the field's challenge source plus the number of E challenges squeezed so far
         typename F::Chal c;
         size_t n = 0;
-        E squeeze() { n++; return c.squeeze(); }
+        bool keep = false;      // record every challenge in squeeze order (a backend's chain in the protocol modes)
+        std::vector<E> seq;
+        E squeeze() { n++; E v = c.squeeze(); if (keep) seq.push_back(v); return v; }
         void absorb(E v) { c.absorb(v); }
         void set_mode(int mode) { c.set_mode(mode); }
     } ch;
     bool ext_memcheck = false;  // mode bit 1: gamma, tau stay in E (prover.rs:36-39 truncates them; README.md:108)
-    // the table-sized checks elsewhere (mode 0): see VerifyBackendT in host.hpp
+    // the table-sized checks elsewhere: see VerifyBackendT in host.hpp
     VerifyBackendT<E>* dev = nullptr;
     std::vector<std::function<void()>> deferred;   // checks that need a ticket: run after dev->finish()
     std::function<E()> late_claim = nullptr;       // a late-bound term of the NEXT node's initial claim (the output evaluation)
@@ -610,17 +612,21 @@ static std::string verify_impl(const Params& p, const LassoPlan& lp, const HCirc
     }
 }
 
-// The same walk with the table-sized sums taken from a backend (mode 0, either field): the host parses the proof, checks the round
+// The same walk with the table-sized sums taken from a backend (either field): the host parses the proof, checks the round
 // polynomials and the Lasso scalars, and hands out tickets; the comparisons that need them run after dev.finish(). Chain offsets
-// count E challenges: two base challenges each over Goldilocks, one Fr each over BN254 (E = F there).
+// count E challenges: two base challenges each over Goldilocks, one Fr each over BN254 (E = F there). In mode 0 they index the
+// fixed chain; in the protocol modes (Goldilocks only) the walk records what it squeezed and hands it to dev.set_chain() before
+// finish(), and the offsets index that record.
 template <class F>
-static std::string verify_with_backend(VerifyBackendT<typename F::E>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len) {
+static std::string verify_with_backend(VerifyBackendT<typename F::E>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode) {
     typedef typename F::E E;
     typedef typename Verifier<F>::Claim Claim;
     try {
         Verifier<F> V;
         V.bytes = ProofBytes{proof, len};
-        V.ch.set_mode(0);
+        V.ch.set_mode(mode);
+        V.ext_memcheck = (mode & 2) != 0;
+        V.ch.keep = mode != 0;
         V.dev = &dev;
         VerifyBackendT<E>* D = &dev;
         const size_t p_off = V.ch.n;
@@ -660,6 +666,7 @@ static std::string verify_with_backend(VerifyBackendT<typename F::E>& dev, const
                 const E want = cl.value;
                 V.deferred.push_back([D, t, want, k] { if (!F::eq(D->value(t), want)) throw Reject("input claim mismatch at input " + std::to_string(k)); });
             }
+        if (mode != 0) dev.set_chain(V.ch.seq);
         dev.finish();
         for (auto& f : V.deferred) f();
         return "";
@@ -670,11 +677,11 @@ static std::string verify_with_backend(VerifyBackendT<typename F::E>& dev, const
 
 }  // namespace
 
-std::string verify_proof_with(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len) {
-    return verify_with_backend<GlField>(dev, p, lp, c, proof, len);
+std::string verify_proof_with(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode) {
+    return verify_with_backend<GlField>(dev, p, lp, c, proof, len, mode);
 }
 std::string verify_proof_with_bn254(VerifyBackendT<bn::Fr>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len) {
-    return verify_with_backend<BnField>(dev, p, lp, c, proof, len);
+    return verify_with_backend<BnField>(dev, p, lp, c, proof, len, 0);
 }
 
 // return "" on accept, the rejection reason otherwise

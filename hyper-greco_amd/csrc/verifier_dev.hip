@@ -5,7 +5,10 @@
 //   Vanilla nodes as Libra gathers over the reverse CSR wiring followed by dot products with the eq table of the sum-check point,
 //   the DFT-row tables of the FFT nodes, and the MLE evaluations of the public inputs.
 // Everything is enqueued on one stream while the host keeps parsing; one synchronisation; then the deferred comparisons.
-// Goldilocks, protocol mode 0 (the evaluation points are offsets into the fixed chain).
+// Goldilocks, protocol modes 0 to 3. The evaluation points are offsets into a challenge chain: in mode 0 the fixed chain the context
+// keeps in HBM (ctx->d_chal); in modes 1 to 3 the challenges the walk squeezed (with the absorbing transcript they depend on the proof),
+// staged into the arena at finish() ahead of the job descriptors. ctx->d_chal itself is never written: the mode-0 prover and its
+// recorded launch graphs read it.
 #include <cstring>
 #include <omp.h>
 #include "prover.hpp"
@@ -55,6 +58,12 @@ struct DevBackend : VerifyBackend {
     hg_ctx* ctx;
     const hg_pk* pk;
     hipStream_t st;
+    // the chain the eq and DFT-row jobs index: ctx->d_chal (mode 0), or the walk's own challenges (modes 1-3: own_chain), which
+    // set_chain() hands over and finish() stages; chain_need = one past the last chain entry a recorded job reads
+    const bool own_chain;
+    const E2* chal = nullptr;   // (set by finish())
+    std::vector<E2> h_chain;
+    size_t chain_need = 0;
     std::vector<const u64*> d_inputs;
     const u64* d_ct0is = nullptr;
     size_t res_used = 0;
@@ -78,7 +87,7 @@ struct DevBackend : VerifyBackend {
     E2* d_u_all = nullptr;
     static constexpr size_t U_CAP = 8192;
 
-    DevBackend(hg_ctx* c, const hg_pk* k) : ctx(c), pk(k), st(c->stream) {
+    DevBackend(hg_ctx* c, const hg_pk* k, int mode) : ctx(c), pk(k), st(c->stream), own_chain(mode != 0) {
         memset(&cs, 0, sizeof(cs));
         d_u_all = ctx->alloc_n<E2>(U_CAP);
     }
@@ -88,6 +97,7 @@ struct DevBackend : VerifyBackend {
     }
     template <typename T> T* upload(const T* src, size_t n) {
         const size_t bytes = n * sizeof(T), need = (bytes + 63) & ~(size_t)63;
+        if (need > ctx->stage_cap) throw Error("verifier: an upload is larger than the staging buffer");
         if (ctx->stage_used + need > ctx->stage_cap) {   // recycle the pinned staging: everything staged so far must have been copied
             hip_check(hipStreamSynchronize(st), "verifier: staging recycle");
             ctx->stage_used = 0;
@@ -99,7 +109,12 @@ struct DevBackend : VerifyBackend {
         hip_check(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st), "verifier: upload descriptor");
         return d;
     }
+    void reads_chain(const dev::ClaimSet& c, int nvars) {   // points: nvars entries from each point_off; alphas: c.n from alpha_off
+        for (int a = 0; a < c.n; a++) chain_need = std::max(chain_need, c.point_off[a] + (size_t)nvars);
+        if (!c.unit_alpha) chain_need = std::max(chain_need, c.alpha_off + (size_t)c.n);
+    }
     E2* eq_of(int nvars, const dev::ClaimSet& c) {
+        reads_chain(c, nvars);
         E2* out = ctx->alloc_n<E2>((size_t)1 << nvars);
         dev::EqJob J;
         memset(&J, 0, sizeof(J));
@@ -188,6 +203,7 @@ struct DevBackend : VerifyBackend {
         const size_t N = (size_t)1 << L;
         E2* F = ctx->alloc_n<E2>(N);
         const u64* W = (n.inverse ? pk->w_inv : pk->w_fwd).at(L);
+        reads_chain(cs, L);
         ffts.push_back(dev::FftJob{F, W, n.inverse ? gl_inv(gl_from_u64(N)) : 1, L, cs});
         fft_max_L = std::max(fft_max_L, L);
         fft_max_claims = std::max(fft_max_claims, cs.n);
@@ -200,12 +216,19 @@ struct DevBackend : VerifyBackend {
         return mle_u64(d_inputs[k], point_off, nvars);
     }
     int mle_ct0is(size_t point_off, int nvars) override { return mle_u64(d_ct0is, point_off, nvars); }
+    void set_chain(const std::vector<E2>& c) override { h_chain = c; }
     void finish() override {
         const bool times = hg_times("verify");   // read at every call (host.hpp)
         const double t0 = times ? omp_get_wtime() : 0;
         if (times) { hip_check(hipStreamSynchronize(st), "sync"); fprintf(stderr, "[hg] verify_device: uploads drained %.2f ms after the walk ended; %zu eq tables, %zu gathers, %zu + %zu, %zu dots\n", (omp_get_wtime() - t0) * 1e3, eqs.size(), gts.size(), gbs.size(), ffts.size(), dots.size()); }
         auto lap = [&](const char* what) { if (times) { hip_check(hipStreamSynchronize(st), "sync"); fprintf(stderr, "[hg] verify_device: %8.2f ms  %s\n", (omp_get_wtime() - t0) * 1e3, what); } };
-        // descriptors first (one staging area; the copies are stream-ordered ahead of the launches), then one launch per kind
+        // the walk's own chain (modes 1-3), then the descriptors (one staging area; the copies are stream-ordered ahead of the
+        // launches), then one launch per kind
+        if (own_chain) {
+            if (chain_need > h_chain.size()) throw Error("verifier: a job reads past the challenges the walk squeezed");
+            chal = upload(h_chain.data(), h_chain.size());
+            if (times) fprintf(stderr, "[hg] verify_device: the walk's chain: %zu challenges staged, the jobs read %zu of them\n", h_chain.size(), chain_need);
+        } else chal = ctx->d_chal;
         const dev::EqJob* d_eqs = eqs.empty() ? nullptr : upload(eqs.data(), eqs.size());
         const dev::GatherJob* d_gts = gts.empty() ? nullptr : upload(gts.data(), gts.size());
         const dev::GatherBJob* d_gbs = gbs.empty() ? nullptr : upload(gbs.data(), gbs.size());
@@ -216,7 +239,7 @@ struct DevBackend : VerifyBackend {
             hip_check(hipMemcpyAsync(d_u_all, staged, h_u.size() * sizeof(E2), hipMemcpyDeviceToDevice, st), "verifier: phase-1 evaluations");
         }
         lap("descriptors uploaded");
-        if (d_eqs) dev::eq_jobs(st, d_eqs, (int)eqs.size(), eq_max_n, ctx->d_chal);
+        if (d_eqs) dev::eq_jobs(st, d_eqs, (int)eqs.size(), eq_max_n, chal);
         lap("eq tables");
         for (const ConstSum& c : consts) {
             const int grid = dev::vanilla_const_sum(st, c.nd->const_gate, c.nd->const_coef, c.nd->nconst, c.eqc, c.log2_G, c.log2_R, ctx->d_partials);
@@ -227,7 +250,7 @@ struct DevBackend : VerifyBackend {
         lap("phase-1 gathers");
         if (d_ffts) {
             E2* tab = ctx->alloc_n<E2>(ffts.size() * (size_t)fft_max_claims * ((size_t)1 << (fft_max_L > 4 ? fft_max_L - 4 : 0)) + 1);
-            dev::fft_jobs(st, d_ffts, (int)ffts.size(), fft_max_L, fft_max_claims, ctx->d_chal, tab);
+            dev::fft_jobs(st, d_ffts, (int)ffts.size(), fft_max_L, fft_max_claims, chal, tab);
         }
         lap("DFT-row tables");
         if (d_gbs) dev::gather_B_jobs(st, d_gbs, (int)gbs.size(), gb_max);
@@ -249,7 +272,7 @@ struct DevBackend : VerifyBackend {
 }  // namespace
 
 // public inputs and ct0is are uploaded (22 MB at n=32768 k=16), the proof is parsed on the host; "" = accepted
-std::string verify_proof_device(hg_ctx* ctx, const hg_pk* pk, const Witness& w, const uint8_t* proof, size_t len) {
+std::string verify_proof_device(hg_ctx* ctx, const hg_pk* pk, const Witness& w, const uint8_t* proof, size_t len, int mode) {
     const double tv0 = omp_get_wtime();
     struct Total { double t0; ~Total() { if (hg_times("verify")) fprintf(stderr, "[hg] verify_device: %.2f ms in all\n", (omp_get_wtime() - t0) * 1e3); } } total{tv0};
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
@@ -265,7 +288,7 @@ std::string verify_proof_device(hg_ctx* ctx, const hg_pk* pk, const Witness& w, 
     } drain{ctx->stream};
     ctx->ensure_chain(16384);
     const Params& p = pk->params;
-    DevBackend D(ctx, pk);
+    DevBackend D(ctx, pk, mode);
     const size_t SZ = p.SZ();
     auto up = [&](const u64* src, size_t n) {
         u64* d = ctx->alloc_n<u64>(n);
@@ -280,7 +303,7 @@ std::string verify_proof_device(hg_ctx* ctx, const hg_pk* pk, const Witness& w, 
     D.d_inputs.push_back(up(w.r2is.data(), w.r2is.size()));
     D.d_ct0is = up(w.ct0is.data(), w.ct0is.size());
     if (hg_times("verify")) fprintf(stderr, "[hg] verify_device: inputs enqueued at %.2f ms\n", (omp_get_wtime() - tv0) * 1e3);
-    return verify_proof_with(D, p, pk->lasso, pk->circuit, proof, len);
+    return verify_proof_with(D, p, pk->lasso, pk->circuit, proof, len, mode);
 }
 
 }  // namespace hg

@@ -148,8 +148,18 @@ int hg_verify(const hg_pk* pk, const hg_witness* w, const uint8_t* proof, size_t
 /* The same check with the table-sized work on the device [REF sk_encryption_circuit.rs:462-517; lasso/src/memory_checking/verifier.rs:
  * 130-176]: the host parses the proof and checks the round polynomials and the Lasso scalars; the eq tables, the wiring-predicate
  * sums of the Vanilla nodes, the DFT rows of the FFT nodes and the MLE evaluations of the public inputs run as kernels (one stream,
- * one synchronisation). Same return values and the same accept / reject decisions as hg_verify; Goldilocks, mode 0. */
+ * one synchronisation). Same return values and the same accept / reject decisions as hg_verify; Goldilocks, mode 0 (the protocol
+ * modes: hg_verify_device_mode). */
 int hg_verify_device(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, const uint8_t* proof, size_t len);
+/* hg_verify_device in a protocol mode (the mode bits of hg_prove_mode / hg_verify_mode below, 0 to 3), Goldilocks only. Mode 0 is
+ * hg_verify_device; modes 1 to 3 make the same accept / reject decision as hg_verify_mode in the same mode. The walk records the
+ * challenges it squeezes (with bit 1 they depend on the proof bytes) and the kernels read that record, staged into the context's
+ * arena; the fixed chain the mode-0 prover reads is left as it is. Of the gaps listed at hg_verify, bit 1 closes the first (the
+ * challenges bind every element read), bit 2 the second (gamma, tau in E); mode 3 closes both. The collation sum-check's final
+ * evaluation, the multiset relation and trailing bytes stay unchecked in every mode. Needs a device context and a device key
+ * (hg_setup(ctx, ..)). Returns 0 accept, 1 reject (reason in hg_last_error), -1 error: a null argument, a host-only key, or a mode
+ * outside 0..3. */
+int hg_verify_device_mode(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, int mode, const uint8_t* proof, size_t len);
 
 /* The same pair in a protocol mode that FIXES the reference's two known soundness gaps. mode bits:
  *   1  absorbing transcript: write_felt / read_felt also hash the element - the rule of the in-tree plonkish-trait writer of

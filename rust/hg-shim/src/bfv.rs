@@ -127,6 +127,16 @@ impl HipBfvEncrypt {
         assert_eq!(rc, 0, "proof rejected");
     }
 
+    /// `verify_json` for a Goldilocks proof made in a protocol mode (`hg_prove_mode`; bit 1 absorbing transcript, bit 2
+    /// extension-field memory checking), on the device: the same decision as `hg_verify_mode` in that mode. Panics on rejection.
+    pub fn verify_json_mode(&self, path: &str, proof: &[u8], mode: i32) {
+        let w = self.load(path, Family::Goldilocks);
+        let rc = unsafe { hg_verify_device_mode(self.ctx, self.pk, w, mode, proof.as_ptr(), proof.len()) };
+        unsafe { hg_witness_free(w) };
+        check(rc, "hg_verify_device_mode");
+        assert_eq!(rc, 0, "proof rejected");
+    }
+
     /// `prove` on tables laid out as `get_inputs` returns them (s, e, k1: 2^L; ais, r1is: k 2^L; r2is: k 2^P; ct0is: k 2^L;
     /// canonical Goldilocks u64 values) [REF sk_encryption_circuit.rs:365-415]
     #[allow(clippy::too_many_arguments)]
