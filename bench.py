@@ -5,16 +5,20 @@ configs[2]), on N MI355X GPUs of one node.
 A "step" = one GKR prove (the reference's "GKR prove" span [REF bfv-gkr/src/sk_encryption_circuit.rs:455-457],
 plus the output-claim evaluation :444-448) of a synthetic witness whose node tables are already resident in
 HBM - a DIFFERENT witness every step (`--witnesses`, default 4 seeds in rotation: the reference proves each witness once,
-test.rs:37-38), every proof of the timed region checked afterwards against the walked proof of the same seed and one of
-them against the CPU oracle. N > 1, default `--mode shard`: ONE proof is sharded over the N GPUs (strong scaling): every rank holds the
+test.rs:37-38), every proof of the timed region checked afterwards against the walked proof of the same seed and (`--full`)
+the walked proofs against the CPU oracle. N > 1, default `--mode shard`: ONE proof is sharded over the N GPUs (strong scaling): every rank holds the
 same witness, runs its share (the Lasso node split by memory, the node reductions dealt out whole) and
 ONE RCCL all-reduce of the scalar result buffer per proof, issued by the library on the prover stream, is the only exchange;
 `value` = max-over-ranks step time = ms per proof.
 `--mode dp`: every rank proves its own independent witness (weak scaling, no collective), `value` = step time / N.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel, HIP events on
-the prover stream over K timed proves run back to back with the K proves behind `value`: see "timed regions" in main()) and
-`cpu_baseline` (the CPU oracle = a port, timed on this host)."""
+Prints ONE JSON line on rank 0. A plain run does only what `value` needs: set-up, the walked proofs and the launch-graph
+capture, `--warmup` proves, the K timed proves (each checked against the walked proof of its witness), `--dump-outputs`, the line.
+`--full` adds everything else, in the same process and order as before the option existed: `roofline` (dominant kernel, HIP events
+on the prover stream over K proves run back to back with the K proves behind `value`: see "timed regions" in main()), the per-class
+and whole-prove figures, the walked-prove region, end-to-end / cold-start / verify / bn254 / sound-mode / shard-projection legs,
+`cpu_baseline` (the CPU oracle = a port, timed on this host) with the proofs checked against it, and for N > 1 the single-GPU
+proof check and the dp leg."""
 import argparse
 import json
 import os
@@ -541,9 +545,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--ring-degree", "--n", dest="n", type=int, default=32768)
     ap.add_argument("--crt-moduli", "--k", dest="k", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true")
-    ap.add_argument("--no-live-counters", action="store_true", help="do not run the rocprofv3 --pmc passes inside this run (read profiles/ instead)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides `value`: roofline and per-class figures, the walked-prove region, the end-to-end / bn254 / sound-mode / "
+                         "shard-projection legs, the CPU baseline and the oracle checks (N > 1: the single-GPU proof check and the dp leg)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --full: no end-to-end, cold-start, verify, sound-mode or shard-projection legs")
+    ap.add_argument("--no-live-counters", action="store_true", help="with --full: do not run the rocprofv3 --pmc passes inside this run (read profiles/ instead)")
     ap.add_argument("--witnesses", type=int, default=4, help="number of different synthetic witnesses proven in rotation (one per step)")
     ap.add_argument("--collective-timeout", type=float, default=300.0,
                     help="N>1: seconds the communicator set-up and the first sharded prove may take before the rank exits non-zero")
@@ -622,7 +629,7 @@ def main():
     per_rank = shard and os.environ.get("HG_BENCH_REPLICATE") != "1"
     out = hg.ProofBuffer()
     unsharded = None
-    if shard:  # the sharded proofs must equal the single-GPU proofs bit for bit: proven once from a full copy, which is then released
+    if shard and args.full:  # the sharded proofs must equal the single-GPU proofs bit for bit: proven once from a full copy, which is then released
         unsharded = []
         for w in witnesses:
             fv = hg.witness_gen(ctx, pk, w)
@@ -689,7 +696,7 @@ def main():
     with deadline(args.collective_timeout if world > 1 else 0, "first sharded prove (the first RCCL all-reduce of the data path)"):
         walked = [step(j).bytes() for j in range(NW)]   # plain launches: the reference every later proof of witness j is compared with
     assert len(set(walked)) == NW or NW == 1, "different witnesses gave identical proofs"
-    if shard:
+    if unsharded is not None:
         assert walked == unsharded, "sharded proof differs from the single-GPU proof"
     for _ in range(2):   # second walk, then the capture: from here on every step replays the launch graph of its values object
         for j in range(NW):
@@ -697,20 +704,21 @@ def main():
     for i in range(args.warmup):
         step(i)
 
-    # which kernel class dominates? untimed proves with events on every class, every launch on ONE stream (with the
-    # second stream active a class's event time also contains whatever shared the GPU with it)
-    ctx.set_option("one_stream", 1)
-    ctx.profile(2)
-    ctx.profile_reset()
-    for i in range(3):
-        step(i)
-    ctx.profile(0)
-    ctx.set_option("one_stream", 0)
-    step()
-    seen = [s for s in ctx.profile_get() if s["name"] in CLASS_SYMBOL and s["launches"]]
-    # the round's fixed class (ROOFLINE_CLASS) where the parameter set launches it, else the class with the largest isolated time
-    DOMINANT = ROOFLINE_CLASS if any(s["name"] == ROOFLINE_CLASS for s in seen) else max(seen, key=lambda s: s["total_ms"])["name"]
-    ctx.profile_select(DOMINANT)
+    if args.full:
+        # which kernel class dominates? untimed proves with events on every class, every launch on ONE stream (with the
+        # second stream active a class's event time also contains whatever shared the GPU with it)
+        ctx.set_option("one_stream", 1)
+        ctx.profile(2)
+        ctx.profile_reset()
+        for i in range(3):
+            step(i)
+        ctx.profile(0)
+        ctx.set_option("one_stream", 0)
+        step()
+        seen = [s for s in ctx.profile_get() if s["name"] in CLASS_SYMBOL and s["launches"]]
+        # the round's fixed class (ROOFLINE_CLASS) where the parameter set launches it, else the class with the largest isolated time
+        DOMINANT = ROOFLINE_CLASS if any(s["name"] == ROOFLINE_CLASS for s in seen) else max(seen, key=lambda s: s["total_ms"])["name"]
+        ctx.profile_select(DOMINANT)
     import gc
     gc.collect()
     gc.disable()  # a cyclic-GC pass over the interpreter's (PyTorch-sized) heap costs 80-100 ms: keep it out of the timed steps
@@ -730,28 +738,32 @@ def main():
     #     the protocol and launch kernel by kernel. `roofline` comes from here.
     #  B: nothing but the proves: the product's steady state (the launch graph of each step's values object replayed). `value`.
     #  C: the same with hg_set_option("graph", 0): every prove walks the protocol (`walked_ms_per_step`).
-    ctx.profile(1)
-    step()
-    ctx.profile_reset()
-    elapsed_a = timed(args.steps)
-    ctx.profile(0)
-    gpu_ms_a = out.timings()["gpu_ms"]
-    for i in range(NW):   # (back on the launch graphs)
-        assert step(i).bytes() == walked[i], "proof changed between runs"
+    # A plain run times region B alone; A and C belong to --full.
+    if args.full:
+        ctx.profile(1)
+        step()
+        ctx.profile_reset()
+        elapsed_a = timed(args.steps)
+        ctx.profile(0)
+        gpu_ms_a = out.timings()["gpu_ms"]
+        for i in range(NW):   # (back on the launch graphs)
+            assert step(i).bytes() == walked[i], "proof changed between runs"
     elapsed = timed(args.steps, keep=True)
     gpu_ms = outs[-1].timings()["gpu_ms"]
     enqueue_ms = outs[-1].timings()["enqueue_ms"]
-    ctx.set_option("graph", 0)
-    step()
-    elapsed_c = timed(args.steps)
-    ctx.set_option("graph", 1)
+    if args.full:
+        ctx.set_option("graph", 0)
+        step()
+        elapsed_c = timed(args.steps)
+        ctx.set_option("graph", 1)
     gc.enable()
     for i in range(args.steps):   # every proof of region B against the walked proof of the same witness
         assert outs[i].bytes() == walked[i % NW], f"timed step {i}: the replayed proof differs from the walked proof of witness {i % NW}"
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, outs[args.steps - 1].bytes())
-    for i in range(NW):
-        assert step(i).bytes() == walked[i]
+    if args.full:
+        for i in range(NW):
+            assert step(i).bytes() == walked[i]
     resident_all = None
     peak_all = None
     witness_ms_all = None
@@ -766,6 +778,7 @@ def main():
         lst = [None] * world
         dist.all_gather_object(lst, round(vals[0].timings["witness_ms"] + vals[0].timings["upload_ms"], 3))
         witness_ms_all = lst
+    if shard and args.full:
         # The same N GPUs used the other way round, in the same run: one INDEPENDENT proof per GPU (no data-path collective, weak
         # scaling) - the aggregate proofs/s the node delivers when latency of one proof does not matter. A different witness per rank
         # (own full table set), the launch graph replayed, every proof compared with the walked proof of its witness.
@@ -791,52 +804,53 @@ def main():
                   "note": "timed like `value` (barrier, K steps, barrier, max over ranks) right after the sharded regions; `value` stays the sharded proof's ms"}
         dp_vals.free()
     elapsed = max_over_ranks(elapsed, world, dist, torch, red_dev)
-    elapsed_a = max_over_ranks(elapsed_a, world, dist, torch, red_dev)
-    elapsed_c = max_over_ranks(elapsed_c, world, dist, torch, red_dev)
     ms_per_step = elapsed / args.steps * 1e3
-    ms_per_step_a = elapsed_a / args.steps * 1e3
-    ms_per_step_c = elapsed_c / args.steps * 1e3
-    dom = [s for s in ctx.profile_get() if s["name"] == DOMINANT][0]
     first = walked[0]
+    if args.full:
+        elapsed_a = max_over_ranks(elapsed_a, world, dist, torch, red_dev)
+        elapsed_c = max_over_ranks(elapsed_c, world, dist, torch, red_dev)
+        ms_per_step_a = elapsed_a / args.steps * 1e3
+        ms_per_step_c = elapsed_c / args.steps * 1e3
+        dom = [s for s in ctx.profile_get() if s["name"] == DOMINANT][0]
 
-    # one extra, untimed pass with events on every kernel class (one stream: isolated class times): the per-class breakdown
-    ctx.set_option("one_stream", 1)
-    step()
-    ctx.profile(2)
-    ctx.profile_reset()
-    step()
-    ctx.profile(0)
-    ctx.set_option("one_stream", 0)
-    # algo_GB: what the class streams by THIS implementation's algorithm (each live table read once, each folded table written once);
-    # model_GB: the same launches in the traffic model of the REFERENCE's algorithm - larger where an algebraic shortcut
-    # avoids tables (grand product #1's top layer runs on the read rows only, the collation sum-check on two tables)
-    # hbm_GB: what the class moves to or from HBM by design (hg_kernel_stat::hbm_bytes: no credit for tables that are recomputed and
-    # never stored, for the intermediate folds of a two-round launch or for rounds inside LDS) - the numerator of every HBM fraction
-    # below; algo_GB: the per-round accounting of SURVEY 8(d) applied to this implementation's tables (a fused launch credited with
-    # both rounds; comparable across rounds of this work, NOT a traffic figure); model_GB: the same launches in the reference's model
-    classes = {s["name"]: {"launches": s["launches"], "ms": round(s["total_ms"], 4), "hbm_GB": round(s["hbm_bytes"] / 1e9, 4),
-                           "algo_GB": round(s["algo_bytes"] / 1e9, 4), "model_GB": round(s["model_bytes"] / 1e9, 4)}
-               for s in ctx.profile_get() if s["launches"]}
+        # one extra, untimed pass with events on every kernel class (one stream: isolated class times): the per-class breakdown
+        ctx.set_option("one_stream", 1)
+        step()
+        ctx.profile(2)
+        ctx.profile_reset()
+        step()
+        ctx.profile(0)
+        ctx.set_option("one_stream", 0)
+        # algo_GB: what the class streams by THIS implementation's algorithm (each live table read once, each folded table written once);
+        # model_GB: the same launches in the traffic model of the REFERENCE's algorithm - larger where an algebraic shortcut
+        # avoids tables (grand product #1's top layer runs on the read rows only, the collation sum-check on two tables)
+        # hbm_GB: what the class moves to or from HBM by design (hg_kernel_stat::hbm_bytes: no credit for tables that are recomputed and
+        # never stored, for the intermediate folds of a two-round launch or for rounds inside LDS) - the numerator of every HBM fraction
+        # below; algo_GB: the per-round accounting of SURVEY 8(d) applied to this implementation's tables (a fused launch credited with
+        # both rounds; comparable across rounds of this work, NOT a traffic figure); model_GB: the same launches in the reference's model
+        classes = {s["name"]: {"launches": s["launches"], "ms": round(s["total_ms"], 4), "hbm_GB": round(s["hbm_bytes"] / 1e9, 4),
+                               "algo_GB": round(s["algo_bytes"] / 1e9, 4), "model_GB": round(s["model_bytes"] / 1e9, 4)}
+                   for s in ctx.profile_get() if s["launches"]}
 
-    # the dominant class once more with every launch on one stream (isolated kernel duration), untimed
-    ctx.set_option("one_stream", 1)
-    step()
-    ctx.profile(1)
-    ctx.profile_reset()
-    for i in range(3):
-        step(i)
-    ctx.profile(0)
-    iso = [s for s in ctx.profile_get() if s["name"] == DOMINANT][0]
-    iso_ms = iso["total_ms"] / max(iso["launches"], 1)
-    iso_achieved = iso["hbm_bytes"] / max(iso["launches"], 1) / (iso_ms * 1e-3) / 1e9 if iso_ms > 0 else 0.0
-    iso_model = iso["model_bytes"] / max(iso["launches"], 1) / (iso_ms * 1e-3) / 1e9 if iso_ms > 0 else 0.0
-    iso_gpu_ms = out.timings()["gpu_ms"]
-    ctx.set_option("one_stream", 0)
+        # the dominant class once more with every launch on one stream (isolated kernel duration), untimed
+        ctx.set_option("one_stream", 1)
+        step()
+        ctx.profile(1)
+        ctx.profile_reset()
+        for i in range(3):
+            step(i)
+        ctx.profile(0)
+        iso = [s for s in ctx.profile_get() if s["name"] == DOMINANT][0]
+        iso_ms = iso["total_ms"] / max(iso["launches"], 1)
+        iso_achieved = iso["hbm_bytes"] / max(iso["launches"], 1) / (iso_ms * 1e-3) / 1e9 if iso_ms > 0 else 0.0
+        iso_model = iso["model_bytes"] / max(iso["launches"], 1) / (iso_ms * 1e-3) / 1e9 if iso_ms > 0 else 0.0
+        iso_gpu_ms = out.timings()["gpu_ms"]
+        ctx.set_option("one_stream", 0)
 
     end_to_end = None
     cold_start = None
     verify_info = None
-    if world == 1 and rank == 0 and not args.no_end_to_end:
+    if args.full and world == 1 and rank == 0 and not args.no_end_to_end:
         end_to_end = measure_end_to_end(hg, ctx, bfv, pk, witnesses, walked, args)
         cold_start = measure_cold_start(hg, local_rank, args, witnesses[0], walked[0])
         # BfvEncrypt::verify (host side, like the reference's; OpenMP over the table-sized loops) on the proof of witness 0
@@ -858,45 +872,46 @@ def main():
                                "inputs uploaded per call); the reference reports 107.9 ms on an M1 Pro (README.md:44)"}
 
     if rank == 0:
-        per_launch_bytes = dom["hbm_bytes"] / max(dom["launches"], 1)
-        avg_ms = dom["total_ms"] / max(dom["launches"], 1)
-        achieved = per_launch_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        live_dir, live_note = (None, "not requested (--no-live-counters)") if args.no_live_counters or world > 1 else live_counter_passes(args.n, args.k)
-        pmc = Counters(args.n, args.k, live_dir=live_dir, live_note=live_note)
-        im = IssueModel()
-        sym = CLASS_SYMBOL.get(DOMINANT, "")
-        traffic, _ = pmc.hbm_bytes(sym)
-        valu_pl = pmc.valu(sym)
-        valu_ach = valu_pl / (avg_ms * 1e-3) / 1e9 if valu_pl and avg_ms > 0 else None
-        valu_frac = valu_ach / VALU_PEAK_G if valu_ach else None
-        hbm_frac = achieved / HBM_PEAK_GBS
-        # the issue roof of THIS kernel: its VALU instructions priced by class (IssueModel) over the same launch duration
-        issue_s = im.seconds(valu_pl, sym)
-        issue_frac = issue_s / (avg_ms * 1e-3) if issue_s is not None and avg_ms > 0 else None
-        issue_frac_iso = issue_s / (iso_ms * 1e-3) if issue_s is not None and iso_ms > 0 else None
-        vbest = issue_frac if issue_frac is not None else valu_frac
-        valu_bound = vbest is not None and vbest > hbm_frac
+        if args.full:
+            per_launch_bytes = dom["hbm_bytes"] / max(dom["launches"], 1)
+            avg_ms = dom["total_ms"] / max(dom["launches"], 1)
+            achieved = per_launch_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+            live_dir, live_note = (None, "not requested (--no-live-counters)") if args.no_live_counters or world > 1 else live_counter_passes(args.n, args.k)
+            pmc = Counters(args.n, args.k, live_dir=live_dir, live_note=live_note)
+            im = IssueModel()
+            sym = CLASS_SYMBOL.get(DOMINANT, "")
+            traffic, _ = pmc.hbm_bytes(sym)
+            valu_pl = pmc.valu(sym)
+            valu_ach = valu_pl / (avg_ms * 1e-3) / 1e9 if valu_pl and avg_ms > 0 else None
+            valu_frac = valu_ach / VALU_PEAK_G if valu_ach else None
+            hbm_frac = achieved / HBM_PEAK_GBS
+            # the issue roof of THIS kernel: its VALU instructions priced by class (IssueModel) over the same launch duration
+            issue_s = im.seconds(valu_pl, sym)
+            issue_frac = issue_s / (avg_ms * 1e-3) if issue_s is not None and avg_ms > 0 else None
+            issue_frac_iso = issue_s / (iso_ms * 1e-3) if issue_s is not None and iso_ms > 0 else None
+            vbest = issue_frac if issue_frac is not None else valu_frac
+            valu_bound = vbest is not None and vbest > hbm_frac
 
-        def class_row(name, c):
-            """one class against both roofs, isolated duration (one stream): frac = the larger of the two"""
-            ms = c["ms"]
-            symc = CLASS_SYMBOL.get(name, "")
-            pb, _ = pmc.hbm_bytes(symc)
-            vi = pmc.valu(symc)
-            ln = max(c["launches"], 1)
-            hf = c["hbm_GB"] / (ms * 1e-3) / HBM_PEAK_GBS if ms > 0 else None
-            pf = pb * ln / 1e9 / (ms * 1e-3) / HBM_PEAK_GBS if pb and ms > 0 else None
-            vf = vi * ln / 1e9 / (ms * 1e-3) / VALU_PEAK_G if vi and ms > 0 else None
-            it = im.seconds(vi * ln if vi else None, symc)
-            isf = it / (ms * 1e-3) if it is not None and ms > 0 else None
-            vbest = isf if isf is not None else vf
-            fr = max(x for x in (hf, vbest) if x is not None) if (hf is not None or vbest is not None) else None
-            return {"kernel": name, "symbol": symc, "launches_per_step": c["launches"], "isolated_avg_launch_us": round(ms / ln * 1e3, 2),
-                    "hbm_frac": round(hf, 4) if hf is not None else None, "pmc_hbm_frac": round(pf, 4) if pf is not None else None,
-                    "issue_frac": round(isf, 4) if isf is not None else None, "class_a_share": round(im.share_a(symc), 3) if im.share_a(symc) is not None else None,
-                    "valu_frac_nominal_614G": round(vf, 4) if vf is not None else None, "frac": round(fr, 4) if fr is not None else None,
-                    "bound": "issue" if (vbest is not None and hf is not None and vbest > hf) else "hbm"}
-        pmc_bytes_prove, valu_prove = pmc.prove_totals()
+            def class_row(name, c):
+                """one class against both roofs, isolated duration (one stream): frac = the larger of the two"""
+                ms = c["ms"]
+                symc = CLASS_SYMBOL.get(name, "")
+                pb, _ = pmc.hbm_bytes(symc)
+                vi = pmc.valu(symc)
+                ln = max(c["launches"], 1)
+                hf = c["hbm_GB"] / (ms * 1e-3) / HBM_PEAK_GBS if ms > 0 else None
+                pf = pb * ln / 1e9 / (ms * 1e-3) / HBM_PEAK_GBS if pb and ms > 0 else None
+                vf = vi * ln / 1e9 / (ms * 1e-3) / VALU_PEAK_G if vi and ms > 0 else None
+                it = im.seconds(vi * ln if vi else None, symc)
+                isf = it / (ms * 1e-3) if it is not None and ms > 0 else None
+                vbest = isf if isf is not None else vf
+                fr = max(x for x in (hf, vbest) if x is not None) if (hf is not None or vbest is not None) else None
+                return {"kernel": name, "symbol": symc, "launches_per_step": c["launches"], "isolated_avg_launch_us": round(ms / ln * 1e3, 2),
+                        "hbm_frac": round(hf, 4) if hf is not None else None, "pmc_hbm_frac": round(pf, 4) if pf is not None else None,
+                        "issue_frac": round(isf, 4) if isf is not None else None, "class_a_share": round(im.share_a(symc), 3) if im.share_a(symc) is not None else None,
+                        "valu_frac_nominal_614G": round(vf, 4) if vf is not None else None, "frac": round(fr, 4) if fr is not None else None,
+                        "bound": "issue" if (vbest is not None and hf is not None and vbest > hf) else "hbm"}
+            pmc_bytes_prove, valu_prove = pmc.prove_totals()
         line = {
             "metric": f"GKR prove ms, n={args.n} k={args.k} Goldilocks; achieved HBM GB/s vs roofline",
             "value": round(ms_per_step if (shard or world == 1) else ms_per_step / world, 4),
@@ -923,11 +938,11 @@ def main():
                        **({"exchange_note": exchange_note} if exchange_note else {}),
                        "proof_bytes": len(first), "gpu_ms_events": round(gpu_ms, 4),
                        "host_enqueue_ms": round(enqueue_ms, 4),
-                       "walked_ms_per_step": round(ms_per_step_c, 4),
+                       **({"walked_ms_per_step": round(ms_per_step_c, 4)} if args.full else {}),
                        "timed_regions": {"value": f"{args.steps} proves, a different witness each, the launch graph of each witness's tables replayed, no profiling events",
-                                         "walked_ms_per_step": f"{args.steps} proves right after, hg_set_option(graph, 0): the protocol walked and launched kernel by kernel",
-                                         "roofline": f"{args.steps} proves immediately before, plain launches with HIP events around the dominant class: "
-                                                     f"{ms_per_step_a:.4f} ms per prove, {gpu_ms_a:.4f} ms of GPU time"},
+                                         **({"walked_ms_per_step": f"{args.steps} proves right after, hg_set_option(graph, 0): the protocol walked and launched kernel by kernel",
+                                             "roofline": f"{args.steps} proves immediately before, plain launches with HIP events around the dominant class: "
+                                                         f"{ms_per_step_a:.4f} ms per prove, {gpu_ms_a:.4f} ms of GPU time"} if args.full else {})},
                        **({"rccl_ranks_seen": rccl_ranks_seen} if rccl_ranks_seen is not None else {}),
                        **({"resident_node_tables": {"rank0_MB": round(resident["resident_bytes"] / 1e6, 1), "per_rank_MB": resident_all,
                                                     "per_rank_peak_MB": peak_all, "per_rank_witness_ms": witness_ms_all,
@@ -939,66 +954,69 @@ def main():
                        **({"cold_start": cold_start} if cold_start else {}),
                        **({"verify": verify_info} if verify_info else {}),
                        "witness_gen_ms_device_first_call": round(vals[0].timings["witness_ms"], 2), "upload_ms_first_call": round(vals[0].timings["upload_ms"], 2)},
-            # `achieved` / `avg_launch_us`: HIP events around the dominant kernel class over the K proves of timed region A, where its launches
-            # share the GPU with the second stream (Vanilla / FFT reductions, counter sorts, openings); `isolated`: the same
-            # launches timed in an extra untimed prove with every launch on one stream.
-            # The class with the largest isolated GPU time, against BOTH roofs; `frac` is the larger fraction and `bound` names its roof.
-            # HBM: bytes the class moves to or from HBM by design (`hbm_bytes_per_launch`) over the average launch duration measured with
-            # HIP events inside timed region A (its launches share the GPU with the other streams there); `traffic` = the same launches'
-            # HBM bytes by the PMC counters. VALU: SQ_INSTS_VALU per launch over the same duration against 614 G wave-instr/s.
-            # `bound` / `frac`: the larger of the HBM fraction and the ISSUE fraction (`issue_frac`: the kernel's VALU instructions priced by
-            # instruction class - IssueModel - over the launch duration; `peak` then is the rate at which THIS kernel's mix issues).
-            "roofline": {"bound": "issue" if valu_bound else "hbm", "kernel": DOMINANT, "symbol": sym,
-                         "achieved": round(valu_ach if valu_bound else achieved, 2),
-                         "peak": (round(valu_ach / issue_frac, 1) if issue_frac else round(VALU_PEAK_G, 1)) if valu_bound else HBM_PEAK_GBS,
-                         "unit": "G wave-instr/s" if valu_bound else "GB/s",
-                         "frac": round(vbest if valu_bound else hbm_frac, 4), "traffic": round(traffic) if traffic else None,
-                         "issue_frac": round(issue_frac, 4) if issue_frac is not None else None,
-                         "issue": {"frac": round(issue_frac, 4) if issue_frac is not None else None,
-                                   "frac_isolated": round(issue_frac_iso, 4) if issue_frac_iso is not None else None,
-                                   "class_a_share": round(im.share_a(sym), 3) if im.share_a(sym) is not None else None,
-                                   "issue_us_per_launch": round(issue_s * 1e6, 2) if issue_s is not None else None,
-                                   "rates": im.describe(),
-                                   "note": "sum over the kernel's VALU instructions of 1 / (issue rate of their class on this chip); class mix from the assembly, count from SQ_INSTS_VALU"},
-                         "hbm": {"achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(hbm_frac, 4),
-                                 "hbm_bytes_per_launch": round(per_launch_bytes),
-                                 "pmc_frac": round(traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic and avg_ms > 0 else None},
-                         "valu": {"achieved": round(valu_ach, 1) if valu_ach else None, "peak": round(VALU_PEAK_G, 1), "unit": "G wave-instr/s",
-                                  "frac": round(valu_frac, 4) if valu_frac else None,
-                                  "frac_of_measured_issue_rate": round(valu_ach / VALU_MEASURED_G, 4) if valu_ach else None,
-                                  "wave_insts_per_launch": round(valu_pl) if valu_pl else None},
-                         "counters": {"measured": pmc.measured, "files": pmc.files, "code_hash": code_hash(), "command": PMC_CMD, **({"note": pmc.note} if pmc.note else {})},
-                         "launches_per_step": dom["launches"] // max(args.steps, 1),
-                         "avg_launch_us": round(avg_ms * 1e3, 3),
-                         "isolated": {"avg_launch_us": round(iso_ms * 1e3, 3), "hbm_achieved": round(iso_achieved, 2),
-                                      "hbm_frac": round(iso_achieved / HBM_PEAK_GBS, 4),
-                                      "valu_frac": round(valu_pl / (iso_ms * 1e-3) / 1e9 / VALU_PEAK_G, 4) if valu_pl and iso_ms > 0 else None,
-                                      "gpu_ms_one_stream": round(iso_gpu_ms, 4),
-                                      "note": "hg_set_option(one_stream): no cross-stream overlap"},
-                         # the same launches priced in the reference algorithm's traffic model (its 2 alpha table pairs per
-                         # layer, hash rows stored): the speed in units of the reference's work - NOT a bandwidth and not bounded by 1
-                         "reference_model": {"bytes_per_launch": round(dom["model_bytes"] / max(dom["launches"], 1)),
-                                             "x_hbm_peak_isolated": round(iso_model / HBM_PEAK_GBS, 4)}},
-            "kernel_classes": classes,
-            # the four largest classes of the per-class pass (one stream: isolated durations) against both roofs
-            "roofline_by_class": [class_row(name, c) for name, c in sorted(classes.items(), key=lambda kv: -kv[1]["ms"])[:5] if name != "aux"][:4],
-            # whole prove: GPU time of one prove (HIP events around the whole enqueue) against the bytes it moves by design, the bytes
-            # the counters saw, and the VALU instructions it issues; reference_model_GB / x_hbm_peak: SURVEY 8(d)'s model of the
-            # REFERENCE's algorithm over the same time (comparable across rounds; above the HBM peak because most of that traffic is no
-            # longer generated - it stopped being a roofline when the shortcuts went in)
-            "whole_prove": {"gpu_ms": round(gpu_ms, 4),
-                            "hbm_GB": round(sum(c["hbm_GB"] for c in classes.values()), 3),
-                            "hbm_frac": round(sum(c["hbm_GB"] for c in classes.values()) / (gpu_ms * 1e-3) / HBM_PEAK_GBS, 4) if gpu_ms > 0 else None,
-                            "pmc_GB": round(pmc_bytes_prove / 1e9, 3) if pmc_bytes_prove else None,
-                            "pmc_hbm_frac": round(pmc_bytes_prove / 1e9 / (gpu_ms * 1e-3) / HBM_PEAK_GBS, 4) if pmc_bytes_prove and gpu_ms > 0 else None,
-                            "valu_wave_insts": round(valu_prove) if valu_prove else None,
-                            "valu_frac": round(valu_prove / 1e9 / (gpu_ms * 1e-3) / VALU_PEAK_G, 4) if valu_prove and gpu_ms > 0 else None,
-                            "valu_frac_of_measured_issue_rate": round(valu_prove / 1e9 / (gpu_ms * 1e-3) / VALU_MEASURED_G, 4) if valu_prove and gpu_ms > 0 else None,
-                            "issue_frac": round(pmc.issue_seconds_of_a_prove(im) / (gpu_ms * 1e-3), 4) if pmc.issue_seconds_of_a_prove(im) and gpu_ms > 0 else None,
-                            "reference_model_GB": round(sum(c["model_GB"] for c in classes.values()), 3),
-                            "reference_model_x_hbm_peak": round(sum(c["model_GB"] for c in classes.values()) / (gpu_ms * 1e-3) / HBM_PEAK_GBS, 4) if gpu_ms > 0 else None},
         }
-        if world == 1:
+        if args.full:
+            line.update({
+                # `achieved` / `avg_launch_us`: HIP events around the dominant kernel class over the K proves of timed region A, where its launches
+                # share the GPU with the second stream (Vanilla / FFT reductions, counter sorts, openings); `isolated`: the same
+                # launches timed in an extra untimed prove with every launch on one stream.
+                # The class with the largest isolated GPU time, against BOTH roofs; `frac` is the larger fraction and `bound` names its roof.
+                # HBM: bytes the class moves to or from HBM by design (`hbm_bytes_per_launch`) over the average launch duration measured with
+                # HIP events inside timed region A (its launches share the GPU with the other streams there); `traffic` = the same launches'
+                # HBM bytes by the PMC counters. VALU: SQ_INSTS_VALU per launch over the same duration against 614 G wave-instr/s.
+                # `bound` / `frac`: the larger of the HBM fraction and the ISSUE fraction (`issue_frac`: the kernel's VALU instructions priced by
+                # instruction class - IssueModel - over the launch duration; `peak` then is the rate at which THIS kernel's mix issues).
+                "roofline": {"bound": "issue" if valu_bound else "hbm", "kernel": DOMINANT, "symbol": sym,
+                             "achieved": round(valu_ach if valu_bound else achieved, 2),
+                             "peak": (round(valu_ach / issue_frac, 1) if issue_frac else round(VALU_PEAK_G, 1)) if valu_bound else HBM_PEAK_GBS,
+                             "unit": "G wave-instr/s" if valu_bound else "GB/s",
+                             "frac": round(vbest if valu_bound else hbm_frac, 4), "traffic": round(traffic) if traffic else None,
+                             "issue_frac": round(issue_frac, 4) if issue_frac is not None else None,
+                             "issue": {"frac": round(issue_frac, 4) if issue_frac is not None else None,
+                                       "frac_isolated": round(issue_frac_iso, 4) if issue_frac_iso is not None else None,
+                                       "class_a_share": round(im.share_a(sym), 3) if im.share_a(sym) is not None else None,
+                                       "issue_us_per_launch": round(issue_s * 1e6, 2) if issue_s is not None else None,
+                                       "rates": im.describe(),
+                                       "note": "sum over the kernel's VALU instructions of 1 / (issue rate of their class on this chip); class mix from the assembly, count from SQ_INSTS_VALU"},
+                             "hbm": {"achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(hbm_frac, 4),
+                                     "hbm_bytes_per_launch": round(per_launch_bytes),
+                                     "pmc_frac": round(traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic and avg_ms > 0 else None},
+                             "valu": {"achieved": round(valu_ach, 1) if valu_ach else None, "peak": round(VALU_PEAK_G, 1), "unit": "G wave-instr/s",
+                                      "frac": round(valu_frac, 4) if valu_frac else None,
+                                      "frac_of_measured_issue_rate": round(valu_ach / VALU_MEASURED_G, 4) if valu_ach else None,
+                                      "wave_insts_per_launch": round(valu_pl) if valu_pl else None},
+                             "counters": {"measured": pmc.measured, "files": pmc.files, "code_hash": code_hash(), "command": PMC_CMD, **({"note": pmc.note} if pmc.note else {})},
+                             "launches_per_step": dom["launches"] // max(args.steps, 1),
+                             "avg_launch_us": round(avg_ms * 1e3, 3),
+                             "isolated": {"avg_launch_us": round(iso_ms * 1e3, 3), "hbm_achieved": round(iso_achieved, 2),
+                                          "hbm_frac": round(iso_achieved / HBM_PEAK_GBS, 4),
+                                          "valu_frac": round(valu_pl / (iso_ms * 1e-3) / 1e9 / VALU_PEAK_G, 4) if valu_pl and iso_ms > 0 else None,
+                                          "gpu_ms_one_stream": round(iso_gpu_ms, 4),
+                                          "note": "hg_set_option(one_stream): no cross-stream overlap"},
+                             # the same launches priced in the reference algorithm's traffic model (its 2 alpha table pairs per
+                             # layer, hash rows stored): the speed in units of the reference's work - NOT a bandwidth and not bounded by 1
+                             "reference_model": {"bytes_per_launch": round(dom["model_bytes"] / max(dom["launches"], 1)),
+                                                 "x_hbm_peak_isolated": round(iso_model / HBM_PEAK_GBS, 4)}},
+                "kernel_classes": classes,
+                # the four largest classes of the per-class pass (one stream: isolated durations) against both roofs
+                "roofline_by_class": [class_row(name, c) for name, c in sorted(classes.items(), key=lambda kv: -kv[1]["ms"])[:5] if name != "aux"][:4],
+                # whole prove: GPU time of one prove (HIP events around the whole enqueue) against the bytes it moves by design, the bytes
+                # the counters saw, and the VALU instructions it issues; reference_model_GB / x_hbm_peak: SURVEY 8(d)'s model of the
+                # REFERENCE's algorithm over the same time (comparable across rounds; above the HBM peak because most of that traffic is no
+                # longer generated - it stopped being a roofline when the shortcuts went in)
+                "whole_prove": {"gpu_ms": round(gpu_ms, 4),
+                                "hbm_GB": round(sum(c["hbm_GB"] for c in classes.values()), 3),
+                                "hbm_frac": round(sum(c["hbm_GB"] for c in classes.values()) / (gpu_ms * 1e-3) / HBM_PEAK_GBS, 4) if gpu_ms > 0 else None,
+                                "pmc_GB": round(pmc_bytes_prove / 1e9, 3) if pmc_bytes_prove else None,
+                                "pmc_hbm_frac": round(pmc_bytes_prove / 1e9 / (gpu_ms * 1e-3) / HBM_PEAK_GBS, 4) if pmc_bytes_prove and gpu_ms > 0 else None,
+                                "valu_wave_insts": round(valu_prove) if valu_prove else None,
+                                "valu_frac": round(valu_prove / 1e9 / (gpu_ms * 1e-3) / VALU_PEAK_G, 4) if valu_prove and gpu_ms > 0 else None,
+                                "valu_frac_of_measured_issue_rate": round(valu_prove / 1e9 / (gpu_ms * 1e-3) / VALU_MEASURED_G, 4) if valu_prove and gpu_ms > 0 else None,
+                                "issue_frac": round(pmc.issue_seconds_of_a_prove(im) / (gpu_ms * 1e-3), 4) if pmc.issue_seconds_of_a_prove(im) and gpu_ms > 0 else None,
+                                "reference_model_GB": round(sum(c["model_GB"] for c in classes.values()), 3),
+                                "reference_model_x_hbm_peak": round(sum(c["model_GB"] for c in classes.values()) / (gpu_ms * 1e-3) / HBM_PEAK_GBS, 4) if gpu_ms > 0 else None},
+            })
+        if args.full and world == 1:
             # the same proof over bn256::Fr (BASELINE config 5's field) on the same witness: reported next to the headline
             # number, never part of `value`; 5 runs after one warm-up, median of 5
             try:
@@ -1046,7 +1064,7 @@ def main():
                     pass
             except Exception as ex:
                 line["bn254"] = {"error": str(ex)}
-        if world == 1 and not args.no_end_to_end:
+        if args.full and world == 1 and not args.no_end_to_end:
             # the protocol with both soundness fixes upstream is likely to make (absorbing transcript, extension-field
             # memory checking): every round's challenge depends on the round's message, so the rounds run one after the other
             try:
@@ -1132,7 +1150,7 @@ def main():
                     line["sound_mode"]["sharded_two_ranks_one_gpu"] = {"error": str(ex)}
             except Exception as ex:
                 line["sound_mode"] = {"error": str(ex)}
-        if world == 1 and not args.no_end_to_end:
+        if args.full and world == 1 and not args.no_end_to_end:
             # BASELINE config 4 as far as one GPU can show it: the shares of 2 / 4 / 8 ranks run one after the other on this GPU, each
             # from its own resident tables (hg_witness_gen_shard), each through its own launch graph; the partial result buffers are
             # summed as the all-reduce would (hg_shard_combine_host) and replayed: the proof must be the single-GPU proof. Reported:
@@ -1172,7 +1190,7 @@ def main():
                                                                      "from the rank's launch graph, median of 3; not a multi-GPU measurement")
             except Exception as ex:
                 line["config"]["shard_projection"] = {"error": str(ex)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             oracle_proofs = {}
             try:
                 line["cpu_baseline"] = cpu_baseline(args.n, args.k, args.seed, proofs_out=oracle_proofs)

@@ -5,6 +5,7 @@
 tag=${1:-r06_a}
 set -x
 cd $GRAFT_REPO_ROOT
+R=$PWD
 O=$GRAFT_REPO_ROOT/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 if [ "$2" = "pmc" ]; then
@@ -24,10 +25,10 @@ cd $GRAFT_REPO_ROOT
 ( cd scripts/ub && ./ratebench ) > $GRAFT_REPO_ROOT/profiles/${tag%_*}_ratebench.txt 2>&1
 python3 scripts/isa_census.py hyper-greco_amd/csrc/kernels.hip hyper-greco_amd/csrc/bn254.hip --json $GRAFT_REPO_ROOT/profiles/${tag%_*}_isa_mix.json > $O/${tag}_isa_census.txt 2>&1
 cp $GRAFT_REPO_ROOT/profiles/${tag%_*}_ratebench.txt $O/${tag}_ratebench.txt; cp $GRAFT_REPO_ROOT/profiles/${tag%_*}_isa_mix.json $O/${tag}_isa_mix.json
-python bench.py > $O/bench_$tag.json 2> $O/bench_$tag.err
+python bench.py --full > $O/bench_$tag.json 2> $O/bench_$tag.err
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $O/prof_$tag -o runc --output-format csv -- python3 $GRAFT_REPO_ROOT/scripts/prove_once.py 32768 16 6 > $O/prove_once_$tag.txt 2>/dev/null
-rocprofv3 --kernel-trace --stats -d $O/profb_$tag -o runc --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_${tag}_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats -d $O/profb_$tag -o runc --output-format csv -- python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_${tag}_under_rocprof.json 2>/dev/null
 HG_ONE_STREAM=1 rocprofv3 --kernel-trace --stats -d $O/profi_$tag -o runc --output-format csv -- python3 $GRAFT_REPO_ROOT/scripts/prove_once.py 32768 16 6 > /dev/null 2>&1
 cd $GRAFT_REPO_ROOT
 python3 scripts/summarize_trace.py $(ls $O/profb_$tag/*kernel_trace.csv | head -1) 60 > $O/${tag}_bench_kernel_trace_summary.txt

@@ -1045,20 +1045,45 @@ def test_exchange_limb_kernels_for_more_than_one_rank(ctx, world):
 
 def test_bench_sharded_two_processes_on_one_gpu():
     """The N>1 bench path end to end with two real processes (gloo all-reduce through host tensors, both ranks on
-    device 0): rendezvous, per-rank job ownership, the all-reduce, replay; bench.py itself asserts that the sharded
+    device 0): rendezvous, per-rank job ownership, the all-reduce, replay; bench.py --full itself asserts that the sharded
     proof equals the single-GPU proof."""
     import json, subprocess, sys
     from hglib import ROOT
     env = dict(os.environ, HG_BENCH_BACKEND="gloo", HG_BENCH_SAME_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--ring-degree", "4096", "--crt-moduli", "2",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     outp = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert outp.returncode == 0, outp.stderr[-3000:]
     lines = [l for l in outp.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["value"] == d["ms_per_step"]
+
+
+def test_bench_plain_run_and_full(tmp_path):
+    """bench.py --gpus 1: a plain run prints the headline fields and none of what --full measures; --full adds the roofline objects,
+    the walked-prove region and the bn254 leg. The timed steps are the same in both: the last timed proof is dumped word for word alike."""
+    import json, subprocess, sys
+    from hglib import ROOT
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--ring-degree", "4096", "--crt-moduli", "2"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-end-to-end", "--no-live-counters"])):
+        outp = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert outp.returncode == 0, outp.stderr[-3000:]
+        got = [l for l in outp.stdout.splitlines() if l.startswith("{")]
+        assert len(got) == 1
+        lines[name] = json.loads(got[0])
+    plain, full = lines["plain"], lines["full"]
+    for d in (plain, full):
+        assert d["unit"] == "ms" and d["higher_is_better"] is False and d["dtype"] == "u64" and d["steps"] == 3 and d["warmup"] == 1
+        assert d["value"] == d["ms_per_step"] > 0 and d["metric"].startswith("GKR prove ms, n=4096 k=2 Goldilocks")
+        assert d["config"]["proof_checks"]["timed_steps_equal_to_the_walked_proof_of_their_witness"] == 3
+    assert not {"roofline", "kernel_classes", "roofline_by_class", "whole_prove", "bn254", "cpu_baseline"} & set(plain)
+    assert "walked_ms_per_step" not in plain["config"] and list(plain["config"]["timed_regions"]) == ["value"]
+    assert {"roofline", "kernel_classes", "roofline_by_class", "whole_prove", "bn254"} <= set(full) and "cpu_baseline" not in full
+    assert full["config"]["walked_ms_per_step"] > 0 and set(full["config"]["timed_regions"]) == {"value", "walked_ms_per_step", "roofline"}
+    assert np.array_equal(np.load(tmp_path / "plain" / "proof.npy"), np.load(tmp_path / "full" / "proof.npy"))
 
 
 @pytest.mark.parametrize("n,k,bits", [(1024, 1, 27), (8192, 4, 55)])
