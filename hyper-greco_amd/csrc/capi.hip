@@ -135,6 +135,7 @@ int hg_set_option(hg_ctx* ctx, const char* name, int64_t value) {
     const std::string n(name);
     if (n == "one_stream") { if (ctx->one_stream != (value != 0)) ctx->walk_counts.clear(); ctx->one_stream = value != 0; }
     else if (n == "graph") { ctx->use_graph = value != 0; if (!ctx->use_graph) prove_cache_drop(ctx); }
+    else if (n == "verify_batch_group") { if (value < 0) throw Error("hg_set_option: verify_batch_group must be >= 0"); ctx->verify_batch_group = value; }
     else throw Error("hg_set_option: unknown option " + n);
     return 0;
     HG_CATCH(-1)
@@ -857,6 +858,43 @@ int hg_verify_device_mode(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, int
     if (why.empty()) return 0;
     g_last_error = why;
     return 1;
+    HG_CATCH(-1)
+}
+
+int hg_verify_device_batch(hg_ctx* ctx, const hg_pk* pk, const hg_witness* const* ws, const uint8_t* const* proofs, const size_t* lens, size_t n,
+                           int mode, int* results, char* reasons, size_t reason_cap) {
+    HG_TRY
+    if (!ctx || !pk || (n && (!ws || !proofs || !lens || !results))) throw Error("hg_verify_device_batch: null argument");
+    if (!pk->ctx) throw Error("hg_verify_device_batch: needs a device prover key (hg_setup with a context)");
+    if (mode < 0 || mode > 3) throw Error("hg_verify_device_batch: unknown mode bits");
+    std::vector<const Witness*> W(n);
+    std::vector<const uint8_t*> P(n);
+    std::vector<size_t> N(n);
+    for (size_t i = 0; i < n; i++) {
+        if (!ws[i] || !proofs[i]) throw Error("hg_verify_device_batch: null witness or proof at index " + std::to_string(i));
+        check_witness(pk, ws[i], "hg_verify_device_batch");
+        W[i] = &ws[i]->w; P[i] = proofs[i]; N[i] = lens[i];
+    }
+    if (!n) return 0;
+    std::vector<std::string> why;
+    try {
+        verify_batch_device(ctx, pk, W, P, N, mode, why);
+    } catch (const std::exception& e) {
+        const std::string m = e.what();
+        throw Error(m.rfind("hg_verify_device_batch", 0) == 0 ? m : "hg_verify_device_batch: " + m);
+    }
+    int rejected = 0;
+    for (size_t i = 0; i < n; i++) {
+        results[i] = why[i].empty() ? 0 : 1;
+        rejected += results[i];
+        if (reasons && reason_cap) {
+            char* r = reasons + i * reason_cap;
+            const size_t m = std::min(why[i].size(), reason_cap - 1);
+            memcpy(r, why[i].data(), m);
+            r[m] = 0;
+        }
+    }
+    return rejected;
     HG_CATCH(-1)
 }
 

@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <cstddef>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 #include <stdexcept>
@@ -208,6 +209,18 @@ template <class E> struct VerifyBackendT {
 };
 typedef VerifyBackendT<E2> VerifyBackend;
 std::string verify_proof_with(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode);
+// verify_proof_with in two steps (hg_verify_device_batch): the walk, which records its work with the backend and returns the checks
+// that wait for the backend's results, and - after the caller has finished the backend, with `chain` handed over in modes != 0 -
+// the completion, which runs them ("" = accepted, else the rejection reason). A walk that rejects early sets `reason` and leaves
+// nothing pending; the jobs it recorded up to there are not needed.
+template <class E> struct VerifyPendingT {
+    std::string reason;
+    std::vector<E> chain;                              // modes != 0: every challenge the walk squeezed, in order
+    std::vector<std::function<void()>> deferred;       // the comparisons; they read the backend's tickets
+};
+typedef VerifyPendingT<E2> VerifyPending;
+VerifyPending verify_walk(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode);
+std::string verify_complete(VerifyPending& v);
 namespace bn { struct Fr; }
 std::string verify_proof_with_bn254(VerifyBackendT<bn::Fr>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len);
 // the same over bn256::Fr (F = E = Fr, 32-byte proof elements): the bn254 test family

@@ -121,6 +121,7 @@ hg_ctx::~hg_ctx() {
     hg::ctx_register(this, false);
     hg::pending_shard_drop(this);
     hg::prove_cache_drop(this);
+    hg::verify_batch_drop(this);
     if (scratch_values) hg::values_free(scratch_values);
     for (auto& v : stream_values) if (v) hg::values_free(v);
     for (auto& p : stream_pinned) if (p) (void)hipHostFree(p);

@@ -75,6 +75,8 @@ struct hg_ctx {
     // options (hg_set_option)
     bool one_stream = false;  // keep every launch on `stream` (per-kernel timings without cross-stream interference)
     int mode = 0;             // protocol mode of the next proves: bit 0 absorbing transcript, bit 1 extension-field memory checking
+    int64_t verify_batch_group = 0;   // hg_verify_device_batch: most proofs per device pass (0: sized from the arena budget)
+    void* verify_batch = nullptr;     // verifier_batch.hip: VerifyBatchBufs (pinned and device input sets, upload stream), freed with the context
     // bump arena: chunks are kept across proves, offsets reset per prove
     struct Chunk { char* p; size_t cap, used; size_t high = 0; };  // high: largest `used` since the last reset
     std::vector<Chunk> chunks;
@@ -264,6 +266,17 @@ void hip_check(hipError_t e, const char* what);
 // BfvEncrypt::verify with the table-sized work on the device (verifier_dev.hip); "" = accepted, else the rejection reason.
 // mode: the protocol mode bits of hg_verify_mode (0..3)
 std::string verify_proof_device(hg_ctx* ctx, const hg_pk* pk, const Witness& w, const uint8_t* proof, size_t len, int mode = 0);
+// the verifier's dot products (verifier_dev.hip): job q = sum_i a_q[i] * b_q[i] (a: an E2 table or a table of base-field integers,
+// b: an eq table) into res[slot], in launches of at most VD_MAX_Y jobs; partials: njobs * VD_BLOCKS entries
+struct DotJob { const void* a; const E2* b; size_t n; int slot; int a_is_u64; };
+constexpr int VD_BLOCKS = 32;
+constexpr size_t VD_MAX_Y = 65535;
+void vdot_jobs(hipStream_t st, const DotJob* d_jobs, size_t njobs, E2* partials, E2* res);
+// hg_verify_device_batch (verifier_batch.hip): proof i against ws[i], all in `mode`; why[i] = "" accepted, else the reason. An
+// hg::Error inside one proof's walk names its index. group: proofs per device pass (0: sized from the arena budget)
+void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Witness*>& ws, const std::vector<const uint8_t*>& proofs,
+                         const std::vector<size_t>& lens, int mode, std::vector<std::string>& why);
+void verify_batch_drop(hg_ctx* ctx);   // the context's batch buffers (hg_destroy)
 void prove_cache_drop(hg_ctx* ctx);
 
 }  // namespace hg

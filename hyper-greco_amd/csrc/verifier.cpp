@@ -617,10 +617,14 @@ static std::string verify_impl(const Params& p, const LassoPlan& lp, const HCirc
 // count E challenges: two base challenges each over Goldilocks, one Fr each over BN254 (E = F there). In mode 0 they index the
 // fixed chain; in the protocol modes (Goldilocks only) the walk records what it squeezed and hands it to dev.set_chain() before
 // finish(), and the offsets index that record.
+// walk_with_backend is the walk alone: it returns the pending checks (or the reason of an early rejection) and neither hands the
+// chain over nor finishes the backend, so a batch can walk many proofs - on several host threads, with a backend that only records
+// (verifier_batch.hip) - and finish them together. The walk itself opens no OpenMP region.
 template <class F>
-static std::string verify_with_backend(VerifyBackendT<typename F::E>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode) {
+static VerifyPendingT<typename F::E> walk_with_backend(VerifyBackendT<typename F::E>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode) {
     typedef typename F::E E;
     typedef typename Verifier<F>::Claim Claim;
+    VerifyPendingT<E> out;
     try {
         Verifier<F> V;
         V.bytes = ProofBytes{proof, len};
@@ -666,13 +670,31 @@ static std::string verify_with_backend(VerifyBackendT<typename F::E>& dev, const
                 const E want = cl.value;
                 V.deferred.push_back([D, t, want, k] { if (!F::eq(D->value(t), want)) throw Reject("input claim mismatch at input " + std::to_string(k)); });
             }
-        if (mode != 0) dev.set_chain(V.ch.seq);
-        dev.finish();
-        for (auto& f : V.deferred) f();
+        if (mode != 0) out.chain = std::move(V.ch.seq);
+        out.deferred = std::move(V.deferred);   // (the checks capture the backend and their own values, never the walk's state)
+    } catch (const Reject& r) {
+        out.reason = r.what();
+        out.deferred.clear();
+    }
+    return out;
+}
+// the deferred comparisons, in walk order, once the backend's results are in: "" or the first failure
+template <class E> static std::string complete_pending(VerifyPendingT<E>& v) {
+    if (!v.reason.empty()) return v.reason;
+    try {
+        for (auto& f : v.deferred) f();
         return "";
     } catch (const Reject& r) {
         return r.what();
     }
+}
+template <class F>
+static std::string verify_with_backend(VerifyBackendT<typename F::E>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode) {
+    VerifyPendingT<typename F::E> v = walk_with_backend<F>(dev, p, lp, c, proof, len, mode);
+    if (!v.reason.empty()) return v.reason;
+    if (mode != 0) dev.set_chain(v.chain);
+    dev.finish();
+    return complete_pending(v);
 }
 
 }  // namespace
@@ -680,6 +702,10 @@ static std::string verify_with_backend(VerifyBackendT<typename F::E>& dev, const
 std::string verify_proof_with(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode) {
     return verify_with_backend<GlField>(dev, p, lp, c, proof, len, mode);
 }
+VerifyPending verify_walk(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode) {
+    return walk_with_backend<GlField>(dev, p, lp, c, proof, len, mode);
+}
+std::string verify_complete(VerifyPending& v) { return complete_pending(v); }
 std::string verify_proof_with_bn254(VerifyBackendT<bn::Fr>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len) {
     return verify_with_backend<BnField>(dev, p, lp, c, proof, len, 0);
 }

@@ -1,0 +1,606 @@
+// hg_verify_device_batch: BfvEncrypt::verify of a run of proofs under one key in one device pass per group [REF
+// bfv-gkr/src/sk_encryption_circuit.rs:462-517]. Every proof gets exactly the decision of verify_proof_device (verifier_dev.hip).
+//   1. The walks (verifier.cpp: verify_walk) run on the host threads, one proof each, against a backend that only RECORDS its jobs
+//      symbolically (no device call, no arena allocation: the bump allocator is not thread-safe). The walk opens no OpenMP region of
+//      its own, so nothing nests.
+//   2. The jobs of a group are merged. Chain offsets are made absolute - mode 0 reads the context's fixed chain, modes 1-3 the
+//      concatenation of the proofs' own chains, each proof's offsets shifted by its base - and identical tables are built once:
+//      in mode 0 every eq table, constant-gate sum, Libra gather, DFT-row table and their dot products are the same for every
+//      proof (they depend on the key only), so a group pays for them once. Phase-2 gathers (they read the proof's own phase-1
+//      evaluations) and the input evaluations (they read the proof's own witness) are never shared.
+//   3. One allocation, one descriptor copy, one launch per kind (the launchers of the single-proof verifier), one synchronisation,
+//      then every proof's deferred comparisons (verify_complete) on the host threads.
+// The public inputs are gathered by host threads into page-locked memory and copied on a stream of their own: group g+1's copies
+// and walks run while group g's kernels do.
+#include <algorithm>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <omp.h>
+#include "prover.hpp"
+#include "gl_wide.hpp"
+
+namespace hg {
+namespace {
+
+// ---- the MLE evaluations of the public inputs -------------------------------------------------------------------------------------
+// Work unit: one eq table and the P input tables evaluated at its point (mode 0: the group's tables of one input; modes 1-3: one).
+// A workgroup owns VB_TILE consecutive entries: it reads its eq tile once into registers and multiply-accumulates it against each
+// of the P tables, eight products per accumulator before one reduction (gl_wide.hpp), one partial per (member, workgroup). A second
+// launch adds every member's partials into its result slot. HBM traffic: 8 B per input entry plus 16 / P B of eq.
+constexpr int VB_TPB = 256, VB_ITEMS = 8, VB_TILE = VB_TPB * VB_ITEMS;
+struct VinUnit { const E2* eq; size_t n; int first, P, nblk; size_t part0; };   // member p's partial of workgroup b: part0 + p * nblk + b
+struct VinMember { const u64* a; int unit, slot; };
+struct VinBlock { int unit, blk; };
+
+__global__ __launch_bounds__(VB_TPB) void k_vin_dots(const VinUnit* __restrict__ units, const VinMember* __restrict__ members,
+                                                     const VinBlock* __restrict__ blocks, E2* __restrict__ partials) {
+    __shared__ E2 sm[2][VB_TPB / 64];
+    const VinBlock B = blocks[blockIdx.x];
+    const VinUnit U = units[B.unit];
+    const size_t base = (size_t)B.blk * VB_TILE + threadIdx.x;
+    E2 eq[VB_ITEMS];
+#pragma unroll
+    for (int j = 0; j < VB_ITEMS; j++) {
+        const size_t i = base + (size_t)j * VB_TPB;
+        eq[j] = i < U.n ? U.eq[i] : e2_zero();
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int p = 0; p < U.P; p++) {
+        const u64* __restrict__ a = members[U.first + p].a;
+        u64 v[VB_ITEMS];
+#pragma unroll
+        for (int j = 0; j < VB_ITEMS; j++) {
+            const size_t i = base + (size_t)j * VB_TPB;
+            v[j] = i < U.n ? a[i] : 0;
+        }
+        WAcc c0 = wacc_zero(), c1 = wacc_zero();
+#pragma unroll
+        for (int j = 0; j < VB_ITEMS; j++) wmac2(c0, eq[j].c0, v[j], c1, eq[j].c1, v[j]);
+        E2 s = e2(wreduce(c0), wreduce(c1));
+        for (int o = 32; o > 0; o >>= 1) {
+            E2 t;
+            t.c0 = __shfl_xor(s.c0, o);
+            t.c1 = __shfl_xor(s.c1, o);
+            s = e2_add(s, t);
+        }
+        // (two LDS buffers: member p + 1 writes the other one, and thread 0 has read this one before the next barrier)
+        if (lane == 0) sm[p & 1][wave] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            E2 t = sm[p & 1][0];
+            for (int w = 1; w < VB_TPB / 64; w++) t = e2_add(t, sm[p & 1][w]);
+            partials[U.part0 + (size_t)p * U.nblk + B.blk] = t;
+        }
+    }
+}
+// one wave per member: its unit's nblk partials into its slot
+__global__ __launch_bounds__(64) void k_vin_reduce(const VinUnit* __restrict__ units, const VinMember* __restrict__ members,
+                                                   const E2* __restrict__ partials, E2* __restrict__ res) {
+    const VinMember M = members[blockIdx.x];
+    const VinUnit U = units[M.unit];
+    const E2* part = partials + U.part0 + (size_t)(blockIdx.x - U.first) * U.nblk;
+    E2 s = e2_zero();
+    for (int b = threadIdx.x; b < U.nblk; b += 64) s = e2_add(s, part[b]);
+    for (int o = 32; o > 0; o >>= 1) {
+        E2 t;
+        t.c0 = __shfl_xor(s.c0, o);
+        t.c1 = __shfl_xor(s.c1, o);
+        s = e2_add(s, t);
+    }
+    if (threadIdx.x == 0) res[M.slot] = s;
+}
+
+// ---- the recording backend ----------------------------------------------------------------------------------------------------------
+// The same calls as DevBackend (verifier_dev.hip), kept as symbolic jobs: tables are indices into the proof's own lists, chain
+// offsets are local to the proof's chain, tickets are local result slots. value() reads the slots the batch copied back.
+struct RecBackend : VerifyBackend {
+    const hg_pk* pk;
+    size_t n_inputs;
+    struct Eq { int nvars; dev::ClaimSet cs; };
+    struct Const { int node, eqc, slot; };
+    struct Lin { int node, in, eqc; };
+    struct Mul { int node, in, eqc, eqx; size_t u_at; };
+    struct Fft { int node; dev::ClaimSet cs; };
+    enum { D_LIN, D_MUL, D_FFT };
+    struct Dot { int kind, tab, eq, slot; };
+    struct In { int k, eq, slot; };   // k < 0: ct0is
+    std::vector<Eq> eqs;
+    std::vector<Const> consts;
+    std::vector<Lin> lins;
+    std::vector<Mul> muls;
+    std::vector<Fft> ffts;
+    std::vector<Dot> dots;
+    std::vector<In> ins;
+    std::vector<E2> us;            // phase-1 evaluations of the Vanilla nodes with a phase 2, back to back
+    size_t chain_need = 0;         // one past the last chain entry a job reads
+    int nslots = 0;
+    std::vector<E2> res;           // the results, filled after the group's synchronisation
+    int node = -1, eqc = -1, eqx = -1, eqy = -1;
+    size_t u_at = 0;
+    dev::ClaimSet cs;
+
+    RecBackend(const hg_pk* k) : pk(k), n_inputs(2 * (size_t)k->params.k + 4) { memset(&cs, 0, sizeof(cs)); }
+    int slot() { return nslots++; }
+    void reads_chain(const dev::ClaimSet& c, int nvars) {
+        for (int a = 0; a < c.n; a++) chain_need = std::max(chain_need, c.point_off[a] + (size_t)nvars);
+        if (!c.unit_alpha) chain_need = std::max(chain_need, c.alpha_off + (size_t)c.n);
+    }
+    int eq_of(int nvars, const dev::ClaimSet& c) {
+        reads_chain(c, nvars);
+        eqs.push_back(Eq{nvars, c});
+        return (int)eqs.size() - 1;
+    }
+    int eq_single(int nvars, size_t off) {
+        dev::ClaimSet c;
+        memset(&c, 0, sizeof(c));
+        c.n = 1; c.unit_alpha = 1; c.point_off[0] = off;
+        return eq_of(nvars, c);
+    }
+    int dot(int kind, int tab, int eq) { const int t = slot(); dots.push_back(Dot{kind, tab, eq, t}); return t; }
+
+    void begin_node(int id, const ClaimOffs& cl) override {
+        node = id;
+        const HNode& n = pk->circuit.nodes[id];
+        if (cl.point_off.size() > (size_t)dev::MAX_CLAIMS) throw Error("verifier: too many claims on one node");
+        memset(&cs, 0, sizeof(cs));
+        cs.n = (int)cl.point_off.size();
+        cs.unit_alpha = cl.unit ? 1 : 0;
+        cs.alpha_off = cl.alpha_off;
+        for (int a = 0; a < cs.n; a++) cs.point_off[a] = cl.point_off[a];
+        eqc = n.kind == NK_VANILLA ? eq_of(n.log2_out(), cs) : -1;
+        eqx = eqy = -1;
+    }
+    int const_sum() override { const int t = slot(); consts.push_back(Const{node, eqc, t}); return t; }
+    void set_x(size_t x_off) override {
+        const HNode& n = pk->circuit.nodes[node];
+        eqx = eq_single(n.kind == NK_VANILLA ? n.log2_sub_in + n.log2_reps : n.log2_size, x_off);
+    }
+    std::vector<int> lin_terms() override {
+        const HNode& n = pk->circuit.nodes[node];
+        const hg_pk::NodeDev& nd = pk->node_dev[node];
+        std::vector<int> tk(n.arity, -1);
+        for (int i = 0; i < n.arity; i++) {
+            if (!n.left_use[i] || !nd.lin[i].ptr) continue;
+            lins.push_back(Lin{node, i, eqc});
+            tk[i] = dot(D_LIN, (int)lins.size() - 1, eqx);
+        }
+        return tk;
+    }
+    void set_y(size_t y_off, const std::vector<E2>& u) override {
+        const HNode& n = pk->circuit.nodes[node];
+        eqy = eq_single(n.log2_sub_in + n.log2_reps, y_off);
+        u_at = us.size();
+        us.insert(us.end(), u.begin(), u.end());
+    }
+    std::vector<int> mul_terms() override {
+        const HNode& n = pk->circuit.nodes[node];
+        const hg_pk::NodeDev& nd = pk->node_dev[node];
+        std::vector<int> tk(n.arity, -1);
+        for (int i = 0; i < n.arity; i++) {
+            if (!n.right_use[i] || !nd.mulR[i].ptr) continue;
+            muls.push_back(Mul{node, i, eqc, eqx, u_at});
+            tk[i] = dot(D_MUL, (int)muls.size() - 1, eqy);
+        }
+        return tk;
+    }
+    int fft_term() override {
+        reads_chain(cs, pk->circuit.nodes[node].log2_size);
+        ffts.push_back(Fft{node, cs});
+        return dot(D_FFT, (int)ffts.size() - 1, eqx);
+    }
+    void end_node() override { node = -1; }
+    int mle_input(size_t k, size_t point_off, int nvars) override {
+        if (k >= n_inputs) throw Error("verifier: no such input table");
+        const int t = slot();
+        ins.push_back(In{(int)k, eq_single(nvars, point_off), t});
+        return t;
+    }
+    int mle_ct0is(size_t point_off, int nvars) override { const int t = slot(); ins.push_back(In{-1, eq_single(nvars, point_off), t}); return t; }
+    void finish() override { throw Error("verifier: a recording backend is finished by its batch"); }
+    E2 value(int t) const override { return res[t]; }
+};
+
+// dedup keys: the descriptor with absolute chain offsets
+typedef std::vector<u64> Key;
+void key_cs(Key& k, const dev::ClaimSet& c, size_t base) {
+    k.push_back((u64)c.n);
+    k.push_back((u64)c.unit_alpha);
+    if (!c.unit_alpha) k.push_back(c.alpha_off + base);
+    for (int a = 0; a < c.n; a++) k.push_back(c.point_off[a] + base);
+}
+dev::ClaimSet shift_cs(dev::ClaimSet c, size_t base) {
+    if (!c.unit_alpha) c.alpha_off += base;
+    for (int a = 0; a < c.n; a++) c.point_off[a] += base;
+    return c;
+}
+
+// the context's batch buffers: two sets of a group's public inputs (page-locked and in HBM) and the stream that copies them
+struct VerifyBatchBufs {
+    hipStream_t up = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};   // the copies of set s are done
+    bool recorded[2] = {false, false};
+    u64* h_in[2] = {nullptr, nullptr};
+    u64* d_in[2] = {nullptr, nullptr};
+    size_t words[2] = {0, 0};
+    char* h_desc = nullptr;                  // page-locked descriptor staging of one group
+    size_t desc_cap = 0;
+};
+VerifyBatchBufs* batch_bufs(hg_ctx* ctx) {
+    if (!ctx->verify_batch) {
+        auto* b = new VerifyBatchBufs();
+        ctx->verify_batch = b;
+        hip_check(hipStreamCreateWithFlags(&b->up, hipStreamNonBlocking), "hipStreamCreate(batch uploads)");
+        for (auto& e : b->ev) hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate(batch uploads)");
+    }
+    return static_cast<VerifyBatchBufs*>(ctx->verify_batch);
+}
+
+// budget of one group: its inputs in one set (and, in modes 1-3, each proof's own node tables in the arena: about five times its
+// inputs, 0.13 GB at n=32768 k=16)
+constexpr size_t VB_INPUT_BUDGET = (size_t)1 << 30, VB_TABLE_BUDGET = (size_t)4 << 30;
+constexpr size_t VB_MAX_GROUP = 64;
+
+struct Walked {   // one proof of a group
+    size_t idx;
+    std::unique_ptr<RecBackend> rec;
+    VerifyPending pend;
+    std::string error;                       // an hg::Error of the walk
+    std::vector<int> gslot;                  // local slot -> the group's result slot
+    const u64* d_in = nullptr;               // its inputs in HBM: s, e, k1, ais, r1is, r2is, ct0is
+};
+
+}  // namespace
+
+void verify_batch_drop(hg_ctx* ctx) {
+    if (!ctx->verify_batch) return;
+    auto* b = static_cast<VerifyBatchBufs*>(ctx->verify_batch);
+    if (b->up) { (void)hipStreamSynchronize(b->up); (void)hipStreamDestroy(b->up); }
+    for (auto e : b->ev) if (e) (void)hipEventDestroy(e);
+    for (auto p : b->h_in) if (p) (void)hipHostFree(p);
+    for (auto p : b->d_in) if (p) (void)hipFree(p);
+    if (b->h_desc) (void)hipHostFree(b->h_desc);
+    delete b;
+    ctx->verify_batch = nullptr;
+}
+
+void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Witness*>& ws, const std::vector<const uint8_t*>& proofs,
+                         const std::vector<size_t>& lens, int mode, std::vector<std::string>& why) {
+    const size_t n = ws.size();
+    why.assign(n, std::string());
+    if (!n) return;
+    const bool times = hg_times("verify");
+    const double t0 = omp_get_wtime();
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    VerifyBatchBufs* B = batch_bufs(ctx);
+    // kernels, descriptor copies and input copies may be queued on any way out (a rejection, an hg::Error): drain both streams before
+    // the caller may reuse the arena and the staging or free a witness
+    struct Drain {
+        hipStream_t a, b;
+        ~Drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); }
+    } drain{ctx->stream, B->up};
+    hip_check(hipStreamSynchronize(ctx->stream), "hg_verify_device_batch: synchronise");   // (the arena is reset below)
+    ctx->ensure_chain(16384);
+    const Params& p = pk->params;
+    const size_t SZ = p.SZ(), PZ = p.PZ(), K = (size_t)p.k;
+    // one proof's inputs in HBM, in the order of verify_proof_device: s, e, k1, ais (k), r1is (k), r2is, then ct0is
+    const size_t words = (3 + 3 * K) * SZ + K * PZ;
+    const size_t in_bytes = words * sizeof(u64);
+    size_t G = (size_t)std::max<int64_t>(0, ctx->verify_batch_group);
+    if (!G) {
+        G = std::max<size_t>(1, VB_INPUT_BUDGET / in_bytes);
+        if (mode != 0) G = std::min(G, std::max<size_t>(1, VB_TABLE_BUDGET / (5 * in_bytes)));
+        G = std::min(G, VB_MAX_GROUP);
+    }
+    const size_t ngroups = (n + G - 1) / G;
+    [[maybe_unused]] const int nthr = std::max(1, hg_omp_threads());   // (the device pass of hipcc ignores the pragmas)
+
+    std::vector<std::vector<Walked>> groups(ngroups);
+    // stage group g: gather its inputs into page-locked set g & 1 (host threads), copy them on the upload stream
+    auto stage = [&](size_t g) {
+        const int s = (int)(g & 1);
+        const size_t i0 = g * G, i1 = std::min(n, i0 + G), np = i1 - i0;
+        if (B->recorded[s]) hip_check(hipEventSynchronize(B->ev[s]), "hg_verify_device_batch: input set reuse");
+        if (B->words[s] < np * words) {
+            if (B->h_in[s]) { (void)hipHostFree(B->h_in[s]); B->h_in[s] = nullptr; }
+            if (B->d_in[s]) { (void)hipFree(B->d_in[s]); B->d_in[s] = nullptr; }
+            B->words[s] = 0;
+            hip_check(hipHostMalloc((void**)&B->h_in[s], np * words * sizeof(u64), hipHostMallocDefault), "hipHostMalloc(batch inputs)");
+            hip_check(hipMalloc((void**)&B->d_in[s], np * words * sizeof(u64)), "hipMalloc(batch inputs)");
+            B->words[s] = np * words;
+        }
+        struct Piece { u64* dst; const u64* src; size_t n; };
+        std::vector<Piece> pieces;
+        constexpr size_t PIECE = (size_t)1 << 18;   // 2 MB
+        for (size_t i = i0; i < i1; i++) {
+            const Witness& w = *ws[i];
+            u64* dst = B->h_in[s] + (i - i0) * words;
+            const std::pair<const u64*, size_t> tabs[] = {{w.s.data(), SZ}, {w.e.data(), SZ}, {w.k1.data(), SZ}, {w.ais.data(), K * SZ},
+                                                          {w.r1is.data(), K * SZ}, {w.r2is.data(), K * PZ}, {w.ct0is.data(), K * SZ}};
+            for (auto& t : tabs) {
+                for (size_t o = 0; o < t.second; o += PIECE) pieces.push_back(Piece{dst + o, t.first + o, std::min(PIECE, t.second - o)});
+                dst += t.second;
+            }
+        }
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)pieces.size()))
+        for (long long q = 0; q < (long long)pieces.size(); q++) memcpy(pieces[q].dst, pieces[q].src, pieces[q].n * sizeof(u64));
+        hip_check(hipMemcpyAsync(B->d_in[s], B->h_in[s], np * words * sizeof(u64), hipMemcpyHostToDevice, B->up), "hg_verify_device_batch: upload inputs");
+        hip_check(hipEventRecord(B->ev[s], B->up), "hipEventRecord");
+        B->recorded[s] = true;
+    };
+    // walk group g on the host threads
+    auto walk = [&](size_t g) {
+        const size_t i0 = g * G, i1 = std::min(n, i0 + G);
+        std::vector<Walked>& W = groups[g];
+        W.resize(i1 - i0);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)W.size()))
+        for (long long q = 0; q < (long long)W.size(); q++) {
+            Walked& x = W[q];
+            x.idx = i0 + (size_t)q;
+            try {
+                x.rec.reset(new RecBackend(pk));
+                x.pend = verify_walk(*x.rec, p, pk->lasso, pk->circuit, proofs[x.idx], lens[x.idx], mode);
+            } catch (const std::exception& e) { x.error = e.what(); }
+        }
+        for (auto& x : W)
+            if (!x.error.empty()) throw Error("hg_verify_device_batch: proof " + std::to_string(x.idx) + ": " + x.error);
+    };
+    // merge group g's jobs and enqueue them; returns the result slots used
+    auto launch = [&](size_t g) -> size_t {
+        const int s = (int)(g & 1);
+        std::vector<Walked>& W = groups[g];
+        hipStream_t st = ctx->stream;
+        ctx->arena_reset();
+        std::vector<dev::EqJob> eqs;
+        int eq_max_n = 0;
+        struct ConstG { int node, eq, slot; };
+        std::vector<ConstG> consts;
+        struct LinG { int node, in, eq; };
+        std::vector<LinG> lins;
+        struct MulG { int node, in, eqc, eqx; size_t u_at; };
+        std::vector<MulG> muls;
+        struct FftG { int node; dev::ClaimSet cs; };
+        std::vector<FftG> ffts;
+        int fft_max_L = 0, fft_max_claims = 0;
+        struct DotG { int kind, tab, eq, slot; };
+        std::vector<DotG> dots;
+        struct InM { int eq; const u64* a; int slot; };
+        std::vector<InM> ins;
+        std::vector<E2> chain, us;
+        std::map<Key, int> eq_ix, const_ix, lin_ix, fft_ix, dot_ix;
+        int nslot = 0;
+        size_t gt_max = 0, gb_max = 0;
+        for (Walked& x : W) {
+            x.d_in = B->d_in[s] + (x.idx - g * G) * words;
+            if (!x.pend.reason.empty()) continue;   // rejected by the walk: its recorded prefix is not launched
+            RecBackend& R = *x.rec;
+            size_t base = 0;
+            if (mode != 0) {
+                if (R.chain_need > x.pend.chain.size()) throw Error("hg_verify_device_batch: proof " + std::to_string(x.idx) + ": verifier: a job reads past the challenges the walk squeezed");
+                base = chain.size();
+                chain.insert(chain.end(), x.pend.chain.begin(), x.pend.chain.end());
+            } else if (R.chain_need > ctx->chal_e) throw Error("hg_verify_device_batch: proof " + std::to_string(x.idx) + ": verifier: a job reads past the fixed chain");
+            x.gslot.assign(R.nslots, -1);
+            auto new_slot = [&] { return nslot++; };
+            std::vector<int> geq(R.eqs.size());
+            for (size_t e = 0; e < R.eqs.size(); e++) {
+                Key k{(u64)R.eqs[e].nvars};
+                key_cs(k, R.eqs[e].cs, base);
+                auto it = eq_ix.find(k);
+                if (it == eq_ix.end()) {
+                    dev::EqJob J;
+                    memset(&J, 0, sizeof(J));
+                    J.n = R.eqs[e].nvars; J.cs = shift_cs(R.eqs[e].cs, base);
+                    eqs.push_back(J);
+                    eq_max_n = std::max(eq_max_n, J.n);
+                    it = eq_ix.emplace(k, (int)eqs.size() - 1).first;
+                }
+                geq[e] = it->second;
+            }
+            for (auto& c : R.consts) {
+                Key k{(u64)c.node, (u64)geq[c.eqc]};
+                auto it = const_ix.find(k);
+                if (it == const_ix.end()) { consts.push_back(ConstG{c.node, geq[c.eqc], new_slot()}); it = const_ix.emplace(k, (int)consts.size() - 1).first; }
+                x.gslot[c.slot] = consts[it->second].slot;
+            }
+            std::vector<int> glin(R.lins.size()), gmul(R.muls.size()), gfft(R.ffts.size());
+            for (size_t i = 0; i < R.lins.size(); i++) {
+                const auto& l = R.lins[i];
+                Key k{(u64)l.node, (u64)l.in, (u64)geq[l.eqc]};
+                auto it = lin_ix.find(k);
+                if (it == lin_ix.end()) { lins.push_back(LinG{l.node, l.in, geq[l.eqc]}); it = lin_ix.emplace(k, (int)lins.size() - 1).first; }
+                glin[i] = it->second;
+            }
+            for (size_t i = 0; i < R.muls.size(); i++) {   // (never shared: they read the proof's phase-1 evaluations)
+                const auto& m = R.muls[i];
+                muls.push_back(MulG{m.node, m.in, geq[m.eqc], geq[m.eqx], us.size() + m.u_at});
+                gmul[i] = (int)muls.size() - 1;
+            }
+            us.insert(us.end(), R.us.begin(), R.us.end());
+            for (size_t i = 0; i < R.ffts.size(); i++) {
+                Key k{(u64)R.ffts[i].node};
+                key_cs(k, R.ffts[i].cs, base);
+                auto it = fft_ix.find(k);
+                if (it == fft_ix.end()) {
+                    ffts.push_back(FftG{R.ffts[i].node, shift_cs(R.ffts[i].cs, base)});
+                    fft_max_L = std::max(fft_max_L, pk->circuit.nodes[R.ffts[i].node].log2_size);
+                    fft_max_claims = std::max(fft_max_claims, R.ffts[i].cs.n);
+                    it = fft_ix.emplace(k, (int)ffts.size() - 1).first;
+                }
+                gfft[i] = it->second;
+            }
+            for (auto& d : R.dots) {
+                const int tab = d.kind == RecBackend::D_LIN ? glin[d.tab] : d.kind == RecBackend::D_MUL ? gmul[d.tab] : gfft[d.tab];
+                if (d.kind == RecBackend::D_MUL) { dots.push_back(DotG{d.kind, tab, geq[d.eq], new_slot()}); x.gslot[d.slot] = dots.back().slot; continue; }
+                Key k{(u64)d.kind, (u64)tab, (u64)geq[d.eq]};
+                auto it = dot_ix.find(k);
+                if (it == dot_ix.end()) { dots.push_back(DotG{d.kind, tab, geq[d.eq], new_slot()}); it = dot_ix.emplace(k, (int)dots.size() - 1).first; }
+                x.gslot[d.slot] = dots[it->second].slot;
+            }
+            for (auto& in : R.ins) {   // (never shared: they read the proof's own witness)
+                size_t off;
+                if (in.k < 0) off = (3 + 2 * K) * SZ + K * PZ;
+                else if (in.k < 3) off = (size_t)in.k * SZ;
+                else if ((size_t)in.k < 3 + 2 * K) off = (size_t)in.k * SZ;   // ais then r1is, SZ each
+                else off = (3 + 2 * K) * SZ;                                  // r2is
+                const int sl = new_slot();
+                ins.push_back(InM{geq[in.eq], x.d_in + off, sl});
+                x.gslot[in.slot] = sl;
+            }
+        }
+        if ((size_t)nslot > ctx->res_cap)
+            throw Error("hg_verify_device_batch: a group needs " + std::to_string(nslot) + " result slots, the context has " + std::to_string(ctx->res_cap) + ": lower verify_batch_group");
+        // device tables (arena)
+        for (auto& J : eqs) J.out = ctx->alloc_n<E2>((size_t)1 << J.n);
+        std::vector<dev::GatherJob> gts(lins.size());
+        std::vector<E2*> lin_T(lins.size()), mul_B(muls.size()), fft_F(ffts.size());
+        for (size_t i = 0; i < lins.size(); i++) {
+            const HNode& nd = pk->circuit.nodes[lins[i].node];
+            const size_t SR = (size_t)1 << (nd.log2_sub_in + nd.log2_reps);
+            dev::GatherJob& gj = gts[i];
+            memset(&gj, 0, sizeof(gj));
+            gj.g.lin = pk->node_dev[lins[i].node].lin[lins[i].in];
+            gj.eqc = eqs[lins[i].eq].out; gj.log2_S = nd.log2_sub_in; gj.log2_G = nd.log2_sub_out; gj.log2_R = nd.log2_reps;
+            gj.T = lin_T[i] = ctx->alloc_n<E2>(SR);
+            gt_max = std::max(gt_max, SR);
+        }
+        std::vector<dev::FftJob> fjs(ffts.size());
+        for (size_t i = 0; i < ffts.size(); i++) {
+            const HNode& nd = pk->circuit.nodes[ffts[i].node];
+            const int L = nd.log2_size;
+            const size_t N = (size_t)1 << L;
+            fjs[i] = dev::FftJob{fft_F[i] = ctx->alloc_n<E2>(N), (nd.inverse ? pk->w_inv : pk->w_fwd).at(L), nd.inverse ? gl_inv(gl_from_u64(N)) : 1, L, ffts[i].cs};
+        }
+        // the descriptors, the walks' chains and phase-1 evaluations: one page-locked staging, one copy ahead of the launches
+        std::vector<VinUnit> units;
+        std::vector<VinMember> members;
+        std::vector<VinBlock> blocks;
+        {
+            std::vector<std::vector<const InM*>> by_eq(eqs.size());
+            for (auto& m : ins) by_eq[m.eq].push_back(&m);
+            size_t part = 0;
+            for (size_t e = 0; e < eqs.size(); e++) {
+                if (by_eq[e].empty()) continue;
+                VinUnit U;
+                U.eq = eqs[e].out; U.n = (size_t)1 << eqs[e].n; U.first = (int)members.size(); U.P = (int)by_eq[e].size();
+                U.nblk = (int)((U.n + VB_TILE - 1) / VB_TILE); U.part0 = part;
+                part += (size_t)U.P * U.nblk;
+                for (const InM* m : by_eq[e]) members.push_back(VinMember{m->a, (int)units.size(), m->slot});
+                for (int b = 0; b < U.nblk; b++) blocks.push_back(VinBlock{(int)units.size(), b});
+                units.push_back(U);
+            }
+        }
+        size_t vin_parts = 0, vin_bytes = 0;   // (vin_bytes: what k_vin_dots reads, eq tables and input tables)
+        for (auto& U : units) { vin_parts += (size_t)U.P * U.nblk; vin_bytes += U.n * (sizeof(E2) + (size_t)U.P * sizeof(u64)); }
+        size_t desc_bytes = 0;
+        auto place = [&](size_t bytes) { const size_t o = desc_bytes; desc_bytes += (bytes + 255) & ~(size_t)255; return o; };
+        const size_t o_chain = place(chain.size() * sizeof(E2)), o_us = place(us.size() * sizeof(E2)), o_eq = place(eqs.size() * sizeof(dev::EqJob)),
+                     o_gt = place(gts.size() * sizeof(dev::GatherJob)), o_gb = place(muls.size() * sizeof(dev::GatherBJob)),
+                     o_fft = place(fjs.size() * sizeof(dev::FftJob)), o_dot = place(dots.size() * sizeof(DotJob)),
+                     o_unit = place(units.size() * sizeof(VinUnit)), o_mem = place(members.size() * sizeof(VinMember)),
+                     o_blk = place(blocks.size() * sizeof(VinBlock));
+        char* d_desc = static_cast<char*>(ctx->alloc(desc_bytes));
+        if (desc_bytes > B->desc_cap) {
+            if (B->h_desc) (void)hipHostFree(B->h_desc);
+            B->h_desc = nullptr;
+            B->desc_cap = 0;
+            hip_check(hipHostMalloc((void**)&B->h_desc, desc_bytes, hipHostMallocDefault), "hipHostMalloc(batch descriptors)");
+            B->desc_cap = desc_bytes;
+        }
+        char* h = B->h_desc;
+        const E2* chal = mode != 0 ? reinterpret_cast<const E2*>(d_desc + o_chain) : ctx->d_chal;
+        const E2* d_us = reinterpret_cast<const E2*>(d_desc + o_us);
+        if (!chain.empty()) memcpy(h + o_chain, chain.data(), chain.size() * sizeof(E2));
+        if (!us.empty()) memcpy(h + o_us, us.data(), us.size() * sizeof(E2));
+        if (!eqs.empty()) memcpy(h + o_eq, eqs.data(), eqs.size() * sizeof(dev::EqJob));
+        if (!gts.empty()) memcpy(h + o_gt, gts.data(), gts.size() * sizeof(dev::GatherJob));
+        for (size_t i = 0; i < muls.size(); i++) {
+            const MulG& m = muls[i];
+            const HNode& nd = pk->circuit.nodes[m.node];
+            const size_t SR = (size_t)1 << (nd.log2_sub_in + nd.log2_reps);
+            mul_B[i] = ctx->alloc_n<E2>(SR);
+            gb_max = std::max(gb_max, SR);
+            const dev::GatherBJob J{pk->node_dev[m.node].mulR[m.in], eqs[m.eqc].out, eqs[m.eqx].out, d_us + m.u_at, nd.log2_sub_in, nd.log2_sub_out, nd.log2_reps, mul_B[i]};
+            memcpy(h + o_gb + i * sizeof(dev::GatherBJob), &J, sizeof(J));
+        }
+        if (!fjs.empty()) memcpy(h + o_fft, fjs.data(), fjs.size() * sizeof(dev::FftJob));
+        for (size_t i = 0; i < dots.size(); i++) {
+            const DotG& d = dots[i];
+            const E2* a = d.kind == RecBackend::D_LIN ? lin_T[d.tab] : d.kind == RecBackend::D_MUL ? mul_B[d.tab] : fft_F[d.tab];
+            const DotJob J{a, eqs[d.eq].out, (size_t)1 << eqs[d.eq].n, d.slot, 0};
+            memcpy(h + o_dot + i * sizeof(DotJob), &J, sizeof(J));
+        }
+        if (!units.empty()) {
+            memcpy(h + o_unit, units.data(), units.size() * sizeof(VinUnit));
+            memcpy(h + o_mem, members.data(), members.size() * sizeof(VinMember));
+            memcpy(h + o_blk, blocks.data(), blocks.size() * sizeof(VinBlock));
+        }
+        if (desc_bytes) hip_check(hipMemcpyAsync(d_desc, h, desc_bytes, hipMemcpyHostToDevice, st), "hg_verify_device_batch: upload descriptors");
+        // one launch per kind (the job index is gridDim.y: launches of at most VD_MAX_Y jobs)
+        auto chunks = [](size_t njobs, size_t per, auto fn) { for (size_t q0 = 0; q0 < njobs; q0 += per) fn(q0, std::min(per, njobs - q0)); };
+        const auto* d_eqs = reinterpret_cast<const dev::EqJob*>(d_desc + o_eq);
+        chunks(eqs.size(), VD_MAX_Y, [&](size_t q0, size_t nq) { dev::eq_jobs(st, d_eqs + q0, (int)nq, eq_max_n, chal); });
+        for (const ConstG& c : consts) {
+            const HNode& nd = pk->circuit.nodes[c.node];
+            const hg_pk::NodeDev& dv = pk->node_dev[c.node];
+            const int grid = dev::vanilla_const_sum(st, dv.const_gate, dv.const_coef, dv.nconst, eqs[c.eq].out, nd.log2_sub_out, nd.log2_reps, ctx->d_partials);
+            dev::reduce_partials(st, ctx->d_partials, grid, 1, ctx->d_res + c.slot);
+        }
+        const auto* d_gts = reinterpret_cast<const dev::GatherJob*>(d_desc + o_gt);
+        chunks(gts.size(), VD_MAX_Y, [&](size_t q0, size_t nq) { dev::gather_jobs(st, d_gts + q0, (int)nq, gt_max); });
+        if (!fjs.empty()) {
+            const size_t per = VD_MAX_Y / (size_t)fft_max_claims;   // (k_fft_tab: gridDim.y = jobs * claims)
+            E2* tab = ctx->alloc_n<E2>(std::min(per, fjs.size()) * (size_t)fft_max_claims * ((size_t)1 << (fft_max_L > 4 ? fft_max_L - 4 : 0)) + 1);
+            const auto* d_ffts = reinterpret_cast<const dev::FftJob*>(d_desc + o_fft);
+            chunks(fjs.size(), per, [&](size_t q0, size_t nq) { dev::fft_jobs(st, d_ffts + q0, (int)nq, fft_max_L, fft_max_claims, chal, tab); });
+        }
+        const auto* d_gbs = reinterpret_cast<const dev::GatherBJob*>(d_desc + o_gb);
+        chunks(muls.size(), VD_MAX_Y, [&](size_t q0, size_t nq) { dev::gather_B_jobs(st, d_gbs + q0, (int)nq, gb_max); });
+        if (!dots.empty()) vdot_jobs(st, reinterpret_cast<const DotJob*>(d_desc + o_dot), dots.size(), ctx->alloc_n<E2>(dots.size() * (size_t)VD_BLOCKS), ctx->d_res);
+        if (!units.empty()) {
+            hip_check(hipStreamWaitEvent(st, B->ev[s], 0), "hg_verify_device_batch: wait for the inputs");
+            E2* part = ctx->alloc_n<E2>(vin_parts);
+            k_vin_dots<<<(unsigned)blocks.size(), VB_TPB, 0, st>>>(reinterpret_cast<const VinUnit*>(d_desc + o_unit), reinterpret_cast<const VinMember*>(d_desc + o_mem),
+                                                                   reinterpret_cast<const VinBlock*>(d_desc + o_blk), part);
+            k_vin_reduce<<<(unsigned)members.size(), 64, 0, st>>>(reinterpret_cast<const VinUnit*>(d_desc + o_unit), reinterpret_cast<const VinMember*>(d_desc + o_mem),
+                                                                   part, ctx->d_res);
+        }
+        if (ctx->d_res != ctx->h_res && nslot)
+            hip_check(hipMemcpyAsync(ctx->h_res, ctx->d_res, (size_t)nslot * sizeof(E2), hipMemcpyDeviceToHost, st), "hg_verify_device_batch: copy results");
+        if (times)
+            fprintf(stderr, "[hg] verify_batch: group %zu (%zu proofs): %zu eq tables, %zu constant sums, %zu + %zu gathers, %zu DFT rows, %zu dots, %zu input evaluations in %zu units (%.1f MB); %d slots\n",
+                    g, W.size(), eqs.size(), consts.size(), lins.size(), muls.size(), ffts.size(), dots.size(), members.size(), units.size(), vin_bytes / 1e6, nslot);
+        return (size_t)nslot;
+    };
+    auto complete = [&](size_t g) {
+        std::vector<Walked>& W = groups[g];
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)W.size()))
+        for (long long q = 0; q < (long long)W.size(); q++) {
+            Walked& x = W[q];
+            if (x.pend.reason.empty()) {
+                x.rec->res.resize(x.gslot.size());
+                for (size_t t = 0; t < x.gslot.size(); t++) x.rec->res[t] = ctx->h_res[x.gslot[t]];
+            }
+            why[x.idx] = verify_complete(x.pend);
+        }
+        W.clear();
+    };
+
+    stage(0);
+    walk(0);
+    double t_walk = omp_get_wtime() - t0, t_sync = 0;
+    for (size_t g = 0; g < ngroups; g++) {
+        launch(g);
+        if (g + 1 < ngroups) { const double tw = omp_get_wtime(); stage(g + 1); walk(g + 1); t_walk += omp_get_wtime() - tw; }
+        const double ts = omp_get_wtime();
+        hip_check(hipStreamSynchronize(ctx->stream), "hg_verify_device_batch: synchronise");
+        hip_check(hipGetLastError(), "hg_verify_device_batch: kernels");
+        t_sync += omp_get_wtime() - ts;
+        complete(g);
+    }
+    if (times)
+        fprintf(stderr, "[hg] verify_batch: %zu proofs in %zu groups of up to %zu: %.2f ms in all (staging and walks %.2f, waiting for the device %.2f)\n", n,
+                ngroups, G, (omp_get_wtime() - t0) * 1e3, t_walk * 1e3, t_sync * 1e3);
+}
+
+}  // namespace hg

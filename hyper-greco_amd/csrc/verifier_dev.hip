@@ -9,6 +9,7 @@
 // keeps in HBM (ctx->d_chal); in modes 1 to 3 the challenges the walk squeezed (with the absorbing transcript they depend on the proof),
 // staged into the arena at finish() ahead of the job descriptors. ctx->d_chal itself is never written: the mode-0 prover and its
 // recorded launch graphs read it.
+#include <algorithm>
 #include <cstring>
 #include <omp.h>
 #include "prover.hpp"
@@ -16,10 +17,8 @@
 namespace hg {
 namespace {
 
-// every dot product of the verification in two launches: job q = sum_i a_q[i] * b_q[i] (a: E2 table or a table of base-field
-// integers, b: an eq table), VD_BLOCKS workgroups per job, then one workgroup per job adds their partial sums into the job's slot
-constexpr int VD_BLOCKS = 32;
-struct DotJob { const void* a; const E2* b; size_t n; int slot; int a_is_u64; };
+// every dot product of the verification in two launches (DotJob: prover.hpp): VD_BLOCKS workgroups per job, then one workgroup per
+// job adds their partial sums into the job's slot
 __global__ __launch_bounds__(256) void k_vdot_jobs(const DotJob* __restrict__ jobs, E2* __restrict__ partials) {
     __shared__ E2 sm[256];
     const DotJob& J = jobs[blockIdx.y];
@@ -255,11 +254,7 @@ struct DevBackend : VerifyBackend {
         lap("DFT-row tables");
         if (d_gbs) dev::gather_B_jobs(st, d_gbs, (int)gbs.size(), gb_max);
         lap("phase-2 gathers");
-        if (d_dots) {
-            E2* part = ctx->alloc_n<E2>(dots.size() * (size_t)VD_BLOCKS);
-            k_vdot_jobs<<<dim3(VD_BLOCKS, (unsigned)dots.size()), 256, 0, st>>>(d_dots, part);
-            k_vdot_reduce<<<(unsigned)dots.size(), 64, 0, st>>>(d_dots, part, ctx->d_res);
-        }
+        if (d_dots) vdot_jobs(st, d_dots, dots.size(), ctx->alloc_n<E2>(dots.size() * (size_t)VD_BLOCKS), ctx->d_res);
         lap("dot products");
         if (ctx->d_res != ctx->h_res && res_used)
             hip_check(hipMemcpyAsync(ctx->h_res, ctx->d_res, res_used * sizeof(E2), hipMemcpyDeviceToHost, st), "verifier: copy results");
@@ -270,6 +265,14 @@ struct DevBackend : VerifyBackend {
 };
 
 }  // namespace
+
+void vdot_jobs(hipStream_t st, const DotJob* d_jobs, size_t njobs, E2* partials, E2* res) {
+    for (size_t q0 = 0; q0 < njobs; q0 += VD_MAX_Y) {   // (the job index is gridDim.y)
+        const unsigned nq = (unsigned)std::min(njobs - q0, VD_MAX_Y);
+        k_vdot_jobs<<<dim3(VD_BLOCKS, nq), 256, 0, st>>>(d_jobs + q0, partials + q0 * VD_BLOCKS);
+        k_vdot_reduce<<<nq, 64, 0, st>>>(d_jobs + q0, partials + q0 * VD_BLOCKS, res);
+    }
+}
 
 // public inputs and ct0is are uploaded (22 MB at n=32768 k=16), the proof is parsed on the host; "" = accepted
 std::string verify_proof_device(hg_ctx* ctx, const hg_pk* pk, const Witness& w, const uint8_t* proof, size_t len, int mode) {

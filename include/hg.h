@@ -75,6 +75,7 @@ void hg_destroy(hg_ctx* ctx);
  *                 values object the third is captured into a hipGraph and later ones replay it - the launch sequence depends on
  *                 addresses only, because every challenge is known up front; a values object refilled by hg_witness_gen_into
  *                 keeps its graph; up to HG_GRAPH_ENTRIES (8) graphs per context, each with a private workspace)
+ *   "verify_batch_group"  the most proofs one device pass of hg_verify_device_batch holds (default 0: sized from the arena budget)
  * Returns 0, or -1 for an unknown name. */
 int hg_set_option(hg_ctx* ctx, const char* name, int64_t value);
 
@@ -160,6 +161,15 @@ int hg_verify_device(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, const ui
  * (hg_setup(ctx, ..)). Returns 0 accept, 1 reject (reason in hg_last_error), -1 error: a null argument, a host-only key, or a mode
  * outside 0..3. */
 int hg_verify_device_mode(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, int mode, const uint8_t* proof, size_t len);
+/* hg_verify_device_mode for a run of n proofs under one key: proof i (proofs[i], lens[i]) is checked against witness ws[i] in
+ * `mode` (0..3). results[i] = 0 accepted / 1 rejected, exactly the decision hg_verify_device_mode makes for that pair.
+ * reasons (may be NULL): proof i's rejection reason, NUL-terminated and truncated to reason_cap bytes, at reasons + i*reason_cap
+ * ("" when accepted). Returns the number of rejected proofs (>= 0), or -1 on an error (hg_last_error names the function and,
+ * for an error inside one proof's check, its index). n == 0 returns 0.
+ * The walks run on the host threads, the table-sized work of a group of proofs (context option "verify_batch_group") in one
+ * launch per kind, tables that depend on the key only built once per group; the inputs of the next group are copied meanwhile. */
+int hg_verify_device_batch(hg_ctx* ctx, const hg_pk* pk, const hg_witness* const* ws, const uint8_t* const* proofs,
+                           const size_t* lens, size_t n, int mode, int* results, char* reasons, size_t reason_cap);
 
 /* The same pair in a protocol mode that FIXES the reference's two known soundness gaps. mode bits:
  *   1  absorbing transcript: write_felt / read_felt also hash the element - the rule of the in-tree plonkish-trait writer of

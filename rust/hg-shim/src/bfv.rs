@@ -11,6 +11,7 @@
 //! instead (what `get_inputs` returns, as canonical u64 limbs).
 use crate::{check, ffi::*};
 use std::ffi::CString;
+use std::os::raw::{c_char, c_int};
 use std::ptr;
 
 /// Which test family of the reference: `generate_sk_enc_test!("goldilocks", Goldilocks, GoldilocksExt2, ..)` or
@@ -135,6 +136,36 @@ impl HipBfvEncrypt {
         unsafe { hg_witness_free(w) };
         check(rc, "hg_verify_device_mode");
         assert_eq!(rc, 0, "proof rejected");
+    }
+
+    /// `verify_json_mode` for a run of (witness file, proof) pairs in one call (`hg_verify_device_batch`): the host walks run on
+    /// several threads and the table-sized work of a group of proofs in one device pass. Returns, per pair, `None` when accepted
+    /// or `Some(reason)`: the decision and reason `hg_verify_device_mode` gives that pair alone. Panics on an error.
+    pub fn verify_batch(&self, pairs: &[(&str, &[u8])], mode: i32) -> Vec<Option<String>> {
+        const CAP: usize = 256;
+        let ws: Vec<*mut HgWitness> = pairs.iter().map(|(path, _)| self.load(path, Family::Goldilocks)).collect();
+        let wp: Vec<*const HgWitness> = ws.iter().map(|w| *w as *const HgWitness).collect();
+        let proofs: Vec<*const u8> = pairs.iter().map(|(_, p)| p.as_ptr()).collect();
+        let lens: Vec<usize> = pairs.iter().map(|(_, p)| p.len()).collect();
+        let mut results = vec![0 as c_int; pairs.len()];
+        let mut reasons = vec![0 as c_char; pairs.len() * CAP];
+        let rc = unsafe {
+            hg_verify_device_batch(self.ctx, self.pk, wp.as_ptr(), proofs.as_ptr(), lens.as_ptr(), pairs.len(), mode, results.as_mut_ptr(),
+                                   reasons.as_mut_ptr(), CAP)
+        };
+        for w in ws {
+            unsafe { hg_witness_free(w) };
+        }
+        check(rc, "hg_verify_device_batch");
+        (0..pairs.len())
+            .map(|i| {
+                if results[i] == 0 {
+                    return None;
+                }
+                let r = unsafe { std::ffi::CStr::from_ptr(reasons[i * CAP..].as_ptr()) };
+                Some(r.to_string_lossy().into_owned())
+            })
+            .collect()
     }
 
     /// `prove` on tables laid out as `get_inputs` returns them (s, e, k1: 2^L; ais, r1is: k 2^L; r2is: k 2^P; ct0is: k 2^L;

@@ -1,16 +1,20 @@
 #!/usr/bin/env python3
 """The dispatches of a rocprofv3 --kernel-trace CSV that follow its longest idle gap (scripts/verify_mode_times.py --trace pauses
 between the prove and the verification), in start order: time, start relative to the first of them, grid. Then the totals.
-Usage: trace_after_gap.py <kernel_trace.csv>"""
+--last-gap-ms G: cut at the LAST idle gap longer than G ms instead (a longer idle stretch comes earlier, e.g. while
+scripts/verify_batch_times.py --trace synthesises its witnesses).
+Usage: trace_after_gap.py <kernel_trace.csv> [--last-gap-ms G]"""
 import csv
 import sys
 
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))
 ts = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows]
+last_gap = float(sys.argv[3]) * 1e6 if len(sys.argv) > 3 and sys.argv[2] == "--last-gap-ms" else None
 cut, gap, busy_until = 0, -1, ts[0][1]
 for i in range(1, len(ts)):
-    if ts[i][0] - busy_until > gap:
-        cut, gap = i, ts[i][0] - busy_until
+    g = ts[i][0] - busy_until
+    if (last_gap is None and g > gap) or (last_gap is not None and g > last_gap):
+        cut, gap = i, g
     busy_until = max(busy_until, ts[i][1])
 sel = rows[cut:]
 t0 = int(sel[0]["Start_Timestamp"])

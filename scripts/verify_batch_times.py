@@ -1,0 +1,82 @@
+#!/usr/bin/env python3
+"""Per-proof time of hg_verify_device_batch against the same proofs through hg_verify_device (hg_verify_device_mode in modes 1-3)
+one by one, in one process. For each mode: up to 16 synthetic witnesses and their proofs of that mode (a batch of B > 16 cycles
+through them); for each B of --batch, a warm-up batch call of B proofs, then the median of --reps batch calls divided by B, and
+next to it the median of --reps one-by-one passes over the same B proofs divided by B. Every decision is checked (all accepted).
+  --trace: prove 16 proofs in mode 3, pause, then ONE batch call of those 16 and nothing else (run it under rocprofv3
+           --kernel-trace --stats; scripts/trace_after_gap.py then keeps the dispatches behind the pause).
+Usage: verify_batch_times.py [n k] [--modes 0,3] [--batch 1,4,16,64] [--reps 5] [--trace]"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import __graft_entry__ as entry  # noqa: E402
+
+hg = entry.load_package()
+DISTINCT = 16
+
+
+def timed(fn):
+    t0 = time.perf_counter()
+    fn()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("n", type=int, nargs="?", default=32768)
+    ap.add_argument("k", type=int, nargs="?", default=16)
+    ap.add_argument("--modes", default="0,3")
+    ap.add_argument("--batch", default="1,4,16,64")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--trace", action="store_true")
+    a = ap.parse_args()
+    ctx = hg.Context(0)
+    bfv = hg.BfvEncrypt.new(a.n, a.k)
+    pk = bfv.setup(ctx)
+    batches = [int(b) for b in a.batch.split(",")]
+    nw = DISTINCT if a.trace else min(DISTINCT, max(batches))
+    ws = [hg.Witness.synthetic(bfv.params, 0x4752454330 + a.n + i) for i in range(nw)]
+    if a.trace:
+        ps = [bfv.prove(ctx, pk, w, cap=1 << 25, mode=3)[0] for w in ws]
+        time.sleep(3.0)   # (longer than any idle stretch of setup, witness generation and prove)
+        got = hg.verify_device_batch(ctx, pk, ws, ps, mode=3)
+        assert all(ok for ok, _ in got), got
+        print("n=%d k=%d: one mode-3 batch of %d proofs of %d bytes" % (a.n, a.k, len(ps), len(ps[0])))
+    else:
+        print("n=%d k=%d, %d distinct witnesses, median of %d after a warm-up, per proof, one process" % (a.n, a.k, nw, a.reps))
+        for mode in [int(m) for m in a.modes.split(",")]:
+            ps = [bfv.prove(ctx, pk, w, cap=1 << 25, mode=mode)[0] for w in ws]
+            for B in batches:
+                W = [ws[i % nw] for i in range(B)]
+                P = [ps[i % nw] for i in range(B)]
+
+                def batch():
+                    got = hg.verify_device_batch(ctx, pk, W, P, mode=mode)
+                    assert all(ok for ok, _ in got), got
+
+                def singles():
+                    for w, p in zip(W, P):
+                        ok, why = hg.verify_device(ctx, pk, w, p, mode=mode)
+                        assert ok, why
+                batch()
+                tb = [timed(batch) / B for _ in range(a.reps)]
+                singles()
+                ts = [timed(singles) / B for _ in range(a.reps)]
+                mb, ms = statistics.median(tb), statistics.median(ts)
+                print("mode %d B=%3d: batch %.3f ms/proof (%s); one by one %.3f ms/proof (%s); ratio %.2f" % (
+                    mode, B, mb, " ".join("%.3f" % x for x in tb), ms, " ".join("%.3f" % x for x in ts), mb / ms))
+                sys.stdout.flush()
+            os.environ["HG_TIMES"] = "verify"
+            print("mode %d, B=%d with HG_TIMES=verify:" % (mode, max(batches)), file=sys.stderr)
+            hg.verify_device_batch(ctx, pk, [ws[i % nw] for i in range(max(batches))], [ps[i % nw] for i in range(max(batches))], mode=mode)
+            del os.environ["HG_TIMES"]
+    pk.free()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
