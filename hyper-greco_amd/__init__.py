@@ -39,7 +39,7 @@ EXPORTS = [
     "hg_last_error", "hg_device_count", "hg_create", "hg_destroy", "hg_set_option", "hg_params_builtin", "hg_params_derive", "hg_grand_product", "hg_fold", "hg_setup", "hg_pk_free",
     "hg_pk_lasso_layout", "hg_pk_info", "hg_pk_node_eq_form", "hg_witness_from_json", "hg_witness_synthetic", "hg_witness_from_arrays",
     "hg_witness_get", "hg_witness_free", "hg_prove", "hg_warmup", "hg_prove_stream", "hg_verify", "hg_verify_device", "hg_verify_device_mode", "hg_verify_device_batch", "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_mle_eval",
-    "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
+    "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
 ]
 
 
@@ -784,6 +784,31 @@ def verify_device_bn254(ctx, pk, witness, proof):
     if rc < 0:
         raise HgError(lib().hg_last_error().decode())
     return rc == 0, ("" if rc == 0 else lib().hg_last_error().decode())
+
+
+def verify_device_batch_bn254(ctx, pk, witnesses, proofs, reason_cap=256):
+    """hg_verify_device_batch_bn254: BN254 proof i against witnesses[i], the run verified in device passes of a group of proofs each:
+    a list of (accepted, reason), one per proof, the decisions of verify_device_bn254(ctx, pk, witnesses[i], proofs[i])."""
+    L = lib()
+    L.hg_verify_device_batch_bn254.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
+                                               C.c_size_t, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
+    n = len(proofs)
+    if len(witnesses) != n:
+        raise ValueError("verify_device_batch_bn254: one witness per proof")
+    ws = (C.c_void_p * max(n, 1))(*[w.h.value for w in witnesses])
+    ps = (C.c_char_p * max(n, 1))(*[bytes(p) for p in proofs])
+    lens = (C.c_size_t * max(n, 1))(*[len(p) for p in proofs])
+    res = (C.c_int * max(n, 1))()
+    reasons = C.create_string_buffer(max(n, 1) * reason_cap)
+    rc = L.hg_verify_device_batch_bn254(ctx.h if ctx is not None else None, pk.h, ws, ps, lens, n, res, reasons, reason_cap)
+    if rc < 0:
+        raise HgError(lib().hg_last_error().decode())
+    raw = reasons.raw
+    out = []
+    for i in range(n):
+        r = raw[i * reason_cap:(i + 1) * reason_cap].split(b"\0", 1)[0].decode()
+        out.append((res[i] == 0, r))
+    return out
 
 
 def verify_bn254(pk, witness, proof):

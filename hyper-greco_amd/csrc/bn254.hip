@@ -20,6 +20,7 @@
 #include <functional>
 #include <memory>
 #include <map>
+#include <omp.h>
 #include "bn254_field.hpp"
 #include "bn254_wide.hpp"
 #include "bn254_lazy.hpp"
@@ -27,6 +28,7 @@
 #include "host.hpp"
 #include "prover.hpp"
 #include "kernels.hpp"
+#include "verifier_batch.hpp"
 
 namespace hg {
 namespace bn {
@@ -1856,6 +1858,7 @@ static void lasso_prove_bn254_impl(hg_ctx* ctx, const hg_pk* pk, const u64* in4,
                                    u64* claim_out, const std::function<void()>* mid = nullptr, int mid_at = 0);
 #include "bn254_gkr.inc"
 #include "bn254_verify.inc"
+#include "bn254_verify_batch.inc"
 
 // ---- LassoNode::prove_claim_reduction over Fr [REF lasso/src/lasso.rs:57-114] -------------------------------------------
 // The limb split and the counters are integer work on the low limb (fe_to_bits_le truncates to at most 63 bits,

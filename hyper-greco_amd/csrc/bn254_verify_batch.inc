@@ -1,0 +1,597 @@
+// hg_verify_device_batch_bn254: BfvEncrypt::verify::<Fr, Fr> of a run of proofs under one key in one device pass per group [REF
+// bfv-gkr/src/sk_encryption_circuit.rs:462-517, 614-626] - included by bn254.hip behind bn254_verify.inc, inside namespace hg::bn,
+// so that it launches that translation unit's BN254 job kernels. Every proof gets exactly the decision of verify_proof_device_bn254.
+// The BN254 counterpart of verifier_batch.hip, in mode 0 only (every evaluation point is a run of the fixed Fr chain):
+//   1. The walks (verifier.cpp: verify_walk_bn254) run on the host threads, one proof each, against a backend that only RECORDS the
+//      calls BnDevBackend makes (no device call, no arena or DevPool allocation: the bump allocator is not thread-safe).
+//   2. The jobs of a group are merged. Chain offsets are absolute already, so every eq table, constant-gate sum, Libra phase-1
+//      gather, DFT-row table and their dot products - they depend on the key only - are built once per group. Phase-2 gathers (they
+//      read the proof's own phase-1 evaluations) and the input evaluations (they read the proof's own witness) are never shared.
+//   3. One descriptor copy (the Fr chain in Montgomery form among the descriptors), one launch per kind through the single-proof
+//      verifier's kernels, the input evaluations (k_bn_vin_dots), one synchronisation, then every proof's deferred comparisons
+//      (verify_complete_bn254) on the host threads.
+// The public inputs are the same signed integers in the same layout as over Goldilocks: they are staged and copied by the code of
+// the Goldilocks batch (verifier_batch.hpp), so group g+1's copies and walks run while group g's kernels do.
+
+// ---- the MLE evaluations of the public inputs -------------------------------------------------------------------------------------
+// Work unit: one eq table and the P input tables evaluated at its point (mode 0: the group's tables of one input, so P is the group
+// size). A workgroup owns VBN_TILE consecutive entries: it reads its eq tile once into registers and multiply-accumulates it against
+// each of the P integer tables, one Montgomery reduction per thread and member, one partial per (member, wave): no barrier, and the
+// next member's loads are issued ahead of this member's arithmetic. A second launch adds every member's partials into its result
+// slot. HBM traffic: 8 B per input entry plus 32 / P B of eq. Resources (hipcc -Rpass-analysis=kernel-resource-usage): 230 VGPRs,
+// no scratch, 2 waves per SIMD.
+// Arithmetic (the lift of k_bn_vdot_jobs): an entry v >= 2^63 is the negative integer -(GL_P - v), so the thread accumulates
+// (GL_P - v) (r - b~) instead. Each product is below 2^63 r, a thread's VBN_ITEMS = 8 of them below 2^66 r - far inside lz_reduce's
+// 2^12 r^2. The reduction gives value R^-1 = sum z b~ R^-1 = sum z b (b~ = b R: the eq table is in Montgomery form): the PLAIN residue
+// of the thread's sum, so the partials and the slots are plain residues, canonical for the host without a conversion.
+constexpr int VBN_TPB = 256, VBN_ITEMS = 8, VBN_TILE = VBN_TPB * VBN_ITEMS, VBN_WAVES = VBN_TPB / 64;
+struct BnVinUnit { const Fr* eq; size_t n; int first, P, nblk, pad; size_t part0; };   // member p's partial of wave w of workgroup b: part0 + (p * nblk + b) * VBN_WAVES + w
+struct BnVinMember { const u64* a; int unit, slot; };
+struct BnVinBlock { int unit, blk; };
+
+__device__ __forceinline__ Fr vbn_shfl_xor(const Fr& v, int o) {
+    Fr t;
+#pragma unroll
+    for (int i = 0; i < 4; i++) t.l[i] = __shfl_xor(v.l[i], o);
+    return t;
+}
+__global__ __launch_bounds__(VBN_TPB) void k_bn_vin_dots(const BnVinUnit* __restrict__ units, const BnVinMember* __restrict__ members,
+                                                         const BnVinBlock* __restrict__ blocks, Fr* __restrict__ partials) {
+    const BnVinBlock B = blocks[blockIdx.x];
+    const BnVinUnit U = units[B.unit];
+    const size_t base = (size_t)B.blk * VBN_TILE + threadIdx.x;
+    Fr eq[VBN_ITEMS];
+#pragma unroll
+    for (int j = 0; j < VBN_ITEMS; j++) {
+        const size_t i = base + (size_t)j * VBN_TPB;
+        eq[j] = i < U.n ? U.eq[i] : fr_zero();
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    u64 v[VBN_ITEMS];
+    auto load = [&](int p, u64* out) {
+        const u64* __restrict__ a = members[U.first + p].a;
+#pragma unroll
+        for (int j = 0; j < VBN_ITEMS; j++) {
+            const size_t i = base + (size_t)j * VBN_TPB;
+            out[j] = i < U.n ? a[i] : 0;
+        }
+    };
+    load(0, v);
+    for (int p = 0; p < U.P; p++) {
+        u64 nx[VBN_ITEMS];
+        if (p + 1 < U.P) load(p + 1, nx);   // (the next member's loads are in flight under this member's arithmetic)
+        WCol w = wcol_zero();
+#pragma unroll
+        for (int j = 0; j < VBN_ITEMS; j++) {
+            const bool neg = v[j] >= (1ULL << 63);
+            wcol_mac_u64(w, neg ? GL_P - v[j] : v[j], vd_negate_if(eq[j], neg));
+        }
+        Fr s = lz_canon(lz_reduce(w));
+        for (int o = 32; o > 0; o >>= 1) s = fr_add(s, vbn_shfl_xor(s, o));
+        if (lane == 0) partials[U.part0 + ((size_t)p * U.nblk + B.blk) * VBN_WAVES + wave] = s;   // (one partial per wave: no barrier)
+#pragma unroll
+        for (int j = 0; j < VBN_ITEMS; j++) v[j] = nx[j];
+    }
+}
+// one wave per member: its unit's nblk * VBN_WAVES partials into its slot (canonical)
+__global__ __launch_bounds__(64) void k_bn_vin_reduce(const BnVinUnit* __restrict__ units, const BnVinMember* __restrict__ members,
+                                                      const Fr* __restrict__ partials, Fr* __restrict__ res) {
+    const BnVinMember M = members[blockIdx.x];
+    const BnVinUnit U = units[M.unit];
+    const size_t np = (size_t)U.nblk * VBN_WAVES;
+    const Fr* part = partials + U.part0 + (size_t)(blockIdx.x - U.first) * np;
+    Fr s = fr_zero();
+    for (size_t b = threadIdx.x; b < np; b += 64) s = fr_add(s, part[b]);
+    for (int o = 32; o > 0; o >>= 1) s = fr_add(s, vbn_shfl_xor(s, o));
+    if (threadIdx.x == 0) res[M.slot] = s;
+}
+
+namespace {
+
+// ---- the recording backend ----------------------------------------------------------------------------------------------------------
+// The same calls as BnDevBackend, kept as symbolic jobs: tables are indices into the proof's own lists, tickets are local result
+// slots. value() reads the slots the batch copied back (canonical) in Montgomery form, as BnDevBackend::value does.
+struct BnRecBackend : VerifyBackendT<Fr> {
+    const hg_pk* pk;
+    BatchInputs L;
+    struct Eq { int nvars; dev::ClaimSet cs; };
+    struct Const { int node, eqc, slot; };
+    struct Lin { int node, in, eqc; };
+    struct Mul { int node, in, eqc, eqx; size_t u_at; };
+    struct Fft { int node; dev::ClaimSet cs; };
+    enum { D_LIN, D_MUL, D_FFT };
+    struct Dot { int kind, tab, eq, slot; };
+    struct In { int k, eq, slot; };   // k < 0: ct0is
+    std::vector<Eq> eqs;
+    std::vector<Const> consts;
+    std::vector<Lin> lins;
+    std::vector<Mul> muls;
+    std::vector<Fft> ffts;
+    std::vector<Dot> dots;
+    std::vector<In> ins;
+    std::vector<Fr> us;            // phase-1 evaluations of the Vanilla nodes with a phase 2 (Montgomery, as the walk has them)
+    size_t chain_need = 0;         // one past the last chain entry a job reads
+    int nslots = 0;
+    std::vector<Fr> res;           // the results (Montgomery), filled after the group's synchronisation
+    int node = -1, eqc = -1, eqx = -1, eqy = -1;
+    size_t u_at = 0;
+    dev::ClaimSet cs;
+
+    BnRecBackend(const hg_pk* k) : pk(k), L(k->params) { memset(&cs, 0, sizeof(cs)); }
+    int slot() { return nslots++; }
+    void reads_chain(const dev::ClaimSet& c, int nvars) {
+        for (int a = 0; a < c.n; a++) chain_need = std::max(chain_need, c.point_off[a] + (size_t)nvars);
+        if (!c.unit_alpha) chain_need = std::max(chain_need, c.alpha_off + (size_t)c.n);
+    }
+    int eq_of(int nvars, const dev::ClaimSet& c) {
+        reads_chain(c, nvars);
+        eqs.push_back(Eq{nvars, c});
+        return (int)eqs.size() - 1;
+    }
+    int eq_single(int nvars, size_t off) {
+        dev::ClaimSet c;
+        memset(&c, 0, sizeof(c));
+        c.n = 1; c.unit_alpha = 1; c.point_off[0] = off;
+        return eq_of(nvars, c);
+    }
+    int dot(int kind, int tab, int eq) { const int t = slot(); dots.push_back(Dot{kind, tab, eq, t}); return t; }
+
+    void begin_node(int id, const ClaimOffs& cl) override {
+        node = id;
+        const HNode& n = pk->circuit.nodes[id];
+        if (cl.point_off.size() > (size_t)dev::MAX_CLAIMS) throw Error("verifier: too many claims on one node");
+        memset(&cs, 0, sizeof(cs));
+        cs.n = (int)cl.point_off.size();
+        cs.unit_alpha = cl.unit ? 1 : 0;
+        cs.alpha_off = cl.alpha_off;
+        for (int a = 0; a < cs.n; a++) cs.point_off[a] = cl.point_off[a];
+        eqc = n.kind == NK_VANILLA ? eq_of(n.log2_out(), cs) : -1;
+        eqx = eqy = -1;
+    }
+    int const_sum() override { const int t = slot(); consts.push_back(Const{node, eqc, t}); return t; }
+    void set_x(size_t x_off) override {
+        const HNode& n = pk->circuit.nodes[node];
+        eqx = eq_single(n.kind == NK_VANILLA ? n.log2_sub_in + n.log2_reps : n.log2_size, x_off);
+    }
+    std::vector<int> lin_terms() override {
+        const HNode& n = pk->circuit.nodes[node];
+        const hg_pk::NodeDev& nd = pk->node_dev[node];
+        std::vector<int> tk(n.arity, -1);
+        for (int i = 0; i < n.arity; i++) {
+            if (!n.left_use[i] || !nd.lin[i].ptr) continue;
+            lins.push_back(Lin{node, i, eqc});
+            tk[i] = dot(D_LIN, (int)lins.size() - 1, eqx);
+        }
+        return tk;
+    }
+    void set_y(size_t y_off, const std::vector<Fr>& u) override {
+        const HNode& n = pk->circuit.nodes[node];
+        if (n.arity > dev::PS_MAX_PAIRS) throw Error("verifier: arity too large");
+        eqy = eq_single(n.log2_sub_in + n.log2_reps, y_off);
+        u_at = us.size();
+        us.insert(us.end(), u.begin(), u.end());
+    }
+    std::vector<int> mul_terms() override {
+        const HNode& n = pk->circuit.nodes[node];
+        const hg_pk::NodeDev& nd = pk->node_dev[node];
+        std::vector<int> tk(n.arity, -1);
+        for (int i = 0; i < n.arity; i++) {
+            if (!n.right_use[i] || !nd.mulR[i].ptr) continue;
+            muls.push_back(Mul{node, i, eqc, eqx, u_at});
+            tk[i] = dot(D_MUL, (int)muls.size() - 1, eqy);
+        }
+        return tk;
+    }
+    int fft_term() override {
+        const int L2 = pk->circuit.nodes[node].log2_size;
+        if (L2 > 28) throw Error("bn254: two-adicity is 28");
+        reads_chain(cs, L2);
+        ffts.push_back(Fft{node, cs});
+        return dot(D_FFT, (int)ffts.size() - 1, eqx);
+    }
+    void end_node() override { node = -1; }
+    int mle_int(int k, size_t point_off, int nvars) {
+        if (nvars < 0 || nvars > 40 || ((size_t)1 << nvars) != L.length(k)) throw Error("verifier: claim point does not fit the input table");
+        const int t = slot();
+        ins.push_back(In{k, eq_single(nvars, point_off), t});
+        return t;
+    }
+    int mle_input(size_t k, size_t point_off, int nvars) override {
+        if (k >= 3 + 2 * L.K + 1) throw Error("verifier: no such input table");
+        return mle_int((int)k, point_off, nvars);
+    }
+    int mle_ct0is(size_t point_off, int nvars) override { return mle_int(-1, point_off, nvars); }
+    void finish() override { throw Error("verifier: a recording backend is finished by its batch"); }
+    Fr value(int t) const override { return res[t]; }
+};
+
+struct BnWalked {   // one proof of a group
+    size_t idx;
+    std::unique_ptr<BnRecBackend> rec;
+    VerifyPendingT<Fr> pend;
+    std::string error;                       // an hg::Error of the walk
+    std::vector<int> gslot;                  // local slot -> the group's result slot
+    const u64* d_in = nullptr;               // its inputs in HBM: s, e, k1, ais, r1is, r2is, ct0is
+};
+
+}  // namespace
+
+void verify_batch_device_bn254(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Witness*>& ws, const std::vector<const uint8_t*>& proofs,
+                               const std::vector<size_t>& lens, std::vector<std::string>& why) {
+    static const char* WHO = "hg_verify_device_batch_bn254";
+    const size_t n = ws.size();
+    why.assign(n, std::string());
+    if (!n) return;
+    const bool times = hg_times("verify");
+    const double t0 = omp_get_wtime();
+    hipc(hipSetDevice(ctx->device), "hipSetDevice");
+    VerifyBatchBufs* B = batch_bufs(ctx);
+    // kernels, descriptor copies and input copies may be queued on any way out (a rejection, an hg::Error): drain both streams before
+    // the caller may reuse the arena and the staging or free a witness
+    struct Drain {
+        hipStream_t a, b;
+        ~Drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); }
+    } drain{ctx->stream, B->up};
+    hipc(hipStreamSynchronize(ctx->stream), "hg_verify_device_batch_bn254: synchronise");   // (the arena is reset below)
+    const Params& p = pk->params;
+    const BatchInputs L(p);
+    const size_t words = L.words, in_bytes = words * sizeof(u64);
+    size_t G = (size_t)std::max<int64_t>(0, ctx->verify_batch_group);
+    if (!G) G = std::min(std::max<size_t>(1, VB_INPUT_BUDGET / in_bytes), VB_MAX_GROUP);
+    const size_t ngroups = (n + G - 1) / G;
+    const size_t res_cap_fr = ctx->res_cap * sizeof(E2) / sizeof(Fr);   // (result slots hold Fr here: 32 bytes each)
+    [[maybe_unused]] const int nthr = std::max(1, hg_omp_threads());   // (the device pass of hipcc ignores the pragmas)
+    std::vector<Fr> chm;   // the fixed chain in Montgomery form, as far as the walks have used it
+    auto chain_upto = [&](size_t end) {
+        if (chm.size() >= end) return;
+        const size_t have = chm.size();
+        chm.resize(end);
+        bn_chain_copy(have, end - have, chm.data() + have);
+        for (size_t q = have; q < end; q++) chm[q] = fr_to_mont(chm[q]);
+    };
+
+    std::vector<std::vector<BnWalked>> groups(ngroups);
+    auto stage = [&](size_t g) { batch_stage_inputs(B, (int)(g & 1), ws, g * G, std::min(n, g * G + G), L, nthr, WHO); };
+    auto walk = [&](size_t g) {
+        const size_t i0 = g * G, i1 = std::min(n, i0 + G);
+        std::vector<BnWalked>& W = groups[g];
+        W.resize(i1 - i0);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)W.size()))
+        for (long long q = 0; q < (long long)W.size(); q++) {
+            BnWalked& x = W[q];
+            x.idx = i0 + (size_t)q;
+            try {
+                x.rec.reset(new BnRecBackend(pk));
+                x.pend = verify_walk_bn254(*x.rec, p, pk->lasso, pk->circuit, proofs[x.idx], lens[x.idx]);
+            } catch (const std::exception& e) { x.error = e.what(); }
+        }
+        for (auto& x : W)
+            if (!x.error.empty()) throw Error(std::string(WHO) + ": proof " + std::to_string(x.idx) + ": " + x.error);
+    };
+    // merge group g's jobs and enqueue them; returns the result slots used
+    auto launch = [&](size_t g) -> size_t {
+        const int s = (int)(g & 1);
+        std::vector<BnWalked>& W = groups[g];
+        hipStream_t st = ctx->stream;
+        ctx->arena_reset();
+        struct EqG { int n; dev::ClaimSet cs; Fr* out; };
+        std::vector<EqG> eqs;
+        struct ConstG { int node, eq, slot; };
+        std::vector<ConstG> consts;
+        struct LinG { int node, in, eq; };
+        std::vector<LinG> lins;
+        struct MulG { int node, in, eqc, eqx; size_t u_at; };
+        std::vector<MulG> muls;
+        struct FftG { int node; dev::ClaimSet cs; };
+        std::vector<FftG> ffts;
+        struct DotG { int kind, tab, eq, slot; };
+        std::vector<DotG> dots;
+        struct InM { int eq; const u64* a; int slot; };
+        std::vector<InM> ins;
+        std::vector<Fr> us;   // canonical: k_bn_gather_B_jobs reads them as the prover's result slots
+        std::map<Key, int> eq_ix, const_ix, lin_ix, fft_ix, dot_ix;
+        int nslot = 0;
+        size_t chain_need = 0;
+        for (BnWalked& x : W) {
+            x.d_in = B->d_in[s] + (x.idx - g * G) * words;
+            if (!x.pend.reason.empty()) continue;   // rejected by the walk: its recorded prefix is not launched
+            BnRecBackend& R = *x.rec;
+            chain_need = std::max(chain_need, R.chain_need);
+            x.gslot.assign(R.nslots, -1);
+            auto new_slot = [&] { return nslot++; };
+            std::vector<int> geq(R.eqs.size());
+            for (size_t e = 0; e < R.eqs.size(); e++) {
+                Key k{(u64)R.eqs[e].nvars};
+                key_cs(k, R.eqs[e].cs, 0);
+                auto it = eq_ix.find(k);
+                if (it == eq_ix.end()) {
+                    eqs.push_back(EqG{R.eqs[e].nvars, R.eqs[e].cs, nullptr});
+                    it = eq_ix.emplace(k, (int)eqs.size() - 1).first;
+                }
+                geq[e] = it->second;
+            }
+            for (auto& c : R.consts) {
+                Key k{(u64)c.node, (u64)geq[c.eqc]};
+                auto it = const_ix.find(k);
+                if (it == const_ix.end()) { consts.push_back(ConstG{c.node, geq[c.eqc], new_slot()}); it = const_ix.emplace(k, (int)consts.size() - 1).first; }
+                x.gslot[c.slot] = consts[it->second].slot;
+            }
+            std::vector<int> glin(R.lins.size()), gmul(R.muls.size()), gfft(R.ffts.size());
+            for (size_t i = 0; i < R.lins.size(); i++) {
+                const auto& l = R.lins[i];
+                Key k{(u64)l.node, (u64)l.in, (u64)geq[l.eqc]};
+                auto it = lin_ix.find(k);
+                if (it == lin_ix.end()) { lins.push_back(LinG{l.node, l.in, geq[l.eqc]}); it = lin_ix.emplace(k, (int)lins.size() - 1).first; }
+                glin[i] = it->second;
+            }
+            for (size_t i = 0; i < R.muls.size(); i++) {   // (never shared: they read the proof's phase-1 evaluations)
+                const auto& m = R.muls[i];
+                muls.push_back(MulG{m.node, m.in, geq[m.eqc], geq[m.eqx], us.size() + m.u_at});
+                gmul[i] = (int)muls.size() - 1;
+            }
+            for (const Fr& u : R.us) us.push_back(fr_from_mont(u));
+            for (size_t i = 0; i < R.ffts.size(); i++) {
+                Key k{(u64)R.ffts[i].node};
+                key_cs(k, R.ffts[i].cs, 0);
+                auto it = fft_ix.find(k);
+                if (it == fft_ix.end()) { ffts.push_back(FftG{R.ffts[i].node, R.ffts[i].cs}); it = fft_ix.emplace(k, (int)ffts.size() - 1).first; }
+                gfft[i] = it->second;
+            }
+            for (auto& d : R.dots) {
+                const int tab = d.kind == BnRecBackend::D_LIN ? glin[d.tab] : d.kind == BnRecBackend::D_MUL ? gmul[d.tab] : gfft[d.tab];
+                if (d.kind == BnRecBackend::D_MUL) { dots.push_back(DotG{d.kind, tab, geq[d.eq], new_slot()}); x.gslot[d.slot] = dots.back().slot; continue; }
+                Key k{(u64)d.kind, (u64)tab, (u64)geq[d.eq]};
+                auto it = dot_ix.find(k);
+                if (it == dot_ix.end()) { dots.push_back(DotG{d.kind, tab, geq[d.eq], new_slot()}); it = dot_ix.emplace(k, (int)dots.size() - 1).first; }
+                x.gslot[d.slot] = dots[it->second].slot;
+            }
+            for (auto& in : R.ins) {   // (never shared: they read the proof's own witness)
+                const int sl = new_slot();
+                ins.push_back(InM{geq[in.eq], x.d_in + L.offset(in.k), sl});
+                x.gslot[in.slot] = sl;
+            }
+        }
+        if ((size_t)nslot > res_cap_fr)
+            throw Error(std::string(WHO) + ": a group needs " + std::to_string(nslot) + " result slots, the context has " + std::to_string(res_cap_fr) +
+                        ": lower verify_batch_group");
+        // the chain the jobs read: uploaded with the descriptors, exactly as far as the furthest job of the group reads
+        chain_upto(chain_need);
+        for (auto& e : eqs) {   // (every job reads below chain_need by construction; checked here against what is uploaded)
+            for (int a = 0; a < e.cs.n; a++)
+                if (e.cs.point_off[a] + (size_t)e.n > chm.size()) throw Error(std::string(WHO) + ": verifier: a job reads past the uploaded chain");
+            if (!e.cs.unit_alpha && e.cs.alpha_off + (size_t)e.cs.n > chm.size()) throw Error(std::string(WHO) + ": verifier: a job reads past the uploaded chain");
+        }
+        Fr* res = reinterpret_cast<Fr*>(ctx->d_res);
+        // device tables (arena) and host descriptors
+        std::vector<VeqPrep> preps;
+        std::vector<VeqFill> fills;
+        int prep_max_h = 0, fill_max_n = 0;
+        for (auto& e : eqs) {
+            e.out = ctx->alloc_n<Fr>((size_t)1 << e.n);
+            const size_t stride = veq_stride(e.n);
+            Fr* ab = ctx->alloc_n<Fr>(stride * (size_t)e.cs.n);
+            for (int a = 0; a < e.cs.n; a++) {
+                VeqPrep P;
+                memset(&P, 0, sizeof(P));
+                P.ab = ab + (size_t)a * stride; P.point_off = e.cs.point_off[a]; P.n = e.n; P.unit = e.cs.unit_alpha;
+                P.alpha_off = e.cs.alpha_off + a;
+                preps.push_back(P);
+            }
+            fills.push_back(VeqFill{e.out, ab, e.n, e.cs.n});
+            prep_max_h = std::max(prep_max_h, e.n > 8 ? e.n - 8 : 0);
+            fill_max_n = std::max(fill_max_n, e.n);
+        }
+        std::vector<BnGatherTJob> gts(lins.size());
+        std::vector<const Fr*> lin_T(lins.size()), mul_B(muls.size()), fft_F(ffts.size());
+        size_t gt_max = 0, gb_max = 0;
+        for (size_t i = 0; i < lins.size(); i++) {
+            const HNode& nd = pk->circuit.nodes[lins[i].node];
+            const size_t SR = (size_t)1 << (nd.log2_sub_in + nd.log2_reps);
+            BnGatherTJob& gj = gts[i];
+            memset(&gj, 0, sizeof(gj));
+            gj.lin = pk->node_dev[lins[i].node].lin[lins[i].in];   // (no mul part: the verifier's linear term has no input tables)
+            gj.eqc = eqs[lins[i].eq].out; gj.log2_S = nd.log2_sub_in; gj.log2_G = nd.log2_sub_out; gj.log2_R = nd.log2_reps;
+            Fr* T = ctx->alloc_n<Fr>(SR);
+            gj.T = T;
+            lin_T[i] = T;
+            gt_max = std::max(gt_max, SR);
+        }
+        std::vector<BnGatherBJob> gbs(muls.size());
+        for (size_t i = 0; i < muls.size(); i++) {
+            const MulG& m = muls[i];
+            const HNode& nd = pk->circuit.nodes[m.node];
+            const size_t SR = (size_t)1 << (nd.log2_sub_in + nd.log2_reps);
+            BnGatherBJob& bj = gbs[i];
+            memset(&bj, 0, sizeof(bj));
+            Fr* Bt = ctx->alloc_n<Fr>(SR);
+            bj.m = pk->node_dev[m.node].mulR[m.in]; bj.eqc = eqs[m.eqc].out; bj.eqx = eqs[m.eqx].out; bj.B = Bt;   // bj.fin: set below
+            for (int q = 0; q < dev::PS_MAX_PAIRS; q++) bj.us.slot[q] = q < nd.arity ? (int)(m.u_at + q) : -1;
+            bj.arity = nd.arity; bj.log2_S = nd.log2_sub_in; bj.log2_G = nd.log2_sub_out; bj.log2_R = nd.log2_reps;
+            mul_B[i] = Bt;
+            gb_max = std::max(gb_max, SR);
+        }
+        // the DFT-row tables (bn254_verify.inc fft_term): w^i tables per (size, direction), direct factors b < s1, parts over [s1, s2) and [s2, L)
+        std::map<std::pair<int, int>, Fr*> Wt;
+        std::vector<FftPartJob> fft_parts;
+        std::vector<FftTabJob> fft_tabs;
+        std::vector<FftTabClaim> fft_claims;
+        std::vector<size_t> claims_at;   // per fft_tabs entry: its first claim in fft_claims
+        size_t part_max = 0, tab_max = 0;
+        for (size_t i = 0; i < ffts.size(); i++) {
+            const HNode& nd = pk->circuit.nodes[ffts[i].node];
+            const dev::ClaimSet& c = ffts[i].cs;
+            const int L2 = nd.log2_size;
+            const size_t N = (size_t)1 << L2;
+            Fr*& Wp = Wt[{L2, (int)nd.inverse}];
+            if (!Wp) {
+                Wp = ctx->alloc_n<Fr>(N);
+                Fr wr = fr_root_of_unity(L2);
+                if (nd.inverse) wr = fr_inv(wr);
+                k_bn_powers<<<grid_of(N), 256, 0, st>>>(Wp, wr, N);
+            }
+            const Fr scale = nd.inverse ? fr_inv(fr_small((u64)N)) : fr_one_mont();
+            const int s1 = std::min(4, L2), s2 = std::min(8, L2);
+            claims_at.push_back(fft_claims.size());
+            for (int a = 0; a < c.n; a++) {
+                FftPartJob pj;
+                memset(&pj, 0, sizeof(pj));
+                for (int b = 0; b < L2; b++) pj.pt.r[b] = chm[c.point_off[a] + b];
+                pj.W = Wp; pj.L = L2;
+                FftTabClaim tc;
+                memset(&tc, 0, sizeof(tc));
+                for (int b = 0; b < s1; b++) tc.r[b] = pj.pt.r[b];
+                tc.coef = c.unit_alpha ? scale : fr_mul(chm[c.alpha_off + a], scale);
+                if (s2 > s1) { Fr* T = ctx->alloc_n<Fr>((size_t)1 << (L2 - s1)); tc.T1 = pj.T = T; pj.b_lo = s1; pj.b_hi = s2; fft_parts.push_back(pj); part_max = std::max(part_max, (size_t)1 << (L2 - s1)); }
+                if (L2 > s2) { Fr* T = ctx->alloc_n<Fr>((size_t)1 << (L2 - s2)); tc.T2 = pj.T = T; pj.b_lo = s2; pj.b_hi = L2; fft_parts.push_back(pj); part_max = std::max(part_max, (size_t)1 << (L2 - s2)); }
+                fft_claims.push_back(tc);
+            }
+            FftTabJob tj;
+            memset(&tj, 0, sizeof(tj));
+            Fr* F = ctx->alloc_n<Fr>(N);
+            tj.F = F; tj.W = Wp; tj.L = L2; tj.s1 = s1; tj.s2 = s2; tj.nclaims = c.n;   // tj.claims: set below
+            fft_tabs.push_back(tj);
+            fft_F[i] = F;
+            tab_max = std::max(tab_max, N);
+        }
+        std::vector<VdotJob> vdots(dots.size());
+        std::vector<int> blk_job;
+        for (size_t i = 0; i < dots.size(); i++) {
+            const DotG& d = dots[i];
+            VdotJob& J = vdots[i];
+            memset(&J, 0, sizeof(J));
+            J.a = d.kind == BnRecBackend::D_LIN ? lin_T[d.tab] : d.kind == BnRecBackend::D_MUL ? mul_B[d.tab] : fft_F[d.tab];
+            J.b = eqs[d.eq].out; J.n = (size_t)1 << eqs[d.eq].n; J.out = res + d.slot; J.a_is_int = 0;
+            J.blk0 = (int)blk_job.size();
+            J.nblk = (int)((J.n + VD_TILE - 1) / VD_TILE);
+            blk_job.insert(blk_job.end(), (size_t)J.nblk, (int)i);
+        }
+        std::vector<BnVinUnit> units;
+        std::vector<BnVinMember> members;
+        std::vector<BnVinBlock> blocks;
+        {
+            std::vector<std::vector<const InM*>> by_eq(eqs.size());
+            for (auto& m : ins) by_eq[m.eq].push_back(&m);
+            size_t part = 0;
+            for (size_t e = 0; e < eqs.size(); e++) {
+                if (by_eq[e].empty()) continue;
+                BnVinUnit U;
+                memset(&U, 0, sizeof(U));
+                U.eq = eqs[e].out; U.n = (size_t)1 << eqs[e].n; U.first = (int)members.size(); U.P = (int)by_eq[e].size();
+                U.nblk = (int)((U.n + VBN_TILE - 1) / VBN_TILE); U.part0 = part;
+                part += (size_t)U.P * U.nblk * VBN_WAVES;
+                for (const InM* m : by_eq[e]) members.push_back(BnVinMember{m->a, (int)units.size(), m->slot});
+                for (int b = 0; b < U.nblk; b++) blocks.push_back(BnVinBlock{(int)units.size(), b});
+                units.push_back(U);
+            }
+        }
+        size_t vin_parts = 0, vin_bytes = 0;   // (vin_bytes: what k_bn_vin_dots reads, eq tables and input tables)
+        for (auto& U : units) { vin_parts += (size_t)U.P * U.nblk * VBN_WAVES; vin_bytes += U.n * (sizeof(Fr) + (size_t)U.P * sizeof(u64)); }
+        // the chain, the phase-1 evaluations and every descriptor: one page-locked staging, one copy ahead of the launches
+        size_t desc_bytes = 0;
+        auto place = [&](size_t bytes) { const size_t o = desc_bytes; desc_bytes += (bytes + 255) & ~(size_t)255; return o; };
+        const size_t o_chain = place(chm.size() * sizeof(Fr)), o_us = place(us.size() * sizeof(Fr)), o_prep = place(preps.size() * sizeof(VeqPrep)),
+                     o_fill = place(fills.size() * sizeof(VeqFill)), o_gt = place(gts.size() * sizeof(BnGatherTJob)),
+                     o_gb = place(gbs.size() * sizeof(BnGatherBJob)), o_part = place(fft_parts.size() * sizeof(FftPartJob)),
+                     o_claim = place(fft_claims.size() * sizeof(FftTabClaim)), o_tab = place(fft_tabs.size() * sizeof(FftTabJob)),
+                     o_dot = place(vdots.size() * sizeof(VdotJob)), o_bj = place(blk_job.size() * sizeof(int)),
+                     o_unit = place(units.size() * sizeof(BnVinUnit)), o_mem = place(members.size() * sizeof(BnVinMember)),
+                     o_blk = place(blocks.size() * sizeof(BnVinBlock));
+        char* d_desc = static_cast<char*>(ctx->alloc(std::max<size_t>(desc_bytes, 1)));
+        char* h = batch_desc_host(B, std::max<size_t>(desc_bytes, 1));
+        const Fr* d_chal = reinterpret_cast<const Fr*>(d_desc + o_chain);
+        for (auto& j : gbs) j.fin = reinterpret_cast<const Fr*>(d_desc + o_us);
+        for (size_t q = 0; q < fft_tabs.size(); q++) fft_tabs[q].claims = reinterpret_cast<const FftTabClaim*>(d_desc + o_claim) + claims_at[q];
+        auto put = [&](size_t o, const auto& v) { if (!v.empty()) memcpy(h + o, v.data(), v.size() * sizeof(v[0])); };
+        put(o_chain, chm); put(o_us, us); put(o_prep, preps); put(o_fill, fills); put(o_gt, gts); put(o_gb, gbs); put(o_part, fft_parts);
+        put(o_claim, fft_claims); put(o_tab, fft_tabs); put(o_dot, vdots); put(o_bj, blk_job); put(o_unit, units); put(o_mem, members);
+        put(o_blk, blocks);
+        if (desc_bytes) hipc(hipMemcpyAsync(d_desc, h, desc_bytes, hipMemcpyHostToDevice, st), "hg_verify_device_batch_bn254: upload descriptors");
+        // one launch per kind (launchers that index their jobs by gridDim.y: launches of at most VD_MAX_Y jobs)
+        auto chunks = [](size_t njobs, auto fn) { for (size_t q0 = 0; q0 < njobs; q0 += VD_MAX_Y) fn(q0, (unsigned)std::min(VD_MAX_Y, njobs - q0)); };
+        const auto* d_prep = reinterpret_cast<const VeqPrep*>(d_desc + o_prep);
+        const auto* d_fill = reinterpret_cast<const VeqFill*>(d_desc + o_fill);
+        chunks(preps.size(), [&](size_t q0, unsigned nq) {
+            k_bn_veq_prep<<<dim3(1 + (unsigned)(((size_t)1 << prep_max_h) + 255) / 256, nq), 256, 0, st>>>(d_prep + q0, d_chal);
+        });
+        chunks(fills.size(), [&](size_t q0, unsigned nq) {
+            k_bn_veq_fill<<<dim3((unsigned)std::min<size_t>((((size_t)1 << fill_max_n) + 255) / 256, 1024), nq), 256, 0, st>>>(d_fill + q0);
+        });
+        if (!consts.empty()) {
+            Fr* d_cpart = ctx->alloc_n<Fr>(1024);   // one after the other on the stream: one partials buffer serves them all
+            for (const ConstG& c : consts) {
+                const HNode& nd = pk->circuit.nodes[c.node];
+                const hg_pk::NodeDev& dv = pk->node_dev[c.node];
+                const size_t total = dv.nconst << nd.log2_reps;
+                const int grid = (int)std::max<size_t>(1, std::min<size_t>((total + BN_TPB - 1) / BN_TPB, 1024));
+                k_bn_const_sum<<<grid, BN_TPB, 0, st>>>(dv.const_gate, dv.const_coef, dv.nconst, eqs[c.eq].out, nd.log2_sub_out, nd.log2_reps, d_cpart);
+                k_bn_reduce<<<1, BN_TPB, 0, st>>>(d_cpart, grid, 1, res + c.slot);
+            }
+        }
+        const auto* d_gt = reinterpret_cast<const BnGatherTJob*>(d_desc + o_gt);
+        chunks(gts.size(), [&](size_t q0, unsigned nq) {
+            k_bn_gather_T_jobs<<<dim3((unsigned)std::min<size_t>((gt_max + BN_TPB - 1) / BN_TPB, 2048), nq), BN_TPB, 0, st>>>(d_gt + q0);
+        });
+        const auto* d_part = reinterpret_cast<const FftPartJob*>(d_desc + o_part);
+        const auto* d_tab = reinterpret_cast<const FftTabJob*>(d_desc + o_tab);
+        chunks(fft_parts.size(), [&](size_t q0, unsigned nq) {
+            k_bn_fft_part_jobs<<<dim3((unsigned)std::min<size_t>((part_max + 255) / 256, 2048), nq), 256, 0, st>>>(d_part + q0);
+        });
+        chunks(fft_tabs.size(), [&](size_t q0, unsigned nq) {
+            k_bn_fft_tab_jobs<<<dim3((unsigned)std::min<size_t>((tab_max + 255) / 256, 2048), nq), 256, 0, st>>>(d_tab + q0);
+        });
+        const auto* d_gb = reinterpret_cast<const BnGatherBJob*>(d_desc + o_gb);
+        chunks(gbs.size(), [&](size_t q0, unsigned nq) {
+            k_bn_gather_B_jobs<<<dim3((unsigned)std::min<size_t>((gb_max + BN_TPB - 1) / BN_TPB, 2048), nq), BN_TPB, 0, st>>>(d_gb + q0);
+        });
+        if (!vdots.empty()) {   // (a flat grid: blockIdx.x, not y, indexes the tiles)
+            Fr* part = ctx->alloc_n<Fr>(blk_job.size());
+            const auto* d_dots = reinterpret_cast<const VdotJob*>(d_desc + o_dot);
+            k_bn_vdot_jobs<<<(unsigned)blk_job.size(), 256, 0, st>>>(d_dots, reinterpret_cast<const int*>(d_desc + o_bj), part);
+            k_bn_vdot_reduce<<<(unsigned)vdots.size(), 256, 0, st>>>(d_dots, part);
+        }
+        if (!units.empty()) {
+            hipc(hipStreamWaitEvent(st, B->ev[s], 0), "hg_verify_device_batch_bn254: wait for the inputs");
+            Fr* part = ctx->alloc_n<Fr>(vin_parts);
+            const auto* d_units = reinterpret_cast<const BnVinUnit*>(d_desc + o_unit);
+            const auto* d_mem = reinterpret_cast<const BnVinMember*>(d_desc + o_mem);
+            k_bn_vin_dots<<<(unsigned)blocks.size(), VBN_TPB, 0, st>>>(d_units, d_mem, reinterpret_cast<const BnVinBlock*>(d_desc + o_blk), part);
+            k_bn_vin_reduce<<<(unsigned)members.size(), 64, 0, st>>>(d_units, d_mem, part, res);
+        }
+        if (ctx->d_res != ctx->h_res && nslot)
+            hipc(hipMemcpyAsync(ctx->h_res, ctx->d_res, (size_t)nslot * sizeof(Fr), hipMemcpyDeviceToHost, st), "hg_verify_device_batch_bn254: copy results");
+        if (times)
+            fprintf(stderr, "[hg] verify_batch_bn254: group %zu (%zu proofs): %zu eq tables, %zu constant sums, %zu + %zu gathers, %zu DFT rows, %zu dots, %zu input evaluations in %zu units (%.1f MB); %d slots\n",
+                    g, W.size(), eqs.size(), consts.size(), lins.size(), muls.size(), ffts.size(), dots.size(), members.size(), units.size(), vin_bytes / 1e6, nslot);
+        return (size_t)nslot;
+    };
+    auto complete = [&](size_t g) {
+        std::vector<BnWalked>& W = groups[g];
+        const Fr* h_res = reinterpret_cast<const Fr*>(ctx->h_res);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)W.size()))
+        for (long long q = 0; q < (long long)W.size(); q++) {
+            BnWalked& x = W[q];
+            if (x.pend.reason.empty()) {
+                x.rec->res.resize(x.gslot.size());
+                for (size_t t = 0; t < x.gslot.size(); t++) x.rec->res[t] = fr_to_mont(h_res[x.gslot[t]]);
+            }
+            why[x.idx] = verify_complete_bn254(x.pend);
+        }
+        W.clear();
+    };
+
+    stage(0);
+    walk(0);
+    double t_walk = omp_get_wtime() - t0, t_sync = 0;
+    for (size_t g = 0; g < ngroups; g++) {
+        launch(g);
+        if (g + 1 < ngroups) { const double tw = omp_get_wtime(); stage(g + 1); walk(g + 1); t_walk += omp_get_wtime() - tw; }
+        const double ts = omp_get_wtime();
+        hipc(hipStreamSynchronize(ctx->stream), "hg_verify_device_batch_bn254: synchronise");
+        hipc(hipGetLastError(), "hg_verify_device_batch_bn254: kernels");
+        t_sync += omp_get_wtime() - ts;
+        complete(g);
+    }
+    if (times)
+        fprintf(stderr, "[hg] verify_batch_bn254: %zu proofs in %zu groups of up to %zu: %.2f ms in all (staging and walks %.2f, waiting for the device %.2f)\n", n,
+                ngroups, G, (omp_get_wtime() - t0) * 1e3, t_walk * 1e3, t_sync * 1e3);
+}

@@ -920,6 +920,42 @@ int hg_verify_device_bn254(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, co
     HG_CATCH(-1)
 }
 
+int hg_verify_device_batch_bn254(hg_ctx* ctx, const hg_pk* pk, const hg_witness* const* ws, const uint8_t* const* proofs, const size_t* lens, size_t n,
+                                 int* results, char* reasons, size_t reason_cap) {
+    HG_TRY
+    if (!ctx || !pk || (n && (!ws || !proofs || !lens || !results))) throw Error("hg_verify_device_batch_bn254: null argument");
+    if (!pk->ctx) throw Error("hg_verify_device_batch_bn254: needs a device prover key (hg_setup with a context)");
+    std::vector<const Witness*> W(n);
+    std::vector<const uint8_t*> P(n);
+    std::vector<size_t> N(n);
+    for (size_t i = 0; i < n; i++) {
+        if (!ws[i] || !proofs[i]) throw Error("hg_verify_device_batch_bn254: null witness or proof at index " + std::to_string(i));
+        check_witness(pk, ws[i], "hg_verify_device_batch_bn254");
+        W[i] = &ws[i]->w; P[i] = proofs[i]; N[i] = lens[i];
+    }
+    if (!n) return 0;
+    std::vector<std::string> why;
+    try {
+        hg::bn::verify_batch_device_bn254(ctx, pk, W, P, N, why);
+    } catch (const std::exception& e) {
+        const std::string m = e.what();
+        throw Error(m.rfind("hg_verify_device_batch_bn254", 0) == 0 ? m : "hg_verify_device_batch_bn254: " + m);
+    }
+    int rejected = 0;
+    for (size_t i = 0; i < n; i++) {
+        results[i] = why[i].empty() ? 0 : 1;
+        rejected += results[i];
+        if (reasons && reason_cap) {
+            char* r = reasons + i * reason_cap;
+            const size_t m = std::min(why[i].size(), reason_cap - 1);
+            memcpy(r, why[i].data(), m);
+            r[m] = 0;
+        }
+    }
+    return rejected;
+    HG_CATCH(-1)
+}
+
 int hg_circuit_eval(const hg_pk* pk, const hg_witness* w, uint64_t* lasso_in, size_t lasso_cap, uint64_t* sum_out, size_t sum_cap) {
     HG_TRY
     if (!pk || !w) throw Error("hg_circuit_eval: null argument");

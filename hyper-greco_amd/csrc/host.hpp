@@ -223,10 +223,19 @@ VerifyPending verify_walk(VerifyBackend& dev, const Params& p, const LassoPlan& 
 std::string verify_complete(VerifyPending& v);
 namespace bn { struct Fr; }
 std::string verify_proof_with_bn254(VerifyBackendT<bn::Fr>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len);
+// its two steps (hg_verify_device_batch_bn254), as verify_walk / verify_complete (mode 0: no chain is handed over)
+VerifyPendingT<bn::Fr> verify_walk_bn254(VerifyBackendT<bn::Fr>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len);
+std::string verify_complete_bn254(VerifyPendingT<bn::Fr>& v);
 // the same over bn256::Fr (F = E = Fr, 32-byte proof elements): the bn254 test family
 std::string verify_proof_bn254(const Params& p, const LassoPlan& lp, const HCircuit& c, const Witness& w, const uint8_t* proof, size_t len);
 // the same with the table-sized work on the device (bn254_verify.inc; needs a device context and a device key)
-namespace bn { std::string verify_proof_device_bn254(hg_ctx* ctx, const hg_pk* pk, const Witness& w, const uint8_t* proof, size_t len); }
+namespace bn {
+std::string verify_proof_device_bn254(hg_ctx* ctx, const hg_pk* pk, const Witness& w, const uint8_t* proof, size_t len);
+// hg_verify_device_batch_bn254 (bn254_verify_batch.inc): proof i against ws[i]; why[i] = "" accepted, else the reason. An hg::Error
+// inside one proof's walk names its index.
+void verify_batch_device_bn254(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Witness*>& ws, const std::vector<const uint8_t*>& proofs,
+                               const std::vector<size_t>& lens, std::vector<std::string>& why);
+}
 void ntt_host(u64* a, int log2n, bool inverse);  // in place, natural order
 u64 root_of_unity(int log2n);                    // 2^log2n-th root from ROOT_OF_UNITY = 7^((p-1)/2^32)
 

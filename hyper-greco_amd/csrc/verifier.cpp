@@ -709,6 +709,10 @@ std::string verify_complete(VerifyPending& v) { return complete_pending(v); }
 std::string verify_proof_with_bn254(VerifyBackendT<bn::Fr>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len) {
     return verify_with_backend<BnField>(dev, p, lp, c, proof, len, 0);
 }
+VerifyPendingT<bn::Fr> verify_walk_bn254(VerifyBackendT<bn::Fr>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len) {
+    return walk_with_backend<BnField>(dev, p, lp, c, proof, len, 0);
+}
+std::string verify_complete_bn254(VerifyPendingT<bn::Fr>& v) { return complete_pending(v); }
 
 // return "" on accept, the rejection reason otherwise
 std::string verify_proof(const Params& p, const LassoPlan& lp, const HCircuit& c, const Witness& w, const uint8_t* proof, size_t len, int mode) {

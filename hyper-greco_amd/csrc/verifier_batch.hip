@@ -17,7 +17,7 @@
 #include <map>
 #include <memory>
 #include <omp.h>
-#include "prover.hpp"
+#include "verifier_batch.hpp"
 #include "gl_wide.hpp"
 
 namespace hg {
@@ -201,45 +201,11 @@ struct RecBackend : VerifyBackend {
     E2 value(int t) const override { return res[t]; }
 };
 
-// dedup keys: the descriptor with absolute chain offsets
-typedef std::vector<u64> Key;
-void key_cs(Key& k, const dev::ClaimSet& c, size_t base) {
-    k.push_back((u64)c.n);
-    k.push_back((u64)c.unit_alpha);
-    if (!c.unit_alpha) k.push_back(c.alpha_off + base);
-    for (int a = 0; a < c.n; a++) k.push_back(c.point_off[a] + base);
-}
 dev::ClaimSet shift_cs(dev::ClaimSet c, size_t base) {
     if (!c.unit_alpha) c.alpha_off += base;
     for (int a = 0; a < c.n; a++) c.point_off[a] += base;
     return c;
 }
-
-// the context's batch buffers: two sets of a group's public inputs (page-locked and in HBM) and the stream that copies them
-struct VerifyBatchBufs {
-    hipStream_t up = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};   // the copies of set s are done
-    bool recorded[2] = {false, false};
-    u64* h_in[2] = {nullptr, nullptr};
-    u64* d_in[2] = {nullptr, nullptr};
-    size_t words[2] = {0, 0};
-    char* h_desc = nullptr;                  // page-locked descriptor staging of one group
-    size_t desc_cap = 0;
-};
-VerifyBatchBufs* batch_bufs(hg_ctx* ctx) {
-    if (!ctx->verify_batch) {
-        auto* b = new VerifyBatchBufs();
-        ctx->verify_batch = b;
-        hip_check(hipStreamCreateWithFlags(&b->up, hipStreamNonBlocking), "hipStreamCreate(batch uploads)");
-        for (auto& e : b->ev) hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate(batch uploads)");
-    }
-    return static_cast<VerifyBatchBufs*>(ctx->verify_batch);
-}
-
-// budget of one group: its inputs in one set (and, in modes 1-3, each proof's own node tables in the arena: about five times its
-// inputs, 0.13 GB at n=32768 k=16)
-constexpr size_t VB_INPUT_BUDGET = (size_t)1 << 30, VB_TABLE_BUDGET = (size_t)4 << 30;
-constexpr size_t VB_MAX_GROUP = 64;
 
 struct Walked {   // one proof of a group
     size_t idx;
@@ -251,6 +217,60 @@ struct Walked {   // one proof of a group
 };
 
 }  // namespace
+
+VerifyBatchBufs* batch_bufs(hg_ctx* ctx) {
+    if (!ctx->verify_batch) {
+        auto* b = new VerifyBatchBufs();
+        ctx->verify_batch = b;
+        hip_check(hipStreamCreateWithFlags(&b->up, hipStreamNonBlocking), "hipStreamCreate(batch uploads)");
+        for (auto& e : b->ev) hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate(batch uploads)");
+    }
+    return static_cast<VerifyBatchBufs*>(ctx->verify_batch);
+}
+
+char* batch_desc_host(VerifyBatchBufs* B, size_t bytes) {
+    if (bytes > B->desc_cap) {
+        if (B->h_desc) (void)hipHostFree(B->h_desc);
+        B->h_desc = nullptr;
+        B->desc_cap = 0;
+        hip_check(hipHostMalloc((void**)&B->h_desc, bytes, hipHostMallocDefault), "hipHostMalloc(batch descriptors)");
+        B->desc_cap = bytes;
+    }
+    return B->h_desc;
+}
+
+void batch_stage_inputs(VerifyBatchBufs* B, int s, const std::vector<const Witness*>& ws, size_t i0, size_t i1, const BatchInputs& L,
+                        [[maybe_unused]] int nthr, const char* who) {
+    const size_t np = i1 - i0, words = L.words, SZ = L.SZ, PZ = L.PZ, K = L.K;
+    const std::string w(who);
+    if (B->recorded[s]) hip_check(hipEventSynchronize(B->ev[s]), (w + ": input set reuse").c_str());
+    if (B->words[s] < np * words) {
+        if (B->h_in[s]) { (void)hipHostFree(B->h_in[s]); B->h_in[s] = nullptr; }
+        if (B->d_in[s]) { (void)hipFree(B->d_in[s]); B->d_in[s] = nullptr; }
+        B->words[s] = 0;
+        hip_check(hipHostMalloc((void**)&B->h_in[s], np * words * sizeof(u64), hipHostMallocDefault), "hipHostMalloc(batch inputs)");
+        hip_check(hipMalloc((void**)&B->d_in[s], np * words * sizeof(u64)), "hipMalloc(batch inputs)");
+        B->words[s] = np * words;
+    }
+    struct Piece { u64* dst; const u64* src; size_t n; };
+    std::vector<Piece> pieces;
+    constexpr size_t PIECE = (size_t)1 << 18;   // 2 MB
+    for (size_t i = i0; i < i1; i++) {
+        const Witness& x = *ws[i];
+        u64* dst = B->h_in[s] + (i - i0) * words;
+        const std::pair<const u64*, size_t> tabs[] = {{x.s.data(), SZ}, {x.e.data(), SZ}, {x.k1.data(), SZ}, {x.ais.data(), K * SZ},
+                                                      {x.r1is.data(), K * SZ}, {x.r2is.data(), K * PZ}, {x.ct0is.data(), K * SZ}};
+        for (auto& t : tabs) {
+            for (size_t o = 0; o < t.second; o += PIECE) pieces.push_back(Piece{dst + o, t.first + o, std::min(PIECE, t.second - o)});
+            dst += t.second;
+        }
+    }
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)pieces.size()))
+    for (long long q = 0; q < (long long)pieces.size(); q++) memcpy(pieces[q].dst, pieces[q].src, pieces[q].n * sizeof(u64));
+    hip_check(hipMemcpyAsync(B->d_in[s], B->h_in[s], np * words * sizeof(u64), hipMemcpyHostToDevice, B->up), (w + ": upload inputs").c_str());
+    hip_check(hipEventRecord(B->ev[s], B->up), "hipEventRecord");
+    B->recorded[s] = true;
+}
 
 void verify_batch_drop(hg_ctx* ctx) {
     if (!ctx->verify_batch) return;
@@ -282,9 +302,9 @@ void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const W
     hip_check(hipStreamSynchronize(ctx->stream), "hg_verify_device_batch: synchronise");   // (the arena is reset below)
     ctx->ensure_chain(16384);
     const Params& p = pk->params;
-    const size_t SZ = p.SZ(), PZ = p.PZ(), K = (size_t)p.k;
     // one proof's inputs in HBM, in the order of verify_proof_device: s, e, k1, ais (k), r1is (k), r2is, then ct0is
-    const size_t words = (3 + 3 * K) * SZ + K * PZ;
+    const BatchInputs L(p);
+    const size_t words = L.words;
     const size_t in_bytes = words * sizeof(u64);
     size_t G = (size_t)std::max<int64_t>(0, ctx->verify_batch_group);
     if (!G) {
@@ -297,37 +317,7 @@ void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const W
 
     std::vector<std::vector<Walked>> groups(ngroups);
     // stage group g: gather its inputs into page-locked set g & 1 (host threads), copy them on the upload stream
-    auto stage = [&](size_t g) {
-        const int s = (int)(g & 1);
-        const size_t i0 = g * G, i1 = std::min(n, i0 + G), np = i1 - i0;
-        if (B->recorded[s]) hip_check(hipEventSynchronize(B->ev[s]), "hg_verify_device_batch: input set reuse");
-        if (B->words[s] < np * words) {
-            if (B->h_in[s]) { (void)hipHostFree(B->h_in[s]); B->h_in[s] = nullptr; }
-            if (B->d_in[s]) { (void)hipFree(B->d_in[s]); B->d_in[s] = nullptr; }
-            B->words[s] = 0;
-            hip_check(hipHostMalloc((void**)&B->h_in[s], np * words * sizeof(u64), hipHostMallocDefault), "hipHostMalloc(batch inputs)");
-            hip_check(hipMalloc((void**)&B->d_in[s], np * words * sizeof(u64)), "hipMalloc(batch inputs)");
-            B->words[s] = np * words;
-        }
-        struct Piece { u64* dst; const u64* src; size_t n; };
-        std::vector<Piece> pieces;
-        constexpr size_t PIECE = (size_t)1 << 18;   // 2 MB
-        for (size_t i = i0; i < i1; i++) {
-            const Witness& w = *ws[i];
-            u64* dst = B->h_in[s] + (i - i0) * words;
-            const std::pair<const u64*, size_t> tabs[] = {{w.s.data(), SZ}, {w.e.data(), SZ}, {w.k1.data(), SZ}, {w.ais.data(), K * SZ},
-                                                          {w.r1is.data(), K * SZ}, {w.r2is.data(), K * PZ}, {w.ct0is.data(), K * SZ}};
-            for (auto& t : tabs) {
-                for (size_t o = 0; o < t.second; o += PIECE) pieces.push_back(Piece{dst + o, t.first + o, std::min(PIECE, t.second - o)});
-                dst += t.second;
-            }
-        }
-#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)pieces.size()))
-        for (long long q = 0; q < (long long)pieces.size(); q++) memcpy(pieces[q].dst, pieces[q].src, pieces[q].n * sizeof(u64));
-        hip_check(hipMemcpyAsync(B->d_in[s], B->h_in[s], np * words * sizeof(u64), hipMemcpyHostToDevice, B->up), "hg_verify_device_batch: upload inputs");
-        hip_check(hipEventRecord(B->ev[s], B->up), "hipEventRecord");
-        B->recorded[s] = true;
-    };
+    auto stage = [&](size_t g) { batch_stage_inputs(B, (int)(g & 1), ws, g * G, std::min(n, g * G + G), L, nthr, "hg_verify_device_batch"); };
     // walk group g on the host threads
     auto walk = [&](size_t g) {
         const size_t i0 = g * G, i1 = std::min(n, i0 + G);
@@ -438,13 +428,8 @@ void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const W
                 x.gslot[d.slot] = dots[it->second].slot;
             }
             for (auto& in : R.ins) {   // (never shared: they read the proof's own witness)
-                size_t off;
-                if (in.k < 0) off = (3 + 2 * K) * SZ + K * PZ;
-                else if (in.k < 3) off = (size_t)in.k * SZ;
-                else if ((size_t)in.k < 3 + 2 * K) off = (size_t)in.k * SZ;   // ais then r1is, SZ each
-                else off = (3 + 2 * K) * SZ;                                  // r2is
                 const int sl = new_slot();
-                ins.push_back(InM{geq[in.eq], x.d_in + off, sl});
+                ins.push_back(InM{geq[in.eq], x.d_in + L.offset(in.k), sl});
                 x.gslot[in.slot] = sl;
             }
         }
@@ -500,14 +485,7 @@ void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const W
                      o_unit = place(units.size() * sizeof(VinUnit)), o_mem = place(members.size() * sizeof(VinMember)),
                      o_blk = place(blocks.size() * sizeof(VinBlock));
         char* d_desc = static_cast<char*>(ctx->alloc(desc_bytes));
-        if (desc_bytes > B->desc_cap) {
-            if (B->h_desc) (void)hipHostFree(B->h_desc);
-            B->h_desc = nullptr;
-            B->desc_cap = 0;
-            hip_check(hipHostMalloc((void**)&B->h_desc, desc_bytes, hipHostMallocDefault), "hipHostMalloc(batch descriptors)");
-            B->desc_cap = desc_bytes;
-        }
-        char* h = B->h_desc;
+        char* h = batch_desc_host(B, desc_bytes);
         const E2* chal = mode != 0 ? reinterpret_cast<const E2*>(d_desc + o_chain) : ctx->d_chal;
         const E2* d_us = reinterpret_cast<const E2*>(d_desc + o_us);
         if (!chain.empty()) memcpy(h + o_chain, chain.data(), chain.size() * sizeof(E2));

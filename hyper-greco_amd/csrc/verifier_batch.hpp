@@ -1,0 +1,59 @@
+// What the two batched device verifiers share (verifier_batch.hip: hg_verify_device_batch over Goldilocks; bn254_verify_batch.inc:
+// hg_verify_device_batch_bn254 over bn256::Fr): the context's input sets and upload stream, the layout of one proof's public inputs
+// in a set, the default group size, and the staging of a group's inputs.
+#pragma once
+#include <string>
+#include <vector>
+#include "kernels.hpp"
+#include "prover.hpp"
+
+namespace hg {
+
+// the context's batch buffers: two sets of a group's public inputs (page-locked and in HBM) and the stream that copies them
+struct VerifyBatchBufs {
+    hipStream_t up = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};   // the copies of set s are done
+    bool recorded[2] = {false, false};
+    u64* h_in[2] = {nullptr, nullptr};
+    u64* d_in[2] = {nullptr, nullptr};
+    size_t words[2] = {0, 0};
+    char* h_desc = nullptr;                  // page-locked descriptor staging of one group
+    size_t desc_cap = 0;
+};
+VerifyBatchBufs* batch_bufs(hg_ctx* ctx);
+// the page-locked descriptor staging, grown to `bytes` (call it only after the previous group's copy has been waited for)
+char* batch_desc_host(VerifyBatchBufs* B, size_t bytes);
+
+// one proof's public inputs in a set, in the order of the single-proof verifiers: s, e, k1, ais (k), r1is (k), r2is, then ct0is -
+// the same signed integers in the same layout over both fields
+struct BatchInputs {
+    size_t SZ, PZ, K, words;
+    explicit BatchInputs(const Params& p) : SZ(p.SZ()), PZ(p.PZ()), K((size_t)p.k), words((3 + 3 * K) * SZ + K * PZ) {}
+    size_t offset(int k) const {   // the verifier's input table k (k < 0: ct0is)
+        if (k < 0) return (3 + 2 * K) * SZ + K * PZ;
+        if ((size_t)k < 3 + 2 * K) return (size_t)k * SZ;   // s, e, k1, then ais and r1is, SZ each
+        return (3 + 2 * K) * SZ;                           // r2is
+    }
+    size_t length(int k) const { return k < 0 ? K * SZ : (size_t)k == 3 + 2 * K ? K * PZ : SZ; }
+};
+
+// budget of one group: its inputs in one set (and, in modes 1-3 of the Goldilocks batch, each proof's own node tables in the arena:
+// about five times its inputs, 0.13 GB at n=32768 k=16)
+constexpr size_t VB_INPUT_BUDGET = (size_t)1 << 30, VB_TABLE_BUDGET = (size_t)4 << 30;
+constexpr size_t VB_MAX_GROUP = 64;
+
+// dedup keys of the group merge: a job's descriptor with absolute chain offsets
+typedef std::vector<u64> Key;
+inline void key_cs(Key& k, const dev::ClaimSet& c, size_t base) {
+    k.push_back((u64)c.n);
+    k.push_back((u64)c.unit_alpha);
+    if (!c.unit_alpha) k.push_back(c.alpha_off + base);
+    for (int a = 0; a < c.n; a++) k.push_back(c.point_off[a] + base);
+}
+
+// gathers the inputs of proofs [i0, i1) into page-locked set `set` on the host threads (at most nthr) and copies them on the
+// upload stream; the set's event marks the copy. `who` prefixes the error messages.
+void batch_stage_inputs(VerifyBatchBufs* B, int set, const std::vector<const Witness*>& ws, size_t i0, size_t i1, const BatchInputs& L,
+                        int nthr, const char* who);
+
+}  // namespace hg

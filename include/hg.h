@@ -75,7 +75,8 @@ void hg_destroy(hg_ctx* ctx);
  *                 values object the third is captured into a hipGraph and later ones replay it - the launch sequence depends on
  *                 addresses only, because every challenge is known up front; a values object refilled by hg_witness_gen_into
  *                 keeps its graph; up to HG_GRAPH_ENTRIES (8) graphs per context, each with a private workspace)
- *   "verify_batch_group"  the most proofs one device pass of hg_verify_device_batch holds (default 0: sized from the arena budget)
+ *   "verify_batch_group"  the most proofs one device pass of hg_verify_device_batch or hg_verify_device_batch_bn254 holds
+ *                 (default 0: sized from the memory budget, at most 64)
  * Returns 0, or -1 for an unknown name. */
 int hg_set_option(hg_ctx* ctx, const char* name, int64_t value);
 
@@ -377,6 +378,16 @@ int hg_verify_bn254(const hg_pk* pk, const hg_witness* w, const uint8_t* proof, 
  * kernels over bn256::Fr (one stream, one synchronisation). Needs a device context and a device key (hg_setup(ctx, ..)). Same return
  * values and the same accept / reject decisions as hg_verify_bn254; mode 0 only. */
 int hg_verify_device_bn254(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, const uint8_t* proof, size_t len);
+/* hg_verify_device_bn254 for a run of n proofs under one key: the contract of hg_verify_device_batch without a mode (BN254 is mode 0
+ * only). results[i] = 0 accepted / 1 rejected, exactly the decision hg_verify_device_bn254 (and hg_verify_bn254) makes for
+ * (ws[i], proofs[i]); reasons (may be NULL) receives the reason that call leaves in hg_last_error, NUL-terminated and truncated to
+ * reason_cap bytes, at reasons + i*reason_cap ("" when accepted). Returns the number of rejected proofs (>= 0), or -1 on an error
+ * (hg_last_error names the function and, for an error inside one proof's check, its index). n == 0 returns 0. Needs a device
+ * context and a device key. The walks run on the host threads; the table-sized work of a group of proofs (context option
+ * "verify_batch_group") runs in one launch per kind, tables that depend on the key only built once per group; the inputs of the
+ * next group are copied meanwhile. */
+int hg_verify_device_batch_bn254(hg_ctx* ctx, const hg_pk* pk, const hg_witness* const* ws, const uint8_t* const* proofs,
+                                 const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap);
 
 /* profiling: level 0 off, 1 = events around the selected kernel class only, 2 = every class */
 int hg_profile(hg_ctx* ctx, int level);

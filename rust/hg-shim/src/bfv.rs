@@ -168,6 +168,35 @@ impl HipBfvEncrypt {
             .collect()
     }
 
+    /// `verify_batch` for the bn254 family (`hg_verify_device_batch_bn254`, mode 0 only): per (witness file, proof) pair, `None`
+    /// when accepted or `Some(reason)`, the decision and reason `hg_verify_device_bn254` gives that pair alone. Panics on an error.
+    pub fn verify_batch_bn254(&self, pairs: &[(&str, &[u8])]) -> Vec<Option<String>> {
+        const CAP: usize = 256;
+        let ws: Vec<*mut HgWitness> = pairs.iter().map(|(path, _)| self.load(path, Family::Bn254)).collect();
+        let wp: Vec<*const HgWitness> = ws.iter().map(|w| *w as *const HgWitness).collect();
+        let proofs: Vec<*const u8> = pairs.iter().map(|(_, p)| p.as_ptr()).collect();
+        let lens: Vec<usize> = pairs.iter().map(|(_, p)| p.len()).collect();
+        let mut results = vec![0 as c_int; pairs.len()];
+        let mut reasons = vec![0 as c_char; pairs.len() * CAP];
+        let rc = unsafe {
+            hg_verify_device_batch_bn254(self.ctx, self.pk, wp.as_ptr(), proofs.as_ptr(), lens.as_ptr(), pairs.len(), results.as_mut_ptr(),
+                                         reasons.as_mut_ptr(), CAP)
+        };
+        for w in ws {
+            unsafe { hg_witness_free(w) };
+        }
+        check(rc, "hg_verify_device_batch_bn254");
+        (0..pairs.len())
+            .map(|i| {
+                if results[i] == 0 {
+                    return None;
+                }
+                let r = unsafe { std::ffi::CStr::from_ptr(reasons[i * CAP..].as_ptr()) };
+                Some(r.to_string_lossy().into_owned())
+            })
+            .collect()
+    }
+
     /// `prove` on tables laid out as `get_inputs` returns them (s, e, k1: 2^L; ais, r1is: k 2^L; r2is: k 2^P; ct0is: k 2^L;
     /// canonical Goldilocks u64 values) [REF sk_encryption_circuit.rs:365-415]
     #[allow(clippy::too_many_arguments)]

@@ -3,9 +3,10 @@
 one by one, in one process. For each mode: up to 16 synthetic witnesses and their proofs of that mode (a batch of B > 16 cycles
 through them); for each B of --batch, a warm-up batch call of B proofs, then the median of --reps batch calls divided by B, and
 next to it the median of --reps one-by-one passes over the same B proofs divided by B. Every decision is checked (all accepted).
-  --trace: prove 16 proofs in mode 3, pause, then ONE batch call of those 16 and nothing else (run it under rocprofv3
+  --field bn254: the same for hg_verify_device_batch_bn254 against hg_verify_device_bn254 (proofs of hg_prove_bn254, mode 0 only).
+  --trace: prove 16 proofs in mode 3 (bn254: mode 0), pause, then ONE batch call of those 16 and nothing else (run it under rocprofv3
            --kernel-trace --stats; scripts/trace_after_gap.py then keeps the dispatches behind the pause).
-Usage: verify_batch_times.py [n k] [--modes 0,3] [--batch 1,4,16,64] [--reps 5] [--trace]"""
+Usage: verify_batch_times.py [n k] [--field goldilocks|bn254] [--modes 0,3] [--batch 1,4,16,64] [--reps 5] [--trace]"""
 import argparse
 import os
 import statistics
@@ -33,7 +34,20 @@ def main():
     ap.add_argument("--batch", default="1,4,16,64")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--field", choices=("goldilocks", "bn254"), default="goldilocks")
     a = ap.parse_args()
+    bn = a.field == "bn254"
+    if bn:
+        a.modes = "0"
+
+    def prove(w, mode):
+        return ctx.prove_bn254(pk, w, cap=1 << 25)[0] if bn else bfv.prove(ctx, pk, w, cap=1 << 25, mode=mode)[0]
+
+    def verify_batch(W, P, mode):
+        return hg.verify_device_batch_bn254(ctx, pk, W, P) if bn else hg.verify_device_batch(ctx, pk, W, P, mode=mode)
+
+    def verify_one(w, p, mode):
+        return hg.verify_device_bn254(ctx, pk, w, p) if bn else hg.verify_device(ctx, pk, w, p, mode=mode)
     ctx = hg.Context(0)
     bfv = hg.BfvEncrypt.new(a.n, a.k)
     pk = bfv.setup(ctx)
@@ -41,26 +55,27 @@ def main():
     nw = DISTINCT if a.trace else min(DISTINCT, max(batches))
     ws = [hg.Witness.synthetic(bfv.params, 0x4752454330 + a.n + i) for i in range(nw)]
     if a.trace:
-        ps = [bfv.prove(ctx, pk, w, cap=1 << 25, mode=3)[0] for w in ws]
+        mode = 0 if bn else 3
+        ps = [prove(w, mode) for w in ws]
         time.sleep(3.0)   # (longer than any idle stretch of setup, witness generation and prove)
-        got = hg.verify_device_batch(ctx, pk, ws, ps, mode=3)
+        got = verify_batch(ws, ps, mode)
         assert all(ok for ok, _ in got), got
-        print("n=%d k=%d: one mode-3 batch of %d proofs of %d bytes" % (a.n, a.k, len(ps), len(ps[0])))
+        print("n=%d k=%d %s: one mode-%d batch of %d proofs of %d bytes" % (a.n, a.k, a.field, mode, len(ps), len(ps[0])))
     else:
-        print("n=%d k=%d, %d distinct witnesses, median of %d after a warm-up, per proof, one process" % (a.n, a.k, nw, a.reps))
+        print("n=%d k=%d %s, %d distinct witnesses, median of %d after a warm-up, per proof, one process" % (a.n, a.k, a.field, nw, a.reps))
         for mode in [int(m) for m in a.modes.split(",")]:
-            ps = [bfv.prove(ctx, pk, w, cap=1 << 25, mode=mode)[0] for w in ws]
+            ps = [prove(w, mode) for w in ws]
             for B in batches:
                 W = [ws[i % nw] for i in range(B)]
                 P = [ps[i % nw] for i in range(B)]
 
                 def batch():
-                    got = hg.verify_device_batch(ctx, pk, W, P, mode=mode)
+                    got = verify_batch(W, P, mode)
                     assert all(ok for ok, _ in got), got
 
                 def singles():
                     for w, p in zip(W, P):
-                        ok, why = hg.verify_device(ctx, pk, w, p, mode=mode)
+                        ok, why = verify_one(w, p, mode)
                         assert ok, why
                 batch()
                 tb = [timed(batch) / B for _ in range(a.reps)]
@@ -72,7 +87,7 @@ def main():
                 sys.stdout.flush()
             os.environ["HG_TIMES"] = "verify"
             print("mode %d, B=%d with HG_TIMES=verify:" % (mode, max(batches)), file=sys.stderr)
-            hg.verify_device_batch(ctx, pk, [ws[i % nw] for i in range(max(batches))], [ps[i % nw] for i in range(max(batches))], mode=mode)
+            verify_batch([ws[i % nw] for i in range(max(batches))], [ps[i % nw] for i in range(max(batches))], mode)
             del os.environ["HG_TIMES"]
     pk.free()
     ctx.close()
