@@ -37,7 +37,7 @@ class HgKernelStat(C.Structure):
 
 EXPORTS = [
     "hg_last_error", "hg_device_count", "hg_create", "hg_destroy", "hg_set_option", "hg_params_builtin", "hg_params_derive", "hg_grand_product", "hg_fold", "hg_setup", "hg_pk_free",
-    "hg_pk_lasso_layout", "hg_pk_info", "hg_pk_node_eq_form", "hg_witness_from_json", "hg_witness_synthetic", "hg_witness_from_arrays",
+    "hg_pk_lasso_layout", "hg_pk_info", "hg_pk_node_eq_form", "hg_witness_from_json", "hg_witness_synthetic", "hg_witness_from_arrays", "hg_witness_derive", "hg_witness_derive_into",
     "hg_witness_get", "hg_witness_free", "hg_prove", "hg_warmup", "hg_prove_stream", "hg_verify", "hg_verify_device", "hg_verify_device_mode", "hg_verify_device_batch", "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_mle_eval",
     "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
 ]
@@ -340,6 +340,24 @@ class Witness:
         _check(lib().hg_witness_from_arrays(C.byref(params), *[_ptr(a) for a in arrs], C.byref(h)))
         return cls(h, params)
 
+    @staticmethod
+    def _derive_inputs(params, d):
+        arrs = [np.ascontiguousarray(d[f], dtype=np.uint64) for f in ("s", "e", "k1", "ais")]
+        sz = 2 * params.n
+        if [a.size for a in arrs] != [sz, sz, sz, params.k * sz]:
+            raise ValueError("derive: s, e, k1 hold 2n words and ais k * 2n")
+        return arrs
+
+    @classmethod
+    def derive(cls, ctx, params, d):
+        """hg_witness_derive: ct0is, r2is, r1is from the laid-out tables d['s'], d['e'], d['k1'], d['ais'] on the device."""
+        h = C.c_void_p()
+        arrs = cls._derive_inputs(params, d)
+        L = lib()
+        L.hg_witness_derive.argtypes = [C.c_void_p, C.POINTER(HgParams)] + [u64p] * 4 + [C.POINTER(C.c_void_p)]
+        _check(L.hg_witness_derive(ctx.h if ctx is not None else None, C.byref(params), *[_ptr(a) for a in arrs], C.byref(h)))
+        return cls(h, params)
+
     def arrays(self):
         out = {}
         for i, f in enumerate(self.FIELDS):
@@ -505,6 +523,19 @@ def witness_gen_into(ctx, pk, witness, values):
     _check(lib().hg_witness_gen_into(ctx.h, pk.h, witness.h, values.h, C.byref(tm)))
     values.timings = {f: getattr(tm, f) for f, _ in HgTimings._fields_}
     return values
+
+
+def witness_derive_into(ctx, pk, d, values):
+    """hg_witness_derive_into: derives the witness of d['s'], d['e'], d['k1'], d['ais'] straight into the resident tables of `values`
+    and evaluates the circuit behind it; returns the host handle (Witness). values.timings holds total_ms and gpu_ms."""
+    h = C.c_void_p()
+    tm = HgTimings()
+    arrs = Witness._derive_inputs(pk.params, d)
+    L = lib()
+    L.hg_witness_derive_into.argtypes = [C.c_void_p, C.c_void_p] + [u64p] * 4 + [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(HgTimings)]
+    _check(L.hg_witness_derive_into(ctx.h if ctx is not None else None, pk.h, *[_ptr(a) for a in arrs], values.h, C.byref(h), C.byref(tm)))
+    values.timings = {f: getattr(tm, f) for f, _ in HgTimings._fields_}
+    return Witness(h, pk.params)
 
 
 class ProofBuffer:

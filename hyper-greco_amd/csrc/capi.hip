@@ -476,6 +476,35 @@ int hg_witness_from_arrays(const hg_params* params, const uint64_t* s, const uin
     HG_CATCH(-1)
 }
 
+int hg_witness_derive(hg_ctx* ctx, const hg_params* params, const uint64_t* s, const uint64_t* e, const uint64_t* k1, const uint64_t* ais,
+                      hg_witness** w) {
+    HG_TRY
+    if (w) *w = nullptr;
+    if (!ctx) throw Error("hg_witness_derive: needs a device context (the derivation runs on the GPU and has no host fallback)");
+    if (!params || !s || !e || !k1 || !ais || !w) throw Error("hg_witness_derive: null argument");
+    Params p(*params);
+    std::unique_ptr<hg_witness> hw(new hg_witness{witness_derive(ctx, p, s, e, k1, ais), *params});
+    *w = hw.release();
+    return 0;
+    HG_CATCH(-1)
+}
+
+int hg_witness_derive_into(hg_ctx* ctx, const hg_pk* pk, const uint64_t* s, const uint64_t* e, const uint64_t* k1, const uint64_t* ais,
+                           hg_values* v, hg_witness** w, hg_timings* timings) {
+    HG_TRY
+    if (w) *w = nullptr;
+    if (!ctx) throw Error("hg_witness_derive_into: needs a device context (the derivation runs on the GPU and has no host fallback)");
+    if (!pk || !s || !e || !k1 || !ais || !v) throw Error("hg_witness_derive_into: null argument");
+    if (!pk->ctx) throw Error("hg_witness_derive_into: host-only prover key (created without a context)");
+    double total = 0, gpu = 0;
+    Witness host;
+    witness_derive_into(ctx, pk, s, e, k1, ais, v, w ? &host : nullptr, &total, timings ? &gpu : nullptr);
+    if (w) *w = new hg_witness{std::move(host), pk->params.raw};
+    if (timings) { memset(timings, 0, sizeof(*timings)); timings->witness_ms = total; timings->total_ms = total; timings->gpu_ms = gpu; }
+    return 0;
+    HG_CATCH(-1)
+}
+
 int64_t hg_witness_get(const hg_witness* w, int which, uint64_t* out, size_t cap) {
     if (!w) { g_last_error = "hg_witness_get: null witness"; return -1; }
     const std::vector<u64>* v = nullptr;

@@ -11,6 +11,7 @@
 #include <type_traits>
 #include "kernels.hpp"
 #include "gl_wide.hpp"
+#include "derive_math.hpp"
 
 namespace hg {
 namespace dev {
@@ -3295,6 +3296,106 @@ void ntt_batch(hipStream_t st, u64* data, int log2n, size_t batch, const u64* W,
     int grid = (int)std::min<size_t>((total + TPB - 1) / TPB, 4096);
     for (int s = log2n - 1; s >= 0; s--) k_ntt_stage<<<grid, TPB, 0, st>>>(data, log2n, s, batch, W);
     k_ntt_bitrev<<<grid * 2, TPB, 0, st>>>(data, log2n, batch, scale);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Witness derivation (kernels.hpp): streaming kernels around the batched NTTs. Table positions are those of get_inputs
+// (sk_encryption_circuit.rs:365-415): s, a_i: coefficient j at n-1-j; e, k1, r1_i, ct0_i: at 2n-2-j; r2_i: at n-2-j.
+// DeriveArgs travels as a kernel argument (about 1.6 KB of the 4 KB a launch may carry).
+static_assert(sizeof(DeriveArgs) <= 2048, "DeriveArgs is passed by value: keep it well inside the kernel-argument limit");
+__device__ __forceinline__ void derive_flag(u32* flags, int table, int mod, u32 bits) {
+    if (bits) atomicOr(&flags[table * DRV_MAX_K + mod], bits);
+}
+__device__ __forceinline__ u64 derive_mag(int64_t z) { return z < 0 ? (u64)0 - (u64)z : (u64)z; }
+__device__ __forceinline__ u32 derive_check(u64 w, bool holds_coefficient, u64 bound) {
+    if (w >= GL_P) return DRV_NONCANONICAL;
+    if (!holds_coefficient) return w ? DRV_PADDING : 0;
+    return derive_mag(drv::gl_signed(w)) > bound ? DRV_BOUND : 0;
+}
+// blockIdx.y == 0: s (-> X[0]), e, k1; blockIdx.y == i + 1: a_i (-> X[1 + 2i] = lo, X[2 + 2i] = hi). One thread per table position.
+__global__ __launch_bounds__(TPB) void k_derive_unpack(DeriveArgs A) {
+    const size_t n = (size_t)1 << A.n_log2, N = 2 * n;
+    const size_t m = (size_t)blockIdx.x * TPB + threadIdx.x;
+    if (m >= N) return;
+    if (blockIdx.y == 0) {
+        const u64 ws = A.s[m];
+        derive_flag(A.flags, 0, 0, derive_check(ws, m < n, A.s_bound));
+        if (m < n) A.X[n - 1 - m] = ws; else A.X[m] = 0;
+        const bool mid = m + 1 >= n && m + 1 < N;   // e, k1: coefficients at n-1 .. 2n-2
+        derive_flag(A.flags, 1, 0, derive_check(A.e[m], mid, A.e_bound));
+        derive_flag(A.flags, 2, 0, derive_check(A.k1[m], mid, A.k1_bound));
+        return;
+    }
+    const int i = (int)blockIdx.y - 1;
+    const u64 w = A.ais[i][m];
+    derive_flag(A.flags, 3, i, derive_check(w, m < n, A.mod[i].half));
+    u64* lo = A.X + (size_t)(1 + 2 * i) * N;
+    u64* hi = lo + N;
+    if (m < n) {
+        const int64_t z = drv::gl_signed(w);
+        lo[n - 1 - m] = (u64)z & 0xFFFFFFFFULL;
+        hi[n - 1 - m] = drv::gl_assign(z >> 32);
+    } else {
+        lo[m] = 0; hi[m] = 0;
+    }
+}
+__global__ __launch_bounds__(TPB) void k_derive_mul(u64* __restrict__ X, int log2_len) {
+    const size_t N = (size_t)1 << log2_len;
+    const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+    if (i >= N) return;
+    u64* v = X + ((size_t)blockIdx.y + 1) * N;
+    v[i] = gl_mul(v[i], X[i]);
+}
+// One thread per (modulus blockIdx.y, j < n): h[j] and h[j+n] from the four product words, e[j], k1[j]; ct0[j], r2[j], r1[j], r1[j+n].
+__global__ __launch_bounds__(TPB) void k_derive_combine(DeriveArgs A) {
+    using namespace drv;
+    const size_t n = (size_t)1 << A.n_log2, N = 2 * n;
+    const size_t j = (size_t)blockIdx.x * TPB + threadIdx.x;
+    if (j >= n) return;
+    const int i = (int)blockIdx.y;
+    const DeriveMod& D = A.mod[i];
+    const Modulus M{D.q, D.d, D.v, D.qinv, D.half, D.sh};
+    const u64* lo = A.X + (size_t)(1 + 2 * i) * N;
+    const u64* hi = lo + N;
+    // (a word of the product above p/2 is a negative integer: |lo * s| and |hi * s| stay below p/2, checked by derive_plan in prover.hip)
+    S128 h0 = s128_add(s128_shl32(gl_signed(hi[j])), s128(gl_signed(lo[j])));
+    const S128 h1 = s128_add(s128_shl32(gl_signed(hi[j + n])), s128(gl_signed(lo[j + n])));   // (h[2n-1] = 0)
+    h0 = s128_add(h0, s128(gl_signed(A.e[N - 2 - j])));
+    h0 = s128_add(h0, s128_mul(gl_signed(A.k1[N - 2 - j]), D.k0));
+    const bool has_r2 = j + 1 < n;
+    const int64_t ct0 = centre_mod(s128_sub(h0, h1), M);
+    const int64_t r2 = has_r2 ? centre_mod(s128_neg(h1), M) : 0;
+    bool ex0 = true, ex1 = true;
+    const int64_t r1_0 = exact_quotient(s128_sub(s128_sub(s128(ct0), h0), s128(r2)), M, &ex0);
+    const int64_t r1_1 = has_r2 ? exact_quotient(s128_neg(s128_add(h1, s128(r2))), M, &ex1) : 0;
+    u32 f1 = (ex0 && ex1) ? 0 : DRV_INEXACT;
+    if (derive_mag(r1_0) > D.r1_bound || derive_mag(r1_1) > D.r1_bound) f1 |= DRV_BOUND;
+    derive_flag(A.flags, 4, i, f1);
+    derive_flag(A.flags, 5, i, derive_mag(r2) > D.r2_bound ? DRV_BOUND : 0);
+    u64* ct = A.ct0is + (size_t)i * N;
+    u64* r1 = A.r1is[i];
+    u64* r2t = A.r2is + (size_t)i * n;
+    ct[N - 2 - j] = gl_assign(ct0);
+    r1[N - 2 - j] = gl_assign(r1_0);
+    if (has_r2) {
+        ct[j] = 0;                         // positions 0 .. n-2 of ct0is are its left padding
+        r1[n - 2 - j] = gl_assign(r1_1);
+        r2t[n - 2 - j] = gl_assign(r2);
+    } else {                               // j = n-1: the trailing zero of each table
+        ct[N - 1] = 0; r1[N - 1] = 0; r2t[n - 1] = 0;
+    }
+}
+void derive_unpack(hipStream_t st, const DeriveArgs& a) {
+    const size_t N = (size_t)2 << a.n_log2;
+    k_derive_unpack<<<dim3((unsigned)((N + TPB - 1) / TPB), (unsigned)a.k + 1), TPB, 0, st>>>(a);
+}
+void derive_mul(hipStream_t st, u64* X, int log2_len, int batch) {
+    const size_t N = (size_t)1 << log2_len;
+    k_derive_mul<<<dim3((unsigned)((N + TPB - 1) / TPB), (unsigned)batch), TPB, 0, st>>>(X, log2_len);
+}
+void derive_combine(hipStream_t st, const DeriveArgs& a) {
+    const size_t n = (size_t)1 << a.n_log2;
+    k_derive_combine<<<dim3((unsigned)((n + TPB - 1) / TPB), (unsigned)a.k), TPB, 0, st>>>(a);
 }
 
 }  // namespace dev

@@ -374,5 +374,34 @@ void gate_eval(hipStream_t st, const EvalNode& n);
 // (two launches); otherwise radix-2 stages in HBM. W = w^i for i < N.
 void ntt_batch(hipStream_t st, u64* data, int log2n, size_t batch, const u64* W, u64 scale, u64* scratch);
 
+// ---- witness derivation (hg_witness_derive): ct0is, r2is, r1is from s, e, k1, ais [REF scripts/circuit_sk.py:18-140] -------------
+// The exact integer product a_i * s as 2k+1 Goldilocks NTTs of size 2n: a_i is split as lo + 2^32 hi (lo = low 32 bits, hi the
+// arithmetic shift), so every coefficient of lo * s and of hi * s stays far below p / 2 in magnitude and the NTT gives the integers.
+//   derive_unpack   laid-out tables -> X = [s | lo_0 | hi_0 | lo_1 | ...], 2k+1 ascending-degree, zero-padded vectors of 2n words;
+//                   checks every input word (canonical, inside its bound, zero where the layout pads)
+//   ntt_batch(X, 2k+1 forward), derive_mul (X[b] *= X[0]), ntt_batch(X + 2n, 2k inverse)
+//   derive_combine  h = hi 2^32 + lo + e + k0_i k1 in 128 bits, reduced by X^n + 1 and q_i -> the three tables at their laid-out
+//                   positions (descending degree, zero padding included); checks the quotients and the range bounds
+// A failed check ORs a bit into flags[table * DRV_MAX_K + modulus] (table: 0 s, 1 e, 2 k1, 3 ais, 4 r1is, 5 r2is).
+constexpr int DRV_MAX_K = 16;   // = HG_MAX_K (static_assert in prover.hip, which sees include/hg.h)
+constexpr u32 DRV_NONCANONICAL = 1, DRV_BOUND = 2, DRV_PADDING = 4, DRV_INEXACT = 8;
+constexpr int DRV_FLAG_WORDS = 6 * DRV_MAX_K;
+struct DeriveMod { u64 q, d, v, qinv, half, k0, r1_bound, r2_bound; int sh; int pad; };
+struct DeriveArgs {
+    const u64* s; const u64* e; const u64* k1;     // 2n words each
+    const u64* ais[DRV_MAX_K];                     // 2n words each
+    u64* r1is[DRV_MAX_K];                          // 2n words each
+    u64* r2is;                                     // k * n
+    u64* ct0is;                                    // k * 2n
+    u64* X;                                        // (2k+1) * 2n
+    u32* flags;                                    // DRV_FLAG_WORDS, zeroed by the caller
+    DeriveMod mod[DRV_MAX_K];
+    u64 s_bound, e_bound, k1_bound;
+    int n_log2, k;
+};
+void derive_unpack(hipStream_t st, const DeriveArgs& a);
+void derive_mul(hipStream_t st, u64* X, int log2_len, int batch);   // X[b][i] *= X[0][i], 1 <= b <= batch
+void derive_combine(hipStream_t st, const DeriveArgs& a);
+
 }  // namespace dev
 }  // namespace hg

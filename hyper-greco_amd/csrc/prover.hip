@@ -563,6 +563,39 @@ double prove_warmup(hg_ctx* ctx, const hg_pk* pk) {
     for (int i = 0; i < 4 && !cache_find(ctx, pk, ctx->scratch_values, 0, 1); i++) (void)prove_resident(ctx, pk, ctx->scratch_values, true);
     return wall_ms() - t0;
 }
+// Circuit::evaluate behind the input tables of `v` (already on their way on `st`): level by level, nothing waits
+static void circuit_levels(const hg_pk* pk, hg_values* v, hipStream_t st) {
+    const HCircuit& c = pk->circuit;
+    auto dv = [&](int id) { return const_cast<u64*>(v->d_vals[id]); };
+    auto in = [&](int id) { return v->mask.empty() || v->mask[id]; };
+    for (int l = 1; l <= v->max_level; l++) {
+        for (int inv = 0; inv < 2; inv++) {  // FFT groups
+            std::vector<int> grp;
+            for (int id : v->order) if (c.nodes[id].kind == NK_FFT && v->level[id] == l && (int)c.nodes[id].inverse == inv && in(id)) grp.push_back(id);
+            if (grp.empty()) continue;
+            const int L = c.nodes[grp[0]].log2_size;
+            const size_t N = (size_t)1 << L;
+            for (int id : grp) {
+                if (c.nodes[id].log2_size != L) throw Error("circuit: mixed FFT sizes in one level");
+                hip_check(hipMemcpyAsync(dv(id), dv(c.nodes[id].preds[0]), N * 8, hipMemcpyDeviceToDevice, st), "copy fft input");
+            }
+            const u64* W = (inv ? pk->w_inv : pk->w_fwd).at(L);
+            dev::ntt_batch(st, dv(grp[0]), L, grp.size(), W, inv ? gl_inv(gl_from_u64(N)) : 1, v->ntt_scratch);
+        }
+        for (int id : c.topo) {
+            const HNode& n = c.nodes[id];
+            if (v->level[id] != l || !in(id)) continue;
+            if (n.kind == NK_VANILLA) {
+                dev::EvalNode e = pk->node_dev[id].fwd;
+                for (int i = 0; i < n.arity; i++) e.in[i] = dv(n.preds[i]);
+                e.out = dv(id);
+                dev::gate_eval(st, e);
+            } else if (n.kind == NK_LASSO) {
+                hip_check(hipMemsetAsync(dv(id), 0, 8, st), "lasso output");  // LassoNode::evaluate returns [0] (lasso.rs:53-55)
+            }
+        }
+    }
+}
 // `st`: the stream everything is enqueued on; sync == false: nothing waits (the caller orders later work behind an event on `st`)
 // `pinned` (hg_prove_stream): page-locked staging for the whole witness. The caller's arrays are pageable, and an "asynchronous" copy
 // from pageable memory is staged by the runtime inside the call, 37 times per witness (0.9 ms of host time at n=32768 k=16, during
@@ -637,33 +670,7 @@ static void witness_fill(hg_ctx* ctx, const hg_pk* pk, const Witness& w, hg_valu
     }
     if (upload_ms && sync) hip_check(hipStreamSynchronize(st), "upload sync");   // (only to split the two timings)
     double t1 = wall_ms();
-    for (int l = 1; l <= v->max_level; l++) {
-        for (int inv = 0; inv < 2; inv++) {  // FFT groups
-            std::vector<int> grp;
-            for (int id : v->order) if (c.nodes[id].kind == NK_FFT && v->level[id] == l && (int)c.nodes[id].inverse == inv && in(id)) grp.push_back(id);
-            if (grp.empty()) continue;
-            const int L = c.nodes[grp[0]].log2_size;
-            const size_t N = (size_t)1 << L;
-            for (int id : grp) {
-                if (c.nodes[id].log2_size != L) throw Error("circuit: mixed FFT sizes in one level");
-                hip_check(hipMemcpyAsync(dv(id), dv(c.nodes[id].preds[0]), N * 8, hipMemcpyDeviceToDevice, st), "copy fft input");
-            }
-            const u64* W = (inv ? pk->w_inv : pk->w_fwd).at(L);
-            dev::ntt_batch(st, dv(grp[0]), L, grp.size(), W, inv ? gl_inv(gl_from_u64(N)) : 1, v->ntt_scratch);
-        }
-        for (int id : c.topo) {
-            const HNode& n = c.nodes[id];
-            if (v->level[id] != l || !in(id)) continue;
-            if (n.kind == NK_VANILLA) {
-                dev::EvalNode e = pk->node_dev[id].fwd;
-                for (int i = 0; i < n.arity; i++) e.in[i] = dv(n.preds[i]);
-                e.out = dv(id);
-                dev::gate_eval(st, e);
-            } else if (n.kind == NK_LASSO) {
-                hip_check(hipMemsetAsync(dv(id), 0, 8, st), "lasso output");  // LassoNode::evaluate returns [0] (lasso.rs:53-55)
-            }
-        }
-    }
+    circuit_levels(pk, v, st);
     if (sync) hip_check(hipStreamSynchronize(st), "witness generation sync");
     hip_check(hipGetLastError(), "witness generation");
     double t2 = wall_ms();
@@ -675,6 +682,181 @@ hg_values* witness_gen(hg_ctx* ctx, const hg_pk* pk, const Witness& w, double* w
     hg_values* v = values_alloc(ctx, pk);
     try { witness_gen_into(ctx, pk, w, v, witness_ms, upload_ms); } catch (...) { values_free(v); throw; }
     return v;
+}
+
+// ---- witness derivation: ct0is, r2is, r1is from s, e, k1, ais on the device (hg_witness_derive, hg_witness_derive_into) ---------------
+// [REF scripts/circuit_sk.py:18-140; the rule is restated in host.cpp above witness_synthetic]. Kernels: kernels.hip k_derive_*.
+static_assert(dev::DRV_MAX_K == HG_MAX_K, "the derive kernels index their per-modulus arrays with the library's maximum k");
+// The parameter set as the derive kernels read it, after the checks that make their arithmetic exact for this set:
+//   q_i odd (the quotient by q_i goes through q_i^-1 mod 2^64) and below 2^62 (so q_i << sh shifts by 2 .. 63 bits);
+//   every coefficient of lo * s and hi * s below p / 2 in magnitude (the Goldilocks NTT of size 2n then gives the integers);
+//   every value the combine step reduces by q_i inside the precondition of drv::mod_u128, every quotient below 2^62.
+static void derive_plan(const Params& p, dev::DeriveArgs* a) {
+    typedef unsigned __int128 u128;
+    const hg_params& r = p.raw;
+    memset(a, 0, sizeof(*a));
+    if (p.k < 1 || p.k > dev::DRV_MAX_K) throw Error("witness derivation: k out of range");
+    if (p.n_log2 < 1 || p.L > 32) throw Error("witness derivation: no Goldilocks NTT of size 2n for this ring degree");
+    if (r.s_bound == 0 || r.s_bound >= (1ULL << 31) || r.e_bound >= (1ULL << 62) || r.k1_bound >= (1ULL << 62))
+        throw Error("witness derivation: s_bound / e_bound / k1_bound outside what the 128-bit arithmetic of the derivation covers");
+    a->n_log2 = p.n_log2; a->k = p.k;
+    a->s_bound = r.s_bound; a->e_bound = r.e_bound; a->k1_bound = r.k1_bound;
+    const u128 n = (u128)1 << p.n_log2, half_p = GL_P >> 1;
+    for (int i = 0; i < p.k; i++) {
+        const u64 q = r.qis[i], k0 = r.k0is[i];
+        const std::string who = "witness derivation: modulus " + std::to_string(i) + " (q = " + std::to_string(q) + ")";
+        if (q < 3 || !(q & 1)) throw Error(who + " is even or below 3: the exact quotient by q_i needs an odd modulus");
+        if (q >= (1ULL << 62)) throw Error(who + " has 62 bits or more");
+        if (k0 >= (1ULL << 62) || r.r1_bounds[i] >= (1ULL << 62)) throw Error(who + ": k0 or r1 bound of 62 bits or more");
+        const u64 half = (q - 1) / 2;
+        if (n * r.s_bound * 0xFFFFFFFFULL >= half_p || n * r.s_bound * ((u128)(half >> 32) + 1) >= half_p)
+            throw Error(who + ": a coefficient of a_i * s can reach p / 2, the NTT product would not be exact");
+        const u128 H = n * r.s_bound * half + r.e_bound + (u128)k0 * r.k1_bound;   // |h[j]| <= H (< 2^125 by the checks above)
+        const u128 big = 2 * H + q;                                                  // |h[j] - h[j+n]|, |ct0 - h - r2| <= big
+        const int sh = __builtin_clzll(q);
+        const u64 d = q << sh;
+        if ((big >> (127 - sh)) != 0 || (u64)((big << sh) >> 64) >= d) throw Error(who + ": h = a_i s + e + k0_i k1 too large for the 128-bit reduction");
+        if ((H + q) / q >= ((u128)1 << 62)) throw Error(who + ": a quotient r1_i could leave 62 bits");
+        u64 qinv = q;   // Newton: 3 correct bits, doubled five times
+        for (int it = 0; it < 5; it++) qinv *= 2 - q * qinv;
+        dev::DeriveMod& m = a->mod[i];
+        m.q = q; m.d = d; m.v = (u64)(~(u128)0 / d - ((u128)1 << 64)); m.qinv = qinv; m.half = half; m.k0 = k0; m.sh = sh;
+        m.r1_bound = r.r1_bounds[i];
+        m.r2_bound = std::min(r.r2_bounds[i], r.r2_bounds[0]);   // (the circuit range-checks every r2_i chunk with R2_BOUND_0: host.cpp, lasso rows)
+    }
+}
+// unpack, 2k+1 forward NTTs, pointwise product by NTT(s), 2k inverse NTTs, combine - all on `st`, nothing waits
+static void derive_enqueue(hipStream_t st, const dev::DeriveArgs& a, int L, const u64* Wf, const u64* Wi, u64* scratch) {
+    const size_t N = (size_t)1 << L;
+    hip_check(hipMemsetAsync(a.flags, 0, dev::DRV_FLAG_WORDS * sizeof(u32), st), "clear derive flags");
+    dev::derive_unpack(st, a);
+    dev::ntt_batch(st, a.X, L, (size_t)2 * a.k + 1, Wf, 1, scratch);
+    dev::derive_mul(st, a.X, L, 2 * a.k);
+    dev::ntt_batch(st, a.X + N, L, (size_t)2 * a.k, Wi, gl_inv(gl_from_u64(N)), scratch);
+    dev::derive_combine(st, a);
+    hip_check(hipGetLastError(), "witness derivation: kernel launch");
+}
+// the first failed check as an error that names the table, the modulus and the cause (inputs before derived tables)
+static void derive_check_flags(const Params& p, const u32* flags, const char* who) {
+    static const char* names[6] = {"s", "e", "k1", "ais", "r1is", "r2is"};
+    for (int t = 0; t < 6; t++)
+        for (int i = 0; i < p.k; i++) {
+            const u32 f = flags[t * dev::DRV_MAX_K + i];
+            if (!f) continue;
+            std::string m = std::string(who) + ": table " + names[t];
+            if (t >= 3) m += " of modulus " + std::to_string(i) + " (q = " + std::to_string(p.raw.qis[i]) + ")";
+            if (f & dev::DRV_NONCANONICAL) m += ": non-canonical field element (a word >= p)";
+            else if (f & dev::DRV_PADDING) m += ": a nonzero word where the layout pads with zeros";
+            else if (f & dev::DRV_INEXACT) m += ": a derived quotient is not exact (d mod q_i != 0)";
+            else if (t == 0) m += ": a coefficient outside s_bound = " + std::to_string(p.raw.s_bound);
+            else if (t == 1) m += ": a coefficient outside e_bound = " + std::to_string(p.raw.e_bound);
+            else if (t == 2) m += ": a coefficient outside k1_bound = " + std::to_string(p.raw.k1_bound);
+            else if (t == 3) m += ": a coefficient outside [-(q_i-1)/2, (q_i-1)/2]";
+            else if (t == 4) m += ": a derived coefficient outside its bound r1_bounds = " + std::to_string(p.raw.r1_bounds[i]) + " (such a witness cannot be proven)";
+            else m += ": a derived coefficient outside its bound r2_bounds = " + std::to_string(std::min(p.raw.r2_bounds[i], p.raw.r2_bounds[0])) + " (such a witness cannot be proven)";
+            throw Error(m);
+        }
+}
+Witness witness_derive(hg_ctx* ctx, const Params& p, const u64* s, const u64* e, const u64* k1, const u64* ais) {
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    dev::DeriveArgs a;
+    derive_plan(p, &a);
+    const size_t SZ = p.SZ(), PZ = p.PZ(), k = (size_t)p.k;
+    hipStream_t st = ctx->stream;
+    ctx->arena_reset();
+    u64* d_in = ctx->alloc_n<u64>((3 + k) * SZ);
+    u64* d_r1 = ctx->alloc_n<u64>(k * SZ);
+    a.r2is = ctx->alloc_n<u64>(k * PZ);
+    a.ct0is = ctx->alloc_n<u64>(k * SZ);
+    a.X = ctx->alloc_n<u64>((2 * k + 1) * SZ);
+    u64* scratch = ctx->alloc_n<u64>((2 * k + 1) * SZ);
+    u64* Wf = ctx->alloc_n<u64>(SZ);
+    u64* Wi = ctx->alloc_n<u64>(SZ);
+    a.flags = ctx->alloc_n<u32>(dev::DRV_FLAG_WORDS);
+    a.s = d_in; a.e = d_in + SZ; a.k1 = d_in + 2 * SZ;
+    for (size_t i = 0; i < k; i++) { a.ais[i] = d_in + (3 + i) * SZ; a.r1is[i] = d_r1 + i * SZ; }
+    hip_check(hipMemcpyAsync(d_in, s, SZ * 8, hipMemcpyHostToDevice, st), "upload s");
+    hip_check(hipMemcpyAsync(d_in + SZ, e, SZ * 8, hipMemcpyHostToDevice, st), "upload e");
+    hip_check(hipMemcpyAsync(d_in + 2 * SZ, k1, SZ * 8, hipMemcpyHostToDevice, st), "upload k1");
+    hip_check(hipMemcpyAsync(d_in + 3 * SZ, ais, k * SZ * 8, hipMemcpyHostToDevice, st), "upload ais");
+    const u64 w = root_of_unity(p.L);
+    dev::powers_table(st, Wf, w, SZ);
+    dev::powers_table(st, Wi, gl_inv(w), SZ);
+    derive_enqueue(st, a, p.L, Wf, Wi, scratch);
+    u32 flags[dev::DRV_FLAG_WORDS];
+    Witness out;
+    out.r1is.resize(k * SZ); out.r2is.resize(k * PZ); out.ct0is.resize(k * SZ);
+    hip_check(hipMemcpyAsync(flags, a.flags, sizeof(flags), hipMemcpyDeviceToHost, st), "download derive flags");
+    hip_check(hipMemcpyAsync(out.r1is.data(), d_r1, k * SZ * 8, hipMemcpyDeviceToHost, st), "download r1is");
+    hip_check(hipMemcpyAsync(out.r2is.data(), a.r2is, k * PZ * 8, hipMemcpyDeviceToHost, st), "download r2is");
+    hip_check(hipMemcpyAsync(out.ct0is.data(), a.ct0is, k * SZ * 8, hipMemcpyDeviceToHost, st), "download ct0is");
+    hip_check(hipStreamSynchronize(st), "witness derivation sync");
+    derive_check_flags(p, flags, "hg_witness_derive");
+    out.s.assign(s, s + SZ); out.e.assign(e, e + SZ); out.k1.assign(k1, k1 + SZ); out.ais.assign(ais, ais + k * SZ);
+    return out;
+}
+// The same with the tables of `v` as the kernels' inputs and outputs, the circuit evaluated behind them on the same stream. The copy
+// back (flags; r1is, r2is, ct0is for the handle) runs on the second stream beside the evaluation.
+void witness_derive_into(hg_ctx* ctx, const hg_pk* pk, const u64* s, const u64* e, const u64* k1, const u64* ais, hg_values* v, Witness* out,
+                         double* total_ms, double* gpu_ms) {
+    const double t0 = wall_ms();
+    if (v->pk_serial != pk->serial) throw Error("hg_witness_derive_into: the values object was laid out for another prover key");
+    if (v->device != ctx->device || v->ctx != ctx) throw Error("hg_witness_derive_into: the values object was created on another context");
+    if (v->shard_rank >= 0 || !v->mask.empty() || !v->d_ct0is) throw Error("hg_witness_derive_into: needs a values object that holds every table (hg_witness_gen), not a rank's share");
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    const Params& p = pk->params;
+    const HCircuit& c = pk->circuit;
+    dev::DeriveArgs a;
+    derive_plan(p, &a);
+    const size_t SZ = p.SZ(), PZ = p.PZ(), k = (size_t)p.k;
+    if (c.input_ids.size() != 3 + 2 * k + 1) throw Error("hg_witness_derive_into: unexpected input nodes");
+    auto dv = [&](size_t q) { return const_cast<u64*>(v->d_vals[c.input_ids[q]]); };
+    hipStream_t st = ctx->stream;
+    ctx->arena_reset();
+    a.X = ctx->alloc_n<u64>((2 * k + 1) * SZ);
+    u64* scratch = ctx->alloc_n<u64>((2 * k + 1) * SZ);
+    a.flags = ctx->alloc_n<u32>(dev::DRV_FLAG_WORDS);
+    a.s = dv(0); a.e = dv(1); a.k1 = dv(2);
+    for (size_t i = 0; i < k; i++) { a.ais[i] = dv(3 + i); a.r1is[i] = dv(3 + k + i); }
+    a.r2is = dv(3 + 2 * k);
+    a.ct0is = const_cast<u64*>(v->d_ct0is);
+    if (v->sizes[c.input_ids[3 + 2 * k]] != k * PZ || v->ct0is_len != k * SZ) throw Error("hg_witness_derive_into: table size mismatch");
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    struct Ev { hipEvent_t& a; hipEvent_t& b; ~Ev() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev_guard{ev0, ev1};
+    if (gpu_ms) {
+        hip_check(hipEventCreate(&ev0), "hipEventCreate"); hip_check(hipEventCreate(&ev1), "hipEventCreate");
+        hip_check(hipEventRecord(ev0, st), "event record");
+    }
+    hip_check(hipMemcpyAsync(dv(0), s, SZ * 8, hipMemcpyHostToDevice, st), "upload s");
+    hip_check(hipMemcpyAsync(dv(1), e, SZ * 8, hipMemcpyHostToDevice, st), "upload e");
+    hip_check(hipMemcpyAsync(dv(2), k1, SZ * 8, hipMemcpyHostToDevice, st), "upload k1");
+    for (size_t i = 0; i < k; i++) hip_check(hipMemcpyAsync(dv(3 + i), ais + i * SZ, SZ * 8, hipMemcpyHostToDevice, st), "upload ais");
+    derive_enqueue(st, a, p.L, pk->w_fwd.at(p.L), pk->w_inv.at(p.L), scratch);
+    hip_check(hipEventRecord(ctx->ev_fork, st), "event record");
+    circuit_levels(pk, v, st);
+    if (gpu_ms) hip_check(hipEventRecord(ev1, st), "event record");
+    // beside the evaluation: the flag words and, for the handle, the derived tables
+    hipStream_t s2 = ctx->stream2;
+    hip_check(hipStreamWaitEvent(s2, ctx->ev_fork, 0), "stream wait");
+    u32 flags[dev::DRV_FLAG_WORDS];
+    hip_check(hipMemcpyAsync(flags, a.flags, sizeof(flags), hipMemcpyDeviceToHost, s2), "download derive flags");
+    Witness w;
+    if (out) {
+        w.r1is.resize(k * SZ); w.r2is.resize(k * PZ); w.ct0is.resize(k * SZ);
+        for (size_t i = 0; i < k; i++) hip_check(hipMemcpyAsync(&w.r1is[i * SZ], a.r1is[i], SZ * 8, hipMemcpyDeviceToHost, s2), "download r1is");
+        hip_check(hipMemcpyAsync(w.r2is.data(), a.r2is, k * PZ * 8, hipMemcpyDeviceToHost, s2), "download r2is");
+        hip_check(hipMemcpyAsync(w.ct0is.data(), a.ct0is, k * SZ * 8, hipMemcpyDeviceToHost, s2), "download ct0is");
+    }
+    hip_check(hipStreamSynchronize(s2), "witness derivation sync");
+    hip_check(hipStreamSynchronize(st), "witness generation sync");
+    hip_check(hipGetLastError(), "witness generation");
+    derive_check_flags(p, flags, "hg_witness_derive_into");
+    if (out) {
+        w.s.assign(s, s + SZ); w.e.assign(e, e + SZ); w.k1.assign(k1, k1 + SZ); w.ais.assign(ais, ais + k * SZ);
+        *out = std::move(w);
+    }
+    if (gpu_ms) { float ms = 0; hip_check(hipEventElapsedTime(&ms, ev0, ev1), "event elapsed"); *gpu_ms = ms; }
+    if (total_ms) *total_ms = wall_ms() - t0;
 }
 
 // ---- a rank's share of the node tables (BASELINE config 4: the witness is NOT replicated) ---------------------------------------------

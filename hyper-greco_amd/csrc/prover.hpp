@@ -225,6 +225,11 @@ hg_values* witness_gen_shard(hg_ctx* ctx, const hg_pk* pk, const Witness& w, int
 void witness_gen_into(hg_ctx* ctx, const hg_pk* pk, const Witness& w, hg_values* v, double* witness_ms, double* upload_ms);
 void witness_gen_into_staged(hg_ctx* ctx, const hg_pk* pk, const Witness& w, hg_values* v, double* witness_ms, double* upload_ms);   // through the context's page-locked staging
 double prove_warmup(hg_ctx* ctx, const hg_pk* pk);   // hg_warmup
+// ct0is, r2is, r1is derived from s, e, k1, ais on the device (laid-out tables in, laid-out tables out); throws on a failed check
+Witness witness_derive(hg_ctx* ctx, const Params& p, const u64* s, const u64* e, const u64* k1, const u64* ais);
+// the same straight into the input tables of `v`, the circuit evaluated behind them; out (may be null): the host handle's tables
+void witness_derive_into(hg_ctx* ctx, const hg_pk* pk, const u64* s, const u64* e, const u64* k1, const u64* ais, hg_values* v, Witness* out,
+                         double* total_ms, double* gpu_ms);
 // BfvEncrypt::prove for a run of witnesses, pipelined: upload + circuit.evaluate of witness i+1 overlap the GKR prove of witness i
 std::vector<ProveResult> prove_stream(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Witness*>& ws, double* total_ms);
 void values_free(hg_values* v);

@@ -109,11 +109,22 @@ int hg_pk_node_eq_form(const hg_pk* pk, int node, int64_t out[6]);
 int hg_witness_from_json(const hg_params* params, const char* path, hg_witness** w);
 /* Replaces scripts/circuit_sk.py (offline witness generator) with a seeded synthetic BFV sk-encryption
  * [REF scripts/circuit_sk.py:18-140, scripts/utils.py:4-18]; needed because the n=32768 fixture is a missing blob. */
-int hg_witness_synthetic(const hg_params* params, uint64_t seed, hg_witness** w);
+int hg_witness_synthetic(const hg_params* params, uint64_t seed, hg_witness** w);   /* caller-supplied secrets: hg_witness_derive */
 /* Already laid-out tables: s,e,k1: 2^L; ais,r1is: k*2^L; r2is: k*2^P; ct0is: k*2^L (L = log2 n + 1, P = log2 n) */
 int hg_witness_from_arrays(const hg_params* params, const uint64_t* s, const uint64_t* e, const uint64_t* k1,
                            const uint64_t* ais, const uint64_t* r1is, const uint64_t* r2is, const uint64_t* ct0is,
                            hg_witness** w);
+/* = the witness half of scripts/circuit_sk.py for secrets the CALLER holds [REF scripts/circuit_sk.py:18-140], on the device: from
+ *   the laid-out tables s, e, k1 (2^L each) and ais (k*2^L) of hg_witness_from_arrays it derives ct0is, r2is and r1is - per modulus
+ *   h = a_i s + e + k0_i k1 over Z (2k+1 Goldilocks NTTs of size 2n on 32-bit halves of a_i), ct0_i = h mod (X^n + 1, q_i) centred,
+ *   r2_i = cmod(-h[j+n], q_i), r1_i = (ct0_i - h - r2_i (X^n + 1)) / q_i - and returns the handle hg_witness_from_arrays would
+ *   return for all seven tables. Needs a device context; never falls back to the host.
+ *   Errors (-1, text in hg_last_error, *w = NULL): null argument; no context; a word >= p; a coefficient of s / e / k1 outside
+ *   s_bound / e_bound / k1_bound, of a_i outside [-(q_i-1)/2, (q_i-1)/2], or a nonzero word where the layout pads; a derived r1_i /
+ *   r2_i coefficient outside its bound in params (table and modulus are named: such a witness cannot be proven, its Lasso lookups
+ *   fail); an even q_i, q_i >= 2^62, or parameters for which the products are not exact below p/2 or h leaves the 128-bit reduction. */
+int hg_witness_derive(hg_ctx* ctx, const hg_params* params, const uint64_t* s, const uint64_t* e, const uint64_t* k1,
+                      const uint64_t* ais, hg_witness** w);
 /* which: 0 s, 1 e, 2 k1, 3 ais, 4 r1is, 5 r2is, 6 ct0is. Returns the element count (copies min(count, cap)). */
 int64_t hg_witness_get(const hg_witness* w, int which, uint64_t* out, size_t cap);
 void hg_witness_free(hg_witness* w);
@@ -224,6 +235,17 @@ int hg_witness_gen(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, hg_values*
  * addresses only - the next hg_prove_resident(v) replays it on the new witness. hg_prove does this internally with a values
  * object owned by the context. */
 int hg_witness_gen_into(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, hg_values* v, hg_timings* timings);
+/* hg_witness_derive and hg_witness_gen_into in one: the steady state of a proving service that receives encryptions, not witnesses
+ * [REF scripts/circuit_sk.py:18-140 followed by sk_encryption_circuit.rs:439-442]. s, e, k1, ais are uploaded into the input tables
+ * of `v` (a full values object of this key and context, from hg_witness_gen), the derivation kernels write r1is, r2is and ct0is
+ * straight into its tables - they do not visit the host on the way to the prover - and the circuit is evaluated behind them on the
+ * same stream. `v` keeps its addresses, so the launch graph recorded for it proves the new witness. *w (w may be NULL) receives
+ * the host handle the verifiers need for ct0is; its copy back runs beside the evaluation. timings (may be NULL): total_ms =
+ * witness_ms = wall clock of the call, gpu_ms = HIP events around uploads, derivation and evaluation on the prover stream.
+ * Errors as hg_witness_derive, plus a host-only key or a rank's share as `v`; after a failed check (-1) no handle is produced and the
+ * CONTENTS of `v` are clobbered (it stays valid for the next hg_witness_gen_into / hg_witness_derive_into). */
+int hg_witness_derive_into(hg_ctx* ctx, const hg_pk* pk, const uint64_t* s, const uint64_t* e, const uint64_t* k1,
+                           const uint64_t* ais, hg_values* v, hg_witness** w, hg_timings* timings);
 /* The same for ONE rank of a proof sharded over `world` GPUs (BASELINE config 4): only the node tables the rank's share reads stay
  * resident - the Lasso node's input, the inputs of the Vanilla / FFT node reductions the planner deals to it, ct0is on the rank that
  * evaluates the output claim; the per-modulus objects a rank does not own [REF sk_encryption_circuit.rs:122-128, 245-260] are released.
