@@ -680,6 +680,32 @@ Witness witness_synthetic(const Params& p, u64 seed) {
     throw Error("synthetic witness: could not satisfy the range bounds");
 }
 
+// hg_encryption_layout: the rule of layout_inputs (get_inputs, sk_encryption_circuit.rs:365-415; Poly::new_padded / new_shifted,
+// poly.rs:20-44) for polynomials held as signed coefficients in ascending degree: coefficient j of s and of a_i at word n-1-j
+// (descending degree, zeros behind), of e and k1 at word 2n-2-j (shifted so that they end at 2^L - 2), a negative z as p - |z|
+// (utils.py:4-18). The device form of the same rule is k_derive_pack (kernels.hip); the tests compare the two.
+void encryption_layout(const Params& p, const int64_t* s, const int64_t* e, const int64_t* k1, const int64_t* a, u64* s_t, u64* e_t, u64* k1_t,
+                       u64* ais_t) {
+    const size_t n = p.PZ(), SZ = p.SZ(), k = (size_t)p.k;
+    auto word = [](int64_t z) -> u64 {
+        if (z == INT64_MIN) throw Error("hg_encryption_layout: a coefficient equal to INT64_MIN has no magnitude in 64 bits");
+        return z >= 0 ? (u64)z : GL_P - (u64)(-z);
+    };
+    auto padded = [&](const int64_t* c, u64* t) {    // new_padded
+        for (size_t j = 0; j < n; j++) t[n - 1 - j] = word(c[j]);
+        std::fill(t + n, t + SZ, (u64)0);
+    };
+    auto shifted_to = [&](const int64_t* c, u64* t) {   // new_shifted(.., 2^L - 1), one trailing zero
+        std::fill(t, t + (n - 1), (u64)0);
+        for (size_t j = 0; j < n; j++) t[SZ - 2 - j] = word(c[j]);
+        t[SZ - 1] = 0;
+    };
+    padded(s, s_t);
+    shifted_to(e, e_t);
+    shifted_to(k1, k1_t);
+    for (size_t i = 0; i < k; i++) padded(a + i * n, ais_t + i * SZ);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Lasso preprocessing
 int LassoPlan::lookup_index(u64 bound) const {

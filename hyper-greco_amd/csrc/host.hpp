@@ -119,6 +119,9 @@ struct Witness {  // tables exactly as get_inputs lays them out
 Witness witness_from_json(const Params& p, const std::string& path);
 Witness witness_from_json_bn254(const Params& p, const std::string& path);  // bn256::Fr fixture -> signed integers in Goldilocks form
 Witness witness_synthetic(const Params& p, u64 seed);
+// hg_encryption_layout: get_inputs for the four tables an encryptor holds (signed coefficients, ascending degree; a: k*n, modulus-major)
+void encryption_layout(const Params& p, const int64_t* s, const int64_t* e, const int64_t* k1, const int64_t* a, u64* s_t, u64* e_t, u64* k1_t,
+                       u64* ais_t);
 
 // ---------------------------------------------------------------------------------------------
 // Lasso preprocessing (host description; the device copy lives in the prover key)

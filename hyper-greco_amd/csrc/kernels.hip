@@ -3339,6 +3339,60 @@ __global__ __launch_bounds__(TPB) void k_derive_unpack(DeriveArgs A) {
         lo[m] = 0; hi[m] = 0;
     }
 }
+// hg_prove_encryptions: the same X and the same flag bits from the COMPACT device copy C = [s | e | k1 | a_0 | .. | a_{k-1}] of signed
+// coefficients in ascending degree (n words each), and the laid-out input tables written beside them (A.s, A.e, A.k1, A.ais[] are
+// OUTPUTS here, padding zeros included) - what "upload four laid-out tables, k_derive_unpack" produced, from a quarter of the bytes.
+// blockIdx.y as in k_derive_unpack. One thread per PAIR of table positions (2t, 2t+1): s and a_i read their two coefficients as one
+// 16-byte load (n is even, so the pair n-2-2t, n-1-2t is aligned); e and k1 sit one word off that grid (coefficient j at 2n-2-j) and
+// read two adjacent 8-byte words, still contiguous across the wave. Every store is 16 bytes. Every coefficient is read exactly once.
+__device__ __forceinline__ u32 derive_check_z(int64_t z, u64 bound) { return derive_mag(z) > bound ? DRV_BOUND : 0; }
+__global__ __launch_bounds__(TPB) void k_derive_pack(DeriveArgs A, const int64_t* __restrict__ C) {
+    const size_t n = (size_t)1 << A.n_log2, N = 2 * n;
+    const size_t t = (size_t)blockIdx.x * TPB + threadIdx.x;
+    if (t >= n) return;
+    const size_t m = 2 * t;   // table positions m, m + 1
+    if (blockIdx.y == 0) {
+        u64* st = const_cast<u64*>(A.s);
+        if (m < n) {
+            const u64x2_t c = load16(C + (n - 2 - m));   // coefficients n-2-m (-> position m+1), n-1-m (-> position m)
+            const int64_t z0 = (int64_t)c.x, z1 = (int64_t)c.y;
+            derive_flag(A.flags, 0, 0, derive_check_z(z0, A.s_bound) | derive_check_z(z1, A.s_bound));
+            const u64 w0 = drv::gl_assign(z0), w1 = drv::gl_assign(z1);
+            store_u64x2(st + m, w1, w0);
+            store_u64x2(A.X + (n - 2 - m), w0, w1);
+        } else {
+            store_u64x2(st + m, 0, 0);
+            store_u64x2(A.X + m, 0, 0);
+        }
+        // e, k1: position p holds coefficient 2n-2-p for n-1 <= p <= 2n-2
+        const bool v0 = m + 1 >= n, v1 = m + 2 >= n && m + 2 < N;
+        const int64_t* Ce = C + n;
+        const int64_t* Ck = C + 2 * n;
+        const int64_t e0 = v0 ? Ce[N - 2 - m] : 0, e1 = v1 ? Ce[N - 3 - m] : 0;
+        const int64_t q0 = v0 ? Ck[N - 2 - m] : 0, q1 = v1 ? Ck[N - 3 - m] : 0;
+        derive_flag(A.flags, 1, 0, derive_check_z(e0, A.e_bound) | derive_check_z(e1, A.e_bound));
+        derive_flag(A.flags, 2, 0, derive_check_z(q0, A.k1_bound) | derive_check_z(q1, A.k1_bound));
+        store_u64x2(const_cast<u64*>(A.e) + m, drv::gl_assign(e0), drv::gl_assign(e1));
+        store_u64x2(const_cast<u64*>(A.k1) + m, drv::gl_assign(q0), drv::gl_assign(q1));
+        return;
+    }
+    const int i = (int)blockIdx.y - 1;
+    u64* at = const_cast<u64*>(A.ais[i]);
+    u64* lo = A.X + (size_t)(1 + 2 * i) * N;
+    u64* hi = lo + N;
+    if (m < n) {
+        const u64x2_t c = load16(C + (3 + (size_t)i) * n + (n - 2 - m));
+        const int64_t z0 = (int64_t)c.x, z1 = (int64_t)c.y;
+        derive_flag(A.flags, 3, i, derive_check_z(z0, A.mod[i].half) | derive_check_z(z1, A.mod[i].half));
+        store_u64x2(at + m, drv::gl_assign(z1), drv::gl_assign(z0));
+        store_u64x2(lo + (n - 2 - m), (u64)z0 & 0xFFFFFFFFULL, (u64)z1 & 0xFFFFFFFFULL);
+        store_u64x2(hi + (n - 2 - m), drv::gl_assign(z0 >> 32), drv::gl_assign(z1 >> 32));
+    } else {
+        store_u64x2(at + m, 0, 0);
+        store_u64x2(lo + m, 0, 0);
+        store_u64x2(hi + m, 0, 0);
+    }
+}
 __global__ __launch_bounds__(TPB) void k_derive_mul(u64* __restrict__ X, int log2_len) {
     const size_t N = (size_t)1 << log2_len;
     const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
@@ -3388,6 +3442,10 @@ __global__ __launch_bounds__(TPB) void k_derive_combine(DeriveArgs A) {
 void derive_unpack(hipStream_t st, const DeriveArgs& a) {
     const size_t N = (size_t)2 << a.n_log2;
     k_derive_unpack<<<dim3((unsigned)((N + TPB - 1) / TPB), (unsigned)a.k + 1), TPB, 0, st>>>(a);
+}
+void derive_pack(hipStream_t st, const DeriveArgs& a, const int64_t* compact) {
+    const size_t n = (size_t)1 << a.n_log2;
+    k_derive_pack<<<dim3((unsigned)((n + TPB - 1) / TPB), (unsigned)a.k + 1), TPB, 0, st>>>(a, compact);
 }
 void derive_mul(hipStream_t st, u64* X, int log2_len, int batch) {
     const size_t N = (size_t)1 << log2_len;

@@ -379,6 +379,8 @@ void ntt_batch(hipStream_t st, u64* data, int log2n, size_t batch, const u64* W,
 // arithmetic shift), so every coefficient of lo * s and of hi * s stays far below p / 2 in magnitude and the NTT gives the integers.
 //   derive_unpack   laid-out tables -> X = [s | lo_0 | hi_0 | lo_1 | ...], 2k+1 ascending-degree, zero-padded vectors of 2n words;
 //                   checks every input word (canonical, inside its bound, zero where the layout pads)
+//   derive_pack     (hg_prove_encryptions) signed ascending coefficients -> the same X, the same bound checks, and the laid-out
+//                   input tables themselves (descending degree, p - |z|, padding zeros), in one pass
 //   ntt_batch(X, 2k+1 forward), derive_mul (X[b] *= X[0]), ntt_batch(X + 2n, 2k inverse)
 //   derive_combine  h = hi 2^32 + lo + e + k0_i k1 in 128 bits, reduced by X^n + 1 and q_i -> the three tables at their laid-out
 //                   positions (descending degree, zero padding included); checks the quotients and the range bounds
@@ -400,6 +402,9 @@ struct DeriveArgs {
     int n_log2, k;
 };
 void derive_unpack(hipStream_t st, const DeriveArgs& a);
+// hg_prove_encryptions: derive_unpack's X and flag bits from the compact copy [s | e | k1 | a_0 .. a_{k-1}] of signed coefficients in
+// ascending degree ((3+k) n words, 16-byte aligned, n >= 2); a.s, a.e, a.k1, a.ais[] (16-byte aligned) are WRITTEN: the laid-out tables
+void derive_pack(hipStream_t st, const DeriveArgs& a, const int64_t* compact);
 void derive_mul(hipStream_t st, u64* X, int log2_len, int batch);   // X[b][i] *= X[0][i], 1 <= b <= batch
 void derive_combine(hipStream_t st, const DeriveArgs& a);
 

@@ -122,6 +122,7 @@ hg_ctx::~hg_ctx() {
     hg::pending_shard_drop(this);
     hg::prove_cache_drop(this);
     hg::verify_batch_drop(this);
+    hg::enc_pipe_drop(this);
     if (scratch_values) hg::values_free(scratch_values);
     for (auto& v : stream_values) if (v) hg::values_free(v);
     for (auto& p : stream_pinned) if (p) (void)hipHostFree(p);
@@ -1321,6 +1322,220 @@ std::vector<ProveResult> prove_stream(hg_ctx* ctx, const hg_pk* pk, const std::v
     }
     finish();
     hip_check(hipStreamSynchronize(ctx->stream3), "stream3");
+    if (total_ms) *total_ms = wall_ms() - t_all;
+    return out;
+}
+
+// ---- hg_prove_encryptions: prove_stream fed by the derivation instead of finished witnesses ------------------------------------------
+// What the pipeline keeps per context, sized for one key: the derivation's work buffers (X and the NTT scratch, (2k+1) 2^L words each -
+// NOT the context arena, which the prover uses while the derivation runs), the compact coefficients of one encryption on both sides of
+// the bus, one set of flag words per table set, the copy-back stream and, once handles are asked for, page-locked staging of the seven
+// tables per table set.
+struct EncPipe {
+    uint64_t pk_serial = 0;
+    int device = 0;
+    hipStream_t copy_stream = nullptr;
+    u64* d_work = nullptr;            // X | scratch
+    int64_t* d_compact = nullptr;     // (3+k) n
+    int64_t* h_compact = nullptr;     // pinned
+    u32* d_flags = nullptr;           // 2 x DRV_FLAG_WORDS
+    u32* h_flags = nullptr;           // pinned, 2 x DRV_FLAG_WORDS
+    u64* h_back[2] = {nullptr, nullptr};   // pinned: s | e | k1 | ais | r1is | r2is | ct0is of one item each
+    hipEvent_t ev_t0[2] = {}, ev_t1[2] = {}, ev_derived[2] = {}, ev_flags[2] = {}, ev_copied[2] = {};
+    ~EncPipe() {
+        (void)hipSetDevice(device);
+        if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
+        if (d_work) (void)hipFree(d_work);
+        if (d_compact) (void)hipFree(d_compact);
+        if (d_flags) (void)hipFree(d_flags);
+        if (h_compact) (void)hipHostFree(h_compact);
+        if (h_flags) (void)hipHostFree(h_flags);
+        for (auto p : h_back) if (p) (void)hipHostFree(p);
+        for (auto* evs : {ev_t0, ev_t1, ev_derived, ev_flags, ev_copied}) for (int q = 0; q < 2; q++) if (evs[q]) (void)hipEventDestroy(evs[q]);
+    }
+};
+void enc_pipe_drop(hg_ctx* ctx) {
+    if (!ctx->enc_pipe) return;
+    if (ctx->stream3) (void)hipStreamSynchronize(ctx->stream3);
+    delete static_cast<EncPipe*>(ctx->enc_pipe);
+    ctx->enc_pipe = nullptr;
+}
+static EncPipe* enc_pipe_get(hg_ctx* ctx, const hg_pk* pk, bool want_w) {
+    const Params& p = pk->params;
+    const size_t SZ = p.SZ(), PZ = p.PZ(), k = (size_t)p.k;
+    EncPipe* E = static_cast<EncPipe*>(ctx->enc_pipe);
+    if (E && E->pk_serial != pk->serial) { enc_pipe_drop(ctx); E = nullptr; }
+    if (!E) {
+        std::unique_ptr<EncPipe> N(new EncPipe());
+        N->pk_serial = pk->serial; N->device = ctx->device;
+        hip_check(hipStreamCreateWithFlags(&N->copy_stream, hipStreamNonBlocking), "hipStreamCreate");
+        hip_check(hipMalloc((void**)&N->d_work, 2 * (2 * k + 1) * SZ * 8), "hipMalloc(derivation work buffers)");
+        hip_check(hipMalloc((void**)&N->d_compact, (3 + k) * PZ * 8), "hipMalloc(compact coefficients)");
+        hip_check(hipMalloc((void**)&N->d_flags, 2 * dev::DRV_FLAG_WORDS * sizeof(u32)), "hipMalloc(derive flags)");
+        hip_check(hipHostMalloc((void**)&N->h_compact, (3 + k) * PZ * 8, hipHostMallocDefault), "hipHostMalloc(compact coefficients)");
+        hip_check(hipHostMalloc((void**)&N->h_flags, 2 * dev::DRV_FLAG_WORDS * sizeof(u32), hipHostMallocDefault), "hipHostMalloc(derive flags)");
+        for (int q = 0; q < 2; q++) {
+            hip_check(hipEventCreate(&N->ev_t0[q]), "hipEventCreate"); hip_check(hipEventCreate(&N->ev_t1[q]), "hipEventCreate");
+            hip_check(hipEventCreateWithFlags(&N->ev_derived[q], hipEventDisableTiming), "hipEventCreate");
+            hip_check(hipEventCreateWithFlags(&N->ev_flags[q], hipEventDisableTiming), "hipEventCreate");
+            hip_check(hipEventCreateWithFlags(&N->ev_copied[q], hipEventDisableTiming), "hipEventCreate");
+        }
+        ctx->enc_pipe = E = N.release();
+    }
+    if (want_w)
+        for (auto& b : E->h_back)
+            if (!b) hip_check(hipHostMalloc((void**)&b, ((3 + 3 * k) * SZ + k * PZ) * 8, hipHostMallocDefault), "hipHostMalloc(witness copy-back staging)");
+    return E;
+}
+// a host copy by all host threads (pieces of 64 KiB), as the gather of witness_fill
+static void par_copy(void* dst, const void* src, size_t bytes) {
+    const size_t piece = (size_t)1 << 16, np = (bytes + piece - 1) / piece;
+    [[maybe_unused]] const int nt = (int)std::max<size_t>(1, std::min<size_t>({(size_t)hg_omp_threads(), 32, np}));
+#pragma omp parallel for schedule(static) num_threads(nt)
+    for (long long q = 0; q < (long long)np; q++) {
+        const size_t o = (size_t)q * piece;
+        memcpy((char*)dst + o, (const char*)src + o, std::min(piece, bytes - o));
+    }
+}
+// Schedule, per item i (table set i & 1), in the steady state (both sets have their launch graph):
+//   host: wait for item i's flag words (its derivation ran under prove i-1) - a refused item is never proven;
+//         launch prove i behind prove i-1; wait for prove i-1, replay its transcript, take its handle out of the staging;
+//         stage item i+1's coefficients, enqueue on stream3 into the OTHER set: one copy, k_derive_pack, NTTs, derive_mul,
+//         derive_combine, [event] circuit_levels, [ev_ready]; on the copy stream behind [event]: flag words, then the tables of the handle.
+// Walked proves (the first two per table set, the recording third, option "graph" = 0) run one after the other as in prove_stream;
+// the derivation of the next item still runs beside them, in its own buffers.
+std::vector<EncResult> prove_encryptions(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e, const int64_t* const* k1,
+                                         const int64_t* const* a, size_t n_enc, bool want_w, double* total_ms) {
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    const double t_all = wall_ms();
+    const Params& p = pk->params;
+    const HCircuit& c = pk->circuit;
+    dev::DeriveArgs plan;
+    derive_plan(p, &plan);   // (parameters the derivation cannot serve are an error of the call, before anything is enqueued)
+    std::vector<EncResult> out(n_enc);
+    if (!n_enc) return out;
+    const size_t SZ = p.SZ(), PZ = p.PZ(), k = (size_t)p.k;
+    if (c.input_ids.size() != 3 + 2 * k + 1) throw Error("hg_prove_encryptions: unexpected input nodes");
+    if (!ctx->stream3) {
+        hip_check(hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking), "hipStreamCreate");
+        for (auto& ev : ctx->ev_ready) hip_check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
+    }
+    if (ctx->stream_values[0] && ctx->stream_values_serial != pk->serial)
+        for (auto& v : ctx->stream_values) { values_free(v); v = nullptr; }
+    if (!ctx->stream_values[0]) {
+        for (auto& v : ctx->stream_values) v = values_alloc(ctx, pk);
+        ctx->stream_values[0]->res_limit = ctx->res_cap / 2;
+        ctx->stream_values[1]->res_base = ctx->res_cap / 2;
+        ctx->stream_values_serial = pk->serial;
+    }
+    hg_values** V = ctx->stream_values;
+    EncPipe* E = enc_pipe_get(ctx, pk, want_w);
+    hipStream_t s3 = ctx->stream3, s4 = E->copy_stream;
+    // whatever happens, nothing of this run is left in flight on the two side streams when the call returns
+    struct Drain { hipStream_t a, b; ~Drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); } } drain{s3, s4};
+    dev::DeriveArgs A[2];
+    for (int q = 0; q < 2; q++) {
+        hg_values* v = V[q];
+        if (v->sizes[c.input_ids[3 + 2 * k]] != k * PZ || v->ct0is_len != k * SZ || !v->d_ct0is) throw Error("hg_prove_encryptions: table size mismatch");
+        auto dv = [&](size_t x) { return const_cast<u64*>(v->d_vals[c.input_ids[x]]); };
+        A[q] = plan;
+        A[q].s = dv(0); A[q].e = dv(1); A[q].k1 = dv(2);
+        for (size_t i = 0; i < k; i++) { A[q].ais[i] = dv(3 + i); A[q].r1is[i] = dv(3 + k + i); }
+        A[q].r2is = dv(3 + 2 * k);
+        A[q].ct0is = const_cast<u64*>(v->d_ct0is);
+        A[q].X = E->d_work;
+        A[q].flags = E->d_flags + (size_t)q * dev::DRV_FLAG_WORDS;
+        for (size_t x = 0; x < 3 + k; x++)
+            if (((uintptr_t)dv(x) & 15) != 0 || v->sizes[c.input_ids[x]] != SZ) throw Error("hg_prove_encryptions: an input table is not laid out for 16-byte stores");
+    }
+    u64* scratch = E->d_work + (2 * k + 1) * SZ;
+    // derivation + evaluation of item i into table set `set`, on stream3; copy-back behind the derivation on the copy stream
+    auto fill = [&](size_t i, int set) {
+        int64_t* h = E->h_compact;   // (its last DMA, item i-1's, is complete: that item's flag words have been waited for)
+        par_copy(h, s[i], PZ * 8); par_copy(h + PZ, e[i], PZ * 8); par_copy(h + 2 * PZ, k1[i], PZ * 8); par_copy(h + 3 * PZ, a[i], k * PZ * 8);
+        if (want_w) hip_check(hipStreamWaitEvent(s3, E->ev_copied[set], 0), "stream wait");   // (the handle of the set's last item has left its tables)
+        hip_check(hipEventRecord(E->ev_t0[set], s3), "event record");
+        hip_check(hipMemcpyAsync(E->d_compact, h, (3 + k) * PZ * 8, hipMemcpyHostToDevice, s3), "upload coefficients");
+        hip_check(hipMemsetAsync(A[set].flags, 0, dev::DRV_FLAG_WORDS * sizeof(u32), s3), "clear derive flags");
+        dev::derive_pack(s3, A[set], E->d_compact);
+        dev::ntt_batch(s3, A[set].X, p.L, 2 * k + 1, pk->w_fwd.at(p.L), 1, scratch);
+        dev::derive_mul(s3, A[set].X, p.L, 2 * (int)k);
+        dev::ntt_batch(s3, A[set].X + SZ, p.L, 2 * k, pk->w_inv.at(p.L), gl_inv(gl_from_u64(SZ)), scratch);
+        dev::derive_combine(s3, A[set]);
+        hip_check(hipGetLastError(), "witness derivation: kernel launch");
+        hip_check(hipEventRecord(E->ev_derived[set], s3), "event record");
+        circuit_levels(pk, V[set], s3);
+        hip_check(hipEventRecord(E->ev_t1[set], s3), "event record");
+        hip_check(hipEventRecord(ctx->ev_ready[set], s3), "event record");
+        hip_check(hipStreamWaitEvent(s4, E->ev_derived[set], 0), "stream wait");
+        hip_check(hipMemcpyAsync(E->h_flags + (size_t)set * dev::DRV_FLAG_WORDS, A[set].flags, dev::DRV_FLAG_WORDS * sizeof(u32), hipMemcpyDeviceToHost, s4), "download derive flags");
+        hip_check(hipEventRecord(E->ev_flags[set], s4), "event record");
+        if (want_w) {
+            u64* b = E->h_back[set];
+            auto back = [&](const u64* src, size_t words) { hip_check(hipMemcpyAsync(b, src, words * 8, hipMemcpyDeviceToHost, s4), "download witness table"); b += words; };
+            back(A[set].s, SZ); back(A[set].e, SZ); back(A[set].k1, SZ);
+            for (size_t i2 = 0; i2 < k; i2++) back(A[set].ais[i2], SZ);
+            for (size_t i2 = 0; i2 < k; i2++) back(A[set].r1is[i2], SZ);
+            back(A[set].r2is, k * PZ); back(A[set].ct0is, k * SZ);
+            hip_check(hipEventRecord(E->ev_copied[set], s4), "event record");
+        }
+    };
+    // the flag words of item i: "" or the reason it is refused
+    auto refusal = [&](size_t i, int set) -> std::string {
+        hip_check(hipEventSynchronize(E->ev_flags[set]), "wait for the derive flags");
+        try {
+            derive_check_flags(p, E->h_flags + (size_t)set * dev::DRV_FLAG_WORDS, ("hg_prove_encryptions: encryption " + std::to_string(i)).c_str());
+        } catch (const Error& err) { return err.what(); }
+        return "";
+    };
+    // after prove i has completed: device time of its derivation + evaluation, its handle
+    auto collect = [&](size_t i, int set) {
+        float ms = 0;
+        hip_check(hipEventElapsedTime(&ms, E->ev_t0[set], E->ev_t1[set]), "event elapsed");
+        out[i].witness_gpu_ms = ms;
+        if (!want_w) return;
+        hip_check(hipEventSynchronize(E->ev_copied[set]), "wait for the witness copy-back");
+        Witness& w = out[i].w;
+        const u64* b = E->h_back[set];
+        auto take = [&](std::vector<u64>& dst, size_t words) { dst.resize(words); par_copy(dst.data(), b, words * 8); b += words; };
+        take(w.s, SZ); take(w.e, SZ); take(w.k1, SZ); take(w.ais, k * SZ); take(w.r1is, k * SZ); take(w.r2is, k * PZ); take(w.ct0is, k * SZ);
+    };
+    fill(0, 0);
+    struct Pending { std::shared_ptr<ProveCache> C; size_t idx = 0; double t0 = 0; } pend;
+    auto finish = [&] {
+        if (!pend.C) return;
+        out[pend.idx].r = prove_from_cache(ctx, pend.C.get(), false, true, true, pend.t0, true);
+        pend.C = nullptr;
+        collect(pend.idx, (int)(pend.idx & 1));
+    };
+    for (size_t i = 0; i < n_enc; i++) {
+        const int cur = (int)(i & 1), nxt = cur ^ 1;
+        auto fill_next = [&] { if (i + 1 < n_enc) fill(i + 1, nxt); };   // (V[nxt] was last read by prove i-1, which has completed)
+        out[i].reason = refusal(i, cur);
+        out[i].refused = !out[i].reason.empty();
+        if (out[i].refused) {   // never proven: the tables of this set hold a witness that fails its range checks
+            finish();
+            fill_next();
+            continue;
+        }
+        hip_check(hipStreamWaitEvent(ctx->stream, ctx->ev_ready[cur], 0), "wait for the witness");
+        std::shared_ptr<ProveCache> C = graph_allowed(ctx) ? cache_find(ctx, pk, V[cur], 0, 1) : nullptr;
+        if (C && !(ctx->slow_graph_serial == pk->serial && ctx->slow_graph_share == 1)) {
+            const double t0 = wall_ms();
+            cache_launch(ctx, C.get(), false);
+            finish();
+            fill_next();
+            pend.C = C; pend.idx = i; pend.t0 = t0;
+        } else {
+            finish();
+            fill_next();
+            out[i].r = prove_resident(ctx, pk, V[cur]);
+            collect(i, cur);
+        }
+    }
+    finish();
+    hip_check(hipStreamSynchronize(s3), "stream3");
+    hip_check(hipStreamSynchronize(s4), "copy stream");
     if (total_ms) *total_ms = wall_ms() - t_all;
     return out;
 }

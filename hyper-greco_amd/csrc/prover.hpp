@@ -62,6 +62,7 @@ struct hg_ctx {
     uint64_t stream_values_serial = 0;     // key serial they were laid out for
     hg::u64* stream_pinned[2] = {nullptr, nullptr};   // pinned staging of one witness each (hg_prove_stream): host arrays are pageable
     size_t stream_pinned_words = 0;
+    void* enc_pipe = nullptr;              // prover.hip: EncPipe of hg_prove_encryptions (work buffers, staging, copy-back stream), freed with the context
     hg_values* scratch_values = nullptr;   // hg_prove's resident tables, refilled in place per call (so its launch graph survives)
     uint64_t scratch_serial = 0;           // key serial they were laid out for
     uint64_t no_graph_serial = 0;          // key whose graph capture failed: its proves walk (no retry)
@@ -232,6 +233,13 @@ void witness_derive_into(hg_ctx* ctx, const hg_pk* pk, const u64* s, const u64* 
                          double* total_ms, double* gpu_ms);
 // BfvEncrypt::prove for a run of witnesses, pipelined: upload + circuit.evaluate of witness i+1 overlap the GKR prove of witness i
 std::vector<ProveResult> prove_stream(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Witness*>& ws, double* total_ms);
+// BfvEncrypt::prove for a run of ENCRYPTIONS (signed coefficients, ascending degree: s, e, k1 of n words, a of k*n): derivation and
+// circuit.evaluate of encryption i+1 on the third stream under the prove of encryption i. An item whose derivation checks fail is
+// not proven: refused = true, `reason` names table, modulus and cause. want_w: the host handle of every proven item (all seven tables)
+struct EncResult { ProveResult r; bool refused = false; std::string reason; Witness w; double witness_gpu_ms = 0; };
+std::vector<EncResult> prove_encryptions(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e, const int64_t* const* k1,
+                                         const int64_t* const* a, size_t n_enc, bool want_w, double* total_ms);
+void enc_pipe_drop(hg_ctx* ctx);
 void values_free(hg_values* v);
 void pending_shard_drop(hg_ctx* ctx);
 void ctx_register(hg_ctx* ctx, bool alive);

@@ -150,6 +150,37 @@ int hg_warmup(hg_ctx* ctx, const hg_pk* pk, double* ms);
 int hg_prove_stream(hg_ctx* ctx, const hg_pk* pk, const hg_witness* const* ws, size_t n, uint8_t* proofs, size_t cap_each,
                     size_t* lens, hg_timings* timings);
 
+/* = BfvEncrypt::get_inputs / Poly::{new_padded, new_shifted} [REF sk_encryption_circuit.rs:365-415, poly.rs:20-44] for the four
+ *   polynomials an encryptor holds, as SIGNED coefficients in ASCENDING degree: s, e, k1: n coefficients; a: k*n (modulus-major).
+ *   Writes the laid-out tables hg_witness_derive / hg_witness_from_arrays take (s_t, e_t, k1_t: 2^L words, ais_t: k*2^L): coefficient
+ *   j of s and of a_i at word n-1-j, of e and k1 at word 2n-2-j, every other word zero, a negative z as p - |z| [REF scripts/utils.py:
+ *   4-18]. Host only, no context. Bounds are not checked here (the derivation checks them); INT64_MIN or a null argument: -1. */
+int hg_encryption_layout(const hg_params* params, const int64_t* s, const int64_t* e, const int64_t* k1, const int64_t* a,
+                         uint64_t* s_t, uint64_t* e_t, uint64_t* k1_t, uint64_t* ais_t);
+/* hg_witness_derive and hg_prove for a run of n_enc ENCRYPTIONS under one key, pipelined [REF scripts/circuit_sk.py:18-140 followed by
+ *   sk_encryption_circuit.rs:417-460; the loop a proving service writes around them - the reference has no batch entry]: s[i], e[i],
+ *   k1[i] (n each) and a[i] (k*n) are the signed ascending polynomials of hg_encryption_layout. They cross the bus as they are
+ *   ((3+k) n words, a quarter of the laid-out tables); one kernel lays the tables out on the device, checks every coefficient and
+ *   feeds the derivation; derivation and circuit.evaluate of encryption i+1 run on a third stream, in buffers of their own, into a
+ *   second set of node tables while encryption i is proven. Proof i is written at proofs + i*cap_each, its length to lens[i], and is
+ *   byte-identical to hg_prove of hg_witness_derive of the laid-out inputs. ws (may be NULL): ws[i] = the handle hg_witness_derive
+ *   would return (all seven tables; the caller frees it).
+ *   status[i] = 0 proven, 1 REFUSED: a check of hg_witness_derive failed (a coefficient of s / e / k1 outside its bound, of a_i outside
+ *   [-(q_i-1)/2, (q_i-1)/2], a derived r1_i / r2_i outside its bound, an inexact quotient). A refused encryption is never proven:
+ *   lens[i] = 0, ws[i] = NULL, no proof bytes; reasons (may be NULL) receives at reasons + i*reason_cap the text that names table,
+ *   modulus and cause, NUL-terminated and truncated to reason_cap bytes ("" when proven). The run continues; the other proofs are
+ *   what they would be without the refused item.
+ *   Returns the number of refused encryptions (>= 0; n_enc == 0 returns 0), or -1 on an error of the call: a null argument, no
+ *   context, a host-only key, a proof larger than cap_each, parameters the derivation cannot serve (hg_witness_derive's last error
+ *   class). hg_last_error names the function and, where it applies, the index.
+ *   timings (may be NULL): total_ms = wall clock of the run; prove_ms / gpu_ms / replay_ms = sums over the proven items; witness_ms =
+ *   sum over the proven items of the device time of upload + derivation + evaluation (HIP events on the stream they run on).
+ *   The first proofs of a context + key walk the protocol one after the other (the launch graph of a table set is recorded on its
+ *   third prove, as in hg_prove_stream); after that a proof costs about max(prove, derive + evaluate). */
+int hg_prove_encryptions(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e, const int64_t* const* k1,
+                         const int64_t* const* a, size_t n_enc, uint8_t* proofs, size_t cap_each, size_t* lens, int* status,
+                         hg_witness** ws, char* reasons, size_t reason_cap, hg_timings* timings);
+
 /* = BfvEncrypt::verify [REF sk_encryption_circuit.rs:462-517] (host-side, like the reference's): the witness handle
  *   supplies the public inputs and ct0is. Returns 0 = accepted, 1 = rejected (reason via hg_last_error), < 0 = error.
  *   Works with a host-only key (hg_setup(NULL, ..)).
