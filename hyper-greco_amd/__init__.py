@@ -39,7 +39,7 @@ EXPORTS = [
     "hg_last_error", "hg_device_count", "hg_create", "hg_destroy", "hg_set_option", "hg_params_builtin", "hg_params_derive", "hg_grand_product", "hg_fold", "hg_setup", "hg_pk_free",
     "hg_pk_lasso_layout", "hg_pk_info", "hg_pk_node_eq_form", "hg_witness_from_json", "hg_witness_synthetic", "hg_witness_from_arrays", "hg_witness_derive", "hg_witness_derive_into",
     "hg_witness_get", "hg_witness_free", "hg_prove", "hg_warmup", "hg_prove_stream", "hg_encryption_layout", "hg_prove_encryptions", "hg_verify", "hg_verify_device", "hg_verify_device_mode", "hg_verify_device_batch", "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_mle_eval",
-    "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
+    "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_prove_encryptions_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
 ]
 
 
@@ -567,13 +567,22 @@ def prove_encryptions(ctx, pk, encs, cap_each=1 << 20, witnesses=True, reason_ca
     of encryption i+1 run under the prove of encryption i. Returns (proofs, statuses, reasons, witnesses, timings): proofs[i] the
     bytes (None when refused), statuses[i] 0 proven / 1 refused, reasons[i] the refusal's text, witnesses[i] the Witness handle of a
     proven item (None when refused or witnesses=False)."""
+    return _prove_encryptions(lib().hg_prove_encryptions, ctx, pk, encs, cap_each, witnesses, reason_cap)
+
+
+def prove_encryptions_bn254(ctx, pk, encs, cap_each=1 << 24, witnesses=True, reason_cap=256):
+    """hg_prove_encryptions_bn254: prove_encryptions over bn256::Fr (proofs of 32-byte big-endian elements, each the bytes
+    Context.prove_bn254 gives for Witness.derive of the laid-out encryption). Same arguments, same 5-tuple."""
+    return _prove_encryptions(lib().hg_prove_encryptions_bn254, ctx, pk, encs, cap_each, witnesses, reason_cap)
+
+
+def _prove_encryptions(fn, ctx, pk, encs, cap_each, witnesses, reason_cap):
     n = len(encs)
     arrs = [_encryption_arrays(pk.params, *enc) for enc in encs]
-    L = lib()
     pp = C.POINTER(i64p)
-    L.hg_prove_encryptions.argtypes = [C.c_void_p, C.c_void_p, pp, pp, pp, pp, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
-                                       C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t, C.POINTER(HgTimings)]
-    L.hg_prove_encryptions.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, pp, pp, pp, pp, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                   C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t, C.POINTER(HgTimings)]
+    fn.restype = C.c_int
     cols = [(i64p * max(n, 1))(*[x[f].ctypes.data_as(i64p) for x in arrs]) for f in range(4)]
     buf = (C.c_uint8 * (cap_each * max(n, 1)))()
     lens = (C.c_size_t * max(n, 1))()
@@ -581,7 +590,7 @@ def prove_encryptions(ctx, pk, encs, cap_each=1 << 20, witnesses=True, reason_ca
     hs = (C.c_void_p * max(n, 1))() if witnesses else None
     reasons = C.create_string_buffer(max(n, 1) * reason_cap)
     tm = HgTimings()
-    rc = L.hg_prove_encryptions(ctx.h if ctx is not None else None, pk.h, *cols, n, buf, cap_each, lens, status, hs, reasons, reason_cap, C.byref(tm))
+    rc = fn(ctx.h if ctx is not None else None, pk.h, *cols, n, buf, cap_each, lens, status, hs, reasons, reason_cap, C.byref(tm))
     if rc < 0:
         raise HgError(lib().hg_last_error().decode())
     raw, rr = memoryview(buf), reasons.raw

@@ -1857,6 +1857,7 @@ void ntt_bn254(hg_ctx* ctx, const u64* in4, int log2n, bool inverse, size_t batc
 static void lasso_prove_bn254_impl(hg_ctx* ctx, const hg_pk* pk, const u64* in4, const Fr* d_in_mont, size_t chain_skip, std::vector<uint8_t>& proof,
                                    u64* claim_out, const std::function<void()>* mid = nullptr, int mid_at = 0);
 #include "bn254_gkr.inc"
+#include "bn254_encpipe.inc"
 #include "bn254_verify.inc"
 #include "bn254_verify_batch.inc"
 

@@ -39,6 +39,24 @@ __global__ __launch_bounds__(256) void k_bn_lift_jobs(LiftJobs J) {
         out[i] = v < (1ULL << 63) ? fr_to_mont(fr_make(v, 0, 0, 0)) : fr_sub(fr_zero(), fr_to_mont(fr_make(GL_P - v, 0, 0, 0)));
     }
 }
+// The same for tables that lie in device memory already (hg_prove_encryptions_bn254: the derivation wrote them): a lane reads two words
+// as one 16-byte load and writes two whole elements. A zero word - every word the layout pads with, half of most tables - is stored as
+// the zero element without the Montgomery product (a wave of padding skips the branch). Tables: 16-byte aligned, even length.
+__device__ __forceinline__ Fr fr_lift_signed(u64 v) {
+    Fr r = fr_zero();
+    if (v) r = v < (1ULL << 63) ? fr_to_mont(fr_make(v, 0, 0, 0)) : fr_sub(fr_zero(), fr_to_mont(fr_make(GL_P - v, 0, 0, 0)));
+    return r;
+}
+__global__ __launch_bounds__(256) void k_bn_lift_pairs(LiftJobs J) {
+    const ulonglong2* __restrict__ in = reinterpret_cast<const ulonglong2*>(J.src[blockIdx.y]);
+    Fr* __restrict__ out = J.dst[blockIdx.y];
+    const size_t half = J.len[blockIdx.y] / 2;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < half; i += (size_t)gridDim.x * 256) {
+        const ulonglong2 v = in[i];
+        out[2 * i] = fr_lift_signed(v.x);
+        out[2 * i + 1] = fr_lift_signed(v.y);
+    }
+}
 
 struct BnPtrs { const Fr* p[dev::PS_MAX_PAIRS]; };
 // Vanilla node evaluation over Fr (same gate-major wiring as k_gate_eval)
@@ -529,99 +547,106 @@ struct BnValues {
     std::map<std::pair<int, int>, const Fr*> W;  // (log2n, inverse) -> w^i for i < 2^log2n, shared by the NTTs and the DFT-row tables
 };
 
-static void bn_witness_gen(hg_ctx* ctx, const hg_pk* pk, const Witness& w, DevPool& pool, BnValues& V) {
-    // Circuit::evaluate on the device, level by level (Vanilla nodes: gate-major kernel; FFT nodes of one level and direction are
-    // laid out contiguously and transformed as one batch), as the Goldilocks witness_gen does
-    const HCircuit& c = pk->circuit;
-    const Params& p = pk->params;
-    hipStream_t st = ctx->stream;
-    const bool times = hg_times("bn");   // read at every call (host.hpp)
-    const double tw0 = wall_ms();
-    auto stamp = [&](const char* what) { if (times) fprintf(stderr, "[hg bn] witness %8.3f ms  %s\n", wall_ms() - tw0, what); };
-    const size_t nn = c.nodes.size();
-    std::vector<int> level(nn, 0);
+// Witness generation over Fr = Circuit::evaluate on the device, level by level (Vanilla nodes: gate-major kernel; FFT nodes of one
+// level and direction are laid out contiguously and transformed as one batch), as the Goldilocks witness_gen does. Two parts:
+//   bn_witness_layout   where every node table lies, and the omega tables (they depend on the key only);
+//   bn_witness_enqueue  lift of the input tables, FFT groups, gate maps - launches on the stream passed in and nothing else.
+struct BnLayout {
+    std::vector<int> level, order;   // `order` keeps a (level, direction, size) group of FFT nodes contiguous in memory
     int maxl = 0;
-    for (int id : c.topo) { for (int pr : c.nodes[id].preds) level[id] = std::max(level[id], level[pr] + 1); maxl = std::max(maxl, level[id]); }
-    std::vector<int> order(nn);
-    for (size_t i = 0; i < nn; i++) order[i] = (int)i;
-    auto key = [&](int id) { const HNode& n = c.nodes[id]; return std::make_tuple(n.kind == NK_FFT ? 1 : 0, level[id], n.inverse ? 1 : 0, n.log2_size, id); };
-    std::sort(order.begin(), order.end(), [&](int x, int y) { return key(x) < key(y); });
-    size_t total = 0;
-    for (size_t id = 0; id < nn; id++) total += (size_t)1 << c.nodes[id].log2_out();
-    Fr* base = pool.get<Fr>(total);
+    size_t total = 0;                // elements of all node tables
+    size_t max_grp = 1;              // elements of the largest FFT group: the transforms' scratch
+};
+// the gate constants must be non-negative integers below 2^63 (they are lifted into Fr as such): a property of the KEY, checked
+// once per key - walking the ~10^7 gate terms of the headline circuit on the host took 8 ms of every witness generation
+static void bn_check_gate_constants(const hg_pk* pk) {
+    static std::mutex mu;
+    static std::vector<uint64_t> checked;
+    std::lock_guard<std::mutex> lk(mu);
+    if (std::find(checked.begin(), checked.end(), pk->serial) != checked.end()) return;
+    for (const HNode& n : pk->circuit.nodes) {
+        if (n.kind != NK_VANILLA) continue;
+        for (auto& t : n.lin) if (t.c >> 63) throw Error("bn254: gate constant is not a non-negative integer below 2^63");
+        for (auto& t : n.mul) if (t.c >> 63) throw Error("bn254: gate constant is not a non-negative integer below 2^63");
+        for (auto& t : n.w0) if (t.c >> 63) throw Error("bn254: gate constant is not a non-negative integer below 2^63");
+    }
+    if (checked.size() > 64) checked.clear();
+    checked.push_back(pk->serial);
+}
+// get(n): n elements of device memory (the context arena for one prove, memory of its own for a pipeline). share_w: a table set of the
+// same key whose omega tables this one reads too (null: they are built, on `st`)
+template <typename Get>
+static BnLayout bn_witness_layout(const hg_pk* pk, hipStream_t st, Get&& get, size_t ct0is_len, BnValues& V, const BnValues* share_w = nullptr) {
+    const HCircuit& c = pk->circuit;
+    BnLayout Y;
+    const size_t nn = c.nodes.size();
+    Y.level.assign(nn, 0);
+    for (int id : c.topo) { for (int pr : c.nodes[id].preds) Y.level[id] = std::max(Y.level[id], Y.level[pr] + 1); Y.maxl = std::max(Y.maxl, Y.level[id]); }
+    Y.order.resize(nn);
+    for (size_t i = 0; i < nn; i++) Y.order[i] = (int)i;
+    auto key = [&](int id) { const HNode& n = c.nodes[id]; return std::make_tuple(n.kind == NK_FFT ? 1 : 0, Y.level[id], n.inverse ? 1 : 0, n.log2_size, id); };
+    std::sort(Y.order.begin(), Y.order.end(), [&](int x, int y) { return key(x) < key(y); });
+    for (size_t id = 0; id < nn; id++) Y.total += (size_t)1 << c.nodes[id].log2_out();
+    Fr* base = get(Y.total);
     V.node.assign(nn, nullptr);
     {
         size_t off = 0;
-        for (int id : order) { V.node[id] = base + off; off += (size_t)1 << c.nodes[id].log2_out(); }
+        for (int id : Y.order) { V.node[id] = base + off; off += (size_t)1 << c.nodes[id].log2_out(); }
     }
-    V.ct0is = pool.get<Fr>(w.ct0is.size());
+    V.ct0is = get(ct0is_len);
+    if (share_w) V.W = share_w->W;
     for (size_t id = 0; id < nn; id++) {
         const HNode& n = c.nodes[id];
         if (n.kind != NK_FFT || V.W.count({n.log2_size, (int)n.inverse})) continue;
         if (n.log2_size > 28) throw Error("bn254: two-adicity is 28");
         const size_t N = (size_t)1 << n.log2_size;
-        Fr* W = pool.get<Fr>(N);
+        Fr* W = get(N);
         Fr wr = fr_root_of_unity(n.log2_size);
         if (n.inverse) wr = fr_inv(wr);
         k_bn_powers<<<grid_of(N), 256, 0, st>>>(W, wr, N);
         V.W[{n.log2_size, (int)n.inverse}] = W;
     }
-    {   // the gate constants must be non-negative integers below 2^63 (they are lifted into Fr as such): a property of the KEY, checked
-        // once per key - walking the ~10^7 gate terms of the headline circuit on the host took 8 ms of every witness generation
-        static std::mutex mu;
-        static std::vector<uint64_t> checked;
-        std::lock_guard<std::mutex> lk(mu);
-        if (std::find(checked.begin(), checked.end(), pk->serial) == checked.end()) {
-            for (const HNode& n : c.nodes) {
-                if (n.kind != NK_VANILLA) continue;
-                for (auto& t : n.lin) if (t.c >> 63) throw Error("bn254: gate constant is not a non-negative integer below 2^63");
-                for (auto& t : n.mul) if (t.c >> 63) throw Error("bn254: gate constant is not a non-negative integer below 2^63");
-                for (auto& t : n.w0) if (t.c >> 63) throw Error("bn254: gate constant is not a non-negative integer below 2^63");
-            }
-            if (checked.size() > 64) checked.clear();
-            checked.push_back(pk->serial);
-        }
+    bn_check_gate_constants(pk);
+    std::map<std::tuple<int, int, int>, size_t> grp_sz;
+    for (size_t id = 0; id < nn; id++)
+        if (c.nodes[id].kind == NK_FFT) grp_sz[{Y.level[id], (int)c.nodes[id].inverse, c.nodes[id].log2_size}] += (size_t)1 << c.nodes[id].log2_size;
+    for (auto& kv : grp_sz) Y.max_grp = std::max(Y.max_grp, kv.second);
+    return Y;
+}
+// the input tables of a witness as lift jobs, in NodeId order: s, e, k1, ais.., r1is.., r2is (chain_par! sk_encryption_circuit.rs:408),
+// then ct0is. src(q, len): where table q lies on the device as u64 words
+template <typename Src>
+static size_t bn_lift_jobs(const hg_pk* pk, const BnValues& V, Src&& src, LiftJobs& LJ) {
+    const HCircuit& c = pk->circuit;
+    const Params& p = pk->params;
+    const size_t SZ = p.SZ(), k = (size_t)p.k;
+    memset(&LJ, 0, sizeof(LJ));
+    size_t max_len = 0;
+    auto put = [&](size_t len, Fr* dst) {
+        if (LJ.n >= 64) throw Error("circuit: more than 64 input tables");
+        LJ.src[LJ.n] = src(LJ.n, len); LJ.dst[LJ.n] = dst; LJ.len[LJ.n] = len; LJ.n++;
+        max_len = std::max(max_len, len);
+    };
+    if (c.input_ids.size() != 3 + 2 * k + 1) throw Error("circuit: unexpected input nodes");
+    for (size_t q = 0; q < 3 + 2 * k + 1; q++) {
+        const int id = c.input_ids[q];
+        const size_t len = q < 3 + 2 * k ? SZ : k * p.PZ();
+        if (len != (size_t)1 << c.nodes[id].log2_out()) throw Error("circuit: input size mismatch");
+        put(len, V.node[id]);
     }
-    stamp("tables laid out, omega tables enqueued");
-    const size_t mark = pool.mark();
-    {   // inputs in NodeId order: s, e, k1, ais.., r1is.., r2is (chain_par! sk_encryption_circuit.rs:408): every upload first (a copy from
-        // pageable memory makes the host wait for whatever the stream still holds: no kernel may sit between them), then ONE lift launch
-        const size_t SZ = p.SZ();
-        const size_t n_in = (size_t)(3 + 2 * p.k) * SZ + w.r2is.size() + w.ct0is.size();
-        u64* stage = pool.get<u64>(n_in);
-        LiftJobs LJ;
-        memset(&LJ, 0, sizeof(LJ));
-        size_t idx = 0, soff = 0, max_len = 0;
-        auto put = [&](const u64* src, size_t len, Fr* dst) {
-            if (LJ.n >= 64) throw Error("circuit: more than 64 input tables");
-            hipc(hipMemcpyAsync(stage + soff, src, len * 8, hipMemcpyHostToDevice, st), "upload input");
-            LJ.src[LJ.n] = stage + soff; LJ.dst[LJ.n] = dst; LJ.len[LJ.n] = len; LJ.n++;
-            max_len = std::max(max_len, len);
-            soff += len;
-        };
-        auto put_in = [&](const u64* src, size_t len) {
-            const int id = c.input_ids.at(idx++);
-            if (len != (size_t)1 << c.nodes[id].log2_out()) throw Error("circuit: input size mismatch");
-            put(src, len, V.node[id]);
-        };
-        put_in(w.s.data(), SZ); put_in(w.e.data(), SZ); put_in(w.k1.data(), SZ);
-        for (int i = 0; i < p.k; i++) put_in(&w.ais[i * SZ], SZ);
-        for (int i = 0; i < p.k; i++) put_in(&w.r1is[i * SZ], SZ);
-        put_in(w.r2is.data(), w.r2is.size());
-        put(w.ct0is.data(), w.ct0is.size(), V.ct0is);
-        k_bn_lift_jobs<<<dim3((unsigned)std::min<size_t>((max_len + 255) / 256, 1024), (unsigned)LJ.n), 256, 0, st>>>(LJ);
-    }
-    stamp("inputs uploaded, lift enqueued");
-    size_t max_grp = 1;
-    {
-        std::map<std::tuple<int, int, int>, size_t> grp_sz;
-        for (size_t id = 0; id < nn; id++)
-            if (c.nodes[id].kind == NK_FFT) grp_sz[{level[id], (int)c.nodes[id].inverse, c.nodes[id].log2_size}] += (size_t)1 << c.nodes[id].log2_size;
-        for (auto& kv : grp_sz) max_grp = std::max(max_grp, kv.second);
-    }
-    Fr* tmp = pool.get<Fr>(max_grp);
-    for (int l = 1; l <= maxl; l++) {
-        // FFT groups of this level: `order` keeps a (level, direction, size) group contiguous in memory
+    put(k * SZ, V.ct0is);
+    return max_len;
+}
+// tmp: Y.max_grp elements. pairs: the lift that reads two words per lane (k_bn_lift_pairs: 16-byte aligned tables of even length)
+static void bn_witness_enqueue(const hg_pk* pk, const BnLayout& Y, const BnValues& V, const LiftJobs& LJ, size_t max_len, bool pairs, Fr* tmp, hipStream_t st) {
+    const HCircuit& c = pk->circuit;
+    const size_t nn = c.nodes.size();
+    if (pairs) k_bn_lift_pairs<<<dim3((unsigned)std::min<size_t>((max_len / 2 + 255) / 256, 1024), (unsigned)LJ.n), 256, 0, st>>>(LJ);
+    else k_bn_lift_jobs<<<dim3((unsigned)std::min<size_t>((max_len + 255) / 256, 1024), (unsigned)LJ.n), 256, 0, st>>>(LJ);
+    const std::vector<int>& level = Y.level;
+    const std::vector<int>& order = Y.order;
+    for (int l = 1; l <= Y.maxl; l++) {
+        // FFT groups of this level
         for (size_t q = 0; q < nn;) {
             const int id0 = order[q];
             const HNode& n0 = c.nodes[id0];
@@ -658,7 +683,39 @@ static void bn_witness_gen(hg_ctx* ctx, const hg_pk* pk, const Witness& w, DevPo
             }
         }
     }
-    stamp("circuit enqueued");
+}
+
+// both parts for a host witness, in the context's arena: the tables are uploaded, and the stream is drained before the prover starts
+static void bn_witness_gen(hg_ctx* ctx, const hg_pk* pk, const Witness& w, DevPool& pool, BnValues& V) {
+    const Params& p = pk->params;
+    hipStream_t st = ctx->stream;
+    const bool times = hg_times("bn");   // read at every call (host.hpp)
+    const double tw0 = wall_ms();
+    auto stamp = [&](const char* what) { if (times) fprintf(stderr, "[hg bn] witness %8.3f ms  %s\n", wall_ms() - tw0, what); };
+    const BnLayout Y = bn_witness_layout(pk, st, [&](size_t n) { return pool.get<Fr>(n); }, w.ct0is.size(), V);
+    stamp("tables laid out, omega tables enqueued");
+    const size_t mark = pool.mark();
+    // every upload first (a copy from pageable memory makes the host wait for whatever the stream still holds: no kernel may sit
+    // between them), then ONE lift launch
+    const size_t SZ = p.SZ(), k = (size_t)p.k;
+    if (w.r2is.size() != k * p.PZ() || w.ct0is.size() != k * SZ) throw Error("circuit: input size mismatch");
+    const size_t n_in = (3 + 2 * k) * SZ + w.r2is.size() + w.ct0is.size();
+    u64* stage = pool.get<u64>(n_in);
+    size_t soff = 0;
+    LiftJobs LJ;
+    const size_t max_len = bn_lift_jobs(pk, V, [&](int q, size_t len) {
+        const size_t K = (size_t)p.k, x = (size_t)q;
+        const u64* h = x == 0 ? w.s.data() : x == 1 ? w.e.data() : x == 2 ? w.k1.data() : x < 3 + K ? &w.ais[(x - 3) * SZ] : x < 3 + 2 * K ? &w.r1is[(x - 3 - K) * SZ]
+                       : x == 3 + 2 * K ? w.r2is.data() : w.ct0is.data();
+        hipc(hipMemcpyAsync(stage + soff, h, len * 8, hipMemcpyHostToDevice, st), "upload input");
+        const u64* d = stage + soff;
+        soff += len;
+        return d;
+    }, LJ);
+    stamp("inputs uploaded");
+    Fr* tmp = pool.get<Fr>(Y.max_grp);
+    bn_witness_enqueue(pk, Y, V, LJ, max_len, false, tmp, st);
+    stamp("lift and circuit enqueued");
     hipc(hipStreamSynchronize(st), "bn254 witness generation: sync");
     stamp("drained");
     hipc(hipGetLastError(), "bn254 witness generation: launch");
@@ -1043,10 +1100,25 @@ struct BnProver {
     }
 
     void run(const Witness& w, double* ms) {
-        const HCircuit& c = pk->circuit;
-        const Params& p = pk->params;
         const double t0 = wall_ms();
         bn_witness_gen(ctx, pk, w, pool, V);
+        const double t1 = wall_ms();
+        prove_tables();
+        if (ms) { ms[0] = t1 - t0; ms[1] = wall_ms() - t1; }
+    }
+    // The prove on tables it did not build (hg_prove_encryptions_bn254): `filled` lies outside the arena and is complete once `ready` has
+    // been reached on the stream that filled it - both prover streams wait for that event on the device, the host does not.
+    void run_filled(const BnValues& filled, hipEvent_t ready, double* prove_ms) {
+        const double t1 = wall_ms();
+        V = filled;
+        hipc(hipStreamWaitEvent(ctx->stream, ready, 0), "stream wait");
+        if (ctx->stream2 != ctx->stream) hipc(hipStreamWaitEvent(ctx->stream2, ready, 0), "stream wait");
+        prove_tables();
+        if (prove_ms) *prove_ms = wall_ms() - t1;
+    }
+    void prove_tables() {
+        const HCircuit& c = pk->circuit;
+        const Params& p = pk->params;
         const double t1 = wall_ms();
         // "eval output" (sk_encryption_circuit.rs:444-448): point, ct0is MLE value
         const int ov = p.ct0is_log2();
@@ -1104,8 +1176,6 @@ struct BnProver {
         *out.val = fr_to_mont(*out_slot);
         for (auto& f : replay) f();
         stamp("replayed");
-        const double t2 = wall_ms();
-        if (ms) { ms[0] = t1 - t0; ms[1] = t2 - t1; }
     }
 };
 

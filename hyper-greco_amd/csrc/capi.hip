@@ -792,6 +792,42 @@ int hg_prove_encryptions(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, 
     HG_CATCH(-1)
 }
 
+int hg_prove_encryptions_bn254(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e, const int64_t* const* k1,
+                               const int64_t* const* a, size_t n_enc, uint8_t* proofs, size_t cap_each, size_t* lens, int* status, hg_witness** ws,
+                               char* reasons, size_t reason_cap, hg_timings* timings) {
+    HG_TRY
+    if (ws) for (size_t i = 0; i < n_enc; i++) ws[i] = nullptr;
+    if (!ctx) throw Error("hg_prove_encryptions_bn254: needs a device context (derivation and proving run on the GPU and have no host fallback)");
+    if (!pk || (n_enc && (!s || !e || !k1 || !a || !proofs || !lens || !status))) throw Error("hg_prove_encryptions_bn254: null argument");
+    if (!pk->ctx) throw Error("hg_prove_encryptions_bn254: host-only prover key (created without a context)");
+    for (size_t i = 0; i < n_enc; i++)
+        if (!s[i] || !e[i] || !k1[i] || !a[i]) throw Error("hg_prove_encryptions_bn254: encryption " + std::to_string(i) + ": null polynomial");
+    double total = 0;
+    std::vector<EncResult> rs = bn::prove_encryptions_bn254(ctx, pk, s, e, k1, a, n_enc, ws != nullptr, &total);
+    if (timings) { memset(timings, 0, sizeof(*timings)); timings->total_ms = total; }
+    for (size_t i = 0; i < n_enc; i++)
+        if (!rs[i].refused && rs[i].r.proof.size() > cap_each)
+            throw Error("hg_prove_encryptions_bn254: encryption " + std::to_string(i) + ": proof buffer too small (" + std::to_string(rs[i].r.proof.size()) + " bytes)");
+    int refused = 0;
+    for (size_t i = 0; i < n_enc; i++) {
+        const EncResult& r = rs[i];
+        status[i] = r.refused ? 1 : 0;
+        lens[i] = r.refused ? 0 : r.r.proof.size();
+        if (reasons && reason_cap) {
+            char* dst = reasons + i * reason_cap;
+            const size_t m = std::min(r.reason.size(), reason_cap - 1);
+            memcpy(dst, r.reason.data(), m);
+            dst[m] = 0;
+        }
+        if (r.refused) { refused++; continue; }
+        memcpy(proofs + i * cap_each, r.r.proof.data(), r.r.proof.size());
+        if (ws) ws[i] = new hg_witness{std::move(rs[i].w), pk->params.raw};
+        if (timings) { timings->prove_ms += r.r.prove_ms; timings->witness_ms += r.witness_gpu_ms; }
+    }
+    return refused;
+    HG_CATCH(-1)
+}
+
 int hg_prove_resident_mode(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, int mode, uint8_t* proof, size_t cap, size_t* len, hg_timings* timings) {
     HG_TRY
     if (!ctx || !pk || !v || !pk->ctx || !proof || !len) throw Error("hg_prove_resident_mode: needs a device context, a device prover key and resident values");

@@ -123,6 +123,7 @@ hg_ctx::~hg_ctx() {
     hg::prove_cache_drop(this);
     hg::verify_batch_drop(this);
     hg::enc_pipe_drop(this);
+    hg::bn::bn_enc_pipe_drop(this);
     if (scratch_values) hg::values_free(scratch_values);
     for (auto& v : stream_values) if (v) hg::values_free(v);
     for (auto& p : stream_pinned) if (p) (void)hipHostFree(p);
@@ -692,7 +693,7 @@ static_assert(dev::DRV_MAX_K == HG_MAX_K, "the derive kernels index their per-mo
 //   q_i odd (the quotient by q_i goes through q_i^-1 mod 2^64) and below 2^62 (so q_i << sh shifts by 2 .. 63 bits);
 //   every coefficient of lo * s and hi * s below p / 2 in magnitude (the Goldilocks NTT of size 2n then gives the integers);
 //   every value the combine step reduces by q_i inside the precondition of drv::mod_u128, every quotient below 2^62.
-static void derive_plan(const Params& p, dev::DeriveArgs* a) {
+void derive_plan(const Params& p, dev::DeriveArgs* a) {
     typedef unsigned __int128 u128;
     const hg_params& r = p.raw;
     memset(a, 0, sizeof(*a));
@@ -737,8 +738,20 @@ static void derive_enqueue(hipStream_t st, const dev::DeriveArgs& a, int L, cons
     dev::derive_combine(st, a);
     hip_check(hipGetLastError(), "witness derivation: kernel launch");
 }
+// The same from the COMPACT signed coefficients of an encryption (hg_prove_encryptions, hg_prove_encryptions_bn254): k_derive_pack lays
+// the four input tables out where a.s, a.e, a.k1, a.ais[] point and fills X, the rest is the same
+void derive_enqueue_compact(hipStream_t st, const dev::DeriveArgs& a, const int64_t* compact, int L, const u64* Wf, const u64* Wi, u64* scratch) {
+    const size_t N = (size_t)1 << L;
+    hip_check(hipMemsetAsync(a.flags, 0, dev::DRV_FLAG_WORDS * sizeof(u32), st), "clear derive flags");
+    dev::derive_pack(st, a, compact);
+    dev::ntt_batch(st, a.X, L, (size_t)2 * a.k + 1, Wf, 1, scratch);
+    dev::derive_mul(st, a.X, L, 2 * a.k);
+    dev::ntt_batch(st, a.X + N, L, (size_t)2 * a.k, Wi, gl_inv(gl_from_u64(N)), scratch);
+    dev::derive_combine(st, a);
+    hip_check(hipGetLastError(), "witness derivation: kernel launch");
+}
 // the first failed check as an error that names the table, the modulus and the cause (inputs before derived tables)
-static void derive_check_flags(const Params& p, const u32* flags, const char* who) {
+void derive_check_flags(const Params& p, const u32* flags, const char* who) {
     static const char* names[6] = {"s", "e", "k1", "ais", "r1is", "r2is"};
     for (int t = 0; t < 6; t++)
         for (int i = 0; i < p.k; i++) {
@@ -1388,7 +1401,7 @@ static EncPipe* enc_pipe_get(hg_ctx* ctx, const hg_pk* pk, bool want_w) {
     return E;
 }
 // a host copy by all host threads (pieces of 64 KiB), as the gather of witness_fill
-static void par_copy(void* dst, const void* src, size_t bytes) {
+void par_copy(void* dst, const void* src, size_t bytes) {
     const size_t piece = (size_t)1 << 16, np = (bytes + piece - 1) / piece;
     [[maybe_unused]] const int nt = (int)std::max<size_t>(1, std::min<size_t>({(size_t)hg_omp_threads(), 32, np}));
 #pragma omp parallel for schedule(static) num_threads(nt)
@@ -1456,13 +1469,7 @@ std::vector<EncResult> prove_encryptions(hg_ctx* ctx, const hg_pk* pk, const int
         if (want_w) hip_check(hipStreamWaitEvent(s3, E->ev_copied[set], 0), "stream wait");   // (the handle of the set's last item has left its tables)
         hip_check(hipEventRecord(E->ev_t0[set], s3), "event record");
         hip_check(hipMemcpyAsync(E->d_compact, h, (3 + k) * PZ * 8, hipMemcpyHostToDevice, s3), "upload coefficients");
-        hip_check(hipMemsetAsync(A[set].flags, 0, dev::DRV_FLAG_WORDS * sizeof(u32), s3), "clear derive flags");
-        dev::derive_pack(s3, A[set], E->d_compact);
-        dev::ntt_batch(s3, A[set].X, p.L, 2 * k + 1, pk->w_fwd.at(p.L), 1, scratch);
-        dev::derive_mul(s3, A[set].X, p.L, 2 * (int)k);
-        dev::ntt_batch(s3, A[set].X + SZ, p.L, 2 * k, pk->w_inv.at(p.L), gl_inv(gl_from_u64(SZ)), scratch);
-        dev::derive_combine(s3, A[set]);
-        hip_check(hipGetLastError(), "witness derivation: kernel launch");
+        derive_enqueue_compact(s3, A[set], E->d_compact, p.L, pk->w_fwd.at(p.L), pk->w_inv.at(p.L), scratch);
         hip_check(hipEventRecord(E->ev_derived[set], s3), "event record");
         circuit_levels(pk, V[set], s3);
         hip_check(hipEventRecord(E->ev_t1[set], s3), "event record");

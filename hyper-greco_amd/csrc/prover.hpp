@@ -62,6 +62,7 @@ struct hg_ctx {
     uint64_t stream_values_serial = 0;     // key serial they were laid out for
     hg::u64* stream_pinned[2] = {nullptr, nullptr};   // pinned staging of one witness each (hg_prove_stream): host arrays are pageable
     size_t stream_pinned_words = 0;
+    void* bn_enc_pipe = nullptr;           // bn254.hip: BnEncPipe of hg_prove_encryptions_bn254 (two sets of Fr node tables and everything that feeds them), freed with the context
     void* enc_pipe = nullptr;              // prover.hip: EncPipe of hg_prove_encryptions (work buffers, staging, copy-back stream), freed with the context
     hg_values* scratch_values = nullptr;   // hg_prove's resident tables, refilled in place per call (so its launch graph survives)
     uint64_t scratch_serial = 0;           // key serial they were laid out for
@@ -240,6 +241,18 @@ struct EncResult { ProveResult r; bool refused = false; std::string reason; Witn
 std::vector<EncResult> prove_encryptions(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e, const int64_t* const* k1,
                                          const int64_t* const* a, size_t n_enc, bool want_w, double* total_ms);
 void enc_pipe_drop(hg_ctx* ctx);
+// the same over bn256::Fr (bn254.hip): EncResult::r holds the proof bytes and prove_ms only
+namespace bn {
+std::vector<EncResult> prove_encryptions_bn254(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e, const int64_t* const* k1,
+                                               const int64_t* const* a, size_t n_enc, bool want_w, double* total_ms);
+void bn_enc_pipe_drop(hg_ctx* ctx);
+}
+// pieces of the derivation both pipelines share (prover.hip): the parameter set as the derive kernels read it (throws for a set the
+// derivation cannot serve), the launches from the compact coefficients, the flag words as an error that names table, modulus and cause
+void derive_plan(const Params& p, dev::DeriveArgs* a);
+void derive_enqueue_compact(hipStream_t st, const dev::DeriveArgs& a, const int64_t* compact, int L, const u64* Wf, const u64* Wi, u64* scratch);
+void derive_check_flags(const Params& p, const u32* flags, const char* who);
+void par_copy(void* dst, const void* src, size_t bytes);   // a host copy by all host threads
 void values_free(hg_values* v);
 void pending_shard_drop(hg_ctx* ctx);
 void ctx_register(hg_ctx* ctx, bool alive);

@@ -442,6 +442,31 @@ int hg_verify_device_bn254(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, co
 int hg_verify_device_batch_bn254(hg_ctx* ctx, const hg_pk* pk, const hg_witness* const* ws, const uint8_t* const* proofs,
                                  const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap);
 
+/* hg_witness_derive and hg_prove_bn254 for a run of n_enc ENCRYPTIONS under one key, pipelined: hg_prove_encryptions over bn256::Fr
+ *   [REF scripts/circuit_sk.py:18-140 followed by sk_encryption_circuit.rs:417-460, 614-626; the loop a proving service writes around
+ *   them - the reference has no batch entry]. The contract is that of hg_prove_encryptions: s[i], e[i], k1[i] (n each) and a[i] (k*n)
+ *   are the signed ascending polynomials of hg_encryption_layout and cross the bus as they are ((3+k) n words); one kernel lays the
+ *   tables out on the device and checks every coefficient, the derivation writes r1is, r2is and ct0is beside them, one launch lifts
+ *   all of them into Fr and the circuit is evaluated over Fr - all of it for encryption i+1 on a stream of its own, into a second
+ *   set of node tables, while encryption i is proven; no table visits the host on the way to the prover. Proof i is written at
+ *   proofs + i*cap_each (32-byte big-endian elements), its length to lens[i], and is byte-identical to hg_prove_bn254 of
+ *   hg_witness_derive of the laid-out inputs. ws (may be NULL): ws[i] = the handle hg_witness_derive would return (all seven tables;
+ *   the caller frees it), usable with hg_verify_bn254 and hg_verify_device[_batch]_bn254.
+ *   status[i] = 0 proven, 1 REFUSED (a check of hg_witness_derive failed); a refused encryption is never proven: lens[i] = 0,
+ *   ws[i] = NULL, no proof bytes; reasons (may be NULL) receives at reasons + i*reason_cap the text that names table, modulus and
+ *   cause, NUL-terminated and truncated to reason_cap bytes ("" when proven). The run continues; the other proofs are what they would
+ *   be without the refused item.
+ *   Returns the number of refused encryptions (>= 0; n_enc == 0 returns 0), or -1 on an error of the call: a null argument, no
+ *   context, a host-only key, a proof larger than cap_each, parameters the derivation cannot serve, a key with a gate constant that
+ *   is not below 2^63 (it could not be lifted into Fr). hg_last_error names the function and, where it applies, the index.
+ *   timings (may be NULL): total_ms = wall clock of the run; prove_ms = sum of the proving spans of the proven items (wall clock,
+ *   from the first launch of a prove to its replayed transcript); witness_ms = sum over the proven items of the device time of
+ *   upload + derivation + lift + evaluation (HIP events on the stream they run on). upload_ms, gpu_ms, enqueue_ms, sync_ms and
+ *   replay_ms have no meaning on this path and are 0. */
+int hg_prove_encryptions_bn254(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e, const int64_t* const* k1,
+                               const int64_t* const* a, size_t n_enc, uint8_t* proofs, size_t cap_each, size_t* lens, int* status,
+                               hg_witness** ws, char* reasons, size_t reason_cap, hg_timings* timings);
+
 /* profiling: level 0 off, 1 = events around the selected kernel class only, 2 = every class */
 int hg_profile(hg_ctx* ctx, int level);
 /* selects the class that level 1 times (a name hg_profile_get reported); returns 0, or -1 if there is no such class */
