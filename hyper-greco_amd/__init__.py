@@ -35,10 +35,17 @@ class HgKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double), ("algo_bytes", C.c_double), ("model_bytes", C.c_double), ("hbm_bytes", C.c_double)]
 
 
+class HgInputClaim(C.Structure):
+    """hg_input_claim: a claim hg_verify_public leaves on a secret input (point_off counts coordinates of the points array)."""
+    _fields_ = [("input", C.c_uint32), ("nvars", C.c_uint32), ("point_off", C.c_uint64), ("value", C.c_uint64 * 2)]
+
+
 EXPORTS = [
     "hg_last_error", "hg_device_count", "hg_create", "hg_destroy", "hg_set_option", "hg_params_builtin", "hg_params_derive", "hg_grand_product", "hg_fold", "hg_setup", "hg_pk_free",
     "hg_pk_lasso_layout", "hg_pk_info", "hg_pk_node_eq_form", "hg_witness_from_json", "hg_witness_synthetic", "hg_witness_from_arrays", "hg_witness_derive", "hg_witness_derive_into",
-    "hg_witness_get", "hg_witness_free", "hg_prove", "hg_warmup", "hg_prove_stream", "hg_encryption_layout", "hg_prove_encryptions", "hg_verify", "hg_verify_device", "hg_verify_device_mode", "hg_verify_device_batch", "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_mle_eval",
+    "hg_witness_get", "hg_witness_free", "hg_prove", "hg_warmup", "hg_prove_stream", "hg_encryption_layout", "hg_prove_encryptions", "hg_verify", "hg_verify_device", "hg_verify_device_mode", "hg_verify_device_batch",
+    "hg_instance_from_ciphertext", "hg_instance_from_witness", "hg_instance_free", "hg_instance_coeffs", "hg_instance_get", "hg_pk_claim_shape", "hg_verify_public", "hg_verify_public_device", "hg_claims_settle", "hg_instance_mle",
+    "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_mle_eval",
     "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_prove_encryptions_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
 ]
 
@@ -902,6 +909,127 @@ def verify_device_batch_bn254(ctx, pk, witnesses, proofs, reason_cap=256):
         r = raw[i * reason_cap:(i + 1) * reason_cap].split(b"\0", 1)[0].decode()
         out.append((res[i] == 0, r))
     return out
+
+
+class Instance:
+    """hg_instance: the public instance of one encryption - a_i and ct0_i as signed coefficients (k x n, ascending degree)."""
+
+    def __init__(self, handle, params):
+        self.h = handle
+        self.params = params
+
+    @classmethod
+    def from_ciphertext(cls, params, a, ct0):
+        """hg_instance_from_ciphertext: every coefficient in [-(q_i-1)/2, (q_i-1)/2], else HgError naming table, modulus, index."""
+        kn = params.k * params.n
+        arrs = [np.ascontiguousarray(x, dtype=np.int64).reshape(-1) for x in (a, ct0)]
+        if [x.size for x in arrs] != [kn, kn]:
+            raise ValueError("instance: a and ct0 hold k * n signed coefficients each")
+        L = lib()
+        L.hg_instance_from_ciphertext.argtypes = [C.POINTER(HgParams), i64p, i64p, C.POINTER(C.c_void_p)]
+        h = C.c_void_p()
+        _check(L.hg_instance_from_ciphertext(C.byref(params), arrs[0].ctypes.data_as(i64p), arrs[1].ctypes.data_as(i64p), C.byref(h)))
+        return cls(h, params)
+
+    @classmethod
+    def from_witness(cls, witness):
+        """hg_instance_from_witness: the layout of the handle's ais and ct0is tables inverted."""
+        L = lib()
+        L.hg_instance_from_witness.argtypes = [C.POINTER(HgParams), C.c_void_p, C.POINTER(C.c_void_p)]
+        h = C.c_void_p()
+        _check(L.hg_instance_from_witness(C.byref(witness.params), witness.h, C.byref(h)))
+        return cls(h, witness.params)
+
+    def coeffs(self):
+        """hg_instance_coeffs: (a, ct0) as int64 arrays of k * n coefficients."""
+        kn = self.params.k * self.params.n
+        a, ct0 = np.zeros(kn, dtype=np.int64), np.zeros(kn, dtype=np.int64)
+        L = lib()
+        L.hg_instance_coeffs.argtypes = [C.c_void_p, i64p, i64p]
+        _check(L.hg_instance_coeffs(self.h, a.ctypes.data_as(i64p), ct0.ctypes.data_as(i64p)))
+        return a, ct0
+
+    def table(self, which):
+        """hg_instance_get: the laid-out ais (which 0) or ct0is (which 1) table, as Witness.arrays() holds it."""
+        L = lib()
+        L.hg_instance_get.argtypes = [C.c_void_p, C.c_int, u64p, C.c_size_t]
+        L.hg_instance_get.restype = C.c_int64
+        n = _check(L.hg_instance_get(self.h, which, None, 0))
+        out = np.zeros(n, dtype=np.uint64)
+        _check(L.hg_instance_get(self.h, which, _ptr(out), n))
+        return out
+
+    def mle(self, ctx, which, index, point):
+        """hg_instance_mle: the MLE of ais[index] (which 0) or ct0is (which 1) at an E point (u64 pairs); ctx None: host loop."""
+        point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1)
+        out = np.zeros(2, dtype=np.uint64)
+        L = lib()
+        L.hg_instance_mle.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, u64p, C.c_size_t, u64p]
+        _check(L.hg_instance_mle(ctx.h if ctx is not None else None, self.h, which, index, _ptr(point), point.size // 2, _ptr(out)))
+        return out
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().hg_instance_free.argtypes = [C.c_void_p]
+                lib().hg_instance_free(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
+class InputClaims:
+    """What verify_public leaves open: `claims` (a ctypes array of HgInputClaim) and `points` (u64, two words per coordinate)."""
+
+    def __init__(self, claims, n, points):
+        self.claims, self.n, self.points = claims, n, points
+
+    def as_tuples(self):
+        """[(input, nvars, point words, value words)]: the whole content, for comparisons."""
+        out = []
+        for i in range(self.n):
+            c = self.claims[i]
+            out.append((int(c.input), int(c.nvars), tuple(int(x) for x in self.points[2 * c.point_off:2 * (c.point_off + c.nvars)]), (int(c.value[0]), int(c.value[1]))))
+        return out
+
+
+def pk_claim_shape(pk):
+    """hg_pk_claim_shape: (claims on secret inputs a proof of this key leaves, their coordinates in all)."""
+    L = lib()
+    L.hg_pk_claim_shape.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    a, b = C.c_size_t(0), C.c_size_t(0)
+    _check(L.hg_pk_claim_shape(pk.h, C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def verify_public(pk, instance, proof, mode=0, ctx=None, device=False):
+    """hg_verify_public (device=True: hg_verify_public_device on ctx): the part of BfvEncrypt::verify that the key, the proof, a_i
+    and ct0_i decide. Returns (accepted, reason, InputClaims or None): the claims left on the secret inputs, for claims_settle."""
+    L = lib()
+    nc, nco = pk_claim_shape(pk)
+    claims = (HgInputClaim * max(nc, 1))()
+    points = np.zeros(2 * max(nco, 1), dtype=np.uint64)
+    n = C.c_size_t(0)
+    tail = [C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.hg_verify_public.argtypes = tail
+    L.hg_verify_public_device.argtypes = [C.c_void_p] + tail
+    args = (pk.h, instance.h, mode, proof, len(proof), claims, nc, _ptr(points), nco, C.byref(n))
+    rc = L.hg_verify_public_device(ctx.h if ctx is not None else None, *args) if device else L.hg_verify_public(*args)
+    if rc < 0:
+        raise HgError(lib().hg_last_error().decode())
+    if rc:
+        return False, lib().hg_last_error().decode(), None
+    return True, "", InputClaims(claims, n.value, points)
+
+
+def claims_settle(ctx, params, witness, claims):
+    """hg_claims_settle: every claim of an InputClaims against the witness handle (ctx None: host): (accepted, reason)."""
+    L = lib()
+    L.hg_claims_settle.argtypes = [C.c_void_p, C.POINTER(HgParams), C.c_void_p, C.c_void_p, C.c_size_t, u64p]
+    rc = L.hg_claims_settle(ctx.h if ctx is not None else None, C.byref(params), witness.h, claims.claims, claims.n, _ptr(claims.points))
+    if rc < 0:
+        raise HgError(lib().hg_last_error().decode())
+    return rc == 0, ("" if rc == 0 else lib().hg_last_error().decode())
 
 
 def verify_bn254(pk, witness, proof):

@@ -1009,6 +1009,173 @@ int hg_verify_device_batch(hg_ctx* ctx, const hg_pk* pk, const hg_witness* const
     HG_CATCH(-1)
 }
 
+// ---- verification from the ciphertext (hg.h: hg_verify_public and what goes with it) -------------------------------------------
+static const hg_instance* as_instance(const void* h) { return static_cast<const hg_instance*>(h); }
+
+int hg_instance_from_ciphertext(const hg_params* params, const int64_t* a, const int64_t* ct0, void** out) {
+    HG_TRY
+    if (out) *out = nullptr;
+    if (!params || !a || !ct0 || !out) throw Error("hg_instance_from_ciphertext: null argument");
+    Params p(*params);
+    std::unique_ptr<hg_instance> h(new hg_instance{instance_from_ciphertext(p, a, ct0), *params});
+    *out = h.release();
+    return 0;
+    HG_CATCH(-1)
+}
+
+int hg_instance_from_witness(const hg_params* params, const hg_witness* w, void** out) {
+    HG_TRY
+    if (out) *out = nullptr;
+    if (!params || !w || !out) throw Error("hg_instance_from_witness: null argument");
+    Params p(*params);
+    if (w->params.n != params->n || w->params.k != params->k || w->w.ais.size() != (size_t)p.k * p.SZ() || w->w.ct0is.size() != (size_t)p.k * p.SZ())
+        throw Error("hg_instance_from_witness: the witness was built for other parameters");
+    std::unique_ptr<hg_instance> h(new hg_instance{instance_from_witness(p, w->w), *params});
+    *out = h.release();
+    return 0;
+    HG_CATCH(-1)
+}
+
+void hg_instance_free(void* instance) { delete static_cast<hg_instance*>(instance); }
+
+int hg_instance_coeffs(const void* instance, int64_t* a, int64_t* ct0) {
+    HG_TRY
+    if (!instance || !a || !ct0) throw Error("hg_instance_coeffs: null argument");
+    const Instance& in = as_instance(instance)->inst;
+    memcpy(a, in.a.data(), in.a.size() * 8);
+    memcpy(ct0, in.ct0.data(), in.ct0.size() * 8);
+    return 0;
+    HG_CATCH(-1)
+}
+
+int64_t hg_instance_get(const void* instance, int which, uint64_t* out, size_t cap) {
+    HG_TRY
+    if (!instance) throw Error("hg_instance_get: null instance");
+    if (which != 0 && which != 1) throw Error("hg_instance_get: bad selector");
+    const hg_instance* in = as_instance(instance);
+    Params p(in->params);
+    const size_t n = p.PZ(), SZ = p.SZ(), k = (size_t)p.k, top = which ? SZ - 2 : n - 1;
+    const std::vector<int64_t>& c = which ? in->inst.ct0 : in->inst.a;
+    if (out)
+        for (size_t x = 0; x < std::min(cap, k * SZ); x++) {   // word w of block i: coefficient top - w where there is one, else padding
+            const size_t i = x / SZ, w = x % SZ;
+            const int64_t z = (w <= top && w + n > top) ? c[i * n + (top - w)] : 0;
+            out[x] = z >= 0 ? (u64)z : GL_P - (u64)(-z);
+        }
+    return (int64_t)(k * SZ);
+    HG_CATCH(-1)
+}
+
+int hg_pk_claim_shape(const hg_pk* pk, size_t* n_claims, size_t* n_coords) {
+    HG_TRY
+    if (!pk || !n_claims || !n_coords) throw Error("hg_pk_claim_shape: null argument");
+    claim_shape(pk->params, pk->lasso, pk->circuit, n_claims, n_coords);
+    return 0;
+    HG_CATCH(-1)
+}
+
+// the instance must have been built for the key's parameter set: the walk indexes its coefficients with sizes taken from the key
+static void check_instance(const hg_pk* pk, const hg_instance* in, const char* who) {
+    const hg_params& a = pk->params.raw;
+    const hg_params& b = in->params;
+    const size_t kn = (size_t)a.k * a.n;
+    if (a.n != b.n || a.k != b.k || memcmp(a.qis, b.qis, sizeof(a.qis[0]) * a.k) != 0 || in->inst.a.size() != kn || in->inst.ct0.size() != kn)
+        throw Error(std::string(who) + ": the instance was built for other parameters than the key (n=" + std::to_string(b.n) + " k=" + std::to_string(b.k) + " against n=" +
+                    std::to_string(a.n) + " k=" + std::to_string(a.k) + ", or other moduli)");
+}
+static int verify_public_entry(const char* who, hg_ctx* ctx, bool device, const hg_pk* pk, const void* instance, int mode, const uint8_t* proof, size_t len,
+                               void* claims, size_t claim_cap, uint64_t* points, size_t coord_cap, size_t* n_claims) {
+    if (n_claims) *n_claims = 0;
+    if (device && (!ctx || !pk || !pk->ctx)) throw Error(std::string(who) + ": needs a device context and a device prover key");
+    if (!pk || !instance || !proof || !n_claims) throw Error(std::string(who) + ": null argument");
+    if (mode < 0 || mode > 3) throw Error(std::string(who) + ": unknown mode bits");
+    const hg_instance* in = as_instance(instance);
+    check_instance(pk, in, who);
+    size_t need_claims = 0, need_coords = 0;
+    claim_shape(pk->params, pk->lasso, pk->circuit, &need_claims, &need_coords);
+    if (claim_cap < need_claims || coord_cap < need_coords || (need_claims && !claims) || (need_coords && !points))
+        throw Error(std::string(who) + ": room for " + std::to_string(need_claims) + " claims and " + std::to_string(need_coords) + " coordinates is needed (hg_pk_claim_shape)");
+    std::vector<OpenClaim> open;
+    const std::string why = device ? verify_public_device(ctx, pk, in->inst, proof, len, mode, open)
+                                   : verify_public(pk->params, pk->lasso, pk->circuit, in->inst, proof, len, mode, open);
+    if (!why.empty()) { g_last_error = why; return 1; }
+    size_t coords = 0;
+    for (const OpenClaim& c : open) coords += c.point.size();
+    if (open.size() > claim_cap || coords > coord_cap) throw Error(std::string(who) + ": the walk left more claims than hg_pk_claim_shape counts");
+    hg_input_claim* out = static_cast<hg_input_claim*>(claims);
+    size_t off = 0;
+    for (size_t i = 0; i < open.size(); i++) {
+        out[i].input = (uint32_t)open[i].input;
+        out[i].nvars = (uint32_t)open[i].point.size();
+        out[i].point_off = off;
+        out[i].value[0] = open[i].value.c0; out[i].value[1] = open[i].value.c1;
+        for (const E2& x : open[i].point) { points[2 * off] = x.c0; points[2 * off + 1] = x.c1; off++; }
+    }
+    *n_claims = open.size();
+    return 0;
+}
+
+int hg_verify_public(const hg_pk* pk, const void* instance, int mode, const uint8_t* proof, size_t len, void* claims, size_t claim_cap, uint64_t* points,
+                     size_t coord_cap, size_t* n_claims) {
+    HG_TRY
+    return verify_public_entry("hg_verify_public", nullptr, false, pk, instance, mode, proof, len, claims, claim_cap, points, coord_cap, n_claims);
+    HG_CATCH(-1)
+}
+
+int hg_verify_public_device(hg_ctx* ctx, const hg_pk* pk, const void* instance, int mode, const uint8_t* proof, size_t len, void* claims, size_t claim_cap,
+                            uint64_t* points, size_t coord_cap, size_t* n_claims) {
+    HG_TRY
+    return verify_public_entry("hg_verify_public_device", ctx, true, pk, instance, mode, proof, len, claims, claim_cap, points, coord_cap, n_claims);
+    HG_CATCH(-1)
+}
+
+int hg_claims_settle(hg_ctx* ctx, const hg_params* params, const hg_witness* w, const void* claims, size_t n, const uint64_t* points) {
+    HG_TRY
+    if (!params || !w || (n && (!claims || !points))) throw Error("hg_claims_settle: null argument");
+    Params p(*params);
+    const size_t SZ = p.SZ(), k = (size_t)p.k;
+    const Witness& v = w->w;
+    if (w->params.n != params->n || w->params.k != params->k || v.s.size() != SZ || v.e.size() != SZ || v.k1.size() != SZ || v.ais.size() != k * SZ ||
+        v.r1is.size() != k * SZ || v.r2is.size() != k * p.PZ())
+        throw Error("hg_claims_settle: the witness was built for other parameters");
+    const hg_input_claim* in = static_cast<const hg_input_claim*>(claims);
+    std::vector<OpenClaim> cl(n);
+    for (size_t i = 0; i < n; i++) {
+        if (in[i].input > 3 + 2 * k) throw Error("hg_claims_settle: input " + std::to_string(in[i].input) + " is not an input of the circuit");
+        if (in[i].nvars > 40) throw Error("hg_claims_settle: a claim with " + std::to_string(in[i].nvars) + " coordinates");
+        cl[i].input = in[i].input;
+        cl[i].value = e2(in[i].value[0], in[i].value[1]);
+        cl[i].point.resize(in[i].nvars);
+        for (size_t j = 0; j < in[i].nvars; j++) cl[i].point[j] = e2(points[2 * (in[i].point_off + j)], points[2 * (in[i].point_off + j) + 1]);
+        for (const E2& x : cl[i].point) if (x.c0 >= GL_P || x.c1 >= GL_P) throw Error("hg_claims_settle: non-canonical coordinate");
+        if (cl[i].value.c0 >= GL_P || cl[i].value.c1 >= GL_P) throw Error("hg_claims_settle: non-canonical value");
+    }
+    const std::string why = ctx ? claims_settle_device(ctx, p, v, cl) : claims_settle(p, v, cl);
+    if (why.empty()) return 0;
+    g_last_error = why;
+    return 1;
+    HG_CATCH(-1)
+}
+
+int hg_instance_mle(hg_ctx* ctx, const void* instance, int which, int index, const uint64_t* point, size_t nvars, uint64_t out2[2]) {
+    HG_TRY
+    if (!instance || (nvars && !point) || !out2) throw Error("hg_instance_mle: null argument");
+    const hg_instance* in = as_instance(instance);
+    Params p(in->params);
+    if (which != 0 && which != 1) throw Error("hg_instance_mle: which is 0 (ais[index]) or 1 (ct0is)");
+    if (which == 0 && (index < 0 || index >= p.k)) throw Error("hg_instance_mle: no such modulus");
+    if (nvars != (size_t)(which ? p.ct0is_log2() : p.L)) throw Error("hg_instance_mle: the table has " + std::to_string(which ? p.ct0is_log2() : p.L) + " variables");
+    std::vector<E2> pt(nvars);
+    for (size_t i = 0; i < nvars; i++) {
+        if (point[2 * i] >= GL_P || point[2 * i + 1] >= GL_P) throw Error("hg_instance_mle: non-canonical coordinate");
+        pt[i] = e2(point[2 * i], point[2 * i + 1]);
+    }
+    const E2 v = ctx ? instance_mle_device(ctx, p, in->inst, which, index, pt) : instance_mle(p, in->inst, which, index, pt);
+    out2[0] = v.c0; out2[1] = v.c1;
+    return 0;
+    HG_CATCH(-1)
+}
+
 int hg_verify_bn254(const hg_pk* pk, const hg_witness* w, const uint8_t* proof, size_t len) {
     HG_TRY
     if (!pk || !w || !proof) throw Error("hg_verify_bn254: null argument");

@@ -563,6 +563,51 @@ static Witness witness_from_json_impl(const Params& p, const std::string& path, 
     return w;
 }
 
+// hg_instance_from_ciphertext / hg_instance_from_witness (host.hpp Instance)
+Instance instance_from_ciphertext(const Params& p, const int64_t* a, const int64_t* ct0) {
+    const size_t n = p.PZ(), k = (size_t)p.k;
+    Instance out;
+    for (int t = 0; t < 2; t++) {
+        const int64_t* c = t ? ct0 : a;
+        for (size_t i = 0; i < k; i++) {
+            const int64_t half = (int64_t)((p.raw.qis[i] - 1) / 2);
+            for (size_t j = 0; j < n; j++)
+                if (c[i * n + j] > half || c[i * n + j] < -half)
+                    throw Error(std::string("hg_instance_from_ciphertext: ") + (t ? "ct0" : "a") + ", modulus " + std::to_string(i) + ", coefficient " + std::to_string(j) +
+                                " is outside [-(q_i-1)/2, (q_i-1)/2]");
+        }
+        (t ? out.ct0 : out.a).assign(c, c + k * n);
+    }
+    return out;
+}
+Instance instance_from_witness(const Params& p, const Witness& w) {
+    const size_t n = p.PZ(), SZ = p.SZ(), k = (size_t)p.k;
+    Instance out;
+    out.a.resize(k * n);
+    out.ct0.resize(k * n);
+    for (int t = 0; t < 2; t++) {
+        const std::vector<u64>& tab = t ? w.ct0is : w.ais;
+        const size_t top = t ? SZ - 2 : n - 1;
+        const char* name = t ? "ct0is" : "ais";
+        for (size_t i = 0; i < k; i++) {
+            const u64 half = (p.raw.qis[i] - 1) / 2;
+            for (size_t x = 0; x < SZ; x++) {
+                const u64 v = tab[i * SZ + x];
+                if (x > top || x + n <= top) {   // a word the layout pads
+                    if (v) throw Error(std::string("hg_instance_from_witness: ") + name + ", modulus " + std::to_string(i) + ", word " + std::to_string(x) + " is padding but not zero");
+                    continue;
+                }
+                int64_t z;
+                if (v <= half) z = (int64_t)v;
+                else if (v < GL_P && GL_P - v <= half) z = -(int64_t)(GL_P - v);
+                else throw Error(std::string("hg_instance_from_witness: ") + name + ", modulus " + std::to_string(i) + ", word " + std::to_string(x) + " is not a signed value in [-(q_i-1)/2, (q_i-1)/2]");
+                (t ? out.ct0 : out.a)[i * n + (top - x)] = z;
+            }
+        }
+    }
+    return out;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Synthetic witness: the math of scripts/circuit_sk.py:18-140 on seeded integer-only samplers.
 //   s uniform in {-1,0,1}; e centred binomial (eta = 20, variance 10 ~ sigma 3.2) truncated to +-19;

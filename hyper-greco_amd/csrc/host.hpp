@@ -123,6 +123,16 @@ Witness witness_synthetic(const Params& p, u64 seed);
 void encryption_layout(const Params& p, const int64_t* s, const int64_t* e, const int64_t* k1, const int64_t* a, u64* s_t, u64* e_t, u64* k1_t,
                        u64* ais_t);
 
+// hg_instance: the public instance of one encryption, what a recipient holds - a_i and ct0_i as SIGNED coefficients in ascending
+// degree, modulus-major (k*n each; the convention of hg_encryption_layout). The laid-out tables: coefficient j of a_i at word n-1-j
+// of ais[i] (Poly::new_padded), of ct0_i at word 2n-2-j of block i of ct0is (new_shifted to 2^L, the first word dropped, a zero
+// pushed: sk_encryption_circuit.rs:393-396), every other word zero, a negative z as p - |z|.
+struct Instance { std::vector<int64_t> a, ct0; };
+// every coefficient in [-(q_i-1)/2, (q_i-1)/2], else an Error naming table, modulus and index
+Instance instance_from_ciphertext(const Params& p, const int64_t* a, const int64_t* ct0);
+// the layout inverted; an Error if a padding word is nonzero or a word is not a small signed value in that range
+Instance instance_from_witness(const Params& p, const Witness& w);
+
 // ---------------------------------------------------------------------------------------------
 // Lasso preprocessing (host description; the device copy lives in the prover key)
 struct LassoLookup {
@@ -216,14 +226,31 @@ std::string verify_proof_with(VerifyBackend& dev, const Params& p, const LassoPl
 // that wait for the backend's results, and - after the caller has finished the backend, with `chain` handed over in modes != 0 -
 // the completion, which runs them ("" = accepted, else the rejection reason). A walk that rejects early sets `reason` and leaves
 // nothing pending; the jobs it recorded up to there are not needed.
+// a claim the public variant of the walk leaves open: input `input` (chain_par! order) evaluates to `value` at `point`
+template <class E> struct OpenClaimT { size_t input; std::vector<E> point; E value; };
+typedef OpenClaimT<E2> OpenClaim;
 template <class E> struct VerifyPendingT {
     std::string reason;
     std::vector<E> chain;                              // modes != 0: every challenge the walk squeezed, in order
     std::vector<std::function<void()>> deferred;       // the comparisons; they read the backend's tickets
+    std::vector<OpenClaimT<E>> open;                   // public_only walks: the claims on the secret inputs, in walk order per ascending input
 };
 typedef VerifyPendingT<E2> VerifyPending;
-VerifyPending verify_walk(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode);
+// public_only (hg_verify_public_device): claims on the inputs outside 3 .. 3+k-1 are not handed to the backend but returned in `open`
+VerifyPending verify_walk(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode,
+                          bool public_only = false);
 std::string verify_complete(VerifyPending& v);
+// hg_verify_public on the host: everything the key, the proof, a_i and ct0_i decide; "" = accepted, `open` = the claims left on the
+// secret inputs (inputs ascending, within one input the order in which the walk pushed them), else the reason and no claims
+std::string verify_public(const Params& p, const LassoPlan& lp, const HCircuit& c, const Instance& inst, const uint8_t* proof, size_t len, int mode,
+                          std::vector<OpenClaim>& open);
+void claim_shape(const Params& p, const LassoPlan& lp, const HCircuit& c, size_t* n_claims, size_t* n_coords);   // hg_pk_claim_shape
+// table `input` of the handle and its number of variables (an Error for an index past 3+2k)
+const u64* input_table(const Params& p, const Witness& w, size_t input, int* log2_size);
+// hg_claims_settle on the host: "" or "input claim mismatch at input K" for the lowest failing K
+std::string claims_settle(const Params& p, const Witness& w, const std::vector<OpenClaim>& claims);
+// hg_instance_mle on the host: which 0: ais[index] (L variables), 1: ct0is (L + log2 k)
+E2 instance_mle(const Params& p, const Instance& inst, int which, int index, const std::vector<E2>& pt);
 namespace bn { struct Fr; }
 std::string verify_proof_with_bn254(VerifyBackendT<bn::Fr>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len);
 // its two steps (hg_verify_device_batch_bn254), as verify_walk / verify_complete (mode 0: no chain is handed over)

@@ -140,6 +140,11 @@ struct hg_witness {
     hg_params params;
 };
 
+struct hg_instance {
+    hg::Instance inst;
+    hg_params params;
+};
+
 struct hg_pk {
     uint64_t serial = 0;  // unique per hg_setup: identifies the key even if its address is reused after hg_pk_free
     hg_ctx* ctx = nullptr;
@@ -298,6 +303,15 @@ struct DotJob { const void* a; const E2* b; size_t n; int slot; int a_is_u64; };
 constexpr int VD_BLOCKS = 32;
 constexpr size_t VD_MAX_Y = 65535;
 void vdot_jobs(hipStream_t st, const DotJob* d_jobs, size_t njobs, E2* partials, E2* res);
+// a dot product of an eq table with a public table held as compact signed coefficients (hg_instance): nblk blocks of 2n eq entries
+// and n = 2^log2_n coefficients each; eq word lo + r of block b meets coefficient n-1-r of block b (ais[i]: one block, lo = 0;
+// ct0is: k blocks, lo = n-1). d_slots[q].slot = job q's result slot (what k_vdot_reduce reads)
+struct CompactDotJob { const int64_t* c; const E2* eq; u32 log2_n, nblk, lo; };
+void vdot_compact_jobs(hipStream_t st, const CompactDotJob* d_jobs, const DotJob* d_slots, size_t njobs, E2* partials, E2* res);
+// hg_verify_public_device: the public part of the verification; "" = accepted and `open` = the claims left on the secret inputs
+std::string verify_public_device(hg_ctx* ctx, const hg_pk* pk, const Instance& inst, const uint8_t* proof, size_t len, int mode, std::vector<OpenClaim>& open);
+std::string claims_settle_device(hg_ctx* ctx, const Params& p, const Witness& w, const std::vector<OpenClaim>& claims);   // hg_claims_settle with a context
+E2 instance_mle_device(hg_ctx* ctx, const Params& p, const Instance& inst, int which, int index, const std::vector<E2>& pt);   // hg_instance_mle with a context
 // hg_verify_device_batch (verifier_batch.hip): proof i against ws[i], all in `mode`; why[i] = "" accepted, else the reason. An
 // hg::Error inside one proof's walk names its index. group: proofs per device pass (0: sized from the arena budget)
 void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Witness*>& ws, const std::vector<const uint8_t*>& proofs,

@@ -187,6 +187,20 @@ template <class F> typename F::E horner(const std::vector<typename F::E>& c, typ
     return r;
 }
 
+// The MLE of a laid-out public table at `pt`, from the compact signed coefficients of hg_instance (host.hpp Instance): block b of
+// 2n table words holds coefficient j of c[b*n ..] at word top - j, zeros elsewhere (ais[i]: one block, top = n-1, Poly::new_padded;
+// ct0is: k blocks, top = 2n-2, get_inputs sk_encryption_circuit.rs:393-396); a negative z counts as p - |z| (utils.py:4-18).
+template <class F> typename F::E mle_compact(const int64_t* c, size_t n, size_t nblk, size_t top, const std::vector<typename F::E>& pt) {
+    typedef typename F::E E;
+    std::vector<E> eq = eq_table<F>(pt);
+    if (eq.size() != nblk * 2 * n) throw Error("verifier: a point of the wrong length for a public table");
+    return par_sum<F>(nblk * n, 4096, [&](size_t t) -> E {
+        const size_t b = t / n, j = t % n;
+        const int64_t z = c[t];
+        return z ? F::mul_table(eq[b * 2 * n + top - j], z > 0 ? (u64)z : GL_P - (u64)(-z)) : F::zero();
+    });
+}
+
 template <class F> struct Verifier {
     typedef typename F::E E;
     static constexpr size_t NOPOS = (size_t)-1;
@@ -544,8 +558,12 @@ template <class F> struct Verifier {
 };
 
 
+// inst / open (both or neither; hg_verify_public): the public variant of the same walk. ct0is and the ais tables are evaluated from
+// the instance's compact coefficients, and a claim on any other input - the encryptor's secrets - is not evaluated but appended to
+// `open` (inputs ascending, within one input in the order the walk pushed them); `w` is not read.
 template <class F>
-static std::string verify_impl(const Params& p, const LassoPlan& lp, const HCircuit& c, const Witness& w, const uint8_t* proof, size_t len, int mode) {
+static std::string verify_impl(const Params& p, const LassoPlan& lp, const HCircuit& c, const Witness& w, const uint8_t* proof, size_t len, int mode,
+                               const Instance* inst = nullptr, std::vector<OpenClaimT<typename F::E>>* open = nullptr) {
     typedef typename F::E E;
     typedef typename Verifier<F>::Claim Claim;
     try {
@@ -556,7 +574,7 @@ static std::string verify_impl(const Params& p, const LassoPlan& lp, const HCirc
         double t_kind[3] = {0, 0, 0};
         const double tv0 = omp_get_wtime();
         std::vector<E> point = V.squeeze_n(p.ct0is_log2());         // sk_encryption_circuit.rs:482
-        E value = mle_eval<F>(w.ct0is.data(), point);               // :495
+        E value = inst ? mle_compact<F>(inst->ct0.data(), p.PZ(), (size_t)p.k, p.SZ() - 2, point) : mle_eval<F>(w.ct0is.data(), point);   // :495
         std::vector<std::vector<Claim>> claims(c.nodes.size());
         claims[c.lasso_id].push_back(Claim{{}, F::zero()});         // :500
         claims[c.sum_id].push_back(Claim{point, value});
@@ -584,20 +602,28 @@ static std::string verify_impl(const Params& p, const LassoPlan& lp, const HCirc
         // (the reference does not check that the proof stream is fully consumed either)
         // izip_eq!(inputs, input_claims): input.evaluate(point) == value (:512-516)
         const size_t SZ = p.SZ();
-        std::vector<const u64*> tabs = {w.s.data(), w.e.data(), w.k1.data()};
-        for (int i = 0; i < p.k; i++) tabs.push_back(&w.ais[i * SZ]);
-        for (int i = 0; i < p.k; i++) tabs.push_back(&w.r1is[i * SZ]);
-        tabs.push_back(w.r2is.data());
+        std::vector<const u64*> tabs;
+        if (!inst) {
+            tabs = {w.s.data(), w.e.data(), w.k1.data()};
+            for (int i = 0; i < p.k; i++) tabs.push_back(&w.ais[i * SZ]);
+            for (int i = 0; i < p.k; i++) tabs.push_back(&w.r1is[i * SZ]);
+            tabs.push_back(w.r2is.data());
+        }
         // (the 2k+4 inputs carry several claims each; every check is an eq table plus a dot product over 2^L entries: the checks are
         // independent, so they are dealt to the cores and each runs its own loops single-threaded inside the region)
         const double t_checks = omp_get_wtime();
         std::vector<std::pair<size_t, const Claim*>> checks;
         for (size_t k = 0; k < c.input_ids.size(); k++)
-            for (auto& cl : claims[c.input_ids[k]]) checks.push_back({k, &cl});
+            for (auto& cl : claims[c.input_ids[k]]) {
+                if (inst && (k < 3 || k >= 3 + (size_t)p.k)) open->push_back(OpenClaimT<E>{k, cl.point, cl.value});
+                else checks.push_back({k, &cl});
+            }
         long long bad = -1;
 #pragma omp parallel for schedule(dynamic, 1) num_threads(threads_for(checks.size(), 1))
         for (long long q = 0; q < (long long)checks.size(); q++) {
-            if (!F::eq(mle_eval<F>(tabs[checks[q].first], checks[q].second->point), checks[q].second->value)) {
+            const E got = inst ? mle_compact<F>(&inst->a[(checks[q].first - 3) * p.PZ()], p.PZ(), 1, p.PZ() - 1, checks[q].second->point)
+                               : mle_eval<F>(tabs[checks[q].first], checks[q].second->point);
+            if (!F::eq(got, checks[q].second->value)) {
 #pragma omp critical
                 if (bad < 0 || (long long)checks[q].first < bad) bad = (long long)checks[q].first;
             }
@@ -621,7 +647,8 @@ static std::string verify_impl(const Params& p, const LassoPlan& lp, const HCirc
 // chain over nor finishes the backend, so a batch can walk many proofs - on several host threads, with a backend that only records
 // (verifier_batch.hip) - and finish them together. The walk itself opens no OpenMP region.
 template <class F>
-static VerifyPendingT<typename F::E> walk_with_backend(VerifyBackendT<typename F::E>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode) {
+static VerifyPendingT<typename F::E> walk_with_backend(VerifyBackendT<typename F::E>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode,
+                                                       bool public_only = false) {
     typedef typename F::E E;
     typedef typename Verifier<F>::Claim Claim;
     VerifyPendingT<E> out;
@@ -666,6 +693,10 @@ static VerifyPendingT<typename F::E> walk_with_backend(VerifyBackendT<typename F
         for (size_t k = 0; k < c.input_ids.size(); k++)
             for (auto& cl : claims[c.input_ids[k]]) {
                 if (cl.off == Verifier<F>::NOPOS) throw Reject("verifier: an input claim point is not a run of the challenge chain");
+                if (public_only && (k < 3 || k >= 3 + (size_t)p.k)) {   // a secret input (hg_verify_public): left open, nothing recorded
+                    out.open.push_back(OpenClaimT<E>{k, cl.point, cl.value});
+                    continue;
+                }
                 const int t = D->mle_input(k, cl.off, (int)cl.point.size());
                 const E want = cl.value;
                 V.deferred.push_back([D, t, want, k] { if (!F::eq(D->value(t), want)) throw Reject("input claim mismatch at input " + std::to_string(k)); });
@@ -675,6 +706,7 @@ static VerifyPendingT<typename F::E> walk_with_backend(VerifyBackendT<typename F
     } catch (const Reject& r) {
         out.reason = r.what();
         out.deferred.clear();
+        out.open.clear();
     }
     return out;
 }
@@ -702,8 +734,8 @@ static std::string verify_with_backend(VerifyBackendT<typename F::E>& dev, const
 std::string verify_proof_with(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode) {
     return verify_with_backend<GlField>(dev, p, lp, c, proof, len, mode);
 }
-VerifyPending verify_walk(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode) {
-    return walk_with_backend<GlField>(dev, p, lp, c, proof, len, mode);
+VerifyPending verify_walk(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode, bool public_only) {
+    return walk_with_backend<GlField>(dev, p, lp, c, proof, len, mode, public_only);
 }
 std::string verify_complete(VerifyPending& v) { return complete_pending(v); }
 std::string verify_proof_with_bn254(VerifyBackendT<bn::Fr>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len) {
@@ -720,6 +752,67 @@ std::string verify_proof(const Params& p, const LassoPlan& lp, const HCircuit& c
 }
 std::string verify_proof_bn254(const Params& p, const LassoPlan& lp, const HCircuit& c, const Witness& w, const uint8_t* proof, size_t len) {
     return verify_impl<BnField>(p, lp, c, w, proof, len, 0);
+}
+
+// ---- hg_verify_public / hg_claims_settle: the verifier split where the public data ends -------------------------------------------
+std::string verify_public(const Params& p, const LassoPlan& lp, const HCircuit& c, const Instance& inst, const uint8_t* proof, size_t len, int mode,
+                          std::vector<OpenClaim>& open) {
+    open.clear();
+    const Witness none;
+    std::string why = verify_impl<GlField>(p, lp, c, none, proof, len, mode, &inst, &open);
+    if (!why.empty()) open.clear();
+    return why;
+}
+E2 instance_mle(const Params& p, const Instance& inst, int which, int index, const std::vector<E2>& pt) {
+    if (which == 0) return mle_compact<GlField>(&inst.a[(size_t)index * p.PZ()], p.PZ(), 1, p.PZ() - 1, pt);
+    return mle_compact<GlField>(inst.ct0.data(), p.PZ(), (size_t)p.k, p.SZ() - 2, pt);
+}
+// The claims the walk leaves on the secret inputs, counted from the wiring alone: every non-input node hands each predecessor the
+// claims the walk above hands it (Vanilla: one per left use at the phase-1 point, one per right use at the phase-2 point; FFT and
+// Lasso: one), and a claim's point has as many coordinates as the sum-check that produced it had rounds.
+void claim_shape(const Params& p, const LassoPlan& lp, const HCircuit& c, size_t* n_claims, size_t* n_coords) {
+    std::vector<std::vector<int>> nv(c.nodes.size());
+    nv[c.lasso_id].push_back(0);
+    nv[c.sum_id].push_back(p.ct0is_log2());
+    for (size_t q = c.topo.size(); q-- > 0;) {
+        const HNode& n = c.nodes[c.topo[q]];
+        if (n.kind == NK_INPUT || nv[c.topo[q]].empty()) continue;
+        if (n.kind == NK_VANILLA) {
+            const int nin = n.log2_sub_in + n.log2_reps;
+            for (size_t i = 0; i < n.preds.size(); i++) {
+                if (n.left_use[i]) nv[n.preds[i]].push_back(nin);
+                if (!n.mul.empty() && n.right_use[i]) nv[n.preds[i]].push_back(nin);
+            }
+        } else nv[n.preds[0]].push_back(n.kind == NK_FFT ? n.log2_size : lp.nu);
+    }
+    size_t nc = 0, co = 0;
+    for (size_t k = 0; k < c.input_ids.size(); k++) {
+        if (k >= 3 && k < 3 + (size_t)p.k) continue;
+        for (int v : nv[c.input_ids[k]]) { nc++; co += (size_t)v; }
+    }
+    *n_claims = nc;
+    *n_coords = co;
+}
+const u64* input_table(const Params& p, const Witness& w, size_t input, int* log2_size) {
+    const size_t K = (size_t)p.k, SZ = p.SZ();
+    *log2_size = p.L;
+    if (input == 0) return w.s.data();
+    if (input == 1) return w.e.data();
+    if (input == 2) return w.k1.data();
+    if (input < 3 + K) return &w.ais[(input - 3) * SZ];
+    if (input < 3 + 2 * K) return &w.r1is[(input - 3 - K) * SZ];
+    if (input == 3 + 2 * K) { *log2_size = p.n_log2 + p.log2k; return w.r2is.data(); }
+    throw Error("hg_claims_settle: input " + std::to_string(input) + " is not an input of the circuit");
+}
+std::string claims_settle(const Params& p, const Witness& w, const std::vector<OpenClaim>& claims) {
+    long long bad = -1;
+    for (const OpenClaim& cl : claims) {
+        int lg = 0;
+        const u64* tab = input_table(p, w, cl.input, &lg);
+        if ((size_t)lg != cl.point.size()) throw Error("hg_claims_settle: a claim on input " + std::to_string(cl.input) + " has " + std::to_string(cl.point.size()) + " coordinates, its table " + std::to_string(lg) + " variables");
+        if (!e2_eq(mle_eval<GlField>(tab, cl.point), cl.value) && (bad < 0 || (long long)cl.input < bad)) bad = (long long)cl.input;
+    }
+    return bad < 0 ? std::string() : "input claim mismatch at input " + std::to_string(bad);
 }
 
 }  // namespace hg

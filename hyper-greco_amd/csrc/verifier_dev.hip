@@ -49,6 +49,30 @@ __global__ __launch_bounds__(64) void k_vdot_reduce(const DotJob* __restrict__ j
     if (threadIdx.x == 0) res[jobs[blockIdx.x].slot] = sm[0];
 }
 
+// The MLE evaluations of the public tables of hg_verify_public_device, from the compact signed coefficients (CompactDotJob:
+// prover.hpp): workgroup (x, job) walks the WORD index - block b, word lo + r meets coefficient n-1-r of that block - so the eq loads
+// are consecutive across a wavefront (the coefficients are read in descending order over the same cache lines), turns the sign into
+// the field element in registers (a negative z is p - |z|) and reduces as k_vdot_jobs does: VD_BLOCKS partial sums per job, then
+// k_vdot_reduce. Only the half of the eq table that meets a non-padding word is read. Field addition is exact: the order is free.
+__global__ __launch_bounds__(256) void k_vdot_compact_jobs(const CompactDotJob* __restrict__ jobs, E2* __restrict__ partials) {
+    __shared__ E2 sm[256];
+    const CompactDotJob& J = jobs[blockIdx.y];
+    const size_t n = (size_t)1 << J.log2_n, total = n * J.nblk;
+    E2 acc = e2_zero();
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)VD_BLOCKS * 256) {
+        const size_t b = t >> J.log2_n, r = t & (n - 1);
+        const int64_t z = J.c[b * n + (n - 1 - r)];
+        if (z) acc = e2_add(acc, e2_mul_f(J.eq[b * 2 * n + J.lo + r], z > 0 ? (u64)z : GL_P - (u64)(-z)));
+    }
+    sm[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sm[threadIdx.x] = e2_add(sm[threadIdx.x], sm[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partials[(size_t)blockIdx.y * VD_BLOCKS + blockIdx.x] = sm[0];
+}
+
 // The walk (verifier.cpp) only RECORDS what it needs - every evaluation point is a run of the challenge chain, so no table depends
 // on a value the host would have to read back - and finish() launches it by kind over job arrays, as the prover's bookkeeping does:
 // all eq tables (a node's claims combined inside the kernel), the constant-gate sums, all Libra gathers, all DFT-row tables, all
@@ -82,6 +106,12 @@ struct DevBackend : VerifyBackend {
     std::vector<dev::FftJob> ffts;
     int fft_max_L = 0, fft_max_claims = 0;
     std::vector<DotJob> dots;
+    // hg_verify_public_device / hg_instance_mle: the public tables as compact signed coefficients in HBM (cp set: a of k*n words,
+    // ct0 of k*n words); mle_input / mle_ct0is then record compact dot jobs (cdot_slots: their result slots, for k_vdot_reduce)
+    const Params* cp = nullptr;
+    const int64_t *d_ca = nullptr, *d_cct0 = nullptr;
+    std::vector<CompactDotJob> cdots;
+    std::vector<DotJob> cdot_slots;
     std::vector<E2> h_u;          // the phase-1 evaluations of every Vanilla node with a phase 2, back to back
     E2* d_u_all = nullptr;
     static constexpr size_t U_CAP = 8192;
@@ -210,11 +240,28 @@ struct DevBackend : VerifyBackend {
     }
     void end_node() override { node = -1; }
     int mle_u64(const u64* tab, size_t point_off, int nvars) { return dot(tab, true, eq_single(nvars, point_off), (size_t)1 << nvars); }
+    int mle_compact(const int64_t* c, int nblk, size_t lo, size_t point_off, int nvars) {
+        int lg = 0;
+        while ((1 << lg) < nblk) lg++;
+        if (nvars != cp->L + lg) throw Error("verifier: a point of the wrong length for a public table");   // (the job reads nblk * 2n eq entries)
+        const int t = slot();
+        const E2* eq = eq_single(nvars, point_off);
+        cdots.push_back(CompactDotJob{c, eq, (u32)cp->n_log2, (u32)nblk, (u32)lo});
+        cdot_slots.push_back(DotJob{nullptr, eq, 0, t, 0});
+        return t;
+    }
     int mle_input(size_t k, size_t point_off, int nvars) override {
+        if (cp) {
+            if (k < 3 || k >= 3 + (size_t)cp->k) throw Error("verifier: input " + std::to_string(k) + " is not a public table");
+            return mle_compact(d_ca + (k - 3) * cp->PZ(), 1, 0, point_off, nvars);
+        }
         if (k >= d_inputs.size()) throw Error("verifier: no such input table");
         return mle_u64(d_inputs[k], point_off, nvars);
     }
-    int mle_ct0is(size_t point_off, int nvars) override { return mle_u64(d_ct0is, point_off, nvars); }
+    int mle_ct0is(size_t point_off, int nvars) override {
+        if (cp) return mle_compact(d_cct0, cp->k, cp->PZ() - 1, point_off, nvars);
+        return mle_u64(d_ct0is, point_off, nvars);
+    }
     void set_chain(const std::vector<E2>& c) override { h_chain = c; }
     void finish() override {
         const bool times = hg_times("verify");   // read at every call (host.hpp)
@@ -233,6 +280,8 @@ struct DevBackend : VerifyBackend {
         const dev::GatherBJob* d_gbs = gbs.empty() ? nullptr : upload(gbs.data(), gbs.size());
         const dev::FftJob* d_ffts = ffts.empty() ? nullptr : upload(ffts.data(), ffts.size());
         const DotJob* d_dots = dots.empty() ? nullptr : upload(dots.data(), dots.size());
+        const CompactDotJob* d_cdots = cdots.empty() ? nullptr : upload(cdots.data(), cdots.size());
+        const DotJob* d_cslots = cdots.empty() ? nullptr : upload(cdot_slots.data(), cdot_slots.size());
         if (!h_u.empty()) {
             const E2* staged = upload(h_u.data(), h_u.size());
             hip_check(hipMemcpyAsync(d_u_all, staged, h_u.size() * sizeof(E2), hipMemcpyDeviceToDevice, st), "verifier: phase-1 evaluations");
@@ -255,6 +304,7 @@ struct DevBackend : VerifyBackend {
         if (d_gbs) dev::gather_B_jobs(st, d_gbs, (int)gbs.size(), gb_max);
         lap("phase-2 gathers");
         if (d_dots) vdot_jobs(st, d_dots, dots.size(), ctx->alloc_n<E2>(dots.size() * (size_t)VD_BLOCKS), ctx->d_res);
+        if (d_cdots) vdot_compact_jobs(st, d_cdots, d_cslots, cdots.size(), ctx->alloc_n<E2>(cdots.size() * (size_t)VD_BLOCKS), ctx->d_res);
         lap("dot products");
         if (ctx->d_res != ctx->h_res && res_used)
             hip_check(hipMemcpyAsync(ctx->h_res, ctx->d_res, res_used * sizeof(E2), hipMemcpyDeviceToHost, st), "verifier: copy results");
@@ -271,6 +321,14 @@ void vdot_jobs(hipStream_t st, const DotJob* d_jobs, size_t njobs, E2* partials,
         const unsigned nq = (unsigned)std::min(njobs - q0, VD_MAX_Y);
         k_vdot_jobs<<<dim3(VD_BLOCKS, nq), 256, 0, st>>>(d_jobs + q0, partials + q0 * VD_BLOCKS);
         k_vdot_reduce<<<nq, 64, 0, st>>>(d_jobs + q0, partials + q0 * VD_BLOCKS, res);
+    }
+}
+
+void vdot_compact_jobs(hipStream_t st, const CompactDotJob* d_jobs, const DotJob* d_slots, size_t njobs, E2* partials, E2* res) {
+    for (size_t q0 = 0; q0 < njobs; q0 += VD_MAX_Y) {
+        const unsigned nq = (unsigned)std::min(njobs - q0, VD_MAX_Y);
+        k_vdot_compact_jobs<<<dim3(VD_BLOCKS, nq), 256, 0, st>>>(d_jobs + q0, partials + q0 * VD_BLOCKS);
+        k_vdot_reduce<<<nq, 64, 0, st>>>(d_slots + q0, partials + q0 * VD_BLOCKS, res);
     }
 }
 
@@ -307,6 +365,96 @@ std::string verify_proof_device(hg_ctx* ctx, const hg_pk* pk, const Witness& w, 
     D.d_ct0is = up(w.ct0is.data(), w.ct0is.size());
     if (hg_times("verify")) fprintf(stderr, "[hg] verify_device: inputs enqueued at %.2f ms\n", (omp_get_wtime() - tv0) * 1e3);
     return verify_proof_with(D, p, pk->lasso, pk->circuit, proof, len, mode);
+}
+
+// ---- hg_verify_public_device, hg_claims_settle, hg_instance_mle ----------------------------------------------------------------
+namespace {
+// every way out of an entry drains the stream before the staging buffer, the arena or the caller's arrays are reused (see above)
+struct Drain {
+    hipStream_t st;
+    ~Drain() { (void)hipStreamSynchronize(st); }
+};
+const int64_t* upload_coeffs(hg_ctx* ctx, const int64_t* src, size_t n) {
+    int64_t* d = ctx->alloc_n<int64_t>(n);
+    hip_check(hipMemcpyAsync(d, src, n * 8, hipMemcpyHostToDevice, ctx->stream), "verifier: upload the instance");
+    return d;
+}
+}  // namespace
+
+// The public part of the verification on the device: the instance's 2 k n signed words are uploaded as they are (8 MB at n=32768
+// k=16 against 22 MB of laid-out tables), the walk records compact dot jobs for ct0is and the ais claims and NOTHING for the secret
+// inputs - their claims come back in `open`, value from the walk and point from the challenges it squeezed.
+std::string verify_public_device(hg_ctx* ctx, const hg_pk* pk, const Instance& inst, const uint8_t* proof, size_t len, int mode, std::vector<OpenClaim>& open) {
+    const double tv0 = omp_get_wtime();
+    struct Total { double t0; ~Total() { if (hg_times("verify")) fprintf(stderr, "[hg] verify_public_device: %.2f ms in all\n", (omp_get_wtime() - t0) * 1e3); } } total{tv0};
+    open.clear();
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->arena_reset();
+    Drain drain{ctx->stream};
+    ctx->ensure_chain(16384);
+    const Params& p = pk->params;
+    DevBackend D(ctx, pk, mode);
+    D.cp = &p;
+    D.d_ca = upload_coeffs(ctx, inst.a.data(), inst.a.size());
+    D.d_cct0 = upload_coeffs(ctx, inst.ct0.data(), inst.ct0.size());
+    VerifyPending v = verify_walk(D, p, pk->lasso, pk->circuit, proof, len, mode, true);
+    if (!v.reason.empty()) return v.reason;
+    if (mode != 0) D.set_chain(v.chain);
+    D.finish();
+    std::string why = verify_complete(v);
+    if (why.empty()) open = std::move(v.open);
+    return why;
+}
+
+// The settle step on the device: the claim points staged as a chain of their own (the own_chain mechanism of modes 1-3), one eq job
+// and one dot product over the uploaded witness table per claim, one synchronisation.
+std::string claims_settle_device(hg_ctx* ctx, const Params& p, const Witness& w, const std::vector<OpenClaim>& claims) {
+    if (claims.empty()) return "";
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->arena_reset();
+    Drain drain{ctx->stream};
+    DevBackend D(ctx, nullptr, 1);
+    std::map<size_t, const u64*> d_tab;   // one upload per table, however many claims it carries
+    std::vector<int> ticket;
+    for (const OpenClaim& cl : claims) {
+        int lg = 0;
+        const u64* tab = input_table(p, w, cl.input, &lg);
+        if ((size_t)lg != cl.point.size()) throw Error("hg_claims_settle: a claim on input " + std::to_string(cl.input) + " has " + std::to_string(cl.point.size()) + " coordinates, its table " + std::to_string(lg) + " variables");
+        auto it = d_tab.find(cl.input);
+        if (it == d_tab.end()) {
+            u64* d = ctx->alloc_n<u64>((size_t)1 << lg);
+            hip_check(hipMemcpyAsync(d, tab, ((size_t)1 << lg) * 8, hipMemcpyHostToDevice, ctx->stream), "hg_claims_settle: upload inputs");
+            it = d_tab.emplace(cl.input, d).first;
+        }
+        const size_t off = D.h_chain.size();
+        D.h_chain.insert(D.h_chain.end(), cl.point.begin(), cl.point.end());
+        ticket.push_back(D.mle_u64(it->second, off, lg));
+    }
+    D.finish();
+    long long bad = -1;
+    for (size_t i = 0; i < claims.size(); i++)
+        if (!e2_eq(D.value(ticket[i]), claims[i].value) && (bad < 0 || (long long)claims[i].input < bad)) bad = (long long)claims[i].input;
+    return bad < 0 ? std::string() : "input claim mismatch at input " + std::to_string(bad);
+}
+
+// one eq job and one compact dot job
+E2 instance_mle_device(hg_ctx* ctx, const Params& p, const Instance& inst, int which, int index, const std::vector<E2>& pt) {
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->arena_reset();
+    Drain drain{ctx->stream};
+    DevBackend D(ctx, nullptr, 1);
+    D.cp = &p;
+    D.h_chain = pt;
+    int t;
+    if (which == 0) {
+        D.d_ca = upload_coeffs(ctx, inst.a.data(), inst.a.size());
+        t = D.mle_input(3 + (size_t)index, 0, (int)pt.size());
+    } else {
+        D.d_cct0 = upload_coeffs(ctx, inst.ct0.data(), inst.ct0.size());
+        t = D.mle_ct0is(0, (int)pt.size());
+    }
+    D.finish();
+    return D.value(t);
 }
 
 }  // namespace hg

@@ -25,6 +25,7 @@ typedef struct hg_pk hg_pk;           /* prover key = LassoPreprocessing + circu
 typedef struct hg_witness hg_witness; /* BfvSkEncryptArgs after get_inputs(): laid-out field tables (host) */
 typedef struct hg_values hg_values;   /* circuit.evaluate() result: every node's table, resident in HBM */
 typedef struct hg_group hg_group;     /* the ranks of a sharded round-by-round prove: who adds the partial round sums */
+typedef struct hg_instance hg_instance; /* the public instance of one encryption: a_i and ct0_i, host. Crosses the ABI as void* */
 
 /* Per-parameter-set constants [REF bfv-gkr/src/constants/mod.rs:16-35, constants/sk_enc_constants_*.rs] */
 typedef struct hg_params {
@@ -213,6 +214,71 @@ int hg_verify_device_mode(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, int
  * launch per kind, tables that depend on the key only built once per group; the inputs of the next group are copied meanwhile. */
 int hg_verify_device_batch(hg_ctx* ctx, const hg_pk* pk, const hg_witness* const* ws, const uint8_t* const* proofs,
                            const size_t* lens, size_t n, int mode, int* results, char* reasons, size_t reason_cap);
+
+/* ---- Verification from the ciphertext: the verifier split where the public data ends ------------------------------------------
+ * Every verifier above takes an hg_witness, as the reference's verify evaluates EVERY input polynomial at the claim points GKR
+ * leaves [REF sk_encryption_circuit.rs:462-517; izip_eq!(inputs, input_claims) :512-516]; five of those seven tables (s, e, k1,
+ * r1is, r2is) are the encryptor's secrets. A recipient holds the ciphertext (ct0_i, a_i) and the proof. The entries below decide
+ * everything those and the key decide - the output claim, every node reduction, the Lasso scalars, the input claims on the ais
+ * tables - and hand back what is left, the claims (input, point, value) on the five secret inputs: what a commitment layer would
+ * open (the reference's PCS type parameter is dead). hg_claims_settle checks such claims against a witness handle,
+ * which is the reference's contract again: hg_verify_public followed by hg_claims_settle decides what hg_verify_mode decides.
+ * Goldilocks, modes 0..3, one proof per call.
+ * The instance handle (hg_instance*) and the claim array (hg_input_claim*) cross the ABI as void pointers. */
+typedef struct hg_input_claim {
+    uint32_t input;      /* chain_par! order [REF sk_encryption_circuit.rs:476-481]: 0 s, 1 e, 2 k1, 3+k+i r1is[i], 3+2k r2is (never 3..3+k-1: the claims on ais are settled inside) */
+    uint32_t nvars;
+    uint64_t point_off;  /* coordinates points[2*point_off .. 2*(point_off+nvars)), (c0, c1) each */
+    uint64_t value[2];
+} hg_input_claim;
+
+/* = the public half of BfvSkEncryptArgs [REF sk_encryption_circuit.rs:64-73: ais, ct0is] as a recipient holds it. a, ct0: k*n SIGNED
+ *   coefficients each, modulus-major, ASCENDING degree (the convention of hg_encryption_layout). Laid out as get_inputs does
+ *   [REF sk_encryption_circuit.rs:365-415]: coefficient j of a_i at word n-1-j of ais[i] [REF poly.rs:20-28], of ct0_i at word 2n-2-j of
+ *   modulus i's 2n-word block of ct0is (new_shifted to 2^L, the first word dropped, a zero pushed [REF :393-396]), a negative z as
+ *   p - |z| [REF scripts/utils.py:4-18]. Every coefficient must lie in [-(q_i-1)/2, (q_i-1)/2], else -1 naming table, modulus and
+ *   index. Host only. *out: an hg_instance*. */
+int hg_instance_from_ciphertext(const hg_params* params, const int64_t* a, const int64_t* ct0, void** out);
+/* The same from a handle: the layout of tables 3 (ais) and 6 (ct0is) inverted. -1 if a padding word is nonzero or a word is not a
+ * signed value in that range. */
+int hg_instance_from_witness(const hg_params* params, const hg_witness* w, void** out);
+void hg_instance_free(void* instance);
+/* copies the coefficients back out: a and ct0 receive k*n signed words each, as hg_instance_from_ciphertext takes them */
+int hg_instance_coeffs(const void* instance, int64_t* a, int64_t* ct0);
+/* the laid-out table the instance stands for, as hg_witness_get returns it: which 0 ais, 1 ct0is (k*2^L words each). Returns the
+ * element count (copies min(count, cap)); -1 for a null handle or another selector. */
+int64_t hg_instance_get(const void* instance, int which, uint64_t* out, size_t cap);
+
+/* key-only: how many claims on secret inputs a proof of this key leaves, and their coordinates in all (host-only keys too) */
+int hg_pk_claim_shape(const hg_pk* pk, size_t* n_claims, size_t* n_coords);
+
+/* = BfvEncrypt::verify [REF sk_encryption_circuit.rs:462-517] up to the point where it needs a secret: the walk of hg_verify_mode in
+ *   `mode` (0..3) with ct0is and the ais tables evaluated from the instance's compact coefficients; a claim on any other input is
+ *   not evaluated but written out. instance: an hg_instance*; claims: room for claim_cap hg_input_claim; points: room for coord_cap
+ *   coordinates (2 words each). Returns 0 accept (claims and points filled, *n_claims set), 1 reject (reason in hg_last_error,
+ *   *n_claims = 0; the reasons are hg_verify_mode's), -1 error: a null argument, a mode outside 0..3, claim_cap or coord_cap below
+ *   hg_pk_claim_shape, an instance of other parameters; the device form also: no context, a host-only key.
+ *   Claim order: inputs ascending, within one input the order in which the walk pushes them; the same for both forms. Points are
+ *   always written out as values (in mode 0 they are runs of the fixed chain; the caller still receives the values).
+ *   hg_verify_public is the host form (works with hg_setup(NULL, ..)). hg_verify_public_device runs the table-sized work as
+ *   hg_verify_device_mode does, with the instance uploaded as it is (2 k n words: 8 MB at n=32768 k=16 against the 22 MB of laid-out
+ *   tables) and the MLE evaluations of ais and ct0is in one kernel that reads the signed words and the half of each eq table that
+ *   meets a non-padding word; the secret inputs launch nothing. Same decisions, claims and points as the host form, bit for bit. */
+int hg_verify_public(const hg_pk* pk, const void* instance, int mode, const uint8_t* proof, size_t len, void* claims, size_t claim_cap,
+                     uint64_t* points, size_t coord_cap, size_t* n_claims);
+int hg_verify_public_device(hg_ctx* ctx, const hg_pk* pk, const void* instance, int mode, const uint8_t* proof, size_t len, void* claims,
+                            size_t claim_cap, uint64_t* points, size_t coord_cap, size_t* n_claims);
+
+/* = izip_eq!(inputs, input_claims) [REF sk_encryption_circuit.rs:512-516] for the n claims of an hg_input_claim array: table `input`
+ *   of w (any input 0 .. 3+2k) at the point == value, for every claim. ctx == NULL: host; with a context: one batch of eq tables and
+ *   dot products on the device, one synchronisation. Returns 0, 1 ("input claim mismatch at input K", the lowest failing K: the
+ *   verifiers' text) or -1 (a null argument, a handle of other parameters, no such input, nvars that is not the table's). */
+int hg_claims_settle(hg_ctx* ctx, const hg_params* params, const hg_witness* w, const void* claims, size_t n, const uint64_t* points);
+
+/* part exposed for parity tests: the MLE of one laid-out public table at an E point, computed from the compact coefficients
+ * (ctx == NULL: host loop; else the kernel of hg_verify_public_device). which 0: ais[index] (L vars); 1: ct0is, the whole table
+ * (L + log2 k vars, index ignored). */
+int hg_instance_mle(hg_ctx* ctx, const void* instance, int which, int index, const uint64_t* point, size_t nvars, uint64_t out2[2]);
 
 /* The same pair in a protocol mode that FIXES the reference's two known soundness gaps. mode bits:
  *   1  absorbing transcript: write_felt / read_felt also hash the element - the rule of the in-tree plonkish-trait writer of
