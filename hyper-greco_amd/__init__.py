@@ -44,7 +44,7 @@ EXPORTS = [
     "hg_last_error", "hg_device_count", "hg_create", "hg_destroy", "hg_set_option", "hg_params_builtin", "hg_params_derive", "hg_grand_product", "hg_fold", "hg_setup", "hg_pk_free",
     "hg_pk_lasso_layout", "hg_pk_info", "hg_pk_node_eq_form", "hg_witness_from_json", "hg_witness_synthetic", "hg_witness_from_arrays", "hg_witness_derive", "hg_witness_derive_into",
     "hg_witness_get", "hg_witness_free", "hg_prove", "hg_warmup", "hg_prove_stream", "hg_encryption_layout", "hg_prove_encryptions", "hg_verify", "hg_verify_device", "hg_verify_device_mode", "hg_verify_device_batch",
-    "hg_instance_from_ciphertext", "hg_instance_from_witness", "hg_instance_free", "hg_instance_coeffs", "hg_instance_get", "hg_pk_claim_shape", "hg_verify_public", "hg_verify_public_device", "hg_claims_settle", "hg_instance_mle",
+    "hg_instance_from_ciphertext", "hg_instance_from_witness", "hg_instance_free", "hg_instance_coeffs", "hg_instance_get", "hg_pk_claim_shape", "hg_verify_public", "hg_verify_public_device", "hg_verify_public_batch", "hg_claims_settle", "hg_instance_mle", "hg_instance_mle_batch",
     "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_mle_eval",
     "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_prove_encryptions_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
 ]
@@ -1020,6 +1020,54 @@ def verify_public(pk, instance, proof, mode=0, ctx=None, device=False):
     if rc:
         return False, lib().hg_last_error().decode(), None
     return True, "", InputClaims(claims, n.value, points)
+
+
+def verify_public_batch(ctx, pk, instances, proofs, mode=0, reason_cap=256):
+    """hg_verify_public_batch: proof i against instances[i] in `mode`, the run verified in device passes of a group of proofs each:
+    a list of (accepted, reason, InputClaims or None), one per proof: what verify_public(pk, instances[i], proofs[i], mode, ctx,
+    device=True) returns for that pair alone."""
+    L = lib()
+    L.hg_verify_public_batch.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_int,
+                                         C.POINTER(C.c_int), C.c_void_p, C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]
+    n = len(proofs)
+    if len(instances) != n:
+        raise ValueError("verify_public_batch: one instance per proof")
+    nc, nco = pk_claim_shape(pk)
+    m = max(n, 1)
+    hs = (C.c_void_p * m)(*[x.h.value for x in instances])
+    ps = (C.c_char_p * m)(*[bytes(p) for p in proofs])
+    lens = (C.c_size_t * m)(*[len(p) for p in proofs])
+    res = (C.c_int * m)()
+    claims = (HgInputClaim * (m * max(nc, 1)))()
+    points = np.zeros(2 * m * max(nco, 1), dtype=np.uint64)
+    counts = (C.c_size_t * m)()
+    reasons = C.create_string_buffer(m * reason_cap)
+    rc = L.hg_verify_public_batch(ctx.h if ctx is not None else None, pk.h, hs, ps, lens, n, mode, res, claims, max(nc, 1), _ptr(points), max(nco, 1), counts,
+                                  reasons, reason_cap)
+    if rc < 0:
+        raise HgError(lib().hg_last_error().decode())
+    raw = reasons.raw
+    out = []
+    for i in range(n):
+        if res[i]:
+            out.append((False, raw[i * reason_cap:(i + 1) * reason_cap].split(b"\0", 1)[0].decode(), None))
+            continue
+        mine = (HgInputClaim * max(nc, 1))(*claims[i * max(nc, 1):(i + 1) * max(nc, 1)])
+        out.append((True, "", InputClaims(mine, counts[i], points[2 * i * max(nco, 1):2 * (i + 1) * max(nco, 1)].copy())))
+    return out
+
+
+def instance_mle_batch(ctx, instances, which, index, point):
+    """hg_instance_mle_batch: the MLE of ais[index] (which 0) or ct0is (which 1) of every instance at ONE E point (u64 pairs),
+    through the kernel of hg_verify_public_batch as one work unit: an (n, 2) array. Device only."""
+    point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1)
+    n = len(instances)
+    out = np.zeros((n, 2), dtype=np.uint64)
+    hs = (C.c_void_p * max(n, 1))(*[x.h.value for x in instances])
+    L = lib()
+    L.hg_instance_mle_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.c_int, C.c_int, u64p, C.c_size_t, u64p]
+    _check(L.hg_instance_mle_batch(ctx.h if ctx is not None else None, hs, n, which, index, _ptr(point), point.size // 2, _ptr(out)))
+    return out
 
 
 def claims_settle(ctx, params, witness, claims):

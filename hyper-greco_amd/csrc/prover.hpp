@@ -77,7 +77,7 @@ struct hg_ctx {
     // options (hg_set_option)
     bool one_stream = false;  // keep every launch on `stream` (per-kernel timings without cross-stream interference)
     int mode = 0;             // protocol mode of the next proves: bit 0 absorbing transcript, bit 1 extension-field memory checking
-    int64_t verify_batch_group = 0;   // hg_verify_device_batch: most proofs per device pass (0: sized from the arena budget)
+    int64_t verify_batch_group = 0;   // hg_verify_device_batch, hg_verify_public_batch: most proofs per device pass (0: sized from the arena budget)
     void* verify_batch = nullptr;     // verifier_batch.hip: VerifyBatchBufs (pinned and device input sets, upload stream), freed with the context
     // bump arena: chunks are kept across proves, offsets reset per prove
     struct Chunk { char* p; size_t cap, used; size_t high = 0; };  // high: largest `used` since the last reset
@@ -316,6 +316,13 @@ E2 instance_mle_device(hg_ctx* ctx, const Params& p, const Instance& inst, int w
 // hg::Error inside one proof's walk names its index. group: proofs per device pass (0: sized from the arena budget)
 void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Witness*>& ws, const std::vector<const uint8_t*>& proofs,
                          const std::vector<size_t>& lens, int mode, std::vector<std::string>& why);
+// hg_verify_public_batch (verifier_batch.hip): the same pass from the ciphertext - proof i against insts[i], why[i] as above and
+// open[i] = the claims an accepted proof leaves on the secret inputs (what verify_public_device hands back for that pair)
+void verify_public_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Instance*>& insts, const std::vector<const uint8_t*>& proofs,
+                                const std::vector<size_t>& lens, int mode, std::vector<std::string>& why, std::vector<std::vector<OpenClaim>>& open);
+// hg_instance_mle_batch: one public table (which / index as instance_mle_device) of every instance at one point, through the batch's
+// kernel as one work unit; out: one E2 per instance
+void instance_mle_batch_device(hg_ctx* ctx, const Params& p, const std::vector<const Instance*>& insts, int which, int index, const std::vector<E2>& pt, E2* out);
 void verify_batch_drop(hg_ctx* ctx);   // the context's batch buffers (hg_destroy)
 void prove_cache_drop(hg_ctx* ctx);
 

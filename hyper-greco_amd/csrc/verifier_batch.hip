@@ -12,6 +12,9 @@
 //      then every proof's deferred comparisons (verify_complete) on the host threads.
 // The public inputs are gathered by host threads into page-locked memory and copied on a stream of their own: group g+1's copies
 // and walks run while group g's kernels do.
+// hg_verify_public_batch is the same pass from the ciphertext (the batch form of verify_public_device, verifier_dev.hip): the walks
+// run with public_only, the recording backend in its compact form, each proof's instance is staged as it is (2 k n signed words),
+// k_vin_compact_dots evaluates ais and ct0is from them, and the claims on the secret inputs come back from each proof's pending state.
 #include <algorithm>
 #include <cstring>
 #include <map>
@@ -29,7 +32,8 @@ namespace {
 // of the P tables, eight products per accumulator before one reduction (gl_wide.hpp), one partial per (member, workgroup). A second
 // launch adds every member's partials into its result slot. HBM traffic: 8 B per input entry plus 16 / P B of eq.
 constexpr int VB_TPB = 256, VB_ITEMS = 8, VB_TILE = VB_TPB * VB_ITEMS;
-struct VinUnit { const E2* eq; size_t n; int first, P, nblk; size_t part0; };   // member p's partial of workgroup b: part0 + p * nblk + b
+// (log2_n, lo: k_vin_compact_dots only - n is then the count of non-padding words, blocks of 2^log2_n, word lo + r of a block's 2^(log2_n+1) eq entries)
+struct VinUnit { const E2* eq; size_t n; int first, P, nblk; size_t part0; u32 log2_n, lo; };   // member p's partial of workgroup b: part0 + p * nblk + b
 struct VinMember { const u64* a; int unit, slot; };
 struct VinBlock { int unit, blk; };
 
@@ -65,6 +69,58 @@ __global__ __launch_bounds__(VB_TPB) void k_vin_dots(const VinUnit* __restrict__
             s = e2_add(s, t);
         }
         // (two LDS buffers: member p + 1 writes the other one, and thread 0 has read this one before the next barrier)
+        if (lane == 0) sm[p & 1][wave] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            E2 t = sm[p & 1][0];
+            for (int w = 1; w < VB_TPB / 64; w++) t = e2_add(t, sm[p & 1][w]);
+            partials[U.part0 + (size_t)p * U.nblk + B.blk] = t;
+        }
+    }
+}
+// k_vin_dots over the compact signed coefficients of public instances (hg_verify_public_batch; CompactDotJob, prover.hpp, is the
+// single-proof form). A unit is one eq table and the P members' coefficient blocks evaluated at its point (mode 0: the group's
+// tables of one public input; modes 1-3: one). A workgroup owns VB_TILE consecutive WORD indices t of the non-padding range only
+// (U.n = blocks * 2^log2_n of them): with b = t >> log2_n and r = t & (n-1), eq entry b * 2n + lo + r meets coefficient n-1-r of
+// block b, exactly as k_vdot_compact_jobs indexes (ais[i]: one block, lo = 0; ct0is: k blocks, lo = n-1). The eq tile is loaded
+// once into registers; per member the eight int64 words are read (descending over the same cache lines as the eq loads ascend) and
+// the sign becomes the field element in registers, a negative z being GL_P - |z|. Accumulator bound: k_vin_dots's, eight products of
+// canonical operands per accumulator before one reduction - |z| <= (q_i-1)/2 < 2^61 (hg_instance_from_ciphertext checks the range),
+// so the lifted word is canonical, and the eq entries are. One partial per (member, workgroup); k_vin_reduce adds them. HBM traffic
+// by design: 8 B per coefficient plus 16 / P B of eq, nothing for padding words - the padding half of an eq table is never read.
+__global__ __launch_bounds__(VB_TPB) void k_vin_compact_dots(const VinUnit* __restrict__ units, const VinMember* __restrict__ members,
+                                                             const VinBlock* __restrict__ blocks, E2* __restrict__ partials) {
+    __shared__ E2 sm[2][VB_TPB / 64];
+    const VinBlock B = blocks[blockIdx.x];
+    const VinUnit U = units[B.unit];
+    const size_t base = (size_t)B.blk * VB_TILE + threadIdx.x, nm1 = ((size_t)1 << U.log2_n) - 1;
+    E2 eq[VB_ITEMS];
+#pragma unroll
+    for (int j = 0; j < VB_ITEMS; j++) {
+        const size_t t = base + (size_t)j * VB_TPB, r = t & nm1;
+        eq[j] = t < U.n ? U.eq[2 * (t - r) + U.lo + r] : e2_zero();
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int p = 0; p < U.P; p++) {
+        const int64_t* __restrict__ c = reinterpret_cast<const int64_t*>(members[U.first + p].a);
+        u64 v[VB_ITEMS];
+#pragma unroll
+        for (int j = 0; j < VB_ITEMS; j++) {
+            const size_t t = base + (size_t)j * VB_TPB, r = t & nm1;
+            const int64_t z = t < U.n ? c[(t - r) + (nm1 - r)] : 0;
+            v[j] = z >= 0 ? (u64)z : GL_P - (u64)(-z);
+        }
+        WAcc c0 = wacc_zero(), c1 = wacc_zero();
+#pragma unroll
+        for (int j = 0; j < VB_ITEMS; j++) wmac2(c0, eq[j].c0, v[j], c1, eq[j].c1, v[j]);
+        E2 s = e2(wreduce(c0), wreduce(c1));
+        for (int o = 32; o > 0; o >>= 1) {
+            E2 t;
+            t.c0 = __shfl_xor(s.c0, o);
+            t.c1 = __shfl_xor(s.c1, o);
+            s = e2_add(s, t);
+        }
+        // (two LDS buffers, as in k_vin_dots)
         if (lane == 0) sm[p & 1][wave] = s;
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -120,7 +176,11 @@ struct RecBackend : VerifyBackend {
     size_t u_at = 0;
     dev::ClaimSet cs;
 
-    RecBackend(const hg_pk* k) : pk(k), n_inputs(2 * (size_t)k->params.k + 4) { memset(&cs, 0, sizeof(cs)); }
+    // hg_verify_public_batch (the counterpart of DevBackend::cp): the public tables are compact signed coefficients, mle_input for
+    // inputs 3 .. 3+k-1 and mle_ct0is record compact input jobs, any other input is refused
+    const Params* cp = nullptr;
+
+    RecBackend(const hg_pk* k, bool compact = false) : pk(k), n_inputs(2 * (size_t)k->params.k + 4), cp(compact ? &k->params : nullptr) { memset(&cs, 0, sizeof(cs)); }
     int slot() { return nslots++; }
     void reads_chain(const dev::ClaimSet& c, int nvars) {
         for (int a = 0; a < c.n; a++) chain_need = std::max(chain_need, c.point_off[a] + (size_t)nvars);
@@ -191,12 +251,21 @@ struct RecBackend : VerifyBackend {
     }
     void end_node() override { node = -1; }
     int mle_input(size_t k, size_t point_off, int nvars) override {
+        if (cp) {
+            if (k < 3 || k >= 3 + (size_t)cp->k) throw Error("verifier: input " + std::to_string(k) + " is not a public table");
+            if (nvars != cp->L) throw Error("verifier: a point of the wrong length for a public table");   // (the job reads 2n eq entries)
+        }
         if (k >= n_inputs) throw Error("verifier: no such input table");
         const int t = slot();
         ins.push_back(In{(int)k, eq_single(nvars, point_off), t});
         return t;
     }
-    int mle_ct0is(size_t point_off, int nvars) override { const int t = slot(); ins.push_back(In{-1, eq_single(nvars, point_off), t}); return t; }
+    int mle_ct0is(size_t point_off, int nvars) override {
+        if (cp && nvars != cp->ct0is_log2()) throw Error("verifier: a point of the wrong length for a public table");   // (k * 2n eq entries)
+        const int t = slot();
+        ins.push_back(In{-1, eq_single(nvars, point_off), t});
+        return t;
+    }
     void finish() override { throw Error("verifier: a recording backend is finished by its batch"); }
     E2 value(int t) const override { return res[t]; }
 };
@@ -239,37 +308,64 @@ char* batch_desc_host(VerifyBatchBufs* B, size_t bytes) {
     return B->h_desc;
 }
 
-void batch_stage_inputs(VerifyBatchBufs* B, int s, const std::vector<const Witness*>& ws, size_t i0, size_t i1, const BatchInputs& L,
-                        [[maybe_unused]] int nthr, const char* who) {
-    const size_t np = i1 - i0, words = L.words, SZ = L.SZ, PZ = L.PZ, K = L.K;
-    const std::string w(who);
+namespace {
+// set s free again (its last copy waited for) and grown to `total` words
+void stage_set(VerifyBatchBufs* B, int s, size_t total, const std::string& w) {
     if (B->recorded[s]) hip_check(hipEventSynchronize(B->ev[s]), (w + ": input set reuse").c_str());
-    if (B->words[s] < np * words) {
+    if (B->words[s] < total) {
         if (B->h_in[s]) { (void)hipHostFree(B->h_in[s]); B->h_in[s] = nullptr; }
         if (B->d_in[s]) { (void)hipFree(B->d_in[s]); B->d_in[s] = nullptr; }
         B->words[s] = 0;
-        hip_check(hipHostMalloc((void**)&B->h_in[s], np * words * sizeof(u64), hipHostMallocDefault), "hipHostMalloc(batch inputs)");
-        hip_check(hipMalloc((void**)&B->d_in[s], np * words * sizeof(u64)), "hipMalloc(batch inputs)");
-        B->words[s] = np * words;
+        hip_check(hipHostMalloc((void**)&B->h_in[s], total * sizeof(u64), hipHostMallocDefault), "hipHostMalloc(batch inputs)");
+        hip_check(hipMalloc((void**)&B->d_in[s], total * sizeof(u64)), "hipMalloc(batch inputs)");
+        B->words[s] = total;
     }
-    struct Piece { u64* dst; const u64* src; size_t n; };
-    std::vector<Piece> pieces;
+}
+// the gather of a set in pieces of 2 MB on the host threads, then its copy on the upload stream
+struct Piece { u64* dst; const u64* src; size_t n; };
+void stage_table(std::vector<Piece>& pieces, u64*& dst, const u64* src, size_t n) {
     constexpr size_t PIECE = (size_t)1 << 18;   // 2 MB
+    for (size_t o = 0; o < n; o += PIECE) pieces.push_back(Piece{dst + o, src + o, std::min(PIECE, n - o)});
+    dst += n;
+}
+void stage_copy(VerifyBatchBufs* B, int s, const std::vector<Piece>& pieces, size_t total, [[maybe_unused]] int nthr, const std::string& w) {
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)pieces.size()))
+    for (long long q = 0; q < (long long)pieces.size(); q++) memcpy(pieces[q].dst, pieces[q].src, pieces[q].n * sizeof(u64));
+    hip_check(hipMemcpyAsync(B->d_in[s], B->h_in[s], total * sizeof(u64), hipMemcpyHostToDevice, B->up), (w + ": upload inputs").c_str());
+    hip_check(hipEventRecord(B->ev[s], B->up), "hipEventRecord");
+    B->recorded[s] = true;
+}
+}  // namespace
+
+void batch_stage_inputs(VerifyBatchBufs* B, int s, const std::vector<const Witness*>& ws, size_t i0, size_t i1, const BatchInputs& L,
+                        int nthr, const char* who) {
+    const size_t np = i1 - i0, words = L.words, SZ = L.SZ, PZ = L.PZ, K = L.K;
+    const std::string w(who);
+    stage_set(B, s, np * words, w);
+    std::vector<Piece> pieces;
     for (size_t i = i0; i < i1; i++) {
         const Witness& x = *ws[i];
         u64* dst = B->h_in[s] + (i - i0) * words;
         const std::pair<const u64*, size_t> tabs[] = {{x.s.data(), SZ}, {x.e.data(), SZ}, {x.k1.data(), SZ}, {x.ais.data(), K * SZ},
                                                       {x.r1is.data(), K * SZ}, {x.r2is.data(), K * PZ}, {x.ct0is.data(), K * SZ}};
-        for (auto& t : tabs) {
-            for (size_t o = 0; o < t.second; o += PIECE) pieces.push_back(Piece{dst + o, t.first + o, std::min(PIECE, t.second - o)});
-            dst += t.second;
-        }
+        for (auto& t : tabs) stage_table(pieces, dst, t.first, t.second);
     }
-#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)pieces.size()))
-    for (long long q = 0; q < (long long)pieces.size(); q++) memcpy(pieces[q].dst, pieces[q].src, pieces[q].n * sizeof(u64));
-    hip_check(hipMemcpyAsync(B->d_in[s], B->h_in[s], np * words * sizeof(u64), hipMemcpyHostToDevice, B->up), (w + ": upload inputs").c_str());
-    hip_check(hipEventRecord(B->ev[s], B->up), "hipEventRecord");
-    B->recorded[s] = true;
+    stage_copy(B, s, pieces, np * words, nthr, w);
+}
+
+void batch_stage_instances(VerifyBatchBufs* B, int s, const std::vector<const Instance*>& insts, size_t i0, size_t i1, size_t kn, int nthr,
+                           const char* who) {
+    const size_t np = i1 - i0;
+    const std::string w(who);
+    stage_set(B, s, np * 2 * kn, w);
+    std::vector<Piece> pieces;
+    for (size_t i = i0; i < i1; i++) {
+        const Instance& x = *insts[i];
+        u64* dst = B->h_in[s] + (i - i0) * 2 * kn;
+        stage_table(pieces, dst, reinterpret_cast<const u64*>(x.a.data()), kn);
+        stage_table(pieces, dst, reinterpret_cast<const u64*>(x.ct0.data()), kn);
+    }
+    stage_copy(B, s, pieces, np * 2 * kn, nthr, w);
 }
 
 void verify_batch_drop(hg_ctx* ctx) {
@@ -284,31 +380,54 @@ void verify_batch_drop(hg_ctx* ctx) {
     ctx->verify_batch = nullptr;
 }
 
-void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Witness*>& ws, const std::vector<const uint8_t*>& proofs,
-                         const std::vector<size_t>& lens, int mode, std::vector<std::string>& why) {
-    const size_t n = ws.size();
+namespace {
+// kernels, descriptor copies and input copies may be queued on any way out (a rejection, an hg::Error): drain both streams before
+// the caller may reuse the arena and the staging or free a witness or an instance
+struct Drain {
+    hipStream_t a, b;
+    ~Drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); }
+};
+// the MLE evaluations of the inputs: one partial per (member, workgroup), then every member's partials into its slot
+void vin_launch(hipStream_t st, bool compact, const VinUnit* units, const VinMember* members, size_t nmembers, const VinBlock* blocks, size_t nblocks,
+                E2* part, E2* res) {
+    if (compact) k_vin_compact_dots<<<(unsigned)nblocks, VB_TPB, 0, st>>>(units, members, blocks, part);
+    else k_vin_dots<<<(unsigned)nblocks, VB_TPB, 0, st>>>(units, members, blocks, part);
+    k_vin_reduce<<<(unsigned)nmembers, 64, 0, st>>>(units, members, part, res);
+}
+
+// What a batch checks its proofs against: witness handles (hg_verify_device_batch: ws) or public instances (hg_verify_public_batch:
+// insts, and open[i] receives the claims an accepted proof i leaves on the secret inputs). `who` prefixes the error messages.
+struct BatchSrc {
+    const char* who;
+    const std::vector<const Witness*>* ws;
+    const std::vector<const Instance*>* insts;
+    std::vector<std::vector<OpenClaim>>* open;
+};
+
+void verify_batch_run(hg_ctx* ctx, const hg_pk* pk, const BatchSrc& src, const std::vector<const uint8_t*>& proofs, const std::vector<size_t>& lens, int mode,
+                      std::vector<std::string>& why) {
+    const size_t n = proofs.size();
+    const bool pub = src.insts != nullptr;
+    const std::string who(src.who);
     why.assign(n, std::string());
+    if (pub) src.open->assign(n, std::vector<OpenClaim>());
     if (!n) return;
     const bool times = hg_times("verify");
     const double t0 = omp_get_wtime();
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
     VerifyBatchBufs* B = batch_bufs(ctx);
-    // kernels, descriptor copies and input copies may be queued on any way out (a rejection, an hg::Error): drain both streams before
-    // the caller may reuse the arena and the staging or free a witness
-    struct Drain {
-        hipStream_t a, b;
-        ~Drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); }
-    } drain{ctx->stream, B->up};
-    hip_check(hipStreamSynchronize(ctx->stream), "hg_verify_device_batch: synchronise");   // (the arena is reset below)
+    Drain drain{ctx->stream, B->up};
+    hip_check(hipStreamSynchronize(ctx->stream), (who + ": synchronise").c_str());   // (the arena is reset below)
     ctx->ensure_chain(16384);
     const Params& p = pk->params;
-    // one proof's inputs in HBM, in the order of verify_proof_device: s, e, k1, ais (k), r1is (k), r2is, then ct0is
+    // one proof's inputs in HBM, in the order of verify_proof_device: s, e, k1, ais (k), r1is (k), r2is, then ct0is; from the
+    // ciphertext: its instance as it is, a then ct0, k n signed words each (the node tables of modes 1-3 are as large either way)
     const BatchInputs L(p);
-    const size_t words = L.words;
-    const size_t in_bytes = words * sizeof(u64);
+    const size_t kn = L.K * L.PZ, words = pub ? 2 * kn : L.words;
+    const size_t in_bytes = L.words * sizeof(u64);
     size_t G = (size_t)std::max<int64_t>(0, ctx->verify_batch_group);
     if (!G) {
-        G = std::max<size_t>(1, VB_INPUT_BUDGET / in_bytes);
+        G = std::max<size_t>(1, VB_INPUT_BUDGET / (words * sizeof(u64)));
         if (mode != 0) G = std::min(G, std::max<size_t>(1, VB_TABLE_BUDGET / (5 * in_bytes)));
         G = std::min(G, VB_MAX_GROUP);
     }
@@ -317,7 +436,10 @@ void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const W
 
     std::vector<std::vector<Walked>> groups(ngroups);
     // stage group g: gather its inputs into page-locked set g & 1 (host threads), copy them on the upload stream
-    auto stage = [&](size_t g) { batch_stage_inputs(B, (int)(g & 1), ws, g * G, std::min(n, g * G + G), L, nthr, "hg_verify_device_batch"); };
+    auto stage = [&](size_t g) {
+        if (pub) batch_stage_instances(B, (int)(g & 1), *src.insts, g * G, std::min(n, g * G + G), kn, nthr, src.who);
+        else batch_stage_inputs(B, (int)(g & 1), *src.ws, g * G, std::min(n, g * G + G), L, nthr, src.who);
+    };
     // walk group g on the host threads
     auto walk = [&](size_t g) {
         const size_t i0 = g * G, i1 = std::min(n, i0 + G);
@@ -328,12 +450,12 @@ void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const W
             Walked& x = W[q];
             x.idx = i0 + (size_t)q;
             try {
-                x.rec.reset(new RecBackend(pk));
-                x.pend = verify_walk(*x.rec, p, pk->lasso, pk->circuit, proofs[x.idx], lens[x.idx], mode);
+                x.rec.reset(new RecBackend(pk, pub));
+                x.pend = verify_walk(*x.rec, p, pk->lasso, pk->circuit, proofs[x.idx], lens[x.idx], mode, pub);
             } catch (const std::exception& e) { x.error = e.what(); }
         }
         for (auto& x : W)
-            if (!x.error.empty()) throw Error("hg_verify_device_batch: proof " + std::to_string(x.idx) + ": " + x.error);
+            if (!x.error.empty()) throw Error(who + ": proof " + std::to_string(x.idx) + ": " + x.error);
     };
     // merge group g's jobs and enqueue them; returns the result slots used
     auto launch = [&](size_t g) -> size_t {
@@ -354,7 +476,7 @@ void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const W
         int fft_max_L = 0, fft_max_claims = 0;
         struct DotG { int kind, tab, eq, slot; };
         std::vector<DotG> dots;
-        struct InM { int eq; const u64* a; int slot; };
+        struct InM { int eq; const u64* a; int slot; int ct0; };   // (ct0: the public form's ct0is, k blocks at lo = n-1)
         std::vector<InM> ins;
         std::vector<E2> chain, us;
         std::map<Key, int> eq_ix, const_ix, lin_ix, fft_ix, dot_ix;
@@ -366,10 +488,10 @@ void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const W
             RecBackend& R = *x.rec;
             size_t base = 0;
             if (mode != 0) {
-                if (R.chain_need > x.pend.chain.size()) throw Error("hg_verify_device_batch: proof " + std::to_string(x.idx) + ": verifier: a job reads past the challenges the walk squeezed");
+                if (R.chain_need > x.pend.chain.size()) throw Error(who + ": proof " + std::to_string(x.idx) + ": verifier: a job reads past the challenges the walk squeezed");
                 base = chain.size();
                 chain.insert(chain.end(), x.pend.chain.begin(), x.pend.chain.end());
-            } else if (R.chain_need > ctx->chal_e) throw Error("hg_verify_device_batch: proof " + std::to_string(x.idx) + ": verifier: a job reads past the fixed chain");
+            } else if (R.chain_need > ctx->chal_e) throw Error(who + ": proof " + std::to_string(x.idx) + ": verifier: a job reads past the fixed chain");
             x.gslot.assign(R.nslots, -1);
             auto new_slot = [&] { return nslot++; };
             std::vector<int> geq(R.eqs.size());
@@ -427,14 +549,15 @@ void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const W
                 if (it == dot_ix.end()) { dots.push_back(DotG{d.kind, tab, geq[d.eq], new_slot()}); it = dot_ix.emplace(k, (int)dots.size() - 1).first; }
                 x.gslot[d.slot] = dots[it->second].slot;
             }
-            for (auto& in : R.ins) {   // (never shared: they read the proof's own witness)
+            for (auto& in : R.ins) {   // (never shared: they read the proof's own witness or instance)
                 const int sl = new_slot();
-                ins.push_back(InM{geq[in.eq], x.d_in + L.offset(in.k), sl});
+                if (pub) ins.push_back(InM{geq[in.eq], x.d_in + (in.k < 0 ? kn : (size_t)(in.k - 3) * L.PZ), sl, in.k < 0});
+                else ins.push_back(InM{geq[in.eq], x.d_in + L.offset(in.k), sl, 0});
                 x.gslot[in.slot] = sl;
             }
         }
         if ((size_t)nslot > ctx->res_cap)
-            throw Error("hg_verify_device_batch: a group needs " + std::to_string(nslot) + " result slots, the context has " + std::to_string(ctx->res_cap) + ": lower verify_batch_group");
+            throw Error(who + ": a group needs " + std::to_string(nslot) + " result slots, the context has " + std::to_string(ctx->res_cap) + ": lower verify_batch_group");
         // device tables (arena)
         for (auto& J : eqs) J.out = ctx->alloc_n<E2>((size_t)1 << J.n);
         std::vector<dev::GatherJob> gts(lins.size());
@@ -461,21 +584,27 @@ void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const W
         std::vector<VinMember> members;
         std::vector<VinBlock> blocks;
         {
-            std::vector<std::vector<const InM*>> by_eq(eqs.size());
-            for (auto& m : ins) by_eq[m.eq].push_back(&m);
+            // (an ais table and ct0is never share a unit, even at one point: their words sit at other places of the eq table)
+            std::vector<std::vector<const InM*>> by_eq(2 * eqs.size());
+            for (auto& m : ins) by_eq[2 * (size_t)m.eq + m.ct0].push_back(&m);
             size_t part = 0;
-            for (size_t e = 0; e < eqs.size(); e++) {
-                if (by_eq[e].empty()) continue;
+            for (size_t e2x = 0; e2x < by_eq.size(); e2x++) {
+                if (by_eq[e2x].empty()) continue;
+                const size_t e = e2x / 2;
                 VinUnit U;
-                U.eq = eqs[e].out; U.n = (size_t)1 << eqs[e].n; U.first = (int)members.size(); U.P = (int)by_eq[e].size();
+                memset(&U, 0, sizeof(U));
+                U.eq = eqs[e].out; U.n = (size_t)1 << eqs[e].n; U.first = (int)members.size(); U.P = (int)by_eq[e2x].size();
+                if (pub) {   // the non-padding words only: n of an ais table, k n of ct0is (the walk checked the eq table's size)
+                    U.n = e2x & 1 ? kn : L.PZ; U.log2_n = (u32)p.n_log2; U.lo = e2x & 1 ? (u32)(L.PZ - 1) : 0;
+                }
                 U.nblk = (int)((U.n + VB_TILE - 1) / VB_TILE); U.part0 = part;
                 part += (size_t)U.P * U.nblk;
-                for (const InM* m : by_eq[e]) members.push_back(VinMember{m->a, (int)units.size(), m->slot});
+                for (const InM* m : by_eq[e2x]) members.push_back(VinMember{m->a, (int)units.size(), m->slot});
                 for (int b = 0; b < U.nblk; b++) blocks.push_back(VinBlock{(int)units.size(), b});
                 units.push_back(U);
             }
         }
-        size_t vin_parts = 0, vin_bytes = 0;   // (vin_bytes: what k_vin_dots reads, eq tables and input tables)
+        size_t vin_parts = 0, vin_bytes = 0;   // (vin_bytes: what k_vin_dots / k_vin_compact_dots reads, eq tables and input tables)
         for (auto& U : units) { vin_parts += (size_t)U.P * U.nblk; vin_bytes += U.n * (sizeof(E2) + (size_t)U.P * sizeof(u64)); }
         size_t desc_bytes = 0;
         auto place = [&](size_t bytes) { const size_t o = desc_bytes; desc_bytes += (bytes + 255) & ~(size_t)255; return o; };
@@ -513,7 +642,7 @@ void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const W
             memcpy(h + o_mem, members.data(), members.size() * sizeof(VinMember));
             memcpy(h + o_blk, blocks.data(), blocks.size() * sizeof(VinBlock));
         }
-        if (desc_bytes) hip_check(hipMemcpyAsync(d_desc, h, desc_bytes, hipMemcpyHostToDevice, st), "hg_verify_device_batch: upload descriptors");
+        if (desc_bytes) hip_check(hipMemcpyAsync(d_desc, h, desc_bytes, hipMemcpyHostToDevice, st), (who + ": upload descriptors").c_str());
         // one launch per kind (the job index is gridDim.y: launches of at most VD_MAX_Y jobs)
         auto chunks = [](size_t njobs, size_t per, auto fn) { for (size_t q0 = 0; q0 < njobs; q0 += per) fn(q0, std::min(per, njobs - q0)); };
         const auto* d_eqs = reinterpret_cast<const dev::EqJob*>(d_desc + o_eq);
@@ -536,15 +665,12 @@ void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const W
         chunks(muls.size(), VD_MAX_Y, [&](size_t q0, size_t nq) { dev::gather_B_jobs(st, d_gbs + q0, (int)nq, gb_max); });
         if (!dots.empty()) vdot_jobs(st, reinterpret_cast<const DotJob*>(d_desc + o_dot), dots.size(), ctx->alloc_n<E2>(dots.size() * (size_t)VD_BLOCKS), ctx->d_res);
         if (!units.empty()) {
-            hip_check(hipStreamWaitEvent(st, B->ev[s], 0), "hg_verify_device_batch: wait for the inputs");
-            E2* part = ctx->alloc_n<E2>(vin_parts);
-            k_vin_dots<<<(unsigned)blocks.size(), VB_TPB, 0, st>>>(reinterpret_cast<const VinUnit*>(d_desc + o_unit), reinterpret_cast<const VinMember*>(d_desc + o_mem),
-                                                                   reinterpret_cast<const VinBlock*>(d_desc + o_blk), part);
-            k_vin_reduce<<<(unsigned)members.size(), 64, 0, st>>>(reinterpret_cast<const VinUnit*>(d_desc + o_unit), reinterpret_cast<const VinMember*>(d_desc + o_mem),
-                                                                   part, ctx->d_res);
+            hip_check(hipStreamWaitEvent(st, B->ev[s], 0), (who + ": wait for the inputs").c_str());
+            vin_launch(st, pub, reinterpret_cast<const VinUnit*>(d_desc + o_unit), reinterpret_cast<const VinMember*>(d_desc + o_mem), members.size(),
+                       reinterpret_cast<const VinBlock*>(d_desc + o_blk), blocks.size(), ctx->alloc_n<E2>(vin_parts), ctx->d_res);
         }
         if (ctx->d_res != ctx->h_res && nslot)
-            hip_check(hipMemcpyAsync(ctx->h_res, ctx->d_res, (size_t)nslot * sizeof(E2), hipMemcpyDeviceToHost, st), "hg_verify_device_batch: copy results");
+            hip_check(hipMemcpyAsync(ctx->h_res, ctx->d_res, (size_t)nslot * sizeof(E2), hipMemcpyDeviceToHost, st), (who + ": copy results").c_str());
         if (times)
             fprintf(stderr, "[hg] verify_batch: group %zu (%zu proofs): %zu eq tables, %zu constant sums, %zu + %zu gathers, %zu DFT rows, %zu dots, %zu input evaluations in %zu units (%.1f MB); %d slots\n",
                     g, W.size(), eqs.size(), consts.size(), lins.size(), muls.size(), ffts.size(), dots.size(), members.size(), units.size(), vin_bytes / 1e6, nslot);
@@ -560,6 +686,7 @@ void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const W
                 for (size_t t = 0; t < x.gslot.size(); t++) x.rec->res[t] = ctx->h_res[x.gslot[t]];
             }
             why[x.idx] = verify_complete(x.pend);
+            if (pub && why[x.idx].empty()) (*src.open)[x.idx] = std::move(x.pend.open);
         }
         W.clear();
     };
@@ -571,14 +698,73 @@ void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const W
         launch(g);
         if (g + 1 < ngroups) { const double tw = omp_get_wtime(); stage(g + 1); walk(g + 1); t_walk += omp_get_wtime() - tw; }
         const double ts = omp_get_wtime();
-        hip_check(hipStreamSynchronize(ctx->stream), "hg_verify_device_batch: synchronise");
-        hip_check(hipGetLastError(), "hg_verify_device_batch: kernels");
+        hip_check(hipStreamSynchronize(ctx->stream), (who + ": synchronise").c_str());
+        hip_check(hipGetLastError(), (who + ": kernels").c_str());
         t_sync += omp_get_wtime() - ts;
         complete(g);
     }
     if (times)
         fprintf(stderr, "[hg] verify_batch: %zu proofs in %zu groups of up to %zu: %.2f ms in all (staging and walks %.2f, waiting for the device %.2f)\n", n,
                 ngroups, G, (omp_get_wtime() - t0) * 1e3, t_walk * 1e3, t_sync * 1e3);
+}
+
+}  // namespace
+
+void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Witness*>& ws, const std::vector<const uint8_t*>& proofs,
+                         const std::vector<size_t>& lens, int mode, std::vector<std::string>& why) {
+    verify_batch_run(ctx, pk, BatchSrc{"hg_verify_device_batch", &ws, nullptr, nullptr}, proofs, lens, mode, why);
+}
+
+void verify_public_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Instance*>& insts, const std::vector<const uint8_t*>& proofs,
+                                const std::vector<size_t>& lens, int mode, std::vector<std::string>& why, std::vector<std::vector<OpenClaim>>& open) {
+    verify_batch_run(ctx, pk, BatchSrc{"hg_verify_public_batch", nullptr, &insts, &open}, proofs, lens, mode, why);
+}
+
+// one eq job, then k_vin_compact_dots as ONE unit whose members are the instances' tables
+void instance_mle_batch_device(hg_ctx* ctx, const Params& p, const std::vector<const Instance*>& insts, int which, int index, const std::vector<E2>& pt, E2* out) {
+    const size_t np = insts.size();
+    if (!np) return;
+    const char* who = "hg_instance_mle_batch";
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    VerifyBatchBufs* B = batch_bufs(ctx);
+    Drain drain{ctx->stream, B->up};
+    hip_check(hipStreamSynchronize(ctx->stream), "hg_instance_mle_batch: synchronise");   // (the arena is reset below)
+    ctx->arena_reset();
+    hipStream_t st = ctx->stream;
+    const size_t n = p.PZ(), kn = (size_t)p.k * n;
+    batch_stage_instances(B, 0, insts, 0, np, kn, std::max(1, hg_omp_threads()), who);
+    dev::EqJob J;
+    memset(&J, 0, sizeof(J));
+    J.n = (int)pt.size(); J.cs.n = 1; J.cs.unit_alpha = 1;   // (point_off[0] = 0: the point is the whole chain)
+    J.out = ctx->alloc_n<E2>((size_t)1 << J.n);
+    VinUnit U;
+    memset(&U, 0, sizeof(U));
+    U.eq = J.out; U.n = which ? kn : n; U.P = (int)np; U.nblk = (int)((U.n + VB_TILE - 1) / VB_TILE);
+    U.log2_n = (u32)p.n_log2; U.lo = which ? (u32)(n - 1) : 0;
+    std::vector<VinMember> members(np);
+    for (size_t i = 0; i < np; i++) members[i] = VinMember{B->d_in[0] + i * 2 * kn + (which ? kn : (size_t)index * n), 0, (int)i};
+    std::vector<VinBlock> blocks((size_t)U.nblk);
+    for (int b = 0; b < U.nblk; b++) blocks[b] = VinBlock{0, b};
+    size_t desc_bytes = 0;
+    auto place = [&](size_t bytes) { const size_t o = desc_bytes; desc_bytes += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_chain = place(pt.size() * sizeof(E2)), o_eq = place(sizeof(J)), o_unit = place(sizeof(U)), o_mem = place(np * sizeof(VinMember)),
+                 o_blk = place(blocks.size() * sizeof(VinBlock));
+    char* d_desc = static_cast<char*>(ctx->alloc(desc_bytes));
+    char* h = batch_desc_host(B, desc_bytes);
+    if (!pt.empty()) memcpy(h + o_chain, pt.data(), pt.size() * sizeof(E2));
+    memcpy(h + o_eq, &J, sizeof(J));
+    memcpy(h + o_unit, &U, sizeof(U));
+    memcpy(h + o_mem, members.data(), np * sizeof(VinMember));
+    memcpy(h + o_blk, blocks.data(), blocks.size() * sizeof(VinBlock));
+    hip_check(hipMemcpyAsync(d_desc, h, desc_bytes, hipMemcpyHostToDevice, st), "hg_instance_mle_batch: upload descriptors");
+    dev::eq_jobs(st, reinterpret_cast<const dev::EqJob*>(d_desc + o_eq), 1, J.n, reinterpret_cast<const E2*>(d_desc + o_chain));
+    hip_check(hipStreamWaitEvent(st, B->ev[0], 0), "hg_instance_mle_batch: wait for the instances");
+    E2* res = ctx->alloc_n<E2>(np);
+    vin_launch(st, true, reinterpret_cast<const VinUnit*>(d_desc + o_unit), reinterpret_cast<const VinMember*>(d_desc + o_mem), np,
+               reinterpret_cast<const VinBlock*>(d_desc + o_blk), blocks.size(), ctx->alloc_n<E2>(np * (size_t)U.nblk), res);
+    hip_check(hipMemcpyAsync(out, res, np * sizeof(E2), hipMemcpyDeviceToHost, st), "hg_instance_mle_batch: copy results");
+    hip_check(hipStreamSynchronize(st), "hg_instance_mle_batch: synchronise");
+    hip_check(hipGetLastError(), "hg_instance_mle_batch: kernels");
 }
 
 }  // namespace hg

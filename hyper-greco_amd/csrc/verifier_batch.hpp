@@ -1,5 +1,5 @@
-// What the two batched device verifiers share (verifier_batch.hip: hg_verify_device_batch over Goldilocks; bn254_verify_batch.inc:
-// hg_verify_device_batch_bn254 over bn256::Fr): the context's input sets and upload stream, the layout of one proof's public inputs
+// What the batched device verifiers share (verifier_batch.hip: hg_verify_device_batch and hg_verify_public_batch over Goldilocks;
+// bn254_verify_batch.inc: hg_verify_device_batch_bn254 over bn256::Fr): the context's input sets and upload stream, the layout of one proof's public inputs
 // in a set, the default group size, and the staging of a group's inputs.
 #pragma once
 #include <string>
@@ -55,5 +55,9 @@ inline void key_cs(Key& k, const dev::ClaimSet& c, size_t base) {
 // upload stream; the set's event marks the copy. `who` prefixes the error messages.
 void batch_stage_inputs(VerifyBatchBufs* B, int set, const std::vector<const Witness*>& ws, size_t i0, size_t i1, const BatchInputs& L,
                         int nthr, const char* who);
+
+// the same for the public instances of proofs [i0, i1) (hg_verify_public_batch): each as it is, a then ct0, kn = k * n signed words each
+void batch_stage_instances(VerifyBatchBufs* B, int set, const std::vector<const Instance*>& insts, size_t i0, size_t i1, size_t kn, int nthr,
+                           const char* who);
 
 }  // namespace hg

@@ -76,7 +76,8 @@ void hg_destroy(hg_ctx* ctx);
  *                 values object the third is captured into a hipGraph and later ones replay it - the launch sequence depends on
  *                 addresses only, because every challenge is known up front; a values object refilled by hg_witness_gen_into
  *                 keeps its graph; up to HG_GRAPH_ENTRIES (8) graphs per context, each with a private workspace)
- *   "verify_batch_group"  the most proofs one device pass of hg_verify_device_batch or hg_verify_device_batch_bn254 holds
+ *   "verify_batch_group"  the most proofs one device pass of hg_verify_device_batch, hg_verify_device_batch_bn254 or
+ *                 hg_verify_public_batch holds
  *                 (default 0: sized from the memory budget, at most 64)
  * Returns 0, or -1 for an unknown name. */
 int hg_set_option(hg_ctx* ctx, const char* name, int64_t value);
@@ -223,7 +224,7 @@ int hg_verify_device_batch(hg_ctx* ctx, const hg_pk* pk, const hg_witness* const
  * tables - and hand back what is left, the claims (input, point, value) on the five secret inputs: what a commitment layer would
  * open (the reference's PCS type parameter is dead). hg_claims_settle checks such claims against a witness handle,
  * which is the reference's contract again: hg_verify_public followed by hg_claims_settle decides what hg_verify_mode decides.
- * Goldilocks, modes 0..3, one proof per call.
+ * Goldilocks, modes 0..3, one proof per call (hg_verify_public_batch: a run of them in one device pass).
  * The instance handle (hg_instance*) and the claim array (hg_input_claim*) cross the ABI as void pointers. */
 typedef struct hg_input_claim {
     uint32_t input;      /* chain_par! order [REF sk_encryption_circuit.rs:476-481]: 0 s, 1 e, 2 k1, 3+k+i r1is[i], 3+2k r2is (never 3..3+k-1: the claims on ais are settled inside) */
@@ -269,6 +270,24 @@ int hg_verify_public(const hg_pk* pk, const void* instance, int mode, const uint
 int hg_verify_public_device(hg_ctx* ctx, const hg_pk* pk, const void* instance, int mode, const uint8_t* proof, size_t len, void* claims,
                             size_t claim_cap, uint64_t* points, size_t coord_cap, size_t* n_claims);
 
+/* hg_verify_public_device for a run of n proofs under one key: proof i (proofs[i], lens[i]) is checked against instances[i] (an
+ *   hg_instance* of the key's parameters) in `mode` (0..3). Device only. results[i] = 0 accepted / 1 rejected, exactly the decision
+ *   hg_verify_public_device makes for that pair alone; reasons (may be NULL): at reasons + i*reason_cap the text that call leaves in
+ *   hg_last_error, NUL-terminated and truncated to reason_cap bytes ("" when accepted). An accepted proof i writes its claims at
+ *   (hg_input_claim*)claims + i*claim_cap_each and its points at points + 2*i*coord_cap_each, point_off relative to that proof's own
+ *   block, and n_claims[i] = the claim count: claim order, values and points are bit for bit those of the single call. A rejected
+ *   proof gets n_claims[i] = 0. Returns the number of rejected proofs (>= 0); n == 0 returns 0 and writes nothing; -1 on an error of
+ *   the call, which writes no output either (hg_last_error names the function and, where it applies, the index): a null argument or
+ *   a null element, no context, a host-only key, a mode outside 0..3, claim_cap_each or coord_cap_each below hg_pk_claim_shape, an
+ *   instance of other parameters.
+ *   The pass is hg_verify_device_batch's - walks on the host threads, a group of proofs (context option "verify_batch_group", at
+ *   most 64) in one launch per kind, key-only tables built once per group, the next group's copies under this group's kernels -
+ *   with each proof's instance staged as it is (2 k n signed words) and ais / ct0is evaluated from them by one kernel per group
+ *   that reads the non-padding half of each eq table once for all the group's members; the secret inputs launch nothing. */
+int hg_verify_public_batch(hg_ctx* ctx, const hg_pk* pk, const void* const* instances, const uint8_t* const* proofs,
+                           const size_t* lens, size_t n, int mode, int* results, void* claims, size_t claim_cap_each,
+                           uint64_t* points, size_t coord_cap_each, size_t* n_claims, char* reasons, size_t reason_cap);
+
 /* = izip_eq!(inputs, input_claims) [REF sk_encryption_circuit.rs:512-516] for the n claims of an hg_input_claim array: table `input`
  *   of w (any input 0 .. 3+2k) at the point == value, for every claim. ctx == NULL: host; with a context: one batch of eq tables and
  *   dot products on the device, one synchronisation. Returns 0, 1 ("input claim mismatch at input K", the lowest failing K: the
@@ -279,6 +298,11 @@ int hg_claims_settle(hg_ctx* ctx, const hg_params* params, const hg_witness* w, 
  * (ctx == NULL: host loop; else the kernel of hg_verify_public_device). which 0: ais[index] (L vars); 1: ct0is, the whole table
  * (L + log2 k vars, index ignored). */
 int hg_instance_mle(hg_ctx* ctx, const void* instance, int which, int index, const uint64_t* point, size_t nvars, uint64_t out2[2]);
+/* the same for the kernel of hg_verify_public_batch: the table (which / index as above) of n instances of one parameter set at ONE
+ * shared point, as one work unit of that kernel with n members; out receives 2 words per instance. Device only. Returns 0, or -1
+ * for a null argument or element, no context, or instances of mixed parameters. */
+int hg_instance_mle_batch(hg_ctx* ctx, const void* const* instances, size_t n, int which, int index, const uint64_t* point,
+                          size_t nvars, uint64_t* out);
 
 /* The same pair in a protocol mode that FIXES the reference's two known soundness gaps. mode bits:
  *   1  absorbing transcript: write_felt / read_felt also hash the element - the rule of the in-tree plonkish-trait writer of

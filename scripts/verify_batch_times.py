@@ -6,7 +6,11 @@ next to it the median of --reps one-by-one passes over the same B proofs divided
   --field bn254: the same for hg_verify_device_batch_bn254 against hg_verify_device_bn254 (proofs of hg_prove_bn254, mode 0 only).
   --trace: prove 16 proofs in mode 3 (bn254: mode 0), pause, then ONE batch call of those 16 and nothing else (run it under rocprofv3
            --kernel-trace --stats; scripts/trace_after_gap.py then keeps the dispatches behind the pause).
-Usage: verify_batch_times.py [n k] [--field goldilocks|bn254] [--modes 0,3] [--batch 1,4,16,64] [--reps 5] [--trace]"""
+  --public: hg_verify_public_batch, three legs per proof over the same B pairs, their runs ALTERNATED (a, b, c, a, b, c, ..) after a
+           warm-up call of each: (a) the batch from the ciphertext, (b) the same pairs through hg_verify_public_device one by one,
+           (c) hg_verify_device_batch on the same proofs with the witness handles. Medians and ranges of --reps runs, a/b, and
+           whether the whole range of (a) lies below the whole range of (b). With --trace: one public batch of 16 in mode 3.
+Usage: verify_batch_times.py [n k] [--field goldilocks|bn254] [--public] [--modes 0,3] [--batch 1,4,16,64] [--reps 5] [--trace]"""
 import argparse
 import os
 import statistics
@@ -35,7 +39,10 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--field", choices=("goldilocks", "bn254"), default="goldilocks")
+    ap.add_argument("--public", action="store_true")
     a = ap.parse_args()
+    if a.public and a.field == "bn254":
+        ap.error("--public is Goldilocks only")
     bn = a.field == "bn254"
     if bn:
         a.modes = "0"
@@ -54,13 +61,52 @@ def main():
     batches = [int(b) for b in a.batch.split(",")]
     nw = DISTINCT if a.trace else min(DISTINCT, max(batches))
     ws = [hg.Witness.synthetic(bfv.params, 0x4752454330 + a.n + i) for i in range(nw)]
+    insts = [hg.Instance.from_witness(w) for w in ws] if a.public else None
     if a.trace:
         mode = 0 if bn else 3
         ps = [prove(w, mode) for w in ws]
         time.sleep(3.0)   # (longer than any idle stretch of setup, witness generation and prove)
-        got = verify_batch(ws, ps, mode)
-        assert all(ok for ok, _ in got), got
-        print("n=%d k=%d %s: one mode-%d batch of %d proofs of %d bytes" % (a.n, a.k, a.field, mode, len(ps), len(ps[0])))
+        got = hg.verify_public_batch(ctx, pk, insts, ps, mode) if a.public else verify_batch(ws, ps, mode)
+        assert all(g[0] for g in got), got
+        print("n=%d k=%d %s: one mode-%d %sbatch of %d proofs of %d bytes" % (a.n, a.k, a.field, mode, "public " if a.public else "", len(ps), len(ps[0])))
+    elif a.public:
+        print("n=%d k=%d, %d distinct witnesses, per proof, one process; %d alternating runs of (a) hg_verify_public_batch, (b) hg_verify_public_device one "
+              "by one, (c) hg_verify_device_batch, after a warm-up call of each: median [min .. max]" % (a.n, a.k, nw, a.reps))
+        for mode in [int(m) for m in a.modes.split(",")]:
+            ps = [prove(w, mode) for w in ws]
+            for B in batches:
+                W, I, P = ([x[i % nw] for i in range(B)] for x in (ws, insts, ps))
+
+                def leg_a():
+                    got = hg.verify_public_batch(ctx, pk, I, P, mode)
+                    assert all(ok for ok, _, _ in got), got
+
+                def leg_b():
+                    for inst, p in zip(I, P):
+                        ok, why, _ = hg.verify_public(pk, inst, p, mode, ctx=ctx, device=True)
+                        assert ok, why
+
+                def leg_c():
+                    got = hg.verify_device_batch(ctx, pk, W, P, mode=mode)
+                    assert all(ok for ok, _ in got), got
+                legs = (leg_a, leg_b, leg_c)
+                for f in legs:
+                    f()
+                t = [[], [], []]
+                for _ in range(a.reps):
+                    for j, f in enumerate(legs):
+                        t[j].append(timed(f) / B)
+                med = [statistics.median(x) for x in t]
+                print("mode %d B=%3d: %s; a/b %.2f; range of (a) %s range of (b); a/c %.2f" % (
+                    mode, B, "; ".join("(%s) %.3f [%.3f .. %.3f]" % ("abc"[j], med[j], min(t[j]), max(t[j])) for j in range(3)), med[0] / med[1],
+                    "below" if max(t[0]) < min(t[1]) else "NOT below", med[0] / med[2]))
+                sys.stdout.flush()
+            os.environ["HG_TIMES"] = "verify"
+            Bm = max(batches)
+            print("mode %d, B=%d with HG_TIMES=verify: the public batch, then hg_verify_device_batch" % (mode, Bm), file=sys.stderr)
+            hg.verify_public_batch(ctx, pk, [insts[i % nw] for i in range(Bm)], [ps[i % nw] for i in range(Bm)], mode)
+            hg.verify_device_batch(ctx, pk, [ws[i % nw] for i in range(Bm)], [ps[i % nw] for i in range(Bm)], mode=mode)
+            del os.environ["HG_TIMES"]
     else:
         print("n=%d k=%d %s, %d distinct witnesses, median of %d after a warm-up, per proof, one process" % (a.n, a.k, a.field, nw, a.reps))
         for mode in [int(m) for m in a.modes.split(",")]:
