@@ -40,13 +40,18 @@ class HgInputClaim(C.Structure):
     _fields_ = [("input", C.c_uint32), ("nvars", C.c_uint32), ("point_off", C.c_uint64), ("value", C.c_uint64 * 2)]
 
 
+class HgInputClaimBn254(C.Structure):
+    """hg_input_claim_bn254: a claim hg_verify_public_bn254 leaves on a secret input (4 canonical limbs per element)."""
+    _fields_ = [("input", C.c_uint32), ("nvars", C.c_uint32), ("point_off", C.c_uint64), ("value", C.c_uint64 * 4)]
+
+
 EXPORTS = [
     "hg_last_error", "hg_device_count", "hg_create", "hg_destroy", "hg_set_option", "hg_params_builtin", "hg_params_derive", "hg_grand_product", "hg_fold", "hg_setup", "hg_pk_free",
     "hg_pk_lasso_layout", "hg_pk_info", "hg_pk_node_eq_form", "hg_witness_from_json", "hg_witness_synthetic", "hg_witness_from_arrays", "hg_witness_derive", "hg_witness_derive_into",
     "hg_witness_get", "hg_witness_free", "hg_prove", "hg_warmup", "hg_prove_stream", "hg_encryption_layout", "hg_prove_encryptions", "hg_verify", "hg_verify_device", "hg_verify_device_mode", "hg_verify_device_batch",
     "hg_instance_from_ciphertext", "hg_instance_from_witness", "hg_instance_free", "hg_instance_coeffs", "hg_instance_get", "hg_pk_claim_shape", "hg_verify_public", "hg_verify_public_device", "hg_verify_public_batch", "hg_claims_settle", "hg_instance_mle", "hg_instance_mle_batch",
     "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_mle_eval",
-    "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_prove_encryptions_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
+    "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_verify_public_bn254", "hg_verify_public_device_bn254", "hg_claims_settle_bn254", "hg_instance_mle_bn254", "hg_prove_encryptions_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
 ]
 
 
@@ -968,6 +973,16 @@ class Instance:
         _check(L.hg_instance_mle(ctx.h if ctx is not None else None, self.h, which, index, _ptr(point), point.size // 2, _ptr(out)))
         return out
 
+    def mle_bn254(self, ctx, which, index, point):
+        """hg_instance_mle_bn254: the MLE of ais[index] (which 0) or ct0is (which 1) at an Fr point (Python ints below r) as a
+        Python int; ctx None: host loop, else the compact dot kernel over Fr."""
+        pt = Context._fr_pack(point)
+        out = np.zeros(4, dtype=np.uint64)
+        L = lib()
+        L.hg_instance_mle_bn254.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, u64p, C.c_size_t, u64p]
+        _check(L.hg_instance_mle_bn254(ctx.h if ctx is not None else None, self.h, which, index, _ptr(pt), len(point), _ptr(out)))
+        return Context._fr_unpack(out)[0]
+
     def __del__(self):
         try:
             if self.h:
@@ -1075,6 +1090,51 @@ def claims_settle(ctx, params, witness, claims):
     L = lib()
     L.hg_claims_settle.argtypes = [C.c_void_p, C.POINTER(HgParams), C.c_void_p, C.c_void_p, C.c_size_t, u64p]
     rc = L.hg_claims_settle(ctx.h if ctx is not None else None, C.byref(params), witness.h, claims.claims, claims.n, _ptr(claims.points))
+    if rc < 0:
+        raise HgError(lib().hg_last_error().decode())
+    return rc == 0, ("" if rc == 0 else lib().hg_last_error().decode())
+
+
+class InputClaimsBn254:
+    """What verify_public_bn254 leaves open: `claims` (a ctypes array of HgInputClaimBn254) and `points` (u64, four limbs per coordinate)."""
+
+    def __init__(self, claims, n, points):
+        self.claims, self.n, self.points = claims, n, points
+
+    def as_tuples(self):
+        """[(input, nvars, point limbs, value limbs)]: the whole content, for comparisons."""
+        out = []
+        for i in range(self.n):
+            c = self.claims[i]
+            out.append((int(c.input), int(c.nvars), tuple(int(x) for x in self.points[4 * c.point_off:4 * (c.point_off + c.nvars)]), tuple(int(x) for x in c.value)))
+        return out
+
+
+def verify_public_bn254(pk, instance, proof, ctx=None, device=False):
+    """hg_verify_public_bn254 (device=True: hg_verify_public_device_bn254 on ctx): the part of BfvEncrypt::verify over bn256::Fr that
+    the key, the proof, a_i and ct0_i decide. Returns (accepted, reason, InputClaimsBn254 or None), for claims_settle_bn254."""
+    L = lib()
+    nc, nco = pk_claim_shape(pk)
+    claims = (HgInputClaimBn254 * max(nc, 1))()
+    points = np.zeros(4 * max(nco, 1), dtype=np.uint64)
+    n = C.c_size_t(0)
+    tail = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.hg_verify_public_bn254.argtypes = tail
+    L.hg_verify_public_device_bn254.argtypes = [C.c_void_p] + tail
+    args = (pk.h, instance.h, proof, len(proof), claims, nc, _ptr(points), nco, C.byref(n))
+    rc = L.hg_verify_public_device_bn254(ctx.h if ctx is not None else None, *args) if device else L.hg_verify_public_bn254(*args)
+    if rc < 0:
+        raise HgError(lib().hg_last_error().decode())
+    if rc:
+        return False, lib().hg_last_error().decode(), None
+    return True, "", InputClaimsBn254(claims, n.value, points)
+
+
+def claims_settle_bn254(ctx, params, witness, claims):
+    """hg_claims_settle_bn254: every claim of an InputClaimsBn254 against the witness handle (ctx None: host): (accepted, reason)."""
+    L = lib()
+    L.hg_claims_settle_bn254.argtypes = [C.c_void_p, C.POINTER(HgParams), C.c_void_p, C.c_void_p, C.c_size_t, u64p]
+    rc = L.hg_claims_settle_bn254(ctx.h if ctx is not None else None, C.byref(params), witness.h, claims.claims, claims.n, _ptr(claims.points))
     if rc < 0:
         raise HgError(lib().hg_last_error().decode())
     return rc == 0, ("" if rc == 0 else lib().hg_last_error().decode())

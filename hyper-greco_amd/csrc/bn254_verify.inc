@@ -7,6 +7,8 @@
 //   the constant-gate sums (k_bn_const_sum), the Libra gathers over the reverse CSR wiring (k_bn_gather_T_jobs / k_bn_gather_B_jobs),
 //   the zkCNN DFT-row tables (k_bn_fft_part_jobs / k_bn_fft_tab_jobs), and every dot product of a table with an eq table in two
 //   launches (k_bn_vdot_jobs / k_bn_vdot_reduce), the MLE evaluations of the public inputs and of ct0is among them.
+// From the ciphertext (hg_verify_public_device_bn254): the public tables stay the compact signed coefficients of hg_instance and
+// are evaluated by k_bn_vdot_compact_jobs; the claims on the secret inputs launch nothing and are handed back.
 // Mode 0 only (the protocol modes are Goldilocks-only): every evaluation point is a run of the fixed Fr chain (BnChain).
 
 // ---- eq tables from chain offsets ---------------------------------------------------------------------------------------------
@@ -111,6 +113,40 @@ __global__ __launch_bounds__(256) void k_bn_vdot_reduce(const VdotJob* __restric
     if (threadIdx.x == 0) *J.out = fr_from_mont(a);   // canonical for the host
 }
 
+// The MLE evaluations of the public tables from the compact signed coefficients of hg_instance (the Fr counterpart of
+// k_vdot_compact_jobs, verifier_dev.hip). A job is nblk blocks of n = 2^log2_n coefficients and of 2n eq entries each; its WORD
+// indices t < nblk n are dealt out in tiles of VD_TILE to a flat grid through blk_job, as the jobs of k_bn_vdot_jobs are. Word t is
+// block b = t >> log2_n, r = t & (n-1): eq entry b 2n + lo + r meets coefficient n-1-r of block b (ais[i]: one block, lo = 0; ct0is:
+// k blocks, lo = n-1), so the 32-byte eq loads of a wavefront are consecutive and the coefficients are read descending over the same
+// cache lines. Only the half of each eq table that meets a non-padding word is read. The sign stays in registers: |z| times eq, or
+// times r - eq for a negative z; a zero coefficient is skipped.
+// Arithmetic: the integer rule of VD_ITEMS above. An instance holds |z| <= (q_i-1)/2 < 2^61 (instance_from_ciphertext), so a thread's
+// VD_ITEMS products stay below VD_ITEMS 2^61 r, far inside lz_reduce's 2^12 r^2; one lz_reduce and one fr_to_mont per thread.
+// Launch 2 is k_bn_vdot_reduce over a VdotJob per compact job (blk0, nblk = its tiles, out).
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): 54 VGPRs, no scratch, 8 waves per SIMD.
+struct BnCompactDotJob { const int64_t* c; const Fr* eq; u32 log2_n, nblk, lo; int blk0; };
+__global__ __launch_bounds__(256) void k_bn_vdot_compact_jobs(const BnCompactDotJob* __restrict__ jobs, const int* __restrict__ blk_job, Fr* __restrict__ partials) {
+    __shared__ Fr sm[256];
+    const BnCompactDotJob& J = jobs[blk_job[blockIdx.x]];
+    const size_t n = (size_t)1 << J.log2_n, total = n * J.nblk;
+    const size_t base = (size_t)(blockIdx.x - J.blk0) * VD_TILE + threadIdx.x;
+    const int64_t* __restrict__ c = J.c;
+    const Fr* __restrict__ eq = J.eq + J.lo;
+    WCol w = wcol_zero();
+    for (int k = 0; k < VD_ITEMS; k++) {
+        const size_t t = base + (size_t)k * 256;
+        if (t >= total) break;
+        const size_t b = t >> J.log2_n, r = t & (n - 1);
+        const int64_t z = c[b * n + (n - 1 - r)];
+        if (!z) continue;
+        const bool neg = z < 0;
+        wcol_mac_u64(w, neg ? (u64)0 - (u64)z : (u64)z, vd_negate_if(eq[b * 2 * n + r], neg));
+    }
+    Fr s = fr_to_mont(lz_canon(lz_reduce(w)));
+    s = block_sum_fr(s, sm);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
 // ---- the backend ----------------------------------------------------------------------------------------------------------------
 struct BnDevBackend : VerifyBackendT<Fr> {
     hg_ctx* ctx;
@@ -123,9 +159,12 @@ struct BnDevBackend : VerifyBackendT<Fr> {
     size_t ct0is_len = 0;
     std::vector<ResRef> slots;        // ticket -> result slot (bn254.hip res_slots: the bound check of the result buffer)
     // the challenge chain on the host (Montgomery), as far as the walk has used it; uploaded once in finish()
+    // own_chain (hg_claims_settle_bn254, hg_instance_mle_bn254: the points are the caller's): chm IS the chain, set by the caller
     std::vector<Fr> chm;
     size_t chain_need = 0;
+    bool own_chain = false;
     const Fr& chain_at(size_t i) {
+        if (own_chain && chm.size() <= i) throw Error("verifier: a job reads past the points it was given");
         if (chm.size() <= i) {
             const size_t have = chm.size(), want = std::max(i + 1, have + 2048);
             chm.resize(want);
@@ -157,8 +196,15 @@ struct BnDevBackend : VerifyBackendT<Fr> {
     std::map<std::pair<int, int>, const Fr*> W;        // (log2 size, inverse) -> w^i
     std::map<int, Fr> inv_size;
     std::vector<VdotJob> dots;
+    // hg_verify_public_device_bn254 / hg_instance_mle_bn254: the public tables as compact signed coefficients in HBM (cp set: a of
+    // k*n words, ct0 of k*n words); mle_input / mle_ct0is then record compact dot jobs (cdot_slots: what k_bn_vdot_reduce reads)
+    const Params* cp = nullptr;
+    const int64_t *d_ca = nullptr, *d_cct0 = nullptr;
+    std::vector<BnCompactDotJob> cdots;
+    std::vector<VdotJob> cdot_slots;
     std::vector<Fr> h_u;                               // the phase-1 evaluations of the Vanilla nodes with a phase 2 (canonical), back to back
     double t_begin = 0;                                // wall_ms() at the start of the verification (HG_TIMES=verify)
+    const char* who = "verify_device_bn254";           // the entry the HG_TIMES=verify lines name
 
     BnDevBackend(hg_ctx* c, const hg_pk* k, DevPool& p) : ctx(c), pk(k), st(c->stream), pool(p) { memset(&cs, 0, sizeof(cs)); }
     int slot() {
@@ -313,11 +359,33 @@ struct BnDevBackend : VerifyBackendT<Fr> {
         if (nvars < 0 || nvars > 40 || ((size_t)1 << nvars) != len) throw Error("verifier: claim point does not fit the input table");
         return dot(tab, true, eq_single(nvars, point_off), len);
     }
+    int mle_compact(const int64_t* c, int nblk, size_t lo, size_t point_off, int nvars) {
+        int lg = 0;
+        while ((1 << lg) < nblk) lg++;
+        if (nvars != cp->L + lg) throw Error("verifier: a point of the wrong length for a public table");   // (the job reads nblk * 2n eq entries)
+        const int t = slot();
+        BnCompactDotJob J;
+        memset(&J, 0, sizeof(J));
+        J.c = c; J.eq = eq_single(nvars, point_off); J.log2_n = (u32)cp->n_log2; J.nblk = (u32)nblk; J.lo = (u32)lo;
+        cdots.push_back(J);
+        VdotJob S;
+        memset(&S, 0, sizeof(S));
+        S.out = slots[t].dev;
+        cdot_slots.push_back(S);
+        return t;
+    }
     int mle_input(size_t k, size_t point_off, int nvars) override {
+        if (cp) {
+            if (k < 3 || k >= 3 + (size_t)cp->k) throw Error("verifier: input " + std::to_string(k) + " is not a public table");
+            return mle_compact(d_ca + (k - 3) * cp->PZ(), 1, 0, point_off, nvars);
+        }
         if (k >= d_inputs.size()) throw Error("verifier: no such input table");
         return mle_int(d_inputs[k], input_len[k], point_off, nvars);
     }
-    int mle_ct0is(size_t point_off, int nvars) override { return mle_int(d_ct0is, ct0is_len, point_off, nvars); }
+    int mle_ct0is(size_t point_off, int nvars) override {
+        if (cp) return mle_compact(d_cct0, cp->k, cp->PZ() - 1, point_off, nvars);
+        return mle_int(d_ct0is, ct0is_len, point_off, nvars);
+    }
 
     void finish() override {
         const bool times = hg_times("verify");   // read at every call (host.hpp)
@@ -325,14 +393,14 @@ struct BnDevBackend : VerifyBackendT<Fr> {
         if (times) {
             size_t n_fr = 0, n_int = 0;
             for (auto& d : dots) (d.a_is_int ? n_int : n_fr) += d.n;
-            fprintf(stderr, "[hg] verify_device_bn254: host walk ended at %.2f ms\n", t0 - t_begin);
+            fprintf(stderr, "[hg] %s: host walk ended at %.2f ms\n", who, t0 - t_begin);
             hipc(hipStreamSynchronize(st), "sync");
-            fprintf(stderr, "[hg] verify_device_bn254: uploads drained %.2f ms after the walk ended; %zu eq tables (%zu claim tables), %zu gathers, %zu + %zu, %zu dots (%zu Fr x Fr entries, %zu integer x Fr entries)\n",
-                    wall_ms() - t0, fills.size(), preps.size(), gts.size(), gbs.size(), fft_tabs.size(), dots.size(), n_fr, n_int);
+            fprintf(stderr, "[hg] %s: uploads drained %.2f ms after the walk ended; %zu eq tables (%zu claim tables), %zu gathers, %zu + %zu, %zu dots (%zu Fr x Fr entries, %zu integer x Fr entries), %zu compact dots\n",
+                    who, wall_ms() - t0, fills.size(), preps.size(), gts.size(), gbs.size(), fft_tabs.size(), dots.size(), n_fr, n_int, cdots.size());
         }
-        auto lap = [&](const char* what) { if (times) { hipc(hipStreamSynchronize(st), "sync"); fprintf(stderr, "[hg] verify_device_bn254: %8.2f ms  %s\n", wall_ms() - t0, what); } };
+        auto lap = [&](const char* what) { if (times) { hipc(hipStreamSynchronize(st), "sync"); fprintf(stderr, "[hg] %s: %8.2f ms  %s\n", who, wall_ms() - t0, what); } };
         // the chain run the walk used, then every job array, staged side by side and copied over in one transfer (bn_flush)
-        (void)chain_at(chain_need ? chain_need - 1 : 0);
+        if (!own_chain || chain_need) (void)chain_at(chain_need ? chain_need - 1 : 0);
         const Fr* d_chal = bn_stage(ctx, chm.data(), std::max<size_t>(chain_need, 1));
         const VeqPrep* d_prep = preps.empty() ? nullptr : bn_stage(ctx, preps.data(), preps.size());
         const VeqFill* d_fill = fills.empty() ? nullptr : bn_stage(ctx, fills.data(), fills.size());
@@ -353,6 +421,16 @@ struct BnDevBackend : VerifyBackendT<Fr> {
         }
         const VdotJob* d_dots = dots.empty() ? nullptr : bn_stage(ctx, dots.data(), dots.size());
         const int* d_blk_job = blk_job.empty() ? nullptr : bn_stage(ctx, blk_job.data(), blk_job.size());
+        std::vector<int> cblk_job;
+        for (size_t q = 0; q < cdots.size(); q++) {
+            const size_t words = (size_t)cdots[q].nblk << cdots[q].log2_n;
+            cdots[q].blk0 = cdot_slots[q].blk0 = (int)cblk_job.size();
+            cdot_slots[q].nblk = (int)((words + VD_TILE - 1) / VD_TILE);
+            cblk_job.insert(cblk_job.end(), (size_t)cdot_slots[q].nblk, (int)q);
+        }
+        const BnCompactDotJob* d_cdots = cdots.empty() ? nullptr : bn_stage(ctx, cdots.data(), cdots.size());
+        const VdotJob* d_cslots = cdots.empty() ? nullptr : bn_stage(ctx, cdot_slots.data(), cdot_slots.size());
+        const int* d_cblk_job = cblk_job.empty() ? nullptr : bn_stage(ctx, cblk_job.data(), cblk_job.size());
         bn_flush(ctx, st);
         lap("descriptors uploaded");
         if (d_prep) {
@@ -381,6 +459,11 @@ struct BnDevBackend : VerifyBackendT<Fr> {
             Fr* part = pool.get<Fr>(blk_job.size());
             k_bn_vdot_jobs<<<(unsigned)blk_job.size(), 256, 0, st>>>(d_dots, d_blk_job, part);
             k_bn_vdot_reduce<<<(unsigned)dots.size(), 256, 0, st>>>(d_dots, part);
+        }
+        if (d_cdots) {
+            Fr* part = pool.get<Fr>(cblk_job.size());
+            k_bn_vdot_compact_jobs<<<(unsigned)cblk_job.size(), 256, 0, st>>>(d_cdots, d_cblk_job, part);
+            k_bn_vdot_reduce<<<(unsigned)cdots.size(), 256, 0, st>>>(d_cslots, part);
         }
         lap("dot products");
         res_sync(ctx, st, "verifier: synchronise");
@@ -425,4 +508,100 @@ std::string verify_proof_device_bn254(hg_ctx* ctx, const hg_pk* pk, const Witnes
     D.input_len.pop_back();
     if (hg_times("verify")) fprintf(stderr, "[hg] verify_device_bn254: inputs enqueued at %.2f ms\n", wall_ms() - tv0);
     return verify_proof_with_bn254(D, p, pk->lasso, pk->circuit, proof, len);
+}
+
+// ---- hg_verify_public_device_bn254, hg_claims_settle_bn254, hg_instance_mle_bn254 ------------------------------------------------
+// every way out of an entry drains the stream before the staging buffer, the arena or the caller's arrays are reused (see above)
+struct BnDrain {
+    hipStream_t st;
+    ~BnDrain() { (void)hipStreamSynchronize(st); }
+};
+static const int64_t* bn_upload_coeffs(hg_ctx* ctx, DevPool& pool, const std::vector<int64_t>& src) {
+    int64_t* d = pool.get<int64_t>(src.size());
+    hipc(hipMemcpyAsync(d, src.data(), src.size() * 8, hipMemcpyHostToDevice, ctx->stream), "verifier: upload the instance");
+    return d;
+}
+static Fr fr_from_limbs_mont(const u64* v) { return fr_to_mont(fr_make(v[0], v[1], v[2], v[3])); }
+
+// The public part of the verification on the device: the instance's 2 k n signed words are uploaded as they are (8.4 MB at n=32768
+// k=16 against 30.9 MB of laid-out tables), the walk records compact dot jobs for ct0is and the ais claims and NOTHING for the secret
+// inputs - their claims come back in `open`, value from the walk and point from the chain. One stream, one synchronisation.
+std::string verify_public_device_bn254(hg_ctx* ctx, const hg_pk* pk, const Instance& inst, const uint8_t* proof, size_t len, std::vector<OpenClaimBn>& open) {
+    if (!pk->ctx) throw Error("hg_verify_public_device_bn254: host-only prover key");
+    const double tv0 = wall_ms();
+    struct Total { double t0; ~Total() { if (hg_times("verify")) fprintf(stderr, "[hg] verify_public_device_bn254: %.2f ms in all\n", wall_ms() - t0); } } total{tv0};
+    open.clear();
+    hipc(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->arena_reset();
+    DevPool pool(ctx);
+    BnDrain drain{ctx->stream};
+    const Params& p = pk->params;
+    BnDevBackend D(ctx, pk, pool);
+    D.t_begin = tv0;
+    D.who = "verify_public_device_bn254";
+    D.cp = &p;
+    D.d_ca = bn_upload_coeffs(ctx, pool, inst.a);
+    D.d_cct0 = bn_upload_coeffs(ctx, pool, inst.ct0);
+    VerifyPendingT<Fr> v = verify_walk_bn254(D, p, pk->lasso, pk->circuit, proof, len, true);
+    if (!v.reason.empty()) return v.reason;
+    D.finish();
+    std::string why = verify_complete_bn254(v);
+    if (why.empty()) for (const auto& cl : v.open) open.push_back(open_claim_bn254(cl));
+    return why;
+}
+
+// The settle step on the device: the claim points staged as a chain of their own for the eq jobs, each witness table uploaded once
+// (as the integers it holds: the integer path of k_bn_vdot_jobs lifts them), one dot product per claim, one synchronisation.
+std::string claims_settle_device_bn254(hg_ctx* ctx, const Params& p, const Witness& w, const std::vector<OpenClaimBn>& claims) {
+    if (claims.empty()) return "";
+    hipc(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->arena_reset();
+    DevPool pool(ctx);
+    BnDrain drain{ctx->stream};
+    BnDevBackend D(ctx, nullptr, pool);
+    D.own_chain = true;
+    std::map<size_t, const u64*> d_tab;   // one upload per table, however many claims it carries
+    std::vector<int> ticket;
+    for (const OpenClaimBn& cl : claims) {
+        int lg = 0;
+        const u64* tab = input_table(p, w, cl.input, &lg);
+        const size_t nv = cl.point4.size() / 4;
+        if ((size_t)lg != nv) throw Error("hg_claims_settle_bn254: a claim on input " + std::to_string(cl.input) + " has " + std::to_string(nv) + " coordinates, its table " + std::to_string(lg) + " variables");
+        auto it = d_tab.find(cl.input);
+        if (it == d_tab.end()) {
+            u64* d = pool.get<u64>((size_t)1 << lg);
+            hipc(hipMemcpyAsync(d, tab, ((size_t)1 << lg) * 8, hipMemcpyHostToDevice, ctx->stream), "hg_claims_settle_bn254: upload inputs");
+            it = d_tab.emplace(cl.input, d).first;
+        }
+        const size_t off = D.chm.size();
+        for (size_t j = 0; j < nv; j++) D.chm.push_back(fr_from_limbs_mont(&cl.point4[4 * j]));
+        ticket.push_back(D.mle_int(it->second, (size_t)1 << lg, off, lg));
+    }
+    D.finish();
+    long long bad = -1;
+    for (size_t i = 0; i < claims.size(); i++)
+        if (memcmp(D.slots[ticket[i]].host->l, claims[i].value, 32) != 0 && (bad < 0 || (long long)claims[i].input < bad)) bad = (long long)claims[i].input;
+    return bad < 0 ? std::string() : "input claim mismatch at input " + std::to_string(bad);
+}
+
+// one eq job and one compact dot job
+void instance_mle_device_bn254(hg_ctx* ctx, const Params& p, const Instance& inst, int which, int index, const u64* point4, size_t nvars, u64 out4[4]) {
+    hipc(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->arena_reset();
+    DevPool pool(ctx);
+    BnDrain drain{ctx->stream};
+    BnDevBackend D(ctx, nullptr, pool);
+    D.own_chain = true;
+    D.cp = &p;
+    for (size_t j = 0; j < nvars; j++) D.chm.push_back(fr_from_limbs_mont(point4 + 4 * j));
+    int t;
+    if (which == 0) {
+        D.d_ca = bn_upload_coeffs(ctx, pool, inst.a);
+        t = D.mle_input(3 + (size_t)index, 0, (int)nvars);
+    } else {
+        D.d_cct0 = bn_upload_coeffs(ctx, pool, inst.ct0);
+        t = D.mle_ct0is(0, (int)nvars);
+    }
+    D.finish();
+    memcpy(out4, D.slots[t].host->l, 32);
 }

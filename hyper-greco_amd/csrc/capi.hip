@@ -1327,6 +1327,96 @@ int hg_verify_device_batch_bn254(hg_ctx* ctx, const hg_pk* pk, const hg_witness*
     HG_CATCH(-1)
 }
 
+// ---- verification from the ciphertext over bn256::Fr (hg.h: hg_verify_public_bn254 and what goes with it) -------------------------
+static int verify_public_entry_bn254(const char* who, hg_ctx* ctx, bool device, const hg_pk* pk, const void* instance, const uint8_t* proof, size_t len,
+                                     void* claims, size_t claim_cap, uint64_t* points4, size_t coord_cap, size_t* n_claims) {
+    if (n_claims) *n_claims = 0;
+    if (device && (!ctx || !pk || !pk->ctx)) throw Error(std::string(who) + ": needs a device context and a device prover key");
+    if (!pk || !instance || !proof || !n_claims) throw Error(std::string(who) + ": null argument");
+    const hg_instance* in = as_instance(instance);
+    check_instance(pk, in, who);
+    size_t need_claims = 0, need_coords = 0;
+    claim_shape(pk->params, pk->lasso, pk->circuit, &need_claims, &need_coords);
+    if (claim_cap < need_claims || coord_cap < need_coords || (need_claims && !claims) || (need_coords && !points4))
+        throw Error(std::string(who) + ": room for " + std::to_string(need_claims) + " claims and " + std::to_string(need_coords) + " coordinates is needed (hg_pk_claim_shape)");
+    std::vector<OpenClaimBn> open;
+    const std::string why = device ? hg::bn::verify_public_device_bn254(ctx, pk, in->inst, proof, len, open)
+                                   : verify_public_bn254(pk->params, pk->lasso, pk->circuit, in->inst, proof, len, open);
+    if (!why.empty()) { g_last_error = why; return 1; }
+    size_t coords = 0;
+    for (const OpenClaimBn& c : open) coords += c.point4.size() / 4;
+    if (open.size() > claim_cap || coords > coord_cap) throw Error(std::string(who) + ": the walk left more claims than hg_pk_claim_shape counts");
+    hg_input_claim_bn254* out = static_cast<hg_input_claim_bn254*>(claims);
+    size_t off = 0;
+    for (size_t i = 0; i < open.size(); i++) {
+        out[i].input = (uint32_t)open[i].input;
+        out[i].nvars = (uint32_t)(open[i].point4.size() / 4);
+        out[i].point_off = off;
+        memcpy(out[i].value, open[i].value, 32);
+        if (!open[i].point4.empty()) memcpy(points4 + 4 * off, open[i].point4.data(), open[i].point4.size() * 8);
+        off += out[i].nvars;
+    }
+    *n_claims = open.size();
+    return 0;
+}
+
+int hg_verify_public_bn254(const hg_pk* pk, const void* instance, const uint8_t* proof, size_t len, void* claims, size_t claim_cap, uint64_t* points4,
+                           size_t coord_cap, size_t* n_claims) {
+    HG_TRY
+    return verify_public_entry_bn254("hg_verify_public_bn254", nullptr, false, pk, instance, proof, len, claims, claim_cap, points4, coord_cap, n_claims);
+    HG_CATCH(-1)
+}
+
+int hg_verify_public_device_bn254(hg_ctx* ctx, const hg_pk* pk, const void* instance, const uint8_t* proof, size_t len, void* claims, size_t claim_cap,
+                                  uint64_t* points4, size_t coord_cap, size_t* n_claims) {
+    HG_TRY
+    return verify_public_entry_bn254("hg_verify_public_device_bn254", ctx, true, pk, instance, proof, len, claims, claim_cap, points4, coord_cap, n_claims);
+    HG_CATCH(-1)
+}
+
+int hg_claims_settle_bn254(hg_ctx* ctx, const hg_params* params, const hg_witness* w, const void* claims, size_t n, const uint64_t* points4) {
+    HG_TRY
+    if (!params || !w || (n && (!claims || !points4))) throw Error("hg_claims_settle_bn254: null argument");
+    Params p(*params);
+    const size_t SZ = p.SZ(), k = (size_t)p.k;
+    const Witness& v = w->w;
+    if (w->params.n != params->n || w->params.k != params->k || v.s.size() != SZ || v.e.size() != SZ || v.k1.size() != SZ || v.ais.size() != k * SZ ||
+        v.r1is.size() != k * SZ || v.r2is.size() != k * p.PZ())
+        throw Error("hg_claims_settle_bn254: the witness was built for other parameters");
+    const hg_input_claim_bn254* in = static_cast<const hg_input_claim_bn254*>(claims);
+    std::vector<OpenClaimBn> cl(n);
+    for (size_t i = 0; i < n; i++) {
+        if (in[i].input > 3 + 2 * k) throw Error("hg_claims_settle_bn254: input " + std::to_string(in[i].input) + " is not an input of the circuit");
+        if (in[i].nvars > 40) throw Error("hg_claims_settle_bn254: a claim with " + std::to_string(in[i].nvars) + " coordinates");
+        cl[i].input = in[i].input;
+        memcpy(cl[i].value, in[i].value, 32);
+        cl[i].point4.assign(points4 + 4 * in[i].point_off, points4 + 4 * (in[i].point_off + in[i].nvars));
+        for (size_t j = 0; j < in[i].nvars; j++) if (!bn254_canonical(&cl[i].point4[4 * j])) throw Error("hg_claims_settle_bn254: non-canonical coordinate");
+        if (!bn254_canonical(cl[i].value)) throw Error("hg_claims_settle_bn254: non-canonical value");
+    }
+    const std::string why = ctx ? hg::bn::claims_settle_device_bn254(ctx, p, v, cl) : claims_settle_bn254(p, v, cl);
+    if (why.empty()) return 0;
+    g_last_error = why;
+    return 1;
+    HG_CATCH(-1)
+}
+
+int hg_instance_mle_bn254(hg_ctx* ctx, const void* instance, int which, int index, const uint64_t* point4, size_t nvars, uint64_t out4[4]) {
+    HG_TRY
+    if (!instance || (nvars && !point4) || !out4) throw Error("hg_instance_mle_bn254: null argument");
+    const hg_instance* in = as_instance(instance);
+    Params p(in->params);
+    if (which != 0 && which != 1) throw Error("hg_instance_mle_bn254: which is 0 (ais[index]) or 1 (ct0is)");
+    if (which == 0 && (index < 0 || index >= p.k)) throw Error("hg_instance_mle_bn254: no such modulus");
+    if (nvars != (size_t)(which ? p.ct0is_log2() : p.L)) throw Error("hg_instance_mle_bn254: the table has " + std::to_string(which ? p.ct0is_log2() : p.L) + " variables");
+    for (size_t i = 0; i < nvars; i++)
+        if (!bn254_canonical(point4 + 4 * i)) throw Error("hg_instance_mle_bn254: non-canonical coordinate");
+    if (ctx) hg::bn::instance_mle_device_bn254(ctx, p, in->inst, which, index, point4, nvars, out4);
+    else instance_mle_bn254(p, in->inst, which, index, point4, nvars, out4);
+    return 0;
+    HG_CATCH(-1)
+}
+
 int hg_circuit_eval(const hg_pk* pk, const hg_witness* w, uint64_t* lasso_in, size_t lasso_cap, uint64_t* sum_out, size_t sum_cap) {
     HG_TRY
     if (!pk || !w) throw Error("hg_circuit_eval: null argument");

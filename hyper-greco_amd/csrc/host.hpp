@@ -254,13 +254,29 @@ E2 instance_mle(const Params& p, const Instance& inst, int which, int index, con
 namespace bn { struct Fr; }
 std::string verify_proof_with_bn254(VerifyBackendT<bn::Fr>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len);
 // its two steps (hg_verify_device_batch_bn254), as verify_walk / verify_complete (mode 0: no chain is handed over)
-VerifyPendingT<bn::Fr> verify_walk_bn254(VerifyBackendT<bn::Fr>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len);
+// public_only (hg_verify_public_device_bn254): as in verify_walk
+VerifyPendingT<bn::Fr> verify_walk_bn254(VerifyBackendT<bn::Fr>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len,
+                                         bool public_only = false);
 std::string verify_complete_bn254(VerifyPendingT<bn::Fr>& v);
 // the same over bn256::Fr (F = E = Fr, 32-byte proof elements): the bn254 test family
 std::string verify_proof_bn254(const Params& p, const LassoPlan& lp, const HCircuit& c, const Witness& w, const uint8_t* proof, size_t len);
+// The split verifier over bn256::Fr (hg_verify_public_bn254, hg_claims_settle_bn254, hg_instance_mle_bn254). The walk keeps its
+// elements in Montgomery form; a claim that leaves it is an OpenClaimBn: 4 canonical little-endian limbs per element, the form of
+// the C ABI. Contracts as verify_public / claims_settle / instance_mle; mode 0 only; input_table's Error names hg_claims_settle.
+struct OpenClaimBn { size_t input; std::vector<u64> point4; u64 value[4]; };
+bool bn254_canonical(const u64 v[4]);   // below r
+OpenClaimBn open_claim_bn254(const OpenClaimT<bn::Fr>& c);
+std::string verify_public_bn254(const Params& p, const LassoPlan& lp, const HCircuit& c, const Instance& inst, const uint8_t* proof, size_t len,
+                                std::vector<OpenClaimBn>& open);
+std::string claims_settle_bn254(const Params& p, const Witness& w, const std::vector<OpenClaimBn>& claims);
+void instance_mle_bn254(const Params& p, const Instance& inst, int which, int index, const u64* point4, size_t nvars, u64 out4[4]);
 // the same with the table-sized work on the device (bn254_verify.inc; needs a device context and a device key)
 namespace bn {
 std::string verify_proof_device_bn254(hg_ctx* ctx, const hg_pk* pk, const Witness& w, const uint8_t* proof, size_t len);
+// hg_verify_public_device_bn254, hg_claims_settle_bn254 with a context, hg_instance_mle_bn254 with a context
+std::string verify_public_device_bn254(hg_ctx* ctx, const hg_pk* pk, const Instance& inst, const uint8_t* proof, size_t len, std::vector<OpenClaimBn>& open);
+std::string claims_settle_device_bn254(hg_ctx* ctx, const Params& p, const Witness& w, const std::vector<OpenClaimBn>& claims);
+void instance_mle_device_bn254(hg_ctx* ctx, const Params& p, const Instance& inst, int which, int index, const u64* point4, size_t nvars, u64 out4[4]);
 // hg_verify_device_batch_bn254 (bn254_verify_batch.inc): proof i against ws[i]; why[i] = "" accepted, else the reason. An hg::Error
 // inside one proof's walk names its index.
 void verify_batch_device_bn254(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Witness*>& ws, const std::vector<const uint8_t*>& proofs,

@@ -741,8 +741,9 @@ std::string verify_complete(VerifyPending& v) { return complete_pending(v); }
 std::string verify_proof_with_bn254(VerifyBackendT<bn::Fr>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len) {
     return verify_with_backend<BnField>(dev, p, lp, c, proof, len, 0);
 }
-VerifyPendingT<bn::Fr> verify_walk_bn254(VerifyBackendT<bn::Fr>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len) {
-    return walk_with_backend<BnField>(dev, p, lp, c, proof, len, 0);
+VerifyPendingT<bn::Fr> verify_walk_bn254(VerifyBackendT<bn::Fr>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len,
+                                         bool public_only) {
+    return walk_with_backend<BnField>(dev, p, lp, c, proof, len, 0, public_only);
 }
 std::string verify_complete_bn254(VerifyPendingT<bn::Fr>& v) { return complete_pending(v); }
 
@@ -811,6 +812,51 @@ std::string claims_settle(const Params& p, const Witness& w, const std::vector<O
         const u64* tab = input_table(p, w, cl.input, &lg);
         if ((size_t)lg != cl.point.size()) throw Error("hg_claims_settle: a claim on input " + std::to_string(cl.input) + " has " + std::to_string(cl.point.size()) + " coordinates, its table " + std::to_string(lg) + " variables");
         if (!e2_eq(mle_eval<GlField>(tab, cl.point), cl.value) && (bad < 0 || (long long)cl.input < bad)) bad = (long long)cl.input;
+    }
+    return bad < 0 ? std::string() : "input claim mismatch at input " + std::to_string(bad);
+}
+
+// ---- the same split over bn256::Fr (hg_verify_public_bn254 and what goes with it) ------------------------------------------------
+// The walk keeps its elements in Montgomery form; OpenClaimBn is what crosses the C ABI: canonical limbs.
+bool bn254_canonical(const u64 v[4]) { return !bn::fr_geq_p(bn::fr_make(v[0], v[1], v[2], v[3])); }
+OpenClaimBn open_claim_bn254(const OpenClaimT<bn::Fr>& c) {
+    OpenClaimBn o;
+    o.input = c.input;
+    o.point4.resize(4 * c.point.size());
+    for (size_t j = 0; j < c.point.size(); j++) { const bn::Fr x = bn::fr_from_mont(c.point[j]); memcpy(&o.point4[4 * j], x.l, 32); }
+    const bn::Fr v = bn::fr_from_mont(c.value);
+    memcpy(o.value, v.l, 32);
+    return o;
+}
+static std::vector<bn::Fr> bn_point(const u64* point4, size_t nvars) {
+    std::vector<bn::Fr> pt(nvars);
+    for (size_t j = 0; j < nvars; j++) pt[j] = bn::fr_to_mont(bn::fr_make(point4[4 * j], point4[4 * j + 1], point4[4 * j + 2], point4[4 * j + 3]));
+    return pt;
+}
+std::string verify_public_bn254(const Params& p, const LassoPlan& lp, const HCircuit& c, const Instance& inst, const uint8_t* proof, size_t len,
+                                std::vector<OpenClaimBn>& open) {
+    open.clear();
+    const Witness none;
+    std::vector<OpenClaimT<bn::Fr>> left;
+    std::string why = verify_impl<BnField>(p, lp, c, none, proof, len, 0, &inst, &left);
+    if (why.empty()) for (const auto& cl : left) open.push_back(open_claim_bn254(cl));
+    return why;
+}
+void instance_mle_bn254(const Params& p, const Instance& inst, int which, int index, const u64* point4, size_t nvars, u64 out4[4]) {
+    const std::vector<bn::Fr> pt = bn_point(point4, nvars);
+    const bn::Fr v = bn::fr_from_mont(which == 0 ? mle_compact<BnField>(&inst.a[(size_t)index * p.PZ()], p.PZ(), 1, p.PZ() - 1, pt)
+                                                 : mle_compact<BnField>(inst.ct0.data(), p.PZ(), (size_t)p.k, p.SZ() - 2, pt));
+    memcpy(out4, v.l, 32);
+}
+std::string claims_settle_bn254(const Params& p, const Witness& w, const std::vector<OpenClaimBn>& claims) {
+    long long bad = -1;
+    for (const OpenClaimBn& cl : claims) {
+        int lg = 0;
+        const u64* tab = input_table(p, w, cl.input, &lg);
+        const size_t nv = cl.point4.size() / 4;
+        if ((size_t)lg != nv) throw Error("hg_claims_settle_bn254: a claim on input " + std::to_string(cl.input) + " has " + std::to_string(nv) + " coordinates, its table " + std::to_string(lg) + " variables");
+        const bn::Fr got = bn::fr_from_mont(mle_eval<BnField>(tab, bn_point(cl.point4.data(), nv)));
+        if (memcmp(got.l, cl.value, 32) != 0 && (bad < 0 || (long long)cl.input < bad)) bad = (long long)cl.input;
     }
     return bad < 0 ? std::string() : "input claim mismatch at input " + std::to_string(bad);
 }

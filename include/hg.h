@@ -224,7 +224,9 @@ int hg_verify_device_batch(hg_ctx* ctx, const hg_pk* pk, const hg_witness* const
  * tables - and hand back what is left, the claims (input, point, value) on the five secret inputs: what a commitment layer would
  * open (the reference's PCS type parameter is dead). hg_claims_settle checks such claims against a witness handle,
  * which is the reference's contract again: hg_verify_public followed by hg_claims_settle decides what hg_verify_mode decides.
- * Goldilocks, modes 0..3, one proof per call (hg_verify_public_batch: a run of them in one device pass).
+ * Goldilocks, modes 0..3, one proof per call (hg_verify_public_batch: a run of them in one device pass). Over bn256::Fr:
+ * hg_verify_public_bn254 and its neighbours, below hg_verify_device_batch_bn254; the instance handle and hg_pk_claim_shape serve
+ * both fields (an instance holds signed integers, the claim shape depends on the wiring only).
  * The instance handle (hg_instance*) and the claim array (hg_input_claim*) cross the ABI as void pointers. */
 typedef struct hg_input_claim {
     uint32_t input;      /* chain_par! order [REF sk_encryption_circuit.rs:476-481]: 0 s, 1 e, 2 k1, 3+k+i r1is[i], 3+2k r2is (never 3..3+k-1: the claims on ais are settled inside) */
@@ -531,6 +533,48 @@ int hg_verify_device_bn254(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, co
  * next group are copied meanwhile. */
 int hg_verify_device_batch_bn254(hg_ctx* ctx, const hg_pk* pk, const hg_witness* const* ws, const uint8_t* const* proofs,
                                  const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap);
+
+/* ---- Verification from the ciphertext over bn256::Fr: the counterparts of hg_verify_public, hg_verify_public_device,
+ * hg_claims_settle and hg_instance_mle (above), with the same contracts, return values and error rules. BN254 is mode 0 only: no
+ * entry takes a mode. An element crosses the ABI as 4 canonical little-endian u64 limbs. The instance is the field-independent
+ * hg_instance* of hg_instance_from_ciphertext / hg_instance_from_witness, the claim counts are hg_pk_claim_shape's; instance and
+ * claim array (hg_input_claim_bn254*) cross as void pointers. hg_verify_public_bn254 followed by hg_claims_settle_bn254 decides
+ * what hg_verify_bn254 decides. One proof per call; there is no batched form. */
+typedef struct hg_input_claim_bn254 {
+    uint32_t input;      /* as hg_input_claim: 0 s, 1 e, 2 k1, 3+k+i r1is[i], 3+2k r2is (never 3..3+k-1) */
+    uint32_t nvars;
+    uint64_t point_off;  /* coordinates points4[4*point_off .. 4*(point_off+nvars)), 4 limbs each */
+    uint64_t value[4];
+} hg_input_claim_bn254;
+
+/* = BfvEncrypt::verify::<Fr, Fr> [REF sk_encryption_circuit.rs:462-517, 614-626] up to the point where it needs a secret: the walk
+ *   of hg_verify_bn254 with ct0is and the ais tables evaluated from the instance's compact coefficients (a negative z counts as
+ *   r - |z|); a claim on any other input is not evaluated but written out. claims: room for claim_cap hg_input_claim_bn254; points4:
+ *   room for coord_cap coordinates (4 words each). Returns 0 accept (claims and points filled, *n_claims set), 1 reject (reason in
+ *   hg_last_error, *n_claims = 0; the reasons are hg_verify_bn254's), -1 error: a null argument, claim_cap or coord_cap below
+ *   hg_pk_claim_shape, an instance of other parameters; the device form also: no context, a host-only key.
+ *   Claim order: inputs ascending, within one input the order in which the walk pushes them; the same for both forms. Points are
+ *   written out as values.
+ *   hg_verify_public_bn254 is the host form (works with hg_setup(NULL, ..)). hg_verify_public_device_bn254 runs the table-sized
+ *   work as hg_verify_device_bn254 does (one stream, one synchronisation), with the instance uploaded as it is (2 k n signed words:
+ *   8.4 MB at n=32768 k=16, and no witness table) and the MLE evaluations of ais and ct0is in one kernel over Fr that reads the signed
+ *   words and the half of each eq table that meets a non-padding word; the secret inputs launch nothing. Same decisions, claims and
+ *   points as the host form, bit for bit. */
+int hg_verify_public_bn254(const hg_pk* pk, const void* instance, const uint8_t* proof, size_t len, void* claims, size_t claim_cap,
+                           uint64_t* points4, size_t coord_cap, size_t* n_claims);
+int hg_verify_public_device_bn254(hg_ctx* ctx, const hg_pk* pk, const void* instance, const uint8_t* proof, size_t len, void* claims,
+                                  size_t claim_cap, uint64_t* points4, size_t coord_cap, size_t* n_claims);
+/* = izip_eq!(inputs, input_claims) [REF sk_encryption_circuit.rs:512-516] over Fr for the n claims of an hg_input_claim_bn254 array:
+ *   table `input` of w (any input 0 .. 3+2k) at the point == value, for every claim. ctx == NULL: host; with a context: the points
+ *   staged as a chain of their own, each table uploaded once, one batch of eq tables and dot products, one synchronisation. Returns
+ *   0, 1 ("input claim mismatch at input K", the lowest failing K: the verifiers' text) or -1 (a null argument, a handle of other
+ *   parameters, no such input, nvars that is not the table's, a coordinate or value that is not below r). */
+int hg_claims_settle_bn254(hg_ctx* ctx, const hg_params* params, const hg_witness* w, const void* claims, size_t n, const uint64_t* points4);
+/* part exposed for parity tests: the MLE of one laid-out public table at an Fr point, computed from the compact coefficients
+ * (ctx == NULL: host loop; else the kernel of hg_verify_public_device_bn254). which 0: ais[index] (L vars); 1: ct0is, the whole
+ * table (L + log2 k vars, index ignored). out4: canonical limbs. -1 for a null argument, another selector or modulus, nvars that is
+ * not the table's, a coordinate that is not below r. */
+int hg_instance_mle_bn254(hg_ctx* ctx, const void* instance, int which, int index, const uint64_t* point4, size_t nvars, uint64_t out4[4]);
 
 /* hg_witness_derive and hg_prove_bn254 for a run of n_enc ENCRYPTIONS under one key, pipelined: hg_prove_encryptions over bn256::Fr
  *   [REF scripts/circuit_sk.py:18-140 followed by sk_encryption_circuit.rs:417-460, 614-626; the loop a proving service writes around
