@@ -1466,6 +1466,24 @@ int hg_sumcheck(hg_ctx* ctx, int kind, size_t nv, size_t ntab, const uint64_t* c
     HG_TRY
     if (!ctx || !tables || !is_base || !claim2 || (npw && !pw)) throw Error("hg_sumcheck: null argument (a HIP device is required)");
     if (ntab == 0 || nv == 0 || nv > 30) throw Error("hg_sumcheck: bad shape");
+    // everything the kernels cannot do is refused here, on the host, before anything is uploaded or launched
+    if (kind < 0 || kind > 2) throw Error("hg_sumcheck: kind must be 0 (collation), 1 (grand product) or 2 (prodsum)");
+    if (kind != 0 && (ntab & 1)) throw Error("hg_sumcheck: kinds 1 and 2 take an even number of tables (pairs)");
+    const size_t max_tab = kind == 0 ? (size_t)dev::PW_MAX : kind == 1 ? 2 * (size_t)dev::PW_MAX : 2 * (size_t)dev::PS_MAX_PAIRS;
+    if (ntab > max_tab) throw Error("hg_sumcheck: kind " + std::to_string(kind) + " carries at most " + std::to_string(max_tab) + " tables");
+    const size_t need_pw = kind == 0 ? ntab : kind == 1 ? ntab / 2 : 0;
+    if (npw < need_pw) throw Error("hg_sumcheck: kind " + std::to_string(kind) + " with " + std::to_string(ntab) + " tables needs " + std::to_string(need_pw) + " powers");
+    for (size_t i = 0; i < ntab; i++) {
+        if (!tables[i]) throw Error("hg_sumcheck: null table");
+        if (kind == 2 ? (is_base[i] != 0) != (i % 2 == 0) : (is_base[i] != 0) != (is_base[0] != 0))
+            throw Error(kind == 2 ? "hg_sumcheck: prodsum expects (base, ext) table pairs" : "hg_sumcheck: mixed table fields");
+    }
+    if (claim2[0] >= GL_P || claim2[1] >= GL_P) throw Error("hg_sumcheck: non-canonical claim");
+    for (size_t i = 0; i < 2 * npw; i++) if (pw[i] >= GL_P) throw Error("hg_sumcheck: non-canonical power");
+    for (size_t i = 0; i < ntab; i++) {
+        const size_t words = (is_base[i] ? (size_t)1 : (size_t)2) << nv;
+        for (size_t j = 0; j < words; j++) if (tables[i][j] >= GL_P) throw Error("hg_sumcheck: non-canonical entry in table " + std::to_string(i));
+    }
     SumcheckIO io;
     io.kind = kind; io.nv = nv; io.chain_skip = chain_skip;
     io.tables.assign(tables, tables + ntab);

@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1640,7 +1641,11 @@ std::vector<uint8_t> prove_lasso_node(hg_ctx* ctx, const hg_pk* pk, const u64* l
     const size_t N = (size_t)1 << pk->lasso.nu;
     u64* d_in = ctx->alloc_n<u64>(N);
     hip_check(hipMemcpyAsync(d_in, lasso_in_host, N * 8, hipMemcpyHostToDevice, ctx->stream), "upload lasso input");
+    // the node as a prove runs it: forked ahead of it, its side streams joined behind it (the context option one_stream: in place)
+    P.record_fork();
     ClaimRef cr = P.lasso_node(d_in);
+    P.fork_nodes_stream();   // (no node reductions here: the stream the node's openings would follow them on)
+    P.join_side_streams();
     P.finish();
     if (claim_out) {
         const u64* chain = challenge_chain(2 * (cr.point_off + cr.len));
@@ -1685,6 +1690,7 @@ void sumcheck_on_tables(hg_ctx* ctx, SumcheckIO& io) {
         dev::Powers pw;
         memset(&pw, 0, sizeof(pw));
         for (size_t i = 0; i < io.pw.size() && i < (size_t)dev::PW_MAX; i++) pw.v[i] = io.pw[i];
+        P.record_fork();   // the plan a prove builds: small grand-product rounds split, their sums on the side stream (one_stream: whole rounds)
         h = P.sc_stride(io.kind == 1 ? dev::SC_GRANDPROD : dev::SC_COLLATION, d, base, N, ntab, (int)io.nv, pw, ctx->d_res + evals);
         P.flush_stride();
     }
@@ -1702,6 +1708,7 @@ void sumcheck_on_tables(hg_ctx* ctx, SumcheckIO& io) {
         for (size_t i = 0; i < io.pw.size() && i < (size_t)dev::PW_MAX; i++) pw.v[i] = io.pw[i];
         P.defer_gp_unscale(evals, ntab / 2, pw);
     }
+    P.join_side_streams();
     P.finish();
     io.point = h.rs;
     io.evals.assign(ctx->h_res + evals, ctx->h_res + evals + ntab);
@@ -1732,8 +1739,10 @@ std::vector<uint8_t> grand_product_on_tables(hg_ctx* ctx, size_t nb, size_t len,
         for (size_t i = 0; i < len; i++) if (tables[b][i] >= GL_P) throw Error("hg_grand_product: non-canonical table entry");
         hip_check(hipMemcpyAsync(H + b * len, tables[b], len * 8, hipMemcpyHostToDevice, ctx->stream), "upload table");
     }
+    P.record_fork();   // as gkr() does ahead of the walk: the layers' small rounds are split as in a prove (one_stream: whole rounds)
     Prover::GpOut g = P.grand_product(H, len, (int)nb, std::vector<int>(nv, 0));
     P.flush_stride();
+    P.join_side_streams();
     P.finish();
     if (claims_out) *claims_out = *g.claims;
     if (point_out) {

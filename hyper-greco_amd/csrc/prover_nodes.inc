@@ -322,8 +322,11 @@
         }
         st = ctx->stream2; partials = ctx->d_partials2; ctx->prof_stream = st; forked = true;
     }
-    void join_nodes_stream() {
+    void join_sum_stream() {   // the split rounds' sums (flush_stride, mode 2) back into the main stream
         if (ctx->sum_pending) { hip_check(hipStreamWaitEvent(ctx->stream, ctx->ev_sum[1], 0), "split rounds: join wait"); ctx->sum_pending = false; }
+    }
+    void join_nodes_stream() {
+        join_sum_stream();
         if (nodes_on_col) { hip_check(hipEventRecord(ctx->ev_col, ctx->stream_col), "node reductions: done event"); col_pending = true; nodes_on_col = false; }
         if (col_pending) { hip_check(hipStreamWaitEvent(ctx->stream, ctx->ev_col, 0), "collation: join wait"); col_pending = false; }
         if (!forked) return;
@@ -383,6 +386,12 @@
             early_slot = slot(1);
             dev::set_e2(st, d_res() + early_slot, e2(1, 0));
         }
+        join_side_streams();
+    }
+    // The end of a forked walk: what the Lasso node left for the node reductions' stream (its openings), then every side stream
+    // joined to the main one. gkr() ends with it, and so do the kernel-level entries (prove_lasso_node, sumcheck_on_tables,
+    // grand_product_on_tables), which record the fork as gkr() does and so build the launch plan a prove builds.
+    void join_side_streams() {
         for (auto& f : late_aux) f();          // the Lasso node's openings (lasso_node)
         late_aux.clear();
         if (!late_col.empty()) {

@@ -212,6 +212,14 @@
                 if (!lc.items.empty()) plan.push_back(lc);
             }
         }
+        if (hg_debug("plan"))   // one line per launch, in launch order (read at every call: the tests switch it per case)
+            for (const Launch& L : plan) {
+                if (L.after_seq) { fprintf(stderr, "[hg plan] stride kind=%d after_seq=1\n", L.kind); continue; }
+                int lo = INT_MAX, hi = INT_MIN;
+                for (const dev::StItem& it : L.items) { const int v = L.tail ? it.nrounds : it.h_log2; lo = std::min(lo, v); hi = std::max(hi, v); }
+                fprintf(stderr, "[hg plan] stride kind=%d base=%d nrounds=%d mode=%d tail=%d hash=%d items=%zu %s=%d..%d\n", L.kind, L.base ? 1 : 0, L.nrounds,
+                        L.mode, L.tail ? 1 : 0, L.hash ? 1 : 0, L.items.size(), L.tail ? "rounds" : "h", lo, hi);
+            }
         dev::StJob* d_jobs = ctx->alloc_n<dev::StJob>(nj);
         upload(d_jobs, st_jobs.data(), (size_t)nj * sizeof(dev::StJob), "upload jobs");
         std::vector<dev::StItem> flat;
@@ -544,6 +552,21 @@
             }
         }
         for (int q = 0; q < nj; q++) jobs[q].tail_buf = cur_buf[q];
+        if (hg_debug("plan")) {   // one line per launch, in launch order, then the tail's
+            for (const PsLaunch& L : launches) {
+                int lo = INT_MAX, hi = INT_MIN;
+                std::string hs;
+                for (int q = 0; q < L.cnt; q++) {
+                    const dev::PsItem& it = all_items[L.off + q];
+                    lo = std::min(lo, it.rd); hi = std::max(hi, it.rd);
+                    hs += (q ? "," : "") + std::to_string(jobs[it.job].nvars - 1 - it.rd);
+                }
+                fprintf(stderr, "[hg plan] prodsum two=%d eq=%d cnt=%d rd=%d..%d h=[%s]\n", L.two ? 1 : 0, L.eq ? 1 : 0, L.cnt, lo, hi, hs.c_str());
+            }
+            int lo = INT_MAX, hi = INT_MIN;
+            for (auto& J : jobs) { lo = std::min(lo, J.tail_rd); hi = std::max(hi, J.tail_rd); }
+            fprintf(stderr, "[hg plan] prodsum tail jobs=%d tail_rd=%d..%d\n", nj, lo, hi);
+        }
         dev::PsJob* d_jobs = ctx->alloc_n<dev::PsJob>(nj);
         upload(d_jobs, jobs.data(), (size_t)nj * sizeof(dev::PsJob), "upload jobs");
         {   // A = sum_i kappa_i a_i of the eq-factored jobs with several tables

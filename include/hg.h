@@ -431,6 +431,9 @@ int hg_lasso_prove(hg_ctx* ctx, const hg_pk* pk, const uint64_t* lasso_in, uint8
                    uint64_t* claim_out);
 /* The same, entered inside a larger transcript: `chain_skip` E challenges have already been squeezed by the caller
  * (what a Rust `impl Node` shim passes: the position of its `&mut dyn TranscriptWrite` in the challenge chain). */
+/* Launch plan: the node runs as it does inside hg_prove - the fork recorded ahead of it, counters, grand product #2's tree and the
+ * openings on the side streams, the small grand-product rounds split, every side stream joined before the results are read. With
+ * hg_set_option(ctx, "one_stream", 1) it runs the unforked plan, every launch on the main stream. The bytes are the same. */
 int hg_lasso_prove_at(hg_ctx* ctx, const hg_pk* pk, const uint64_t* lasso_in, size_t chain_skip, uint8_t* proof, size_t cap,
                       size_t* len, uint64_t* claim_out);
 
@@ -442,7 +445,14 @@ int hg_lasso_num_challenges(const hg_pk* pk, size_t* n_e);
 /* = gkr::sum_check::prove_sum_check [REF call sites lasso.rs:278-279, prover.rs:242-252] on caller tables.
  *   kind: 0 collation g = p0*sum M^i p_i, 1 grand product g = p0*sum gam^i p_2i p_2i+1, 2 sum of pair products.
  *   tables[i]: host pointer, 2^nv u64 (is_base) or 2^nv (c0,c1) pairs. The challenge chain starts after
- *   `chain_skip` E challenges. Outputs: msgs nv*(d+1) E, point nv E, evals ntab E, sums nv*d E (raw per-round sums). */
+ *   `chain_skip` E challenges. Outputs: msgs nv*(d+1) E, point nv E, evals ntab E, sums nv*d E (raw per-round sums).
+ *   Refused with -1 (hg_last_error names hg_sumcheck), checked on the host before anything is launched: kind outside 0..2; an odd
+ *   ntab in kinds 1 and 2; npw < ntab (kind 0) or npw < ntab/2 (kind 1; kind 2 reads no powers); more tables than the kernels carry
+ *   powers or pairs for - ntab > 64 (kind 0), ntab/2 > 64 (kind 1), ntab/2 > 32 (kind 2); tables of mixed fields in kinds 0 and 1,
+ *   anything but (base, ext) pairs in kind 2; a table entry, power or claim coordinate >= p (values are canonical everywhere).
+ *   Launch plan: kinds 0 and 1 record the fork as hg_prove does, so a grand product's small rounds (half <= 2^14, behind the first
+ *   round) are split - folds on the main stream, their sums in one pass on a side stream that is joined before the results are
+ *   read. hg_set_option(ctx, "one_stream", 1) selects the unforked plan (whole rounds, one stream). HG_DEBUG=plan prints either. */
 int hg_sumcheck(hg_ctx* ctx, int kind, size_t nv, size_t ntab, const uint64_t* const* tables, const int* is_base,
                 const uint64_t* pw, size_t npw, const uint64_t* claim2, size_t chain_skip, uint64_t* msgs,
                 uint64_t* point, uint64_t* evals, uint64_t* sums);
@@ -450,7 +460,9 @@ int hg_sumcheck(hg_ctx* ctx, int kind, size_t nv, size_t ntab, const uint64_t* c
 /* = prove_grand_product [REF lasso/src/memory_checking/prover.rs:183-266] on nb host tables of len = 2^nv base-field values: product
  *   tree on the MSB split, root products, per layer the batched degree-3 sum-check, 2 nb evaluations and the mu fold. The transcript
  *   starts after `chain_skip` E challenges. claims2: nb final claims (E), point2: nv coordinates (E). (Goldilocks counterpart of
- *   hg_grand_product_bn254) */
+ *   hg_grand_product_bn254)
+ *   Launch plan: as in hg_prove - the fork is recorded ahead of the layers, whose small rounds are split (folds on the main stream,
+ *   sums on a side stream joined before the results are read); hg_set_option(ctx, "one_stream", 1): whole rounds on one stream. */
 int hg_grand_product(hg_ctx* ctx, size_t nb, size_t len, const uint64_t* const* tables, size_t chain_skip, uint8_t* proof, size_t cap,
                      size_t* proof_len, uint64_t* claims2, uint64_t* point2);
 /* = BoxMultilinearPoly::fix_var on the lowest variable (inside gkr::sum_check::prove_sum_check; SURVEY.md 8(c) convention C3):

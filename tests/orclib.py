@@ -45,6 +45,42 @@ def ptr(a):
     return a.ctypes.data_as(u64p)
 
 
+# ---- kernel-level sum-check helpers shared by test_gpu_parity.py and test_launch_plans.py ----------------------------------
+def rand_f(rng, n):
+    edge = [0, 1, P - 1, P - 2, 0xFFFFFFFF, 0x100000000, 0xFFFFFFFF00000000]
+    v = [rng.randrange(P) for _ in range(n)]
+    for i, e in enumerate(edge[:n]):
+        v[rng.randrange(n)] = e
+    return np.array(v, dtype=np.uint64)
+
+
+# Every entry an edge of the Goldilocks reductions, so that edge meets edge in the unfolded first round: small values, p - 1 (zero low
+# word), p - 2, the 2^32 boundary, the largest canonical value with all four 16-bit quarters set, 2^63, and the two halves of p.
+EDGE_POOL = [0, 1, 2, P - 1, P - 2, 0xFFFFFFFF, 0x100000000, 0x100000001, 0xFFFFFFFEFFFFFFFF, 1 << 63, (P - 1) // 2, (P + 1) // 2]
+
+
+def edge_f(rng, n):
+    return np.array(rng.choices(EDGE_POOL, k=n), dtype=np.uint64)
+
+
+def oracle_sumcheck(kind, tables, is_base, pw, claim, chain_skip=0, threads=4):
+    ntab = len(tables)
+    nv = int(np.log2(tables[0].size if is_base[0] else tables[0].size // 2))
+    d = 3 if kind == 1 else 2
+    tabs = [np.ascontiguousarray(t, dtype=np.uint64) for t in tables]
+    ptrs = (u64p * ntab)(*[ptr(t) for t in tabs])
+    flags = (C.c_int * ntab)(*[int(b) for b in is_base])
+    pw = np.ascontiguousarray(pw, dtype=np.uint64).reshape(-1)
+    claim = np.ascontiguousarray(claim, dtype=np.uint64)
+    msgs = np.zeros(nv * (d + 1) * 2, dtype=np.uint64)
+    point = np.zeros(nv * 2, dtype=np.uint64)
+    evals = np.zeros(ntab * 2, dtype=np.uint64)
+    sums = np.zeros(nv * d * 2, dtype=np.uint64)
+    lib().orc_sumcheck(kind, C.c_size_t(nv), C.c_size_t(ntab), ptrs, flags, ptr(pw), C.c_size_t(pw.size // 2), ptr(claim),
+                       C.c_size_t(chain_skip), threads, ptr(msgs), ptr(point), ptr(evals), ptr(sums))
+    return msgs, point, evals, sums
+
+
 def constants(n, k):
     return json.load(open(os.path.join(GOLDEN, "constants.json")))[f"{n}_{k}"]
 
@@ -265,6 +301,8 @@ def limbs_of(field):
 
 def to_limbs(vals, nl):
     """Python integers -> canonical little-endian u64 limbs (nl per element)."""
+    if nl == 1 and isinstance(vals, np.ndarray):   # (long Goldilocks tables: already in that form)
+        return np.ascontiguousarray(vals, dtype=np.uint64)
     a = np.zeros(len(vals) * nl, dtype=np.uint64)
     for i, v in enumerate(vals):
         for j in range(nl):

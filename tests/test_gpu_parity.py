@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import orclib
-from orclib import P, ptr
+from orclib import P, ptr, rand_f, oracle_sumcheck
 from hglib import hg
 
 pytestmark = pytest.mark.gpu
@@ -32,37 +32,14 @@ def _first_diff(a, b, nbytes=32):
     return "identical"
 
 
-def rand_f(rng, n):
-    edge = [0, 1, P - 1, P - 2, 0xFFFFFFFF, 0x100000000, 0xFFFFFFFF00000000]
-    v = [rng.randrange(P) for _ in range(n)]
-    for i, e in enumerate(edge[:n]):
-        v[rng.randrange(n)] = e
-    return np.array(v, dtype=np.uint64)
-
-
-def oracle_sumcheck(kind, tables, is_base, pw, claim, chain_skip=0, threads=4):
-    ntab = len(tables)
-    nv = int(np.log2(tables[0].size if is_base[0] else tables[0].size // 2))
-    d = 3 if kind == 1 else 2
-    tabs = [np.ascontiguousarray(t, dtype=np.uint64) for t in tables]
-    ptrs = (orclib.u64p * ntab)(*[ptr(t) for t in tabs])
-    flags = (C.c_int * ntab)(*[int(b) for b in is_base])
-    pw = np.ascontiguousarray(pw, dtype=np.uint64).reshape(-1)
-    claim = np.ascontiguousarray(claim, dtype=np.uint64)
-    msgs = np.zeros(nv * (d + 1) * 2, dtype=np.uint64)
-    point = np.zeros(nv * 2, dtype=np.uint64)
-    evals = np.zeros(ntab * 2, dtype=np.uint64)
-    sums = np.zeros(nv * d * 2, dtype=np.uint64)
-    OL.orc_sumcheck(kind, C.c_size_t(nv), C.c_size_t(ntab), ptrs, flags, ptr(pw), C.c_size_t(pw.size // 2), ptr(claim),
-                    C.c_size_t(chain_skip), threads, ptr(msgs), ptr(point), ptr(evals), ptr(sums))
-    return msgs, point, evals, sums
-
-
 @pytest.mark.parametrize("kind,ntab,nv,base", [
     (0, 6, 10, True), (0, 25, 12, True), (0, 3, 1, True), (0, 9, 7, False),
     (1, 12, 9, True), (1, 100, 11, True), (1, 4, 1, True), (1, 2, 14, True), (1, 8, 6, False),
     (2, 2, 11, None), (2, 10, 9, None), (2, 54, 8, None), (2, 2, 1, None),
-    # long tables: fused two-round grand-product launches (half >= 2^13), mixed-size launches, chunked last rounds
+    # long tables: a base-field or Ext2 first round at half = 2^14 / 2^15, then single rounds of Ext2 tables down to the tail (split on
+    # a forked context) and chunked last rounds; (2, 4, 14): one fused PRODSUM pair, then the tail. No fused two-round stride launch:
+    # those pairs are formed from half = 2^15 up behind the first round, which needs nv >= 17 - they, the mixed-size launches and the
+    # PRODSUM single rounds are in test_launch_plans.py
     (1, 6, 15, True), (1, 4, 16, True), (1, 4, 15, False), (0, 5, 15, True), (2, 4, 14, None),
 ])
 def test_sumcheck_kernels_bit_exact(ctx, kind, ntab, nv, base):
