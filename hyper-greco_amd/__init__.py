@@ -51,7 +51,7 @@ EXPORTS = [
     "hg_witness_get", "hg_witness_free", "hg_prove", "hg_warmup", "hg_prove_stream", "hg_encryption_layout", "hg_prove_encryptions", "hg_verify", "hg_verify_device", "hg_verify_device_mode", "hg_verify_device_batch",
     "hg_instance_from_ciphertext", "hg_instance_from_witness", "hg_instance_free", "hg_instance_coeffs", "hg_instance_get", "hg_pk_claim_shape", "hg_verify_public", "hg_verify_public_device", "hg_verify_public_batch", "hg_claims_settle", "hg_instance_mle", "hg_instance_mle_batch",
     "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_mle_eval",
-    "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_verify_public_bn254", "hg_verify_public_device_bn254", "hg_claims_settle_bn254", "hg_instance_mle_bn254", "hg_prove_encryptions_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
+    "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_verify_public_bn254", "hg_verify_public_device_bn254", "hg_verify_public_batch_bn254", "hg_claims_settle_bn254", "hg_instance_mle_bn254", "hg_instance_mle_batch_bn254", "hg_prove_encryptions_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
 ]
 
 
@@ -1128,6 +1128,53 @@ def verify_public_bn254(pk, instance, proof, ctx=None, device=False):
     if rc:
         return False, lib().hg_last_error().decode(), None
     return True, "", InputClaimsBn254(claims, n.value, points)
+
+
+def verify_public_batch_bn254(ctx, pk, instances, proofs, reason_cap=256):
+    """hg_verify_public_batch_bn254: BN254 proof i against instances[i], the run verified in device passes of a group of proofs each:
+    a list of (accepted, reason, InputClaimsBn254 or None), one per proof: what verify_public_bn254(pk, instances[i], proofs[i], ctx,
+    device=True) returns for that pair alone."""
+    L = lib()
+    L.hg_verify_public_batch_bn254.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t,
+                                               C.POINTER(C.c_int), C.c_void_p, C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]
+    n = len(proofs)
+    if len(instances) != n:
+        raise ValueError("verify_public_batch_bn254: one instance per proof")
+    nc, nco = pk_claim_shape(pk)
+    m, nc1, nco1 = max(n, 1), max(nc, 1), max(nco, 1)
+    hs = (C.c_void_p * m)(*[x.h.value for x in instances])
+    ps = (C.c_char_p * m)(*[bytes(p) for p in proofs])
+    lens = (C.c_size_t * m)(*[len(p) for p in proofs])
+    res = (C.c_int * m)()
+    claims = (HgInputClaimBn254 * (m * nc1))()
+    points = np.zeros(4 * m * nco1, dtype=np.uint64)
+    counts = (C.c_size_t * m)()
+    reasons = C.create_string_buffer(m * reason_cap)
+    rc = L.hg_verify_public_batch_bn254(ctx.h if ctx is not None else None, pk.h, hs, ps, lens, n, res, claims, nc1, _ptr(points), nco1, counts, reasons, reason_cap)
+    if rc < 0:
+        raise HgError(lib().hg_last_error().decode())
+    raw = reasons.raw
+    out = []
+    for i in range(n):
+        if res[i]:
+            out.append((False, raw[i * reason_cap:(i + 1) * reason_cap].split(b"\0", 1)[0].decode(), None))
+            continue
+        mine = (HgInputClaimBn254 * nc1)(*claims[i * nc1:(i + 1) * nc1])
+        out.append((True, "", InputClaimsBn254(mine, counts[i], points[4 * i * nco1:4 * (i + 1) * nco1].copy())))
+    return out
+
+
+def instance_mle_batch_bn254(ctx, instances, which, index, point):
+    """hg_instance_mle_batch_bn254: the MLE of ais[index] (which 0) or ct0is (which 1) of every instance at ONE Fr point (Python ints
+    below r), through the kernel of hg_verify_public_batch_bn254 as one work unit: a list of Python ints. Device only."""
+    pt = Context._fr_pack(point)
+    n = len(instances)
+    out = np.zeros(4 * max(n, 1), dtype=np.uint64)
+    hs = (C.c_void_p * max(n, 1))(*[x.h.value for x in instances])
+    L = lib()
+    L.hg_instance_mle_batch_bn254.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.c_int, C.c_int, u64p, C.c_size_t, u64p]
+    _check(L.hg_instance_mle_batch_bn254(ctx.h if ctx is not None else None, hs, n, which, index, _ptr(pt), len(point), _ptr(out)))
+    return Context._fr_unpack(out)[:n]
 
 
 def claims_settle_bn254(ctx, params, witness, claims):

@@ -12,6 +12,10 @@
 //      (verify_complete_bn254) on the host threads.
 // The public inputs are the same signed integers in the same layout as over Goldilocks: they are staged and copied by the code of
 // the Goldilocks batch (verifier_batch.hpp), so group g+1's copies and walks run while group g's kernels do.
+// hg_verify_public_batch_bn254 is the same pass from the ciphertext (the batch form of verify_public_device_bn254, bn254_verify.inc):
+// the walks run with public_only, the recording backend in its compact form, each proof's instance is staged as it is (2 k n signed
+// words), k_bn_vin_compact_dots evaluates ais and ct0is from them, and the claims on the secret inputs come back from each proof's
+// pending state.
 
 // ---- the MLE evaluations of the public inputs -------------------------------------------------------------------------------------
 // Work unit: one eq table and the P input tables evaluated at its point (mode 0: the group's tables of one input, so P is the group
@@ -25,7 +29,8 @@
 // 2^12 r^2. The reduction gives value R^-1 = sum z b~ R^-1 = sum z b (b~ = b R: the eq table is in Montgomery form): the PLAIN residue
 // of the thread's sum, so the partials and the slots are plain residues, canonical for the host without a conversion.
 constexpr int VBN_TPB = 256, VBN_ITEMS = 8, VBN_TILE = VBN_TPB * VBN_ITEMS, VBN_WAVES = VBN_TPB / 64;
-struct BnVinUnit { const Fr* eq; size_t n; int first, P, nblk, pad; size_t part0; };   // member p's partial of wave w of workgroup b: part0 + (p * nblk + b) * VBN_WAVES + w
+// (log2_n, lo: k_bn_vin_compact_dots only - n is then the count of non-padding words, blocks of 2^log2_n, word lo + r of a block's 2^(log2_n+1) eq entries)
+struct BnVinUnit { const Fr* eq; size_t n; int first, P, nblk; u32 log2_n; size_t part0; u32 lo, pad; };   // member p's partial of wave w of workgroup b: part0 + (p * nblk + b) * VBN_WAVES + w
 struct BnVinMember { const u64* a; int unit, slot; };
 struct BnVinBlock { int unit, blk; };
 
@@ -65,6 +70,59 @@ __global__ __launch_bounds__(VBN_TPB) void k_bn_vin_dots(const BnVinUnit* __rest
         for (int j = 0; j < VBN_ITEMS; j++) {
             const bool neg = v[j] >= (1ULL << 63);
             wcol_mac_u64(w, neg ? GL_P - v[j] : v[j], vd_negate_if(eq[j], neg));
+        }
+        Fr s = lz_canon(lz_reduce(w));
+        for (int o = 32; o > 0; o >>= 1) s = fr_add(s, vbn_shfl_xor(s, o));
+        if (lane == 0) partials[U.part0 + ((size_t)p * U.nblk + B.blk) * VBN_WAVES + wave] = s;   // (one partial per wave: no barrier)
+#pragma unroll
+        for (int j = 0; j < VBN_ITEMS; j++) v[j] = nx[j];
+    }
+}
+// k_bn_vin_dots over the compact signed coefficients of public instances (hg_verify_public_batch_bn254; k_bn_vdot_compact_jobs,
+// bn254_verify.inc, is the single-proof form and k_vin_compact_dots, verifier_batch.hip, the Goldilocks one). A unit is one eq table
+// (Fr, Montgomery form) and the P members' coefficient blocks evaluated at its point (mode 0: the group's tables of one public input,
+// so P is the group size). A workgroup owns VBN_TILE consecutive WORD indices t of the non-padding range only (U.n = blocks *
+// 2^log2_n of them): with b = t >> log2_n and r = t & (n-1), eq entry b * 2n + lo + r meets coefficient n-1-r of block b, exactly as
+// k_bn_vdot_compact_jobs indexes (ais[i]: one block, lo = 0; ct0is: k blocks, lo = n-1). Both addresses of an item come from one
+// (t, r) pair. The eq tile is loaded once into registers; per member the thread reads its VBN_ITEMS int64 words (descending over the
+// same cache lines as the eq loads ascend) and accumulates |z| times eq, or times r - eq for a negative z; a word beyond U.n counts
+// as zero. One lz_reduce / lz_canon per thread and member, one partial per (member, wave): no barrier, and the next member's loads
+// are issued ahead of this member's arithmetic, as in k_bn_vin_dots. k_bn_vin_reduce adds the partials: with b~ = b R the reduction
+// yields plain residues, so the slots are canonical for the host.
+// Bound: |z| <= (q_i-1)/2 < 2^61 (hg_instance_from_ciphertext checks the range), each product is below 2^61 r and a thread's
+// VBN_ITEMS = 8 of them below 2^64 r - far inside lz_reduce's 2^12 r^2.
+// HBM traffic by design: 8 B per coefficient plus 32 / P B of eq, nothing for padding words - the padding half of an eq table is
+// never read. Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): 248 VGPRs, no scratch, 2 waves per SIMD.
+__global__ __launch_bounds__(VBN_TPB) void k_bn_vin_compact_dots(const BnVinUnit* __restrict__ units, const BnVinMember* __restrict__ members,
+                                                                 const BnVinBlock* __restrict__ blocks, Fr* __restrict__ partials) {
+    const BnVinBlock B = blocks[blockIdx.x];
+    const BnVinUnit U = units[B.unit];
+    const size_t base = (size_t)B.blk * VBN_TILE + threadIdx.x, nm1 = ((size_t)1 << U.log2_n) - 1;
+    Fr eq[VBN_ITEMS];
+#pragma unroll
+    for (int j = 0; j < VBN_ITEMS; j++) {
+        const size_t t = base + (size_t)j * VBN_TPB, r = t & nm1;
+        eq[j] = t < U.n ? U.eq[2 * (t - r) + U.lo + r] : fr_zero();
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int64_t v[VBN_ITEMS];
+    auto load = [&](int p, int64_t* out) {
+        const int64_t* __restrict__ c = reinterpret_cast<const int64_t*>(members[U.first + p].a);
+#pragma unroll
+        for (int j = 0; j < VBN_ITEMS; j++) {
+            const size_t t = base + (size_t)j * VBN_TPB, r = t & nm1;
+            out[j] = t < U.n ? c[(t - r) + (nm1 - r)] : 0;
+        }
+    };
+    load(0, v);
+    for (int p = 0; p < U.P; p++) {
+        int64_t nx[VBN_ITEMS];
+        if (p + 1 < U.P) load(p + 1, nx);   // (the next member's loads are in flight under this member's arithmetic)
+        WCol w = wcol_zero();
+#pragma unroll
+        for (int j = 0; j < VBN_ITEMS; j++) {
+            const bool neg = v[j] < 0;
+            wcol_mac_u64(w, neg ? (u64)0 - (u64)v[j] : (u64)v[j], vd_negate_if(eq[j], neg));
         }
         Fr s = lz_canon(lz_reduce(w));
         for (int o = 32; o > 0; o >>= 1) s = fr_add(s, vbn_shfl_xor(s, o));
@@ -117,7 +175,11 @@ struct BnRecBackend : VerifyBackendT<Fr> {
     size_t u_at = 0;
     dev::ClaimSet cs;
 
-    BnRecBackend(const hg_pk* k) : pk(k), L(k->params) { memset(&cs, 0, sizeof(cs)); }
+    // hg_verify_public_batch_bn254 (the counterpart of BnDevBackend::cp): the public tables are compact signed coefficients, mle_input
+    // for inputs 3 .. 3+k-1 and mle_ct0is record compact input jobs, any other input is refused
+    const Params* cp = nullptr;
+
+    BnRecBackend(const hg_pk* k, bool compact = false) : pk(k), L(k->params), cp(compact ? &k->params : nullptr) { memset(&cs, 0, sizeof(cs)); }
     int slot() { return nslots++; }
     void reads_chain(const dev::ClaimSet& c, int nvars) {
         for (int a = 0; a < c.n; a++) chain_need = std::max(chain_need, c.point_off[a] + (size_t)nvars);
@@ -196,11 +258,23 @@ struct BnRecBackend : VerifyBackendT<Fr> {
         ins.push_back(In{k, eq_single(nvars, point_off), t});
         return t;
     }
+    int mle_compact(int k, int nblk, size_t point_off, int nvars) {
+        int lg = 0;
+        while ((1 << lg) < nblk) lg++;
+        if (nvars != cp->L + lg) throw Error("verifier: a point of the wrong length for a public table");   // (the job reads nblk * 2n eq entries)
+        const int t = slot();
+        ins.push_back(In{k, eq_single(nvars, point_off), t});
+        return t;
+    }
     int mle_input(size_t k, size_t point_off, int nvars) override {
+        if (cp) {
+            if (k < 3 || k >= 3 + (size_t)cp->k) throw Error("verifier: input " + std::to_string(k) + " is not a public table");
+            return mle_compact((int)k, 1, point_off, nvars);
+        }
         if (k >= 3 + 2 * L.K + 1) throw Error("verifier: no such input table");
         return mle_int((int)k, point_off, nvars);
     }
-    int mle_ct0is(size_t point_off, int nvars) override { return mle_int(-1, point_off, nvars); }
+    int mle_ct0is(size_t point_off, int nvars) override { return cp ? mle_compact(-1, cp->k, point_off, nvars) : mle_int(-1, point_off, nvars); }
     void finish() override { throw Error("verifier: a recording backend is finished by its batch"); }
     Fr value(int t) const override { return res[t]; }
 };
@@ -211,31 +285,45 @@ struct BnWalked {   // one proof of a group
     VerifyPendingT<Fr> pend;
     std::string error;                       // an hg::Error of the walk
     std::vector<int> gslot;                  // local slot -> the group's result slot
-    const u64* d_in = nullptr;               // its inputs in HBM: s, e, k1, ais, r1is, r2is, ct0is
+    const u64* d_in = nullptr;               // its inputs in HBM: s, e, k1, ais, r1is, r2is, ct0is; from the ciphertext: a, ct0
 };
 
-}  // namespace
+// kernels, descriptor copies and input copies may be queued on any way out (a rejection, an hg::Error): drain both streams before
+// the caller may reuse the arena and the staging or free a witness or an instance
+struct BnBatchDrain {
+    hipStream_t a, b;
+    ~BnBatchDrain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); }
+};
 
-void verify_batch_device_bn254(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Witness*>& ws, const std::vector<const uint8_t*>& proofs,
-                               const std::vector<size_t>& lens, std::vector<std::string>& why) {
-    static const char* WHO = "hg_verify_device_batch_bn254";
-    const size_t n = ws.size();
+// What a batch checks its proofs against: witness handles (hg_verify_device_batch_bn254: ws) or public instances
+// (hg_verify_public_batch_bn254: insts, and open[i] receives the claims an accepted proof i leaves on the secret inputs). `who`
+// prefixes the error messages.
+struct BnBatchSrc {
+    const char* who;
+    const std::vector<const Witness*>* ws;
+    const std::vector<const Instance*>* insts;
+    std::vector<std::vector<OpenClaimBn>>* open;
+};
+
+void verify_batch_run_bn254(hg_ctx* ctx, const hg_pk* pk, const BnBatchSrc& src, const std::vector<const uint8_t*>& proofs, const std::vector<size_t>& lens,
+                            std::vector<std::string>& why) {
+    const size_t n = proofs.size();
+    const bool pub = src.insts != nullptr;
+    const std::string who(src.who);
     why.assign(n, std::string());
+    if (pub) src.open->assign(n, std::vector<OpenClaimBn>());
     if (!n) return;
     const bool times = hg_times("verify");
     const double t0 = omp_get_wtime();
     hipc(hipSetDevice(ctx->device), "hipSetDevice");
     VerifyBatchBufs* B = batch_bufs(ctx);
-    // kernels, descriptor copies and input copies may be queued on any way out (a rejection, an hg::Error): drain both streams before
-    // the caller may reuse the arena and the staging or free a witness
-    struct Drain {
-        hipStream_t a, b;
-        ~Drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); }
-    } drain{ctx->stream, B->up};
-    hipc(hipStreamSynchronize(ctx->stream), "hg_verify_device_batch_bn254: synchronise");   // (the arena is reset below)
+    BnBatchDrain drain{ctx->stream, B->up};
+    hipc(hipStreamSynchronize(ctx->stream), (who + ": synchronise").c_str());   // (the arena is reset below)
     const Params& p = pk->params;
+    // one proof's inputs in HBM, in the order of verify_proof_device_bn254: s, e, k1, ais (k), r1is (k), r2is, then ct0is; from the
+    // ciphertext: its instance as it is, a then ct0, k n signed words each
     const BatchInputs L(p);
-    const size_t words = L.words, in_bytes = words * sizeof(u64);
+    const size_t kn = L.K * L.PZ, words = pub ? 2 * kn : L.words, in_bytes = words * sizeof(u64);
     size_t G = (size_t)std::max<int64_t>(0, ctx->verify_batch_group);
     if (!G) G = std::min(std::max<size_t>(1, VB_INPUT_BUDGET / in_bytes), VB_MAX_GROUP);
     const size_t ngroups = (n + G - 1) / G;
@@ -251,7 +339,10 @@ void verify_batch_device_bn254(hg_ctx* ctx, const hg_pk* pk, const std::vector<c
     };
 
     std::vector<std::vector<BnWalked>> groups(ngroups);
-    auto stage = [&](size_t g) { batch_stage_inputs(B, (int)(g & 1), ws, g * G, std::min(n, g * G + G), L, nthr, WHO); };
+    auto stage = [&](size_t g) {
+        if (pub) batch_stage_instances(B, (int)(g & 1), *src.insts, g * G, std::min(n, g * G + G), kn, nthr, src.who);
+        else batch_stage_inputs(B, (int)(g & 1), *src.ws, g * G, std::min(n, g * G + G), L, nthr, src.who);
+    };
     auto walk = [&](size_t g) {
         const size_t i0 = g * G, i1 = std::min(n, i0 + G);
         std::vector<BnWalked>& W = groups[g];
@@ -261,12 +352,12 @@ void verify_batch_device_bn254(hg_ctx* ctx, const hg_pk* pk, const std::vector<c
             BnWalked& x = W[q];
             x.idx = i0 + (size_t)q;
             try {
-                x.rec.reset(new BnRecBackend(pk));
-                x.pend = verify_walk_bn254(*x.rec, p, pk->lasso, pk->circuit, proofs[x.idx], lens[x.idx]);
+                x.rec.reset(new BnRecBackend(pk, pub));
+                x.pend = verify_walk_bn254(*x.rec, p, pk->lasso, pk->circuit, proofs[x.idx], lens[x.idx], pub);
             } catch (const std::exception& e) { x.error = e.what(); }
         }
         for (auto& x : W)
-            if (!x.error.empty()) throw Error(std::string(WHO) + ": proof " + std::to_string(x.idx) + ": " + x.error);
+            if (!x.error.empty()) throw Error(who + ": proof " + std::to_string(x.idx) + ": " + x.error);
     };
     // merge group g's jobs and enqueue them; returns the result slots used
     auto launch = [&](size_t g) -> size_t {
@@ -286,7 +377,7 @@ void verify_batch_device_bn254(hg_ctx* ctx, const hg_pk* pk, const std::vector<c
         std::vector<FftG> ffts;
         struct DotG { int kind, tab, eq, slot; };
         std::vector<DotG> dots;
-        struct InM { int eq; const u64* a; int slot; };
+        struct InM { int eq; const u64* a; int slot; int ct0; };   // (ct0: the public form's ct0is, k blocks at lo = n-1)
         std::vector<InM> ins;
         std::vector<Fr> us;   // canonical: k_bn_gather_B_jobs reads them as the prover's result slots
         std::map<Key, int> eq_ix, const_ix, lin_ix, fft_ix, dot_ix;
@@ -345,21 +436,22 @@ void verify_batch_device_bn254(hg_ctx* ctx, const hg_pk* pk, const std::vector<c
                 if (it == dot_ix.end()) { dots.push_back(DotG{d.kind, tab, geq[d.eq], new_slot()}); it = dot_ix.emplace(k, (int)dots.size() - 1).first; }
                 x.gslot[d.slot] = dots[it->second].slot;
             }
-            for (auto& in : R.ins) {   // (never shared: they read the proof's own witness)
+            for (auto& in : R.ins) {   // (never shared: they read the proof's own witness or instance)
                 const int sl = new_slot();
-                ins.push_back(InM{geq[in.eq], x.d_in + L.offset(in.k), sl});
+                if (pub) ins.push_back(InM{geq[in.eq], x.d_in + (in.k < 0 ? kn : (size_t)(in.k - 3) * L.PZ), sl, in.k < 0});
+                else ins.push_back(InM{geq[in.eq], x.d_in + L.offset(in.k), sl, 0});
                 x.gslot[in.slot] = sl;
             }
         }
         if ((size_t)nslot > res_cap_fr)
-            throw Error(std::string(WHO) + ": a group needs " + std::to_string(nslot) + " result slots, the context has " + std::to_string(res_cap_fr) +
+            throw Error(who + ": a group needs " + std::to_string(nslot) + " result slots, the context has " + std::to_string(res_cap_fr) +
                         ": lower verify_batch_group");
         // the chain the jobs read: uploaded with the descriptors, exactly as far as the furthest job of the group reads
         chain_upto(chain_need);
         for (auto& e : eqs) {   // (every job reads below chain_need by construction; checked here against what is uploaded)
             for (int a = 0; a < e.cs.n; a++)
-                if (e.cs.point_off[a] + (size_t)e.n > chm.size()) throw Error(std::string(WHO) + ": verifier: a job reads past the uploaded chain");
-            if (!e.cs.unit_alpha && e.cs.alpha_off + (size_t)e.cs.n > chm.size()) throw Error(std::string(WHO) + ": verifier: a job reads past the uploaded chain");
+                if (e.cs.point_off[a] + (size_t)e.n > chm.size()) throw Error(who + ": verifier: a job reads past the uploaded chain");
+            if (!e.cs.unit_alpha && e.cs.alpha_off + (size_t)e.cs.n > chm.size()) throw Error(who + ": verifier: a job reads past the uploaded chain");
         }
         Fr* res = reinterpret_cast<Fr*>(ctx->d_res);
         // device tables (arena) and host descriptors
@@ -469,22 +561,27 @@ void verify_batch_device_bn254(hg_ctx* ctx, const hg_pk* pk, const std::vector<c
         std::vector<BnVinMember> members;
         std::vector<BnVinBlock> blocks;
         {
-            std::vector<std::vector<const InM*>> by_eq(eqs.size());
-            for (auto& m : ins) by_eq[m.eq].push_back(&m);
+            // (an ais table and ct0is never share a unit, even at one point: their words sit at other places of the eq table)
+            std::vector<std::vector<const InM*>> by_eq(2 * eqs.size());
+            for (auto& m : ins) by_eq[2 * (size_t)m.eq + m.ct0].push_back(&m);
             size_t part = 0;
-            for (size_t e = 0; e < eqs.size(); e++) {
-                if (by_eq[e].empty()) continue;
+            for (size_t e2x = 0; e2x < by_eq.size(); e2x++) {
+                if (by_eq[e2x].empty()) continue;
+                const size_t e = e2x / 2;
                 BnVinUnit U;
                 memset(&U, 0, sizeof(U));
-                U.eq = eqs[e].out; U.n = (size_t)1 << eqs[e].n; U.first = (int)members.size(); U.P = (int)by_eq[e].size();
+                U.eq = eqs[e].out; U.n = (size_t)1 << eqs[e].n; U.first = (int)members.size(); U.P = (int)by_eq[e2x].size();
+                if (pub) {   // the non-padding words only: n of an ais table, k n of ct0is (the walk checked the eq table's size)
+                    U.n = e2x & 1 ? kn : L.PZ; U.log2_n = (u32)p.n_log2; U.lo = e2x & 1 ? (u32)(L.PZ - 1) : 0;
+                }
                 U.nblk = (int)((U.n + VBN_TILE - 1) / VBN_TILE); U.part0 = part;
                 part += (size_t)U.P * U.nblk * VBN_WAVES;
-                for (const InM* m : by_eq[e]) members.push_back(BnVinMember{m->a, (int)units.size(), m->slot});
+                for (const InM* m : by_eq[e2x]) members.push_back(BnVinMember{m->a, (int)units.size(), m->slot});
                 for (int b = 0; b < U.nblk; b++) blocks.push_back(BnVinBlock{(int)units.size(), b});
                 units.push_back(U);
             }
         }
-        size_t vin_parts = 0, vin_bytes = 0;   // (vin_bytes: what k_bn_vin_dots reads, eq tables and input tables)
+        size_t vin_parts = 0, vin_bytes = 0;   // (vin_bytes: what k_bn_vin_dots / k_bn_vin_compact_dots reads, eq tables and input tables)
         for (auto& U : units) { vin_parts += (size_t)U.P * U.nblk * VBN_WAVES; vin_bytes += U.n * (sizeof(Fr) + (size_t)U.P * sizeof(u64)); }
         // the chain, the phase-1 evaluations and every descriptor: one page-locked staging, one copy ahead of the launches
         size_t desc_bytes = 0;
@@ -505,7 +602,7 @@ void verify_batch_device_bn254(hg_ctx* ctx, const hg_pk* pk, const std::vector<c
         put(o_chain, chm); put(o_us, us); put(o_prep, preps); put(o_fill, fills); put(o_gt, gts); put(o_gb, gbs); put(o_part, fft_parts);
         put(o_claim, fft_claims); put(o_tab, fft_tabs); put(o_dot, vdots); put(o_bj, blk_job); put(o_unit, units); put(o_mem, members);
         put(o_blk, blocks);
-        if (desc_bytes) hipc(hipMemcpyAsync(d_desc, h, desc_bytes, hipMemcpyHostToDevice, st), "hg_verify_device_batch_bn254: upload descriptors");
+        if (desc_bytes) hipc(hipMemcpyAsync(d_desc, h, desc_bytes, hipMemcpyHostToDevice, st), (who + ": upload descriptors").c_str());
         // one launch per kind (launchers that index their jobs by gridDim.y: launches of at most VD_MAX_Y jobs)
         auto chunks = [](size_t njobs, auto fn) { for (size_t q0 = 0; q0 < njobs; q0 += VD_MAX_Y) fn(q0, (unsigned)std::min(VD_MAX_Y, njobs - q0)); };
         const auto* d_prep = reinterpret_cast<const VeqPrep*>(d_desc + o_prep);
@@ -550,15 +647,17 @@ void verify_batch_device_bn254(hg_ctx* ctx, const hg_pk* pk, const std::vector<c
             k_bn_vdot_reduce<<<(unsigned)vdots.size(), 256, 0, st>>>(d_dots, part);
         }
         if (!units.empty()) {
-            hipc(hipStreamWaitEvent(st, B->ev[s], 0), "hg_verify_device_batch_bn254: wait for the inputs");
+            hipc(hipStreamWaitEvent(st, B->ev[s], 0), (who + ": wait for the inputs").c_str());
             Fr* part = ctx->alloc_n<Fr>(vin_parts);
             const auto* d_units = reinterpret_cast<const BnVinUnit*>(d_desc + o_unit);
             const auto* d_mem = reinterpret_cast<const BnVinMember*>(d_desc + o_mem);
-            k_bn_vin_dots<<<(unsigned)blocks.size(), VBN_TPB, 0, st>>>(d_units, d_mem, reinterpret_cast<const BnVinBlock*>(d_desc + o_blk), part);
+            const auto* d_blk = reinterpret_cast<const BnVinBlock*>(d_desc + o_blk);
+            if (pub) k_bn_vin_compact_dots<<<(unsigned)blocks.size(), VBN_TPB, 0, st>>>(d_units, d_mem, d_blk, part);
+            else k_bn_vin_dots<<<(unsigned)blocks.size(), VBN_TPB, 0, st>>>(d_units, d_mem, d_blk, part);
             k_bn_vin_reduce<<<(unsigned)members.size(), 64, 0, st>>>(d_units, d_mem, part, res);
         }
         if (ctx->d_res != ctx->h_res && nslot)
-            hipc(hipMemcpyAsync(ctx->h_res, ctx->d_res, (size_t)nslot * sizeof(Fr), hipMemcpyDeviceToHost, st), "hg_verify_device_batch_bn254: copy results");
+            hipc(hipMemcpyAsync(ctx->h_res, ctx->d_res, (size_t)nslot * sizeof(Fr), hipMemcpyDeviceToHost, st), (who + ": copy results").c_str());
         if (times)
             fprintf(stderr, "[hg] verify_batch_bn254: group %zu (%zu proofs): %zu eq tables, %zu constant sums, %zu + %zu gathers, %zu DFT rows, %zu dots, %zu input evaluations in %zu units (%.1f MB); %d slots\n",
                     g, W.size(), eqs.size(), consts.size(), lins.size(), muls.size(), ffts.size(), dots.size(), members.size(), units.size(), vin_bytes / 1e6, nslot);
@@ -575,6 +674,8 @@ void verify_batch_device_bn254(hg_ctx* ctx, const hg_pk* pk, const std::vector<c
                 for (size_t t = 0; t < x.gslot.size(); t++) x.rec->res[t] = fr_to_mont(h_res[x.gslot[t]]);
             }
             why[x.idx] = verify_complete_bn254(x.pend);
+            if (pub && why[x.idx].empty())
+                for (const auto& cl : x.pend.open) (*src.open)[x.idx].push_back(open_claim_bn254(cl));
         }
         W.clear();
     };
@@ -586,12 +687,85 @@ void verify_batch_device_bn254(hg_ctx* ctx, const hg_pk* pk, const std::vector<c
         launch(g);
         if (g + 1 < ngroups) { const double tw = omp_get_wtime(); stage(g + 1); walk(g + 1); t_walk += omp_get_wtime() - tw; }
         const double ts = omp_get_wtime();
-        hipc(hipStreamSynchronize(ctx->stream), "hg_verify_device_batch_bn254: synchronise");
-        hipc(hipGetLastError(), "hg_verify_device_batch_bn254: kernels");
+        hipc(hipStreamSynchronize(ctx->stream), (who + ": synchronise").c_str());
+        hipc(hipGetLastError(), (who + ": kernels").c_str());
         t_sync += omp_get_wtime() - ts;
         complete(g);
     }
     if (times)
         fprintf(stderr, "[hg] verify_batch_bn254: %zu proofs in %zu groups of up to %zu: %.2f ms in all (staging and walks %.2f, waiting for the device %.2f)\n", n,
                 ngroups, G, (omp_get_wtime() - t0) * 1e3, t_walk * 1e3, t_sync * 1e3);
+}
+
+}  // namespace
+
+void verify_batch_device_bn254(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Witness*>& ws, const std::vector<const uint8_t*>& proofs,
+                               const std::vector<size_t>& lens, std::vector<std::string>& why) {
+    verify_batch_run_bn254(ctx, pk, BnBatchSrc{"hg_verify_device_batch_bn254", &ws, nullptr, nullptr}, proofs, lens, why);
+}
+
+void verify_public_batch_device_bn254(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Instance*>& insts, const std::vector<const uint8_t*>& proofs,
+                                      const std::vector<size_t>& lens, std::vector<std::string>& why, std::vector<std::vector<OpenClaimBn>>& open) {
+    verify_batch_run_bn254(ctx, pk, BnBatchSrc{"hg_verify_public_batch_bn254", nullptr, &insts, &open}, proofs, lens, why);
+}
+
+// one eq table over the caller's point, then k_bn_vin_compact_dots as ONE unit whose members are the instances' tables
+void instance_mle_batch_device_bn254(hg_ctx* ctx, const Params& p, const std::vector<const Instance*>& insts, int which, int index, const u64* point4,
+                                     size_t nvars, u64* out4) {
+    const size_t np = insts.size();
+    if (!np) return;
+    const char* who = "hg_instance_mle_batch_bn254";
+    hipc(hipSetDevice(ctx->device), "hipSetDevice");
+    VerifyBatchBufs* B = batch_bufs(ctx);
+    BnBatchDrain drain{ctx->stream, B->up};
+    hipc(hipStreamSynchronize(ctx->stream), "hg_instance_mle_batch_bn254: synchronise");   // (the arena is reset below)
+    ctx->arena_reset();
+    hipStream_t st = ctx->stream;
+    const size_t n = p.PZ(), kn = (size_t)p.k * n;
+    batch_stage_instances(B, 0, insts, 0, np, kn, std::max(1, hg_omp_threads()), who);
+    std::vector<Fr> chm(nvars);   // (the point is the whole chain, in Montgomery form)
+    for (size_t j = 0; j < nvars; j++) chm[j] = fr_from_limbs_mont(point4 + 4 * j);
+    const int nv = (int)nvars;
+    Fr* eq = ctx->alloc_n<Fr>((size_t)1 << nv);
+    Fr* ab = ctx->alloc_n<Fr>(veq_stride(nv));
+    VeqPrep P;
+    memset(&P, 0, sizeof(P));
+    P.ab = ab; P.n = nv; P.unit = 1;
+    const VeqFill F{eq, ab, nv, 1};
+    BnVinUnit U;
+    memset(&U, 0, sizeof(U));
+    U.eq = eq; U.n = which ? kn : n; U.P = (int)np; U.nblk = (int)((U.n + VBN_TILE - 1) / VBN_TILE);
+    U.log2_n = (u32)p.n_log2; U.lo = which ? (u32)(n - 1) : 0;
+    std::vector<BnVinMember> members(np);
+    for (size_t i = 0; i < np; i++) members[i] = BnVinMember{B->d_in[0] + i * 2 * kn + (which ? kn : (size_t)index * n), 0, (int)i};
+    std::vector<BnVinBlock> blocks((size_t)U.nblk);
+    for (int b = 0; b < U.nblk; b++) blocks[b] = BnVinBlock{0, b};
+    size_t desc_bytes = 0;
+    auto place = [&](size_t bytes) { const size_t o = desc_bytes; desc_bytes += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_chain = place(std::max<size_t>(nvars, 1) * sizeof(Fr)), o_prep = place(sizeof(P)), o_fill = place(sizeof(F)), o_unit = place(sizeof(U)),
+                 o_mem = place(np * sizeof(BnVinMember)), o_blk = place(blocks.size() * sizeof(BnVinBlock));
+    char* d_desc = static_cast<char*>(ctx->alloc(desc_bytes));
+    char* h = batch_desc_host(B, desc_bytes);
+    if (nvars) memcpy(h + o_chain, chm.data(), nvars * sizeof(Fr));
+    memcpy(h + o_prep, &P, sizeof(P));
+    memcpy(h + o_fill, &F, sizeof(F));
+    memcpy(h + o_unit, &U, sizeof(U));
+    memcpy(h + o_mem, members.data(), np * sizeof(BnVinMember));
+    memcpy(h + o_blk, blocks.data(), blocks.size() * sizeof(BnVinBlock));
+    hipc(hipMemcpyAsync(d_desc, h, desc_bytes, hipMemcpyHostToDevice, st), "hg_instance_mle_batch_bn254: upload descriptors");
+    const size_t high = (size_t)1 << (nv > 8 ? nv - 8 : 0);
+    k_bn_veq_prep<<<dim3(1 + (unsigned)((high + 255) / 256), 1), 256, 0, st>>>(reinterpret_cast<const VeqPrep*>(d_desc + o_prep),
+                                                                              reinterpret_cast<const Fr*>(d_desc + o_chain));
+    k_bn_veq_fill<<<dim3((unsigned)std::min<size_t>((((size_t)1 << nv) + 255) / 256, 1024), 1), 256, 0, st>>>(reinterpret_cast<const VeqFill*>(d_desc + o_fill));
+    hipc(hipStreamWaitEvent(st, B->ev[0], 0), "hg_instance_mle_batch_bn254: wait for the instances");
+    Fr* res = ctx->alloc_n<Fr>(np);
+    Fr* part = ctx->alloc_n<Fr>(np * (size_t)U.nblk * VBN_WAVES);
+    const auto* d_units = reinterpret_cast<const BnVinUnit*>(d_desc + o_unit);
+    const auto* d_mem = reinterpret_cast<const BnVinMember*>(d_desc + o_mem);
+    k_bn_vin_compact_dots<<<(unsigned)blocks.size(), VBN_TPB, 0, st>>>(d_units, d_mem, reinterpret_cast<const BnVinBlock*>(d_desc + o_blk), part);
+    k_bn_vin_reduce<<<(unsigned)np, 64, 0, st>>>(d_units, d_mem, part, res);
+    static_assert(sizeof(Fr) == 4 * sizeof(u64), "an Fr result slot is 4 limbs");
+    hipc(hipMemcpyAsync(out4, res, np * sizeof(Fr), hipMemcpyDeviceToHost, st), "hg_instance_mle_batch_bn254: copy results");
+    hipc(hipStreamSynchronize(st), "hg_instance_mle_batch_bn254: synchronise");
+    hipc(hipGetLastError(), "hg_instance_mle_batch_bn254: kernels");
 }

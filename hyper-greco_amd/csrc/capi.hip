@@ -1374,6 +1374,68 @@ int hg_verify_public_device_bn254(hg_ctx* ctx, const hg_pk* pk, const void* inst
     HG_CATCH(-1)
 }
 
+int hg_verify_public_batch_bn254(hg_ctx* ctx, const hg_pk* pk, const void* const* instances, const uint8_t* const* proofs, const size_t* lens, size_t n,
+                                 int* results, void* claims, size_t claim_cap_each, uint64_t* points4, size_t coord_cap_each, size_t* n_claims, char* reasons,
+                                 size_t reason_cap) {
+    HG_TRY
+    const std::string who = "hg_verify_public_batch_bn254";
+    if (!ctx || !pk || !pk->ctx) throw Error(who + ": needs a device context and a device prover key");
+    if (n && (!instances || !proofs || !lens || !results || !n_claims)) throw Error(who + ": null argument");
+    size_t need_claims = 0, need_coords = 0;
+    claim_shape(pk->params, pk->lasso, pk->circuit, &need_claims, &need_coords);
+    if (n && (claim_cap_each < need_claims || coord_cap_each < need_coords || (need_claims && !claims) || (need_coords && !points4)))
+        throw Error(who + ": room for " + std::to_string(need_claims) + " claims and " + std::to_string(need_coords) + " coordinates per proof is needed (hg_pk_claim_shape)");
+    std::vector<const Instance*> I(n);
+    std::vector<const uint8_t*> P(n);
+    std::vector<size_t> N(n);
+    for (size_t i = 0; i < n; i++) {
+        if (!instances[i] || !proofs[i]) throw Error(who + ": null instance or proof at index " + std::to_string(i));
+        check_instance(pk, as_instance(instances[i]), (who + ": index " + std::to_string(i)).c_str());
+        I[i] = &as_instance(instances[i])->inst; P[i] = proofs[i]; N[i] = lens[i];
+    }
+    if (!n) return 0;
+    std::vector<std::string> why;
+    std::vector<std::vector<OpenClaimBn>> open;
+    try {
+        hg::bn::verify_public_batch_device_bn254(ctx, pk, I, P, N, why, open);
+    } catch (const std::exception& e) {
+        const std::string m = e.what();
+        throw Error(m.rfind(who, 0) == 0 ? m : who + ": " + m);
+    }
+    for (size_t i = 0; i < n; i++) {   // (checked before anything is written: an error of the call leaves the outputs alone)
+        size_t coords = 0;
+        for (const OpenClaimBn& c : open[i]) coords += c.point4.size() / 4;
+        if (open[i].size() > claim_cap_each || coords > coord_cap_each) throw Error(who + ": proof " + std::to_string(i) + ": the walk left more claims than hg_pk_claim_shape counts");
+    }
+    int rejected = 0;
+    for (size_t i = 0; i < n; i++) {
+        results[i] = why[i].empty() ? 0 : 1;
+        rejected += results[i];
+        if (reasons && reason_cap) {
+            char* r = reasons + i * reason_cap;
+            const size_t m = std::min(why[i].size(), reason_cap - 1);
+            memcpy(r, why[i].data(), m);
+            r[m] = 0;
+        }
+        n_claims[i] = results[i] ? 0 : open[i].size();
+        if (results[i]) continue;
+        hg_input_claim_bn254* out = static_cast<hg_input_claim_bn254*>(claims) + i * claim_cap_each;
+        uint64_t* pts = points4 + 4 * i * coord_cap_each;
+        size_t off = 0;
+        for (size_t j = 0; j < open[i].size(); j++) {
+            const OpenClaimBn& c = open[i][j];
+            out[j].input = (uint32_t)c.input;
+            out[j].nvars = (uint32_t)(c.point4.size() / 4);
+            out[j].point_off = off;
+            memcpy(out[j].value, c.value, 32);
+            if (!c.point4.empty()) memcpy(pts + 4 * off, c.point4.data(), c.point4.size() * 8);
+            off += out[j].nvars;
+        }
+    }
+    return rejected;
+    HG_CATCH(-1)
+}
+
 int hg_claims_settle_bn254(hg_ctx* ctx, const hg_params* params, const hg_witness* w, const void* claims, size_t n, const uint64_t* points4) {
     HG_TRY
     if (!params || !w || (n && (!claims || !points4))) throw Error("hg_claims_settle_bn254: null argument");
@@ -1413,6 +1475,34 @@ int hg_instance_mle_bn254(hg_ctx* ctx, const void* instance, int which, int inde
         if (!bn254_canonical(point4 + 4 * i)) throw Error("hg_instance_mle_bn254: non-canonical coordinate");
     if (ctx) hg::bn::instance_mle_device_bn254(ctx, p, in->inst, which, index, point4, nvars, out4);
     else instance_mle_bn254(p, in->inst, which, index, point4, nvars, out4);
+    return 0;
+    HG_CATCH(-1)
+}
+
+int hg_instance_mle_batch_bn254(hg_ctx* ctx, const void* const* instances, size_t n, int which, int index, const uint64_t* point4, size_t nvars, uint64_t* out4) {
+    HG_TRY
+    if (!ctx) throw Error("hg_instance_mle_batch_bn254: needs a device context");
+    if (!instances || (nvars && !point4) || !out4) throw Error("hg_instance_mle_batch_bn254: null argument");
+    if (!n) return 0;
+    std::vector<const Instance*> I(n);
+    for (size_t i = 0; i < n; i++) {
+        if (!instances[i]) throw Error("hg_instance_mle_batch_bn254: null instance at index " + std::to_string(i));
+        const hg_params &a = as_instance(instances[0])->params, &b = as_instance(instances[i])->params;
+        if (a.n != b.n || a.k != b.k || memcmp(a.qis, b.qis, sizeof(a.qis[0]) * a.k) != 0)
+            throw Error("hg_instance_mle_batch_bn254: the instance at index " + std::to_string(i) + " was built for other parameters than the first");
+        I[i] = &as_instance(instances[i])->inst;
+    }
+    Params p(as_instance(instances[0])->params);
+    if (which != 0 && which != 1) throw Error("hg_instance_mle_batch_bn254: which is 0 (ais[index]) or 1 (ct0is)");
+    if (which == 0 && (index < 0 || index >= p.k)) throw Error("hg_instance_mle_batch_bn254: no such modulus");
+    if (nvars != (size_t)(which ? p.ct0is_log2() : p.L)) throw Error("hg_instance_mle_batch_bn254: the table has " + std::to_string(which ? p.ct0is_log2() : p.L) + " variables");
+    for (const Instance* x : I)
+        if (x->a.size() != (size_t)p.k * p.PZ() || x->ct0.size() != (size_t)p.k * p.PZ()) throw Error("hg_instance_mle_batch_bn254: an instance of the wrong size");
+    for (size_t i = 0; i < nvars; i++)
+        if (!bn254_canonical(point4 + 4 * i)) throw Error("hg_instance_mle_batch_bn254: non-canonical coordinate");
+    std::vector<u64> res(4 * n);   // (an error of the device pass leaves out4 alone)
+    hg::bn::instance_mle_batch_device_bn254(ctx, p, I, which, index, point4, nvars, res.data());
+    memcpy(out4, res.data(), res.size() * sizeof(u64));
     return 0;
     HG_CATCH(-1)
 }

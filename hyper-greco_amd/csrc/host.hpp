@@ -281,6 +281,14 @@ void instance_mle_device_bn254(hg_ctx* ctx, const Params& p, const Instance& ins
 // inside one proof's walk names its index.
 void verify_batch_device_bn254(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Witness*>& ws, const std::vector<const uint8_t*>& proofs,
                                const std::vector<size_t>& lens, std::vector<std::string>& why);
+// hg_verify_public_batch_bn254: the same pass from the ciphertext - proof i against insts[i], why[i] as above and open[i] = the claims
+// an accepted proof leaves on the secret inputs (what verify_public_device_bn254 hands back for that pair)
+void verify_public_batch_device_bn254(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Instance*>& insts, const std::vector<const uint8_t*>& proofs,
+                                      const std::vector<size_t>& lens, std::vector<std::string>& why, std::vector<std::vector<OpenClaimBn>>& open);
+// hg_instance_mle_batch_bn254: one public table (which / index as instance_mle_device_bn254) of every instance at one point, through
+// the batch's kernel as ONE unit with insts.size() members; out4: 4 canonical limbs per instance
+void instance_mle_batch_device_bn254(hg_ctx* ctx, const Params& p, const std::vector<const Instance*>& insts, int which, int index, const u64* point4,
+                                     size_t nvars, u64* out4);
 }
 void ntt_host(u64* a, int log2n, bool inverse);  // in place, natural order
 u64 root_of_unity(int log2n);                    // 2^log2n-th root from ROOT_OF_UNITY = 7^((p-1)/2^32)

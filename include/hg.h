@@ -76,8 +76,8 @@ void hg_destroy(hg_ctx* ctx);
  *                 values object the third is captured into a hipGraph and later ones replay it - the launch sequence depends on
  *                 addresses only, because every challenge is known up front; a values object refilled by hg_witness_gen_into
  *                 keeps its graph; up to HG_GRAPH_ENTRIES (8) graphs per context, each with a private workspace)
- *   "verify_batch_group"  the most proofs one device pass of hg_verify_device_batch, hg_verify_device_batch_bn254 or
- *                 hg_verify_public_batch holds
+ *   "verify_batch_group"  the most proofs one device pass of hg_verify_device_batch, hg_verify_device_batch_bn254,
+ *                 hg_verify_public_batch or hg_verify_public_batch_bn254 holds
  *                 (default 0: sized from the memory budget, at most 64)
  * Returns 0, or -1 for an unknown name. */
 int hg_set_option(hg_ctx* ctx, const char* name, int64_t value);
@@ -551,7 +551,7 @@ int hg_verify_device_batch_bn254(hg_ctx* ctx, const hg_pk* pk, const hg_witness*
  * entry takes a mode. An element crosses the ABI as 4 canonical little-endian u64 limbs. The instance is the field-independent
  * hg_instance* of hg_instance_from_ciphertext / hg_instance_from_witness, the claim counts are hg_pk_claim_shape's; instance and
  * claim array (hg_input_claim_bn254*) cross as void pointers. hg_verify_public_bn254 followed by hg_claims_settle_bn254 decides
- * what hg_verify_bn254 decides. One proof per call; there is no batched form. */
+ * what hg_verify_bn254 decides. One proof per call; hg_verify_public_batch_bn254 (below) verifies a run of them in one device pass. */
 typedef struct hg_input_claim_bn254 {
     uint32_t input;      /* as hg_input_claim: 0 s, 1 e, 2 k1, 3+k+i r1is[i], 3+2k r2is (never 3..3+k-1) */
     uint32_t nvars;
@@ -587,6 +587,32 @@ int hg_claims_settle_bn254(hg_ctx* ctx, const hg_params* params, const hg_witnes
  * table (L + log2 k vars, index ignored). out4: canonical limbs. -1 for a null argument, another selector or modulus, nvars that is
  * not the table's, a coordinate that is not below r. */
 int hg_instance_mle_bn254(hg_ctx* ctx, const void* instance, int which, int index, const uint64_t* point4, size_t nvars, uint64_t out4[4]);
+
+/* hg_verify_public_device_bn254 for a run of n proofs under one key: the contract of hg_verify_public_batch without a mode (BN254 is
+ *   mode 0 only), with the element conventions of hg_verify_public_device_bn254. Proof i (proofs[i], lens[i]) is checked against
+ *   instances[i] (an hg_instance* of the key's parameters). Device only. results[i] = 0 accepted / 1 rejected, exactly the decision
+ *   hg_verify_public_device_bn254 makes for that pair alone; reasons (may be NULL): at reasons + i*reason_cap the text that call leaves
+ *   in hg_last_error, NUL-terminated and truncated to reason_cap bytes ("" when accepted). An accepted proof i writes its claims at
+ *   (hg_input_claim_bn254*)claims + i*claim_cap_each and its points at points4 + 4*i*coord_cap_each, point_off relative to that
+ *   proof's own block, and n_claims[i] = the claim count: claim order, values and points are bit for bit those of the single call. A
+ *   rejected proof gets n_claims[i] = 0. Returns the number of rejected proofs (>= 0); n == 0 returns 0 and writes nothing; -1 on an
+ *   error of the call, which writes no output either (hg_last_error begins with the function's name and gives "index i" where an
+ *   element is at fault): no context, a host-only key, a null argument or a null element, claim_cap_each or coord_cap_each below
+ *   hg_pk_claim_shape, an instance of other parameters.
+ *   The pass is hg_verify_device_batch_bn254's - walks on the host threads, a group of proofs (context option "verify_batch_group",
+ *   at most 64) in one launch per kind, key-only tables built once per group, the next group's copies under this group's kernels -
+ *   with each proof's instance staged as it is (2 k n signed words: 8.4 MB at n=32768 k=16 against 30.9 MB of witness tables) and
+ *   ais / ct0is evaluated from them by one kernel over Fr per group that reads the non-padding half of each eq table once for all
+ *   the group's members; the secret inputs launch nothing. */
+int hg_verify_public_batch_bn254(hg_ctx* ctx, const hg_pk* pk, const void* const* instances, const uint8_t* const* proofs,
+                                 const size_t* lens, size_t n, int* results, void* claims, size_t claim_cap_each,
+                                 uint64_t* points4, size_t coord_cap_each, size_t* n_claims, char* reasons, size_t reason_cap);
+/* hg_instance_mle_bn254 for the kernel of hg_verify_public_batch_bn254: the table (which / index as above) of n instances of one
+ * parameter set at ONE shared point of 4-limb coordinates below r, as one work unit of that kernel with n members; out4 receives 4
+ * canonical limbs per instance. Device only. Returns 0, or -1 for a null argument or element, no context, instances of mixed
+ * parameters, another selector or modulus, nvars that is not the table's, a coordinate that is not below r. */
+int hg_instance_mle_batch_bn254(hg_ctx* ctx, const void* const* instances, size_t n, int which, int index,
+                                const uint64_t* point4, size_t nvars, uint64_t* out4);
 
 /* hg_witness_derive and hg_prove_bn254 for a run of n_enc ENCRYPTIONS under one key, pipelined: hg_prove_encryptions over bn256::Fr
  *   [REF scripts/circuit_sk.py:18-140 followed by sk_encryption_circuit.rs:417-460, 614-626; the loop a proving service writes around

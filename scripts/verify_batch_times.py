@@ -10,6 +10,8 @@ next to it the median of --reps one-by-one passes over the same B proofs divided
            warm-up call of each: (a) the batch from the ciphertext, (b) the same pairs through hg_verify_public_device one by one,
            (c) hg_verify_device_batch on the same proofs with the witness handles. Medians and ranges of --reps runs, a/b, and
            whether the whole range of (a) lies below the whole range of (b). With --trace: one public batch of 16 in mode 3.
+           With --field bn254: (a) hg_verify_public_batch_bn254, (b) hg_verify_public_device_bn254 one by one, (c)
+           hg_verify_device_batch_bn254 on the witnesses of the same pairs (mode 0 only; --trace: one public batch of 16).
 Usage: verify_batch_times.py [n k] [--field goldilocks|bn254] [--public] [--modes 0,3] [--batch 1,4,16,64] [--reps 5] [--trace]"""
 import argparse
 import os
@@ -41,8 +43,6 @@ def main():
     ap.add_argument("--field", choices=("goldilocks", "bn254"), default="goldilocks")
     ap.add_argument("--public", action="store_true")
     a = ap.parse_args()
-    if a.public and a.field == "bn254":
-        ap.error("--public is Goldilocks only")
     bn = a.field == "bn254"
     if bn:
         a.modes = "0"
@@ -55,6 +55,14 @@ def main():
 
     def verify_one(w, p, mode):
         return hg.verify_device_bn254(ctx, pk, w, p) if bn else hg.verify_device(ctx, pk, w, p, mode=mode)
+
+    def public_batch(I, P, mode):
+        return hg.verify_public_batch_bn254(ctx, pk, I, P) if bn else hg.verify_public_batch(ctx, pk, I, P, mode)
+
+    def public_one(inst, p, mode):
+        return hg.verify_public_bn254(pk, inst, p, ctx=ctx, device=True) if bn else hg.verify_public(pk, inst, p, mode, ctx=ctx, device=True)
+    names = (("hg_verify_public_batch_bn254", "hg_verify_public_device_bn254", "hg_verify_device_batch_bn254") if bn else
+             ("hg_verify_public_batch", "hg_verify_public_device", "hg_verify_device_batch"))
     ctx = hg.Context(0)
     bfv = hg.BfvEncrypt.new(a.n, a.k)
     pk = bfv.setup(ctx)
@@ -66,28 +74,28 @@ def main():
         mode = 0 if bn else 3
         ps = [prove(w, mode) for w in ws]
         time.sleep(3.0)   # (longer than any idle stretch of setup, witness generation and prove)
-        got = hg.verify_public_batch(ctx, pk, insts, ps, mode) if a.public else verify_batch(ws, ps, mode)
+        got = public_batch(insts, ps, mode) if a.public else verify_batch(ws, ps, mode)
         assert all(g[0] for g in got), got
         print("n=%d k=%d %s: one mode-%d %sbatch of %d proofs of %d bytes" % (a.n, a.k, a.field, mode, "public " if a.public else "", len(ps), len(ps[0])))
     elif a.public:
-        print("n=%d k=%d, %d distinct witnesses, per proof, one process; %d alternating runs of (a) hg_verify_public_batch, (b) hg_verify_public_device one "
-              "by one, (c) hg_verify_device_batch, after a warm-up call of each: median [min .. max]" % (a.n, a.k, nw, a.reps))
+        print("n=%d k=%d, %d distinct witnesses, per proof, one process; %d alternating runs of (a) %s, (b) %s one "
+              "by one, (c) %s, after a warm-up call of each: median [min .. max]" % ((a.n, a.k, nw, a.reps) + names))
         for mode in [int(m) for m in a.modes.split(",")]:
             ps = [prove(w, mode) for w in ws]
             for B in batches:
                 W, I, P = ([x[i % nw] for i in range(B)] for x in (ws, insts, ps))
 
                 def leg_a():
-                    got = hg.verify_public_batch(ctx, pk, I, P, mode)
+                    got = public_batch(I, P, mode)
                     assert all(ok for ok, _, _ in got), got
 
                 def leg_b():
                     for inst, p in zip(I, P):
-                        ok, why, _ = hg.verify_public(pk, inst, p, mode, ctx=ctx, device=True)
+                        ok, why, _ = public_one(inst, p, mode)
                         assert ok, why
 
                 def leg_c():
-                    got = hg.verify_device_batch(ctx, pk, W, P, mode=mode)
+                    got = verify_batch(W, P, mode)
                     assert all(ok for ok, _ in got), got
                 legs = (leg_a, leg_b, leg_c)
                 for f in legs:
@@ -103,9 +111,9 @@ def main():
                 sys.stdout.flush()
             os.environ["HG_TIMES"] = "verify"
             Bm = max(batches)
-            print("mode %d, B=%d with HG_TIMES=verify: the public batch, then hg_verify_device_batch" % (mode, Bm), file=sys.stderr)
-            hg.verify_public_batch(ctx, pk, [insts[i % nw] for i in range(Bm)], [ps[i % nw] for i in range(Bm)], mode)
-            hg.verify_device_batch(ctx, pk, [ws[i % nw] for i in range(Bm)], [ps[i % nw] for i in range(Bm)], mode=mode)
+            print("mode %d, B=%d with HG_TIMES=verify: the public batch, then %s" % (mode, Bm, names[2]), file=sys.stderr)
+            public_batch([insts[i % nw] for i in range(Bm)], [ps[i % nw] for i in range(Bm)], mode)
+            verify_batch([ws[i % nw] for i in range(Bm)], [ps[i % nw] for i in range(Bm)], mode)
             del os.environ["HG_TIMES"]
     else:
         print("n=%d k=%d %s, %d distinct witnesses, median of %d after a warm-up, per proof, one process" % (a.n, a.k, a.field, nw, a.reps))
