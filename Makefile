@@ -5,6 +5,8 @@
 #                 verifier tests against it                                       -> profiles/r06_asan_tests.txt
 #   make fuzz     libFuzzer runs (FUZZ_SECONDS each, default 600) of tests/fuzz/fuzz_host.cpp over the JSON witness loaders and both host
 #                 verifiers, against the sanitized library                        -> profiles/r06_fuzz_*.txt
+#   make fuzz-pcs libFuzzer runs (FUZZ_SECONDS each) of tests/fuzz/fuzz_pcs.cpp over hg_pcs_verify and hg_claims_verify, against the
+#                 sanitized library; the driver writes its own seeds              -> build/fuzz/pcs*.log, build/fuzz/claims.log
 ROOT := $(abspath .)
 CLANG := /opt/rocm/lib/llvm/bin/clang++
 ASAN_RT := $(shell $(CLANG) --print-file-name=libclang_rt.asan-x86_64.so)
@@ -43,7 +45,21 @@ fuzz: build/fuzz/fuzz_host
 	  ( echo "# make fuzz: HG_FUZZ_TARGET=$$t, $(FUZZ_SECONDS) s of libFuzzer (address + undefined-behaviour sanitizers) on tests/fuzz/fuzz_host.cpp"; grep -E "^#[0-9]+.*(INITED|DONE)|stat::|ERROR|SUMMARY|exit code" build/fuzz/$$t.log ) > profiles/r06_fuzz_$$t.txt; \
 	done; cat profiles/r06_fuzz_*.txt
 
+# (the program links the sanitizer's runtime itself; libstdc++ precedes it in the library list, hence verify_asan_link_order=0 as in `fuzz`)
+build/fuzz/fuzz_pcs: tests/fuzz/fuzz_pcs.cpp build/asan/libhypergreco.so
+	mkdir -p build/fuzz
+	$(CLANG) -O1 -g -std=c++17 -fsanitize=fuzzer,address,undefined -mllvm -asan-globals=0 -shared-libsan tests/fuzz/fuzz_pcs.cpp -o $@ -Lbuild/asan -lhypergreco -Wl,-rpath,$(ROOT)/build/asan -Wl,-rpath,$(dir $(ASAN_RT))
+
+fuzz-pcs: build/fuzz/fuzz_pcs
+	for t in pcs pcsargs claims; do \
+	  mkdir -p build/fuzz/$$t; \
+	  HG_FUZZ_TARGET=$$t HG_FUZZ_ROOT=$(ROOT) HG_FUZZ_SEEDS=build/fuzz/$$t ASAN_OPTIONS=detect_leaks=0:verify_asan_link_order=0:detect_odr_violation=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 ./build/fuzz/fuzz_pcs build/fuzz/$$t -max_len=65536 -rss_limit_mb=6000 -timeout=60 \
+	    -max_total_time=$(FUZZ_SECONDS) -print_final_stats=1 -artifact_prefix=build/fuzz/crash_$$t- > build/fuzz/$$t.log 2>&1; \
+	  echo "exit code $$?" >> build/fuzz/$$t.log; \
+	  grep -E "^#[0-9]+.*(INITED|DONE)|stat::|ERROR|SUMMARY|exit code" build/fuzz/$$t.log; \
+	done
+
 clean:
 	$(MAKE) -C hyper-greco_amd/csrc clean
 	rm -rf build/asan build/fuzz
-.PHONY: all asan fuzz clean
+.PHONY: all asan fuzz fuzz-pcs clean

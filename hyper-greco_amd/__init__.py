@@ -50,6 +50,7 @@ EXPORTS = [
     "hg_pk_lasso_layout", "hg_pk_info", "hg_pk_node_eq_form", "hg_witness_from_json", "hg_witness_synthetic", "hg_witness_from_arrays", "hg_witness_derive", "hg_witness_derive_into",
     "hg_witness_get", "hg_witness_free", "hg_prove", "hg_warmup", "hg_prove_stream", "hg_encryption_layout", "hg_prove_encryptions", "hg_verify", "hg_verify_device", "hg_verify_device_mode", "hg_verify_device_batch",
     "hg_instance_from_ciphertext", "hg_instance_from_witness", "hg_instance_free", "hg_instance_coeffs", "hg_instance_get", "hg_pk_claim_shape", "hg_verify_public", "hg_verify_public_device", "hg_verify_public_batch", "hg_claims_settle", "hg_instance_mle", "hg_instance_mle_batch",
+    "hg_pcs_commit", "hg_pcs_free", "hg_pcs_open", "hg_pcs_verify", "hg_secrets_commit", "hg_claims_open", "hg_claims_verify",
     "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_mle_eval",
     "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_verify_public_bn254", "hg_verify_public_device_bn254", "hg_verify_public_batch_bn254", "hg_claims_settle_bn254", "hg_instance_mle_bn254", "hg_instance_mle_batch_bn254", "hg_prove_encryptions_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
 ]
@@ -1093,6 +1094,128 @@ def claims_settle(ctx, params, witness, claims):
     if rc < 0:
         raise HgError(lib().hg_last_error().decode())
     return rc == 0, ("" if rc == 0 else lib().hg_last_error().decode())
+
+
+u32p = C.POINTER(C.c_uint32)
+u8p = C.POINTER(C.c_uint8)
+PCS_DEFAULT_QUERIES = 241
+
+
+def pcs_row_log2(nvars, log2_row=0):
+    """The row length an hg_pcs_* call uses: log2_row, or for 0 min(min v_t, ceil(log2(sum 2^v_t) / 2))."""
+    if log2_row:
+        return log2_row
+    total, c = sum(1 << v for v in nvars), 0
+    while (1 << (2 * c)) < total:
+        c += 1
+    return min(c, min(nvars))
+
+
+def pcs_opening_bytes(nvars, n_claims, n_queries=0, log2_row=0):
+    """16 C (n+1) + Q (8 R + 32 (c+2)): the exact length of an opening."""
+    c = pcs_row_log2(nvars, log2_row)
+    rows = sum(1 << (v - c) for v in nvars)
+    return 16 * (1 << c) * (n_claims + 1) + (n_queries or PCS_DEFAULT_QUERIES) * (8 * rows + 32 * (c + 2))
+
+
+def _pcs_protos():
+    L = lib()
+    L.hg_pcs_commit.argtypes = [C.c_void_p, C.POINTER(u64p), u32p, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p), u8p]
+    L.hg_pcs_free.argtypes = [C.c_void_p]
+    L.hg_pcs_free.restype = None
+    L.hg_pcs_open.argtypes = [C.c_void_p, C.c_void_p, u32p, u64p, u64p, C.c_size_t, C.c_size_t, u8p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.hg_pcs_verify.argtypes = [C.c_char_p, u32p, C.c_size_t, C.c_size_t, u32p, u64p, u64p, C.c_size_t, C.c_size_t, C.c_char_p, C.c_size_t]
+    L.hg_secrets_commit.argtypes = [C.c_void_p, C.POINTER(HgParams), C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), u8p]
+    L.hg_claims_open.argtypes = [C.c_void_p, C.POINTER(HgParams), C.c_void_p, C.c_void_p, C.c_size_t, u64p, C.c_size_t, u8p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.hg_claims_verify.argtypes = [C.POINTER(HgParams), C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, u64p, C.c_size_t, C.c_char_p, C.c_size_t]
+    return L
+
+
+def _pcs_claim_arrays(claims):
+    """claims: [(table, point words (2 per coordinate), (v0, v1))] -> ctypes / numpy arguments"""
+    n = len(claims)
+    table = (C.c_uint32 * max(n, 1))(*[int(c[0]) for c in claims])
+    pts = np.array([int(x) for c in claims for x in c[1]] or [0], dtype=np.uint64)
+    vals = np.array([int(x) for c in claims for x in c[2]] or [0], dtype=np.uint64)
+    return table, pts, vals
+
+
+class Commitment:
+    """hg_pcs_commit / hg_secrets_commit: the handle of a polynomial commitment (host form: ctx None) and its 32-byte root."""
+
+    def __init__(self, handle, root, ctx, nvars, log2_row):
+        self.h, self.root, self.ctx, self.nvars, self.log2_row = handle, root, ctx, list(nvars), log2_row
+
+    @classmethod
+    def commit(cls, ctx, tables, log2_row=0):
+        """tables: numpy u64 arrays of 2^v_t canonical words."""
+        L = _pcs_protos()
+        tabs = [np.ascontiguousarray(t, dtype=np.uint64) for t in tables]
+        nvars = [t.size.bit_length() - 1 for t in tabs]
+        ptrs = (u64p * len(tabs))(*[_ptr(t) for t in tabs])
+        nv = (C.c_uint32 * len(tabs))(*nvars)
+        h, root = C.c_void_p(), (C.c_uint8 * 32)()
+        _check(L.hg_pcs_commit(ctx.h if ctx is not None else None, ptrs, nv, len(tabs), log2_row, C.byref(h), root))
+        return cls(h, bytes(root), ctx, nvars, pcs_row_log2(nvars, log2_row))
+
+    @classmethod
+    def secrets(cls, ctx, params, witness, log2_row=0):
+        """hg_secrets_commit: the five secret inputs of a witness handle (tables s, e, k1, r1is[0..k-1], r2is)."""
+        L = _pcs_protos()
+        h, root = C.c_void_p(), (C.c_uint8 * 32)()
+        _check(L.hg_secrets_commit(ctx.h if ctx is not None else None, C.byref(params), witness.h, log2_row, C.byref(h), root))
+        lg = params.n.bit_length() - 1
+        nvars = [lg + 1] * (3 + params.k) + [lg + params.k.bit_length() - 1]
+        return cls(h, bytes(root), ctx, nvars, pcs_row_log2(nvars, log2_row))
+
+    def open(self, claims, n_queries=0):
+        """hg_pcs_open: claims = [(table, point words, (v0, v1))] -> the opening bytes."""
+        L = _pcs_protos()
+        cap = pcs_opening_bytes(self.nvars, len(claims), n_queries, self.log2_row)
+        buf, ln = (C.c_uint8 * cap)(), C.c_size_t(0)
+        table, pts, vals = _pcs_claim_arrays(claims)
+        _check(L.hg_pcs_open(self.ctx.h if self.ctx is not None else None, self.h, table, _ptr(pts), _ptr(vals), len(claims), n_queries, buf, cap, C.byref(ln)))
+        return bytes(memoryview(buf)[:ln.value])
+
+    def open_claims(self, params, claims, n_queries=0):
+        """hg_claims_open: the opening of an InputClaims (what verify_public returns) against a Commitment.secrets handle."""
+        L = _pcs_protos()
+        cap = pcs_opening_bytes(self.nvars, claims.n, n_queries, self.log2_row)
+        buf, ln = (C.c_uint8 * cap)(), C.c_size_t(0)
+        _check(L.hg_claims_open(self.ctx.h if self.ctx is not None else None, C.byref(params), self.h, claims.claims, claims.n, _ptr(claims.points), n_queries, buf, cap,
+                                C.byref(ln)))
+        return bytes(memoryview(buf)[:ln.value])
+
+    def free(self):
+        if self.h:
+            _pcs_protos().hg_pcs_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def pcs_verify(root, nvars, claims, proof, n_queries=0, log2_row=0):
+    """hg_pcs_verify (host only): (accepted, reason). claims as Commitment.open takes them."""
+    L = _pcs_protos()
+    nv = (C.c_uint32 * len(nvars))(*nvars)
+    table, pts, vals = _pcs_claim_arrays(claims)
+    rc = L.hg_pcs_verify(bytes(root), nv, len(nvars), log2_row, table, _ptr(pts), _ptr(vals), len(claims), n_queries, bytes(proof), len(proof))
+    if rc < 0:
+        raise HgError(L.hg_last_error().decode())
+    return rc == 0, ("" if rc == 0 else L.hg_last_error().decode())
+
+
+def claims_verify(params, root, claims, opening, n_queries=0, log2_row=0):
+    """hg_claims_verify (host only): an InputClaims against the root of hg_secrets_commit: (accepted, reason)."""
+    L = _pcs_protos()
+    rc = L.hg_claims_verify(C.byref(params), bytes(root), log2_row, claims.claims, claims.n, _ptr(claims.points), n_queries, bytes(opening), len(opening))
+    if rc < 0:
+        raise HgError(L.hg_last_error().decode())
+    return rc == 0, ("" if rc == 0 else L.hg_last_error().decode())
 
 
 class InputClaimsBn254:

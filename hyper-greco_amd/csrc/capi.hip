@@ -10,6 +10,7 @@
 #include <string>
 #include <tuple>
 #include "prover.hpp"
+#include "pcs.hpp"
 
 // BN254 slice (bn254.hip)
 namespace hg { namespace bn {
@@ -1739,6 +1740,168 @@ int hg_ntt_bn254(hg_ctx* ctx, const uint64_t* in4, size_t log2n, int inverse, si
     if (!ctx) throw hg::Error("hg_ntt_bn254: no context (a HIP device is required)");
     hg::bn::ntt_bn254(ctx, in4, (int)log2n, inverse != 0, batch, out4);
     return 0;
+    HG_CATCH(-1)
+}
+
+// ---- polynomial commitment (pcs.hpp): hg_pcs_* on caller tables, hg_secrets_commit / hg_claims_open / hg_claims_verify for the
+// five secret inputs of an encryption
+static std::vector<pcs::Claim> pcs_claims(const char* who, const pcs::Shape& sh, const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n) {
+    const std::string w(who);
+    if (n > pcs::MAX_CLAIMS) throw Error(w + ": more than " + std::to_string(pcs::MAX_CLAIMS) + " claims");
+    std::vector<pcs::Claim> cl(n);
+    size_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (table[i] >= sh.nvars.size()) throw Error(w + ": claim " + std::to_string(i) + " names table " + std::to_string(table[i]) + " of " + std::to_string(sh.nvars.size()));
+        cl[i].table = table[i];
+        cl[i].point.resize((size_t)sh.nvars[table[i]]);
+        for (E2& x : cl[i].point) { x = e2(points[2 * at], points[2 * at + 1]); at++; }
+        cl[i].value = e2(values[2 * i], values[2 * i + 1]);
+        for (const E2& x : cl[i].point) if (x.c0 >= GL_P || x.c1 >= GL_P) throw Error(w + ": claim " + std::to_string(i) + ": non-canonical coordinate");
+        if (cl[i].value.c0 >= GL_P || cl[i].value.c1 >= GL_P) throw Error(w + ": claim " + std::to_string(i) + ": non-canonical value");
+    }
+    return cl;
+}
+static size_t pcs_queries(const char* who, size_t n_queries) {
+    if (n_queries > pcs::MAX_QUERIES) throw Error(std::string(who) + ": more than " + std::to_string(pcs::MAX_QUERIES) + " queries");
+    return n_queries ? n_queries : pcs::DEFAULT_QUERIES;
+}
+static void pcs_emit(const char* who, const std::vector<uint8_t>& bytes, uint8_t* out, size_t cap, size_t* len) {
+    *len = bytes.size();
+    if (bytes.size() > cap) throw Error(std::string(who) + ": the opening has " + std::to_string(bytes.size()) + " bytes, the buffer " + std::to_string(cap));
+    memcpy(out, bytes.data(), bytes.size());
+}
+// the secret inputs as commitment tables, in input order s, e, k1, r1is[0..k-1], r2is
+static std::vector<uint32_t> secrets_nvars(const Params& p) {
+    std::vector<uint32_t> v(3 + (size_t)p.k, (uint32_t)p.L);
+    v.push_back((uint32_t)(p.n_log2 + p.log2k));
+    return v;
+}
+// hg_input_claim array -> (table, points, values) of the commitment over the secret inputs
+static void secrets_claims(const char* who, const Params& p, const void* claims, size_t n, const uint64_t* points, std::vector<uint32_t>& table,
+                           std::vector<uint64_t>& pts, std::vector<uint64_t>& vals) {
+    const std::string w(who);
+    if (n > pcs::MAX_CLAIMS) throw Error(w + ": more than " + std::to_string(pcs::MAX_CLAIMS) + " claims");
+    const hg_input_claim* in = static_cast<const hg_input_claim*>(claims);
+    const std::vector<uint32_t> nv = secrets_nvars(p);
+    const uint32_t k = (uint32_t)p.k;
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t id = in[i].input;
+        uint32_t t;
+        if (id < 3) t = id;
+        else if (id >= 3 + k && id < 3 + 2 * k) t = id - k;
+        else if (id == 3 + 2 * k) t = 3 + k;
+        else throw Error(w + ": claim " + std::to_string(i) + " is on input " + std::to_string(id) + ", which is not a secret input (0, 1, 2, " + std::to_string(3 + k) + " .. " + std::to_string(3 + 2 * k) + ")");
+        if (in[i].nvars != nv[t]) throw Error(w + ": claim " + std::to_string(i) + " has " + std::to_string(in[i].nvars) + " coordinates, input " + std::to_string(id) + " has " + std::to_string(nv[t]) + " variables");
+        table.push_back(t);
+        for (size_t j = 0; j < in[i].nvars; j++) { pts.push_back(points[2 * (in[i].point_off + j)]); pts.push_back(points[2 * (in[i].point_off + j) + 1]); }
+        vals.push_back(in[i].value[0]); vals.push_back(in[i].value[1]);
+    }
+}
+
+int hg_pcs_commit(hg_ctx* ctx, const uint64_t* const* tables, const uint32_t* nvars, size_t n_tables, size_t log2_row, void** commitment, uint8_t root[32]) {
+    HG_TRY
+    if (commitment) *commitment = nullptr;
+    if (!tables || !nvars || !commitment || !root) throw Error("hg_pcs_commit: null argument");
+    const pcs::Shape sh = pcs::make_shape("hg_pcs_commit", nvars, n_tables, log2_row);
+    for (size_t t = 0; t < n_tables; t++) if (!tables[t]) throw Error("hg_pcs_commit: null table " + std::to_string(t));
+    pcs::Commitment* cm = ctx ? pcs::commit_device(ctx, sh, tables) : pcs::commit_host(sh, tables);
+    memcpy(root, cm->root(), 32);
+    *commitment = cm;
+    return 0;
+    HG_CATCH(-1)
+}
+
+void hg_pcs_free(void* commitment) { delete static_cast<pcs::Commitment*>(commitment); }
+
+static int pcs_open_entry(const char* who, hg_ctx* ctx, const pcs::Commitment* cm, const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n_claims,
+                          size_t n_queries, uint8_t* proof, size_t cap, size_t* len) {
+    if (cm->ctx != ctx) throw Error(std::string(who) + ": the commitment was made " + (cm->ctx ? "on a device context: pass that context" : "by the host form: pass no context"));
+    const std::vector<pcs::Claim> cl = pcs_claims(who, cm->sh, table, points, values, n_claims);
+    pcs_emit(who, pcs::open(who, *cm, cl, pcs_queries(who, n_queries)), proof, cap, len);
+    return 0;
+}
+
+int hg_pcs_open(hg_ctx* ctx, const void* commitment, const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n_claims, size_t n_queries,
+                uint8_t* proof, size_t cap, size_t* len) {
+    HG_TRY
+    if (len) *len = 0;
+    if (!commitment || !proof || !len || (n_claims && (!table || !points || !values))) throw Error("hg_pcs_open: null argument");
+    return pcs_open_entry("hg_pcs_open", ctx, static_cast<const pcs::Commitment*>(commitment), table, points, values, n_claims, n_queries, proof, cap, len);
+    HG_CATCH(-1)
+}
+
+int hg_pcs_verify(const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table, const uint64_t* points,
+                  const uint64_t* values, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
+    HG_TRY
+    if (!root || !nvars || (len && !proof) || (n_claims && (!table || !points || !values))) throw Error("hg_pcs_verify: null argument");
+    const pcs::Shape sh = pcs::make_shape("hg_pcs_verify", nvars, n_tables, log2_row);
+    const std::vector<pcs::Claim> cl = pcs_claims("hg_pcs_verify", sh, table, points, values, n_claims);
+    const std::string why = pcs::verify(sh, root, cl, pcs_queries("hg_pcs_verify", n_queries), proof, len);
+    if (why.empty()) return 0;
+    g_last_error = why;
+    return 1;
+    HG_CATCH(-1)
+}
+
+int hg_secrets_commit(hg_ctx* ctx, const hg_params* params, const hg_witness* w, size_t log2_row, void** commitment, uint8_t root[32]) {
+    HG_TRY
+    if (commitment) *commitment = nullptr;
+    if (!params || !w || !commitment || !root) throw Error("hg_secrets_commit: null argument");
+    Params p(*params);
+    const size_t SZ = p.SZ(), k = (size_t)p.k;
+    const Witness& v = w->w;
+    if (w->params.n != params->n || w->params.k != params->k || v.s.size() != SZ || v.e.size() != SZ || v.k1.size() != SZ || v.r1is.size() != k * SZ ||
+        v.r2is.size() != k * p.PZ())
+        throw Error("hg_secrets_commit: the witness was built for other parameters");
+    const std::vector<uint32_t> nv = secrets_nvars(p);
+    std::vector<const uint64_t*> tabs = {v.s.data(), v.e.data(), v.k1.data()};
+    for (size_t i = 0; i < k; i++) tabs.push_back(v.r1is.data() + i * SZ);
+    tabs.push_back(v.r2is.data());
+    const pcs::Shape sh = pcs::make_shape("hg_secrets_commit", nv.data(), nv.size(), log2_row);
+    pcs::Commitment* cm;
+    try {
+        cm = ctx ? pcs::commit_device(ctx, sh, tabs.data()) : pcs::commit_host(sh, tabs.data());
+    } catch (const std::exception& e) {
+        throw Error(std::string("hg_secrets_commit: ") + e.what());
+    }
+    memcpy(root, cm->root(), 32);
+    *commitment = cm;
+    return 0;
+    HG_CATCH(-1)
+}
+
+int hg_claims_open(hg_ctx* ctx, const hg_params* params, const void* commitment, const void* claims, size_t n, const uint64_t* points, size_t n_queries,
+                   uint8_t* opening, size_t cap, size_t* len) {
+    HG_TRY
+    if (len) *len = 0;
+    if (!params || !commitment || !opening || !len || (n && (!claims || !points))) throw Error("hg_claims_open: null argument");
+    Params p(*params);
+    const pcs::Commitment* cm = static_cast<const pcs::Commitment*>(commitment);
+    const std::vector<uint32_t> nv = secrets_nvars(p);
+    if (cm->sh.nvars.size() != nv.size() || !std::equal(nv.begin(), nv.end(), cm->sh.nvars.begin(), [](uint32_t a, int b) { return (int)a == b; }))
+        throw Error("hg_claims_open: the commitment is not hg_secrets_commit's for these parameters");
+    std::vector<uint32_t> table;
+    std::vector<uint64_t> pts, vals;
+    secrets_claims("hg_claims_open", p, claims, n, points, table, pts, vals);
+    return pcs_open_entry("hg_claims_open", ctx, cm, table.data(), pts.data(), vals.data(), n, n_queries, opening, cap, len);
+    HG_CATCH(-1)
+}
+
+int hg_claims_verify(const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points, size_t n_queries,
+                     const uint8_t* opening, size_t len) {
+    HG_TRY
+    if (!params || !root || (len && !opening) || (n && (!claims || !points))) throw Error("hg_claims_verify: null argument");
+    Params p(*params);
+    const std::vector<uint32_t> nv = secrets_nvars(p);
+    const pcs::Shape sh = pcs::make_shape("hg_claims_verify", nv.data(), nv.size(), log2_row);
+    std::vector<uint32_t> table;
+    std::vector<uint64_t> pts, vals;
+    secrets_claims("hg_claims_verify", p, claims, n, points, table, pts, vals);
+    const std::vector<pcs::Claim> cl = pcs_claims("hg_claims_verify", sh, table.data(), pts.data(), vals.data(), n);
+    const std::string why = pcs::verify(sh, root, cl, pcs_queries("hg_claims_verify", n_queries), opening, len);
+    if (why.empty()) return 0;
+    g_last_error = why;
+    return 1;
     HG_CATCH(-1)
 }
 

@@ -1,0 +1,77 @@
+// Multilinear polynomial commitment of the Brakedown / Ligero shape over Goldilocks: the layer that opens the claims
+// hg_verify_public leaves on the secret inputs. The reference names MultilinearBrakedown<F, Keccak256, BrakedownSpec6> as its Pcs type
+// parameter [REF bfv-gkr/src/sk_encryption_circuit.rs:543-550] and never uses it. What differs here: the linear code
+// is Reed-Solomon of rate 1/4 (the forward NTT of the zero-padded row: Goldilocks has the two-adicity, Brakedown's argument only
+// needs linearity), not the expander code of BrakedownSpec6; and evaluation points are E = GoldilocksExt2 points.
+//
+// Scheme (include/hg.h states it in full). Tables T_0 .. T_{m-1} of 2^{v_t} canonical words are cut into rows of C = 2^c words
+// and stacked in table order (R rows, off_t = first row of table t). Enc(row) = NTT_{4C}(row || 0). Leaf j of the Keccak-256
+// Merkle tree hashes LE64(0) || column j of the encoded matrix; an inner node hashes LE64(1) || left || right. An opening of n
+// claims carries u_0 = sum_r rho^r row_r, u_i = sum_r eq(z_i[c..])[r] row_{off_t + r} and Q opened columns with their paths.
+#pragma once
+#include <string>
+#include <vector>
+#include "host.hpp"
+
+struct hg_ctx;
+
+namespace hg {
+namespace pcs {
+
+constexpr int MAX_TABLES = 64, MAX_NVARS = 30, MAX_LOG2_ROW = 24;
+constexpr size_t MAX_CLAIMS = 4096, MAX_QUERIES = 65536;
+constexpr size_t DEFAULT_QUERIES = 241;   // ceil(100 / log2(4/3)): the (3/4)^Q term at rate 1/4, proximity parameter d/3
+
+struct Shape {
+    int c = 0;                   // log2 of the row length
+    std::vector<int> nvars;      // v_t
+    std::vector<size_t> off;     // first row of table t
+    size_t R = 0;                // rows in all
+    size_t C() const { return (size_t)1 << c; }
+    size_t N() const { return (size_t)4 << c; }   // code length
+    int depth() const { return c + 2; }
+};
+// log2_row == 0 selects min(min_t v_t, ceil(log2(sum_t 2^{v_t}) / 2)); an Error naming `who` for a shape outside the limits above
+// or c > v_t
+Shape make_shape(const char* who, const uint32_t* nvars, size_t n_tables, size_t log2_row);
+inline size_t opening_bytes(const Shape& sh, size_t n_claims, size_t Q) { return 16 * sh.C() * (n_claims + 1) + Q * (8 * sh.R + 32 * (size_t)sh.depth()); }
+
+struct Claim { size_t table; std::vector<E2> point; E2 value; };
+
+// One handle for both forms. The tree is always on the host: level l (0 = leaves) starts at node 2N - (2N >> l), 32 bytes a node.
+struct Commitment {
+    Shape sh;
+    hg_ctx* ctx = nullptr;          // null: host form
+    std::vector<u64> rows, M;       // host form: R x C raw rows, R x 4C encoded rows
+    u64* d_rows = nullptr;          // device form: the same two matrices in HBM, owned
+    u64* d_M = nullptr;
+    std::vector<uint8_t> tree;
+    const uint8_t* root() const { return tree.data() + 32 * (2 * sh.N() - 2); }
+    const uint8_t* node(int level, size_t i) const { return tree.data() + 32 * (2 * sh.N() - ((2 * sh.N()) >> level) + i); }
+    ~Commitment();
+};
+
+// the Keccak-256 calls of the tree
+void leaf_hash(const u64* words, size_t R, uint8_t out[32]);                      // Keccak256(LE64(0) || LE64(words[0]) || ...)
+void node_hash(const uint8_t* left, const uint8_t* right, uint8_t out[32]);       // Keccak256(LE64(1) || left || right)
+std::vector<E2> eq_table(const E2* pt, size_t n);                                 // coordinate i belongs to bit i of the index
+
+// ---- host form (pcs.cpp)
+Commitment* commit_host(const Shape& sh, const u64* const* tables);
+// ---- device form (pcs.hip): rows staged and encoded in HBM, column hashes and the tree by kernels, one synchronisation
+Commitment* commit_device(hg_ctx* ctx, const Shape& sh, const u64* const* tables);
+
+// One row combination of an opening: u[j] = sum_{r < nrows} w[r] * row_{row0 + r}[j]
+struct CombineJob { size_t row0, nrows; std::vector<E2> w; };
+void combine_host(const Commitment& cm, const std::vector<CombineJob>& jobs, E2* u);                 // u: jobs.size() x C
+void columns_host(const Commitment& cm, const std::vector<size_t>& js, u64* cols);                   // cols: js.size() x R
+void combine_device(const Commitment& cm, const std::vector<CombineJob>& jobs, E2* u);
+void columns_device(const Commitment& cm, const std::vector<size_t>& js, u64* cols);
+
+// hg_pcs_open: the opening bytes; an Error (naming `who` and the claim) if a value is not <u_i, eq(z_i[..c])>
+std::vector<uint8_t> open(const char* who, const Commitment& cm, const std::vector<Claim>& claims, size_t Q);
+// hg_pcs_verify: "" = accepted, else the reason
+std::string verify(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof, size_t len);
+
+}  // namespace pcs
+}  // namespace hg

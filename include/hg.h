@@ -222,7 +222,7 @@ int hg_verify_device_batch(hg_ctx* ctx, const hg_pk* pk, const hg_witness* const
  * r1is, r2is) are the encryptor's secrets. A recipient holds the ciphertext (ct0_i, a_i) and the proof. The entries below decide
  * everything those and the key decide - the output claim, every node reduction, the Lasso scalars, the input claims on the ais
  * tables - and hand back what is left, the claims (input, point, value) on the five secret inputs: what a commitment layer would
- * open (the reference's PCS type parameter is dead). hg_claims_settle checks such claims against a witness handle,
+ * open (the reference's PCS type parameter is dead): hg_claims_open / hg_claims_verify below. hg_claims_settle checks such claims against a witness handle,
  * which is the reference's contract again: hg_verify_public followed by hg_claims_settle decides what hg_verify_mode decides.
  * Goldilocks, modes 0..3, one proof per call (hg_verify_public_batch: a run of them in one device pass). Over bn256::Fr:
  * hg_verify_public_bn254 and its neighbours, below hg_verify_device_batch_bn254; the instance handle and hg_pk_claim_shape serve
@@ -305,6 +305,78 @@ int hg_instance_mle(hg_ctx* ctx, const void* instance, int which, int index, con
  * for a null argument or element, no context, or instances of mixed parameters. */
 int hg_instance_mle_batch(hg_ctx* ctx, const void* const* instances, size_t n, int which, int index, const uint64_t* point,
                           size_t nvars, uint64_t* out);
+
+/* ---- Polynomial commitment: what opens the claims hg_verify_public leaves ------------------------------------------------------
+ * The reference names MultilinearBrakedown<F, Keccak256, BrakedownSpec6> as its Pcs type parameter
+ * [REF sk_encryption_circuit.rs:543-550] and never calls it. This is that layer for Goldilocks: a multilinear
+ * commitment of the Brakedown / Ligero shape with the reference's hash, Keccak-256. Two things differ from the type the reference
+ * names: the linear code is Reed-Solomon of rate 1/4 (the NTT of the zero-padded row; Brakedown's argument needs a linear code, not
+ * the expander code of BrakedownSpec6), and evaluation points are E = GoldilocksExt2 points. Not zero knowledge: an opening
+ * reveals linear combinations and whole encoded columns of the tables. The root is NOT yet absorbed into the GKR transcript.
+ *
+ * The scheme. Coordinate i of a point belongs to bit i of the table index (the convention of hg_mle_eval and hg_claims_settle).
+ *   Rows.   Tables T_0 .. T_{m-1}, table t of 2^{v_t} canonical words. Row length C = 2^c (c = log2_row, c <= v_t for every t).
+ *           Table t gives 2^{v_t - c} rows, row r = T_t[r C .. (r+1) C); the rows of all tables are stacked in table order, R rows
+ *           in all; off_t = the first row of table t.
+ *   Code.   Enc(row) = the forward NTT of size N = 4C of the row zero-padded to 4C words, natural order, root root_of_unity(c+2):
+ *           what hg_ntt(.., log2n = c+2, inverse = 0, ..) computes. On an E vector Enc acts on the c0 and the c1 coordinates apart.
+ *   Tree.   leaf_j = Keccak256(LE64(0) || LE64(M[0][j]) || .. || LE64(M[R-1][j])), j < 4C, M[r] = Enc(row_r); an inner node is
+ *           Keccak256(LE64(1) || left || right); the commitment is the 32-byte root. Keccak-256 with the original padding.
+ *   Opening of n claims (t_i, z_i in E^{v_{t_i}}, y_i) with Q = n_queries:
+ *     1. an absorbing transcript (mode bit 1 above) whose hash state starts as the ASCII bytes "hg-pcs-1", the root, then as 4-byte
+ *        little-endian c, m, v_0 .. v_{m-1}, Q, n, then per claim t_i (4-byte LE), the point's words and the value's two words (8-byte LE);
+ *     2. rho = a squeezed E challenge; u_0[j] = sum_{r<R} rho^r row_r[j], j < C (the proximity combination);
+ *     3. per claim w_i = eq(z_i[c..]) (2^{v_t - c} entries) and u_i[j] = sum_r w_i[r] row_{off_t + r}[j];
+ *     4. u_0, u_1 .. u_n are written (big-endian, as every proof element) and absorbed;
+ *     5. Q column indices j_q = (a squeezed base-field challenge) & (4C - 1), duplicates kept;
+ *     6. per query the R column words M[.][j_q] (8-byte big-endian) and the c+2 siblings bottom-up (32 raw bytes each).
+ *     Length: exactly 16 C (n+1) + Q (8 R + 32 (c+2)) bytes.
+ *   Verification (host only), in this order, the first failure is the reason in hg_last_error:
+ *     1. the exact length ("pcs: the opening has .. bytes, .. expected");  2. every element and column word below p ("pcs:
+ *     non-canonical word at byte ..");  3. <u_i, eq(z_i[..c])> == y_i, claims ascending ("pcs: evaluation mismatch at claim i");
+ *     4. per query, ascending: leaf hash and path reach the root ("pcs: Merkle path mismatch at query q"), sum_r rho^r col[r] ==
+ *     Enc(u_0)[j_q] ("pcs: proximity mismatch at query q"), per claim sum_r w_i[r] col[off_t + r] == Enc(u_i)[j_q] ("pcs: claim i
+ *     inconsistent at query q").
+ *   Parameters, plain arguments on every side (the verifier passes what it requires): n_queries = 0 means 241 =
+ *     ceil(100 / log2(4/3)), the (3/4)^Q term of the unique-decoding analysis at rate 1/4 with proximity parameter d/3 - no more is
+ *     claimed; at most 65536. log2_row = 0 means min(min_t v_t, ceil(log2(sum_t 2^{v_t}) / 2)); at most 24. m <= 64, v_t <= 30,
+ *     n <= 4096.
+ * Contracts: 0, 1 = rejected with the reason (the verifiers only), -1 with text in hg_last_error that names the function. The
+ * commitment handle crosses as void*.
+ *
+ * hg_pcs_commit: the generic layer on caller tables (tables[t]: 2^{nvars[t]} host words). ctx == NULL: the host form; with a
+ *   context the device form - rows staged and encoded in HBM by the batched NTT, one Keccak-f[1600] state per thread for the
+ *   column hashes and for every tree node, one synchronisation; the handle then owns the raw and the encoded matrix in HBM (14 MB +
+ *   57 MB for the secrets of n=32768 k=16 at c=11) and a host copy of the tree. Both forms give the same root. -1: a null argument
+ *   or table, a shape outside the limits, log2_row above a table's variables, a word that is not below p, more than 65535 rows on
+ *   the device.
+ * hg_pcs_open: points = the claims' points one behind the other, 2 words per coordinate, nvars[table[i]] coordinates for claim i;
+ *   values: 2 words per claim. ctx must be the context the commitment was made on (NULL for the host form). The device form runs
+ *   the row combinations as one launch (weights built on the host, staged in one copy) and gathers the opened columns with
+ *   another; the column indices depend on the u_i through the transcript, so it synchronises twice. Same bytes as the host form.
+ *   n_claims == 0 is allowed: the proximity test alone. *len = the opening's length, also when cap is too small (-1). -1 also: a
+ *   null argument, a table index out of range, a non-canonical coordinate or value, and - naming the claim - a value that is not
+ *   <u_i, eq(z_i[..c])>: the prover holds u_i, so the check is free.
+ * hg_pcs_verify: host only, no context. -1: a null argument, a shape or a count outside the limits, a table index out of range, a
+ *   non-canonical coordinate or value.
+ * hg_secrets_commit: hg_pcs_commit of the five secret inputs of a witness handle, tables in input order s, e, k1, r1is[0] ..
+ *   r1is[k-1], r2is: m = k+4, variables L, L, L, L x k, P + log2 k (L = log2 n + 1, P = log2 n).
+ * hg_claims_open / hg_claims_verify: hg_pcs_open / hg_pcs_verify for an hg_input_claim array exactly as hg_verify_public* returns
+ *   it (claims, n, points). Input ids map to tables 0, 1, 2 -> 0, 1, 2; 3+k+i -> 3+i; 3+2k -> 3+k; a claim on input 3 .. 3+k-1 (the
+ *   public ais) or past 3+2k is an error (-1), so is a claim whose nvars is not its input's. hg_verify_public followed by
+ *   hg_claims_verify against a root the encryptor published is a verification that needs no secret. */
+int hg_pcs_commit(hg_ctx* ctx, const uint64_t* const* tables, const uint32_t* nvars, size_t n_tables, size_t log2_row, void** commitment,
+                  uint8_t root[32]);
+void hg_pcs_free(void* commitment);
+int hg_pcs_open(hg_ctx* ctx, const void* commitment, const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n_claims,
+                size_t n_queries, uint8_t* proof, size_t cap, size_t* len);
+int hg_pcs_verify(const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table, const uint64_t* points,
+                  const uint64_t* values, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len);
+int hg_secrets_commit(hg_ctx* ctx, const hg_params* params, const hg_witness* w, size_t log2_row, void** commitment, uint8_t root[32]);
+int hg_claims_open(hg_ctx* ctx, const hg_params* params, const void* commitment, const void* claims, size_t n, const uint64_t* points,
+                   size_t n_queries, uint8_t* opening, size_t cap, size_t* len);
+int hg_claims_verify(const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points,
+                     size_t n_queries, const uint8_t* opening, size_t len);
 
 /* The same pair in a protocol mode that FIXES the reference's two known soundness gaps. mode bits:
  *   1  absorbing transcript: write_felt / read_felt also hash the element - the rule of the in-tree plonkish-trait writer of

@@ -10,8 +10,9 @@ out=$root/build/$name
 mkdir -p "$out"
 CXX="/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -fopenmp --offload-arch=gfx950 -Wall -Wno-unused-function -Wno-unused-result -Wno-sign-compare $flags"
 pids=()
-for f in kernels.hip prover.hip prover_seq.hip capi.hip bn254.hip comm.hip verifier_dev.hip verifier_batch.hip; do $CXX -c "$src/$f" -o "$out/${f%.hip}.o" & pids+=($!); done
+for f in kernels.hip prover.hip prover_seq.hip capi.hip bn254.hip comm.hip verifier_dev.hip verifier_batch.hip pcs.hip; do $CXX -c "$src/$f" -o "$out/${f%.hip}.o" & pids+=($!); done
 for f in host.cpp verifier.cpp; do $CXX -x hip -c "$src/$f" -o "$out/${f%.cpp}.o" & pids+=($!); done
+$CXX -x hip -c "$src/pcs.cpp" -o "$out/pcs_host.o" & pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
 # sanitizer flags (make asan) must reach the link too
 lflags=$(echo "$flags" | tr ' ' '\n' | grep -E '^-fsanitize|^-shared-libsan|^-fno-gpu-sanitize' | tr '\n' ' ' || true)

@@ -1,0 +1,78 @@
+#!/usr/bin/env python3
+"""Times of the polynomial commitment over the secret inputs, device form against host form (ctx == NULL), in one process: the legs
+ALTERNATED on one synthetic witness and the claims hg_verify_public_device leaves on its hg_prove proof, after one warm-up call of
+each leg, --reps timed calls each:
+  commit_dev / commit_host   hg_secrets_commit with a context / without (upload or copy of the tables, encoding, column hashes, tree)
+  open_dev / open_host       hg_claims_open of those claims on the commitment of that form (default 241 queries)
+  verify                     hg_claims_verify of the opening (host only)
+Prints the opening's bytes, median and range per leg, and whether the whole range of commit_dev lies below that of commit_host.
+Usage: pcs_times.py [n k] [--reps 5]"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import __graft_entry__ as entry  # noqa: E402
+
+hg = entry.load_package()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("n", type=int, nargs="?", default=32768)
+    ap.add_argument("k", type=int, nargs="?", default=16)
+    ap.add_argument("--reps", type=int, default=5)
+    a = ap.parse_args()
+    ctx = hg.Context(0)
+    bfv = hg.BfvEncrypt.new(a.n, a.k)
+    pk = bfv.setup(ctx)
+    w = hg.Witness.synthetic(bfv.params, 0x4752454330 + a.n)
+    proof, _ = bfv.prove(ctx, pk, w, cap=1 << 25)
+    ok, why, claims = hg.verify_public(pk, hg.Instance.from_witness(w), proof, 0, ctx=ctx, device=True)
+    assert ok, why
+    held = {"dev": hg.Commitment.secrets(ctx, bfv.params, w), "host": hg.Commitment.secrets(None, bfv.params, w)}
+    assert held["dev"].root == held["host"].root
+    opening = held["dev"].open_claims(bfv.params, claims)
+    assert opening == held["host"].open_claims(bfv.params, claims)
+
+    def commit(form):
+        held[form].free()
+        held[form] = hg.Commitment.secrets(ctx if form == "dev" else None, bfv.params, w)
+
+    legs = [("commit_dev", lambda: commit("dev")), ("commit_host", lambda: commit("host")),
+            ("open_dev", lambda: held["dev"].open_claims(bfv.params, claims)), ("open_host", lambda: held["host"].open_claims(bfv.params, claims)),
+            ("verify", lambda: hg.claims_verify(bfv.params, held["host"].root, claims, opening))]
+    times = {name: [] for name, _ in legs}
+    for rep in range(a.reps + 1):   # rep 0: the warm-up call of each leg
+        for name, fn in legs:
+            t0 = time.perf_counter()
+            out = fn()
+            dt = (time.perf_counter() - t0) * 1e3
+            if name == "verify":
+                assert out == (True, ""), out
+            if rep:
+                times[name].append(dt)
+    c = held["dev"]
+    print("n=%d k=%d: %d tables, log2_row %d, %d rows, code length %d; %d claims, 241 queries, opening %d bytes; legs alternated, %d timed calls each "
+          "after one warm-up call, one process" % (a.n, a.k, len(c.nvars), c.log2_row, sum(1 << (v - c.log2_row) for v in c.nvars), 4 << c.log2_row, claims.n,
+                                                   len(opening), a.reps))
+    for name, _ in legs:
+        t = times[name]
+        print("%-11s median %.2f ms, range %.2f .. %.2f ms (%s)" % (name, statistics.median(t), min(t), max(t), " ".join("%.2f" % x for x in t)))
+    dev, host = times["commit_dev"], times["commit_host"]
+    if max(dev) < min(host):
+        print("commit_dev is faster than commit_host: its whole range lies below the host form's")
+    elif min(dev) > max(host):
+        print("commit_dev is SLOWER than commit_host: its whole range lies above the host form's")
+    else:
+        print("commit_dev and commit_host overlap: no difference shown")
+    for h in held.values():
+        h.free()
+    pk.free()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
