@@ -51,6 +51,7 @@ EXPORTS = [
     "hg_witness_get", "hg_witness_free", "hg_prove", "hg_warmup", "hg_prove_stream", "hg_encryption_layout", "hg_prove_encryptions", "hg_verify", "hg_verify_device", "hg_verify_device_mode", "hg_verify_device_batch",
     "hg_instance_from_ciphertext", "hg_instance_from_witness", "hg_instance_free", "hg_instance_coeffs", "hg_instance_get", "hg_pk_claim_shape", "hg_verify_public", "hg_verify_public_device", "hg_verify_public_batch", "hg_claims_settle", "hg_instance_mle", "hg_instance_mle_batch",
     "hg_pcs_commit", "hg_pcs_free", "hg_pcs_open", "hg_pcs_verify", "hg_secrets_commit", "hg_claims_open", "hg_claims_verify",
+    "hg_pcs_verify_device", "hg_claims_verify_device",
     "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_mle_eval",
     "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_verify_public_bn254", "hg_verify_public_device_bn254", "hg_verify_public_batch_bn254", "hg_claims_settle_bn254", "hg_instance_mle_bn254", "hg_instance_mle_batch_bn254", "hg_prove_encryptions_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
 ]
@@ -1128,6 +1129,8 @@ def _pcs_protos():
     L.hg_secrets_commit.argtypes = [C.c_void_p, C.POINTER(HgParams), C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), u8p]
     L.hg_claims_open.argtypes = [C.c_void_p, C.POINTER(HgParams), C.c_void_p, C.c_void_p, C.c_size_t, u64p, C.c_size_t, u8p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.hg_claims_verify.argtypes = [C.POINTER(HgParams), C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, u64p, C.c_size_t, C.c_char_p, C.c_size_t]
+    L.hg_pcs_verify_device.argtypes = [C.c_void_p] + L.hg_pcs_verify.argtypes
+    L.hg_claims_verify_device.argtypes = [C.c_void_p] + L.hg_claims_verify.argtypes
     return L
 
 
@@ -1198,21 +1201,23 @@ class Commitment:
             pass
 
 
-def pcs_verify(root, nvars, claims, proof, n_queries=0, log2_row=0):
-    """hg_pcs_verify (host only): (accepted, reason). claims as Commitment.open takes them."""
+def pcs_verify(root, nvars, claims, proof, n_queries=0, log2_row=0, ctx=None):
+    """hg_pcs_verify, with a context hg_pcs_verify_device: (accepted, reason). claims as Commitment.open takes them."""
     L = _pcs_protos()
     nv = (C.c_uint32 * len(nvars))(*nvars)
     table, pts, vals = _pcs_claim_arrays(claims)
-    rc = L.hg_pcs_verify(bytes(root), nv, len(nvars), log2_row, table, _ptr(pts), _ptr(vals), len(claims), n_queries, bytes(proof), len(proof))
+    args = (bytes(root), nv, len(nvars), log2_row, table, _ptr(pts), _ptr(vals), len(claims), n_queries, bytes(proof), len(proof))
+    rc = L.hg_pcs_verify(*args) if ctx is None else L.hg_pcs_verify_device(ctx.h, *args)
     if rc < 0:
         raise HgError(L.hg_last_error().decode())
     return rc == 0, ("" if rc == 0 else L.hg_last_error().decode())
 
 
-def claims_verify(params, root, claims, opening, n_queries=0, log2_row=0):
-    """hg_claims_verify (host only): an InputClaims against the root of hg_secrets_commit: (accepted, reason)."""
+def claims_verify(params, root, claims, opening, n_queries=0, log2_row=0, ctx=None):
+    """hg_claims_verify, with a context hg_claims_verify_device: an InputClaims against the root of hg_secrets_commit: (accepted, reason)."""
     L = _pcs_protos()
-    rc = L.hg_claims_verify(C.byref(params), bytes(root), log2_row, claims.claims, claims.n, _ptr(claims.points), n_queries, bytes(opening), len(opening))
+    args = (C.byref(params), bytes(root), log2_row, claims.claims, claims.n, _ptr(claims.points), n_queries, bytes(opening), len(opening))
+    rc = L.hg_claims_verify(*args) if ctx is None else L.hg_claims_verify_device(ctx.h, *args)
     if rc < 0:
         raise HgError(L.hg_last_error().decode())
     return rc == 0, ("" if rc == 0 else L.hg_last_error().decode())

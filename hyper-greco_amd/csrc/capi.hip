@@ -1830,16 +1830,41 @@ int hg_pcs_open(hg_ctx* ctx, const void* commitment, const uint32_t* table, cons
     HG_CATCH(-1)
 }
 
-int hg_pcs_verify(const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table, const uint64_t* points,
-                  const uint64_t* values, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
-    HG_TRY
-    if (!root || !nvars || (len && !proof) || (n_claims && (!table || !points || !values))) throw Error("hg_pcs_verify: null argument");
-    const pcs::Shape sh = pcs::make_shape("hg_pcs_verify", nvars, n_tables, log2_row);
-    const std::vector<pcs::Claim> cl = pcs_claims("hg_pcs_verify", sh, table, points, values, n_claims);
-    const std::string why = pcs::verify(sh, root, cl, pcs_queries("hg_pcs_verify", n_queries), proof, len);
+// hg_pcs_verify (device == false) and hg_pcs_verify_device: the same argument checks in the same order, then the form's verifier
+static int pcs_verify_entry(const char* who, bool device, hg_ctx* ctx, const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row,
+                            const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
+    const std::string w(who);
+    if (!root || !nvars || (len && !proof) || (n_claims && (!table || !points || !values))) throw Error(w + ": null argument");
+    const pcs::Shape sh = pcs::make_shape(who, nvars, n_tables, log2_row);
+    const std::vector<pcs::Claim> cl = pcs_claims(who, sh, table, points, values, n_claims);
+    const size_t Q = pcs_queries(who, n_queries);
+    if (device && !ctx) throw Error(w + ": no context");
+    std::string why;
+    if (device) {
+        try {
+            why = pcs::verify_device(ctx, sh, root, cl, Q, proof, len);
+        } catch (const std::exception& e) {
+            throw Error(w + ": " + e.what());
+        }
+    } else {
+        why = pcs::verify(sh, root, cl, Q, proof, len);
+    }
     if (why.empty()) return 0;
     g_last_error = why;
     return 1;
+}
+
+int hg_pcs_verify(const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table, const uint64_t* points,
+                  const uint64_t* values, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
+    HG_TRY
+    return pcs_verify_entry("hg_pcs_verify", false, nullptr, root, nvars, n_tables, log2_row, table, points, values, n_claims, n_queries, proof, len);
+    HG_CATCH(-1)
+}
+
+int hg_pcs_verify_device(hg_ctx* ctx, const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table,
+                         const uint64_t* points, const uint64_t* values, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
+    HG_TRY
+    return pcs_verify_entry("hg_pcs_verify_device", true, ctx, root, nvars, n_tables, log2_row, table, points, values, n_claims, n_queries, proof, len);
     HG_CATCH(-1)
 }
 
@@ -1887,21 +1912,29 @@ int hg_claims_open(hg_ctx* ctx, const hg_params* params, const void* commitment,
     HG_CATCH(-1)
 }
 
+static int claims_verify_entry(const char* who, bool device, hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n,
+                               const uint64_t* points, size_t n_queries, const uint8_t* opening, size_t len) {
+    if (!params || !root || (len && !opening) || (n && (!claims || !points))) throw Error(std::string(who) + ": null argument");
+    Params p(*params);
+    const std::vector<uint32_t> nv = secrets_nvars(p);
+    std::vector<uint32_t> table;
+    std::vector<uint64_t> pts, vals;
+    (void)pcs::make_shape(who, nv.data(), nv.size(), log2_row);   // a shape error is reported ahead of a claim's
+    secrets_claims(who, p, claims, n, points, table, pts, vals);
+    return pcs_verify_entry(who, device, ctx, root, nv.data(), nv.size(), log2_row, table.data(), pts.data(), vals.data(), n, n_queries, opening, len);
+}
+
 int hg_claims_verify(const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points, size_t n_queries,
                      const uint8_t* opening, size_t len) {
     HG_TRY
-    if (!params || !root || (len && !opening) || (n && (!claims || !points))) throw Error("hg_claims_verify: null argument");
-    Params p(*params);
-    const std::vector<uint32_t> nv = secrets_nvars(p);
-    const pcs::Shape sh = pcs::make_shape("hg_claims_verify", nv.data(), nv.size(), log2_row);
-    std::vector<uint32_t> table;
-    std::vector<uint64_t> pts, vals;
-    secrets_claims("hg_claims_verify", p, claims, n, points, table, pts, vals);
-    const std::vector<pcs::Claim> cl = pcs_claims("hg_claims_verify", sh, table.data(), pts.data(), vals.data(), n);
-    const std::string why = pcs::verify(sh, root, cl, pcs_queries("hg_claims_verify", n_queries), opening, len);
-    if (why.empty()) return 0;
-    g_last_error = why;
-    return 1;
+    return claims_verify_entry("hg_claims_verify", false, nullptr, params, root, log2_row, claims, n, points, n_queries, opening, len);
+    HG_CATCH(-1)
+}
+
+int hg_claims_verify_device(hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points,
+                            size_t n_queries, const uint8_t* opening, size_t len) {
+    HG_TRY
+    return claims_verify_entry("hg_claims_verify_device", true, ctx, params, root, log2_row, claims, n, points, n_queries, opening, len);
     HG_CATCH(-1)
 }
 

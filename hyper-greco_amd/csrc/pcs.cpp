@@ -1,5 +1,5 @@
 // Host side of the polynomial commitment (pcs.hpp): the host form of commit, the opening's transcript and byte layout (shared by
-// both forms) and the verifier, which is host only.
+// both forms), the host verifier and the pieces it shares with the device verifier (pcs.hip).
 #include "pcs.hpp"
 #include <algorithm>
 #include <memory>
@@ -121,7 +121,7 @@ void columns_host(const Commitment& cm, const std::vector<size_t>& js, u64* cols
 // ---- the transcript both sides start from
 static void put_le32(std::vector<uint8_t>& v, uint32_t x) { for (int i = 0; i < 4; i++) v.push_back((uint8_t)(x >> (8 * i))); }
 static void put_le64(std::vector<uint8_t>& v, u64 x) { for (int i = 0; i < 8; i++) v.push_back((uint8_t)(x >> (8 * i))); }
-static FsTranscript start_transcript(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q) {
+FsTranscript start_transcript(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q) {
     FsTranscript tr;
     tr.absorb = true;
     static const char tag[] = "hg-pcs-1";
@@ -140,7 +140,7 @@ static FsTranscript start_transcript(const Shape& sh, const uint8_t root[32], co
     }
     return tr;
 }
-static std::vector<E2> rho_powers(E2 rho, size_t R) {
+std::vector<E2> rho_powers(E2 rho, size_t R) {
     std::vector<E2> w(R);
     E2 x = e2_one();
     for (size_t r = 0; r < R; r++) { w[r] = x; x = e2_mul(x, rho); }
@@ -196,18 +196,38 @@ std::vector<uint8_t> open(const char* who, const Commitment& cm, const std::vect
 
 static u64 read_be64(const uint8_t* p) { u64 v; memcpy(&v, p, 8); return __builtin_bswap64(v); }
 
+// ---- shared by verify and verify_device
+std::string length_reason(const Shape& sh, size_t n_claims, size_t Q, size_t len) {
+    const size_t want = opening_bytes(sh, n_claims, Q);
+    return len == want ? "" : "pcs: the opening has " + std::to_string(len) + " bytes, " + std::to_string(want) + " expected";
+}
+void absorb_words(FsTranscript& tr, const u64* words, size_t count) {   // little-endian host: the words are their LE64 encoding
+    const uint8_t* b = reinterpret_cast<const uint8_t*>(words);
+    tr.pending.insert(tr.pending.end(), b, b + 8 * count);
+}
+std::vector<size_t> squeeze_indices(FsTranscript& tr, size_t N, size_t Q) {
+    std::vector<size_t> js(Q);
+    for (size_t q = 0; q < Q; q++) js[q] = (size_t)(tr.squeeze_f() & (u64)(N - 1));
+    return js;
+}
+std::string reason_noncanonical(size_t byte) { return "pcs: non-canonical word at byte " + std::to_string(byte); }
+std::string reason_evaluation(size_t claim) { return "pcs: evaluation mismatch at claim " + std::to_string(claim); }
+std::string reason_merkle(size_t query) { return "pcs: Merkle path mismatch at query " + std::to_string(query); }
+std::string reason_proximity(size_t query) { return "pcs: proximity mismatch at query " + std::to_string(query); }
+std::string reason_claim(size_t claim, size_t query) { return "pcs: claim " + std::to_string(claim) + " inconsistent at query " + std::to_string(query); }
+
 std::string verify(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof, size_t len) {
     const size_t C = sh.C(), N = sh.N(), R = sh.R, n = claims.size();
     const int depth = sh.depth();
     // 1. exact length
-    const size_t want = opening_bytes(sh, n, Q);
-    if (len != want) return "pcs: the opening has " + std::to_string(len) + " bytes, " + std::to_string(want) + " expected";
+    const std::string bad_len = length_reason(sh, n, Q, len);
+    if (!bad_len.empty()) return bad_len;
     // 2. every element and column word below p
     const size_t u_words = 2 * C * (n + 1), q_bytes = 8 * R + 32 * (size_t)depth;
     std::vector<E2> u((n + 1) * C);
     for (size_t i = 0; i < u_words; i++) {
         const u64 v = read_be64(proof + 8 * i);
-        if (v >= GL_P) return "pcs: non-canonical word at byte " + std::to_string(8 * i);
+        if (v >= GL_P) return reason_noncanonical(8 * i);
         if (i & 1) u[i / 2].c1 = v; else u[i / 2].c0 = v;
     }
     std::vector<u64> cols(Q * R);
@@ -215,20 +235,20 @@ std::string verify(const Shape& sh, const uint8_t root[32], const std::vector<Cl
         for (size_t r = 0; r < R; r++) {
             const size_t at = 8 * u_words + q * q_bytes + 8 * r;
             const u64 v = read_be64(proof + at);
-            if (v >= GL_P) return "pcs: non-canonical word at byte " + std::to_string(at);
+            if (v >= GL_P) return reason_noncanonical(at);
             cols[q * R + r] = v;
         }
     // 3. <u_i, eq(z_i[..c])> == y_i
     for (size_t i = 0; i < n; i++) {
         const std::vector<E2> lo = eq_table(claims[i].point.data(), (size_t)sh.c);
-        if (!e2_eq(dot_e(u.data() + (i + 1) * C, lo.data(), C), claims[i].value)) return "pcs: evaluation mismatch at claim " + std::to_string(i);
+        if (!e2_eq(dot_e(u.data() + (i + 1) * C, lo.data(), C), claims[i].value)) return reason_evaluation(i);
     }
     // the challenges
     FsTranscript tr = start_transcript(sh, root, claims, Q);
     const std::vector<E2> rho = rho_powers(tr.squeeze(), R);
-    for (const E2& x : u) { tr.absorb_read(x.c0); tr.absorb_read(x.c1); }
-    std::vector<size_t> js(Q);
-    for (size_t q = 0; q < Q; q++) js[q] = (size_t)(tr.squeeze_f() & (u64)(N - 1));
+    static_assert(sizeof(E2) == 16, "an E2 vector is read as its c0, c1 words");
+    absorb_words(tr, reinterpret_cast<const u64*>(u.data()), 2 * u.size());
+    const std::vector<size_t> js = squeeze_indices(tr, N, Q);
     // Enc(u_i): the code acts on the c0 and the c1 coordinates separately
     std::vector<u64> enc(2 * (n + 1) * N, 0);
     std::vector<std::vector<E2>> w(n);
@@ -254,16 +274,16 @@ std::string verify(const Shape& sh, const uint8_t root[32], const std::vector<Cl
             if (idx & 1) node_hash(sib + 32 * l, h, nx); else node_hash(h, sib + 32 * l, nx);
             memcpy(h, nx, 32);
         }
-        if (memcmp(h, root, 32) != 0) return "pcs: Merkle path mismatch at query " + std::to_string(q);
+        if (memcmp(h, root, 32) != 0) return reason_merkle(q);
         E2 s = e2_zero();
         for (size_t r = 0; r < R; r++) s = e2_add(s, e2_mul_f(rho[r], col[r]));
-        if (!e2_eq(s, e2(enc[js[q]], enc[N + js[q]]))) return "pcs: proximity mismatch at query " + std::to_string(q);
+        if (!e2_eq(s, e2(enc[js[q]], enc[N + js[q]]))) return reason_proximity(q);
         for (size_t i = 0; i < n; i++) {
             const u64* part = col + sh.off[claims[i].table];
             E2 t = e2_zero();
             for (size_t r = 0; r < w[i].size(); r++) t = e2_add(t, e2_mul_f(w[i][r], part[r]));
             if (!e2_eq(t, e2(enc[2 * (i + 1) * N + js[q]], enc[(2 * (i + 1) + 1) * N + js[q]])))
-                return "pcs: claim " + std::to_string(i) + " inconsistent at query " + std::to_string(q);
+                return reason_claim(i, q);
         }
     }
     return "";

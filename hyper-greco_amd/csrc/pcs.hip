@@ -1,6 +1,7 @@
 // Device form of the polynomial commitment (pcs.hpp): rows staged into the zero-padded 4C-stride matrix and encoded by the batched
 // NTT, one Keccak-f[1600] state per thread for the column hashes and the tree, the E x F row combinations of an opening through
 // the deferred-reduction accumulators, a gather of the opened columns. The handle owns the raw and the encoded matrix in HBM.
+// The verifier of an opening (verify_device) reuses the encoding and the leaf hash and adds five kernels of its own.
 #include "pcs.hpp"
 #include "prover.hpp"
 #include "gl_wide.hpp"
@@ -56,30 +57,34 @@ __global__ __launch_bounds__(PCS_TPB) void k_pcs_stage(const u64* __restrict__ r
     if (bad) atomicOr(flag, 1u);
 }
 
-// One thread per column j of the encoded matrix: Keccak256(LE64(0) || M[0][j] || .. || M[R-1][j]) -> leaves[j]. A wavefront reads
-// 64 adjacent words of a row at a time. 17 message words per permutation, the prefix word first; padding 0x01 .. 0x80.
-__global__ __launch_bounds__(PCS_TPB) void k_pcs_leaf_hash(const u64* __restrict__ M, size_t N, size_t R, u64* __restrict__ leaves) {
-    const size_t j = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
-    if (j >= N) return;
-    u64 a[25];
+// Keccak256(LE64(0) || col[0] || col[stride] || .. || col[(R-1) * stride]) into the first four words of `a`: 17 message words per
+// permutation, the prefix word first; padding 0x01 .. 0x80
+__device__ __forceinline__ void leaf_absorb(const u64* __restrict__ col, size_t stride, size_t R, u64 (&a)[25]) {
 #pragma unroll
     for (int i = 0; i < 25; i++) a[i] = 0;
     const size_t words = R + 1;                       // message words, the prefix included
     const size_t blocks = words / RATE_WORDS + 1;     // the last block holds the rest (possibly nothing) and the padding
-    const u64* col = M + j;
     for (size_t b = 0; b < blocks; b++) {
         const size_t base = b * RATE_WORDS;
 #pragma unroll
         for (int i = 0; i < RATE_WORDS; i++) {
-            const size_t idx = base + i;              // word 0 is LE64(0), word idx >= 1 is M[idx - 1][j]
+            const size_t idx = base + i;              // word 0 is LE64(0), word idx >= 1 is element idx - 1 of the column
             u64 w = 0;
-            if (idx >= 1 && idx < words) w = col[(idx - 1) * N];
+            if (idx >= 1 && idx < words) w = col[(idx - 1) * stride];
             if (idx == words) w = 0x01;
             a[i] ^= w;
         }
         if (b + 1 == blocks) a[RATE_WORDS - 1] ^= 0x8000000000000000ull;
         keccak_f(a);
     }
+}
+// One thread per column j of the encoded matrix: the leaf hash of M[0][j] .. M[R-1][j] -> leaves[j]. A wavefront reads 64 adjacent
+// words of a row at a time.
+__global__ __launch_bounds__(PCS_TPB) void k_pcs_leaf_hash(const u64* __restrict__ M, size_t N, size_t R, u64* __restrict__ leaves) {
+    const size_t j = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
+    if (j >= N) return;
+    u64 a[25];
+    leaf_absorb(M + j, N, R, a);
     u64* out = leaves + 4 * j;
     out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
 }
@@ -147,6 +152,128 @@ __global__ __launch_bounds__(PCS_TPB) void k_pcs_gather(const u64* __restrict__ 
     const size_t r = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
     if (r >= R) return;
     cols[(size_t)blockIdx.y * R + r] = M[r * N + js[blockIdx.y]];
+}
+
+// ---- the verifier of an opening (verify_device). Grids are one-dimensional throughout: Q reaches 65536, one more than a grid's y.
+// A word of the opening only ever becomes a number; every index below comes from the shape, from the host's masked j_q or from
+// table offsets the entry point validated.
+constexpr u64 PCSV_NONE = ~(u64)0;   // a cell no thread lowered: nothing failed
+__device__ __forceinline__ void cell_min(u64* cell, u64 v) { atomicMin(reinterpret_cast<unsigned long long*>(cell), (unsigned long long)v); }
+
+// Big-endian words of the opening -> native words. Word i < u_words is coordinate i & 1 of element i >> 1 of the u vectors: kept in
+// u (as E2) and scattered into row 2 * (i >> (c+1)) + (i & 1) of the matrix the NTT encodes (zeroed beforehand). The others are
+// the Q * R column words, query q at word u_words + q * q_words. cells[0] = the lowest byte offset of a word that is not below p.
+__global__ __launch_bounds__(PCS_TPB) void k_pcsv_canon(const u64* __restrict__ proof, size_t u_words, size_t Q, size_t R, size_t q_words, int c,
+                                                        u64* __restrict__ u, u64* __restrict__ cols, u64* __restrict__ enc, u64* __restrict__ cells) {
+    const size_t total = u_words + Q * R, Cm = ((size_t)1 << c) - 1;
+    u64 bad = PCSV_NONE;
+    for (size_t i = (size_t)blockIdx.x * PCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * PCS_TPB) {
+        size_t at = i;
+        if (i >= u_words) { const size_t k = i - u_words, q = k / R; at = u_words + q * q_words + (k - q * R); }
+        const u64 v = __builtin_bswap64(proof[at]);
+        if (v >= GL_P && 8 * at < bad) bad = 8 * at;
+        if (i < u_words) {
+            const size_t e = i >> 1, row = 2 * (e >> c) + (i & 1);
+            u[i] = v;
+            enc[(row << (c + 2)) + (e & Cm)] = v;
+        } else {
+            cols[i - u_words] = v;
+        }
+    }
+    if (bad != PCSV_NONE) cell_min(cells, bad);
+}
+
+// <u_i, eq(z_i[..c])> == y_i, one workgroup per claim i (blockIdx.x). eq(z, x) = prod_b (x_b ? z_b : 1 - z_b) is formed per entry:
+// a thread keeps the factor of the low eight bits of x, which its entries share. cells[1] = the lowest failing claim.
+__global__ __launch_bounds__(PCS_TPB) void k_pcsv_eval(const E2* __restrict__ u, int c, const E2* __restrict__ zlo, const E2* __restrict__ y, u64* __restrict__ cells) {
+    __shared__ E2 part[PCS_TPB];
+    const size_t C = (size_t)1 << c, i = blockIdx.x;
+    const E2* z = zlo + i * (size_t)c;
+    const E2* ui = u + (i + 1) * C;
+    const int lo = c < 8 ? c : 8;
+    E2 f = e2_one();
+    for (int b = 0; b < lo; b++) f = e2_mul(f, (threadIdx.x >> b) & 1 ? z[b] : e2_sub(e2_one(), z[b]));
+    E2 s = e2_zero();
+    for (size_t x = threadIdx.x; x < C; x += PCS_TPB) {
+        E2 g = f;
+        for (int b = 8; b < c; b++) g = e2_mul(g, (x >> b) & 1 ? z[b] : e2_sub(e2_one(), z[b]));
+        s = e2_add(s, e2_mul(ui[x], g));
+    }
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = PCS_TPB / 2; h >= 1; h >>= 1) {
+        if (threadIdx.x < h) part[threadIdx.x] = e2_add(part[threadIdx.x], part[threadIdx.x + h]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && !e2_eq(part[0], y[i])) cell_min(cells + 1, (u64)i);
+}
+
+// One thread per query: the leaf hash of its R column words -> leaves[q]
+__global__ __launch_bounds__(PCS_TPB) void k_pcsv_leaf(const u64* __restrict__ cols, size_t Q, size_t R, u64* __restrict__ leaves) {
+    const size_t q = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
+    if (q >= Q) return;
+    u64 a[25];
+    leaf_absorb(cols + q * R, 1, R, a);
+    u64* out = leaves + 4 * q;
+    out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
+}
+
+// One thread per (query q, job i): s[q][i] = sum_{r < nrows} w[woff + r] * col_q[row0 + r]. Job 0 is the proximity combination
+// (rho^r over the whole column), job 1 + i claim i's (eq(z_i[c..]) over the rows of its table). Reduced every COMBINE_CHUNK products.
+__global__ __launch_bounds__(PCS_TPB) void k_pcsv_dots(const u64* __restrict__ cols, size_t Q, size_t R, const CombineDesc* __restrict__ jobs, size_t njobs,
+                                                       const E2* __restrict__ w, E2* __restrict__ s) {
+    const size_t id = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
+    if (id >= Q * njobs) return;
+    const size_t q = id / njobs;
+    const CombineDesc job = jobs[id - q * njobs];
+    const u64* src = cols + q * R + job.row0;
+    const E2* wq = w + job.woff;
+    u64 s0 = 0, s1 = 0;
+    for (u64 r0 = 0; r0 < job.nrows; r0 += COMBINE_CHUNK) {
+        const u64 r1 = r0 + COMBINE_CHUNK < job.nrows ? r0 + COMBINE_CHUNK : job.nrows;
+        WAcc A = wacc_zero(), B = wacc_zero();
+        for (u64 r = r0; r < r1; r++) {
+            const u64 x = src[r];
+            const E2 wr = wq[r];
+            wmac2(A, x, wr.c0, B, x, wr.c1);
+        }
+        s0 = gl_add(s0, wreduce(A));
+        s1 = gl_add(s1, wreduce(B));
+    }
+    s[id] = e2(s0, s1);
+}
+
+// One thread per query, once the host has the column indices: the path from the leaf hash over the c+2 siblings (32 raw bytes
+// each behind the query's column words; bit l of j_q says on which side level l's sibling lies) against the root, then s[q][0]
+// against Enc(u_0)[j_q], then s[q][1 + i] against Enc(u_i)[j_q]. enc: rows 2i, 2i + 1 = the encoded c0, c1 coordinates of u_i.
+// cells[2] = the lowest q * (n + 2) + kind that failed: kind 0 the path, 1 proximity, 2 + i claim i.
+__global__ __launch_bounds__(PCS_TPB) void k_pcsv_query(const u64* __restrict__ proof, size_t u_words, size_t q_words, size_t Q, size_t R, int depth,
+                                                        const u64* __restrict__ leaves, const E2* __restrict__ s, const u64* __restrict__ enc, size_t n,
+                                                        const u64* __restrict__ js, const u64* __restrict__ root, u64* __restrict__ cells) {
+    const size_t q = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
+    if (q >= Q) return;
+    const size_t N = (size_t)1 << depth, j = js[q];
+    const u64* sib = proof + u_words + q * q_words + R;
+    u64 h0 = leaves[4 * q], h1 = leaves[4 * q + 1], h2 = leaves[4 * q + 2], h3 = leaves[4 * q + 3];
+    for (int l = 0; l < depth; l++) {
+        const bool right = (j >> l) & 1;   // this node is the right child
+        const u64 t0 = sib[4 * l], t1 = sib[4 * l + 1], t2 = sib[4 * l + 2], t3 = sib[4 * l + 3];
+        u64 a[25];
+        a[0] = 1;
+        a[1] = right ? t0 : h0; a[2] = right ? t1 : h1; a[3] = right ? t2 : h2; a[4] = right ? t3 : h3;
+        a[5] = right ? h0 : t0; a[6] = right ? h1 : t1; a[7] = right ? h2 : t2; a[8] = right ? h3 : t3;
+        a[9] = 0x01;
+#pragma unroll
+        for (int k = 10; k < 25; k++) a[k] = 0;
+        a[RATE_WORDS - 1] = 0x8000000000000000ull;
+        keccak_f(a);
+        h0 = a[0]; h1 = a[1]; h2 = a[2]; h3 = a[3];
+    }
+    const size_t key = q * (n + 2);
+    if (h0 != root[0] || h1 != root[1] || h2 != root[2] || h3 != root[3]) { cell_min(cells + 2, key); return; }
+    const E2* sq = s + q * (n + 1);
+    for (size_t i = 0; i <= n; i++)
+        if (!e2_eq(sq[i], e2(enc[2 * i * N + j], enc[(2 * i + 1) * N + j]))) { cell_min(cells + 2, key + 1 + i); return; }
 }
 
 Commitment::~Commitment() {
@@ -240,6 +367,119 @@ void columns_device(const Commitment& cm, const std::vector<size_t>& js, u64* co
     hip_check(hipMemcpyAsync(cols, d_cols, Q * R * 8, hipMemcpyDeviceToHost, st), "download columns");
     hip_check(hipStreamSynchronize(st), "hg_pcs_open: sync");
     hip_check(hipGetLastError(), "hg_pcs_open: launch");
+}
+
+// hg_pcs_verify_device. Everything but the last kernel needs no column index, so it is enqueued first and runs while the host
+// hashes the u_i; the indices follow on the same stream, then the three result cells come back: one synchronisation.
+std::string verify_device(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof, size_t len) {
+    const size_t C = sh.C(), N = sh.N(), R = sh.R, n = claims.size();
+    const int depth = sh.depth();
+    const std::string bad_len = length_reason(sh, n, Q, len);
+    if (!bad_len.empty()) return bad_len;
+    const size_t u_words = 2 * C * (n + 1), q_words = R + 4 * (size_t)depth, njobs = n + 1;
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->arena_reset();
+    hipStream_t st = ctx->stream;
+    // root, descriptors, values, the low coordinates of the points and the weight tables in one staged copy
+    FsTranscript tr = start_transcript(sh, root, claims, Q);
+    const std::vector<E2> rho = rho_powers(tr.squeeze(), R);
+    size_t nw = R;
+    for (const Claim& cl : claims) nw += (size_t)1 << (sh.nvars[cl.table] - sh.c);
+    const size_t desc_at = 32, y_at = desc_at + ((njobs * sizeof(CombineDesc) + 15) & ~(size_t)15), z_at = y_at + n * sizeof(E2),
+                 w_at = z_at + n * (size_t)sh.c * sizeof(E2);
+    std::vector<char> stage(w_at + nw * sizeof(E2));
+    memcpy(stage.data(), root, 32);
+    CombineDesc* hd = reinterpret_cast<CombineDesc*>(stage.data() + desc_at);
+    E2* hy = reinterpret_cast<E2*>(stage.data() + y_at);
+    E2* hz = reinterpret_cast<E2*>(stage.data() + z_at);
+    E2* hw = reinterpret_cast<E2*>(stage.data() + w_at);
+    hd[0].row0 = 0; hd[0].nrows = R; hd[0].woff = 0;
+    memcpy(hw, rho.data(), R * sizeof(E2));
+    size_t off = R;
+    for (size_t i = 0; i < n; i++) {
+        const Claim& cl = claims[i];
+        const std::vector<E2> w = eq_table(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
+        hd[i + 1].row0 = sh.off[cl.table]; hd[i + 1].nrows = w.size(); hd[i + 1].woff = off;
+        memcpy(hw + off, w.data(), w.size() * sizeof(E2));
+        off += w.size();
+        hy[i] = cl.value;
+        memcpy(hz + i * (size_t)sh.c, cl.point.data(), (size_t)sh.c * sizeof(E2));
+    }
+    const bool four_step = depth >= 8 && depth <= 16;
+    u64 *d_proof, *d_u, *d_cols, *d_enc, *d_scratch = nullptr, *d_W, *d_leaves, *d_js, *d_cells;
+    char* d_stage;
+    E2* d_s;
+    try {
+        d_proof = ctx->alloc_n<u64>(len / 8);
+        d_stage = ctx->alloc_n<char>(stage.size());
+        d_u = ctx->alloc_n<u64>(u_words);
+        d_cols = ctx->alloc_n<u64>(Q * R);
+        d_enc = ctx->alloc_n<u64>(2 * njobs * N);
+        if (four_step) d_scratch = ctx->alloc_n<u64>(2 * njobs * N);
+        d_W = ctx->alloc_n<u64>(N);
+        d_leaves = ctx->alloc_n<u64>(4 * Q);
+        d_s = ctx->alloc_n<E2>(Q * njobs);
+        d_js = ctx->alloc_n<u64>(Q);
+        d_cells = ctx->alloc_n<u64>(4);
+    } catch (const std::exception& e) {
+        throw Error(std::string("the context's arena cannot hold the opening (") + e.what() + ")");
+    }
+    struct Drain {   // an error between the first enqueue and the synchronisation must not leave copies of dead host buffers behind
+        hipStream_t st; bool armed = true;
+        ~Drain() { if (armed) (void)hipStreamSynchronize(st); }
+    } drain{st};
+    const int cls = ctx->prof_class("pcs_verify", false);
+    ctx->prof_stream = st;
+    const CombineDesc* d_jobs = reinterpret_cast<const CombineDesc*>(d_stage + desc_at);
+    const u64* d_root = reinterpret_cast<const u64*>(d_stage);
+    hip_check(hipMemcpyAsync(d_proof, proof, len, hipMemcpyHostToDevice, st), "upload opening");
+    hip_check(hipMemcpyAsync(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, st), "upload claims");
+    hip_check(hipMemsetAsync(d_cells, 0xff, 32, st), "memset");
+    hip_check(hipMemsetAsync(d_enc, 0, 2 * njobs * N * 8, st), "memset");
+    ctx->prof_begin(cls, (double)(u_words + Q * R) * 24);
+    k_pcsv_canon<<<(unsigned)std::min<size_t>(blocks_for(u_words + Q * R), 4096), PCS_TPB, 0, st>>>(d_proof, u_words, Q, R, q_words, sh.c, d_u, d_cols, d_enc, d_cells);
+    ctx->prof_end();
+    if (n) {
+        ctx->prof_begin(cls, (double)n * C * 16);
+        k_pcsv_eval<<<(unsigned)n, PCS_TPB, 0, st>>>(reinterpret_cast<const E2*>(d_u), sh.c, reinterpret_cast<const E2*>(d_stage + z_at),
+                                                     reinterpret_cast<const E2*>(d_stage + y_at), d_cells);
+        ctx->prof_end();
+    }
+    ctx->prof_begin(cls, (double)njobs * N * 64);
+    dev::powers_table(st, d_W, root_of_unity(depth), N);
+    dev::ntt_batch(st, d_enc, depth, 2 * njobs, d_W, 1, d_scratch);
+    ctx->prof_end();
+    ctx->prof_begin(cls, (double)Q * R * 8);
+    k_pcsv_leaf<<<blocks_for(Q), PCS_TPB, 0, st>>>(d_cols, Q, R, d_leaves);
+    ctx->prof_end();
+    ctx->prof_begin(cls, (double)Q * nw * 24);
+    k_pcsv_dots<<<blocks_for(Q * njobs), PCS_TPB, 0, st>>>(d_cols, Q, R, d_jobs, njobs, reinterpret_cast<const E2*>(d_stage + w_at), d_s);
+    ctx->prof_end();
+    // the host's share, beside the kernels: the u_i into the transcript, the column indices out of it
+    std::vector<u64> words(u_words);
+    for (size_t i = 0; i < u_words; i++) { u64 v; memcpy(&v, proof + 8 * i, 8); words[i] = __builtin_bswap64(v); }
+    absorb_words(tr, words.data(), u_words);
+    const std::vector<size_t> js = squeeze_indices(tr, N, Q);
+    const std::vector<u64> hj(js.begin(), js.end());
+    hip_check(hipMemcpyAsync(d_js, hj.data(), Q * 8, hipMemcpyHostToDevice, st), "upload column indices");
+    ctx->prof_begin(cls, (double)Q * (32.0 * depth + 48.0 * njobs));
+    k_pcsv_query<<<blocks_for(Q), PCS_TPB, 0, st>>>(d_proof, u_words, q_words, Q, R, depth, d_leaves, d_s, d_enc, n, d_js, d_root, d_cells);
+    ctx->prof_end();
+    u64 cells[4];
+    hip_check(hipMemcpyAsync(cells, d_cells, 32, hipMemcpyDeviceToHost, st), "download verdict");
+    const hipError_t synced = hipStreamSynchronize(st);
+    drain.armed = false;
+    hip_check(synced, "hg_pcs_verify_device: sync");
+    hip_check(hipGetLastError(), "hg_pcs_verify_device: launch");
+    ctx->prof_collect();
+    // the host's order: a non-canonical word, the lowest claim whose evaluation fails, the lowest failing query
+    if (cells[0] != PCSV_NONE) return reason_noncanonical((size_t)cells[0]);
+    if (cells[1] != PCSV_NONE) return reason_evaluation((size_t)cells[1]);
+    if (cells[2] != PCSV_NONE) {
+        const size_t q = (size_t)(cells[2] / (n + 2)), kind = (size_t)(cells[2] % (n + 2));
+        return kind == 0 ? reason_merkle(q) : kind == 1 ? reason_proximity(q) : reason_claim(kind - 2, q);
+    }
+    return "";
 }
 
 }  // namespace pcs

@@ -72,6 +72,21 @@ void columns_device(const Commitment& cm, const std::vector<size_t>& js, u64* co
 std::vector<uint8_t> open(const char* who, const Commitment& cm, const std::vector<Claim>& claims, size_t Q);
 // hg_pcs_verify: "" = accepted, else the reason
 std::string verify(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof, size_t len);
+// hg_pcs_verify_device (pcs.hip): the same decision and the same reason with the table-sized work on the context's stream; the
+// Fiat-Shamir hash over the u_i stays on the host and runs beside the kernels. Throws an Error if the arena cannot hold the opening
+std::string verify_device(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof, size_t len);
+
+// ---- what both forms of the verifier share (pcs.cpp): the length check, the transcript up to the column indices, the reasons
+std::string length_reason(const Shape& sh, size_t n_claims, size_t Q, size_t len);   // "" if the length is the opening's
+FsTranscript start_transcript(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q);
+std::vector<E2> rho_powers(E2 rho, size_t R);
+void absorb_words(FsTranscript& tr, const u64* words, size_t count);                 // the u_i as read: c0, c1 of every element
+std::vector<size_t> squeeze_indices(FsTranscript& tr, size_t N, size_t Q);           // j_q = a squeezed word & (N - 1)
+std::string reason_noncanonical(size_t byte);
+std::string reason_evaluation(size_t claim);
+std::string reason_merkle(size_t query);
+std::string reason_proximity(size_t query);
+std::string reason_claim(size_t claim, size_t query);
 
 }  // namespace pcs
 }  // namespace hg

@@ -331,7 +331,7 @@ int hg_instance_mle_batch(hg_ctx* ctx, const void* const* instances, size_t n, i
  *     5. Q column indices j_q = (a squeezed base-field challenge) & (4C - 1), duplicates kept;
  *     6. per query the R column words M[.][j_q] (8-byte big-endian) and the c+2 siblings bottom-up (32 raw bytes each).
  *     Length: exactly 16 C (n+1) + Q (8 R + 32 (c+2)) bytes.
- *   Verification (host only), in this order, the first failure is the reason in hg_last_error:
+ *   Verification (hg_pcs_verify on the host, hg_pcs_verify_device on a context), in this order, the first failure is the reason in hg_last_error:
  *     1. the exact length ("pcs: the opening has .. bytes, .. expected");  2. every element and column word below p ("pcs:
  *     non-canonical word at byte ..");  3. <u_i, eq(z_i[..c])> == y_i, claims ascending ("pcs: evaluation mismatch at claim i");
  *     4. per query, ascending: leaf hash and path reach the root ("pcs: Merkle path mismatch at query q"), sum_r rho^r col[r] ==
@@ -359,12 +359,20 @@ int hg_instance_mle_batch(hg_ctx* ctx, const void* const* instances, size_t n, i
  *   <u_i, eq(z_i[..c])>: the prover holds u_i, so the check is free.
  * hg_pcs_verify: host only, no context. -1: a null argument, a shape or a count outside the limits, a table index out of range, a
  *   non-canonical coordinate or value.
+ * hg_pcs_verify_device: hg_pcs_verify with the table-sized work on the context's stream; the decision and the reason are the host
+ *   verifier's on every input, also where several checks fail at once (the order above decides). The opening is uploaded as it
+ *   is; kernels byte-swap and range-check its words, check the evaluations, encode the u_i with the batched NTT, hash the opened
+ *   columns and form their inner products while the host hashes the u_i into the transcript; the Q column indices follow on the
+ *   same stream and a last kernel walks the paths and compares; three result words come back: one synchronisation. -1 as
+ *   hg_pcs_verify (naming this function), for a null context (".. : no context"), and if the context's arena cannot hold the
+ *   opening. It uses the context's arena like a prove: not concurrently with another call on the same context.
  * hg_secrets_commit: hg_pcs_commit of the five secret inputs of a witness handle, tables in input order s, e, k1, r1is[0] ..
  *   r1is[k-1], r2is: m = k+4, variables L, L, L, L x k, P + log2 k (L = log2 n + 1, P = log2 n).
  * hg_claims_open / hg_claims_verify: hg_pcs_open / hg_pcs_verify for an hg_input_claim array exactly as hg_verify_public* returns
  *   it (claims, n, points). Input ids map to tables 0, 1, 2 -> 0, 1, 2; 3+k+i -> 3+i; 3+2k -> 3+k; a claim on input 3 .. 3+k-1 (the
  *   public ais) or past 3+2k is an error (-1), so is a claim whose nvars is not its input's. hg_verify_public followed by
- *   hg_claims_verify against a root the encryptor published is a verification that needs no secret. */
+ *   hg_claims_verify against a root the encryptor published is a verification that needs no secret. hg_claims_verify_device is
+ *   hg_pcs_verify_device under the same mapping. */
 int hg_pcs_commit(hg_ctx* ctx, const uint64_t* const* tables, const uint32_t* nvars, size_t n_tables, size_t log2_row, void** commitment,
                   uint8_t root[32]);
 void hg_pcs_free(void* commitment);
@@ -372,11 +380,15 @@ int hg_pcs_open(hg_ctx* ctx, const void* commitment, const uint32_t* table, cons
                 size_t n_queries, uint8_t* proof, size_t cap, size_t* len);
 int hg_pcs_verify(const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table, const uint64_t* points,
                   const uint64_t* values, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len);
+int hg_pcs_verify_device(hg_ctx* ctx, const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table,
+                         const uint64_t* points, const uint64_t* values, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len);
 int hg_secrets_commit(hg_ctx* ctx, const hg_params* params, const hg_witness* w, size_t log2_row, void** commitment, uint8_t root[32]);
 int hg_claims_open(hg_ctx* ctx, const hg_params* params, const void* commitment, const void* claims, size_t n, const uint64_t* points,
                    size_t n_queries, uint8_t* opening, size_t cap, size_t* len);
 int hg_claims_verify(const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points,
                      size_t n_queries, const uint8_t* opening, size_t len);
+int hg_claims_verify_device(hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n,
+                            const uint64_t* points, size_t n_queries, const uint8_t* opening, size_t len);
 
 /* The same pair in a protocol mode that FIXES the reference's two known soundness gaps. mode bits:
  *   1  absorbing transcript: write_felt / read_felt also hash the element - the rule of the in-tree plonkish-trait writer of

@@ -4,8 +4,9 @@ ALTERNATED on one synthetic witness and the claims hg_verify_public_device leave
 each leg, --reps timed calls each:
   commit_dev / commit_host   hg_secrets_commit with a context / without (upload or copy of the tables, encoding, column hashes, tree)
   open_dev / open_host       hg_claims_open of those claims on the commitment of that form (default 241 queries)
-  verify                     hg_claims_verify of the opening (host only)
-Prints the opening's bytes, median and range per leg, and whether the whole range of commit_dev lies below that of commit_host.
+  verify_dev / verify_host   hg_claims_verify_device / hg_claims_verify of the opening: the whole call, upload included
+Prints the opening's bytes, median and range per leg, and for the commit and the verify pair whether the whole range of the device
+form lies below that of the host form.
 Usage: pcs_times.py [n k] [--reps 5]"""
 import argparse
 import os
@@ -43,14 +44,15 @@ def main():
 
     legs = [("commit_dev", lambda: commit("dev")), ("commit_host", lambda: commit("host")),
             ("open_dev", lambda: held["dev"].open_claims(bfv.params, claims)), ("open_host", lambda: held["host"].open_claims(bfv.params, claims)),
-            ("verify", lambda: hg.claims_verify(bfv.params, held["host"].root, claims, opening))]
+            ("verify_dev", lambda: hg.claims_verify(bfv.params, held["host"].root, claims, opening, ctx=ctx)),
+            ("verify_host", lambda: hg.claims_verify(bfv.params, held["host"].root, claims, opening))]
     times = {name: [] for name, _ in legs}
     for rep in range(a.reps + 1):   # rep 0: the warm-up call of each leg
         for name, fn in legs:
             t0 = time.perf_counter()
             out = fn()
             dt = (time.perf_counter() - t0) * 1e3
-            if name == "verify":
+            if name.startswith("verify"):
                 assert out == (True, ""), out
             if rep:
                 times[name].append(dt)
@@ -61,13 +63,14 @@ def main():
     for name, _ in legs:
         t = times[name]
         print("%-11s median %.2f ms, range %.2f .. %.2f ms (%s)" % (name, statistics.median(t), min(t), max(t), " ".join("%.2f" % x for x in t)))
-    dev, host = times["commit_dev"], times["commit_host"]
-    if max(dev) < min(host):
-        print("commit_dev is faster than commit_host: its whole range lies below the host form's")
-    elif min(dev) > max(host):
-        print("commit_dev is SLOWER than commit_host: its whole range lies above the host form's")
-    else:
-        print("commit_dev and commit_host overlap: no difference shown")
+    for leg in ("commit", "verify"):
+        dev, host = times[leg + "_dev"], times[leg + "_host"]
+        if max(dev) < min(host):
+            print("%s_dev is faster than %s_host: its whole range lies below the host form's" % (leg, leg))
+        elif min(dev) > max(host):
+            print("%s_dev is SLOWER than %s_host: its whole range lies above the host form's" % (leg, leg))
+        else:
+            print("%s_dev and %s_host overlap: no difference shown" % (leg, leg))
     for h in held.values():
         h.free()
     pk.free()
