@@ -52,6 +52,7 @@ EXPORTS = [
     "hg_instance_from_ciphertext", "hg_instance_from_witness", "hg_instance_free", "hg_instance_coeffs", "hg_instance_get", "hg_pk_claim_shape", "hg_verify_public", "hg_verify_public_device", "hg_verify_public_batch", "hg_claims_settle", "hg_instance_mle", "hg_instance_mle_batch",
     "hg_pcs_commit", "hg_pcs_free", "hg_pcs_open", "hg_pcs_verify", "hg_secrets_commit", "hg_claims_open", "hg_claims_verify",
     "hg_pcs_verify_device", "hg_claims_verify_device",
+    "hg_pcs_commit_bn254", "hg_pcs_open_bn254", "hg_pcs_verify_bn254", "hg_secrets_commit_bn254", "hg_claims_open_bn254", "hg_claims_verify_bn254",
     "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_mle_eval",
     "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_verify_public_bn254", "hg_verify_public_device_bn254", "hg_verify_public_batch_bn254", "hg_claims_settle_bn254", "hg_instance_mle_bn254", "hg_instance_mle_batch_bn254", "hg_prove_encryptions_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
 ]
@@ -185,9 +186,9 @@ class Context:
     def profile_reset(self):
         lib().hg_profile_reset(self.h)
 
-    def profile_get(self):
-        arr = (HgKernelStat * 32)()
-        n = lib().hg_profile_get(self.h, arr, 32)
+    def profile_get(self, cap=32):
+        arr = (HgKernelStat * cap)()
+        n = lib().hg_profile_get(self.h, arr, cap)
         return [dict(name=arr[i].name.decode(), launches=int(arr[i].launches), total_ms=arr[i].total_ms, algo_bytes=arr[i].algo_bytes, model_bytes=arr[i].model_bytes, hbm_bytes=arr[i].hbm_bytes)
                 for i in range(n)]
 
@@ -1131,6 +1132,8 @@ def _pcs_protos():
     L.hg_claims_verify.argtypes = [C.POINTER(HgParams), C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, u64p, C.c_size_t, C.c_char_p, C.c_size_t]
     L.hg_pcs_verify_device.argtypes = [C.c_void_p] + L.hg_pcs_verify.argtypes
     L.hg_claims_verify_device.argtypes = [C.c_void_p] + L.hg_claims_verify.argtypes
+    for name in ("hg_pcs_commit", "hg_pcs_open", "hg_pcs_verify", "hg_secrets_commit", "hg_claims_open", "hg_claims_verify"):   # the same C types, 4 words an element
+        getattr(L, name + "_bn254").argtypes = getattr(L, name).argtypes
     return L
 
 
@@ -1143,11 +1146,57 @@ def _pcs_claim_arrays(claims):
     return table, pts, vals
 
 
-class Commitment:
-    """hg_pcs_commit / hg_secrets_commit: the handle of a polynomial commitment (host form: ctx None) and its 32-byte root."""
+def _pcs_claim_arrays_bn254(claims):
+    """claims: [(table, point (Python ints below r), value)] -> ctypes / numpy arguments, 4 limbs per element"""
+    n = len(claims)
+    table = (C.c_uint32 * max(n, 1))(*[int(c[0]) for c in claims])
+    pts = Context._fr_pack([x for c in claims for x in c[1]] or [0])
+    vals = Context._fr_pack([c[2] for c in claims] or [0])
+    return table, pts, vals
 
-    def __init__(self, handle, root, ctx, nvars, log2_row):
-        self.h, self.root, self.ctx, self.nvars, self.log2_row = handle, root, ctx, list(nvars), log2_row
+
+def _fr_table(t):
+    """a table of Fr elements as 4 little-endian u64 limbs each: a u64 array of limbs as it is, anything else as Python ints"""
+    if isinstance(t, np.ndarray) and t.dtype == np.uint64:
+        return np.ascontiguousarray(t).reshape(-1)
+    return Context._fr_pack(t)
+
+
+def pcs_opening_bytes_bn254(nvars, n_claims, n_queries=0, log2_row=0):
+    """32 C (n+1) + Q (32 R + 32 (c+2)): the exact length of an opening over BN254."""
+    c = pcs_row_log2(nvars, log2_row)
+    rows = sum(1 << (v - c) for v in nvars)
+    return 32 * (1 << c) * (n_claims + 1) + (n_queries or PCS_DEFAULT_QUERIES) * (32 * rows + 32 * (c + 2))
+
+
+class Commitment:
+    """hg_pcs_commit / hg_secrets_commit and their _bn254 forms: the handle of a polynomial commitment (host form: ctx None) and its
+    32-byte root. field is "goldilocks" or "bn254"; open and open_claims call the entry of the handle's field."""
+
+    def __init__(self, handle, root, ctx, nvars, log2_row, field="goldilocks"):
+        self.h, self.root, self.ctx, self.nvars, self.log2_row, self.field = handle, root, ctx, list(nvars), log2_row, field
+
+    @classmethod
+    def commit_bn254(cls, ctx, tables, log2_row=0):
+        """hg_pcs_commit_bn254. tables: per table 2^v_t elements, Python ints below r or a numpy u64 array of 4 limbs each."""
+        L = _pcs_protos()
+        tabs = [_fr_table(t) for t in tables]
+        nvars = [(t.size // 4).bit_length() - 1 for t in tabs]
+        ptrs = (u64p * len(tabs))(*[_ptr(t) for t in tabs])
+        nv = (C.c_uint32 * len(tabs))(*nvars)
+        h, root = C.c_void_p(), (C.c_uint8 * 32)()
+        _check(L.hg_pcs_commit_bn254(ctx.h if ctx is not None else None, ptrs, nv, len(tabs), log2_row, C.byref(h), root))
+        return cls(h, bytes(root), ctx, nvars, pcs_row_log2(nvars, log2_row), "bn254")
+
+    @classmethod
+    def secrets_bn254(cls, ctx, params, witness, log2_row=0):
+        """hg_secrets_commit_bn254: the five secret inputs of a witness handle, every word lifted into Fr by the signed rule."""
+        L = _pcs_protos()
+        h, root = C.c_void_p(), (C.c_uint8 * 32)()
+        _check(L.hg_secrets_commit_bn254(ctx.h if ctx is not None else None, C.byref(params), witness.h, log2_row, C.byref(h), root))
+        lg = params.n.bit_length() - 1
+        nvars = [lg + 1] * (3 + params.k) + [lg + params.k.bit_length() - 1]
+        return cls(h, bytes(root), ctx, nvars, pcs_row_log2(nvars, log2_row), "bn254")
 
     @classmethod
     def commit(cls, ctx, tables, log2_row=0):
@@ -1172,20 +1221,26 @@ class Commitment:
         return cls(h, bytes(root), ctx, nvars, pcs_row_log2(nvars, log2_row))
 
     def open(self, claims, n_queries=0):
-        """hg_pcs_open: claims = [(table, point words, (v0, v1))] -> the opening bytes."""
+        """hg_pcs_open: claims = [(table, point words, (v0, v1))] -> the opening bytes. On a BN254 handle hg_pcs_open_bn254:
+        claims = [(table, point (Python ints below r), value)]."""
         L = _pcs_protos()
-        cap = pcs_opening_bytes(self.nvars, len(claims), n_queries, self.log2_row)
+        bn = self.field == "bn254"
+        cap = (pcs_opening_bytes_bn254 if bn else pcs_opening_bytes)(self.nvars, len(claims), n_queries, self.log2_row)
         buf, ln = (C.c_uint8 * cap)(), C.c_size_t(0)
-        table, pts, vals = _pcs_claim_arrays(claims)
-        _check(L.hg_pcs_open(self.ctx.h if self.ctx is not None else None, self.h, table, _ptr(pts), _ptr(vals), len(claims), n_queries, buf, cap, C.byref(ln)))
+        table, pts, vals = (_pcs_claim_arrays_bn254 if bn else _pcs_claim_arrays)(claims)
+        fn = L.hg_pcs_open_bn254 if bn else L.hg_pcs_open
+        _check(fn(self.ctx.h if self.ctx is not None else None, self.h, table, _ptr(pts), _ptr(vals), len(claims), n_queries, buf, cap, C.byref(ln)))
         return bytes(memoryview(buf)[:ln.value])
 
     def open_claims(self, params, claims, n_queries=0):
-        """hg_claims_open: the opening of an InputClaims (what verify_public returns) against a Commitment.secrets handle."""
+        """hg_claims_open: the opening of an InputClaims (what verify_public returns) against a Commitment.secrets handle. On a BN254
+        handle hg_claims_open_bn254 of an InputClaimsBn254 (what verify_public_bn254 returns)."""
         L = _pcs_protos()
-        cap = pcs_opening_bytes(self.nvars, claims.n, n_queries, self.log2_row)
+        bn = self.field == "bn254"
+        cap = (pcs_opening_bytes_bn254 if bn else pcs_opening_bytes)(self.nvars, claims.n, n_queries, self.log2_row)
         buf, ln = (C.c_uint8 * cap)(), C.c_size_t(0)
-        _check(L.hg_claims_open(self.ctx.h if self.ctx is not None else None, C.byref(params), self.h, claims.claims, claims.n, _ptr(claims.points), n_queries, buf, cap,
+        fn = L.hg_claims_open_bn254 if bn else L.hg_claims_open
+        _check(fn(self.ctx.h if self.ctx is not None else None, C.byref(params), self.h, claims.claims, claims.n, _ptr(claims.points), n_queries, buf, cap,
                                 C.byref(ln)))
         return bytes(memoryview(buf)[:ln.value])
 
@@ -1218,6 +1273,26 @@ def claims_verify(params, root, claims, opening, n_queries=0, log2_row=0, ctx=No
     L = _pcs_protos()
     args = (C.byref(params), bytes(root), log2_row, claims.claims, claims.n, _ptr(claims.points), n_queries, bytes(opening), len(opening))
     rc = L.hg_claims_verify(*args) if ctx is None else L.hg_claims_verify_device(ctx.h, *args)
+    if rc < 0:
+        raise HgError(L.hg_last_error().decode())
+    return rc == 0, ("" if rc == 0 else L.hg_last_error().decode())
+
+
+def pcs_verify_bn254(root, nvars, claims, proof, n_queries=0, log2_row=0):
+    """hg_pcs_verify_bn254 (host only): (accepted, reason). claims as Commitment.open takes them on a BN254 handle."""
+    L = _pcs_protos()
+    nv = (C.c_uint32 * len(nvars))(*nvars)
+    table, pts, vals = _pcs_claim_arrays_bn254(claims)
+    rc = L.hg_pcs_verify_bn254(bytes(root), nv, len(nvars), log2_row, table, _ptr(pts), _ptr(vals), len(claims), n_queries, bytes(proof), len(proof))
+    if rc < 0:
+        raise HgError(L.hg_last_error().decode())
+    return rc == 0, ("" if rc == 0 else L.hg_last_error().decode())
+
+
+def claims_verify_bn254(params, root, claims, opening, n_queries=0, log2_row=0):
+    """hg_claims_verify_bn254: an InputClaimsBn254 against the root of hg_secrets_commit_bn254: (accepted, reason)."""
+    L = _pcs_protos()
+    rc = L.hg_claims_verify_bn254(C.byref(params), bytes(root), log2_row, claims.claims, claims.n, _ptr(claims.points), n_queries, bytes(opening), len(opening))
     if rc < 0:
         raise HgError(L.hg_last_error().decode())
     return rc == 0, ("" if rc == 0 else L.hg_last_error().decode())

@@ -29,6 +29,8 @@
 #include "prover.hpp"
 #include "kernels.hpp"
 #include "verifier_batch.hpp"
+#include "pcs_bn254.hpp"
+#include "pcs_keccak.hpp"
 
 namespace hg {
 namespace bn {
@@ -1787,6 +1789,21 @@ __global__ void k_bn_scale(Fr* __restrict__ a, Fr c, size_t n) {
     if (i < n) a[i] = fr_mul(a[i], c);
 }
 
+// The batched transform on device pointers (pcs_bn254.hpp states the contract): what the commitment's encoding calls
+__global__ void k_bn_scale_into(const Fr* __restrict__ in, Fr* __restrict__ out, Fr c, int scaled, size_t n) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = scaled ? fr_mul(in[i], c) : in[i];
+}
+void ntt_batch_dev(hipStream_t st, Fr* a, Fr* tmp, const Fr* W, int log2n, size_t batch, const Fr* scale) {
+    const Fr sc = scale ? *scale : fr_zero();
+    if (log2n >= 8 && log2n <= 16 && batch > 65535) throw Error("bn254: more than 65535 transforms in one four-step batch");
+    if (ntt4_dev(st, a, tmp, W, log2n, scale != nullptr, sc, batch)) return;
+    const size_t total = batch << log2n, th = total / 2;
+    k_bn_bitrev<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(a, tmp, log2n, total);
+    for (int s = 0; s < log2n; s++) k_bn_ntt_stage<<<(unsigned)((th + 255) / 256), 256, 0, st>>>(tmp, W, log2n, s, th);
+    k_bn_scale_into<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(tmp, a, sc, scale ? 1 : 0, total);
+}
+
 // 2^28-th root of unity of bn256::Fr = 7^((r-1)/2^28) (halo2curves ROOT_OF_UNITY, S = 28; checked: order exactly 2^28)
 static Fr fr_root_of_unity(int log2n) {
     if (log2n > 28) throw Error("bn254: two-adicity is 28");
@@ -1860,6 +1877,7 @@ static void lasso_prove_bn254_impl(hg_ctx* ctx, const hg_pk* pk, const u64* in4,
 #include "bn254_encpipe.inc"
 #include "bn254_verify.inc"
 #include "bn254_verify_batch.inc"
+#include "bn254_pcs.inc"
 
 // ---- LassoNode::prove_claim_reduction over Fr [REF lasso/src/lasso.rs:57-114] -------------------------------------------
 // The limb split and the counters are integer work on the low limb (fe_to_bits_le truncates to at most 63 bits,

@@ -11,6 +11,7 @@
 #include <tuple>
 #include "prover.hpp"
 #include "pcs.hpp"
+#include "pcs_bn254.hpp"
 
 // BN254 slice (bn254.hip)
 namespace hg { namespace bn {
@@ -1815,6 +1816,7 @@ void hg_pcs_free(void* commitment) { delete static_cast<pcs::Commitment*>(commit
 
 static int pcs_open_entry(const char* who, hg_ctx* ctx, const pcs::Commitment* cm, const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n_claims,
                           size_t n_queries, uint8_t* proof, size_t cap, size_t* len) {
+    if (cm->field != pcs::GOLDILOCKS) throw Error(std::string(who) + ": the commitment is over BN254: open it with the _bn254 entry");
     if (cm->ctx != ctx) throw Error(std::string(who) + ": the commitment was made " + (cm->ctx ? "on a device context: pass that context" : "by the host form: pass no context"));
     const std::vector<pcs::Claim> cl = pcs_claims(who, cm->sh, table, points, values, n_claims);
     pcs_emit(who, pcs::open(who, *cm, cl, pcs_queries(who, n_queries)), proof, cap, len);
@@ -1902,6 +1904,7 @@ int hg_claims_open(hg_ctx* ctx, const hg_params* params, const void* commitment,
     if (!params || !commitment || !opening || !len || (n && (!claims || !points))) throw Error("hg_claims_open: null argument");
     Params p(*params);
     const pcs::Commitment* cm = static_cast<const pcs::Commitment*>(commitment);
+    if (cm->field != pcs::GOLDILOCKS) throw Error("hg_claims_open: the commitment is over BN254: open it with the _bn254 entry");
     const std::vector<uint32_t> nv = secrets_nvars(p);
     if (cm->sh.nvars.size() != nv.size() || !std::equal(nv.begin(), nv.end(), cm->sh.nvars.begin(), [](uint32_t a, int b) { return (int)a == b; }))
         throw Error("hg_claims_open: the commitment is not hg_secrets_commit's for these parameters");
@@ -1935,6 +1938,152 @@ int hg_claims_verify_device(hg_ctx* ctx, const hg_params* params, const uint8_t 
                             size_t n_queries, const uint8_t* opening, size_t len) {
     HG_TRY
     return claims_verify_entry("hg_claims_verify_device", true, ctx, params, root, log2_row, claims, n, points, n_queries, opening, len);
+    HG_CATCH(-1)
+}
+
+// ---- the same layer over bn256::Fr (pcs_bn254.hpp): an element crosses as 4 canonical words
+static std::vector<bn::PcsClaim> pcs_claims_bn254(const char* who, const pcs::Shape& sh, const uint32_t* table, const uint64_t* points4, const uint64_t* values4, size_t n) {
+    const std::string w(who);
+    if (n > pcs::MAX_CLAIMS) throw Error(w + ": more than " + std::to_string(pcs::MAX_CLAIMS) + " claims");
+    std::vector<bn::PcsClaim> cl(n);
+    size_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (table[i] >= sh.nvars.size()) throw Error(w + ": claim " + std::to_string(i) + " names table " + std::to_string(table[i]) + " of " + std::to_string(sh.nvars.size()));
+        cl[i].table = table[i];
+        cl[i].point.resize((size_t)sh.nvars[table[i]]);
+        for (bn::Fr& x : cl[i].point) { memcpy(x.l, points4 + 4 * at, 32); at++; }
+        memcpy(cl[i].value.l, values4 + 4 * i, 32);
+        for (const bn::Fr& x : cl[i].point) if (bn::fr_geq_p(x)) throw Error(w + ": claim " + std::to_string(i) + ": non-canonical coordinate");
+        if (bn::fr_geq_p(cl[i].value)) throw Error(w + ": claim " + std::to_string(i) + ": non-canonical value");
+    }
+    return cl;
+}
+// hg_input_claim_bn254 array -> (table, points, values) of the commitment over the secret inputs: the mapping of secrets_claims
+static void secrets_claims_bn254(const char* who, const Params& p, const void* claims, size_t n, const uint64_t* points4, std::vector<uint32_t>& table,
+                                 std::vector<uint64_t>& pts, std::vector<uint64_t>& vals) {
+    const std::string w(who);
+    if (n > pcs::MAX_CLAIMS) throw Error(w + ": more than " + std::to_string(pcs::MAX_CLAIMS) + " claims");
+    const hg_input_claim_bn254* in = static_cast<const hg_input_claim_bn254*>(claims);
+    const std::vector<uint32_t> nv = secrets_nvars(p);
+    const uint32_t k = (uint32_t)p.k;
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t id = in[i].input;
+        uint32_t t;
+        if (id < 3) t = id;
+        else if (id >= 3 + k && id < 3 + 2 * k) t = id - k;
+        else if (id == 3 + 2 * k) t = 3 + k;
+        else throw Error(w + ": claim " + std::to_string(i) + " is on input " + std::to_string(id) + ", which is not a secret input (0, 1, 2, " + std::to_string(3 + k) + " .. " + std::to_string(3 + 2 * k) + ")");
+        if (in[i].nvars != nv[t]) throw Error(w + ": claim " + std::to_string(i) + " has " + std::to_string(in[i].nvars) + " coordinates, input " + std::to_string(id) + " has " + std::to_string(nv[t]) + " variables");
+        table.push_back(t);
+        pts.insert(pts.end(), points4 + 4 * in[i].point_off, points4 + 4 * (in[i].point_off + in[i].nvars));
+        vals.insert(vals.end(), in[i].value, in[i].value + 4);
+    }
+}
+
+int hg_pcs_commit_bn254(hg_ctx* ctx, const uint64_t* const* tables4, const uint32_t* nvars, size_t n_tables, size_t log2_row, void** commitment, uint8_t root[32]) {
+    HG_TRY
+    if (commitment) *commitment = nullptr;
+    if (!tables4 || !nvars || !commitment || !root) throw Error("hg_pcs_commit_bn254: null argument");
+    const pcs::Shape sh = pcs::make_shape("hg_pcs_commit_bn254", nvars, n_tables, log2_row);
+    for (size_t t = 0; t < n_tables; t++) if (!tables4[t]) throw Error("hg_pcs_commit_bn254: null table " + std::to_string(t));
+    pcs::Commitment* cm = ctx ? bn::pcs_commit_device("hg_pcs_commit_bn254", ctx, sh, tables4, false) : bn::pcs_commit_host("hg_pcs_commit_bn254", sh, tables4, false);
+    memcpy(root, cm->root(), 32);
+    *commitment = cm;
+    return 0;
+    HG_CATCH(-1)
+}
+
+static int pcs_open_entry_bn254(const char* who, hg_ctx* ctx, const pcs::Commitment* cm, const uint32_t* table, const uint64_t* points4, const uint64_t* values4,
+                                size_t n_claims, size_t n_queries, uint8_t* proof, size_t cap, size_t* len) {
+    if (cm->ctx != ctx) throw Error(std::string(who) + ": the commitment was made " + (cm->ctx ? "on a device context: pass that context" : "by the host form: pass no context"));
+    const std::vector<bn::PcsClaim> cl = pcs_claims_bn254(who, cm->sh, table, points4, values4, n_claims);
+    pcs_emit(who, bn::pcs_open(who, *cm, cl, pcs_queries(who, n_queries)), proof, cap, len);
+    return 0;
+}
+
+int hg_pcs_open_bn254(hg_ctx* ctx, const void* commitment, const uint32_t* table, const uint64_t* points4, const uint64_t* values4, size_t n_claims, size_t n_queries,
+                      uint8_t* proof, size_t cap, size_t* len) {
+    HG_TRY
+    if (len) *len = 0;
+    if (!commitment || !proof || !len || (n_claims && (!table || !points4 || !values4))) throw Error("hg_pcs_open_bn254: null argument");
+    const pcs::Commitment* cm = static_cast<const pcs::Commitment*>(commitment);
+    if (cm->field != pcs::BN254) throw Error("hg_pcs_open_bn254: the commitment is over Goldilocks: open it with hg_pcs_open");
+    return pcs_open_entry_bn254("hg_pcs_open_bn254", ctx, cm, table, points4, values4, n_claims, n_queries, proof, cap, len);
+    HG_CATCH(-1)
+}
+
+static int pcs_verify_entry_bn254(const char* who, const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table,
+                                  const uint64_t* points4, const uint64_t* values4, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
+    const std::string w(who);
+    if (!root || !nvars || (len && !proof) || (n_claims && (!table || !points4 || !values4))) throw Error(w + ": null argument");
+    const pcs::Shape sh = pcs::make_shape(who, nvars, n_tables, log2_row);
+    const std::vector<bn::PcsClaim> cl = pcs_claims_bn254(who, sh, table, points4, values4, n_claims);
+    const std::string why = bn::pcs_verify(sh, root, cl, pcs_queries(who, n_queries), proof, len);
+    if (why.empty()) return 0;
+    g_last_error = why;
+    return 1;
+}
+
+int hg_pcs_verify_bn254(const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table, const uint64_t* points4,
+                        const uint64_t* values4, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
+    HG_TRY
+    return pcs_verify_entry_bn254("hg_pcs_verify_bn254", root, nvars, n_tables, log2_row, table, points4, values4, n_claims, n_queries, proof, len);
+    HG_CATCH(-1)
+}
+
+int hg_secrets_commit_bn254(hg_ctx* ctx, const hg_params* params, const hg_witness* w, size_t log2_row, void** commitment, uint8_t root[32]) {
+    HG_TRY
+    if (commitment) *commitment = nullptr;
+    if (!params || !w || !commitment || !root) throw Error("hg_secrets_commit_bn254: null argument");
+    Params p(*params);
+    const size_t SZ = p.SZ(), k = (size_t)p.k;
+    const Witness& v = w->w;
+    if (w->params.n != params->n || w->params.k != params->k || v.s.size() != SZ || v.e.size() != SZ || v.k1.size() != SZ || v.r1is.size() != k * SZ ||
+        v.r2is.size() != k * p.PZ())
+        throw Error("hg_secrets_commit_bn254: the witness was built for other parameters");
+    const std::vector<uint32_t> nv = secrets_nvars(p);
+    std::vector<const uint64_t*> tabs = {v.s.data(), v.e.data(), v.k1.data()};
+    for (size_t i = 0; i < k; i++) tabs.push_back(v.r1is.data() + i * SZ);
+    tabs.push_back(v.r2is.data());
+    const pcs::Shape sh = pcs::make_shape("hg_secrets_commit_bn254", nv.data(), nv.size(), log2_row);
+    // the witness words are lifted into Fr by the signed rule (the table hg_claims_settle_bn254 evaluates)
+    pcs::Commitment* cm = ctx ? bn::pcs_commit_device("hg_secrets_commit_bn254", ctx, sh, tabs.data(), true) : bn::pcs_commit_host("hg_secrets_commit_bn254", sh, tabs.data(), true);
+    memcpy(root, cm->root(), 32);
+    *commitment = cm;
+    return 0;
+    HG_CATCH(-1)
+}
+
+int hg_claims_open_bn254(hg_ctx* ctx, const hg_params* params, const void* commitment, const void* claims, size_t n, const uint64_t* points4, size_t n_queries,
+                         uint8_t* opening, size_t cap, size_t* len) {
+    HG_TRY
+    if (len) *len = 0;
+    if (!params || !commitment || !opening || !len || (n && (!claims || !points4))) throw Error("hg_claims_open_bn254: null argument");
+    Params p(*params);
+    const pcs::Commitment* cm = static_cast<const pcs::Commitment*>(commitment);
+    if (cm->field != pcs::BN254) throw Error("hg_claims_open_bn254: the commitment is over Goldilocks: open it with hg_claims_open");
+    const std::vector<uint32_t> nv = secrets_nvars(p);
+    if (cm->sh.nvars.size() != nv.size() || !std::equal(nv.begin(), nv.end(), cm->sh.nvars.begin(), [](uint32_t a, int b) { return (int)a == b; }))
+        throw Error("hg_claims_open_bn254: the commitment is not hg_secrets_commit_bn254's for these parameters");
+    std::vector<uint32_t> table;
+    std::vector<uint64_t> pts, vals;
+    secrets_claims_bn254("hg_claims_open_bn254", p, claims, n, points4, table, pts, vals);
+    return pcs_open_entry_bn254("hg_claims_open_bn254", ctx, cm, table.data(), pts.data(), vals.data(), n, n_queries, opening, cap, len);
+    HG_CATCH(-1)
+}
+
+int hg_claims_verify_bn254(const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points4, size_t n_queries,
+                           const uint8_t* opening, size_t len) {
+    HG_TRY
+    const char* who = "hg_claims_verify_bn254";
+    if (!params || !root || (len && !opening) || (n && (!claims || !points4))) throw Error(std::string(who) + ": null argument");
+    Params p(*params);
+    const std::vector<uint32_t> nv = secrets_nvars(p);
+    std::vector<uint32_t> table;
+    std::vector<uint64_t> pts, vals;
+    (void)pcs::make_shape(who, nv.data(), nv.size(), log2_row);   // a shape error is reported ahead of a claim's
+    secrets_claims_bn254(who, p, claims, n, points4, table, pts, vals);
+    return pcs_verify_entry_bn254(who, root, nv.data(), nv.size(), log2_row, table.data(), pts.data(), vals.data(), n, n_queries, opening, len);
     HG_CATCH(-1)
 }
 

@@ -197,10 +197,10 @@ std::vector<uint8_t> open(const char* who, const Commitment& cm, const std::vect
 static u64 read_be64(const uint8_t* p) { u64 v; memcpy(&v, p, 8); return __builtin_bswap64(v); }
 
 // ---- shared by verify and verify_device
-std::string length_reason(const Shape& sh, size_t n_claims, size_t Q, size_t len) {
-    const size_t want = opening_bytes(sh, n_claims, Q);
+std::string length_reason(size_t len, size_t want) {
     return len == want ? "" : "pcs: the opening has " + std::to_string(len) + " bytes, " + std::to_string(want) + " expected";
 }
+std::string length_reason(const Shape& sh, size_t n_claims, size_t Q, size_t len) { return length_reason(len, opening_bytes(sh, n_claims, Q)); }
 void absorb_words(FsTranscript& tr, const u64* words, size_t count) {   // little-endian host: the words are their LE64 encoding
     const uint8_t* b = reinterpret_cast<const uint8_t*>(words);
     tr.pending.insert(tr.pending.end(), b, b + 8 * count);

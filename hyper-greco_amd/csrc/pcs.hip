@@ -5,43 +5,12 @@
 #include "pcs.hpp"
 #include "prover.hpp"
 #include "gl_wide.hpp"
+#include "pcs_keccak.hpp"
 
 namespace hg {
 namespace pcs {
 
 constexpr int PCS_TPB = 256;
-
-// ---- Keccak-f[1600], the whole state in registers: 24 rounds unrolled, every lane index a compile-time constant (a run-time index
-// would put the state into scratch memory)
-__device__ constexpr u64 KRC[24] = {
-    0x0000000000000001ull, 0x0000000000008082ull, 0x800000000000808aull, 0x8000000080008000ull, 0x000000000000808bull, 0x0000000080000001ull,
-    0x8000000080008081ull, 0x8000000000008009ull, 0x000000000000008aull, 0x0000000000000088ull, 0x0000000080008009ull, 0x000000008000000aull,
-    0x000000008000808bull, 0x800000000000008bull, 0x8000000000008089ull, 0x8000000000008003ull, 0x8000000000008002ull, 0x8000000000000080ull,
-    0x000000000000800aull, 0x800000008000000aull, 0x8000000080008081ull, 0x8000000000008080ull, 0x0000000080000001ull, 0x8000000080008008ull};
-__device__ constexpr int KROT[25] = {0, 1, 62, 28, 27, 36, 44, 6, 55, 20, 3, 10, 43, 25, 39, 41, 45, 15, 21, 8, 18, 2, 61, 56, 14};   // rho offsets, lane x + 5y
-__device__ __forceinline__ u64 krotl(u64 v, int s) { return s ? (v << s) | (v >> (64 - s)) : v; }
-__device__ __forceinline__ void keccak_f(u64 (&a)[25]) {
-#pragma unroll
-    for (int rd = 0; rd < 24; rd++) {
-        u64 c[5], d[5], b[25];
-#pragma unroll
-        for (int x = 0; x < 5; x++) c[x] = a[x] ^ a[x + 5] ^ a[x + 10] ^ a[x + 15] ^ a[x + 20];
-#pragma unroll
-        for (int x = 0; x < 5; x++) d[x] = c[(x + 4) % 5] ^ krotl(c[(x + 1) % 5], 1);
-#pragma unroll
-        for (int i = 0; i < 25; i++) a[i] ^= d[i % 5];
-#pragma unroll
-        for (int x = 0; x < 5; x++)
-#pragma unroll
-            for (int y = 0; y < 5; y++) b[y + 5 * ((2 * x + 3 * y) % 5)] = krotl(a[x + 5 * y], KROT[x + 5 * y]);
-#pragma unroll
-        for (int y = 0; y < 5; y++)
-#pragma unroll
-            for (int x = 0; x < 5; x++) a[x + 5 * y] = b[x + 5 * y] ^ (~b[(x + 1) % 5 + 5 * y] & b[(x + 2) % 5 + 5 * y]);
-        a[0] ^= KRC[rd];
-    }
-}
-constexpr int RATE_WORDS = 17;   // Keccak-256: 136 bytes
 
 // M[r][j] = j < C ? rows[r][j] : 0 ahead of the encoding; a word that is not below p sets *flag
 __global__ __launch_bounds__(PCS_TPB) void k_pcs_stage(const u64* __restrict__ rows, u64* __restrict__ M, size_t R, int c, unsigned* __restrict__ flag) {
@@ -89,20 +58,6 @@ __global__ __launch_bounds__(PCS_TPB) void k_pcs_leaf_hash(const u64* __restrict
     out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
 }
 
-__device__ __forceinline__ void merkle_node(const u64* below, u64* here, size_t i) {
-    u64 a[25];
-    const u64* in = below + 8 * i;   // left || right
-    a[0] = 1;
-#pragma unroll
-    for (int k = 0; k < 8; k++) a[1 + k] = in[k];
-    a[9] = 0x01;
-#pragma unroll
-    for (int k = 10; k < 25; k++) a[k] = 0;
-    a[RATE_WORDS - 1] = 0x8000000000000000ull;
-    keccak_f(a);
-    u64* out = here + 4 * i;
-    out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
-}
 // One level of the tree: node i of `here` = Keccak256(LE64(1) || nodes 2i and 2i + 1 of `below`), one permutation a node
 __global__ __launch_bounds__(PCS_TPB) void k_pcs_merkle(const u64* __restrict__ below, u64* __restrict__ here, size_t count) {
     const size_t i = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
@@ -283,6 +238,16 @@ Commitment::~Commitment() {
 
 static unsigned blocks_for(size_t n) { return (unsigned)((n + PCS_TPB - 1) / PCS_TPB); }
 
+void merkle_levels_device(hipStream_t st, u64* d_tree, size_t N) {
+    u64* below = d_tree;
+    size_t count = N / 2;
+    for (; count > (size_t)PCS_TPB; count >>= 1) {
+        k_pcs_merkle<<<blocks_for(count), PCS_TPB, 0, st>>>(below, below + 8 * count, count);
+        below += 8 * count;
+    }
+    k_pcs_merkle_top<<<1, PCS_TPB, 0, st>>>(below, count);
+}
+
 Commitment* commit_device(hg_ctx* ctx, const Shape& sh, const u64* const* tables) {
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
     ctx->arena_reset();
@@ -306,13 +271,7 @@ Commitment* commit_device(hg_ctx* ctx, const Shape& sh, const u64* const* tables
     dev::powers_table(st, W, root_of_unity(log2n), N);
     dev::ntt_batch(st, cm->d_M, log2n, R, W, 1, scratch);
     k_pcs_leaf_hash<<<blocks_for(N), PCS_TPB, 0, st>>>(cm->d_M, N, R, d_tree);
-    u64* below = d_tree;
-    size_t count = N / 2;
-    for (; count > (size_t)PCS_TPB; count >>= 1) {
-        k_pcs_merkle<<<blocks_for(count), PCS_TPB, 0, st>>>(below, below + 8 * count, count);
-        below += 8 * count;
-    }
-    k_pcs_merkle_top<<<1, PCS_TPB, 0, st>>>(below, count);
+    merkle_levels_device(st, d_tree, N);
     cm->tree.resize(32 * (2 * N - 1));
     unsigned flag = 0;
     hip_check(hipMemcpyAsync(cm->tree.data(), d_tree, cm->tree.size(), hipMemcpyDeviceToHost, st), "download tree");

@@ -38,8 +38,11 @@ inline size_t opening_bytes(const Shape& sh, size_t n_claims, size_t Q) { return
 
 struct Claim { size_t table; std::vector<E2> point; E2 value; };
 
-// One handle for both forms. The tree is always on the host: level l (0 = leaves) starts at node 2N - (2N >> l), 32 bytes a node.
+// One handle for both forms and both fields. The tree is always on the host: level l (0 = leaves) starts at node 2N - (2N >> l),
+// 32 bytes a node.
+enum Field { GOLDILOCKS = 0, BN254 = 1 };   // BN254 (pcs_bn254.hpp): an element is 4 canonical little-endian words in rows, M, d_rows, d_M
 struct Commitment {
+    Field field = GOLDILOCKS;
     Shape sh;
     hg_ctx* ctx = nullptr;          // null: host form
     std::vector<u64> rows, M;       // host form: R x C raw rows, R x 4C encoded rows
@@ -60,6 +63,9 @@ std::vector<E2> eq_table(const E2* pt, size_t n);                               
 Commitment* commit_host(const Shape& sh, const u64* const* tables);
 // ---- device form (pcs.hip): rows staged and encoded in HBM, column hashes and the tree by kernels, one synchronisation
 Commitment* commit_device(hg_ctx* ctx, const Shape& sh, const u64* const* tables);
+// the levels above the 4C leaf hashes at d_tree (4 words a node, the levels one behind the other), enqueued on st; nodes are 32 bytes
+// in either field
+void merkle_levels_device(hipStream_t st, u64* d_tree, size_t N);
 
 // One row combination of an opening: u[j] = sum_{r < nrows} w[r] * row_{row0 + r}[j]
 struct CombineJob { size_t row0, nrows; std::vector<E2> w; };
@@ -78,6 +84,7 @@ std::string verify_device(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], 
 
 // ---- what both forms of the verifier share (pcs.cpp): the length check, the transcript up to the column indices, the reasons
 std::string length_reason(const Shape& sh, size_t n_claims, size_t Q, size_t len);   // "" if the length is the opening's
+std::string length_reason(size_t len, size_t want);                                   // the same for a length worked out by the caller
 FsTranscript start_transcript(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q);
 std::vector<E2> rho_powers(E2 rho, size_t R);
 void absorb_words(FsTranscript& tr, const u64* words, size_t count);                 // the u_i as read: c0, c1 of every element

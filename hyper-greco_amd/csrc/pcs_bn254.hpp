@@ -1,0 +1,52 @@
+// The polynomial commitment of pcs.hpp over bn256::Fr (F = E = Fr): what opens the claims hg_verify_public_bn254 leaves on the secret
+// inputs. Same scheme, shape rules and limits; an element is 32 bytes. What differs (include/hg.h states it in full): the code is
+// the Fr NTT of size 4C with the root of hg_ntt_bn254; a leaf hashes LE64(0) and the 32-byte little-endian canonical elements of a
+// column; the transcript starts as "hg-pcs-bn254-1", absorbs elements as those 32 bytes, and a challenge is LE(hash) mod r (the rule
+// of hg_challenges_bn254 over the absorbed bytes), one element for rho; elements cross the opening as 32 bytes big-endian.
+//
+// A handle is the pcs::Commitment of pcs.hpp with field == BN254: rows, M, d_rows, d_M hold 4 canonical (non-Montgomery) words an
+// element, so the leaf hash and the column gather read them as they are. Weights (powers of rho, eq tables) are in Montgomery
+// form, so a Montgomery product weight x element is the plain product.
+#pragma once
+#include "pcs.hpp"
+#include "bn254_field.hpp"
+
+namespace hg {
+namespace bn {
+
+inline size_t pcs_opening_bytes(const pcs::Shape& sh, size_t n_claims, size_t Q) { return 32 * sh.C() * (n_claims + 1) + Q * (32 * sh.R + 32 * (size_t)sh.depth()); }
+
+struct PcsClaim { size_t table; std::vector<Fr> point; Fr value; };   // canonical elements
+
+// `who`: the entry point an Error names. words == false: tables[t] = 2^{v_t} elements of 4 canonical words (an element that is not
+// below r is an Error); words == true: tables[t] = 2^{v_t} witness words, lifted by the signed rule of fr_lift_signed (a word below
+// 2^63 is itself, any other is r - (p_goldilocks - word)) - on the device by a kernel, so a quarter of the bytes is uploaded.
+pcs::Commitment* pcs_commit_host(const char* who, const pcs::Shape& sh, const u64* const* tables, bool words);
+// bn254_pcs.inc (part of bn254.hip): rows staged, encoded by the batched NTT, hashed, the tree by the kernels of pcs.hip; one synchronisation
+pcs::Commitment* pcs_commit_device(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const u64* const* tables, bool words);
+
+// One row combination of an opening: u[j] = sum_{r < nrows} w[r] * row_{row0 + r}[j]; w in Montgomery form, u canonical
+struct PcsJob { size_t row0, nrows; std::vector<Fr> w; };
+void pcs_combine_host(const pcs::Commitment& cm, const std::vector<PcsJob>& jobs, Fr* u);        // u: jobs.size() x C
+void pcs_columns_host(const pcs::Commitment& cm, const std::vector<size_t>& js, Fr* cols);       // cols: js.size() x R
+void pcs_combine_device(const pcs::Commitment& cm, const std::vector<PcsJob>& jobs, Fr* u);
+void pcs_columns_device(const pcs::Commitment& cm, const std::vector<size_t>& js, Fr* cols);
+
+// hg_pcs_open_bn254: the opening bytes; an Error (naming `who` and the claim) if a value is not <u_i, eq(z_i[..c])>. Transcript and
+// byte layout are here for both forms: device bytes equal host bytes by construction
+std::vector<uint8_t> pcs_open(const char* who, const pcs::Commitment& cm, const std::vector<PcsClaim>& claims, size_t Q);
+// hg_pcs_verify_bn254: "" = accepted, else the reason (the strings and the order of pcs::verify)
+std::string pcs_verify(const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof, size_t len);
+
+// the signed lift of a witness word, canonical (host side of fr_lift_signed)
+BN_HD Fr fr_lift_signed_canon(u64 v) { return v < (1ULL << 63) ? fr_make(v, 0, 0, 0) : fr_sub(fr_zero(), fr_make(0xFFFFFFFF00000001ULL - v, 0, 0, 0)); }
+
+// bn254.hip: `batch` transforms of size 2^log2n in place on device pointers, natural order in and out, through tmp (same size).
+// W[i] = w^i in Montgomery form, i < 2^log2n. 8 <= log2n <= 16: the four-step LDS kernels (batch <= 65535, the grid's y), any other
+// size: bit reversal and radix-2 stages. scale (null: none) is multiplied on by a Montgomery product on the way out. The transform
+// is linear and every twiddle product is a Montgomery product with a Montgomery-form power of w, so elements keep the form they
+// came in: Montgomery in, Montgomery out; canonical plain words in, canonical plain words out.
+void ntt_batch_dev(hipStream_t st, Fr* a, Fr* tmp, const Fr* W, int log2n, size_t batch, const Fr* scale);
+
+}  // namespace bn
+}  // namespace hg

@@ -698,6 +698,69 @@ int hg_verify_public_batch_bn254(hg_ctx* ctx, const hg_pk* pk, const void* const
 int hg_instance_mle_batch_bn254(hg_ctx* ctx, const void* const* instances, size_t n, int which, int index,
                                 const uint64_t* point4, size_t nvars, uint64_t* out4);
 
+/* ---- Polynomial commitment over bn256::Fr: what opens the claims hg_verify_public_bn254 leaves --------------------------------------
+ * The scheme of the Goldilocks block above (hg_pcs_commit ..) with F = E = Fr (r = the order of bn256's scalar field). Shape rules,
+ * limits, the log2_row = 0 rule, n_queries = 0 -> 241 and the 65535-row cap of the device commit are unchanged; the 241 is the same
+ * (3/4)^Q term, and with a 254-bit field ONE rho is enough for the combination's own error - no more is claimed. Not zero knowledge;
+ * the root is not yet absorbed into the GKR transcript. An element crosses the ABI as 4 canonical little-endian u64 limbs, as
+ * everywhere in the BN254 entries. repr(x) below is the 32-byte little-endian canonical, non-Montgomery form (halo2curves to_repr).
+ *   Rows.   Table t has 2^{v_t} elements and is cut into rows of C = 2^c elements; rows are stacked in table order (R rows, off_t).
+ *   Code.   Enc(row) = the forward NTT of size N = 4C of the row zero-padded to 4C elements, natural order, root of unity
+ *           7^((r-1)/2^(c+2)): what hg_ntt_bn254(.., log2n = c+2, inverse = 0, ..) computes.
+ *   Tree.   leaf_j = Keccak256(LE64(0) || repr(M[0][j]) || .. || repr(M[R-1][j])), j < 4C, M[r] = Enc(row_r); an inner node is
+ *           Keccak256(LE64(1) || left || right), as above; the commitment is the 32-byte root.
+ *   Transcript. Absorbing: the hash state starts as the ASCII bytes "hg-pcs-bn254-1", the root, then as 4-byte little-endian c, m,
+ *           v_0 .. v_{m-1}, Q, n, then per claim t_i (4-byte LE), repr of every coordinate of the point, repr of the value. A
+ *           challenge: h = Keccak256(state); the challenge is LE(h) mod r; the state becomes h (what is absorbed later is appended
+ *           to it). With nothing absorbed this is the chain of hg_challenges_bn254.
+ *   Opening of n claims (t_i, z_i in Fr^{v_{t_i}}, y_i) with Q = n_queries:
+ *     1. rho = one squeezed element; u_0[j] = sum_{r<R} rho^r row_r[j], j < C;
+ *     2. per claim w_i = eq(z_i[c..]) and u_i[j] = sum_r w_i[r] row_{off_t + r}[j];
+ *     3. u_0, u_1 .. u_n are written as 32-byte big-endian elements (as every BN254 proof element) and absorbed as repr;
+ *     4. Q column indices j_q = (the low 64 bits of a squeezed canonical element) & (4C - 1), duplicates kept;
+ *     5. per query the R column elements M[.][j_q] (32-byte big-endian), then the c+2 siblings bottom-up (32 raw bytes each).
+ *     Length: exactly 32 C (n+1) + Q (32 R + 32 (c+2)) bytes.
+ *   Verification (hg_pcs_verify_bn254, host): the order of checks and the reason strings of hg_pcs_verify - length; every element
+ *     below r ("pcs: non-canonical word at byte B", B = the offset of the first byte of the first element that is not below r, the
+ *     u_i first, then the columns query by query); <u_i, eq(z_i[..c])> == y_i; per query the path, the proximity combination against
+ *     Enc(u_0)[j_q], every claim's combination against Enc(u_i)[j_q].
+ * Contracts as above: 0, 1 = rejected with the reason in hg_last_error (the verifiers only), -1 with text that names the function.
+ * A handle carries its field: hg_pcs_free frees a handle of either; a Goldilocks handle given to hg_pcs_open_bn254 /
+ * hg_claims_open_bn254 is an error (-1), and so is a BN254 handle given to hg_pcs_open / hg_claims_open.
+ *
+ * hg_pcs_commit_bn254: tables4[t] = 2^{nvars[t]} elements of 4 limbs. ctx == NULL: the host form (radix-2 NTT and hashes on the
+ *   host's threads); with a context the device form on one stream with one synchronisation: the tables are uploaded as they are, a
+ *   kernel writes the zero-padded 4C-stride matrix, the batched Fr NTT encodes it in place (four-step in LDS for 8 <= c+2 <= 16,
+ *   radix-2 stages otherwise), one thread per column hashes it with the Keccak state in registers, the tree is built by the kernels
+ *   of hg_pcs_commit. The encoded matrix stays in HBM as canonical plain limbs; the handle owns it and the raw rows (57 MB + 227 MB
+ *   for the secrets of n=32768 k=16 at c=11) and a host copy of the tree; the NTT temporary is the context's arena. Both forms give
+ *   the same root. -1: a null argument or table, a shape outside the limits, an element that is not below r (the same text in both
+ *   forms), more than 65535 rows on the device.
+ * hg_pcs_open_bn254: points4 = the claims' points one behind the other, 4 limbs per coordinate; values4: 4 limbs per claim. ctx
+ *   must be the context the commitment was made on (NULL for the host form). The device form runs the row combinations as one
+ *   launch and gathers the opened columns with another; it synchronises twice, as hg_pcs_open. Same bytes as the host form. -1 as
+ *   hg_pcs_open, and for a handle over Goldilocks.
+ * hg_pcs_verify_bn254: host only. -1 as hg_pcs_verify.
+ * hg_secrets_commit_bn254: hg_pcs_commit_bn254 of the five secret inputs of a witness handle, tables in input order and with the
+ *   variable counts of hg_secrets_commit; every u64 word of the handle is lifted into Fr by the signed rule - a word below 2^63 is
+ *   itself, any other is r - (p_goldilocks - word) - which is the table hg_claims_settle_bn254 evaluates. The device form uploads
+ *   the words (a quarter of the bytes) and lifts them by a kernel.
+ * hg_claims_open_bn254 / hg_claims_verify_bn254: hg_pcs_open_bn254 / hg_pcs_verify_bn254 for an hg_input_claim_bn254 array and
+ *   points4 exactly as hg_verify_public_bn254 / hg_verify_public_batch_bn254 return them, with the input-to-table mapping and the -1
+ *   cases of hg_claims_open / hg_claims_verify. hg_verify_public_bn254 followed by hg_claims_verify_bn254 against a root the
+ *   encryptor published is a BN254 verification that needs no secret. */
+int hg_pcs_commit_bn254(hg_ctx* ctx, const uint64_t* const* tables4, const uint32_t* nvars, size_t n_tables, size_t log2_row,
+                        void** commitment, uint8_t root[32]);
+int hg_pcs_open_bn254(hg_ctx* ctx, const void* commitment, const uint32_t* table, const uint64_t* points4, const uint64_t* values4,
+                      size_t n_claims, size_t n_queries, uint8_t* proof, size_t cap, size_t* len);
+int hg_pcs_verify_bn254(const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table,
+                        const uint64_t* points4, const uint64_t* values4, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len);
+int hg_secrets_commit_bn254(hg_ctx* ctx, const hg_params* params, const hg_witness* w, size_t log2_row, void** commitment, uint8_t root[32]);
+int hg_claims_open_bn254(hg_ctx* ctx, const hg_params* params, const void* commitment, const void* claims, size_t n,
+                         const uint64_t* points4, size_t n_queries, uint8_t* opening, size_t cap, size_t* len);
+int hg_claims_verify_bn254(const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n,
+                           const uint64_t* points4, size_t n_queries, const uint8_t* opening, size_t len);
+
 /* hg_witness_derive and hg_prove_bn254 for a run of n_enc ENCRYPTIONS under one key, pipelined: hg_prove_encryptions over bn256::Fr
  *   [REF scripts/circuit_sk.py:18-140 followed by sk_encryption_circuit.rs:417-460, 614-626; the loop a proving service writes around
  *   them - the reference has no batch entry]. The contract is that of hg_prove_encryptions: s[i], e[i], k1[i] (n each) and a[i] (k*n)

@@ -13,6 +13,7 @@ pids=()
 for f in kernels.hip prover.hip prover_seq.hip capi.hip bn254.hip comm.hip verifier_dev.hip verifier_batch.hip pcs.hip; do $CXX -c "$src/$f" -o "$out/${f%.hip}.o" & pids+=($!); done
 for f in host.cpp verifier.cpp; do $CXX -x hip -c "$src/$f" -o "$out/${f%.cpp}.o" & pids+=($!); done
 $CXX -x hip -c "$src/pcs.cpp" -o "$out/pcs_host.o" & pids+=($!)
+$CXX -x hip -c "$src/pcs_bn254.cpp" -o "$out/pcs_bn254_host.o" & pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
 # sanitizer flags (make asan) must reach the link too
 lflags=$(echo "$flags" | tr ' ' '\n' | grep -E '^-fsanitize|^-shared-libsan|^-fno-gpu-sanitize' | tr '\n' ' ' || true)

@@ -7,7 +7,10 @@ each leg, --reps timed calls each:
   verify_dev / verify_host   hg_claims_verify_device / hg_claims_verify of the opening: the whole call, upload included
 Prints the opening's bytes, median and range per leg, and for the commit and the verify pair whether the whole range of the device
 form lies below that of the host form.
-Usage: pcs_times.py [n k] [--reps 5]"""
+--field bn254 times the BN254 commitment on the claims hg_verify_public_device_bn254 leaves on an hg_prove_bn254 proof: the commit and
+open pairs and the host verifier (there is no device verifier over BN254), then one more device commit and open under hg_profile
+for the kernel time by class.
+Usage: pcs_times.py [n k] [--reps 5] [--field goldilocks|bn254]"""
 import argparse
 import os
 import statistics
@@ -25,27 +28,36 @@ def main():
     ap.add_argument("n", type=int, nargs="?", default=32768)
     ap.add_argument("k", type=int, nargs="?", default=16)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--field", choices=["goldilocks", "bn254"], default="goldilocks")
     a = ap.parse_args()
+    bn = a.field == "bn254"
     ctx = hg.Context(0)
     bfv = hg.BfvEncrypt.new(a.n, a.k)
     pk = bfv.setup(ctx)
     w = hg.Witness.synthetic(bfv.params, 0x4752454330 + a.n)
-    proof, _ = bfv.prove(ctx, pk, w, cap=1 << 25)
-    ok, why, claims = hg.verify_public(pk, hg.Instance.from_witness(w), proof, 0, ctx=ctx, device=True)
+    if bn:
+        proof = ctx.prove_bn254(pk, w, cap=1 << 25)[0]
+        ok, why, claims = hg.verify_public_bn254(pk, hg.Instance.from_witness(w), proof, ctx=ctx, device=True)
+    else:
+        proof, _ = bfv.prove(ctx, pk, w, cap=1 << 25)
+        ok, why, claims = hg.verify_public(pk, hg.Instance.from_witness(w), proof, 0, ctx=ctx, device=True)
     assert ok, why
-    held = {"dev": hg.Commitment.secrets(ctx, bfv.params, w), "host": hg.Commitment.secrets(None, bfv.params, w)}
+    secrets = hg.Commitment.secrets_bn254 if bn else hg.Commitment.secrets
+    verify = hg.claims_verify_bn254 if bn else hg.claims_verify
+    held = {"dev": secrets(ctx, bfv.params, w), "host": secrets(None, bfv.params, w)}
     assert held["dev"].root == held["host"].root
     opening = held["dev"].open_claims(bfv.params, claims)
     assert opening == held["host"].open_claims(bfv.params, claims)
 
     def commit(form):
         held[form].free()
-        held[form] = hg.Commitment.secrets(ctx if form == "dev" else None, bfv.params, w)
+        held[form] = secrets(ctx if form == "dev" else None, bfv.params, w)
 
     legs = [("commit_dev", lambda: commit("dev")), ("commit_host", lambda: commit("host")),
-            ("open_dev", lambda: held["dev"].open_claims(bfv.params, claims)), ("open_host", lambda: held["host"].open_claims(bfv.params, claims)),
-            ("verify_dev", lambda: hg.claims_verify(bfv.params, held["host"].root, claims, opening, ctx=ctx)),
-            ("verify_host", lambda: hg.claims_verify(bfv.params, held["host"].root, claims, opening))]
+            ("open_dev", lambda: held["dev"].open_claims(bfv.params, claims)), ("open_host", lambda: held["host"].open_claims(bfv.params, claims))]
+    if not bn:
+        legs.append(("verify_dev", lambda: hg.claims_verify(bfv.params, held["host"].root, claims, opening, ctx=ctx)))
+    legs.append(("verify_host", lambda: verify(bfv.params, held["host"].root, claims, opening)))
     times = {name: [] for name, _ in legs}
     for rep in range(a.reps + 1):   # rep 0: the warm-up call of each leg
         for name, fn in legs:
@@ -57,13 +69,14 @@ def main():
             if rep:
                 times[name].append(dt)
     c = held["dev"]
+    print("field %s" % a.field)
     print("n=%d k=%d: %d tables, log2_row %d, %d rows, code length %d; %d claims, 241 queries, opening %d bytes; legs alternated, %d timed calls each "
           "after one warm-up call, one process" % (a.n, a.k, len(c.nvars), c.log2_row, sum(1 << (v - c.log2_row) for v in c.nvars), 4 << c.log2_row, claims.n,
                                                    len(opening), a.reps))
     for name, _ in legs:
         t = times[name]
         print("%-11s median %.2f ms, range %.2f .. %.2f ms (%s)" % (name, statistics.median(t), min(t), max(t), " ".join("%.2f" % x for x in t)))
-    for leg in ("commit", "verify"):
+    for leg in ("commit", "open") if bn else ("commit", "verify"):
         dev, host = times[leg + "_dev"], times[leg + "_host"]
         if max(dev) < min(host):
             print("%s_dev is faster than %s_host: its whole range lies below the host form's" % (leg, leg))
@@ -71,6 +84,15 @@ def main():
             print("%s_dev is SLOWER than %s_host: its whole range lies above the host form's" % (leg, leg))
         else:
             print("%s_dev and %s_host overlap: no difference shown" % (leg, leg))
+    if bn:   # one more device commit and open with every launch class timed by events
+        ctx.profile(2)
+        ctx.profile_reset()
+        commit("dev")
+        held["dev"].open_claims(bfv.params, claims)
+        for st in ctx.profile_get(256):
+            if st["name"].startswith("pcs_bn254"):
+                print("%-18s %2d launches %8.3f ms  %7.1f MB by the algorithm" % (st["name"], st["launches"], st["total_ms"], st["algo_bytes"] / 1e6))
+        ctx.profile(0)
     for h in held.values():
         h.free()
     pk.free()
