@@ -639,6 +639,28 @@ __global__ __launch_bounds__(256) void k_st_step(const StJob* __restrict__ jobs,
     }
     if (nblocks > 1) finish_partials(part, NV, tickets_of(partials) + y * 32, res + J.sums_slot + (size_t)rd * NV, sm, nblocks);
 }
+// ---- limbs without the limb table (kernels.hpp: LimbSrc) -----------------------------------------------------------------
+// the four limbs of row j in one word: the node input masked to its lookup's width, 0 beyond `rows`; limb c of it
+__device__ __forceinline__ u64 limb_word(const u64* __restrict__ input, const uint8_t* __restrict__ seg_lookup, int seg_shift, size_t rows,
+                                         const u64* lookup_mask, size_t j) {
+    return j < rows ? input[j] & lookup_mask[seg_lookup[j >> seg_shift]] : 0;
+}
+__device__ __forceinline__ u32 limb_of(u64 word, int c) { return (u32)(word >> (16 * c)) & 0xFFFF; }
+// limb c of rows j2, j2 + 1 (j2 even: one row segment, rows even) as the limb table's 16-byte load would return them
+template <typename S>
+__device__ __forceinline__ ulonglong2 limb_pair(const S& H, size_t j2, int c) {
+    if (j2 >= H.rows) return make_ulonglong2(0, 0);
+    const ulonglong2 w = *reinterpret_cast<const ulonglong2*>(H.input + j2);
+    const u64 m = H.lookup_mask[H.seg_lookup[j2 >> H.seg_shift]];
+    return make_ulonglong2(limb_of(w.x & m, c), limb_of(w.y & m, c));
+}
+LimbSrc limb_src(const LassoDev& L, const u64* input) {
+    LimbSrc S;
+    memset(&S, 0, sizeof(S));
+    S.input = input; S.seg_lookup = L.seg_lookup; S.seg_shift = L.seg_shift; S.rows = L.rows;
+    memcpy(S.lookup_mask, L.lookup_mask, sizeof(S.lookup_mask));
+    return S;
+}
 // ---- first round of grand product #1's top layer straight from the Lasso integer tables ----------------------------------
 // The level-0 rows (the 2 alpha multiset-hash tables of 2^nu entries, 838 MB at n=32768 k=16) are never materialised: thread j
 // recomputes h = dim + E gamma + ts gamma^2 - tau at the four indices 2j, 2j+1, N/2 + 2j, N/2 + 2j+1 it needs (v_l, v_r are the
@@ -696,9 +718,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLOT ? HG_H
             const GpHashMem M = H.mems[mi];
             if (M.chunk != cur_chunk) {  // uniform: memories are listed chunk by chunk
                 cur_chunk = M.chunk;
-                const u64* __restrict__ dim = H.dim[cur_chunk];
                 const u64* __restrict__ ts = H.ts[cur_chunk];
-                const ulonglong2 dl = *reinterpret_cast<const ulonglong2*>(dim + 2 * j), dh = *reinterpret_cast<const ulonglong2*>(dim + hN + 2 * j);
+                ulonglong2 dl, dh;
+                if (H.limb_sh) { dl = limb_pair(H, 2 * j, cur_chunk); dh = limb_pair(H, hN + 2 * j, cur_chunk); }   // (the same words per chunk: from cache)
+                else {
+                    const u64* __restrict__ dim = H.dim[cur_chunk];
+                    dl = *reinterpret_cast<const ulonglong2*>(dim + 2 * j); dh = *reinterpret_cast<const ulonglong2*>(dim + hN + 2 * j);
+                }
                 const ulonglong2 tl = *reinterpret_cast<const ulonglong2*>(ts + 2 * j), th = *reinterpret_cast<const ulonglong2*>(ts + hN + 2 * j);
                 c0 = gl_sub(gl_add(dl.x, gl_mul_small(gamma2, (u32)tl.x)), tau); c1 = gl_sub(gl_add(dl.y, gl_mul_small(gamma2, (u32)tl.y)), tau);
                 c2 = gl_sub(gl_add(dh.x, gl_mul_small(gamma2, (u32)th.x)), tau); c3 = gl_sub(gl_add(dh.y, gl_mul_small(gamma2, (u32)th.y)), tau);
@@ -829,8 +855,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     __shared__ HashSlotD D[64];
     __shared__ const u64* s_dim[4];
     __shared__ const u64* s_ts[4];
-    __shared__ int s_ng, s_glo[65], s_gchunk[64];   // runs of slots whose classes share a chunk (the memories are listed chunk by chunk): [s_glo[k], s_glo[k+1])
+    __shared__ int s_ng, s_glo[65], s_gchunk[64], s_gsh[64];   // runs of slots whose classes share a chunk (the memories are listed chunk by chunk): [s_glo[k], s_glo[k+1])
     __shared__ u32 s_uses[2];
+    __shared__ u64 s_mask[2];   // the masks of the two row segments' lookups, 0 beyond `rows` (GpHashSrc::lookup_mask: all ones for the limb table)
     int staged_sp = -1;
     auto stage = [&](int sp, size_t tile) {   // (all threads; uniform arguments)
         __syncthreads();
@@ -845,11 +872,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             if (d.valid) { const GpHashMem M = H.mems[mi]; d.chunk = M.chunk; d.rd_row = M.rd_row; d.mem = M.mem; d.cutoff = M.cutoff; }
             D[tid] = d;
         }
-        if (tid < 4) { s_dim[tid] = H.dim[tid]; s_ts[tid] = H.ts[tid]; }
-        if (tid == 64) {   // the memories the lookups of this tile's two row segments use (alpha <= 32)
+        if (tid < 4) { s_dim[tid] = H.dim[tid]; s_ts[tid] = H.ts[tid]; }   // (limbs from the node input: dim[] is the input four times - every chunk's run asks for the same words)
+        if (tid == 64) {   // the memories the lookups of this tile's two row segments use (alpha <= 32), and the lookups' masks
             const size_t p = tile << 9;
-            s_uses[0] = p < H.rows ? (u32)H.lookup_uses[H.seg_lookup[p >> seg_shift]] : 0u;
-            s_uses[1] = hN + p < H.rows ? (u32)H.lookup_uses[H.seg_lookup[(hN + p) >> seg_shift]] : 0u;
+            const int l0 = p < H.rows ? H.seg_lookup[p >> seg_shift] : -1, l1 = hN + p < H.rows ? H.seg_lookup[(hN + p) >> seg_shift] : -1;
+            s_uses[0] = l0 >= 0 ? (u32)H.lookup_uses[l0] : 0u;
+            s_uses[1] = l1 >= 0 ? (u32)H.lookup_uses[l1] : 0u;
+            s_mask[0] = l0 >= 0 ? H.lookup_mask[l0] : 0;
+            s_mask[1] = l1 >= 0 ? H.lookup_mask[l1] : 0;
         }
         __syncthreads();
         if (tid == 0) {
@@ -857,9 +887,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             for (int m = 0; m < nslots; m++) {
                 if (!D[m].valid || D[m].chunk == cur) continue;
                 cur = D[m].chunk;
-                s_glo[ng] = ng == 0 ? 0 : m; s_gchunk[ng] = cur; ng++;
+                s_glo[ng] = ng == 0 ? 0 : m; s_gchunk[ng] = cur; s_gsh[ng] = H.limb_sh * cur; ng++;   // (s_gsh: where the run's limb sits in the word asked for)
             }
-            if (ng == 0) { s_glo[0] = 0; s_gchunk[0] = 0; ng = 1; }   // (no class at all here: zero tables; the values asked for are ignored)
+            if (ng == 0) { s_glo[0] = 0; s_gchunk[0] = 0; s_gsh[0] = 0; ng = 1; }   // (no class at all here: zero tables; the values asked for are ignored)
             s_glo[ng] = nslots;
             s_ng = ng;
         }
@@ -897,9 +927,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         // take the values asked for, ask for the next run's: this tile's, else the next tile's first (the last run of the workgroup asks
         // for its own again: every run issues the same loads). The values are consumed BEFORE the request and the slots of the run
         // do not touch them: the loop over the slots carries no copy of values in flight.
-        const u64 c0 = gl_sub(gl_add(nxt.dl.x, gl_mul_small(gamma2, (u32)nxt.tl.x)), tau), c1 = gl_sub(gl_add(nxt.dl.y, gl_mul_small(gamma2, (u32)nxt.tl.y)), tau);
-        const u64 c2 = gl_sub(gl_add(nxt.dh.x, gl_mul_small(gamma2, (u32)nxt.th.x)), tau), c3 = gl_sub(gl_add(nxt.dh.y, gl_mul_small(gamma2, (u32)nxt.th.y)), tau);
-        const u32 a01 = (u32)nxt.dl.x | ((u32)nxt.dl.y << 16), a23 = (u32)nxt.dh.x | ((u32)nxt.dh.y << 16);   // the chunk's 16-bit limbs at 2j, 2j+1 | N/2+2j, N/2+2j+1
+        // the chunk's 16-bit limbs at 2j, 2j+1 | N/2+2j, N/2+2j+1: the limb table's values as they are (mask of ones, no shift), or the
+        // node input's words, of which the run's chunk picks the limb (`rows` ends on a segment boundary: the mask of a tile is uniform)
+        const int shc = __builtin_amdgcn_readfirstlane(s_gsh[k]);
+        // (32-bit throughout: the half of the word the limb sits in, that half of the mask, a shift by 0 or 16)
+        const bool up = (shc & 32) != 0;
+        const int sh16 = shc & 16;
+        const u32 ml = (u32)__builtin_amdgcn_readfirstlane((int)(s_mask[0] >> (up ? 32 : 0))) >> sh16 & 0xFFFF;
+        const u32 mh = (u32)__builtin_amdgcn_readfirstlane((int)(s_mask[1] >> (up ? 32 : 0))) >> sh16 & 0xFFFF;
+        const u32 d0 = ((up ? (u32)(nxt.dl.x >> 32) : (u32)nxt.dl.x) >> sh16) & ml, d1 = ((up ? (u32)(nxt.dl.y >> 32) : (u32)nxt.dl.y) >> sh16) & ml;
+        const u32 d2 = ((up ? (u32)(nxt.dh.x >> 32) : (u32)nxt.dh.x) >> sh16) & mh, d3 = ((up ? (u32)(nxt.dh.y >> 32) : (u32)nxt.dh.y) >> sh16) & mh;
+        const u64 c0 = gl_sub(gl_add((u64)d0, gl_mul_small(gamma2, (u32)nxt.tl.x)), tau), c1 = gl_sub(gl_add((u64)d1, gl_mul_small(gamma2, (u32)nxt.tl.y)), tau);
+        const u64 c2 = gl_sub(gl_add((u64)d2, gl_mul_small(gamma2, (u32)nxt.th.x)), tau), c3 = gl_sub(gl_add((u64)d3, gl_mul_small(gamma2, (u32)nxt.th.y)), tau);
+        const u32 a01 = d0 | (d1 << 16), a23 = d2 | (d3 << 16);
         {
             const bool more_k = k + 1 < ng, more_t = tile + 1 < t_hi;
             request(more_k || !more_t ? tile : tile + 1, s_gchunk[more_k ? k + 1 : (more_t ? 0 : k)], nxt);
@@ -2238,6 +2278,9 @@ void eq_jobs_ab(hipStream_t st, const EqJob* jobs, int njobs, EqAbGrid grid, con
     k_eq_prep<<<grid.prep, 256, 0, st>>>(jobs, njobs, chal);
     k_eq_fill<<<grid.fill, 256, 0, st>>>(jobs, njobs);
 }
+void eq_jobs_prep(hipStream_t st, const EqJob* jobs, int njobs, EqAbGrid grid, const E2* chal) {
+    k_eq_prep<<<grid.prep, 256, 0, st>>>(jobs, njobs, chal);
+}
 void eq_jobs(hipStream_t st, const EqJob* jobs, int njobs, int max_n, const E2* chal) {
     int hi = max_n > 8 ? max_n - 8 : 0;
     size_t nblk = ((size_t)1 << hi) / eq_k_for(hi);
@@ -2511,7 +2554,7 @@ static CounterPlan counter_plan(const LassoDev& L, unsigned chunk_mask) {
 size_t lasso_counters_all_elems(const LassoDev& L, unsigned chunk_mask) { CounterPlan P = counter_plan(L, chunk_mask); return P.off[P.nchunks]; }
 size_t lasso_counters_all_temp_bytes(size_t n_elems) { return cs_temp_bytes(n_elems); }
 struct CsGenAll {   // pair q of the concatenated chunks: ((chunk, address), row); rows ascend inside a chunk and the sort is stable
-    LassoDev L; CounterPlan P; const u64* dims;
+    LassoDev L; CounterPlan P; const u64* dims; const u64* input;   // dims == nullptr: the limbs come from the node input
     __device__ __forceinline__ void operator()(size_t q, u32& key, u32& val) const {
         const size_t N = (size_t)1 << L.nu;
         const size_t smask = ((size_t)1 << L.seg_shift) - 1;
@@ -2520,7 +2563,8 @@ struct CsGenAll {   // pair q of the concatenated chunks: ((chunk, address), row
         const int c = P.chunk[s];
         const size_t local = q - P.off[s];
         const size_t row = ((size_t)L.cnt_segs[c][local >> L.seg_shift] << L.seg_shift) | (local & smask);
-        key = ((u32)c << 16) | (u32)dims[(size_t)L.mem_dim[c] * N + row];
+        const u32 a = dims ? (u32)dims[(size_t)L.mem_dim[c] * N + row] : limb_of(limb_word(input, L.seg_lookup, L.seg_shift, L.rows, L.lookup_mask, row), L.mem_dim[c]);
+        key = ((u32)c << 16) | a;
         val = (u32)row;
     }
 };
@@ -2544,8 +2588,9 @@ __global__ __launch_bounds__(TPB) void k_counter_clear(CounterOut out, CounterPl
     }
 }
 void lasso_counters_all(hipStream_t st, const LassoDev& L, unsigned chunk_mask, const u64* dims, const CounterOut& out, void* temp, size_t temp_bytes,
-                        u32* keys, u32* keys_sorted, u32* vals, u32* vals_sorted, u32* starts) {
+                        u32* keys, u32* keys_sorted, u32* vals, u32* vals_sorted, u32* starts, const u64* input) {
     const size_t N = (size_t)1 << L.nu;
+    if (!dims && !input) throw std::runtime_error("lasso_counters_all: neither a limb table nor the node input");
     const CounterPlan P = counter_plan(L, chunk_mask);
     // rows outside a chunk's counted segments and addresses never touched keep counter 0: one clearing launch for all chunks
     // (eight hipMemsetAsync calls cost 5-14 us each on the stream and, as nodes of a captured graph, ~60 us each)
@@ -2554,7 +2599,7 @@ void lasso_counters_all(hipStream_t st, const LassoDev& L, unsigned chunk_mask, 
     if (total == 0) return;
     const int grid = grid_for(total);
     // stable sort on (chunk, address) keeps the rows of one address of one chunk in row order
-    cs_sort_pairs(st, temp, temp_bytes, keys, keys_sorted, vals, vals_sorted, total, CsGenAll{L, P, dims});
+    cs_sort_pairs(st, temp, temp_bytes, keys, keys_sorted, vals, vals_sorted, total, CsGenAll{L, P, dims, input});
     k_counter_starts<<<grid, TPB, 0, st>>>(keys, total, starts);
     k_counter_ranks_all<<<grid, TPB, 0, st>>>(keys, vals, total, starts, out);
 }
@@ -2578,11 +2623,21 @@ __global__ __launch_bounds__(TPB) void k_lasso_claim(LassoDev L, const E2* __res
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 // the same with the E values recomputed from the node input (no E tables): own = bit mask of the memories whose terms this rank sums
+// AB: `eq` holds the factor tables k_eq_prep leaves (A: 256 entries, then B) and eq[k] = A[k & 255] * B[k >> 8] is formed here: a
+// workgroup walks whole table rows of 256, so a thread keeps its A entry and the B entry is uniform per step
+template <bool AB>
 __global__ __launch_bounds__(TPB) void k_lasso_claim_in(LassoDev L, const E2* __restrict__ eq, const u64* __restrict__ input, u32 own,
                                                         E2* __restrict__ partials) {
     __shared__ E2 sm[TPB / 64];
     E2 acc = e2_zero();
-    for (size_t k = (size_t)blockIdx.x * TPB + threadIdx.x; k < L.rows; k += (size_t)gridDim.x * TPB) {
+    [[maybe_unused]] E2 ea = e2_zero();
+    if constexpr (AB) ea = eq[threadIdx.x];
+    for (size_t k0 = (size_t)blockIdx.x * TPB; k0 < L.rows; k0 += (size_t)gridDim.x * TPB) {
+        const size_t k = k0 + threadIdx.x;
+        E2 e;
+        if constexpr (AB) e = e2_mul(ea, eq[256 + (k0 >> 8)]);
+        if (k >= L.rows) break;
+        if constexpr (!AB) e = eq[k];
         const int l = L.seg_lookup[k >> L.seg_shift];
         const u64 v = input[k] & L.lookup_mask[l];
         u64 comb = 0;  // combine_lookups (range.rs:184-195): sum_i M^i * operand_i
@@ -2592,14 +2647,18 @@ __global__ __launch_bounds__(TPB) void k_lasso_claim_in(LassoDev L, const E2* __
             const u32 a = (u32)(v >> (16 * L.mem_dim[m])) & 0xFFFF;
             if (a < L.mem_cutoff[m]) comb = gl_add(comb, gl_mul_small(L.mpow[i], a));
         }
-        acc = e2_add(acc, e2_mul_f(eq[k], comb));
+        acc = e2_add(acc, e2_mul_f(e, comb));
     }
     E2 s = block_sum(acc, sm);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
-int lasso_claim_in(hipStream_t st, const LassoDev& L, const E2* eq, const u64* input, u32 own, E2* partials) {
+int lasso_claim_in(hipStream_t st, const LassoDev& L, const E2* eq, const u64* input, u32 own, E2* partials, bool eq_is_ab) {
+    static_assert(TPB == 256, "the factored form takes a workgroup's rows for one row of the A x B product");
     int grid = grid_for(L.rows);
-    k_lasso_claim_in<<<grid, TPB, 0, st>>>(L, eq, input, own, partials);
+    if (eq_is_ab) {
+        if (L.nu < 8) throw std::runtime_error("lasso_claim_in: factor tables need at least 8 variables");
+        k_lasso_claim_in<true><<<grid, TPB, 0, st>>>(L, eq, input, own, partials);
+    } else k_lasso_claim_in<false><<<grid, TPB, 0, st>>>(L, eq, input, own, partials);
     return grid;
 }
 int lasso_claim(hipStream_t st, const LassoDev& L, const E2* eq, const u64* e_polys, const EpRows& rows, E2* partials) {
@@ -2614,12 +2673,15 @@ int lasso_claim(hipStream_t st, const LassoDev& L, const E2* eq, const u64* e_po
 // h(a,v,t) = a + v*gamma + t*gamma^2 - tau (prover.rs:44); the address/counter part is computed once per row and
 // reused for every memory. Thread j handles rows 2j, 2j+1 and their partners in the upper half (16-byte accesses), and
 // also emits the first product-tree level rd1[j] = rd[j] rd[j + n/2] (Layer::bottom + Layer::up, prover.rs:310-354).
+template <bool IN>   // IN: dim is limb `chunk` of the node input (S), not a column of the limb table
 __global__ __launch_bounds__(TPB) void k_hash_rw(size_t n, const u64* __restrict__ dim, const u64* __restrict__ ts, HashRwArgs args, int nmem,
-                                                 u64 gamma, u64 gamma2, u64 tau) {
+                                                 u64 gamma, u64 gamma2, u64 tau, LimbSrc S, int chunk) {
     const size_t h = n >> 1;
     typedef ulonglong2 V2;
     for (size_t j = ((size_t)blockIdx.x * TPB + threadIdx.x) * 2; j < h; j += (size_t)gridDim.x * TPB * 2) {
-        const V2 dl = *reinterpret_cast<const V2*>(dim + j), dh = *reinterpret_cast<const V2*>(dim + j + h);
+        V2 dl, dh;
+        if constexpr (IN) { dl = limb_pair(S, j, chunk); dh = limb_pair(S, j + h, chunk); }
+        else { dl = *reinterpret_cast<const V2*>(dim + j); dh = *reinterpret_cast<const V2*>(dim + j + h); }
         const V2 tl = *reinterpret_cast<const V2*>(ts + j), th = *reinterpret_cast<const V2*>(ts + j + h);
         const u64 c0 = gl_sub(gl_add(dl.x, gl_mul(tl.x, gamma2)), tau), c1 = gl_sub(gl_add(dl.y, gl_mul(tl.y, gamma2)), tau);
         const u64 c2 = gl_sub(gl_add(dh.x, gl_mul(th.x, gamma2)), tau), c3 = gl_sub(gl_add(dh.y, gl_mul(th.y, gamma2)), tau);
@@ -2640,8 +2702,15 @@ __global__ __launch_bounds__(TPB) void k_hash_rw(size_t n, const u64* __restrict
         }
     }
 }
-void lasso_hash_rw(hipStream_t st, size_t n, const u64* dim, const u64* read_ts, const HashRwArgs& args, int nmem, u64 gamma, u64 tau) {
-    k_hash_rw<<<grid_for(n >> 2) * 4, TPB, 0, st>>>(n, dim, read_ts, args, nmem, gamma, gl_mul(gamma, gamma), tau);
+void lasso_hash_rw(hipStream_t st, size_t n, const u64* dim, const u64* read_ts, const HashRwArgs& args, int nmem, u64 gamma, u64 tau,
+                   const LimbSrc* limbs, int chunk) {
+    LimbSrc S;
+    memset(&S, 0, sizeof(S));
+    if (!dim) {
+        if (!limbs || !limbs->input) throw std::runtime_error("lasso_hash_rw: neither a limb column nor the node input");
+        S = *limbs;
+        k_hash_rw<true><<<grid_for(n >> 2) * 4, TPB, 0, st>>>(n, dim, read_ts, args, nmem, gamma, gl_mul(gamma, gamma), tau, S, chunk);
+    } else k_hash_rw<false><<<grid_for(n >> 2) * 4, TPB, 0, st>>>(n, dim, read_ts, args, nmem, gamma, gl_mul(gamma, gamma), tau, S, chunk);
 }
 __global__ __launch_bounds__(TPB) void k_hash_if(HashIfArgs args, u64 gamma, u64 gamma2, u64 tau, u64* __restrict__ H2, int G) {
     const int i = blockIdx.y;  // memory
@@ -2760,8 +2829,13 @@ __global__ __launch_bounds__(TPB) void k_dot_eq(const E2* __restrict__ eq, DotTa
                     if (tab) acc[t] = e2_add(acc[t], e2_mul_f(e, tab[j]));
                     else {
                         const int m = tabs.emem[t0 + t];
-                        const u32 a = (u32)(v >> (16 * V.mem_dim[m])) & 0xFFFF;
-                        if (((uses >> m) & 1) && a && a < V.mem_cutoff[m]) acc[t] = e2_add(acc[t], e2(gl_mul_small(e.c0, a), gl_mul_small(e.c1, a)));
+                        if (m < 0) {   // column -1 - m of the limb table
+                            const u32 a = limb_of(v, -1 - m);
+                            if (a) acc[t] = e2_add(acc[t], e2(gl_mul_small(e.c0, a), gl_mul_small(e.c1, a)));
+                        } else {
+                            const u32 a = limb_of(v, V.mem_dim[m]);
+                            if (((uses >> m) & 1) && a && a < V.mem_cutoff[m]) acc[t] = e2_add(acc[t], e2(gl_mul_small(e.c0, a), gl_mul_small(e.c1, a)));
+                        }
                     }
                 }
         }
@@ -2811,8 +2885,13 @@ void dot_eq_many(hipStream_t st, const E2* eq, const DotTabs& tabs, int ntab, si
     else k_dot_eq<false><<<dim3(gx, (ntab + 7) / 8), TPB, 0, st>>>(eq, tabs, ntab, n, partials, V);
     k_dot_reduce<<<ntab, TPB, 0, st>>>(partials, gx, ntab, tabs, out);
 }
-struct OpenPlan { int nmat, nvirt; short mat[DOT_MAX], virt[DOT_MAX]; };
+// mat: the tables of the streamed groups of eight - materialised ones and the limb table's columns (nlimb of them: emem = -1 - c,
+// limb c of the node input word under the workgroup's lookup mask); virt: the recomputed E tables
+struct OpenPlan { int nmat, nvirt, nlimb; short mat[DOT_MAX], virt[DOT_MAX]; };
 constexpr int OPEN_ACT = 8;
+// AB: `eq` holds the factor tables k_eq_prep leaves (A: 256 entries, then B) and eq[j] = A[j & 255] * B[j >> 8] is formed here (a
+// workgroup's rows are whole table rows of 256: a thread keeps its A entry, the B entry is uniform per step)
+template <bool AB>
 __global__ __launch_bounds__(TPB) void k_open_x(const E2* __restrict__ eq, DotTabs tabs, OpenPlan P, int ntab_all, size_t n, size_t chunk,
                                                 E2* __restrict__ partials, DotVirt V) {
     __shared__ E2 sm[TPB / 64];
@@ -2820,17 +2899,34 @@ __global__ __launch_bounds__(TPB) void k_open_x(const E2* __restrict__ eq, DotTa
     __shared__ int s_nact, s_l;
     const size_t row0 = (size_t)blockIdx.x * chunk, row1 = row0 + chunk < n ? row0 + chunk : n;
     const int ngm = (P.nmat + 7) / 8;
+    [[maybe_unused]] E2 ea = e2_zero();
+    if constexpr (AB) ea = eq[threadIdx.x];
     E2 acc[8];
 #pragma unroll
     for (int t = 0; t < 8; t++) acc[t] = e2_zero();
-    if ((int)blockIdx.y < ngm) {   // a group of materialised tables
+    if ((int)blockIdx.y < ngm) {   // a group of streamed tables
         const int t0 = blockIdx.y * 8;
         const int nt = P.nmat - t0 < 8 ? P.nmat - t0 : 8;
-        for (size_t j = row0 + threadIdx.x; j < row1; j += TPB) {
-            const E2 e = eq[j];
+        // (limb columns: the rows of this workgroup belong to one lookup - one mask; beyond `rows` the limbs are 0)
+        const u64 mask = P.nlimb && row0 < V.rows ? V.lookup_mask[V.seg_lookup[row0 >> V.seg_shift]] : 0;
+        for (size_t j0 = row0; j0 < row1; j0 += TPB) {
+            const size_t j = j0 + threadIdx.x;
+            E2 e;
+            if constexpr (AB) e = e2_mul(ea, eq[256 + (j0 >> 8)]);
+            if (j >= row1) break;
+            if constexpr (!AB) e = eq[j];
+            const u64 v = P.nlimb && j < V.rows ? V.input[j] & mask : 0;
 #pragma unroll
             for (int t = 0; t < 8; t++)
-                if (t < nt) acc[t] = e2_add(acc[t], e2_mul_f(e, tabs.t[P.mat[t0 + t]][j]));
+                if (t < nt) {
+                    const int ti = P.mat[t0 + t];
+                    const u64* __restrict__ tab = tabs.t[ti];
+                    if (tab) acc[t] = e2_add(acc[t], e2_mul_f(e, tab[j]));
+                    else {
+                        const u32 a = limb_of(v, -1 - tabs.emem[ti]);
+                        acc[t] = e2_add(acc[t], e2(gl_mul_small(e.c0, a), gl_mul_small(e.c1, a)));
+                    }
+                }
         }
 #pragma unroll
         for (int t = 0; t < 8; t++)
@@ -2859,8 +2955,12 @@ __global__ __launch_bounds__(TPB) void k_open_x(const E2* __restrict__ eq, DotTa
 #pragma unroll
     for (int k = 0; k < OPEN_ACT; k++) { const int m = k < nact ? s_act[k] : 0; sh[k] = 16 * V.mem_dim[m]; cut[k] = k < nact ? V.mem_cutoff[m] : 0u; }
     const size_t rend = row1 < V.rows ? row1 : V.rows;
-    for (size_t j = row0 + threadIdx.x; j < rend; j += TPB) {
-        const E2 e = eq[j];
+    for (size_t j0 = row0; j0 < rend; j0 += TPB) {
+        const size_t j = j0 + threadIdx.x;
+        E2 e;
+        if constexpr (AB) e = e2_mul(ea, eq[256 + (j0 >> 8)]);
+        if (j >= rend) break;
+        if constexpr (!AB) e = eq[j];
         const u64 v = V.input[j] & mask;
 #pragma unroll
         for (int k = 0; k < OPEN_ACT; k++) {
@@ -2880,22 +2980,64 @@ __global__ __launch_bounds__(TPB) void k_open_x(const E2* __restrict__ eq, DotTa
             partials[(size_t)blockIdx.x * ntab_all + vi] = val;
         }
 }
-bool open_x(hipStream_t st, const E2* eq, const DotTabs& tabs, int ntab, size_t n, E2* partials, E2* out, const DotVirt& virt) {
-    if (ntab <= 0 || ntab > DOT_MAX) return false;   // (false: the caller takes dot_eq_many's groups of eight)
+// rows per workgroup of open_x's launch, 0 where the shape does not fit
+static size_t open_x_chunk(const DotTabs& tabs, int ntab, size_t n, const DotVirt& virt) {
+    if (ntab <= 0 || ntab > DOT_MAX) return 0;
     const int gx = grid_for((n + 1) / 2);
-    if (n % (size_t)gx) return false;
+    if (n % (size_t)gx) return 0;
     const size_t chunk = n / (size_t)gx;
-    if ((chunk & (chunk - 1)) || chunk > ((size_t)1 << virt.seg_shift)) return false;
-    for (int l = 0; l < 32; l++) if (__builtin_popcountll(virt.lookup_uses[l]) > OPEN_ACT) return false;
+    if ((chunk & (chunk - 1)) || chunk > ((size_t)1 << virt.seg_shift)) return 0;
+    for (int l = 0; l < 32; l++) if (__builtin_popcountll(virt.lookup_uses[l]) > OPEN_ACT) return 0;
+    return chunk;
+}
+bool open_x_takes_ab(const DotTabs& tabs, int ntab, size_t n, const DotVirt& virt) {
+    const size_t chunk = open_x_chunk(tabs, ntab, n, virt);
+    return chunk >= 256 && n >= 256;   // (a power of two: whole rows of the A x B product)
+}
+bool open_x(hipStream_t st, const E2* eq, const DotTabs& tabs, int ntab, size_t n, E2* partials, E2* out, const DotVirt& virt, bool eq_is_ab) {
+    const size_t chunk = open_x_chunk(tabs, ntab, n, virt);
+    if (!chunk) {   // (false: the caller takes dot_eq_many's groups of eight)
+        if (eq_is_ab) throw std::runtime_error("open_x: the launch shape does not take factor tables");
+        return false;
+    }
+    if (eq_is_ab && !open_x_takes_ab(tabs, ntab, n, virt)) throw std::runtime_error("open_x: the launch shape does not take factor tables");
+    const int gx = (int)(n / chunk);
     OpenPlan P;
     memset(&P, 0, sizeof(P));
     for (int t = 0; t < ntab; t++) {
-        if (tabs.t[t]) P.mat[P.nmat++] = (short)t; else P.virt[P.nvirt++] = (short)t;
+        if (tabs.t[t]) P.mat[P.nmat++] = (short)t;
+        else if (tabs.emem[t] < 0) { P.mat[P.nmat++] = (short)t; P.nlimb++; }
+        else P.virt[P.nvirt++] = (short)t;
     }
     const int ngm = (P.nmat + 7) / 8;
-    k_open_x<<<dim3(gx, ngm + (P.nvirt ? 1 : 0)), TPB, 0, st>>>(eq, tabs, P, ntab, n, chunk, partials, virt);
+    const dim3 grid(gx, ngm + (P.nvirt ? 1 : 0));
+    if (eq_is_ab) k_open_x<true><<<grid, TPB, 0, st>>>(eq, tabs, P, ntab, n, chunk, partials, virt);
+    else k_open_x<false><<<grid, TPB, 0, st>>>(eq, tabs, P, ntab, n, chunk, partials, virt);
     k_dot_reduce<<<ntab, TPB, 0, st>>>(partials, gx, ntab, tabs, out);
     return true;
+}
+// one table against the factor tables of eq (n = 2^nvars >= 256 entries): two entries per thread, whose A entries stay put
+__global__ __launch_bounds__(TPB) void k_dot_eq_ab(const E2* __restrict__ ab, const u64* __restrict__ tab, size_t n, E2* __restrict__ partials) {
+    __shared__ E2 sm[TPB / 64];
+    const int lo = (2 * (int)threadIdx.x) & 255;
+    const E2 a0 = ab[lo], a1 = ab[lo + 1];
+    E2 acc = e2_zero();
+    for (size_t j = ((size_t)blockIdx.x * TPB + threadIdx.x) * 2; j < n; j += (size_t)gridDim.x * TPB * 2) {
+        const E2 b = ab[256 + (j >> 8)];
+        const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(tab + j);
+        acc = e2_add(acc, e2_add(e2_mul_f(e2_mul(a0, b), v.x), e2_mul_f(e2_mul(a1, b), v.y)));
+    }
+    const E2 s = block_sum(acc, sm);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+void dot_eq_ab(hipStream_t st, const E2* ab, int nvars, const u64* tab, E2* partials, E2* out) {
+    if (nvars < 8) throw std::runtime_error("dot_eq_ab: factor tables need at least 8 variables");
+    const size_t n = (size_t)1 << nvars;
+    const int gx = grid_for(n / 2);
+    DotTabs d;
+    memset(&d, 0, sizeof(d));
+    k_dot_eq_ab<<<gx, TPB, 0, st>>>(ab, tab, n, partials);
+    k_dot_reduce<<<1, TPB, 0, st>>>(partials, gx, 1, d, out);
 }
 void dot_eq(hipStream_t st, const E2* eq, const u64* const tabs[8], int ntab, size_t n, E2* partials, E2* out) {
     DotTabs d;

@@ -48,7 +48,7 @@ struct GpHashMem {
     int mem;             // "recompute it from the chunk's limb" (GpHashSrc::seg_lookup ...), the E tables are then never written
 };
 struct GpHashSrc {
-    const u64* dim[4];
+    const u64* dim[4];      // the limb table's columns; unused where the limbs come from the node input (`input` below)
     const u64* ts[4];
     const GpHashMem* mems;  // chunk-major (memory-GKR order)
     int nmem;
@@ -58,6 +58,11 @@ struct GpHashSrc {
     size_t rows;
     const uint8_t* seg_lookup;
     u64 lookup_uses[32];
+    // limbs without the limb table (LimbSrc): limb_sh = 16, `input` (and every dim[c]) is the node input and the chunk's dim value of
+    // row j is limb `chunk` of the input word under its lookup's mask. Limb table: limb_sh = 0, lookup_mask all ones.
+    const u64* input;
+    int limb_sh;
+    u64 lookup_mask[32];
     // Slot form of the mirrored top layer (prover.hip: grand_product): inside a lookup segment the memories the lookup does not use
     // have, per chunk position, identical hash rows, and the layer pairs segment s with s + npairs - memories in the same class in
     // both segments ("joint class") contribute w_b l r with the same l r. slot_of[row * npairs + sp] numbers the joint classes of
@@ -245,6 +250,10 @@ __host__ __device__ inline size_t eq_ab_entries(int n) { return 256 + ((size_t)1
 struct EqAbGrid { int prep, fill; };
 EqAbGrid eq_ab_plan(EqJob* host_jobs, int njobs);
 void eq_jobs_ab(hipStream_t st, const EqJob* jobs, int njobs, EqAbGrid grid, const E2* chal);
+// The prep launch alone, for a table with ONE reader that walks rows in workgroups of 256: the reader takes `ab` of a one-claim job
+// with unit alpha and n >= 8 and forms eq[j] = A[j & 255] * B[j >> 8] itself (A = ab[0 .. 255], B behind it) - the same canonical
+// product k_eq_fill would store, without the 16-byte store, the 16-byte load and the fill launch.
+void eq_jobs_prep(hipStream_t st, const EqJob* jobs, int njobs, EqAbGrid grid, const E2* chal);
 void sum_tables(hipStream_t st, E2* out, const E2* tabs, int ntabs, size_t n);  // out[i] = sum_t tabs[t*n + i]
 
 // ---- Lasso ------------------------------------------------------------------------------------
@@ -263,6 +272,14 @@ struct LassoDev {
     int cnt_nsegs[4];
     uint8_t cnt_segs[4][128];
 };
+// The limb table dims[c][j] (4 x 2^nu) is a cheap function of the node input: limb c of row j = ((input[j] & lookup_mask[lookup of
+// j's row segment]) >> 16 c) & 0xFFFF, 0 for j >= rows. Every reader of it has a form that takes the input instead (the device helper
+// limb_word / limb_of in kernels.hip): the mode-0 prover never writes the table. The forms that take a materialised table stay for the
+// round-by-round and the BN254 provers. The input forms take `rows` that end on a segment boundary, segments of two rows at least
+// (a 16-byte load of a row pair has one mask; the slot-form hash kernel's tile of 512 rows has one).
+struct LimbSrc { const u64* input; const uint8_t* seg_lookup; int seg_shift; size_t rows; u64 lookup_mask[32]; };
+LimbSrc limb_src(const LassoDev& L, const u64* input);
+inline bool limbs_from_input_ok(const LassoDev& L) { return L.seg_shift >= 1 && (L.rows & (((size_t)1 << L.seg_shift) - 1)) == 0; }
 // dims[c][j] (4 x 2^nu) and E[m][j] (alpha x 2^nu), zero beyond `rows`.
 // EpRows (multi-GPU: a rank only materialises the E tables of its own memories): row[m] = row of memory m in e_polys, -1 = not held.
 struct EpRows { signed char row[32]; };
@@ -283,19 +300,23 @@ void lasso_counters(hipStream_t st, const LassoDev& L, int m, const u64* dims, u
 struct CounterOut { u64* read_ts[4]; u64* final_cts[4]; };
 size_t lasso_counters_all_elems(const LassoDev& L, unsigned chunk_mask);             // number of (row, chunk) pairs to sort
 size_t lasso_counters_all_temp_bytes(size_t n_elems);
+// dims == nullptr: the limbs come from `input` (the node input)
 void lasso_counters_all(hipStream_t st, const LassoDev& L, unsigned chunk_mask, const u64* dims, const CounterOut& out, void* temp, size_t temp_bytes,
-                        u32* keys, u32* keys_sorted, u32* vals, u32* vals_sorted, u32* starts /* 4 * 65536 + 1 */);
+                        u32* keys, u32* keys_sorted, u32* vals, u32* vals_sorted, u32* starts /* 4 * 65536 + 1 */, const u64* input = nullptr);
 // sum_k eq[k] * sum_i M^i E_{mems(lookup(k))[i]}[k]  -> partials (nv = 1)
 // (memories not held - EpRows::row < 0 - contribute nothing: the ranks' partial claimed sums add up)
 int lasso_claim(hipStream_t st, const LassoDev& L, const E2* eq, const u64* e_polys, const EpRows& rows, E2* partials);
 // ... with the E values recomputed from the node input (no E tables); own = bit mask of the memories whose terms are summed
-int lasso_claim_in(hipStream_t st, const LassoDev& L, const E2* eq, const u64* input, u32 own, E2* partials);
+// eq_is_ab: `eq` is the factor tables of eq_jobs_prep (nu >= 8), not the table
+int lasso_claim_in(hipStream_t st, const LassoDev& L, const E2* eq, const u64* input, u32 own, E2* partials, bool eq_is_ab = false);
 // multiset hashes h = a + v*gamma + t*gamma^2 - tau
 // for up to HASH_RW_MAX memories of one chunk (shared dim / read_ts columns); n >= 4, a multiple of 4
 // rd1/wr1 (may be null): first product-tree level rd[j]*rd[j+n/2], wr[j]*wr[j+n/2], n/2 entries each
 constexpr int HASH_RW_MAX = 8;
 struct HashRwArgs { const u64* ep[HASH_RW_MAX]; u64* rd[HASH_RW_MAX]; u64* wr[HASH_RW_MAX]; u64* rd1[HASH_RW_MAX]; u64* wr1[HASH_RW_MAX]; };
-void lasso_hash_rw(hipStream_t st, size_t n, const u64* dim, const u64* read_ts, const HashRwArgs& args, int nmem, u64 gamma, u64 tau);
+// dim == nullptr: limb `chunk` of the node input (limbs)
+void lasso_hash_rw(hipStream_t st, size_t n, const u64* dim, const u64* read_ts, const HashRwArgs& args, int nmem, u64 gamma, u64 tau,
+                   const LimbSrc* limbs = nullptr, int chunk = 0);
 // init / final hashes of all G memories in one launch: H2[i] = init_i, H2[G + i] = final_i (2^16 entries each)
 struct HashIfArgs { u32 cutoff[32]; const u64* fc[32]; int row_init[32], row_fin[32]; };  // rows of H2 (2^16 entries each); -1 = skip
 void lasso_hash_if(hipStream_t st, const HashIfArgs& args, int G, u64 gamma, u64 tau, u64* H2);
@@ -313,7 +334,8 @@ void gp_top(hipStream_t st, const u64* top, int nb, E2* roots, E2* evals);
 void dot_eq(hipStream_t st, const E2* eq, const u64* const tabs[8], int ntab, size_t n, E2* partials, E2* out);
 // the same for up to DOT_MAX tables in one launch (+ one reduction launch): result t goes to out[tabs.slot[t]]
 constexpr int DOT_MAX = 64;
-struct DotTabs { const u64* t[DOT_MAX]; int slot[DOT_MAX]; signed char emem[DOT_MAX]; };   // t == nullptr: the E table of memory emem (DotVirt)
+// t == nullptr (DotVirt): emem >= 0: the E table of memory emem; emem = -1 - c: the limb table's column c
+struct DotTabs { const u64* t[DOT_MAX]; int slot[DOT_MAX]; signed char emem[DOT_MAX]; };
 // what recomputing E_m[j] = (row j's lookup uses m and limb < cutoff_m) ? limb : 0 takes (k_lasso_split): the node input and LassoDev's maps
 struct DotVirt {
     const u64* input; const uint8_t* seg_lookup; int seg_shift; size_t rows;
@@ -325,7 +347,12 @@ void dot_eq_many(hipStream_t st, const E2* eq, const DotTabs& tabs, int ntab, si
 // multiply-add per row and USED memory instead of one per row and memory, eq and the node input read once for all of them; the
 // materialised tables (chunk values, read counters) in groups of eight beside it. Returns false (nothing launched) when the shape
 // does not fit (rows per workgroup not a power of two inside a segment, a lookup with more than eight memories): use dot_eq_many.
-bool open_x(hipStream_t st, const E2* eq, const DotTabs& tabs, int ntab, size_t n, E2* partials, E2* out, const DotVirt& virt);
+// eq_is_ab: `eq` is the factor tables of eq_jobs_prep; only where open_x_takes_ab says so (the shape fits and a workgroup's rows are whole
+// rows of 256) - the caller decides with it whether to fill the table.
+bool open_x_takes_ab(const DotTabs& tabs, int ntab, size_t n, const DotVirt& virt);
+bool open_x(hipStream_t st, const E2* eq, const DotTabs& tabs, int ntab, size_t n, E2* partials, E2* out, const DotVirt& virt, bool eq_is_ab = false);
+// out[0] = sum_j eq[j] * tab[j] over 2^nvars entries, eq given by its factor tables (eq_jobs_prep; nvars >= 8)
+void dot_eq_ab(hipStream_t st, const E2* ab, int nvars, const u64* tab, E2* partials, E2* out);
 
 // ---- Vanilla / FFT nodes ----------------------------------------------------------------------
 struct CsrLin { const u32* ptr; const u32* gate; const u64* coef; };           // per input position -> (gate, c)

@@ -981,10 +981,15 @@ static void enqueue_prove(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, Prov
     // (on the main stream: moved behind the counter sorts on the second stream it starts the limb split 30 us earlier and changes
     // nothing at the end of the prove - and the launch graph's stream assignment is touchy about what forks first)
     if (P->mine(P->own_out_claim)) {
-        E2* eq = ctx->alloc_n<E2>((size_t)1 << ov);
-        P->eq_now(eq, ov, point_off);
-        const u64* tabs[8] = {v->d_ct0is};
-        dev::dot_eq(ctx->stream, eq, tabs, 1, (size_t)1 << ov, ctx->d_partials, P->d_res() + vslot);
+        // one reader: the dot product forms eq from its factor tables (HG_LASSO_TABLES=1, fewer than 8 variables: the table, filled)
+        E2* ab = Prover::lasso_tables() ? nullptr : P->eq_prep_now(ov, point_off);
+        if (ab) dev::dot_eq_ab(ctx->stream, ab, ov, v->d_ct0is, ctx->d_partials, P->d_res() + vslot);
+        else {
+            E2* eq = ctx->alloc_n<E2>((size_t)1 << ov);
+            P->eq_now(eq, ov, point_off);
+            const u64* tabs[8] = {v->d_ct0is};
+            dev::dot_eq(ctx->stream, eq, tabs, 1, (size_t)1 << ov, ctx->d_partials, P->d_res() + vslot);
+        }
     }
     Cell out_value = cell();
     P->cur_early = world == 1 && Prover::early_replay_on();   // (its slot is written ahead of the fork of the second stream)

@@ -323,6 +323,10 @@
         u32 own_mask = 0;
         for (int m = 0; m < A && m < 32; m++) if (own_mem[m]) own_mask |= 1u << m;
         // polynomialize (lasso.rs:157-250)
+        // The limb table (dims[c][j]: limb c of row j) is not written: every reader - counter sorts, hash round / hash tables, openings -
+        // takes the limbs from the node input it loads anyway (dev::LimbSrc). HG_LASSO_TABLES=1: the table, as the other provers keep it.
+        const bool limbs_in = !lasso_tables() && dev::limbs_from_input_ok(L);
+        const dev::LimbSrc limb_src = dev::limb_src(L, d_input);
         u64* dims = nullptr;
         u64* ep = nullptr;
         auto epm = [&](int m) -> const u64* {
@@ -330,7 +334,7 @@
             return ep + (size_t)ep_rows.row[m] * N;
         };
         if (need_split) {
-            dims = ctx->alloc_n<u64>(4 * N);
+            if (!limbs_in) dims = ctx->alloc_n<u64>(4 * N);
             // one more row behind the E tables: C = sum_m M^m E_m over this rank's memories - with E_0 all the collation sum-check needs
             ep = ctx->alloc_n<u64>((size_t)(ep_count + 1) * N);
             dev::ColPow cp;
@@ -341,13 +345,17 @@
             }
             // two streams: the limbs first, in their own small launch - the counter sorts (second stream) need nothing else and start
             // while the E tables are still being written
+            // (limbs from the input: nothing of the node is ahead of the event - it stays where it is, the counters still wait for it)
             if (fork_recorded) {
-                ctx->prof_begin(cls_aux, (double)N * 8 * (1 + 4));
-                dev::lasso_dims(st, L, d_input, dims);
-                ctx->prof_end();
+                if (!limbs_in) {
+                    ctx->prof_begin(cls_aux, (double)N * 8 * (1 + 4));
+                    dev::lasso_dims(st, L, d_input, dims);
+                    ctx->prof_end();
+                }
                 hip_check(hipEventRecord(ctx->ev_aux[0], st), "lasso: limbs event");
             }
-            ctx->prof_begin(cls_aux, (double)N * 8 * (1 + (fork_recorded ? 0 : 4) + ep_count + 1), (double)N * 8 * (1 + (fork_recorded ? 0 : 4) + ep_count_full + 1));
+            const int dim_rows = fork_recorded ? 0 : 4;   // (the reference's traffic model writes the limb table)
+            ctx->prof_begin(cls_aux, (double)N * 8 * (1 + (limbs_in ? 0 : dim_rows) + ep_count + 1), (double)N * 8 * (1 + dim_rows + ep_count_full + 1));
             dev::lasso_split(st, L, d_input, fork_recorded ? nullptr : dims, ep, ep_rows, &cp, ep + (size_t)ep_count * N);
             stamp("limb split done");
             ctx->prof_end();
@@ -372,7 +380,12 @@
         // r, claimed sum (lasso.rs:85, 264-269)
         size_t r_off = epos();
         for (int i = 0; i < nu; i++) squeeze();
-        E2* eq = (do_col || do_open) ? ctx->alloc_n<E2>(N) : nullptr;
+        // eq(r, .) and the opening point's table below have ONE reader each (the claimed sum, the openings at x): where the reader's
+        // launch shape admits it, only their factor tables are built (eq_prep_now) and the reader forms the product per row.
+        // HG_LASSO_TABLES=1: the tables, filled and read back.
+        E2* eq = nullptr;
+        auto eq_table = [&]() -> E2* { if (!eq) eq = ctx->alloc_n<E2>(N); return eq; };
+        bool claim_ab = false, open_ab = false;
         size_t claim_slot = slot(1);
         // Stream assignment inside the node (one rank): the main stream goes from the limb split to the first hash round; counters,
         // grand product #2's tree and the opening tables on the second stream; the collation rounds on the third (col_third below).
@@ -384,8 +397,10 @@
         // stream goes from the limb split straight into the collation rounds, the second stream is idle at that point anyway).
         const bool claim_late = use_aux;
         auto do_claim = [&] {
-            eq_now(eq, nu, r_off);
-            int grid = lean_e ? dev::lasso_claim_in(st, L, eq, d_input, own_mask, partials)
+            E2* ab = (lean_e && !lasso_tables()) ? eq_prep_now(nu, r_off) : nullptr;
+            claim_ab = ab != nullptr;
+            if (!ab) eq_now(eq_table(), nu, r_off);
+            int grid = lean_e ? dev::lasso_claim_in(st, L, ab ? ab : eq, d_input, own_mask, partials, ab != nullptr)
                               : dev::lasso_claim(st, L, eq, ep, ep_rows_own, partials);  // sharded: this rank's memories only (partial sum)
             reduce(grid, 1, claim_slot);
         };
@@ -450,7 +465,7 @@
             dev::CounterOut co;
             memset(&co, 0, sizeof(co));
             for (int c = 0; c < 4; c++) if ((mask >> c) & 1) { co.read_ts[c] = read_ts[c]; co.final_cts[c] = final_cts[c]; }
-            dev::lasso_counters_all(st, L, mask, dims, co, temp, tb, keys, keys2, rows, rows2, starts);
+            dev::lasso_counters_all(st, L, mask, dims, co, temp, tb, keys, keys2, rows, rows2, starts, limbs_in ? d_input : nullptr);
             ctx->prof_end();
             stamp("counters done");
             if (use_aux) { hip_check(hipEventRecord(ctx->ev_aux[3], st), "lasso: counters event"); counters_event_recorded = true; counters_event_live = true; }
@@ -476,7 +491,9 @@
             }
             dev::GpHashSrc hs;
             memset(&hs, 0, sizeof(hs));
-            for (int c = 0; c < 4; c++) { hs.dim[c] = dims + (size_t)c * N; hs.ts[c] = read_ts.count(c) ? read_ts[c] : nullptr; }
+            for (int c = 0; c < 4; c++) { hs.dim[c] = dims ? dims + (size_t)c * N : d_input; hs.ts[c] = read_ts.count(c) ? read_ts[c] : nullptr; }
+            if (limbs_in) { hs.input = d_input; hs.limb_sh = 16; memcpy(hs.lookup_mask, L.lookup_mask, sizeof(hs.lookup_mask)); }
+            else memset(hs.lookup_mask, 0xFF, sizeof(hs.lookup_mask));
             for (auto& m : hm) if (!hs.ts[m.chunk]) throw Error("lasso: counters of a needed chunk were not computed");
             dev::GpHashMem* d_hm = ctx->alloc_n<dev::GpHashMem>(hm.size());
             upload(d_hm, hm.data(), hm.size() * sizeof(dev::GpHashMem), "upload hash sources");
@@ -642,7 +659,7 @@
                     ha.ep[q] = epm(lp.gkr_order[r.i]); ha.rd[q] = r.rd; ha.wr[q] = r.wr; ha.rd1[q] = r.rd1; ha.wr1[q] = r.wr1;
                 }
                 ctx->prof_begin(cls_hash, (double)N * 8 * (2 + cnt * (L1 ? 4 : 3)));
-                dev::lasso_hash_rw(st, N, dims + (size_t)c * N, read_ts[c], ha, cnt, gamma, tau);
+                dev::lasso_hash_rw(st, N, dims ? dims + (size_t)c * N : nullptr, read_ts[c], ha, cnt, gamma, tau, &limb_src, c);
                 ctx->prof_end();
             }
         }
@@ -698,7 +715,6 @@
         // the order they were recorded, a few microseconds each, so the main stream's first grand-product kernel could not start before
         // everything recorded ahead of it was out - on a sharded rank, whose kernels are short, that left the main stream idle for
         // 100-150 us (scripts/ub/graph_order.hip shows the effect in isolation).
-        E2* eqx = (use_aux && do_open) ? ctx->alloc_n<E2>(N) : eq;  // (one stream: the eq(r,.) table is dead by now)
         E2* eqy = do_open ? ctx->alloc_n<E2>(M) : nullptr;
         // every opening at x in one launch, every opening at y in another (dev::dot_eq_many): results land in their wire slots
         dev::DotTabs tx, ty;
@@ -718,7 +734,8 @@
             const bool own_chunk = do_open && own_mem[chk.second[0]];
             const size_t base_slot = slot(3 + chk.second.size());
             if (own_chunk) {
-                add_x(dims + (size_t)c * N, base_slot);
+                if (dims) add_x(dims + (size_t)c * N, base_slot);
+                else { if (nx >= dev::DOT_MAX) throw Error("lasso: too many openings"); tx.t[nx] = nullptr; tx.emem[nx] = (signed char)(-1 - c); tx.slot[nx] = (int)base_slot; nx++; }
                 add_x(read_ts[c], base_slot + 1);
                 ty.t[ny] = final_cts[c]; ty.slot[ny] = (int)(base_slot + 2); ny++;
             }
@@ -740,35 +757,43 @@
             // the openings (two dot-product launches over every opened table: bandwidth) by value, so that they can also run later
             const dev::DotTabs txv = tx, tyv = ty;
             const int nxv = nx, nyv = ny;
-            const bool do_open_v = do_open, lean_v = lean_e;
-            E2 *eqx_v = eqx, *eqy_v = eqy;
+            const bool lean_v = lean_e;
+            E2* eqy_v = eqy;
             const size_t p1 = g1.point_off, p2 = g2.point_off;
-            const dev::LassoDev* Lp = &L;
+            dev::DotVirt dv;
+            memset(&dv, 0, sizeof(dv));
+            const bool virt_v = lean_e || limbs_in;   // tables recomputed from the node input among the opened ones
+            if (virt_v) {
+                dv.input = d_input; dv.seg_lookup = L.seg_lookup; dv.seg_shift = L.seg_shift; dv.rows = L.rows;
+                memcpy(dv.lookup_mask, L.lookup_mask, sizeof(dv.lookup_mask)); memcpy(dv.lookup_uses, L.lookup_uses, sizeof(dv.lookup_uses));
+                memcpy(dv.mem_dim, L.mem_dim, sizeof(dv.mem_dim)); memcpy(dv.mem_cutoff, L.mem_cutoff, sizeof(dv.mem_cutoff));
+            }
+            // (dot_eq_many's groups of eight re-read eq per group: where open_x does not take the shape the table is filled)
+            open_ab = do_open && lean_e && nx > 0 && !lasso_tables() && nu >= 8 && nu <= 24 && dev::open_x_takes_ab(tx, nx, N, dv);
             // the two eq tables of the opening points are challenges only: built right away on the second stream (beside the first hash
             // round), whatever the place of the dot products - at the end of the second stream they ran alone, 0.05 ms of its length
-            auto open_tables = [this, do_open_v, eqx_v, eqy_v, p1, p2, nu] {
-                if (do_open_v) {
+            E2* eqx_v = nullptr;   // the table, or its factor tables (open_ab)
+            aux([&] {
+                if (!do_open) return;
+                if (open_ab) eqx_v = eq_prep_now(nu, p1);
+                else {
+                    eqx_v = use_aux ? ctx->alloc_n<E2>(N) : eq_table();  // (one stream: the eq(r,.) table is dead by now)
                     eq_now(eqx_v, nu, p1);
-                    eq_now(eqy_v, 16, p2);
                 }
-            };
-            auto openings = [this, txv, tyv, nxv, nyv, lean_v, eqx_v, eqy_v, Lp, d_input, N] {
+                eq_now(eqy_v, 16, p2);
+            });
+            if (open_ab && !eqx_v) throw Error("lasso: no factor tables for the opening point");
+            const bool open_ab_v = open_ab;
+            if (use_aux && world == 1) hip_check(hipEventRecord(ctx->ev_aux[4], ctx->stream2), "lasso: opening tables event");
+            auto openings = [this, txv, tyv, nxv, nyv, lean_v, virt_v, eqx_v, eqy_v, dv, open_ab_v, N] {
                 if (nxv) {
                     int nvirt = 0;
                     for (int t = 0; t < nxv; t++) nvirt += txv.t[t] == nullptr;
                     // (a group of eight re-reads eq; recomputed E tables cost their group one 8-byte input read per entry)
                     ctx->prof_begin(cls_aux, (double)N * (16.0 * ((nxv + 7) / 8) + 8.0 * (nxv - nvirt) + (nvirt ? 8.0 * ((nxv + 7) / 8) : 0.0)),
                                     (double)N * (16.0 * ((nxv + 7) / 8) + 8.0 * nxv));   // (reference model: every opened table is read)
-                    dev::DotVirt dv;
-                    memset(&dv, 0, sizeof(dv));
-                    if (lean_v) {
-                        const dev::LassoDev& L = *Lp;
-                        dv.input = d_input; dv.seg_lookup = L.seg_lookup; dv.seg_shift = L.seg_shift; dv.rows = L.rows;
-                        memcpy(dv.lookup_mask, L.lookup_mask, sizeof(dv.lookup_mask)); memcpy(dv.lookup_uses, L.lookup_uses, sizeof(dv.lookup_uses));
-                        memcpy(dv.mem_dim, L.mem_dim, sizeof(dv.mem_dim)); memcpy(dv.mem_cutoff, L.mem_cutoff, sizeof(dv.mem_cutoff));
-                    }
-                    if (!(lean_v && dev::open_x(st, eqx_v, txv, nxv, N, partials, d_res(), dv)))
-                        dev::dot_eq_many(st, eqx_v, txv, nxv, N, partials, d_res(), lean_v ? &dv : nullptr);
+                    if (!(lean_v && dev::open_x(st, eqx_v, txv, nxv, N, partials, d_res(), dv, open_ab_v)))
+                        dev::dot_eq_many(st, eqx_v, txv, nxv, N, partials, d_res(), virt_v ? &dv : nullptr);
                     ctx->prof_end();
                 }
                 if (nyv) dev::dot_eq_many(st, eqy_v, tyv, nyv, M, partials, d_res());
@@ -781,12 +806,18 @@
             // the main stream behind the grand products (1.87-1.91; the round-4 default) against 1.83-1.86 ms; a fourth stream for the
             // node reductions alone: 1.85 - a replayed launch graph does not run a fourth branch beside the other three (its first
             // kernel starts 0.6 ms into the prove, with or without GPU_MAX_HW_QUEUES=8).
-            aux(open_tables);
             if (use_aux && world == 1) {
-                hip_check(hipEventRecord(ctx->ev_aux[4], ctx->stream2), "lasso: opening tables event");
                 late_col.push_back(openings);
             } else if (use_aux) late_aux.push_back(openings);
             else aux(openings);
+        }
+        // which form each piece took (out_eq: the output claim's table, enqueue_prove - the same rule, stated here). HG_DEBUG=plan,lasso:
+        // a token of its own, since the launch-plan lines of HG_DEBUG=plan are all numbers and are read as such
+        if (hg_debug("lasso")) {
+            const int ov = pk->params.ct0is_log2();
+            const bool out_ab = !lasso_tables() && eq_two_launch() && ov >= 8 && ov <= 24;
+            fprintf(stderr, "[hg plan] lasso limbs=%s claim_eq=%s open_eq=%s out_eq=%s\n", limbs_in ? "input" : "table", claim_ab ? "factored" : "table",
+                    open_ab ? "factored" : "table", out_ab ? "factored" : "table");
         }
         stamp("grand products done");
         return ClaimRef{r_off, nu, claimed};  // (r, claimed_sum) for the single predecessor (lasso.rs:97,113)

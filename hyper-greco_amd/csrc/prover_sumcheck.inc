@@ -702,6 +702,25 @@
         else dev::eq_jobs(st, d, 1, n, ctx->d_chal);
         ctx->prof_end();
     }
+    // The factor tables of the same table alone (k_eq_prep, no fill): for a table with ONE reader that forms A[j & 255] * B[j >> 8] per
+    // row itself (dev::eq_jobs_prep). nullptr where that form does not exist (fewer than 8 variables, more than 24): use eq_now.
+    E2* eq_prep_now(int n, size_t point_off) {
+        if (!eq_two_launch() || n < 8 || n > 24) return nullptr;
+        dev::EqJob J;
+        memset(&J, 0, sizeof(J));
+        J.n = n;
+        J.cs.n = 1; J.cs.unit_alpha = 1; J.cs.point_off[0] = point_off;
+        J.ab = ctx->alloc_n<E2>(dev::eq_ab_entries(n));
+        const dev::EqAbGrid grid = dev::eq_ab_plan(&J, 1);
+        dev::EqJob* d = ctx->alloc_n<dev::EqJob>(1);
+        upload(d, &J, sizeof(J), "upload eq job");
+        ctx->prof_begin(cls_aux, 16.0 * dev::eq_ab_entries(n), 16.0 * ((size_t)1 << n));   // (reference model: the table is written)
+        dev::eq_jobs_prep(st, d, 1, grid, ctx->d_chal);
+        ctx->prof_end();
+        return J.ab;
+    }
+    // HG_LASSO_TABLES=1: the general form of the Lasso node's single-reader eq tables (and of the output claim's) - filled, then read
+    static bool lasso_tables() { static const bool on = hg_env_on("HG_LASSO_TABLES"); return on; }
     std::vector<std::function<void()>> eq_post;  // sums of per-claim eq tables, run right after the eq batch
     // (tables of more than 2^24 entries take the one-launch kernel, whose workgroups rebuild their own low / high factor tables)
     static bool eq_two_launch() { return true; }
