@@ -174,6 +174,64 @@ __device__ __forceinline__ u64 wreduce(const WAcc& w) {
     return u;
 }
 
+// restart: the canonical value so far as the start of a fresh accumulator (its low word is a plain residue; the counters start at 0)
+__device__ __forceinline__ WAcc wacc_from(u64 x) { WAcc w = wacc_zero(); w.L = x; return w; }
+
+// Capacity of a WAcc, for loops whose trip count nothing bounds: wreduce wants the carry counters below 2^8. One product adds at most
+// one carry to tL, two to tM (two partial products of weight 2^32) and one to tH; wmac_pair adds two products, so at most 2 / 4 / 2.
+// A loop that calls wmac / wmac2 at most twice or wmac_pair at most once per accumulator and trip therefore banks at most 4 carries per
+// counter and trip, and after WFLUSH_TRIPS = 16 trips at most 64 (+ 1: a start value in L) - a quarter of the bound. Such loops reduce
+// and restart (wacc_from) every WFLUSH_TRIPS trips; 16 is short enough for a test to cross it several times at a moderate size, and
+// where a thread makes 8 trips (2^21 rows over 1024 workgroups of 256) it never fires.
+constexpr int WFLUSH_TRIPS = 16;
+
+// Narrow accumulator for SMALL multiplicands (the 16-bit limbs of the Lasso node's inputs) times any 64-bit residue x = x0 + x1 2^32:
+//   value(WNar) = L + M 2^32,   L += a x0,  M += a x1   (two v_mad_u64_u32, no carry to bank, 4 VGPRs against WAcc's 9)
+// Capacity: with a < 2^16 a term is below 2^16 (2^32 - 1) < 2^48, so 2^16 - 1 terms on top of a start value below 2^32 stay below
+// 2^64 in each column. wnar_from starts both columns below 2^32; callers restart every WFLUSH_TRIPS trips like the WAcc loops, far
+// inside that bound (multiplicands up to 2^32 would need the carry counters back: not built, no caller has them).
+struct WNar {
+    u64 L, M;
+};
+__device__ __forceinline__ WNar wnar_zero() { WNar w; w.L = w.M = 0; return w; }
+__device__ __forceinline__ WNar wnar_from(u64 x) { WNar w; w.L = (u32)x; w.M = x >> 32; return w; }
+// w += a * x   (a < 2^16)
+__device__ __forceinline__ void wnar_mac(WNar& w, u32 a, u64 x) {
+    w.L += (u64)a * (u32)x;
+    w.M += (u64)a * (u32)(x >> 32);
+}
+__device__ __forceinline__ u64 wnar_reduce(const WNar& w) {
+    // L + M0 2^32 + M1 2^64: the low 64 bits and their carry, then M1 + carry < 2^33 as the high word
+    const u64 m0 = w.M << 32;
+    const u64 lo = w.L + m0;
+    const u64 hi = (w.M >> 32) + (lo < m0 ? 1u : 0u);
+    return gl_reduce128(lo, hi);
+}
+// an Ext2 value times small multiplicands: one narrow accumulator per coordinate
+struct WNar2 {
+    WNar c0, c1;
+};
+__device__ __forceinline__ WNar2 wnar2_zero() { WNar2 w; w.c0 = wnar_zero(); w.c1 = wnar_zero(); return w; }
+__device__ __forceinline__ WNar2 wnar2_from(E2 x) { WNar2 w; w.c0 = wnar_from(x.c0); w.c1 = wnar_from(x.c1); return w; }
+__device__ __forceinline__ void wnar2_mac(WNar2& w, E2 e, u32 a) { wnar_mac(w.c0, a, e.c0); wnar_mac(w.c1, a, e.c1); }
+__device__ __forceinline__ E2 wnar2_reduce(const WNar2& w) { return e2(wnar_reduce(w.c0), wnar_reduce(w.c1)); }
+
+// two column accumulators hold an unreduced sum of Ext2 products, one per coordinate
+struct W2 {
+    WAcc c0, c1;
+};
+__device__ __forceinline__ W2 w2_zero() { W2 w; w.c0 = wacc_zero(); w.c1 = wacc_zero(); return w; }
+__device__ __forceinline__ W2 w2_from(E2 x) { W2 w; w.c0 = wacc_from(x.c0); w.c1 = wacc_from(x.c1); return w; }
+// w += a * b over Ext2 (X^2 = 7): two products per coordinate
+__device__ __forceinline__ void w2_mac(W2& w, E2 a, E2 b) {
+    const u64 a7 = gl_mul7_lazy(a.c1);  // any 64-bit residue will do as a multiplicand
+    wmac_pair(w.c0, a.c0, b.c0, a7, b.c1);
+    wmac_pair(w.c1, a.c0, b.c1, a.c1, b.c0);
+}
+// w += e * v for a base-field residue v: one product per coordinate
+__device__ __forceinline__ void w2_mac_f(W2& w, E2 e, u64 v) { wmac2(w.c0, e.c0, v, w.c1, e.c1, v); }
+__device__ __forceinline__ E2 w2_reduce(const W2& w) { return e2(wreduce(w.c0), wreduce(w.c1)); }
+
 // three column accumulators hold an unreduced Ext2 dot product: A = sum a0 b0, B = sum a1 b1, C = sum a0 b1 + a1 b0
 struct WE2 {
     WAcc A, B, C;
@@ -198,5 +256,8 @@ __device__ __forceinline__ E2 e2_fold_wide(E2 x, E2 d, const FoldR& f) {
     const WAcc b = wacc_pair_init(x.c1, f.r0, d.c1, f.r1, d.c0);
     return e2(wreduce(a), wreduce(b));
 }
+// a * b for a loop-invariant a = fold_r's argument (the A entry of eq's factor tables times a table's sum): the fold on top of 0 - four products in two column
+// accumulators and ONE reduction per coordinate, against Karatsuba's three reduced products, the product by 7 and five canonical adds
+__device__ __forceinline__ E2 e2_mul_wide(const FoldR& fa, E2 b) { return e2_fold_wide(e2_zero(), b, fa); }
 
 }  // namespace hg

@@ -318,6 +318,13 @@ __device__ __forceinline__ void sc_round_body(const T* __restrict__ in, size_t i
     const int jj = tid & ((1 << jb_log2) - 1), g = tid >> jb_log2;
     const size_t ntiles = half >> jb_log2;  // host guarantees 2^jb_log2 <= half
     [[maybe_unused]] GpItemE2 gp_cur = gp_item_any();   // (grand product, later rounds: the item in flight across the tile loop)
+    // collation: p_0 * (sum over the tables) at 0 and 2, summed over the tiles unreduced (gl_wide.hpp: one w2_mac / w2_mac_f per
+    // accumulator and tile, restarted every WFLUSH_TRIPS tiles) and reduced once behind the loop
+    // (kept where it measured faster - the base-field first round and the LDS tail, whose one workgroup walks every tile; the Ext2
+    // rounds of k_st_step, a tile or two per thread, showed no gain for 40 more registers and keep the product per tile)
+    constexpr bool COL_WIDE = KIND != SC_GRANDPROD && (std::is_same<T, u64>::value || !GIO);
+    [[maybe_unused]] W2 col0 = w2_zero(), col2 = w2_zero();
+    [[maybe_unused]] int col_trips = 0;
     for (size_t tile = first_tile; tile < ntiles; tile += tile_step) {
         const size_t j = (tile << jb_log2) + jj;
         const size_t jo = dpos(j, half);  // this round's output (length `half`) is written de-interleaved
@@ -477,11 +484,20 @@ __device__ __forceinline__ void sc_round_body(const T* __restrict__ in, size_t i
                 }
                 __syncthreads();
             }
-            if (g == 0) {
-                acc[0] = e2_add(acc[0], e2_mul(V::lift(p0), t0));
-                acc[1] = e2_add(acc[1], e2_mul(V::lift(p2), t2));
+            if (g == 0) {   // (behind the sum over the table groups: the quirky g = p_0 * (sum_i ..))
+                if constexpr (!COL_WIDE) {
+                    acc[0] = e2_add(acc[0], e2_mul(V::lift(p0), t0));
+                    acc[1] = e2_add(acc[1], e2_mul(V::lift(p2), t2));
+                } else {
+                    if constexpr (std::is_same<T, u64>::value) { w2_mac_f(col0, t0, p0); w2_mac_f(col2, t2, p2); }   // base-field p_0: no lift
+                    else { w2_mac(col0, p0, t0); w2_mac(col2, p2, t2); }
+                    if (++col_trips == WFLUSH_TRIPS) { col0 = w2_from(w2_reduce(col0)); col2 = w2_from(w2_reduce(col2)); col_trips = 0; }
+                }
             }
         }
+    }
+    if constexpr (COL_WIDE) {
+        if (g == 0) { acc[0] = e2_add(acc[0], w2_reduce(col0)); acc[1] = e2_add(acc[1], w2_reduce(col2)); }
     }
 }
 
@@ -1026,14 +1042,6 @@ void st_first_hash(hipStream_t st, const StJob* job, const StItem* item, int gri
 // d'l d'r is split by Ext2 coordinate (the sign of d' cancels in the product). Round-t sums use two column
 // accumulators per Ext2 sum (7 a1 pre-multiplied), so the register count stays that of the single-round kernel.
 // HBM traffic per (pair, j): 64 B read + 16 B written instead of (64 + 32) + (32 + 16).
-struct W2 { WAcc c0, c1; };
-__device__ __forceinline__ W2 w2_zero() { W2 w; w.c0 = wacc_zero(); w.c1 = wacc_zero(); return w; }
-__device__ __forceinline__ void w2_mac(W2& w, E2 a, E2 b) {
-    const u64 a7 = gl_mul7_lazy(a.c1);  // any 64-bit residue will do as a multiplicand
-    wmac_pair(w.c0, a.c0, b.c0, a7, b.c1);
-    wmac_pair(w.c1, a.c0, b.c1, a.c1, b.c0);
-}
-__device__ __forceinline__ E2 w2_reduce(const W2& w) { return e2(wreduce(w.c0), wreduce(w.c1)); }
 __device__ __forceinline__ u64 swap_lane_u64(u64 v) {
     u32 lo = (u32)v, hi = (u32)(v >> 32);
     lo = (u32)__builtin_amdgcn_mov_dpp((int)lo, 0xB1, 0xF, 0xF, true);  // quad_perm:[1,0,3,2]
@@ -1182,9 +1190,11 @@ __global__ __launch_bounds__(256) void k_col_step2(const StJob* __restrict__ job
     const FoldR fa = fold_r(chal[J.r_off + rd]);
     const E2 rb = chal[J.r_off + rd + 1];
     const FoldR fb = fold_r(odd ? e2_sub(e2_one(), rb) : rb);  // odd lane: y' + (1 - r)(x' - y')
-    E2 acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) acc[t] = e2_zero();
+    // The four products per tile are summed over the tiles unreduced (gl_wide.hpp: one w2_mac per accumulator and tile, restarted every
+    // WFLUSH_TRIPS tiles) and reduced once ahead of the workgroup sum. Round t+1's two share ONE accumulator: the even lane adds
+    // q0 * (sum x'), the odd lane q2 * (2 sum y' - sum x') from its own side of the pair, and the lanes' parity sorts them at the end.
+    W2 w0 = w2_zero(), w2 = w2_zero(), wq = w2_zero();
+    int trips = 0;
     for (size_t tile = bx; tile < ntiles; tile += nblocks) {
         const size_t j = (tile << 8) + tid;
         const size_t jo2 = dpos(j >> 1, half2);
@@ -1210,14 +1220,15 @@ __global__ __launch_bounds__(256) void k_col_step2(const StJob* __restrict__ job
             const E2 fx = odd ? mb : ma, fd = odd ? e2_sub(ob, mb) : e2_sub(oa, ma);
             if (!odd || two) store_e2(out + (size_t)(i + (odd ? 1 : 0)) * half2 + jo2, e2_fold_wide(fx, fd, fb));
         }
-        acc[0] = e2_add(acc[0], e2_mul(p0, s0));
-        acc[1] = e2_add(acc[1], e2_mul(p2, s2));
+        w2_mac(w0, p0, s0);
+        w2_mac(w2, p2, s2);
         const E2 other = swap_lane(own);
-        if (!odd) {  // s0' = sum x', s2' = sum (2 y' - x')
-            acc[2] = e2_add(acc[2], e2_mul(q0, own));
-            acc[3] = e2_add(acc[3], e2_mul(q2, e2_sub(e2_dbl(other), own)));
-        }
+        // s0' = sum x' (the even lane's own), s2' = sum (2 y' - x') (the odd lane's own is sum y')
+        w2_mac(wq, odd ? q2 : q0, odd ? e2_sub(e2_dbl(own), other) : own);
+        if (++trips == WFLUSH_TRIPS) { w0 = w2_from(w2_reduce(w0)); w2 = w2_from(w2_reduce(w2)); wq = w2_from(w2_reduce(wq)); trips = 0; }
     }
+    const E2 rq = w2_reduce(wq);
+    E2 acc[4] = {w2_reduce(w0), w2_reduce(w2), odd ? e2_zero() : rq, odd ? rq : e2_zero()};
     E2* sm = dyn_lds;
     E2* part = partials + (size_t)y * SC_MAX_BLOCKS * 4;
     block_sum_multi<4>(acc, sm);
@@ -2629,15 +2640,18 @@ template <bool AB>
 __global__ __launch_bounds__(TPB) void k_lasso_claim_in(LassoDev L, const E2* __restrict__ eq, const u64* __restrict__ input, u32 own,
                                                         E2* __restrict__ partials) {
     __shared__ E2 sm[TPB / 64];
-    E2 acc = e2_zero();
-    [[maybe_unused]] E2 ea = e2_zero();
-    if constexpr (AB) ea = eq[threadIdx.x];
+    // the eq-weighted sum stays unreduced (gl_wide.hpp): one product per trip into each column accumulator, restarted every WFLUSH_TRIPS trips
+    W2 acc = w2_zero();
+    int trips = 0;
+    [[maybe_unused]] FoldR fa = fold_r(e2_zero());
+    if constexpr (AB) fa = fold_r(eq[threadIdx.x]);
     for (size_t k0 = (size_t)blockIdx.x * TPB; k0 < L.rows; k0 += (size_t)gridDim.x * TPB) {
         const size_t k = k0 + threadIdx.x;
-        E2 e;
-        if constexpr (AB) e = e2_mul(ea, eq[256 + (k0 >> 8)]);
         if (k >= L.rows) break;
-        if constexpr (!AB) e = eq[k];
+        // AB: the step's B entry (uniform) is the weight and the thread's A entry, the same for all of its rows, multiplies the sum once
+        E2 e;
+        if constexpr (AB) e = eq[256 + (k0 >> 8)];
+        else e = eq[k];
         const int l = L.seg_lookup[k >> L.seg_shift];
         const u64 v = input[k] & L.lookup_mask[l];
         u64 comb = 0;  // combine_lookups (range.rs:184-195): sum_i M^i * operand_i
@@ -2647,9 +2661,12 @@ __global__ __launch_bounds__(TPB) void k_lasso_claim_in(LassoDev L, const E2* __
             const u32 a = (u32)(v >> (16 * L.mem_dim[m])) & 0xFFFF;
             if (a < L.mem_cutoff[m]) comb = gl_add(comb, gl_mul_small(L.mpow[i], a));
         }
-        acc = e2_add(acc, e2_mul_f(e, comb));
+        w2_mac_f(acc, e, comb);
+        if (++trips == WFLUSH_TRIPS) { acc = w2_from(w2_reduce(acc)); trips = 0; }
     }
-    E2 s = block_sum(acc, sm);
+    E2 mine = w2_reduce(acc);
+    if constexpr (AB) mine = e2_mul_wide(fa, mine);
+    E2 s = block_sum(mine, sm);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 int lasso_claim_in(hipStream_t st, const LassoDev& L, const E2* eq, const u64* input, u32 own, E2* partials, bool eq_is_ab) {
@@ -2877,7 +2894,8 @@ void dot_eq_many(hipStream_t st, const E2* eq, const DotTabs& tabs, int ntab, si
     if (ntab <= 0) return;
     if (ntab > DOT_MAX) throw std::runtime_error("dot_eq_many: too many tables");
     // (measured slower here: column accumulators - 8 independent 8-byte streams per thread need the occupancy more -
-    // and the last-arriving-workgroup reduction - 8 values x 1024 partials)
+    // and the last-arriving-workgroup reduction - 8 values x 1024 partials; measured again with the tables walked four at a time, W2
+    // accumulators restarted every WFLUSH_TRIPS trips, 118 VGPRs = 4 waves per SIMD: 10.0-10.6 against 10.4 us per launch - not kept)
     const int gx = grid_for((n + 1) / 2);
     DotVirt V;
     memset(&V, 0, sizeof(V));
@@ -2891,48 +2909,103 @@ struct OpenPlan { int nmat, nvirt, nlimb; short mat[DOT_MAX], virt[DOT_MAX]; };
 constexpr int OPEN_ACT = 8;
 // AB: `eq` holds the factor tables k_eq_prep leaves (A: 256 entries, then B) and eq[j] = A[j & 255] * B[j >> 8] is formed here (a
 // workgroup's rows are whole table rows of 256: a thread keeps its A entry, the B entry is uniform per step)
+// The sums stay unreduced (gl_wide.hpp) and are reduced once per thread and table. AB: a step's weight is its B entry (uniform over the
+// workgroup) and the thread's A entry, the same for all of its rows, multiplies each table's sum once after the loop: no product per
+// row. With nothing per row left to share between the tables, a workgroup walks its rows once per table behind a pointer (any 64-bit
+// residue: a pair of column accumulators), once for the limb columns and once per four E memories (16-bit multiplicands: narrow
+// accumulators), U steps at a time: the U loads of a table are in flight together and a pass holds the accumulators of its own
+// tables only.
+constexpr int OPEN_PASS_E = 4;
 template <bool AB>
 __global__ __launch_bounds__(TPB) void k_open_x(const E2* __restrict__ eq, DotTabs tabs, OpenPlan P, int ntab_all, size_t n, size_t chunk,
                                                 E2* __restrict__ partials, DotVirt V) {
     __shared__ E2 sm[TPB / 64];
     __shared__ int s_act[OPEN_ACT];
     __shared__ int s_nact, s_l;
+    // steps per block: UP in a pointer table's pass (18 registers of accumulators), UN in a narrow pass (32); AB: the weights are scalars,
+    // else a weight is four registers per step
+    constexpr int UP = 4, UN = AB ? 4 : 2;
+    static_assert(WFLUSH_TRIPS % UP == 0 && WFLUSH_TRIPS % UN == 0, "the accumulators restart after whole blocks of steps");
     const size_t row0 = (size_t)blockIdx.x * chunk, row1 = row0 + chunk < n ? row0 + chunk : n;
     const int ngm = (P.nmat + 7) / 8;
-    [[maybe_unused]] E2 ea = e2_zero();
-    if constexpr (AB) ea = eq[threadIdx.x];
-    E2 acc[8];
+    [[maybe_unused]] FoldR fa = fold_r(e2_zero());
+    if constexpr (AB) fa = fold_r(eq[threadIdx.x]);
+    // the weights of the U steps from row jb on (zero past `end`)
+    auto weights = [&](size_t jb, size_t end, auto& e) {
+        constexpr int U = sizeof(e) / sizeof(E2);
 #pragma unroll
-    for (int t = 0; t < 8; t++) acc[t] = e2_zero();
+        for (int u = 0; u < U; u++) {
+            const size_t j0 = jb + (size_t)u * TPB;
+            if constexpr (AB) e[u] = j0 < end ? eq[256 + (j0 >> 8)] : e2_zero();
+            else e[u] = j0 + threadIdx.x < end ? eq[j0 + threadIdx.x] : e2_zero();
+        }
+    };
+    auto finish = [&](E2 s) -> E2 {
+        if constexpr (AB) return e2_mul_wide(fa, s);
+        else return s;
+    };
     if ((int)blockIdx.y < ngm) {   // a group of streamed tables
         const int t0 = blockIdx.y * 8;
         const int nt = P.nmat - t0 < 8 ? P.nmat - t0 : 8;
-        // (limb columns: the rows of this workgroup belong to one lookup - one mask; beyond `rows` the limbs are 0)
-        const u64 mask = P.nlimb && row0 < V.rows ? V.lookup_mask[V.seg_lookup[row0 >> V.seg_shift]] : 0;
-        for (size_t j0 = row0; j0 < row1; j0 += TPB) {
-            const size_t j = j0 + threadIdx.x;
-            E2 e;
-            if constexpr (AB) e = e2_mul(ea, eq[256 + (j0 >> 8)]);
-            if (j >= row1) break;
-            if constexpr (!AB) e = eq[j];
-            const u64 v = P.nlimb && j < V.rows ? V.input[j] & mask : 0;
+        int col[4] = {-1, -1, -1, -1};   // >= 0: limb column c is among the group's tables
+        for (int t = 0; t < nt; t++) {
+            const int x = P.mat[t0 + t];
+            const u64* __restrict__ tab = tabs.t[x];
+            if (!tab) {
+                const int c = -1 - tabs.emem[x];
 #pragma unroll
-            for (int t = 0; t < 8; t++)
-                if (t < nt) {
-                    const int ti = P.mat[t0 + t];
-                    const u64* __restrict__ tab = tabs.t[ti];
-                    if (tab) acc[t] = e2_add(acc[t], e2_mul_f(e, tab[j]));
-                    else {
-                        const u32 a = limb_of(v, -1 - tabs.emem[ti]);
-                        acc[t] = e2_add(acc[t], e2(gl_mul_small(e.c0, a), gl_mul_small(e.c1, a)));
-                    }
-                }
+                for (int k = 0; k < 4; k++) if (c == k) col[k] = x;
+                continue;
+            }
+            W2 acc = w2_zero();
+            int blocks = 0;
+            for (size_t jb = row0; jb < row1; jb += (size_t)UP * TPB) {
+                E2 e[UP];
+                u64 v[UP];
+                weights(jb, row1, e);
+#pragma unroll
+                for (int u = 0; u < UP; u++) { const size_t j = jb + (size_t)u * TPB + threadIdx.x; v[u] = j < row1 ? tab[j] : 0; }
+#pragma unroll
+                for (int u = 0; u < UP; u++) w2_mac_f(acc, e[u], v[u]);
+                if (++blocks == WFLUSH_TRIPS / UP) { acc = w2_from(w2_reduce(acc)); blocks = 0; }
+            }
+            const E2 r = block_sum(finish(w2_reduce(acc)), sm);
+            if (threadIdx.x == 0) partials[(size_t)blockIdx.x * ntab_all + x] = r;
+        }
+        if (col[0] < 0 && col[1] < 0 && col[2] < 0 && col[3] < 0) return;
+        // limb columns: the rows of this workgroup belong to one lookup - one mask; beyond `rows` the limbs are 0
+        const u64 mask = row0 < V.rows ? V.lookup_mask[V.seg_lookup[row0 >> V.seg_shift]] : 0;
+        const size_t rend = row1 < V.rows ? row1 : V.rows;
+        WNar2 acc[4];
+#pragma unroll
+        for (int c = 0; c < 4; c++) acc[c] = wnar2_zero();
+        int blocks = 0;
+        for (size_t jb = row0; jb < rend; jb += (size_t)UN * TPB) {
+            E2 e[UN];
+            u64 v[UN];
+            weights(jb, rend, e);
+#pragma unroll
+            for (int u = 0; u < UN; u++) { const size_t j = jb + (size_t)u * TPB + threadIdx.x; v[u] = j < rend ? V.input[j] & mask : 0; }
+#pragma unroll
+            for (int u = 0; u < UN; u++) {
+#pragma unroll
+                for (int c = 0; c < 4; c++) if (col[c] >= 0) wnar2_mac(acc[c], e[u], limb_of(v[u], c));
+            }
+            if (++blocks == WFLUSH_TRIPS / UN) {
+                blocks = 0;
+#pragma unroll
+                for (int c = 0; c < 4; c++) acc[c] = wnar2_from(wnar2_reduce(acc[c]));
+            }
         }
 #pragma unroll
-        for (int t = 0; t < 8; t++)
-            if (t < nt) {
-                const E2 s = block_sum(acc[t], sm);
-                if (threadIdx.x == 0) partials[(size_t)blockIdx.x * ntab_all + P.mat[t0 + t]] = s;
+        for (int c = 0; c < 4; c++)
+            if (col[c] >= 0) {   // (uniform: the barriers inside match)
+                const E2 r = block_sum(finish(wnar2_reduce(acc[c])), sm);
+                if (threadIdx.x == 0)
+                    for (int t = 0; t < nt; t++) {
+                        const int x = P.mat[t0 + t];
+                        if (!tabs.t[x] && -1 - tabs.emem[x] == c) partials[(size_t)blockIdx.x * ntab_all + x] = r;
+                    }
             }
         return;
     }
@@ -2950,34 +3023,59 @@ __global__ __launch_bounds__(TPB) void k_open_x(const E2* __restrict__ eq, DotTa
     __syncthreads();
     const int nact = s_nact;
     const u64 mask = V.lookup_mask[s_l];
-    int sh[OPEN_ACT];
-    u32 cut[OPEN_ACT];
-#pragma unroll
-    for (int k = 0; k < OPEN_ACT; k++) { const int m = k < nact ? s_act[k] : 0; sh[k] = 16 * V.mem_dim[m]; cut[k] = k < nact ? V.mem_cutoff[m] : 0u; }
+    // every multiplicand is a limb below its memory's cutoff <= 2^16: narrow accumulators, OPEN_PASS_E memories per pass (their shifts
+    // and cutoffs are uniform: scalar registers)
     const size_t rend = row1 < V.rows ? row1 : V.rows;
-    for (size_t j0 = row0; j0 < rend; j0 += TPB) {
-        const size_t j = j0 + threadIdx.x;
-        E2 e;
-        if constexpr (AB) e = e2_mul(ea, eq[256 + (j0 >> 8)]);
-        if (j >= rend) break;
-        if constexpr (!AB) e = eq[j];
-        const u64 v = V.input[j] & mask;
+    for (int kb = 0; kb < nact; kb += OPEN_PASS_E) {
+        int sh[OPEN_PASS_E];
+        u32 cut[OPEN_PASS_E];
 #pragma unroll
-        for (int k = 0; k < OPEN_ACT; k++) {
-            const u32 a = (u32)(v >> sh[k]) & 0xFFFF;
-            if (a && a < cut[k]) acc[k] = e2_add(acc[k], e2(gl_mul_small(e.c0, a), gl_mul_small(e.c1, a)));
+        for (int k = 0; k < OPEN_PASS_E; k++) {
+            const int m = kb + k < nact ? s_act[kb + k] : 0;
+            sh[k] = __builtin_amdgcn_readfirstlane(16 * V.mem_dim[m]);
+            cut[k] = (u32)__builtin_amdgcn_readfirstlane((int)(kb + k < nact ? V.mem_cutoff[m] : 0u));
         }
-    }
-    E2 sum[OPEN_ACT];
+        WNar2 acc[OPEN_PASS_E];
 #pragma unroll
-    for (int k = 0; k < OPEN_ACT; k++) sum[k] = k < nact ? block_sum(acc[k], sm) : e2_zero();   // (nact is uniform: the barriers inside match)
-    if (threadIdx.x == 0)
+        for (int k = 0; k < OPEN_PASS_E; k++) acc[k] = wnar2_zero();
+        int blocks = 0;
+        for (size_t jb = row0; jb < rend; jb += (size_t)UN * TPB) {
+            E2 e[UN];
+            u64 v[UN];
+            weights(jb, rend, e);
+#pragma unroll
+            for (int u = 0; u < UN; u++) { const size_t j = jb + (size_t)u * TPB + threadIdx.x; v[u] = j < rend ? V.input[j] & mask : 0; }
+#pragma unroll
+            for (int u = 0; u < UN; u++) {
+#pragma unroll
+                for (int k = 0; k < OPEN_PASS_E; k++) {
+                    const u32 a = (u32)(v[u] >> sh[k]) & 0xFFFF;
+                    wnar2_mac(acc[k], e[u], a < cut[k] ? a : 0u);
+                }
+            }
+            if (++blocks == WFLUSH_TRIPS / UN) {
+                blocks = 0;
+#pragma unroll
+                for (int k = 0; k < OPEN_PASS_E; k++) acc[k] = wnar2_from(wnar2_reduce(acc[k]));
+            }
+        }
+        E2 sum[OPEN_PASS_E];
+#pragma unroll
+        for (int k = 0; k < OPEN_PASS_E; k++)   // (nact is uniform: the barriers inside match)
+            sum[k] = kb + k < nact ? block_sum(finish(wnar2_reduce(acc[k])), sm) : e2_zero();
+        if (threadIdx.x == 0)
+            for (int i = 0; i < P.nvirt; i++) {
+                const int vi = P.virt[i], m = tabs.emem[vi];
+#pragma unroll
+                for (int k = 0; k < OPEN_PASS_E; k++) if (kb + k < nact && s_act[kb + k] == m) partials[(size_t)blockIdx.x * ntab_all + vi] = sum[k];
+            }
+    }
+    if (threadIdx.x == 0)   // the memories this lookup does not use: zero over the workgroup's rows
         for (int i = 0; i < P.nvirt; i++) {
             const int vi = P.virt[i], m = tabs.emem[vi];
-            E2 val = e2_zero();
-#pragma unroll
-            for (int k = 0; k < OPEN_ACT; k++) if (k < nact && s_act[k] == m) val = sum[k];
-            partials[(size_t)blockIdx.x * ntab_all + vi] = val;
+            bool used = false;
+            for (int k = 0; k < nact; k++) used |= s_act[k] == m;
+            if (!used) partials[(size_t)blockIdx.x * ntab_all + vi] = e2_zero();
         }
 }
 // rows per workgroup of open_x's launch, 0 where the shape does not fit
@@ -3020,14 +3118,19 @@ bool open_x(hipStream_t st, const E2* eq, const DotTabs& tabs, int ntab, size_t 
 __global__ __launch_bounds__(TPB) void k_dot_eq_ab(const E2* __restrict__ ab, const u64* __restrict__ tab, size_t n, E2* __restrict__ partials) {
     __shared__ E2 sm[TPB / 64];
     const int lo = (2 * (int)threadIdx.x) & 255;
-    const E2 a0 = ab[lo], a1 = ab[lo + 1];
-    E2 acc = e2_zero();
+    const FoldR f0 = fold_r(ab[lo]), f1 = fold_r(ab[lo + 1]);
+    // unreduced sums (gl_wide.hpp): one product per trip into each column accumulator, restarted every WFLUSH_TRIPS trips;
+    // the B entry of a step weighs both entries; the thread's two A entries multiply their sums once after the loop
+    W2 s0 = w2_zero(), s1 = w2_zero();
+    int trips = 0;
     for (size_t j = ((size_t)blockIdx.x * TPB + threadIdx.x) * 2; j < n; j += (size_t)gridDim.x * TPB * 2) {
         const E2 b = ab[256 + (j >> 8)];
         const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(tab + j);
-        acc = e2_add(acc, e2_add(e2_mul_f(e2_mul(a0, b), v.x), e2_mul_f(e2_mul(a1, b), v.y)));
+        w2_mac_f(s0, b, v.x);
+        w2_mac_f(s1, b, v.y);
+        if (++trips == WFLUSH_TRIPS) { s0 = w2_from(w2_reduce(s0)); s1 = w2_from(w2_reduce(s1)); trips = 0; }
     }
-    const E2 s = block_sum(acc, sm);
+    const E2 s = block_sum(e2_add(e2_mul_wide(f0, w2_reduce(s0)), e2_mul_wide(f1, w2_reduce(s1))), sm);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 void dot_eq_ab(hipStream_t st, const E2* ab, int nvars, const u64* tab, E2* partials, E2* out) {
