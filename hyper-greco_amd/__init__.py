@@ -18,6 +18,9 @@ HG_MAX_K = 16
 P = 0xFFFFFFFF00000001
 
 u64p = C.POINTER(C.c_uint64)
+i64p = C.POINTER(C.c_int64)
+u32p = C.POINTER(C.c_uint32)
+u8p = C.POINTER(C.c_uint8)
 
 
 class HgParams(C.Structure):
@@ -65,6 +68,40 @@ def build(force=False):
         subprocess.check_call(["make", "-C", src, "clean"])
     subprocess.check_call(["make", "-C", src, "-j4"])
     return _LIB_PATH
+
+
+def _two_field_protos(L):
+    """the verifier, instance and commitment entries: the two fields have the same C types (an element is 2 or 4 words behind a
+    pointer); the Goldilocks entries with protocol modes take an int where marked"""
+    vp, sz, ci, cp, szp = C.c_void_p, C.c_size_t, C.c_int, C.c_char_p, C.POINTER(C.c_size_t)
+    L.hg_verify_mode.argtypes = [vp, vp, ci, cp, sz]
+    L.hg_verify_device.argtypes = L.hg_verify_device_bn254.argtypes = [vp, vp, vp, cp, sz]
+    L.hg_verify_device_mode.argtypes = [vp, vp, vp, ci, cp, sz]
+    L.hg_instance_from_ciphertext.argtypes = [C.POINTER(HgParams), i64p, i64p, C.POINTER(vp)]
+    L.hg_instance_from_witness.argtypes = [C.POINTER(HgParams), vp, C.POINTER(vp)]
+    L.hg_instance_coeffs.argtypes = [vp, i64p, i64p]
+    L.hg_instance_get.argtypes, L.hg_instance_get.restype = [vp, ci, u64p, sz], C.c_int64
+    L.hg_instance_free.argtypes = [vp]
+    L.hg_pk_claim_shape.argtypes = [vp, szp, szp]
+    batch = [vp, vp, C.POINTER(vp), C.POINTER(cp), szp, sz]          # ctx, key, handles, proofs, lengths, n
+    room = [vp, sz, u64p, sz, szp]                                    # claims, their capacity, points, their capacity, claims written
+    for sfx, mode in (("", [ci]), ("_bn254", [])):
+        getattr(L, "hg_verify_device_batch" + sfx).argtypes = batch + mode + [C.POINTER(ci), cp, sz]
+        getattr(L, "hg_verify_public_batch" + sfx).argtypes = batch + mode + [C.POINTER(ci)] + room + [cp, sz]
+        getattr(L, "hg_verify_public" + sfx).argtypes = [vp, vp] + mode + [cp, sz] + room
+        getattr(L, "hg_verify_public_device" + sfx).argtypes = [vp, vp, vp] + mode + [cp, sz] + room
+        getattr(L, "hg_claims_settle" + sfx).argtypes = [vp, C.POINTER(HgParams), vp, vp, sz, u64p]
+        getattr(L, "hg_instance_mle" + sfx).argtypes = [vp, vp, ci, ci, u64p, sz, u64p]
+        getattr(L, "hg_instance_mle_batch" + sfx).argtypes = [vp, C.POINTER(vp), sz, ci, ci, u64p, sz, u64p]
+        getattr(L, "hg_pcs_commit" + sfx).argtypes = [vp, C.POINTER(u64p), u32p, sz, sz, C.POINTER(vp), u8p]
+        getattr(L, "hg_pcs_open" + sfx).argtypes = [vp, vp, u32p, u64p, u64p, sz, sz, u8p, sz, szp]
+        getattr(L, "hg_pcs_verify" + sfx).argtypes = [cp, u32p, sz, sz, u32p, u64p, u64p, sz, sz, cp, sz]
+        getattr(L, "hg_secrets_commit" + sfx).argtypes = [vp, C.POINTER(HgParams), vp, sz, C.POINTER(vp), u8p]
+        getattr(L, "hg_claims_open" + sfx).argtypes = [vp, C.POINTER(HgParams), vp, vp, sz, u64p, sz, u8p, sz, szp]
+        getattr(L, "hg_claims_verify" + sfx).argtypes = [C.POINTER(HgParams), cp, sz, vp, sz, u64p, sz, cp, sz]
+    L.hg_pcs_free.argtypes, L.hg_pcs_free.restype = [vp], None
+    L.hg_pcs_verify_device.argtypes = [vp] + L.hg_pcs_verify.argtypes
+    L.hg_claims_verify_device.argtypes = [vp] + L.hg_claims_verify.argtypes
 
 
 _lib = None
@@ -126,6 +163,7 @@ def lib():
         L.hg_profile_select.argtypes = [C.c_void_p, C.c_char_p]
         L.hg_profile_reset.argtypes = [C.c_void_p]
         L.hg_profile_get.argtypes = [C.c_void_p, C.POINTER(HgKernelStat), C.c_int]
+        _two_field_protos(L)
         _lib = L
     return _lib
 
@@ -553,9 +591,6 @@ def witness_derive_into(ctx, pk, d, values):
     return Witness(h, pk.params)
 
 
-i64p = C.POINTER(C.c_int64)
-
-
 def _encryption_arrays(params, s, e, k1, a):
     n, k = params.n, params.k
     arrs = [np.ascontiguousarray(x, dtype=np.int64).reshape(-1) for x in (s, e, k1, a)]
@@ -834,89 +869,96 @@ def challenges_bn254(n):
     return Context._fr_unpack(out)
 
 
-def verify(pk, witness, proof, mode=0):
-    """BfvEncrypt::verify [REF sk_encryption_circuit.rs:462-517]: (accepted, reason). mode: see hg_verify_mode."""
-    L = lib()
-    L.hg_verify_mode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]
-    rc = L.hg_verify_mode(pk.h, witness.h, mode, proof, len(proof)) if mode else L.hg_verify(pk.h, witness.h, proof, len(proof))
+def _decision(rc):
+    """the tail of every verifier call: (accepted, reason); a negative status is an HgError"""
     if rc < 0:
         raise HgError(lib().hg_last_error().decode())
     return rc == 0, ("" if rc == 0 else lib().hg_last_error().decode())
+
+
+def _h(ctx):
+    return ctx.h if ctx is not None else None
+
+
+def verify(pk, witness, proof, mode=0):
+    """BfvEncrypt::verify [REF sk_encryption_circuit.rs:462-517]: (accepted, reason). mode: see hg_verify_mode."""
+    L = lib()
+    return _decision(L.hg_verify_mode(pk.h, witness.h, mode, proof, len(proof)) if mode else L.hg_verify(pk.h, witness.h, proof, len(proof)))
+
+
+def verify_bn254(pk, witness, proof):
+    """BfvEncrypt::verify over bn256::Fr [REF sk_encryption_circuit.rs:462-517, 614-626]: (accepted, reason)."""
+    return _decision(lib().hg_verify_bn254(pk.h, witness.h, proof, len(proof)))
 
 
 def verify_device(ctx, pk, witness, proof, mode=0):
     """hg_verify_device: BfvEncrypt::verify with the table-sized work on the device: (accepted, reason). mode != 0:
     hg_verify_device_mode (the mode bits of hg_verify_mode)."""
     L = lib()
-    L.hg_verify_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
-    L.hg_verify_device_mode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]
     if mode:
-        rc = L.hg_verify_device_mode(ctx.h if ctx is not None else None, pk.h, witness.h, mode, proof, len(proof))
-    else:
-        rc = L.hg_verify_device(ctx.h, pk.h, witness.h, proof, len(proof))
-    if rc < 0:
+        return _decision(L.hg_verify_device_mode(_h(ctx), pk.h, witness.h, mode, proof, len(proof)))
+    return _decision(L.hg_verify_device(ctx.h, pk.h, witness.h, proof, len(proof)))
+
+
+def verify_device_bn254(ctx, pk, witness, proof):
+    """hg_verify_device_bn254: BfvEncrypt::verify over bn256::Fr with the table-sized work on the device: (accepted, reason)."""
+    return _decision(lib().hg_verify_device_bn254(_h(ctx), pk.h, witness.h, proof, len(proof)))
+
+
+def _verify_batch(fn, ctx, pk, handles, proofs, extra_args, reason_cap, outputs=()):
+    """One call of a batch entry: fn(ctx, pk, handles, proofs, lens, n, *extra_args, results, *outputs, reasons, reason_cap).
+    Returns [(accepted, reason)], one per proof."""
+    n = len(proofs)
+    m = max(n, 1)
+    hs = (C.c_void_p * m)(*[x.h.value for x in handles])
+    ps = (C.c_char_p * m)(*[bytes(p) for p in proofs])
+    lens = (C.c_size_t * m)(*[len(p) for p in proofs])
+    res = (C.c_int * m)()
+    reasons = C.create_string_buffer(m * reason_cap)
+    if fn(_h(ctx), pk.h, hs, ps, lens, n, *extra_args, res, *outputs, reasons, reason_cap) < 0:
         raise HgError(lib().hg_last_error().decode())
-    return rc == 0, ("" if rc == 0 else lib().hg_last_error().decode())
+    raw = reasons.raw
+    return [(res[i] == 0, raw[i * reason_cap:(i + 1) * reason_cap].split(b"\0", 1)[0].decode()) for i in range(n)]
 
 
 def verify_device_batch(ctx, pk, witnesses, proofs, mode=0, reason_cap=256):
     """hg_verify_device_batch: proof i against witnesses[i] in `mode`, the run verified in device passes of a group of proofs each:
     a list of (accepted, reason), one per proof, the decisions of verify_device(ctx, pk, witnesses[i], proofs[i], mode)."""
-    L = lib()
-    L.hg_verify_device_batch.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
-                                         C.c_size_t, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
-    n = len(proofs)
-    if len(witnesses) != n:
+    if len(witnesses) != len(proofs):
         raise ValueError("verify_device_batch: one witness per proof")
-    ws = (C.c_void_p * max(n, 1))(*[w.h.value for w in witnesses])
-    ps = (C.c_char_p * max(n, 1))(*[bytes(p) for p in proofs])
-    lens = (C.c_size_t * max(n, 1))(*[len(p) for p in proofs])
-    res = (C.c_int * max(n, 1))()
-    reasons = C.create_string_buffer(max(n, 1) * reason_cap)
-    rc = L.hg_verify_device_batch(ctx.h if ctx is not None else None, pk.h, ws, ps, lens, n, mode, res, reasons, reason_cap)
-    if rc < 0:
-        raise HgError(lib().hg_last_error().decode())
-    raw = reasons.raw
-    out = []
-    for i in range(n):
-        r = raw[i * reason_cap:(i + 1) * reason_cap].split(b"\0", 1)[0].decode()
-        out.append((res[i] == 0, r))
-    return out
-
-
-def verify_device_bn254(ctx, pk, witness, proof):
-    """hg_verify_device_bn254: BfvEncrypt::verify over bn256::Fr with the table-sized work on the device: (accepted, reason)."""
-    L = lib()
-    L.hg_verify_device_bn254.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
-    rc = L.hg_verify_device_bn254(ctx.h if ctx is not None else None, pk.h, witness.h, proof, len(proof))
-    if rc < 0:
-        raise HgError(lib().hg_last_error().decode())
-    return rc == 0, ("" if rc == 0 else lib().hg_last_error().decode())
+    return _verify_batch(lib().hg_verify_device_batch, ctx, pk, witnesses, proofs, (mode,), reason_cap)
 
 
 def verify_device_batch_bn254(ctx, pk, witnesses, proofs, reason_cap=256):
     """hg_verify_device_batch_bn254: BN254 proof i against witnesses[i], the run verified in device passes of a group of proofs each:
     a list of (accepted, reason), one per proof, the decisions of verify_device_bn254(ctx, pk, witnesses[i], proofs[i])."""
-    L = lib()
-    L.hg_verify_device_batch_bn254.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
-                                               C.c_size_t, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
-    n = len(proofs)
-    if len(witnesses) != n:
+    if len(witnesses) != len(proofs):
         raise ValueError("verify_device_batch_bn254: one witness per proof")
-    ws = (C.c_void_p * max(n, 1))(*[w.h.value for w in witnesses])
-    ps = (C.c_char_p * max(n, 1))(*[bytes(p) for p in proofs])
-    lens = (C.c_size_t * max(n, 1))(*[len(p) for p in proofs])
-    res = (C.c_int * max(n, 1))()
-    reasons = C.create_string_buffer(max(n, 1) * reason_cap)
-    rc = L.hg_verify_device_batch_bn254(ctx.h if ctx is not None else None, pk.h, ws, ps, lens, n, res, reasons, reason_cap)
-    if rc < 0:
-        raise HgError(lib().hg_last_error().decode())
-    raw = reasons.raw
-    out = []
-    for i in range(n):
-        r = raw[i * reason_cap:(i + 1) * reason_cap].split(b"\0", 1)[0].decode()
-        out.append((res[i] == 0, r))
-    return out
+    return _verify_batch(lib().hg_verify_device_batch_bn254, ctx, pk, witnesses, proofs, (), reason_cap)
+
+
+class InputClaims:
+    """What verify_public leaves open: `claims` (a ctypes array of HgInputClaim) and `points` (u64, two words per coordinate)."""
+    WORDS, STRUCT, SFX = 2, HgInputClaim, ""     # how an element crosses the ABI; the entries of this field are hg_<name> + SFX
+
+    def __init__(self, claims, n, points):
+        self.claims, self.n, self.points = claims, n, points
+
+    def as_tuples(self):
+        """[(input, nvars, point words, value words)]: the whole content, for comparisons."""
+        W = self.WORDS
+        return [(int(c.input), int(c.nvars), tuple(int(x) for x in self.points[W * c.point_off:W * (c.point_off + c.nvars)]), tuple(int(x) for x in c.value))
+                for c in self.claims[:self.n]]
+
+
+class InputClaimsBn254(InputClaims):
+    """What verify_public_bn254 leaves open: `claims` (a ctypes array of HgInputClaimBn254) and `points` (u64, four limbs per coordinate)."""
+    WORDS, STRUCT, SFX = 4, HgInputClaimBn254, "_bn254"
+
+
+def _pack(F, elems):
+    """elements of field F as ABI words: u64 words as they are (Goldilocks), Python ints below r as 4 limbs each (BN254)"""
+    return Context._fr_pack(elems) if F is InputClaimsBn254 else np.ascontiguousarray(elems, dtype=np.uint64).reshape(-1)
 
 
 class Instance:
@@ -933,173 +975,149 @@ class Instance:
         arrs = [np.ascontiguousarray(x, dtype=np.int64).reshape(-1) for x in (a, ct0)]
         if [x.size for x in arrs] != [kn, kn]:
             raise ValueError("instance: a and ct0 hold k * n signed coefficients each")
-        L = lib()
-        L.hg_instance_from_ciphertext.argtypes = [C.POINTER(HgParams), i64p, i64p, C.POINTER(C.c_void_p)]
         h = C.c_void_p()
-        _check(L.hg_instance_from_ciphertext(C.byref(params), arrs[0].ctypes.data_as(i64p), arrs[1].ctypes.data_as(i64p), C.byref(h)))
+        _check(lib().hg_instance_from_ciphertext(C.byref(params), arrs[0].ctypes.data_as(i64p), arrs[1].ctypes.data_as(i64p), C.byref(h)))
         return cls(h, params)
 
     @classmethod
     def from_witness(cls, witness):
         """hg_instance_from_witness: the layout of the handle's ais and ct0is tables inverted."""
-        L = lib()
-        L.hg_instance_from_witness.argtypes = [C.POINTER(HgParams), C.c_void_p, C.POINTER(C.c_void_p)]
         h = C.c_void_p()
-        _check(L.hg_instance_from_witness(C.byref(witness.params), witness.h, C.byref(h)))
+        _check(lib().hg_instance_from_witness(C.byref(witness.params), witness.h, C.byref(h)))
         return cls(h, witness.params)
 
     def coeffs(self):
         """hg_instance_coeffs: (a, ct0) as int64 arrays of k * n coefficients."""
         kn = self.params.k * self.params.n
         a, ct0 = np.zeros(kn, dtype=np.int64), np.zeros(kn, dtype=np.int64)
-        L = lib()
-        L.hg_instance_coeffs.argtypes = [C.c_void_p, i64p, i64p]
-        _check(L.hg_instance_coeffs(self.h, a.ctypes.data_as(i64p), ct0.ctypes.data_as(i64p)))
+        _check(lib().hg_instance_coeffs(self.h, a.ctypes.data_as(i64p), ct0.ctypes.data_as(i64p)))
         return a, ct0
 
     def table(self, which):
         """hg_instance_get: the laid-out ais (which 0) or ct0is (which 1) table, as Witness.arrays() holds it."""
         L = lib()
-        L.hg_instance_get.argtypes = [C.c_void_p, C.c_int, u64p, C.c_size_t]
-        L.hg_instance_get.restype = C.c_int64
         n = _check(L.hg_instance_get(self.h, which, None, 0))
         out = np.zeros(n, dtype=np.uint64)
         _check(L.hg_instance_get(self.h, which, _ptr(out), n))
         return out
 
+    def _mle(self, F, ctx, which, index, point):
+        pt = _pack(F, point)
+        out = np.zeros(F.WORDS, dtype=np.uint64)
+        _check(getattr(lib(), "hg_instance_mle" + F.SFX)(_h(ctx), self.h, which, index, _ptr(pt), pt.size // F.WORDS, _ptr(out)))
+        return out
+
     def mle(self, ctx, which, index, point):
         """hg_instance_mle: the MLE of ais[index] (which 0) or ct0is (which 1) at an E point (u64 pairs); ctx None: host loop."""
-        point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1)
-        out = np.zeros(2, dtype=np.uint64)
-        L = lib()
-        L.hg_instance_mle.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, u64p, C.c_size_t, u64p]
-        _check(L.hg_instance_mle(ctx.h if ctx is not None else None, self.h, which, index, _ptr(point), point.size // 2, _ptr(out)))
-        return out
+        return self._mle(InputClaims, ctx, which, index, point)
 
     def mle_bn254(self, ctx, which, index, point):
         """hg_instance_mle_bn254: the MLE of ais[index] (which 0) or ct0is (which 1) at an Fr point (Python ints below r) as a
         Python int; ctx None: host loop, else the compact dot kernel over Fr."""
-        pt = Context._fr_pack(point)
-        out = np.zeros(4, dtype=np.uint64)
-        L = lib()
-        L.hg_instance_mle_bn254.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, u64p, C.c_size_t, u64p]
-        _check(L.hg_instance_mle_bn254(ctx.h if ctx is not None else None, self.h, which, index, _ptr(pt), len(point), _ptr(out)))
-        return Context._fr_unpack(out)[0]
+        return Context._fr_unpack(self._mle(InputClaimsBn254, ctx, which, index, point))[0]
 
     def __del__(self):
         try:
             if self.h:
-                lib().hg_instance_free.argtypes = [C.c_void_p]
                 lib().hg_instance_free(self.h)
                 self.h = None
         except Exception:
             pass
 
 
-class InputClaims:
-    """What verify_public leaves open: `claims` (a ctypes array of HgInputClaim) and `points` (u64, two words per coordinate)."""
-
-    def __init__(self, claims, n, points):
-        self.claims, self.n, self.points = claims, n, points
-
-    def as_tuples(self):
-        """[(input, nvars, point words, value words)]: the whole content, for comparisons."""
-        out = []
-        for i in range(self.n):
-            c = self.claims[i]
-            out.append((int(c.input), int(c.nvars), tuple(int(x) for x in self.points[2 * c.point_off:2 * (c.point_off + c.nvars)]), (int(c.value[0]), int(c.value[1]))))
-        return out
-
-
 def pk_claim_shape(pk):
     """hg_pk_claim_shape: (claims on secret inputs a proof of this key leaves, their coordinates in all)."""
-    L = lib()
-    L.hg_pk_claim_shape.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     a, b = C.c_size_t(0), C.c_size_t(0)
-    _check(L.hg_pk_claim_shape(pk.h, C.byref(a), C.byref(b)))
+    _check(lib().hg_pk_claim_shape(pk.h, C.byref(a), C.byref(b)))
     return a.value, b.value
+
+
+def _verify_public(F, pk, instance, proof, mode_args, ctx, device):
+    nc, nco = pk_claim_shape(pk)
+    claims = (F.STRUCT * max(nc, 1))()
+    points = np.zeros(F.WORDS * max(nco, 1), dtype=np.uint64)
+    n = C.c_size_t(0)
+    args = (pk.h, instance.h, *mode_args, proof, len(proof), claims, nc, _ptr(points), nco, C.byref(n))
+    L = lib()
+    ok, why = _decision(getattr(L, "hg_verify_public_device" + F.SFX)(_h(ctx), *args) if device else getattr(L, "hg_verify_public" + F.SFX)(*args))
+    return ok, why, (F(claims, n.value, points) if ok else None)
 
 
 def verify_public(pk, instance, proof, mode=0, ctx=None, device=False):
     """hg_verify_public (device=True: hg_verify_public_device on ctx): the part of BfvEncrypt::verify that the key, the proof, a_i
     and ct0_i decide. Returns (accepted, reason, InputClaims or None): the claims left on the secret inputs, for claims_settle."""
-    L = lib()
+    return _verify_public(InputClaims, pk, instance, proof, (mode,), ctx, device)
+
+
+def verify_public_bn254(pk, instance, proof, ctx=None, device=False):
+    """hg_verify_public_bn254 (device=True: hg_verify_public_device_bn254 on ctx): the part of BfvEncrypt::verify over bn256::Fr that
+    the key, the proof, a_i and ct0_i decide. Returns (accepted, reason, InputClaimsBn254 or None), for claims_settle_bn254."""
+    return _verify_public(InputClaimsBn254, pk, instance, proof, (), ctx, device)
+
+
+def _verify_public_batch(F, ctx, pk, instances, proofs, mode_args, reason_cap):
+    name = "verify_public_batch" + F.SFX
+    if len(instances) != len(proofs):
+        raise ValueError(name + ": one instance per proof")
     nc, nco = pk_claim_shape(pk)
-    claims = (HgInputClaim * max(nc, 1))()
-    points = np.zeros(2 * max(nco, 1), dtype=np.uint64)
-    n = C.c_size_t(0)
-    tail = [C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.hg_verify_public.argtypes = tail
-    L.hg_verify_public_device.argtypes = [C.c_void_p] + tail
-    args = (pk.h, instance.h, mode, proof, len(proof), claims, nc, _ptr(points), nco, C.byref(n))
-    rc = L.hg_verify_public_device(ctx.h if ctx is not None else None, *args) if device else L.hg_verify_public(*args)
-    if rc < 0:
-        raise HgError(lib().hg_last_error().decode())
-    if rc:
-        return False, lib().hg_last_error().decode(), None
-    return True, "", InputClaims(claims, n.value, points)
+    m, nc1, nco1 = max(len(proofs), 1), max(nc, 1), max(nco, 1)
+    claims = (F.STRUCT * (m * nc1))()
+    points = np.zeros(F.WORDS * m * nco1, dtype=np.uint64)
+    counts = (C.c_size_t * m)()
+    got = _verify_batch(getattr(lib(), "hg_" + name), ctx, pk, instances, proofs, mode_args, reason_cap, (claims, nc1, _ptr(points), nco1, counts))
+    return [(ok, why, F((F.STRUCT * nc1)(*claims[i * nc1:(i + 1) * nc1]), counts[i], points[F.WORDS * i * nco1:F.WORDS * (i + 1) * nco1].copy()) if ok else None)
+            for i, (ok, why) in enumerate(got)]
 
 
 def verify_public_batch(ctx, pk, instances, proofs, mode=0, reason_cap=256):
     """hg_verify_public_batch: proof i against instances[i] in `mode`, the run verified in device passes of a group of proofs each:
     a list of (accepted, reason, InputClaims or None), one per proof: what verify_public(pk, instances[i], proofs[i], mode, ctx,
     device=True) returns for that pair alone."""
-    L = lib()
-    L.hg_verify_public_batch.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_int,
-                                         C.POINTER(C.c_int), C.c_void_p, C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]
-    n = len(proofs)
-    if len(instances) != n:
-        raise ValueError("verify_public_batch: one instance per proof")
-    nc, nco = pk_claim_shape(pk)
-    m = max(n, 1)
-    hs = (C.c_void_p * m)(*[x.h.value for x in instances])
-    ps = (C.c_char_p * m)(*[bytes(p) for p in proofs])
-    lens = (C.c_size_t * m)(*[len(p) for p in proofs])
-    res = (C.c_int * m)()
-    claims = (HgInputClaim * (m * max(nc, 1)))()
-    points = np.zeros(2 * m * max(nco, 1), dtype=np.uint64)
-    counts = (C.c_size_t * m)()
-    reasons = C.create_string_buffer(m * reason_cap)
-    rc = L.hg_verify_public_batch(ctx.h if ctx is not None else None, pk.h, hs, ps, lens, n, mode, res, claims, max(nc, 1), _ptr(points), max(nco, 1), counts,
-                                  reasons, reason_cap)
-    if rc < 0:
-        raise HgError(lib().hg_last_error().decode())
-    raw = reasons.raw
-    out = []
-    for i in range(n):
-        if res[i]:
-            out.append((False, raw[i * reason_cap:(i + 1) * reason_cap].split(b"\0", 1)[0].decode(), None))
-            continue
-        mine = (HgInputClaim * max(nc, 1))(*claims[i * max(nc, 1):(i + 1) * max(nc, 1)])
-        out.append((True, "", InputClaims(mine, counts[i], points[2 * i * max(nco, 1):2 * (i + 1) * max(nco, 1)].copy())))
-    return out
+    return _verify_public_batch(InputClaims, ctx, pk, instances, proofs, (mode,), reason_cap)
+
+
+def verify_public_batch_bn254(ctx, pk, instances, proofs, reason_cap=256):
+    """hg_verify_public_batch_bn254: BN254 proof i against instances[i], the run verified in device passes of a group of proofs each:
+    a list of (accepted, reason, InputClaimsBn254 or None), one per proof: what verify_public_bn254(pk, instances[i], proofs[i], ctx,
+    device=True) returns for that pair alone."""
+    return _verify_public_batch(InputClaimsBn254, ctx, pk, instances, proofs, (), reason_cap)
+
+
+def _instance_mle_batch(F, ctx, instances, which, index, point):
+    pt = _pack(F, point)
+    n = len(instances)
+    out = np.zeros(F.WORDS * max(n, 1), dtype=np.uint64)
+    hs = (C.c_void_p * max(n, 1))(*[x.h.value for x in instances])
+    _check(getattr(lib(), "hg_instance_mle_batch" + F.SFX)(_h(ctx), hs, n, which, index, _ptr(pt), pt.size // F.WORDS, _ptr(out)))
+    return out[:F.WORDS * n]
 
 
 def instance_mle_batch(ctx, instances, which, index, point):
     """hg_instance_mle_batch: the MLE of ais[index] (which 0) or ct0is (which 1) of every instance at ONE E point (u64 pairs),
     through the kernel of hg_verify_public_batch as one work unit: an (n, 2) array. Device only."""
-    point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1)
-    n = len(instances)
-    out = np.zeros((n, 2), dtype=np.uint64)
-    hs = (C.c_void_p * max(n, 1))(*[x.h.value for x in instances])
-    L = lib()
-    L.hg_instance_mle_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.c_int, C.c_int, u64p, C.c_size_t, u64p]
-    _check(L.hg_instance_mle_batch(ctx.h if ctx is not None else None, hs, n, which, index, _ptr(point), point.size // 2, _ptr(out)))
-    return out
+    return _instance_mle_batch(InputClaims, ctx, instances, which, index, point).reshape(len(instances), 2)
+
+
+def instance_mle_batch_bn254(ctx, instances, which, index, point):
+    """hg_instance_mle_batch_bn254: the MLE of ais[index] (which 0) or ct0is (which 1) of every instance at ONE Fr point (Python ints
+    below r), through the kernel of hg_verify_public_batch_bn254 as one work unit: a list of Python ints. Device only."""
+    return Context._fr_unpack(_instance_mle_batch(InputClaimsBn254, ctx, instances, which, index, point))
+
+
+def _claims_settle(fn, ctx, params, witness, claims):
+    return _decision(fn(_h(ctx), C.byref(params), witness.h, claims.claims, claims.n, _ptr(claims.points)))
 
 
 def claims_settle(ctx, params, witness, claims):
     """hg_claims_settle: every claim of an InputClaims against the witness handle (ctx None: host): (accepted, reason)."""
-    L = lib()
-    L.hg_claims_settle.argtypes = [C.c_void_p, C.POINTER(HgParams), C.c_void_p, C.c_void_p, C.c_size_t, u64p]
-    rc = L.hg_claims_settle(ctx.h if ctx is not None else None, C.byref(params), witness.h, claims.claims, claims.n, _ptr(claims.points))
-    if rc < 0:
-        raise HgError(lib().hg_last_error().decode())
-    return rc == 0, ("" if rc == 0 else lib().hg_last_error().decode())
+    return _claims_settle(lib().hg_claims_settle, ctx, params, witness, claims)
 
 
-u32p = C.POINTER(C.c_uint32)
-u8p = C.POINTER(C.c_uint8)
+def claims_settle_bn254(ctx, params, witness, claims):
+    """hg_claims_settle_bn254: every claim of an InputClaimsBn254 against the witness handle (ctx None: host): (accepted, reason)."""
+    return _claims_settle(lib().hg_claims_settle_bn254, ctx, params, witness, claims)
+
+
 PCS_DEFAULT_QUERIES = 241
 
 
@@ -1113,28 +1131,25 @@ def pcs_row_log2(nvars, log2_row=0):
     return min(c, min(nvars))
 
 
-def pcs_opening_bytes(nvars, n_claims, n_queries=0, log2_row=0):
-    """16 C (n+1) + Q (8 R + 32 (c+2)): the exact length of an opening."""
+def _opening_bytes(elem_bytes, word_bytes, nvars, n_claims, n_queries, log2_row):
     c = pcs_row_log2(nvars, log2_row)
     rows = sum(1 << (v - c) for v in nvars)
-    return 16 * (1 << c) * (n_claims + 1) + (n_queries or PCS_DEFAULT_QUERIES) * (8 * rows + 32 * (c + 2))
+    return elem_bytes * (1 << c) * (n_claims + 1) + (n_queries or PCS_DEFAULT_QUERIES) * (word_bytes * rows + 32 * (c + 2))
+
+
+def pcs_opening_bytes(nvars, n_claims, n_queries=0, log2_row=0):
+    """16 C (n+1) + Q (8 R + 32 (c+2)): the exact length of an opening."""
+    return _opening_bytes(16, 8, nvars, n_claims, n_queries, log2_row)
+
+
+def pcs_opening_bytes_bn254(nvars, n_claims, n_queries=0, log2_row=0):
+    """32 C (n+1) + Q (32 R + 32 (c+2)): the exact length of an opening over BN254."""
+    return _opening_bytes(32, 32, nvars, n_claims, n_queries, log2_row)
 
 
 def _pcs_protos():
-    L = lib()
-    L.hg_pcs_commit.argtypes = [C.c_void_p, C.POINTER(u64p), u32p, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p), u8p]
-    L.hg_pcs_free.argtypes = [C.c_void_p]
-    L.hg_pcs_free.restype = None
-    L.hg_pcs_open.argtypes = [C.c_void_p, C.c_void_p, u32p, u64p, u64p, C.c_size_t, C.c_size_t, u8p, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.hg_pcs_verify.argtypes = [C.c_char_p, u32p, C.c_size_t, C.c_size_t, u32p, u64p, u64p, C.c_size_t, C.c_size_t, C.c_char_p, C.c_size_t]
-    L.hg_secrets_commit.argtypes = [C.c_void_p, C.POINTER(HgParams), C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), u8p]
-    L.hg_claims_open.argtypes = [C.c_void_p, C.POINTER(HgParams), C.c_void_p, C.c_void_p, C.c_size_t, u64p, C.c_size_t, u8p, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.hg_claims_verify.argtypes = [C.POINTER(HgParams), C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, u64p, C.c_size_t, C.c_char_p, C.c_size_t]
-    L.hg_pcs_verify_device.argtypes = [C.c_void_p] + L.hg_pcs_verify.argtypes
-    L.hg_claims_verify_device.argtypes = [C.c_void_p] + L.hg_claims_verify.argtypes
-    for name in ("hg_pcs_commit", "hg_pcs_open", "hg_pcs_verify", "hg_secrets_commit", "hg_claims_open", "hg_claims_verify"):   # the same C types, 4 words an element
-        getattr(L, name + "_bn254").argtypes = getattr(L, name).argtypes
-    return L
+    """the library: the prototypes of the commitment entries are assigned with the others when it is loaded"""
+    return lib()
 
 
 def _pcs_claim_arrays(claims):
@@ -1162,13 +1177,6 @@ def _fr_table(t):
     return Context._fr_pack(t)
 
 
-def pcs_opening_bytes_bn254(nvars, n_claims, n_queries=0, log2_row=0):
-    """32 C (n+1) + Q (32 R + 32 (c+2)): the exact length of an opening over BN254."""
-    c = pcs_row_log2(nvars, log2_row)
-    rows = sum(1 << (v - c) for v in nvars)
-    return 32 * (1 << c) * (n_claims + 1) + (n_queries or PCS_DEFAULT_QUERIES) * (32 * rows + 32 * (c + 2))
-
-
 class Commitment:
     """hg_pcs_commit / hg_secrets_commit and their _bn254 forms: the handle of a polynomial commitment (host form: ctx None) and its
     32-byte root. field is "goldilocks" or "bn254"; open and open_claims call the entry of the handle's field."""
@@ -1177,76 +1185,66 @@ class Commitment:
         self.h, self.root, self.ctx, self.nvars, self.log2_row, self.field = handle, root, ctx, list(nvars), log2_row, field
 
     @classmethod
-    def commit_bn254(cls, ctx, tables, log2_row=0):
-        """hg_pcs_commit_bn254. tables: per table 2^v_t elements, Python ints below r or a numpy u64 array of 4 limbs each."""
-        L = _pcs_protos()
-        tabs = [_fr_table(t) for t in tables]
-        nvars = [(t.size // 4).bit_length() - 1 for t in tabs]
+    def _commit(cls, field, ctx, tabs, words, log2_row):
+        nvars = [(t.size // words).bit_length() - 1 for t in tabs]
         ptrs = (u64p * len(tabs))(*[_ptr(t) for t in tabs])
         nv = (C.c_uint32 * len(tabs))(*nvars)
         h, root = C.c_void_p(), (C.c_uint8 * 32)()
-        _check(L.hg_pcs_commit_bn254(ctx.h if ctx is not None else None, ptrs, nv, len(tabs), log2_row, C.byref(h), root))
-        return cls(h, bytes(root), ctx, nvars, pcs_row_log2(nvars, log2_row), "bn254")
+        fn = lib().hg_pcs_commit_bn254 if field == "bn254" else lib().hg_pcs_commit
+        _check(fn(_h(ctx), ptrs, nv, len(tabs), log2_row, C.byref(h), root))
+        return cls(h, bytes(root), ctx, nvars, pcs_row_log2(nvars, log2_row), field)
+
+    @classmethod
+    def _secrets(cls, field, ctx, params, witness, log2_row):
+        h, root = C.c_void_p(), (C.c_uint8 * 32)()
+        fn = lib().hg_secrets_commit_bn254 if field == "bn254" else lib().hg_secrets_commit
+        _check(fn(_h(ctx), C.byref(params), witness.h, log2_row, C.byref(h), root))
+        lg = params.n.bit_length() - 1
+        nvars = [lg + 1] * (3 + params.k) + [lg + params.k.bit_length() - 1]
+        return cls(h, bytes(root), ctx, nvars, pcs_row_log2(nvars, log2_row), field)
+
+    @classmethod
+    def commit_bn254(cls, ctx, tables, log2_row=0):
+        """hg_pcs_commit_bn254. tables: per table 2^v_t elements, Python ints below r or a numpy u64 array of 4 limbs each."""
+        return cls._commit("bn254", ctx, [_fr_table(t) for t in tables], 4, log2_row)
 
     @classmethod
     def secrets_bn254(cls, ctx, params, witness, log2_row=0):
         """hg_secrets_commit_bn254: the five secret inputs of a witness handle, every word lifted into Fr by the signed rule."""
-        L = _pcs_protos()
-        h, root = C.c_void_p(), (C.c_uint8 * 32)()
-        _check(L.hg_secrets_commit_bn254(ctx.h if ctx is not None else None, C.byref(params), witness.h, log2_row, C.byref(h), root))
-        lg = params.n.bit_length() - 1
-        nvars = [lg + 1] * (3 + params.k) + [lg + params.k.bit_length() - 1]
-        return cls(h, bytes(root), ctx, nvars, pcs_row_log2(nvars, log2_row), "bn254")
+        return cls._secrets("bn254", ctx, params, witness, log2_row)
 
     @classmethod
     def commit(cls, ctx, tables, log2_row=0):
         """tables: numpy u64 arrays of 2^v_t canonical words."""
-        L = _pcs_protos()
-        tabs = [np.ascontiguousarray(t, dtype=np.uint64) for t in tables]
-        nvars = [t.size.bit_length() - 1 for t in tabs]
-        ptrs = (u64p * len(tabs))(*[_ptr(t) for t in tabs])
-        nv = (C.c_uint32 * len(tabs))(*nvars)
-        h, root = C.c_void_p(), (C.c_uint8 * 32)()
-        _check(L.hg_pcs_commit(ctx.h if ctx is not None else None, ptrs, nv, len(tabs), log2_row, C.byref(h), root))
-        return cls(h, bytes(root), ctx, nvars, pcs_row_log2(nvars, log2_row))
+        return cls._commit("goldilocks", ctx, [np.ascontiguousarray(t, dtype=np.uint64) for t in tables], 1, log2_row)
 
     @classmethod
     def secrets(cls, ctx, params, witness, log2_row=0):
         """hg_secrets_commit: the five secret inputs of a witness handle (tables s, e, k1, r1is[0..k-1], r2is)."""
-        L = _pcs_protos()
-        h, root = C.c_void_p(), (C.c_uint8 * 32)()
-        _check(L.hg_secrets_commit(ctx.h if ctx is not None else None, C.byref(params), witness.h, log2_row, C.byref(h), root))
-        lg = params.n.bit_length() - 1
-        nvars = [lg + 1] * (3 + params.k) + [lg + params.k.bit_length() - 1]
-        return cls(h, bytes(root), ctx, nvars, pcs_row_log2(nvars, log2_row))
+        return cls._secrets("goldilocks", ctx, params, witness, log2_row)
+
+    def _open(self, entry, head, n_claims, tail, n_queries):
+        """entry(ctx, *head, n_claims, *tail, n_queries, buffer, its size, length out) of the handle's field -> the opening bytes"""
+        bn = self.field == "bn254"
+        cap = (pcs_opening_bytes_bn254 if bn else pcs_opening_bytes)(self.nvars, n_claims, n_queries, self.log2_row)
+        buf, ln = (C.c_uint8 * cap)(), C.c_size_t(0)
+        _check(getattr(lib(), entry + ("_bn254" if bn else ""))(_h(self.ctx), *head, n_claims, *tail, n_queries, buf, cap, C.byref(ln)))
+        return bytes(memoryview(buf)[:ln.value])
 
     def open(self, claims, n_queries=0):
         """hg_pcs_open: claims = [(table, point words, (v0, v1))] -> the opening bytes. On a BN254 handle hg_pcs_open_bn254:
         claims = [(table, point (Python ints below r), value)]."""
-        L = _pcs_protos()
-        bn = self.field == "bn254"
-        cap = (pcs_opening_bytes_bn254 if bn else pcs_opening_bytes)(self.nvars, len(claims), n_queries, self.log2_row)
-        buf, ln = (C.c_uint8 * cap)(), C.c_size_t(0)
-        table, pts, vals = (_pcs_claim_arrays_bn254 if bn else _pcs_claim_arrays)(claims)
-        fn = L.hg_pcs_open_bn254 if bn else L.hg_pcs_open
-        _check(fn(self.ctx.h if self.ctx is not None else None, self.h, table, _ptr(pts), _ptr(vals), len(claims), n_queries, buf, cap, C.byref(ln)))
-        return bytes(memoryview(buf)[:ln.value])
+        table, pts, vals = (_pcs_claim_arrays_bn254 if self.field == "bn254" else _pcs_claim_arrays)(claims)
+        return self._open("hg_pcs_open", (self.h, table, _ptr(pts), _ptr(vals)), len(claims), (), n_queries)
 
     def open_claims(self, params, claims, n_queries=0):
         """hg_claims_open: the opening of an InputClaims (what verify_public returns) against a Commitment.secrets handle. On a BN254
         handle hg_claims_open_bn254 of an InputClaimsBn254 (what verify_public_bn254 returns)."""
-        L = _pcs_protos()
-        bn = self.field == "bn254"
-        cap = (pcs_opening_bytes_bn254 if bn else pcs_opening_bytes)(self.nvars, claims.n, n_queries, self.log2_row)
-        buf, ln = (C.c_uint8 * cap)(), C.c_size_t(0)
-        fn = L.hg_claims_open_bn254 if bn else L.hg_claims_open
-        _check(fn(self.ctx.h if self.ctx is not None else None, C.byref(params), self.h, claims.claims, claims.n, _ptr(claims.points), n_queries, buf, cap,
-                                C.byref(ln)))
-        return bytes(memoryview(buf)[:ln.value])
+        return self._open("hg_claims_open", (C.byref(params), self.h, claims.claims), claims.n, (_ptr(claims.points),), n_queries)
 
     def free(self):
         if self.h:
-            _pcs_protos().hg_pcs_free(self.h)
+            lib().hg_pcs_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -1256,146 +1254,38 @@ class Commitment:
             pass
 
 
+def _pcs_verify(sfx, arrays, root, nvars, claims, proof, n_queries, log2_row, ctx):
+    nv = (C.c_uint32 * len(nvars))(*nvars)
+    table, pts, vals = arrays(claims)
+    args = (bytes(root), nv, len(nvars), log2_row, table, _ptr(pts), _ptr(vals), len(claims), n_queries, bytes(proof), len(proof))
+    L = lib()
+    return _decision(getattr(L, "hg_pcs_verify" + sfx)(*args) if ctx is None else L.hg_pcs_verify_device(ctx.h, *args))
+
+
+def _claims_verify(sfx, params, root, claims, opening, n_queries, log2_row, ctx):
+    args = (C.byref(params), bytes(root), log2_row, claims.claims, claims.n, _ptr(claims.points), n_queries, bytes(opening), len(opening))
+    L = lib()
+    return _decision(getattr(L, "hg_claims_verify" + sfx)(*args) if ctx is None else L.hg_claims_verify_device(ctx.h, *args))
+
+
 def pcs_verify(root, nvars, claims, proof, n_queries=0, log2_row=0, ctx=None):
     """hg_pcs_verify, with a context hg_pcs_verify_device: (accepted, reason). claims as Commitment.open takes them."""
-    L = _pcs_protos()
-    nv = (C.c_uint32 * len(nvars))(*nvars)
-    table, pts, vals = _pcs_claim_arrays(claims)
-    args = (bytes(root), nv, len(nvars), log2_row, table, _ptr(pts), _ptr(vals), len(claims), n_queries, bytes(proof), len(proof))
-    rc = L.hg_pcs_verify(*args) if ctx is None else L.hg_pcs_verify_device(ctx.h, *args)
-    if rc < 0:
-        raise HgError(L.hg_last_error().decode())
-    return rc == 0, ("" if rc == 0 else L.hg_last_error().decode())
+    return _pcs_verify("", _pcs_claim_arrays, root, nvars, claims, proof, n_queries, log2_row, ctx)
 
 
 def claims_verify(params, root, claims, opening, n_queries=0, log2_row=0, ctx=None):
     """hg_claims_verify, with a context hg_claims_verify_device: an InputClaims against the root of hg_secrets_commit: (accepted, reason)."""
-    L = _pcs_protos()
-    args = (C.byref(params), bytes(root), log2_row, claims.claims, claims.n, _ptr(claims.points), n_queries, bytes(opening), len(opening))
-    rc = L.hg_claims_verify(*args) if ctx is None else L.hg_claims_verify_device(ctx.h, *args)
-    if rc < 0:
-        raise HgError(L.hg_last_error().decode())
-    return rc == 0, ("" if rc == 0 else L.hg_last_error().decode())
+    return _claims_verify("", params, root, claims, opening, n_queries, log2_row, ctx)
 
 
 def pcs_verify_bn254(root, nvars, claims, proof, n_queries=0, log2_row=0):
     """hg_pcs_verify_bn254 (host only): (accepted, reason). claims as Commitment.open takes them on a BN254 handle."""
-    L = _pcs_protos()
-    nv = (C.c_uint32 * len(nvars))(*nvars)
-    table, pts, vals = _pcs_claim_arrays_bn254(claims)
-    rc = L.hg_pcs_verify_bn254(bytes(root), nv, len(nvars), log2_row, table, _ptr(pts), _ptr(vals), len(claims), n_queries, bytes(proof), len(proof))
-    if rc < 0:
-        raise HgError(L.hg_last_error().decode())
-    return rc == 0, ("" if rc == 0 else L.hg_last_error().decode())
+    return _pcs_verify("_bn254", _pcs_claim_arrays_bn254, root, nvars, claims, proof, n_queries, log2_row, None)
 
 
 def claims_verify_bn254(params, root, claims, opening, n_queries=0, log2_row=0):
     """hg_claims_verify_bn254: an InputClaimsBn254 against the root of hg_secrets_commit_bn254: (accepted, reason)."""
-    L = _pcs_protos()
-    rc = L.hg_claims_verify_bn254(C.byref(params), bytes(root), log2_row, claims.claims, claims.n, _ptr(claims.points), n_queries, bytes(opening), len(opening))
-    if rc < 0:
-        raise HgError(L.hg_last_error().decode())
-    return rc == 0, ("" if rc == 0 else L.hg_last_error().decode())
-
-
-class InputClaimsBn254:
-    """What verify_public_bn254 leaves open: `claims` (a ctypes array of HgInputClaimBn254) and `points` (u64, four limbs per coordinate)."""
-
-    def __init__(self, claims, n, points):
-        self.claims, self.n, self.points = claims, n, points
-
-    def as_tuples(self):
-        """[(input, nvars, point limbs, value limbs)]: the whole content, for comparisons."""
-        out = []
-        for i in range(self.n):
-            c = self.claims[i]
-            out.append((int(c.input), int(c.nvars), tuple(int(x) for x in self.points[4 * c.point_off:4 * (c.point_off + c.nvars)]), tuple(int(x) for x in c.value)))
-        return out
-
-
-def verify_public_bn254(pk, instance, proof, ctx=None, device=False):
-    """hg_verify_public_bn254 (device=True: hg_verify_public_device_bn254 on ctx): the part of BfvEncrypt::verify over bn256::Fr that
-    the key, the proof, a_i and ct0_i decide. Returns (accepted, reason, InputClaimsBn254 or None), for claims_settle_bn254."""
-    L = lib()
-    nc, nco = pk_claim_shape(pk)
-    claims = (HgInputClaimBn254 * max(nc, 1))()
-    points = np.zeros(4 * max(nco, 1), dtype=np.uint64)
-    n = C.c_size_t(0)
-    tail = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.hg_verify_public_bn254.argtypes = tail
-    L.hg_verify_public_device_bn254.argtypes = [C.c_void_p] + tail
-    args = (pk.h, instance.h, proof, len(proof), claims, nc, _ptr(points), nco, C.byref(n))
-    rc = L.hg_verify_public_device_bn254(ctx.h if ctx is not None else None, *args) if device else L.hg_verify_public_bn254(*args)
-    if rc < 0:
-        raise HgError(lib().hg_last_error().decode())
-    if rc:
-        return False, lib().hg_last_error().decode(), None
-    return True, "", InputClaimsBn254(claims, n.value, points)
-
-
-def verify_public_batch_bn254(ctx, pk, instances, proofs, reason_cap=256):
-    """hg_verify_public_batch_bn254: BN254 proof i against instances[i], the run verified in device passes of a group of proofs each:
-    a list of (accepted, reason, InputClaimsBn254 or None), one per proof: what verify_public_bn254(pk, instances[i], proofs[i], ctx,
-    device=True) returns for that pair alone."""
-    L = lib()
-    L.hg_verify_public_batch_bn254.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t,
-                                               C.POINTER(C.c_int), C.c_void_p, C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]
-    n = len(proofs)
-    if len(instances) != n:
-        raise ValueError("verify_public_batch_bn254: one instance per proof")
-    nc, nco = pk_claim_shape(pk)
-    m, nc1, nco1 = max(n, 1), max(nc, 1), max(nco, 1)
-    hs = (C.c_void_p * m)(*[x.h.value for x in instances])
-    ps = (C.c_char_p * m)(*[bytes(p) for p in proofs])
-    lens = (C.c_size_t * m)(*[len(p) for p in proofs])
-    res = (C.c_int * m)()
-    claims = (HgInputClaimBn254 * (m * nc1))()
-    points = np.zeros(4 * m * nco1, dtype=np.uint64)
-    counts = (C.c_size_t * m)()
-    reasons = C.create_string_buffer(m * reason_cap)
-    rc = L.hg_verify_public_batch_bn254(ctx.h if ctx is not None else None, pk.h, hs, ps, lens, n, res, claims, nc1, _ptr(points), nco1, counts, reasons, reason_cap)
-    if rc < 0:
-        raise HgError(lib().hg_last_error().decode())
-    raw = reasons.raw
-    out = []
-    for i in range(n):
-        if res[i]:
-            out.append((False, raw[i * reason_cap:(i + 1) * reason_cap].split(b"\0", 1)[0].decode(), None))
-            continue
-        mine = (HgInputClaimBn254 * nc1)(*claims[i * nc1:(i + 1) * nc1])
-        out.append((True, "", InputClaimsBn254(mine, counts[i], points[4 * i * nco1:4 * (i + 1) * nco1].copy())))
-    return out
-
-
-def instance_mle_batch_bn254(ctx, instances, which, index, point):
-    """hg_instance_mle_batch_bn254: the MLE of ais[index] (which 0) or ct0is (which 1) of every instance at ONE Fr point (Python ints
-    below r), through the kernel of hg_verify_public_batch_bn254 as one work unit: a list of Python ints. Device only."""
-    pt = Context._fr_pack(point)
-    n = len(instances)
-    out = np.zeros(4 * max(n, 1), dtype=np.uint64)
-    hs = (C.c_void_p * max(n, 1))(*[x.h.value for x in instances])
-    L = lib()
-    L.hg_instance_mle_batch_bn254.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.c_int, C.c_int, u64p, C.c_size_t, u64p]
-    _check(L.hg_instance_mle_batch_bn254(ctx.h if ctx is not None else None, hs, n, which, index, _ptr(pt), len(point), _ptr(out)))
-    return Context._fr_unpack(out)[:n]
-
-
-def claims_settle_bn254(ctx, params, witness, claims):
-    """hg_claims_settle_bn254: every claim of an InputClaimsBn254 against the witness handle (ctx None: host): (accepted, reason)."""
-    L = lib()
-    L.hg_claims_settle_bn254.argtypes = [C.c_void_p, C.POINTER(HgParams), C.c_void_p, C.c_void_p, C.c_size_t, u64p]
-    rc = L.hg_claims_settle_bn254(ctx.h if ctx is not None else None, C.byref(params), witness.h, claims.claims, claims.n, _ptr(claims.points))
-    if rc < 0:
-        raise HgError(lib().hg_last_error().decode())
-    return rc == 0, ("" if rc == 0 else lib().hg_last_error().decode())
-
-
-def verify_bn254(pk, witness, proof):
-    """BfvEncrypt::verify over bn256::Fr [REF sk_encryption_circuit.rs:462-517, 614-626]: (accepted, reason)."""
-    rc = lib().hg_verify_bn254(pk.h, witness.h, proof, len(proof))
-    if rc < 0:
-        raise HgError(lib().hg_last_error().decode())
-    return rc == 0, ("" if rc == 0 else lib().hg_last_error().decode())
+    return _claims_verify("_bn254", params, root, claims, opening, n_queries, log2_row, None)
 
 
 class LassoNode:

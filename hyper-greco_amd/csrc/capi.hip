@@ -36,6 +36,7 @@ static thread_local std::string g_last_error;
     }                                                                           \
     catch (const std::exception& ex) { g_last_error = ex.what(); return ret; } \
     catch (...) { g_last_error = "unknown error"; return ret; }
+#define HG_ENTRY(...) HG_TRY return __VA_ARGS__; HG_CATCH(-1)   // an entry that is one call of a routine of the shared layer
 
 // (called from the worker threads of hg_setup's node loop: the current device is per thread, the key's list of allocations is shared)
 template <typename T>
@@ -73,6 +74,496 @@ static void check_witness(const hg_pk* pk, const hg_witness* w, const char* who)
     if (v.s.size() != SZ || v.e.size() != SZ || v.k1.size() != SZ || v.ais.size() != k * SZ || v.r1is.size() != k * SZ || v.r2is.size() != k * PZ ||
         v.ct0is.size() != k * SZ)
         throw Error(std::string(who) + ": witness table sizes do not match the parameter set");
+}
+
+static const hg_instance* as_instance(const void* h) { return static_cast<const hg_instance*>(h); }
+
+// the instance must have been built for the key's parameter set: the walk indexes its coefficients with sizes taken from the key
+static void check_instance(const hg_pk* pk, const hg_instance* in, const char* who) {
+    const hg_params& a = pk->params.raw;
+    const hg_params& b = in->params;
+    const size_t kn = (size_t)a.k * a.n;
+    if (a.n != b.n || a.k != b.k || memcmp(a.qis, b.qis, sizeof(a.qis[0]) * a.k) != 0 || in->inst.a.size() != kn || in->inst.ct0.size() != kn)
+        throw Error(std::string(who) + ": the instance was built for other parameters than the key (n=" + std::to_string(b.n) + " k=" + std::to_string(b.k) + " against n=" +
+                    std::to_string(a.n) + " k=" + std::to_string(a.k) + ", or other moduli)");
+}
+
+// ---- the layer both fields share -------------------------------------------------------------------------------------------------
+// Every entry point that exists over Goldilocks and over bn256::Fr (`_bn254`) checks its arguments, converts claims, writes results
+// and reasons in the routines below, once. What they need to know of a field is how an element crosses the ABI and which walk,
+// evaluator or commitment scheme to call: GlAbi (an Ext2 element, 2 words, canonical when both are below GL_P) and BnAbi (an Fr
+// element, 4 little-endian words, canonical when below r). The checks, their order and their messages are part of the interface
+// (tests/test_capi_messages.py pins them): where two siblings differ, the difference is a parameter here, marked "historical".
+// An entry without protocol modes passes mode 0.
+namespace {   // (internal linkage: the library exports nothing but the C ABI)
+struct GlAbi {
+    static constexpr size_t WORDS = 2;
+    static constexpr pcs::Field FIELD = pcs::GOLDILOCKS;
+    typedef OpenClaim Open;
+    typedef hg_input_claim Wire;
+    typedef pcs::Claim PcsClaim;
+    typedef E2 Elem;
+    static bool canonical(const u64* w) { return w[0] < GL_P && w[1] < GL_P; }
+    static Elem elem(const u64* w) { return e2(w[0], w[1]); }
+    static std::string other_field(const char* who) { (void)who; return "the commitment is over BN254: open it with the _bn254 entry"; }
+    static size_t nvars(const Open& c) { return c.point.size(); }
+    static Open open_claim(size_t input, const u64* value, const u64* point, size_t nv) {
+        Open c{input, std::vector<E2>(nv), elem(value)};
+        for (size_t j = 0; j < nv; j++) c.point[j] = elem(point + 2 * j);
+        return c;
+    }
+    static void put(const Open& c, u64* value, u64* point) {
+        value[0] = c.value.c0; value[1] = c.value.c1;
+        for (size_t j = 0; j < c.point.size(); j++) { point[2 * j] = c.point[j].c0; point[2 * j + 1] = c.point[j].c1; }
+    }
+    static std::vector<E2> point_of(const u64* point, size_t nv) {
+        std::vector<E2> pt(nv);
+        for (size_t i = 0; i < nv; i++) pt[i] = elem(point + 2 * i);
+        return pt;
+    }
+    static std::string verify_public(hg_ctx* ctx, bool device, const hg_pk* pk, const Instance& inst, const uint8_t* proof, size_t len, int mode, std::vector<Open>& open) {
+        return device ? verify_public_device(ctx, pk, inst, proof, len, mode, open) : hg::verify_public(pk->params, pk->lasso, pk->circuit, inst, proof, len, mode, open);
+    }
+    static std::string settle(hg_ctx* ctx, const Params& p, const Witness& w, const std::vector<Open>& cl) { return ctx ? claims_settle_device(ctx, p, w, cl) : claims_settle(p, w, cl); }
+    static void mle(hg_ctx* ctx, const Params& p, const Instance& inst, int which, int index, const u64* point, size_t nv, u64* out) {
+        const std::vector<E2> pt = point_of(point, nv);
+        const E2 v = ctx ? instance_mle_device(ctx, p, inst, which, index, pt) : instance_mle(p, inst, which, index, pt);
+        out[0] = v.c0; out[1] = v.c1;
+    }
+    static void mle_batch(hg_ctx* ctx, const Params& p, const std::vector<const Instance*>& I, int which, int index, const u64* point, size_t nv, u64* out) {
+        std::vector<E2> res(I.size());
+        instance_mle_batch_device(ctx, p, I, which, index, point_of(point, nv), res.data());
+        for (size_t i = 0; i < I.size(); i++) { out[2 * i] = res[i].c0; out[2 * i + 1] = res[i].c1; }
+    }
+    // historical: a commit error of hg_secrets_commit is wrapped with the entry's name here, the BN254 commit is given the name instead
+    static pcs::Commitment* commit_secrets(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const u64* const* tabs) {
+        try {
+            return ctx ? pcs::commit_device(ctx, sh, tabs) : pcs::commit_host(sh, tabs);
+        } catch (const std::exception& e) {
+            throw Error(std::string(who) + ": " + e.what());
+        }
+    }
+    static std::vector<uint8_t> pcs_open(const char* who, const pcs::Commitment& cm, const std::vector<PcsClaim>& cl, size_t Q) { return pcs::open(who, cm, cl, Q); }
+    // ctx: the device form (hg_pcs_verify_device), whose errors carry the entry's name
+    static std::string pcs_verify(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& cl, size_t Q, const uint8_t* proof, size_t len) {
+        if (!ctx) return pcs::verify(sh, root, cl, Q, proof, len);
+        try {
+            return pcs::verify_device(ctx, sh, root, cl, Q, proof, len);
+        } catch (const std::exception& e) {
+            throw Error(std::string(who) + ": " + e.what());
+        }
+    }
+};
+
+struct BnAbi {
+    static constexpr size_t WORDS = 4;
+    static constexpr pcs::Field FIELD = pcs::BN254;
+    typedef OpenClaimBn Open;
+    typedef hg_input_claim_bn254 Wire;
+    typedef bn::PcsClaim PcsClaim;
+    typedef bn::Fr Elem;
+    static bool canonical(const u64* w) { return bn254_canonical(w); }
+    static Elem elem(const u64* w) { bn::Fr x; memcpy(x.l, w, 32); return x; }
+    static std::string other_field(const char* who) {   // names the Goldilocks entry: `who` without its suffix
+        const std::string w(who);
+        return "the commitment is over Goldilocks: open it with " + w.substr(0, w.size() - strlen("_bn254"));
+    }
+    static size_t nvars(const Open& c) { return c.point4.size() / 4; }
+    static Open open_claim(size_t input, const u64* value, const u64* point, size_t nv) {
+        Open c;
+        c.input = input;
+        memcpy(c.value, value, 32);
+        c.point4.assign(point, point + 4 * nv);
+        return c;
+    }
+    static void put(const Open& c, u64* value, u64* point) {
+        memcpy(value, c.value, 32);
+        if (!c.point4.empty()) memcpy(point, c.point4.data(), c.point4.size() * 8);
+    }
+    static std::string verify_public(hg_ctx* ctx, bool device, const hg_pk* pk, const Instance& inst, const uint8_t* proof, size_t len, int, std::vector<Open>& open) {
+        return device ? bn::verify_public_device_bn254(ctx, pk, inst, proof, len, open) : verify_public_bn254(pk->params, pk->lasso, pk->circuit, inst, proof, len, open);
+    }
+    static std::string settle(hg_ctx* ctx, const Params& p, const Witness& w, const std::vector<Open>& cl) { return ctx ? bn::claims_settle_device_bn254(ctx, p, w, cl) : claims_settle_bn254(p, w, cl); }
+    static void mle(hg_ctx* ctx, const Params& p, const Instance& inst, int which, int index, const u64* point, size_t nv, u64* out) {
+        if (ctx) bn::instance_mle_device_bn254(ctx, p, inst, which, index, point, nv, out);
+        else instance_mle_bn254(p, inst, which, index, point, nv, out);
+    }
+    static void mle_batch(hg_ctx* ctx, const Params& p, const std::vector<const Instance*>& I, int which, int index, const u64* point, size_t nv, u64* out) {
+        std::vector<u64> res(4 * I.size());   // (an error of the device pass leaves out alone)
+        bn::instance_mle_batch_device_bn254(ctx, p, I, which, index, point, nv, res.data());
+        memcpy(out, res.data(), res.size() * sizeof(u64));
+    }
+    // the witness words are lifted into Fr by the signed rule (the table hg_claims_settle_bn254 evaluates)
+    static pcs::Commitment* commit_secrets(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const u64* const* tabs) {
+        return ctx ? bn::pcs_commit_device(who, ctx, sh, tabs, true) : bn::pcs_commit_host(who, sh, tabs, true);
+    }
+    static std::vector<uint8_t> pcs_open(const char* who, const pcs::Commitment& cm, const std::vector<PcsClaim>& cl, size_t Q) { return bn::pcs_open(who, cm, cl, Q); }
+    // (host only: no entry passes a context)
+    static std::string pcs_verify(const char*, hg_ctx*, const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& cl, size_t Q, const uint8_t* proof, size_t len) {
+        return bn::pcs_verify(sh, root, cl, Q, proof, len);
+    }
+};
+}  // namespace
+
+// a decision of a verifier: "" accepted (0), else rejected (1) with the reason where hg_last_error() finds it
+static int decision(const std::string& why) {
+    if (why.empty()) return 0;
+    g_last_error = why;
+    return 1;
+}
+
+// item i's slot of a caller's `reasons`: the text cut to reason_cap - 1 bytes, always terminated
+static void write_reason(char* reasons, size_t reason_cap, size_t i, const std::string& why) {
+    if (!reasons || !reason_cap) return;
+    char* r = reasons + i * reason_cap;
+    const size_t m = std::min(why.size(), reason_cap - 1);
+    memcpy(r, why.data(), m);
+    r[m] = 0;
+}
+
+// why[i] -> results[i] and the reason slots; returns how many were rejected
+static int write_results(const std::vector<std::string>& why, int* results, char* reasons, size_t reason_cap) {
+    int rejected = 0;
+    for (size_t i = 0; i < why.size(); i++) {
+        results[i] = why[i].empty() ? 0 : 1;
+        rejected += results[i];
+        write_reason(reasons, reason_cap, i, why[i]);
+    }
+    return rejected;
+}
+
+// hg_prove_encryptions*: run(want_witnesses, &total_ms) is the field's pipeline. Historical: the Goldilocks entry also sums gpu_ms and
+// replay_ms into the timings (gpu_timings).
+template <class Run>
+static int prove_encryptions_entry(const std::string& who, bool gpu_timings, hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e,
+                                   const int64_t* const* k1, const int64_t* const* a, size_t n_enc, uint8_t* proofs, size_t cap_each, size_t* lens, int* status,
+                                   hg_witness** ws, char* reasons, size_t reason_cap, hg_timings* timings, Run run) {
+    if (ws) for (size_t i = 0; i < n_enc; i++) ws[i] = nullptr;
+    if (!ctx) throw Error(who + ": needs a device context (derivation and proving run on the GPU and have no host fallback)");
+    if (!pk || (n_enc && (!s || !e || !k1 || !a || !proofs || !lens || !status))) throw Error(who + ": null argument");
+    if (!pk->ctx) throw Error(who + ": host-only prover key (created without a context)");
+    for (size_t i = 0; i < n_enc; i++)
+        if (!s[i] || !e[i] || !k1[i] || !a[i]) throw Error(who + ": encryption " + std::to_string(i) + ": null polynomial");
+    double total = 0;
+    std::vector<EncResult> rs = run(ws != nullptr, &total);
+    if (timings) { memset(timings, 0, sizeof(*timings)); timings->total_ms = total; }
+    for (size_t i = 0; i < n_enc; i++)
+        if (!rs[i].refused && rs[i].r.proof.size() > cap_each)
+            throw Error(who + ": encryption " + std::to_string(i) + ": proof buffer too small (" + std::to_string(rs[i].r.proof.size()) + " bytes)");
+    int refused = 0;
+    for (size_t i = 0; i < n_enc; i++) {
+        const EncResult& r = rs[i];
+        status[i] = r.refused ? 1 : 0;
+        lens[i] = r.refused ? 0 : r.r.proof.size();
+        write_reason(reasons, reason_cap, i, r.reason);
+        if (r.refused) { refused++; continue; }
+        memcpy(proofs + i * cap_each, r.r.proof.data(), r.r.proof.size());
+        if (ws) ws[i] = new hg_witness{std::move(rs[i].w), pk->params.raw};
+        if (timings) { timings->prove_ms += r.r.prove_ms; timings->witness_ms += r.witness_gpu_ms; }
+        if (timings && gpu_timings) { timings->gpu_ms += r.r.gpu_ms; timings->replay_ms += r.r.replay_ms; }
+    }
+    return refused;
+}
+
+// the caller's room against hg_pk_claim_shape, ahead of the walk (`each`: " per proof" in a batch)
+static void check_claim_room(const std::string& who, const hg_pk* pk, const void* claims, size_t claim_cap, const u64* points, size_t coord_cap, const char* each) {
+    size_t need_claims = 0, need_coords = 0;
+    claim_shape(pk->params, pk->lasso, pk->circuit, &need_claims, &need_coords);
+    if (claim_cap < need_claims || coord_cap < need_coords || (need_claims && !claims) || (need_coords && !points))
+        throw Error(who + ": room for " + std::to_string(need_claims) + " claims and " + std::to_string(need_coords) + " coordinates" + each + " is needed (hg_pk_claim_shape)");
+}
+
+// ... and after it, before anything is written: an error of the call leaves the outputs alone
+template <class A>
+static void check_claim_count(const std::string& who, const std::vector<typename A::Open>& open, size_t claim_cap, size_t coord_cap) {
+    size_t coords = 0;
+    for (const typename A::Open& c : open) coords += A::nvars(c);
+    if (open.size() > claim_cap || coords > coord_cap) throw Error(who + ": the walk left more claims than hg_pk_claim_shape counts");
+}
+
+// a run of open claims into a caller's block: the claims, and their points one behind the other
+template <class A>
+static void put_claims(const std::vector<typename A::Open>& open, void* claims, u64* points) {
+    typename A::Wire* out = static_cast<typename A::Wire*>(claims);
+    size_t off = 0;
+    for (size_t i = 0; i < open.size(); i++) {
+        out[i].input = (uint32_t)open[i].input;
+        out[i].nvars = (uint32_t)A::nvars(open[i]);
+        out[i].point_off = off;
+        A::put(open[i], out[i].value, points + A::WORDS * off);
+        off += out[i].nvars;
+    }
+}
+
+// hg_verify_public*, hg_verify_public_device*
+template <class A>
+static int verify_public_entry(const char* who, hg_ctx* ctx, bool device, const hg_pk* pk, const void* instance, int mode, const uint8_t* proof, size_t len,
+                               void* claims, size_t claim_cap, uint64_t* points, size_t coord_cap, size_t* n_claims) {
+    if (n_claims) *n_claims = 0;
+    if (device && (!ctx || !pk || !pk->ctx)) throw Error(std::string(who) + ": needs a device context and a device prover key");
+    if (!pk || !instance || !proof || !n_claims) throw Error(std::string(who) + ": null argument");
+    if (mode < 0 || mode > 3) throw Error(std::string(who) + ": unknown mode bits");
+    const hg_instance* in = as_instance(instance);
+    check_instance(pk, in, who);
+    check_claim_room(who, pk, claims, claim_cap, points, coord_cap, "");
+    std::vector<typename A::Open> open;
+    const std::string why = A::verify_public(ctx, device, pk, in->inst, proof, len, mode, open);
+    if (!why.empty()) return decision(why);
+    check_claim_count<A>(who, open, claim_cap, coord_cap);
+    put_claims<A>(open, claims, points);
+    *n_claims = open.size();
+    return 0;
+}
+
+// The four batch entries in one frame: the argument checks, every element checked and gathered, the device pass with its errors given
+// the entry's name, results and reasons, and for the instance-checked ones (hg_verify_public_batch*) the claims. Item is Witness
+// (handles: hg_witness) or Instance (handles: hg_instance); run(items, P, N, why, open) is the field's device pass.
+// Historical: the witness batches report a missing context as "null argument" and a host-only key second, in words of its own; the
+// public batches report both first, in one message.
+template <class A, class Item, class Run>
+static int batch_entry(const std::string& who, hg_ctx* ctx, const hg_pk* pk, const void* const* handles, const uint8_t* const* proofs, const size_t* lens, size_t n, int mode,
+                       int* results, void* claims, size_t claim_cap_each, uint64_t* points, size_t coord_cap_each, size_t* n_claims, char* reasons, size_t reason_cap, Run run) {
+    constexpr bool pub = std::is_same<Item, Instance>::value;
+    if (pub) {
+        if (!ctx || !pk || !pk->ctx) throw Error(who + ": needs a device context and a device prover key");
+        if (n && (!handles || !proofs || !lens || !results || !n_claims)) throw Error(who + ": null argument");
+    } else {
+        if (!ctx || !pk || (n && (!handles || !proofs || !lens || !results))) throw Error(who + ": null argument");
+        if (!pk->ctx) throw Error(who + ": needs a device prover key (hg_setup with a context)");
+    }
+    if (mode < 0 || mode > 3) throw Error(who + ": unknown mode bits");
+    if (pub && n) check_claim_room(who, pk, claims, claim_cap_each, points, coord_cap_each, " per proof");
+    std::vector<const Item*> items(n);
+    std::vector<const uint8_t*> P(n);
+    std::vector<size_t> N(n);
+    for (size_t i = 0; i < n; i++) {
+        if (!handles[i] || !proofs[i]) throw Error(who + ": null " + (pub ? "instance" : "witness") + " or proof at index " + std::to_string(i));
+        if constexpr (pub) {
+            check_instance(pk, as_instance(handles[i]), (who + ": index " + std::to_string(i)).c_str());
+            items[i] = &as_instance(handles[i])->inst;
+        } else {
+            check_witness(pk, static_cast<const hg_witness*>(handles[i]), who.c_str());
+            items[i] = &static_cast<const hg_witness*>(handles[i])->w;
+        }
+        P[i] = proofs[i]; N[i] = lens[i];
+    }
+    if (!n) return 0;
+    std::vector<std::string> why;
+    std::vector<std::vector<typename A::Open>> open;
+    try {
+        run(items, P, N, why, open);
+    } catch (const std::exception& e) {
+        const std::string m = e.what();
+        throw Error(m.rfind(who, 0) == 0 ? m : who + ": " + m);
+    }
+    if (pub)
+        for (size_t i = 0; i < n; i++) check_claim_count<A>(who + ": proof " + std::to_string(i), open[i], claim_cap_each, coord_cap_each);
+    const int rejected = write_results(why, results, reasons, reason_cap);
+    if (pub)
+        for (size_t i = 0; i < n; i++) {
+            n_claims[i] = results[i] ? 0 : open[i].size();
+            if (!results[i]) put_claims<A>(open[i], static_cast<typename A::Wire*>(claims) + i * claim_cap_each, points + A::WORDS * i * coord_cap_each);
+        }
+    return rejected;
+}
+
+// hg_claims_settle*: the claims of the caller's block against the witness handle, on the host or with a context on the device
+template <class A>
+static int claims_settle_entry(const std::string& who, hg_ctx* ctx, const hg_params* params, const hg_witness* w, const void* claims, size_t n, const uint64_t* points) {
+    if (!params || !w || (n && (!claims || !points))) throw Error(who + ": null argument");
+    Params p(*params);
+    const size_t SZ = p.SZ(), k = (size_t)p.k;
+    const Witness& v = w->w;
+    if (w->params.n != params->n || w->params.k != params->k || v.s.size() != SZ || v.e.size() != SZ || v.k1.size() != SZ || v.ais.size() != k * SZ ||
+        v.r1is.size() != k * SZ || v.r2is.size() != k * p.PZ())
+        throw Error(who + ": the witness was built for other parameters");
+    const typename A::Wire* in = static_cast<const typename A::Wire*>(claims);
+    std::vector<typename A::Open> cl(n);
+    for (size_t i = 0; i < n; i++) {
+        if (in[i].input > 3 + 2 * k) throw Error(who + ": input " + std::to_string(in[i].input) + " is not an input of the circuit");
+        if (in[i].nvars > 40) throw Error(who + ": a claim with " + std::to_string(in[i].nvars) + " coordinates");
+        const u64* pt = points + A::WORDS * in[i].point_off;
+        cl[i] = A::open_claim(in[i].input, in[i].value, pt, in[i].nvars);
+        for (size_t j = 0; j < in[i].nvars; j++) if (!A::canonical(pt + A::WORDS * j)) throw Error(who + ": non-canonical coordinate");
+        if (!A::canonical(in[i].value)) throw Error(who + ": non-canonical value");
+    }
+    return decision(A::settle(ctx, p, v, cl));
+}
+
+// hg_instance_mle* (batch false: instances is the one handle) and hg_instance_mle_batch* (device only; every instance of the
+// parameters of the first)
+template <class A>
+static int instance_mle_entry(const std::string& who, bool batch, hg_ctx* ctx, const void* const* instances, size_t n, int which, int index, const uint64_t* point,
+                              size_t nvars, uint64_t* out) {
+    if (batch && !ctx) throw Error(who + ": needs a device context");
+    if (!instances || (!batch && !instances[0]) || (nvars && !point) || !out) throw Error(who + ": null argument");
+    if (!n) return 0;
+    std::vector<const Instance*> I(n);
+    for (size_t i = 0; i < n; i++) {
+        if (batch) {
+            if (!instances[i]) throw Error(who + ": null instance at index " + std::to_string(i));
+            const hg_params &a = as_instance(instances[0])->params, &b = as_instance(instances[i])->params;
+            if (a.n != b.n || a.k != b.k || memcmp(a.qis, b.qis, sizeof(a.qis[0]) * a.k) != 0)
+                throw Error(who + ": the instance at index " + std::to_string(i) + " was built for other parameters than the first");
+        }
+        I[i] = &as_instance(instances[i])->inst;
+    }
+    Params p(as_instance(instances[0])->params);
+    if (which != 0 && which != 1) throw Error(who + ": which is 0 (ais[index]) or 1 (ct0is)");
+    if (which == 0 && (index < 0 || index >= p.k)) throw Error(who + ": no such modulus");
+    if (nvars != (size_t)(which ? p.ct0is_log2() : p.L)) throw Error(who + ": the table has " + std::to_string(which ? p.ct0is_log2() : p.L) + " variables");
+    if (batch)
+        for (const Instance* x : I)
+            if (x->a.size() != (size_t)p.k * p.PZ() || x->ct0.size() != (size_t)p.k * p.PZ()) throw Error(who + ": an instance of the wrong size");
+    for (size_t i = 0; i < nvars; i++)
+        if (!A::canonical(point + A::WORDS * i)) throw Error(who + ": non-canonical coordinate");
+    if (batch) A::mle_batch(ctx, p, I, which, index, point, nvars, out);
+    else A::mle(ctx, p, *I[0], which, index, point, nvars, out);
+    return 0;
+}
+
+// ---- polynomial commitment (pcs.hpp, pcs_bn254.hpp): hg_pcs_* on caller tables, hg_secrets_commit / hg_claims_open / hg_claims_verify
+// for the five secret inputs of an encryption
+template <class A>
+static std::vector<typename A::PcsClaim> pcs_claims(const char* who, const pcs::Shape& sh, const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n) {
+    const std::string w(who);
+    if (n > pcs::MAX_CLAIMS) throw Error(w + ": more than " + std::to_string(pcs::MAX_CLAIMS) + " claims");
+    std::vector<typename A::PcsClaim> cl(n);
+    const uint64_t* pt = points;
+    for (size_t i = 0; i < n; i++) {
+        if (table[i] >= sh.nvars.size()) throw Error(w + ": claim " + std::to_string(i) + " names table " + std::to_string(table[i]) + " of " + std::to_string(sh.nvars.size()));
+        cl[i].table = table[i];
+        cl[i].point.resize((size_t)sh.nvars[table[i]]);
+        for (size_t j = 0; j < cl[i].point.size(); j++) cl[i].point[j] = A::elem(pt + A::WORDS * j);
+        cl[i].value = A::elem(values + A::WORDS * i);
+        for (size_t j = 0; j < cl[i].point.size(); j++) if (!A::canonical(pt + A::WORDS * j)) throw Error(w + ": claim " + std::to_string(i) + ": non-canonical coordinate");
+        if (!A::canonical(values + A::WORDS * i)) throw Error(w + ": claim " + std::to_string(i) + ": non-canonical value");
+        pt += A::WORDS * cl[i].point.size();
+    }
+    return cl;
+}
+static size_t pcs_queries(const char* who, size_t n_queries) {
+    if (n_queries > pcs::MAX_QUERIES) throw Error(std::string(who) + ": more than " + std::to_string(pcs::MAX_QUERIES) + " queries");
+    return n_queries ? n_queries : pcs::DEFAULT_QUERIES;
+}
+static void pcs_emit(const char* who, const std::vector<uint8_t>& bytes, uint8_t* out, size_t cap, size_t* len) {
+    *len = bytes.size();
+    if (bytes.size() > cap) throw Error(std::string(who) + ": the opening has " + std::to_string(bytes.size()) + " bytes, the buffer " + std::to_string(cap));
+    memcpy(out, bytes.data(), bytes.size());
+}
+// the secret inputs as commitment tables, in input order s, e, k1, r1is[0..k-1], r2is
+static std::vector<uint32_t> secrets_nvars(const Params& p) {
+    std::vector<uint32_t> v(3 + (size_t)p.k, (uint32_t)p.L);
+    v.push_back((uint32_t)(p.n_log2 + p.log2k));
+    return v;
+}
+// an array of input claims -> (table, points, values) of the commitment over the secret inputs
+template <class A>
+static void secrets_claims(const char* who, const Params& p, const void* claims, size_t n, const uint64_t* points, std::vector<uint32_t>& table,
+                           std::vector<uint64_t>& pts, std::vector<uint64_t>& vals) {
+    const std::string w(who);
+    if (n > pcs::MAX_CLAIMS) throw Error(w + ": more than " + std::to_string(pcs::MAX_CLAIMS) + " claims");
+    const typename A::Wire* in = static_cast<const typename A::Wire*>(claims);
+    const std::vector<uint32_t> nv = secrets_nvars(p);
+    const uint32_t k = (uint32_t)p.k;
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t id = in[i].input;
+        uint32_t t;
+        if (id < 3) t = id;
+        else if (id >= 3 + k && id < 3 + 2 * k) t = id - k;
+        else if (id == 3 + 2 * k) t = 3 + k;
+        else throw Error(w + ": claim " + std::to_string(i) + " is on input " + std::to_string(id) + ", which is not a secret input (0, 1, 2, " + std::to_string(3 + k) + " .. " + std::to_string(3 + 2 * k) + ")");
+        if (in[i].nvars != nv[t]) throw Error(w + ": claim " + std::to_string(i) + " has " + std::to_string(in[i].nvars) + " coordinates, input " + std::to_string(id) + " has " + std::to_string(nv[t]) + " variables");
+        table.push_back(t);
+        pts.insert(pts.end(), points + A::WORDS * in[i].point_off, points + A::WORDS * (in[i].point_off + in[i].nvars));
+        vals.insert(vals.end(), in[i].value, in[i].value + A::WORDS);
+    }
+}
+
+// hg_pcs_open* after its null checks, and the tail of hg_claims_open* (which has checked the field already)
+template <class A>
+static int pcs_open_entry(const char* who, hg_ctx* ctx, const pcs::Commitment* cm, const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n_claims,
+                          size_t n_queries, uint8_t* proof, size_t cap, size_t* len) {
+    if (cm->field != A::FIELD) throw Error(std::string(who) + ": " + A::other_field(who));
+    if (cm->ctx != ctx) throw Error(std::string(who) + ": the commitment was made " + (cm->ctx ? "on a device context: pass that context" : "by the host form: pass no context"));
+    const std::vector<typename A::PcsClaim> cl = pcs_claims<A>(who, cm->sh, table, points, values, n_claims);
+    pcs_emit(who, A::pcs_open(who, *cm, cl, pcs_queries(who, n_queries)), proof, cap, len);
+    return 0;
+}
+
+template <class A>
+static int pcs_open_api(const char* who, hg_ctx* ctx, const void* commitment, const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n_claims,
+                        size_t n_queries, uint8_t* proof, size_t cap, size_t* len) {
+    if (len) *len = 0;
+    if (!commitment || !proof || !len || (n_claims && (!table || !points || !values))) throw Error(std::string(who) + ": null argument");
+    return pcs_open_entry<A>(who, ctx, static_cast<const pcs::Commitment*>(commitment), table, points, values, n_claims, n_queries, proof, cap, len);
+}
+
+// hg_pcs_verify* (device == false) and hg_pcs_verify_device: the same argument checks in the same order, then the form's verifier
+template <class A>
+static int pcs_verify_entry(const char* who, bool device, hg_ctx* ctx, const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row,
+                            const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
+    const std::string w(who);
+    if (!root || !nvars || (len && !proof) || (n_claims && (!table || !points || !values))) throw Error(w + ": null argument");
+    const pcs::Shape sh = pcs::make_shape(who, nvars, n_tables, log2_row);
+    const std::vector<typename A::PcsClaim> cl = pcs_claims<A>(who, sh, table, points, values, n_claims);
+    const size_t Q = pcs_queries(who, n_queries);
+    if (device && !ctx) throw Error(w + ": no context");
+    return decision(A::pcs_verify(who, device ? ctx : nullptr, sh, root, cl, Q, proof, len));
+}
+
+// hg_secrets_commit*
+template <class A>
+static int secrets_commit_entry(const char* who, hg_ctx* ctx, const hg_params* params, const hg_witness* w, size_t log2_row, void** commitment, uint8_t root[32]) {
+    if (commitment) *commitment = nullptr;
+    if (!params || !w || !commitment || !root) throw Error(std::string(who) + ": null argument");
+    Params p(*params);
+    const size_t SZ = p.SZ(), k = (size_t)p.k;
+    const Witness& v = w->w;
+    if (w->params.n != params->n || w->params.k != params->k || v.s.size() != SZ || v.e.size() != SZ || v.k1.size() != SZ || v.r1is.size() != k * SZ ||
+        v.r2is.size() != k * p.PZ())
+        throw Error(std::string(who) + ": the witness was built for other parameters");
+    const std::vector<uint32_t> nv = secrets_nvars(p);
+    std::vector<const uint64_t*> tabs = {v.s.data(), v.e.data(), v.k1.data()};
+    for (size_t i = 0; i < k; i++) tabs.push_back(v.r1is.data() + i * SZ);
+    tabs.push_back(v.r2is.data());
+    const pcs::Shape sh = pcs::make_shape(who, nv.data(), nv.size(), log2_row);
+    pcs::Commitment* cm = A::commit_secrets(who, ctx, sh, tabs.data());
+    memcpy(root, cm->root(), 32);
+    *commitment = cm;
+    return 0;
+}
+
+// hg_claims_open*: `mine` names the entry that made the commitment (hg_secrets_commit*)
+template <class A>
+static int claims_open_entry(const char* who, const char* mine, hg_ctx* ctx, const hg_params* params, const void* commitment, const void* claims, size_t n, const uint64_t* points,
+                             size_t n_queries, uint8_t* opening, size_t cap, size_t* len) {
+    if (len) *len = 0;
+    if (!params || !commitment || !opening || !len || (n && (!claims || !points))) throw Error(std::string(who) + ": null argument");
+    Params p(*params);
+    const pcs::Commitment* cm = static_cast<const pcs::Commitment*>(commitment);
+    if (cm->field != A::FIELD) throw Error(std::string(who) + ": " + A::other_field(who));
+    const std::vector<uint32_t> nv = secrets_nvars(p);
+    if (cm->sh.nvars.size() != nv.size() || !std::equal(nv.begin(), nv.end(), cm->sh.nvars.begin(), [](uint32_t a, int b) { return (int)a == b; }))
+        throw Error(std::string(who) + ": the commitment is not " + mine + "'s for these parameters");
+    std::vector<uint32_t> table;
+    std::vector<uint64_t> pts, vals;
+    secrets_claims<A>(who, p, claims, n, points, table, pts, vals);
+    return pcs_open_entry<A>(who, ctx, cm, table.data(), pts.data(), vals.data(), n, n_queries, opening, cap, len);
+}
+
+// hg_claims_verify*, hg_claims_verify_device
+template <class A>
+static int claims_verify_entry(const char* who, bool device, hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n,
+                               const uint64_t* points, size_t n_queries, const uint8_t* opening, size_t len) {
+    if (!params || !root || (len && !opening) || (n && (!claims || !points))) throw Error(std::string(who) + ": null argument");
+    Params p(*params);
+    const std::vector<uint32_t> nv = secrets_nvars(p);
+    std::vector<uint32_t> table;
+    std::vector<uint64_t> pts, vals;
+    (void)pcs::make_shape(who, nv.data(), nv.size(), log2_row);   // a shape error is reported ahead of a claim's
+    secrets_claims<A>(who, p, claims, n, points, table, pts, vals);
+    return pcs_verify_entry<A>(who, device, ctx, root, nv.data(), nv.size(), log2_row, table.data(), pts.data(), vals.data(), n, n_queries, opening, len);
 }
 
 extern "C" {
@@ -761,73 +1252,15 @@ int hg_encryption_layout(const hg_params* params, const int64_t* s, const int64_
 int hg_prove_encryptions(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e, const int64_t* const* k1,
                          const int64_t* const* a, size_t n_enc, uint8_t* proofs, size_t cap_each, size_t* lens, int* status, hg_witness** ws,
                          char* reasons, size_t reason_cap, hg_timings* timings) {
-    HG_TRY
-    if (ws) for (size_t i = 0; i < n_enc; i++) ws[i] = nullptr;
-    if (!ctx) throw Error("hg_prove_encryptions: needs a device context (derivation and proving run on the GPU and have no host fallback)");
-    if (!pk || (n_enc && (!s || !e || !k1 || !a || !proofs || !lens || !status))) throw Error("hg_prove_encryptions: null argument");
-    if (!pk->ctx) throw Error("hg_prove_encryptions: host-only prover key (created without a context)");
-    for (size_t i = 0; i < n_enc; i++)
-        if (!s[i] || !e[i] || !k1[i] || !a[i]) throw Error("hg_prove_encryptions: encryption " + std::to_string(i) + ": null polynomial");
-    double total = 0;
-    std::vector<EncResult> rs = prove_encryptions(ctx, pk, s, e, k1, a, n_enc, ws != nullptr, &total);
-    if (timings) { memset(timings, 0, sizeof(*timings)); timings->total_ms = total; }
-    for (size_t i = 0; i < n_enc; i++)
-        if (!rs[i].refused && rs[i].r.proof.size() > cap_each)
-            throw Error("hg_prove_encryptions: encryption " + std::to_string(i) + ": proof buffer too small (" + std::to_string(rs[i].r.proof.size()) + " bytes)");
-    int refused = 0;
-    for (size_t i = 0; i < n_enc; i++) {
-        const EncResult& r = rs[i];
-        status[i] = r.refused ? 1 : 0;
-        lens[i] = r.refused ? 0 : r.r.proof.size();
-        if (reasons && reason_cap) {
-            char* dst = reasons + i * reason_cap;
-            const size_t m = std::min(r.reason.size(), reason_cap - 1);
-            memcpy(dst, r.reason.data(), m);
-            dst[m] = 0;
-        }
-        if (r.refused) { refused++; continue; }
-        memcpy(proofs + i * cap_each, r.r.proof.data(), r.r.proof.size());
-        if (ws) ws[i] = new hg_witness{std::move(rs[i].w), pk->params.raw};
-        if (timings) { timings->prove_ms += r.r.prove_ms; timings->gpu_ms += r.r.gpu_ms; timings->replay_ms += r.r.replay_ms; timings->witness_ms += r.witness_gpu_ms; }
-    }
-    return refused;
-    HG_CATCH(-1)
+    HG_ENTRY(prove_encryptions_entry("hg_prove_encryptions", true, ctx, pk, s, e, k1, a, n_enc, proofs, cap_each, lens, status, ws, reasons, reason_cap, timings,
+                                     [&](bool want, double* total) { return prove_encryptions(ctx, pk, s, e, k1, a, n_enc, want, total); }))
 }
 
 int hg_prove_encryptions_bn254(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e, const int64_t* const* k1,
                                const int64_t* const* a, size_t n_enc, uint8_t* proofs, size_t cap_each, size_t* lens, int* status, hg_witness** ws,
                                char* reasons, size_t reason_cap, hg_timings* timings) {
-    HG_TRY
-    if (ws) for (size_t i = 0; i < n_enc; i++) ws[i] = nullptr;
-    if (!ctx) throw Error("hg_prove_encryptions_bn254: needs a device context (derivation and proving run on the GPU and have no host fallback)");
-    if (!pk || (n_enc && (!s || !e || !k1 || !a || !proofs || !lens || !status))) throw Error("hg_prove_encryptions_bn254: null argument");
-    if (!pk->ctx) throw Error("hg_prove_encryptions_bn254: host-only prover key (created without a context)");
-    for (size_t i = 0; i < n_enc; i++)
-        if (!s[i] || !e[i] || !k1[i] || !a[i]) throw Error("hg_prove_encryptions_bn254: encryption " + std::to_string(i) + ": null polynomial");
-    double total = 0;
-    std::vector<EncResult> rs = bn::prove_encryptions_bn254(ctx, pk, s, e, k1, a, n_enc, ws != nullptr, &total);
-    if (timings) { memset(timings, 0, sizeof(*timings)); timings->total_ms = total; }
-    for (size_t i = 0; i < n_enc; i++)
-        if (!rs[i].refused && rs[i].r.proof.size() > cap_each)
-            throw Error("hg_prove_encryptions_bn254: encryption " + std::to_string(i) + ": proof buffer too small (" + std::to_string(rs[i].r.proof.size()) + " bytes)");
-    int refused = 0;
-    for (size_t i = 0; i < n_enc; i++) {
-        const EncResult& r = rs[i];
-        status[i] = r.refused ? 1 : 0;
-        lens[i] = r.refused ? 0 : r.r.proof.size();
-        if (reasons && reason_cap) {
-            char* dst = reasons + i * reason_cap;
-            const size_t m = std::min(r.reason.size(), reason_cap - 1);
-            memcpy(dst, r.reason.data(), m);
-            dst[m] = 0;
-        }
-        if (r.refused) { refused++; continue; }
-        memcpy(proofs + i * cap_each, r.r.proof.data(), r.r.proof.size());
-        if (ws) ws[i] = new hg_witness{std::move(rs[i].w), pk->params.raw};
-        if (timings) { timings->prove_ms += r.r.prove_ms; timings->witness_ms += r.witness_gpu_ms; }
-    }
-    return refused;
-    HG_CATCH(-1)
+    HG_ENTRY(prove_encryptions_entry("hg_prove_encryptions_bn254", false, ctx, pk, s, e, k1, a, n_enc, proofs, cap_each, lens, status, ws, reasons, reason_cap, timings,
+                                     [&](bool want, double* total) { return bn::prove_encryptions_bn254(ctx, pk, s, e, k1, a, n_enc, want, total); }))
 }
 
 int hg_prove_resident_mode(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, int mode, uint8_t* proof, size_t cap, size_t* len, hg_timings* timings) {
@@ -933,10 +1366,7 @@ int hg_verify_mode(const hg_pk* pk, const hg_witness* w, int mode, const uint8_t
     if (!pk || !w || !proof) throw Error("hg_verify_mode: null argument");
     if (mode < 0 || mode > 3) throw Error("hg_verify_mode: unknown mode bits");
     check_witness(pk, w, "hg_verify_mode");
-    std::string why = verify_proof(pk->params, pk->lasso, pk->circuit, w->w, proof, len, mode);
-    if (why.empty()) return 0;
-    g_last_error = why;
-    return 1;
+    return decision(verify_proof(pk->params, pk->lasso, pk->circuit, w->w, proof, len, mode));
     HG_CATCH(-1)
 }
 
@@ -944,10 +1374,7 @@ int hg_verify(const hg_pk* pk, const hg_witness* w, const uint8_t* proof, size_t
     HG_TRY
     if (!pk || !w || !proof) throw Error("hg_verify: null argument");
     check_witness(pk, w, "hg_verify");
-    std::string why = verify_proof(pk->params, pk->lasso, pk->circuit, w->w, proof, len);
-    if (why.empty()) return 0;
-    g_last_error = why;
-    return 1;
+    return decision(verify_proof(pk->params, pk->lasso, pk->circuit, w->w, proof, len));
     HG_CATCH(-1)
 }
 
@@ -955,10 +1382,7 @@ int hg_verify_device(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, const ui
     HG_TRY
     if (!ctx || !pk || !w || !proof || !pk->ctx) throw Error("hg_verify_device: needs a device context and a device prover key");
     check_witness(pk, w, "hg_verify_device");
-    std::string why = verify_proof_device(ctx, pk, w->w, proof, len);
-    if (why.empty()) return 0;
-    g_last_error = why;
-    return 1;
+    return decision(verify_proof_device(ctx, pk, w->w, proof, len));
     HG_CATCH(-1)
 }
 
@@ -967,53 +1391,17 @@ int hg_verify_device_mode(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, int
     if (!ctx || !pk || !w || !proof || !pk->ctx) throw Error("hg_verify_device_mode: needs a device context and a device prover key");
     if (mode < 0 || mode > 3) throw Error("hg_verify_device_mode: unknown mode bits");
     check_witness(pk, w, "hg_verify_device_mode");
-    std::string why = verify_proof_device(ctx, pk, w->w, proof, len, mode);
-    if (why.empty()) return 0;
-    g_last_error = why;
-    return 1;
+    return decision(verify_proof_device(ctx, pk, w->w, proof, len, mode));
     HG_CATCH(-1)
 }
 
 int hg_verify_device_batch(hg_ctx* ctx, const hg_pk* pk, const hg_witness* const* ws, const uint8_t* const* proofs, const size_t* lens, size_t n,
                            int mode, int* results, char* reasons, size_t reason_cap) {
-    HG_TRY
-    if (!ctx || !pk || (n && (!ws || !proofs || !lens || !results))) throw Error("hg_verify_device_batch: null argument");
-    if (!pk->ctx) throw Error("hg_verify_device_batch: needs a device prover key (hg_setup with a context)");
-    if (mode < 0 || mode > 3) throw Error("hg_verify_device_batch: unknown mode bits");
-    std::vector<const Witness*> W(n);
-    std::vector<const uint8_t*> P(n);
-    std::vector<size_t> N(n);
-    for (size_t i = 0; i < n; i++) {
-        if (!ws[i] || !proofs[i]) throw Error("hg_verify_device_batch: null witness or proof at index " + std::to_string(i));
-        check_witness(pk, ws[i], "hg_verify_device_batch");
-        W[i] = &ws[i]->w; P[i] = proofs[i]; N[i] = lens[i];
-    }
-    if (!n) return 0;
-    std::vector<std::string> why;
-    try {
-        verify_batch_device(ctx, pk, W, P, N, mode, why);
-    } catch (const std::exception& e) {
-        const std::string m = e.what();
-        throw Error(m.rfind("hg_verify_device_batch", 0) == 0 ? m : "hg_verify_device_batch: " + m);
-    }
-    int rejected = 0;
-    for (size_t i = 0; i < n; i++) {
-        results[i] = why[i].empty() ? 0 : 1;
-        rejected += results[i];
-        if (reasons && reason_cap) {
-            char* r = reasons + i * reason_cap;
-            const size_t m = std::min(why[i].size(), reason_cap - 1);
-            memcpy(r, why[i].data(), m);
-            r[m] = 0;
-        }
-    }
-    return rejected;
-    HG_CATCH(-1)
+    HG_ENTRY(batch_entry<GlAbi, Witness>("hg_verify_device_batch", ctx, pk, reinterpret_cast<const void* const*>(ws), proofs, lens, n, mode, results, nullptr, 0, nullptr, 0, nullptr, reasons, reason_cap,
+                                       [&](auto& W, auto& P, auto& N, auto& why, auto&) { verify_batch_device(ctx, pk, W, P, N, mode, why); }))
 }
 
 // ---- verification from the ciphertext (hg.h: hg_verify_public and what goes with it) -------------------------------------------
-static const hg_instance* as_instance(const void* h) { return static_cast<const hg_instance*>(h); }
-
 int hg_instance_from_ciphertext(const hg_params* params, const int64_t* a, const int64_t* ct0, void** out) {
     HG_TRY
     if (out) *out = nullptr;
@@ -1076,209 +1464,40 @@ int hg_pk_claim_shape(const hg_pk* pk, size_t* n_claims, size_t* n_coords) {
     HG_CATCH(-1)
 }
 
-// the instance must have been built for the key's parameter set: the walk indexes its coefficients with sizes taken from the key
-static void check_instance(const hg_pk* pk, const hg_instance* in, const char* who) {
-    const hg_params& a = pk->params.raw;
-    const hg_params& b = in->params;
-    const size_t kn = (size_t)a.k * a.n;
-    if (a.n != b.n || a.k != b.k || memcmp(a.qis, b.qis, sizeof(a.qis[0]) * a.k) != 0 || in->inst.a.size() != kn || in->inst.ct0.size() != kn)
-        throw Error(std::string(who) + ": the instance was built for other parameters than the key (n=" + std::to_string(b.n) + " k=" + std::to_string(b.k) + " against n=" +
-                    std::to_string(a.n) + " k=" + std::to_string(a.k) + ", or other moduli)");
-}
-static int verify_public_entry(const char* who, hg_ctx* ctx, bool device, const hg_pk* pk, const void* instance, int mode, const uint8_t* proof, size_t len,
-                               void* claims, size_t claim_cap, uint64_t* points, size_t coord_cap, size_t* n_claims) {
-    if (n_claims) *n_claims = 0;
-    if (device && (!ctx || !pk || !pk->ctx)) throw Error(std::string(who) + ": needs a device context and a device prover key");
-    if (!pk || !instance || !proof || !n_claims) throw Error(std::string(who) + ": null argument");
-    if (mode < 0 || mode > 3) throw Error(std::string(who) + ": unknown mode bits");
-    const hg_instance* in = as_instance(instance);
-    check_instance(pk, in, who);
-    size_t need_claims = 0, need_coords = 0;
-    claim_shape(pk->params, pk->lasso, pk->circuit, &need_claims, &need_coords);
-    if (claim_cap < need_claims || coord_cap < need_coords || (need_claims && !claims) || (need_coords && !points))
-        throw Error(std::string(who) + ": room for " + std::to_string(need_claims) + " claims and " + std::to_string(need_coords) + " coordinates is needed (hg_pk_claim_shape)");
-    std::vector<OpenClaim> open;
-    const std::string why = device ? verify_public_device(ctx, pk, in->inst, proof, len, mode, open)
-                                   : verify_public(pk->params, pk->lasso, pk->circuit, in->inst, proof, len, mode, open);
-    if (!why.empty()) { g_last_error = why; return 1; }
-    size_t coords = 0;
-    for (const OpenClaim& c : open) coords += c.point.size();
-    if (open.size() > claim_cap || coords > coord_cap) throw Error(std::string(who) + ": the walk left more claims than hg_pk_claim_shape counts");
-    hg_input_claim* out = static_cast<hg_input_claim*>(claims);
-    size_t off = 0;
-    for (size_t i = 0; i < open.size(); i++) {
-        out[i].input = (uint32_t)open[i].input;
-        out[i].nvars = (uint32_t)open[i].point.size();
-        out[i].point_off = off;
-        out[i].value[0] = open[i].value.c0; out[i].value[1] = open[i].value.c1;
-        for (const E2& x : open[i].point) { points[2 * off] = x.c0; points[2 * off + 1] = x.c1; off++; }
-    }
-    *n_claims = open.size();
-    return 0;
-}
-
 int hg_verify_public(const hg_pk* pk, const void* instance, int mode, const uint8_t* proof, size_t len, void* claims, size_t claim_cap, uint64_t* points,
                      size_t coord_cap, size_t* n_claims) {
-    HG_TRY
-    return verify_public_entry("hg_verify_public", nullptr, false, pk, instance, mode, proof, len, claims, claim_cap, points, coord_cap, n_claims);
-    HG_CATCH(-1)
+    HG_ENTRY(verify_public_entry<GlAbi>("hg_verify_public", nullptr, false, pk, instance, mode, proof, len, claims, claim_cap, points, coord_cap, n_claims))
 }
 
 int hg_verify_public_device(hg_ctx* ctx, const hg_pk* pk, const void* instance, int mode, const uint8_t* proof, size_t len, void* claims, size_t claim_cap,
                             uint64_t* points, size_t coord_cap, size_t* n_claims) {
-    HG_TRY
-    return verify_public_entry("hg_verify_public_device", ctx, true, pk, instance, mode, proof, len, claims, claim_cap, points, coord_cap, n_claims);
-    HG_CATCH(-1)
+    HG_ENTRY(verify_public_entry<GlAbi>("hg_verify_public_device", ctx, true, pk, instance, mode, proof, len, claims, claim_cap, points, coord_cap, n_claims))
 }
 
 int hg_verify_public_batch(hg_ctx* ctx, const hg_pk* pk, const void* const* instances, const uint8_t* const* proofs, const size_t* lens, size_t n, int mode,
                            int* results, void* claims, size_t claim_cap_each, uint64_t* points, size_t coord_cap_each, size_t* n_claims, char* reasons,
                            size_t reason_cap) {
-    HG_TRY
-    const std::string who = "hg_verify_public_batch";
-    if (!ctx || !pk || !pk->ctx) throw Error(who + ": needs a device context and a device prover key");
-    if (n && (!instances || !proofs || !lens || !results || !n_claims)) throw Error(who + ": null argument");
-    if (mode < 0 || mode > 3) throw Error(who + ": unknown mode bits");
-    size_t need_claims = 0, need_coords = 0;
-    claim_shape(pk->params, pk->lasso, pk->circuit, &need_claims, &need_coords);
-    if (n && (claim_cap_each < need_claims || coord_cap_each < need_coords || (need_claims && !claims) || (need_coords && !points)))
-        throw Error(who + ": room for " + std::to_string(need_claims) + " claims and " + std::to_string(need_coords) + " coordinates per proof is needed (hg_pk_claim_shape)");
-    std::vector<const Instance*> I(n);
-    std::vector<const uint8_t*> P(n);
-    std::vector<size_t> N(n);
-    for (size_t i = 0; i < n; i++) {
-        if (!instances[i] || !proofs[i]) throw Error(who + ": null instance or proof at index " + std::to_string(i));
-        check_instance(pk, as_instance(instances[i]), (who + ": index " + std::to_string(i)).c_str());
-        I[i] = &as_instance(instances[i])->inst; P[i] = proofs[i]; N[i] = lens[i];
-    }
-    if (!n) return 0;
-    std::vector<std::string> why;
-    std::vector<std::vector<OpenClaim>> open;
-    try {
-        verify_public_batch_device(ctx, pk, I, P, N, mode, why, open);
-    } catch (const std::exception& e) {
-        const std::string m = e.what();
-        throw Error(m.rfind(who, 0) == 0 ? m : who + ": " + m);
-    }
-    for (size_t i = 0; i < n; i++) {   // (checked before anything is written: an error of the call leaves the outputs alone)
-        size_t coords = 0;
-        for (const OpenClaim& c : open[i]) coords += c.point.size();
-        if (open[i].size() > claim_cap_each || coords > coord_cap_each) throw Error(who + ": proof " + std::to_string(i) + ": the walk left more claims than hg_pk_claim_shape counts");
-    }
-    int rejected = 0;
-    for (size_t i = 0; i < n; i++) {
-        results[i] = why[i].empty() ? 0 : 1;
-        rejected += results[i];
-        if (reasons && reason_cap) {
-            char* r = reasons + i * reason_cap;
-            const size_t m = std::min(why[i].size(), reason_cap - 1);
-            memcpy(r, why[i].data(), m);
-            r[m] = 0;
-        }
-        n_claims[i] = results[i] ? 0 : open[i].size();
-        if (results[i]) continue;
-        hg_input_claim* out = static_cast<hg_input_claim*>(claims) + i * claim_cap_each;
-        uint64_t* pts = points + 2 * i * coord_cap_each;
-        size_t off = 0;
-        for (size_t j = 0; j < open[i].size(); j++) {
-            const OpenClaim& c = open[i][j];
-            out[j].input = (uint32_t)c.input;
-            out[j].nvars = (uint32_t)c.point.size();
-            out[j].point_off = off;
-            out[j].value[0] = c.value.c0; out[j].value[1] = c.value.c1;
-            for (const E2& x : c.point) { pts[2 * off] = x.c0; pts[2 * off + 1] = x.c1; off++; }
-        }
-    }
-    return rejected;
-    HG_CATCH(-1)
+    HG_ENTRY(batch_entry<GlAbi, Instance>("hg_verify_public_batch", ctx, pk, instances, proofs, lens, n, mode, results, claims, claim_cap_each, points, coord_cap_each, n_claims,
+                                        reasons, reason_cap, [&](auto& I, auto& P, auto& N, auto& why, auto& open) { verify_public_batch_device(ctx, pk, I, P, N, mode, why, open); }))
 }
 
 int hg_claims_settle(hg_ctx* ctx, const hg_params* params, const hg_witness* w, const void* claims, size_t n, const uint64_t* points) {
-    HG_TRY
-    if (!params || !w || (n && (!claims || !points))) throw Error("hg_claims_settle: null argument");
-    Params p(*params);
-    const size_t SZ = p.SZ(), k = (size_t)p.k;
-    const Witness& v = w->w;
-    if (w->params.n != params->n || w->params.k != params->k || v.s.size() != SZ || v.e.size() != SZ || v.k1.size() != SZ || v.ais.size() != k * SZ ||
-        v.r1is.size() != k * SZ || v.r2is.size() != k * p.PZ())
-        throw Error("hg_claims_settle: the witness was built for other parameters");
-    const hg_input_claim* in = static_cast<const hg_input_claim*>(claims);
-    std::vector<OpenClaim> cl(n);
-    for (size_t i = 0; i < n; i++) {
-        if (in[i].input > 3 + 2 * k) throw Error("hg_claims_settle: input " + std::to_string(in[i].input) + " is not an input of the circuit");
-        if (in[i].nvars > 40) throw Error("hg_claims_settle: a claim with " + std::to_string(in[i].nvars) + " coordinates");
-        cl[i].input = in[i].input;
-        cl[i].value = e2(in[i].value[0], in[i].value[1]);
-        cl[i].point.resize(in[i].nvars);
-        for (size_t j = 0; j < in[i].nvars; j++) cl[i].point[j] = e2(points[2 * (in[i].point_off + j)], points[2 * (in[i].point_off + j) + 1]);
-        for (const E2& x : cl[i].point) if (x.c0 >= GL_P || x.c1 >= GL_P) throw Error("hg_claims_settle: non-canonical coordinate");
-        if (cl[i].value.c0 >= GL_P || cl[i].value.c1 >= GL_P) throw Error("hg_claims_settle: non-canonical value");
-    }
-    const std::string why = ctx ? claims_settle_device(ctx, p, v, cl) : claims_settle(p, v, cl);
-    if (why.empty()) return 0;
-    g_last_error = why;
-    return 1;
-    HG_CATCH(-1)
+    HG_ENTRY(claims_settle_entry<GlAbi>("hg_claims_settle", ctx, params, w, claims, n, points))
 }
 
 int hg_instance_mle(hg_ctx* ctx, const void* instance, int which, int index, const uint64_t* point, size_t nvars, uint64_t out2[2]) {
-    HG_TRY
-    if (!instance || (nvars && !point) || !out2) throw Error("hg_instance_mle: null argument");
-    const hg_instance* in = as_instance(instance);
-    Params p(in->params);
-    if (which != 0 && which != 1) throw Error("hg_instance_mle: which is 0 (ais[index]) or 1 (ct0is)");
-    if (which == 0 && (index < 0 || index >= p.k)) throw Error("hg_instance_mle: no such modulus");
-    if (nvars != (size_t)(which ? p.ct0is_log2() : p.L)) throw Error("hg_instance_mle: the table has " + std::to_string(which ? p.ct0is_log2() : p.L) + " variables");
-    std::vector<E2> pt(nvars);
-    for (size_t i = 0; i < nvars; i++) {
-        if (point[2 * i] >= GL_P || point[2 * i + 1] >= GL_P) throw Error("hg_instance_mle: non-canonical coordinate");
-        pt[i] = e2(point[2 * i], point[2 * i + 1]);
-    }
-    const E2 v = ctx ? instance_mle_device(ctx, p, in->inst, which, index, pt) : instance_mle(p, in->inst, which, index, pt);
-    out2[0] = v.c0; out2[1] = v.c1;
-    return 0;
-    HG_CATCH(-1)
+    HG_ENTRY(instance_mle_entry<GlAbi>("hg_instance_mle", false, ctx, &instance, 1, which, index, point, nvars, out2))
 }
 
 int hg_instance_mle_batch(hg_ctx* ctx, const void* const* instances, size_t n, int which, int index, const uint64_t* point, size_t nvars, uint64_t* out) {
-    HG_TRY
-    if (!ctx) throw Error("hg_instance_mle_batch: needs a device context");
-    if (!instances || (nvars && !point) || !out) throw Error("hg_instance_mle_batch: null argument");
-    if (!n) return 0;
-    std::vector<const Instance*> I(n);
-    for (size_t i = 0; i < n; i++) {
-        if (!instances[i]) throw Error("hg_instance_mle_batch: null instance at index " + std::to_string(i));
-        const hg_params &a = as_instance(instances[0])->params, &b = as_instance(instances[i])->params;
-        if (a.n != b.n || a.k != b.k || memcmp(a.qis, b.qis, sizeof(a.qis[0]) * a.k) != 0)
-            throw Error("hg_instance_mle_batch: the instance at index " + std::to_string(i) + " was built for other parameters than the first");
-        I[i] = &as_instance(instances[i])->inst;
-    }
-    Params p(as_instance(instances[0])->params);
-    if (which != 0 && which != 1) throw Error("hg_instance_mle_batch: which is 0 (ais[index]) or 1 (ct0is)");
-    if (which == 0 && (index < 0 || index >= p.k)) throw Error("hg_instance_mle_batch: no such modulus");
-    if (nvars != (size_t)(which ? p.ct0is_log2() : p.L)) throw Error("hg_instance_mle_batch: the table has " + std::to_string(which ? p.ct0is_log2() : p.L) + " variables");
-    for (const Instance* x : I)
-        if (x->a.size() != (size_t)p.k * p.PZ() || x->ct0.size() != (size_t)p.k * p.PZ()) throw Error("hg_instance_mle_batch: an instance of the wrong size");
-    std::vector<E2> pt(nvars);
-    for (size_t i = 0; i < nvars; i++) {
-        if (point[2 * i] >= GL_P || point[2 * i + 1] >= GL_P) throw Error("hg_instance_mle_batch: non-canonical coordinate");
-        pt[i] = e2(point[2 * i], point[2 * i + 1]);
-    }
-    std::vector<E2> res(n);
-    instance_mle_batch_device(ctx, p, I, which, index, pt, res.data());
-    for (size_t i = 0; i < n; i++) { out[2 * i] = res[i].c0; out[2 * i + 1] = res[i].c1; }
-    return 0;
-    HG_CATCH(-1)
+    HG_ENTRY(instance_mle_entry<GlAbi>("hg_instance_mle_batch", true, ctx, instances, n, which, index, point, nvars, out))
 }
 
 int hg_verify_bn254(const hg_pk* pk, const hg_witness* w, const uint8_t* proof, size_t len) {
     HG_TRY
     if (!pk || !w || !proof) throw Error("hg_verify_bn254: null argument");
     check_witness(pk, w, "hg_verify_bn254");
-    std::string why = verify_proof_bn254(pk->params, pk->lasso, pk->circuit, w->w, proof, len);
-    if (why.empty()) return 0;
-    g_last_error = why;
-    return 1;
+    return decision(verify_proof_bn254(pk->params, pk->lasso, pk->circuit, w->w, proof, len));
     HG_CATCH(-1)
 }
 
@@ -1286,227 +1505,44 @@ int hg_verify_device_bn254(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, co
     HG_TRY
     if (!ctx || !pk || !w || !proof || !pk->ctx) throw Error("hg_verify_device_bn254: needs a device context and a device prover key");
     check_witness(pk, w, "hg_verify_device_bn254");
-    std::string why = hg::bn::verify_proof_device_bn254(ctx, pk, w->w, proof, len);
-    if (why.empty()) return 0;
-    g_last_error = why;
-    return 1;
+    return decision(hg::bn::verify_proof_device_bn254(ctx, pk, w->w, proof, len));
     HG_CATCH(-1)
 }
 
 int hg_verify_device_batch_bn254(hg_ctx* ctx, const hg_pk* pk, const hg_witness* const* ws, const uint8_t* const* proofs, const size_t* lens, size_t n,
                                  int* results, char* reasons, size_t reason_cap) {
-    HG_TRY
-    if (!ctx || !pk || (n && (!ws || !proofs || !lens || !results))) throw Error("hg_verify_device_batch_bn254: null argument");
-    if (!pk->ctx) throw Error("hg_verify_device_batch_bn254: needs a device prover key (hg_setup with a context)");
-    std::vector<const Witness*> W(n);
-    std::vector<const uint8_t*> P(n);
-    std::vector<size_t> N(n);
-    for (size_t i = 0; i < n; i++) {
-        if (!ws[i] || !proofs[i]) throw Error("hg_verify_device_batch_bn254: null witness or proof at index " + std::to_string(i));
-        check_witness(pk, ws[i], "hg_verify_device_batch_bn254");
-        W[i] = &ws[i]->w; P[i] = proofs[i]; N[i] = lens[i];
-    }
-    if (!n) return 0;
-    std::vector<std::string> why;
-    try {
-        hg::bn::verify_batch_device_bn254(ctx, pk, W, P, N, why);
-    } catch (const std::exception& e) {
-        const std::string m = e.what();
-        throw Error(m.rfind("hg_verify_device_batch_bn254", 0) == 0 ? m : "hg_verify_device_batch_bn254: " + m);
-    }
-    int rejected = 0;
-    for (size_t i = 0; i < n; i++) {
-        results[i] = why[i].empty() ? 0 : 1;
-        rejected += results[i];
-        if (reasons && reason_cap) {
-            char* r = reasons + i * reason_cap;
-            const size_t m = std::min(why[i].size(), reason_cap - 1);
-            memcpy(r, why[i].data(), m);
-            r[m] = 0;
-        }
-    }
-    return rejected;
-    HG_CATCH(-1)
+    HG_ENTRY(batch_entry<BnAbi, Witness>("hg_verify_device_batch_bn254", ctx, pk, reinterpret_cast<const void* const*>(ws), proofs, lens, n, 0, results, nullptr, 0, nullptr, 0, nullptr, reasons, reason_cap,
+                                       [&](auto& W, auto& P, auto& N, auto& why, auto&) { hg::bn::verify_batch_device_bn254(ctx, pk, W, P, N, why); }))
 }
 
 // ---- verification from the ciphertext over bn256::Fr (hg.h: hg_verify_public_bn254 and what goes with it) -------------------------
-static int verify_public_entry_bn254(const char* who, hg_ctx* ctx, bool device, const hg_pk* pk, const void* instance, const uint8_t* proof, size_t len,
-                                     void* claims, size_t claim_cap, uint64_t* points4, size_t coord_cap, size_t* n_claims) {
-    if (n_claims) *n_claims = 0;
-    if (device && (!ctx || !pk || !pk->ctx)) throw Error(std::string(who) + ": needs a device context and a device prover key");
-    if (!pk || !instance || !proof || !n_claims) throw Error(std::string(who) + ": null argument");
-    const hg_instance* in = as_instance(instance);
-    check_instance(pk, in, who);
-    size_t need_claims = 0, need_coords = 0;
-    claim_shape(pk->params, pk->lasso, pk->circuit, &need_claims, &need_coords);
-    if (claim_cap < need_claims || coord_cap < need_coords || (need_claims && !claims) || (need_coords && !points4))
-        throw Error(std::string(who) + ": room for " + std::to_string(need_claims) + " claims and " + std::to_string(need_coords) + " coordinates is needed (hg_pk_claim_shape)");
-    std::vector<OpenClaimBn> open;
-    const std::string why = device ? hg::bn::verify_public_device_bn254(ctx, pk, in->inst, proof, len, open)
-                                   : verify_public_bn254(pk->params, pk->lasso, pk->circuit, in->inst, proof, len, open);
-    if (!why.empty()) { g_last_error = why; return 1; }
-    size_t coords = 0;
-    for (const OpenClaimBn& c : open) coords += c.point4.size() / 4;
-    if (open.size() > claim_cap || coords > coord_cap) throw Error(std::string(who) + ": the walk left more claims than hg_pk_claim_shape counts");
-    hg_input_claim_bn254* out = static_cast<hg_input_claim_bn254*>(claims);
-    size_t off = 0;
-    for (size_t i = 0; i < open.size(); i++) {
-        out[i].input = (uint32_t)open[i].input;
-        out[i].nvars = (uint32_t)(open[i].point4.size() / 4);
-        out[i].point_off = off;
-        memcpy(out[i].value, open[i].value, 32);
-        if (!open[i].point4.empty()) memcpy(points4 + 4 * off, open[i].point4.data(), open[i].point4.size() * 8);
-        off += out[i].nvars;
-    }
-    *n_claims = open.size();
-    return 0;
-}
-
 int hg_verify_public_bn254(const hg_pk* pk, const void* instance, const uint8_t* proof, size_t len, void* claims, size_t claim_cap, uint64_t* points4,
                            size_t coord_cap, size_t* n_claims) {
-    HG_TRY
-    return verify_public_entry_bn254("hg_verify_public_bn254", nullptr, false, pk, instance, proof, len, claims, claim_cap, points4, coord_cap, n_claims);
-    HG_CATCH(-1)
+    HG_ENTRY(verify_public_entry<BnAbi>("hg_verify_public_bn254", nullptr, false, pk, instance, 0, proof, len, claims, claim_cap, points4, coord_cap, n_claims))
 }
 
 int hg_verify_public_device_bn254(hg_ctx* ctx, const hg_pk* pk, const void* instance, const uint8_t* proof, size_t len, void* claims, size_t claim_cap,
                                   uint64_t* points4, size_t coord_cap, size_t* n_claims) {
-    HG_TRY
-    return verify_public_entry_bn254("hg_verify_public_device_bn254", ctx, true, pk, instance, proof, len, claims, claim_cap, points4, coord_cap, n_claims);
-    HG_CATCH(-1)
+    HG_ENTRY(verify_public_entry<BnAbi>("hg_verify_public_device_bn254", ctx, true, pk, instance, 0, proof, len, claims, claim_cap, points4, coord_cap, n_claims))
 }
 
 int hg_verify_public_batch_bn254(hg_ctx* ctx, const hg_pk* pk, const void* const* instances, const uint8_t* const* proofs, const size_t* lens, size_t n,
                                  int* results, void* claims, size_t claim_cap_each, uint64_t* points4, size_t coord_cap_each, size_t* n_claims, char* reasons,
                                  size_t reason_cap) {
-    HG_TRY
-    const std::string who = "hg_verify_public_batch_bn254";
-    if (!ctx || !pk || !pk->ctx) throw Error(who + ": needs a device context and a device prover key");
-    if (n && (!instances || !proofs || !lens || !results || !n_claims)) throw Error(who + ": null argument");
-    size_t need_claims = 0, need_coords = 0;
-    claim_shape(pk->params, pk->lasso, pk->circuit, &need_claims, &need_coords);
-    if (n && (claim_cap_each < need_claims || coord_cap_each < need_coords || (need_claims && !claims) || (need_coords && !points4)))
-        throw Error(who + ": room for " + std::to_string(need_claims) + " claims and " + std::to_string(need_coords) + " coordinates per proof is needed (hg_pk_claim_shape)");
-    std::vector<const Instance*> I(n);
-    std::vector<const uint8_t*> P(n);
-    std::vector<size_t> N(n);
-    for (size_t i = 0; i < n; i++) {
-        if (!instances[i] || !proofs[i]) throw Error(who + ": null instance or proof at index " + std::to_string(i));
-        check_instance(pk, as_instance(instances[i]), (who + ": index " + std::to_string(i)).c_str());
-        I[i] = &as_instance(instances[i])->inst; P[i] = proofs[i]; N[i] = lens[i];
-    }
-    if (!n) return 0;
-    std::vector<std::string> why;
-    std::vector<std::vector<OpenClaimBn>> open;
-    try {
-        hg::bn::verify_public_batch_device_bn254(ctx, pk, I, P, N, why, open);
-    } catch (const std::exception& e) {
-        const std::string m = e.what();
-        throw Error(m.rfind(who, 0) == 0 ? m : who + ": " + m);
-    }
-    for (size_t i = 0; i < n; i++) {   // (checked before anything is written: an error of the call leaves the outputs alone)
-        size_t coords = 0;
-        for (const OpenClaimBn& c : open[i]) coords += c.point4.size() / 4;
-        if (open[i].size() > claim_cap_each || coords > coord_cap_each) throw Error(who + ": proof " + std::to_string(i) + ": the walk left more claims than hg_pk_claim_shape counts");
-    }
-    int rejected = 0;
-    for (size_t i = 0; i < n; i++) {
-        results[i] = why[i].empty() ? 0 : 1;
-        rejected += results[i];
-        if (reasons && reason_cap) {
-            char* r = reasons + i * reason_cap;
-            const size_t m = std::min(why[i].size(), reason_cap - 1);
-            memcpy(r, why[i].data(), m);
-            r[m] = 0;
-        }
-        n_claims[i] = results[i] ? 0 : open[i].size();
-        if (results[i]) continue;
-        hg_input_claim_bn254* out = static_cast<hg_input_claim_bn254*>(claims) + i * claim_cap_each;
-        uint64_t* pts = points4 + 4 * i * coord_cap_each;
-        size_t off = 0;
-        for (size_t j = 0; j < open[i].size(); j++) {
-            const OpenClaimBn& c = open[i][j];
-            out[j].input = (uint32_t)c.input;
-            out[j].nvars = (uint32_t)(c.point4.size() / 4);
-            out[j].point_off = off;
-            memcpy(out[j].value, c.value, 32);
-            if (!c.point4.empty()) memcpy(pts + 4 * off, c.point4.data(), c.point4.size() * 8);
-            off += out[j].nvars;
-        }
-    }
-    return rejected;
-    HG_CATCH(-1)
+    HG_ENTRY(batch_entry<BnAbi, Instance>("hg_verify_public_batch_bn254", ctx, pk, instances, proofs, lens, n, 0, results, claims, claim_cap_each, points4, coord_cap_each, n_claims,
+                                        reasons, reason_cap, [&](auto& I, auto& P, auto& N, auto& why, auto& open) { hg::bn::verify_public_batch_device_bn254(ctx, pk, I, P, N, why, open); }))
 }
 
 int hg_claims_settle_bn254(hg_ctx* ctx, const hg_params* params, const hg_witness* w, const void* claims, size_t n, const uint64_t* points4) {
-    HG_TRY
-    if (!params || !w || (n && (!claims || !points4))) throw Error("hg_claims_settle_bn254: null argument");
-    Params p(*params);
-    const size_t SZ = p.SZ(), k = (size_t)p.k;
-    const Witness& v = w->w;
-    if (w->params.n != params->n || w->params.k != params->k || v.s.size() != SZ || v.e.size() != SZ || v.k1.size() != SZ || v.ais.size() != k * SZ ||
-        v.r1is.size() != k * SZ || v.r2is.size() != k * p.PZ())
-        throw Error("hg_claims_settle_bn254: the witness was built for other parameters");
-    const hg_input_claim_bn254* in = static_cast<const hg_input_claim_bn254*>(claims);
-    std::vector<OpenClaimBn> cl(n);
-    for (size_t i = 0; i < n; i++) {
-        if (in[i].input > 3 + 2 * k) throw Error("hg_claims_settle_bn254: input " + std::to_string(in[i].input) + " is not an input of the circuit");
-        if (in[i].nvars > 40) throw Error("hg_claims_settle_bn254: a claim with " + std::to_string(in[i].nvars) + " coordinates");
-        cl[i].input = in[i].input;
-        memcpy(cl[i].value, in[i].value, 32);
-        cl[i].point4.assign(points4 + 4 * in[i].point_off, points4 + 4 * (in[i].point_off + in[i].nvars));
-        for (size_t j = 0; j < in[i].nvars; j++) if (!bn254_canonical(&cl[i].point4[4 * j])) throw Error("hg_claims_settle_bn254: non-canonical coordinate");
-        if (!bn254_canonical(cl[i].value)) throw Error("hg_claims_settle_bn254: non-canonical value");
-    }
-    const std::string why = ctx ? hg::bn::claims_settle_device_bn254(ctx, p, v, cl) : claims_settle_bn254(p, v, cl);
-    if (why.empty()) return 0;
-    g_last_error = why;
-    return 1;
-    HG_CATCH(-1)
+    HG_ENTRY(claims_settle_entry<BnAbi>("hg_claims_settle_bn254", ctx, params, w, claims, n, points4))
 }
 
 int hg_instance_mle_bn254(hg_ctx* ctx, const void* instance, int which, int index, const uint64_t* point4, size_t nvars, uint64_t out4[4]) {
-    HG_TRY
-    if (!instance || (nvars && !point4) || !out4) throw Error("hg_instance_mle_bn254: null argument");
-    const hg_instance* in = as_instance(instance);
-    Params p(in->params);
-    if (which != 0 && which != 1) throw Error("hg_instance_mle_bn254: which is 0 (ais[index]) or 1 (ct0is)");
-    if (which == 0 && (index < 0 || index >= p.k)) throw Error("hg_instance_mle_bn254: no such modulus");
-    if (nvars != (size_t)(which ? p.ct0is_log2() : p.L)) throw Error("hg_instance_mle_bn254: the table has " + std::to_string(which ? p.ct0is_log2() : p.L) + " variables");
-    for (size_t i = 0; i < nvars; i++)
-        if (!bn254_canonical(point4 + 4 * i)) throw Error("hg_instance_mle_bn254: non-canonical coordinate");
-    if (ctx) hg::bn::instance_mle_device_bn254(ctx, p, in->inst, which, index, point4, nvars, out4);
-    else instance_mle_bn254(p, in->inst, which, index, point4, nvars, out4);
-    return 0;
-    HG_CATCH(-1)
+    HG_ENTRY(instance_mle_entry<BnAbi>("hg_instance_mle_bn254", false, ctx, &instance, 1, which, index, point4, nvars, out4))
 }
 
 int hg_instance_mle_batch_bn254(hg_ctx* ctx, const void* const* instances, size_t n, int which, int index, const uint64_t* point4, size_t nvars, uint64_t* out4) {
-    HG_TRY
-    if (!ctx) throw Error("hg_instance_mle_batch_bn254: needs a device context");
-    if (!instances || (nvars && !point4) || !out4) throw Error("hg_instance_mle_batch_bn254: null argument");
-    if (!n) return 0;
-    std::vector<const Instance*> I(n);
-    for (size_t i = 0; i < n; i++) {
-        if (!instances[i]) throw Error("hg_instance_mle_batch_bn254: null instance at index " + std::to_string(i));
-        const hg_params &a = as_instance(instances[0])->params, &b = as_instance(instances[i])->params;
-        if (a.n != b.n || a.k != b.k || memcmp(a.qis, b.qis, sizeof(a.qis[0]) * a.k) != 0)
-            throw Error("hg_instance_mle_batch_bn254: the instance at index " + std::to_string(i) + " was built for other parameters than the first");
-        I[i] = &as_instance(instances[i])->inst;
-    }
-    Params p(as_instance(instances[0])->params);
-    if (which != 0 && which != 1) throw Error("hg_instance_mle_batch_bn254: which is 0 (ais[index]) or 1 (ct0is)");
-    if (which == 0 && (index < 0 || index >= p.k)) throw Error("hg_instance_mle_batch_bn254: no such modulus");
-    if (nvars != (size_t)(which ? p.ct0is_log2() : p.L)) throw Error("hg_instance_mle_batch_bn254: the table has " + std::to_string(which ? p.ct0is_log2() : p.L) + " variables");
-    for (const Instance* x : I)
-        if (x->a.size() != (size_t)p.k * p.PZ() || x->ct0.size() != (size_t)p.k * p.PZ()) throw Error("hg_instance_mle_batch_bn254: an instance of the wrong size");
-    for (size_t i = 0; i < nvars; i++)
-        if (!bn254_canonical(point4 + 4 * i)) throw Error("hg_instance_mle_batch_bn254: non-canonical coordinate");
-    std::vector<u64> res(4 * n);   // (an error of the device pass leaves out4 alone)
-    hg::bn::instance_mle_batch_device_bn254(ctx, p, I, which, index, point4, nvars, res.data());
-    memcpy(out4, res.data(), res.size() * sizeof(u64));
-    return 0;
-    HG_CATCH(-1)
+    HG_ENTRY(instance_mle_entry<BnAbi>("hg_instance_mle_batch_bn254", true, ctx, instances, n, which, index, point4, nvars, out4))
 }
 
 int hg_circuit_eval(const hg_pk* pk, const hg_witness* w, uint64_t* lasso_in, size_t lasso_cap, uint64_t* sum_out, size_t sum_cap) {
@@ -1744,61 +1780,7 @@ int hg_ntt_bn254(hg_ctx* ctx, const uint64_t* in4, size_t log2n, int inverse, si
     HG_CATCH(-1)
 }
 
-// ---- polynomial commitment (pcs.hpp): hg_pcs_* on caller tables, hg_secrets_commit / hg_claims_open / hg_claims_verify for the
-// five secret inputs of an encryption
-static std::vector<pcs::Claim> pcs_claims(const char* who, const pcs::Shape& sh, const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n) {
-    const std::string w(who);
-    if (n > pcs::MAX_CLAIMS) throw Error(w + ": more than " + std::to_string(pcs::MAX_CLAIMS) + " claims");
-    std::vector<pcs::Claim> cl(n);
-    size_t at = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (table[i] >= sh.nvars.size()) throw Error(w + ": claim " + std::to_string(i) + " names table " + std::to_string(table[i]) + " of " + std::to_string(sh.nvars.size()));
-        cl[i].table = table[i];
-        cl[i].point.resize((size_t)sh.nvars[table[i]]);
-        for (E2& x : cl[i].point) { x = e2(points[2 * at], points[2 * at + 1]); at++; }
-        cl[i].value = e2(values[2 * i], values[2 * i + 1]);
-        for (const E2& x : cl[i].point) if (x.c0 >= GL_P || x.c1 >= GL_P) throw Error(w + ": claim " + std::to_string(i) + ": non-canonical coordinate");
-        if (cl[i].value.c0 >= GL_P || cl[i].value.c1 >= GL_P) throw Error(w + ": claim " + std::to_string(i) + ": non-canonical value");
-    }
-    return cl;
-}
-static size_t pcs_queries(const char* who, size_t n_queries) {
-    if (n_queries > pcs::MAX_QUERIES) throw Error(std::string(who) + ": more than " + std::to_string(pcs::MAX_QUERIES) + " queries");
-    return n_queries ? n_queries : pcs::DEFAULT_QUERIES;
-}
-static void pcs_emit(const char* who, const std::vector<uint8_t>& bytes, uint8_t* out, size_t cap, size_t* len) {
-    *len = bytes.size();
-    if (bytes.size() > cap) throw Error(std::string(who) + ": the opening has " + std::to_string(bytes.size()) + " bytes, the buffer " + std::to_string(cap));
-    memcpy(out, bytes.data(), bytes.size());
-}
-// the secret inputs as commitment tables, in input order s, e, k1, r1is[0..k-1], r2is
-static std::vector<uint32_t> secrets_nvars(const Params& p) {
-    std::vector<uint32_t> v(3 + (size_t)p.k, (uint32_t)p.L);
-    v.push_back((uint32_t)(p.n_log2 + p.log2k));
-    return v;
-}
-// hg_input_claim array -> (table, points, values) of the commitment over the secret inputs
-static void secrets_claims(const char* who, const Params& p, const void* claims, size_t n, const uint64_t* points, std::vector<uint32_t>& table,
-                           std::vector<uint64_t>& pts, std::vector<uint64_t>& vals) {
-    const std::string w(who);
-    if (n > pcs::MAX_CLAIMS) throw Error(w + ": more than " + std::to_string(pcs::MAX_CLAIMS) + " claims");
-    const hg_input_claim* in = static_cast<const hg_input_claim*>(claims);
-    const std::vector<uint32_t> nv = secrets_nvars(p);
-    const uint32_t k = (uint32_t)p.k;
-    for (size_t i = 0; i < n; i++) {
-        const uint32_t id = in[i].input;
-        uint32_t t;
-        if (id < 3) t = id;
-        else if (id >= 3 + k && id < 3 + 2 * k) t = id - k;
-        else if (id == 3 + 2 * k) t = 3 + k;
-        else throw Error(w + ": claim " + std::to_string(i) + " is on input " + std::to_string(id) + ", which is not a secret input (0, 1, 2, " + std::to_string(3 + k) + " .. " + std::to_string(3 + 2 * k) + ")");
-        if (in[i].nvars != nv[t]) throw Error(w + ": claim " + std::to_string(i) + " has " + std::to_string(in[i].nvars) + " coordinates, input " + std::to_string(id) + " has " + std::to_string(nv[t]) + " variables");
-        table.push_back(t);
-        for (size_t j = 0; j < in[i].nvars; j++) { pts.push_back(points[2 * (in[i].point_off + j)]); pts.push_back(points[2 * (in[i].point_off + j) + 1]); }
-        vals.push_back(in[i].value[0]); vals.push_back(in[i].value[1]);
-    }
-}
-
+// ---- polynomial commitment: the entries (their bodies: pcs_open_entry .. claims_verify_entry of the shared layer)
 int hg_pcs_commit(hg_ctx* ctx, const uint64_t* const* tables, const uint32_t* nvars, size_t n_tables, size_t log2_row, void** commitment, uint8_t root[32]) {
     HG_TRY
     if (commitment) *commitment = nullptr;
@@ -1814,172 +1796,41 @@ int hg_pcs_commit(hg_ctx* ctx, const uint64_t* const* tables, const uint32_t* nv
 
 void hg_pcs_free(void* commitment) { delete static_cast<pcs::Commitment*>(commitment); }
 
-static int pcs_open_entry(const char* who, hg_ctx* ctx, const pcs::Commitment* cm, const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n_claims,
-                          size_t n_queries, uint8_t* proof, size_t cap, size_t* len) {
-    if (cm->field != pcs::GOLDILOCKS) throw Error(std::string(who) + ": the commitment is over BN254: open it with the _bn254 entry");
-    if (cm->ctx != ctx) throw Error(std::string(who) + ": the commitment was made " + (cm->ctx ? "on a device context: pass that context" : "by the host form: pass no context"));
-    const std::vector<pcs::Claim> cl = pcs_claims(who, cm->sh, table, points, values, n_claims);
-    pcs_emit(who, pcs::open(who, *cm, cl, pcs_queries(who, n_queries)), proof, cap, len);
-    return 0;
-}
-
 int hg_pcs_open(hg_ctx* ctx, const void* commitment, const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n_claims, size_t n_queries,
                 uint8_t* proof, size_t cap, size_t* len) {
-    HG_TRY
-    if (len) *len = 0;
-    if (!commitment || !proof || !len || (n_claims && (!table || !points || !values))) throw Error("hg_pcs_open: null argument");
-    return pcs_open_entry("hg_pcs_open", ctx, static_cast<const pcs::Commitment*>(commitment), table, points, values, n_claims, n_queries, proof, cap, len);
-    HG_CATCH(-1)
-}
-
-// hg_pcs_verify (device == false) and hg_pcs_verify_device: the same argument checks in the same order, then the form's verifier
-static int pcs_verify_entry(const char* who, bool device, hg_ctx* ctx, const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row,
-                            const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
-    const std::string w(who);
-    if (!root || !nvars || (len && !proof) || (n_claims && (!table || !points || !values))) throw Error(w + ": null argument");
-    const pcs::Shape sh = pcs::make_shape(who, nvars, n_tables, log2_row);
-    const std::vector<pcs::Claim> cl = pcs_claims(who, sh, table, points, values, n_claims);
-    const size_t Q = pcs_queries(who, n_queries);
-    if (device && !ctx) throw Error(w + ": no context");
-    std::string why;
-    if (device) {
-        try {
-            why = pcs::verify_device(ctx, sh, root, cl, Q, proof, len);
-        } catch (const std::exception& e) {
-            throw Error(w + ": " + e.what());
-        }
-    } else {
-        why = pcs::verify(sh, root, cl, Q, proof, len);
-    }
-    if (why.empty()) return 0;
-    g_last_error = why;
-    return 1;
+    HG_ENTRY(pcs_open_api<GlAbi>("hg_pcs_open", ctx, commitment, table, points, values, n_claims, n_queries, proof, cap, len))
 }
 
 int hg_pcs_verify(const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table, const uint64_t* points,
                   const uint64_t* values, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
-    HG_TRY
-    return pcs_verify_entry("hg_pcs_verify", false, nullptr, root, nvars, n_tables, log2_row, table, points, values, n_claims, n_queries, proof, len);
-    HG_CATCH(-1)
+    HG_ENTRY(pcs_verify_entry<GlAbi>("hg_pcs_verify", false, nullptr, root, nvars, n_tables, log2_row, table, points, values, n_claims, n_queries, proof, len))
 }
 
-int hg_pcs_verify_device(hg_ctx* ctx, const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table,
-                         const uint64_t* points, const uint64_t* values, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
-    HG_TRY
-    return pcs_verify_entry("hg_pcs_verify_device", true, ctx, root, nvars, n_tables, log2_row, table, points, values, n_claims, n_queries, proof, len);
-    HG_CATCH(-1)
+int hg_pcs_verify_device(hg_ctx* ctx, const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table, const uint64_t* points,
+                         const uint64_t* values, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
+    HG_ENTRY(pcs_verify_entry<GlAbi>("hg_pcs_verify_device", true, ctx, root, nvars, n_tables, log2_row, table, points, values, n_claims, n_queries, proof, len))
 }
 
 int hg_secrets_commit(hg_ctx* ctx, const hg_params* params, const hg_witness* w, size_t log2_row, void** commitment, uint8_t root[32]) {
-    HG_TRY
-    if (commitment) *commitment = nullptr;
-    if (!params || !w || !commitment || !root) throw Error("hg_secrets_commit: null argument");
-    Params p(*params);
-    const size_t SZ = p.SZ(), k = (size_t)p.k;
-    const Witness& v = w->w;
-    if (w->params.n != params->n || w->params.k != params->k || v.s.size() != SZ || v.e.size() != SZ || v.k1.size() != SZ || v.r1is.size() != k * SZ ||
-        v.r2is.size() != k * p.PZ())
-        throw Error("hg_secrets_commit: the witness was built for other parameters");
-    const std::vector<uint32_t> nv = secrets_nvars(p);
-    std::vector<const uint64_t*> tabs = {v.s.data(), v.e.data(), v.k1.data()};
-    for (size_t i = 0; i < k; i++) tabs.push_back(v.r1is.data() + i * SZ);
-    tabs.push_back(v.r2is.data());
-    const pcs::Shape sh = pcs::make_shape("hg_secrets_commit", nv.data(), nv.size(), log2_row);
-    pcs::Commitment* cm;
-    try {
-        cm = ctx ? pcs::commit_device(ctx, sh, tabs.data()) : pcs::commit_host(sh, tabs.data());
-    } catch (const std::exception& e) {
-        throw Error(std::string("hg_secrets_commit: ") + e.what());
-    }
-    memcpy(root, cm->root(), 32);
-    *commitment = cm;
-    return 0;
-    HG_CATCH(-1)
+    HG_ENTRY(secrets_commit_entry<GlAbi>("hg_secrets_commit", ctx, params, w, log2_row, commitment, root))
 }
 
 int hg_claims_open(hg_ctx* ctx, const hg_params* params, const void* commitment, const void* claims, size_t n, const uint64_t* points, size_t n_queries,
                    uint8_t* opening, size_t cap, size_t* len) {
-    HG_TRY
-    if (len) *len = 0;
-    if (!params || !commitment || !opening || !len || (n && (!claims || !points))) throw Error("hg_claims_open: null argument");
-    Params p(*params);
-    const pcs::Commitment* cm = static_cast<const pcs::Commitment*>(commitment);
-    if (cm->field != pcs::GOLDILOCKS) throw Error("hg_claims_open: the commitment is over BN254: open it with the _bn254 entry");
-    const std::vector<uint32_t> nv = secrets_nvars(p);
-    if (cm->sh.nvars.size() != nv.size() || !std::equal(nv.begin(), nv.end(), cm->sh.nvars.begin(), [](uint32_t a, int b) { return (int)a == b; }))
-        throw Error("hg_claims_open: the commitment is not hg_secrets_commit's for these parameters");
-    std::vector<uint32_t> table;
-    std::vector<uint64_t> pts, vals;
-    secrets_claims("hg_claims_open", p, claims, n, points, table, pts, vals);
-    return pcs_open_entry("hg_claims_open", ctx, cm, table.data(), pts.data(), vals.data(), n, n_queries, opening, cap, len);
-    HG_CATCH(-1)
+    HG_ENTRY(claims_open_entry<GlAbi>("hg_claims_open", "hg_secrets_commit", ctx, params, commitment, claims, n, points, n_queries, opening, cap, len))
 }
 
-static int claims_verify_entry(const char* who, bool device, hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n,
-                               const uint64_t* points, size_t n_queries, const uint8_t* opening, size_t len) {
-    if (!params || !root || (len && !opening) || (n && (!claims || !points))) throw Error(std::string(who) + ": null argument");
-    Params p(*params);
-    const std::vector<uint32_t> nv = secrets_nvars(p);
-    std::vector<uint32_t> table;
-    std::vector<uint64_t> pts, vals;
-    (void)pcs::make_shape(who, nv.data(), nv.size(), log2_row);   // a shape error is reported ahead of a claim's
-    secrets_claims(who, p, claims, n, points, table, pts, vals);
-    return pcs_verify_entry(who, device, ctx, root, nv.data(), nv.size(), log2_row, table.data(), pts.data(), vals.data(), n, n_queries, opening, len);
-}
-
-int hg_claims_verify(const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points, size_t n_queries,
-                     const uint8_t* opening, size_t len) {
-    HG_TRY
-    return claims_verify_entry("hg_claims_verify", false, nullptr, params, root, log2_row, claims, n, points, n_queries, opening, len);
-    HG_CATCH(-1)
+int hg_claims_verify(const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points,
+                     size_t n_queries, const uint8_t* opening, size_t len) {
+    HG_ENTRY(claims_verify_entry<GlAbi>("hg_claims_verify", false, nullptr, params, root, log2_row, claims, n, points, n_queries, opening, len))
 }
 
 int hg_claims_verify_device(hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points,
                             size_t n_queries, const uint8_t* opening, size_t len) {
-    HG_TRY
-    return claims_verify_entry("hg_claims_verify_device", true, ctx, params, root, log2_row, claims, n, points, n_queries, opening, len);
-    HG_CATCH(-1)
+    HG_ENTRY(claims_verify_entry<GlAbi>("hg_claims_verify_device", true, ctx, params, root, log2_row, claims, n, points, n_queries, opening, len))
 }
 
-// ---- the same layer over bn256::Fr (pcs_bn254.hpp): an element crosses as 4 canonical words
-static std::vector<bn::PcsClaim> pcs_claims_bn254(const char* who, const pcs::Shape& sh, const uint32_t* table, const uint64_t* points4, const uint64_t* values4, size_t n) {
-    const std::string w(who);
-    if (n > pcs::MAX_CLAIMS) throw Error(w + ": more than " + std::to_string(pcs::MAX_CLAIMS) + " claims");
-    std::vector<bn::PcsClaim> cl(n);
-    size_t at = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (table[i] >= sh.nvars.size()) throw Error(w + ": claim " + std::to_string(i) + " names table " + std::to_string(table[i]) + " of " + std::to_string(sh.nvars.size()));
-        cl[i].table = table[i];
-        cl[i].point.resize((size_t)sh.nvars[table[i]]);
-        for (bn::Fr& x : cl[i].point) { memcpy(x.l, points4 + 4 * at, 32); at++; }
-        memcpy(cl[i].value.l, values4 + 4 * i, 32);
-        for (const bn::Fr& x : cl[i].point) if (bn::fr_geq_p(x)) throw Error(w + ": claim " + std::to_string(i) + ": non-canonical coordinate");
-        if (bn::fr_geq_p(cl[i].value)) throw Error(w + ": claim " + std::to_string(i) + ": non-canonical value");
-    }
-    return cl;
-}
-// hg_input_claim_bn254 array -> (table, points, values) of the commitment over the secret inputs: the mapping of secrets_claims
-static void secrets_claims_bn254(const char* who, const Params& p, const void* claims, size_t n, const uint64_t* points4, std::vector<uint32_t>& table,
-                                 std::vector<uint64_t>& pts, std::vector<uint64_t>& vals) {
-    const std::string w(who);
-    if (n > pcs::MAX_CLAIMS) throw Error(w + ": more than " + std::to_string(pcs::MAX_CLAIMS) + " claims");
-    const hg_input_claim_bn254* in = static_cast<const hg_input_claim_bn254*>(claims);
-    const std::vector<uint32_t> nv = secrets_nvars(p);
-    const uint32_t k = (uint32_t)p.k;
-    for (size_t i = 0; i < n; i++) {
-        const uint32_t id = in[i].input;
-        uint32_t t;
-        if (id < 3) t = id;
-        else if (id >= 3 + k && id < 3 + 2 * k) t = id - k;
-        else if (id == 3 + 2 * k) t = 3 + k;
-        else throw Error(w + ": claim " + std::to_string(i) + " is on input " + std::to_string(id) + ", which is not a secret input (0, 1, 2, " + std::to_string(3 + k) + " .. " + std::to_string(3 + 2 * k) + ")");
-        if (in[i].nvars != nv[t]) throw Error(w + ": claim " + std::to_string(i) + " has " + std::to_string(in[i].nvars) + " coordinates, input " + std::to_string(id) + " has " + std::to_string(nv[t]) + " variables");
-        table.push_back(t);
-        pts.insert(pts.end(), points4 + 4 * in[i].point_off, points4 + 4 * (in[i].point_off + in[i].nvars));
-        vals.insert(vals.end(), in[i].value, in[i].value + 4);
-    }
-}
-
+// ---- the same entries over bn256::Fr (pcs_bn254.hpp): an element crosses as 4 canonical words
 int hg_pcs_commit_bn254(hg_ctx* ctx, const uint64_t* const* tables4, const uint32_t* nvars, size_t n_tables, size_t log2_row, void** commitment, uint8_t root[32]) {
     HG_TRY
     if (commitment) *commitment = nullptr;
@@ -1993,98 +1844,28 @@ int hg_pcs_commit_bn254(hg_ctx* ctx, const uint64_t* const* tables4, const uint3
     HG_CATCH(-1)
 }
 
-static int pcs_open_entry_bn254(const char* who, hg_ctx* ctx, const pcs::Commitment* cm, const uint32_t* table, const uint64_t* points4, const uint64_t* values4,
-                                size_t n_claims, size_t n_queries, uint8_t* proof, size_t cap, size_t* len) {
-    if (cm->ctx != ctx) throw Error(std::string(who) + ": the commitment was made " + (cm->ctx ? "on a device context: pass that context" : "by the host form: pass no context"));
-    const std::vector<bn::PcsClaim> cl = pcs_claims_bn254(who, cm->sh, table, points4, values4, n_claims);
-    pcs_emit(who, bn::pcs_open(who, *cm, cl, pcs_queries(who, n_queries)), proof, cap, len);
-    return 0;
-}
-
 int hg_pcs_open_bn254(hg_ctx* ctx, const void* commitment, const uint32_t* table, const uint64_t* points4, const uint64_t* values4, size_t n_claims, size_t n_queries,
                       uint8_t* proof, size_t cap, size_t* len) {
-    HG_TRY
-    if (len) *len = 0;
-    if (!commitment || !proof || !len || (n_claims && (!table || !points4 || !values4))) throw Error("hg_pcs_open_bn254: null argument");
-    const pcs::Commitment* cm = static_cast<const pcs::Commitment*>(commitment);
-    if (cm->field != pcs::BN254) throw Error("hg_pcs_open_bn254: the commitment is over Goldilocks: open it with hg_pcs_open");
-    return pcs_open_entry_bn254("hg_pcs_open_bn254", ctx, cm, table, points4, values4, n_claims, n_queries, proof, cap, len);
-    HG_CATCH(-1)
-}
-
-static int pcs_verify_entry_bn254(const char* who, const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table,
-                                  const uint64_t* points4, const uint64_t* values4, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
-    const std::string w(who);
-    if (!root || !nvars || (len && !proof) || (n_claims && (!table || !points4 || !values4))) throw Error(w + ": null argument");
-    const pcs::Shape sh = pcs::make_shape(who, nvars, n_tables, log2_row);
-    const std::vector<bn::PcsClaim> cl = pcs_claims_bn254(who, sh, table, points4, values4, n_claims);
-    const std::string why = bn::pcs_verify(sh, root, cl, pcs_queries(who, n_queries), proof, len);
-    if (why.empty()) return 0;
-    g_last_error = why;
-    return 1;
+    HG_ENTRY(pcs_open_api<BnAbi>("hg_pcs_open_bn254", ctx, commitment, table, points4, values4, n_claims, n_queries, proof, cap, len))
 }
 
 int hg_pcs_verify_bn254(const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table, const uint64_t* points4,
                         const uint64_t* values4, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
-    HG_TRY
-    return pcs_verify_entry_bn254("hg_pcs_verify_bn254", root, nvars, n_tables, log2_row, table, points4, values4, n_claims, n_queries, proof, len);
-    HG_CATCH(-1)
+    HG_ENTRY(pcs_verify_entry<BnAbi>("hg_pcs_verify_bn254", false, nullptr, root, nvars, n_tables, log2_row, table, points4, values4, n_claims, n_queries, proof, len))
 }
 
 int hg_secrets_commit_bn254(hg_ctx* ctx, const hg_params* params, const hg_witness* w, size_t log2_row, void** commitment, uint8_t root[32]) {
-    HG_TRY
-    if (commitment) *commitment = nullptr;
-    if (!params || !w || !commitment || !root) throw Error("hg_secrets_commit_bn254: null argument");
-    Params p(*params);
-    const size_t SZ = p.SZ(), k = (size_t)p.k;
-    const Witness& v = w->w;
-    if (w->params.n != params->n || w->params.k != params->k || v.s.size() != SZ || v.e.size() != SZ || v.k1.size() != SZ || v.r1is.size() != k * SZ ||
-        v.r2is.size() != k * p.PZ())
-        throw Error("hg_secrets_commit_bn254: the witness was built for other parameters");
-    const std::vector<uint32_t> nv = secrets_nvars(p);
-    std::vector<const uint64_t*> tabs = {v.s.data(), v.e.data(), v.k1.data()};
-    for (size_t i = 0; i < k; i++) tabs.push_back(v.r1is.data() + i * SZ);
-    tabs.push_back(v.r2is.data());
-    const pcs::Shape sh = pcs::make_shape("hg_secrets_commit_bn254", nv.data(), nv.size(), log2_row);
-    // the witness words are lifted into Fr by the signed rule (the table hg_claims_settle_bn254 evaluates)
-    pcs::Commitment* cm = ctx ? bn::pcs_commit_device("hg_secrets_commit_bn254", ctx, sh, tabs.data(), true) : bn::pcs_commit_host("hg_secrets_commit_bn254", sh, tabs.data(), true);
-    memcpy(root, cm->root(), 32);
-    *commitment = cm;
-    return 0;
-    HG_CATCH(-1)
+    HG_ENTRY(secrets_commit_entry<BnAbi>("hg_secrets_commit_bn254", ctx, params, w, log2_row, commitment, root))
 }
 
 int hg_claims_open_bn254(hg_ctx* ctx, const hg_params* params, const void* commitment, const void* claims, size_t n, const uint64_t* points4, size_t n_queries,
                          uint8_t* opening, size_t cap, size_t* len) {
-    HG_TRY
-    if (len) *len = 0;
-    if (!params || !commitment || !opening || !len || (n && (!claims || !points4))) throw Error("hg_claims_open_bn254: null argument");
-    Params p(*params);
-    const pcs::Commitment* cm = static_cast<const pcs::Commitment*>(commitment);
-    if (cm->field != pcs::BN254) throw Error("hg_claims_open_bn254: the commitment is over Goldilocks: open it with hg_claims_open");
-    const std::vector<uint32_t> nv = secrets_nvars(p);
-    if (cm->sh.nvars.size() != nv.size() || !std::equal(nv.begin(), nv.end(), cm->sh.nvars.begin(), [](uint32_t a, int b) { return (int)a == b; }))
-        throw Error("hg_claims_open_bn254: the commitment is not hg_secrets_commit_bn254's for these parameters");
-    std::vector<uint32_t> table;
-    std::vector<uint64_t> pts, vals;
-    secrets_claims_bn254("hg_claims_open_bn254", p, claims, n, points4, table, pts, vals);
-    return pcs_open_entry_bn254("hg_claims_open_bn254", ctx, cm, table.data(), pts.data(), vals.data(), n, n_queries, opening, cap, len);
-    HG_CATCH(-1)
+    HG_ENTRY(claims_open_entry<BnAbi>("hg_claims_open_bn254", "hg_secrets_commit_bn254", ctx, params, commitment, claims, n, points4, n_queries, opening, cap, len))
 }
 
-int hg_claims_verify_bn254(const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points4, size_t n_queries,
-                           const uint8_t* opening, size_t len) {
-    HG_TRY
-    const char* who = "hg_claims_verify_bn254";
-    if (!params || !root || (len && !opening) || (n && (!claims || !points4))) throw Error(std::string(who) + ": null argument");
-    Params p(*params);
-    const std::vector<uint32_t> nv = secrets_nvars(p);
-    std::vector<uint32_t> table;
-    std::vector<uint64_t> pts, vals;
-    (void)pcs::make_shape(who, nv.data(), nv.size(), log2_row);   // a shape error is reported ahead of a claim's
-    secrets_claims_bn254(who, p, claims, n, points4, table, pts, vals);
-    return pcs_verify_entry_bn254(who, root, nv.data(), nv.size(), log2_row, table.data(), pts.data(), vals.data(), n, n_queries, opening, len);
-    HG_CATCH(-1)
+int hg_claims_verify_bn254(const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points4,
+                           size_t n_queries, const uint8_t* opening, size_t len) {
+    HG_ENTRY(claims_verify_entry<BnAbi>("hg_claims_verify_bn254", false, nullptr, params, root, log2_row, claims, n, points4, n_queries, opening, len))
 }
 
 int hg_profile(hg_ctx* ctx, int level) {
