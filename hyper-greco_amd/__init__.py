@@ -56,6 +56,7 @@ EXPORTS = [
     "hg_pcs_commit", "hg_pcs_free", "hg_pcs_open", "hg_pcs_verify", "hg_secrets_commit", "hg_claims_open", "hg_claims_verify",
     "hg_pcs_verify_device", "hg_claims_verify_device",
     "hg_pcs_commit_bn254", "hg_pcs_open_bn254", "hg_pcs_verify_bn254", "hg_secrets_commit_bn254", "hg_claims_open_bn254", "hg_claims_verify_bn254",
+    "hg_pcs_verify_device_bn254", "hg_claims_verify_device_bn254",
     "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_mle_eval",
     "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_verify_public_bn254", "hg_verify_public_device_bn254", "hg_verify_public_batch_bn254", "hg_claims_settle_bn254", "hg_instance_mle_bn254", "hg_instance_mle_batch_bn254", "hg_prove_encryptions_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
 ]
@@ -99,9 +100,9 @@ def _two_field_protos(L):
         getattr(L, "hg_secrets_commit" + sfx).argtypes = [vp, C.POINTER(HgParams), vp, sz, C.POINTER(vp), u8p]
         getattr(L, "hg_claims_open" + sfx).argtypes = [vp, C.POINTER(HgParams), vp, vp, sz, u64p, sz, u8p, sz, szp]
         getattr(L, "hg_claims_verify" + sfx).argtypes = [C.POINTER(HgParams), cp, sz, vp, sz, u64p, sz, cp, sz]
+        getattr(L, "hg_pcs_verify_device" + sfx).argtypes = [vp] + getattr(L, "hg_pcs_verify" + sfx).argtypes
+        getattr(L, "hg_claims_verify_device" + sfx).argtypes = [vp] + getattr(L, "hg_claims_verify" + sfx).argtypes
     L.hg_pcs_free.argtypes, L.hg_pcs_free.restype = [vp], None
-    L.hg_pcs_verify_device.argtypes = [vp] + L.hg_pcs_verify.argtypes
-    L.hg_claims_verify_device.argtypes = [vp] + L.hg_claims_verify.argtypes
 
 
 _lib = None
@@ -1259,13 +1260,13 @@ def _pcs_verify(sfx, arrays, root, nvars, claims, proof, n_queries, log2_row, ct
     table, pts, vals = arrays(claims)
     args = (bytes(root), nv, len(nvars), log2_row, table, _ptr(pts), _ptr(vals), len(claims), n_queries, bytes(proof), len(proof))
     L = lib()
-    return _decision(getattr(L, "hg_pcs_verify" + sfx)(*args) if ctx is None else L.hg_pcs_verify_device(ctx.h, *args))
+    return _decision(getattr(L, "hg_pcs_verify" + sfx)(*args) if ctx is None else getattr(L, "hg_pcs_verify_device" + sfx)(ctx.h, *args))
 
 
 def _claims_verify(sfx, params, root, claims, opening, n_queries, log2_row, ctx):
     args = (C.byref(params), bytes(root), log2_row, claims.claims, claims.n, _ptr(claims.points), n_queries, bytes(opening), len(opening))
     L = lib()
-    return _decision(getattr(L, "hg_claims_verify" + sfx)(*args) if ctx is None else L.hg_claims_verify_device(ctx.h, *args))
+    return _decision(getattr(L, "hg_claims_verify" + sfx)(*args) if ctx is None else getattr(L, "hg_claims_verify_device" + sfx)(ctx.h, *args))
 
 
 def pcs_verify(root, nvars, claims, proof, n_queries=0, log2_row=0, ctx=None):
@@ -1278,14 +1279,16 @@ def claims_verify(params, root, claims, opening, n_queries=0, log2_row=0, ctx=No
     return _claims_verify("", params, root, claims, opening, n_queries, log2_row, ctx)
 
 
-def pcs_verify_bn254(root, nvars, claims, proof, n_queries=0, log2_row=0):
-    """hg_pcs_verify_bn254 (host only): (accepted, reason). claims as Commitment.open takes them on a BN254 handle."""
-    return _pcs_verify("_bn254", _pcs_claim_arrays_bn254, root, nvars, claims, proof, n_queries, log2_row, None)
+def pcs_verify_bn254(root, nvars, claims, proof, n_queries=0, log2_row=0, ctx=None):
+    """hg_pcs_verify_bn254, with a context hg_pcs_verify_device_bn254: (accepted, reason). claims as Commitment.open takes them on a
+    BN254 handle."""
+    return _pcs_verify("_bn254", _pcs_claim_arrays_bn254, root, nvars, claims, proof, n_queries, log2_row, ctx)
 
 
-def claims_verify_bn254(params, root, claims, opening, n_queries=0, log2_row=0):
-    """hg_claims_verify_bn254: an InputClaimsBn254 against the root of hg_secrets_commit_bn254: (accepted, reason)."""
-    return _claims_verify("_bn254", params, root, claims, opening, n_queries, log2_row, None)
+def claims_verify_bn254(params, root, claims, opening, n_queries=0, log2_row=0, ctx=None):
+    """hg_claims_verify_bn254, with a context hg_claims_verify_device_bn254: an InputClaimsBn254 against the root of
+    hg_secrets_commit_bn254: (accepted, reason)."""
+    return _claims_verify("_bn254", params, root, claims, opening, n_queries, log2_row, ctx)
 
 
 class LassoNode:

@@ -3,6 +3,7 @@
 // Montgomery-form powers of w, so plain words go through ntt_batch_dev and come out plain - no conversion pass on either NTT path,
 // and the leaf hash and the column gather read the matrix as it is. Keccak and the tree are those of the Goldilocks form
 // (pcs_keccak.hpp, pcs::merkle_levels_device): a node is 32 bytes in either field.
+// The verifier of an opening (pcs_verify_device) reuses the encoding, the leaf sponge and the accumulators and adds five kernels.
 
 constexpr int BNPCS_TPB = 256;
 static unsigned bnpcs_blocks(size_t n) { return (unsigned)((n + BNPCS_TPB - 1) / BNPCS_TPB); }
@@ -25,16 +26,11 @@ __global__ __launch_bounds__(BNPCS_TPB) void k_bnpcs_stage(const Fr* __restrict_
     if (bad) atomicOr(flag, 1u);
 }
 
-// One thread per column j of the encoded matrix: leaves[j] = Keccak256(LE64(0) || repr(M[0][j]) || .. || repr(M[R-1][j])). The
-// message is 4R + 1 words, the prefix first; 17 words per permutation; padding 0x01 .. 0x80 (in one word when they meet). Message
-// word w >= 1 is word (w - 1) & 3 of element (w - 1) >> 2: the address is computed, the lane of the state it goes to is a
-// compile-time constant. A wavefront reads 64 adjacent elements of a row; the four words of an element come from one 32-byte sector.
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcs_leaf_hash(const Fr* __restrict__ M, size_t N, size_t R, u64* __restrict__ leaves) {
-    const size_t j = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
-    if (j >= N) return;
-    const u64* __restrict__ col = reinterpret_cast<const u64*>(M + j);
-    const size_t stride = 4 * N;                      // words between the rows
-    u64 a[25];
+// The sponge of a leaf: a = the state after Keccak256(LE64(0) || repr(e_0) || .. || repr(e_{R-1})), element r at col + r * stride
+// (words). The message is 4R + 1 words, the prefix first; 17 words per permutation; padding 0x01 .. 0x80 (in one word when they
+// meet). Message word w >= 1 is word (w - 1) & 3 of element (w - 1) >> 2: the address is computed, the lane of the state it goes
+// to is a compile-time constant.
+__device__ __forceinline__ void bnpcs_leaf_absorb(const u64* __restrict__ col, size_t stride, size_t R, u64 (&a)[25]) {
 #pragma unroll
     for (int i = 0; i < 25; i++) a[i] = 0;
     const size_t words = 4 * R + 1;
@@ -52,6 +48,14 @@ __global__ __launch_bounds__(BNPCS_TPB) void k_bnpcs_leaf_hash(const Fr* __restr
         if (b + 1 == blocks) a[pcs::RATE_WORDS - 1] ^= 0x8000000000000000ull;
         pcs::keccak_f(a);
     }
+}
+// One thread per column j of the encoded matrix: leaves[j] = the leaf hash of M[0][j] .. M[R-1][j]. A wavefront reads 64 adjacent
+// elements of a row; the four words of an element come from one 32-byte sector.
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcs_leaf_hash(const Fr* __restrict__ M, size_t N, size_t R, u64* __restrict__ leaves) {
+    const size_t j = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
+    if (j >= N) return;
+    u64 a[25];
+    bnpcs_leaf_absorb(reinterpret_cast<const u64*>(M + j), 4 * N, R, a);   // 4N words between the rows
     u64* out = leaves + 4 * j;
     out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
 }
@@ -219,4 +223,249 @@ void pcs_columns_device(const pcs::Commitment& cm, const std::vector<size_t>& js
     hipc(hipMemcpyAsync(cols, d_cols, Q * R * sizeof(Fr), hipMemcpyDeviceToHost, st), "download columns");
     hipc(hipStreamSynchronize(st), "hg_pcs_open_bn254: sync");
     hipc(hipGetLastError(), "hg_pcs_open_bn254: launch");
+}
+
+// ---- the verifier of an opening (pcs_verify_device). A word of the opening only ever becomes a number; every index below comes
+// from the shape, from the host's masked j_q or from table offsets the entry point validated. Each result cell holds the lowest
+// offending key (atomicMin), so the reason is the host's also where several checks fail at once.
+constexpr u64 BNPCSV_NONE = ~(u64)0;   // a cell no thread lowered: nothing failed
+__device__ __forceinline__ void bnpcsv_min(u64* cell, u64 v) { atomicMin(reinterpret_cast<unsigned long long*>(cell), (unsigned long long)v); }
+
+// 32 big-endian bytes of the opening -> 4 native limbs (limb w = the byte-swapped word 3 - w). Element i < u_el is element
+// i & (C - 1) of u vector i >> c: kept in u and scattered into row i >> c of the matrix the NTT encodes (zeroed beforehand). The
+// others are the Q * R column elements, query q at element u_el + q * q_el. cells[0] = the lowest byte offset of an element that
+// is not below r (all four limbs compared). Elements stay plain words: no Montgomery conversion (ntt_batch_dev keeps the form).
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsv_canon(const u64* __restrict__ proof, size_t u_el, size_t Q, size_t R, size_t q_el, int c, Fr* __restrict__ u,
+                                                            Fr* __restrict__ cols, Fr* __restrict__ enc, u64* __restrict__ cells) {
+    const size_t total = u_el + Q * R, Cm = ((size_t)1 << c) - 1;
+    u64 bad = BNPCSV_NONE;
+    for (size_t i = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * BNPCS_TPB) {
+        size_t at = i;
+        if (i >= u_el) { const size_t k = i - u_el, q = k / R; at = u_el + q * q_el + (k - q * R); }
+        const u64* p = proof + 4 * at;
+        const Fr v = fr_make(__builtin_bswap64(p[3]), __builtin_bswap64(p[2]), __builtin_bswap64(p[1]), __builtin_bswap64(p[0]));
+        if (fr_geq_p(v) && 32 * at < bad) bad = 32 * at;
+        if (i < u_el) {
+            lz_gstore(u + i, v);
+            lz_gstore(enc + ((i >> c) << (c + 2)) + (i & Cm), v);
+        } else {
+            lz_gstore(cols + (i - u_el), v);
+        }
+    }
+    if (bad != BNPCSV_NONE) bnpcsv_min(cells, bad);
+}
+
+// <u_i, eq(z_i[..c])> == y_i, one workgroup per claim i (blockIdx.x). zlo holds the c low coordinates of every point in Montgomery
+// form, so a factor of eq(z, x) = prod_b (x_b ? z_b : 1 - z_b) is in Montgomery form and factor x plain element is the plain
+// product. The factors are formed per entry: a thread keeps the one of the low eight bits of x, which its entries share.
+// cells[1] = the lowest failing claim.
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsv_eval(const Fr* __restrict__ u, int c, const Fr* __restrict__ zlo, const Fr* __restrict__ y, u64* __restrict__ cells) {
+    __shared__ Fr part[BNPCS_TPB];
+    const size_t C = (size_t)1 << c, i = blockIdx.x;
+    const Fr* z = zlo + i * (size_t)c;
+    const Fr* ui = u + (i + 1) * C;
+    const int lo = c < 8 ? c : 8;
+    Fr f = fr_one_mont();
+    for (int b = 0; b < lo; b++) { const Fr zb = lz_gload(z + b); f = fr_mul(f, (threadIdx.x >> b) & 1 ? zb : fr_sub(fr_one_mont(), zb)); }
+    Fr s = fr_zero();
+    for (size_t x = threadIdx.x; x < C; x += BNPCS_TPB) {
+        Fr g = f;
+        for (int b = 8; b < c; b++) { const Fr zb = lz_gload(z + b); g = fr_mul(g, (x >> b) & 1 ? zb : fr_sub(fr_one_mont(), zb)); }
+        s = fr_add(s, fr_mul(lz_gload(ui + x), g));
+    }
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = BNPCS_TPB / 2; h >= 1; h >>= 1) {
+        if (threadIdx.x < h) part[threadIdx.x] = fr_add(part[threadIdx.x], part[threadIdx.x + h]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && !fr_eq(part[0], lz_gload(y + i))) bnpcsv_min(cells + 1, (u64)i);
+}
+
+// One thread per query: the leaf hash of its R column elements (contiguous: 4 words between them) -> leaves[q]
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsv_leaf(const Fr* __restrict__ cols, size_t Q, size_t R, u64* __restrict__ leaves) {
+    const size_t q = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
+    if (q >= Q) return;
+    u64 a[25];
+    bnpcs_leaf_absorb(reinterpret_cast<const u64*>(cols + q * R), 4, R, a);
+    u64* out = leaves + 4 * q;
+    out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
+}
+
+// Column inner products. A thread owns query q (the grid's x: Q reaches 65536), blockIdx.y is the job, so the weight is uniform
+// over the wavefront: s[job][q] = sum_{r < nrows} w[woff + r] * col_q[row0 + r], canonical. Job 0 is the proximity combination
+// (rho^r over the whole column), job 1 + i claim i's (eq(z_i[c..]) over the rows of its table). The accumulators and their bound
+// are k_bnpcs_combine's: a column element that passed k_bnpcsv_canon is below r, the weight is a residue, BNPCS_CHUNK products a
+// reduction. (An element that did not pass only makes this sum meaningless, and cells[0] decides ahead of whatever reads it.)
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsv_dots(const Fr* __restrict__ cols, size_t Q, size_t R, const BnPcsDesc* __restrict__ jobs, const Fr* __restrict__ w,
+                                                           Fr* __restrict__ s) {
+    const size_t q = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
+    if (q >= Q) return;
+    const BnPcsDesc job = jobs[blockIdx.y];
+    const Fr* src = cols + q * R + job.row0;
+    const u32* wq = reinterpret_cast<const u32*>(w + job.woff);
+    Fr acc = fr_zero();
+    for (u64 r0 = 0; r0 < job.nrows; r0 += BNPCS_CHUNK) {
+        const u64 r1 = r0 + BNPCS_CHUNK < job.nrows ? r0 + BNPCS_CHUNK : job.nrows;
+        WCol A = wcol_zero();
+        for (u64 r = r0; r < r1; r++) {
+            const Fr x = lz_gload(src + r);
+            u32 bl[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) bl[k] = __builtin_amdgcn_readfirstlane(wq[8 * r + k]);
+            bnpcs_mac_uniform(A, x, bl);
+        }
+        acc = lz_add(acc, lz_reduce(A));
+    }
+    lz_gstore(s + (size_t)blockIdx.y * Q + q, lz_canon(acc));
+}
+
+// One thread per query, once the host has the column indices: the path from the leaf hash over the c+2 siblings (32 raw bytes
+// each behind the query's column elements; bit l of j_q says on which side level l's sibling lies) against the root, then s[0][q]
+// against Enc(u_0)[j_q], then s[1 + i][q] against Enc(u_i)[j_q]. cells[2] = the lowest q * (n + 2) + kind that failed: kind 0 the
+// path, 1 proximity, 2 + i claim i.
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsv_query(const u64* __restrict__ proof, size_t u_el, size_t q_el, size_t Q, size_t R, int depth,
+                                                            const u64* __restrict__ leaves, const Fr* __restrict__ s, const Fr* __restrict__ enc, size_t n,
+                                                            const u64* __restrict__ js, const u64* __restrict__ root, u64* __restrict__ cells) {
+    const size_t q = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
+    if (q >= Q) return;
+    const size_t N = (size_t)1 << depth, j = js[q];
+    const u64* sib = proof + 4 * (u_el + q * q_el + R);
+    u64 h0 = leaves[4 * q], h1 = leaves[4 * q + 1], h2 = leaves[4 * q + 2], h3 = leaves[4 * q + 3];
+    for (int l = 0; l < depth; l++) {
+        const bool right = (j >> l) & 1;   // this node is the right child
+        const u64 t0 = sib[4 * l], t1 = sib[4 * l + 1], t2 = sib[4 * l + 2], t3 = sib[4 * l + 3];
+        u64 a[25];
+        a[0] = 1;
+        a[1] = right ? t0 : h0; a[2] = right ? t1 : h1; a[3] = right ? t2 : h2; a[4] = right ? t3 : h3;
+        a[5] = right ? h0 : t0; a[6] = right ? h1 : t1; a[7] = right ? h2 : t2; a[8] = right ? h3 : t3;
+        a[9] = 0x01;
+#pragma unroll
+        for (int k = 10; k < 25; k++) a[k] = 0;
+        a[pcs::RATE_WORDS - 1] = 0x8000000000000000ull;
+        pcs::keccak_f(a);
+        h0 = a[0]; h1 = a[1]; h2 = a[2]; h3 = a[3];
+    }
+    const size_t key = q * (n + 2);
+    if (h0 != root[0] || h1 != root[1] || h2 != root[2] || h3 != root[3]) { bnpcsv_min(cells + 2, key); return; }
+    for (size_t i = 0; i <= n; i++)
+        if (!fr_eq(lz_gload(s + i * Q + q), lz_gload(enc + i * N + j))) { bnpcsv_min(cells + 2, key + 1 + i); return; }
+}
+
+// hg_pcs_verify_device_bn254. Everything but the last kernel needs no column index, so it is enqueued first and runs while the
+// host hashes the u_i; the indices follow on the same stream, then the three result cells come back: one synchronisation. The
+// leaf sponge (serial: 4R + 1 words a thread, Q threads) is the longest of the early kernels and goes last among them, so the two
+// verdicts that need no index and the inner products never wait behind it; the host's own hash of the u_i covers it.
+std::string pcs_verify_device(hg_ctx* ctx, const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof, size_t len) {
+    const size_t C = sh.C(), N = sh.N(), R = sh.R, n = claims.size();
+    const int depth = sh.depth();
+    const std::string bad_len = pcs::length_reason(len, pcs_opening_bytes(sh, n, Q));
+    if (!bad_len.empty()) return bad_len;
+    const size_t u_el = C * (n + 1), q_el = R + (size_t)depth, njobs = n + 1;
+    hipc(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->arena_reset();
+    hipStream_t st = ctx->stream;
+    // root, descriptors, values, the low coordinates of the points (Montgomery) and the weight tables (Montgomery) in one staged copy
+    FsTranscript tr = pcs_start_transcript(sh, root, claims, Q);
+    const std::vector<Fr> rho = pcs_rho_powers(pcs_squeeze(tr), R);
+    size_t nw = R;
+    for (const PcsClaim& cl : claims) nw += (size_t)1 << (sh.nvars[cl.table] - sh.c);
+    const size_t desc_at = 32, y_at = desc_at + ((njobs * sizeof(BnPcsDesc) + 31) & ~(size_t)31), z_at = y_at + n * sizeof(Fr), w_at = z_at + n * (size_t)sh.c * sizeof(Fr);
+    std::vector<char> stage(w_at + nw * sizeof(Fr));
+    memcpy(stage.data(), root, 32);
+    BnPcsDesc* hd = reinterpret_cast<BnPcsDesc*>(stage.data() + desc_at);
+    Fr* hy = reinterpret_cast<Fr*>(stage.data() + y_at);
+    Fr* hz = reinterpret_cast<Fr*>(stage.data() + z_at);
+    Fr* hw = reinterpret_cast<Fr*>(stage.data() + w_at);
+    hd[0].row0 = 0; hd[0].nrows = R; hd[0].woff = 0;
+    memcpy(hw, rho.data(), R * sizeof(Fr));
+    size_t off = R;
+    for (size_t i = 0; i < n; i++) {
+        const PcsClaim& cl = claims[i];
+        const std::vector<Fr> w = pcs_eq_table(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
+        hd[i + 1].row0 = sh.off[cl.table]; hd[i + 1].nrows = w.size(); hd[i + 1].woff = off;
+        memcpy(hw + off, w.data(), w.size() * sizeof(Fr));
+        off += w.size();
+        hy[i] = cl.value;
+        for (int b = 0; b < sh.c; b++) hz[i * (size_t)sh.c + b] = fr_to_mont(cl.point[b]);
+    }
+    u64 *d_proof, *d_leaves, *d_js, *d_cells;
+    Fr *d_u, *d_cols, *d_enc, *d_tmp, *d_W, *d_s;
+    char* d_stage;
+    try {
+        d_proof = ctx->alloc_n<u64>(len / 8);
+        d_stage = ctx->alloc_n<char>(stage.size());
+        d_u = ctx->alloc_n<Fr>(u_el);
+        d_cols = ctx->alloc_n<Fr>(Q * R);
+        d_enc = ctx->alloc_n<Fr>(njobs * N);
+        d_tmp = ctx->alloc_n<Fr>(njobs * N);
+        d_W = ctx->alloc_n<Fr>(N);
+        d_leaves = ctx->alloc_n<u64>(4 * Q);
+        d_s = ctx->alloc_n<Fr>(Q * njobs);
+        d_js = ctx->alloc_n<u64>(Q);
+        d_cells = ctx->alloc_n<u64>(4);
+    } catch (const std::exception& e) {
+        throw Error(std::string("the context's arena cannot hold the opening (") + e.what() + ")");
+    }
+    struct Drain {   // an error between the first enqueue and the synchronisation must not leave copies of dead host buffers behind
+        hipStream_t st; bool armed = true;
+        ~Drain() { if (armed) (void)hipStreamSynchronize(st); }
+    } drain{st};
+    const int cls = ctx->prof_class("pcs_bn254_verify", false);
+    ctx->prof_stream = st;
+    const BnPcsDesc* d_jobs = reinterpret_cast<const BnPcsDesc*>(d_stage + desc_at);
+    const u64* d_root = reinterpret_cast<const u64*>(d_stage);
+    hipc(hipMemcpyAsync(d_proof, proof, len, hipMemcpyHostToDevice, st), "upload opening");
+    hipc(hipMemcpyAsync(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, st), "upload claims");
+    hipc(hipMemsetAsync(d_cells, 0xff, 32, st), "memset");
+    hipc(hipMemsetAsync(d_enc, 0, njobs * N * sizeof(Fr), st), "memset");
+    ctx->prof_begin(cls, (double)(u_el + Q * R) * 64 + (double)u_el * 32);
+    k_bnpcsv_canon<<<(unsigned)std::min<size_t>(bnpcs_blocks(u_el + Q * R), 4096), BNPCS_TPB, 0, st>>>(d_proof, u_el, Q, R, q_el, sh.c, d_u, d_cols, d_enc, d_cells);
+    ctx->prof_end();
+    if (n) {
+        ctx->prof_begin(cls, (double)n * C * 32);
+        k_bnpcsv_eval<<<(unsigned)n, BNPCS_TPB, 0, st>>>(d_u, sh.c, reinterpret_cast<const Fr*>(d_stage + z_at), reinterpret_cast<const Fr*>(d_stage + y_at), d_cells);
+        ctx->prof_end();
+    }
+    ctx->prof_begin(cls, (double)njobs * N * 32 * 4);
+    k_bn_powers<<<bnpcs_blocks(N), 256, 0, st>>>(d_W, fr_root_of_unity(depth), N);
+    ntt_batch_dev(st, d_enc, d_tmp, d_W, depth, njobs, nullptr);
+    ctx->prof_end();
+    if (Q) {
+        ctx->prof_begin(cls, (double)Q * nw * 64);
+        k_bnpcsv_dots<<<dim3(bnpcs_blocks(Q), (unsigned)njobs), BNPCS_TPB, 0, st>>>(d_cols, Q, R, d_jobs, reinterpret_cast<const Fr*>(d_stage + w_at), d_s);
+        ctx->prof_end();
+        ctx->prof_begin(cls, (double)Q * R * 32);
+        k_bnpcsv_leaf<<<bnpcs_blocks(Q), BNPCS_TPB, 0, st>>>(d_cols, Q, R, d_leaves);
+        ctx->prof_end();
+    }
+    // the host's share, beside the kernels: the u_i into the transcript, the column indices out of it
+    {
+        std::vector<Fr> u(u_el);
+        for (size_t i = 0; i < u_el; i++) u[i] = pcs_read_be32(proof + 32 * i);
+        pcs_absorb(tr, u.data(), u_el);
+    }
+    const std::vector<size_t> js = pcs_squeeze_indices(tr, N, Q);
+    const std::vector<u64> hj(js.begin(), js.end());
+    if (Q) {
+        hipc(hipMemcpyAsync(d_js, hj.data(), Q * 8, hipMemcpyHostToDevice, st), "upload column indices");
+        ctx->prof_begin(cls, (double)Q * (32.0 * depth + 64.0 * njobs));
+        k_bnpcsv_query<<<bnpcs_blocks(Q), BNPCS_TPB, 0, st>>>(d_proof, u_el, q_el, Q, R, depth, d_leaves, d_s, d_enc, n, d_js, d_root, d_cells);
+        ctx->prof_end();
+    }
+    u64 cells[4];
+    hipc(hipMemcpyAsync(cells, d_cells, 32, hipMemcpyDeviceToHost, st), "download verdict");
+    const hipError_t synced = hipStreamSynchronize(st);
+    drain.armed = false;
+    hipc(synced, "hg_pcs_verify_device_bn254: sync");
+    hipc(hipGetLastError(), "hg_pcs_verify_device_bn254: launch");
+    ctx->prof_collect();
+    // the host's order: a non-canonical element, the lowest claim whose evaluation fails, the lowest failing query
+    if (cells[0] != BNPCSV_NONE) return pcs::reason_noncanonical((size_t)cells[0]);
+    if (cells[1] != BNPCSV_NONE) return pcs::reason_evaluation((size_t)cells[1]);
+    if (cells[2] != BNPCSV_NONE) {
+        const size_t q = (size_t)(cells[2] / (n + 2)), kind = (size_t)(cells[2] % (n + 2));
+        return kind == 0 ? pcs::reason_merkle(q) : kind == 1 ? pcs::reason_proximity(q) : pcs::reason_claim(kind - 2, q);
+    }
+    return "";
 }

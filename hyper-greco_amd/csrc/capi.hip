@@ -198,9 +198,14 @@ struct BnAbi {
         return ctx ? bn::pcs_commit_device(who, ctx, sh, tabs, true) : bn::pcs_commit_host(who, sh, tabs, true);
     }
     static std::vector<uint8_t> pcs_open(const char* who, const pcs::Commitment& cm, const std::vector<PcsClaim>& cl, size_t Q) { return bn::pcs_open(who, cm, cl, Q); }
-    // (host only: no entry passes a context)
-    static std::string pcs_verify(const char*, hg_ctx*, const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& cl, size_t Q, const uint8_t* proof, size_t len) {
-        return bn::pcs_verify(sh, root, cl, Q, proof, len);
+    // ctx: the device form (hg_pcs_verify_device_bn254), whose errors carry the entry's name
+    static std::string pcs_verify(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& cl, size_t Q, const uint8_t* proof, size_t len) {
+        if (!ctx) return bn::pcs_verify(sh, root, cl, Q, proof, len);
+        try {
+            return bn::pcs_verify_device(ctx, sh, root, cl, Q, proof, len);
+        } catch (const std::exception& e) {
+            throw Error(std::string(who) + ": " + e.what());
+        }
     }
 };
 }  // namespace
@@ -1854,6 +1859,11 @@ int hg_pcs_verify_bn254(const uint8_t root[32], const uint32_t* nvars, size_t n_
     HG_ENTRY(pcs_verify_entry<BnAbi>("hg_pcs_verify_bn254", false, nullptr, root, nvars, n_tables, log2_row, table, points4, values4, n_claims, n_queries, proof, len))
 }
 
+int hg_pcs_verify_device_bn254(hg_ctx* ctx, const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table, const uint64_t* points4,
+                               const uint64_t* values4, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
+    HG_ENTRY(pcs_verify_entry<BnAbi>("hg_pcs_verify_device_bn254", true, ctx, root, nvars, n_tables, log2_row, table, points4, values4, n_claims, n_queries, proof, len))
+}
+
 int hg_secrets_commit_bn254(hg_ctx* ctx, const hg_params* params, const hg_witness* w, size_t log2_row, void** commitment, uint8_t root[32]) {
     HG_ENTRY(secrets_commit_entry<BnAbi>("hg_secrets_commit_bn254", ctx, params, w, log2_row, commitment, root))
 }
@@ -1866,6 +1876,11 @@ int hg_claims_open_bn254(hg_ctx* ctx, const hg_params* params, const void* commi
 int hg_claims_verify_bn254(const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points4,
                            size_t n_queries, const uint8_t* opening, size_t len) {
     HG_ENTRY(claims_verify_entry<BnAbi>("hg_claims_verify_bn254", false, nullptr, params, root, log2_row, claims, n, points4, n_queries, opening, len))
+}
+
+int hg_claims_verify_device_bn254(hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points4,
+                                  size_t n_queries, const uint8_t* opening, size_t len) {
+    HG_ENTRY(claims_verify_entry<BnAbi>("hg_claims_verify_device_bn254", true, ctx, params, root, log2_row, claims, n, points4, n_queries, opening, len))
 }
 
 int hg_profile(hg_ctx* ctx, int level) {

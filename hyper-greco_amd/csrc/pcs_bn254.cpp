@@ -49,7 +49,7 @@ static void leaf_hash_fr(const Fr* col, size_t R, uint8_t out[32]) {   // Keccak
     memcpy(msg.data() + 1, col, 32 * R);
     keccak256(reinterpret_cast<const uint8_t*>(msg.data()), 8 * msg.size(), out);
 }
-static std::vector<Fr> eq_table_fr(const Fr* pt_canon, size_t n) {   // Montgomery form; coordinate i belongs to bit i of the index
+std::vector<Fr> pcs_eq_table(const Fr* pt_canon, size_t n) {   // Montgomery form; coordinate i belongs to bit i of the index
     std::vector<Fr> t(1, fr_one_mont());
     t.reserve((size_t)1 << n);
     for (size_t i = 0; i < n; i++) {
@@ -64,7 +64,7 @@ static std::vector<Fr> eq_table_fr(const Fr* pt_canon, size_t n) {   // Montgome
     }
     return t;
 }
-static std::vector<Fr> rho_powers_fr(const Fr& rho_canon, size_t R) {
+std::vector<Fr> pcs_rho_powers(const Fr& rho_canon, size_t R) {
     std::vector<Fr> w(R);
     const Fr rho = fr_to_mont(rho_canon);
     Fr x = fr_one_mont();
@@ -158,13 +158,14 @@ void pcs_columns_host(const Commitment& cm, const std::vector<size_t>& js, Fr* c
         for (size_t r = 0; r < R; r++) cols[q * R + r] = M[r * N + js[q]];
 }
 
-// ---- the transcript both sides share: FsTranscript's pending bytes and proof stream under the BN254 rules
+// ---- the transcript both sides and both forms of the verifier share (declared in pcs_bn254.hpp): FsTranscript's pending bytes and
+// proof stream under the BN254 rules
 static void put_le32(std::vector<uint8_t>& v, uint32_t x) { for (int i = 0; i < 4; i++) v.push_back((uint8_t)(x >> (8 * i))); }
-static void absorb_repr(FsTranscript& tr, const Fr* x, size_t count) {   // little-endian host: canonical words are the repr
+void pcs_absorb(FsTranscript& tr, const Fr* x, size_t count) {   // little-endian host: canonical words are the repr
     const uint8_t* b = reinterpret_cast<const uint8_t*>(x);
     tr.pending.insert(tr.pending.end(), b, b + 32 * count);
 }
-static Fr squeeze_fr(FsTranscript& tr) {   // LE(hash) mod r, the state re-hashed: hg_challenges_bn254's rule over the absorbed bytes
+Fr pcs_squeeze(FsTranscript& tr) {   // LE(hash) mod r, the state re-hashed: hg_challenges_bn254's rule over the absorbed bytes
     uint8_t h[32];
     keccak256(tr.pending.data(), tr.pending.size(), h);
     tr.pending.assign(h, h + 32);
@@ -173,7 +174,7 @@ static Fr squeeze_fr(FsTranscript& tr) {   // LE(hash) mod r, the state re-hashe
     while (fr_geq_p(v)) v = fr_sub_p(v);   // 2^256 / r < 6
     return v;
 }
-static FsTranscript start_transcript(const Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q) {
+FsTranscript pcs_start_transcript(const Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q) {
     FsTranscript tr;
     tr.absorb = true;
     static const char tag[] = "hg-pcs-bn254-1";
@@ -186,21 +187,21 @@ static FsTranscript start_transcript(const Shape& sh, const uint8_t root[32], co
     put_le32(tr.pending, (uint32_t)claims.size());
     for (const PcsClaim& cl : claims) {
         put_le32(tr.pending, (uint32_t)cl.table);
-        absorb_repr(tr, cl.point.data(), cl.point.size());
-        absorb_repr(tr, &cl.value, 1);
+        pcs_absorb(tr, cl.point.data(), cl.point.size());
+        pcs_absorb(tr, &cl.value, 1);
     }
     return tr;
 }
-static std::vector<size_t> squeeze_indices(FsTranscript& tr, size_t N, size_t Q) {   // the low 64 bits of a squeezed element & (N - 1)
+std::vector<size_t> pcs_squeeze_indices(FsTranscript& tr, size_t N, size_t Q) {   // the low 64 bits of a squeezed element & (N - 1)
     std::vector<size_t> js(Q);
-    for (size_t q = 0; q < Q; q++) js[q] = (size_t)(squeeze_fr(tr).l[0] & (u64)(N - 1));
+    for (size_t q = 0; q < Q; q++) js[q] = (size_t)(pcs_squeeze(tr).l[0] & (u64)(N - 1));
     return js;
 }
 static void write_be32(std::vector<uint8_t>& out, const Fr& x) {   // 32 bytes big-endian, as every BN254 proof element
     for (int w = 3; w >= 0; w--)
         for (int b = 7; b >= 0; b--) out.push_back((uint8_t)(x.l[w] >> (8 * b)));
 }
-static Fr read_be32(const uint8_t* p) {
+Fr pcs_read_be32(const uint8_t* p) {
     Fr v;
     for (int w = 0; w < 4; w++) {
         u64 a = 0;
@@ -213,27 +214,27 @@ static Fr read_be32(const uint8_t* p) {
 std::vector<uint8_t> pcs_open(const char* who, const Commitment& cm, const std::vector<PcsClaim>& claims, size_t Q) {
     const Shape& sh = cm.sh;
     const size_t C = sh.C(), N = sh.N(), R = sh.R, n = claims.size();
-    FsTranscript tr = start_transcript(sh, cm.root(), claims, Q);
+    FsTranscript tr = pcs_start_transcript(sh, cm.root(), claims, Q);
     std::vector<PcsJob> jobs(n + 1);
-    jobs[0].row0 = 0; jobs[0].nrows = R; jobs[0].w = rho_powers_fr(squeeze_fr(tr), R);
+    jobs[0].row0 = 0; jobs[0].nrows = R; jobs[0].w = pcs_rho_powers(pcs_squeeze(tr), R);
     for (size_t i = 0; i < n; i++) {
         const PcsClaim& cl = claims[i];
         jobs[i + 1].row0 = sh.off[cl.table];
         jobs[i + 1].nrows = (size_t)1 << (sh.nvars[cl.table] - sh.c);
-        jobs[i + 1].w = eq_table_fr(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
+        jobs[i + 1].w = pcs_eq_table(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
     }
     std::vector<Fr> u((n + 1) * C);
     if (cm.ctx) pcs_combine_device(cm, jobs, u.data()); else pcs_combine_host(cm, jobs, u.data());
     for (size_t i = 0; i < n; i++) {   // the prover holds u_i: the check is free
-        const std::vector<Fr> lo = eq_table_fr(claims[i].point.data(), (size_t)sh.c);
+        const std::vector<Fr> lo = pcs_eq_table(claims[i].point.data(), (size_t)sh.c);
         if (!fr_eq(dot_fr(lo.data(), u.data() + (i + 1) * C, C), claims[i].value))
             throw Error(std::string(who) + ": claim " + std::to_string(i) + ": the value is not the evaluation of table " + std::to_string(claims[i].table) + " at the point");
     }
     std::vector<uint8_t>& out = tr.bytes;
     out.reserve(pcs_opening_bytes(sh, n, Q));
     for (const Fr& x : u) write_be32(out, x);
-    absorb_repr(tr, u.data(), u.size());
-    const std::vector<size_t> js = squeeze_indices(tr, N, Q);
+    pcs_absorb(tr, u.data(), u.size());
+    const std::vector<size_t> js = pcs_squeeze_indices(tr, N, Q);
     std::vector<Fr> cols(Q * R);
     if (Q) { if (cm.ctx) pcs_columns_device(cm, js, cols.data()); else pcs_columns_host(cm, js, cols.data()); }
     for (size_t q = 0; q < Q; q++) {
@@ -258,26 +259,26 @@ std::string pcs_verify(const Shape& sh, const uint8_t root[32], const std::vecto
     const size_t u_bytes = 32 * C * (n + 1), q_bytes = 32 * R + 32 * (size_t)depth;
     std::vector<Fr> u((n + 1) * C);
     for (size_t i = 0; i < u.size(); i++) {
-        u[i] = read_be32(proof + 32 * i);
+        u[i] = pcs_read_be32(proof + 32 * i);
         if (fr_geq_p(u[i])) return pcs::reason_noncanonical(32 * i);
     }
     std::vector<Fr> cols(Q * R);
     for (size_t q = 0; q < Q; q++)
         for (size_t r = 0; r < R; r++) {
             const size_t at = u_bytes + q * q_bytes + 32 * r;
-            cols[q * R + r] = read_be32(proof + at);
+            cols[q * R + r] = pcs_read_be32(proof + at);
             if (fr_geq_p(cols[q * R + r])) return pcs::reason_noncanonical(at);
         }
     // 3. <u_i, eq(z_i[..c])> == y_i
     for (size_t i = 0; i < n; i++) {
-        const std::vector<Fr> lo = eq_table_fr(claims[i].point.data(), (size_t)sh.c);
+        const std::vector<Fr> lo = pcs_eq_table(claims[i].point.data(), (size_t)sh.c);
         if (!fr_eq(dot_fr(lo.data(), u.data() + (i + 1) * C, C), claims[i].value)) return pcs::reason_evaluation(i);
     }
     // the challenges
-    FsTranscript tr = start_transcript(sh, root, claims, Q);
-    const std::vector<Fr> rho = rho_powers_fr(squeeze_fr(tr), R);
-    absorb_repr(tr, u.data(), u.size());
-    const std::vector<size_t> js = squeeze_indices(tr, N, Q);
+    FsTranscript tr = pcs_start_transcript(sh, root, claims, Q);
+    const std::vector<Fr> rho = pcs_rho_powers(pcs_squeeze(tr), R);
+    pcs_absorb(tr, u.data(), u.size());
+    const std::vector<size_t> js = pcs_squeeze_indices(tr, N, Q);
     // Enc(u_i)
     std::vector<Fr> enc((n + 1) * N, fr_zero());
     std::vector<std::vector<Fr>> w(n);
@@ -289,7 +290,7 @@ std::string pcs_verify(const Shape& sh, const uint8_t root[32], const std::vecto
             memcpy(enc.data() + i * N, u.data() + i * C, 32 * C);
             ntt_host_fr(enc.data() + i * N, depth, W.data());
         }
-        for (size_t i = 0; i < n; i++) w[i] = eq_table_fr(claims[i].point.data() + sh.c, (size_t)(sh.nvars[claims[i].table] - sh.c));
+        for (size_t i = 0; i < n; i++) w[i] = pcs_eq_table(claims[i].point.data() + sh.c, (size_t)(sh.nvars[claims[i].table] - sh.c));
     }
     // 4. per query: path, proximity, claims
     for (size_t q = 0; q < Q; q++) {

@@ -37,6 +37,19 @@ void pcs_columns_device(const pcs::Commitment& cm, const std::vector<size_t>& js
 std::vector<uint8_t> pcs_open(const char* who, const pcs::Commitment& cm, const std::vector<PcsClaim>& claims, size_t Q);
 // hg_pcs_verify_bn254: "" = accepted, else the reason (the strings and the order of pcs::verify)
 std::string pcs_verify(const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof, size_t len);
+// hg_pcs_verify_device_bn254 (bn254_pcs.inc): the same decision and the same reason with the table-sized work on the context's
+// stream; the Fiat-Shamir hash over the u_i stays on the host and runs beside the kernels. Throws an Error if the arena cannot hold
+// the opening
+std::string pcs_verify_device(hg_ctx* ctx, const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof, size_t len);
+
+// ---- what the opening and both forms of the verifier share (pcs_bn254.cpp): the transcript up to the column indices, the weights
+FsTranscript pcs_start_transcript(const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q);
+Fr pcs_squeeze(FsTranscript& tr);                                                    // a challenge, canonical (rho is the first)
+std::vector<Fr> pcs_rho_powers(const Fr& rho_canon, size_t R);                       // rho^r, r < R, Montgomery form
+void pcs_absorb(FsTranscript& tr, const Fr* x, size_t count);                        // canonical elements as their 32 bytes
+std::vector<size_t> pcs_squeeze_indices(FsTranscript& tr, size_t N, size_t Q);       // j_q = a squeezed element's low word & (N - 1)
+std::vector<Fr> pcs_eq_table(const Fr* pt_canon, size_t n);                          // Montgomery form; coordinate i belongs to bit i
+Fr pcs_read_be32(const uint8_t* p);                                                  // an element of the opening as it is read
 
 // the signed lift of a witness word, canonical (host side of fr_lift_signed)
 BN_HD Fr fr_lift_signed_canon(u64 v) { return v < (1ULL << 63) ? fr_make(v, 0, 0, 0) : fr_sub(fr_zero(), fr_make(0xFFFFFFFF00000001ULL - v, 0, 0, 0)); }

@@ -720,7 +720,7 @@ int hg_instance_mle_batch_bn254(hg_ctx* ctx, const void* const* instances, size_
  *     4. Q column indices j_q = (the low 64 bits of a squeezed canonical element) & (4C - 1), duplicates kept;
  *     5. per query the R column elements M[.][j_q] (32-byte big-endian), then the c+2 siblings bottom-up (32 raw bytes each).
  *     Length: exactly 32 C (n+1) + Q (32 R + 32 (c+2)) bytes.
- *   Verification (hg_pcs_verify_bn254, host): the order of checks and the reason strings of hg_pcs_verify - length; every element
+ *   Verification (hg_pcs_verify_bn254 on the host, hg_pcs_verify_device_bn254 on a context): the order of checks and the reason strings of hg_pcs_verify - length; every element
  *     below r ("pcs: non-canonical word at byte B", B = the offset of the first byte of the first element that is not below r, the
  *     u_i first, then the columns query by query); <u_i, eq(z_i[..c])> == y_i; per query the path, the proximity combination against
  *     Enc(u_0)[j_q], every claim's combination against Enc(u_i)[j_q].
@@ -740,7 +740,16 @@ int hg_instance_mle_batch_bn254(hg_ctx* ctx, const void* const* instances, size_
  *   must be the context the commitment was made on (NULL for the host form). The device form runs the row combinations as one
  *   launch and gathers the opened columns with another; it synchronises twice, as hg_pcs_open. Same bytes as the host form. -1 as
  *   hg_pcs_open, and for a handle over Goldilocks.
- * hg_pcs_verify_bn254: host only. -1 as hg_pcs_verify.
+ * hg_pcs_verify_bn254: host only, no context. -1 as hg_pcs_verify.
+ * hg_pcs_verify_device_bn254: hg_pcs_verify_bn254 with the table-sized work on the context's stream; the decision and the reason
+ *   are the host verifier's on every input, also where several checks fail at once (the order above decides: length, the first
+ *   element not below r, the lowest claim whose evaluation fails, the lowest query and within it path, proximity, claims
+ *   ascending). The opening is uploaded as it is; kernels byte-swap its elements into 4 limbs and compare each with r, check the
+ *   evaluations, encode the u_i with the batched Fr NTT, form the inner products of the opened columns and hash them while the host
+ *   hashes the u_i into the transcript; the Q column indices follow on the same stream and a last kernel walks the paths and
+ *   compares; three result words come back: one synchronisation. -1 as hg_pcs_verify_bn254 (naming this function), for a null
+ *   context (".. : no context"), and if the context's arena cannot hold the opening. It uses the context's arena like a prove: not
+ *   concurrently with another call on the same context.
  * hg_secrets_commit_bn254: hg_pcs_commit_bn254 of the five secret inputs of a witness handle, tables in input order and with the
  *   variable counts of hg_secrets_commit; every u64 word of the handle is lifted into Fr by the signed rule - a word below 2^63 is
  *   itself, any other is r - (p_goldilocks - word) - which is the table hg_claims_settle_bn254 evaluates. The device form uploads
@@ -748,18 +757,24 @@ int hg_instance_mle_batch_bn254(hg_ctx* ctx, const void* const* instances, size_
  * hg_claims_open_bn254 / hg_claims_verify_bn254: hg_pcs_open_bn254 / hg_pcs_verify_bn254 for an hg_input_claim_bn254 array and
  *   points4 exactly as hg_verify_public_bn254 / hg_verify_public_batch_bn254 return them, with the input-to-table mapping and the -1
  *   cases of hg_claims_open / hg_claims_verify. hg_verify_public_bn254 followed by hg_claims_verify_bn254 against a root the
- *   encryptor published is a BN254 verification that needs no secret. */
+ *   encryptor published is a BN254 verification that needs no secret. hg_claims_verify_device_bn254 is
+ *   hg_pcs_verify_device_bn254 under the same mapping. */
 int hg_pcs_commit_bn254(hg_ctx* ctx, const uint64_t* const* tables4, const uint32_t* nvars, size_t n_tables, size_t log2_row,
                         void** commitment, uint8_t root[32]);
 int hg_pcs_open_bn254(hg_ctx* ctx, const void* commitment, const uint32_t* table, const uint64_t* points4, const uint64_t* values4,
                       size_t n_claims, size_t n_queries, uint8_t* proof, size_t cap, size_t* len);
 int hg_pcs_verify_bn254(const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table,
                         const uint64_t* points4, const uint64_t* values4, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len);
+int hg_pcs_verify_device_bn254(hg_ctx* ctx, const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table,
+                               const uint64_t* points4, const uint64_t* values4, size_t n_claims, size_t n_queries, const uint8_t* proof,
+                               size_t len);
 int hg_secrets_commit_bn254(hg_ctx* ctx, const hg_params* params, const hg_witness* w, size_t log2_row, void** commitment, uint8_t root[32]);
 int hg_claims_open_bn254(hg_ctx* ctx, const hg_params* params, const void* commitment, const void* claims, size_t n,
                          const uint64_t* points4, size_t n_queries, uint8_t* opening, size_t cap, size_t* len);
 int hg_claims_verify_bn254(const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n,
                            const uint64_t* points4, size_t n_queries, const uint8_t* opening, size_t len);
+int hg_claims_verify_device_bn254(hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n,
+                                  const uint64_t* points4, size_t n_queries, const uint8_t* opening, size_t len);
 
 /* hg_witness_derive and hg_prove_bn254 for a run of n_enc ENCRYPTIONS under one key, pipelined: hg_prove_encryptions over bn256::Fr
  *   [REF scripts/circuit_sk.py:18-140 followed by sk_encryption_circuit.rs:417-460, 614-626; the loop a proving service writes around

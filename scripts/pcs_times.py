@@ -5,11 +5,11 @@ each leg, --reps timed calls each:
   commit_dev / commit_host   hg_secrets_commit with a context / without (upload or copy of the tables, encoding, column hashes, tree)
   open_dev / open_host       hg_claims_open of those claims on the commitment of that form (default 241 queries)
   verify_dev / verify_host   hg_claims_verify_device / hg_claims_verify of the opening: the whole call, upload included
-Prints the opening's bytes, median and range per leg, and for the commit and the verify pair whether the whole range of the device
-form lies below that of the host form.
---field bn254 times the BN254 commitment on the claims hg_verify_public_device_bn254 leaves on an hg_prove_bn254 proof: the commit and
-open pairs and the host verifier (there is no device verifier over BN254), then one more device commit and open under hg_profile
-for the kernel time by class.
+Prints the opening's bytes, median and range per leg, and for the commit and the verify pair (over BN254 the open pair too) whether the
+whole range of the device form lies below that of the host form.
+--field bn254 times the BN254 commitment on the claims hg_verify_public_device_bn254 leaves on an hg_prove_bn254 proof: the same three
+pairs (verify_dev is hg_claims_verify_device_bn254), then one more device commit, open and verification under hg_profile for the kernel
+time by class.
 Usage: pcs_times.py [n k] [--reps 5] [--field goldilocks|bn254]"""
 import argparse
 import os
@@ -54,10 +54,9 @@ def main():
         held[form] = secrets(ctx if form == "dev" else None, bfv.params, w)
 
     legs = [("commit_dev", lambda: commit("dev")), ("commit_host", lambda: commit("host")),
-            ("open_dev", lambda: held["dev"].open_claims(bfv.params, claims)), ("open_host", lambda: held["host"].open_claims(bfv.params, claims))]
-    if not bn:
-        legs.append(("verify_dev", lambda: hg.claims_verify(bfv.params, held["host"].root, claims, opening, ctx=ctx)))
-    legs.append(("verify_host", lambda: verify(bfv.params, held["host"].root, claims, opening)))
+            ("open_dev", lambda: held["dev"].open_claims(bfv.params, claims)), ("open_host", lambda: held["host"].open_claims(bfv.params, claims)),
+            ("verify_dev", lambda: verify(bfv.params, held["host"].root, claims, opening, ctx=ctx)),
+            ("verify_host", lambda: verify(bfv.params, held["host"].root, claims, opening))]
     times = {name: [] for name, _ in legs}
     for rep in range(a.reps + 1):   # rep 0: the warm-up call of each leg
         for name, fn in legs:
@@ -76,7 +75,7 @@ def main():
     for name, _ in legs:
         t = times[name]
         print("%-11s median %.2f ms, range %.2f .. %.2f ms (%s)" % (name, statistics.median(t), min(t), max(t), " ".join("%.2f" % x for x in t)))
-    for leg in ("commit", "open") if bn else ("commit", "verify"):
+    for leg in ("commit", "open", "verify") if bn else ("commit", "verify"):
         dev, host = times[leg + "_dev"], times[leg + "_host"]
         if max(dev) < min(host):
             print("%s_dev is faster than %s_host: its whole range lies below the host form's" % (leg, leg))
@@ -84,11 +83,12 @@ def main():
             print("%s_dev is SLOWER than %s_host: its whole range lies above the host form's" % (leg, leg))
         else:
             print("%s_dev and %s_host overlap: no difference shown" % (leg, leg))
-    if bn:   # one more device commit and open with every launch class timed by events
+    if bn:   # one more device commit, open and verification with every launch class timed by events
         ctx.profile(2)
         ctx.profile_reset()
         commit("dev")
         held["dev"].open_claims(bfv.params, claims)
+        assert verify(bfv.params, held["host"].root, claims, opening, ctx=ctx) == (True, "")
         for st in ctx.profile_get(256):
             if st["name"].startswith("pcs_bn254"):
                 print("%-18s %2d launches %8.3f ms  %7.1f MB by the algorithm" % (st["name"], st["launches"], st["total_ms"], st["algo_bytes"] / 1e6))
