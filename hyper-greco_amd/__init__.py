@@ -54,7 +54,7 @@ EXPORTS = [
     "hg_witness_get", "hg_witness_free", "hg_prove", "hg_warmup", "hg_prove_stream", "hg_encryption_layout", "hg_prove_encryptions", "hg_verify", "hg_verify_device", "hg_verify_device_mode", "hg_verify_device_batch",
     "hg_instance_from_ciphertext", "hg_instance_from_witness", "hg_instance_free", "hg_instance_coeffs", "hg_instance_get", "hg_pk_claim_shape", "hg_verify_public", "hg_verify_public_device", "hg_verify_public_batch", "hg_claims_settle", "hg_instance_mle", "hg_instance_mle_batch",
     "hg_pcs_commit", "hg_pcs_free", "hg_pcs_open", "hg_pcs_verify", "hg_secrets_commit", "hg_claims_open", "hg_claims_verify",
-    "hg_pcs_verify_device", "hg_claims_verify_device",
+    "hg_pcs_verify_device", "hg_claims_verify_device", "hg_pcs_verify_device_batch", "hg_claims_verify_batch",
     "hg_pcs_commit_bn254", "hg_pcs_open_bn254", "hg_pcs_verify_bn254", "hg_secrets_commit_bn254", "hg_claims_open_bn254", "hg_claims_verify_bn254",
     "hg_pcs_verify_device_bn254", "hg_claims_verify_device_bn254",
     "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_mle_eval",
@@ -103,6 +103,9 @@ def _two_field_protos(L):
         getattr(L, "hg_pcs_verify_device" + sfx).argtypes = [vp] + getattr(L, "hg_pcs_verify" + sfx).argtypes
         getattr(L, "hg_claims_verify_device" + sfx).argtypes = [vp] + getattr(L, "hg_claims_verify" + sfx).argtypes
     L.hg_pcs_free.argtypes, L.hg_pcs_free.restype = [vp], None
+    tail = [szp, sz, C.POINTER(cp), szp, sz, C.POINTER(ci), cp, sz]   # claim counts, n_queries, openings, lengths, n, results, reasons, reason_cap
+    L.hg_pcs_verify_device_batch.argtypes = [vp, C.POINTER(cp), u32p, sz, sz, C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u64p)] + tail
+    L.hg_claims_verify_batch.argtypes = [vp, C.POINTER(HgParams), C.POINTER(cp), sz, vp, sz, u64p, sz] + tail
 
 
 _lib = None
@@ -1277,6 +1280,73 @@ def pcs_verify(root, nvars, claims, proof, n_queries=0, log2_row=0, ctx=None):
 def claims_verify(params, root, claims, opening, n_queries=0, log2_row=0, ctx=None):
     """hg_claims_verify, with a context hg_claims_verify_device: an InputClaims against the root of hg_secrets_commit: (accepted, reason)."""
     return _claims_verify("", params, root, claims, opening, n_queries, log2_row, ctx)
+
+
+def _pcs_verify_batch(call, roots, proofs, reason_cap):
+    """One call of a batch entry of the commitment: call(roots, proofs, lens, n, results, reasons, reason_cap) -> [(accepted, reason)]"""
+    n = len(proofs)
+    m = max(n, 1)
+    rs = (C.c_char_p * m)(*[bytes(r) for r in roots])
+    ps = (C.c_char_p * m)(*[bytes(p) for p in proofs])
+    lens = (C.c_size_t * m)(*[len(p) for p in proofs])
+    res = (C.c_int * m)()
+    reasons = C.create_string_buffer(m * reason_cap)
+    if call(rs, ps, lens, n, res, reasons, reason_cap) < 0:
+        raise HgError(lib().hg_last_error().decode())
+    raw = reasons.raw
+    return [(res[i] == 0, raw[i * reason_cap:(i + 1) * reason_cap].split(b"\0", 1)[0].decode()) for i in range(n)]
+
+
+def pcs_verify_batch(ctx, roots, nvars, claims_list, proofs, n_queries=0, log2_row=0, reason_cap=256):
+    """hg_pcs_verify_device_batch: opening i against roots[i] and claims_list[i] (claims as Commitment.open takes them; an empty list
+    is allowed), every item of the shape nvars: a list of (accepted, reason), the decisions of pcs_verify for each item alone."""
+    if not (len(roots) == len(claims_list) == len(proofs)):
+        raise ValueError("pcs_verify_batch: one root and one claim list per opening")
+    m = max(len(proofs), 1)
+    nv = (C.c_uint32 * len(nvars))(*nvars)
+    arrays = [_pcs_claim_arrays(c) for c in claims_list]
+    tabs = (u32p * m)(*[C.cast(a[0], u32p) for a in arrays])
+    pts = (u64p * m)(*[_ptr(a[1]) for a in arrays])
+    vals = (u64p * m)(*[_ptr(a[2]) for a in arrays])
+    counts = (C.c_size_t * m)(*[len(c) for c in claims_list])
+    fn = lib().hg_pcs_verify_device_batch
+    return _pcs_verify_batch(lambda rs, ps, lens, n, res, reasons, cap: fn(_h(ctx), rs, nv, len(nvars), log2_row, tabs, pts, vals, counts, n_queries, ps, lens, n,
+                                                                            res, reasons, cap), roots, proofs, reason_cap)
+
+
+def _claims_batch_arrays(claims_list):
+    """a list of InputClaims (None: no claims) in the layout hg_verify_public_batch writes: (claims, claim_cap_each, points,
+    coord_cap_each, counts); point_off counts from the item's own block"""
+    m = max(len(claims_list), 1)
+    held = [c for c in claims_list if c is not None]
+    nc1 = max([c.n for c in held] + [1])
+    nco1 = max([sum(int(x.nvars) for x in c.claims[:c.n]) for c in held] + [1])
+    claims = (HgInputClaim * (m * nc1))()
+    points = np.zeros(2 * m * nco1, dtype=np.uint64)
+    counts = (C.c_size_t * m)()
+    for i, c in enumerate(claims_list):
+        if c is None:
+            continue
+        counts[i], off = c.n, 0
+        for j in range(c.n):
+            src, dst = c.claims[j], claims[i * nc1 + j]
+            dst.input, dst.nvars, dst.point_off = src.input, src.nvars, off
+            dst.value[0], dst.value[1] = src.value[0], src.value[1]
+            points[2 * (i * nco1 + off):2 * (i * nco1 + off + src.nvars)] = c.points[2 * src.point_off:2 * (src.point_off + src.nvars)]
+            off += src.nvars
+    return claims, nc1, points, nco1, counts
+
+
+def claims_verify_batch(ctx, params, roots, claims_list, openings, n_queries=0, log2_row=0, reason_cap=256):
+    """hg_claims_verify_batch: opening i against roots[i] and the InputClaims claims_list[i] (what verify_public_batch returns; None
+    stands for no claims), packed into the layout hg_verify_public_batch writes: a list of (accepted, reason), the decisions of
+    claims_verify for each item alone."""
+    if not (len(roots) == len(claims_list) == len(openings)):
+        raise ValueError("claims_verify_batch: one root and one InputClaims per opening")
+    claims, nc1, points, nco1, counts = _claims_batch_arrays(claims_list)
+    fn = lib().hg_claims_verify_batch
+    return _pcs_verify_batch(lambda rs, ps, lens, n, res, reasons, cap: fn(_h(ctx), C.byref(params), rs, log2_row, claims, nc1, _ptr(points), nco1, counts, n_queries,
+                                                                            ps, lens, n, res, reasons, cap), roots, openings, reason_cap)
 
 
 def pcs_verify_bn254(root, nvars, claims, proof, n_queries=0, log2_row=0, ctx=None):

@@ -102,6 +102,7 @@ struct GlAbi {
     typedef OpenClaim Open;
     typedef hg_input_claim Wire;
     typedef pcs::Claim PcsClaim;
+    typedef pcs::VerifyItem PcsItem;
     typedef E2 Elem;
     static bool canonical(const u64* w) { return w[0] < GL_P && w[1] < GL_P; }
     static Elem elem(const u64* w) { return e2(w[0], w[1]); }
@@ -152,6 +153,9 @@ struct GlAbi {
         } catch (const std::exception& e) {
             throw Error(std::string(who) + ": " + e.what());
         }
+    }
+    static std::vector<std::string> pcs_verify_batch(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const std::vector<PcsItem>& items, size_t Q) {
+        return pcs::verify_device_batch(who, ctx, sh, items, Q);
     }
 };
 
@@ -569,6 +573,73 @@ static int claims_verify_entry(const char* who, bool device, hg_ctx* ctx, const 
     (void)pcs::make_shape(who, nv.data(), nv.size(), log2_row);   // a shape error is reported ahead of a claim's
     secrets_claims<A>(who, p, claims, n, points, table, pts, vals);
     return pcs_verify_entry<A>(who, device, ctx, root, nv.data(), nv.size(), log2_row, table.data(), pts.data(), vals.data(), n, n_queries, opening, len);
+}
+
+// hg_pcs_verify_device_batch and hg_claims_verify_batch after their argument checks (every item's, ahead of anything enqueued: an
+// error of the call writes no output): the device pass with its errors given the entry's name, results and reasons
+template <class A>
+static int pcs_verify_batch_tail(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const uint8_t* const* roots, const std::vector<std::vector<typename A::PcsClaim>>& cl,
+                                 size_t Q, const uint8_t* const* proofs, const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap) {
+    const std::string w(who);
+    if (!n) return 0;
+    if (!ctx) throw Error(w + ": no context");
+    std::vector<typename A::PcsItem> items(n);
+    for (size_t i = 0; i < n; i++) items[i] = typename A::PcsItem{roots[i], &cl[i], proofs[i], lens[i]};
+    std::vector<std::string> why;
+    try {
+        why = A::pcs_verify_batch(who, ctx, sh, items, Q);
+    } catch (const std::exception& e) {
+        const std::string m = e.what();
+        throw Error(m.rfind(w, 0) == 0 ? m : w + ": " + m);
+    }
+    return write_results(why, results, reasons, reason_cap);
+}
+
+// hg_pcs_verify_device_batch*: item i's checks are pcs_verify_entry's, in its order, under the name "<entry>: index i"
+template <class A>
+static int pcs_verify_batch_entry(const char* who, hg_ctx* ctx, const uint8_t* const* roots, const uint32_t* nvars, size_t n_tables, size_t log2_row,
+                                  const uint32_t* const* tables, const uint64_t* const* points, const uint64_t* const* values, const size_t* n_claims, size_t n_queries,
+                                  const uint8_t* const* proofs, const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap) {
+    const std::string w(who);
+    if (!nvars || (n && (!roots || !n_claims || !proofs || !lens || !results))) throw Error(w + ": null argument");
+    const pcs::Shape sh = pcs::make_shape(who, nvars, n_tables, log2_row);
+    const size_t Q = pcs_queries(who, n_queries);
+    std::vector<std::vector<typename A::PcsClaim>> cl(n);
+    for (size_t i = 0; i < n; i++) {
+        const std::string at = w + ": index " + std::to_string(i);
+        const bool has = n_claims[i] != 0;
+        if (!roots[i] || (lens[i] && !proofs[i]) || (has && (!tables || !points || !values || !tables[i] || !points[i] || !values[i]))) throw Error(at + ": null argument");
+        cl[i] = pcs_claims<A>(at.c_str(), sh, has ? tables[i] : nullptr, has ? points[i] : nullptr, has ? values[i] : nullptr, n_claims[i]);
+    }
+    return pcs_verify_batch_tail<A>(who, ctx, sh, roots, cl, Q, proofs, lens, n, results, reasons, reason_cap);
+}
+
+// hg_claims_verify_batch*: the claim and point blocks as hg_verify_public_batch* writes them, item i's under claims_verify_entry's mapping
+template <class A>
+static int claims_verify_batch_entry(const char* who, hg_ctx* ctx, const hg_params* params, const uint8_t* const* roots, size_t log2_row, const void* claims,
+                                     size_t claim_cap_each, const uint64_t* points, size_t coord_cap_each, const size_t* n_claims, size_t n_queries,
+                                     const uint8_t* const* openings, const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap) {
+    const std::string w(who);
+    if (!params || (n && (!roots || !n_claims || !openings || !lens || !results))) throw Error(w + ": null argument");
+    Params p(*params);
+    const std::vector<uint32_t> nv = secrets_nvars(p);
+    const pcs::Shape sh = pcs::make_shape(who, nv.data(), nv.size(), log2_row);
+    const size_t Q = pcs_queries(who, n_queries);
+    std::vector<std::vector<typename A::PcsClaim>> cl(n);
+    for (size_t i = 0; i < n; i++) {
+        const std::string at = w + ": index " + std::to_string(i);
+        if (!roots[i] || (lens[i] && !openings[i]) || (n_claims[i] && (!claims || !points))) throw Error(at + ": null argument");
+        if (n_claims[i] > claim_cap_each) throw Error(at + ": " + std::to_string(n_claims[i]) + " claims in a block of " + std::to_string(claim_cap_each));
+        const typename A::Wire* in = static_cast<const typename A::Wire*>(claims) + i * claim_cap_each;
+        for (size_t j = 0; j < n_claims[i]; j++)
+            if (in[j].point_off > coord_cap_each || in[j].nvars > coord_cap_each - in[j].point_off)
+                throw Error(at + ": claim " + std::to_string(j) + " has its point outside the block of " + std::to_string(coord_cap_each) + " coordinates");
+        std::vector<uint32_t> table;
+        std::vector<uint64_t> pts, vals;
+        secrets_claims<A>(at.c_str(), p, in, n_claims[i], points ? points + A::WORDS * i * coord_cap_each : nullptr, table, pts, vals);
+        cl[i] = pcs_claims<A>(at.c_str(), sh, table.data(), pts.data(), vals.data(), n_claims[i]);
+    }
+    return pcs_verify_batch_tail<A>(who, ctx, sh, roots, cl, Q, openings, lens, n, results, reasons, reason_cap);
 }
 
 extern "C" {
@@ -1833,6 +1904,18 @@ int hg_claims_verify(const hg_params* params, const uint8_t root[32], size_t log
 int hg_claims_verify_device(hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points,
                             size_t n_queries, const uint8_t* opening, size_t len) {
     HG_ENTRY(claims_verify_entry<GlAbi>("hg_claims_verify_device", true, ctx, params, root, log2_row, claims, n, points, n_queries, opening, len))
+}
+
+int hg_pcs_verify_device_batch(hg_ctx* ctx, const uint8_t* const* roots, const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* const* tables,
+                               const uint64_t* const* points, const uint64_t* const* values, const size_t* n_claims, size_t n_queries, const uint8_t* const* proofs,
+                               const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap) {
+    HG_ENTRY(pcs_verify_batch_entry<GlAbi>("hg_pcs_verify_device_batch", ctx, roots, nvars, n_tables, log2_row, tables, points, values, n_claims, n_queries, proofs, lens, n, results, reasons, reason_cap))
+}
+
+int hg_claims_verify_batch(hg_ctx* ctx, const hg_params* params, const uint8_t* const* roots, size_t log2_row, const void* claims, size_t claim_cap_each,
+                           const uint64_t* points, size_t coord_cap_each, const size_t* n_claims, size_t n_queries, const uint8_t* const* openings, const size_t* lens,
+                           size_t n, int* results, char* reasons, size_t reason_cap) {
+    HG_ENTRY(claims_verify_batch_entry<GlAbi>("hg_claims_verify_batch", ctx, params, roots, log2_row, claims, claim_cap_each, points, coord_cap_each, n_claims, n_queries, openings, lens, n, results, reasons, reason_cap))
 }
 
 // ---- the same entries over bn256::Fr (pcs_bn254.hpp): an element crosses as 4 canonical words

@@ -2,10 +2,13 @@
 // NTT, one Keccak-f[1600] state per thread for the column hashes and the tree, the E x F row combinations of an opening through
 // the deferred-reduction accumulators, a gather of the opened columns. The handle owns the raw and the encoded matrix in HBM.
 // The verifier of an opening (verify_device) reuses the encoding and the leaf hash and adds five kernels of its own.
+// The verifier of a run of openings (verify_device_batch) runs the same five kernels once over a group, driven by a member table.
+#include <omp.h>
 #include "pcs.hpp"
 #include "prover.hpp"
 #include "gl_wide.hpp"
 #include "pcs_keccak.hpp"
+#include "verifier_batch.hpp"
 
 namespace hg {
 namespace pcs {
@@ -231,6 +234,150 @@ __global__ __launch_bounds__(PCS_TPB) void k_pcsv_query(const u64* __restrict__ 
         if (!e2_eq(sq[i], e2(enc[2 * i * N + j], enc[(2 * i + 1) * N + j]))) { cell_min(cells + 2, key + 1 + i); return; }
 }
 
+// ---- the verifier of a run of openings (verify_device_batch): the five kernels above with a member in front of every index. The
+// members of a group share the shape and Q; what differs by member (its claim count, where its opening, u, columns, encoded rows,
+// jobs and weights lie) is read from its descriptor, never derived from a flat id. Grids over queries stay one-dimensional.
+struct VbMember {
+    u64 proof, u, cols, enc_row;               // word offsets of its opening in the set, of its u and of its columns; its first row of enc
+    u64 n, claim0, job0;                       // its claims; the claims and the jobs (claims + 1 each) of the members before it
+    u64 root_at, jobs_at, y_at, z_at, w_at;    // byte offsets in the group's staged copy: root, job descriptors, values, low coordinates, weights
+};
+struct VbGroup { u64 G, Q, R, q_words; int c, depth; };
+
+// blockIdx.y = the member, its words grid-strided over blockIdx.x: k_pcsv_canon on its own opening, into its own u, columns and enc
+// rows; cells[3m] = the lowest byte offset, within its opening, of a word that is not below p
+__global__ __launch_bounds__(PCS_TPB) void k_pcsvb_canon(const u64* __restrict__ set, const VbMember* __restrict__ mem, VbGroup g, u64* __restrict__ u,
+                                                         u64* __restrict__ cols, u64* __restrict__ enc, u64* __restrict__ cells) {
+    const VbMember M = mem[blockIdx.y];
+    const int c = g.c;
+    const size_t Q = g.Q, R = g.R, u_words = (M.n + 1) << (c + 1), total = u_words + Q * R, Cm = ((size_t)1 << c) - 1;
+    const u64* proof = set + M.proof;
+    u64* mu = u + M.u;
+    u64* mcols = cols + M.cols;
+    u64* menc = enc + (M.enc_row << (c + 2));
+    u64 bad = PCSV_NONE;
+    for (size_t i = (size_t)blockIdx.x * PCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * PCS_TPB) {
+        size_t at = i;
+        if (i >= u_words) { const size_t k = i - u_words, q = k / R; at = u_words + q * g.q_words + (k - q * R); }
+        const u64 v = __builtin_bswap64(proof[at]);
+        if (v >= GL_P && 8 * at < bad) bad = 8 * at;
+        if (i < u_words) {
+            const size_t e = i >> 1, row = 2 * (e >> c) + (i & 1);
+            mu[i] = v;
+            menc[(row << (c + 2)) + (e & Cm)] = v;
+        } else {
+            mcols[i - u_words] = v;
+        }
+    }
+    if (bad != PCSV_NONE) cell_min(cells + 3 * blockIdx.y, bad);
+}
+
+// One workgroup per (member, claim): block b belongs to the last member whose claim0 is <= b (a member without claims owns no block).
+// cells[3m + 1] = the member's lowest failing claim.
+__global__ __launch_bounds__(PCS_TPB) void k_pcsvb_eval(const VbMember* __restrict__ mem, unsigned G, int c, const u64* __restrict__ u, const char* __restrict__ stage,
+                                                        u64* __restrict__ cells) {
+    __shared__ E2 part[PCS_TPB];
+    unsigned lo = 0, hi = G;
+    while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].claim0 <= blockIdx.x) lo = mid; else hi = mid; }
+    const VbMember M = mem[lo];
+    const size_t C = (size_t)1 << c, i = blockIdx.x - M.claim0;
+    if (i >= M.n) return;   // (uniform over the workgroup; the grid has exactly the claims of the group)
+    const E2* z = reinterpret_cast<const E2*>(stage + M.z_at) + i * (size_t)c;
+    const E2* ui = reinterpret_cast<const E2*>(u + M.u) + (i + 1) * C;
+    const int lob = c < 8 ? c : 8;
+    E2 f = e2_one();
+    for (int b = 0; b < lob; b++) f = e2_mul(f, (threadIdx.x >> b) & 1 ? z[b] : e2_sub(e2_one(), z[b]));
+    E2 s = e2_zero();
+    for (size_t x = threadIdx.x; x < C; x += PCS_TPB) {
+        E2 gq = f;
+        for (int b = 8; b < c; b++) gq = e2_mul(gq, (x >> b) & 1 ? z[b] : e2_sub(e2_one(), z[b]));
+        s = e2_add(s, e2_mul(ui[x], gq));
+    }
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = PCS_TPB / 2; h >= 1; h >>= 1) {
+        if (threadIdx.x < h) part[threadIdx.x] = e2_add(part[threadIdx.x], part[threadIdx.x + h]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && !e2_eq(part[0], reinterpret_cast<const E2*>(stage + M.y_at)[i])) cell_min(cells + 3 * lo + 1, (u64)i);
+}
+
+// One thread per (member m, query q), id = m Q + q: the leaf hash of its R column words -> leaves[id]
+__global__ __launch_bounds__(PCS_TPB) void k_pcsvb_leaf(const VbMember* __restrict__ mem, VbGroup g, const u64* __restrict__ cols, u64* __restrict__ leaves) {
+    const size_t id = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
+    if (id >= g.G * g.Q) return;
+    const size_t m = id / g.Q, q = id - m * g.Q;
+    u64 a[25];
+    leaf_absorb(cols + mem[m].cols + q * g.R, 1, g.R, a);
+    u64* out = leaves + 4 * id;
+    out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
+}
+
+// One thread per (member, query, job): member m owns the ids from Q job0_m; within it id - Q job0_m = q (n_m + 1) + job, as in
+// k_pcsv_dots, and s[id] is where k_pcsvb_query reads it
+__global__ __launch_bounds__(PCS_TPB) void k_pcsvb_dots(const VbMember* __restrict__ mem, VbGroup g, size_t total, const u64* __restrict__ cols,
+                                                        const char* __restrict__ stage, E2* __restrict__ s) {
+    const size_t id = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
+    if (id >= total) return;
+    unsigned lo = 0, hi = (unsigned)g.G;
+    while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].job0 * g.Q <= id) lo = mid; else hi = mid; }
+    const VbMember M = mem[lo];
+    const size_t local = id - M.job0 * g.Q, njobs = M.n + 1, q = local / njobs;
+    const CombineDesc job = reinterpret_cast<const CombineDesc*>(stage + M.jobs_at)[local - q * njobs];
+    const u64* src = cols + M.cols + q * g.R + job.row0;
+    const E2* wq = reinterpret_cast<const E2*>(stage + M.w_at) + job.woff;
+    u64 s0 = 0, s1 = 0;
+    for (u64 r0 = 0; r0 < job.nrows; r0 += COMBINE_CHUNK) {
+        const u64 r1 = r0 + COMBINE_CHUNK < job.nrows ? r0 + COMBINE_CHUNK : job.nrows;
+        WAcc A = wacc_zero(), B = wacc_zero();
+        for (u64 r = r0; r < r1; r++) {
+            const u64 x = src[r];
+            const E2 wr = wq[r];
+            wmac2(A, x, wr.c0, B, x, wr.c1);
+        }
+        s0 = gl_add(s0, wreduce(A));
+        s1 = gl_add(s1, wreduce(B));
+    }
+    s[id] = e2(s0, s1);
+}
+
+// One thread per (member m, query q), id = m Q + q, once the host has every member's column indices (js[id]): k_pcsv_query on the
+// member's own opening, root, s entries and enc rows. cells[3m + 2] = the member's lowest q (n_m + 2) + kind that failed.
+__global__ __launch_bounds__(PCS_TPB) void k_pcsvb_query(const u64* __restrict__ set, const VbMember* __restrict__ mem, VbGroup g, const u64* __restrict__ leaves,
+                                                         const E2* __restrict__ s, const u64* __restrict__ enc, const u64* __restrict__ js,
+                                                         const char* __restrict__ stage, u64* __restrict__ cells) {
+    const size_t id = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
+    if (id >= g.G * g.Q) return;
+    const size_t m = id / g.Q, q = id - m * g.Q;
+    const VbMember M = mem[m];
+    const int depth = g.depth;
+    const size_t N = (size_t)1 << depth, j = js[id], n = M.n, u_words = (n + 1) << (g.c + 1);
+    const u64* sib = set + M.proof + u_words + q * g.q_words + g.R;
+    const u64* root = reinterpret_cast<const u64*>(stage + M.root_at);
+    u64 h0 = leaves[4 * id], h1 = leaves[4 * id + 1], h2 = leaves[4 * id + 2], h3 = leaves[4 * id + 3];
+    for (int l = 0; l < depth; l++) {
+        const bool right = (j >> l) & 1;   // this node is the right child
+        const u64 t0 = sib[4 * l], t1 = sib[4 * l + 1], t2 = sib[4 * l + 2], t3 = sib[4 * l + 3];
+        u64 a[25];
+        a[0] = 1;
+        a[1] = right ? t0 : h0; a[2] = right ? t1 : h1; a[3] = right ? t2 : h2; a[4] = right ? t3 : h3;
+        a[5] = right ? h0 : t0; a[6] = right ? h1 : t1; a[7] = right ? h2 : t2; a[8] = right ? h3 : t3;
+        a[9] = 0x01;
+#pragma unroll
+        for (int k = 10; k < 25; k++) a[k] = 0;
+        a[RATE_WORDS - 1] = 0x8000000000000000ull;
+        keccak_f(a);
+        h0 = a[0]; h1 = a[1]; h2 = a[2]; h3 = a[3];
+    }
+    u64* cell = cells + 3 * m + 2;
+    const size_t key = q * (n + 2);
+    if (h0 != root[0] || h1 != root[1] || h2 != root[2] || h3 != root[3]) { cell_min(cell, key); return; }
+    const E2* sq = s + M.job0 * g.Q + q * (n + 1);
+    const u64* menc = enc + (M.enc_row << depth);
+    for (size_t i = 0; i <= n; i++)
+        if (!e2_eq(sq[i], e2(menc[2 * i * N + j], menc[(2 * i + 1) * N + j]))) { cell_min(cell, key + 1 + i); return; }
+}
+
 Commitment::~Commitment() {
     if (d_rows) (void)hipFree(d_rows);
     if (d_M) (void)hipFree(d_M);
@@ -439,6 +586,238 @@ std::string verify_device(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], 
         return kind == 0 ? reason_merkle(q) : kind == 1 ? reason_proximity(q) : reason_claim(kind - 2, q);
     }
     return "";
+}
+
+// hg_pcs_verify_device_batch. The items whose length is right are cut into groups (the option verify_batch_group, VB_PCS_BUDGET,
+// the rows ntt_batch takes on its four-step path). A group: its openings gathered into a page-locked set on the host threads and
+// copied on the upload stream; every member's transcript start, rho powers and weight tables written into one staged copy, one
+// member a task; the index-free kernels, one launch each over all members; the members' u_i hashed on the host threads meanwhile;
+// all indices up, the query kernel, three cells a member down: one synchronisation a group. The next group's openings are gathered
+// and copied into the other set before that synchronisation, under this group's kernels.
+std::vector<std::string> verify_device_batch(const char* who_c, hg_ctx* ctx, const Shape& sh, const std::vector<VerifyItem>& items, size_t Q) {
+    const std::string who(who_c);
+    const size_t C = sh.C(), N = sh.N(), R = sh.R;
+    const int depth = sh.depth();
+    const size_t q_words = R + 4 * (size_t)depth;
+    const bool four_step = depth >= 8 && depth <= 16;
+    std::vector<std::string> why(items.size());
+    std::vector<size_t> good;   // the items that reach the device
+    for (size_t i = 0; i < items.size(); i++) {
+        why[i] = length_reason(sh, items[i].claims->size(), Q, items[i].len);
+        if (why[i].empty()) good.push_back(i);
+    }
+    if (good.empty()) return why;
+    // what a member takes: its opening in a set; u, columns, enc rows (and the scratch), leaves, s, indices in the arena
+    auto rows_of = [](size_t n) { return 2 * (n + 1); };
+    auto bytes_of = [&](size_t n, size_t len) {
+        return len + 8 * (2 * C * (n + 1) + Q * R + rows_of(n) * N * (four_step ? 2 : 1) + 5 * Q) + 16 * Q * (n + 1);
+    };
+    size_t cap = VB_MAX_GROUP;
+    if (ctx->verify_batch_group > 0) cap = std::min<size_t>(cap, (size_t)ctx->verify_batch_group);
+    constexpr size_t NTT_ROWS = 65535;   // ntt_batch: the batch is the y extent of its four-step grids
+    std::vector<std::pair<size_t, size_t>> groups;   // [first, last) of good
+    for (size_t a = 0; a < good.size();) {
+        size_t b = a, bytes = 0, rows = 0;
+        while (b < good.size() && b - a < cap) {
+            const size_t n = items[good[b]].claims->size();
+            if (b > a && (bytes + bytes_of(n, items[good[b]].len) > VB_PCS_BUDGET || (four_step && rows + rows_of(n) > NTT_ROWS))) break;
+            bytes += bytes_of(n, items[good[b]].len);
+            rows += rows_of(n);
+            b++;
+        }
+        groups.push_back({a, b});
+        a = b;
+    }
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    VerifyBatchBufs* B = batch_bufs(ctx);
+    hipStream_t st = ctx->stream;
+    std::vector<u64> hj, cells;   // (declared ahead of the guard: copies of them may be queued when it drains)
+    struct Drain {   // every way out, an error included: no copy of a dead host buffer, no kernel on the arena or a set left behind
+        hipStream_t a, b;
+        ~Drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); }
+    } drain{st, B->up};
+    hip_check(hipStreamSynchronize(st), (who + ": synchronise").c_str());   // (the arena is reset below)
+    [[maybe_unused]] const int nthr = std::max(1, hg_omp_threads());        // (the device pass of hipcc ignores the pragmas)
+    const int cls = ctx->prof_class("pcs_verify_batch", false);
+    ctx->prof_stream = st;
+
+    struct Member { size_t idx, n, nw; FsTranscript tr; std::string error; };
+    // the openings of group g into set g & 1, at word offsets that the descriptors repeat
+    auto proof_offsets = [&](size_t g) {
+        std::vector<size_t> off;
+        size_t at = 0;
+        for (size_t x = groups[g].first; x < groups[g].second; x++) { off.push_back(at); at += items[good[x]].len / 8; }
+        off.push_back(at);
+        return off;
+    };
+    auto stage = [&](size_t g) {
+        const std::vector<size_t> off = proof_offsets(g);
+        std::vector<BatchBlob> blobs;
+        for (size_t x = groups[g].first; x < groups[g].second; x++) blobs.push_back(BatchBlob{items[good[x]].proof, items[good[x]].len, off[x - groups[g].first]});
+        batch_stage_blobs(B, (int)(g & 1), blobs, off.back(), nthr, who_c);
+    };
+    const bool times = hg_times("pcs");   // HG_TIMES=pcs: where a group's wall clock goes, on stderr
+    double t_stage = omp_get_wtime();
+    stage(0);
+    t_stage = omp_get_wtime() - t_stage;
+    for (size_t g = 0; g < groups.size(); g++) {
+        const double t0 = omp_get_wtime();
+        const size_t G = groups[g].second - groups[g].first;
+        const int set = (int)(g & 1);
+        std::vector<Member> mem(G);
+        std::vector<VbMember> desc(G);
+        const std::vector<size_t> poff = proof_offsets(g);
+        // the layout of the staged copy: the descriptors, then every member's block, and of the arena buffers
+        size_t at = (G * sizeof(VbMember) + 15) & ~(size_t)15, u_at = 0, row_at = 0, claim_at = 0;
+        for (size_t m = 0; m < G; m++) {
+            Member& x = mem[m];
+            const VerifyItem& it = items[good[groups[g].first + m]];
+            x.idx = good[groups[g].first + m];
+            x.n = it.claims->size();
+            x.nw = R;
+            for (const Claim& cl : *it.claims) x.nw += (size_t)1 << (sh.nvars[cl.table] - sh.c);
+            VbMember& d = desc[m];
+            d.proof = poff[m]; d.u = u_at; d.cols = m * Q * R; d.enc_row = row_at;
+            d.n = x.n; d.claim0 = claim_at; d.job0 = claim_at + m;
+            d.root_at = at;
+            d.jobs_at = d.root_at + 32;
+            d.y_at = d.jobs_at + (((x.n + 1) * sizeof(CombineDesc) + 15) & ~(size_t)15);
+            d.z_at = d.y_at + x.n * sizeof(E2);
+            d.w_at = d.z_at + x.n * (size_t)sh.c * sizeof(E2);
+            at = d.w_at + x.nw * sizeof(E2);
+            u_at += 2 * C * (x.n + 1);
+            row_at += rows_of(x.n);
+            claim_at += x.n;
+        }
+        const size_t stage_bytes = at, u_total = u_at, rows = row_at, claims_total = claim_at, jobs_total = claim_at + G;
+        char* h_stage = batch_desc_host(B, stage_bytes);   // (the previous group's copy of it was waited for)
+        memcpy(h_stage, desc.data(), G * sizeof(VbMember));
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
+        for (long long mq = 0; mq < (long long)G; mq++) {
+            Member& x = mem[mq];
+            try {
+                const VerifyItem& it = items[x.idx];
+                const VbMember& d = desc[mq];
+                x.tr = start_transcript(sh, it.root, *it.claims, Q);
+                const std::vector<E2> rho = rho_powers(x.tr.squeeze(), R);
+                memcpy(h_stage + d.root_at, it.root, 32);
+                CombineDesc* hd = reinterpret_cast<CombineDesc*>(h_stage + d.jobs_at);
+                E2* hy = reinterpret_cast<E2*>(h_stage + d.y_at);
+                E2* hz = reinterpret_cast<E2*>(h_stage + d.z_at);
+                E2* hw = reinterpret_cast<E2*>(h_stage + d.w_at);
+                hd[0].row0 = 0; hd[0].nrows = R; hd[0].woff = 0;
+                memcpy(hw, rho.data(), R * sizeof(E2));
+                size_t off = R;
+                for (size_t i = 0; i < x.n; i++) {
+                    const Claim& cl = (*it.claims)[i];
+                    const std::vector<E2> w = eq_table(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
+                    hd[i + 1].row0 = sh.off[cl.table]; hd[i + 1].nrows = w.size(); hd[i + 1].woff = off;
+                    memcpy(hw + off, w.data(), w.size() * sizeof(E2));
+                    off += w.size();
+                    hy[i] = cl.value;
+                    memcpy(hz + i * (size_t)sh.c, cl.point.data(), (size_t)sh.c * sizeof(E2));
+                }
+            } catch (const std::exception& e) { x.error = e.what(); }
+        }
+        for (const Member& x : mem)
+            if (!x.error.empty()) throw Error(who + ": index " + std::to_string(x.idx) + ": " + x.error);
+        const double t1 = omp_get_wtime();
+        ctx->arena_reset();
+        u64 *d_u, *d_cols, *d_enc, *d_scratch = nullptr, *d_W, *d_leaves, *d_js, *d_cells;
+        char* d_stage;
+        E2* d_s;
+        try {
+            d_stage = ctx->alloc_n<char>(stage_bytes);
+            d_u = ctx->alloc_n<u64>(u_total);
+            d_cols = ctx->alloc_n<u64>(G * Q * R);
+            d_enc = ctx->alloc_n<u64>(rows * N);
+            if (four_step) d_scratch = ctx->alloc_n<u64>(rows * N);
+            d_W = ctx->alloc_n<u64>(N);
+            d_leaves = ctx->alloc_n<u64>(4 * G * Q);
+            d_s = ctx->alloc_n<E2>(Q * jobs_total);
+            d_js = ctx->alloc_n<u64>(G * Q);
+            d_cells = ctx->alloc_n<u64>(3 * G);
+        } catch (const std::exception& e) {
+            throw Error(who + ": the context's arena cannot hold " + (G == 1 ? "the opening at index " + std::to_string(mem[0].idx) : "a group of " + std::to_string(G) + " openings: lower verify_batch_group") +
+                        " (" + e.what() + ")");
+        }
+        const u64* d_set = B->d_in[set];
+        const VbMember* d_mem = reinterpret_cast<const VbMember*>(d_stage);
+        const VbGroup vg{(u64)G, (u64)Q, (u64)R, (u64)q_words, sh.c, depth};
+        size_t words_max = 0, nw_total = 0;
+        for (const Member& x : mem) { words_max = std::max(words_max, 2 * C * (x.n + 1) + Q * R); nw_total += x.nw; }
+        hip_check(hipStreamWaitEvent(st, B->ev[set], 0), "hipStreamWaitEvent");   // the set's openings are up
+        hip_check(hipMemcpyAsync(d_stage, h_stage, stage_bytes, hipMemcpyHostToDevice, st), "upload claims");
+        hip_check(hipMemsetAsync(d_cells, 0xff, 3 * G * 8, st), "memset");
+        hip_check(hipMemsetAsync(d_enc, 0, rows * N * 8, st), "memset");
+        ctx->prof_begin(cls, (double)(u_total + G * Q * R) * 24);
+        k_pcsvb_canon<<<dim3((unsigned)std::min<size_t>(blocks_for(words_max), 1024), (unsigned)G), PCS_TPB, 0, st>>>(d_set, d_mem, vg, d_u, d_cols, d_enc, d_cells);
+        ctx->prof_end();
+        if (claims_total) {
+            ctx->prof_begin(cls, (double)claims_total * C * 16);
+            k_pcsvb_eval<<<(unsigned)claims_total, PCS_TPB, 0, st>>>(d_mem, (unsigned)G, sh.c, d_u, d_stage, d_cells);
+            ctx->prof_end();
+        }
+        ctx->prof_begin(cls, (double)rows * N * 32);
+        dev::powers_table(st, d_W, root_of_unity(depth), N);
+        dev::ntt_batch(st, d_enc, depth, rows, d_W, 1, d_scratch);
+        ctx->prof_end();
+        ctx->prof_begin(cls, (double)G * Q * R * 8);
+        k_pcsvb_leaf<<<blocks_for(G * Q), PCS_TPB, 0, st>>>(d_mem, vg, d_cols, d_leaves);
+        ctx->prof_end();
+        ctx->prof_begin(cls, (double)Q * nw_total * 24);
+        k_pcsvb_dots<<<blocks_for(Q * jobs_total), PCS_TPB, 0, st>>>(d_mem, vg, Q * jobs_total, d_cols, d_stage, d_s);
+        ctx->prof_end();
+        // the host's share, beside the kernels: every member's u_i into its transcript, its column indices out of it
+        const double t2 = omp_get_wtime();
+        hj.assign(G * Q, 0);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
+        for (long long mq = 0; mq < (long long)G; mq++) {
+            Member& x = mem[mq];
+            try {
+                const uint8_t* proof = items[x.idx].proof;
+                const size_t u_words = 2 * C * (x.n + 1);
+                std::vector<u64> words(u_words);
+                for (size_t i = 0; i < u_words; i++) { u64 v; memcpy(&v, proof + 8 * i, 8); words[i] = __builtin_bswap64(v); }
+                absorb_words(x.tr, words.data(), u_words);
+                const std::vector<size_t> js = squeeze_indices(x.tr, N, Q);
+                for (size_t q = 0; q < Q; q++) hj[(size_t)mq * Q + q] = js[q];
+            } catch (const std::exception& e) { x.error = e.what(); }
+        }
+        for (const Member& x : mem)
+            if (!x.error.empty()) throw Error(who + ": index " + std::to_string(x.idx) + ": " + x.error);
+        const double t3 = omp_get_wtime();
+        hip_check(hipMemcpyAsync(d_js, hj.data(), G * Q * 8, hipMemcpyHostToDevice, st), "upload column indices");
+        ctx->prof_begin(cls, (double)G * Q * 32.0 * depth + (double)Q * jobs_total * 48.0);
+        k_pcsvb_query<<<blocks_for(G * Q), PCS_TPB, 0, st>>>(d_set, d_mem, vg, d_leaves, d_s, d_enc, d_js, d_stage, d_cells);
+        ctx->prof_end();
+        cells.assign(3 * G, 0);
+        hip_check(hipMemcpyAsync(cells.data(), d_cells, 3 * G * 8, hipMemcpyDeviceToHost, st), "download verdicts");
+        const double t4 = omp_get_wtime();
+        if (g + 1 < groups.size()) stage(g + 1);   // into the other set, under this group's kernels
+        const double t5 = omp_get_wtime();
+        hip_check(hipStreamSynchronize(st), (who + ": sync").c_str());
+        if (times)
+            fprintf(stderr, "[hg pcs] group %zu of %zu members: gather and copy of its openings %.2f ms, transcripts and weights %.2f, enqueue %.2f, hash %.2f, "
+                            "query enqueue %.2f, next group's gather %.2f, wait %.2f\n", g, G, t_stage * 1e3, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3,
+                    (t5 - t4) * 1e3, (omp_get_wtime() - t5) * 1e3);
+        t_stage = t5 - t4;
+        hip_check(hipGetLastError(), (who + ": launch").c_str());
+        ctx->prof_collect();
+        // per member, the host's order: a non-canonical word, the lowest claim whose evaluation fails, the lowest failing query
+        for (size_t m = 0; m < G; m++) {
+            const u64* cm = cells.data() + 3 * m;
+            const size_t n = mem[m].n;
+            std::string& out = why[mem[m].idx];
+            if (cm[0] != PCSV_NONE) out = reason_noncanonical((size_t)cm[0]);
+            else if (cm[1] != PCSV_NONE) out = reason_evaluation((size_t)cm[1]);
+            else if (cm[2] != PCSV_NONE) {
+                const size_t q = (size_t)(cm[2] / (n + 2)), kind = (size_t)(cm[2] % (n + 2));
+                out = kind == 0 ? reason_merkle(q) : kind == 1 ? reason_proximity(q) : reason_claim(kind - 2, q);
+            }
+        }
+    }
+    return why;
 }
 
 }  // namespace pcs

@@ -81,6 +81,11 @@ std::string verify(const Shape& sh, const uint8_t root[32], const std::vector<Cl
 // hg_pcs_verify_device (pcs.hip): the same decision and the same reason with the table-sized work on the context's stream; the
 // Fiat-Shamir hash over the u_i stays on the host and runs beside the kernels. Throws an Error if the arena cannot hold the opening
 std::string verify_device(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof, size_t len);
+// hg_pcs_verify_device_batch (pcs.hip): a run of openings of one shape and one Q, each with its own root and claims, in device passes
+// of a group of openings each; why[i] is what verify_device returns for item i alone. Throws an Error
+// naming `who` if the arena cannot hold a group
+struct VerifyItem { const uint8_t* root; const std::vector<Claim>* claims; const uint8_t* proof; size_t len; };
+std::vector<std::string> verify_device_batch(const char* who, hg_ctx* ctx, const Shape& sh, const std::vector<VerifyItem>& items, size_t Q);
 
 // ---- what both forms of the verifier share (pcs.cpp): the length check, the transcript up to the column indices, the reasons
 std::string length_reason(const Shape& sh, size_t n_claims, size_t Q, size_t len);   // "" if the length is the opening's

@@ -368,6 +368,21 @@ void batch_stage_instances(VerifyBatchBufs* B, int s, const std::vector<const In
     stage_copy(B, s, pieces, np * 2 * kn, nthr, w);
 }
 
+void batch_stage_blobs(VerifyBatchBufs* B, int s, const std::vector<BatchBlob>& blobs, size_t total_words, [[maybe_unused]] int nthr, const char* who) {
+    const std::string w(who);
+    stage_set(B, s, std::max<size_t>(total_words, 1), w);
+    constexpr size_t PIECE = (size_t)2 << 20;
+    struct BytePiece { char* dst; const uint8_t* src; size_t n; };
+    std::vector<BytePiece> pieces;
+    for (const BatchBlob& b : blobs)
+        for (size_t o = 0; o < b.bytes; o += PIECE) pieces.push_back(BytePiece{reinterpret_cast<char*>(B->h_in[s] + b.word_off) + o, b.p + o, std::min(PIECE, b.bytes - o)});
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::max(1, std::min<int>(nthr, (int)pieces.size())))
+    for (long long q = 0; q < (long long)pieces.size(); q++) memcpy(pieces[q].dst, pieces[q].src, pieces[q].n);
+    if (total_words) hip_check(hipMemcpyAsync(B->d_in[s], B->h_in[s], total_words * sizeof(u64), hipMemcpyHostToDevice, B->up), (w + ": upload openings").c_str());
+    hip_check(hipEventRecord(B->ev[s], B->up), "hipEventRecord");
+    B->recorded[s] = true;
+}
+
 void verify_batch_drop(hg_ctx* ctx) {
     if (!ctx->verify_batch) return;
     auto* b = static_cast<VerifyBatchBufs*>(ctx->verify_batch);

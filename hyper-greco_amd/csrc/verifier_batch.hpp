@@ -41,6 +41,10 @@ struct BatchInputs {
 // about five times its inputs, 0.13 GB at n=32768 k=16)
 constexpr size_t VB_INPUT_BUDGET = (size_t)1 << 30, VB_TABLE_BUDGET = (size_t)4 << 30;
 constexpr size_t VB_MAX_GROUP = 64;
+// hg_pcs_verify_device_batch: what the members of one group may take in all - each one's opening in a set and its u, columns,
+// encoded rows and NTT scratch in the arena (about 19 MB a member at n=32768 k=16: opening 3.3, u 1.5, columns 1.7, enc and the
+// scratch 6.3 each; 64 members: 1.2 GB)
+constexpr size_t VB_PCS_BUDGET = (size_t)2 << 30;
 
 // dedup keys of the group merge: a job's descriptor with absolute chain offsets
 typedef std::vector<u64> Key;
@@ -59,5 +63,10 @@ void batch_stage_inputs(VerifyBatchBufs* B, int set, const std::vector<const Wit
 // the same for the public instances of proofs [i0, i1) (hg_verify_public_batch): each as it is, a then ct0, kn = k * n signed words each
 void batch_stage_instances(VerifyBatchBufs* B, int set, const std::vector<const Instance*>& insts, size_t i0, size_t i1, size_t kn, int nthr,
                            const char* who);
+
+// the same for a run of byte strings (hg_pcs_verify_device_batch: the openings of a group): blob i, a whole number of words, lands at
+// word word_off[i] of the set, which holds total_words
+struct BatchBlob { const uint8_t* p; size_t bytes; size_t word_off; };
+void batch_stage_blobs(VerifyBatchBufs* B, int set, const std::vector<BatchBlob>& blobs, size_t total_words, int nthr, const char* who);
 
 }  // namespace hg

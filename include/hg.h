@@ -77,8 +77,8 @@ void hg_destroy(hg_ctx* ctx);
  *                 addresses only, because every challenge is known up front; a values object refilled by hg_witness_gen_into
  *                 keeps its graph; up to HG_GRAPH_ENTRIES (8) graphs per context, each with a private workspace)
  *   "verify_batch_group"  the most proofs one device pass of hg_verify_device_batch, hg_verify_device_batch_bn254,
- *                 hg_verify_public_batch or hg_verify_public_batch_bn254 holds
- *                 (default 0: sized from the memory budget, at most 64)
+ *                 hg_verify_public_batch or hg_verify_public_batch_bn254 holds, and the most openings one of
+ *                 hg_pcs_verify_device_batch or hg_claims_verify_batch (default 0: sized from the memory budget, at most 64)
  * Returns 0, or -1 for an unknown name. */
 int hg_set_option(hg_ctx* ctx, const char* name, int64_t value);
 
@@ -389,6 +389,41 @@ int hg_claims_verify(const hg_params* params, const uint8_t root[32], size_t log
                      size_t n_queries, const uint8_t* opening, size_t len);
 int hg_claims_verify_device(hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n,
                             const uint64_t* points, size_t n_queries, const uint8_t* opening, size_t len);
+
+/* hg_pcs_verify_device_batch: hg_pcs_verify_device for a run of n openings of ONE shape (nvars, n_tables, log2_row) and one n_queries.
+ *   Item i has its own root roots[i] (32 bytes), its own claims - n_claims[i] of them, 0 allowed; tables[i], points[i], values[i]
+ *   laid out as hg_pcs_verify_device takes them, and may be NULL where n_claims[i] == 0 - and its opening proofs[i] of lens[i] bytes.
+ *   results[i] = 0 accepted / 1 rejected; reasons may be NULL, else the slot at reasons + i*reason_cap receives the item's reason,
+ *   NUL-terminated and cut to reason_cap bytes, "" where it is accepted. Decision and reason are exactly hg_pcs_verify_device's (so
+ *   hg_pcs_verify's) for that item alone, also where several checks fail at once and for a wrong length, which is rejected per item
+ *   and never reaches the device; byte offsets in reasons count from the item's own opening. Returns the number of rejected items;
+ *   n == 0 returns 0 and writes nothing.
+ *   The pass: the items whose length is right are cut into groups - at most 64 or the context option "verify_batch_group", a byte
+ *   budget of 2 GiB (an item takes about 19 MB at n=32768 k=16), and the 65535 rows the batched NTT takes at once. Per group the
+ *   host threads gather the openings into a page-locked set (copied on the context's upload stream) and write every member's
+ *   transcript start, rho powers and eq weight tables into one staged copy; the kernels of hg_pcs_verify_device then run once over all
+ *   members, driven by a member descriptor table - one workgroup per (member, claim), one thread per (member, query) and per (member,
+ *   query, job), one batched NTT over all members' u rows - while the host threads hash each member's u_i into its transcript; one
+ *   copy of all column indices, one query kernel, three result words a member: one synchronisation a group. The next group's
+ *   openings are gathered and copied under the kernels of the current one.
+ *   -1 (nothing is written; hg_last_error begins with the function's name and gives "index i" where an item is at fault; every
+ *   item's arguments are checked before anything is enqueued): a null argument or null element, a shape, log2_row or n_queries
+ *   outside the limits of hg_pcs_verify, n_claims[i] above 4096, a table index out of range, a non-canonical coordinate or value, a
+ *   null context ("hg_pcs_verify_device_batch: no context"), a group the context's arena cannot hold. It uses the context's arena
+ *   and batch buffers: not concurrently with another call on the same context.
+ * hg_claims_verify_batch: the same pass under the mapping of hg_claims_verify_device (input ids to tables, the shape from params),
+ *   on the claim and point arrays exactly as hg_verify_public_batch writes them: item i's claims at (hg_input_claim*)claims +
+ *   i*claim_cap_each, its points at points + 2*i*coord_cap_each with point_off relative to its own block, its count n_claims[i]. An
+ *   item with n_claims[i] == 0 (a proof hg_verify_public_batch rejected, say) is verified as the single call verifies zero claims:
+ *   the proximity test, with its length rule. -1 also, naming the index: a claim on a public input or on an input past 3+2k, a
+ *   wrong nvars, a count above claim_cap_each, a point outside the item's block. */
+int hg_pcs_verify_device_batch(hg_ctx* ctx, const uint8_t* const* roots, const uint32_t* nvars, size_t n_tables, size_t log2_row,
+                               const uint32_t* const* tables, const uint64_t* const* points, const uint64_t* const* values,
+                               const size_t* n_claims, size_t n_queries, const uint8_t* const* proofs, const size_t* lens, size_t n,
+                               int* results, char* reasons, size_t reason_cap);
+int hg_claims_verify_batch(hg_ctx* ctx, const hg_params* params, const uint8_t* const* roots, size_t log2_row, const void* claims,
+                           size_t claim_cap_each, const uint64_t* points, size_t coord_cap_each, const size_t* n_claims, size_t n_queries,
+                           const uint8_t* const* openings, const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap);
 
 /* The same pair in a protocol mode that FIXES the reference's two known soundness gaps. mode bits:
  *   1  absorbing transcript: write_felt / read_felt also hash the element - the rule of the in-tree plonkish-trait writer of
