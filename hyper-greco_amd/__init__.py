@@ -56,7 +56,7 @@ EXPORTS = [
     "hg_pcs_commit", "hg_pcs_free", "hg_pcs_open", "hg_pcs_verify", "hg_secrets_commit", "hg_claims_open", "hg_claims_verify",
     "hg_pcs_verify_device", "hg_claims_verify_device", "hg_pcs_verify_device_batch", "hg_claims_verify_batch",
     "hg_pcs_commit_bn254", "hg_pcs_open_bn254", "hg_pcs_verify_bn254", "hg_secrets_commit_bn254", "hg_claims_open_bn254", "hg_claims_verify_bn254",
-    "hg_pcs_verify_device_bn254", "hg_claims_verify_device_bn254",
+    "hg_pcs_verify_device_bn254", "hg_claims_verify_device_bn254", "hg_pcs_verify_device_batch_bn254", "hg_claims_verify_batch_bn254",
     "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_mle_eval",
     "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_verify_public_bn254", "hg_verify_public_device_bn254", "hg_verify_public_batch_bn254", "hg_claims_settle_bn254", "hg_instance_mle_bn254", "hg_instance_mle_batch_bn254", "hg_prove_encryptions_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
 ]
@@ -104,8 +104,8 @@ def _two_field_protos(L):
         getattr(L, "hg_claims_verify_device" + sfx).argtypes = [vp] + getattr(L, "hg_claims_verify" + sfx).argtypes
     L.hg_pcs_free.argtypes, L.hg_pcs_free.restype = [vp], None
     tail = [szp, sz, C.POINTER(cp), szp, sz, C.POINTER(ci), cp, sz]   # claim counts, n_queries, openings, lengths, n, results, reasons, reason_cap
-    L.hg_pcs_verify_device_batch.argtypes = [vp, C.POINTER(cp), u32p, sz, sz, C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u64p)] + tail
-    L.hg_claims_verify_batch.argtypes = [vp, C.POINTER(HgParams), C.POINTER(cp), sz, vp, sz, u64p, sz] + tail
+    L.hg_pcs_verify_device_batch.argtypes = L.hg_pcs_verify_device_batch_bn254.argtypes = [vp, C.POINTER(cp), u32p, sz, sz, C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u64p)] + tail
+    L.hg_claims_verify_batch.argtypes = L.hg_claims_verify_batch_bn254.argtypes = [vp, C.POINTER(HgParams), C.POINTER(cp), sz, vp, sz, u64p, sz] + tail
 
 
 _lib = None
@@ -1297,32 +1297,38 @@ def _pcs_verify_batch(call, roots, proofs, reason_cap):
     return [(res[i] == 0, raw[i * reason_cap:(i + 1) * reason_cap].split(b"\0", 1)[0].decode()) for i in range(n)]
 
 
-def pcs_verify_batch(ctx, roots, nvars, claims_list, proofs, n_queries=0, log2_row=0, reason_cap=256):
-    """hg_pcs_verify_device_batch: opening i against roots[i] and claims_list[i] (claims as Commitment.open takes them; an empty list
-    is allowed), every item of the shape nvars: a list of (accepted, reason), the decisions of pcs_verify for each item alone."""
+def _pcs_verify_batch_of(sfx, arrays_of, ctx, roots, nvars, claims_list, proofs, n_queries, log2_row, reason_cap):
+    """hg_pcs_verify_device_batch + sfx on claim lists that arrays_of turns into (table, points, values)"""
     if not (len(roots) == len(claims_list) == len(proofs)):
-        raise ValueError("pcs_verify_batch: one root and one claim list per opening")
+        raise ValueError(f"pcs_verify_batch{sfx}: one root and one claim list per opening")
     m = max(len(proofs), 1)
     nv = (C.c_uint32 * len(nvars))(*nvars)
-    arrays = [_pcs_claim_arrays(c) for c in claims_list]
+    arrays = [arrays_of(c) for c in claims_list]
     tabs = (u32p * m)(*[C.cast(a[0], u32p) for a in arrays])
     pts = (u64p * m)(*[_ptr(a[1]) for a in arrays])
     vals = (u64p * m)(*[_ptr(a[2]) for a in arrays])
     counts = (C.c_size_t * m)(*[len(c) for c in claims_list])
-    fn = lib().hg_pcs_verify_device_batch
+    fn = getattr(lib(), "hg_pcs_verify_device_batch" + sfx)
     return _pcs_verify_batch(lambda rs, ps, lens, n, res, reasons, cap: fn(_h(ctx), rs, nv, len(nvars), log2_row, tabs, pts, vals, counts, n_queries, ps, lens, n,
                                                                             res, reasons, cap), roots, proofs, reason_cap)
 
 
-def _claims_batch_arrays(claims_list):
-    """a list of InputClaims (None: no claims) in the layout hg_verify_public_batch writes: (claims, claim_cap_each, points,
-    coord_cap_each, counts); point_off counts from the item's own block"""
+def pcs_verify_batch(ctx, roots, nvars, claims_list, proofs, n_queries=0, log2_row=0, reason_cap=256):
+    """hg_pcs_verify_device_batch: opening i against roots[i] and claims_list[i] (claims as Commitment.open takes them; an empty list
+    is allowed), every item of the shape nvars: a list of (accepted, reason), the decisions of pcs_verify for each item alone."""
+    return _pcs_verify_batch_of("", _pcs_claim_arrays, ctx, roots, nvars, claims_list, proofs, n_queries, log2_row, reason_cap)
+
+
+def _claims_batch_arrays(claims_list, F=InputClaims):
+    """a list of InputClaims of field F (None: no claims) in the layout hg_verify_public_batch and its _bn254 form write: (claims,
+    claim_cap_each, points, coord_cap_each, counts); point_off counts from the item's own block"""
+    W = F.WORDS
     m = max(len(claims_list), 1)
     held = [c for c in claims_list if c is not None]
     nc1 = max([c.n for c in held] + [1])
     nco1 = max([sum(int(x.nvars) for x in c.claims[:c.n]) for c in held] + [1])
-    claims = (HgInputClaim * (m * nc1))()
-    points = np.zeros(2 * m * nco1, dtype=np.uint64)
+    claims = (F.STRUCT * (m * nc1))()
+    points = np.zeros(W * m * nco1, dtype=np.uint64)
     counts = (C.c_size_t * m)()
     for i, c in enumerate(claims_list):
         if c is None:
@@ -1331,22 +1337,40 @@ def _claims_batch_arrays(claims_list):
         for j in range(c.n):
             src, dst = c.claims[j], claims[i * nc1 + j]
             dst.input, dst.nvars, dst.point_off = src.input, src.nvars, off
-            dst.value[0], dst.value[1] = src.value[0], src.value[1]
-            points[2 * (i * nco1 + off):2 * (i * nco1 + off + src.nvars)] = c.points[2 * src.point_off:2 * (src.point_off + src.nvars)]
+            for w in range(W):
+                dst.value[w] = src.value[w]
+            points[W * (i * nco1 + off):W * (i * nco1 + off + src.nvars)] = c.points[W * src.point_off:W * (src.point_off + src.nvars)]
             off += src.nvars
     return claims, nc1, points, nco1, counts
+
+
+def _claims_verify_batch_of(F, ctx, params, roots, claims_list, openings, n_queries, log2_row, reason_cap):
+    """hg_claims_verify_batch of field F"""
+    if not (len(roots) == len(claims_list) == len(openings)):
+        raise ValueError(f"claims_verify_batch{F.SFX}: one root and one {F.__name__} per opening")
+    claims, nc1, points, nco1, counts = _claims_batch_arrays(claims_list, F)
+    fn = getattr(lib(), "hg_claims_verify_batch" + F.SFX)
+    return _pcs_verify_batch(lambda rs, ps, lens, n, res, reasons, cap: fn(_h(ctx), C.byref(params), rs, log2_row, claims, nc1, _ptr(points), nco1, counts, n_queries,
+                                                                            ps, lens, n, res, reasons, cap), roots, openings, reason_cap)
 
 
 def claims_verify_batch(ctx, params, roots, claims_list, openings, n_queries=0, log2_row=0, reason_cap=256):
     """hg_claims_verify_batch: opening i against roots[i] and the InputClaims claims_list[i] (what verify_public_batch returns; None
     stands for no claims), packed into the layout hg_verify_public_batch writes: a list of (accepted, reason), the decisions of
     claims_verify for each item alone."""
-    if not (len(roots) == len(claims_list) == len(openings)):
-        raise ValueError("claims_verify_batch: one root and one InputClaims per opening")
-    claims, nc1, points, nco1, counts = _claims_batch_arrays(claims_list)
-    fn = lib().hg_claims_verify_batch
-    return _pcs_verify_batch(lambda rs, ps, lens, n, res, reasons, cap: fn(_h(ctx), C.byref(params), rs, log2_row, claims, nc1, _ptr(points), nco1, counts, n_queries,
-                                                                            ps, lens, n, res, reasons, cap), roots, openings, reason_cap)
+    return _claims_verify_batch_of(InputClaims, ctx, params, roots, claims_list, openings, n_queries, log2_row, reason_cap)
+
+
+def pcs_verify_batch_bn254(ctx, roots, nvars, claims_list, proofs, n_queries=0, log2_row=0, reason_cap=256):
+    """hg_pcs_verify_device_batch_bn254: pcs_verify_batch over bn256::Fr, claims as Commitment.open takes them on a BN254 handle: a
+    list of (accepted, reason), the decisions of pcs_verify_bn254 for each item alone."""
+    return _pcs_verify_batch_of("_bn254", _pcs_claim_arrays_bn254, ctx, roots, nvars, claims_list, proofs, n_queries, log2_row, reason_cap)
+
+
+def claims_verify_batch_bn254(ctx, params, roots, claims_list, openings, n_queries=0, log2_row=0, reason_cap=256):
+    """hg_claims_verify_batch_bn254: claims_verify_batch on InputClaimsBn254 objects (what verify_public_batch_bn254 returns; None
+    stands for no claims): a list of (accepted, reason), the decisions of claims_verify_bn254 for each item alone."""
+    return _claims_verify_batch_of(InputClaimsBn254, ctx, params, roots, claims_list, openings, n_queries, log2_row, reason_cap)
 
 
 def pcs_verify_bn254(root, nvars, claims, proof, n_queries=0, log2_row=0, ctx=None):

@@ -4,6 +4,7 @@
 // and the leaf hash and the column gather read the matrix as it is. Keccak and the tree are those of the Goldilocks form
 // (pcs_keccak.hpp, pcs::merkle_levels_device): a node is 32 bytes in either field.
 // The verifier of an opening (pcs_verify_device) reuses the encoding, the leaf sponge and the accumulators and adds five kernels.
+// The verifier of a run of openings (pcs_verify_device_batch) runs the same five kernels once over a group, driven by a member table.
 
 constexpr int BNPCS_TPB = 256;
 static unsigned bnpcs_blocks(size_t n) { return (unsigned)((n + BNPCS_TPB - 1) / BNPCS_TPB); }
@@ -468,4 +469,388 @@ std::string pcs_verify_device(hg_ctx* ctx, const pcs::Shape& sh, const uint8_t r
         return kind == 0 ? pcs::reason_merkle(q) : kind == 1 ? pcs::reason_proximity(q) : pcs::reason_claim(kind - 2, q);
     }
     return "";
+}
+
+// ---- the verifier of a run of openings (pcs_verify_device_batch): the five kernels above with a member in front of every index.
+// The members of a group share the shape and Q; what differs by member (its claim count, where its opening, u, columns, encoded
+// rows, jobs and weights lie) is read from its descriptor, never derived from a flat id, and no member's range is assumed to start
+// at a workgroup. Every block of the staged copy starts at a multiple of 32 bytes (lz_gload reads 16-byte halves).
+struct BnVbMember {
+    u64 proof, u, cols, enc_row;               // word offset of its opening in the set; element offsets of its u and columns; its first row of enc
+    u64 n, claim0, job0;                       // its claims; the claims and the jobs (claims + 1 each) of the members before it
+    u64 root_at, jobs_at, y_at, z_at, w_at;    // byte offsets in the group's staged copy: root, job descriptors, values, low coordinates, weights
+};
+struct BnVbGroup { u64 G, Q, R, q_el; int c, depth; };
+
+// blockIdx.y = the member, its elements grid-strided over blockIdx.x: k_bnpcsv_canon on its own opening, into its own u, columns
+// and enc rows; cells[3m] = the lowest byte offset, within its opening, of an element that is not below r
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_canon(const u64* __restrict__ set, const BnVbMember* __restrict__ mem, BnVbGroup g, Fr* __restrict__ u,
+                                                             Fr* __restrict__ cols, Fr* __restrict__ enc, u64* __restrict__ cells) {
+    const BnVbMember M = mem[blockIdx.y];
+    const int c = g.c;
+    const size_t Q = g.Q, R = g.R, u_el = (M.n + 1) << c, total = u_el + Q * R, Cm = ((size_t)1 << c) - 1;
+    const u64* proof = set + M.proof;
+    Fr* mu = u + M.u;
+    Fr* mcols = cols + M.cols;
+    Fr* menc = enc + (M.enc_row << (c + 2));
+    u64 bad = BNPCSV_NONE;
+    for (size_t i = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * BNPCS_TPB) {
+        size_t at = i;
+        if (i >= u_el) { const size_t k = i - u_el, q = k / R; at = u_el + q * g.q_el + (k - q * R); }
+        const u64* p = proof + 4 * at;
+        const Fr v = fr_make(__builtin_bswap64(p[3]), __builtin_bswap64(p[2]), __builtin_bswap64(p[1]), __builtin_bswap64(p[0]));
+        if (fr_geq_p(v) && 32 * at < bad) bad = 32 * at;
+        if (i < u_el) {
+            lz_gstore(mu + i, v);
+            lz_gstore(menc + ((i >> c) << (c + 2)) + (i & Cm), v);
+        } else {
+            lz_gstore(mcols + (i - u_el), v);
+        }
+    }
+    if (bad != BNPCSV_NONE) bnpcsv_min(cells + 3 * blockIdx.y, bad);
+}
+
+// One workgroup per (member, claim): block b belongs to the last member whose claim0 is <= b (a member without claims owns no
+// block). cells[3m + 1] = the member's lowest failing claim.
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_eval(const BnVbMember* __restrict__ mem, unsigned G, int c, const Fr* __restrict__ u, const char* __restrict__ stage,
+                                                            u64* __restrict__ cells) {
+    __shared__ Fr part[BNPCS_TPB];
+    unsigned lo = 0, hi = G;
+    while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].claim0 <= blockIdx.x) lo = mid; else hi = mid; }
+    const BnVbMember M = mem[lo];
+    const size_t C = (size_t)1 << c, i = blockIdx.x - M.claim0;
+    if (i >= M.n) return;   // (uniform over the workgroup; the grid has exactly the claims of the group)
+    const Fr* z = reinterpret_cast<const Fr*>(stage + M.z_at) + i * (size_t)c;
+    const Fr* ui = u + M.u + (i + 1) * C;
+    const int lob = c < 8 ? c : 8;
+    Fr f = fr_one_mont();
+    for (int b = 0; b < lob; b++) { const Fr zb = lz_gload(z + b); f = fr_mul(f, (threadIdx.x >> b) & 1 ? zb : fr_sub(fr_one_mont(), zb)); }
+    Fr s = fr_zero();
+    for (size_t x = threadIdx.x; x < C; x += BNPCS_TPB) {
+        Fr gq = f;
+        for (int b = 8; b < c; b++) { const Fr zb = lz_gload(z + b); gq = fr_mul(gq, (x >> b) & 1 ? zb : fr_sub(fr_one_mont(), zb)); }
+        s = fr_add(s, fr_mul(lz_gload(ui + x), gq));
+    }
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = BNPCS_TPB / 2; h >= 1; h >>= 1) {
+        if (threadIdx.x < h) part[threadIdx.x] = fr_add(part[threadIdx.x], part[threadIdx.x + h]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && !fr_eq(part[0], lz_gload(reinterpret_cast<const Fr*>(stage + M.y_at) + i))) bnpcsv_min(cells + 3 * lo + 1, (u64)i);
+}
+
+// One thread per (member m, query q), id = m Q + q: the leaf hash of its R column elements -> leaves[id]
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_leaf(const BnVbMember* __restrict__ mem, BnVbGroup g, const Fr* __restrict__ cols, u64* __restrict__ leaves) {
+    const size_t id = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
+    if (id >= g.G * g.Q) return;
+    const size_t m = id / g.Q, q = id - m * g.Q;
+    u64 a[25];
+    bnpcs_leaf_absorb(reinterpret_cast<const u64*>(cols + mem[m].cols + q * g.R), 4, g.R, a);
+    u64* out = leaves + 4 * id;
+    out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
+}
+
+// Column inner products of every member: k_bnpcsv_dots, whose weight limbs go through readfirstlane and so must be the same for
+// every lane of a wavefront. A flat id Q job + q would let a wavefront straddle two jobs whenever Q is no multiple of 64, so the
+// job is fixed per workgroup instead: a one-dimensional grid of bq * jobs_total workgroups, bq = the workgroups Q threads take
+// (no y extent: the jobs of a group can pass 65535); workgroup b works on global job b / bq, queries (b % bq) TPB .. . The member
+// is the last one whose job0 is <= the job. s[global job][q], canonical.
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_dots(const BnVbMember* __restrict__ mem, BnVbGroup g, unsigned bq, const Fr* __restrict__ cols,
+                                                            const char* __restrict__ stage, Fr* __restrict__ s) {
+    const size_t gjob = blockIdx.x / bq;
+    const size_t q = (size_t)(blockIdx.x % bq) * BNPCS_TPB + threadIdx.x;
+    if (q >= g.Q) return;
+    unsigned lo = 0, hi = (unsigned)g.G;
+    while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].job0 <= gjob) lo = mid; else hi = mid; }
+    const BnVbMember M = mem[lo];
+    const BnPcsDesc job = reinterpret_cast<const BnPcsDesc*>(stage + M.jobs_at)[gjob - M.job0];
+    const Fr* src = cols + M.cols + q * g.R + job.row0;
+    const u32* wq = reinterpret_cast<const u32*>(reinterpret_cast<const Fr*>(stage + M.w_at) + job.woff);
+    Fr acc = fr_zero();
+    for (u64 r0 = 0; r0 < job.nrows; r0 += BNPCS_CHUNK) {
+        const u64 r1 = r0 + BNPCS_CHUNK < job.nrows ? r0 + BNPCS_CHUNK : job.nrows;
+        WCol A = wcol_zero();
+        for (u64 r = r0; r < r1; r++) {
+            const Fr x = lz_gload(src + r);
+            u32 bl[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) bl[k] = __builtin_amdgcn_readfirstlane(wq[8 * r + k]);
+            bnpcs_mac_uniform(A, x, bl);
+        }
+        acc = lz_add(acc, lz_reduce(A));
+    }
+    lz_gstore(s + gjob * g.Q + q, lz_canon(acc));
+}
+
+// One thread per (member m, query q), id = m Q + q, once the host has every member's column indices (js[id]): k_bnpcsv_query on
+// the member's own opening, root, s entries and enc rows. cells[3m + 2] = the member's lowest q (n_m + 2) + kind that failed.
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_query(const u64* __restrict__ set, const BnVbMember* __restrict__ mem, BnVbGroup g, const u64* __restrict__ leaves,
+                                                             const Fr* __restrict__ s, const Fr* __restrict__ enc, const u64* __restrict__ js,
+                                                             const char* __restrict__ stage, u64* __restrict__ cells) {
+    const size_t id = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
+    if (id >= g.G * g.Q) return;
+    const size_t m = id / g.Q, q = id - m * g.Q;
+    const BnVbMember M = mem[m];
+    const int depth = g.depth;
+    const size_t N = (size_t)1 << depth, j = js[id], n = M.n, u_el = (n + 1) << g.c;
+    const u64* sib = set + M.proof + 4 * (u_el + q * g.q_el + g.R);
+    const u64* root = reinterpret_cast<const u64*>(stage + M.root_at);
+    u64 h0 = leaves[4 * id], h1 = leaves[4 * id + 1], h2 = leaves[4 * id + 2], h3 = leaves[4 * id + 3];
+    for (int l = 0; l < depth; l++) {
+        const bool right = (j >> l) & 1;   // this node is the right child
+        const u64 t0 = sib[4 * l], t1 = sib[4 * l + 1], t2 = sib[4 * l + 2], t3 = sib[4 * l + 3];
+        u64 a[25];
+        a[0] = 1;
+        a[1] = right ? t0 : h0; a[2] = right ? t1 : h1; a[3] = right ? t2 : h2; a[4] = right ? t3 : h3;
+        a[5] = right ? h0 : t0; a[6] = right ? h1 : t1; a[7] = right ? h2 : t2; a[8] = right ? h3 : t3;
+        a[9] = 0x01;
+#pragma unroll
+        for (int k = 10; k < 25; k++) a[k] = 0;
+        a[pcs::RATE_WORDS - 1] = 0x8000000000000000ull;
+        pcs::keccak_f(a);
+        h0 = a[0]; h1 = a[1]; h2 = a[2]; h3 = a[3];
+    }
+    u64* cell = cells + 3 * m + 2;
+    const size_t key = q * (n + 2);
+    if (h0 != root[0] || h1 != root[1] || h2 != root[2] || h3 != root[3]) { bnpcsv_min(cell, key); return; }
+    const Fr* sq = s + M.job0 * g.Q + q;
+    const Fr* menc = enc + (M.enc_row << depth) + j;
+    for (size_t i = 0; i <= n; i++)
+        if (!fr_eq(lz_gload(sq + i * g.Q), lz_gload(menc + i * N))) { bnpcsv_min(cell, key + 1 + i); return; }
+}
+
+// hg_pcs_verify_device_batch_bn254. The items whose length is right are cut into groups (the option verify_batch_group, VB_PCS_BUDGET
+// over what a member takes in 32-byte elements, the transforms ntt_batch_dev takes on its four-step path). A group: its openings
+// gathered into a page-locked set on the host threads and copied on the upload stream; every member's transcript start, rho powers
+// and weight tables written into one staged copy, one member a task; the index-free kernels, one launch each over all members, the
+// leaf sponge last among them as in the single call; the members' u_i hashed on the host threads meanwhile; all indices up, the
+// query kernel, three cells a member down: one synchronisation a group. The next group's openings are gathered and copied into the
+// other set before that synchronisation, under this group's kernels.
+std::vector<std::string> pcs_verify_device_batch(const char* who_c, hg_ctx* ctx, const pcs::Shape& sh, const std::vector<VerifyItem>& items, size_t Q) {
+    const std::string who(who_c);
+    const size_t C = sh.C(), N = sh.N(), R = sh.R;
+    const int depth = sh.depth();
+    const size_t q_el = R + (size_t)depth;
+    const bool four_step = depth >= 8 && depth <= 16;
+    std::vector<std::string> why(items.size());
+    std::vector<size_t> good;   // the items that reach the device
+    for (size_t i = 0; i < items.size(); i++) {
+        why[i] = pcs::length_reason(items[i].len, pcs_opening_bytes(sh, items[i].claims->size(), Q));
+        if (why[i].empty()) good.push_back(i);
+    }
+    if (good.empty()) return why;
+    // what a member takes: its opening in a set; u, columns, enc rows and as many for the NTT temporary, s (32 bytes an element),
+    // leaves and indices in the arena
+    auto rows_of = [](size_t n) { return n + 1; };
+    auto bytes_of = [&](size_t n, size_t len) { return len + sizeof(Fr) * (C * (n + 1) + Q * R + 2 * rows_of(n) * N + Q * (n + 1)) + 8 * 5 * Q; };
+    size_t cap = VB_MAX_GROUP;
+    if (ctx->verify_batch_group > 0) cap = std::min<size_t>(cap, (size_t)ctx->verify_batch_group);
+    constexpr size_t NTT_ROWS = 65535;   // ntt_batch_dev: the batch is the y extent of its four-step grids
+    // k_bnpcsvb_dots: bq workgroups a job (a member's jobs are its rows) in one x extent, and a launch takes fewer than 2^32 threads.
+    // One member is at most 4097 jobs of 256 workgroups, far inside it.
+    const size_t bq = bnpcs_blocks(Q), DOTS_BLOCKS = (((size_t)1 << 32) / BNPCS_TPB - 1) / bq;
+    std::vector<std::pair<size_t, size_t>> groups;   // [first, last) of good
+    for (size_t a = 0; a < good.size();) {
+        size_t b = a, bytes = 0, rows = 0;
+        while (b < good.size() && b - a < cap) {
+            const size_t n = items[good[b]].claims->size();
+            if (b > a && (bytes + bytes_of(n, items[good[b]].len) > VB_PCS_BUDGET || (four_step && rows + rows_of(n) > NTT_ROWS) || rows + rows_of(n) > DOTS_BLOCKS)) break;
+            bytes += bytes_of(n, items[good[b]].len);
+            rows += rows_of(n);
+            b++;
+        }
+        groups.push_back({a, b});
+        a = b;
+    }
+    hipc(hipSetDevice(ctx->device), "hipSetDevice");
+    VerifyBatchBufs* B = batch_bufs(ctx);
+    hipStream_t st = ctx->stream;
+    std::vector<u64> hj, cells;   // (declared ahead of the guard: copies of them may be queued when it drains)
+    struct Drain {   // every way out, an error included: no copy of a dead host buffer, no kernel on the arena or a set left behind
+        hipStream_t a, b;
+        ~Drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); }
+    } drain{st, B->up};
+    hipc(hipStreamSynchronize(st), (who + ": synchronise").c_str());   // (the arena is reset below)
+    [[maybe_unused]] const int nthr = std::max(1, hg_omp_threads());   // (the device pass of hipcc ignores the pragmas)
+    const int cls = ctx->prof_class("pcs_bn254_verify_batch", false);
+    ctx->prof_stream = st;
+
+    struct Member { size_t idx, n, nw; FsTranscript tr; std::string error; };
+    // the openings of group g into set g & 1, at word offsets that the descriptors repeat
+    auto proof_offsets = [&](size_t g) {
+        std::vector<size_t> off;
+        size_t at = 0;
+        for (size_t x = groups[g].first; x < groups[g].second; x++) { off.push_back(at); at += items[good[x]].len / 8; }
+        off.push_back(at);
+        return off;
+    };
+    auto stage = [&](size_t g) {
+        const std::vector<size_t> off = proof_offsets(g);
+        std::vector<BatchBlob> blobs;
+        for (size_t x = groups[g].first; x < groups[g].second; x++) blobs.push_back(BatchBlob{items[good[x]].proof, items[good[x]].len, off[x - groups[g].first]});
+        batch_stage_blobs(B, (int)(g & 1), blobs, off.back(), nthr, who_c);
+    };
+    const bool times = hg_times("pcs");   // HG_TIMES=pcs: where a group's wall clock goes, on stderr
+    double t_stage = omp_get_wtime();
+    stage(0);
+    t_stage = omp_get_wtime() - t_stage;
+    for (size_t g = 0; g < groups.size(); g++) {
+        const double t0 = omp_get_wtime();
+        const size_t G = groups[g].second - groups[g].first;
+        const int set = (int)(g & 1);
+        std::vector<Member> mem(G);
+        std::vector<BnVbMember> desc(G);
+        const std::vector<size_t> poff = proof_offsets(g);
+        // the layout of the staged copy: the descriptors, then every member's block, and of the arena buffers
+        size_t at = (G * sizeof(BnVbMember) + 31) & ~(size_t)31, u_at = 0, row_at = 0, claim_at = 0;
+        for (size_t m = 0; m < G; m++) {
+            Member& x = mem[m];
+            const VerifyItem& it = items[good[groups[g].first + m]];
+            x.idx = good[groups[g].first + m];
+            x.n = it.claims->size();
+            x.nw = R;
+            for (const PcsClaim& cl : *it.claims) x.nw += (size_t)1 << (sh.nvars[cl.table] - sh.c);
+            BnVbMember& d = desc[m];
+            d.proof = poff[m]; d.u = u_at; d.cols = m * Q * R; d.enc_row = row_at;
+            d.n = x.n; d.claim0 = claim_at; d.job0 = claim_at + m;
+            d.root_at = at;
+            d.jobs_at = d.root_at + 32;
+            d.y_at = d.jobs_at + (((x.n + 1) * sizeof(BnPcsDesc) + 31) & ~(size_t)31);
+            d.z_at = d.y_at + x.n * sizeof(Fr);
+            d.w_at = d.z_at + x.n * (size_t)sh.c * sizeof(Fr);
+            at = d.w_at + x.nw * sizeof(Fr);
+            u_at += C * (x.n + 1);
+            row_at += rows_of(x.n);
+            claim_at += x.n;
+        }
+        const size_t stage_bytes = at, u_total = u_at, rows = row_at, claims_total = claim_at, jobs_total = claim_at + G;
+        char* h_stage = batch_desc_host(B, stage_bytes);   // (the previous group's copy of it was waited for)
+        memcpy(h_stage, desc.data(), G * sizeof(BnVbMember));
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
+        for (long long mq = 0; mq < (long long)G; mq++) {
+            Member& x = mem[mq];
+            try {
+                const VerifyItem& it = items[x.idx];
+                const BnVbMember& d = desc[mq];
+                x.tr = pcs_start_transcript(sh, it.root, *it.claims, Q);
+                const std::vector<Fr> rho = pcs_rho_powers(pcs_squeeze(x.tr), R);
+                memcpy(h_stage + d.root_at, it.root, 32);
+                BnPcsDesc* hd = reinterpret_cast<BnPcsDesc*>(h_stage + d.jobs_at);
+                Fr* hy = reinterpret_cast<Fr*>(h_stage + d.y_at);
+                Fr* hz = reinterpret_cast<Fr*>(h_stage + d.z_at);
+                Fr* hw = reinterpret_cast<Fr*>(h_stage + d.w_at);
+                hd[0].row0 = 0; hd[0].nrows = R; hd[0].woff = 0;
+                memcpy(hw, rho.data(), R * sizeof(Fr));
+                size_t off = R;
+                for (size_t i = 0; i < x.n; i++) {
+                    const PcsClaim& cl = (*it.claims)[i];
+                    const std::vector<Fr> w = pcs_eq_table(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
+                    hd[i + 1].row0 = sh.off[cl.table]; hd[i + 1].nrows = w.size(); hd[i + 1].woff = off;
+                    memcpy(hw + off, w.data(), w.size() * sizeof(Fr));
+                    off += w.size();
+                    hy[i] = cl.value;
+                    for (int b = 0; b < sh.c; b++) hz[i * (size_t)sh.c + b] = fr_to_mont(cl.point[b]);
+                }
+            } catch (const std::exception& e) { x.error = e.what(); }
+        }
+        for (const Member& x : mem)
+            if (!x.error.empty()) throw Error(who + ": index " + std::to_string(x.idx) + ": " + x.error);
+        const double t1 = omp_get_wtime();
+        ctx->arena_reset();
+        u64 *d_leaves, *d_js, *d_cells;
+        Fr *d_u, *d_cols, *d_enc, *d_tmp, *d_W, *d_s;
+        char* d_stage;
+        try {
+            d_stage = ctx->alloc_n<char>(stage_bytes);
+            d_u = ctx->alloc_n<Fr>(u_total);
+            d_cols = ctx->alloc_n<Fr>(G * Q * R);
+            d_enc = ctx->alloc_n<Fr>(rows * N);
+            d_tmp = ctx->alloc_n<Fr>(rows * N);
+            d_W = ctx->alloc_n<Fr>(N);
+            d_leaves = ctx->alloc_n<u64>(4 * G * Q);
+            d_s = ctx->alloc_n<Fr>(Q * jobs_total);
+            d_js = ctx->alloc_n<u64>(G * Q);
+            d_cells = ctx->alloc_n<u64>(3 * G);
+        } catch (const std::exception& e) {
+            throw Error(who + ": the context's arena cannot hold " + (G == 1 ? "the opening at index " + std::to_string(mem[0].idx) : "a group of " + std::to_string(G) + " openings: lower verify_batch_group") +
+                        " (" + e.what() + ")");
+        }
+        const u64* d_set = B->d_in[set];
+        const BnVbMember* d_mem = reinterpret_cast<const BnVbMember*>(d_stage);
+        const BnVbGroup vg{(u64)G, (u64)Q, (u64)R, (u64)q_el, sh.c, depth};
+        size_t el_max = 0, nw_total = 0;
+        for (const Member& x : mem) { el_max = std::max(el_max, C * (x.n + 1) + Q * R); nw_total += x.nw; }
+        hipc(hipStreamWaitEvent(st, B->ev[set], 0), "hipStreamWaitEvent");   // the set's openings are up
+        hipc(hipMemcpyAsync(d_stage, h_stage, stage_bytes, hipMemcpyHostToDevice, st), "upload claims");
+        hipc(hipMemsetAsync(d_cells, 0xff, 3 * G * 8, st), "memset");
+        hipc(hipMemsetAsync(d_enc, 0, rows * N * sizeof(Fr), st), "memset");
+        ctx->prof_begin(cls, (double)(u_total + G * Q * R) * 64 + (double)u_total * 32);
+        k_bnpcsvb_canon<<<dim3((unsigned)std::min<size_t>(bnpcs_blocks(el_max), 1024), (unsigned)G), BNPCS_TPB, 0, st>>>(d_set, d_mem, vg, d_u, d_cols, d_enc, d_cells);
+        ctx->prof_end();
+        if (claims_total) {
+            ctx->prof_begin(cls, (double)claims_total * C * 32);
+            k_bnpcsvb_eval<<<(unsigned)claims_total, BNPCS_TPB, 0, st>>>(d_mem, (unsigned)G, sh.c, d_u, d_stage, d_cells);
+            ctx->prof_end();
+        }
+        ctx->prof_begin(cls, (double)rows * N * 32 * 4);
+        k_bn_powers<<<bnpcs_blocks(N), 256, 0, st>>>(d_W, fr_root_of_unity(depth), N);
+        ntt_batch_dev(st, d_enc, d_tmp, d_W, depth, rows, nullptr);
+        ctx->prof_end();
+        ctx->prof_begin(cls, (double)Q * nw_total * 64);
+        k_bnpcsvb_dots<<<(unsigned)(bq * jobs_total), BNPCS_TPB, 0, st>>>(d_mem, vg, (unsigned)bq, d_cols, d_stage, d_s);
+        ctx->prof_end();
+        ctx->prof_begin(cls, (double)G * Q * R * 32);
+        k_bnpcsvb_leaf<<<bnpcs_blocks(G * Q), BNPCS_TPB, 0, st>>>(d_mem, vg, d_cols, d_leaves);
+        ctx->prof_end();
+        // the host's share, beside the kernels: every member's u_i into its transcript, its column indices out of it
+        const double t2 = omp_get_wtime();
+        hj.assign(G * Q, 0);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
+        for (long long mq = 0; mq < (long long)G; mq++) {
+            Member& x = mem[mq];
+            try {
+                const uint8_t* proof = items[x.idx].proof;
+                const size_t u_el = C * (x.n + 1);
+                std::vector<Fr> u(u_el);
+                for (size_t i = 0; i < u_el; i++) u[i] = pcs_read_be32(proof + 32 * i);
+                pcs_absorb(x.tr, u.data(), u_el);
+                const std::vector<size_t> js = pcs_squeeze_indices(x.tr, N, Q);
+                for (size_t q = 0; q < Q; q++) hj[(size_t)mq * Q + q] = js[q];
+            } catch (const std::exception& e) { x.error = e.what(); }
+        }
+        for (const Member& x : mem)
+            if (!x.error.empty()) throw Error(who + ": index " + std::to_string(x.idx) + ": " + x.error);
+        const double t3 = omp_get_wtime();
+        hipc(hipMemcpyAsync(d_js, hj.data(), G * Q * 8, hipMemcpyHostToDevice, st), "upload column indices");
+        ctx->prof_begin(cls, (double)G * Q * 32.0 * depth + (double)Q * jobs_total * 64.0);
+        k_bnpcsvb_query<<<bnpcs_blocks(G * Q), BNPCS_TPB, 0, st>>>(d_set, d_mem, vg, d_leaves, d_s, d_enc, d_js, d_stage, d_cells);
+        ctx->prof_end();
+        cells.assign(3 * G, 0);
+        hipc(hipMemcpyAsync(cells.data(), d_cells, 3 * G * 8, hipMemcpyDeviceToHost, st), "download verdicts");
+        const double t4 = omp_get_wtime();
+        if (g + 1 < groups.size()) stage(g + 1);   // into the other set, under this group's kernels
+        const double t5 = omp_get_wtime();
+        hipc(hipStreamSynchronize(st), (who + ": sync").c_str());
+        if (times)
+            fprintf(stderr, "[hg pcs] group %zu of %zu members: gather and copy of its openings %.2f ms, transcripts and weights %.2f, enqueue %.2f, hash %.2f, "
+                            "query enqueue %.2f, next group's gather %.2f, wait %.2f\n", g, G, t_stage * 1e3, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3,
+                    (t5 - t4) * 1e3, (omp_get_wtime() - t5) * 1e3);
+        t_stage = t5 - t4;
+        hipc(hipGetLastError(), (who + ": launch").c_str());
+        ctx->prof_collect();
+        // per member, the host's order: a non-canonical element, the lowest claim whose evaluation fails, the lowest failing query
+        for (size_t m = 0; m < G; m++) {
+            const u64* cm = cells.data() + 3 * m;
+            const size_t n = mem[m].n;
+            std::string& out = why[mem[m].idx];
+            if (cm[0] != BNPCSV_NONE) out = pcs::reason_noncanonical((size_t)cm[0]);
+            else if (cm[1] != BNPCSV_NONE) out = pcs::reason_evaluation((size_t)cm[1]);
+            else if (cm[2] != BNPCSV_NONE) {
+                const size_t q = (size_t)(cm[2] / (n + 2)), kind = (size_t)(cm[2] % (n + 2));
+                out = kind == 0 ? pcs::reason_merkle(q) : kind == 1 ? pcs::reason_proximity(q) : pcs::reason_claim(kind - 2, q);
+            }
+        }
+    }
+    return why;
 }

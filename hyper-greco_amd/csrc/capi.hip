@@ -38,12 +38,14 @@ static thread_local std::string g_last_error;
     catch (...) { g_last_error = "unknown error"; return ret; }
 #define HG_ENTRY(...) HG_TRY return __VA_ARGS__; HG_CATCH(-1)   // an entry that is one call of a routine of the shared layer
 
-// (called from the worker threads of hg_setup's node loop: the current device is per thread, the key's list of allocations is shared)
+// (called from the worker threads of hg_setup's node loop: the current device is per thread, the key's list of allocations is shared.
+// ONE lock for every element type: a static inside the template would be one mutex per instantiation, and the u32, u64 and
+// GatherSeg uploads of different threads would push onto pk->owned at the same time)
+static std::mutex g_upload_mu;
 template <typename T>
 static const T* upload_vec(hg_pk* pk, const std::vector<T>& v) {
     if (!pk->ctx) return nullptr;  // host-only key (hg_setup(NULL, ..)): wiring without a device copy
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lock(mu);
+    std::lock_guard<std::mutex> lock(g_upload_mu);
     hip_check(hipSetDevice(pk->ctx->device), "hipSetDevice");
     T* d = nullptr;
     size_t bytes = std::max<size_t>(v.size() * sizeof(T), 16);
@@ -165,6 +167,7 @@ struct BnAbi {
     typedef OpenClaimBn Open;
     typedef hg_input_claim_bn254 Wire;
     typedef bn::PcsClaim PcsClaim;
+    typedef bn::VerifyItem PcsItem;
     typedef bn::Fr Elem;
     static bool canonical(const u64* w) { return bn254_canonical(w); }
     static Elem elem(const u64* w) { bn::Fr x; memcpy(x.l, w, 32); return x; }
@@ -210,6 +213,9 @@ struct BnAbi {
         } catch (const std::exception& e) {
             throw Error(std::string(who) + ": " + e.what());
         }
+    }
+    static std::vector<std::string> pcs_verify_batch(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const std::vector<PcsItem>& items, size_t Q) {
+        return bn::pcs_verify_device_batch(who, ctx, sh, items, Q);
     }
 };
 }  // namespace
@@ -1964,6 +1970,18 @@ int hg_claims_verify_bn254(const hg_params* params, const uint8_t root[32], size
 int hg_claims_verify_device_bn254(hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points4,
                                   size_t n_queries, const uint8_t* opening, size_t len) {
     HG_ENTRY(claims_verify_entry<BnAbi>("hg_claims_verify_device_bn254", true, ctx, params, root, log2_row, claims, n, points4, n_queries, opening, len))
+}
+
+int hg_pcs_verify_device_batch_bn254(hg_ctx* ctx, const uint8_t* const* roots, const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* const* tables,
+                                     const uint64_t* const* points4, const uint64_t* const* values4, const size_t* n_claims, size_t n_queries, const uint8_t* const* proofs,
+                                     const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap) {
+    HG_ENTRY(pcs_verify_batch_entry<BnAbi>("hg_pcs_verify_device_batch_bn254", ctx, roots, nvars, n_tables, log2_row, tables, points4, values4, n_claims, n_queries, proofs, lens, n, results, reasons, reason_cap))
+}
+
+int hg_claims_verify_batch_bn254(hg_ctx* ctx, const hg_params* params, const uint8_t* const* roots, size_t log2_row, const void* claims, size_t claim_cap_each,
+                                 const uint64_t* points4, size_t coord_cap_each, const size_t* n_claims, size_t n_queries, const uint8_t* const* openings, const size_t* lens,
+                                 size_t n, int* results, char* reasons, size_t reason_cap) {
+    HG_ENTRY(claims_verify_batch_entry<BnAbi>("hg_claims_verify_batch_bn254", ctx, params, roots, log2_row, claims, claim_cap_each, points4, coord_cap_each, n_claims, n_queries, openings, lens, n, results, reasons, reason_cap))
 }
 
 int hg_profile(hg_ctx* ctx, int level) {

@@ -41,6 +41,11 @@ std::string pcs_verify(const pcs::Shape& sh, const uint8_t root[32], const std::
 // stream; the Fiat-Shamir hash over the u_i stays on the host and runs beside the kernels. Throws an Error if the arena cannot hold
 // the opening
 std::string pcs_verify_device(hg_ctx* ctx, const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof, size_t len);
+// hg_pcs_verify_device_batch_bn254 (bn254_pcs.inc): a run of openings of one shape and one Q, each with its own root and claims, in
+// device passes of a group of openings each; why[i] is what pcs_verify_device returns for item i alone. Throws an Error naming
+// `who` if the arena cannot hold a group
+struct VerifyItem { const uint8_t* root; const std::vector<PcsClaim>* claims; const uint8_t* proof; size_t len; };
+std::vector<std::string> pcs_verify_device_batch(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const std::vector<VerifyItem>& items, size_t Q);
 
 // ---- what the opening and both forms of the verifier share (pcs_bn254.cpp): the transcript up to the column indices, the weights
 FsTranscript pcs_start_transcript(const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q);

@@ -77,7 +77,7 @@ struct hg_ctx {
     // options (hg_set_option)
     bool one_stream = false;  // keep every launch on `stream` (per-kernel timings without cross-stream interference)
     int mode = 0;             // protocol mode of the next proves: bit 0 absorbing transcript, bit 1 extension-field memory checking
-    int64_t verify_batch_group = 0;   // hg_verify_device_batch, hg_verify_public_batch, hg_pcs_verify_device_batch: most proofs or openings per device pass (0: sized from the arena budget)
+    int64_t verify_batch_group = 0;   // hg_verify_device_batch, hg_verify_public_batch, hg_pcs_verify_device_batch and their _bn254 forms: most proofs or openings per device pass (0: sized from the arena budget)
     void* verify_batch = nullptr;     // verifier_batch.hip: VerifyBatchBufs (pinned and device input sets, upload stream), freed with the context
     // bump arena: chunks are kept across proves, offsets reset per prove
     struct Chunk { char* p; size_t cap, used; size_t high = 0; };  // high: largest `used` since the last reset

@@ -43,7 +43,8 @@ constexpr size_t VB_INPUT_BUDGET = (size_t)1 << 30, VB_TABLE_BUDGET = (size_t)4 
 constexpr size_t VB_MAX_GROUP = 64;
 // hg_pcs_verify_device_batch: what the members of one group may take in all - each one's opening in a set and its u, columns,
 // encoded rows and NTT scratch in the arena (about 19 MB a member at n=32768 k=16: opening 3.3, u 1.5, columns 1.7, enc and the
-// scratch 6.3 each; 64 members: 1.2 GB)
+// scratch 6.3 each; 64 members: 1.2 GB). hg_pcs_verify_device_batch_bn254 counts its members' bytes against the same budget, 32 bytes an
+// element (about 45 MB a member at that size: 47 members a group)
 constexpr size_t VB_PCS_BUDGET = (size_t)2 << 30;
 
 // dedup keys of the group merge: a job's descriptor with absolute chain offsets

@@ -78,7 +78,8 @@ void hg_destroy(hg_ctx* ctx);
  *                 keeps its graph; up to HG_GRAPH_ENTRIES (8) graphs per context, each with a private workspace)
  *   "verify_batch_group"  the most proofs one device pass of hg_verify_device_batch, hg_verify_device_batch_bn254,
  *                 hg_verify_public_batch or hg_verify_public_batch_bn254 holds, and the most openings one of
- *                 hg_pcs_verify_device_batch or hg_claims_verify_batch (default 0: sized from the memory budget, at most 64)
+ *                 hg_pcs_verify_device_batch, hg_claims_verify_batch, hg_pcs_verify_device_batch_bn254 or
+ *                 hg_claims_verify_batch_bn254 (default 0: sized from the memory budget, at most 64)
  * Returns 0, or -1 for an unknown name. */
 int hg_set_option(hg_ctx* ctx, const char* name, int64_t value);
 
@@ -810,6 +811,30 @@ int hg_claims_verify_bn254(const hg_params* params, const uint8_t root[32], size
                            const uint64_t* points4, size_t n_queries, const uint8_t* opening, size_t len);
 int hg_claims_verify_device_bn254(hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n,
                                   const uint64_t* points4, size_t n_queries, const uint8_t* opening, size_t len);
+
+/* hg_pcs_verify_device_batch_bn254 / hg_claims_verify_batch_bn254: hg_pcs_verify_device_batch / hg_claims_verify_batch over bn256::Fr,
+ *   the same contract word for word with a coordinate or value of 4 canonical limbs: a run of n openings of ONE shape and one
+ *   n_queries, item i with its own root, claims (0 allowed) and opening; results[i] and the reason slot at reasons + i*reason_cap
+ *   (reasons may be NULL) are exactly what hg_pcs_verify_device_bn254 - so hg_pcs_verify_bn254 - gives for that item alone, also
+ *   where several checks fail at once and for a wrong length, which is rejected per item and never reaches the device; byte offsets
+ *   in reasons count from the item's own opening. Returns the number of rejected items; n == 0 returns 0 and writes nothing.
+ *   claims is an hg_input_claim_bn254 array and points4 is laid out exactly as hg_verify_public_batch_bn254 writes them: item i's
+ *   claims at (hg_input_claim_bn254*)claims + i*claim_cap_each, its points at points4 + 4*i*coord_cap_each with point_off relative
+ *   to its own block.
+ *   The pass is the Goldilocks one over 32-byte elements: groups of at most 64 or "verify_batch_group" members, the 2 GiB budget (a
+ *   member takes about 45 MB at n=32768 k=16, so 64 of them run as groups of 47 and 17), the 65535 transforms the batched Fr NTT takes at
+ *   once and the threads of one launch of the inner products; the kernels of hg_pcs_verify_device_bn254 once over all members,
+ *   the inner products with one job per workgroup; one synchronisation a group.
+ *   -1 (nothing is written; hg_last_error begins with the function's name and gives "index i" where an item is at fault; every
+ *   item is checked before anything is enqueued): the cases of the Goldilocks pair, with an element that is not below r in place
+ *   of a word that is not below p, and "<function>: no context" for a null context, after the argument checks. */
+int hg_pcs_verify_device_batch_bn254(hg_ctx* ctx, const uint8_t* const* roots, const uint32_t* nvars, size_t n_tables, size_t log2_row,
+                                     const uint32_t* const* tables, const uint64_t* const* points4, const uint64_t* const* values4,
+                                     const size_t* n_claims, size_t n_queries, const uint8_t* const* proofs, const size_t* lens, size_t n,
+                                     int* results, char* reasons, size_t reason_cap);
+int hg_claims_verify_batch_bn254(hg_ctx* ctx, const hg_params* params, const uint8_t* const* roots, size_t log2_row, const void* claims,
+                                 size_t claim_cap_each, const uint64_t* points4, size_t coord_cap_each, const size_t* n_claims, size_t n_queries,
+                                 const uint8_t* const* openings, const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap);
 
 /* hg_witness_derive and hg_prove_bn254 for a run of n_enc ENCRYPTIONS under one key, pipelined: hg_prove_encryptions over bn256::Fr
  *   [REF scripts/circuit_sk.py:18-140 followed by sk_encryption_circuit.rs:417-460, 614-626; the loop a proving service writes around
