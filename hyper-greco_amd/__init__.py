@@ -55,6 +55,7 @@ EXPORTS = [
     "hg_instance_from_ciphertext", "hg_instance_from_witness", "hg_instance_free", "hg_instance_coeffs", "hg_instance_get", "hg_pk_claim_shape", "hg_verify_public", "hg_verify_public_device", "hg_verify_public_batch", "hg_claims_settle", "hg_instance_mle", "hg_instance_mle_batch",
     "hg_pcs_commit", "hg_pcs_free", "hg_pcs_open", "hg_pcs_verify", "hg_secrets_commit", "hg_claims_open", "hg_claims_verify",
     "hg_pcs_verify_device", "hg_claims_verify_device", "hg_pcs_verify_device_batch", "hg_claims_verify_batch",
+    "hg_pcs_commit_batch", "hg_secrets_commit_batch", "hg_pcs_open_batch", "hg_claims_open_batch",
     "hg_pcs_commit_bn254", "hg_pcs_open_bn254", "hg_pcs_verify_bn254", "hg_secrets_commit_bn254", "hg_claims_open_bn254", "hg_claims_verify_bn254",
     "hg_pcs_verify_device_bn254", "hg_claims_verify_device_bn254", "hg_pcs_verify_device_batch_bn254", "hg_claims_verify_batch_bn254",
     "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_mle_eval",
@@ -106,6 +107,11 @@ def _two_field_protos(L):
     tail = [szp, sz, C.POINTER(cp), szp, sz, C.POINTER(ci), cp, sz]   # claim counts, n_queries, openings, lengths, n, results, reasons, reason_cap
     L.hg_pcs_verify_device_batch.argtypes = L.hg_pcs_verify_device_batch_bn254.argtypes = [vp, C.POINTER(cp), u32p, sz, sz, C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u64p)] + tail
     L.hg_claims_verify_batch.argtypes = L.hg_claims_verify_batch_bn254.argtypes = [vp, C.POINTER(HgParams), C.POINTER(cp), sz, vp, sz, u64p, sz] + tail
+    L.hg_pcs_commit_batch.argtypes = [vp, C.POINTER(C.POINTER(u64p)), u32p, sz, sz, sz, C.POINTER(vp), u8p]
+    L.hg_secrets_commit_batch.argtypes = [vp, C.POINTER(HgParams), C.POINTER(vp), sz, sz, C.POINTER(vp), u8p]
+    opened = [szp, sz, sz, u8p, sz, szp, C.POINTER(ci), cp, sz]   # claim counts, n_queries, n, openings, cap_each, lengths, status, reasons, reason_cap
+    L.hg_pcs_open_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u64p)] + opened
+    L.hg_claims_open_batch.argtypes = [vp, C.POINTER(HgParams), C.POINTER(vp), vp, sz, u64p, sz] + opened
 
 
 _lib = None
@@ -1227,6 +1233,39 @@ class Commitment:
         """hg_secrets_commit: the five secret inputs of a witness handle (tables s, e, k1, r1is[0..k-1], r2is)."""
         return cls._secrets("goldilocks", ctx, params, witness, log2_row)
 
+    @classmethod
+    def _batch(cls, call, ctx, n, nvars, log2_row):
+        """call(handles, roots) of a commit batch entry -> the n Commitments"""
+        hs, roots = (C.c_void_p * max(n, 1))(), (C.c_uint8 * (32 * max(n, 1)))()
+        _check(call(hs, roots))
+        c = pcs_row_log2(nvars, log2_row)
+        return [cls(C.c_void_p(hs[i]), bytes(roots[32 * i:32 * i + 32]), ctx, nvars, c) for i in range(n)]
+
+    @classmethod
+    def commit_batch(cls, ctx, tables_list, log2_row=0):
+        """hg_pcs_commit_batch: one device Commitment per entry of tables_list (each as commit takes it), all of one shape, their
+        matrices encoded and hashed in device passes of a group of members each."""
+        tabs = [[np.ascontiguousarray(t, dtype=np.uint64) for t in tables] for tables in tables_list]
+        n = len(tabs)
+        if not n:   # (no member, no shape to pass)
+            return []
+        nvars = [t.size.bit_length() - 1 for t in tabs[0]]
+        if any([t.size.bit_length() - 1 for t in tables] != nvars for tables in tabs):
+            raise ValueError("commit_batch: every member has the tables of one shape")
+        rows = [(u64p * len(nvars))(*[_ptr(t) for t in tables]) for tables in tabs]
+        ptrs = (C.POINTER(u64p) * max(n, 1))(*[C.cast(r, C.POINTER(u64p)) for r in rows])
+        nv = (C.c_uint32 * len(nvars))(*nvars)
+        return cls._batch(lambda hs, roots: lib().hg_pcs_commit_batch(_h(ctx), ptrs, nv, len(nvars), log2_row, n, hs, roots), ctx, n, nvars, log2_row)
+
+    @classmethod
+    def secrets_batch(cls, ctx, params, witnesses, log2_row=0):
+        """hg_secrets_commit_batch: one device Commitment to the five secret inputs of every witness handle."""
+        n = len(witnesses)
+        ws = (C.c_void_p * max(n, 1))(*[w.h for w in witnesses])
+        lg = params.n.bit_length() - 1
+        nvars = [lg + 1] * (3 + params.k) + [lg + params.k.bit_length() - 1]
+        return cls._batch(lambda hs, roots: lib().hg_secrets_commit_batch(_h(ctx), C.byref(params), ws, n, log2_row, hs, roots), ctx, n, nvars, log2_row)
+
     def _open(self, entry, head, n_claims, tail, n_queries):
         """entry(ctx, *head, n_claims, *tail, n_queries, buffer, its size, length out) of the handle's field -> the opening bytes"""
         bn = self.field == "bn254"
@@ -1256,6 +1295,47 @@ class Commitment:
             self.free()
         except Exception:
             pass
+
+
+def _open_batch(call, cms, counts, n_queries, reason_cap):
+    """One call of an open batch entry: call(handles, counts, n_queries, n, openings, cap_each, lens, status, reasons, reason_cap) ->
+    [(the opening bytes or None, reason)]"""
+    n = len(cms)
+    m = max(n, 1)
+    cap = max([pcs_opening_bytes(cm.nvars, k, n_queries, cm.log2_row) for cm, k in zip(cms, counts)] + [8])
+    hs = (C.c_void_p * m)(*[cm.h for cm in cms])
+    nc = (C.c_size_t * m)(*counts)
+    buf = np.zeros(m * cap, dtype=np.uint8)
+    lens, status = (C.c_size_t * m)(), (C.c_int * m)()
+    reasons = C.create_string_buffer(m * reason_cap)
+    _check(call(hs, nc, n_queries, n, buf.ctypes.data_as(u8p), cap, lens, status, reasons, reason_cap))
+    raw = reasons.raw
+    return [(None if status[i] else buf[i * cap:i * cap + lens[i]].tobytes(), raw[i * reason_cap:(i + 1) * reason_cap].split(b"\0", 1)[0].decode()) for i in range(n)]
+
+
+def pcs_open_batch(ctx, cms, claims_list, n_queries=0, reason_cap=256):
+    """hg_pcs_open_batch: claims_list[i] (claims as Commitment.open takes them; an empty list is allowed) opened against the device
+    Commitment cms[i], all of one shape: [(bytes or None, reason)] - the bytes of cms[i].open(claims_list[i]), or None and the text of
+    its error where a value is not the evaluation."""
+    if len(cms) != len(claims_list):
+        raise ValueError("pcs_open_batch: one claim list per commitment")
+    m = max(len(cms), 1)
+    arrays = [_pcs_claim_arrays(c) for c in claims_list]
+    tabs = (u32p * m)(*[C.cast(a[0], u32p) for a in arrays])
+    pts = (u64p * m)(*[_ptr(a[1]) for a in arrays])
+    vals = (u64p * m)(*[_ptr(a[2]) for a in arrays])
+    fn = lib().hg_pcs_open_batch
+    return _open_batch(lambda hs, nc, *rest: fn(_h(ctx), hs, tabs, pts, vals, nc, *rest), cms, [len(c) for c in claims_list], n_queries, reason_cap)
+
+
+def claims_open_batch(ctx, params, cms, claims_list, n_queries=0, reason_cap=256):
+    """hg_claims_open_batch: the InputClaims claims_list[i] (what verify_public_batch returns; None stands for no claims) opened
+    against the Commitment.secrets / secrets_batch handle cms[i]: [(bytes or None, reason)]."""
+    if len(cms) != len(claims_list):
+        raise ValueError("claims_open_batch: one InputClaims per commitment")
+    claims, nc1, points, nco1, counts = _claims_batch_arrays(claims_list)
+    fn = lib().hg_claims_open_batch
+    return _open_batch(lambda hs, nc, *rest: fn(_h(ctx), C.byref(params), hs, claims, nc1, _ptr(points), nco1, nc, *rest), cms, list(counts)[:len(cms)], n_queries, reason_cap)
 
 
 def _pcs_verify(sfx, arrays, root, nvars, claims, proof, n_queries, log2_row, ctx):

@@ -159,6 +159,15 @@ struct GlAbi {
     static std::vector<std::string> pcs_verify_batch(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const std::vector<PcsItem>& items, size_t Q) {
         return pcs::verify_device_batch(who, ctx, sh, items, Q);
     }
+    // the batch forms of commit and open (device only): tabs[i * m + t] = table t of member i
+    typedef pcs::OpenItem PcsOpenItem;
+    static size_t opening_bytes(const pcs::Shape& sh, size_t n_claims, size_t Q) { return pcs::opening_bytes(sh, n_claims, Q); }
+    static std::vector<pcs::Commitment*> commit_batch(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const u64* const* tabs, size_t n, bool) {
+        return pcs::commit_device_batch(who, ctx, sh, tabs, n);
+    }
+    static std::vector<pcs::Opened> pcs_open_batch(const char* who, const char* single, hg_ctx* ctx, const std::vector<PcsOpenItem>& items, size_t Q) {
+        return pcs::open_device_batch(who, single, ctx, items, Q);
+    }
 };
 
 struct BnAbi {
@@ -646,6 +655,174 @@ static int claims_verify_batch_entry(const char* who, hg_ctx* ctx, const hg_para
         cl[i] = pcs_claims<A>(at.c_str(), sh, table.data(), pts.data(), vals.data(), n_claims[i]);
     }
     return pcs_verify_batch_tail<A>(who, ctx, sh, roots, cl, Q, openings, lens, n, results, reasons, reason_cap);
+}
+
+// ---- the batch forms of commit and open (device only). An error of the call writes nothing: every item is checked before anything
+// is enqueued, and the outputs are written once the whole run is done.
+// hg_pcs_commit_batch* and hg_secrets_commit_batch* after their argument checks: tabs[i * m + t] = table t of member i (`secrets`:
+// the tables are witness words, which the BN254 form lifts by the signed rule)
+template <class A>
+static int commit_batch_tail(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const std::vector<const u64*>& tabs, size_t n, bool secrets, void** commitments, uint8_t* roots) {
+    const std::string w(who);
+    if (sh.R > 65535) throw Error(w + ": more than 65535 rows (choose a larger log2_row)");
+    if (!n) return 0;
+    if (!ctx) throw Error(w + ": no context");
+    std::vector<pcs::Commitment*> cms;
+    try {
+        cms = A::commit_batch(who, ctx, sh, tabs.data(), n, secrets);
+    } catch (const std::exception& e) {
+        const std::string m = e.what();
+        throw Error(m.rfind(w, 0) == 0 ? m : w + ": " + m);
+    }
+    for (size_t i = 0; i < n; i++) {
+        memcpy(roots + 32 * i, cms[i]->root(), 32);
+        commitments[i] = cms[i];
+    }
+    return 0;
+}
+
+// hg_pcs_commit_batch*
+template <class A>
+static int pcs_commit_batch_entry(const char* who, hg_ctx* ctx, const uint64_t* const* const* tables, const uint32_t* nvars, size_t n_tables, size_t log2_row, size_t n,
+                                  void** commitments, uint8_t* roots) {
+    const std::string w(who);
+    if (!nvars || (n && (!tables || !commitments || !roots))) throw Error(w + ": null argument");
+    const pcs::Shape sh = pcs::make_shape(who, nvars, n_tables, log2_row);
+    std::vector<const u64*> tabs;
+    for (size_t i = 0; i < n; i++) {
+        const std::string at = w + ": index " + std::to_string(i);
+        if (!tables[i]) throw Error(at + ": null argument");
+        for (size_t t = 0; t < n_tables; t++) {
+            if (!tables[i][t]) throw Error(at + ": null table " + std::to_string(t));
+            tabs.push_back(tables[i][t]);
+        }
+    }
+    return commit_batch_tail<A>(who, ctx, sh, tabs, n, false, commitments, roots);
+}
+
+// hg_secrets_commit_batch*: member i's tables are secrets_commit_entry's for ws[i]
+template <class A>
+static int secrets_commit_batch_entry(const char* who, hg_ctx* ctx, const hg_params* params, const hg_witness* const* ws, size_t n, size_t log2_row, void** commitments,
+                                      uint8_t* roots) {
+    const std::string w(who);
+    if (!params || (n && (!ws || !commitments || !roots))) throw Error(w + ": null argument");
+    Params p(*params);
+    const size_t SZ = p.SZ(), k = (size_t)p.k;
+    const std::vector<uint32_t> nv = secrets_nvars(p);
+    const pcs::Shape sh = pcs::make_shape(who, nv.data(), nv.size(), log2_row);
+    std::vector<const u64*> tabs;
+    for (size_t i = 0; i < n; i++) {
+        const std::string at = w + ": index " + std::to_string(i);
+        if (!ws[i]) throw Error(at + ": null argument");
+        const Witness& v = ws[i]->w;
+        if (ws[i]->params.n != params->n || ws[i]->params.k != params->k || v.s.size() != SZ || v.e.size() != SZ || v.k1.size() != SZ || v.r1is.size() != k * SZ ||
+            v.r2is.size() != k * p.PZ())
+            throw Error(at + ": the witness was built for other parameters");
+        tabs.insert(tabs.end(), {v.s.data(), v.e.data(), v.k1.data()});
+        for (size_t j = 0; j < k; j++) tabs.push_back(v.r1is.data() + j * SZ);
+        tabs.push_back(v.r2is.data());
+    }
+    return commit_batch_tail<A>(who, ctx, sh, tabs, n, true, commitments, roots);
+}
+
+// item i's handle of an open batch: a device commitment of this field, of this context and of the shape of item 0's
+template <class A>
+static const pcs::Commitment* open_batch_handle(const char* who, const std::string& at, hg_ctx* ctx, const void* handle, const pcs::Commitment* first) {
+    if (!handle) throw Error(at + ": null argument");
+    const pcs::Commitment* cm = static_cast<const pcs::Commitment*>(handle);
+    if (cm->field != A::FIELD) throw Error(at + ": " + A::other_field(who));
+    if (!cm->ctx) throw Error(at + ": the commitment was made by the host form: a run is opened on device commitments only");
+    if (ctx && cm->ctx != ctx) throw Error(at + ": the commitment was made on another context");
+    if (first && (cm->sh.c != first->sh.c || cm->sh.nvars != first->sh.nvars)) throw Error(at + ": the commitment's shape differs from that of index 0");
+    return cm;
+}
+
+// hg_pcs_open_batch* and hg_claims_open_batch* after their argument checks. `single` names the entry that opens one item: a refused
+// item's reason is the text that entry leaves
+template <class A>
+static int pcs_open_batch_tail(const char* who, const char* single, hg_ctx* ctx, const std::vector<const pcs::Commitment*>& cms,
+                               const std::vector<std::vector<typename A::PcsClaim>>& cl, size_t Q, uint8_t* openings, size_t cap_each, size_t* lens, int* status,
+                               char* reasons, size_t reason_cap) {
+    const std::string w(who);
+    const size_t n = cms.size();
+    if (!n) return 0;
+    size_t need = 0;
+    for (size_t i = 0; i < n; i++) need = std::max(need, A::opening_bytes(cms[i]->sh, cl[i].size(), Q));
+    if (cap_each < need) throw Error(w + ": the largest opening of the run has " + std::to_string(need) + " bytes, cap_each is " + std::to_string(cap_each));
+    if (!ctx) throw Error(w + ": no context");
+    std::vector<typename A::PcsOpenItem> items(n);
+    for (size_t i = 0; i < n; i++) items[i] = typename A::PcsOpenItem{cms[i], &cl[i]};
+    std::vector<pcs::Opened> got;
+    try {
+        got = A::pcs_open_batch(who, single, ctx, items, Q);
+    } catch (const std::exception& e) {
+        const std::string m = e.what();
+        throw Error(m.rfind(w, 0) == 0 ? m : w + ": " + m);
+    }
+    int refused = 0;
+    [[maybe_unused]] const int nthr = std::max(1, std::min<int>(hg_omp_threads(), (int)n));   // (the device pass of hipcc ignores the pragmas)
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthr)
+    for (long long i = 0; i < (long long)n; i++)
+        if (!got[i].refused) memcpy(openings + (size_t)i * cap_each, got[i].bytes.data(), got[i].bytes.size());
+    for (size_t i = 0; i < n; i++) {
+        status[i] = got[i].refused ? 1 : 0;
+        refused += status[i];
+        lens[i] = got[i].bytes.size();
+        write_reason(reasons, reason_cap, i, got[i].reason);
+    }
+    return refused;
+}
+
+// hg_pcs_open_batch*: item i's claim checks are pcs_open_entry's under the name "<entry>: index i"
+template <class A>
+static int pcs_open_batch_entry(const char* who, const char* single, hg_ctx* ctx, const void* const* commitments, const uint32_t* const* tables, const uint64_t* const* points,
+                                const uint64_t* const* values, const size_t* n_claims, size_t n_queries, size_t n, uint8_t* openings, size_t cap_each, size_t* lens,
+                                int* status, char* reasons, size_t reason_cap) {
+    const std::string w(who);
+    if (n && (!commitments || !n_claims || !openings || !lens || !status)) throw Error(w + ": null argument");
+    const size_t Q = pcs_queries(who, n_queries);
+    std::vector<const pcs::Commitment*> cms(n);
+    std::vector<std::vector<typename A::PcsClaim>> cl(n);
+    for (size_t i = 0; i < n; i++) {
+        const std::string at = w + ": index " + std::to_string(i);
+        const bool has = n_claims[i] != 0;
+        if (has && (!tables || !points || !values || !tables[i] || !points[i] || !values[i])) throw Error(at + ": null argument");
+        cms[i] = open_batch_handle<A>(who, at, ctx, commitments[i], i ? cms[0] : nullptr);
+        cl[i] = pcs_claims<A>(at.c_str(), cms[i]->sh, has ? tables[i] : nullptr, has ? points[i] : nullptr, has ? values[i] : nullptr, n_claims[i]);
+    }
+    return pcs_open_batch_tail<A>(who, single, ctx, cms, cl, Q, openings, cap_each, lens, status, reasons, reason_cap);
+}
+
+// hg_claims_open_batch*: the claim and point blocks as hg_verify_public_batch* writes them, item i's under claims_open_entry's mapping;
+// `mine` names the entry that makes a commitment to the secrets
+template <class A>
+static int claims_open_batch_entry(const char* who, const char* single, const char* mine, hg_ctx* ctx, const hg_params* params, const void* const* commitments,
+                                   const void* claims, size_t claim_cap_each, const uint64_t* points, size_t coord_cap_each, const size_t* n_claims, size_t n_queries,
+                                   size_t n, uint8_t* openings, size_t cap_each, size_t* lens, int* status, char* reasons, size_t reason_cap) {
+    const std::string w(who);
+    if (!params || (n && (!commitments || !n_claims || !openings || !lens || !status))) throw Error(w + ": null argument");
+    Params p(*params);
+    const std::vector<uint32_t> nv = secrets_nvars(p);
+    const size_t Q = pcs_queries(who, n_queries);
+    std::vector<const pcs::Commitment*> cms(n);
+    std::vector<std::vector<typename A::PcsClaim>> cl(n);
+    for (size_t i = 0; i < n; i++) {
+        const std::string at = w + ": index " + std::to_string(i);
+        if (n_claims[i] && (!claims || !points)) throw Error(at + ": null argument");
+        cms[i] = open_batch_handle<A>(who, at, ctx, commitments[i], i ? cms[0] : nullptr);
+        if (cms[i]->sh.nvars.size() != nv.size() || !std::equal(nv.begin(), nv.end(), cms[i]->sh.nvars.begin(), [](uint32_t a, int b) { return (int)a == b; }))
+            throw Error(at + ": the commitment is not " + mine + "'s for these parameters");
+        if (n_claims[i] > claim_cap_each) throw Error(at + ": " + std::to_string(n_claims[i]) + " claims in a block of " + std::to_string(claim_cap_each));
+        const typename A::Wire* in = static_cast<const typename A::Wire*>(claims) + i * claim_cap_each;
+        for (size_t j = 0; j < n_claims[i]; j++)
+            if (in[j].point_off > coord_cap_each || in[j].nvars > coord_cap_each - in[j].point_off)
+                throw Error(at + ": claim " + std::to_string(j) + " has its point outside the block of " + std::to_string(coord_cap_each) + " coordinates");
+        std::vector<uint32_t> table;
+        std::vector<uint64_t> pts, vals;
+        secrets_claims<A>(at.c_str(), p, in, n_claims[i], points ? points + A::WORDS * i * coord_cap_each : nullptr, table, pts, vals);
+        cl[i] = pcs_claims<A>(at.c_str(), cms[i]->sh, table.data(), pts.data(), vals.data(), n_claims[i]);
+    }
+    return pcs_open_batch_tail<A>(who, single, ctx, cms, cl, Q, openings, cap_each, lens, status, reasons, reason_cap);
 }
 
 extern "C" {
@@ -1922,6 +2099,28 @@ int hg_claims_verify_batch(hg_ctx* ctx, const hg_params* params, const uint8_t* 
                            const uint64_t* points, size_t coord_cap_each, const size_t* n_claims, size_t n_queries, const uint8_t* const* openings, const size_t* lens,
                            size_t n, int* results, char* reasons, size_t reason_cap) {
     HG_ENTRY(claims_verify_batch_entry<GlAbi>("hg_claims_verify_batch", ctx, params, roots, log2_row, claims, claim_cap_each, points, coord_cap_each, n_claims, n_queries, openings, lens, n, results, reasons, reason_cap))
+}
+
+int hg_pcs_commit_batch(hg_ctx* ctx, const uint64_t* const* const* tables, const uint32_t* nvars, size_t n_tables, size_t log2_row, size_t n, void** commitments,
+                        uint8_t* roots) {
+    HG_ENTRY(pcs_commit_batch_entry<GlAbi>("hg_pcs_commit_batch", ctx, tables, nvars, n_tables, log2_row, n, commitments, roots))
+}
+
+int hg_secrets_commit_batch(hg_ctx* ctx, const hg_params* params, const hg_witness* const* ws, size_t n, size_t log2_row, void** commitments, uint8_t* roots) {
+    HG_ENTRY(secrets_commit_batch_entry<GlAbi>("hg_secrets_commit_batch", ctx, params, ws, n, log2_row, commitments, roots))
+}
+
+int hg_pcs_open_batch(hg_ctx* ctx, const void* const* commitments, const uint32_t* const* tables, const uint64_t* const* points, const uint64_t* const* values,
+                      const size_t* n_claims, size_t n_queries, size_t n, uint8_t* openings, size_t cap_each, size_t* lens, int* status, char* reasons, size_t reason_cap) {
+    HG_ENTRY(pcs_open_batch_entry<GlAbi>("hg_pcs_open_batch", "hg_pcs_open", ctx, commitments, tables, points, values, n_claims, n_queries, n, openings, cap_each, lens, status,
+                                         reasons, reason_cap))
+}
+
+int hg_claims_open_batch(hg_ctx* ctx, const hg_params* params, const void* const* commitments, const void* claims, size_t claim_cap_each, const uint64_t* points,
+                         size_t coord_cap_each, const size_t* n_claims, size_t n_queries, size_t n, uint8_t* openings, size_t cap_each, size_t* lens, int* status,
+                         char* reasons, size_t reason_cap) {
+    HG_ENTRY(claims_open_batch_entry<GlAbi>("hg_claims_open_batch", "hg_claims_open", "hg_secrets_commit", ctx, params, commitments, claims, claim_cap_each, points,
+                                            coord_cap_each, n_claims, n_queries, n, openings, cap_each, lens, status, reasons, reason_cap))
 }
 
 // ---- the same entries over bn256::Fr (pcs_bn254.hpp): an element crosses as 4 canonical words

@@ -3,6 +3,8 @@
 // the deferred-reduction accumulators, a gather of the opened columns. The handle owns the raw and the encoded matrix in HBM.
 // The verifier of an opening (verify_device) reuses the encoding and the leaf hash and adds five kernels of its own.
 // The verifier of a run of openings (verify_device_batch) runs the same five kernels once over a group, driven by a member table.
+// A run of commitments (commit_device_batch) and a run of openings (open_device_batch) do the same for the prover's side: a group's
+// matrices in one allocation that its handles share, the kernels of commit and open once over the group.
 #include <omp.h>
 #include "pcs.hpp"
 #include "prover.hpp"
@@ -379,6 +381,7 @@ __global__ __launch_bounds__(PCS_TPB) void k_pcsvb_query(const u64* __restrict__
 }
 
 Commitment::~Commitment() {
+    if (owner) return;   // (the matrices lie in a group's slab, which goes with its last handle)
     if (d_rows) (void)hipFree(d_rows);
     if (d_M) (void)hipFree(d_M);
 }
@@ -818,6 +821,452 @@ std::vector<std::string> verify_device_batch(const char* who_c, hg_ctx* ctx, con
         }
     }
     return why;
+}
+
+// ---- a run of commitments (commit_device_batch): the kernels of commit_device with a member in front of every index. The members
+// of a group share the shape; member m's raw rows lie at rows + m R C, its encoded rows at M + m R N (so the encoding is one
+// ntt_batch over G R rows) and its tree at trees + m tree_words. Every grid is one-dimensional over (member, item).
+__global__ __launch_bounds__(PCS_TPB) void k_pcsb_stage(const u64* __restrict__ rows, u64* __restrict__ M, size_t G, size_t R, int c, unsigned* __restrict__ flags) {
+    const size_t per = R << (c + 2), total = G * per;
+    const size_t C = (size_t)1 << c, Nm = ((size_t)4 << c) - 1;
+    for (size_t i = (size_t)blockIdx.x * PCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * PCS_TPB) {
+        const size_t m = i / per, k = i - m * per, r = k >> (c + 2), j = k & Nm;
+        u64 v = 0;
+        if (j < C) {
+            v = rows[((m * R + r) << c) + j];
+            if (v >= GL_P) atomicOr(flags + m, 1u);   // one flag a member
+        }
+        M[i] = v;
+    }
+}
+// One thread per (member m, column j), id = m N + j: k_pcs_leaf_hash on the member's own matrix, into the leaves of its own tree
+__global__ __launch_bounds__(PCS_TPB) void k_pcsb_leaf_hash(const u64* __restrict__ M, size_t G, size_t N, size_t R, u64* __restrict__ trees, size_t tree_words) {
+    const size_t id = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
+    if (id >= G * N) return;
+    const size_t m = id / N, j = id - m * N;
+    u64 a[25];
+    leaf_absorb(M + m * R * N + j, N, R, a);
+    u64* out = trees + m * tree_words + 4 * j;
+    out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
+}
+// One thread per (member, node) of one level: `count` nodes over the 2 * count nodes at word below_at of every tree
+__global__ __launch_bounds__(PCS_TPB) void k_pcsb_merkle(u64* __restrict__ trees, size_t tree_words, size_t below_at, size_t count, size_t G) {
+    const size_t id = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
+    if (id >= G * count) return;
+    const size_t m = id / count;
+    u64* below = trees + m * tree_words + below_at;
+    merkle_node(below, below + 8 * count, id - m * count);
+}
+// One workgroup per member (blockIdx.x): k_pcs_merkle_top on its tree
+__global__ __launch_bounds__(PCS_TPB) void k_pcsb_merkle_top(u64* __restrict__ trees, size_t tree_words, size_t below_at, size_t count) {
+    u64* below = trees + (size_t)blockIdx.x * tree_words + below_at;
+    while (count >= 1) {
+        u64* here = below + 8 * count;
+        if (threadIdx.x < count) merkle_node(below, here, threadIdx.x);
+        __syncthreads();
+        below = here;
+        count >>= 1;
+    }
+}
+
+namespace {
+struct Slab {   // a group's raw and encoded rows; its members' handles share it
+    u64* p = nullptr;
+    ~Slab() { if (p) (void)hipFree(p); }
+};
+struct DrainOne {   // every way out, an error included: no copy of a dead host buffer and no kernel on the arena left behind
+    hipStream_t st;
+    ~DrainOne() { (void)hipStreamSynchronize(st); }
+};
+// [first, last) of a run cut into groups: at most VB_MAX_GROUP or the option, `bytes_of(i)` summed within VB_PCS_BUDGET, `rows_of`
+// summed within max_rows; a group holds at least one member
+template <class BytesOf>
+std::vector<std::pair<size_t, size_t>> cut_groups(hg_ctx* ctx, size_t n, BytesOf bytes_of, size_t rows_each, size_t max_rows) {
+    size_t cap = VB_MAX_GROUP;
+    if (ctx->verify_batch_group > 0) cap = std::min<size_t>(cap, (size_t)ctx->verify_batch_group);
+    std::vector<std::pair<size_t, size_t>> groups;
+    for (size_t a = 0; a < n;) {
+        size_t b = a, bytes = 0;
+        while (b < n && b - a < cap) {
+            if (b > a && (bytes + bytes_of(b) > VB_PCS_BUDGET || (b - a + 1) * rows_each > max_rows)) break;
+            bytes += bytes_of(b);
+            b++;
+        }
+        groups.push_back({a, b});
+        a = b;
+    }
+    return groups;
+}
+}  // namespace
+
+// hg_pcs_commit_batch. A group: one allocation for its members' raw and encoded rows, the tables uploaded straight into it, then
+// k_pcsb_stage, one ntt_batch over G R rows, the leaf hashes, the tree levels (per level while a level has more than PCS_TPB nodes,
+// then one workgroup a member), one download of all trees and flags, one synchronisation.
+std::vector<Commitment*> commit_device_batch(const char* who_c, hg_ctx* ctx, const Shape& sh, const u64* const* tables, size_t n) {
+    const std::string who(who_c);
+    const size_t C = sh.C(), N = sh.N(), R = sh.R, nt = sh.nvars.size();
+    const int log2n = sh.depth();
+    if (R > 65535) throw Error(who + ": more than 65535 rows (choose a larger log2_row)");
+    const size_t tree_words = 8 * N;   // 2N nodes of 4 words: the 2N - 1 of a tree and one unused
+    // what a member takes: its rows and encoded rows in the slab; the NTT scratch and its tree in the arena
+    const size_t member_bytes = 8 * (R * C + 2 * R * N + tree_words) + 4;
+    const std::vector<std::pair<size_t, size_t>> groups = cut_groups(ctx, n, [&](size_t) { return member_bytes; }, R, 65535);   // ntt_batch: the batch is the y extent of its four-step grids
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    hipStream_t st = ctx->stream;
+    std::vector<std::unique_ptr<Commitment>> made;
+    std::vector<u64> h_out;   // (declared ahead of the guard: a copy into it may be queued when it drains)
+    DrainOne drain{st};
+    hip_check(hipStreamSynchronize(st), (who + ": synchronise").c_str());   // (the arena is reset below)
+    const int cls = ctx->prof_class("pcs_commit_batch", false);
+    ctx->prof_stream = st;
+    const bool times = hg_times("pcs");   // HG_TIMES=pcs: where a group's wall clock goes, on stderr
+    for (const auto& grp : groups) {
+        const double t0 = omp_get_wtime();
+        const size_t first = grp.first, G = grp.second - grp.first;
+        std::shared_ptr<Slab> slab = std::make_shared<Slab>();
+        hip_check(hipMalloc((void**)&slab->p, G * (R * C + R * N) * 8), "hipMalloc(pcs rows and encoded matrices of a group)");
+        u64* d_rows = slab->p;
+        u64* d_M = slab->p + G * R * C;
+        const double t1 = omp_get_wtime();
+        ctx->arena_reset();
+        u64 *scratch, *W, *d_out;
+        const size_t out_words = G * tree_words + (G + 1) / 2;   // the trees, then one 32-bit flag a member
+        try {
+            scratch = ctx->alloc_n<u64>(G * R * N);
+            W = ctx->alloc_n<u64>(N);
+            d_out = ctx->alloc_n<u64>(out_words);
+        } catch (const std::exception& e) {
+            throw Error(who + ": the context's arena cannot hold a group of " + std::to_string(G) + " commitments: lower verify_batch_group (" + e.what() + ")");
+        }
+        unsigned* d_flags = reinterpret_cast<unsigned*>(d_out + G * tree_words);
+        hip_check(hipMemsetAsync(d_flags, 0, ((G + 1) / 2) * 8, st), "memset");
+        for (size_t m = 0; m < G; m++)
+            for (size_t t = 0; t < nt; t++)
+                hip_check(hipMemcpyAsync(d_rows + (m * R + sh.off[t]) * C, tables[(first + m) * nt + t], ((size_t)8) << sh.nvars[t], hipMemcpyHostToDevice, st), "upload tables");
+        const double t2 = omp_get_wtime();
+        ctx->prof_begin(cls, (double)G * R * (C + N) * 8);
+        k_pcsb_stage<<<(unsigned)std::min<size_t>(blocks_for(G * R * N), 4096), PCS_TPB, 0, st>>>(d_rows, d_M, G, R, sh.c, d_flags);
+        ctx->prof_end();
+        ctx->prof_begin(cls, (double)G * R * N * 32);
+        dev::powers_table(st, W, root_of_unity(log2n), N);
+        dev::ntt_batch(st, d_M, log2n, G * R, W, 1, scratch);
+        ctx->prof_end();
+        ctx->prof_begin(cls, (double)G * R * N * 8);
+        k_pcsb_leaf_hash<<<blocks_for(G * N), PCS_TPB, 0, st>>>(d_M, G, N, R, d_out, tree_words);
+        ctx->prof_end();
+        ctx->prof_begin(cls, (double)G * N * 96);
+        size_t below_at = 0, count = N / 2;
+        for (; count > (size_t)PCS_TPB; count >>= 1) {
+            k_pcsb_merkle<<<blocks_for(G * count), PCS_TPB, 0, st>>>(d_out, tree_words, below_at, count, G);
+            below_at += 8 * count;
+        }
+        k_pcsb_merkle_top<<<(unsigned)G, PCS_TPB, 0, st>>>(d_out, tree_words, below_at, count);
+        ctx->prof_end();
+        h_out.resize(out_words);
+        hip_check(hipMemcpyAsync(h_out.data(), d_out, out_words * 8, hipMemcpyDeviceToHost, st), "download trees and flags");
+        const double t3 = omp_get_wtime();
+        hip_check(hipStreamSynchronize(st), (who + ": sync").c_str());
+        const double t4 = omp_get_wtime();
+        hip_check(hipGetLastError(), (who + ": launch").c_str());
+        ctx->prof_collect();
+        const unsigned* flags = reinterpret_cast<const unsigned*>(h_out.data() + G * tree_words);
+        for (size_t m = 0; m < G; m++)
+            if (flags[m]) throw Error(who + ": index " + std::to_string(first + m) + ": a table holds a word that is not below p");
+        for (size_t m = 0; m < G; m++) {
+            std::unique_ptr<Commitment> cm(new Commitment());
+            cm->sh = sh;
+            cm->ctx = ctx;
+            cm->d_rows = d_rows + m * R * C;
+            cm->d_M = d_M + m * R * N;
+            cm->owner = slab;
+            const uint8_t* tree = reinterpret_cast<const uint8_t*>(h_out.data() + m * tree_words);
+            cm->tree.assign(tree, tree + 32 * (2 * N - 1));
+            made.push_back(std::move(cm));
+        }
+        if (times)
+            fprintf(stderr, "[hg pcs] commit group of %zu members: allocation %.2f ms, uploads %.2f, enqueue %.2f, wait %.2f, trees into the handles %.2f\n", G, (t1 - t0) * 1e3,
+                    (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3, (omp_get_wtime() - t4) * 1e3);
+    }
+    std::vector<Commitment*> out;
+    for (auto& cm : made) out.push_back(cm.release());
+    return out;
+}
+
+// ---- a run of openings (open_device_batch). What differs by item lies in three flat tables of the group's staged copy: a job a row
+// combination (the proximity combination and one a claim, every member's behind the other), a claim an evaluation check, a member
+// where its matrix, its u vectors and its opening image lie. Every grid is one-dimensional.
+struct ObJob { const u64* src; u64 nrows, w_at, u_at; };     // its first raw row; the byte offset of its weights in the staged copy; where u goes (elements)
+struct ObClaim { u64 u_at, z_at, y_at, member, claim; };      // its u_i (elements); byte offsets of the low coordinates and of the value
+struct ObMember { const u64* M; u64 img, u, u_words; };       // its encoded matrix; word offsets of its image and of its u vectors; 2 C (n + 1)
+
+// k_pcs_combine driven by the job table: block b serves job b / cb, columns (b % cb) PCS_TPB ..
+__global__ __launch_bounds__(PCS_TPB) void k_pcsob_combine(int c, unsigned cb, const ObJob* __restrict__ jobs, const char* __restrict__ stage, E2* __restrict__ u) {
+    const size_t C = (size_t)1 << c;
+    const unsigned jq = blockIdx.x / cb;
+    const size_t j = (size_t)(blockIdx.x - jq * cb) * PCS_TPB + threadIdx.x;
+    if (j >= C) return;
+    const ObJob job = jobs[jq];
+    const u64* src = job.src + j;
+    const E2* wq = reinterpret_cast<const E2*>(stage + job.w_at);
+    u64 s0 = 0, s1 = 0;
+    for (u64 r0 = 0; r0 < job.nrows; r0 += COMBINE_CHUNK) {
+        const u64 r1 = r0 + COMBINE_CHUNK < job.nrows ? r0 + COMBINE_CHUNK : job.nrows;
+        WAcc A = wacc_zero(), B = wacc_zero();
+        for (u64 r = r0; r < r1; r++) {
+            const u64 x = src[r << c];
+            const E2 wr = wq[r];
+            wmac2(A, x, wr.c0, B, x, wr.c1);
+        }
+        s0 = gl_add(s0, wreduce(A));
+        s1 = gl_add(s1, wreduce(B));
+    }
+    u[job.u_at + j] = e2(s0, s1);
+}
+// One workgroup per (member, claim), the arithmetic of k_pcsvb_eval: <u_i, eq(z_i[..c])> == y_i; cells[member] = its lowest failing claim
+__global__ __launch_bounds__(PCS_TPB) void k_pcsob_eval(const ObClaim* __restrict__ claims, int c, const E2* __restrict__ u, const char* __restrict__ stage,
+                                                        u64* __restrict__ cells) {
+    __shared__ E2 part[PCS_TPB];
+    const ObClaim cl = claims[blockIdx.x];
+    const size_t C = (size_t)1 << c;
+    const E2* z = reinterpret_cast<const E2*>(stage + cl.z_at);
+    const E2* ui = u + cl.u_at;
+    const int lob = c < 8 ? c : 8;
+    E2 f = e2_one();
+    for (int b = 0; b < lob; b++) f = e2_mul(f, (threadIdx.x >> b) & 1 ? z[b] : e2_sub(e2_one(), z[b]));
+    E2 s = e2_zero();
+    for (size_t x = threadIdx.x; x < C; x += PCS_TPB) {
+        E2 gq = f;
+        for (int b = 8; b < c; b++) gq = e2_mul(gq, (x >> b) & 1 ? z[b] : e2_sub(e2_one(), z[b]));
+        s = e2_add(s, e2_mul(ui[x], gq));
+    }
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = PCS_TPB / 2; h >= 1; h >>= 1) {
+        if (threadIdx.x < h) part[threadIdx.x] = e2_add(part[threadIdx.x], part[threadIdx.x + h]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && !e2_eq(part[0], *reinterpret_cast<const E2*>(stage + cl.y_at))) cell_min(cells + cl.member, cl.claim);
+}
+// Word i of the group's u vectors, big-endian, into its member's image: the member is the last one whose u offset is <= i
+__global__ __launch_bounds__(PCS_TPB) void k_pcsob_emit(const ObMember* __restrict__ mem, unsigned G, size_t total, const u64* __restrict__ u, u64* __restrict__ img) {
+    for (size_t i = (size_t)blockIdx.x * PCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * PCS_TPB) {
+        unsigned lo = 0, hi = G;
+        while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].u <= i) lo = mid; else hi = mid; }
+        img[mem[lo].img + (i - mem[lo].u)] = __builtin_bswap64(u[i]);
+    }
+}
+// One thread per (member m, query q, row r), id = (m Q + q) R + r: M_m[r][j_q] big-endian at its place in the member's image.
+// js[m Q + q] = j_q (masked by the host); js[G Q + m] != 0: the member takes part (it was not refused)
+__global__ __launch_bounds__(PCS_TPB) void k_pcsob_gather(const ObMember* __restrict__ mem, size_t G, size_t Q, size_t R, size_t N, size_t q_words,
+                                                          const u64* __restrict__ js, u64* __restrict__ img) {
+    const size_t id = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
+    if (id >= G * Q * R) return;
+    const size_t m = id / (Q * R), k = id - m * Q * R, q = k / R, r = k - q * R;
+    if (!js[G * Q + m]) return;
+    const ObMember M = mem[m];
+    img[M.img + M.u_words + q * q_words + r] = __builtin_bswap64(M.M[r * N + js[m * Q + q]]);
+}
+
+// hg_pcs_open_batch. A group: the host threads write every member's transcript start, rho powers, weight tables and table entries into
+// one staged copy; the combinations, the evaluation checks and the big-endian u vectors run as one launch each; the u vectors and one
+// cell a member come back (first synchronisation); the host threads hash each member's u_i, one member a thread; all indices go up,
+// the gather writes the opened columns into the images, the images come back (second synchronisation); the host copies the siblings
+// from each handle's tree into the gaps.
+std::vector<Opened> open_device_batch(const char* who_c, const char* single, hg_ctx* ctx, const std::vector<OpenItem>& items, size_t Q) {
+    const std::string who(who_c);
+    std::vector<Opened> res(items.size());
+    if (items.empty()) return res;
+    const Shape& sh = items[0].cm->sh;
+    const size_t C = sh.C(), N = sh.N(), R = sh.R;
+    const int depth = sh.depth();
+    const size_t q_words = R + 4 * (size_t)depth;
+    auto align16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    auto nw_of = [&](const std::vector<Claim>& cl) { size_t nw = R; for (const Claim& x : cl) nw += (size_t)1 << (sh.nvars[x.table] - sh.c); return nw; };
+    // what a member takes: its block of the staged copy, its u vectors and its image in the arena, its indices
+    auto bytes_of = [&](size_t i) {
+        const std::vector<Claim>& cl = *items[i].claims;
+        return sizeof(ObMember) + (cl.size() + 1) * sizeof(ObJob) + cl.size() * (sizeof(ObClaim) + (size_t)(sh.c + 1) * sizeof(E2)) + nw_of(cl) * sizeof(E2) + 64 +
+               16 * C * (cl.size() + 1) + opening_bytes(sh, cl.size(), Q) + 8 * Q + 16;
+    };
+    const std::vector<std::pair<size_t, size_t>> groups = cut_groups(ctx, items.size(), bytes_of, 0, 0);
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    VerifyBatchBufs* B = batch_bufs(ctx);
+    hipStream_t st = ctx->stream;
+    std::vector<u64> hj;   // (declared ahead of the guard: a copy of it may be queued when it drains)
+    DrainOne drain{st};
+    hip_check(hipStreamSynchronize(st), (who + ": synchronise").c_str());   // (the arena is reset below)
+    [[maybe_unused]] const int nthr = std::max(1, hg_omp_threads());        // (the device pass of hipcc ignores the pragmas)
+    const int cls = ctx->prof_class("pcs_open_batch", false);
+    ctx->prof_stream = st;
+    const bool times = hg_times("pcs");   // HG_TIMES=pcs: where a group's wall clock goes, on stderr
+
+    struct Member { size_t idx, n, nw, job0, claim0, y_at, z_at, w_at, img, u, u_words, len; FsTranscript tr; bool refused = false; std::string error; };
+    for (size_t g = 0; g < groups.size(); g++) {
+        const double t0 = omp_get_wtime();
+        const size_t G = groups[g].second - groups[g].first;
+        std::vector<Member> mem(G);
+        // the layout of the staged copy: the three tables, then every member's values, low coordinates and weights
+        size_t jobs_total = 0, claims_total = 0, u_total = 0, img_total = 0;
+        for (size_t m = 0; m < G; m++) {
+            Member& x = mem[m];
+            x.idx = groups[g].first + m;
+            x.n = items[x.idx].claims->size();
+            x.nw = nw_of(*items[x.idx].claims);
+            x.job0 = jobs_total; x.claim0 = claims_total; x.u = u_total; x.img = img_total;
+            x.u_words = 2 * C * (x.n + 1);
+            x.len = opening_bytes(sh, x.n, Q);
+            jobs_total += x.n + 1; claims_total += x.n; u_total += x.u_words; img_total += x.len / 8;
+        }
+        const size_t mem_at = 0, jobs_at = align16(G * sizeof(ObMember)), claims_at = jobs_at + align16(jobs_total * sizeof(ObJob));
+        size_t at = claims_at + align16(claims_total * sizeof(ObClaim));
+        for (Member& x : mem) {
+            x.y_at = at;
+            x.z_at = x.y_at + x.n * sizeof(E2);
+            x.w_at = x.z_at + x.n * (size_t)sh.c * sizeof(E2);
+            at = x.w_at + x.nw * sizeof(E2);
+        }
+        const size_t stage_bytes = std::max<size_t>(at, 16);
+        char* h_stage = batch_desc_host(B, stage_bytes);   // (the previous group's copy of it was waited for)
+        // results of the group, page-locked: the u vectors, the images, one cell a member
+        const size_t hu_at = 0, himg_at = u_total * 8, hcell_at = himg_at + img_total * 8;
+        char* h_out = batch_out_host(B, hcell_at + G * 8);
+        const u64* h_u = reinterpret_cast<const u64*>(h_out + hu_at);
+        uint8_t* h_img = reinterpret_cast<uint8_t*>(h_out + himg_at);
+        const u64* h_cells = reinterpret_cast<const u64*>(h_out + hcell_at);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
+        for (long long mq = 0; mq < (long long)G; mq++) {
+            Member& x = mem[mq];
+            try {
+                const Commitment& cm = *items[x.idx].cm;
+                const std::vector<Claim>& claims = *items[x.idx].claims;
+                x.tr = start_transcript(sh, cm.root(), claims, Q);
+                const std::vector<E2> rho = rho_powers(x.tr.squeeze(), R);
+                ObMember* hm = reinterpret_cast<ObMember*>(h_stage + mem_at) + mq;
+                hm->M = cm.d_M; hm->img = x.img; hm->u = x.u; hm->u_words = x.u_words;
+                ObJob* hd = reinterpret_cast<ObJob*>(h_stage + jobs_at) + x.job0;
+                ObClaim* hc = reinterpret_cast<ObClaim*>(h_stage + claims_at) + x.claim0;
+                E2* hy = reinterpret_cast<E2*>(h_stage + x.y_at);
+                E2* hz = reinterpret_cast<E2*>(h_stage + x.z_at);
+                E2* hw = reinterpret_cast<E2*>(h_stage + x.w_at);
+                hd[0].src = cm.d_rows; hd[0].nrows = R; hd[0].w_at = x.w_at; hd[0].u_at = x.u / 2;
+                memcpy(hw, rho.data(), R * sizeof(E2));
+                size_t off = R;
+                for (size_t i = 0; i < x.n; i++) {
+                    const Claim& cl = claims[i];
+                    const std::vector<E2> w = eq_table(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
+                    hd[i + 1].src = cm.d_rows + (sh.off[cl.table] << sh.c); hd[i + 1].nrows = w.size(); hd[i + 1].w_at = x.w_at + off * sizeof(E2);
+                    hd[i + 1].u_at = x.u / 2 + (i + 1) * C;
+                    memcpy(hw + off, w.data(), w.size() * sizeof(E2));
+                    off += w.size();
+                    hy[i] = cl.value;
+                    memcpy(hz + i * (size_t)sh.c, cl.point.data(), (size_t)sh.c * sizeof(E2));
+                    hc[i].u_at = hd[i + 1].u_at; hc[i].z_at = x.z_at + i * (size_t)sh.c * sizeof(E2); hc[i].y_at = x.y_at + i * sizeof(E2);
+                    hc[i].member = (u64)mq; hc[i].claim = (u64)i;
+                }
+            } catch (const std::exception& e) { x.error = e.what(); }
+        }
+        for (const Member& x : mem)
+            if (!x.error.empty()) throw Error(who + ": index " + std::to_string(x.idx) + ": " + x.error);
+        const double t1 = omp_get_wtime();
+        ctx->arena_reset();
+        char* d_stage;
+        u64 *d_u, *d_img, *d_js, *d_cells;
+        try {
+            d_stage = ctx->alloc_n<char>(stage_bytes);
+            d_u = ctx->alloc_n<u64>(u_total);
+            d_img = ctx->alloc_n<u64>(img_total);
+            d_js = ctx->alloc_n<u64>(G * Q + G);
+            d_cells = ctx->alloc_n<u64>(G);
+        } catch (const std::exception& e) {
+            throw Error(who + ": the context's arena cannot hold a group of " + std::to_string(G) + " openings: lower verify_batch_group (" + e.what() + ")");
+        }
+        const ObMember* d_mem = reinterpret_cast<const ObMember*>(d_stage + mem_at);
+        const unsigned cb = blocks_for(C);
+        if (jobs_total * cb > 0x7fffffffull) throw Error(who + ": a group of " + std::to_string(G) + " openings has too many row combinations for one launch: lower verify_batch_group");
+        hip_check(hipMemcpyAsync(d_stage, h_stage, stage_bytes, hipMemcpyHostToDevice, st), "upload claims");
+        hip_check(hipMemsetAsync(d_cells, 0xff, G * 8, st), "memset");
+        size_t nw_total = 0;
+        for (const Member& x : mem) nw_total += x.nw;
+        ctx->prof_begin(cls, (double)nw_total * C * 8 + (double)u_total * 8);
+        k_pcsob_combine<<<(unsigned)(jobs_total * cb), PCS_TPB, 0, st>>>(sh.c, cb, reinterpret_cast<const ObJob*>(d_stage + jobs_at), d_stage, reinterpret_cast<E2*>(d_u));
+        ctx->prof_end();
+        if (claims_total) {
+            ctx->prof_begin(cls, (double)claims_total * C * 16);
+            k_pcsob_eval<<<(unsigned)claims_total, PCS_TPB, 0, st>>>(reinterpret_cast<const ObClaim*>(d_stage + claims_at), sh.c, reinterpret_cast<const E2*>(d_u), d_stage, d_cells);
+            ctx->prof_end();
+        }
+        ctx->prof_begin(cls, (double)u_total * 16);
+        k_pcsob_emit<<<(unsigned)std::min<size_t>(blocks_for(u_total), 4096), PCS_TPB, 0, st>>>(d_mem, (unsigned)G, u_total, d_u, d_img);
+        ctx->prof_end();
+        hip_check(hipMemcpyAsync(h_out + hu_at, d_u, u_total * 8, hipMemcpyDeviceToHost, st), "download combinations");
+        hip_check(hipMemcpyAsync(h_out + hcell_at, d_cells, G * 8, hipMemcpyDeviceToHost, st), "download evaluation checks");
+        hip_check(hipStreamSynchronize(st), (who + ": sync").c_str());
+        hip_check(hipGetLastError(), (who + ": launch").c_str());
+        const double t2 = omp_get_wtime();
+        // the host's share: every member's u_i into its transcript, its column indices out of it, one member a thread
+        hj.assign(G * Q + G, 0);
+        size_t active = 0;
+        for (size_t m = 0; m < G; m++) {
+            mem[m].refused = h_cells[m] != PCSV_NONE;
+            hj[G * Q + m] = mem[m].refused ? 0 : 1;
+            active += mem[m].refused ? 0 : 1;
+        }
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
+        for (long long mq = 0; mq < (long long)G; mq++) {
+            Member& x = mem[mq];
+            if (x.refused) continue;
+            try {
+                absorb_words(x.tr, h_u + x.u, x.u_words);
+                const std::vector<size_t> js = squeeze_indices(x.tr, N, Q);
+                for (size_t q = 0; q < Q; q++) hj[(size_t)mq * Q + q] = js[q];
+            } catch (const std::exception& e) { x.error = e.what(); }
+        }
+        for (const Member& x : mem)
+            if (!x.error.empty()) throw Error(who + ": index " + std::to_string(x.idx) + ": " + x.error);
+        const double t3 = omp_get_wtime();
+        if (active) {
+            if (Q) {
+                hip_check(hipMemcpyAsync(d_js, hj.data(), hj.size() * 8, hipMemcpyHostToDevice, st), "upload column indices");
+                ctx->prof_begin(cls, (double)active * Q * R * 16);
+                k_pcsob_gather<<<blocks_for(G * Q * R), PCS_TPB, 0, st>>>(d_mem, G, Q, R, N, q_words, d_js, d_img);
+                ctx->prof_end();
+            }
+            hip_check(hipMemcpyAsync(h_img, d_img, img_total * 8, hipMemcpyDeviceToHost, st), "download openings");
+            hip_check(hipStreamSynchronize(st), (who + ": sync").c_str());
+            hip_check(hipGetLastError(), (who + ": launch").c_str());
+        }
+        ctx->prof_collect();
+        const double t4 = omp_get_wtime();
+        // the siblings from each handle's tree into the gaps; a refused member's reason
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
+        for (long long mq = 0; mq < (long long)G; mq++) {
+            Member& x = mem[mq];
+            try {
+                Opened& out = res[x.idx];
+                const Commitment& cm = *items[x.idx].cm;
+                if (x.refused) {
+                    const size_t i = (size_t)h_cells[mq];
+                    out.refused = true;
+                    out.reason = std::string(single) + ": claim " + std::to_string(i) + ": the value is not the evaluation of table " + std::to_string((*items[x.idx].claims)[i].table) +
+                                 " at the point";
+                    continue;
+                }
+                const uint8_t* image = h_img + 8 * x.img;
+                out.bytes.assign(image, image + x.len);
+                for (size_t q = 0; q < Q; q++) {
+                    uint8_t* sib = out.bytes.data() + 8 * (x.u_words + q * q_words + R);
+                    size_t idx = (size_t)hj[(size_t)mq * Q + q];
+                    for (int l = 0; l < depth; l++, idx >>= 1) memcpy(sib + 32 * l, cm.node(l, idx ^ 1), 32);
+                }
+            } catch (const std::exception& e) { x.error = e.what(); }
+        }
+        for (const Member& x : mem)
+            if (!x.error.empty()) throw Error(who + ": index " + std::to_string(x.idx) + ": " + x.error);
+        if (times)
+            fprintf(stderr, "[hg pcs] open group %zu of %zu members: transcripts and weights %.2f ms, combine, checks and u back %.2f, hash %.2f, gather and images back %.2f, "
+                            "siblings %.2f\n", g, G, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3, (omp_get_wtime() - t4) * 1e3);
+    }
+    return res;
 }
 
 }  // namespace pcs

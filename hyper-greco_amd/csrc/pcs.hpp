@@ -9,6 +9,7 @@
 // Merkle tree hashes LE64(0) || column j of the encoded matrix; an inner node hashes LE64(1) || left || right. An opening of n
 // claims carries u_0 = sum_r rho^r row_r, u_i = sum_r eq(z_i[c..])[r] row_{off_t + r} and Q opened columns with their paths.
 #pragma once
+#include <memory>
 #include <string>
 #include <vector>
 #include "host.hpp"
@@ -46,8 +47,9 @@ struct Commitment {
     Shape sh;
     hg_ctx* ctx = nullptr;          // null: host form
     std::vector<u64> rows, M;       // host form: R x C raw rows, R x 4C encoded rows
-    u64* d_rows = nullptr;          // device form: the same two matrices in HBM, owned
+    u64* d_rows = nullptr;          // device form: the same two matrices in HBM, owned unless `owner` is set
     u64* d_M = nullptr;
+    std::shared_ptr<void> owner;    // a handle of commit_device_batch: d_rows and d_M point into its group's slab, freed with the last handle
     std::vector<uint8_t> tree;
     const uint8_t* root() const { return tree.data() + 32 * (2 * sh.N() - 2); }
     const uint8_t* node(int level, size_t i) const { return tree.data() + 32 * (2 * sh.N() - ((2 * sh.N()) >> level) + i); }
@@ -63,6 +65,10 @@ std::vector<E2> eq_table(const E2* pt, size_t n);                               
 Commitment* commit_host(const Shape& sh, const u64* const* tables);
 // ---- device form (pcs.hip): rows staged and encoded in HBM, column hashes and the tree by kernels, one synchronisation
 Commitment* commit_device(hg_ctx* ctx, const Shape& sh, const u64* const* tables);
+// hg_pcs_commit_batch (pcs.hip): n members of one shape, tables[i * m + t] = table t of member i, in device passes of a group of
+// members each: every handle is what commit_device gives for that member, except that a group's matrices share one allocation.
+// Throws an Error naming `who` (and "index i" for a member's word that is not below p); no handle survives an error
+std::vector<Commitment*> commit_device_batch(const char* who, hg_ctx* ctx, const Shape& sh, const u64* const* tables, size_t n);
 // the levels above the 4C leaf hashes at d_tree (4 words a node, the levels one behind the other), enqueued on st; nodes are 32 bytes
 // in either field
 void merkle_levels_device(hipStream_t st, u64* d_tree, size_t N);
@@ -76,6 +82,12 @@ void columns_device(const Commitment& cm, const std::vector<size_t>& js, u64* co
 
 // hg_pcs_open: the opening bytes; an Error (naming `who` and the claim) if a value is not <u_i, eq(z_i[..c])>
 std::vector<uint8_t> open(const char* who, const Commitment& cm, const std::vector<Claim>& claims, size_t Q);
+// hg_pcs_open_batch (pcs.hip): item i's claims opened against its own device commitment (one shape, one context, one Q) in device
+// passes of a group of items each. refused: a value is not the evaluation (reason = open's error text under the name `single`, the
+// lowest failing claim; bytes empty); else bytes = what open gives for the item alone. Throws an Error naming `who`
+struct OpenItem { const Commitment* cm; const std::vector<Claim>* claims; };
+struct Opened { bool refused = false; std::string reason; std::vector<uint8_t> bytes; };
+std::vector<Opened> open_device_batch(const char* who, const char* single, hg_ctx* ctx, const std::vector<OpenItem>& items, size_t Q);
 // hg_pcs_verify: "" = accepted, else the reason
 std::string verify(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof, size_t len);
 // hg_pcs_verify_device (pcs.hip): the same decision and the same reason with the table-sized work on the context's stream; the

@@ -308,6 +308,17 @@ char* batch_desc_host(VerifyBatchBufs* B, size_t bytes) {
     return B->h_desc;
 }
 
+char* batch_out_host(VerifyBatchBufs* B, size_t bytes) {
+    if (bytes > B->out_cap) {
+        if (B->h_out) (void)hipHostFree(B->h_out);
+        B->h_out = nullptr;
+        B->out_cap = 0;
+        hip_check(hipHostMalloc((void**)&B->h_out, bytes, hipHostMallocDefault), "hipHostMalloc(batch results)");
+        B->out_cap = bytes;
+    }
+    return B->h_out;
+}
+
 namespace {
 // set s free again (its last copy waited for) and grown to `total` words
 void stage_set(VerifyBatchBufs* B, int s, size_t total, const std::string& w) {
@@ -391,6 +402,7 @@ void verify_batch_drop(hg_ctx* ctx) {
     for (auto p : b->h_in) if (p) (void)hipHostFree(p);
     for (auto p : b->d_in) if (p) (void)hipFree(p);
     if (b->h_desc) (void)hipHostFree(b->h_desc);
+    if (b->h_out) (void)hipHostFree(b->h_out);
     delete b;
     ctx->verify_batch = nullptr;
 }

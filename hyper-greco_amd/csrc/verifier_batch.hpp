@@ -19,10 +19,14 @@ struct VerifyBatchBufs {
     size_t words[2] = {0, 0};
     char* h_desc = nullptr;                  // page-locked descriptor staging of one group
     size_t desc_cap = 0;
+    char* h_out = nullptr;                   // page-locked results of one group (hg_pcs_open_batch: the u vectors and the opening images)
+    size_t out_cap = 0;
 };
 VerifyBatchBufs* batch_bufs(hg_ctx* ctx);
 // the page-locked descriptor staging, grown to `bytes` (call it only after the previous group's copy has been waited for)
 char* batch_desc_host(VerifyBatchBufs* B, size_t bytes);
+// the page-locked result buffer, grown to `bytes` (call it only when no copy into it is in flight)
+char* batch_out_host(VerifyBatchBufs* B, size_t bytes);
 
 // one proof's public inputs in a set, in the order of the single-proof verifiers: s, e, k1, ais (k), r1is (k), r2is, then ct0is -
 // the same signed integers in the same layout over both fields

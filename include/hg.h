@@ -79,7 +79,9 @@ void hg_destroy(hg_ctx* ctx);
  *   "verify_batch_group"  the most proofs one device pass of hg_verify_device_batch, hg_verify_device_batch_bn254,
  *                 hg_verify_public_batch or hg_verify_public_batch_bn254 holds, and the most openings one of
  *                 hg_pcs_verify_device_batch, hg_claims_verify_batch, hg_pcs_verify_device_batch_bn254 or
- *                 hg_claims_verify_batch_bn254 (default 0: sized from the memory budget, at most 64)
+ *                 hg_claims_verify_batch_bn254, the most members one device pass of hg_pcs_commit_batch or hg_secrets_commit_batch
+ *                 encodes and the most items one of hg_pcs_open_batch or hg_claims_open_batch opens (default 0: sized from the
+ *                 memory budget, at most 64)
  * Returns 0, or -1 for an unknown name. */
 int hg_set_option(hg_ctx* ctx, const char* name, int64_t value);
 
@@ -425,6 +427,63 @@ int hg_pcs_verify_device_batch(hg_ctx* ctx, const uint8_t* const* roots, const u
 int hg_claims_verify_batch(hg_ctx* ctx, const hg_params* params, const uint8_t* const* roots, size_t log2_row, const void* claims,
                            size_t claim_cap_each, const uint64_t* points, size_t coord_cap_each, const size_t* n_claims, size_t n_queries,
                            const uint8_t* const* openings, const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap);
+
+/* hg_pcs_commit_batch: hg_pcs_commit on a context for a run of n members of ONE shape (nvars, n_tables, log2_row); tables[i][t] = table
+ *   t of member i. Member i receives the handle commitments[i] and its root at roots + 32 i. Each handle is what hg_pcs_commit on the
+ *   same context returns for that member - the same root, the same host copy of the tree, the raw and the encoded matrix in HBM - and
+ *   hg_pcs_open, hg_claims_open, hg_pcs_open_batch and hg_pcs_free take it. Device only. Returns 0; n == 0 returns 0 and writes nothing.
+ *   The pass: the members are cut into groups - at most 64 or the context option "verify_batch_group", a byte budget of 2 GiB (a
+ *   member takes 128 MB at n=32768 k=16: its rows, its encoded rows and the NTT scratch), and the 65535 rows the batched NTT takes at
+ *   once. A group's rows and encoded rows live in ONE allocation (member stride R C and R N words); the tables are uploaded straight
+ *   into it; staging with the range check (one flag a member), one batched NTT over all G R rows, the column hashes (one thread per
+ *   member and column), the tree levels (one thread per member and node, the levels of at most 256 nodes in one workgroup a member)
+ *   each run as one launch over the group; one download fetches all trees and flags: one synchronisation a group. A member's handle
+ *   points into the group's allocation and shares its ownership: THE MEMORY RETURNS WHEN THE LAST HANDLE OF THE GROUP IS FREED.
+ *   -1 (nothing is written and no handle survives; hg_last_error begins with the function's name and gives "index i" where a member
+ *   is at fault): a null argument or null element, a shape outside the limits of hg_pcs_commit, more than 65535 rows in a member, a
+ *   word that is not below p (the lowest such member is named), a null context ("hg_pcs_commit_batch: no context", reported after the
+ *   argument checks), a group the arena cannot hold. It uses the context's arena like a prove: not concurrently with another call
+ *   on the same context.
+ * hg_secrets_commit_batch: the same pass on the five secret inputs of the witness handles ws[0 .. n-1] (tables as hg_secrets_commit
+ *   orders them). -1 also, naming the index: a witness built for other parameters.
+ * hg_pcs_open_batch: hg_pcs_open for a run of n items with one n_queries. Item i opens its own claims (n_claims[i] of them, 0 allowed;
+ *   tables[i], points[i], values[i] as hg_pcs_open takes them, NULL allowed where n_claims[i] == 0) against commitments[i]. Every
+ *   handle is a Goldilocks device handle of this context and all have one shape; a handle may appear more than once. Opening i is
+ *   written at openings + i*cap_each and its length to lens[i]: byte for byte what hg_pcs_open gives for that item alone (and what
+ *   the host form gives on a host commitment of the same tables). status[i] = 0 opened; 1 REFUSED - a value is not the evaluation of
+ *   its table at the point: lens[i] = 0, the item's buffer is untouched, and the slot at reasons + i*reason_cap holds the text
+ *   hg_pcs_open leaves in hg_last_error for that item (the lowest failing claim), NUL-terminated and cut to reason_cap; "" where the
+ *   item is opened; reasons may be NULL. The run continues, the other items are what they are without the refused one. Returns the
+ *   number of refused items; n == 0 returns 0 and writes nothing.
+ *   The pass, per group (at most 64 or "verify_batch_group" items, the 2 GiB budget): the host threads write every member's
+ *   transcript start, rho powers, weight tables eq(z[c..]) and the job, claim and member tables into one staged copy; the row
+ *   combinations run as one launch driven by the job table, a second checks <u_i, eq(z_i[..c])> == y_i per (member, claim) with one
+ *   cell a member for its lowest failing claim, a third writes the u vectors big-endian into the members' opening images; the u
+ *   vectors and the cells come back into page-locked memory (first synchronisation); the host threads absorb each member's u_i and
+ *   squeeze its indices, one member a thread; one copy uploads all indices, a gather writes the opened columns big-endian into the
+ *   images of the members that were not refused, the images come back (second synchronisation); the host copies the siblings from
+ *   each handle's tree. Two synchronisations a group, as hg_pcs_open has per item.
+ *   -1 (nothing is written; hg_last_error begins with the function's name and gives "index i" where an item is at fault; every item
+ *   is checked before anything is enqueued): a null argument or element, a host-form handle, a BN254 handle, a handle of another
+ *   context, handles of different shapes, a table index out of range, a non-canonical coordinate or value, more than 4096 claims,
+ *   n_queries above the limit, cap_each below the largest opening of the run (the text gives the bytes needed), a null context
+ *   ("hg_pcs_open_batch: no context", after the argument checks), a group the arena cannot hold. It uses the context's arena and
+ *   batch buffers: not concurrently with another call on the same context.
+ * hg_claims_open_batch: the same pass under the mapping of hg_claims_open, on the claim and point arrays exactly as
+ *   hg_verify_public_batch writes them (item i's claims at (hg_input_claim*)claims + i*claim_cap_each, its points at points +
+ *   2*i*coord_cap_each with point_off relative to its own block, its count n_claims[i]); a refused item's text is hg_claims_open's.
+ *   -1 also, naming the index: the mapping errors of hg_claims_verify_batch and a commitment that is not hg_secrets_commit's for
+ *   these parameters. The BN254 forms of these four entries do not exist yet. */
+int hg_pcs_commit_batch(hg_ctx* ctx, const uint64_t* const* const* tables, const uint32_t* nvars, size_t n_tables, size_t log2_row, size_t n,
+                        void** commitments, uint8_t* roots);
+int hg_secrets_commit_batch(hg_ctx* ctx, const hg_params* params, const hg_witness* const* ws, size_t n, size_t log2_row, void** commitments,
+                            uint8_t* roots);
+int hg_pcs_open_batch(hg_ctx* ctx, const void* const* commitments, const uint32_t* const* tables, const uint64_t* const* points,
+                      const uint64_t* const* values, const size_t* n_claims, size_t n_queries, size_t n, uint8_t* openings, size_t cap_each,
+                      size_t* lens, int* status, char* reasons, size_t reason_cap);
+int hg_claims_open_batch(hg_ctx* ctx, const hg_params* params, const void* const* commitments, const void* claims, size_t claim_cap_each,
+                         const uint64_t* points, size_t coord_cap_each, const size_t* n_claims, size_t n_queries, size_t n, uint8_t* openings,
+                         size_t cap_each, size_t* lens, int* status, char* reasons, size_t reason_cap);
 
 /* The same pair in a protocol mode that FIXES the reference's two known soundness gaps. mode bits:
  *   1  absorbing transcript: write_felt / read_felt also hash the element - the rule of the in-tree plonkish-trait writer of
