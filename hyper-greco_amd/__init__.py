@@ -58,6 +58,7 @@ EXPORTS = [
     "hg_pcs_commit_batch", "hg_secrets_commit_batch", "hg_pcs_open_batch", "hg_claims_open_batch",
     "hg_pcs_commit_bn254", "hg_pcs_open_bn254", "hg_pcs_verify_bn254", "hg_secrets_commit_bn254", "hg_claims_open_bn254", "hg_claims_verify_bn254",
     "hg_pcs_verify_device_bn254", "hg_claims_verify_device_bn254", "hg_pcs_verify_device_batch_bn254", "hg_claims_verify_batch_bn254",
+    "hg_pcs_commit_batch_bn254", "hg_secrets_commit_batch_bn254", "hg_pcs_open_batch_bn254", "hg_claims_open_batch_bn254",
     "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_mle_eval",
     "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_verify_public_bn254", "hg_verify_public_device_bn254", "hg_verify_public_batch_bn254", "hg_claims_settle_bn254", "hg_instance_mle_bn254", "hg_instance_mle_batch_bn254", "hg_prove_encryptions_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
 ]
@@ -107,11 +108,11 @@ def _two_field_protos(L):
     tail = [szp, sz, C.POINTER(cp), szp, sz, C.POINTER(ci), cp, sz]   # claim counts, n_queries, openings, lengths, n, results, reasons, reason_cap
     L.hg_pcs_verify_device_batch.argtypes = L.hg_pcs_verify_device_batch_bn254.argtypes = [vp, C.POINTER(cp), u32p, sz, sz, C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u64p)] + tail
     L.hg_claims_verify_batch.argtypes = L.hg_claims_verify_batch_bn254.argtypes = [vp, C.POINTER(HgParams), C.POINTER(cp), sz, vp, sz, u64p, sz] + tail
-    L.hg_pcs_commit_batch.argtypes = [vp, C.POINTER(C.POINTER(u64p)), u32p, sz, sz, sz, C.POINTER(vp), u8p]
-    L.hg_secrets_commit_batch.argtypes = [vp, C.POINTER(HgParams), C.POINTER(vp), sz, sz, C.POINTER(vp), u8p]
+    L.hg_pcs_commit_batch.argtypes = L.hg_pcs_commit_batch_bn254.argtypes = [vp, C.POINTER(C.POINTER(u64p)), u32p, sz, sz, sz, C.POINTER(vp), u8p]
+    L.hg_secrets_commit_batch.argtypes = L.hg_secrets_commit_batch_bn254.argtypes = [vp, C.POINTER(HgParams), C.POINTER(vp), sz, sz, C.POINTER(vp), u8p]
     opened = [szp, sz, sz, u8p, sz, szp, C.POINTER(ci), cp, sz]   # claim counts, n_queries, n, openings, cap_each, lengths, status, reasons, reason_cap
-    L.hg_pcs_open_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u64p)] + opened
-    L.hg_claims_open_batch.argtypes = [vp, C.POINTER(HgParams), C.POINTER(vp), vp, sz, u64p, sz] + opened
+    L.hg_pcs_open_batch.argtypes = L.hg_pcs_open_batch_bn254.argtypes = [vp, C.POINTER(vp), C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u64p)] + opened
+    L.hg_claims_open_batch.argtypes = L.hg_claims_open_batch_bn254.argtypes = [vp, C.POINTER(HgParams), C.POINTER(vp), vp, sz, u64p, sz] + opened
 
 
 _lib = None
@@ -1234,37 +1235,58 @@ class Commitment:
         return cls._secrets("goldilocks", ctx, params, witness, log2_row)
 
     @classmethod
-    def _batch(cls, call, ctx, n, nvars, log2_row):
-        """call(handles, roots) of a commit batch entry -> the n Commitments"""
+    def _batch(cls, call, ctx, n, nvars, log2_row, field="goldilocks"):
+        """call(handles, roots) of a commit batch entry of `field` -> the n Commitments"""
         hs, roots = (C.c_void_p * max(n, 1))(), (C.c_uint8 * (32 * max(n, 1)))()
         _check(call(hs, roots))
         c = pcs_row_log2(nvars, log2_row)
-        return [cls(C.c_void_p(hs[i]), bytes(roots[32 * i:32 * i + 32]), ctx, nvars, c) for i in range(n)]
+        return [cls(C.c_void_p(hs[i]), bytes(roots[32 * i:32 * i + 32]), ctx, nvars, c, field) for i in range(n)]
+
+    @classmethod
+    def _commit_batch(cls, field, ctx, tabs, words, log2_row):
+        n = len(tabs)
+        if not n:   # (no member, no shape to pass)
+            return []
+        nvars = [(t.size // words).bit_length() - 1 for t in tabs[0]]
+        if any([(t.size // words).bit_length() - 1 for t in tables] != nvars for tables in tabs):
+            raise ValueError("commit_batch: every member has the tables of one shape")
+        rows = [(u64p * len(nvars))(*[_ptr(t) for t in tables]) for tables in tabs]
+        ptrs = (C.POINTER(u64p) * max(n, 1))(*[C.cast(r, C.POINTER(u64p)) for r in rows])
+        nv = (C.c_uint32 * len(nvars))(*nvars)
+        fn = lib().hg_pcs_commit_batch_bn254 if field == "bn254" else lib().hg_pcs_commit_batch
+        return cls._batch(lambda hs, roots: fn(_h(ctx), ptrs, nv, len(nvars), log2_row, n, hs, roots), ctx, n, nvars, log2_row, field)
+
+    @classmethod
+    def _secrets_batch(cls, field, ctx, params, witnesses, log2_row):
+        n = len(witnesses)
+        ws = (C.c_void_p * max(n, 1))(*[w.h for w in witnesses])
+        lg = params.n.bit_length() - 1
+        nvars = [lg + 1] * (3 + params.k) + [lg + params.k.bit_length() - 1]
+        fn = lib().hg_secrets_commit_batch_bn254 if field == "bn254" else lib().hg_secrets_commit_batch
+        return cls._batch(lambda hs, roots: fn(_h(ctx), C.byref(params), ws, n, log2_row, hs, roots), ctx, n, nvars, log2_row, field)
 
     @classmethod
     def commit_batch(cls, ctx, tables_list, log2_row=0):
         """hg_pcs_commit_batch: one device Commitment per entry of tables_list (each as commit takes it), all of one shape, their
         matrices encoded and hashed in device passes of a group of members each."""
-        tabs = [[np.ascontiguousarray(t, dtype=np.uint64) for t in tables] for tables in tables_list]
-        n = len(tabs)
-        if not n:   # (no member, no shape to pass)
-            return []
-        nvars = [t.size.bit_length() - 1 for t in tabs[0]]
-        if any([t.size.bit_length() - 1 for t in tables] != nvars for tables in tabs):
-            raise ValueError("commit_batch: every member has the tables of one shape")
-        rows = [(u64p * len(nvars))(*[_ptr(t) for t in tables]) for tables in tabs]
-        ptrs = (C.POINTER(u64p) * max(n, 1))(*[C.cast(r, C.POINTER(u64p)) for r in rows])
-        nv = (C.c_uint32 * len(nvars))(*nvars)
-        return cls._batch(lambda hs, roots: lib().hg_pcs_commit_batch(_h(ctx), ptrs, nv, len(nvars), log2_row, n, hs, roots), ctx, n, nvars, log2_row)
+        return cls._commit_batch("goldilocks", ctx, [[np.ascontiguousarray(t, dtype=np.uint64) for t in tables] for tables in tables_list], 1, log2_row)
 
     @classmethod
     def secrets_batch(cls, ctx, params, witnesses, log2_row=0):
         """hg_secrets_commit_batch: one device Commitment to the five secret inputs of every witness handle."""
-        n = len(witnesses)
-        ws = (C.c_void_p * max(n, 1))(*[w.h for w in witnesses])
-        lg = params.n.bit_length() - 1
-        nvars = [lg + 1] * (3 + params.k) + [lg + params.k.bit_length() - 1]
-        return cls._batch(lambda hs, roots: lib().hg_secrets_commit_batch(_h(ctx), C.byref(params), ws, n, log2_row, hs, roots), ctx, n, nvars, log2_row)
+        return cls._secrets_batch("goldilocks", ctx, params, witnesses, log2_row)
+
+    @classmethod
+    def commit_batch_bn254(cls, ctx, tables_list, log2_row=0):
+        """hg_pcs_commit_batch_bn254: commit_batch over bn256::Fr, each member's tables as commit_bn254 takes them; the handles are
+        BN254 handles."""
+        return cls._commit_batch("bn254", ctx, [[_fr_table(t) for t in tables] for tables in tables_list], 4, log2_row)
+
+    @classmethod
+    def secrets_batch_bn254(cls, ctx, params, witnesses, log2_row=0):
+        """hg_secrets_commit_batch_bn254: one device BN254 Commitment to the five secret inputs of every witness handle, every word
+        lifted into Fr by the signed rule."""
+        return cls._secrets_batch("bn254", ctx, params, witnesses, log2_row)
 
     def _open(self, entry, head, n_claims, tail, n_queries):
         """entry(ctx, *head, n_claims, *tail, n_queries, buffer, its size, length out) of the handle's field -> the opening bytes"""
@@ -1297,12 +1319,12 @@ class Commitment:
             pass
 
 
-def _open_batch(call, cms, counts, n_queries, reason_cap):
+def _open_batch(call, cms, counts, n_queries, reason_cap, opening_bytes=pcs_opening_bytes):
     """One call of an open batch entry: call(handles, counts, n_queries, n, openings, cap_each, lens, status, reasons, reason_cap) ->
-    [(the opening bytes or None, reason)]"""
+    [(the opening bytes or None, reason)]; opening_bytes sizes the buffers (pcs_opening_bytes_bn254 for the BN254 entries)"""
     n = len(cms)
     m = max(n, 1)
-    cap = max([pcs_opening_bytes(cm.nvars, k, n_queries, cm.log2_row) for cm, k in zip(cms, counts)] + [8])
+    cap = max([opening_bytes(cm.nvars, k, n_queries, cm.log2_row) for cm, k in zip(cms, counts)] + [8])
     hs = (C.c_void_p * m)(*[cm.h for cm in cms])
     nc = (C.c_size_t * m)(*counts)
     buf = np.zeros(m * cap, dtype=np.uint8)
@@ -1313,29 +1335,52 @@ def _open_batch(call, cms, counts, n_queries, reason_cap):
     return [(None if status[i] else buf[i * cap:i * cap + lens[i]].tobytes(), raw[i * reason_cap:(i + 1) * reason_cap].split(b"\0", 1)[0].decode()) for i in range(n)]
 
 
+def _pcs_open_batch_of(sfx, arrays_of, opening_bytes, ctx, cms, claims_list, n_queries, reason_cap):
+    """hg_pcs_open_batch + sfx on claim lists that arrays_of turns into (table, points, values)"""
+    if len(cms) != len(claims_list):
+        raise ValueError(f"pcs_open_batch{sfx}: one claim list per commitment")
+    m = max(len(cms), 1)
+    arrays = [arrays_of(c) for c in claims_list]
+    tabs = (u32p * m)(*[C.cast(a[0], u32p) for a in arrays])
+    pts = (u64p * m)(*[_ptr(a[1]) for a in arrays])
+    vals = (u64p * m)(*[_ptr(a[2]) for a in arrays])
+    fn = getattr(lib(), "hg_pcs_open_batch" + sfx)
+    return _open_batch(lambda hs, nc, *rest: fn(_h(ctx), hs, tabs, pts, vals, nc, *rest), cms, [len(c) for c in claims_list], n_queries, reason_cap, opening_bytes)
+
+
+def _claims_open_batch_of(F, opening_bytes, ctx, params, cms, claims_list, n_queries, reason_cap):
+    """hg_claims_open_batch of field F"""
+    if len(cms) != len(claims_list):
+        raise ValueError(f"claims_open_batch{F.SFX}: one {F.__name__} per commitment")
+    claims, nc1, points, nco1, counts = _claims_batch_arrays(claims_list, F)
+    fn = getattr(lib(), "hg_claims_open_batch" + F.SFX)
+    return _open_batch(lambda hs, nc, *rest: fn(_h(ctx), C.byref(params), hs, claims, nc1, _ptr(points), nco1, nc, *rest), cms, list(counts)[:len(cms)], n_queries, reason_cap,
+                       opening_bytes)
+
+
 def pcs_open_batch(ctx, cms, claims_list, n_queries=0, reason_cap=256):
     """hg_pcs_open_batch: claims_list[i] (claims as Commitment.open takes them; an empty list is allowed) opened against the device
     Commitment cms[i], all of one shape: [(bytes or None, reason)] - the bytes of cms[i].open(claims_list[i]), or None and the text of
     its error where a value is not the evaluation."""
-    if len(cms) != len(claims_list):
-        raise ValueError("pcs_open_batch: one claim list per commitment")
-    m = max(len(cms), 1)
-    arrays = [_pcs_claim_arrays(c) for c in claims_list]
-    tabs = (u32p * m)(*[C.cast(a[0], u32p) for a in arrays])
-    pts = (u64p * m)(*[_ptr(a[1]) for a in arrays])
-    vals = (u64p * m)(*[_ptr(a[2]) for a in arrays])
-    fn = lib().hg_pcs_open_batch
-    return _open_batch(lambda hs, nc, *rest: fn(_h(ctx), hs, tabs, pts, vals, nc, *rest), cms, [len(c) for c in claims_list], n_queries, reason_cap)
+    return _pcs_open_batch_of("", _pcs_claim_arrays, pcs_opening_bytes, ctx, cms, claims_list, n_queries, reason_cap)
 
 
 def claims_open_batch(ctx, params, cms, claims_list, n_queries=0, reason_cap=256):
     """hg_claims_open_batch: the InputClaims claims_list[i] (what verify_public_batch returns; None stands for no claims) opened
     against the Commitment.secrets / secrets_batch handle cms[i]: [(bytes or None, reason)]."""
-    if len(cms) != len(claims_list):
-        raise ValueError("claims_open_batch: one InputClaims per commitment")
-    claims, nc1, points, nco1, counts = _claims_batch_arrays(claims_list)
-    fn = lib().hg_claims_open_batch
-    return _open_batch(lambda hs, nc, *rest: fn(_h(ctx), C.byref(params), hs, claims, nc1, _ptr(points), nco1, nc, *rest), cms, list(counts)[:len(cms)], n_queries, reason_cap)
+    return _claims_open_batch_of(InputClaims, pcs_opening_bytes, ctx, params, cms, claims_list, n_queries, reason_cap)
+
+
+def pcs_open_batch_bn254(ctx, cms, claims_list, n_queries=0, reason_cap=256):
+    """hg_pcs_open_batch_bn254: pcs_open_batch over bn256::Fr on device BN254 Commitments, claims as Commitment.open takes them on a
+    BN254 handle: [(bytes or None, reason)] - the bytes of cms[i].open(claims_list[i]), or None and the text of its error."""
+    return _pcs_open_batch_of("_bn254", _pcs_claim_arrays_bn254, pcs_opening_bytes_bn254, ctx, cms, claims_list, n_queries, reason_cap)
+
+
+def claims_open_batch_bn254(ctx, params, cms, claims_list, n_queries=0, reason_cap=256):
+    """hg_claims_open_batch_bn254: the InputClaimsBn254 claims_list[i] (what verify_public_batch_bn254 returns; None stands for no
+    claims) opened against the Commitment.secrets_bn254 / secrets_batch_bn254 handle cms[i]: [(bytes or None, reason)]."""
+    return _claims_open_batch_of(InputClaimsBn254, pcs_opening_bytes_bn254, ctx, params, cms, claims_list, n_queries, reason_cap)
 
 
 def _pcs_verify(sfx, arrays, root, nvars, claims, proof, n_queries, log2_row, ctx):

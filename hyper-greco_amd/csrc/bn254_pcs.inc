@@ -5,6 +5,8 @@
 // (pcs_keccak.hpp, pcs::merkle_levels_device): a node is 32 bytes in either field.
 // The verifier of an opening (pcs_verify_device) reuses the encoding, the leaf sponge and the accumulators and adds five kernels.
 // The verifier of a run of openings (pcs_verify_device_batch) runs the same five kernels once over a group, driven by a member table.
+// A run of commitments (pcs_commit_device_batch) and a run of openings (pcs_open_device_batch) do the same for the prover's side: a
+// group's matrices in one allocation that its handles share, the kernels of commit and open once over the group.
 
 constexpr int BNPCS_TPB = 256;
 static unsigned bnpcs_blocks(size_t n) { return (unsigned)((n + BNPCS_TPB - 1) / BNPCS_TPB); }
@@ -853,4 +855,422 @@ std::vector<std::string> pcs_verify_device_batch(const char* who_c, hg_ctx* ctx,
         }
     }
     return why;
+}
+
+// ---- a run of commitments (pcs_commit_device_batch): the kernels of pcs_commit_device with a member in front of every index. The
+// members of a group share the shape; member m's raw rows lie at rows + m R C, its encoded rows at M + m R N and its tree at
+// trees + m tree_words. Every grid is one-dimensional over (member, item).
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsb_stage(const Fr* __restrict__ rows, Fr* __restrict__ M, size_t G, size_t R, int c, unsigned* __restrict__ flags) {
+    const size_t per = R << (c + 2), total = G * per;
+    const size_t C = (size_t)1 << c, Nm = ((size_t)4 << c) - 1;
+    for (size_t i = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * BNPCS_TPB) {
+        const size_t m = i / per, k = i - m * per, r = k >> (c + 2), j = k & Nm;
+        Fr v = fr_zero();
+        if (j < C) {
+            v = lz_gload(rows + ((m * R + r) << c) + j);
+            if (fr_geq_p(v)) atomicOr(flags + m, 1u);   // all four limbs compared; one flag a member
+        }
+        lz_gstore(M + i, v);
+    }
+}
+// One thread per (member m, column j), id = m N + j: k_bnpcs_leaf_hash on the member's own matrix, into the leaves of its own tree.
+// A member's columns may begin inside a wavefront (N < 64): every address below comes from the thread's own m and j.
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsb_leaf_hash(const Fr* __restrict__ M, size_t G, size_t N, size_t R, u64* __restrict__ trees, size_t tree_words) {
+    const size_t id = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
+    if (id >= G * N) return;
+    const size_t m = id / N, j = id - m * N;
+    u64 a[25];
+    bnpcs_leaf_absorb(reinterpret_cast<const u64*>(M + m * R * N + j), 4 * N, R, a);   // 4N words between the rows
+    u64* out = trees + m * tree_words + 4 * j;
+    out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
+}
+
+// hg_pcs_commit_batch_bn254. A group: one allocation for its members' raw and encoded rows (a freed group's, where the context
+// holds one that fits: pcs::SlabSpares), the tables (or, `words`, the witness
+// words, lifted by one k_bnpcs_lift over the group) uploaded straight into it, then k_bnpcsb_stage, the encoding in slices of whole
+// members through ONE slice's temporary (the slices follow each other on the stream, so the temporary does not grow with the
+// group), the leaf hashes, the tree levels of pcs::merkle_levels_device_batch, one download of all trees and flags, one
+// synchronisation.
+constexpr size_t BNPCSB_NTT_TMP = (size_t)256 << 20;   // the temporary of one slice: at least one member, else what fits in here
+std::vector<pcs::Commitment*> pcs_commit_device_batch(const char* who_c, hg_ctx* ctx, const pcs::Shape& sh, const u64* const* tables, size_t n, bool words) {
+    const std::string who(who_c);
+    const size_t C = sh.C(), N = sh.N(), R = sh.R, nt = sh.nvars.size();
+    const int log2n = sh.depth();
+    if (R > 65535) throw Error(who + ": more than 65535 rows (choose a larger log2_row)");
+    const size_t tree_words = 8 * N;   // 2N nodes of 4 words: the 2N - 1 of a tree and one unused
+    const size_t member_bytes = sizeof(Fr) * (R * C + R * N);
+    // ntt_batch_dev: the batch is the y extent of its four-step grids, and a slice is at most a group
+    const std::vector<std::pair<size_t, size_t>> groups = pcs::cut_groups(ctx, n, [&](size_t) { return member_bytes; }, R, 65535, VB_PCS_COMMIT_BUDGET_BN254);
+    hipc(hipSetDevice(ctx->device), "hipSetDevice");
+    hipStream_t st = ctx->stream;
+    const std::shared_ptr<pcs::SlabSpares> spares = batch_bufs(ctx)->slabs;
+    std::vector<std::unique_ptr<pcs::Commitment>> made;
+    std::vector<u64> h_out;   // (declared ahead of the guard: a copy into it may be queued when it drains)
+    pcs::DrainOne drain{st};
+    hipc(hipStreamSynchronize(st), (who + ": synchronise").c_str());   // (the arena is reset below)
+    const int cls = ctx->prof_class("pcs_bn254_commit_batch", false);
+    ctx->prof_stream = st;
+    const bool times = hg_times("pcs");   // HG_TIMES=pcs: where a group's wall clock goes, on stderr
+    for (const auto& grp : groups) {
+        const double t0 = omp_get_wtime();
+        const size_t first = grp.first, G = grp.second - grp.first;
+        const size_t slice = std::min(G, std::max<size_t>(1, BNPCSB_NTT_TMP / (R * N * sizeof(Fr))));   // members a slice
+        std::shared_ptr<pcs::Slab> slab = std::make_shared<pcs::Slab>();
+        slab->home = spares;
+        slab->p = spares->take(G * member_bytes, &slab->bytes);   // a freed group's allocation, if the context holds one that fits
+        if (!slab->p) {
+            hipc(hipMalloc((void**)&slab->p, G * member_bytes), "hipMalloc(pcs rows and encoded matrices of a group)");
+            slab->bytes = G * member_bytes;
+        }
+        Fr* d_rows = reinterpret_cast<Fr*>(slab->p);
+        Fr* d_M = d_rows + G * R * C;
+        const double t1 = omp_get_wtime();
+        ctx->arena_reset();
+        Fr *tmp, *W;
+        u64 *d_out, *d_words = nullptr;
+        const size_t out_words = G * tree_words + (G + 1) / 2;   // the trees, then one 32-bit flag a member
+        try {
+            tmp = ctx->alloc_n<Fr>(slice * R * N);
+            W = ctx->alloc_n<Fr>(N);
+            d_out = ctx->alloc_n<u64>(out_words);
+            if (words) d_words = ctx->alloc_n<u64>(G * R * C);
+        } catch (const std::exception& e) {
+            throw Error(who + ": the context's arena cannot hold a group of " + std::to_string(G) + " commitments: lower verify_batch_group (" + e.what() + ")");
+        }
+        unsigned* d_flags = reinterpret_cast<unsigned*>(d_out + G * tree_words);
+        hipc(hipMemsetAsync(d_flags, 0, ((G + 1) / 2) * 8, st), "memset");
+        for (size_t m = 0; m < G; m++)
+            for (size_t t = 0; t < nt; t++) {
+                const size_t len = (size_t)1 << sh.nvars[t], at = (m * R + sh.off[t]) * C;
+                if (words) hipc(hipMemcpyAsync(d_words + at, tables[(first + m) * nt + t], len * 8, hipMemcpyHostToDevice, st), "upload tables");
+                else hipc(hipMemcpyAsync(d_rows + at, tables[(first + m) * nt + t], len * sizeof(Fr), hipMemcpyHostToDevice, st), "upload tables");
+            }
+        const double t2 = omp_get_wtime();
+        ctx->prof_begin(cls, (double)G * R * C * (words ? 40 : 0) + (double)G * R * (C + N) * 32);
+        if (words) k_bnpcs_lift<<<(unsigned)std::min<size_t>(bnpcs_blocks(G * R * C), 4096), BNPCS_TPB, 0, st>>>(d_words, d_rows, G * R * C);
+        k_bnpcsb_stage<<<(unsigned)std::min<size_t>(bnpcs_blocks(G * R * N), 4096), BNPCS_TPB, 0, st>>>(d_rows, d_M, G, R, sh.c, d_flags);
+        ctx->prof_end();
+        ctx->prof_begin(cls, (double)G * R * N * 32 * 4);
+        k_bn_powers<<<bnpcs_blocks(N), 256, 0, st>>>(W, fr_root_of_unity(log2n), N);
+        for (size_t m0 = 0; m0 < G; m0 += slice) ntt_batch_dev(st, d_M + m0 * R * N, tmp, W, log2n, std::min(slice, G - m0) * R, nullptr);
+        ctx->prof_end();
+        ctx->prof_begin(cls, (double)G * R * N * 32);
+        k_bnpcsb_leaf_hash<<<bnpcs_blocks(G * N), BNPCS_TPB, 0, st>>>(d_M, G, N, R, d_out, tree_words);
+        ctx->prof_end();
+        ctx->prof_begin(cls, (double)G * N * 96);
+        pcs::merkle_levels_device_batch(st, d_out, tree_words, N, G);
+        ctx->prof_end();
+        h_out.resize(out_words);
+        hipc(hipMemcpyAsync(h_out.data(), d_out, out_words * 8, hipMemcpyDeviceToHost, st), "download trees and flags");
+        const double t3 = omp_get_wtime();
+        hipc(hipStreamSynchronize(st), (who + ": sync").c_str());
+        const double t4 = omp_get_wtime();
+        hipc(hipGetLastError(), (who + ": launch").c_str());
+        ctx->prof_collect();
+        const unsigned* flags = reinterpret_cast<const unsigned*>(h_out.data() + G * tree_words);
+        for (size_t m = 0; m < G; m++)
+            if (flags[m]) throw Error(who + ": index " + std::to_string(first + m) + ": a table holds an element that is not below r");
+        for (size_t m = 0; m < G; m++) {
+            std::unique_ptr<pcs::Commitment> cm(new pcs::Commitment());
+            cm->field = pcs::BN254;
+            cm->sh = sh;
+            cm->ctx = ctx;
+            cm->d_rows = reinterpret_cast<u64*>(d_rows + m * R * C);
+            cm->d_M = reinterpret_cast<u64*>(d_M + m * R * N);
+            cm->owner = slab;
+            const uint8_t* tree = reinterpret_cast<const uint8_t*>(h_out.data() + m * tree_words);
+            cm->tree.assign(tree, tree + 32 * (2 * N - 1));
+            made.push_back(std::move(cm));
+        }
+        if (times)
+            fprintf(stderr, "[hg pcs] bn254 commit group of %zu members (%zu a slice of the encoding): allocation %.2f ms, uploads %.2f, enqueue %.2f, wait %.2f, trees into the handles %.2f\n",
+                    G, slice, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3, (omp_get_wtime() - t4) * 1e3);
+    }
+    std::vector<pcs::Commitment*> out;
+    for (auto& cm : made) out.push_back(cm.release());
+    return out;
+}
+
+// ---- a run of openings (pcs_open_device_batch). What differs by item lies in three flat tables of the group's staged copy: a job a
+// row combination (the proximity combination and one a claim, every member's behind the other), a claim an evaluation check, a
+// member where its matrix, its u vectors and its opening image lie. Every block of the staged copy starts at a multiple of 32 bytes
+// (lz_gload reads 16-byte halves). Every grid is one-dimensional.
+struct BnObJob { const Fr* src; u64 nrows, w_at, u_at; };      // its first raw row; the byte offset of its weights in the staged copy; where u goes (elements)
+struct BnObClaim { u64 u_at, z_at, y_at, member, claim; };     // its u_i (elements); byte offsets of the low coordinates (Montgomery) and of the value
+struct BnObMember { const Fr* M; u64 img, u, u_words; };       // its encoded matrix; word offsets of its image and of its u vectors; 4 C (n + 1)
+
+// k_bnpcs_combine driven by the job table: workgroup b serves job b / cb alone, columns (b % cb) BNPCS_TPB .. - the weight limbs go
+// through readfirstlane, so every lane of a wavefront must be on one job
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_combine(int c, unsigned cb, const BnObJob* __restrict__ jobs, const char* __restrict__ stage, Fr* __restrict__ u) {
+    const size_t C = (size_t)1 << c;
+    const unsigned jq = blockIdx.x / cb;
+    const size_t j = (size_t)(blockIdx.x - jq * cb) * BNPCS_TPB + threadIdx.x;
+    if (j >= C) return;
+    const BnObJob job = jobs[jq];
+    const Fr* src = job.src + j;
+    const u32* wq = reinterpret_cast<const u32*>(stage + job.w_at);
+    Fr s = fr_zero();
+    for (u64 r0 = 0; r0 < job.nrows; r0 += BNPCS_CHUNK) {
+        const u64 r1 = r0 + BNPCS_CHUNK < job.nrows ? r0 + BNPCS_CHUNK : job.nrows;
+        WCol A = wcol_zero();
+        for (u64 r = r0; r < r1; r++) {
+            const Fr x = lz_gload(src + (r << c));
+            u32 bl[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) bl[k] = __builtin_amdgcn_readfirstlane(wq[8 * r + k]);
+            bnpcs_mac_uniform(A, x, bl);
+        }
+        s = lz_add(s, lz_reduce(A));
+    }
+    lz_gstore(u + job.u_at + j, lz_canon(s));
+}
+// One workgroup per (member, claim), the arithmetic of k_bnpcsvb_eval: <u_i, eq(z_i[..c])> == y_i; cells[member] = its lowest failing claim
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_eval(const BnObClaim* __restrict__ claims, int c, const Fr* __restrict__ u, const char* __restrict__ stage,
+                                                            u64* __restrict__ cells) {
+    __shared__ Fr part[BNPCS_TPB];
+    const BnObClaim cl = claims[blockIdx.x];
+    const size_t C = (size_t)1 << c;
+    const Fr* z = reinterpret_cast<const Fr*>(stage + cl.z_at);
+    const Fr* ui = u + cl.u_at;
+    const int lob = c < 8 ? c : 8;
+    Fr f = fr_one_mont();
+    for (int b = 0; b < lob; b++) { const Fr zb = lz_gload(z + b); f = fr_mul(f, (threadIdx.x >> b) & 1 ? zb : fr_sub(fr_one_mont(), zb)); }
+    Fr s = fr_zero();
+    for (size_t x = threadIdx.x; x < C; x += BNPCS_TPB) {
+        Fr gq = f;
+        for (int b = 8; b < c; b++) { const Fr zb = lz_gload(z + b); gq = fr_mul(gq, (x >> b) & 1 ? zb : fr_sub(fr_one_mont(), zb)); }
+        s = fr_add(s, fr_mul(lz_gload(ui + x), gq));
+    }
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = BNPCS_TPB / 2; h >= 1; h >>= 1) {
+        if (threadIdx.x < h) part[threadIdx.x] = fr_add(part[threadIdx.x], part[threadIdx.x + h]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && !fr_eq(part[0], lz_gload(reinterpret_cast<const Fr*>(stage + cl.y_at)))) bnpcsv_min(cells + cl.member, cl.claim);
+}
+// Word i of the group's u vectors into its member's image, an element as 32 bytes big-endian: word w of the image's element is the
+// byte-swapped limb 3 - w. The member is the last one whose u offset is <= i (offsets are multiples of 4: an element never straddles)
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_emit(const BnObMember* __restrict__ mem, unsigned G, size_t total, const u64* __restrict__ u, u64* __restrict__ img) {
+    for (size_t i = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * BNPCS_TPB) {
+        unsigned lo = 0, hi = G;
+        while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].u <= i) lo = mid; else hi = mid; }
+        img[mem[lo].img + (i - mem[lo].u)] = __builtin_bswap64(u[i ^ 3]);
+    }
+}
+// One thread per (member m, query q, row r), id = (m Q + q) R + r: M_m[r][j_q] big-endian at its place in the member's image.
+// js[m Q + q] = j_q (masked by the host); js[G Q + m] != 0: the member takes part (it was not refused)
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_gather(const BnObMember* __restrict__ mem, size_t G, size_t Q, size_t R, size_t N, size_t q_words,
+                                                              const u64* __restrict__ js, u64* __restrict__ img) {
+    const size_t id = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
+    if (id >= G * Q * R) return;
+    const size_t m = id / (Q * R), k = id - m * Q * R, q = k / R, r = k - q * R;
+    if (!js[G * Q + m]) return;
+    const BnObMember M = mem[m];
+    const Fr v = lz_gload(M.M + r * N + js[m * Q + q]);
+    u64* out = img + M.img + M.u_words + q * q_words + 4 * r;
+    out[0] = __builtin_bswap64(v.l[3]); out[1] = __builtin_bswap64(v.l[2]); out[2] = __builtin_bswap64(v.l[1]); out[3] = __builtin_bswap64(v.l[0]);
+}
+
+// hg_pcs_open_batch_bn254, pcs::open_device_batch step for step. A group: the host threads write every member's transcript start,
+// rho powers, weight tables (Montgomery form) and table entries into one staged copy; the combinations, the evaluation checks and
+// the big-endian u vectors run as one launch each; the u vectors and one cell a member come back (first synchronisation); the host
+// threads hash each member's u_i, one member a thread; all indices go up, the gather writes the opened columns into the images, the
+// images come back (second synchronisation); the host copies the siblings from each handle's tree into the gaps.
+std::vector<pcs::Opened> pcs_open_device_batch(const char* who_c, const char* single, hg_ctx* ctx, const std::vector<PcsOpenItem>& items, size_t Q) {
+    const std::string who(who_c);
+    std::vector<pcs::Opened> res(items.size());
+    if (items.empty()) return res;
+    const pcs::Shape& sh = items[0].cm->sh;
+    const size_t C = sh.C(), N = sh.N(), R = sh.R;
+    const int depth = sh.depth();
+    const size_t q_words = 4 * (R + (size_t)depth);   // a query in the image: R elements and `depth` siblings, 4 words each
+    auto align32 = [](size_t x) { return (x + 31) & ~(size_t)31; };
+    auto nw_of = [&](const std::vector<PcsClaim>& cl) { size_t nw = R; for (const PcsClaim& x : cl) nw += (size_t)1 << (sh.nvars[x.table] - sh.c); return nw; };
+    // what a member takes: its block of the staged copy, its u vectors and its image in the arena, its indices
+    auto bytes_of = [&](size_t i) {
+        const std::vector<PcsClaim>& cl = *items[i].claims;
+        return sizeof(BnObMember) + (cl.size() + 1) * sizeof(BnObJob) + cl.size() * (sizeof(BnObClaim) + (size_t)(sh.c + 1) * sizeof(Fr)) + nw_of(cl) * sizeof(Fr) + 128 +
+               sizeof(Fr) * C * (cl.size() + 1) + pcs_opening_bytes(sh, cl.size(), Q) + 8 * Q + 16;
+    };
+    const std::vector<std::pair<size_t, size_t>> groups = pcs::cut_groups(ctx, items.size(), bytes_of, 0, 0);
+    hipc(hipSetDevice(ctx->device), "hipSetDevice");
+    VerifyBatchBufs* B = batch_bufs(ctx);
+    hipStream_t st = ctx->stream;
+    std::vector<u64> hj;   // (declared ahead of the guard: a copy of it may be queued when it drains)
+    pcs::DrainOne drain{st};
+    hipc(hipStreamSynchronize(st), (who + ": synchronise").c_str());   // (the arena is reset below)
+    [[maybe_unused]] const int nthr = std::max(1, hg_omp_threads());   // (the device pass of hipcc ignores the pragmas)
+    const int cls = ctx->prof_class("pcs_bn254_open_batch", false);
+    ctx->prof_stream = st;
+    const bool times = hg_times("pcs");   // HG_TIMES=pcs: where a group's wall clock goes, on stderr
+
+    struct Member { size_t idx, n, nw, job0, claim0, y_at, z_at, w_at, img, u, u_words, len; FsTranscript tr; bool refused = false; std::string error; };
+    for (size_t g = 0; g < groups.size(); g++) {
+        const double t0 = omp_get_wtime();
+        const size_t G = groups[g].second - groups[g].first;
+        std::vector<Member> mem(G);
+        // the layout of the staged copy: the three tables, then every member's values, low coordinates and weights
+        size_t jobs_total = 0, claims_total = 0, u_total = 0, img_total = 0;   // u_total, img_total: words
+        for (size_t m = 0; m < G; m++) {
+            Member& x = mem[m];
+            x.idx = groups[g].first + m;
+            x.n = items[x.idx].claims->size();
+            x.nw = nw_of(*items[x.idx].claims);
+            x.job0 = jobs_total; x.claim0 = claims_total; x.u = u_total; x.img = img_total;
+            x.u_words = 4 * C * (x.n + 1);
+            x.len = pcs_opening_bytes(sh, x.n, Q);
+            jobs_total += x.n + 1; claims_total += x.n; u_total += x.u_words; img_total += x.len / 8;
+        }
+        const size_t mem_at = 0, jobs_at = align32(G * sizeof(BnObMember)), claims_at = jobs_at + align32(jobs_total * sizeof(BnObJob));
+        size_t at = claims_at + align32(claims_total * sizeof(BnObClaim));
+        for (Member& x : mem) {   // (elements of 32 bytes from a multiple of 32 on)
+            x.y_at = at;
+            x.z_at = x.y_at + x.n * sizeof(Fr);
+            x.w_at = x.z_at + x.n * (size_t)sh.c * sizeof(Fr);
+            at = x.w_at + x.nw * sizeof(Fr);
+        }
+        const size_t stage_bytes = std::max<size_t>(at, 32);
+        char* h_stage = batch_desc_host(B, stage_bytes);   // (the previous group's copy of it was waited for)
+        // results of the group, page-locked: the u vectors, the images, one cell a member
+        const size_t hu_at = 0, himg_at = u_total * 8, hcell_at = himg_at + img_total * 8;
+        char* h_out = batch_out_host(B, hcell_at + G * 8);
+        const u64* h_u = reinterpret_cast<const u64*>(h_out + hu_at);
+        uint8_t* h_img = reinterpret_cast<uint8_t*>(h_out + himg_at);
+        const u64* h_cells = reinterpret_cast<const u64*>(h_out + hcell_at);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
+        for (long long mq = 0; mq < (long long)G; mq++) {
+            Member& x = mem[mq];
+            try {
+                const pcs::Commitment& cm = *items[x.idx].cm;
+                const std::vector<PcsClaim>& claims = *items[x.idx].claims;
+                const Fr* rows = reinterpret_cast<const Fr*>(cm.d_rows);
+                x.tr = pcs_start_transcript(sh, cm.root(), claims, Q);
+                const std::vector<Fr> rho = pcs_rho_powers(pcs_squeeze(x.tr), R);
+                BnObMember* hm = reinterpret_cast<BnObMember*>(h_stage + mem_at) + mq;
+                hm->M = reinterpret_cast<const Fr*>(cm.d_M); hm->img = x.img; hm->u = x.u; hm->u_words = x.u_words;
+                BnObJob* hd = reinterpret_cast<BnObJob*>(h_stage + jobs_at) + x.job0;
+                BnObClaim* hc = reinterpret_cast<BnObClaim*>(h_stage + claims_at) + x.claim0;
+                Fr* hy = reinterpret_cast<Fr*>(h_stage + x.y_at);
+                Fr* hz = reinterpret_cast<Fr*>(h_stage + x.z_at);
+                Fr* hw = reinterpret_cast<Fr*>(h_stage + x.w_at);
+                hd[0].src = rows; hd[0].nrows = R; hd[0].w_at = x.w_at; hd[0].u_at = x.u / 4;
+                memcpy(hw, rho.data(), R * sizeof(Fr));
+                size_t off = R;
+                for (size_t i = 0; i < x.n; i++) {
+                    const PcsClaim& cl = claims[i];
+                    const std::vector<Fr> w = pcs_eq_table(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
+                    hd[i + 1].src = rows + (sh.off[cl.table] << sh.c); hd[i + 1].nrows = w.size(); hd[i + 1].w_at = x.w_at + off * sizeof(Fr);
+                    hd[i + 1].u_at = x.u / 4 + (i + 1) * C;
+                    memcpy(hw + off, w.data(), w.size() * sizeof(Fr));
+                    off += w.size();
+                    hy[i] = cl.value;
+                    for (int b = 0; b < sh.c; b++) hz[i * (size_t)sh.c + b] = fr_to_mont(cl.point[b]);
+                    hc[i].u_at = hd[i + 1].u_at; hc[i].z_at = x.z_at + i * (size_t)sh.c * sizeof(Fr); hc[i].y_at = x.y_at + i * sizeof(Fr);
+                    hc[i].member = (u64)mq; hc[i].claim = (u64)i;
+                }
+            } catch (const std::exception& e) { x.error = e.what(); }
+        }
+        for (const Member& x : mem)
+            if (!x.error.empty()) throw Error(who + ": index " + std::to_string(x.idx) + ": " + x.error);
+        const double t1 = omp_get_wtime();
+        ctx->arena_reset();
+        char* d_stage;
+        u64 *d_u, *d_img, *d_js, *d_cells;
+        try {
+            d_stage = ctx->alloc_n<char>(stage_bytes);
+            d_u = ctx->alloc_n<u64>(u_total);
+            d_img = ctx->alloc_n<u64>(img_total);
+            d_js = ctx->alloc_n<u64>(G * Q + G);
+            d_cells = ctx->alloc_n<u64>(G);
+        } catch (const std::exception& e) {
+            throw Error(who + ": the context's arena cannot hold a group of " + std::to_string(G) + " openings: lower verify_batch_group (" + e.what() + ")");
+        }
+        const BnObMember* d_mem = reinterpret_cast<const BnObMember*>(d_stage + mem_at);
+        const unsigned cb = bnpcs_blocks(C);
+        if (jobs_total * cb > 0x7fffffffull) throw Error(who + ": a group of " + std::to_string(G) + " openings has too many row combinations for one launch: lower verify_batch_group");
+        hipc(hipMemcpyAsync(d_stage, h_stage, stage_bytes, hipMemcpyHostToDevice, st), "upload claims");
+        hipc(hipMemsetAsync(d_cells, 0xff, G * 8, st), "memset");
+        size_t nw_total = 0;
+        for (const Member& x : mem) nw_total += x.nw;
+        ctx->prof_begin(cls, (double)nw_total * C * 32 + (double)u_total * 8);
+        k_bnpcsob_combine<<<(unsigned)(jobs_total * cb), BNPCS_TPB, 0, st>>>(sh.c, cb, reinterpret_cast<const BnObJob*>(d_stage + jobs_at), d_stage, reinterpret_cast<Fr*>(d_u));
+        ctx->prof_end();
+        if (claims_total) {
+            ctx->prof_begin(cls, (double)claims_total * C * 32);
+            k_bnpcsob_eval<<<(unsigned)claims_total, BNPCS_TPB, 0, st>>>(reinterpret_cast<const BnObClaim*>(d_stage + claims_at), sh.c, reinterpret_cast<const Fr*>(d_u), d_stage, d_cells);
+            ctx->prof_end();
+        }
+        ctx->prof_begin(cls, (double)u_total * 16);
+        k_bnpcsob_emit<<<(unsigned)std::min<size_t>(bnpcs_blocks(u_total), 4096), BNPCS_TPB, 0, st>>>(d_mem, (unsigned)G, u_total, d_u, d_img);
+        ctx->prof_end();
+        hipc(hipMemcpyAsync(h_out + hu_at, d_u, u_total * 8, hipMemcpyDeviceToHost, st), "download combinations");
+        hipc(hipMemcpyAsync(h_out + hcell_at, d_cells, G * 8, hipMemcpyDeviceToHost, st), "download evaluation checks");
+        hipc(hipStreamSynchronize(st), (who + ": sync").c_str());
+        hipc(hipGetLastError(), (who + ": launch").c_str());
+        const double t2 = omp_get_wtime();
+        // the host's share: every member's u_i into its transcript, its column indices out of it, one member a thread
+        hj.assign(G * Q + G, 0);
+        size_t active = 0;
+        for (size_t m = 0; m < G; m++) {
+            mem[m].refused = h_cells[m] != BNPCSV_NONE;
+            hj[G * Q + m] = mem[m].refused ? 0 : 1;
+            active += mem[m].refused ? 0 : 1;
+        }
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
+        for (long long mq = 0; mq < (long long)G; mq++) {
+            Member& x = mem[mq];
+            if (x.refused) continue;
+            try {
+                pcs_absorb(x.tr, reinterpret_cast<const Fr*>(h_u + x.u), x.u_words / 4);
+                const std::vector<size_t> js = pcs_squeeze_indices(x.tr, N, Q);
+                for (size_t q = 0; q < Q; q++) hj[(size_t)mq * Q + q] = js[q];
+            } catch (const std::exception& e) { x.error = e.what(); }
+        }
+        for (const Member& x : mem)
+            if (!x.error.empty()) throw Error(who + ": index " + std::to_string(x.idx) + ": " + x.error);
+        const double t3 = omp_get_wtime();
+        if (active) {
+            if (Q) {
+                hipc(hipMemcpyAsync(d_js, hj.data(), hj.size() * 8, hipMemcpyHostToDevice, st), "upload column indices");
+                ctx->prof_begin(cls, (double)active * Q * R * 64);
+                k_bnpcsob_gather<<<bnpcs_blocks(G * Q * R), BNPCS_TPB, 0, st>>>(d_mem, G, Q, R, N, q_words, d_js, d_img);
+                ctx->prof_end();
+            }
+            hipc(hipMemcpyAsync(h_img, d_img, img_total * 8, hipMemcpyDeviceToHost, st), "download openings");
+            hipc(hipStreamSynchronize(st), (who + ": sync").c_str());
+            hipc(hipGetLastError(), (who + ": launch").c_str());
+        }
+        ctx->prof_collect();
+        const double t4 = omp_get_wtime();
+        // the siblings from each handle's tree into the gaps; a refused member's reason
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
+        for (long long mq = 0; mq < (long long)G; mq++) {
+            Member& x = mem[mq];
+            try {
+                pcs::Opened& out = res[x.idx];
+                const pcs::Commitment& cm = *items[x.idx].cm;
+                if (x.refused) {
+                    const size_t i = (size_t)h_cells[mq];
+                    out.refused = true;
+                    out.reason = std::string(single) + ": claim " + std::to_string(i) + ": the value is not the evaluation of table " + std::to_string((*items[x.idx].claims)[i].table) +
+                                 " at the point";
+                    continue;
+                }
+                const uint8_t* image = h_img + 8 * x.img;
+                out.bytes.assign(image, image + x.len);
+                for (size_t q = 0; q < Q; q++) {
+                    uint8_t* sib = out.bytes.data() + 8 * (x.u_words + q * q_words + 4 * R);
+                    size_t idx = (size_t)hj[(size_t)mq * Q + q];
+                    for (int l = 0; l < depth; l++, idx >>= 1) memcpy(sib + 32 * l, cm.node(l, idx ^ 1), 32);
+                }
+            } catch (const std::exception& e) { x.error = e.what(); }
+        }
+        for (const Member& x : mem)
+            if (!x.error.empty()) throw Error(who + ": index " + std::to_string(x.idx) + ": " + x.error);
+        if (times)
+            fprintf(stderr, "[hg pcs] bn254 open group %zu of %zu members: transcripts and weights %.2f ms, combine, checks and u back %.2f, hash %.2f, gather and images back %.2f, "
+                            "siblings %.2f\n", g, G, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3, (omp_get_wtime() - t4) * 1e3);
+    }
+    return res;
 }

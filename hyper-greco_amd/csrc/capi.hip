@@ -226,6 +226,15 @@ struct BnAbi {
     static std::vector<std::string> pcs_verify_batch(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const std::vector<PcsItem>& items, size_t Q) {
         return bn::pcs_verify_device_batch(who, ctx, sh, items, Q);
     }
+    // the batch forms of commit and open (device only): `secrets` says that the tables are witness words, lifted by the signed rule
+    typedef bn::PcsOpenItem PcsOpenItem;
+    static size_t opening_bytes(const pcs::Shape& sh, size_t n_claims, size_t Q) { return bn::pcs_opening_bytes(sh, n_claims, Q); }
+    static std::vector<pcs::Commitment*> commit_batch(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const u64* const* tabs, size_t n, bool secrets) {
+        return bn::pcs_commit_device_batch(who, ctx, sh, tabs, n, secrets);
+    }
+    static std::vector<pcs::Opened> pcs_open_batch(const char* who, const char* single, hg_ctx* ctx, const std::vector<PcsOpenItem>& items, size_t Q) {
+        return bn::pcs_open_device_batch(who, single, ctx, items, Q);
+    }
 };
 }  // namespace
 
@@ -753,6 +762,9 @@ static int pcs_open_batch_tail(const char* who, const char* single, hg_ctx* ctx,
     std::vector<typename A::PcsOpenItem> items(n);
     for (size_t i = 0; i < n; i++) items[i] = typename A::PcsOpenItem{cms[i], &cl[i]};
     std::vector<pcs::Opened> got;
+    const bool times = hg_times("pcs");   // HG_TIMES=pcs: what the run costs around its device passes, on stderr
+    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t0 = now();
     try {
         got = A::pcs_open_batch(who, single, ctx, items, Q);
     } catch (const std::exception& e) {
@@ -760,6 +772,7 @@ static int pcs_open_batch_tail(const char* who, const char* single, hg_ctx* ctx,
         throw Error(m.rfind(w, 0) == 0 ? m : w + ": " + m);
     }
     int refused = 0;
+    const double t1 = now();
     [[maybe_unused]] const int nthr = std::max(1, std::min<int>(hg_omp_threads(), (int)n));   // (the device pass of hipcc ignores the pragmas)
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nthr)
     for (long long i = 0; i < (long long)n; i++)
@@ -769,6 +782,11 @@ static int pcs_open_batch_tail(const char* who, const char* single, hg_ctx* ctx,
         refused += status[i];
         lens[i] = got[i].bytes.size();
         write_reason(reasons, reason_cap, i, got[i].reason);
+    }
+    if (times) {
+        const double t2 = now();
+        std::vector<pcs::Opened>().swap(got);
+        fprintf(stderr, "[hg pcs] open run of %zu items: the passes %.2f ms, the openings into the caller's buffers %.2f, their release %.2f\n", n, t1 - t0, t2 - t1, now() - t2);
     }
     return refused;
 }
@@ -2181,6 +2199,29 @@ int hg_claims_verify_batch_bn254(hg_ctx* ctx, const hg_params* params, const uin
                                  const uint64_t* points4, size_t coord_cap_each, const size_t* n_claims, size_t n_queries, const uint8_t* const* openings, const size_t* lens,
                                  size_t n, int* results, char* reasons, size_t reason_cap) {
     HG_ENTRY(claims_verify_batch_entry<BnAbi>("hg_claims_verify_batch_bn254", ctx, params, roots, log2_row, claims, claim_cap_each, points4, coord_cap_each, n_claims, n_queries, openings, lens, n, results, reasons, reason_cap))
+}
+
+int hg_pcs_commit_batch_bn254(hg_ctx* ctx, const uint64_t* const* const* tables4, const uint32_t* nvars, size_t n_tables, size_t log2_row, size_t n, void** commitments,
+                              uint8_t* roots) {
+    HG_ENTRY(pcs_commit_batch_entry<BnAbi>("hg_pcs_commit_batch_bn254", ctx, tables4, nvars, n_tables, log2_row, n, commitments, roots))
+}
+
+int hg_secrets_commit_batch_bn254(hg_ctx* ctx, const hg_params* params, const hg_witness* const* ws, size_t n, size_t log2_row, void** commitments, uint8_t* roots) {
+    HG_ENTRY(secrets_commit_batch_entry<BnAbi>("hg_secrets_commit_batch_bn254", ctx, params, ws, n, log2_row, commitments, roots))
+}
+
+int hg_pcs_open_batch_bn254(hg_ctx* ctx, const void* const* commitments, const uint32_t* const* tables, const uint64_t* const* points4, const uint64_t* const* values4,
+                            const size_t* n_claims, size_t n_queries, size_t n, uint8_t* openings, size_t cap_each, size_t* lens, int* status, char* reasons,
+                            size_t reason_cap) {
+    HG_ENTRY(pcs_open_batch_entry<BnAbi>("hg_pcs_open_batch_bn254", "hg_pcs_open_bn254", ctx, commitments, tables, points4, values4, n_claims, n_queries, n, openings, cap_each,
+                                         lens, status, reasons, reason_cap))
+}
+
+int hg_claims_open_batch_bn254(hg_ctx* ctx, const hg_params* params, const void* const* commitments, const void* claims, size_t claim_cap_each, const uint64_t* points4,
+                               size_t coord_cap_each, const size_t* n_claims, size_t n_queries, size_t n, uint8_t* openings, size_t cap_each, size_t* lens, int* status,
+                               char* reasons, size_t reason_cap) {
+    HG_ENTRY(claims_open_batch_entry<BnAbi>("hg_claims_open_batch_bn254", "hg_claims_open_bn254", "hg_secrets_commit_bn254", ctx, params, commitments, claims, claim_cap_each,
+                                            points4, coord_cap_each, n_claims, n_queries, n, openings, cap_each, lens, status, reasons, reason_cap))
 }
 
 int hg_profile(hg_ctx* ctx, int level) {

@@ -869,35 +869,16 @@ __global__ __launch_bounds__(PCS_TPB) void k_pcsb_merkle_top(u64* __restrict__ t
     }
 }
 
-namespace {
-struct Slab {   // a group's raw and encoded rows; its members' handles share it
-    u64* p = nullptr;
-    ~Slab() { if (p) (void)hipFree(p); }
-};
-struct DrainOne {   // every way out, an error included: no copy of a dead host buffer and no kernel on the arena left behind
-    hipStream_t st;
-    ~DrainOne() { (void)hipStreamSynchronize(st); }
-};
-// [first, last) of a run cut into groups: at most VB_MAX_GROUP or the option, `bytes_of(i)` summed within VB_PCS_BUDGET, `rows_of`
-// summed within max_rows; a group holds at least one member
-template <class BytesOf>
-std::vector<std::pair<size_t, size_t>> cut_groups(hg_ctx* ctx, size_t n, BytesOf bytes_of, size_t rows_each, size_t max_rows) {
-    size_t cap = VB_MAX_GROUP;
-    if (ctx->verify_batch_group > 0) cap = std::min<size_t>(cap, (size_t)ctx->verify_batch_group);
-    std::vector<std::pair<size_t, size_t>> groups;
-    for (size_t a = 0; a < n;) {
-        size_t b = a, bytes = 0;
-        while (b < n && b - a < cap) {
-            if (b > a && (bytes + bytes_of(b) > VB_PCS_BUDGET || (b - a + 1) * rows_each > max_rows)) break;
-            bytes += bytes_of(b);
-            b++;
-        }
-        groups.push_back({a, b});
-        a = b;
+// merkle_levels_device for the G trees at trees + m tree_words: one launch a level over every (member, node) while a level has more
+// than PCS_TPB nodes, then one workgroup a member
+void merkle_levels_device_batch(hipStream_t st, u64* d_trees, size_t tree_words, size_t N, size_t G) {
+    size_t below_at = 0, count = N / 2;
+    for (; count > (size_t)PCS_TPB; count >>= 1) {
+        k_pcsb_merkle<<<blocks_for(G * count), PCS_TPB, 0, st>>>(d_trees, tree_words, below_at, count, G);
+        below_at += 8 * count;
     }
-    return groups;
+    k_pcsb_merkle_top<<<(unsigned)G, PCS_TPB, 0, st>>>(d_trees, tree_words, below_at, count);
 }
-}  // namespace
 
 // hg_pcs_commit_batch. A group: one allocation for its members' raw and encoded rows, the tables uploaded straight into it, then
 // k_pcsb_stage, one ntt_batch over G R rows, the leaf hashes, the tree levels (per level while a level has more than PCS_TPB nodes,
@@ -955,12 +936,7 @@ std::vector<Commitment*> commit_device_batch(const char* who_c, hg_ctx* ctx, con
         k_pcsb_leaf_hash<<<blocks_for(G * N), PCS_TPB, 0, st>>>(d_M, G, N, R, d_out, tree_words);
         ctx->prof_end();
         ctx->prof_begin(cls, (double)G * N * 96);
-        size_t below_at = 0, count = N / 2;
-        for (; count > (size_t)PCS_TPB; count >>= 1) {
-            k_pcsb_merkle<<<blocks_for(G * count), PCS_TPB, 0, st>>>(d_out, tree_words, below_at, count, G);
-            below_at += 8 * count;
-        }
-        k_pcsb_merkle_top<<<(unsigned)G, PCS_TPB, 0, st>>>(d_out, tree_words, below_at, count);
+        merkle_levels_device_batch(st, d_out, tree_words, N, G);
         ctx->prof_end();
         h_out.resize(out_words);
         hip_check(hipMemcpyAsync(h_out.data(), d_out, out_words * 8, hipMemcpyDeviceToHost, st), "download trees and flags");

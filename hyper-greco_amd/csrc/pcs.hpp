@@ -72,6 +72,8 @@ std::vector<Commitment*> commit_device_batch(const char* who, hg_ctx* ctx, const
 // the levels above the 4C leaf hashes at d_tree (4 words a node, the levels one behind the other), enqueued on st; nodes are 32 bytes
 // in either field
 void merkle_levels_device(hipStream_t st, u64* d_tree, size_t N);
+// the same for the G trees of a group, tree m at d_trees + m tree_words: one launch a level over all members
+void merkle_levels_device_batch(hipStream_t st, u64* d_trees, size_t tree_words, size_t N, size_t G);
 
 // One row combination of an opening: u[j] = sum_{r < nrows} w[r] * row_{row0 + r}[j]
 struct CombineJob { size_t row0, nrows; std::vector<E2> w; };

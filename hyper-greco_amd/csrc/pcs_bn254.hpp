@@ -24,6 +24,12 @@ struct PcsClaim { size_t table; std::vector<Fr> point; Fr value; };   // canonic
 pcs::Commitment* pcs_commit_host(const char* who, const pcs::Shape& sh, const u64* const* tables, bool words);
 // bn254_pcs.inc (part of bn254.hip): rows staged, encoded by the batched NTT, hashed, the tree by the kernels of pcs.hip; one synchronisation
 pcs::Commitment* pcs_commit_device(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const u64* const* tables, bool words);
+// hg_pcs_commit_batch_bn254 (bn254_pcs.inc): n members of one shape, tables[i * m + t] = table t of member i (`words` as above), in
+// device passes of a group of members each: every handle is what pcs_commit_device gives for that member, except that a group's
+// matrices share one allocation (pcs::Commitment::owner). A group is cut by the option verify_batch_group, VB_PCS_COMMIT_BUDGET_BN254
+// over the members' raw and encoded rows and the 65535 rows of ntt_batch_dev; the NTT temporary is one slice's. Throws an Error
+// naming `who` (and "index i" for a member's element that is not below r); no handle survives an error
+std::vector<pcs::Commitment*> pcs_commit_device_batch(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const u64* const* tables, size_t n, bool words);
 
 // One row combination of an opening: u[j] = sum_{r < nrows} w[r] * row_{row0 + r}[j]; w in Montgomery form, u canonical
 struct PcsJob { size_t row0, nrows; std::vector<Fr> w; };
@@ -35,6 +41,11 @@ void pcs_columns_device(const pcs::Commitment& cm, const std::vector<size_t>& js
 // hg_pcs_open_bn254: the opening bytes; an Error (naming `who` and the claim) if a value is not <u_i, eq(z_i[..c])>. Transcript and
 // byte layout are here for both forms: device bytes equal host bytes by construction
 std::vector<uint8_t> pcs_open(const char* who, const pcs::Commitment& cm, const std::vector<PcsClaim>& claims, size_t Q);
+// hg_pcs_open_batch_bn254 (bn254_pcs.inc): item i's claims opened against its own device commitment (one shape, one context, one Q)
+// in device passes of a group of items each. refused: a value is not the evaluation (reason = pcs_open's error text under the name
+// `single`, the lowest failing claim; bytes empty); else bytes = what pcs_open gives for the item alone. Throws an Error naming `who`
+struct PcsOpenItem { const pcs::Commitment* cm; const std::vector<PcsClaim>* claims; };
+std::vector<pcs::Opened> pcs_open_device_batch(const char* who, const char* single, hg_ctx* ctx, const std::vector<PcsOpenItem>& items, size_t Q);
 // hg_pcs_verify_bn254: "" = accepted, else the reason (the strings and the order of pcs::verify)
 std::string pcs_verify(const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof, size_t len);
 // hg_pcs_verify_device_bn254 (bn254_pcs.inc): the same decision and the same reason with the table-sized work on the context's

@@ -291,11 +291,45 @@ VerifyBatchBufs* batch_bufs(hg_ctx* ctx) {
     if (!ctx->verify_batch) {
         auto* b = new VerifyBatchBufs();
         ctx->verify_batch = b;
+        b->slabs = std::make_shared<pcs::SlabSpares>();
+        b->slabs->cap = VB_PCS_COMMIT_BUDGET_BN254;
         hip_check(hipStreamCreateWithFlags(&b->up, hipStreamNonBlocking), "hipStreamCreate(batch uploads)");
         for (auto& e : b->ev) hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate(batch uploads)");
     }
     return static_cast<VerifyBatchBufs*>(ctx->verify_batch);
 }
+
+namespace pcs {
+u64* SlabSpares::take(size_t need, size_t* bytes) {
+    std::lock_guard<std::mutex> lock(mu);
+    size_t best = spare.size();
+    for (size_t i = 0; i < spare.size(); i++)
+        if (spare[i].second >= need && spare[i].second / 2 <= need && (best == spare.size() || spare[i].second < spare[best].second)) best = i;
+    if (best == spare.size()) return nullptr;
+    u64* p = spare[best].first;
+    *bytes = spare[best].second;
+    spare.erase(spare.begin() + best);
+    return p;
+}
+void SlabSpares::give(u64* p, size_t bytes) {
+    std::lock_guard<std::mutex> lock(mu);
+    if (closed || bytes > cap) { (void)hipFree(p); return; }
+    spare.push_back({p, bytes});
+    size_t total = 0;
+    for (const auto& s : spare) total += s.second;
+    while (total > cap) {
+        total -= spare.front().second;
+        (void)hipFree(spare.front().first);
+        spare.erase(spare.begin());
+    }
+}
+void SlabSpares::close() {
+    std::lock_guard<std::mutex> lock(mu);
+    closed = true;
+    for (const auto& s : spare) (void)hipFree(s.first);
+    spare.clear();
+}
+}  // namespace pcs
 
 char* batch_desc_host(VerifyBatchBufs* B, size_t bytes) {
     if (bytes > B->desc_cap) {
@@ -403,6 +437,7 @@ void verify_batch_drop(hg_ctx* ctx) {
     for (auto p : b->d_in) if (p) (void)hipFree(p);
     if (b->h_desc) (void)hipHostFree(b->h_desc);
     if (b->h_out) (void)hipHostFree(b->h_out);
+    if (b->slabs) b->slabs->close();
     delete b;
     ctx->verify_batch = nullptr;
 }

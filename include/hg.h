@@ -79,8 +79,9 @@ void hg_destroy(hg_ctx* ctx);
  *   "verify_batch_group"  the most proofs one device pass of hg_verify_device_batch, hg_verify_device_batch_bn254,
  *                 hg_verify_public_batch or hg_verify_public_batch_bn254 holds, and the most openings one of
  *                 hg_pcs_verify_device_batch, hg_claims_verify_batch, hg_pcs_verify_device_batch_bn254 or
- *                 hg_claims_verify_batch_bn254, the most members one device pass of hg_pcs_commit_batch or hg_secrets_commit_batch
- *                 encodes and the most items one of hg_pcs_open_batch or hg_claims_open_batch opens (default 0: sized from the
+ *                 hg_claims_verify_batch_bn254, the most members one device pass of hg_pcs_commit_batch, hg_secrets_commit_batch,
+ *                 hg_pcs_commit_batch_bn254 or hg_secrets_commit_batch_bn254 encodes and the most items one of hg_pcs_open_batch,
+ *                 hg_claims_open_batch, hg_pcs_open_batch_bn254 or hg_claims_open_batch_bn254 opens (default 0: sized from the
  *                 memory budget, at most 64)
  * Returns 0, or -1 for an unknown name. */
 int hg_set_option(hg_ctx* ctx, const char* name, int64_t value);
@@ -473,7 +474,7 @@ int hg_claims_verify_batch(hg_ctx* ctx, const hg_params* params, const uint8_t* 
  *   hg_verify_public_batch writes them (item i's claims at (hg_input_claim*)claims + i*claim_cap_each, its points at points +
  *   2*i*coord_cap_each with point_off relative to its own block, its count n_claims[i]); a refused item's text is hg_claims_open's.
  *   -1 also, naming the index: the mapping errors of hg_claims_verify_batch and a commitment that is not hg_secrets_commit's for
- *   these parameters. The BN254 forms of these four entries do not exist yet. */
+ *   these parameters. The BN254 forms of these four entries are declared with the other _bn254 entries of the commitment, below. */
 int hg_pcs_commit_batch(hg_ctx* ctx, const uint64_t* const* const* tables, const uint32_t* nvars, size_t n_tables, size_t log2_row, size_t n,
                         void** commitments, uint8_t* roots);
 int hg_secrets_commit_batch(hg_ctx* ctx, const hg_params* params, const hg_witness* const* ws, size_t n, size_t log2_row, void** commitments,
@@ -894,6 +895,48 @@ int hg_pcs_verify_device_batch_bn254(hg_ctx* ctx, const uint8_t* const* roots, c
 int hg_claims_verify_batch_bn254(hg_ctx* ctx, const hg_params* params, const uint8_t* const* roots, size_t log2_row, const void* claims,
                                  size_t claim_cap_each, const uint64_t* points4, size_t coord_cap_each, const size_t* n_claims, size_t n_queries,
                                  const uint8_t* const* openings, const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap);
+
+/* hg_pcs_commit_batch_bn254 / hg_secrets_commit_batch_bn254 / hg_pcs_open_batch_bn254 / hg_claims_open_batch_bn254: hg_pcs_commit_batch,
+ *   hg_secrets_commit_batch, hg_pcs_open_batch and hg_claims_open_batch over bn256::Fr, each with the argument list of its Goldilocks
+ *   sibling and its contract word for word, Fr standing for the Goldilocks field: tables4, points4 and values4 hold 4 canonical
+ *   little-endian words an element, claims is an hg_input_claim_bn254 array and points4 is laid out exactly as
+ *   hg_verify_public_batch_bn254 writes them (item i's claims at (hg_input_claim_bn254*)claims + i*claim_cap_each, its points at
+ *   points4 + 4*i*coord_cap_each with point_off relative to its own block). Device only. Every handle is byte for byte what
+ *   hg_pcs_commit_bn254 / hg_secrets_commit_bn254 on the same context gives for that member alone (the same root, tree and matrices;
+ *   hg_pcs_open_bn254, hg_claims_open_bn254, the open batch and hg_pcs_free take it), except that a group's matrices share one
+ *   allocation: THE MEMORY RETURNS WHEN THE LAST HANDLE OF THE GROUP IS FREED. Every opening is byte for byte what hg_pcs_open_bn254 /
+ *   hg_claims_open_bn254 gives for that item alone. The commit pair returns 0, the open pair the number of refused items; n == 0
+ *   returns 0 and writes nothing. What differs from the Goldilocks contract:
+ *   - a refused open item (status[i] = 1, lens[i] = 0, its buffer untouched) carries the text hg_pcs_open_bn254 / hg_claims_open_bn254
+ *     leaves in hg_last_error for it, the lowest failing claim;
+ *   - a member whose table holds an element that is not below r (all four limbs compared) is named as "<entry>: index i: a table holds
+ *     an element that is not below r", the lowest such member; hg_secrets_commit_batch_bn254 lifts the 8-byte witness words into Fr on
+ *     the device by the signed rule of hg_secrets_commit_bn254, so a quarter of the bytes is uploaded;
+ *   - a Goldilocks handle is refused with "the commitment is over Goldilocks: open it with hg_pcs_open_batch" (hg_claims_open_batch
+ *     for the wrapper).
+ *   The commit pass: groups of at most 64 or "verify_batch_group" members, a byte budget of its own over the members' raw and encoded
+ *   rows (4.25 GiB; a member takes 283 MB at n=32768 k=16: 16 members a group) and the 65535 rows the batched Fr NTT takes at once. A
+ *   group's rows lie in one allocation. An allocation of gigabytes costs between 0.3 ms and 1.4 s on the device, so the context
+ *   KEEPS the allocations of groups whose handles were all freed, up to 4.25 GiB in all (the oldest goes first), and the next group
+ *   takes one that holds it and is at most twice as large; hg_destroy frees them, and a handle may still be freed after it. Staging with the range check (one flag a member), the encoding in slices of whole members
+ *   through one slice's NTT temporary (so the temporary does not grow with the group), the leaf sponges (one thread per member and
+ *   column) and the tree levels of the Goldilocks batch (a node is 32 bytes in either field) each run once over the group; one
+ *   download, one synchronisation a group.
+ *   The open pass is hg_pcs_open_batch's step for step over 32-byte elements: the weights in Montgomery form, the row combinations on
+ *   the deferred-reduction accumulators with one job per workgroup (their weights are wave-uniform scalar operands), elements
+ *   written into the images as 32 bytes big-endian; two synchronisations a group.
+ *   -1 (nothing is written; hg_last_error begins with the function's name and gives "index i" where a member or item is at fault):
+ *   the cases of the Goldilocks entries, "<function>: no context" for a null context after the argument checks. */
+int hg_pcs_commit_batch_bn254(hg_ctx* ctx, const uint64_t* const* const* tables4, const uint32_t* nvars, size_t n_tables, size_t log2_row, size_t n,
+                              void** commitments, uint8_t* roots);
+int hg_secrets_commit_batch_bn254(hg_ctx* ctx, const hg_params* params, const hg_witness* const* ws, size_t n, size_t log2_row, void** commitments,
+                                  uint8_t* roots);
+int hg_pcs_open_batch_bn254(hg_ctx* ctx, const void* const* commitments, const uint32_t* const* tables, const uint64_t* const* points4,
+                            const uint64_t* const* values4, const size_t* n_claims, size_t n_queries, size_t n, uint8_t* openings, size_t cap_each,
+                            size_t* lens, int* status, char* reasons, size_t reason_cap);
+int hg_claims_open_batch_bn254(hg_ctx* ctx, const hg_params* params, const void* const* commitments, const void* claims, size_t claim_cap_each,
+                               const uint64_t* points4, size_t coord_cap_each, const size_t* n_claims, size_t n_queries, size_t n, uint8_t* openings,
+                               size_t cap_each, size_t* lens, int* status, char* reasons, size_t reason_cap);
 
 /* hg_witness_derive and hg_prove_bn254 for a run of n_enc ENCRYPTIONS under one key, pipelined: hg_prove_encryptions over bn256::Fr
  *   [REF scripts/circuit_sk.py:18-140 followed by sk_encryption_circuit.rs:417-460, 614-626; the loop a proving service writes around
