@@ -56,6 +56,7 @@ EXPORTS = [
     "hg_pcs_commit", "hg_pcs_free", "hg_pcs_open", "hg_pcs_verify", "hg_secrets_commit", "hg_claims_open", "hg_claims_verify",
     "hg_pcs_verify_device", "hg_claims_verify_device", "hg_pcs_verify_device_batch", "hg_claims_verify_batch",
     "hg_pcs_commit_batch", "hg_secrets_commit_batch", "hg_pcs_open_batch", "hg_claims_open_batch",
+    "hg_secrets_commit_values", "hg_prove_encryptions_committed",
     "hg_pcs_commit_bn254", "hg_pcs_open_bn254", "hg_pcs_verify_bn254", "hg_secrets_commit_bn254", "hg_claims_open_bn254", "hg_claims_verify_bn254",
     "hg_pcs_verify_device_bn254", "hg_claims_verify_device_bn254", "hg_pcs_verify_device_batch_bn254", "hg_claims_verify_batch_bn254",
     "hg_pcs_commit_batch_bn254", "hg_secrets_commit_batch_bn254", "hg_pcs_open_batch_bn254", "hg_claims_open_batch_bn254",
@@ -110,6 +111,10 @@ def _two_field_protos(L):
     L.hg_claims_verify_batch.argtypes = L.hg_claims_verify_batch_bn254.argtypes = [vp, C.POINTER(HgParams), C.POINTER(cp), sz, vp, sz, u64p, sz] + tail
     L.hg_pcs_commit_batch.argtypes = L.hg_pcs_commit_batch_bn254.argtypes = [vp, C.POINTER(C.POINTER(u64p)), u32p, sz, sz, sz, C.POINTER(vp), u8p]
     L.hg_secrets_commit_batch.argtypes = L.hg_secrets_commit_batch_bn254.argtypes = [vp, C.POINTER(HgParams), C.POINTER(vp), sz, sz, C.POINTER(vp), u8p]
+    L.hg_secrets_commit_values.argtypes = [vp, vp, vp, sz, C.POINTER(vp), u8p]   # ctx, key, values, log2_row, handle out, root out
+    pp = C.POINTER(i64p)
+    L.hg_prove_encryptions_committed.argtypes = [vp, vp, pp, pp, pp, pp, sz, sz, vp, sz, szp, C.POINTER(ci), C.POINTER(vp), u8p, C.POINTER(vp), cp, sz,
+                                                 C.POINTER(HgTimings)]
     opened = [szp, sz, sz, u8p, sz, szp, C.POINTER(ci), cp, sz]   # claim counts, n_queries, n, openings, cap_each, lengths, status, reasons, reason_cap
     L.hg_pcs_open_batch.argtypes = L.hg_pcs_open_batch_bn254.argtypes = [vp, C.POINTER(vp), C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u64p)] + opened
     L.hg_claims_open_batch.argtypes = L.hg_claims_open_batch_bn254.argtypes = [vp, C.POINTER(HgParams), C.POINTER(vp), vp, sz, u64p, sz] + opened
@@ -635,6 +640,42 @@ def prove_encryptions_bn254(ctx, pk, encs, cap_each=1 << 24, witnesses=True, rea
     """hg_prove_encryptions_bn254: prove_encryptions over bn256::Fr (proofs of 32-byte big-endian elements, each the bytes
     Context.prove_bn254 gives for Witness.derive of the laid-out encryption). Same arguments, same 5-tuple."""
     return _prove_encryptions(lib().hg_prove_encryptions_bn254, ctx, pk, encs, cap_each, witnesses, reason_cap)
+
+
+def prove_encryptions_committed(ctx, pk, encs, log2_row=0, cap_each=1 << 20, witnesses=False, reason_cap=256):
+    """hg_prove_encryptions_committed: prove_encryptions with a device Commitment to the five secret inputs of every proven item
+    (what Commitment.from_values gives for its tables), made inside the pipeline. Returns (proofs, statuses, reasons, commitments,
+    roots, witnesses, timings): commitments[i] is None and roots[i] 32 zero bytes for a refused item; timings["upload_ms"] is the
+    commits' device time."""
+    n = len(encs)
+    arrs = [_encryption_arrays(pk.params, *enc) for enc in encs]
+    cols = [(i64p * max(n, 1))(*[x[f].ctypes.data_as(i64p) for x in arrs]) for f in range(4)]
+    buf = (C.c_uint8 * (cap_each * max(n, 1)))()
+    lens = (C.c_size_t * max(n, 1))()
+    status = (C.c_int * max(n, 1))()
+    cms = (C.c_void_p * max(n, 1))()
+    rts = (C.c_uint8 * (32 * max(n, 1)))()
+    hs = (C.c_void_p * max(n, 1))() if witnesses else None
+    reasons = C.create_string_buffer(max(n, 1) * reason_cap)
+    tm = HgTimings()
+    rc = lib().hg_prove_encryptions_committed(_h(ctx), pk.h, *cols, n, log2_row, buf, cap_each, lens, status, cms, rts, hs, reasons, reason_cap, C.byref(tm))
+    if rc < 0:
+        raise HgError(lib().hg_last_error().decode())
+    raw, rr = memoryview(buf), reasons.raw
+    proofs = [None if status[i] else bytes(raw[i * cap_each:i * cap_each + lens[i]]) for i in range(n)]
+    why = [rr[i * reason_cap:(i + 1) * reason_cap].split(b"\0", 1)[0].decode() for i in range(n)]
+    ws = [Witness(C.c_void_p(hs[i]), pk.params) if witnesses and hs[i] else None for i in range(n)]
+    nvars = _secrets_nvars(pk.params)
+    c = pcs_row_log2(nvars, log2_row)
+    roots = [bytes(rts[32 * i:32 * i + 32]) for i in range(n)]
+    commitments = [Commitment(C.c_void_p(cms[i]), roots[i], ctx, nvars, c) if cms[i] else None for i in range(n)]
+    return proofs, [int(status[i]) for i in range(n)], why, commitments, roots, ws, {f: getattr(tm, f) for f, _ in HgTimings._fields_}
+
+
+def _secrets_nvars(params):
+    """the variables of the tables of hg_secrets_commit: s, e, k1, r1is[0..k-1], r2is"""
+    lg = params.n.bit_length() - 1
+    return [lg + 1] * (3 + params.k) + [lg + params.k.bit_length() - 1]
 
 
 def _prove_encryptions(fn, ctx, pk, encs, cap_each, witnesses, reason_cap):
@@ -1233,6 +1274,15 @@ class Commitment:
     def secrets(cls, ctx, params, witness, log2_row=0):
         """hg_secrets_commit: the five secret inputs of a witness handle (tables s, e, k1, r1is[0..k-1], r2is)."""
         return cls._secrets("goldilocks", ctx, params, witness, log2_row)
+
+    @classmethod
+    def from_values(cls, ctx, pk, values, log2_row=0):
+        """hg_secrets_commit_values: the device Commitment of secrets(ctx, ..) to the five secret inputs where witness_gen left them
+        in HBM (a ResidentValues of this key and context that holds every table)."""
+        h, root = C.c_void_p(), (C.c_uint8 * 32)()
+        _check(lib().hg_secrets_commit_values(_h(ctx), pk.h, values.h if values is not None else None, log2_row, C.byref(h), root))
+        nvars = _secrets_nvars(pk.params)
+        return cls(h, bytes(root), ctx, nvars, pcs_row_log2(nvars, log2_row))
 
     @classmethod
     def _batch(cls, call, ctx, n, nvars, log2_row, field="goldilocks"):

@@ -266,17 +266,26 @@ static int write_results(const std::vector<std::string>& why, int* results, char
 }
 
 // hg_prove_encryptions*: run(want_witnesses, &total_ms) is the field's pipeline. Historical: the Goldilocks entry also sums gpu_ms and
-// replay_ms into the timings (gpu_timings).
+// replay_ms into the timings (gpu_timings). cmt (hg_prove_encryptions_committed): the run fills it with every proven item's handle;
+// commitments and roots are required then, a refused item gets a null handle and a zero root, upload_ms sums the commits' device time.
+static std::vector<uint32_t> secrets_nvars(const Params& p);
 template <class Run>
 static int prove_encryptions_entry(const std::string& who, bool gpu_timings, hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e,
                                    const int64_t* const* k1, const int64_t* const* a, size_t n_enc, uint8_t* proofs, size_t cap_each, size_t* lens, int* status,
-                                   hg_witness** ws, char* reasons, size_t reason_cap, hg_timings* timings, Run run) {
+                                   hg_witness** ws, char* reasons, size_t reason_cap, hg_timings* timings, Run run, EncCommit* cmt = nullptr, size_t log2_row = 0,
+                                   void** commitments = nullptr, uint8_t* roots = nullptr) {
     if (ws) for (size_t i = 0; i < n_enc; i++) ws[i] = nullptr;
+    if (cmt && commitments) for (size_t i = 0; i < n_enc; i++) commitments[i] = nullptr;
     if (!ctx) throw Error(who + ": needs a device context (derivation and proving run on the GPU and have no host fallback)");
-    if (!pk || (n_enc && (!s || !e || !k1 || !a || !proofs || !lens || !status))) throw Error(who + ": null argument");
+    if (!pk || (n_enc && (!s || !e || !k1 || !a || !proofs || !lens || !status || (cmt && (!commitments || !roots))))) throw Error(who + ": null argument");
     if (!pk->ctx) throw Error(who + ": host-only prover key (created without a context)");
     for (size_t i = 0; i < n_enc; i++)
         if (!s[i] || !e[i] || !k1[i] || !a[i]) throw Error(who + ": encryption " + std::to_string(i) + ": null polynomial");
+    if (cmt) {   // hg_prove_encryptions_committed: the shape of hg_secrets_commit_values, ahead of anything enqueued
+        const std::vector<uint32_t> nv = secrets_nvars(pk->params);
+        cmt->sh = pcs::make_shape(who.c_str(), nv.data(), nv.size(), log2_row);
+        if (cmt->sh.R > 65535) throw Error(who + ": more than 65535 rows (choose a larger log2_row)");
+    }
     double total = 0;
     std::vector<EncResult> rs = run(ws != nullptr, &total);
     if (timings) { memset(timings, 0, sizeof(*timings)); timings->total_ms = total; }
@@ -289,9 +298,15 @@ static int prove_encryptions_entry(const std::string& who, bool gpu_timings, hg_
         status[i] = r.refused ? 1 : 0;
         lens[i] = r.refused ? 0 : r.r.proof.size();
         write_reason(reasons, reason_cap, i, r.reason);
+        if (cmt) memset(roots + 32 * i, 0, 32);
         if (r.refused) { refused++; continue; }
         memcpy(proofs + i * cap_each, r.r.proof.data(), r.r.proof.size());
         if (ws) ws[i] = new hg_witness{std::move(rs[i].w), pk->params.raw};
+        if (cmt) {
+            memcpy(roots + 32 * i, cmt->cms[i]->root(), 32);
+            commitments[i] = cmt->cms[i].release();
+            if (timings) timings->upload_ms += cmt->ms[i];
+        }
         if (timings) { timings->prove_ms += r.r.prove_ms; timings->witness_ms += r.witness_gpu_ms; }
         if (timings && gpu_timings) { timings->gpu_ms += r.r.gpu_ms; timings->replay_ms += r.r.replay_ms; }
     }
@@ -562,6 +577,43 @@ static int secrets_commit_entry(const char* who, hg_ctx* ctx, const hg_params* p
     tabs.push_back(v.r2is.data());
     const pcs::Shape sh = pcs::make_shape(who, nv.data(), nv.size(), log2_row);
     pcs::Commitment* cm = A::commit_secrets(who, ctx, sh, tabs.data());
+    memcpy(root, cm->root(), 32);
+    *commitment = cm;
+    return 0;
+}
+
+// hg_secrets_commit_values: the tables of secrets_commit_entry where hg_witness_gen left them in HBM
+static int secrets_commit_values_entry(const char* who, hg_ctx* ctx, const hg_pk* pk, const hg_values* v, size_t log2_row, void** commitment, uint8_t root[32]) {
+    const std::string w(who);
+    if (commitment) *commitment = nullptr;
+    if (!pk || !v || !commitment || !root) throw Error(w + ": null argument");
+    if (!ctx) throw Error(w + ": no context");
+    if (!pk->ctx) throw Error(w + ": host-only prover key (created without a context)");
+    if (v->pk_serial != pk->serial) throw Error(w + ": the values were laid out for another prover key");
+    if (v->ctx != ctx || pk->ctx != ctx) throw Error(w + ": the values or the prover key belong to another context");
+    const Params& p = pk->params;
+    const size_t k = (size_t)p.k;
+    const std::vector<int>& ids = pk->circuit.input_ids;
+    if (ids.size() != 3 + 2 * k + 1) throw Error(w + ": unexpected input nodes");
+    const std::vector<uint32_t> nv = secrets_nvars(p);
+    std::vector<size_t> inputs = {0, 1, 2};
+    for (size_t i = 0; i < k; i++) inputs.push_back(3 + k + i);
+    inputs.push_back(3 + 2 * k);
+    std::vector<const u64*> tabs;
+    for (size_t t = 0; t < inputs.size(); t++) {
+        const size_t id = (size_t)ids[inputs[t]];
+        if (id >= v->d_vals.size() || !v->d_vals[id])
+            throw Error(w + ": input " + std::to_string(inputs[t]) + " is not resident in these values (a rank's share of hg_witness_gen_shard holds only what the rank reads)");
+        if (v->sizes[id] != (size_t)1 << nv[t]) throw Error(w + ": table size mismatch");
+        tabs.push_back(v->d_vals[id]);
+    }
+    const pcs::Shape sh = pcs::make_shape(who, nv.data(), nv.size(), log2_row);
+    pcs::Commitment* cm;
+    try {
+        cm = pcs::commit_device_values(ctx, sh, tabs.data());
+    } catch (const std::exception& e) {
+        throw Error(w + ": " + e.what());
+    }
     memcpy(root, cm->root(), 32);
     *commitment = cm;
     return 0;
@@ -1533,6 +1585,19 @@ int hg_prove_encryptions(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, 
                                      [&](bool want, double* total) { return prove_encryptions(ctx, pk, s, e, k1, a, n_enc, want, total); }))
 }
 
+int hg_prove_encryptions_committed(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e, const int64_t* const* k1,
+                                   const int64_t* const* a, size_t n_enc, size_t log2_row, uint8_t* proofs, size_t cap_each, size_t* lens,
+                                   int* status, void** commitments, uint8_t* roots, hg_witness** ws, char* reasons, size_t reason_cap,
+                                   hg_timings* timings) {
+    HG_TRY
+    if (commitments) for (size_t i = 0; i < n_enc; i++) commitments[i] = nullptr;
+    EncCommit cmt;   // (an error of the call drops every handle made so far with it)
+    return prove_encryptions_entry("hg_prove_encryptions_committed", true, ctx, pk, s, e, k1, a, n_enc, proofs, cap_each, lens, status, ws, reasons, reason_cap, timings,
+                                   [&](bool want, double* total) { return prove_encryptions(ctx, pk, s, e, k1, a, n_enc, want, total, "hg_prove_encryptions_committed", &cmt); },
+                                   &cmt, log2_row, commitments, roots);
+    HG_CATCH(-1)
+}
+
 int hg_prove_encryptions_bn254(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e, const int64_t* const* k1,
                                const int64_t* const* a, size_t n_enc, uint8_t* proofs, size_t cap_each, size_t* lens, int* status, hg_witness** ws,
                                char* reasons, size_t reason_cap, hg_timings* timings) {
@@ -2122,6 +2187,10 @@ int hg_claims_verify_batch(hg_ctx* ctx, const hg_params* params, const uint8_t* 
 int hg_pcs_commit_batch(hg_ctx* ctx, const uint64_t* const* const* tables, const uint32_t* nvars, size_t n_tables, size_t log2_row, size_t n, void** commitments,
                         uint8_t* roots) {
     HG_ENTRY(pcs_commit_batch_entry<GlAbi>("hg_pcs_commit_batch", ctx, tables, nvars, n_tables, log2_row, n, commitments, roots))
+}
+
+int hg_secrets_commit_values(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, size_t log2_row, void** commitment, uint8_t root[32]) {
+    HG_ENTRY(secrets_commit_values_entry("hg_secrets_commit_values", ctx, pk, v, log2_row, commitment, root))
 }
 
 int hg_secrets_commit_batch(hg_ctx* ctx, const hg_params* params, const hg_witness* const* ws, size_t n, size_t log2_row, void** commitments, uint8_t* roots) {

@@ -5,6 +5,8 @@
 // The verifier of a run of openings (verify_device_batch) runs the same five kernels once over a group, driven by a member table.
 // A run of commitments (commit_device_batch) and a run of openings (open_device_batch) do the same for the prover's side: a group's
 // matrices in one allocation that its handles share, the kernels of commit and open once over the group.
+// A commitment to tables that lie in HBM (commit_tables_enqueue: hg_secrets_commit_values, the encryption pipeline) stages them with one
+// kernel of its own and goes on with the encoding, the leaf hash and the tree of commit_device.
 #include <omp.h>
 #include "pcs.hpp"
 #include "prover.hpp"
@@ -429,6 +431,134 @@ Commitment* commit_device(hg_ctx* ctx, const Shape& sh, const u64* const* tables
     hip_check(hipStreamSynchronize(st), "hg_pcs_commit: sync");
     hip_check(hipGetLastError(), "hg_pcs_commit: launch");
     if (flag) throw Error("hg_pcs_commit: a table holds a word that is not below p");
+    return cm.release();
+}
+
+// ---- a commitment to tables that lie in HBM already (commit_tables_enqueue, commit_device_values): k_pcs_stage and the copies
+// ahead of it in one pass over the source tables. A unit is what a thread moves at a time: two words (16 bytes) when VEC, else one.
+// A row has U = C / unit words units; 2^lanes_log2 = min(PCS_TPB, U) threads work on a row, so a workgroup holds PCS_TPB >> lanes_log2
+// rows at a time, and a row of more than PCS_TPB units is walked in U >> lanes_log2 steps of which every workgroup of the row takes
+// `split`-th part. The table of a row is looked up once a row (uniform over the workgroup as soon as a row has PCS_TPB units), from
+// the descriptor in the kernel arguments. Per unit: one load, the word test, one store into rows, one into M and three zero stores
+// into the padding of M's row; a wavefront's accesses are adjacent in every one of them.
+struct StageTables {
+    const u64* src[MAX_TABLES];
+    unsigned off[MAX_TABLES + 1];   // first row of table t; off[nt] = R
+    unsigned nt;
+};
+template <bool VEC>
+__global__ __launch_bounds__(PCS_TPB) void k_pcs_stage_tables(const StageTables T, u64* __restrict__ rows, u64* __restrict__ M, int c, int lanes_log2, int split_log2,
+                                                              unsigned* __restrict__ flag) {
+    typedef typename std::conditional<VEC, ulonglong2, u64>::type Unit;
+    const int u_log2 = VEC ? c - 1 : c;                      // log2 of the units in a row
+    const int steps_log2 = u_log2 - lanes_log2 - split_log2;   // steps a workgroup walks along its row(s)
+    const size_t R = T.off[T.nt];
+    const unsigned lane = threadIdx.x & ((1u << lanes_log2) - 1), sub = threadIdx.x >> lanes_log2, rpb = PCS_TPB >> lanes_log2;
+    const size_t groups = (R + rpb - 1) / rpb, items = groups << split_log2;
+    bool bad = false;
+    for (size_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const size_t r = (item >> split_log2) * rpb + sub, part = item & (((size_t)1 << split_log2) - 1);
+        if (r >= R) continue;
+        unsigned t = 0;
+        while (t + 1 < T.nt && T.off[t + 1] <= r) t++;
+        const Unit* src = reinterpret_cast<const Unit*>(T.src[t] + ((r - T.off[t]) << c));
+        Unit* drow = reinterpret_cast<Unit*>(rows + (r << c));
+        Unit* mrow = reinterpret_cast<Unit*>(M + (r << (c + 2)));
+        const size_t U = (size_t)1 << u_log2;
+        for (size_t s = 0; s < ((size_t)1 << steps_log2); s++) {
+            const size_t u = (((part << steps_log2) + s) << lanes_log2) + lane;
+            const Unit v = src[u];
+            Unit z;
+            if constexpr (VEC) { bad |= v.x >= GL_P || v.y >= GL_P; z.x = 0; z.y = 0; }
+            else { bad |= v >= GL_P; z = 0; }
+            drow[u] = v;
+            mrow[u] = v;
+            mrow[U + u] = z;
+            mrow[2 * U + u] = z;
+            mrow[3 * U + u] = z;
+        }
+    }
+    if (bad) atomicOr(flag, 1u);
+}
+
+void commit_tables_enqueue(hipStream_t st, const Shape& sh, const u64* const* d_tables, u64* d_rows, u64* d_M, u64* scratch, u64* W, u64* d_tree, unsigned* d_flag,
+                           hg_ctx* prof, int cls) {
+    const size_t C = sh.C(), N = sh.N(), R = sh.R, nt = sh.nvars.size();
+    const int log2n = sh.depth();
+    if (nt > (size_t)MAX_TABLES || R > 65535) throw Error("commit_tables_enqueue: a shape the staging kernel does not take");
+    StageTables T;
+    bool vec = sh.c >= 1 && ((uintptr_t)d_rows & 15) == 0 && ((uintptr_t)d_M & 15) == 0;
+    for (size_t t = 0; t < nt; t++) {
+        T.src[t] = d_tables[t];
+        T.off[t] = (unsigned)sh.off[t];
+        vec = vec && ((uintptr_t)d_tables[t] & 15) == 0;
+    }
+    T.off[nt] = (unsigned)R;
+    T.nt = (unsigned)nt;
+    const int u_log2 = vec ? sh.c - 1 : sh.c, lanes_log2 = std::min(u_log2, 8);
+    static_assert(PCS_TPB == 256, "2^8 threads a workgroup");
+    const size_t groups = (R + (PCS_TPB >> lanes_log2) - 1) / (PCS_TPB >> lanes_log2);
+    int split_log2 = 0;   // the workgroups of a row: enough of them for about 2048 in all
+    while (split_log2 < u_log2 - lanes_log2 && (groups << split_log2) < 2048) split_log2++;
+    const unsigned grid = (unsigned)std::min<size_t>(groups << split_log2, (size_t)1 << 20);
+    auto begin = [&](double bytes) { if (prof) prof->prof_begin(cls, bytes); };
+    auto end = [&] { if (prof) prof->prof_end(); };
+    hip_check(hipMemsetAsync(d_flag, 0, 4, st), "memset");
+    begin((double)R * (2 * C + N) * 8);
+    if (vec) k_pcs_stage_tables<true><<<grid, PCS_TPB, 0, st>>>(T, d_rows, d_M, sh.c, lanes_log2, split_log2, d_flag);
+    else k_pcs_stage_tables<false><<<grid, PCS_TPB, 0, st>>>(T, d_rows, d_M, sh.c, lanes_log2, split_log2, d_flag);
+    end();
+    begin((double)R * N * 32);
+    dev::powers_table(st, W, root_of_unity(log2n), N);
+    dev::ntt_batch(st, d_M, log2n, R, W, 1, scratch);
+    end();
+    begin((double)R * N * 8);
+    k_pcs_leaf_hash<<<blocks_for(N), PCS_TPB, 0, st>>>(d_M, N, R, d_tree);
+    end();
+    begin((double)N * 96);
+    merkle_levels_device(st, d_tree, N);
+    end();
+}
+
+std::shared_ptr<void> slab_alloc(size_t bytes, u64** p) {
+    std::shared_ptr<Slab> slab = std::make_shared<Slab>();
+    hip_check(hipMalloc((void**)&slab->p, bytes), "hipMalloc(pcs rows and encoded matrices of a group)");
+    slab->bytes = bytes;
+    *p = slab->p;
+    return slab;
+}
+
+Commitment* commit_device_values(hg_ctx* ctx, const Shape& sh, const u64* const* d_tables) {
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->arena_reset();
+    hipStream_t st = ctx->stream;
+    std::unique_ptr<Commitment> cm(new Commitment());
+    cm->sh = sh;
+    cm->ctx = ctx;
+    const size_t C = sh.C(), N = sh.N(), R = sh.R;
+    if (R > 65535) throw Error("more than 65535 rows (choose a larger log2_row)");
+    hip_check(hipMalloc((void**)&cm->d_rows, R * C * 8), "hipMalloc(pcs rows)");
+    hip_check(hipMalloc((void**)&cm->d_M, R * N * 8), "hipMalloc(pcs encoded matrix)");
+    u64* scratch = ctx->alloc_n<u64>(R * N);
+    u64* W = ctx->alloc_n<u64>(N);
+    u64* d_tree = ctx->alloc_n<u64>(4 * 2 * N);
+    unsigned* d_flag = ctx->alloc_n<unsigned>(4);
+    unsigned flag = 0;
+    struct Drain {   // an error between the first enqueue and the synchronisation must not leave copies into dead host buffers behind
+        hipStream_t st; bool armed = true;
+        ~Drain() { if (armed) (void)hipStreamSynchronize(st); }
+    } drain{st};
+    ctx->prof_stream = st;
+    commit_tables_enqueue(st, sh, d_tables, cm->d_rows, cm->d_M, scratch, W, d_tree, d_flag, ctx, ctx->prof_class("pcs_commit_values", false));
+    cm->tree.resize(32 * (2 * N - 1));
+    hip_check(hipMemcpyAsync(cm->tree.data(), d_tree, cm->tree.size(), hipMemcpyDeviceToHost, st), "download tree");
+    hip_check(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st), "download flag");
+    const hipError_t synced = hipStreamSynchronize(st);
+    drain.armed = false;
+    hip_check(synced, "sync");
+    hip_check(hipGetLastError(), "launch");
+    ctx->prof_collect();
+    if (flag) throw Error("a table holds a word that is not below p");
     return cm.release();
 }
 

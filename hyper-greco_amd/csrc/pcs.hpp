@@ -69,6 +69,19 @@ Commitment* commit_device(hg_ctx* ctx, const Shape& sh, const u64* const* tables
 // members each: every handle is what commit_device gives for that member, except that a group's matrices share one allocation.
 // Throws an Error naming `who` (and "index i" for a member's word that is not below p); no handle survives an error
 std::vector<Commitment*> commit_device_batch(const char* who, hg_ctx* ctx, const Shape& sh, const u64* const* tables, size_t n);
+// The whole commit to m tables that lie in HBM (d_tables[t]: table t, 2^{v_t} words), enqueued on st: nothing is synchronised and
+// the context's arena is not touched. The caller supplies d_rows (R C words), d_M (R N), the NTT scratch (R N), W (N), the tree
+// buffer (8 N words: the levels one behind the other) and one flag word, which is set if a word is not below p. Rows of two words or
+// more are moved 16 bytes at a time when every table, d_rows and d_M are 16-byte aligned. prof (may be null): the context whose
+// profiler class cls the launches are counted in (its prof_stream must be st)
+void commit_tables_enqueue(hipStream_t st, const Shape& sh, const u64* const* d_tables, u64* d_rows, u64* d_M, u64* scratch, u64* W, u64* d_tree, unsigned* d_flag,
+                           hg_ctx* prof = nullptr, int cls = -1);
+// hg_secrets_commit_values: commit_tables_enqueue on the context's stream, the scratch from its arena, one synchronisation; the handle
+// owns d_rows and d_M. Its errors do not carry a name
+Commitment* commit_device_values(hg_ctx* ctx, const Shape& sh, const u64* const* d_tables);
+// an allocation of `bytes` that lives until the last copy of the returned owner is dropped (Commitment::owner of handles whose
+// matrices are laid into it by the caller)
+std::shared_ptr<void> slab_alloc(size_t bytes, u64** p);
 // the levels above the 4C leaf hashes at d_tree (4 words a node, the levels one behind the other), enqueued on st; nodes are 32 bytes
 // in either field
 void merkle_levels_device(hipStream_t st, u64* d_tree, size_t N);

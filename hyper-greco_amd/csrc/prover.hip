@@ -1,4 +1,5 @@
 #include "prover.hpp"
+#include "verifier_batch.hpp"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -1361,9 +1362,29 @@ struct EncPipe {
     u32* h_flags = nullptr;           // pinned, 2 x DRV_FLAG_WORDS
     u64* h_back[2] = {nullptr, nullptr};   // pinned: s | e | k1 | ais | r1is | r2is | ct0is of one item each
     hipEvent_t ev_t0[2] = {}, ev_t1[2] = {}, ev_derived[2] = {}, ev_flags[2] = {}, ev_copied[2] = {};
+    // hg_prove_encryptions_committed, sized for the shape (c_log2, c_rows) in use: the commit's NTT scratch (R N words) and twiddle
+    // table (N), which both table sets use one after the other on stream3; per table set the tree (8 N words) with the flag word
+    // behind it, in HBM and in page-locked staging; the commit's timing events and the event of the tree's copy
+    int c_log2 = -1;
+    size_t c_rows = 0;
+    u64* c_scratch = nullptr;
+    u64* c_W = nullptr;
+    u64* c_tree[2] = {nullptr, nullptr};
+    u64* h_tree[2] = {nullptr, nullptr};
+    hipEvent_t ev_c0[2] = {}, ev_c1[2] = {}, ev_tree[2] = {};
+    void commit_bufs_free() {
+        if (c_scratch) (void)hipFree(c_scratch);
+        if (c_W) (void)hipFree(c_W);
+        for (auto& t : c_tree) { if (t) (void)hipFree(t); t = nullptr; }
+        for (auto& t : h_tree) { if (t) (void)hipHostFree(t); t = nullptr; }
+        c_scratch = c_W = nullptr;
+        c_log2 = -1; c_rows = 0;
+    }
     ~EncPipe() {
         (void)hipSetDevice(device);
         if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
+        commit_bufs_free();
+        for (auto* evs : {ev_c0, ev_c1, ev_tree}) for (int q = 0; q < 2; q++) if (evs[q]) (void)hipEventDestroy(evs[q]);
         if (d_work) (void)hipFree(d_work);
         if (d_compact) (void)hipFree(d_compact);
         if (d_flags) (void)hipFree(d_flags);
@@ -1406,6 +1427,24 @@ static EncPipe* enc_pipe_get(hg_ctx* ctx, const hg_pk* pk, bool want_w) {
             if (!b) hip_check(hipHostMalloc((void**)&b, ((3 + 3 * k) * SZ + k * PZ) * 8, hipHostMallocDefault), "hipHostMalloc(witness copy-back staging)");
     return E;
 }
+// the commit's buffers for shape sh (nothing of an earlier run is in flight: every run drains the two side streams on its way out)
+static void enc_pipe_commit_bufs(EncPipe* E, const pcs::Shape& sh) {
+    for (int q = 0; q < 2; q++) {
+        if (E->ev_c0[q]) continue;
+        hip_check(hipEventCreate(&E->ev_c0[q]), "hipEventCreate"); hip_check(hipEventCreate(&E->ev_c1[q]), "hipEventCreate");
+        hip_check(hipEventCreateWithFlags(&E->ev_tree[q], hipEventDisableTiming), "hipEventCreate");
+    }
+    if (E->c_log2 == sh.c && E->c_rows == sh.R) return;
+    E->commit_bufs_free();
+    const size_t N = sh.N(), R = sh.R;
+    hip_check(hipMalloc((void**)&E->c_scratch, R * N * 8), "hipMalloc(commit NTT scratch)");
+    hip_check(hipMalloc((void**)&E->c_W, N * 8), "hipMalloc(commit twiddles)");
+    for (int q = 0; q < 2; q++) {
+        hip_check(hipMalloc((void**)&E->c_tree[q], (8 * N + 2) * 8), "hipMalloc(commit tree)");
+        hip_check(hipHostMalloc((void**)&E->h_tree[q], (8 * N + 2) * 8, hipHostMallocDefault), "hipHostMalloc(commit tree staging)");
+    }
+    E->c_log2 = sh.c; E->c_rows = R;
+}
 // a host copy by all host threads (pieces of 64 KiB), as the gather of witness_fill
 void par_copy(void* dst, const void* src, size_t bytes) {
     const size_t piece = (size_t)1 << 16, np = (bytes + piece - 1) / piece;
@@ -1423,18 +1462,26 @@ void par_copy(void* dst, const void* src, size_t bytes) {
 //         derive_combine, [event] circuit_levels, [ev_ready]; on the copy stream behind [event]: flag words, then the tables of the handle.
 // Walked proves (the first two per table set, the recording third, option "graph" = 0) run one after the other as in prove_stream;
 // the derivation of the next item still runs beside them, in its own buffers.
+// With cmt (hg_prove_encryptions_committed) the fill goes on, still on stream3, behind [ev_ready]: [ev_c0] the commit to the set's secret
+// tables into the item's slot of its group's allocation (pcs::commit_tables_enqueue: staging kernel, NTT, column hashes, tree) [ev_c1];
+// on the copy stream behind [ev_c1]: the tree and the flag word into page-locked staging [ev_tree]. The commit is no part of a launch
+// graph and delays neither [ev_ready] nor the flag words; the refill of the set two items later is behind it on the same stream.
+// On a stream of its own behind [ev_derived] (the refill waiting for [ev_c1]) an item took 3.40 ms against 3.23 ms this way at
+// n=32768 k=16 in runs of 16 (one box, one run each): a fifth stream shares the four hardware queues with the prove's.
 std::vector<EncResult> prove_encryptions(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e, const int64_t* const* k1,
-                                         const int64_t* const* a, size_t n_enc, bool want_w, double* total_ms) {
+                                         const int64_t* const* a, size_t n_enc, bool want_w, double* total_ms, const char* who_c, EncCommit* cmt) {
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
     const double t_all = wall_ms();
+    const std::string who(who_c);
     const Params& p = pk->params;
     const HCircuit& c = pk->circuit;
     dev::DeriveArgs plan;
     derive_plan(p, &plan);   // (parameters the derivation cannot serve are an error of the call, before anything is enqueued)
     std::vector<EncResult> out(n_enc);
+    if (cmt) { cmt->cms.clear(); cmt->cms.resize(n_enc); cmt->ms.assign(n_enc, 0.0); }
     if (!n_enc) return out;
     const size_t SZ = p.SZ(), PZ = p.PZ(), k = (size_t)p.k;
-    if (c.input_ids.size() != 3 + 2 * k + 1) throw Error("hg_prove_encryptions: unexpected input nodes");
+    if (c.input_ids.size() != 3 + 2 * k + 1) throw Error(who + ": unexpected input nodes");
     if (!ctx->stream3) {
         hip_check(hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking), "hipStreamCreate");
         for (auto& ev : ctx->ev_ready) hip_check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
@@ -1450,12 +1497,30 @@ std::vector<EncResult> prove_encryptions(hg_ctx* ctx, const hg_pk* pk, const int
     hg_values** V = ctx->stream_values;
     EncPipe* E = enc_pipe_get(ctx, pk, want_w);
     hipStream_t s3 = ctx->stream3, s4 = E->copy_stream;
+    // the commitments' matrices: items in groups of at most 64 within VB_PCS_BUDGET, a group's in one allocation that its handles share,
+    // made when the group's first item is filled. A slot is taken for good once its item is known to be proven: a refused item's
+    // slot is written again by the next item, behind it on stream3. (Declared ahead of the guard: it drains before they are freed.)
+    struct Slot { std::shared_ptr<void> owner; u64* rows = nullptr; u64* M = nullptr; };
+    std::vector<Slot> slots(cmt ? n_enc : 0);
+    struct { std::shared_ptr<void> owner; u64* p = nullptr; size_t cap = 0, used = 0; } slab;
+    size_t c_member = 0, c_group = 0, c_N = 0;
+    const u64* c_tabs[2][pcs::MAX_TABLES];
+    if (cmt) {
+        const pcs::Shape& sh = cmt->sh;
+        bool fits = sh.R <= 65535 && sh.nvars.size() == 4 + k;
+        for (size_t t = 0; fits && t < 4 + k; t++) fits = ((size_t)1 << sh.nvars[t]) == (t < 3 + k ? SZ : k * PZ);
+        if (!fits) throw Error(who + ": the commitment's shape is not that of the secret inputs");
+        enc_pipe_commit_bufs(E, sh);
+        c_N = sh.N();
+        c_member = sh.R * (sh.C() + c_N);   // words
+        c_group = std::max<size_t>(1, std::min<size_t>(VB_MAX_GROUP, VB_PCS_BUDGET / (c_member * 8)));
+    }
     // whatever happens, nothing of this run is left in flight on the two side streams when the call returns
     struct Drain { hipStream_t a, b; ~Drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); } } drain{s3, s4};
     dev::DeriveArgs A[2];
     for (int q = 0; q < 2; q++) {
         hg_values* v = V[q];
-        if (v->sizes[c.input_ids[3 + 2 * k]] != k * PZ || v->ct0is_len != k * SZ || !v->d_ct0is) throw Error("hg_prove_encryptions: table size mismatch");
+        if (v->sizes[c.input_ids[3 + 2 * k]] != k * PZ || v->ct0is_len != k * SZ || !v->d_ct0is) throw Error(who + ": table size mismatch");
         auto dv = [&](size_t x) { return const_cast<u64*>(v->d_vals[c.input_ids[x]]); };
         A[q] = plan;
         A[q].s = dv(0); A[q].e = dv(1); A[q].k1 = dv(2);
@@ -1465,7 +1530,16 @@ std::vector<EncResult> prove_encryptions(hg_ctx* ctx, const hg_pk* pk, const int
         A[q].X = E->d_work;
         A[q].flags = E->d_flags + (size_t)q * dev::DRV_FLAG_WORDS;
         for (size_t x = 0; x < 3 + k; x++)
-            if (((uintptr_t)dv(x) & 15) != 0 || v->sizes[c.input_ids[x]] != SZ) throw Error("hg_prove_encryptions: an input table is not laid out for 16-byte stores");
+            if (((uintptr_t)dv(x) & 15) != 0 || v->sizes[c.input_ids[x]] != SZ) throw Error(who + ": an input table is not laid out for 16-byte stores");
+        if (cmt) {   // the tables of hg_secrets_commit, in its order
+            size_t t = 0;
+            c_tabs[q][t++] = A[q].s; c_tabs[q][t++] = A[q].e; c_tabs[q][t++] = A[q].k1;
+            for (size_t i = 0; i < k; i++) {
+                if (v->sizes[c.input_ids[3 + k + i]] != SZ) throw Error(who + ": table size mismatch");
+                c_tabs[q][t++] = A[q].r1is[i];
+            }
+            c_tabs[q][t++] = A[q].r2is;
+        }
     }
     u64* scratch = E->d_work + (2 * k + 1) * SZ;
     // derivation + evaluation of item i into table set `set`, on stream3; copy-back behind the derivation on the copy stream
@@ -1492,12 +1566,31 @@ std::vector<EncResult> prove_encryptions(hg_ctx* ctx, const hg_pk* pk, const int
             back(A[set].r2is, k * PZ); back(A[set].ct0is, k * SZ);
             hip_check(hipEventRecord(E->ev_copied[set], s4), "event record");
         }
+        if (cmt) {   // behind the evaluation, so that ev_ready is not held up: the commit to the set's five kinds of secret tables
+            if (!slab.owner || slab.used == slab.cap) {
+                slab.cap = std::min(c_group, n_enc - i);
+                slab.used = 0;
+                slab.owner = pcs::slab_alloc(slab.cap * c_member * 8, &slab.p);
+            }
+            Slot& sl = slots[i];
+            sl.owner = slab.owner;
+            sl.rows = slab.p + slab.used * cmt->sh.R * cmt->sh.C();
+            sl.M = slab.p + slab.cap * cmt->sh.R * cmt->sh.C() + slab.used * cmt->sh.R * c_N;
+            u64* tree = E->c_tree[set];
+            hip_check(hipStreamWaitEvent(s3, E->ev_tree[set], 0), "stream wait");   // (the tree of the set's last item has left the device)
+            hip_check(hipEventRecord(E->ev_c0[set], s3), "event record");
+            pcs::commit_tables_enqueue(s3, cmt->sh, c_tabs[set], sl.rows, sl.M, E->c_scratch, E->c_W, tree, reinterpret_cast<unsigned*>(tree + 8 * c_N));
+            hip_check(hipEventRecord(E->ev_c1[set], s3), "event record");
+            hip_check(hipStreamWaitEvent(s4, E->ev_c1[set], 0), "stream wait");
+            hip_check(hipMemcpyAsync(E->h_tree[set], tree, (8 * c_N + 1) * 8, hipMemcpyDeviceToHost, s4), "download tree and flag");
+            hip_check(hipEventRecord(E->ev_tree[set], s4), "event record");
+        }
     };
     // the flag words of item i: "" or the reason it is refused
     auto refusal = [&](size_t i, int set) -> std::string {
         hip_check(hipEventSynchronize(E->ev_flags[set]), "wait for the derive flags");
         try {
-            derive_check_flags(p, E->h_flags + (size_t)set * dev::DRV_FLAG_WORDS, ("hg_prove_encryptions: encryption " + std::to_string(i)).c_str());
+            derive_check_flags(p, E->h_flags + (size_t)set * dev::DRV_FLAG_WORDS, (who + ": encryption " + std::to_string(i)).c_str());
         } catch (const Error& err) { return err.what(); }
         return "";
     };
@@ -1506,6 +1599,23 @@ std::vector<EncResult> prove_encryptions(hg_ctx* ctx, const hg_pk* pk, const int
         float ms = 0;
         hip_check(hipEventElapsedTime(&ms, E->ev_t0[set], E->ev_t1[set]), "event elapsed");
         out[i].witness_gpu_ms = ms;
+        if (cmt) {   // the tree into the handle; the commit's device time counts as the witness's
+            hip_check(hipEventSynchronize(E->ev_tree[set]), "wait for the commitment's tree");
+            const u64* h = E->h_tree[set];
+            if ((unsigned)h[8 * c_N]) throw Error(who + ": encryption " + std::to_string(i) + ": a derived table holds a word that is not below p");
+            hip_check(hipEventElapsedTime(&ms, E->ev_c0[set], E->ev_c1[set]), "event elapsed");
+            cmt->ms[i] = ms;
+            out[i].witness_gpu_ms += ms;
+            std::unique_ptr<pcs::Commitment> cm(new pcs::Commitment());
+            cm->sh = cmt->sh;
+            cm->ctx = ctx;
+            cm->d_rows = slots[i].rows;
+            cm->d_M = slots[i].M;
+            cm->owner = slots[i].owner;
+            cm->tree.resize(32 * (2 * c_N - 1));
+            par_copy(cm->tree.data(), h, cm->tree.size());
+            cmt->cms[i] = std::move(cm);
+        }
         if (!want_w) return;
         hip_check(hipEventSynchronize(E->ev_copied[set]), "wait for the witness copy-back");
         Witness& w = out[i].w;
@@ -1531,6 +1641,7 @@ std::vector<EncResult> prove_encryptions(hg_ctx* ctx, const hg_pk* pk, const int
             fill_next();
             continue;
         }
+        if (cmt) slab.used++;   // (the next fill takes the next slot)
         hip_check(hipStreamWaitEvent(ctx->stream, ctx->ev_ready[cur], 0), "wait for the witness");
         std::shared_ptr<ProveCache> C = graph_allowed(ctx) ? cache_find(ctx, pk, V[cur], 0, 1) : nullptr;
         if (C && !(ctx->slow_graph_serial == pk->serial && ctx->slow_graph_share == 1)) {

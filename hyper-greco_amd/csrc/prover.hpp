@@ -15,6 +15,7 @@
 #include <vector>
 #include "host.hpp"
 #include "kernels.hpp"
+#include "pcs.hpp"
 
 struct hg_ctx {
     typedef hg::u64 u64;
@@ -243,8 +244,14 @@ std::vector<ProveResult> prove_stream(hg_ctx* ctx, const hg_pk* pk, const std::v
 // circuit.evaluate of encryption i+1 on the third stream under the prove of encryption i. An item whose derivation checks fail is
 // not proven: refused = true, `reason` names table, modulus and cause. want_w: the host handle of every proven item (all seven tables)
 struct EncResult { ProveResult r; bool refused = false; std::string reason; Witness w; double witness_gpu_ms = 0; };
+// cmt (hg_prove_encryptions_committed, may be null): the commitment of hg_secrets_commit_values to every item's tables as well, made
+// on the third stream behind the item's evaluation. In: sh, the shape (R <= 65535). Out: cms[i], the handle of item i (null for a
+// refused one; a group of items shares one allocation, as the handles of commit_device_batch do), and ms[i], its commit's device
+// time. who: the entry's name in every message
+struct EncCommit { pcs::Shape sh; std::vector<std::unique_ptr<pcs::Commitment>> cms; std::vector<double> ms; };
 std::vector<EncResult> prove_encryptions(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e, const int64_t* const* k1,
-                                         const int64_t* const* a, size_t n_enc, bool want_w, double* total_ms);
+                                         const int64_t* const* a, size_t n_enc, bool want_w, double* total_ms, const char* who = "hg_prove_encryptions",
+                                         EncCommit* cmt = nullptr);
 void enc_pipe_drop(hg_ctx* ctx);
 // the same over bn256::Fr (bn254.hip): EncResult::r holds the proof bytes and prove_ms only
 namespace bn {

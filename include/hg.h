@@ -374,7 +374,8 @@ int hg_instance_mle_batch(hg_ctx* ctx, const void* const* instances, size_t n, i
  *   r1is[k-1], r2is: m = k+4, variables L, L, L, L x k, P + log2 k (L = log2 n + 1, P = log2 n).
  * hg_claims_open / hg_claims_verify: hg_pcs_open / hg_pcs_verify for an hg_input_claim array exactly as hg_verify_public* returns
  *   it (claims, n, points). Input ids map to tables 0, 1, 2 -> 0, 1, 2; 3+k+i -> 3+i; 3+2k -> 3+k; a claim on input 3 .. 3+k-1 (the
- *   public ais) or past 3+2k is an error (-1), so is a claim whose nvars is not its input's. hg_verify_public followed by
+ *   public ais) or past 3+2k is an error (-1), so is a claim whose nvars is not its input's. The commitment is one hg_secrets_commit
+ *   or hg_secrets_commit_batch made, or hg_secrets_commit_values / hg_prove_encryptions_committed. hg_verify_public followed by
  *   hg_claims_verify against a root the encryptor published is a verification that needs no secret. hg_claims_verify_device is
  *   hg_pcs_verify_device under the same mapping. */
 int hg_pcs_commit(hg_ctx* ctx, const uint64_t* const* tables, const uint32_t* nvars, size_t n_tables, size_t log2_row, void** commitment,
@@ -485,6 +486,44 @@ int hg_pcs_open_batch(hg_ctx* ctx, const void* const* commitments, const uint32_
 int hg_claims_open_batch(hg_ctx* ctx, const hg_params* params, const void* const* commitments, const void* claims, size_t claim_cap_each,
                          const uint64_t* points, size_t coord_cap_each, const size_t* n_claims, size_t n_queries, size_t n, uint8_t* openings,
                          size_t cap_each, size_t* lens, int* status, char* reasons, size_t reason_cap);
+
+/* hg_secrets_commit_values: hg_secrets_commit on a context, taken from where the tables lie in HBM: inputs 0, 1, 2, 3+k .. 3+2k-1 and
+ *   3+2k of v (s, e, k1, r1is[i], r2is), an hg_values of hg_witness_gen / hg_witness_gen_into / hg_witness_derive_into for this key on
+ *   this context. The handle is a Goldilocks device handle of ctx (hg_claims_open, hg_claims_open_batch, hg_pcs_open, hg_pcs_open_batch
+ *   and hg_pcs_free take it); its root and every opening made from it are byte for byte those of the host form of hg_secrets_commit on
+ *   the witness whose tables v holds. The handle owns copies of the rows: v may be refilled or freed afterwards.
+ *   One kernel reads every word of the k+4 tables once (16 bytes a thread where a row has two words or more) and writes it into the
+ *   handle's raw rows and into the zero-padded rows of the matrix to encode, with the padding and the range check; the batched NTT,
+ *   the column hashes and the tree follow as in hg_pcs_commit: nothing crosses the bus but the tree. The context's stream, its arena
+ *   for the scratch, one synchronisation: not concurrently with another call on the same context. Profiler class pcs_commit_values.
+ *   *commitment = NULL first. -1, hg_last_error beginning with the function's name, in this order: a null argument (pk, v,
+ *   commitment, root); a null context (".. : no context"); a host-only key; values of another key or of another context; a rank's
+ *   share of hg_witness_gen_shard, in which a secret input is not resident (the input is named); a log2_row outside the limits of
+ *   hg_pcs_commit or above the smallest table; more than 65535 rows; a word that is not below p.
+ * hg_prove_encryptions_committed: hg_prove_encryptions that also commits to every item's secret inputs, inside the pipeline.
+ *   Everything hg_prove_encryptions does and returns, with its checks in its order under this function's name (a refusal's text reads
+ *   "hg_prove_encryptions_committed: encryption i: .."); proof i is byte-identical to hg_prove_encryptions's. commitments and roots
+ *   are required when n_enc > 0: commitments[i] is what hg_secrets_commit_values(.., log2_row, ..) gives for item i's tables, the 32
+ *   bytes at roots + 32 i are its root. A refused item gets commitments[i] = NULL and 32 zero bytes. ws may be NULL, and the entry is
+ *   made to be called that way: the seven tables then never visit the host.
+ *   The commit of item i is enqueued on the third stream behind the item's derivation and evaluation, so it runs under the prove of
+ *   the item before (and of item i) and does not delay the event that prove i waits for; its tree comes back on the copy stream
+ *   into page-locked staging and enters the handle once prove i has completed. The NTT scratch, the twiddles and the tree buffers
+ *   belong to the pipeline, not to the arena. The raw and encoded rows of the items lie in group allocations - at most 64 items or
+ *   the 2 GiB budget of hg_pcs_commit_batch, allocated when a group's first item is filled - that the group's handles share: THE
+ *   MEMORY RETURNS WHEN THE LAST HANDLE OF THE GROUP IS FREED. The commit is outside the launch graph of a table set: the walked,
+ *   recording and replayed schedules and option "graph" = 0 give the same handles.
+ *   All commitments[i] are NULL at entry, as ws[i]. Returns the number of refused encryptions (n_enc == 0 returns 0) or -1, after
+ *   which no handle is alive: the errors of hg_prove_encryptions (commitments and roots count among the null arguments); then, ahead
+ *   of anything enqueued, the log2_row errors of hg_secrets_commit_values and more than 65535 rows; a derived table holding a word
+ *   that is not below p (".. encryption i: a derived table holds a word that is not below p"), which a correct derivation never gives.
+ *   timings: the fields of hg_prove_encryptions; witness_ms includes the commits' device time; upload_ms = the sum over the proven
+ *   items of the commit's device time alone (HIP events on the stream it runs on). Goldilocks, mode 0. */
+int hg_secrets_commit_values(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, size_t log2_row, void** commitment, uint8_t root[32]);
+int hg_prove_encryptions_committed(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e, const int64_t* const* k1,
+                                   const int64_t* const* a, size_t n_enc, size_t log2_row, uint8_t* proofs, size_t cap_each, size_t* lens,
+                                   int* status, void** commitments, uint8_t* roots, hg_witness** ws, char* reasons, size_t reason_cap,
+                                   hg_timings* timings);
 
 /* The same pair in a protocol mode that FIXES the reference's two known soundness gaps. mode bits:
  *   1  absorbing transcript: write_felt / read_felt also hash the element - the rule of the in-tree plonkish-trait writer of
