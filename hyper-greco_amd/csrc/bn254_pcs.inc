@@ -3,10 +3,11 @@
 // Montgomery-form powers of w, so plain words go through ntt_batch_dev and come out plain - no conversion pass on either NTT path,
 // and the leaf hash and the column gather read the matrix as it is. Keccak and the tree are those of the Goldilocks form
 // (pcs_keccak.hpp, pcs::merkle_levels_device): a node is 32 bytes in either field.
-// The verifier of an opening (pcs_verify_device) reuses the encoding, the leaf sponge and the accumulators and adds five kernels.
-// The verifier of a run of openings (pcs_verify_device_batch) runs the same five kernels once over a group, driven by a member table.
-// A run of commitments (pcs_commit_device_batch) and a run of openings (pcs_open_device_batch) do the same for the prover's side: a
-// group's matrices in one allocation that its handles share, the kernels of commit and open once over the group.
+// The verifier of an opening reuses the encoding, the leaf sponge and the accumulators and adds five kernels.
+// Every step has one kernel, written for a group of members and driven by a member or job table; the forms for a run
+// (pcs_commit_device_batch, pcs_open_device_batch, pcs_verify_device_batch) launch it once over a group, whose matrices lie in one
+// allocation that its handles share, and the forms for one (pcs_commit_device, pcs_combine_device, pcs_verify_device) launch it
+// over a group of one from a host flow of their own.
 
 constexpr int BNPCS_TPB = 256;
 static unsigned bnpcs_blocks(size_t n) { return (unsigned)((n + BNPCS_TPB - 1) / BNPCS_TPB); }
@@ -15,18 +16,23 @@ static unsigned bnpcs_blocks(size_t n) { return (unsigned)((n + BNPCS_TPB - 1) /
 __global__ __launch_bounds__(BNPCS_TPB) void k_bnpcs_lift(const u64* __restrict__ words, Fr* __restrict__ rows, size_t n) {
     for (size_t i = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x; i < n; i += (size_t)gridDim.x * BNPCS_TPB) lz_gstore(rows + i, fr_lift_signed_canon(words[i]));
 }
-// M[r][j] = j < C ? rows[r][j] : 0 ahead of the encoding; an element that is not below r sets *flag
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcs_stage(const Fr* __restrict__ rows, Fr* __restrict__ M, size_t R, int c, unsigned* __restrict__ flag) {
+// ---- the kernels of a commitment, written for a group of G members of one shape (pcs_commit_device_batch); one commitment is a
+// group of one. Member m's raw rows lie at rows + m R C, its encoded rows at M + m R N and its tree at trees + m tree_words.
+// blockIdx.y = the member, its elements grid-strided over blockIdx.x: M[r][j] = j < C ? rows[r][j] : 0 ahead of the encoding; an
+// element that is not below r (all four limbs compared) sets the member's flag
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsb_stage(const Fr* __restrict__ rows, Fr* __restrict__ M, size_t R, int c, unsigned* __restrict__ flags) {
     const size_t total = R << (c + 2);
     const size_t C = (size_t)1 << c, Nm = ((size_t)4 << c) - 1;
+    const Fr* src = rows + (((size_t)blockIdx.y * R) << c);
+    Fr* dst = M + (size_t)blockIdx.y * total;
     bool bad = false;
     for (size_t i = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * BNPCS_TPB) {
         const size_t r = i >> (c + 2), j = i & Nm;
         Fr v = fr_zero();
-        if (j < C) { v = lz_gload(rows + (r << c) + j); bad |= fr_geq_p(v); }
-        lz_gstore(M + i, v);
+        if (j < C) { v = lz_gload(src + (r << c) + j); bad |= fr_geq_p(v); }
+        lz_gstore(dst + i, v);
     }
-    if (bad) atomicOr(flag, 1u);
+    if (bad) atomicOr(flags + blockIdx.y, 1u);
 }
 
 // The sponge of a leaf: a = the state after Keccak256(LE64(0) || repr(e_0) || .. || repr(e_{R-1})), element r at col + r * stride
@@ -52,14 +58,17 @@ __device__ __forceinline__ void bnpcs_leaf_absorb(const u64* __restrict__ col, s
         pcs::keccak_f(a);
     }
 }
-// One thread per column j of the encoded matrix: leaves[j] = the leaf hash of M[0][j] .. M[R-1][j]. A wavefront reads 64 adjacent
-// elements of a row; the four words of an element come from one 32-byte sector.
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcs_leaf_hash(const Fr* __restrict__ M, size_t N, size_t R, u64* __restrict__ leaves) {
-    const size_t j = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
-    if (j >= N) return;
+// One thread per (member m, column j) of the encoded matrices (N = 2^depth columns), id = m N + j: the leaf hash of the member's
+// M[0][j] .. M[R-1][j] into the leaves of its own tree. A wavefront reads 64 adjacent elements of a row; the four words of an element
+// come from one 32-byte sector. A member's columns may begin inside a wavefront (N < 64): every address comes from the thread's own
+// m and j.
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsb_leaf_hash(const Fr* __restrict__ M, size_t G, int depth, size_t R, u64* __restrict__ trees, size_t tree_words) {
+    const size_t id = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
+    if (id >= G << depth) return;
+    const size_t N = (size_t)1 << depth, m = id >> depth, j = id & (N - 1);
     u64 a[25];
-    bnpcs_leaf_absorb(reinterpret_cast<const u64*>(M + j), 4 * N, R, a);   // 4N words between the rows
-    u64* out = leaves + 4 * j;
+    bnpcs_leaf_absorb(reinterpret_cast<const u64*>(M + m * R * N + j), 4 * N, R, a);   // 4N words between the rows
+    u64* out = trees + m * tree_words + 4 * j;
     out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
 }
 
@@ -74,29 +83,22 @@ __device__ __forceinline__ void bnpcs_mac_uniform(WCol& w, const Fr& a, const u3
         BN_WIDE_ROW4S(w.C[i + 4], w.C[i + 5], w.C[i + 6], w.C[i + 7], w.T[i + 4], w.T[i + 5], w.T[i + 6], w.T[i + 7], al[i], bl[4], bl[5], bl[6], bl[7]);
     }
 }
-// Row combinations of an opening. Job q (blockIdx.y): u_q[j] = sum_{r < nrows} w[woff + r] * rows[row0 + r][j]; a thread owns column j,
-// the weight is uniform over the workgroup. Products of a canonical element and a Montgomery-form weight go into the column
-// accumulators and are reduced every BNPCS_CHUNK rows by lz_reduce, which takes a value below 2^12 p^2: both factors are below
-// p, so a chunk sums to less than BNPCS_CHUNK p^2 and any BNPCS_CHUNK <= 4096 = 2^12 is inside the bound. 1024 is chosen: a
-// quarter of the bound (also inside wcol_reduce's 2^10 r^2), and the reduction is already 1/1024 of the multiply-adds. The carry
-// counters (32 bits, at most one carry a multiply-add, 16 multiply-adds a column and product) are nowhere near their range.
-struct BnPcsDesc { u64 row0, nrows, woff; };
+// sum_{r < nrows} w[r] * src[r << shift], canonical, for weights that are uniform over the wavefront (their limbs go through
+// readfirstlane). Products of a canonical element and a Montgomery-form weight go into the column accumulators and are reduced
+// every BNPCS_CHUNK rows by lz_reduce, which takes a value below 2^12 p^2: both factors are below p, so a chunk sums to less than
+// BNPCS_CHUNK p^2 and any BNPCS_CHUNK <= 4096 = 2^12 is inside the bound. 1024 is chosen: a quarter of the bound (also inside
+// wcol_reduce's 2^10 r^2), and the reduction is already 1/1024 of the multiply-adds. The carry counters (32 bits, at most one carry
+// a multiply-add, 16 multiply-adds a column and product) are nowhere near their range.
 constexpr int BNPCS_CHUNK = 1024;
 static_assert(BNPCS_CHUNK <= 4096, "lz_reduce takes a value below 2^12 p^2");
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcs_combine(const Fr* __restrict__ rows, int c, const BnPcsDesc* __restrict__ jobs, const Fr* __restrict__ w,
-                                                             Fr* __restrict__ u) {
-    const size_t C = (size_t)1 << c;
-    const size_t j = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
-    if (j >= C) return;
-    const BnPcsDesc job = jobs[blockIdx.y];
-    const Fr* src = rows + (job.row0 << c) + j;
-    const u32* wq = reinterpret_cast<const u32*>(w + job.woff);
+__device__ __forceinline__ Fr bnpcs_dot_chunked(const Fr* __restrict__ src, int shift, const Fr* __restrict__ w, u64 nrows) {
+    const u32* wq = reinterpret_cast<const u32*>(w);
     Fr s = fr_zero();
-    for (u64 r0 = 0; r0 < job.nrows; r0 += BNPCS_CHUNK) {
-        const u64 r1 = r0 + BNPCS_CHUNK < job.nrows ? r0 + BNPCS_CHUNK : job.nrows;
+    for (u64 r0 = 0; r0 < nrows; r0 += BNPCS_CHUNK) {
+        const u64 r1 = r0 + BNPCS_CHUNK < nrows ? r0 + BNPCS_CHUNK : nrows;
         WCol A = wcol_zero();
         for (u64 r = r0; r < r1; r++) {
-            const Fr x = lz_gload(src + (r << c));
+            const Fr x = lz_gload(src + (r << shift));
             u32 bl[8];
 #pragma unroll
             for (int k = 0; k < 8; k++) bl[k] = __builtin_amdgcn_readfirstlane(wq[8 * r + k]);
@@ -104,7 +106,7 @@ __global__ __launch_bounds__(BNPCS_TPB) void k_bnpcs_combine(const Fr* __restric
         }
         s = lz_add(s, lz_reduce(A));
     }
-    lz_gstore(u + (size_t)blockIdx.y * C + j, lz_canon(s));
+    return lz_canon(s);
 }
 
 // cols[q][r] = M[r][js[q]]
@@ -112,6 +114,196 @@ __global__ __launch_bounds__(BNPCS_TPB) void k_bnpcs_gather(const Fr* __restrict
     const size_t r = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
     if (r >= R) return;
     lz_gstore(cols + (size_t)blockIdx.y * R + r, lz_gload(M + r * N + js[blockIdx.y]));
+}
+
+// ---- the kernels of the verifier, written for a group of G openings of one shape and one Q (pcs_verify_device_batch); one opening
+// (pcs_verify_device) is a group of one, its device copy the set. What differs by member (its claim count, where its opening, u,
+// columns, encoded rows, jobs and weights lie) is read from its descriptor, never derived from a flat id, and no member's range is
+// assumed to start at a workgroup. Every block of the staged copy starts at a multiple of 32 bytes (lz_gload reads 16-byte halves).
+// A word of an opening only ever becomes a number; every index below comes from the shape, from the host's masked j_q or from table
+// offsets the entry point validated. Each result cell holds the lowest offending key (atomicMin), so the reason is the host's also
+// where several checks fail at once.
+constexpr u64 BNPCSV_NONE = ~(u64)0;   // a cell no thread lowered: nothing failed
+__device__ __forceinline__ void bnpcsv_min(u64* cell, u64 v) { atomicMin(reinterpret_cast<unsigned long long*>(cell), (unsigned long long)v); }
+struct BnPcsDesc { u64 row0, nrows, woff; };   // a row combination: sum_{r < nrows} w[woff + r] * row_{row0 + r}
+struct BnVbMember {
+    u64 proof, u, cols, enc_row;               // word offset of its opening in the set; element offsets of its u and columns; its first row of enc
+    u64 n, claim0, job0;                       // its claims; the claims and the jobs (claims + 1 each) of the members before it
+    u64 root_at, jobs_at, y_at, z_at, w_at;    // byte offsets in the group's staged copy: root, job descriptors, values, low coordinates, weights
+};
+struct BnVbGroup { u64 G, Q, R, q_el; int c, depth; };
+
+// 32 big-endian bytes of an opening -> 4 native limbs (limb w = the byte-swapped word 3 - w); blockIdx.y = the member, its elements
+// grid-strided over blockIdx.x. Element i < u_el is element i & (C - 1) of u vector i >> c: kept in u and scattered into row i >> c
+// of the member's rows of the matrix the NTT encodes (zeroed beforehand). The others are the Q * R column elements, query q at
+// element u_el + q * q_el. cells[3m] = the lowest byte offset, within its opening, of an element that is not below r (all four limbs
+// compared). Elements stay plain words: no Montgomery conversion (ntt_batch_dev keeps the form).
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_canon(const u64* __restrict__ set, const BnVbMember* __restrict__ mem, BnVbGroup g, Fr* __restrict__ u,
+                                                             Fr* __restrict__ cols, Fr* __restrict__ enc, u64* __restrict__ cells) {
+    const BnVbMember M = mem[blockIdx.y];
+    const int c = g.c;
+    const size_t Q = g.Q, R = g.R, u_el = (M.n + 1) << c, total = u_el + Q * R, Cm = ((size_t)1 << c) - 1;
+    const u64* proof = set + M.proof;
+    Fr* mu = u + M.u;
+    Fr* mcols = cols + M.cols;
+    Fr* menc = enc + (M.enc_row << (c + 2));
+    u64 bad = BNPCSV_NONE;
+    for (size_t i = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * BNPCS_TPB) {
+        size_t at = i;
+        if (i >= u_el) { const size_t k = i - u_el, q = k / R; at = u_el + q * g.q_el + (k - q * R); }
+        const u64* p = proof + 4 * at;
+        const Fr v = fr_make(__builtin_bswap64(p[3]), __builtin_bswap64(p[2]), __builtin_bswap64(p[1]), __builtin_bswap64(p[0]));
+        if (fr_geq_p(v) && 32 * at < bad) bad = 32 * at;
+        if (i < u_el) {
+            lz_gstore(mu + i, v);
+            lz_gstore(menc + ((i >> c) << (c + 2)) + (i & Cm), v);
+        } else {
+            lz_gstore(mcols + (i - u_el), v);
+        }
+    }
+    if (bad != BNPCSV_NONE) bnpcsv_min(cells + 3 * blockIdx.y, bad);
+}
+
+// <ui, eq(z[..c])> != y, by one workgroup; the answer is thread 0's. z holds the c low coordinates of the point in Montgomery form,
+// so a factor of eq(z, x) = prod_b (x_b ? z_b : 1 - z_b) is in Montgomery form and factor x plain element is the plain product. The
+// factors are formed per entry: a thread keeps the one of the low eight bits of x, which its entries share.
+__device__ __forceinline__ bool bnpcs_eval_differs(const Fr* __restrict__ ui, const Fr* __restrict__ z, const Fr* __restrict__ y, int c) {
+    __shared__ Fr part[BNPCS_TPB];
+    const size_t C = (size_t)1 << c;
+    const int lob = c < 8 ? c : 8;
+    Fr f = fr_one_mont();
+    for (int b = 0; b < lob; b++) { const Fr zb = lz_gload(z + b); f = fr_mul(f, (threadIdx.x >> b) & 1 ? zb : fr_sub(fr_one_mont(), zb)); }
+    Fr s = fr_zero();
+    for (size_t x = threadIdx.x; x < C; x += BNPCS_TPB) {
+        Fr gq = f;
+        for (int b = 8; b < c; b++) { const Fr zb = lz_gload(z + b); gq = fr_mul(gq, (x >> b) & 1 ? zb : fr_sub(fr_one_mont(), zb)); }
+        s = fr_add(s, fr_mul(lz_gload(ui + x), gq));
+    }
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = BNPCS_TPB / 2; h >= 1; h >>= 1) {
+        if (threadIdx.x < h) part[threadIdx.x] = fr_add(part[threadIdx.x], part[threadIdx.x + h]);
+        __syncthreads();
+    }
+    return threadIdx.x == 0 && !fr_eq(part[0], lz_gload(y));
+}
+// <u_i, eq(z_i[..c])> == y_i, one workgroup per (member, claim): block b belongs to the last member whose claim0 is <= b (a member
+// without claims owns no block). cells[3m + 1] = the member's lowest failing claim.
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_eval(const BnVbMember* __restrict__ mem, unsigned G, int c, const Fr* __restrict__ u, const char* __restrict__ stage,
+                                                            u64* __restrict__ cells) {
+    unsigned lo = 0, hi = G;
+    while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].claim0 <= blockIdx.x) lo = mid; else hi = mid; }
+    const BnVbMember M = mem[lo];
+    const size_t i = blockIdx.x - M.claim0;
+    if (i >= M.n) return;   // (uniform over the workgroup; the grid has exactly the claims of the group)
+    if (bnpcs_eval_differs(u + M.u + ((i + 1) << c), reinterpret_cast<const Fr*>(stage + M.z_at) + i * (size_t)c, reinterpret_cast<const Fr*>(stage + M.y_at) + i, c))
+        bnpcsv_min(cells + 3 * lo + 1, (u64)i);
+}
+
+// One thread per (member m, query q), id = m Q + q: the leaf hash of its R column elements (contiguous: 4 words between them) -> leaves[id]
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_leaf(const BnVbMember* __restrict__ mem, BnVbGroup g, const Fr* __restrict__ cols, u64* __restrict__ leaves) {
+    const size_t id = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
+    if (id >= g.G * g.Q) return;
+    const size_t m = id / g.Q, q = id - m * g.Q;
+    u64 a[25];
+    bnpcs_leaf_absorb(reinterpret_cast<const u64*>(cols + mem[m].cols + q * g.R), 4, g.R, a);
+    u64* out = leaves + 4 * id;
+    out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
+}
+
+// Column inner products of every member: s[global job][q] = sum_{r < nrows} w[woff + r] * col_q[row0 + r], canonical. Job 0 of a
+// member is the proximity combination (rho^r over the whole column), job 1 + i claim i's (eq(z_i[c..]) over the rows of its table).
+// The weight limbs go through readfirstlane and so must be the same for every lane of a wavefront. A flat id Q job + q would let a
+// wavefront straddle two jobs whenever Q is no multiple of 64, so the job is fixed per workgroup instead: a one-dimensional grid of
+// bq * jobs_total workgroups, bq = the workgroups Q threads take (no y extent: the jobs of a group can pass 65535); workgroup b
+// works on global job b / bq, queries (b % bq) TPB .. . The member is the last one whose job0 is <= the job. A column element that
+// passed k_bnpcsvb_canon is below r and the weight is a residue, which is bnpcs_dot_chunked's bound. (An element that did not pass
+// only makes this sum meaningless, and cells[3m] decides ahead of whatever reads it.)
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_dots(const BnVbMember* __restrict__ mem, BnVbGroup g, unsigned bq, const Fr* __restrict__ cols,
+                                                            const char* __restrict__ stage, Fr* __restrict__ s) {
+    const size_t gjob = blockIdx.x / bq;
+    const size_t q = (size_t)(blockIdx.x % bq) * BNPCS_TPB + threadIdx.x;
+    if (q >= g.Q) return;
+    unsigned lo = 0, hi = (unsigned)g.G;
+    while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].job0 <= gjob) lo = mid; else hi = mid; }
+    const BnVbMember M = mem[lo];
+    const BnPcsDesc job = reinterpret_cast<const BnPcsDesc*>(stage + M.jobs_at)[gjob - M.job0];
+    lz_gstore(s + gjob * g.Q + q, bnpcs_dot_chunked(cols + M.cols + q * g.R + job.row0, 0, reinterpret_cast<const Fr*>(stage + M.w_at) + job.woff, job.nrows));
+}
+
+// One thread per (member m, query q), id = m Q + q, once the host has every member's column indices (js[id]): the path from the leaf
+// hash over the c+2 siblings (32 raw bytes each behind the query's column elements) against the member's root, then s[job 0][q]
+// against Enc(u_0)[j_q], then s[job 1 + i][q] against Enc(u_i)[j_q]. cells[3m + 2] = the member's lowest q (n_m + 2) + kind that
+// failed: kind 0 the path, 1 proximity, 2 + i claim i.
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_query(const u64* __restrict__ set, const BnVbMember* __restrict__ mem, BnVbGroup g, const u64* __restrict__ leaves,
+                                                             const Fr* __restrict__ s, const Fr* __restrict__ enc, const u64* __restrict__ js,
+                                                             const char* __restrict__ stage, u64* __restrict__ cells) {
+    const size_t id = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
+    if (id >= g.G * g.Q) return;
+    const size_t m = id / g.Q, q = id - m * g.Q;
+    const BnVbMember M = mem[m];
+    const int depth = g.depth;
+    const size_t N = (size_t)1 << depth, j = js[id], n = M.n, u_el = (n + 1) << g.c;
+    const u64* sib = set + M.proof + 4 * (u_el + q * g.q_el + g.R);
+    const u64* root = reinterpret_cast<const u64*>(stage + M.root_at);
+    u64 h[4] = {leaves[4 * id], leaves[4 * id + 1], leaves[4 * id + 2], leaves[4 * id + 3]};
+    pcs::merkle_climb(h, sib, j, depth);
+    u64* cell = cells + 3 * m + 2;
+    const size_t key = q * (n + 2);
+    if (h[0] != root[0] || h[1] != root[1] || h[2] != root[2] || h[3] != root[3]) { bnpcsv_min(cell, key); return; }
+    const Fr* sq = s + M.job0 * g.Q + q;
+    const Fr* menc = enc + (M.enc_row << depth) + j;
+    for (size_t i = 0; i <= n; i++)
+        if (!fr_eq(lz_gload(sq + i * g.Q), lz_gload(menc + i * N))) { bnpcsv_min(cell, key + 1 + i); return; }
+}
+
+// ---- the kernels of the prover's side of an opening, written for a group of items (pcs_open_device_batch); the row combinations of
+// one opening (pcs_combine_device) are a job table of their own. What differs by item lies in three flat tables of the staged copy:
+// a job a row combination (the proximity combination and one a claim, every member's behind the other), a claim an evaluation
+// check, a member where its matrix, its u vectors and its opening image lie. Every block of the staged copy starts at a multiple of
+// 32 bytes (lz_gload reads 16-byte halves). Every grid is one-dimensional.
+struct BnObJob { const Fr* src; u64 nrows, w_at, u_at; };      // its first raw row; the byte offset of its weights in the staged copy; where u goes (elements)
+struct BnObClaim { u64 u_at, z_at, y_at, member, claim; };     // its u_i (elements); byte offsets of the low coordinates (Montgomery) and of the value
+struct BnObMember { const Fr* M; u64 img, u, u_words; };       // its encoded matrix; word offsets of its image and of its u vectors; 4 C (n + 1)
+
+// Row combinations: u[u_at + j] = sum_{r < nrows} w[r] * src[r][j] for the job of the workgroup, a thread owns column j. Workgroup b
+// serves job b / cb alone, columns (b % cb) BNPCS_TPB .. - the weight limbs go through readfirstlane, so every lane of a wavefront
+// must be on one job
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_combine(int c, unsigned cb, const BnObJob* __restrict__ jobs, const char* __restrict__ stage, Fr* __restrict__ u) {
+    const size_t C = (size_t)1 << c;
+    const unsigned jq = blockIdx.x / cb;
+    const size_t j = (size_t)(blockIdx.x - jq * cb) * BNPCS_TPB + threadIdx.x;
+    if (j >= C) return;
+    const BnObJob job = jobs[jq];
+    lz_gstore(u + job.u_at + j, bnpcs_dot_chunked(job.src + j, c, reinterpret_cast<const Fr*>(stage + job.w_at), job.nrows));
+}
+// One workgroup per (member, claim): <u_i, eq(z_i[..c])> == y_i; cells[member] = its lowest failing claim
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_eval(const BnObClaim* __restrict__ claims, int c, const Fr* __restrict__ u, const char* __restrict__ stage,
+                                                            u64* __restrict__ cells) {
+    const BnObClaim cl = claims[blockIdx.x];
+    if (bnpcs_eval_differs(u + cl.u_at, reinterpret_cast<const Fr*>(stage + cl.z_at), reinterpret_cast<const Fr*>(stage + cl.y_at), c)) bnpcsv_min(cells + cl.member, cl.claim);
+}
+// Word i of the group's u vectors into its member's image, an element as 32 bytes big-endian: word w of the image's element is the
+// byte-swapped limb 3 - w. The member is the last one whose u offset is <= i (offsets are multiples of 4: an element never straddles)
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_emit(const BnObMember* __restrict__ mem, unsigned G, size_t total, const u64* __restrict__ u, u64* __restrict__ img) {
+    for (size_t i = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * BNPCS_TPB) {
+        unsigned lo = 0, hi = G;
+        while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].u <= i) lo = mid; else hi = mid; }
+        img[mem[lo].img + (i - mem[lo].u)] = __builtin_bswap64(u[i ^ 3]);
+    }
+}
+// One thread per (member m, query q, row r), id = (m Q + q) R + r: M_m[r][j_q] big-endian at its place in the member's image.
+// js[m Q + q] = j_q (masked by the host); js[G Q + m] != 0: the member takes part (it was not refused)
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_gather(const BnObMember* __restrict__ mem, size_t G, size_t Q, size_t R, size_t N, size_t q_words,
+                                                              const u64* __restrict__ js, u64* __restrict__ img) {
+    const size_t id = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
+    if (id >= G * Q * R) return;
+    const size_t m = id / (Q * R), k = id - m * Q * R, q = k / R, r = k - q * R;
+    if (!js[G * Q + m]) return;
+    const BnObMember M = mem[m];
+    const Fr v = lz_gload(M.M + r * N + js[m * Q + q]);
+    u64* out = img + M.img + M.u_words + q * q_words + 4 * r;
+    out[0] = __builtin_bswap64(v.l[3]); out[1] = __builtin_bswap64(v.l[2]); out[2] = __builtin_bswap64(v.l[1]); out[3] = __builtin_bswap64(v.l[0]);
 }
 
 // One stream, one synchronisation. The NTT temporary (the size of the encoded matrix) and the uploaded witness words live in the
@@ -140,10 +332,7 @@ pcs::Commitment* pcs_commit_device(const char* who, hg_ctx* ctx, const pcs::Shap
     const int c_stage = ctx->prof_class("pcs_bn254_stage", false), c_ntt = ctx->prof_class("pcs_bn254_ntt", false), c_leaf = ctx->prof_class("pcs_bn254_leaf", false),
               c_tree = ctx->prof_class("pcs_bn254_tree", false);
     ctx->prof_stream = st;
-    struct Drain {   // an error between the first enqueue and the synchronisation must not leave copies of the caller's tables behind
-        hipStream_t st; bool armed = true;
-        ~Drain() { if (armed) (void)hipStreamSynchronize(st); }
-    } drain{st};
+    pcs::DrainOne drain{st};   // (drains on an error; after the synchronisation below its own is one more, on an idle stream)
     hipc(hipMemsetAsync(d_flag, 0, 16, st), "memset");
     for (size_t t = 0; t < sh.nvars.size(); t++) {
         const size_t len = (size_t)1 << sh.nvars[t];
@@ -152,14 +341,14 @@ pcs::Commitment* pcs_commit_device(const char* who, hg_ctx* ctx, const pcs::Shap
     }
     ctx->prof_begin(c_stage, (double)R * C * (words ? 40 : 0) + (double)R * C * 32 + (double)R * N * 32);
     if (words) k_bnpcs_lift<<<(unsigned)std::min<size_t>(bnpcs_blocks(R * C), 4096), BNPCS_TPB, 0, st>>>(d_words, d_rows, R * C);
-    k_bnpcs_stage<<<(unsigned)std::min<size_t>(bnpcs_blocks(R * N), 4096), BNPCS_TPB, 0, st>>>(d_rows, d_M, R, sh.c, d_flag);
+    k_bnpcsb_stage<<<(unsigned)std::min<size_t>(bnpcs_blocks(R * N), 4096), BNPCS_TPB, 0, st>>>(d_rows, d_M, R, sh.c, d_flag);
     ctx->prof_end();
     ctx->prof_begin(c_ntt, (double)R * N * 32 * 4);
     k_bn_powers<<<bnpcs_blocks(N), 256, 0, st>>>(W, fr_root_of_unity(log2n), N);
     ntt_batch_dev(st, d_M, tmp, W, log2n, R, nullptr);
     ctx->prof_end();
     ctx->prof_begin(c_leaf, (double)R * N * 32);
-    k_bnpcs_leaf_hash<<<bnpcs_blocks(N), BNPCS_TPB, 0, st>>>(d_M, N, R, d_tree);
+    k_bnpcsb_leaf_hash<<<bnpcs_blocks(N), BNPCS_TPB, 0, st>>>(d_M, 1, log2n, R, d_tree, 8 * N);
     ctx->prof_end();
     ctx->prof_begin(c_tree, (double)N * 96);
     pcs::merkle_levels_device(st, d_tree, N);
@@ -168,9 +357,7 @@ pcs::Commitment* pcs_commit_device(const char* who, hg_ctx* ctx, const pcs::Shap
     unsigned flag = 0;
     hipc(hipMemcpyAsync(cm->tree.data(), d_tree, cm->tree.size(), hipMemcpyDeviceToHost, st), "download tree");
     hipc(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st), "download flag");
-    const hipError_t synced = hipStreamSynchronize(st);
-    drain.armed = false;
-    hipc(synced, (me + ": sync").c_str());
+    hipc(hipStreamSynchronize(st), (me + ": sync").c_str());
     hipc(hipGetLastError(), (me + ": launch").c_str());
     ctx->prof_collect();
     if (flag) throw Error(me + ": a table holds an element that is not below r");
@@ -184,27 +371,26 @@ void pcs_combine_device(const pcs::Commitment& cm, const std::vector<PcsJob>& jo
     hipStream_t st = ctx->stream;
     const size_t C = cm.sh.C(), nj = jobs.size();
     if (nj > 65535) throw Error("hg_pcs_open_bn254: more than 65534 claims");
-    // descriptors and weights in one staged copy
+    // the job table and the weights in one staged copy; job q's u vector is the q-th
     size_t nw = 0;
     for (const PcsJob& j : jobs) nw += j.nrows;
-    const size_t desc_bytes = (nj * sizeof(BnPcsDesc) + 31) & ~(size_t)31;
+    const size_t desc_bytes = (nj * sizeof(BnObJob) + 31) & ~(size_t)31;
     std::vector<char> stage(desc_bytes + nw * sizeof(Fr));
-    BnPcsDesc* hd = reinterpret_cast<BnPcsDesc*>(stage.data());
-    char* hw = stage.data() + desc_bytes;
-    size_t off = 0;
+    BnObJob* hd = reinterpret_cast<BnObJob*>(stage.data());
+    size_t w_at = desc_bytes;
     for (size_t q = 0; q < nj; q++) {
-        hd[q].row0 = jobs[q].row0; hd[q].nrows = jobs[q].nrows; hd[q].woff = off;
-        memcpy(hw + off * sizeof(Fr), jobs[q].w.data(), jobs[q].nrows * sizeof(Fr));
-        off += jobs[q].nrows;
+        hd[q].src = reinterpret_cast<const Fr*>(cm.d_rows) + (jobs[q].row0 << cm.sh.c); hd[q].nrows = jobs[q].nrows; hd[q].w_at = w_at; hd[q].u_at = q * C;
+        memcpy(stage.data() + w_at, jobs[q].w.data(), jobs[q].nrows * sizeof(Fr));
+        w_at += jobs[q].nrows * sizeof(Fr);
     }
     char* d_stage = ctx->alloc_n<char>(stage.size());
     Fr* d_u = ctx->alloc_n<Fr>(nj * C);
+    const unsigned cb = bnpcs_blocks(C);   // (at most 2^16 workgroups a job and, by the entry point, MAX_CLAIMS + 1 jobs: inside a grid's x)
     const int cls = ctx->prof_class("pcs_bn254_combine", false);
     ctx->prof_stream = st;
     hipc(hipMemcpyAsync(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, st), "upload weights");
     ctx->prof_begin(cls, (double)nw * C * 32);
-    k_bnpcs_combine<<<dim3(bnpcs_blocks(C), (unsigned)nj), BNPCS_TPB, 0, st>>>(reinterpret_cast<const Fr*>(cm.d_rows), cm.sh.c, reinterpret_cast<const BnPcsDesc*>(d_stage),
-                                                                               reinterpret_cast<const Fr*>(d_stage + desc_bytes), d_u);
+    k_bnpcsob_combine<<<(unsigned)(nj * cb), BNPCS_TPB, 0, st>>>(cm.sh.c, cb, reinterpret_cast<const BnObJob*>(d_stage), d_stage, d_u);
     ctx->prof_end();
     hipc(hipMemcpyAsync(u, d_u, nj * C * sizeof(Fr), hipMemcpyDeviceToHost, st), "download combinations");
     hipc(hipStreamSynchronize(st), "hg_pcs_open_bn254: sync");
@@ -228,137 +414,61 @@ void pcs_columns_device(const pcs::Commitment& cm, const std::vector<size_t>& js
     hipc(hipGetLastError(), "hg_pcs_open_bn254: launch");
 }
 
-// ---- the verifier of an opening (pcs_verify_device). A word of the opening only ever becomes a number; every index below comes
-// from the shape, from the host's masked j_q or from table offsets the entry point validated. Each result cell holds the lowest
-// offending key (atomicMin), so the reason is the host's also where several checks fail at once.
-constexpr u64 BNPCSV_NONE = ~(u64)0;   // a cell no thread lowered: nothing failed
-__device__ __forceinline__ void bnpcsv_min(u64* cell, u64 v) { atomicMin(reinterpret_cast<unsigned long long*>(cell), (unsigned long long)v); }
-
-// 32 big-endian bytes of the opening -> 4 native limbs (limb w = the byte-swapped word 3 - w). Element i < u_el is element
-// i & (C - 1) of u vector i >> c: kept in u and scattered into row i >> c of the matrix the NTT encodes (zeroed beforehand). The
-// others are the Q * R column elements, query q at element u_el + q * q_el. cells[0] = the lowest byte offset of an element that
-// is not below r (all four limbs compared). Elements stay plain words: no Montgomery conversion (ntt_batch_dev keeps the form).
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsv_canon(const u64* __restrict__ proof, size_t u_el, size_t Q, size_t R, size_t q_el, int c, Fr* __restrict__ u,
-                                                            Fr* __restrict__ cols, Fr* __restrict__ enc, u64* __restrict__ cells) {
-    const size_t total = u_el + Q * R, Cm = ((size_t)1 << c) - 1;
-    u64 bad = BNPCSV_NONE;
-    for (size_t i = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * BNPCS_TPB) {
-        size_t at = i;
-        if (i >= u_el) { const size_t k = i - u_el, q = k / R; at = u_el + q * q_el + (k - q * R); }
-        const u64* p = proof + 4 * at;
-        const Fr v = fr_make(__builtin_bswap64(p[3]), __builtin_bswap64(p[2]), __builtin_bswap64(p[1]), __builtin_bswap64(p[0]));
-        if (fr_geq_p(v) && 32 * at < bad) bad = 32 * at;
-        if (i < u_el) {
-            lz_gstore(u + i, v);
-            lz_gstore(enc + ((i >> c) << (c + 2)) + (i & Cm), v);
-        } else {
-            lz_gstore(cols + (i - u_el), v);
-        }
+// ---- what the two verifiers share on the host: a member's block of the staged copy and the reading of its three result cells
+// the entries of a member's weight tables: R powers of rho, then eq(z_i[c..]) over the rows of every claim's table
+static size_t bnpcs_weights_of(const pcs::Shape& sh, const std::vector<PcsClaim>& claims) {
+    size_t nw = sh.R;
+    for (const PcsClaim& cl : claims) nw += (size_t)1 << (sh.nvars[cl.table] - sh.c);
+    return nw;
+}
+// The block of a member of n claims and nw weights from byte `at` (a multiple of 32) of a staged copy on: root, job descriptors,
+// values, the low coordinates of the points, weight tables. Into its descriptor -> the byte behind the block
+static size_t bnpcs_block_layout(BnVbMember& d, const pcs::Shape& sh, size_t n, size_t nw, size_t at) {
+    d.root_at = at;
+    d.jobs_at = d.root_at + 32;
+    d.y_at = d.jobs_at + (((n + 1) * sizeof(BnPcsDesc) + 31) & ~(size_t)31);
+    d.z_at = d.y_at + n * sizeof(Fr);
+    d.w_at = d.z_at + n * (size_t)sh.c * sizeof(Fr);
+    return d.w_at + nw * sizeof(Fr);
+}
+// fills the block (the low coordinates and the weights in Montgomery form) -> the member's transcript, rho squeezed
+static FsTranscript bnpcs_block_fill(char* h_stage, const BnVbMember& d, const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q) {
+    const size_t R = sh.R;
+    FsTranscript tr = pcs_start_transcript(sh, root, claims, Q);
+    const std::vector<Fr> rho = pcs_rho_powers(pcs_squeeze(tr), R);
+    memcpy(h_stage + d.root_at, root, 32);
+    BnPcsDesc* hd = reinterpret_cast<BnPcsDesc*>(h_stage + d.jobs_at);
+    Fr* hy = reinterpret_cast<Fr*>(h_stage + d.y_at);
+    Fr* hz = reinterpret_cast<Fr*>(h_stage + d.z_at);
+    Fr* hw = reinterpret_cast<Fr*>(h_stage + d.w_at);
+    hd[0].row0 = 0; hd[0].nrows = R; hd[0].woff = 0;
+    memcpy(hw, rho.data(), R * sizeof(Fr));
+    size_t off = R;
+    for (size_t i = 0; i < claims.size(); i++) {
+        const PcsClaim& cl = claims[i];
+        const std::vector<Fr> w = pcs_eq_table(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
+        hd[i + 1].row0 = sh.off[cl.table]; hd[i + 1].nrows = w.size(); hd[i + 1].woff = off;
+        memcpy(hw + off, w.data(), w.size() * sizeof(Fr));
+        off += w.size();
+        hy[i] = cl.value;
+        for (int b = 0; b < sh.c; b++) hz[i * (size_t)sh.c + b] = fr_to_mont(cl.point[b]);
     }
-    if (bad != BNPCSV_NONE) bnpcsv_min(cells, bad);
+    return tr;
+}
+// the host's order: a non-canonical element, the lowest claim whose evaluation fails, the lowest failing query; "" = accepted
+static std::string bnpcs_cells_reason(const u64* cells, size_t n) {
+    if (cells[0] != BNPCSV_NONE) return pcs::reason_noncanonical((size_t)cells[0]);
+    if (cells[1] != BNPCSV_NONE) return pcs::reason_evaluation((size_t)cells[1]);
+    if (cells[2] == BNPCSV_NONE) return "";
+    const size_t q = (size_t)(cells[2] / (n + 2)), kind = (size_t)(cells[2] % (n + 2));
+    return kind == 0 ? pcs::reason_merkle(q) : kind == 1 ? pcs::reason_proximity(q) : pcs::reason_claim(kind - 2, q);
 }
 
-// <u_i, eq(z_i[..c])> == y_i, one workgroup per claim i (blockIdx.x). zlo holds the c low coordinates of every point in Montgomery
-// form, so a factor of eq(z, x) = prod_b (x_b ? z_b : 1 - z_b) is in Montgomery form and factor x plain element is the plain
-// product. The factors are formed per entry: a thread keeps the one of the low eight bits of x, which its entries share.
-// cells[1] = the lowest failing claim.
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsv_eval(const Fr* __restrict__ u, int c, const Fr* __restrict__ zlo, const Fr* __restrict__ y, u64* __restrict__ cells) {
-    __shared__ Fr part[BNPCS_TPB];
-    const size_t C = (size_t)1 << c, i = blockIdx.x;
-    const Fr* z = zlo + i * (size_t)c;
-    const Fr* ui = u + (i + 1) * C;
-    const int lo = c < 8 ? c : 8;
-    Fr f = fr_one_mont();
-    for (int b = 0; b < lo; b++) { const Fr zb = lz_gload(z + b); f = fr_mul(f, (threadIdx.x >> b) & 1 ? zb : fr_sub(fr_one_mont(), zb)); }
-    Fr s = fr_zero();
-    for (size_t x = threadIdx.x; x < C; x += BNPCS_TPB) {
-        Fr g = f;
-        for (int b = 8; b < c; b++) { const Fr zb = lz_gload(z + b); g = fr_mul(g, (x >> b) & 1 ? zb : fr_sub(fr_one_mont(), zb)); }
-        s = fr_add(s, fr_mul(lz_gload(ui + x), g));
-    }
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int h = BNPCS_TPB / 2; h >= 1; h >>= 1) {
-        if (threadIdx.x < h) part[threadIdx.x] = fr_add(part[threadIdx.x], part[threadIdx.x + h]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && !fr_eq(part[0], lz_gload(y + i))) bnpcsv_min(cells + 1, (u64)i);
-}
-
-// One thread per query: the leaf hash of its R column elements (contiguous: 4 words between them) -> leaves[q]
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsv_leaf(const Fr* __restrict__ cols, size_t Q, size_t R, u64* __restrict__ leaves) {
-    const size_t q = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
-    if (q >= Q) return;
-    u64 a[25];
-    bnpcs_leaf_absorb(reinterpret_cast<const u64*>(cols + q * R), 4, R, a);
-    u64* out = leaves + 4 * q;
-    out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
-}
-
-// Column inner products. A thread owns query q (the grid's x: Q reaches 65536), blockIdx.y is the job, so the weight is uniform
-// over the wavefront: s[job][q] = sum_{r < nrows} w[woff + r] * col_q[row0 + r], canonical. Job 0 is the proximity combination
-// (rho^r over the whole column), job 1 + i claim i's (eq(z_i[c..]) over the rows of its table). The accumulators and their bound
-// are k_bnpcs_combine's: a column element that passed k_bnpcsv_canon is below r, the weight is a residue, BNPCS_CHUNK products a
-// reduction. (An element that did not pass only makes this sum meaningless, and cells[0] decides ahead of whatever reads it.)
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsv_dots(const Fr* __restrict__ cols, size_t Q, size_t R, const BnPcsDesc* __restrict__ jobs, const Fr* __restrict__ w,
-                                                           Fr* __restrict__ s) {
-    const size_t q = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
-    if (q >= Q) return;
-    const BnPcsDesc job = jobs[blockIdx.y];
-    const Fr* src = cols + q * R + job.row0;
-    const u32* wq = reinterpret_cast<const u32*>(w + job.woff);
-    Fr acc = fr_zero();
-    for (u64 r0 = 0; r0 < job.nrows; r0 += BNPCS_CHUNK) {
-        const u64 r1 = r0 + BNPCS_CHUNK < job.nrows ? r0 + BNPCS_CHUNK : job.nrows;
-        WCol A = wcol_zero();
-        for (u64 r = r0; r < r1; r++) {
-            const Fr x = lz_gload(src + r);
-            u32 bl[8];
-#pragma unroll
-            for (int k = 0; k < 8; k++) bl[k] = __builtin_amdgcn_readfirstlane(wq[8 * r + k]);
-            bnpcs_mac_uniform(A, x, bl);
-        }
-        acc = lz_add(acc, lz_reduce(A));
-    }
-    lz_gstore(s + (size_t)blockIdx.y * Q + q, lz_canon(acc));
-}
-
-// One thread per query, once the host has the column indices: the path from the leaf hash over the c+2 siblings (32 raw bytes
-// each behind the query's column elements; bit l of j_q says on which side level l's sibling lies) against the root, then s[0][q]
-// against Enc(u_0)[j_q], then s[1 + i][q] against Enc(u_i)[j_q]. cells[2] = the lowest q * (n + 2) + kind that failed: kind 0 the
-// path, 1 proximity, 2 + i claim i.
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsv_query(const u64* __restrict__ proof, size_t u_el, size_t q_el, size_t Q, size_t R, int depth,
-                                                            const u64* __restrict__ leaves, const Fr* __restrict__ s, const Fr* __restrict__ enc, size_t n,
-                                                            const u64* __restrict__ js, const u64* __restrict__ root, u64* __restrict__ cells) {
-    const size_t q = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
-    if (q >= Q) return;
-    const size_t N = (size_t)1 << depth, j = js[q];
-    const u64* sib = proof + 4 * (u_el + q * q_el + R);
-    u64 h0 = leaves[4 * q], h1 = leaves[4 * q + 1], h2 = leaves[4 * q + 2], h3 = leaves[4 * q + 3];
-    for (int l = 0; l < depth; l++) {
-        const bool right = (j >> l) & 1;   // this node is the right child
-        const u64 t0 = sib[4 * l], t1 = sib[4 * l + 1], t2 = sib[4 * l + 2], t3 = sib[4 * l + 3];
-        u64 a[25];
-        a[0] = 1;
-        a[1] = right ? t0 : h0; a[2] = right ? t1 : h1; a[3] = right ? t2 : h2; a[4] = right ? t3 : h3;
-        a[5] = right ? h0 : t0; a[6] = right ? h1 : t1; a[7] = right ? h2 : t2; a[8] = right ? h3 : t3;
-        a[9] = 0x01;
-#pragma unroll
-        for (int k = 10; k < 25; k++) a[k] = 0;
-        a[pcs::RATE_WORDS - 1] = 0x8000000000000000ull;
-        pcs::keccak_f(a);
-        h0 = a[0]; h1 = a[1]; h2 = a[2]; h3 = a[3];
-    }
-    const size_t key = q * (n + 2);
-    if (h0 != root[0] || h1 != root[1] || h2 != root[2] || h3 != root[3]) { bnpcsv_min(cells + 2, key); return; }
-    for (size_t i = 0; i <= n; i++)
-        if (!fr_eq(lz_gload(s + i * Q + q), lz_gload(enc + i * N + j))) { bnpcsv_min(cells + 2, key + 1 + i); return; }
-}
-
-// hg_pcs_verify_device_bn254. Everything but the last kernel needs no column index, so it is enqueued first and runs while the
-// host hashes the u_i; the indices follow on the same stream, then the three result cells come back: one synchronisation. The
-// leaf sponge (serial: 4R + 1 words a thread, Q threads) is the longest of the early kernels and goes last among them, so the two
-// verdicts that need no index and the inner products never wait behind it; the host's own hash of the u_i covers it.
+// hg_pcs_verify_device_bn254: a group of one member, whose opening in the arena is the set. Everything but the last kernel needs no
+// column index, so it is enqueued first and runs while the host hashes the u_i; the indices follow on the same stream, then the
+// three result cells come back: one synchronisation. The leaf sponge (serial: 4R + 1 words a thread, Q threads) is the longest of the
+// early kernels and goes last among them, so the two verdicts that need no index and the inner products never wait behind it; the
+// host's own hash of the u_i covers it.
 std::string pcs_verify_device(hg_ctx* ctx, const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof, size_t len) {
     const size_t C = sh.C(), N = sh.N(), R = sh.R, n = claims.size();
     const int depth = sh.depth();
@@ -368,30 +478,14 @@ std::string pcs_verify_device(hg_ctx* ctx, const pcs::Shape& sh, const uint8_t r
     hipc(hipSetDevice(ctx->device), "hipSetDevice");
     ctx->arena_reset();
     hipStream_t st = ctx->stream;
-    // root, descriptors, values, the low coordinates of the points (Montgomery) and the weight tables (Montgomery) in one staged copy
-    FsTranscript tr = pcs_start_transcript(sh, root, claims, Q);
-    const std::vector<Fr> rho = pcs_rho_powers(pcs_squeeze(tr), R);
-    size_t nw = R;
-    for (const PcsClaim& cl : claims) nw += (size_t)1 << (sh.nvars[cl.table] - sh.c);
-    const size_t desc_at = 32, y_at = desc_at + ((njobs * sizeof(BnPcsDesc) + 31) & ~(size_t)31), z_at = y_at + n * sizeof(Fr), w_at = z_at + n * (size_t)sh.c * sizeof(Fr);
-    std::vector<char> stage(w_at + nw * sizeof(Fr));
-    memcpy(stage.data(), root, 32);
-    BnPcsDesc* hd = reinterpret_cast<BnPcsDesc*>(stage.data() + desc_at);
-    Fr* hy = reinterpret_cast<Fr*>(stage.data() + y_at);
-    Fr* hz = reinterpret_cast<Fr*>(stage.data() + z_at);
-    Fr* hw = reinterpret_cast<Fr*>(stage.data() + w_at);
-    hd[0].row0 = 0; hd[0].nrows = R; hd[0].woff = 0;
-    memcpy(hw, rho.data(), R * sizeof(Fr));
-    size_t off = R;
-    for (size_t i = 0; i < n; i++) {
-        const PcsClaim& cl = claims[i];
-        const std::vector<Fr> w = pcs_eq_table(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
-        hd[i + 1].row0 = sh.off[cl.table]; hd[i + 1].nrows = w.size(); hd[i + 1].woff = off;
-        memcpy(hw + off, w.data(), w.size() * sizeof(Fr));
-        off += w.size();
-        hy[i] = cl.value;
-        for (int b = 0; b < sh.c; b++) hz[i * (size_t)sh.c + b] = fr_to_mont(cl.point[b]);
-    }
+    // the member's descriptor and its block in one staged copy
+    const size_t nw = bnpcs_weights_of(sh, claims);
+    BnVbMember desc{};   // (every offset into the set and the arena buffers is 0)
+    desc.n = n;
+    std::vector<char> stage(bnpcs_block_layout(desc, sh, n, nw, sizeof(BnVbMember)));
+    static_assert(sizeof(BnVbMember) % 32 == 0, "the block starts at a multiple of 32");
+    memcpy(stage.data(), &desc, sizeof(BnVbMember));
+    FsTranscript tr = bnpcs_block_fill(stage.data(), desc, sh, root, claims, Q);
     u64 *d_proof, *d_leaves, *d_js, *d_cells;
     Fr *d_u, *d_cols, *d_enc, *d_tmp, *d_W, *d_s;
     char* d_stage;
@@ -410,24 +504,22 @@ std::string pcs_verify_device(hg_ctx* ctx, const pcs::Shape& sh, const uint8_t r
     } catch (const std::exception& e) {
         throw Error(std::string("the context's arena cannot hold the opening (") + e.what() + ")");
     }
-    struct Drain {   // an error between the first enqueue and the synchronisation must not leave copies of dead host buffers behind
-        hipStream_t st; bool armed = true;
-        ~Drain() { if (armed) (void)hipStreamSynchronize(st); }
-    } drain{st};
+    pcs::DrainOne drain{st};   // (drains on an error; after the synchronisation below its own is one more, on an idle stream)
     const int cls = ctx->prof_class("pcs_bn254_verify", false);
     ctx->prof_stream = st;
-    const BnPcsDesc* d_jobs = reinterpret_cast<const BnPcsDesc*>(d_stage + desc_at);
-    const u64* d_root = reinterpret_cast<const u64*>(d_stage);
+    const BnVbMember* d_mem = reinterpret_cast<const BnVbMember*>(d_stage);
+    const BnVbGroup vg{1, (u64)Q, (u64)R, (u64)q_el, sh.c, depth};
+    const size_t bq = bnpcs_blocks(Q);   // k_bnpcsvb_dots: the workgroups of a job
     hipc(hipMemcpyAsync(d_proof, proof, len, hipMemcpyHostToDevice, st), "upload opening");
     hipc(hipMemcpyAsync(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, st), "upload claims");
     hipc(hipMemsetAsync(d_cells, 0xff, 32, st), "memset");
     hipc(hipMemsetAsync(d_enc, 0, njobs * N * sizeof(Fr), st), "memset");
     ctx->prof_begin(cls, (double)(u_el + Q * R) * 64 + (double)u_el * 32);
-    k_bnpcsv_canon<<<(unsigned)std::min<size_t>(bnpcs_blocks(u_el + Q * R), 4096), BNPCS_TPB, 0, st>>>(d_proof, u_el, Q, R, q_el, sh.c, d_u, d_cols, d_enc, d_cells);
+    k_bnpcsvb_canon<<<(unsigned)std::min<size_t>(bnpcs_blocks(u_el + Q * R), 4096), BNPCS_TPB, 0, st>>>(d_proof, d_mem, vg, d_u, d_cols, d_enc, d_cells);
     ctx->prof_end();
     if (n) {
         ctx->prof_begin(cls, (double)n * C * 32);
-        k_bnpcsv_eval<<<(unsigned)n, BNPCS_TPB, 0, st>>>(d_u, sh.c, reinterpret_cast<const Fr*>(d_stage + z_at), reinterpret_cast<const Fr*>(d_stage + y_at), d_cells);
+        k_bnpcsvb_eval<<<(unsigned)n, BNPCS_TPB, 0, st>>>(d_mem, 1, sh.c, d_u, d_stage, d_cells);
         ctx->prof_end();
     }
     ctx->prof_begin(cls, (double)njobs * N * 32 * 4);
@@ -436,10 +528,10 @@ std::string pcs_verify_device(hg_ctx* ctx, const pcs::Shape& sh, const uint8_t r
     ctx->prof_end();
     if (Q) {
         ctx->prof_begin(cls, (double)Q * nw * 64);
-        k_bnpcsv_dots<<<dim3(bnpcs_blocks(Q), (unsigned)njobs), BNPCS_TPB, 0, st>>>(d_cols, Q, R, d_jobs, reinterpret_cast<const Fr*>(d_stage + w_at), d_s);
+        k_bnpcsvb_dots<<<(unsigned)(bq * njobs), BNPCS_TPB, 0, st>>>(d_mem, vg, (unsigned)bq, d_cols, d_stage, d_s);
         ctx->prof_end();
         ctx->prof_begin(cls, (double)Q * R * 32);
-        k_bnpcsv_leaf<<<bnpcs_blocks(Q), BNPCS_TPB, 0, st>>>(d_cols, Q, R, d_leaves);
+        k_bnpcsvb_leaf<<<bnpcs_blocks(Q), BNPCS_TPB, 0, st>>>(d_mem, vg, d_cols, d_leaves);
         ctx->prof_end();
     }
     // the host's share, beside the kernels: the u_i into the transcript, the column indices out of it
@@ -453,173 +545,15 @@ std::string pcs_verify_device(hg_ctx* ctx, const pcs::Shape& sh, const uint8_t r
     if (Q) {
         hipc(hipMemcpyAsync(d_js, hj.data(), Q * 8, hipMemcpyHostToDevice, st), "upload column indices");
         ctx->prof_begin(cls, (double)Q * (32.0 * depth + 64.0 * njobs));
-        k_bnpcsv_query<<<bnpcs_blocks(Q), BNPCS_TPB, 0, st>>>(d_proof, u_el, q_el, Q, R, depth, d_leaves, d_s, d_enc, n, d_js, d_root, d_cells);
+        k_bnpcsvb_query<<<bnpcs_blocks(Q), BNPCS_TPB, 0, st>>>(d_proof, d_mem, vg, d_leaves, d_s, d_enc, d_js, d_stage, d_cells);
         ctx->prof_end();
     }
     u64 cells[4];
     hipc(hipMemcpyAsync(cells, d_cells, 32, hipMemcpyDeviceToHost, st), "download verdict");
-    const hipError_t synced = hipStreamSynchronize(st);
-    drain.armed = false;
-    hipc(synced, "hg_pcs_verify_device_bn254: sync");
+    hipc(hipStreamSynchronize(st), "hg_pcs_verify_device_bn254: sync");
     hipc(hipGetLastError(), "hg_pcs_verify_device_bn254: launch");
     ctx->prof_collect();
-    // the host's order: a non-canonical element, the lowest claim whose evaluation fails, the lowest failing query
-    if (cells[0] != BNPCSV_NONE) return pcs::reason_noncanonical((size_t)cells[0]);
-    if (cells[1] != BNPCSV_NONE) return pcs::reason_evaluation((size_t)cells[1]);
-    if (cells[2] != BNPCSV_NONE) {
-        const size_t q = (size_t)(cells[2] / (n + 2)), kind = (size_t)(cells[2] % (n + 2));
-        return kind == 0 ? pcs::reason_merkle(q) : kind == 1 ? pcs::reason_proximity(q) : pcs::reason_claim(kind - 2, q);
-    }
-    return "";
-}
-
-// ---- the verifier of a run of openings (pcs_verify_device_batch): the five kernels above with a member in front of every index.
-// The members of a group share the shape and Q; what differs by member (its claim count, where its opening, u, columns, encoded
-// rows, jobs and weights lie) is read from its descriptor, never derived from a flat id, and no member's range is assumed to start
-// at a workgroup. Every block of the staged copy starts at a multiple of 32 bytes (lz_gload reads 16-byte halves).
-struct BnVbMember {
-    u64 proof, u, cols, enc_row;               // word offset of its opening in the set; element offsets of its u and columns; its first row of enc
-    u64 n, claim0, job0;                       // its claims; the claims and the jobs (claims + 1 each) of the members before it
-    u64 root_at, jobs_at, y_at, z_at, w_at;    // byte offsets in the group's staged copy: root, job descriptors, values, low coordinates, weights
-};
-struct BnVbGroup { u64 G, Q, R, q_el; int c, depth; };
-
-// blockIdx.y = the member, its elements grid-strided over blockIdx.x: k_bnpcsv_canon on its own opening, into its own u, columns
-// and enc rows; cells[3m] = the lowest byte offset, within its opening, of an element that is not below r
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_canon(const u64* __restrict__ set, const BnVbMember* __restrict__ mem, BnVbGroup g, Fr* __restrict__ u,
-                                                             Fr* __restrict__ cols, Fr* __restrict__ enc, u64* __restrict__ cells) {
-    const BnVbMember M = mem[blockIdx.y];
-    const int c = g.c;
-    const size_t Q = g.Q, R = g.R, u_el = (M.n + 1) << c, total = u_el + Q * R, Cm = ((size_t)1 << c) - 1;
-    const u64* proof = set + M.proof;
-    Fr* mu = u + M.u;
-    Fr* mcols = cols + M.cols;
-    Fr* menc = enc + (M.enc_row << (c + 2));
-    u64 bad = BNPCSV_NONE;
-    for (size_t i = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * BNPCS_TPB) {
-        size_t at = i;
-        if (i >= u_el) { const size_t k = i - u_el, q = k / R; at = u_el + q * g.q_el + (k - q * R); }
-        const u64* p = proof + 4 * at;
-        const Fr v = fr_make(__builtin_bswap64(p[3]), __builtin_bswap64(p[2]), __builtin_bswap64(p[1]), __builtin_bswap64(p[0]));
-        if (fr_geq_p(v) && 32 * at < bad) bad = 32 * at;
-        if (i < u_el) {
-            lz_gstore(mu + i, v);
-            lz_gstore(menc + ((i >> c) << (c + 2)) + (i & Cm), v);
-        } else {
-            lz_gstore(mcols + (i - u_el), v);
-        }
-    }
-    if (bad != BNPCSV_NONE) bnpcsv_min(cells + 3 * blockIdx.y, bad);
-}
-
-// One workgroup per (member, claim): block b belongs to the last member whose claim0 is <= b (a member without claims owns no
-// block). cells[3m + 1] = the member's lowest failing claim.
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_eval(const BnVbMember* __restrict__ mem, unsigned G, int c, const Fr* __restrict__ u, const char* __restrict__ stage,
-                                                            u64* __restrict__ cells) {
-    __shared__ Fr part[BNPCS_TPB];
-    unsigned lo = 0, hi = G;
-    while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].claim0 <= blockIdx.x) lo = mid; else hi = mid; }
-    const BnVbMember M = mem[lo];
-    const size_t C = (size_t)1 << c, i = blockIdx.x - M.claim0;
-    if (i >= M.n) return;   // (uniform over the workgroup; the grid has exactly the claims of the group)
-    const Fr* z = reinterpret_cast<const Fr*>(stage + M.z_at) + i * (size_t)c;
-    const Fr* ui = u + M.u + (i + 1) * C;
-    const int lob = c < 8 ? c : 8;
-    Fr f = fr_one_mont();
-    for (int b = 0; b < lob; b++) { const Fr zb = lz_gload(z + b); f = fr_mul(f, (threadIdx.x >> b) & 1 ? zb : fr_sub(fr_one_mont(), zb)); }
-    Fr s = fr_zero();
-    for (size_t x = threadIdx.x; x < C; x += BNPCS_TPB) {
-        Fr gq = f;
-        for (int b = 8; b < c; b++) { const Fr zb = lz_gload(z + b); gq = fr_mul(gq, (x >> b) & 1 ? zb : fr_sub(fr_one_mont(), zb)); }
-        s = fr_add(s, fr_mul(lz_gload(ui + x), gq));
-    }
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int h = BNPCS_TPB / 2; h >= 1; h >>= 1) {
-        if (threadIdx.x < h) part[threadIdx.x] = fr_add(part[threadIdx.x], part[threadIdx.x + h]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && !fr_eq(part[0], lz_gload(reinterpret_cast<const Fr*>(stage + M.y_at) + i))) bnpcsv_min(cells + 3 * lo + 1, (u64)i);
-}
-
-// One thread per (member m, query q), id = m Q + q: the leaf hash of its R column elements -> leaves[id]
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_leaf(const BnVbMember* __restrict__ mem, BnVbGroup g, const Fr* __restrict__ cols, u64* __restrict__ leaves) {
-    const size_t id = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
-    if (id >= g.G * g.Q) return;
-    const size_t m = id / g.Q, q = id - m * g.Q;
-    u64 a[25];
-    bnpcs_leaf_absorb(reinterpret_cast<const u64*>(cols + mem[m].cols + q * g.R), 4, g.R, a);
-    u64* out = leaves + 4 * id;
-    out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
-}
-
-// Column inner products of every member: k_bnpcsv_dots, whose weight limbs go through readfirstlane and so must be the same for
-// every lane of a wavefront. A flat id Q job + q would let a wavefront straddle two jobs whenever Q is no multiple of 64, so the
-// job is fixed per workgroup instead: a one-dimensional grid of bq * jobs_total workgroups, bq = the workgroups Q threads take
-// (no y extent: the jobs of a group can pass 65535); workgroup b works on global job b / bq, queries (b % bq) TPB .. . The member
-// is the last one whose job0 is <= the job. s[global job][q], canonical.
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_dots(const BnVbMember* __restrict__ mem, BnVbGroup g, unsigned bq, const Fr* __restrict__ cols,
-                                                            const char* __restrict__ stage, Fr* __restrict__ s) {
-    const size_t gjob = blockIdx.x / bq;
-    const size_t q = (size_t)(blockIdx.x % bq) * BNPCS_TPB + threadIdx.x;
-    if (q >= g.Q) return;
-    unsigned lo = 0, hi = (unsigned)g.G;
-    while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].job0 <= gjob) lo = mid; else hi = mid; }
-    const BnVbMember M = mem[lo];
-    const BnPcsDesc job = reinterpret_cast<const BnPcsDesc*>(stage + M.jobs_at)[gjob - M.job0];
-    const Fr* src = cols + M.cols + q * g.R + job.row0;
-    const u32* wq = reinterpret_cast<const u32*>(reinterpret_cast<const Fr*>(stage + M.w_at) + job.woff);
-    Fr acc = fr_zero();
-    for (u64 r0 = 0; r0 < job.nrows; r0 += BNPCS_CHUNK) {
-        const u64 r1 = r0 + BNPCS_CHUNK < job.nrows ? r0 + BNPCS_CHUNK : job.nrows;
-        WCol A = wcol_zero();
-        for (u64 r = r0; r < r1; r++) {
-            const Fr x = lz_gload(src + r);
-            u32 bl[8];
-#pragma unroll
-            for (int k = 0; k < 8; k++) bl[k] = __builtin_amdgcn_readfirstlane(wq[8 * r + k]);
-            bnpcs_mac_uniform(A, x, bl);
-        }
-        acc = lz_add(acc, lz_reduce(A));
-    }
-    lz_gstore(s + gjob * g.Q + q, lz_canon(acc));
-}
-
-// One thread per (member m, query q), id = m Q + q, once the host has every member's column indices (js[id]): k_bnpcsv_query on
-// the member's own opening, root, s entries and enc rows. cells[3m + 2] = the member's lowest q (n_m + 2) + kind that failed.
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_query(const u64* __restrict__ set, const BnVbMember* __restrict__ mem, BnVbGroup g, const u64* __restrict__ leaves,
-                                                             const Fr* __restrict__ s, const Fr* __restrict__ enc, const u64* __restrict__ js,
-                                                             const char* __restrict__ stage, u64* __restrict__ cells) {
-    const size_t id = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
-    if (id >= g.G * g.Q) return;
-    const size_t m = id / g.Q, q = id - m * g.Q;
-    const BnVbMember M = mem[m];
-    const int depth = g.depth;
-    const size_t N = (size_t)1 << depth, j = js[id], n = M.n, u_el = (n + 1) << g.c;
-    const u64* sib = set + M.proof + 4 * (u_el + q * g.q_el + g.R);
-    const u64* root = reinterpret_cast<const u64*>(stage + M.root_at);
-    u64 h0 = leaves[4 * id], h1 = leaves[4 * id + 1], h2 = leaves[4 * id + 2], h3 = leaves[4 * id + 3];
-    for (int l = 0; l < depth; l++) {
-        const bool right = (j >> l) & 1;   // this node is the right child
-        const u64 t0 = sib[4 * l], t1 = sib[4 * l + 1], t2 = sib[4 * l + 2], t3 = sib[4 * l + 3];
-        u64 a[25];
-        a[0] = 1;
-        a[1] = right ? t0 : h0; a[2] = right ? t1 : h1; a[3] = right ? t2 : h2; a[4] = right ? t3 : h3;
-        a[5] = right ? h0 : t0; a[6] = right ? h1 : t1; a[7] = right ? h2 : t2; a[8] = right ? h3 : t3;
-        a[9] = 0x01;
-#pragma unroll
-        for (int k = 10; k < 25; k++) a[k] = 0;
-        a[pcs::RATE_WORDS - 1] = 0x8000000000000000ull;
-        pcs::keccak_f(a);
-        h0 = a[0]; h1 = a[1]; h2 = a[2]; h3 = a[3];
-    }
-    u64* cell = cells + 3 * m + 2;
-    const size_t key = q * (n + 2);
-    if (h0 != root[0] || h1 != root[1] || h2 != root[2] || h3 != root[3]) { bnpcsv_min(cell, key); return; }
-    const Fr* sq = s + M.job0 * g.Q + q;
-    const Fr* menc = enc + (M.enc_row << depth) + j;
-    for (size_t i = 0; i <= n; i++)
-        if (!fr_eq(lz_gload(sq + i * g.Q), lz_gload(menc + i * N))) { bnpcsv_min(cell, key + 1 + i); return; }
+    return bnpcs_cells_reason(cells, n);
 }
 
 // hg_pcs_verify_device_batch_bn254. The items whose length is right are cut into groups (the option verify_batch_group, VB_PCS_BUDGET
@@ -669,10 +603,7 @@ std::vector<std::string> pcs_verify_device_batch(const char* who_c, hg_ctx* ctx,
     VerifyBatchBufs* B = batch_bufs(ctx);
     hipStream_t st = ctx->stream;
     std::vector<u64> hj, cells;   // (declared ahead of the guard: copies of them may be queued when it drains)
-    struct Drain {   // every way out, an error included: no copy of a dead host buffer, no kernel on the arena or a set left behind
-        hipStream_t a, b;
-        ~Drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); }
-    } drain{st, B->up};
+    pcs::DrainOne drain_up{B->up}, drain{st};   // (the upload stream as well: no kernel on a set left behind)
     hipc(hipStreamSynchronize(st), (who + ": synchronise").c_str());   // (the arena is reset below)
     [[maybe_unused]] const int nthr = std::max(1, hg_omp_threads());   // (the device pass of hipcc ignores the pragmas)
     const int cls = ctx->prof_class("pcs_bn254_verify_batch", false);
@@ -711,17 +642,11 @@ std::vector<std::string> pcs_verify_device_batch(const char* who_c, hg_ctx* ctx,
             const VerifyItem& it = items[good[groups[g].first + m]];
             x.idx = good[groups[g].first + m];
             x.n = it.claims->size();
-            x.nw = R;
-            for (const PcsClaim& cl : *it.claims) x.nw += (size_t)1 << (sh.nvars[cl.table] - sh.c);
+            x.nw = bnpcs_weights_of(sh, *it.claims);
             BnVbMember& d = desc[m];
             d.proof = poff[m]; d.u = u_at; d.cols = m * Q * R; d.enc_row = row_at;
             d.n = x.n; d.claim0 = claim_at; d.job0 = claim_at + m;
-            d.root_at = at;
-            d.jobs_at = d.root_at + 32;
-            d.y_at = d.jobs_at + (((x.n + 1) * sizeof(BnPcsDesc) + 31) & ~(size_t)31);
-            d.z_at = d.y_at + x.n * sizeof(Fr);
-            d.w_at = d.z_at + x.n * (size_t)sh.c * sizeof(Fr);
-            at = d.w_at + x.nw * sizeof(Fr);
+            at = bnpcs_block_layout(d, sh, x.n, x.nw, at);
             u_at += C * (x.n + 1);
             row_at += rows_of(x.n);
             claim_at += x.n;
@@ -734,26 +659,7 @@ std::vector<std::string> pcs_verify_device_batch(const char* who_c, hg_ctx* ctx,
             Member& x = mem[mq];
             try {
                 const VerifyItem& it = items[x.idx];
-                const BnVbMember& d = desc[mq];
-                x.tr = pcs_start_transcript(sh, it.root, *it.claims, Q);
-                const std::vector<Fr> rho = pcs_rho_powers(pcs_squeeze(x.tr), R);
-                memcpy(h_stage + d.root_at, it.root, 32);
-                BnPcsDesc* hd = reinterpret_cast<BnPcsDesc*>(h_stage + d.jobs_at);
-                Fr* hy = reinterpret_cast<Fr*>(h_stage + d.y_at);
-                Fr* hz = reinterpret_cast<Fr*>(h_stage + d.z_at);
-                Fr* hw = reinterpret_cast<Fr*>(h_stage + d.w_at);
-                hd[0].row0 = 0; hd[0].nrows = R; hd[0].woff = 0;
-                memcpy(hw, rho.data(), R * sizeof(Fr));
-                size_t off = R;
-                for (size_t i = 0; i < x.n; i++) {
-                    const PcsClaim& cl = (*it.claims)[i];
-                    const std::vector<Fr> w = pcs_eq_table(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
-                    hd[i + 1].row0 = sh.off[cl.table]; hd[i + 1].nrows = w.size(); hd[i + 1].woff = off;
-                    memcpy(hw + off, w.data(), w.size() * sizeof(Fr));
-                    off += w.size();
-                    hy[i] = cl.value;
-                    for (int b = 0; b < sh.c; b++) hz[i * (size_t)sh.c + b] = fr_to_mont(cl.point[b]);
-                }
+                x.tr = bnpcs_block_fill(h_stage, desc[mq], sh, it.root, *it.claims, Q);
             } catch (const std::exception& e) { x.error = e.what(); }
         }
         for (const Member& x : mem)
@@ -841,48 +747,9 @@ std::vector<std::string> pcs_verify_device_batch(const char* who_c, hg_ctx* ctx,
         t_stage = t5 - t4;
         hipc(hipGetLastError(), (who + ": launch").c_str());
         ctx->prof_collect();
-        // per member, the host's order: a non-canonical element, the lowest claim whose evaluation fails, the lowest failing query
-        for (size_t m = 0; m < G; m++) {
-            const u64* cm = cells.data() + 3 * m;
-            const size_t n = mem[m].n;
-            std::string& out = why[mem[m].idx];
-            if (cm[0] != BNPCSV_NONE) out = pcs::reason_noncanonical((size_t)cm[0]);
-            else if (cm[1] != BNPCSV_NONE) out = pcs::reason_evaluation((size_t)cm[1]);
-            else if (cm[2] != BNPCSV_NONE) {
-                const size_t q = (size_t)(cm[2] / (n + 2)), kind = (size_t)(cm[2] % (n + 2));
-                out = kind == 0 ? pcs::reason_merkle(q) : kind == 1 ? pcs::reason_proximity(q) : pcs::reason_claim(kind - 2, q);
-            }
-        }
+        for (size_t m = 0; m < G; m++) why[mem[m].idx] = bnpcs_cells_reason(cells.data() + 3 * m, mem[m].n);
     }
     return why;
-}
-
-// ---- a run of commitments (pcs_commit_device_batch): the kernels of pcs_commit_device with a member in front of every index. The
-// members of a group share the shape; member m's raw rows lie at rows + m R C, its encoded rows at M + m R N and its tree at
-// trees + m tree_words. Every grid is one-dimensional over (member, item).
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsb_stage(const Fr* __restrict__ rows, Fr* __restrict__ M, size_t G, size_t R, int c, unsigned* __restrict__ flags) {
-    const size_t per = R << (c + 2), total = G * per;
-    const size_t C = (size_t)1 << c, Nm = ((size_t)4 << c) - 1;
-    for (size_t i = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * BNPCS_TPB) {
-        const size_t m = i / per, k = i - m * per, r = k >> (c + 2), j = k & Nm;
-        Fr v = fr_zero();
-        if (j < C) {
-            v = lz_gload(rows + ((m * R + r) << c) + j);
-            if (fr_geq_p(v)) atomicOr(flags + m, 1u);   // all four limbs compared; one flag a member
-        }
-        lz_gstore(M + i, v);
-    }
-}
-// One thread per (member m, column j), id = m N + j: k_bnpcs_leaf_hash on the member's own matrix, into the leaves of its own tree.
-// A member's columns may begin inside a wavefront (N < 64): every address below comes from the thread's own m and j.
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsb_leaf_hash(const Fr* __restrict__ M, size_t G, size_t N, size_t R, u64* __restrict__ trees, size_t tree_words) {
-    const size_t id = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
-    if (id >= G * N) return;
-    const size_t m = id / N, j = id - m * N;
-    u64 a[25];
-    bnpcs_leaf_absorb(reinterpret_cast<const u64*>(M + m * R * N + j), 4 * N, R, a);   // 4N words between the rows
-    u64* out = trees + m * tree_words + 4 * j;
-    out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
 }
 
 // hg_pcs_commit_batch_bn254. A group: one allocation for its members' raw and encoded rows (a freed group's, where the context
@@ -948,14 +815,14 @@ std::vector<pcs::Commitment*> pcs_commit_device_batch(const char* who_c, hg_ctx*
         const double t2 = omp_get_wtime();
         ctx->prof_begin(cls, (double)G * R * C * (words ? 40 : 0) + (double)G * R * (C + N) * 32);
         if (words) k_bnpcs_lift<<<(unsigned)std::min<size_t>(bnpcs_blocks(G * R * C), 4096), BNPCS_TPB, 0, st>>>(d_words, d_rows, G * R * C);
-        k_bnpcsb_stage<<<(unsigned)std::min<size_t>(bnpcs_blocks(G * R * N), 4096), BNPCS_TPB, 0, st>>>(d_rows, d_M, G, R, sh.c, d_flags);
+        k_bnpcsb_stage<<<dim3((unsigned)std::min<size_t>(bnpcs_blocks(R * N), (4096 + G - 1) / G), (unsigned)G), BNPCS_TPB, 0, st>>>(d_rows, d_M, R, sh.c, d_flags);   // about 4096 workgroups in all; G in the grid's y: cut_groups keeps it at VB_MAX_GROUP = 64 or below
         ctx->prof_end();
         ctx->prof_begin(cls, (double)G * R * N * 32 * 4);
         k_bn_powers<<<bnpcs_blocks(N), 256, 0, st>>>(W, fr_root_of_unity(log2n), N);
         for (size_t m0 = 0; m0 < G; m0 += slice) ntt_batch_dev(st, d_M + m0 * R * N, tmp, W, log2n, std::min(slice, G - m0) * R, nullptr);
         ctx->prof_end();
         ctx->prof_begin(cls, (double)G * R * N * 32);
-        k_bnpcsb_leaf_hash<<<bnpcs_blocks(G * N), BNPCS_TPB, 0, st>>>(d_M, G, N, R, d_out, tree_words);
+        k_bnpcsb_leaf_hash<<<bnpcs_blocks(G * N), BNPCS_TPB, 0, st>>>(d_M, G, log2n, R, d_out, tree_words);
         ctx->prof_end();
         ctx->prof_begin(cls, (double)G * N * 96);
         pcs::merkle_levels_device_batch(st, d_out, tree_words, N, G);
@@ -989,87 +856,6 @@ std::vector<pcs::Commitment*> pcs_commit_device_batch(const char* who_c, hg_ctx*
     std::vector<pcs::Commitment*> out;
     for (auto& cm : made) out.push_back(cm.release());
     return out;
-}
-
-// ---- a run of openings (pcs_open_device_batch). What differs by item lies in three flat tables of the group's staged copy: a job a
-// row combination (the proximity combination and one a claim, every member's behind the other), a claim an evaluation check, a
-// member where its matrix, its u vectors and its opening image lie. Every block of the staged copy starts at a multiple of 32 bytes
-// (lz_gload reads 16-byte halves). Every grid is one-dimensional.
-struct BnObJob { const Fr* src; u64 nrows, w_at, u_at; };      // its first raw row; the byte offset of its weights in the staged copy; where u goes (elements)
-struct BnObClaim { u64 u_at, z_at, y_at, member, claim; };     // its u_i (elements); byte offsets of the low coordinates (Montgomery) and of the value
-struct BnObMember { const Fr* M; u64 img, u, u_words; };       // its encoded matrix; word offsets of its image and of its u vectors; 4 C (n + 1)
-
-// k_bnpcs_combine driven by the job table: workgroup b serves job b / cb alone, columns (b % cb) BNPCS_TPB .. - the weight limbs go
-// through readfirstlane, so every lane of a wavefront must be on one job
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_combine(int c, unsigned cb, const BnObJob* __restrict__ jobs, const char* __restrict__ stage, Fr* __restrict__ u) {
-    const size_t C = (size_t)1 << c;
-    const unsigned jq = blockIdx.x / cb;
-    const size_t j = (size_t)(blockIdx.x - jq * cb) * BNPCS_TPB + threadIdx.x;
-    if (j >= C) return;
-    const BnObJob job = jobs[jq];
-    const Fr* src = job.src + j;
-    const u32* wq = reinterpret_cast<const u32*>(stage + job.w_at);
-    Fr s = fr_zero();
-    for (u64 r0 = 0; r0 < job.nrows; r0 += BNPCS_CHUNK) {
-        const u64 r1 = r0 + BNPCS_CHUNK < job.nrows ? r0 + BNPCS_CHUNK : job.nrows;
-        WCol A = wcol_zero();
-        for (u64 r = r0; r < r1; r++) {
-            const Fr x = lz_gload(src + (r << c));
-            u32 bl[8];
-#pragma unroll
-            for (int k = 0; k < 8; k++) bl[k] = __builtin_amdgcn_readfirstlane(wq[8 * r + k]);
-            bnpcs_mac_uniform(A, x, bl);
-        }
-        s = lz_add(s, lz_reduce(A));
-    }
-    lz_gstore(u + job.u_at + j, lz_canon(s));
-}
-// One workgroup per (member, claim), the arithmetic of k_bnpcsvb_eval: <u_i, eq(z_i[..c])> == y_i; cells[member] = its lowest failing claim
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_eval(const BnObClaim* __restrict__ claims, int c, const Fr* __restrict__ u, const char* __restrict__ stage,
-                                                            u64* __restrict__ cells) {
-    __shared__ Fr part[BNPCS_TPB];
-    const BnObClaim cl = claims[blockIdx.x];
-    const size_t C = (size_t)1 << c;
-    const Fr* z = reinterpret_cast<const Fr*>(stage + cl.z_at);
-    const Fr* ui = u + cl.u_at;
-    const int lob = c < 8 ? c : 8;
-    Fr f = fr_one_mont();
-    for (int b = 0; b < lob; b++) { const Fr zb = lz_gload(z + b); f = fr_mul(f, (threadIdx.x >> b) & 1 ? zb : fr_sub(fr_one_mont(), zb)); }
-    Fr s = fr_zero();
-    for (size_t x = threadIdx.x; x < C; x += BNPCS_TPB) {
-        Fr gq = f;
-        for (int b = 8; b < c; b++) { const Fr zb = lz_gload(z + b); gq = fr_mul(gq, (x >> b) & 1 ? zb : fr_sub(fr_one_mont(), zb)); }
-        s = fr_add(s, fr_mul(lz_gload(ui + x), gq));
-    }
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int h = BNPCS_TPB / 2; h >= 1; h >>= 1) {
-        if (threadIdx.x < h) part[threadIdx.x] = fr_add(part[threadIdx.x], part[threadIdx.x + h]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && !fr_eq(part[0], lz_gload(reinterpret_cast<const Fr*>(stage + cl.y_at)))) bnpcsv_min(cells + cl.member, cl.claim);
-}
-// Word i of the group's u vectors into its member's image, an element as 32 bytes big-endian: word w of the image's element is the
-// byte-swapped limb 3 - w. The member is the last one whose u offset is <= i (offsets are multiples of 4: an element never straddles)
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_emit(const BnObMember* __restrict__ mem, unsigned G, size_t total, const u64* __restrict__ u, u64* __restrict__ img) {
-    for (size_t i = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * BNPCS_TPB) {
-        unsigned lo = 0, hi = G;
-        while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].u <= i) lo = mid; else hi = mid; }
-        img[mem[lo].img + (i - mem[lo].u)] = __builtin_bswap64(u[i ^ 3]);
-    }
-}
-// One thread per (member m, query q, row r), id = (m Q + q) R + r: M_m[r][j_q] big-endian at its place in the member's image.
-// js[m Q + q] = j_q (masked by the host); js[G Q + m] != 0: the member takes part (it was not refused)
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_gather(const BnObMember* __restrict__ mem, size_t G, size_t Q, size_t R, size_t N, size_t q_words,
-                                                              const u64* __restrict__ js, u64* __restrict__ img) {
-    const size_t id = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
-    if (id >= G * Q * R) return;
-    const size_t m = id / (Q * R), k = id - m * Q * R, q = k / R, r = k - q * R;
-    if (!js[G * Q + m]) return;
-    const BnObMember M = mem[m];
-    const Fr v = lz_gload(M.M + r * N + js[m * Q + q]);
-    u64* out = img + M.img + M.u_words + q * q_words + 4 * r;
-    out[0] = __builtin_bswap64(v.l[3]); out[1] = __builtin_bswap64(v.l[2]); out[2] = __builtin_bswap64(v.l[1]); out[3] = __builtin_bswap64(v.l[0]);
 }
 
 // hg_pcs_open_batch_bn254, pcs::open_device_batch step for step. A group: the host threads write every member's transcript start,

@@ -1,10 +1,10 @@
 // Device form of the polynomial commitment (pcs.hpp): rows staged into the zero-padded 4C-stride matrix and encoded by the batched
 // NTT, one Keccak-f[1600] state per thread for the column hashes and the tree, the E x F row combinations of an opening through
 // the deferred-reduction accumulators, a gather of the opened columns. The handle owns the raw and the encoded matrix in HBM.
-// The verifier of an opening (verify_device) reuses the encoding and the leaf hash and adds five kernels of its own.
-// The verifier of a run of openings (verify_device_batch) runs the same five kernels once over a group, driven by a member table.
-// A run of commitments (commit_device_batch) and a run of openings (open_device_batch) do the same for the prover's side: a group's
-// matrices in one allocation that its handles share, the kernels of commit and open once over the group.
+// The verifier of an opening reuses the encoding and the leaf hash and adds five kernels of its own.
+// Every step has one kernel, written for a group of members and driven by a member or job table; the forms for a run (commit_device_batch,
+// open_device_batch, verify_device_batch) launch it once over a group, whose matrices lie in one allocation that its handles share,
+// and the forms for one (commit_device, combine_device, verify_device) launch it over a group of one from a host flow of their own.
 // A commitment to tables that lie in HBM (commit_tables_enqueue: hg_secrets_commit_values, the encryption pipeline) stages them with one
 // kernel of its own and goes on with the encoding, the leaf hash and the tree of commit_device.
 #include <omp.h>
@@ -19,18 +19,24 @@ namespace pcs {
 
 constexpr int PCS_TPB = 256;
 
-// M[r][j] = j < C ? rows[r][j] : 0 ahead of the encoding; a word that is not below p sets *flag
-__global__ __launch_bounds__(PCS_TPB) void k_pcs_stage(const u64* __restrict__ rows, u64* __restrict__ M, size_t R, int c, unsigned* __restrict__ flag) {
+// ---- the kernels of a commitment, written for a group of G members of one shape (commit_device_batch); one commitment is a group
+// of one. Member m's raw rows lie at rows + m R C, its encoded rows at M + m R N (so a group's encoding is one ntt_batch over G R
+// rows) and its tree at trees + m tree_words.
+// blockIdx.y = the member, its words grid-strided over blockIdx.x: M[r][j] = j < C ? rows[r][j] : 0 ahead of the encoding; a word that
+// is not below p sets the member's flag
+__global__ __launch_bounds__(PCS_TPB) void k_pcsb_stage(const u64* __restrict__ rows, u64* __restrict__ M, size_t R, int c, unsigned* __restrict__ flags) {
     const size_t total = R << (c + 2);
     const size_t C = (size_t)1 << c, Nm = ((size_t)4 << c) - 1;
+    const u64* src = rows + (((size_t)blockIdx.y * R) << c);
+    u64* dst = M + (size_t)blockIdx.y * total;
     bool bad = false;
     for (size_t i = (size_t)blockIdx.x * PCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * PCS_TPB) {
         const size_t r = i >> (c + 2), j = i & Nm;
         u64 v = 0;
-        if (j < C) { v = rows[(r << c) + j]; bad |= v >= GL_P; }
-        M[i] = v;
+        if (j < C) { v = src[(r << c) + j]; bad |= v >= GL_P; }
+        dst[i] = v;
     }
-    if (bad) atomicOr(flag, 1u);
+    if (bad) atomicOr(flags + blockIdx.y, 1u);
 }
 
 // Keccak256(LE64(0) || col[0] || col[stride] || .. || col[(R-1) * stride]) into the first four words of `a`: 17 message words per
@@ -54,24 +60,30 @@ __device__ __forceinline__ void leaf_absorb(const u64* __restrict__ col, size_t 
         keccak_f(a);
     }
 }
-// One thread per column j of the encoded matrix: the leaf hash of M[0][j] .. M[R-1][j] -> leaves[j]. A wavefront reads 64 adjacent
-// words of a row at a time.
-__global__ __launch_bounds__(PCS_TPB) void k_pcs_leaf_hash(const u64* __restrict__ M, size_t N, size_t R, u64* __restrict__ leaves) {
-    const size_t j = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
-    if (j >= N) return;
+// One thread per (member m, column j) of the encoded matrices (N = 2^depth columns), id = m N + j: the leaf hash of the member's
+// M[0][j] .. M[R-1][j] into the leaves of its own tree. A wavefront reads 64 adjacent words of a row at a time.
+__global__ __launch_bounds__(PCS_TPB) void k_pcsb_leaf_hash(const u64* __restrict__ M, size_t G, int depth, size_t R, u64* __restrict__ trees, size_t tree_words) {
+    const size_t id = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
+    if (id >= G << depth) return;
+    const size_t N = (size_t)1 << depth, m = id >> depth, j = id & (N - 1);
     u64 a[25];
-    leaf_absorb(M + j, N, R, a);
-    u64* out = leaves + 4 * j;
+    leaf_absorb(M + m * R * N + j, N, R, a);
+    u64* out = trees + m * tree_words + 4 * j;
     out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
 }
-
-// One level of the tree: node i of `here` = Keccak256(LE64(1) || nodes 2i and 2i + 1 of `below`), one permutation a node
-__global__ __launch_bounds__(PCS_TPB) void k_pcs_merkle(const u64* __restrict__ below, u64* __restrict__ here, size_t count) {
-    const size_t i = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
-    if (i < count) merkle_node(below, here, i);
+// One level of the trees, one thread per (member, node): node i of the 2^lg at word below_at + 8 * 2^lg of a tree =
+// Keccak256(LE64(1) || nodes 2i and 2i + 1 of the 2 * 2^lg at word below_at), one permutation a node
+__global__ __launch_bounds__(PCS_TPB) void k_pcsb_merkle(u64* __restrict__ trees, size_t tree_words, size_t below_at, int lg, size_t G) {
+    const size_t id = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
+    if (id >= G << lg) return;
+    const size_t count = (size_t)1 << lg;
+    u64* below = trees + (id >> lg) * tree_words + below_at;
+    merkle_node(below, below + 8 * count, id & (count - 1));
 }
-// The levels from `count` (<= PCS_TPB) nodes up to the root in one workgroup; the levels lie one behind the other in the tree buffer
-__global__ __launch_bounds__(PCS_TPB) void k_pcs_merkle_top(u64* below, size_t count) {
+// One workgroup per member (blockIdx.x): the levels from `count` (<= PCS_TPB) nodes up to the root of its tree; the levels lie one
+// behind the other in the tree buffer
+__global__ __launch_bounds__(PCS_TPB) void k_pcsb_merkle_top(u64* __restrict__ trees, size_t tree_words, size_t below_at, size_t count) {
+    u64* below = trees + (size_t)blockIdx.x * tree_words + below_at;
     while (count >= 1) {
         u64* here = below + 8 * count;   // `below` has 2 * count nodes of 4 words
         if (threadIdx.x < count) merkle_node(below, here, threadIdx.x);
@@ -81,32 +93,23 @@ __global__ __launch_bounds__(PCS_TPB) void k_pcs_merkle_top(u64* below, size_t c
     }
 }
 
-// Row combinations of an opening. Job q (blockIdx.y): u_q[j] = sum_{r < nrows} w[woff + r] * rows[row0 + r][j]; a thread owns column
-// j. The weights are uniform over the workgroup. Products go into two column accumulators (c0 and c1 of the weight) that are
-// reduced every COMBINE_CHUNK rows: the carry counters of gl_wide.hpp stay below 2^8 for up to 127 products.
-struct CombineDesc { u64 row0, nrows, woff; };
+// sum_{r < nrows} w[r] * src[r << shift]. Products go into two accumulators (c0 and c1 of the weight) that are reduced every
+// COMBINE_CHUNK rows: the carry counters of gl_wide.hpp stay below 2^8 for up to 127 products.
 constexpr int COMBINE_CHUNK = 64;
-__global__ __launch_bounds__(PCS_TPB) void k_pcs_combine(const u64* __restrict__ rows, int c, const CombineDesc* __restrict__ jobs, const E2* __restrict__ w,
-                                                         E2* __restrict__ u) {
-    const size_t C = (size_t)1 << c;
-    const size_t j = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
-    if (j >= C) return;
-    const CombineDesc job = jobs[blockIdx.y];
-    const u64* src = rows + (job.row0 << c) + j;
-    const E2* wq = w + job.woff;
+__device__ __forceinline__ E2 dot_chunked(const u64* __restrict__ src, int shift, const E2* __restrict__ w, u64 nrows) {
     u64 s0 = 0, s1 = 0;
-    for (u64 r0 = 0; r0 < job.nrows; r0 += COMBINE_CHUNK) {
-        const u64 r1 = r0 + COMBINE_CHUNK < job.nrows ? r0 + COMBINE_CHUNK : job.nrows;
+    for (u64 r0 = 0; r0 < nrows; r0 += COMBINE_CHUNK) {
+        const u64 r1 = r0 + COMBINE_CHUNK < nrows ? r0 + COMBINE_CHUNK : nrows;
         WAcc A = wacc_zero(), B = wacc_zero();
         for (u64 r = r0; r < r1; r++) {
-            const u64 x = src[r << c];
-            const E2 wr = wq[r];
+            const u64 x = src[r << shift];
+            const E2 wr = w[r];
             wmac2(A, x, wr.c0, B, x, wr.c1);
         }
         s0 = gl_add(s0, wreduce(A));
         s1 = gl_add(s1, wreduce(B));
     }
-    u[(size_t)blockIdx.y * C + j] = e2(s0, s1);
+    return e2(s0, s1);
 }
 
 // cols[q][r] = M[r][js[q]]
@@ -116,131 +119,15 @@ __global__ __launch_bounds__(PCS_TPB) void k_pcs_gather(const u64* __restrict__ 
     cols[(size_t)blockIdx.y * R + r] = M[r * N + js[blockIdx.y]];
 }
 
-// ---- the verifier of an opening (verify_device). Grids are one-dimensional throughout: Q reaches 65536, one more than a grid's y.
-// A word of the opening only ever becomes a number; every index below comes from the shape, from the host's masked j_q or from
-// table offsets the entry point validated.
+// ---- the kernels of the verifier, written for a group of G openings of one shape and one Q (verify_device_batch); one opening
+// (verify_device) is a group of one, its device copy the set. What differs by member (its claim count, where its opening, u, columns,
+// encoded rows, jobs and weights lie) is read from its descriptor, never derived from a flat id. Grids over queries are
+// one-dimensional: Q reaches 65536, one more than a grid's y. A word of an opening only ever becomes a number; every index below comes
+// from the shape, from the host's masked j_q or from table offsets the entry point validated. A result cell holds the lowest
+// offending key (atomicMin), so the reason is the host's also where several checks fail at once.
 constexpr u64 PCSV_NONE = ~(u64)0;   // a cell no thread lowered: nothing failed
 __device__ __forceinline__ void cell_min(u64* cell, u64 v) { atomicMin(reinterpret_cast<unsigned long long*>(cell), (unsigned long long)v); }
-
-// Big-endian words of the opening -> native words. Word i < u_words is coordinate i & 1 of element i >> 1 of the u vectors: kept in
-// u (as E2) and scattered into row 2 * (i >> (c+1)) + (i & 1) of the matrix the NTT encodes (zeroed beforehand). The others are
-// the Q * R column words, query q at word u_words + q * q_words. cells[0] = the lowest byte offset of a word that is not below p.
-__global__ __launch_bounds__(PCS_TPB) void k_pcsv_canon(const u64* __restrict__ proof, size_t u_words, size_t Q, size_t R, size_t q_words, int c,
-                                                        u64* __restrict__ u, u64* __restrict__ cols, u64* __restrict__ enc, u64* __restrict__ cells) {
-    const size_t total = u_words + Q * R, Cm = ((size_t)1 << c) - 1;
-    u64 bad = PCSV_NONE;
-    for (size_t i = (size_t)blockIdx.x * PCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * PCS_TPB) {
-        size_t at = i;
-        if (i >= u_words) { const size_t k = i - u_words, q = k / R; at = u_words + q * q_words + (k - q * R); }
-        const u64 v = __builtin_bswap64(proof[at]);
-        if (v >= GL_P && 8 * at < bad) bad = 8 * at;
-        if (i < u_words) {
-            const size_t e = i >> 1, row = 2 * (e >> c) + (i & 1);
-            u[i] = v;
-            enc[(row << (c + 2)) + (e & Cm)] = v;
-        } else {
-            cols[i - u_words] = v;
-        }
-    }
-    if (bad != PCSV_NONE) cell_min(cells, bad);
-}
-
-// <u_i, eq(z_i[..c])> == y_i, one workgroup per claim i (blockIdx.x). eq(z, x) = prod_b (x_b ? z_b : 1 - z_b) is formed per entry:
-// a thread keeps the factor of the low eight bits of x, which its entries share. cells[1] = the lowest failing claim.
-__global__ __launch_bounds__(PCS_TPB) void k_pcsv_eval(const E2* __restrict__ u, int c, const E2* __restrict__ zlo, const E2* __restrict__ y, u64* __restrict__ cells) {
-    __shared__ E2 part[PCS_TPB];
-    const size_t C = (size_t)1 << c, i = blockIdx.x;
-    const E2* z = zlo + i * (size_t)c;
-    const E2* ui = u + (i + 1) * C;
-    const int lo = c < 8 ? c : 8;
-    E2 f = e2_one();
-    for (int b = 0; b < lo; b++) f = e2_mul(f, (threadIdx.x >> b) & 1 ? z[b] : e2_sub(e2_one(), z[b]));
-    E2 s = e2_zero();
-    for (size_t x = threadIdx.x; x < C; x += PCS_TPB) {
-        E2 g = f;
-        for (int b = 8; b < c; b++) g = e2_mul(g, (x >> b) & 1 ? z[b] : e2_sub(e2_one(), z[b]));
-        s = e2_add(s, e2_mul(ui[x], g));
-    }
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int h = PCS_TPB / 2; h >= 1; h >>= 1) {
-        if (threadIdx.x < h) part[threadIdx.x] = e2_add(part[threadIdx.x], part[threadIdx.x + h]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && !e2_eq(part[0], y[i])) cell_min(cells + 1, (u64)i);
-}
-
-// One thread per query: the leaf hash of its R column words -> leaves[q]
-__global__ __launch_bounds__(PCS_TPB) void k_pcsv_leaf(const u64* __restrict__ cols, size_t Q, size_t R, u64* __restrict__ leaves) {
-    const size_t q = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
-    if (q >= Q) return;
-    u64 a[25];
-    leaf_absorb(cols + q * R, 1, R, a);
-    u64* out = leaves + 4 * q;
-    out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
-}
-
-// One thread per (query q, job i): s[q][i] = sum_{r < nrows} w[woff + r] * col_q[row0 + r]. Job 0 is the proximity combination
-// (rho^r over the whole column), job 1 + i claim i's (eq(z_i[c..]) over the rows of its table). Reduced every COMBINE_CHUNK products.
-__global__ __launch_bounds__(PCS_TPB) void k_pcsv_dots(const u64* __restrict__ cols, size_t Q, size_t R, const CombineDesc* __restrict__ jobs, size_t njobs,
-                                                       const E2* __restrict__ w, E2* __restrict__ s) {
-    const size_t id = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
-    if (id >= Q * njobs) return;
-    const size_t q = id / njobs;
-    const CombineDesc job = jobs[id - q * njobs];
-    const u64* src = cols + q * R + job.row0;
-    const E2* wq = w + job.woff;
-    u64 s0 = 0, s1 = 0;
-    for (u64 r0 = 0; r0 < job.nrows; r0 += COMBINE_CHUNK) {
-        const u64 r1 = r0 + COMBINE_CHUNK < job.nrows ? r0 + COMBINE_CHUNK : job.nrows;
-        WAcc A = wacc_zero(), B = wacc_zero();
-        for (u64 r = r0; r < r1; r++) {
-            const u64 x = src[r];
-            const E2 wr = wq[r];
-            wmac2(A, x, wr.c0, B, x, wr.c1);
-        }
-        s0 = gl_add(s0, wreduce(A));
-        s1 = gl_add(s1, wreduce(B));
-    }
-    s[id] = e2(s0, s1);
-}
-
-// One thread per query, once the host has the column indices: the path from the leaf hash over the c+2 siblings (32 raw bytes
-// each behind the query's column words; bit l of j_q says on which side level l's sibling lies) against the root, then s[q][0]
-// against Enc(u_0)[j_q], then s[q][1 + i] against Enc(u_i)[j_q]. enc: rows 2i, 2i + 1 = the encoded c0, c1 coordinates of u_i.
-// cells[2] = the lowest q * (n + 2) + kind that failed: kind 0 the path, 1 proximity, 2 + i claim i.
-__global__ __launch_bounds__(PCS_TPB) void k_pcsv_query(const u64* __restrict__ proof, size_t u_words, size_t q_words, size_t Q, size_t R, int depth,
-                                                        const u64* __restrict__ leaves, const E2* __restrict__ s, const u64* __restrict__ enc, size_t n,
-                                                        const u64* __restrict__ js, const u64* __restrict__ root, u64* __restrict__ cells) {
-    const size_t q = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
-    if (q >= Q) return;
-    const size_t N = (size_t)1 << depth, j = js[q];
-    const u64* sib = proof + u_words + q * q_words + R;
-    u64 h0 = leaves[4 * q], h1 = leaves[4 * q + 1], h2 = leaves[4 * q + 2], h3 = leaves[4 * q + 3];
-    for (int l = 0; l < depth; l++) {
-        const bool right = (j >> l) & 1;   // this node is the right child
-        const u64 t0 = sib[4 * l], t1 = sib[4 * l + 1], t2 = sib[4 * l + 2], t3 = sib[4 * l + 3];
-        u64 a[25];
-        a[0] = 1;
-        a[1] = right ? t0 : h0; a[2] = right ? t1 : h1; a[3] = right ? t2 : h2; a[4] = right ? t3 : h3;
-        a[5] = right ? h0 : t0; a[6] = right ? h1 : t1; a[7] = right ? h2 : t2; a[8] = right ? h3 : t3;
-        a[9] = 0x01;
-#pragma unroll
-        for (int k = 10; k < 25; k++) a[k] = 0;
-        a[RATE_WORDS - 1] = 0x8000000000000000ull;
-        keccak_f(a);
-        h0 = a[0]; h1 = a[1]; h2 = a[2]; h3 = a[3];
-    }
-    const size_t key = q * (n + 2);
-    if (h0 != root[0] || h1 != root[1] || h2 != root[2] || h3 != root[3]) { cell_min(cells + 2, key); return; }
-    const E2* sq = s + q * (n + 1);
-    for (size_t i = 0; i <= n; i++)
-        if (!e2_eq(sq[i], e2(enc[2 * i * N + j], enc[(2 * i + 1) * N + j]))) { cell_min(cells + 2, key + 1 + i); return; }
-}
-
-// ---- the verifier of a run of openings (verify_device_batch): the five kernels above with a member in front of every index. The
-// members of a group share the shape and Q; what differs by member (its claim count, where its opening, u, columns, encoded rows,
-// jobs and weights lie) is read from its descriptor, never derived from a flat id. Grids over queries stay one-dimensional.
+struct CombineDesc { u64 row0, nrows, woff; };   // a row combination: sum_{r < nrows} w[woff + r] * row_{row0 + r}
 struct VbMember {
     u64 proof, u, cols, enc_row;               // word offsets of its opening in the set, of its u and of its columns; its first row of enc
     u64 n, claim0, job0;                       // its claims; the claims and the jobs (claims + 1 each) of the members before it
@@ -248,8 +135,10 @@ struct VbMember {
 };
 struct VbGroup { u64 G, Q, R, q_words; int c, depth; };
 
-// blockIdx.y = the member, its words grid-strided over blockIdx.x: k_pcsv_canon on its own opening, into its own u, columns and enc
-// rows; cells[3m] = the lowest byte offset, within its opening, of a word that is not below p
+// Big-endian words of an opening -> native words; blockIdx.y = the member, its words grid-strided over blockIdx.x. Word i < u_words is
+// coordinate i & 1 of element i >> 1 of the u vectors: kept in u (as E2) and scattered into row 2 * (i >> (c+1)) + (i & 1) of the
+// member's rows of the matrix the NTT encodes (zeroed beforehand). The others are the Q * R column words, query q at word
+// u_words + q * q_words. cells[3m] = the lowest byte offset, within its opening, of a word that is not below p.
 __global__ __launch_bounds__(PCS_TPB) void k_pcsvb_canon(const u64* __restrict__ set, const VbMember* __restrict__ mem, VbGroup g, u64* __restrict__ u,
                                                          u64* __restrict__ cols, u64* __restrict__ enc, u64* __restrict__ cells) {
     const VbMember M = mem[blockIdx.y];
@@ -276,18 +165,11 @@ __global__ __launch_bounds__(PCS_TPB) void k_pcsvb_canon(const u64* __restrict__
     if (bad != PCSV_NONE) cell_min(cells + 3 * blockIdx.y, bad);
 }
 
-// One workgroup per (member, claim): block b belongs to the last member whose claim0 is <= b (a member without claims owns no block).
-// cells[3m + 1] = the member's lowest failing claim.
-__global__ __launch_bounds__(PCS_TPB) void k_pcsvb_eval(const VbMember* __restrict__ mem, unsigned G, int c, const u64* __restrict__ u, const char* __restrict__ stage,
-                                                        u64* __restrict__ cells) {
+// <ui, eq(z[..c])> != y, by one workgroup; the answer is thread 0's. eq(z, x) = prod_b (x_b ? z_b : 1 - z_b) is formed per entry: a
+// thread keeps the factor of the low eight bits of x, which its entries share.
+__device__ __forceinline__ bool eval_differs(const E2* __restrict__ ui, const E2* __restrict__ z, const E2* __restrict__ y, int c) {
     __shared__ E2 part[PCS_TPB];
-    unsigned lo = 0, hi = G;
-    while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].claim0 <= blockIdx.x) lo = mid; else hi = mid; }
-    const VbMember M = mem[lo];
-    const size_t C = (size_t)1 << c, i = blockIdx.x - M.claim0;
-    if (i >= M.n) return;   // (uniform over the workgroup; the grid has exactly the claims of the group)
-    const E2* z = reinterpret_cast<const E2*>(stage + M.z_at) + i * (size_t)c;
-    const E2* ui = reinterpret_cast<const E2*>(u + M.u) + (i + 1) * C;
+    const size_t C = (size_t)1 << c;
     const int lob = c < 8 ? c : 8;
     E2 f = e2_one();
     for (int b = 0; b < lob; b++) f = e2_mul(f, (threadIdx.x >> b) & 1 ? z[b] : e2_sub(e2_one(), z[b]));
@@ -303,7 +185,20 @@ __global__ __launch_bounds__(PCS_TPB) void k_pcsvb_eval(const VbMember* __restri
         if (threadIdx.x < h) part[threadIdx.x] = e2_add(part[threadIdx.x], part[threadIdx.x + h]);
         __syncthreads();
     }
-    if (threadIdx.x == 0 && !e2_eq(part[0], reinterpret_cast<const E2*>(stage + M.y_at)[i])) cell_min(cells + 3 * lo + 1, (u64)i);
+    return threadIdx.x == 0 && !e2_eq(part[0], *y);
+}
+// <u_i, eq(z_i[..c])> == y_i, one workgroup per (member, claim): block b belongs to the last member whose claim0 is <= b (a member
+// without claims owns no block). cells[3m + 1] = the member's lowest failing claim.
+__global__ __launch_bounds__(PCS_TPB) void k_pcsvb_eval(const VbMember* __restrict__ mem, unsigned G, int c, const u64* __restrict__ u, const char* __restrict__ stage,
+                                                        u64* __restrict__ cells) {
+    unsigned lo = 0, hi = G;
+    while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].claim0 <= blockIdx.x) lo = mid; else hi = mid; }
+    const VbMember M = mem[lo];
+    const size_t i = blockIdx.x - M.claim0;
+    if (i >= M.n) return;   // (uniform over the workgroup; the grid has exactly the claims of the group)
+    if (eval_differs(reinterpret_cast<const E2*>(u + M.u) + ((i + 1) << c), reinterpret_cast<const E2*>(stage + M.z_at) + i * (size_t)c,
+                     reinterpret_cast<const E2*>(stage + M.y_at) + i, c))
+        cell_min(cells + 3 * lo + 1, (u64)i);
 }
 
 // One thread per (member m, query q), id = m Q + q: the leaf hash of its R column words -> leaves[id]
@@ -317,8 +212,9 @@ __global__ __launch_bounds__(PCS_TPB) void k_pcsvb_leaf(const VbMember* __restri
     out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
 }
 
-// One thread per (member, query, job): member m owns the ids from Q job0_m; within it id - Q job0_m = q (n_m + 1) + job, as in
-// k_pcsv_dots, and s[id] is where k_pcsvb_query reads it
+// One thread per (member, query, job): s[id] = sum_{r < nrows} w[woff + r] * col_q[row0 + r]. Member m owns the ids from Q job0_m;
+// within it id - Q job0_m = q (n_m + 1) + job. Job 0 is the proximity combination (rho^r over the whole column), job 1 + i claim i's
+// (eq(z_i[c..]) over the rows of its table).
 __global__ __launch_bounds__(PCS_TPB) void k_pcsvb_dots(const VbMember* __restrict__ mem, VbGroup g, size_t total, const u64* __restrict__ cols,
                                                         const char* __restrict__ stage, E2* __restrict__ s) {
     const size_t id = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
@@ -328,25 +224,13 @@ __global__ __launch_bounds__(PCS_TPB) void k_pcsvb_dots(const VbMember* __restri
     const VbMember M = mem[lo];
     const size_t local = id - M.job0 * g.Q, njobs = M.n + 1, q = local / njobs;
     const CombineDesc job = reinterpret_cast<const CombineDesc*>(stage + M.jobs_at)[local - q * njobs];
-    const u64* src = cols + M.cols + q * g.R + job.row0;
-    const E2* wq = reinterpret_cast<const E2*>(stage + M.w_at) + job.woff;
-    u64 s0 = 0, s1 = 0;
-    for (u64 r0 = 0; r0 < job.nrows; r0 += COMBINE_CHUNK) {
-        const u64 r1 = r0 + COMBINE_CHUNK < job.nrows ? r0 + COMBINE_CHUNK : job.nrows;
-        WAcc A = wacc_zero(), B = wacc_zero();
-        for (u64 r = r0; r < r1; r++) {
-            const u64 x = src[r];
-            const E2 wr = wq[r];
-            wmac2(A, x, wr.c0, B, x, wr.c1);
-        }
-        s0 = gl_add(s0, wreduce(A));
-        s1 = gl_add(s1, wreduce(B));
-    }
-    s[id] = e2(s0, s1);
+    s[id] = dot_chunked(cols + M.cols + q * g.R + job.row0, 0, reinterpret_cast<const E2*>(stage + M.w_at) + job.woff, job.nrows);
 }
 
-// One thread per (member m, query q), id = m Q + q, once the host has every member's column indices (js[id]): k_pcsv_query on the
-// member's own opening, root, s entries and enc rows. cells[3m + 2] = the member's lowest q (n_m + 2) + kind that failed.
+// One thread per (member m, query q), id = m Q + q, once the host has every member's column indices (js[id]): the path from the leaf
+// hash over the c+2 siblings (32 raw bytes each behind the query's column words) against the member's root, then s[q][0] against
+// Enc(u_0)[j_q], then s[q][1 + i] against Enc(u_i)[j_q]. enc: rows 2i, 2i + 1 of the member = the encoded c0, c1 coordinates of
+// u_i. cells[3m + 2] = the member's lowest q (n_m + 2) + kind that failed: kind 0 the path, 1 proximity, 2 + i claim i.
 __global__ __launch_bounds__(PCS_TPB) void k_pcsvb_query(const u64* __restrict__ set, const VbMember* __restrict__ mem, VbGroup g, const u64* __restrict__ leaves,
                                                          const E2* __restrict__ s, const u64* __restrict__ enc, const u64* __restrict__ js,
                                                          const char* __restrict__ stage, u64* __restrict__ cells) {
@@ -358,28 +242,59 @@ __global__ __launch_bounds__(PCS_TPB) void k_pcsvb_query(const u64* __restrict__
     const size_t N = (size_t)1 << depth, j = js[id], n = M.n, u_words = (n + 1) << (g.c + 1);
     const u64* sib = set + M.proof + u_words + q * g.q_words + g.R;
     const u64* root = reinterpret_cast<const u64*>(stage + M.root_at);
-    u64 h0 = leaves[4 * id], h1 = leaves[4 * id + 1], h2 = leaves[4 * id + 2], h3 = leaves[4 * id + 3];
-    for (int l = 0; l < depth; l++) {
-        const bool right = (j >> l) & 1;   // this node is the right child
-        const u64 t0 = sib[4 * l], t1 = sib[4 * l + 1], t2 = sib[4 * l + 2], t3 = sib[4 * l + 3];
-        u64 a[25];
-        a[0] = 1;
-        a[1] = right ? t0 : h0; a[2] = right ? t1 : h1; a[3] = right ? t2 : h2; a[4] = right ? t3 : h3;
-        a[5] = right ? h0 : t0; a[6] = right ? h1 : t1; a[7] = right ? h2 : t2; a[8] = right ? h3 : t3;
-        a[9] = 0x01;
-#pragma unroll
-        for (int k = 10; k < 25; k++) a[k] = 0;
-        a[RATE_WORDS - 1] = 0x8000000000000000ull;
-        keccak_f(a);
-        h0 = a[0]; h1 = a[1]; h2 = a[2]; h3 = a[3];
-    }
+    u64 h[4] = {leaves[4 * id], leaves[4 * id + 1], leaves[4 * id + 2], leaves[4 * id + 3]};
+    merkle_climb(h, sib, j, depth);
     u64* cell = cells + 3 * m + 2;
     const size_t key = q * (n + 2);
-    if (h0 != root[0] || h1 != root[1] || h2 != root[2] || h3 != root[3]) { cell_min(cell, key); return; }
+    if (h[0] != root[0] || h[1] != root[1] || h[2] != root[2] || h[3] != root[3]) { cell_min(cell, key); return; }
     const E2* sq = s + M.job0 * g.Q + q * (n + 1);
     const u64* menc = enc + (M.enc_row << depth);
     for (size_t i = 0; i <= n; i++)
         if (!e2_eq(sq[i], e2(menc[2 * i * N + j], menc[(2 * i + 1) * N + j]))) { cell_min(cell, key + 1 + i); return; }
+}
+
+// ---- the kernels of the prover's side of an opening, written for a group of items (open_device_batch); the row combinations of one
+// opening (combine_device) are a job table of their own. What differs by item lies in three flat tables of the staged copy: a job a
+// row combination (the proximity combination and one a claim, every member's behind the other), a claim an evaluation check, a
+// member where its matrix, its u vectors and its opening image lie. Every grid is one-dimensional.
+struct ObJob { const u64* src; u64 nrows, w_at, u_at; };     // its first raw row; the byte offset of its weights in the staged copy; where u goes (elements)
+struct ObClaim { u64 u_at, z_at, y_at, member, claim; };      // its u_i (elements); byte offsets of the low coordinates and of the value
+struct ObMember { const u64* M; u64 img, u, u_words; };       // its encoded matrix; word offsets of its image and of its u vectors; 2 C (n + 1)
+
+// Row combinations: u[u_at + j] = sum_{r < nrows} w[r] * src[r][j] for the job of the block, a thread owns column j. Block b serves job
+// b / cb, columns (b % cb) PCS_TPB .. ; the weights are uniform over the workgroup.
+__global__ __launch_bounds__(PCS_TPB) void k_pcsob_combine(int c, unsigned cb, const ObJob* __restrict__ jobs, const char* __restrict__ stage, E2* __restrict__ u) {
+    const size_t C = (size_t)1 << c;
+    const unsigned jq = blockIdx.x / cb;
+    const size_t j = (size_t)(blockIdx.x - jq * cb) * PCS_TPB + threadIdx.x;
+    if (j >= C) return;
+    const ObJob job = jobs[jq];
+    u[job.u_at + j] = dot_chunked(job.src + j, c, reinterpret_cast<const E2*>(stage + job.w_at), job.nrows);
+}
+// One workgroup per (member, claim): <u_i, eq(z_i[..c])> == y_i; cells[member] = its lowest failing claim
+__global__ __launch_bounds__(PCS_TPB) void k_pcsob_eval(const ObClaim* __restrict__ claims, int c, const E2* __restrict__ u, const char* __restrict__ stage,
+                                                        u64* __restrict__ cells) {
+    const ObClaim cl = claims[blockIdx.x];
+    if (eval_differs(u + cl.u_at, reinterpret_cast<const E2*>(stage + cl.z_at), reinterpret_cast<const E2*>(stage + cl.y_at), c)) cell_min(cells + cl.member, cl.claim);
+}
+// Word i of the group's u vectors, big-endian, into its member's image: the member is the last one whose u offset is <= i
+__global__ __launch_bounds__(PCS_TPB) void k_pcsob_emit(const ObMember* __restrict__ mem, unsigned G, size_t total, const u64* __restrict__ u, u64* __restrict__ img) {
+    for (size_t i = (size_t)blockIdx.x * PCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * PCS_TPB) {
+        unsigned lo = 0, hi = G;
+        while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].u <= i) lo = mid; else hi = mid; }
+        img[mem[lo].img + (i - mem[lo].u)] = __builtin_bswap64(u[i]);
+    }
+}
+// One thread per (member m, query q, row r), id = (m Q + q) R + r: M_m[r][j_q] big-endian at its place in the member's image.
+// js[m Q + q] = j_q (masked by the host); js[G Q + m] != 0: the member takes part (it was not refused)
+__global__ __launch_bounds__(PCS_TPB) void k_pcsob_gather(const ObMember* __restrict__ mem, size_t G, size_t Q, size_t R, size_t N, size_t q_words,
+                                                          const u64* __restrict__ js, u64* __restrict__ img) {
+    const size_t id = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
+    if (id >= G * Q * R) return;
+    const size_t m = id / (Q * R), k = id - m * Q * R, q = k / R, r = k - q * R;
+    if (!js[G * Q + m]) return;
+    const ObMember M = mem[m];
+    img[M.img + M.u_words + q * q_words + r] = __builtin_bswap64(M.M[r * N + js[m * Q + q]]);
 }
 
 Commitment::~Commitment() {
@@ -390,15 +305,17 @@ Commitment::~Commitment() {
 
 static unsigned blocks_for(size_t n) { return (unsigned)((n + PCS_TPB - 1) / PCS_TPB); }
 
-void merkle_levels_device(hipStream_t st, u64* d_tree, size_t N) {
-    u64* below = d_tree;
-    size_t count = N / 2;
+// The levels above the leaf hashes of the G trees at trees + m tree_words: one launch a level over every (member, node) while a level
+// has more than PCS_TPB nodes, then one workgroup a member
+void merkle_levels_device_batch(hipStream_t st, u64* d_trees, size_t tree_words, size_t N, size_t G) {
+    size_t below_at = 0, count = N / 2;
     for (; count > (size_t)PCS_TPB; count >>= 1) {
-        k_pcs_merkle<<<blocks_for(count), PCS_TPB, 0, st>>>(below, below + 8 * count, count);
-        below += 8 * count;
+        k_pcsb_merkle<<<blocks_for(G * count), PCS_TPB, 0, st>>>(d_trees, tree_words, below_at, __builtin_ctzll(count), G);
+        below_at += 8 * count;
     }
-    k_pcs_merkle_top<<<1, PCS_TPB, 0, st>>>(below, count);
+    k_pcsb_merkle_top<<<(unsigned)G, PCS_TPB, 0, st>>>(d_trees, tree_words, below_at, count);
 }
+void merkle_levels_device(hipStream_t st, u64* d_tree, size_t N) { merkle_levels_device_batch(st, d_tree, 8 * N, N, 1); }
 
 Commitment* commit_device(hg_ctx* ctx, const Shape& sh, const u64* const* tables) {
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
@@ -419,10 +336,10 @@ Commitment* commit_device(hg_ctx* ctx, const Shape& sh, const u64* const* tables
     hip_check(hipMemsetAsync(d_flag, 0, 16, st), "memset");
     for (size_t t = 0; t < sh.nvars.size(); t++)
         hip_check(hipMemcpyAsync(cm->d_rows + sh.off[t] * C, tables[t], ((size_t)8) << sh.nvars[t], hipMemcpyHostToDevice, st), "upload tables");
-    k_pcs_stage<<<(unsigned)std::min<size_t>(blocks_for(R * N), 4096), PCS_TPB, 0, st>>>(cm->d_rows, cm->d_M, R, sh.c, d_flag);
+    k_pcsb_stage<<<(unsigned)std::min<size_t>(blocks_for(R * N), 4096), PCS_TPB, 0, st>>>(cm->d_rows, cm->d_M, R, sh.c, d_flag);
     dev::powers_table(st, W, root_of_unity(log2n), N);
     dev::ntt_batch(st, cm->d_M, log2n, R, W, 1, scratch);
-    k_pcs_leaf_hash<<<blocks_for(N), PCS_TPB, 0, st>>>(cm->d_M, N, R, d_tree);
+    k_pcsb_leaf_hash<<<blocks_for(N), PCS_TPB, 0, st>>>(cm->d_M, 1, log2n, R, d_tree, 8 * N);
     merkle_levels_device(st, d_tree, N);
     cm->tree.resize(32 * (2 * N - 1));
     unsigned flag = 0;
@@ -434,7 +351,7 @@ Commitment* commit_device(hg_ctx* ctx, const Shape& sh, const u64* const* tables
     return cm.release();
 }
 
-// ---- a commitment to tables that lie in HBM already (commit_tables_enqueue, commit_device_values): k_pcs_stage and the copies
+// ---- a commitment to tables that lie in HBM already (commit_tables_enqueue, commit_device_values): k_pcsb_stage and the copies
 // ahead of it in one pass over the source tables. A unit is what a thread moves at a time: two words (16 bytes) when VEC, else one.
 // A row has U = C / unit words units; 2^lanes_log2 = min(PCS_TPB, U) threads work on a row, so a workgroup holds PCS_TPB >> lanes_log2
 // rows at a time, and a row of more than PCS_TPB units is walked in U >> lanes_log2 steps of which every workgroup of the row takes
@@ -513,7 +430,7 @@ void commit_tables_enqueue(hipStream_t st, const Shape& sh, const u64* const* d_
     dev::ntt_batch(st, d_M, log2n, R, W, 1, scratch);
     end();
     begin((double)R * N * 8);
-    k_pcs_leaf_hash<<<blocks_for(N), PCS_TPB, 0, st>>>(d_M, N, R, d_tree);
+    k_pcsb_leaf_hash<<<blocks_for(N), PCS_TPB, 0, st>>>(d_M, 1, log2n, R, d_tree, 8 * N);
     end();
     begin((double)N * 96);
     merkle_levels_device(st, d_tree, N);
@@ -544,18 +461,13 @@ Commitment* commit_device_values(hg_ctx* ctx, const Shape& sh, const u64* const*
     u64* d_tree = ctx->alloc_n<u64>(4 * 2 * N);
     unsigned* d_flag = ctx->alloc_n<unsigned>(4);
     unsigned flag = 0;
-    struct Drain {   // an error between the first enqueue and the synchronisation must not leave copies into dead host buffers behind
-        hipStream_t st; bool armed = true;
-        ~Drain() { if (armed) (void)hipStreamSynchronize(st); }
-    } drain{st};
+    DrainOne drain{st};   // (drains on an error; after the synchronisation below its own is one more, on an idle stream)
     ctx->prof_stream = st;
     commit_tables_enqueue(st, sh, d_tables, cm->d_rows, cm->d_M, scratch, W, d_tree, d_flag, ctx, ctx->prof_class("pcs_commit_values", false));
     cm->tree.resize(32 * (2 * N - 1));
     hip_check(hipMemcpyAsync(cm->tree.data(), d_tree, cm->tree.size(), hipMemcpyDeviceToHost, st), "download tree");
     hip_check(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st), "download flag");
-    const hipError_t synced = hipStreamSynchronize(st);
-    drain.armed = false;
-    hip_check(synced, "sync");
+    hip_check(hipStreamSynchronize(st), "sync");
     hip_check(hipGetLastError(), "launch");
     ctx->prof_collect();
     if (flag) throw Error("a table holds a word that is not below p");
@@ -569,24 +481,23 @@ void combine_device(const Commitment& cm, const std::vector<CombineJob>& jobs, E
     hipStream_t st = ctx->stream;
     const size_t C = cm.sh.C(), nj = jobs.size();
     if (nj > 65535) throw Error("hg_pcs_open: more than 65534 claims");
-    // descriptors and weights in one staged copy
+    // the job table and the weights in one staged copy; job q's u vector is the q-th
     size_t nw = 0;
     for (const CombineJob& j : jobs) nw += j.nrows;
-    const size_t desc_bytes = (nj * sizeof(CombineDesc) + 15) & ~(size_t)15;
+    const size_t desc_bytes = (nj * sizeof(ObJob) + 15) & ~(size_t)15;
     std::vector<char> stage(desc_bytes + nw * sizeof(E2));
-    CombineDesc* hd = reinterpret_cast<CombineDesc*>(stage.data());
-    E2* hw = reinterpret_cast<E2*>(stage.data() + desc_bytes);
-    size_t off = 0;
+    ObJob* hd = reinterpret_cast<ObJob*>(stage.data());
+    size_t w_at = desc_bytes;
     for (size_t q = 0; q < nj; q++) {
-        hd[q].row0 = jobs[q].row0; hd[q].nrows = jobs[q].nrows; hd[q].woff = off;
-        memcpy(hw + off, jobs[q].w.data(), jobs[q].nrows * sizeof(E2));
-        off += jobs[q].nrows;
+        hd[q].src = cm.d_rows + (jobs[q].row0 << cm.sh.c); hd[q].nrows = jobs[q].nrows; hd[q].w_at = w_at; hd[q].u_at = q * C;
+        memcpy(stage.data() + w_at, jobs[q].w.data(), jobs[q].nrows * sizeof(E2));
+        w_at += jobs[q].nrows * sizeof(E2);
     }
     char* d_stage = ctx->alloc_n<char>(stage.size());
     E2* d_u = ctx->alloc_n<E2>(nj * C);
+    const unsigned cb = blocks_for(C);   // (at most 2^16 workgroups a job and, by the entry point, MAX_CLAIMS + 1 jobs: inside a grid's x)
     hip_check(hipMemcpyAsync(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, st), "upload weights");
-    k_pcs_combine<<<dim3(blocks_for(C), (unsigned)nj), PCS_TPB, 0, st>>>(cm.d_rows, cm.sh.c, reinterpret_cast<const CombineDesc*>(d_stage),
-                                                                         reinterpret_cast<const E2*>(d_stage + desc_bytes), d_u);
+    k_pcsob_combine<<<(unsigned)(nj * cb), PCS_TPB, 0, st>>>(cm.sh.c, cb, reinterpret_cast<const ObJob*>(d_stage), d_stage, d_u);
     hip_check(hipMemcpyAsync(u, d_u, nj * C * sizeof(E2), hipMemcpyDeviceToHost, st), "download combinations");
     hip_check(hipStreamSynchronize(st), "hg_pcs_open: sync");
     hip_check(hipGetLastError(), "hg_pcs_open: launch");
@@ -608,8 +519,59 @@ void columns_device(const Commitment& cm, const std::vector<size_t>& js, u64* co
     hip_check(hipGetLastError(), "hg_pcs_open: launch");
 }
 
-// hg_pcs_verify_device. Everything but the last kernel needs no column index, so it is enqueued first and runs while the host
-// hashes the u_i; the indices follow on the same stream, then the three result cells come back: one synchronisation.
+// ---- what the two verifiers share on the host: a member's block of the staged copy and the reading of its three result cells
+// the entries of a member's weight tables: R powers of rho, then eq(z_i[c..]) over the rows of every claim's table
+static size_t weights_of(const Shape& sh, const std::vector<Claim>& claims) {
+    size_t nw = sh.R;
+    for (const Claim& cl : claims) nw += (size_t)1 << (sh.nvars[cl.table] - sh.c);
+    return nw;
+}
+// The block of a member of n claims and nw weights from byte `at` (a multiple of 16) of a staged copy on: root, job descriptors,
+// values, the low coordinates of the points, weight tables. Into its descriptor -> the byte behind the block
+static size_t member_block_layout(VbMember& d, const Shape& sh, size_t n, size_t nw, size_t at) {
+    d.root_at = at;
+    d.jobs_at = d.root_at + 32;
+    d.y_at = d.jobs_at + (((n + 1) * sizeof(CombineDesc) + 15) & ~(size_t)15);
+    d.z_at = d.y_at + n * sizeof(E2);
+    d.w_at = d.z_at + n * (size_t)sh.c * sizeof(E2);
+    return d.w_at + nw * sizeof(E2);
+}
+// fills the block -> the member's transcript, rho squeezed
+static FsTranscript member_block_fill(char* h_stage, const VbMember& d, const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q) {
+    const size_t R = sh.R;
+    FsTranscript tr = start_transcript(sh, root, claims, Q);
+    const std::vector<E2> rho = rho_powers(tr.squeeze(), R);
+    memcpy(h_stage + d.root_at, root, 32);
+    CombineDesc* hd = reinterpret_cast<CombineDesc*>(h_stage + d.jobs_at);
+    E2* hy = reinterpret_cast<E2*>(h_stage + d.y_at);
+    E2* hz = reinterpret_cast<E2*>(h_stage + d.z_at);
+    E2* hw = reinterpret_cast<E2*>(h_stage + d.w_at);
+    hd[0].row0 = 0; hd[0].nrows = R; hd[0].woff = 0;
+    memcpy(hw, rho.data(), R * sizeof(E2));
+    size_t off = R;
+    for (size_t i = 0; i < claims.size(); i++) {
+        const Claim& cl = claims[i];
+        const std::vector<E2> w = eq_table(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
+        hd[i + 1].row0 = sh.off[cl.table]; hd[i + 1].nrows = w.size(); hd[i + 1].woff = off;
+        memcpy(hw + off, w.data(), w.size() * sizeof(E2));
+        off += w.size();
+        hy[i] = cl.value;
+        memcpy(hz + i * (size_t)sh.c, cl.point.data(), (size_t)sh.c * sizeof(E2));
+    }
+    return tr;
+}
+// the host's order: a non-canonical word, the lowest claim whose evaluation fails, the lowest failing query; "" = accepted
+static std::string cells_reason(const u64* cells, size_t n) {
+    if (cells[0] != PCSV_NONE) return reason_noncanonical((size_t)cells[0]);
+    if (cells[1] != PCSV_NONE) return reason_evaluation((size_t)cells[1]);
+    if (cells[2] == PCSV_NONE) return "";
+    const size_t q = (size_t)(cells[2] / (n + 2)), kind = (size_t)(cells[2] % (n + 2));
+    return kind == 0 ? reason_merkle(q) : kind == 1 ? reason_proximity(q) : reason_claim(kind - 2, q);
+}
+
+// hg_pcs_verify_device: a group of one member, whose opening in the arena is the set. Everything but the last kernel needs no column
+// index, so it is enqueued first and runs while the host hashes the u_i; the indices follow on the same stream, then the three
+// result cells come back: one synchronisation.
 std::string verify_device(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof, size_t len) {
     const size_t C = sh.C(), N = sh.N(), R = sh.R, n = claims.size();
     const int depth = sh.depth();
@@ -619,31 +581,14 @@ std::string verify_device(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], 
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
     ctx->arena_reset();
     hipStream_t st = ctx->stream;
-    // root, descriptors, values, the low coordinates of the points and the weight tables in one staged copy
-    FsTranscript tr = start_transcript(sh, root, claims, Q);
-    const std::vector<E2> rho = rho_powers(tr.squeeze(), R);
-    size_t nw = R;
-    for (const Claim& cl : claims) nw += (size_t)1 << (sh.nvars[cl.table] - sh.c);
-    const size_t desc_at = 32, y_at = desc_at + ((njobs * sizeof(CombineDesc) + 15) & ~(size_t)15), z_at = y_at + n * sizeof(E2),
-                 w_at = z_at + n * (size_t)sh.c * sizeof(E2);
-    std::vector<char> stage(w_at + nw * sizeof(E2));
-    memcpy(stage.data(), root, 32);
-    CombineDesc* hd = reinterpret_cast<CombineDesc*>(stage.data() + desc_at);
-    E2* hy = reinterpret_cast<E2*>(stage.data() + y_at);
-    E2* hz = reinterpret_cast<E2*>(stage.data() + z_at);
-    E2* hw = reinterpret_cast<E2*>(stage.data() + w_at);
-    hd[0].row0 = 0; hd[0].nrows = R; hd[0].woff = 0;
-    memcpy(hw, rho.data(), R * sizeof(E2));
-    size_t off = R;
-    for (size_t i = 0; i < n; i++) {
-        const Claim& cl = claims[i];
-        const std::vector<E2> w = eq_table(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
-        hd[i + 1].row0 = sh.off[cl.table]; hd[i + 1].nrows = w.size(); hd[i + 1].woff = off;
-        memcpy(hw + off, w.data(), w.size() * sizeof(E2));
-        off += w.size();
-        hy[i] = cl.value;
-        memcpy(hz + i * (size_t)sh.c, cl.point.data(), (size_t)sh.c * sizeof(E2));
-    }
+    // the member's descriptor and its block in one staged copy
+    const size_t nw = weights_of(sh, claims);
+    VbMember desc{};   // (every offset into the set and the arena buffers is 0)
+    desc.n = n;
+    std::vector<char> stage(member_block_layout(desc, sh, n, nw, sizeof(VbMember)));
+    static_assert(sizeof(VbMember) % 16 == 0, "the block starts at a multiple of 16");
+    memcpy(stage.data(), &desc, sizeof(VbMember));
+    FsTranscript tr = member_block_fill(stage.data(), desc, sh, root, claims, Q);
     const bool four_step = depth >= 8 && depth <= 16;
     u64 *d_proof, *d_u, *d_cols, *d_enc, *d_scratch = nullptr, *d_W, *d_leaves, *d_js, *d_cells;
     char* d_stage;
@@ -663,25 +608,21 @@ std::string verify_device(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], 
     } catch (const std::exception& e) {
         throw Error(std::string("the context's arena cannot hold the opening (") + e.what() + ")");
     }
-    struct Drain {   // an error between the first enqueue and the synchronisation must not leave copies of dead host buffers behind
-        hipStream_t st; bool armed = true;
-        ~Drain() { if (armed) (void)hipStreamSynchronize(st); }
-    } drain{st};
+    DrainOne drain{st};   // (drains on an error; after the synchronisation below its own is one more, on an idle stream)
     const int cls = ctx->prof_class("pcs_verify", false);
     ctx->prof_stream = st;
-    const CombineDesc* d_jobs = reinterpret_cast<const CombineDesc*>(d_stage + desc_at);
-    const u64* d_root = reinterpret_cast<const u64*>(d_stage);
+    const VbMember* d_mem = reinterpret_cast<const VbMember*>(d_stage);
+    const VbGroup vg{1, (u64)Q, (u64)R, (u64)q_words, sh.c, depth};
     hip_check(hipMemcpyAsync(d_proof, proof, len, hipMemcpyHostToDevice, st), "upload opening");
     hip_check(hipMemcpyAsync(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, st), "upload claims");
     hip_check(hipMemsetAsync(d_cells, 0xff, 32, st), "memset");
     hip_check(hipMemsetAsync(d_enc, 0, 2 * njobs * N * 8, st), "memset");
     ctx->prof_begin(cls, (double)(u_words + Q * R) * 24);
-    k_pcsv_canon<<<(unsigned)std::min<size_t>(blocks_for(u_words + Q * R), 4096), PCS_TPB, 0, st>>>(d_proof, u_words, Q, R, q_words, sh.c, d_u, d_cols, d_enc, d_cells);
+    k_pcsvb_canon<<<(unsigned)std::min<size_t>(blocks_for(u_words + Q * R), 4096), PCS_TPB, 0, st>>>(d_proof, d_mem, vg, d_u, d_cols, d_enc, d_cells);
     ctx->prof_end();
     if (n) {
         ctx->prof_begin(cls, (double)n * C * 16);
-        k_pcsv_eval<<<(unsigned)n, PCS_TPB, 0, st>>>(reinterpret_cast<const E2*>(d_u), sh.c, reinterpret_cast<const E2*>(d_stage + z_at),
-                                                     reinterpret_cast<const E2*>(d_stage + y_at), d_cells);
+        k_pcsvb_eval<<<(unsigned)n, PCS_TPB, 0, st>>>(d_mem, 1, sh.c, d_u, d_stage, d_cells);
         ctx->prof_end();
     }
     ctx->prof_begin(cls, (double)njobs * N * 64);
@@ -689,10 +630,10 @@ std::string verify_device(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], 
     dev::ntt_batch(st, d_enc, depth, 2 * njobs, d_W, 1, d_scratch);
     ctx->prof_end();
     ctx->prof_begin(cls, (double)Q * R * 8);
-    k_pcsv_leaf<<<blocks_for(Q), PCS_TPB, 0, st>>>(d_cols, Q, R, d_leaves);
+    k_pcsvb_leaf<<<blocks_for(Q), PCS_TPB, 0, st>>>(d_mem, vg, d_cols, d_leaves);
     ctx->prof_end();
     ctx->prof_begin(cls, (double)Q * nw * 24);
-    k_pcsv_dots<<<blocks_for(Q * njobs), PCS_TPB, 0, st>>>(d_cols, Q, R, d_jobs, njobs, reinterpret_cast<const E2*>(d_stage + w_at), d_s);
+    k_pcsvb_dots<<<blocks_for(Q * njobs), PCS_TPB, 0, st>>>(d_mem, vg, Q * njobs, d_cols, d_stage, d_s);
     ctx->prof_end();
     // the host's share, beside the kernels: the u_i into the transcript, the column indices out of it
     std::vector<u64> words(u_words);
@@ -702,23 +643,14 @@ std::string verify_device(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], 
     const std::vector<u64> hj(js.begin(), js.end());
     hip_check(hipMemcpyAsync(d_js, hj.data(), Q * 8, hipMemcpyHostToDevice, st), "upload column indices");
     ctx->prof_begin(cls, (double)Q * (32.0 * depth + 48.0 * njobs));
-    k_pcsv_query<<<blocks_for(Q), PCS_TPB, 0, st>>>(d_proof, u_words, q_words, Q, R, depth, d_leaves, d_s, d_enc, n, d_js, d_root, d_cells);
+    k_pcsvb_query<<<blocks_for(Q), PCS_TPB, 0, st>>>(d_proof, d_mem, vg, d_leaves, d_s, d_enc, d_js, d_stage, d_cells);
     ctx->prof_end();
     u64 cells[4];
     hip_check(hipMemcpyAsync(cells, d_cells, 32, hipMemcpyDeviceToHost, st), "download verdict");
-    const hipError_t synced = hipStreamSynchronize(st);
-    drain.armed = false;
-    hip_check(synced, "hg_pcs_verify_device: sync");
+    hip_check(hipStreamSynchronize(st), "hg_pcs_verify_device: sync");
     hip_check(hipGetLastError(), "hg_pcs_verify_device: launch");
     ctx->prof_collect();
-    // the host's order: a non-canonical word, the lowest claim whose evaluation fails, the lowest failing query
-    if (cells[0] != PCSV_NONE) return reason_noncanonical((size_t)cells[0]);
-    if (cells[1] != PCSV_NONE) return reason_evaluation((size_t)cells[1]);
-    if (cells[2] != PCSV_NONE) {
-        const size_t q = (size_t)(cells[2] / (n + 2)), kind = (size_t)(cells[2] % (n + 2));
-        return kind == 0 ? reason_merkle(q) : kind == 1 ? reason_proximity(q) : reason_claim(kind - 2, q);
-    }
-    return "";
+    return cells_reason(cells, n);
 }
 
 // hg_pcs_verify_device_batch. The items whose length is right are cut into groups (the option verify_batch_group, VB_PCS_BUDGET,
@@ -765,10 +697,7 @@ std::vector<std::string> verify_device_batch(const char* who_c, hg_ctx* ctx, con
     VerifyBatchBufs* B = batch_bufs(ctx);
     hipStream_t st = ctx->stream;
     std::vector<u64> hj, cells;   // (declared ahead of the guard: copies of them may be queued when it drains)
-    struct Drain {   // every way out, an error included: no copy of a dead host buffer, no kernel on the arena or a set left behind
-        hipStream_t a, b;
-        ~Drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); }
-    } drain{st, B->up};
+    DrainOne drain_up{B->up}, drain{st};   // (the upload stream as well: no kernel on a set left behind)
     hip_check(hipStreamSynchronize(st), (who + ": synchronise").c_str());   // (the arena is reset below)
     [[maybe_unused]] const int nthr = std::max(1, hg_omp_threads());        // (the device pass of hipcc ignores the pragmas)
     const int cls = ctx->prof_class("pcs_verify_batch", false);
@@ -807,17 +736,11 @@ std::vector<std::string> verify_device_batch(const char* who_c, hg_ctx* ctx, con
             const VerifyItem& it = items[good[groups[g].first + m]];
             x.idx = good[groups[g].first + m];
             x.n = it.claims->size();
-            x.nw = R;
-            for (const Claim& cl : *it.claims) x.nw += (size_t)1 << (sh.nvars[cl.table] - sh.c);
+            x.nw = weights_of(sh, *it.claims);
             VbMember& d = desc[m];
             d.proof = poff[m]; d.u = u_at; d.cols = m * Q * R; d.enc_row = row_at;
             d.n = x.n; d.claim0 = claim_at; d.job0 = claim_at + m;
-            d.root_at = at;
-            d.jobs_at = d.root_at + 32;
-            d.y_at = d.jobs_at + (((x.n + 1) * sizeof(CombineDesc) + 15) & ~(size_t)15);
-            d.z_at = d.y_at + x.n * sizeof(E2);
-            d.w_at = d.z_at + x.n * (size_t)sh.c * sizeof(E2);
-            at = d.w_at + x.nw * sizeof(E2);
+            at = member_block_layout(d, sh, x.n, x.nw, at);
             u_at += 2 * C * (x.n + 1);
             row_at += rows_of(x.n);
             claim_at += x.n;
@@ -830,26 +753,7 @@ std::vector<std::string> verify_device_batch(const char* who_c, hg_ctx* ctx, con
             Member& x = mem[mq];
             try {
                 const VerifyItem& it = items[x.idx];
-                const VbMember& d = desc[mq];
-                x.tr = start_transcript(sh, it.root, *it.claims, Q);
-                const std::vector<E2> rho = rho_powers(x.tr.squeeze(), R);
-                memcpy(h_stage + d.root_at, it.root, 32);
-                CombineDesc* hd = reinterpret_cast<CombineDesc*>(h_stage + d.jobs_at);
-                E2* hy = reinterpret_cast<E2*>(h_stage + d.y_at);
-                E2* hz = reinterpret_cast<E2*>(h_stage + d.z_at);
-                E2* hw = reinterpret_cast<E2*>(h_stage + d.w_at);
-                hd[0].row0 = 0; hd[0].nrows = R; hd[0].woff = 0;
-                memcpy(hw, rho.data(), R * sizeof(E2));
-                size_t off = R;
-                for (size_t i = 0; i < x.n; i++) {
-                    const Claim& cl = (*it.claims)[i];
-                    const std::vector<E2> w = eq_table(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
-                    hd[i + 1].row0 = sh.off[cl.table]; hd[i + 1].nrows = w.size(); hd[i + 1].woff = off;
-                    memcpy(hw + off, w.data(), w.size() * sizeof(E2));
-                    off += w.size();
-                    hy[i] = cl.value;
-                    memcpy(hz + i * (size_t)sh.c, cl.point.data(), (size_t)sh.c * sizeof(E2));
-                }
+                x.tr = member_block_fill(h_stage, desc[mq], sh, it.root, *it.claims, Q);
             } catch (const std::exception& e) { x.error = e.what(); }
         }
         for (const Member& x : mem)
@@ -937,77 +841,9 @@ std::vector<std::string> verify_device_batch(const char* who_c, hg_ctx* ctx, con
         t_stage = t5 - t4;
         hip_check(hipGetLastError(), (who + ": launch").c_str());
         ctx->prof_collect();
-        // per member, the host's order: a non-canonical word, the lowest claim whose evaluation fails, the lowest failing query
-        for (size_t m = 0; m < G; m++) {
-            const u64* cm = cells.data() + 3 * m;
-            const size_t n = mem[m].n;
-            std::string& out = why[mem[m].idx];
-            if (cm[0] != PCSV_NONE) out = reason_noncanonical((size_t)cm[0]);
-            else if (cm[1] != PCSV_NONE) out = reason_evaluation((size_t)cm[1]);
-            else if (cm[2] != PCSV_NONE) {
-                const size_t q = (size_t)(cm[2] / (n + 2)), kind = (size_t)(cm[2] % (n + 2));
-                out = kind == 0 ? reason_merkle(q) : kind == 1 ? reason_proximity(q) : reason_claim(kind - 2, q);
-            }
-        }
+        for (size_t m = 0; m < G; m++) why[mem[m].idx] = cells_reason(cells.data() + 3 * m, mem[m].n);
     }
     return why;
-}
-
-// ---- a run of commitments (commit_device_batch): the kernels of commit_device with a member in front of every index. The members
-// of a group share the shape; member m's raw rows lie at rows + m R C, its encoded rows at M + m R N (so the encoding is one
-// ntt_batch over G R rows) and its tree at trees + m tree_words. Every grid is one-dimensional over (member, item).
-__global__ __launch_bounds__(PCS_TPB) void k_pcsb_stage(const u64* __restrict__ rows, u64* __restrict__ M, size_t G, size_t R, int c, unsigned* __restrict__ flags) {
-    const size_t per = R << (c + 2), total = G * per;
-    const size_t C = (size_t)1 << c, Nm = ((size_t)4 << c) - 1;
-    for (size_t i = (size_t)blockIdx.x * PCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * PCS_TPB) {
-        const size_t m = i / per, k = i - m * per, r = k >> (c + 2), j = k & Nm;
-        u64 v = 0;
-        if (j < C) {
-            v = rows[((m * R + r) << c) + j];
-            if (v >= GL_P) atomicOr(flags + m, 1u);   // one flag a member
-        }
-        M[i] = v;
-    }
-}
-// One thread per (member m, column j), id = m N + j: k_pcs_leaf_hash on the member's own matrix, into the leaves of its own tree
-__global__ __launch_bounds__(PCS_TPB) void k_pcsb_leaf_hash(const u64* __restrict__ M, size_t G, size_t N, size_t R, u64* __restrict__ trees, size_t tree_words) {
-    const size_t id = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
-    if (id >= G * N) return;
-    const size_t m = id / N, j = id - m * N;
-    u64 a[25];
-    leaf_absorb(M + m * R * N + j, N, R, a);
-    u64* out = trees + m * tree_words + 4 * j;
-    out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
-}
-// One thread per (member, node) of one level: `count` nodes over the 2 * count nodes at word below_at of every tree
-__global__ __launch_bounds__(PCS_TPB) void k_pcsb_merkle(u64* __restrict__ trees, size_t tree_words, size_t below_at, size_t count, size_t G) {
-    const size_t id = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
-    if (id >= G * count) return;
-    const size_t m = id / count;
-    u64* below = trees + m * tree_words + below_at;
-    merkle_node(below, below + 8 * count, id - m * count);
-}
-// One workgroup per member (blockIdx.x): k_pcs_merkle_top on its tree
-__global__ __launch_bounds__(PCS_TPB) void k_pcsb_merkle_top(u64* __restrict__ trees, size_t tree_words, size_t below_at, size_t count) {
-    u64* below = trees + (size_t)blockIdx.x * tree_words + below_at;
-    while (count >= 1) {
-        u64* here = below + 8 * count;
-        if (threadIdx.x < count) merkle_node(below, here, threadIdx.x);
-        __syncthreads();
-        below = here;
-        count >>= 1;
-    }
-}
-
-// merkle_levels_device for the G trees at trees + m tree_words: one launch a level over every (member, node) while a level has more
-// than PCS_TPB nodes, then one workgroup a member
-void merkle_levels_device_batch(hipStream_t st, u64* d_trees, size_t tree_words, size_t N, size_t G) {
-    size_t below_at = 0, count = N / 2;
-    for (; count > (size_t)PCS_TPB; count >>= 1) {
-        k_pcsb_merkle<<<blocks_for(G * count), PCS_TPB, 0, st>>>(d_trees, tree_words, below_at, count, G);
-        below_at += 8 * count;
-    }
-    k_pcsb_merkle_top<<<(unsigned)G, PCS_TPB, 0, st>>>(d_trees, tree_words, below_at, count);
 }
 
 // hg_pcs_commit_batch. A group: one allocation for its members' raw and encoded rows, the tables uploaded straight into it, then
@@ -1056,14 +892,14 @@ std::vector<Commitment*> commit_device_batch(const char* who_c, hg_ctx* ctx, con
                 hip_check(hipMemcpyAsync(d_rows + (m * R + sh.off[t]) * C, tables[(first + m) * nt + t], ((size_t)8) << sh.nvars[t], hipMemcpyHostToDevice, st), "upload tables");
         const double t2 = omp_get_wtime();
         ctx->prof_begin(cls, (double)G * R * (C + N) * 8);
-        k_pcsb_stage<<<(unsigned)std::min<size_t>(blocks_for(G * R * N), 4096), PCS_TPB, 0, st>>>(d_rows, d_M, G, R, sh.c, d_flags);
+        k_pcsb_stage<<<dim3((unsigned)std::min<size_t>(blocks_for(R * N), (4096 + G - 1) / G), (unsigned)G), PCS_TPB, 0, st>>>(d_rows, d_M, R, sh.c, d_flags);   // about 4096 workgroups in all; G in the grid's y: cut_groups keeps it at VB_MAX_GROUP = 64 or below
         ctx->prof_end();
         ctx->prof_begin(cls, (double)G * R * N * 32);
         dev::powers_table(st, W, root_of_unity(log2n), N);
         dev::ntt_batch(st, d_M, log2n, G * R, W, 1, scratch);
         ctx->prof_end();
         ctx->prof_begin(cls, (double)G * R * N * 8);
-        k_pcsb_leaf_hash<<<blocks_for(G * N), PCS_TPB, 0, st>>>(d_M, G, N, R, d_out, tree_words);
+        k_pcsb_leaf_hash<<<blocks_for(G * N), PCS_TPB, 0, st>>>(d_M, G, log2n, R, d_out, tree_words);
         ctx->prof_end();
         ctx->prof_begin(cls, (double)G * N * 96);
         merkle_levels_device_batch(st, d_out, tree_words, N, G);
@@ -1096,81 +932,6 @@ std::vector<Commitment*> commit_device_batch(const char* who_c, hg_ctx* ctx, con
     std::vector<Commitment*> out;
     for (auto& cm : made) out.push_back(cm.release());
     return out;
-}
-
-// ---- a run of openings (open_device_batch). What differs by item lies in three flat tables of the group's staged copy: a job a row
-// combination (the proximity combination and one a claim, every member's behind the other), a claim an evaluation check, a member
-// where its matrix, its u vectors and its opening image lie. Every grid is one-dimensional.
-struct ObJob { const u64* src; u64 nrows, w_at, u_at; };     // its first raw row; the byte offset of its weights in the staged copy; where u goes (elements)
-struct ObClaim { u64 u_at, z_at, y_at, member, claim; };      // its u_i (elements); byte offsets of the low coordinates and of the value
-struct ObMember { const u64* M; u64 img, u, u_words; };       // its encoded matrix; word offsets of its image and of its u vectors; 2 C (n + 1)
-
-// k_pcs_combine driven by the job table: block b serves job b / cb, columns (b % cb) PCS_TPB ..
-__global__ __launch_bounds__(PCS_TPB) void k_pcsob_combine(int c, unsigned cb, const ObJob* __restrict__ jobs, const char* __restrict__ stage, E2* __restrict__ u) {
-    const size_t C = (size_t)1 << c;
-    const unsigned jq = blockIdx.x / cb;
-    const size_t j = (size_t)(blockIdx.x - jq * cb) * PCS_TPB + threadIdx.x;
-    if (j >= C) return;
-    const ObJob job = jobs[jq];
-    const u64* src = job.src + j;
-    const E2* wq = reinterpret_cast<const E2*>(stage + job.w_at);
-    u64 s0 = 0, s1 = 0;
-    for (u64 r0 = 0; r0 < job.nrows; r0 += COMBINE_CHUNK) {
-        const u64 r1 = r0 + COMBINE_CHUNK < job.nrows ? r0 + COMBINE_CHUNK : job.nrows;
-        WAcc A = wacc_zero(), B = wacc_zero();
-        for (u64 r = r0; r < r1; r++) {
-            const u64 x = src[r << c];
-            const E2 wr = wq[r];
-            wmac2(A, x, wr.c0, B, x, wr.c1);
-        }
-        s0 = gl_add(s0, wreduce(A));
-        s1 = gl_add(s1, wreduce(B));
-    }
-    u[job.u_at + j] = e2(s0, s1);
-}
-// One workgroup per (member, claim), the arithmetic of k_pcsvb_eval: <u_i, eq(z_i[..c])> == y_i; cells[member] = its lowest failing claim
-__global__ __launch_bounds__(PCS_TPB) void k_pcsob_eval(const ObClaim* __restrict__ claims, int c, const E2* __restrict__ u, const char* __restrict__ stage,
-                                                        u64* __restrict__ cells) {
-    __shared__ E2 part[PCS_TPB];
-    const ObClaim cl = claims[blockIdx.x];
-    const size_t C = (size_t)1 << c;
-    const E2* z = reinterpret_cast<const E2*>(stage + cl.z_at);
-    const E2* ui = u + cl.u_at;
-    const int lob = c < 8 ? c : 8;
-    E2 f = e2_one();
-    for (int b = 0; b < lob; b++) f = e2_mul(f, (threadIdx.x >> b) & 1 ? z[b] : e2_sub(e2_one(), z[b]));
-    E2 s = e2_zero();
-    for (size_t x = threadIdx.x; x < C; x += PCS_TPB) {
-        E2 gq = f;
-        for (int b = 8; b < c; b++) gq = e2_mul(gq, (x >> b) & 1 ? z[b] : e2_sub(e2_one(), z[b]));
-        s = e2_add(s, e2_mul(ui[x], gq));
-    }
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int h = PCS_TPB / 2; h >= 1; h >>= 1) {
-        if (threadIdx.x < h) part[threadIdx.x] = e2_add(part[threadIdx.x], part[threadIdx.x + h]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && !e2_eq(part[0], *reinterpret_cast<const E2*>(stage + cl.y_at))) cell_min(cells + cl.member, cl.claim);
-}
-// Word i of the group's u vectors, big-endian, into its member's image: the member is the last one whose u offset is <= i
-__global__ __launch_bounds__(PCS_TPB) void k_pcsob_emit(const ObMember* __restrict__ mem, unsigned G, size_t total, const u64* __restrict__ u, u64* __restrict__ img) {
-    for (size_t i = (size_t)blockIdx.x * PCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * PCS_TPB) {
-        unsigned lo = 0, hi = G;
-        while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].u <= i) lo = mid; else hi = mid; }
-        img[mem[lo].img + (i - mem[lo].u)] = __builtin_bswap64(u[i]);
-    }
-}
-// One thread per (member m, query q, row r), id = (m Q + q) R + r: M_m[r][j_q] big-endian at its place in the member's image.
-// js[m Q + q] = j_q (masked by the host); js[G Q + m] != 0: the member takes part (it was not refused)
-__global__ __launch_bounds__(PCS_TPB) void k_pcsob_gather(const ObMember* __restrict__ mem, size_t G, size_t Q, size_t R, size_t N, size_t q_words,
-                                                          const u64* __restrict__ js, u64* __restrict__ img) {
-    const size_t id = (size_t)blockIdx.x * PCS_TPB + threadIdx.x;
-    if (id >= G * Q * R) return;
-    const size_t m = id / (Q * R), k = id - m * Q * R, q = k / R, r = k - q * R;
-    if (!js[G * Q + m]) return;
-    const ObMember M = mem[m];
-    img[M.img + M.u_words + q * q_words + r] = __builtin_bswap64(M.M[r * N + js[m * Q + q]]);
 }
 
 // hg_pcs_open_batch. A group: the host threads write every member's transcript start, rho powers, weight tables and table entries into

@@ -1,5 +1,5 @@
-// Keccak-f[1600] on the device with the whole state in registers, and the inner node of the commitment's Merkle tree: shared by the
-// column-hash and tree kernels of both fields (pcs.hip: Goldilocks words, bn254_pcs.inc: 32-byte Fr elements; a node is 32 bytes
+// Keccak-f[1600] on the device with the whole state in registers, the inner node of the commitment's Merkle tree and the climb of an
+// opened column's path: shared by the column-hash, tree and query kernels of both fields (pcs.hip: Goldilocks words, bn254_pcs.inc: 32-byte Fr elements; a node is 32 bytes
 // either way).
 #pragma once
 #include <stdint.h>
@@ -55,6 +55,24 @@ __device__ __forceinline__ void merkle_node(const u64* below, u64* here, size_t 
     keccak_f(a);
     u64* out = here + 4 * i;
     out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
+}
+// The path of column j from its leaf hash h up to the root, which replaces h: level l's sibling is the 4 words at sib + 4l, and
+// bit l of j says on which side it lies
+__device__ __forceinline__ void merkle_climb(u64 (&h)[4], const u64* __restrict__ sib, size_t j, int depth) {
+    for (int l = 0; l < depth; l++) {
+        const bool right = (j >> l) & 1;   // this node is the right child
+        const u64 t0 = sib[4 * l], t1 = sib[4 * l + 1], t2 = sib[4 * l + 2], t3 = sib[4 * l + 3];
+        u64 a[25];
+        a[0] = 1;
+        a[1] = right ? t0 : h[0]; a[2] = right ? t1 : h[1]; a[3] = right ? t2 : h[2]; a[4] = right ? t3 : h[3];
+        a[5] = right ? h[0] : t0; a[6] = right ? h[1] : t1; a[7] = right ? h[2] : t2; a[8] = right ? h[3] : t3;
+        a[9] = 0x01;
+#pragma unroll
+        for (int k = 10; k < 25; k++) a[k] = 0;
+        a[RATE_WORDS - 1] = 0x8000000000000000ull;
+        keccak_f(a);
+        h[0] = a[0]; h[1] = a[1]; h[2] = a[2]; h[3] = a[3];
+    }
 }
 
 }  // namespace pcs

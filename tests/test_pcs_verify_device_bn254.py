@@ -229,7 +229,9 @@ def test_two_reduction_chunks_of_the_largest_elements(ctx):
 
 @pytest.mark.gpu
 def test_one_query_past_a_workgroup(ctx):
-    """R = 129, Q = 257: one query past a workgroup of 256, with duplicate indices at code length 16"""
+    """R = 129, Q = 257: one query past a workgroup of 256, with duplicate indices at code length 16. The single entry launches the
+    inner-product kernel of the batch form: two workgroups a job here, and Q no multiple of 64 (every weight table is a part of one
+    reduction chunk of 1024 rows at this R; two whole chunks with two workgroups a job are the case below)"""
     nvars, Q = [9, 2], 257
     tables = tb.make_tables(nvars, 0xd129)
     cm = hg.Commitment.commit_bn254(None, tables, 2)
@@ -239,6 +241,20 @@ def test_one_query_past_a_workgroup(ctx):
     assert len(proof) == cols_at + Q * qb
     assert both(ctx, cm.root, nvars, claims, proof, Q, 2) == (True, "")
     assert both(ctx, cm.root, nvars, claims, flip(proof, cols_at + 256 * qb + 32 * (Rn - 1) + 31), Q, 2) == (False, "pcs: Merkle path mismatch at query 256")
+
+
+@pytest.mark.gpu
+def test_two_workgroups_a_job_over_two_reduction_chunks(ctx):
+    """nvars [13] at c = 2, Q = 257: R = 2048, so the column's job and the claim's are two whole chunks of 1024 rows each, and every
+    job takes two workgroups, the second with one query"""
+    nvars, Q = [13], 257
+    tables = tb.make_tables(nvars, 0xd257)
+    cm = hg.Commitment.commit_bn254(None, tables, 2)
+    claims = tb.make_claims(tables, 1, 13)
+    proof = cm.open(claims, Q)
+    assert both(ctx, cm.root, nvars, claims, proof, Q, 2) == (True, "")
+    bad = flip(proof, last_column_element(nvars, 2, 1, Q) + 31)
+    assert both(ctx, cm.root, nvars, claims, bad, Q, 2) == (False, "pcs: Merkle path mismatch at query 256")
 
 
 def checker(ctx, nvars, Q):
