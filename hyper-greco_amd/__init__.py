@@ -56,7 +56,7 @@ EXPORTS = [
     "hg_pcs_commit", "hg_pcs_free", "hg_pcs_open", "hg_pcs_verify", "hg_secrets_commit", "hg_claims_open", "hg_claims_verify",
     "hg_pcs_verify_device", "hg_claims_verify_device", "hg_pcs_verify_device_batch", "hg_claims_verify_batch",
     "hg_pcs_commit_batch", "hg_secrets_commit_batch", "hg_pcs_open_batch", "hg_claims_open_batch",
-    "hg_secrets_commit_values", "hg_prove_encryptions_committed",
+    "hg_secrets_commit_values", "hg_prove_encryptions_committed", "hg_prove_encryptions_committed_bn254",
     "hg_pcs_commit_bn254", "hg_pcs_open_bn254", "hg_pcs_verify_bn254", "hg_secrets_commit_bn254", "hg_claims_open_bn254", "hg_claims_verify_bn254",
     "hg_pcs_verify_device_bn254", "hg_claims_verify_device_bn254", "hg_pcs_verify_device_batch_bn254", "hg_claims_verify_batch_bn254",
     "hg_pcs_commit_batch_bn254", "hg_secrets_commit_batch_bn254", "hg_pcs_open_batch_bn254", "hg_claims_open_batch_bn254",
@@ -113,8 +113,8 @@ def _two_field_protos(L):
     L.hg_secrets_commit_batch.argtypes = L.hg_secrets_commit_batch_bn254.argtypes = [vp, C.POINTER(HgParams), C.POINTER(vp), sz, sz, C.POINTER(vp), u8p]
     L.hg_secrets_commit_values.argtypes = [vp, vp, vp, sz, C.POINTER(vp), u8p]   # ctx, key, values, log2_row, handle out, root out
     pp = C.POINTER(i64p)
-    L.hg_prove_encryptions_committed.argtypes = [vp, vp, pp, pp, pp, pp, sz, sz, vp, sz, szp, C.POINTER(ci), C.POINTER(vp), u8p, C.POINTER(vp), cp, sz,
-                                                 C.POINTER(HgTimings)]
+    L.hg_prove_encryptions_committed.argtypes = L.hg_prove_encryptions_committed_bn254.argtypes = [
+        vp, vp, pp, pp, pp, pp, sz, sz, vp, sz, szp, C.POINTER(ci), C.POINTER(vp), u8p, C.POINTER(vp), cp, sz, C.POINTER(HgTimings)]
     opened = [szp, sz, sz, u8p, sz, szp, C.POINTER(ci), cp, sz]   # claim counts, n_queries, n, openings, cap_each, lengths, status, reasons, reason_cap
     L.hg_pcs_open_batch.argtypes = L.hg_pcs_open_batch_bn254.argtypes = [vp, C.POINTER(vp), C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u64p)] + opened
     L.hg_claims_open_batch.argtypes = L.hg_claims_open_batch_bn254.argtypes = [vp, C.POINTER(HgParams), C.POINTER(vp), vp, sz, u64p, sz] + opened
@@ -647,6 +647,18 @@ def prove_encryptions_committed(ctx, pk, encs, log2_row=0, cap_each=1 << 20, wit
     (what Commitment.from_values gives for its tables), made inside the pipeline. Returns (proofs, statuses, reasons, commitments,
     roots, witnesses, timings): commitments[i] is None and roots[i] 32 zero bytes for a refused item; timings["upload_ms"] is the
     commits' device time."""
+    return _prove_encryptions_committed("goldilocks", ctx, pk, encs, log2_row, cap_each, witnesses, reason_cap)
+
+
+def prove_encryptions_committed_bn254(ctx, pk, encs, log2_row=0, cap_each=1 << 24, witnesses=False, reason_cap=256):
+    """hg_prove_encryptions_committed_bn254: prove_encryptions_bn254 with a BN254 device Commitment to the five secret inputs of every
+    proven item (what Commitment.secrets_bn254 gives for the item's witness), made inside the pipeline from the tables in HBM. The
+    7-tuple of prove_encryptions_committed; the commitments have field "bn254"."""
+    return _prove_encryptions_committed("bn254", ctx, pk, encs, log2_row, cap_each, witnesses, reason_cap)
+
+
+def _prove_encryptions_committed(field, ctx, pk, encs, log2_row, cap_each, witnesses, reason_cap):
+    fn = lib().hg_prove_encryptions_committed_bn254 if field == "bn254" else lib().hg_prove_encryptions_committed
     n = len(encs)
     arrs = [_encryption_arrays(pk.params, *enc) for enc in encs]
     cols = [(i64p * max(n, 1))(*[x[f].ctypes.data_as(i64p) for x in arrs]) for f in range(4)]
@@ -658,7 +670,7 @@ def prove_encryptions_committed(ctx, pk, encs, log2_row=0, cap_each=1 << 20, wit
     hs = (C.c_void_p * max(n, 1))() if witnesses else None
     reasons = C.create_string_buffer(max(n, 1) * reason_cap)
     tm = HgTimings()
-    rc = lib().hg_prove_encryptions_committed(_h(ctx), pk.h, *cols, n, log2_row, buf, cap_each, lens, status, cms, rts, hs, reasons, reason_cap, C.byref(tm))
+    rc = fn(_h(ctx), pk.h, *cols, n, log2_row, buf, cap_each, lens, status, cms, rts, hs, reasons, reason_cap, C.byref(tm))
     if rc < 0:
         raise HgError(lib().hg_last_error().decode())
     raw, rr = memoryview(buf), reasons.raw
@@ -668,7 +680,7 @@ def prove_encryptions_committed(ctx, pk, encs, log2_row=0, cap_each=1 << 20, wit
     nvars = _secrets_nvars(pk.params)
     c = pcs_row_log2(nvars, log2_row)
     roots = [bytes(rts[32 * i:32 * i + 32]) for i in range(n)]
-    commitments = [Commitment(C.c_void_p(cms[i]), roots[i], ctx, nvars, c) if cms[i] else None for i in range(n)]
+    commitments = [Commitment(C.c_void_p(cms[i]), roots[i], ctx, nvars, c, field) if cms[i] else None for i in range(n)]
     return proofs, [int(status[i]) for i in range(n)], why, commitments, roots, ws, {f: getattr(tm, f) for f, _ in HgTimings._fields_}
 
 

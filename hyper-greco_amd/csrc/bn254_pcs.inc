@@ -364,6 +364,81 @@ pcs::Commitment* pcs_commit_device(const char* who, hg_ctx* ctx, const pcs::Shap
     return cm.release();
 }
 
+// ---- a commitment to witness words that lie in HBM already (pcs_commit_words_enqueue: the encryption pipeline): k_bnpcs_lift and
+// k_bnpcsb_stage in one pass over the source tables, pcs::k_pcs_stage_tables over Fr. A thread moves a unit of two words (one 16-byte
+// load); a row has U = C / 2 units; 2^lanes_log2 = min(BNPCS_TPB, U) threads work on a row, so a workgroup holds
+// BNPCS_TPB >> lanes_log2 rows at a time, and a row of more than BNPCS_TPB units is walked in U >> lanes_log2 steps of which every
+// workgroup of the row takes `split`-th part. The table of a row is looked up once a row from the descriptor in the kernel
+// arguments. Per unit: the word test, the signed lift of both words, the two canonical elements (64 bytes) into the raw row and
+// into the row of M, and twelve 16-byte zero stores into the 3C elements of padding behind them, unit-strided, so that the lanes
+// of a wavefront write adjacent 16 bytes there and adjacent elements elsewhere. 16 bytes in and 320 out a unit (the two-kernel path: 80 in, 320 out); no LDS.
+struct BnStageWords {
+    const u64* src[pcs::MAX_TABLES];
+    unsigned off[pcs::MAX_TABLES + 1];   // first row of table t; off[nt] = R
+    unsigned nt;
+};
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcs_stage_words(const BnStageWords T, Fr* __restrict__ rows, Fr* __restrict__ M, int c, int lanes_log2, int split_log2,
+                                                                 unsigned* __restrict__ flag) {
+    const int u_log2 = c - 1;                                  // log2 of the units in a row
+    const int steps_log2 = u_log2 - lanes_log2 - split_log2;   // steps a workgroup walks along its row(s)
+    const size_t R = T.off[T.nt];
+    const unsigned lane = threadIdx.x & ((1u << lanes_log2) - 1), sub = threadIdx.x >> lanes_log2, rpb = BNPCS_TPB >> lanes_log2;
+    const size_t groups = (R + rpb - 1) / rpb, items = groups << split_log2;
+    const size_t U = (size_t)1 << u_log2;
+    const lz_u32x4 zero = {0, 0, 0, 0};
+    bool bad = false;
+    for (size_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const size_t r = (item >> split_log2) * rpb + sub, part = item & (((size_t)1 << split_log2) - 1);
+        if (r >= R) continue;
+        unsigned t = 0;
+        while (t + 1 < T.nt && T.off[t + 1] <= r) t++;
+        const ulonglong2* src = reinterpret_cast<const ulonglong2*>(T.src[t] + ((r - T.off[t]) << c));
+        Fr* drow = rows + (r << c);
+        Fr* mrow = M + (r << (c + 2));
+        __attribute__((address_space(1))) lz_u32x4* pad = (__attribute__((address_space(1))) lz_u32x4*)(mrow + 2 * U);   // 3C elements = 12 U units of 16 bytes
+        for (size_t s = 0; s < ((size_t)1 << steps_log2); s++) {
+            const size_t u = (((part << steps_log2) + s) << lanes_log2) + lane;
+            const ulonglong2 v = src[u];
+            bad |= v.x >= GL_P || v.y >= GL_P;
+            const Fr a = fr_lift_signed_canon(v.x), b = fr_lift_signed_canon(v.y);
+            lz_gstore(drow + 2 * u, a);
+            lz_gstore(drow + 2 * u + 1, b);
+            lz_gstore(mrow + 2 * u, a);
+            lz_gstore(mrow + 2 * u + 1, b);
+#pragma unroll
+            for (int q = 0; q < 12; q++) pad[(size_t)q * U + u] = zero;
+        }
+    }
+    if (bad) atomicOr(flag, 1u);
+}
+
+void pcs_commit_words_enqueue(hipStream_t st, const pcs::Shape& sh, const u64* const* d_tables, Fr* d_rows, Fr* d_M, Fr* tmp, Fr* W, u64* d_tree, unsigned* d_flag) {
+    const size_t N = sh.N(), R = sh.R, nt = sh.nvars.size();
+    const int log2n = sh.depth();
+    bool fits = nt <= (size_t)pcs::MAX_TABLES && R <= 65535 && sh.c >= 1 && ((uintptr_t)d_rows & 15) == 0 && ((uintptr_t)d_M & 15) == 0;
+    BnStageWords T;
+    for (size_t t = 0; fits && t < nt; t++) {
+        T.src[t] = d_tables[t];
+        T.off[t] = (unsigned)sh.off[t];
+        fits = ((uintptr_t)d_tables[t] & 15) == 0;
+    }
+    if (!fits) throw Error("pcs_commit_words_enqueue: a shape or an alignment the staging kernel does not take");
+    T.off[nt] = (unsigned)R;
+    T.nt = (unsigned)nt;
+    const int u_log2 = sh.c - 1, lanes_log2 = std::min(u_log2, 8);
+    static_assert(BNPCS_TPB == 256, "2^8 threads a workgroup");
+    const size_t groups = (R + (BNPCS_TPB >> lanes_log2) - 1) / (BNPCS_TPB >> lanes_log2);
+    int split_log2 = 0;   // the workgroups of a row: enough of them for about 2048 in all
+    while (split_log2 < u_log2 - lanes_log2 && (groups << split_log2) < 2048) split_log2++;
+    const unsigned grid = (unsigned)std::min<size_t>(groups << split_log2, (size_t)1 << 20);
+    hipc(hipMemsetAsync(d_flag, 0, 4, st), "memset");
+    k_bnpcs_stage_words<<<grid, BNPCS_TPB, 0, st>>>(T, d_rows, d_M, sh.c, lanes_log2, split_log2, d_flag);
+    k_bn_powers<<<bnpcs_blocks(N), 256, 0, st>>>(W, fr_root_of_unity(log2n), N);
+    ntt_batch_dev(st, d_M, tmp, W, log2n, R, nullptr);
+    k_bnpcsb_leaf_hash<<<bnpcs_blocks(N), BNPCS_TPB, 0, st>>>(d_M, 1, log2n, R, d_tree, 8 * N);
+    pcs::merkle_levels_device(st, d_tree, N);
+}
+
 void pcs_combine_device(const pcs::Commitment& cm, const std::vector<PcsJob>& jobs, Fr* u) {
     hg_ctx* ctx = cm.ctx;
     hipc(hipSetDevice(ctx->device), "hipSetDevice");

@@ -266,7 +266,7 @@ static int write_results(const std::vector<std::string>& why, int* results, char
 }
 
 // hg_prove_encryptions*: run(want_witnesses, &total_ms) is the field's pipeline. Historical: the Goldilocks entry also sums gpu_ms and
-// replay_ms into the timings (gpu_timings). cmt (hg_prove_encryptions_committed): the run fills it with every proven item's handle;
+// replay_ms into the timings (gpu_timings). cmt (hg_prove_encryptions_committed[_bn254]): the run fills it with every proven item's handle;
 // commitments and roots are required then, a refused item gets a null handle and a zero root, upload_ms sums the commits' device time.
 static std::vector<uint32_t> secrets_nvars(const Params& p);
 template <class Run>
@@ -1603,6 +1603,22 @@ int hg_prove_encryptions_bn254(hg_ctx* ctx, const hg_pk* pk, const int64_t* cons
                                char* reasons, size_t reason_cap, hg_timings* timings) {
     HG_ENTRY(prove_encryptions_entry("hg_prove_encryptions_bn254", false, ctx, pk, s, e, k1, a, n_enc, proofs, cap_each, lens, status, ws, reasons, reason_cap, timings,
                                      [&](bool want, double* total) { return bn::prove_encryptions_bn254(ctx, pk, s, e, k1, a, n_enc, want, total); }))
+}
+
+int hg_prove_encryptions_committed_bn254(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e, const int64_t* const* k1,
+                                         const int64_t* const* a, size_t n_enc, size_t log2_row, uint8_t* proofs, size_t cap_each, size_t* lens,
+                                         int* status, void** commitments, uint8_t* roots, hg_witness** ws, char* reasons, size_t reason_cap,
+                                         hg_timings* timings) {
+    HG_TRY
+    if (commitments) for (size_t i = 0; i < n_enc; i++) commitments[i] = nullptr;
+    EncCommit cmt;   // (an error of the call drops every handle made so far with it)
+    return prove_encryptions_entry("hg_prove_encryptions_committed_bn254", false, ctx, pk, s, e, k1, a, n_enc, proofs, cap_each, lens, status, ws, reasons, reason_cap,
+                                   timings,
+                                   [&](bool want, double* total) {
+                                       return bn::prove_encryptions_bn254(ctx, pk, s, e, k1, a, n_enc, want, total, "hg_prove_encryptions_committed_bn254", &cmt);
+                                   },
+                                   &cmt, log2_row, commitments, roots);
+    HG_CATCH(-1)
 }
 
 int hg_prove_resident_mode(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, int mode, uint8_t* proof, size_t cap, size_t* len, hg_timings* timings) {

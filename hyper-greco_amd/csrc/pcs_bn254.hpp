@@ -77,5 +77,14 @@ BN_HD Fr fr_lift_signed_canon(u64 v) { return v < (1ULL << 63) ? fr_make(v, 0, 0
 // came in: Montgomery in, Montgomery out; canonical plain words in, canonical plain words out.
 void ntt_batch_dev(hipStream_t st, Fr* a, Fr* tmp, const Fr* W, int log2n, size_t batch, const Fr* scale);
 
+// bn254_pcs.inc: pcs::commit_tables_enqueue over Fr - the whole commit of pcs_commit_device(.., words = true) to m tables of witness
+// words that lie in HBM (d_tables[t]: table t, 2^{v_t} words, 16-byte aligned), enqueued on st: nothing is synchronised and the
+// context's arena is not touched. The caller supplies d_rows (R C elements), d_M (R N), the NTT temporary (R N), W (N: filled here
+// with the Montgomery-form powers of the root), the tree buffer (8 N words: the levels one behind the other) and one flag word,
+// which is set if a word is not below the Goldilocks p (the signed lift is defined for such words only). One kernel,
+// k_bnpcs_stage_words, reads every word once, lifts it and writes the raw row and the zero-padded row of M. Needs c >= 1 and
+// R <= 65535 (ntt_batch_dev)
+void pcs_commit_words_enqueue(hipStream_t st, const pcs::Shape& sh, const u64* const* d_tables, Fr* d_rows, Fr* d_M, Fr* tmp, Fr* W, u64* d_tree, unsigned* d_flag);
+
 }  // namespace bn
 }  // namespace hg

@@ -253,10 +253,13 @@ std::vector<EncResult> prove_encryptions(hg_ctx* ctx, const hg_pk* pk, const int
                                          const int64_t* const* a, size_t n_enc, bool want_w, double* total_ms, const char* who = "hg_prove_encryptions",
                                          EncCommit* cmt = nullptr);
 void enc_pipe_drop(hg_ctx* ctx);
-// the same over bn256::Fr (bn254.hip): EncResult::r holds the proof bytes and prove_ms only
+// the same over bn256::Fr (bn254.hip): EncResult::r holds the proof bytes and prove_ms only. cmt (hg_prove_encryptions_committed_bn254,
+// may be null): the commitment of hg_secrets_commit_bn254 to every item's secret tables as well, made on the feed stream behind the
+// item's node tables from the laid-out u64 tables (bn::pcs_commit_words_enqueue); cms[i] is a BN254 device handle
 namespace bn {
 std::vector<EncResult> prove_encryptions_bn254(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e, const int64_t* const* k1,
-                                               const int64_t* const* a, size_t n_enc, bool want_w, double* total_ms);
+                                               const int64_t* const* a, size_t n_enc, bool want_w, double* total_ms,
+                                               const char* who = "hg_prove_encryptions_bn254", EncCommit* cmt = nullptr);
 void bn_enc_pipe_drop(hg_ctx* ctx);
 }
 // pieces of the derivation both pipelines share (prover.hip): the parameter set as the derive kernels read it (throws for a set the

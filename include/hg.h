@@ -893,7 +893,8 @@ int hg_instance_mle_batch_bn254(hg_ctx* ctx, const void* const* instances, size_
  *   points4 exactly as hg_verify_public_bn254 / hg_verify_public_batch_bn254 return them, with the input-to-table mapping and the -1
  *   cases of hg_claims_open / hg_claims_verify. hg_verify_public_bn254 followed by hg_claims_verify_bn254 against a root the
  *   encryptor published is a BN254 verification that needs no secret. hg_claims_verify_device_bn254 is
- *   hg_pcs_verify_device_bn254 under the same mapping. */
+ *   hg_pcs_verify_device_bn254 under the same mapping. hg_claims_open_bn254 takes a commitment hg_secrets_commit_bn254 or
+ *   hg_secrets_commit_batch_bn254 made, or hg_prove_encryptions_committed_bn254. */
 int hg_pcs_commit_bn254(hg_ctx* ctx, const uint64_t* const* tables4, const uint32_t* nvars, size_t n_tables, size_t log2_row,
                         void** commitment, uint8_t root[32]);
 int hg_pcs_open_bn254(hg_ctx* ctx, const void* commitment, const uint32_t* table, const uint64_t* points4, const uint64_t* values4,
@@ -944,7 +945,8 @@ int hg_claims_verify_batch_bn254(hg_ctx* ctx, const hg_params* params, const uin
  *   hg_pcs_commit_bn254 / hg_secrets_commit_bn254 on the same context gives for that member alone (the same root, tree and matrices;
  *   hg_pcs_open_bn254, hg_claims_open_bn254, the open batch and hg_pcs_free take it), except that a group's matrices share one
  *   allocation: THE MEMORY RETURNS WHEN THE LAST HANDLE OF THE GROUP IS FREED. Every opening is byte for byte what hg_pcs_open_bn254 /
- *   hg_claims_open_bn254 gives for that item alone. The commit pair returns 0, the open pair the number of refused items; n == 0
+ *   hg_claims_open_bn254 gives for that item alone; the open pair also takes the handles of hg_prove_encryptions_committed_bn254,
+ *   mixed with the others in one call. The commit pair returns 0, the open pair the number of refused items; n == 0
  *   returns 0 and writes nothing. What differs from the Goldilocks contract:
  *   - a refused open item (status[i] = 1, lens[i] = 0, its buffer untouched) carries the text hg_pcs_open_bn254 / hg_claims_open_bn254
  *     leaves in hg_last_error for it, the lowest failing claim;
@@ -997,10 +999,45 @@ int hg_claims_open_batch_bn254(hg_ctx* ctx, const hg_params* params, const void*
  *   timings (may be NULL): total_ms = wall clock of the run; prove_ms = sum of the proving spans of the proven items (wall clock,
  *   from the first launch of a prove to its replayed transcript); witness_ms = sum over the proven items of the device time of
  *   upload + derivation + lift + evaluation (HIP events on the stream they run on). upload_ms, gpu_ms, enqueue_ms, sync_ms and
- *   replay_ms have no meaning on this path and are 0. */
+ *   replay_ms have no meaning on this path and are 0.
+ * hg_prove_encryptions_committed_bn254: hg_prove_encryptions_bn254 that also commits to every item's secret inputs, inside the
+ *   pipeline - hg_prove_encryptions_committed over bn256::Fr, with its argument list. Everything hg_prove_encryptions_bn254 does and
+ *   returns, with its checks in its order under this function's name (a refusal's text reads
+ *   "hg_prove_encryptions_committed_bn254: encryption i: .."); proof i is byte-identical to hg_prove_encryptions_bn254's.
+ *   commitments and roots are required when n_enc > 0: commitments[i] is a BN254 device handle of ctx (hg_claims_open_bn254,
+ *   hg_claims_open_batch_bn254, hg_pcs_open_bn254, hg_pcs_open_batch_bn254 and hg_pcs_free take it); its root, the 32 bytes at
+ *   roots + 32 i, and every opening made from it are byte for byte those of the host form hg_secrets_commit_bn254(NULL, params, w_i,
+ *   log2_row, ..) on the witness hg_witness_derive gives for item i: the tables in the order of hg_secrets_commit, the words lifted
+ *   by the signed rule of hg_secrets_commit_bn254. A refused item gets commitments[i] = NULL and 32 zero bytes. ws may be NULL, and
+ *   the entry is made to be called that way: then no table visits the host.
+ *   The commit of item i starts from the laid-out u64 tables of its table set in HBM: one kernel reads every word once, lifts it and
+ *   writes the canonical 32-byte element into the handle's raw row and into the zero-padded row to encode (8 bytes in and 160 out an
+ *   element); the batched Fr NTT, the leaf sponges and the tree follow as in hg_pcs_commit_bn254: nothing crosses the bus but the
+ *   tree. It is enqueued on the feed stream behind the item's node tables, so it runs under the prove of the item before (and of
+ *   item i) and delays neither the event that prove i waits for nor the flag words; the refill of the set two items later is behind
+ *   it on the same stream. The tree and the flag word come back on the copy stream into page-locked staging, one per set, and
+ *   enter the handle once prove i has completed. The commit of an item is enqueued before it is known whether the item is refused;
+ *   a refused item's slot is written again by the next item. The Montgomery-form twiddles, the NTT temporary (rows x code length
+ *   elements: 227 MB at n=32768 k=16) and the two tree buffers belong to the pipeline, not to the arena (every BN254 prove resets
+ *   it); they are sized for the shape in use and rebuilt when it changes. The raw and encoded rows of the items lie in group
+ *   allocations, cut as hg_pcs_commit_batch_bn254 cuts its groups - at most 64 items, "verify_batch_group", its 4.25 GiB budget -
+ *   and taken when a group's first item is filled, from the allocations the context keeps of freed groups where one fits; the
+ *   group's handles share it: THE MEMORY RETURNS WHEN THE LAST HANDLE OF THE GROUP IS FREED (to the context, as for the batch entries).
+ *   All commitments[i] are NULL at entry, as ws[i]. Returns the number of refused encryptions (n_enc == 0 returns 0) or -1, after
+ *   which no handle is alive, in this order: the errors of hg_prove_encryptions_bn254 (commitments and roots count among the null
+ *   arguments); then, ahead of anything enqueued, the log2_row errors of hg_pcs_commit for the shape of the secrets (outside the
+ *   limits, above the smallest table) and ".. more than 65535 rows (choose a larger log2_row)" (the batched Fr NTT takes so many
+ *   at once); during the run a derived word that is not below the Goldilocks p (".. encryption i: a derived table holds a word
+ *   that is not below p"; the signed lift is only defined for such words), which a correct derivation never gives.
+ *   timings: the fields of hg_prove_encryptions_bn254; witness_ms includes the commits' device time; upload_ms = the sum over the
+ *   proven items of the commit's device time alone (HIP events on the stream it runs on). */
 int hg_prove_encryptions_bn254(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e, const int64_t* const* k1,
                                const int64_t* const* a, size_t n_enc, uint8_t* proofs, size_t cap_each, size_t* lens, int* status,
                                hg_witness** ws, char* reasons, size_t reason_cap, hg_timings* timings);
+int hg_prove_encryptions_committed_bn254(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, const int64_t* const* e, const int64_t* const* k1,
+                                         const int64_t* const* a, size_t n_enc, size_t log2_row, uint8_t* proofs, size_t cap_each, size_t* lens,
+                                         int* status, void** commitments, uint8_t* roots, hg_witness** ws, char* reasons, size_t reason_cap,
+                                         hg_timings* timings);
 
 /* profiling: level 0 off, 1 = events around the selected kernel class only, 2 = every class */
 int hg_profile(hg_ctx* ctx, int level);

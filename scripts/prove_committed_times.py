@@ -8,7 +8,11 @@ Both must give identical proofs and roots (asserted before anything is timed). P
 both legs, their ratio, and for leg A the commit's device time per item (timings.upload_ms / n) and gpu_ms / n beside leg B's gpu_ms / n
 (the prove's device time with and without a commit running beside it).
 
-Usage: python scripts/prove_committed_times.py [n k] [--runs 16,64] [--reps 5] [--log2-row 0]"""
+--bn254 runs the same legs over the BN254 entries: A hg_prove_encryptions_committed_bn254(.., ws = NULL), B hg_prove_encryptions_bn254(.., ws)
+followed by hg_secrets_commit_batch_bn254, and hg_prove_encryptions_bn254(.., ws = NULL) alone. That path has no gpu_ms; prove_ms / n (the
+proving spans, wall clock) stands in its place.
+
+Usage: python scripts/prove_committed_times.py [n k] [--runs 16,64] [--reps 5] [--log2-row 0] [--bn254]"""
 import argparse
 import os
 import statistics
@@ -49,7 +53,12 @@ def main():
     ap.add_argument("--runs", default="16,64")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--log2-row", type=int, default=0)
+    ap.add_argument("--bn254", action="store_true")
     args = ap.parse_args()
+    if args.bn254:
+        committed, plain, commit_batch, dev, sfx = hg.prove_encryptions_committed_bn254, hg.prove_encryptions_bn254, hg.Commitment.secrets_batch_bn254, "prove_ms", "_bn254"
+    else:
+        committed, plain, commit_batch, dev, sfx = hg.prove_encryptions_committed, hg.prove_encryptions, hg.Commitment.secrets_batch, "gpu_ms", ""
     runs = [int(x) for x in args.runs.split(",")]
     ctx = hg.Context(0)
     bfv = hg.BfvEncrypt.new(args.n, args.k)
@@ -63,7 +72,7 @@ def main():
 
         def leg_a():
             t0 = time.perf_counter()
-            proofs, status, _, cms, roots, _, tm = hg.prove_encryptions_committed(ctx, pk, encs, log2_row=args.log2_row, cap_each=cap)
+            proofs, status, _, cms, roots, _, tm = committed(ctx, pk, encs, log2_row=args.log2_row, cap_each=cap)
             for cm in cms:
                 cm.free()
             ms = (time.perf_counter() - t0) * 1e3 / run
@@ -72,8 +81,8 @@ def main():
 
         def leg_b():
             t0 = time.perf_counter()
-            proofs, status, _, ws, tm = hg.prove_encryptions(ctx, pk, encs, cap_each=cap, witnesses=True)
-            cms = hg.Commitment.secrets_batch(ctx, params, ws, args.log2_row)
+            proofs, status, _, ws, tm = plain(ctx, pk, encs, cap_each=cap, witnesses=True)
+            cms = commit_batch(ctx, params, ws, args.log2_row)
             roots = [cm.root for cm in cms]
             for cm in cms:
                 cm.free()
@@ -84,7 +93,7 @@ def main():
 
         def alone():   # the pipeline without commitments and without handles: what the commit is enqueued beside
             t0 = time.perf_counter()
-            proofs, status, _, _, tm = hg.prove_encryptions(ctx, pk, encs, cap_each=cap, witnesses=False)
+            proofs, status, _, _, tm = plain(ctx, pk, encs, cap_each=cap, witnesses=False)
             return (time.perf_counter() - t0) * 1e3 / run, proofs, tm
 
         for _ in range(2):   # warm-up: launch graphs, staging, group allocations, thread pool
@@ -96,20 +105,20 @@ def main():
         for _ in range(args.reps):
             ms, proofs, tm = alone()
             assert proofs == want
-            tc.append(ms); gpu_c.append(tm["gpu_ms"] / run)
+            tc.append(ms); gpu_c.append(tm[dev] / run)
             ms, proofs, roots, tm = leg_b()
             assert proofs == want and roots == want_roots
-            tb.append(ms); gpu_b.append(tm["gpu_ms"] / run)
+            tb.append(ms); gpu_b.append(tm[dev] / run)
             ms, proofs, roots, tm = leg_a()
             assert proofs == want and roots == want_roots
-            ta.append(ms); commit.append(tm["upload_ms"] / run); gpu_a.append(tm["gpu_ms"] / run); wit.append(tm["witness_ms"] / run)
+            ta.append(ms); commit.append(tm["upload_ms"] / run); gpu_a.append(tm[dev] / run); wit.append(tm["witness_ms"] / run)
         med = statistics.median
-        print("n=%d k=%d run=%d, per item, median of %d (min .. max):" % (args.n, args.k, run, args.reps))
+        print("n=%d k=%d run=%d%s, per item, median of %d (min .. max):" % (args.n, args.k, run, " over bn256::Fr" if args.bn254 else "", args.reps))
         print("  A committed pipeline          %.3f ms (%.3f .. %.3f)" % (med(ta), min(ta), max(ta)))
         print("  B prove, then commit batch    %.3f ms (%.3f .. %.3f)   A / B = %.3f" % (med(tb), min(tb), max(tb), med(ta) / med(tb)))
         print("  A commit device time          %.3f ms; derivation + evaluation + commit %.3f ms" % (med(commit), med(wit)))
-        print("  hg_prove_encryptions alone    %.3f ms (%.3f .. %.3f), no commitment, no handles" % (med(tc), min(tc), max(tc)))
-        print("  gpu_ms / n                    A %.3f ms beside the commit, B %.3f ms, hg_prove_encryptions alone %.3f ms" % (med(gpu_a), med(gpu_b), med(gpu_c)))
+        print("  hg_prove_encryptions%s alone    %.3f ms (%.3f .. %.3f), no commitment, no handles" % (sfx, med(tc), min(tc), max(tc)))
+        print("  %s / n                    A %.3f ms beside the commit, B %.3f ms, hg_prove_encryptions%s alone %.3f ms" % (dev, med(gpu_a), med(gpu_b), sfx, med(gpu_c)))
     pk.free()
     ctx.close()
 
