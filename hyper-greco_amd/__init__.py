@@ -61,7 +61,7 @@ EXPORTS = [
     "hg_pcs_verify_device_bn254", "hg_claims_verify_device_bn254", "hg_pcs_verify_device_batch_bn254", "hg_claims_verify_batch_bn254",
     "hg_pcs_commit_batch_bn254", "hg_secrets_commit_batch_bn254", "hg_pcs_open_batch_bn254", "hg_claims_open_batch_bn254",
     "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_mle_eval",
-    "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_verify_public_bn254", "hg_verify_public_device_bn254", "hg_verify_public_batch_bn254", "hg_claims_settle_bn254", "hg_instance_mle_bn254", "hg_instance_mle_batch_bn254", "hg_prove_encryptions_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
+    "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_prodsum_jobs_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_verify_public_bn254", "hg_verify_public_device_bn254", "hg_verify_public_batch_bn254", "hg_claims_settle_bn254", "hg_instance_mle_bn254", "hg_instance_mle_batch_bn254", "hg_prove_encryptions_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
 ]
 
 
@@ -167,6 +167,8 @@ def lib():
         L.hg_bn254_field_op.argtypes = [C.c_void_p, C.c_int, C.c_size_t, u64p, u64p, u64p]
         L.hg_sumcheck_bn254.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(u64p), u64p, C.c_size_t, u64p, C.c_size_t,
                                         u64p, u64p, u64p, u64p]
+        L.hg_prodsum_jobs_bn254.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(u64p), C.POINTER(C.c_size_t),
+                                            C.c_size_t, u64p, u64p]
         L.hg_grand_product_bn254.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(u64p), C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t,
                                              C.POINTER(C.c_size_t), u64p, u64p]
         L.hg_lasso_prove_bn254.argtypes = [C.c_void_p, C.c_void_p, u64p, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t), u64p]
@@ -246,9 +248,14 @@ class Context:
         return [dict(name=arr[i].name.decode(), launches=int(arr[i].launches), total_ms=arr[i].total_ms, algo_bytes=arr[i].algo_bytes, model_bytes=arr[i].model_bytes, hbm_bytes=arr[i].hbm_bytes)
                 for i in range(n)]
 
-    # ---- BN254 slice: elements are Python ints at this level, 4 little-endian u64 limbs at the C ABI
+    # ---- BN254 slice: elements are Python ints at this level, 4 little-endian u64 limbs at the C ABI; a long table may be given as
+    # the limbs themselves, an (n, 4) uint64 array, which is passed on as it is
     @staticmethod
     def _fr_pack(vals):
+        if isinstance(vals, np.ndarray) and vals.ndim == 2:
+            if vals.shape[1] != 4 or vals.dtype != np.uint64:
+                raise ValueError("a limb table is an (n, 4) uint64 array")
+            return np.ascontiguousarray(vals).reshape(-1)
         a = np.zeros((len(vals), 4), dtype=np.uint64)
         for i, v in enumerate(vals):
             for k in range(4):
@@ -342,6 +349,33 @@ class Context:
         m = self._fr_unpack(msgs)[: nv * (d + 1)]
         return ([m[i * (d + 1):(i + 1) * (d + 1)] for i in range(nv)], self._fr_unpack(point)[:nv], self._fr_unpack(evals),
                 [self._fr_unpack(sums)[i * d:(i + 1) * d] for i in range(nv)])
+
+    def prodsum_jobs_bn254(self, jobs, chain_skip=0):
+        """hg_prodsum_jobs_bn254: the prover's PRODSUM launches on a batch of jobs, one flush. jobs: [(tables, window)] with tables =
+        [a_0, b_0, a_1, b_1, ..] (lists of ints or (n, 4) limb arrays; the same OBJECT in several places is uploaded from one
+        pointer, which is what selects the shared-b form) and window = (lo, hi) or None. -> per job (sums [[g(0), g(2)]] per round,
+        evals [2 npairs]) as ints."""
+        packed = {}
+
+        def pk(t):
+            if id(t) not in packed:
+                packed[id(t)] = self._fr_pack(t)
+            return packed[id(t)]
+        nj = len(jobs)
+        nvs = [(len(tabs[0]) - 1).bit_length() if len(tabs) else 0 for tabs, _ in jobs]
+        nps = [len(tabs) // 2 for tabs, _ in jobs]
+        flat = [pk(t) for tabs, _ in jobs for t in tabs]
+        ptrs = (u64p * max(len(flat), 1))(*[_ptr(t) for t in flat])
+        sz = C.c_size_t * max(nj, 1)
+        win = (C.c_size_t * max(2 * nj, 1))(*[int(x) for _, w in jobs for x in (w or (0, 0))])
+        sums = np.zeros(max(2 * sum(nvs), 1) * 4, dtype=np.uint64)
+        evals = np.zeros(max(2 * sum(nps), 1) * 4, dtype=np.uint64)
+        _check(lib().hg_prodsum_jobs_bn254(self.h, nj, sz(*nvs), sz(*nps), ptrs, win, chain_skip, _ptr(sums), _ptr(evals)))
+        s, e, out, so, eo = self._fr_unpack(sums), self._fr_unpack(evals), [], 0, 0
+        for nv, np_ in zip(nvs, nps):
+            out.append(([s[so + 2 * i:so + 2 * i + 2] for i in range(nv)], e[eo:eo + 2 * np_]))
+            so, eo = so + 2 * nv, eo + 2 * np_
+        return out
 
     # kernel-level entry points (parity tests)
     def sumcheck(self, kind, tables, is_base, pw, claim, chain_skip=0):

@@ -1215,6 +1215,21 @@ static void gp_launch_set(hg_ctx* ctx, hipStream_t st, GpLaunchSet& S) {
         MfA* mfa = static_cast<MfA*>(ctx->alloc(descs.size() * sizeof(MfA)));
         for (size_t i = 0; i < descs.size(); i++) descs[i].mf = mfa + i;
     }
+    if (hg_debug("bnplan")) {   // the descriptors as they are staged, in launch order (read at every call: the tests switch it per case)
+        auto lg = [](size_t v) { int n = 0; while (((size_t)1 << n) < v) n++; return n; };
+        for (size_t rd = 0; rd < S.by_rd.size(); rd++)
+            for (size_t q = 0; q < S.by_rd[rd].size(); q++) {
+                const GpJobDev& d = descs[off[rd] + q];
+                const size_t jstep = (size_t)d.gx * BN_GP_J;   // items: the (pair, j) items of the job's busiest wave (k_bn_gp_round_jobs)
+                fprintf(stderr, "[hg bnplan] gp rd=%zu layer=%d half=%llu nb=%d gx=%d gy=%d acc=%d mirror=%d items=%zu\n", rd, (int)rd + 1 + lg(d.half), d.half, d.nb,
+                        d.gx, d.gy, d.acc ? 1 : 0, d.mirror, (size_t)((d.half + jstep - 1) / jstep) * (size_t)((d.nb + d.gy - 1) / d.gy));
+            }
+        for (const TailJobDev& t : S.tails) {   // (a tail continues the sums of its layer's reduce job: that is where its round count is)
+            int shared = -1;
+            for (const RedJobDev& r : S.reds) if (t.sums_out == r.out + (size_t)r.nrounds * 3) shared = r.nrounds;
+            fprintf(stderr, "[hg bnplan] gp tail layer=%d half0=%d rounds=%d npairs=%d\n", shared < 0 ? -1 : shared + t.nrounds, t.half0, t.nrounds, t.npairs);
+        }
+    }
     const GpJobDev* d_descs = bn_stage(ctx, descs.data(), descs.size());
     const unsigned short* d_map = bn_stage(ctx, jobmap.data(), jobmap.size());
     const RedJobDev* d_reds = S.reds.empty() ? nullptr : bn_stage(ctx, S.reds.data(), S.reds.size());
@@ -1411,6 +1426,8 @@ static void grand_product_core(hg_ctx* ctx, size_t nb, size_t len, const u64* co
         ProdTailLevels tl;
         memset(&tl, 0, sizeof(tl));
         tl.nb = (int)nb;
+        const bool trace = hg_debug("bnplan");   // which kernel builds each tree level (read at every call: the tests switch it per case)
+        auto trace_level = [&](int k, const char* kernel) { if (trace) fprintf(stderr, "[hg bnplan] gp tree level=%d rowlen=%zu nb=%zu kernel=%s\n", k, len >> k, nb, kernel); };
         for (int k = 1; k < nv; k++) {
             Fr* lk = dalloc(nb * (len >> k));
             const int n = nv - 1 - k;
@@ -1420,6 +1437,7 @@ static void grand_product_core(hg_ctx* ctx, size_t nb, size_t len, const u64* co
                 FoldK kc;
                 fold_consts(*mirror_c, &kc);
                 const size_t hh = len >> 1;
+                trace_level(k, fused0 ? "level0_slots_fused" : D1 >= 1 ? "mirror_slots" : "mirror");
                 if (fused0)
                     k_bn_level0_slots_fused<<<(unsigned)((hh + 255) / 256), 256, 0, st>>>(lev[0], len, lk, (int)nb, fr_mul(*mirror_c, *mirror_c), kc, fkW[0], lw_n, slots->d_slot_of, slots->npairs,
                                                                                       slots->deep[0].d_rep, slots->deep[0].ng, slots->deep[0].V, slots->seg_shift, top_dW, top_fkW,
@@ -1433,6 +1451,7 @@ static void grand_product_core(hg_ctx* ctx, size_t nb, size_t len, const u64* co
             }
             else if (lw_n && (len >> k) >= 256) {   // long rows: the row index on grid.y, the row's weight as a launch-wide constant
                 const size_t hh = len >> k;
+                trace_level(k, k >= 2 && k - 1 < D1 ? "slots" : k >= 2 && k - 2 < D1 ? "rows_map" : "rows");
                 if (k >= 2 && k - 1 < D1)          // slot rows of the level above -> this level's slot rows (layer nv - 1 - k = deep[k - 1])
                     k_bn_prod_level_slots<<<dim3((unsigned)((hh + 255) / 256), (unsigned)slots->deep[k - 1].V), 256, 0, st>>>(lev[k - 1], len >> (k - 1), lk, fkW[k - 1], lw_n, slots->deep[k - 2].d_slot_of,
                                                                                                                       slots->deep[k - 2].ng, slots->deep[k - 1].d_rep, slots->deep[k - 1].ng, slots->seg_shift);
@@ -1445,6 +1464,7 @@ static void grand_product_core(hg_ctx* ctx, size_t nb, size_t len, const u64* co
             else {   // short rows: queued for the single-workgroup launch below
                 if (tl.nlev == 0) { tl.in = lev[k - 1]; tl.in_len = len >> (k - 1); }
                 if (tl.nlev >= 12) throw Error("hg_grand_product_bn254: more than 12 short tree levels");
+                trace_level(k, "tail_levels");
                 tl.lev[tl.nlev] = lk; tl.lw[tl.nlev] = lw_n; tl.pw[tl.nlev] = pw_n; tl.nlev++;
             }
             lev[k] = lk;

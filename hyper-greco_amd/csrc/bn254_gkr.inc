@@ -265,6 +265,21 @@ static void prodsum_flush(hipStream_t st, DevPool& pool, std::vector<PsPlan>& qu
         MfA* mfa = pool.get<MfA>(descs->size());
         for (size_t i = 0; i < descs->size(); i++) (*descs)[i].mf = mfa + i;
     }
+    if (hg_debug("bnplan")) {   // the descriptors as they are staged, in launch order (read at every call: the tests switch it per case)
+        size_t i = 0;
+        for (int rd = 0; rd < max_main; rd++)
+            for (size_t q = 0; q < nj; q++) {
+                if (rd >= nmain[q]) continue;
+                const PsJobDev& d = (*descs)[i++];
+                const bool mf = d.mf && (d.half & 63) == 0 && (!(d.pad & 4) || ((d.wlo | d.whi) & 63) == 0);   // as k_bn_ps_round_jobs decides
+                char win[48] = "-";
+                if (d.pad & 4) snprintf(win, sizeof(win), "%llu..%llu", d.wlo, d.whi);
+                fprintf(stderr, "[hg bnplan] ps job=%zu rd=%d half=%llu npairs=%d gx=%d gy=%d mf=%d shared=%d rep=%d win=%s zero=%d\n", q, rd, d.half, d.npairs, d.gx, d.gy,
+                        mf ? 1 : 0, d.pad & 1, (d.pad >> 1) & 1, win, (d.pad >> 3) & 1);
+            }
+        for (size_t q = 0; q < nj; q++)
+            fprintf(stderr, "[hg bnplan] ps tail job=%zu half0=%d rounds=%d npairs=%d\n", q, (*tails)[q].half0, (*tails)[q].nrounds, (*tails)[q].npairs);
+    }
     const PsJobDev* d_descs = bn_stage(pool.ctx, descs->data(), descs->size());
     const unsigned short* d_map = bn_stage(pool.ctx, jobmap.data(), jobmap.size());
     const RedJobDev* d_reds = bn_stage(pool.ctx, reds->data(), nj);
@@ -277,6 +292,74 @@ static void prodsum_flush(hipStream_t st, DevPool& pool, std::vector<PsPlan>& qu
     k_bn_reduce_jobs<<<dim3(32, (unsigned)nj), BN_TPB, 0, st>>>(d_reds, 2);
     k_bn_tail_jobs<BN_PRODSUM><<<(unsigned)nj, 2 * BN_TPB, 0, st>>>(d_tails);
     queue.clear();
+}
+
+// hg_prodsum_jobs_bn254: the prover's PRODSUM launches on caller tables, for kernel-level tests. Every job is queued with
+// prodsum_defer and the batch is run by ONE prodsum_flush, so it takes the launches a prove takes (jobmap / wg0 packing of jobs of
+// different sizes, shared-b and windowed forms, one tail workgroup per job). tables: a_0, b_0, a_1, b_1, .. of every job in job order
+// (host, canonical). A job of several pairs whose b pointers are all the same host pointer uploads b once (the shared-b form).
+void prodsum_jobs_bn254(hg_ctx* ctx, size_t njobs, const size_t* nv, const size_t* npairs, const u64* const* tables, const size_t* win, size_t chain_skip,
+                        u64* sums4, u64* evals4) {
+    const char* const who = "hg_prodsum_jobs_bn254: ";
+    if (!nv || !npairs || !tables || !win || !sums4 || !evals4) throw Error(std::string(who) + "null argument");
+    if (njobs < 1 || njobs > 64) throw Error(std::string(who) + "njobs must be 1 .. 64");
+    size_t total_nv = 0;
+    for (size_t q = 0; q < njobs; q++) {
+        if (nv[q] < 2 || nv[q] > 32) throw Error(std::string(who) + "nv must be 2 .. 32 (job " + std::to_string(q) + ")");
+        if (npairs[q] < 1 || npairs[q] > (size_t)dev::PS_MAX_PAIRS) throw Error(std::string(who) + "npairs must be 1 .. " + std::to_string(dev::PS_MAX_PAIRS) + " (job " + std::to_string(q) + ")");
+        total_nv += nv[q];
+    }
+    for (size_t q = 0, t0 = 0; q < njobs; t0 += 2 * npairs[q], q++) {   // everything is checked before anything is uploaded or launched
+        const size_t N = (size_t)1 << nv[q], wlo = win[2 * q], whi = win[2 * q + 1];
+        const bool windowed = wlo || whi;
+        if (windowed && npairs[q] != 1) throw Error(std::string(who) + "a window needs a job of one pair (job " + std::to_string(q) + ")");
+        if (windowed && (wlo >= whi || whi > N)) throw Error(std::string(who) + "bad window (job " + std::to_string(q) + ")");
+        for (size_t t = 0; t < 2 * npairs[q]; t++) {
+            const u64* tab = tables[t0 + t];
+            if (!tab) throw Error(std::string(who) + "null table (job " + std::to_string(q) + ")");
+            if (t >= 3 && (t & 1) && tab == tables[t0 + 1]) continue;   // the b table of pair 0 again: checked once
+            for (size_t i = 0; i < N; i++) {
+                Fr v;
+                memcpy(v.l, tab + 4 * i, 32);
+                if (fr_geq_p(v)) throw Error(std::string(who) + "table entry not below r (job " + std::to_string(q) + ", table " + std::to_string(t) + ")");
+                if (windowed && t == 1 && (i < wlo || i >= whi) && (v.l[0] | v.l[1] | v.l[2] | v.l[3]))
+                    throw Error(std::string(who) + "b is not zero outside its window (job " + std::to_string(q) + ", entry " + std::to_string(i) + ")");
+            }
+        }
+    }
+    hipc(hipSetDevice(ctx->device), "hipSetDevice");
+    hipStream_t st = ctx->stream;
+    ctx->arena_reset();
+    DevPool pool(ctx);
+    const std::vector<Fr> chain = challenge_chain_bn254(chain_skip + total_nv);
+    std::vector<PsPlan> queue;
+    std::vector<PsOut> outs;
+    std::vector<std::shared_ptr<void>> keep;
+    auto upload = [&](const u64* src, size_t N) {
+        Fr* d = pool.get<Fr>(N);
+        hipc(hipMemcpyAsync(d, src, N * sizeof(Fr), hipMemcpyHostToDevice, st), "upload table");
+        k_bn_to_mont<<<grid_of(N), 256, 0, st>>>(d, N);
+        return (const Fr*)d;
+    };
+    for (size_t q = 0, t0 = 0, c0 = chain_skip; q < njobs; t0 += 2 * npairs[q], c0 += nv[q], q++) {
+        const size_t N = (size_t)1 << nv[q], np = npairs[q];
+        bool same_b = np > 1;
+        for (size_t i = 1; i < np; i++) same_b = same_b && tables[t0 + 2 * i + 1] == tables[t0 + 1];
+        std::vector<const Fr*> a(np), b(np);
+        for (size_t i = 0; i < np; i++) {
+            a[i] = upload(tables[t0 + 2 * i], N);
+            b[i] = same_b && i ? b[0] : upload(tables[t0 + 2 * i + 1], N);
+        }
+        const std::vector<Fr> rs(chain.begin() + c0, chain.begin() + c0 + nv[q]);
+        outs.push_back(prodsum_defer(pool, queue, a, b, (int)nv[q], rs, win[2 * q], win[2 * q + 1]));
+    }
+    prodsum_flush(st, pool, queue, keep);
+    res_sync(ctx, st, "hg_prodsum_jobs_bn254: sync");
+    for (size_t q = 0; q < njobs; q++) {
+        memcpy(sums4, outs[q].sums.host, nv[q] * 2 * sizeof(Fr));
+        memcpy(evals4, outs[q].fin.host, 2 * npairs[q] * sizeof(Fr));
+        sums4 += nv[q] * 2 * 4; evals4 += 2 * npairs[q] * 4;
+    }
 }
 
 // sum over reps and constant gates of eqc[rep*G + gate] * c -> per-workgroup partials

@@ -17,6 +17,8 @@
 namespace hg { namespace bn {
 void sumcheck_bn254(hg_ctx* ctx, int kind, size_t nv, size_t ntab, const u64* const* tables, const u64* pw4, size_t npw, const u64* claim4,
                     size_t chain_skip, u64* msgs, u64* point, u64* evals, u64* sums);
+void prodsum_jobs_bn254(hg_ctx* ctx, size_t njobs, const size_t* nv, const size_t* npairs, const u64* const* tables, const size_t* win, size_t chain_skip,
+                        u64* sums4, u64* evals4);
 void field_op_bn254(hg_ctx* ctx, int op, size_t n, const u64* a, const u64* b, u64* out);
 void challenges_bn254_raw(size_t n, uint64_t* out4);
 void mle_eval_bn254(hg_ctx* ctx, const u64* table4, size_t nv, const u64* point4, u64* out4);
@@ -2059,6 +2061,14 @@ int hg_sumcheck_bn254(hg_ctx* ctx, int kind, size_t nv, size_t ntab, const uint6
     HG_TRY
     if (!ctx) throw hg::Error("hg_sumcheck_bn254: no context (a HIP device is required)");
     hg::bn::sumcheck_bn254(ctx, kind, nv, ntab, tables, pw4, npw, claim4, chain_skip, msgs, point, evals, sums);
+    return 0;
+    HG_CATCH(-1)
+}
+int hg_prodsum_jobs_bn254(hg_ctx* ctx, size_t njobs, const size_t* nv, const size_t* npairs, const uint64_t* const* tables, const size_t* win, size_t chain_skip,
+                          uint64_t* sums4, uint64_t* evals4) {
+    HG_TRY
+    if (!ctx) throw hg::Error("hg_prodsum_jobs_bn254: no context (a HIP device is required)");
+    hg::bn::prodsum_jobs_bn254(ctx, njobs, nv, npairs, tables, win, chain_skip, sums4, evals4);
     return 0;
     HG_CATCH(-1)
 }

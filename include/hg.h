@@ -712,9 +712,25 @@ int hg_challenges_bn254(size_t n, uint64_t* out4);
 int hg_bn254_field_op(hg_ctx* ctx, int op, size_t n, const uint64_t* a4, const uint64_t* b4, uint64_t* out4);
 /* = gkr::sum_check::prove_sum_check over Fr on caller tables, same shapes and conventions as hg_sumcheck
  *   [REF call sites lasso.rs:278-279, prover.rs:242-252]. tables[i]: host pointer, 2^nv elements (4 limbs each).
- *   Outputs: msgs nv*(d+1), point nv, evals ntab, sums nv*d elements. */
+ *   Outputs: msgs nv*(d+1), point nv, evals ntab, sums nv*d elements.
+ *   Its round kernel (k_bn_round, with k_bn_reduce) is a plain form of the three shapes that nothing else launches: it is NOT one of
+ *   the kernels hg_prove_bn254 runs. Those are reached through hg_prodsum_jobs_bn254 (PRODSUM) and hg_grand_product_bn254. */
 int hg_sumcheck_bn254(hg_ctx* ctx, int kind, size_t nv, size_t ntab, const uint64_t* const* tables, const uint64_t* pw4, size_t npw,
                       const uint64_t* claim4, size_t chain_skip, uint64_t* msgs, uint64_t* point, uint64_t* evals, uint64_t* sums);
+/* The prover's own PRODSUM launches (the Libra / zkCNN node reductions of hg_prove_bn254) on caller tables, for kernel-level tests:
+ *   job q is the sum-check of g = sum_i a_i b_i over 2^nv[q] entries with npairs[q] pairs; every job is queued and the batch runs as
+ *   ONE round-synchronised flush - the shared round launches over jobs of different sizes, one reduce launch, one tail workgroup per job.
+ *   tables: a_0, b_0, a_1, b_1, .. of every job, in job order (host pointers, 2^nv[q] canonical elements each). A job of more than one
+ *   pair whose b pointers are all the SAME host pointer uploads b once and takes the shared-b form. win[2q], win[2q+1]: b of job q is
+ *   zero outside the entries [lo, hi) ((0, 0): no window; needs npairs[q] == 1, and the entries outside are checked to be zero); a
+ *   window that is not a run of whole pairs in every shared round is dropped and the job runs the plain form. Job q takes its nv[q]
+ *   round challenges from the chain at chain_skip + sum_{q' < q} nv[q'].
+ *   sums4: per job nv[q] x (g(0), g(2)), concatenated; evals4: per job the 2 npairs[q] folded values (a_0, b_0, a_1, ..), concatenated.
+ *   HG_DEBUG=bnplan prints the staged descriptors (`[hg bnplan] ps ..`; `gp ..` for hg_grand_product_bn254): which form each round took.
+ *   -1 before any launch for: njobs outside 1..64, nv outside 2..32, npairs outside 1..32, an element >= r, a window on a job of
+ *   several pairs, a non-zero entry outside a window. */
+int hg_prodsum_jobs_bn254(hg_ctx* ctx, size_t njobs, const size_t* nv, const size_t* npairs, const uint64_t* const* tables, const size_t* win,
+                          size_t chain_skip, uint64_t* sums4, uint64_t* evals4);
 
 /* = prove_grand_product over Fr [REF lasso/src/memory_checking/prover.rs:183-266]: nb tables of len = 2^nv elements; product tree on
  *   the MSB split, root products, per layer a degree-3 sum-check with g = poly(0) * sum_b gamma^b v_l,b v_r,b, 2 nb evaluations and the

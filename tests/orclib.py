@@ -300,9 +300,12 @@ def limbs_of(field):
 
 
 def to_limbs(vals, nl):
-    """Python integers -> canonical little-endian u64 limbs (nl per element)."""
+    """Python integers -> canonical little-endian u64 limbs (nl per element); an (n, nl) uint64 array holds the limbs already."""
     if nl == 1 and isinstance(vals, np.ndarray):   # (long Goldilocks tables: already in that form)
         return np.ascontiguousarray(vals, dtype=np.uint64)
+    if isinstance(vals, np.ndarray) and vals.ndim == 2:   # (long bn254 tables: rand_fr / edge_fr)
+        assert vals.shape[1] == nl and vals.dtype == np.uint64, (vals.shape, vals.dtype)
+        return np.ascontiguousarray(vals).reshape(-1)
     a = np.zeros(len(vals) * nl, dtype=np.uint64)
     for i, v in enumerate(vals):
         for j in range(nl):
@@ -403,6 +406,66 @@ def grand_product_f(field, tabs, chain_skip=0, threads=1, cap=1 << 24):
     if rc != 0:
         raise RuntimeError(err.value.decode())
     return bytes(buf[:ln.value]), from_limbs(claims, el), from_limbs(point, el)
+
+
+def sumcheck_f(field, kind, tabs, pw=(), claim=0, chain_skip=0, threads=1):
+    """prove_sum_check of the C++ oracle over `field` on base-field tables (lists of Python ints or limb arrays), kind 0 collation,
+    1 grand product, 2 prodsum; pw, claim: Python ints. -> (msgs, point, evals, sums) as flat lists of ints (sums: the true round
+    sums at 0, 2[, 3], which do not depend on the claim)."""
+    fl, el = limbs_of(field)
+    ntab = len(tabs)
+    nv = (len(tabs[0]) - 1).bit_length()
+    d = 3 if kind == 1 else 2
+    arrs = [to_limbs(t, fl) for t in tabs]
+    ptrs = (u64p * ntab)(*[ptr(a) for a in arrs])
+    flags = (C.c_int * ntab)(*([1] * ntab))
+    ppw = to_limbs(list(pw), el) if len(pw) else np.zeros(el, dtype=np.uint64)
+    pcl = to_limbs([claim], el)
+    msgs = np.zeros(max(nv * (d + 1), 1) * el, dtype=np.uint64)
+    point = np.zeros(max(nv, 1) * el, dtype=np.uint64)
+    evals = np.zeros(ntab * el, dtype=np.uint64)
+    sums = np.zeros(max(nv * d, 1) * el, dtype=np.uint64)
+    _sym(field, "sumcheck")(kind, C.c_size_t(nv), C.c_size_t(ntab), ptrs, flags, ptr(ppw), C.c_size_t(len(pw)), ptr(pcl), C.c_size_t(chain_skip), threads,
+                            ptr(msgs), ptr(point), ptr(evals), ptr(sums))
+    return from_limbs(msgs, el)[:nv * (d + 1)], from_limbs(point, el)[:nv], from_limbs(evals, el), from_limbs(sums, el)[:nv * d]
+
+
+def mle_eval_f(field, table, point):
+    """BoxMultilinearPoly::evaluate of the C++ oracle: a base-field table (Python ints or a limb array) at a point of Python ints."""
+    fl, el = limbs_of(field)
+    nv = (len(table) - 1).bit_length()
+    out = np.zeros(el, dtype=np.uint64)
+    pt = to_limbs(list(point), el) if len(point) else np.zeros(el, dtype=np.uint64)
+    _sym(field, "mle_eval_f")(ptr(to_limbs(table, fl)), C.c_size_t(nv), ptr(pt), ptr(out))
+    return from_limbs(out, el)[0]
+
+
+# ---- long bn254 tables as (n, 4) uint64 limb arrays: no Python loop over the elements ---------------------------------------------
+# Every edge of the 256-bit arithmetic: the small values, r - 1 and r - 2 (the largest canonical values), the two halves of r, the
+# limb boundaries 2^64 - 1, 2^64, 2^128 + 5, the top bit 2^253, and r - k for small k (the lifts of negative integers).
+EDGE_POOL_FR = [0, 1, 2, R_BN - 1, R_BN - 2, (R_BN - 1) // 2, (R_BN + 1) // 2, (1 << 64) - 1, 1 << 64, (1 << 128) + 5, 1 << 253] + \
+               [R_BN - k for k in (3, 4, 7, 19, 255, 65537)]
+
+
+def fr_limbs(vals):
+    """Python ints (a short list) -> (n, 4) uint64 limbs"""
+    return to_limbs(list(vals), 4).reshape(-1, 4)
+
+
+def rand_fr(rng, n):
+    """n random canonical bn254 elements as (n, 4) limbs (rng: numpy Generator). The top limb is drawn below the top limb of r, which
+    makes every value canonical by construction; every edge of EDGE_POOL_FR is planted at a random position (the first n of them in
+    a table shorter than the pool)."""
+    a = rng.integers(0, 1 << 64, size=(n, 4), dtype=np.uint64)
+    a[:, 3] = rng.integers(0, R_BN >> 192, size=n, dtype=np.uint64)
+    pool = fr_limbs(EDGE_POOL_FR)[:n]
+    a[rng.choice(n, size=len(pool), replace=False)] = pool
+    return a
+
+
+def edge_fr(rng, n):
+    """n elements, every one drawn from EDGE_POOL_FR, so that edge meets edge in the unfolded first round"""
+    return fr_limbs(EDGE_POOL_FR)[rng.integers(0, len(EDGE_POOL_FR), size=n)]
 
 
 def gl_form(v):
