@@ -31,6 +31,7 @@
 #include "verifier_batch.hpp"
 #include "pcs_bn254.hpp"
 #include "pcs_keccak.hpp"
+#include "pcs_flow.hpp"
 
 namespace hg {
 namespace bn {

@@ -4,10 +4,12 @@
 // and the leaf hash and the column gather read the matrix as it is. Keccak and the tree are those of the Goldilocks form
 // (pcs_keccak.hpp, pcs::merkle_levels_device): a node is 32 bytes in either field.
 // The verifier of an opening reuses the encoding, the leaf sponge and the accumulators and adds five kernels.
-// Every step has one kernel, written for a group of members and driven by a member or job table; the forms for a run
-// (pcs_commit_device_batch, pcs_open_device_batch, pcs_verify_device_batch) launch it once over a group, whose matrices lie in one
-// allocation that its handles share, and the forms for one (pcs_commit_device, pcs_combine_device, pcs_verify_device) launch it
-// over a group of one from a host flow of their own.
+// Every step has one kernel, written for a group of members and driven by a member or job table (the descriptors of pcs_flow.hpp,
+// which both fields share); the forms for a run launch it once over a group, whose matrices lie in one allocation that its handles
+// share, and the forms for one launch it over a group of one.
+// The host flows of the verifiers, the batch opener, the batch committer, pcs_combine_device and pcs_columns_device are the templates
+// of pcs_flow.hpp, written once for both fields; this file gives them BnPcs, the BN254 policy: the types, the transcript calls, the
+// texts and one launch function per kernel step. pcs_commit_device and pcs_commit_words_enqueue keep a host flow of their own.
 
 constexpr int BNPCS_TPB = 256;
 static unsigned bnpcs_blocks(size_t n) { return (unsigned)((n + BNPCS_TPB - 1) / BNPCS_TPB); }
@@ -121,36 +123,33 @@ __global__ __launch_bounds__(BNPCS_TPB) void k_bnpcs_gather(const Fr* __restrict
 // columns, encoded rows, jobs and weights lie) is read from its descriptor, never derived from a flat id, and no member's range is
 // assumed to start at a workgroup. Every block of the staged copy starts at a multiple of 32 bytes (lz_gload reads 16-byte halves).
 // A word of an opening only ever becomes a number; every index below comes from the shape, from the host's masked j_q or from table
-// offsets the entry point validated. Each result cell holds the lowest offending key (atomicMin), so the reason is the host's also
-// where several checks fail at once.
-constexpr u64 BNPCSV_NONE = ~(u64)0;   // a cell no thread lowered: nothing failed
-__device__ __forceinline__ void bnpcsv_min(u64* cell, u64 v) { atomicMin(reinterpret_cast<unsigned long long*>(cell), (unsigned long long)v); }
-struct BnPcsDesc { u64 row0, nrows, woff; };   // a row combination: sum_{r < nrows} w[woff + r] * row_{row0 + r}
-struct BnVbMember {
-    u64 proof, u, cols, enc_row;               // word offset of its opening in the set; element offsets of its u and columns; its first row of enc
-    u64 n, claim0, job0;                       // its claims; the claims and the jobs (claims + 1 each) of the members before it
-    u64 root_at, jobs_at, y_at, z_at, w_at;    // byte offsets in the group's staged copy: root, job descriptors, values, low coordinates, weights
-};
-struct BnVbGroup { u64 G, Q, R, q_el; int c, depth; };
+// offsets the entry point validated. The descriptors (VbMember, VbGroup, CombineDesc) and the result cells are those of
+// pcs_flow.hpp; a row element is an Fr, so the offsets in Row units are element offsets.
+using pcs::CombineDesc;
+using pcs::VbMember;
+using pcs::VbGroup;
+using pcs::ObClaim;
+typedef pcs::ObJob<Fr> ObJob;
+typedef pcs::ObMember<Fr> ObMember;
 
 // 32 big-endian bytes of an opening -> 4 native limbs (limb w = the byte-swapped word 3 - w); blockIdx.y = the member, its elements
 // grid-strided over blockIdx.x. Element i < u_el is element i & (C - 1) of u vector i >> c: kept in u and scattered into row i >> c
 // of the member's rows of the matrix the NTT encodes (zeroed beforehand). The others are the Q * R column elements, query q at
-// element u_el + q * q_el. cells[3m] = the lowest byte offset, within its opening, of an element that is not below r (all four limbs
+// element u_el + q * q_stride. cells[3m] = the lowest byte offset, within its opening, of an element that is not below r (all four limbs
 // compared). Elements stay plain words: no Montgomery conversion (ntt_batch_dev keeps the form).
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_canon(const u64* __restrict__ set, const BnVbMember* __restrict__ mem, BnVbGroup g, Fr* __restrict__ u,
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_canon(const u64* __restrict__ set, const VbMember* __restrict__ mem, VbGroup g, Fr* __restrict__ u,
                                                              Fr* __restrict__ cols, Fr* __restrict__ enc, u64* __restrict__ cells) {
-    const BnVbMember M = mem[blockIdx.y];
+    const VbMember M = mem[blockIdx.y];
     const int c = g.c;
     const size_t Q = g.Q, R = g.R, u_el = (M.n + 1) << c, total = u_el + Q * R, Cm = ((size_t)1 << c) - 1;
     const u64* proof = set + M.proof;
     Fr* mu = u + M.u;
     Fr* mcols = cols + M.cols;
     Fr* menc = enc + (M.enc_row << (c + 2));
-    u64 bad = BNPCSV_NONE;
+    u64 bad = pcs::PCSV_NONE;
     for (size_t i = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * BNPCS_TPB) {
         size_t at = i;
-        if (i >= u_el) { const size_t k = i - u_el, q = k / R; at = u_el + q * g.q_el + (k - q * R); }
+        if (i >= u_el) { const size_t k = i - u_el, q = k / R; at = u_el + q * g.q_stride + (k - q * R); }
         const u64* p = proof + 4 * at;
         const Fr v = fr_make(__builtin_bswap64(p[3]), __builtin_bswap64(p[2]), __builtin_bswap64(p[1]), __builtin_bswap64(p[0]));
         if (fr_geq_p(v) && 32 * at < bad) bad = 32 * at;
@@ -161,7 +160,7 @@ __global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_canon(const u64* __restri
             lz_gstore(mcols + (i - u_el), v);
         }
     }
-    if (bad != BNPCSV_NONE) bnpcsv_min(cells + 3 * blockIdx.y, bad);
+    if (bad != pcs::PCSV_NONE) pcs::cell_min(cells + 3 * blockIdx.y, bad);
 }
 
 // <ui, eq(z[..c])> != y, by one workgroup; the answer is thread 0's. z holds the c low coordinates of the point in Montgomery form,
@@ -189,19 +188,19 @@ __device__ __forceinline__ bool bnpcs_eval_differs(const Fr* __restrict__ ui, co
 }
 // <u_i, eq(z_i[..c])> == y_i, one workgroup per (member, claim): block b belongs to the last member whose claim0 is <= b (a member
 // without claims owns no block). cells[3m + 1] = the member's lowest failing claim.
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_eval(const BnVbMember* __restrict__ mem, unsigned G, int c, const Fr* __restrict__ u, const char* __restrict__ stage,
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_eval(const VbMember* __restrict__ mem, unsigned G, int c, const Fr* __restrict__ u, const char* __restrict__ stage,
                                                             u64* __restrict__ cells) {
     unsigned lo = 0, hi = G;
     while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].claim0 <= blockIdx.x) lo = mid; else hi = mid; }
-    const BnVbMember M = mem[lo];
+    const VbMember M = mem[lo];
     const size_t i = blockIdx.x - M.claim0;
     if (i >= M.n) return;   // (uniform over the workgroup; the grid has exactly the claims of the group)
     if (bnpcs_eval_differs(u + M.u + ((i + 1) << c), reinterpret_cast<const Fr*>(stage + M.z_at) + i * (size_t)c, reinterpret_cast<const Fr*>(stage + M.y_at) + i, c))
-        bnpcsv_min(cells + 3 * lo + 1, (u64)i);
+        pcs::cell_min(cells + 3 * lo + 1, (u64)i);
 }
 
 // One thread per (member m, query q), id = m Q + q: the leaf hash of its R column elements (contiguous: 4 words between them) -> leaves[id]
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_leaf(const BnVbMember* __restrict__ mem, BnVbGroup g, const Fr* __restrict__ cols, u64* __restrict__ leaves) {
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_leaf(const VbMember* __restrict__ mem, VbGroup g, const Fr* __restrict__ cols, u64* __restrict__ leaves) {
     const size_t id = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
     if (id >= g.G * g.Q) return;
     const size_t m = id / g.Q, q = id - m * g.Q;
@@ -219,15 +218,15 @@ __global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_leaf(const BnVbMember* __
 // works on global job b / bq, queries (b % bq) TPB .. . The member is the last one whose job0 is <= the job. A column element that
 // passed k_bnpcsvb_canon is below r and the weight is a residue, which is bnpcs_dot_chunked's bound. (An element that did not pass
 // only makes this sum meaningless, and cells[3m] decides ahead of whatever reads it.)
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_dots(const BnVbMember* __restrict__ mem, BnVbGroup g, unsigned bq, const Fr* __restrict__ cols,
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_dots(const VbMember* __restrict__ mem, VbGroup g, unsigned bq, const Fr* __restrict__ cols,
                                                             const char* __restrict__ stage, Fr* __restrict__ s) {
     const size_t gjob = blockIdx.x / bq;
     const size_t q = (size_t)(blockIdx.x % bq) * BNPCS_TPB + threadIdx.x;
     if (q >= g.Q) return;
     unsigned lo = 0, hi = (unsigned)g.G;
     while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].job0 <= gjob) lo = mid; else hi = mid; }
-    const BnVbMember M = mem[lo];
-    const BnPcsDesc job = reinterpret_cast<const BnPcsDesc*>(stage + M.jobs_at)[gjob - M.job0];
+    const VbMember M = mem[lo];
+    const CombineDesc job = reinterpret_cast<const CombineDesc*>(stage + M.jobs_at)[gjob - M.job0];
     lz_gstore(s + gjob * g.Q + q, bnpcs_dot_chunked(cols + M.cols + q * g.R + job.row0, 0, reinterpret_cast<const Fr*>(stage + M.w_at) + job.woff, job.nrows));
 }
 
@@ -235,57 +234,55 @@ __global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_dots(const BnVbMember* __
 // hash over the c+2 siblings (32 raw bytes each behind the query's column elements) against the member's root, then s[job 0][q]
 // against Enc(u_0)[j_q], then s[job 1 + i][q] against Enc(u_i)[j_q]. cells[3m + 2] = the member's lowest q (n_m + 2) + kind that
 // failed: kind 0 the path, 1 proximity, 2 + i claim i.
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_query(const u64* __restrict__ set, const BnVbMember* __restrict__ mem, BnVbGroup g, const u64* __restrict__ leaves,
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsvb_query(const u64* __restrict__ set, const VbMember* __restrict__ mem, VbGroup g, const u64* __restrict__ leaves,
                                                              const Fr* __restrict__ s, const Fr* __restrict__ enc, const u64* __restrict__ js,
                                                              const char* __restrict__ stage, u64* __restrict__ cells) {
     const size_t id = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
     if (id >= g.G * g.Q) return;
     const size_t m = id / g.Q, q = id - m * g.Q;
-    const BnVbMember M = mem[m];
+    const VbMember M = mem[m];
     const int depth = g.depth;
     const size_t N = (size_t)1 << depth, j = js[id], n = M.n, u_el = (n + 1) << g.c;
-    const u64* sib = set + M.proof + 4 * (u_el + q * g.q_el + g.R);
+    const u64* sib = set + M.proof + 4 * (u_el + q * g.q_stride + g.R);
     const u64* root = reinterpret_cast<const u64*>(stage + M.root_at);
     u64 h[4] = {leaves[4 * id], leaves[4 * id + 1], leaves[4 * id + 2], leaves[4 * id + 3]};
     pcs::merkle_climb(h, sib, j, depth);
     u64* cell = cells + 3 * m + 2;
     const size_t key = q * (n + 2);
-    if (h[0] != root[0] || h[1] != root[1] || h[2] != root[2] || h[3] != root[3]) { bnpcsv_min(cell, key); return; }
+    if (h[0] != root[0] || h[1] != root[1] || h[2] != root[2] || h[3] != root[3]) { pcs::cell_min(cell, key); return; }
     const Fr* sq = s + M.job0 * g.Q + q;
     const Fr* menc = enc + (M.enc_row << depth) + j;
     for (size_t i = 0; i <= n; i++)
-        if (!fr_eq(lz_gload(sq + i * g.Q), lz_gload(menc + i * N))) { bnpcsv_min(cell, key + 1 + i); return; }
+        if (!fr_eq(lz_gload(sq + i * g.Q), lz_gload(menc + i * N))) { pcs::cell_min(cell, key + 1 + i); return; }
 }
 
 // ---- the kernels of the prover's side of an opening, written for a group of items (pcs_open_device_batch); the row combinations of
 // one opening (pcs_combine_device) are a job table of their own. What differs by item lies in three flat tables of the staged copy:
 // a job a row combination (the proximity combination and one a claim, every member's behind the other), a claim an evaluation
-// check, a member where its matrix, its u vectors and its opening image lie. Every block of the staged copy starts at a multiple of
-// 32 bytes (lz_gload reads 16-byte halves). Every grid is one-dimensional.
-struct BnObJob { const Fr* src; u64 nrows, w_at, u_at; };      // its first raw row; the byte offset of its weights in the staged copy; where u goes (elements)
-struct BnObClaim { u64 u_at, z_at, y_at, member, claim; };     // its u_i (elements); byte offsets of the low coordinates (Montgomery) and of the value
-struct BnObMember { const Fr* M; u64 img, u, u_words; };       // its encoded matrix; word offsets of its image and of its u vectors; 4 C (n + 1)
+// check, a member where its matrix, its u vectors and its opening image lie (ObJob, ObClaim, ObMember of pcs_flow.hpp; the low
+// coordinates in Montgomery form). Every block of the staged copy starts at a multiple of 32 bytes (lz_gload reads 16-byte halves).
+// Every grid is one-dimensional.
 
 // Row combinations: u[u_at + j] = sum_{r < nrows} w[r] * src[r][j] for the job of the workgroup, a thread owns column j. Workgroup b
 // serves job b / cb alone, columns (b % cb) BNPCS_TPB .. - the weight limbs go through readfirstlane, so every lane of a wavefront
 // must be on one job
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_combine(int c, unsigned cb, const BnObJob* __restrict__ jobs, const char* __restrict__ stage, Fr* __restrict__ u) {
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_combine(int c, unsigned cb, const ObJob* __restrict__ jobs, const char* __restrict__ stage, Fr* __restrict__ u) {
     const size_t C = (size_t)1 << c;
     const unsigned jq = blockIdx.x / cb;
     const size_t j = (size_t)(blockIdx.x - jq * cb) * BNPCS_TPB + threadIdx.x;
     if (j >= C) return;
-    const BnObJob job = jobs[jq];
+    const ObJob job = jobs[jq];
     lz_gstore(u + job.u_at + j, bnpcs_dot_chunked(job.src + j, c, reinterpret_cast<const Fr*>(stage + job.w_at), job.nrows));
 }
 // One workgroup per (member, claim): <u_i, eq(z_i[..c])> == y_i; cells[member] = its lowest failing claim
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_eval(const BnObClaim* __restrict__ claims, int c, const Fr* __restrict__ u, const char* __restrict__ stage,
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_eval(const ObClaim* __restrict__ claims, int c, const Fr* __restrict__ u, const char* __restrict__ stage,
                                                             u64* __restrict__ cells) {
-    const BnObClaim cl = claims[blockIdx.x];
-    if (bnpcs_eval_differs(u + cl.u_at, reinterpret_cast<const Fr*>(stage + cl.z_at), reinterpret_cast<const Fr*>(stage + cl.y_at), c)) bnpcsv_min(cells + cl.member, cl.claim);
+    const ObClaim cl = claims[blockIdx.x];
+    if (bnpcs_eval_differs(u + cl.u_at, reinterpret_cast<const Fr*>(stage + cl.z_at), reinterpret_cast<const Fr*>(stage + cl.y_at), c)) pcs::cell_min(cells + cl.member, cl.claim);
 }
 // Word i of the group's u vectors into its member's image, an element as 32 bytes big-endian: word w of the image's element is the
 // byte-swapped limb 3 - w. The member is the last one whose u offset is <= i (offsets are multiples of 4: an element never straddles)
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_emit(const BnObMember* __restrict__ mem, unsigned G, size_t total, const u64* __restrict__ u, u64* __restrict__ img) {
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_emit(const ObMember* __restrict__ mem, unsigned G, size_t total, const u64* __restrict__ u, u64* __restrict__ img) {
     for (size_t i = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * BNPCS_TPB) {
         unsigned lo = 0, hi = G;
         while (hi - lo > 1) { const unsigned mid = (lo + hi) >> 1; if (mem[mid].u <= i) lo = mid; else hi = mid; }
@@ -294,13 +291,13 @@ __global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_emit(const BnObMember* __
 }
 // One thread per (member m, query q, row r), id = (m Q + q) R + r: M_m[r][j_q] big-endian at its place in the member's image.
 // js[m Q + q] = j_q (masked by the host); js[G Q + m] != 0: the member takes part (it was not refused)
-__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_gather(const BnObMember* __restrict__ mem, size_t G, size_t Q, size_t R, size_t N, size_t q_words,
+__global__ __launch_bounds__(BNPCS_TPB) void k_bnpcsob_gather(const ObMember* __restrict__ mem, size_t G, size_t Q, size_t R, size_t N, size_t q_words,
                                                               const u64* __restrict__ js, u64* __restrict__ img) {
     const size_t id = (size_t)blockIdx.x * BNPCS_TPB + threadIdx.x;
     if (id >= G * Q * R) return;
     const size_t m = id / (Q * R), k = id - m * Q * R, q = k / R, r = k - q * R;
     if (!js[G * Q + m]) return;
-    const BnObMember M = mem[m];
+    const ObMember M = mem[m];
     const Fr v = lz_gload(M.M + r * N + js[m * Q + q]);
     u64* out = img + M.img + M.u_words + q * q_words + 4 * r;
     out[0] = __builtin_bswap64(v.l[3]); out[1] = __builtin_bswap64(v.l[2]); out[2] = __builtin_bswap64(v.l[1]); out[3] = __builtin_bswap64(v.l[0]);
@@ -439,699 +436,142 @@ void pcs_commit_words_enqueue(hipStream_t st, const pcs::Shape& sh, const u64* c
     pcs::merkle_levels_device(st, d_tree, N);
 }
 
-void pcs_combine_device(const pcs::Commitment& cm, const std::vector<PcsJob>& jobs, Fr* u) {
-    hg_ctx* ctx = cm.ctx;
-    hipc(hipSetDevice(ctx->device), "hipSetDevice");
-    ctx->arena_reset();
-    hipStream_t st = ctx->stream;
-    const size_t C = cm.sh.C(), nj = jobs.size();
-    if (nj > 65535) throw Error("hg_pcs_open_bn254: more than 65534 claims");
-    // the job table and the weights in one staged copy; job q's u vector is the q-th
-    size_t nw = 0;
-    for (const PcsJob& j : jobs) nw += j.nrows;
-    const size_t desc_bytes = (nj * sizeof(BnObJob) + 31) & ~(size_t)31;
-    std::vector<char> stage(desc_bytes + nw * sizeof(Fr));
-    BnObJob* hd = reinterpret_cast<BnObJob*>(stage.data());
-    size_t w_at = desc_bytes;
-    for (size_t q = 0; q < nj; q++) {
-        hd[q].src = reinterpret_cast<const Fr*>(cm.d_rows) + (jobs[q].row0 << cm.sh.c); hd[q].nrows = jobs[q].nrows; hd[q].w_at = w_at; hd[q].u_at = q * C;
-        memcpy(stage.data() + w_at, jobs[q].w.data(), jobs[q].nrows * sizeof(Fr));
-        w_at += jobs[q].nrows * sizeof(Fr);
+// ---- the BN254 policy of the flows of pcs_flow.hpp. A row element, an element of u and a weight are an Fr each: a u vector is encoded
+// as one row. Weights and low coordinates go into the staged copy in Montgomery form.
+struct BnPcs {
+    typedef Fr Row;
+    typedef Fr W;
+    typedef PcsClaim Claim;
+    typedef PcsJob Job;
+    typedef bn::VerifyItem VerifyItem;
+    typedef PcsOpenItem OpenItem;
+    static constexpr size_t U_ROWS = 1, ALIGN = 32, TPB = BNPCS_TPB;
+    static constexpr pcs::Field FIELD = pcs::BN254;
+    // The leaf sponge (serial: 4R + 1 words a thread, Q threads a member) is the longest of the index-free kernels and goes last among
+    // them, so the two verdicts that need no index and the inner products never wait behind it; the host's own hash of the u_i covers it.
+    static constexpr bool LEAF_AFTER_DOTS = true;
+    static constexpr const char *CLS_VERIFY = "pcs_bn254_verify", *CLS_VERIFY_BATCH = "pcs_bn254_verify_batch", *CLS_OPEN_BATCH = "pcs_bn254_open_batch",
+                                *CLS_COMMIT_BATCH = "pcs_bn254_commit_batch", *CLS_COMBINE = "pcs_bn254_combine";
+    static constexpr const char *VERIFY_NAME = "hg_pcs_verify_device_bn254", *OPEN_NAME = "hg_pcs_open_bn254", *TIMES_TAG = "bn254 ",
+                                *NOT_BELOW = "a table holds an element that is not below r";
+    static size_t opening_bytes(const pcs::Shape& sh, size_t n, size_t Q) { return pcs_opening_bytes(sh, n, Q); }
+    // the transcript
+    static FsTranscript start_transcript(const pcs::Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q) { return pcs_start_transcript(sh, root, claims, Q); }
+    static std::vector<Fr> rho_powers(FsTranscript& tr, size_t R) { return pcs_rho_powers(pcs_squeeze(tr), R); }
+    static std::vector<Fr> eq_table(const Fr* pt, size_t n) { return pcs_eq_table(pt, n); }
+    static void store_low(Fr* dst, const Fr* pt, int c) { for (int b = 0; b < c; b++) dst[b] = fr_to_mont(pt[b]); }
+    static void absorb_opening(FsTranscript& tr, const uint8_t* proof, size_t n_u) {   // the u_i as the opening holds them: 32 bytes big-endian
+        std::vector<Fr> u(n_u);
+        for (size_t i = 0; i < n_u; i++) u[i] = pcs_read_be32(proof + 32 * i);
+        pcs_absorb(tr, u.data(), n_u);
     }
-    char* d_stage = ctx->alloc_n<char>(stage.size());
-    Fr* d_u = ctx->alloc_n<Fr>(nj * C);
-    const unsigned cb = bnpcs_blocks(C);   // (at most 2^16 workgroups a job and, by the entry point, MAX_CLAIMS + 1 jobs: inside a grid's x)
-    const int cls = ctx->prof_class("pcs_bn254_combine", false);
-    ctx->prof_stream = st;
-    hipc(hipMemcpyAsync(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, st), "upload weights");
-    ctx->prof_begin(cls, (double)nw * C * 32);
-    k_bnpcsob_combine<<<(unsigned)(nj * cb), BNPCS_TPB, 0, st>>>(cm.sh.c, cb, reinterpret_cast<const BnObJob*>(d_stage), d_stage, d_u);
-    ctx->prof_end();
-    hipc(hipMemcpyAsync(u, d_u, nj * C * sizeof(Fr), hipMemcpyDeviceToHost, st), "download combinations");
-    hipc(hipStreamSynchronize(st), "hg_pcs_open_bn254: sync");
-    hipc(hipGetLastError(), "hg_pcs_open_bn254: launch");
-    ctx->prof_collect();
-}
-
-void pcs_columns_device(const pcs::Commitment& cm, const std::vector<size_t>& js, Fr* cols) {
-    hg_ctx* ctx = cm.ctx;
-    hipc(hipSetDevice(ctx->device), "hipSetDevice");
-    hipStream_t st = ctx->stream;
-    const size_t N = cm.sh.N(), R = cm.sh.R, Q = js.size();
-    if (Q > 65535) throw Error("hg_pcs_open_bn254: more than 65535 queries on the device");
-    std::vector<u64> hj(js.begin(), js.end());
-    u64* d_js = ctx->alloc_n<u64>(Q);
-    Fr* d_cols = ctx->alloc_n<Fr>(Q * R);
-    hipc(hipMemcpyAsync(d_js, hj.data(), Q * 8, hipMemcpyHostToDevice, st), "upload column indices");
-    k_bnpcs_gather<<<dim3(bnpcs_blocks(R), (unsigned)Q), BNPCS_TPB, 0, st>>>(reinterpret_cast<const Fr*>(cm.d_M), N, R, d_js, d_cols);
-    hipc(hipMemcpyAsync(cols, d_cols, Q * R * sizeof(Fr), hipMemcpyDeviceToHost, st), "download columns");
-    hipc(hipStreamSynchronize(st), "hg_pcs_open_bn254: sync");
-    hipc(hipGetLastError(), "hg_pcs_open_bn254: launch");
-}
-
-// ---- what the two verifiers share on the host: a member's block of the staged copy and the reading of its three result cells
-// the entries of a member's weight tables: R powers of rho, then eq(z_i[c..]) over the rows of every claim's table
-static size_t bnpcs_weights_of(const pcs::Shape& sh, const std::vector<PcsClaim>& claims) {
-    size_t nw = sh.R;
-    for (const PcsClaim& cl : claims) nw += (size_t)1 << (sh.nvars[cl.table] - sh.c);
-    return nw;
-}
-// The block of a member of n claims and nw weights from byte `at` (a multiple of 32) of a staged copy on: root, job descriptors,
-// values, the low coordinates of the points, weight tables. Into its descriptor -> the byte behind the block
-static size_t bnpcs_block_layout(BnVbMember& d, const pcs::Shape& sh, size_t n, size_t nw, size_t at) {
-    d.root_at = at;
-    d.jobs_at = d.root_at + 32;
-    d.y_at = d.jobs_at + (((n + 1) * sizeof(BnPcsDesc) + 31) & ~(size_t)31);
-    d.z_at = d.y_at + n * sizeof(Fr);
-    d.w_at = d.z_at + n * (size_t)sh.c * sizeof(Fr);
-    return d.w_at + nw * sizeof(Fr);
-}
-// fills the block (the low coordinates and the weights in Montgomery form) -> the member's transcript, rho squeezed
-static FsTranscript bnpcs_block_fill(char* h_stage, const BnVbMember& d, const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q) {
-    const size_t R = sh.R;
-    FsTranscript tr = pcs_start_transcript(sh, root, claims, Q);
-    const std::vector<Fr> rho = pcs_rho_powers(pcs_squeeze(tr), R);
-    memcpy(h_stage + d.root_at, root, 32);
-    BnPcsDesc* hd = reinterpret_cast<BnPcsDesc*>(h_stage + d.jobs_at);
-    Fr* hy = reinterpret_cast<Fr*>(h_stage + d.y_at);
-    Fr* hz = reinterpret_cast<Fr*>(h_stage + d.z_at);
-    Fr* hw = reinterpret_cast<Fr*>(h_stage + d.w_at);
-    hd[0].row0 = 0; hd[0].nrows = R; hd[0].woff = 0;
-    memcpy(hw, rho.data(), R * sizeof(Fr));
-    size_t off = R;
-    for (size_t i = 0; i < claims.size(); i++) {
-        const PcsClaim& cl = claims[i];
-        const std::vector<Fr> w = pcs_eq_table(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
-        hd[i + 1].row0 = sh.off[cl.table]; hd[i + 1].nrows = w.size(); hd[i + 1].woff = off;
-        memcpy(hw + off, w.data(), w.size() * sizeof(Fr));
-        off += w.size();
-        hy[i] = cl.value;
-        for (int b = 0; b < sh.c; b++) hz[i * (size_t)sh.c + b] = fr_to_mont(cl.point[b]);
-    }
-    return tr;
-}
-// the host's order: a non-canonical element, the lowest claim whose evaluation fails, the lowest failing query; "" = accepted
-static std::string bnpcs_cells_reason(const u64* cells, size_t n) {
-    if (cells[0] != BNPCSV_NONE) return pcs::reason_noncanonical((size_t)cells[0]);
-    if (cells[1] != BNPCSV_NONE) return pcs::reason_evaluation((size_t)cells[1]);
-    if (cells[2] == BNPCSV_NONE) return "";
-    const size_t q = (size_t)(cells[2] / (n + 2)), kind = (size_t)(cells[2] % (n + 2));
-    return kind == 0 ? pcs::reason_merkle(q) : kind == 1 ? pcs::reason_proximity(q) : pcs::reason_claim(kind - 2, q);
-}
-
-// hg_pcs_verify_device_bn254: a group of one member, whose opening in the arena is the set. Everything but the last kernel needs no
-// column index, so it is enqueued first and runs while the host hashes the u_i; the indices follow on the same stream, then the
-// three result cells come back: one synchronisation. The leaf sponge (serial: 4R + 1 words a thread, Q threads) is the longest of the
-// early kernels and goes last among them, so the two verdicts that need no index and the inner products never wait behind it; the
-// host's own hash of the u_i covers it.
-std::string pcs_verify_device(hg_ctx* ctx, const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof, size_t len) {
-    const size_t C = sh.C(), N = sh.N(), R = sh.R, n = claims.size();
-    const int depth = sh.depth();
-    const std::string bad_len = pcs::length_reason(len, pcs_opening_bytes(sh, n, Q));
-    if (!bad_len.empty()) return bad_len;
-    const size_t u_el = C * (n + 1), q_el = R + (size_t)depth, njobs = n + 1;
-    hipc(hipSetDevice(ctx->device), "hipSetDevice");
-    ctx->arena_reset();
-    hipStream_t st = ctx->stream;
-    // the member's descriptor and its block in one staged copy
-    const size_t nw = bnpcs_weights_of(sh, claims);
-    BnVbMember desc{};   // (every offset into the set and the arena buffers is 0)
-    desc.n = n;
-    std::vector<char> stage(bnpcs_block_layout(desc, sh, n, nw, sizeof(BnVbMember)));
-    static_assert(sizeof(BnVbMember) % 32 == 0, "the block starts at a multiple of 32");
-    memcpy(stage.data(), &desc, sizeof(BnVbMember));
-    FsTranscript tr = bnpcs_block_fill(stage.data(), desc, sh, root, claims, Q);
-    u64 *d_proof, *d_leaves, *d_js, *d_cells;
-    Fr *d_u, *d_cols, *d_enc, *d_tmp, *d_W, *d_s;
-    char* d_stage;
-    try {
-        d_proof = ctx->alloc_n<u64>(len / 8);
-        d_stage = ctx->alloc_n<char>(stage.size());
-        d_u = ctx->alloc_n<Fr>(u_el);
-        d_cols = ctx->alloc_n<Fr>(Q * R);
-        d_enc = ctx->alloc_n<Fr>(njobs * N);
-        d_tmp = ctx->alloc_n<Fr>(njobs * N);
-        d_W = ctx->alloc_n<Fr>(N);
-        d_leaves = ctx->alloc_n<u64>(4 * Q);
-        d_s = ctx->alloc_n<Fr>(Q * njobs);
-        d_js = ctx->alloc_n<u64>(Q);
-        d_cells = ctx->alloc_n<u64>(4);
-    } catch (const std::exception& e) {
-        throw Error(std::string("the context's arena cannot hold the opening (") + e.what() + ")");
-    }
-    pcs::DrainOne drain{st};   // (drains on an error; after the synchronisation below its own is one more, on an idle stream)
-    const int cls = ctx->prof_class("pcs_bn254_verify", false);
-    ctx->prof_stream = st;
-    const BnVbMember* d_mem = reinterpret_cast<const BnVbMember*>(d_stage);
-    const BnVbGroup vg{1, (u64)Q, (u64)R, (u64)q_el, sh.c, depth};
-    const size_t bq = bnpcs_blocks(Q);   // k_bnpcsvb_dots: the workgroups of a job
-    hipc(hipMemcpyAsync(d_proof, proof, len, hipMemcpyHostToDevice, st), "upload opening");
-    hipc(hipMemcpyAsync(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, st), "upload claims");
-    hipc(hipMemsetAsync(d_cells, 0xff, 32, st), "memset");
-    hipc(hipMemsetAsync(d_enc, 0, njobs * N * sizeof(Fr), st), "memset");
-    ctx->prof_begin(cls, (double)(u_el + Q * R) * 64 + (double)u_el * 32);
-    k_bnpcsvb_canon<<<(unsigned)std::min<size_t>(bnpcs_blocks(u_el + Q * R), 4096), BNPCS_TPB, 0, st>>>(d_proof, d_mem, vg, d_u, d_cols, d_enc, d_cells);
-    ctx->prof_end();
-    if (n) {
-        ctx->prof_begin(cls, (double)n * C * 32);
-        k_bnpcsvb_eval<<<(unsigned)n, BNPCS_TPB, 0, st>>>(d_mem, 1, sh.c, d_u, d_stage, d_cells);
-        ctx->prof_end();
-    }
-    ctx->prof_begin(cls, (double)njobs * N * 32 * 4);
-    k_bn_powers<<<bnpcs_blocks(N), 256, 0, st>>>(d_W, fr_root_of_unity(depth), N);
-    ntt_batch_dev(st, d_enc, d_tmp, d_W, depth, njobs, nullptr);
-    ctx->prof_end();
-    if (Q) {
-        ctx->prof_begin(cls, (double)Q * nw * 64);
-        k_bnpcsvb_dots<<<(unsigned)(bq * njobs), BNPCS_TPB, 0, st>>>(d_mem, vg, (unsigned)bq, d_cols, d_stage, d_s);
-        ctx->prof_end();
-        ctx->prof_begin(cls, (double)Q * R * 32);
-        k_bnpcsvb_leaf<<<bnpcs_blocks(Q), BNPCS_TPB, 0, st>>>(d_mem, vg, d_cols, d_leaves);
-        ctx->prof_end();
-    }
-    // the host's share, beside the kernels: the u_i into the transcript, the column indices out of it
-    {
-        std::vector<Fr> u(u_el);
-        for (size_t i = 0; i < u_el; i++) u[i] = pcs_read_be32(proof + 32 * i);
-        pcs_absorb(tr, u.data(), u_el);
-    }
-    const std::vector<size_t> js = pcs_squeeze_indices(tr, N, Q);
-    const std::vector<u64> hj(js.begin(), js.end());
-    if (Q) {
-        hipc(hipMemcpyAsync(d_js, hj.data(), Q * 8, hipMemcpyHostToDevice, st), "upload column indices");
-        ctx->prof_begin(cls, (double)Q * (32.0 * depth + 64.0 * njobs));
-        k_bnpcsvb_query<<<bnpcs_blocks(Q), BNPCS_TPB, 0, st>>>(d_proof, d_mem, vg, d_leaves, d_s, d_enc, d_js, d_stage, d_cells);
-        ctx->prof_end();
-    }
-    u64 cells[4];
-    hipc(hipMemcpyAsync(cells, d_cells, 32, hipMemcpyDeviceToHost, st), "download verdict");
-    hipc(hipStreamSynchronize(st), "hg_pcs_verify_device_bn254: sync");
-    hipc(hipGetLastError(), "hg_pcs_verify_device_bn254: launch");
-    ctx->prof_collect();
-    return bnpcs_cells_reason(cells, n);
-}
-
-// hg_pcs_verify_device_batch_bn254. The items whose length is right are cut into groups (the option verify_batch_group, VB_PCS_BUDGET
-// over what a member takes in 32-byte elements, the transforms ntt_batch_dev takes on its four-step path). A group: its openings
-// gathered into a page-locked set on the host threads and copied on the upload stream; every member's transcript start, rho powers
-// and weight tables written into one staged copy, one member a task; the index-free kernels, one launch each over all members, the
-// leaf sponge last among them as in the single call; the members' u_i hashed on the host threads meanwhile; all indices up, the
-// query kernel, three cells a member down: one synchronisation a group. The next group's openings are gathered and copied into the
-// other set before that synchronisation, under this group's kernels.
-std::vector<std::string> pcs_verify_device_batch(const char* who_c, hg_ctx* ctx, const pcs::Shape& sh, const std::vector<VerifyItem>& items, size_t Q) {
-    const std::string who(who_c);
-    const size_t C = sh.C(), N = sh.N(), R = sh.R;
-    const int depth = sh.depth();
-    const size_t q_el = R + (size_t)depth;
-    const bool four_step = depth >= 8 && depth <= 16;
-    std::vector<std::string> why(items.size());
-    std::vector<size_t> good;   // the items that reach the device
-    for (size_t i = 0; i < items.size(); i++) {
-        why[i] = pcs::length_reason(items[i].len, pcs_opening_bytes(sh, items[i].claims->size(), Q));
-        if (why[i].empty()) good.push_back(i);
-    }
-    if (good.empty()) return why;
-    // what a member takes: its opening in a set; u, columns, enc rows and as many for the NTT temporary, s (32 bytes an element),
-    // leaves and indices in the arena
-    auto rows_of = [](size_t n) { return n + 1; };
-    auto bytes_of = [&](size_t n, size_t len) { return len + sizeof(Fr) * (C * (n + 1) + Q * R + 2 * rows_of(n) * N + Q * (n + 1)) + 8 * 5 * Q; };
-    size_t cap = VB_MAX_GROUP;
-    if (ctx->verify_batch_group > 0) cap = std::min<size_t>(cap, (size_t)ctx->verify_batch_group);
-    constexpr size_t NTT_ROWS = 65535;   // ntt_batch_dev: the batch is the y extent of its four-step grids
+    static void absorb_u(FsTranscript& tr, const u64* words, size_t n_words) { pcs_absorb(tr, reinterpret_cast<const Fr*>(words), n_words / 4); }
+    static std::vector<size_t> squeeze_indices(FsTranscript& tr, size_t N, size_t Q) { return pcs_squeeze_indices(tr, N, Q); }
+    // limits and sizes
+    static bool ntt_needs_tmp(int) { return true; }   // ntt_batch_dev goes through a temporary on either path
     // k_bnpcsvb_dots: bq workgroups a job (a member's jobs are its rows) in one x extent, and a launch takes fewer than 2^32 threads.
     // One member is at most 4097 jobs of 256 workgroups, far inside it.
-    const size_t bq = bnpcs_blocks(Q), DOTS_BLOCKS = (((size_t)1 << 32) / BNPCS_TPB - 1) / bq;
-    std::vector<std::pair<size_t, size_t>> groups;   // [first, last) of good
-    for (size_t a = 0; a < good.size();) {
-        size_t b = a, bytes = 0, rows = 0;
-        while (b < good.size() && b - a < cap) {
-            const size_t n = items[good[b]].claims->size();
-            if (b > a && (bytes + bytes_of(n, items[good[b]].len) > VB_PCS_BUDGET || (four_step && rows + rows_of(n) > NTT_ROWS) || rows + rows_of(n) > DOTS_BLOCKS)) break;
-            bytes += bytes_of(n, items[good[b]].len);
-            rows += rows_of(n);
-            b++;
-        }
-        groups.push_back({a, b});
-        a = b;
+    static size_t dots_max_rows(size_t Q) { return (((size_t)1 << 32) / BNPCS_TPB - 1) / bnpcs_blocks(Q); }
+    // the committer's temporary is one slice's: at least one member, else what fits in here (the slices follow each other on the
+    // stream, so the temporary does not grow with the group)
+    static constexpr size_t COMMIT_BUDGET = VB_PCS_COMMIT_BUDGET_BN254, NTT_TMP = (size_t)256 << 20;
+    static size_t commit_member_bytes(size_t R, size_t C, size_t N) { return sizeof(Fr) * (R * C + R * N); }   // its rows and encoded rows in the slab
+    // a freed group's allocation, if the context holds one that fits (pcs::SlabSpares); the slab goes back there with its last handle
+    static void slab_spare(hg_ctx* ctx, pcs::Slab& slab, size_t bytes) {
+        slab.home = batch_bufs(ctx)->slabs;
+        slab.p = slab.home->take(bytes, &slab.bytes);
     }
-    hipc(hipSetDevice(ctx->device), "hipSetDevice");
-    VerifyBatchBufs* B = batch_bufs(ctx);
-    hipStream_t st = ctx->stream;
-    std::vector<u64> hj, cells;   // (declared ahead of the guard: copies of them may be queued when it drains)
-    pcs::DrainOne drain_up{B->up}, drain{st};   // (the upload stream as well: no kernel on a set left behind)
-    hipc(hipStreamSynchronize(st), (who + ": synchronise").c_str());   // (the arena is reset below)
-    [[maybe_unused]] const int nthr = std::max(1, hg_omp_threads());   // (the device pass of hipcc ignores the pragmas)
-    const int cls = ctx->prof_class("pcs_bn254_verify_batch", false);
-    ctx->prof_stream = st;
 
-    struct Member { size_t idx, n, nw; FsTranscript tr; std::string error; };
-    // the openings of group g into set g & 1, at word offsets that the descriptors repeat
-    auto proof_offsets = [&](size_t g) {
-        std::vector<size_t> off;
-        size_t at = 0;
-        for (size_t x = groups[g].first; x < groups[g].second; x++) { off.push_back(at); at += items[good[x]].len / 8; }
-        off.push_back(at);
-        return off;
-    };
-    auto stage = [&](size_t g) {
-        const std::vector<size_t> off = proof_offsets(g);
-        std::vector<BatchBlob> blobs;
-        for (size_t x = groups[g].first; x < groups[g].second; x++) blobs.push_back(BatchBlob{items[good[x]].proof, items[good[x]].len, off[x - groups[g].first]});
-        batch_stage_blobs(B, (int)(g & 1), blobs, off.back(), nthr, who_c);
-    };
-    const bool times = hg_times("pcs");   // HG_TIMES=pcs: where a group's wall clock goes, on stderr
-    double t_stage = omp_get_wtime();
-    stage(0);
-    t_stage = omp_get_wtime() - t_stage;
-    for (size_t g = 0; g < groups.size(); g++) {
-        const double t0 = omp_get_wtime();
-        const size_t G = groups[g].second - groups[g].first;
-        const int set = (int)(g & 1);
-        std::vector<Member> mem(G);
-        std::vector<BnVbMember> desc(G);
-        const std::vector<size_t> poff = proof_offsets(g);
-        // the layout of the staged copy: the descriptors, then every member's block, and of the arena buffers
-        size_t at = (G * sizeof(BnVbMember) + 31) & ~(size_t)31, u_at = 0, row_at = 0, claim_at = 0;
-        for (size_t m = 0; m < G; m++) {
-            Member& x = mem[m];
-            const VerifyItem& it = items[good[groups[g].first + m]];
-            x.idx = good[groups[g].first + m];
-            x.n = it.claims->size();
-            x.nw = bnpcs_weights_of(sh, *it.claims);
-            BnVbMember& d = desc[m];
-            d.proof = poff[m]; d.u = u_at; d.cols = m * Q * R; d.enc_row = row_at;
-            d.n = x.n; d.claim0 = claim_at; d.job0 = claim_at + m;
-            at = bnpcs_block_layout(d, sh, x.n, x.nw, at);
-            u_at += C * (x.n + 1);
-            row_at += rows_of(x.n);
-            claim_at += x.n;
-        }
-        const size_t stage_bytes = at, u_total = u_at, rows = row_at, claims_total = claim_at, jobs_total = claim_at + G;
-        char* h_stage = batch_desc_host(B, stage_bytes);   // (the previous group's copy of it was waited for)
-        memcpy(h_stage, desc.data(), G * sizeof(BnVbMember));
-#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
-        for (long long mq = 0; mq < (long long)G; mq++) {
-            Member& x = mem[mq];
-            try {
-                const VerifyItem& it = items[x.idx];
-                x.tr = bnpcs_block_fill(h_stage, desc[mq], sh, it.root, *it.claims, Q);
-            } catch (const std::exception& e) { x.error = e.what(); }
-        }
-        for (const Member& x : mem)
-            if (!x.error.empty()) throw Error(who + ": index " + std::to_string(x.idx) + ": " + x.error);
-        const double t1 = omp_get_wtime();
-        ctx->arena_reset();
-        u64 *d_leaves, *d_js, *d_cells;
-        Fr *d_u, *d_cols, *d_enc, *d_tmp, *d_W, *d_s;
-        char* d_stage;
-        try {
-            d_stage = ctx->alloc_n<char>(stage_bytes);
-            d_u = ctx->alloc_n<Fr>(u_total);
-            d_cols = ctx->alloc_n<Fr>(G * Q * R);
-            d_enc = ctx->alloc_n<Fr>(rows * N);
-            d_tmp = ctx->alloc_n<Fr>(rows * N);
-            d_W = ctx->alloc_n<Fr>(N);
-            d_leaves = ctx->alloc_n<u64>(4 * G * Q);
-            d_s = ctx->alloc_n<Fr>(Q * jobs_total);
-            d_js = ctx->alloc_n<u64>(G * Q);
-            d_cells = ctx->alloc_n<u64>(3 * G);
-        } catch (const std::exception& e) {
-            throw Error(who + ": the context's arena cannot hold " + (G == 1 ? "the opening at index " + std::to_string(mem[0].idx) : "a group of " + std::to_string(G) + " openings: lower verify_batch_group") +
-                        " (" + e.what() + ")");
-        }
-        const u64* d_set = B->d_in[set];
-        const BnVbMember* d_mem = reinterpret_cast<const BnVbMember*>(d_stage);
-        const BnVbGroup vg{(u64)G, (u64)Q, (u64)R, (u64)q_el, sh.c, depth};
-        size_t el_max = 0, nw_total = 0;
-        for (const Member& x : mem) { el_max = std::max(el_max, C * (x.n + 1) + Q * R); nw_total += x.nw; }
-        hipc(hipStreamWaitEvent(st, B->ev[set], 0), "hipStreamWaitEvent");   // the set's openings are up
-        hipc(hipMemcpyAsync(d_stage, h_stage, stage_bytes, hipMemcpyHostToDevice, st), "upload claims");
-        hipc(hipMemsetAsync(d_cells, 0xff, 3 * G * 8, st), "memset");
-        hipc(hipMemsetAsync(d_enc, 0, rows * N * sizeof(Fr), st), "memset");
-        ctx->prof_begin(cls, (double)(u_total + G * Q * R) * 64 + (double)u_total * 32);
-        k_bnpcsvb_canon<<<dim3((unsigned)std::min<size_t>(bnpcs_blocks(el_max), 1024), (unsigned)G), BNPCS_TPB, 0, st>>>(d_set, d_mem, vg, d_u, d_cols, d_enc, d_cells);
-        ctx->prof_end();
-        if (claims_total) {
-            ctx->prof_begin(cls, (double)claims_total * C * 32);
-            k_bnpcsvb_eval<<<(unsigned)claims_total, BNPCS_TPB, 0, st>>>(d_mem, (unsigned)G, sh.c, d_u, d_stage, d_cells);
-            ctx->prof_end();
-        }
-        ctx->prof_begin(cls, (double)rows * N * 32 * 4);
-        k_bn_powers<<<bnpcs_blocks(N), 256, 0, st>>>(d_W, fr_root_of_unity(depth), N);
-        ntt_batch_dev(st, d_enc, d_tmp, d_W, depth, rows, nullptr);
-        ctx->prof_end();
-        ctx->prof_begin(cls, (double)Q * nw_total * 64);
-        k_bnpcsvb_dots<<<(unsigned)(bq * jobs_total), BNPCS_TPB, 0, st>>>(d_mem, vg, (unsigned)bq, d_cols, d_stage, d_s);
-        ctx->prof_end();
-        ctx->prof_begin(cls, (double)G * Q * R * 32);
-        k_bnpcsvb_leaf<<<bnpcs_blocks(G * Q), BNPCS_TPB, 0, st>>>(d_mem, vg, d_cols, d_leaves);
-        ctx->prof_end();
-        // the host's share, beside the kernels: every member's u_i into its transcript, its column indices out of it
-        const double t2 = omp_get_wtime();
-        hj.assign(G * Q, 0);
-#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
-        for (long long mq = 0; mq < (long long)G; mq++) {
-            Member& x = mem[mq];
-            try {
-                const uint8_t* proof = items[x.idx].proof;
-                const size_t u_el = C * (x.n + 1);
-                std::vector<Fr> u(u_el);
-                for (size_t i = 0; i < u_el; i++) u[i] = pcs_read_be32(proof + 32 * i);
-                pcs_absorb(x.tr, u.data(), u_el);
-                const std::vector<size_t> js = pcs_squeeze_indices(x.tr, N, Q);
-                for (size_t q = 0; q < Q; q++) hj[(size_t)mq * Q + q] = js[q];
-            } catch (const std::exception& e) { x.error = e.what(); }
-        }
-        for (const Member& x : mem)
-            if (!x.error.empty()) throw Error(who + ": index " + std::to_string(x.idx) + ": " + x.error);
-        const double t3 = omp_get_wtime();
-        hipc(hipMemcpyAsync(d_js, hj.data(), G * Q * 8, hipMemcpyHostToDevice, st), "upload column indices");
-        ctx->prof_begin(cls, (double)G * Q * 32.0 * depth + (double)Q * jobs_total * 64.0);
-        k_bnpcsvb_query<<<bnpcs_blocks(G * Q), BNPCS_TPB, 0, st>>>(d_set, d_mem, vg, d_leaves, d_s, d_enc, d_js, d_stage, d_cells);
-        ctx->prof_end();
-        cells.assign(3 * G, 0);
-        hipc(hipMemcpyAsync(cells.data(), d_cells, 3 * G * 8, hipMemcpyDeviceToHost, st), "download verdicts");
-        const double t4 = omp_get_wtime();
-        if (g + 1 < groups.size()) stage(g + 1);   // into the other set, under this group's kernels
-        const double t5 = omp_get_wtime();
-        hipc(hipStreamSynchronize(st), (who + ": sync").c_str());
-        if (times)
-            fprintf(stderr, "[hg pcs] group %zu of %zu members: gather and copy of its openings %.2f ms, transcripts and weights %.2f, enqueue %.2f, hash %.2f, "
-                            "query enqueue %.2f, next group's gather %.2f, wait %.2f\n", g, G, t_stage * 1e3, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3,
-                    (t5 - t4) * 1e3, (omp_get_wtime() - t5) * 1e3);
-        t_stage = t5 - t4;
-        hipc(hipGetLastError(), (who + ": launch").c_str());
-        ctx->prof_collect();
-        for (size_t m = 0; m < G; m++) why[mem[m].idx] = bnpcs_cells_reason(cells.data() + 3 * m, mem[m].n);
-    }
-    return why;
-}
-
-// hg_pcs_commit_batch_bn254. A group: one allocation for its members' raw and encoded rows (a freed group's, where the context
-// holds one that fits: pcs::SlabSpares), the tables (or, `words`, the witness
-// words, lifted by one k_bnpcs_lift over the group) uploaded straight into it, then k_bnpcsb_stage, the encoding in slices of whole
-// members through ONE slice's temporary (the slices follow each other on the stream, so the temporary does not grow with the
-// group), the leaf hashes, the tree levels of pcs::merkle_levels_device_batch, one download of all trees and flags, one
-// synchronisation.
-constexpr size_t BNPCSB_NTT_TMP = (size_t)256 << 20;   // the temporary of one slice: at least one member, else what fits in here
-std::vector<pcs::Commitment*> pcs_commit_device_batch(const char* who_c, hg_ctx* ctx, const pcs::Shape& sh, const u64* const* tables, size_t n, bool words) {
-    const std::string who(who_c);
-    const size_t C = sh.C(), N = sh.N(), R = sh.R, nt = sh.nvars.size();
-    const int log2n = sh.depth();
-    if (R > 65535) throw Error(who + ": more than 65535 rows (choose a larger log2_row)");
-    const size_t tree_words = 8 * N;   // 2N nodes of 4 words: the 2N - 1 of a tree and one unused
-    const size_t member_bytes = sizeof(Fr) * (R * C + R * N);
-    // ntt_batch_dev: the batch is the y extent of its four-step grids, and a slice is at most a group
-    const std::vector<std::pair<size_t, size_t>> groups = pcs::cut_groups(ctx, n, [&](size_t) { return member_bytes; }, R, 65535, VB_PCS_COMMIT_BUDGET_BN254);
-    hipc(hipSetDevice(ctx->device), "hipSetDevice");
-    hipStream_t st = ctx->stream;
-    const std::shared_ptr<pcs::SlabSpares> spares = batch_bufs(ctx)->slabs;
-    std::vector<std::unique_ptr<pcs::Commitment>> made;
-    std::vector<u64> h_out;   // (declared ahead of the guard: a copy into it may be queued when it drains)
-    pcs::DrainOne drain{st};
-    hipc(hipStreamSynchronize(st), (who + ": synchronise").c_str());   // (the arena is reset below)
-    const int cls = ctx->prof_class("pcs_bn254_commit_batch", false);
-    ctx->prof_stream = st;
-    const bool times = hg_times("pcs");   // HG_TIMES=pcs: where a group's wall clock goes, on stderr
-    for (const auto& grp : groups) {
-        const double t0 = omp_get_wtime();
-        const size_t first = grp.first, G = grp.second - grp.first;
-        const size_t slice = std::min(G, std::max<size_t>(1, BNPCSB_NTT_TMP / (R * N * sizeof(Fr))));   // members a slice
-        std::shared_ptr<pcs::Slab> slab = std::make_shared<pcs::Slab>();
-        slab->home = spares;
-        slab->p = spares->take(G * member_bytes, &slab->bytes);   // a freed group's allocation, if the context holds one that fits
-        if (!slab->p) {
-            hipc(hipMalloc((void**)&slab->p, G * member_bytes), "hipMalloc(pcs rows and encoded matrices of a group)");
-            slab->bytes = G * member_bytes;
-        }
-        Fr* d_rows = reinterpret_cast<Fr*>(slab->p);
-        Fr* d_M = d_rows + G * R * C;
-        const double t1 = omp_get_wtime();
-        ctx->arena_reset();
-        Fr *tmp, *W;
-        u64 *d_out, *d_words = nullptr;
-        const size_t out_words = G * tree_words + (G + 1) / 2;   // the trees, then one 32-bit flag a member
-        try {
-            tmp = ctx->alloc_n<Fr>(slice * R * N);
-            W = ctx->alloc_n<Fr>(N);
-            d_out = ctx->alloc_n<u64>(out_words);
-            if (words) d_words = ctx->alloc_n<u64>(G * R * C);
-        } catch (const std::exception& e) {
-            throw Error(who + ": the context's arena cannot hold a group of " + std::to_string(G) + " commitments: lower verify_batch_group (" + e.what() + ")");
-        }
-        unsigned* d_flags = reinterpret_cast<unsigned*>(d_out + G * tree_words);
-        hipc(hipMemsetAsync(d_flags, 0, ((G + 1) / 2) * 8, st), "memset");
-        for (size_t m = 0; m < G; m++)
-            for (size_t t = 0; t < nt; t++) {
-                const size_t len = (size_t)1 << sh.nvars[t], at = (m * R + sh.off[t]) * C;
-                if (words) hipc(hipMemcpyAsync(d_words + at, tables[(first + m) * nt + t], len * 8, hipMemcpyHostToDevice, st), "upload tables");
-                else hipc(hipMemcpyAsync(d_rows + at, tables[(first + m) * nt + t], len * sizeof(Fr), hipMemcpyHostToDevice, st), "upload tables");
-            }
-        const double t2 = omp_get_wtime();
+    // the steps of the committer; words != null: witness words, lifted into the raw rows first
+    static void stage(hg_ctx* ctx, int cls, hipStream_t st, size_t G, size_t R, int c, const u64* words, Fr* rows, Fr* M, unsigned* flags) {
+        const size_t C = (size_t)1 << c, N = (size_t)4 << c;
         ctx->prof_begin(cls, (double)G * R * C * (words ? 40 : 0) + (double)G * R * (C + N) * 32);
-        if (words) k_bnpcs_lift<<<(unsigned)std::min<size_t>(bnpcs_blocks(G * R * C), 4096), BNPCS_TPB, 0, st>>>(d_words, d_rows, G * R * C);
-        k_bnpcsb_stage<<<dim3((unsigned)std::min<size_t>(bnpcs_blocks(R * N), (4096 + G - 1) / G), (unsigned)G), BNPCS_TPB, 0, st>>>(d_rows, d_M, R, sh.c, d_flags);   // about 4096 workgroups in all; G in the grid's y: cut_groups keeps it at VB_MAX_GROUP = 64 or below
+        if (words) k_bnpcs_lift<<<(unsigned)std::min<size_t>(bnpcs_blocks(G * R * C), 4096), BNPCS_TPB, 0, st>>>(words, rows, G * R * C);
+        k_bnpcsb_stage<<<dim3((unsigned)std::min<size_t>(bnpcs_blocks(R * N), (4096 + G - 1) / G), (unsigned)G), BNPCS_TPB, 0, st>>>(rows, M, R, c, flags);   // about 4096 workgroups in all; G in the grid's y: cut_groups keeps it at VB_MAX_GROUP = 64 or below
         ctx->prof_end();
-        ctx->prof_begin(cls, (double)G * R * N * 32 * 4);
-        k_bn_powers<<<bnpcs_blocks(N), 256, 0, st>>>(W, fr_root_of_unity(log2n), N);
-        for (size_t m0 = 0; m0 < G; m0 += slice) ntt_batch_dev(st, d_M + m0 * R * N, tmp, W, log2n, std::min(slice, G - m0) * R, nullptr);
-        ctx->prof_end();
-        ctx->prof_begin(cls, (double)G * R * N * 32);
-        k_bnpcsb_leaf_hash<<<bnpcs_blocks(G * N), BNPCS_TPB, 0, st>>>(d_M, G, log2n, R, d_out, tree_words);
-        ctx->prof_end();
-        ctx->prof_begin(cls, (double)G * N * 96);
-        pcs::merkle_levels_device_batch(st, d_out, tree_words, N, G);
-        ctx->prof_end();
-        h_out.resize(out_words);
-        hipc(hipMemcpyAsync(h_out.data(), d_out, out_words * 8, hipMemcpyDeviceToHost, st), "download trees and flags");
-        const double t3 = omp_get_wtime();
-        hipc(hipStreamSynchronize(st), (who + ": sync").c_str());
-        const double t4 = omp_get_wtime();
-        hipc(hipGetLastError(), (who + ": launch").c_str());
-        ctx->prof_collect();
-        const unsigned* flags = reinterpret_cast<const unsigned*>(h_out.data() + G * tree_words);
-        for (size_t m = 0; m < G; m++)
-            if (flags[m]) throw Error(who + ": index " + std::to_string(first + m) + ": a table holds an element that is not below r");
-        for (size_t m = 0; m < G; m++) {
-            std::unique_ptr<pcs::Commitment> cm(new pcs::Commitment());
-            cm->field = pcs::BN254;
-            cm->sh = sh;
-            cm->ctx = ctx;
-            cm->d_rows = reinterpret_cast<u64*>(d_rows + m * R * C);
-            cm->d_M = reinterpret_cast<u64*>(d_M + m * R * N);
-            cm->owner = slab;
-            const uint8_t* tree = reinterpret_cast<const uint8_t*>(h_out.data() + m * tree_words);
-            cm->tree.assign(tree, tree + 32 * (2 * N - 1));
-            made.push_back(std::move(cm));
-        }
-        if (times)
-            fprintf(stderr, "[hg pcs] bn254 commit group of %zu members (%zu a slice of the encoding): allocation %.2f ms, uploads %.2f, enqueue %.2f, wait %.2f, trees into the handles %.2f\n",
-                    G, slice, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3, (omp_get_wtime() - t4) * 1e3);
     }
-    std::vector<pcs::Commitment*> out;
-    for (auto& cm : made) out.push_back(cm.release());
-    return out;
-}
-
-// hg_pcs_open_batch_bn254, pcs::open_device_batch step for step. A group: the host threads write every member's transcript start,
-// rho powers, weight tables (Montgomery form) and table entries into one staged copy; the combinations, the evaluation checks and
-// the big-endian u vectors run as one launch each; the u vectors and one cell a member come back (first synchronisation); the host
-// threads hash each member's u_i, one member a thread; all indices go up, the gather writes the opened columns into the images, the
-// images come back (second synchronisation); the host copies the siblings from each handle's tree into the gaps.
-std::vector<pcs::Opened> pcs_open_device_batch(const char* who_c, const char* single, hg_ctx* ctx, const std::vector<PcsOpenItem>& items, size_t Q) {
-    const std::string who(who_c);
-    std::vector<pcs::Opened> res(items.size());
-    if (items.empty()) return res;
-    const pcs::Shape& sh = items[0].cm->sh;
-    const size_t C = sh.C(), N = sh.N(), R = sh.R;
-    const int depth = sh.depth();
-    const size_t q_words = 4 * (R + (size_t)depth);   // a query in the image: R elements and `depth` siblings, 4 words each
-    auto align32 = [](size_t x) { return (x + 31) & ~(size_t)31; };
-    auto nw_of = [&](const std::vector<PcsClaim>& cl) { size_t nw = R; for (const PcsClaim& x : cl) nw += (size_t)1 << (sh.nvars[x.table] - sh.c); return nw; };
-    // what a member takes: its block of the staged copy, its u vectors and its image in the arena, its indices
-    auto bytes_of = [&](size_t i) {
-        const std::vector<PcsClaim>& cl = *items[i].claims;
-        return sizeof(BnObMember) + (cl.size() + 1) * sizeof(BnObJob) + cl.size() * (sizeof(BnObClaim) + (size_t)(sh.c + 1) * sizeof(Fr)) + nw_of(cl) * sizeof(Fr) + 128 +
-               sizeof(Fr) * C * (cl.size() + 1) + pcs_opening_bytes(sh, cl.size(), Q) + 8 * Q + 16;
-    };
-    const std::vector<std::pair<size_t, size_t>> groups = pcs::cut_groups(ctx, items.size(), bytes_of, 0, 0);
-    hipc(hipSetDevice(ctx->device), "hipSetDevice");
-    VerifyBatchBufs* B = batch_bufs(ctx);
-    hipStream_t st = ctx->stream;
-    std::vector<u64> hj;   // (declared ahead of the guard: a copy of it may be queued when it drains)
-    pcs::DrainOne drain{st};
-    hipc(hipStreamSynchronize(st), (who + ": synchronise").c_str());   // (the arena is reset below)
-    [[maybe_unused]] const int nthr = std::max(1, hg_omp_threads());   // (the device pass of hipcc ignores the pragmas)
-    const int cls = ctx->prof_class("pcs_bn254_open_batch", false);
-    ctx->prof_stream = st;
-    const bool times = hg_times("pcs");   // HG_TIMES=pcs: where a group's wall clock goes, on stderr
-
-    struct Member { size_t idx, n, nw, job0, claim0, y_at, z_at, w_at, img, u, u_words, len; FsTranscript tr; bool refused = false; std::string error; };
-    for (size_t g = 0; g < groups.size(); g++) {
-        const double t0 = omp_get_wtime();
-        const size_t G = groups[g].second - groups[g].first;
-        std::vector<Member> mem(G);
-        // the layout of the staged copy: the three tables, then every member's values, low coordinates and weights
-        size_t jobs_total = 0, claims_total = 0, u_total = 0, img_total = 0;   // u_total, img_total: words
-        for (size_t m = 0; m < G; m++) {
-            Member& x = mem[m];
-            x.idx = groups[g].first + m;
-            x.n = items[x.idx].claims->size();
-            x.nw = nw_of(*items[x.idx].claims);
-            x.job0 = jobs_total; x.claim0 = claims_total; x.u = u_total; x.img = img_total;
-            x.u_words = 4 * C * (x.n + 1);
-            x.len = pcs_opening_bytes(sh, x.n, Q);
-            jobs_total += x.n + 1; claims_total += x.n; u_total += x.u_words; img_total += x.len / 8;
-        }
-        const size_t mem_at = 0, jobs_at = align32(G * sizeof(BnObMember)), claims_at = jobs_at + align32(jobs_total * sizeof(BnObJob));
-        size_t at = claims_at + align32(claims_total * sizeof(BnObClaim));
-        for (Member& x : mem) {   // (elements of 32 bytes from a multiple of 32 on)
-            x.y_at = at;
-            x.z_at = x.y_at + x.n * sizeof(Fr);
-            x.w_at = x.z_at + x.n * (size_t)sh.c * sizeof(Fr);
-            at = x.w_at + x.nw * sizeof(Fr);
-        }
-        const size_t stage_bytes = std::max<size_t>(at, 32);
-        char* h_stage = batch_desc_host(B, stage_bytes);   // (the previous group's copy of it was waited for)
-        // results of the group, page-locked: the u vectors, the images, one cell a member
-        const size_t hu_at = 0, himg_at = u_total * 8, hcell_at = himg_at + img_total * 8;
-        char* h_out = batch_out_host(B, hcell_at + G * 8);
-        const u64* h_u = reinterpret_cast<const u64*>(h_out + hu_at);
-        uint8_t* h_img = reinterpret_cast<uint8_t*>(h_out + himg_at);
-        const u64* h_cells = reinterpret_cast<const u64*>(h_out + hcell_at);
-#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
-        for (long long mq = 0; mq < (long long)G; mq++) {
-            Member& x = mem[mq];
-            try {
-                const pcs::Commitment& cm = *items[x.idx].cm;
-                const std::vector<PcsClaim>& claims = *items[x.idx].claims;
-                const Fr* rows = reinterpret_cast<const Fr*>(cm.d_rows);
-                x.tr = pcs_start_transcript(sh, cm.root(), claims, Q);
-                const std::vector<Fr> rho = pcs_rho_powers(pcs_squeeze(x.tr), R);
-                BnObMember* hm = reinterpret_cast<BnObMember*>(h_stage + mem_at) + mq;
-                hm->M = reinterpret_cast<const Fr*>(cm.d_M); hm->img = x.img; hm->u = x.u; hm->u_words = x.u_words;
-                BnObJob* hd = reinterpret_cast<BnObJob*>(h_stage + jobs_at) + x.job0;
-                BnObClaim* hc = reinterpret_cast<BnObClaim*>(h_stage + claims_at) + x.claim0;
-                Fr* hy = reinterpret_cast<Fr*>(h_stage + x.y_at);
-                Fr* hz = reinterpret_cast<Fr*>(h_stage + x.z_at);
-                Fr* hw = reinterpret_cast<Fr*>(h_stage + x.w_at);
-                hd[0].src = rows; hd[0].nrows = R; hd[0].w_at = x.w_at; hd[0].u_at = x.u / 4;
-                memcpy(hw, rho.data(), R * sizeof(Fr));
-                size_t off = R;
-                for (size_t i = 0; i < x.n; i++) {
-                    const PcsClaim& cl = claims[i];
-                    const std::vector<Fr> w = pcs_eq_table(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
-                    hd[i + 1].src = rows + (sh.off[cl.table] << sh.c); hd[i + 1].nrows = w.size(); hd[i + 1].w_at = x.w_at + off * sizeof(Fr);
-                    hd[i + 1].u_at = x.u / 4 + (i + 1) * C;
-                    memcpy(hw + off, w.data(), w.size() * sizeof(Fr));
-                    off += w.size();
-                    hy[i] = cl.value;
-                    for (int b = 0; b < sh.c; b++) hz[i * (size_t)sh.c + b] = fr_to_mont(cl.point[b]);
-                    hc[i].u_at = hd[i + 1].u_at; hc[i].z_at = x.z_at + i * (size_t)sh.c * sizeof(Fr); hc[i].y_at = x.y_at + i * sizeof(Fr);
-                    hc[i].member = (u64)mq; hc[i].claim = (u64)i;
-                }
-            } catch (const std::exception& e) { x.error = e.what(); }
-        }
-        for (const Member& x : mem)
-            if (!x.error.empty()) throw Error(who + ": index " + std::to_string(x.idx) + ": " + x.error);
-        const double t1 = omp_get_wtime();
-        ctx->arena_reset();
-        char* d_stage;
-        u64 *d_u, *d_img, *d_js, *d_cells;
-        try {
-            d_stage = ctx->alloc_n<char>(stage_bytes);
-            d_u = ctx->alloc_n<u64>(u_total);
-            d_img = ctx->alloc_n<u64>(img_total);
-            d_js = ctx->alloc_n<u64>(G * Q + G);
-            d_cells = ctx->alloc_n<u64>(G);
-        } catch (const std::exception& e) {
-            throw Error(who + ": the context's arena cannot hold a group of " + std::to_string(G) + " openings: lower verify_batch_group (" + e.what() + ")");
-        }
-        const BnObMember* d_mem = reinterpret_cast<const BnObMember*>(d_stage + mem_at);
+    // the powers of the root and the encoding of `rows` rows, rows_a_call at a time through one temporary
+    static void ntt(hg_ctx* ctx, int cls, hipStream_t st, Fr* a, Fr* tmp, Fr* W, int depth, size_t rows, size_t rows_a_call) {
+        const size_t N = (size_t)1 << depth;
+        ctx->prof_begin(cls, (double)rows * N * 32 * 4);
+        k_bn_powers<<<bnpcs_blocks(N), 256, 0, st>>>(W, fr_root_of_unity(depth), N);
+        for (size_t r0 = 0; r0 < rows; r0 += rows_a_call) ntt_batch_dev(st, a + r0 * N, tmp, W, depth, std::min(rows_a_call, rows - r0), nullptr);
+        ctx->prof_end();
+    }
+    static void leaf_hash(hg_ctx* ctx, int cls, hipStream_t st, const Fr* M, size_t G, int depth, size_t R, u64* trees, size_t tree_words) {
+        ctx->prof_begin(cls, (double)(G << depth) * R * 32);
+        k_bnpcsb_leaf_hash<<<bnpcs_blocks(G << depth), BNPCS_TPB, 0, st>>>(M, G, depth, R, trees, tree_words);
+        ctx->prof_end();
+    }
+    // the steps of the verifiers
+    static void canon(hg_ctx* ctx, int cls, hipStream_t st, unsigned cap, const u64* set, const VbMember* mem, const VbGroup& g, size_t u_total, size_t unit_max, Fr* u, Fr* cols,
+                      Fr* enc, u64* cells) {
+        ctx->prof_begin(cls, (double)(u_total + g.G * g.Q * g.R) * 64 + (double)u_total * 32);
+        k_bnpcsvb_canon<<<dim3((unsigned)std::min<size_t>(bnpcs_blocks(unit_max), cap), (unsigned)g.G), BNPCS_TPB, 0, st>>>(set, mem, g, u, cols, enc, cells);
+        ctx->prof_end();
+    }
+    static void eval(hg_ctx* ctx, int cls, hipStream_t st, const VbMember* mem, const VbGroup& g, size_t claims, const Fr* u, const char* stage, u64* cells) {
+        ctx->prof_begin(cls, (double)(claims << g.c) * 32);
+        k_bnpcsvb_eval<<<(unsigned)claims, BNPCS_TPB, 0, st>>>(mem, (unsigned)g.G, g.c, u, stage, cells);
+        ctx->prof_end();
+    }
+    static void leaf(hg_ctx* ctx, int cls, hipStream_t st, const VbMember* mem, const VbGroup& g, const Fr* cols, u64* leaves) {
+        ctx->prof_begin(cls, (double)g.G * g.Q * g.R * 32);
+        k_bnpcsvb_leaf<<<bnpcs_blocks(g.G * g.Q), BNPCS_TPB, 0, st>>>(mem, g, cols, leaves);
+        ctx->prof_end();
+    }
+    static void dots(hg_ctx* ctx, int cls, hipStream_t st, const VbMember* mem, const VbGroup& g, size_t jobs, size_t nw, const Fr* cols, const char* stage, Fr* s) {
+        const size_t bq = bnpcs_blocks(g.Q);   // the workgroups of a job
+        ctx->prof_begin(cls, (double)g.Q * nw * 64);
+        k_bnpcsvb_dots<<<(unsigned)(bq * jobs), BNPCS_TPB, 0, st>>>(mem, g, (unsigned)bq, cols, stage, s);
+        ctx->prof_end();
+    }
+    static void query(hg_ctx* ctx, int cls, hipStream_t st, const u64* set, const VbMember* mem, const VbGroup& g, size_t jobs, const u64* leaves, const Fr* s, const Fr* enc,
+                      const u64* js, const char* stage, u64* cells) {
+        ctx->prof_begin(cls, (double)g.G * g.Q * 32.0 * g.depth + (double)g.Q * jobs * 64.0);
+        k_bnpcsvb_query<<<bnpcs_blocks(g.G * g.Q), BNPCS_TPB, 0, st>>>(set, mem, g, leaves, s, enc, js, stage, cells);
+        ctx->prof_end();
+    }
+    // the steps of the openers
+    static void combine(hg_ctx* ctx, int cls, hipStream_t st, int c, size_t jobs, size_t nw, size_t u_words, const ObJob* job, const char* stage, Fr* u) {
+        const size_t C = (size_t)1 << c;
         const unsigned cb = bnpcs_blocks(C);
-        if (jobs_total * cb > 0x7fffffffull) throw Error(who + ": a group of " + std::to_string(G) + " openings has too many row combinations for one launch: lower verify_batch_group");
-        hipc(hipMemcpyAsync(d_stage, h_stage, stage_bytes, hipMemcpyHostToDevice, st), "upload claims");
-        hipc(hipMemsetAsync(d_cells, 0xff, G * 8, st), "memset");
-        size_t nw_total = 0;
-        for (const Member& x : mem) nw_total += x.nw;
-        ctx->prof_begin(cls, (double)nw_total * C * 32 + (double)u_total * 8);
-        k_bnpcsob_combine<<<(unsigned)(jobs_total * cb), BNPCS_TPB, 0, st>>>(sh.c, cb, reinterpret_cast<const BnObJob*>(d_stage + jobs_at), d_stage, reinterpret_cast<Fr*>(d_u));
+        ctx->prof_begin(cls, (double)nw * C * 32 + (double)u_words * 8);
+        k_bnpcsob_combine<<<(unsigned)(jobs * cb), BNPCS_TPB, 0, st>>>(c, cb, job, stage, u);
         ctx->prof_end();
-        if (claims_total) {
-            ctx->prof_begin(cls, (double)claims_total * C * 32);
-            k_bnpcsob_eval<<<(unsigned)claims_total, BNPCS_TPB, 0, st>>>(reinterpret_cast<const BnObClaim*>(d_stage + claims_at), sh.c, reinterpret_cast<const Fr*>(d_u), d_stage, d_cells);
-            ctx->prof_end();
-        }
-        ctx->prof_begin(cls, (double)u_total * 16);
-        k_bnpcsob_emit<<<(unsigned)std::min<size_t>(bnpcs_blocks(u_total), 4096), BNPCS_TPB, 0, st>>>(d_mem, (unsigned)G, u_total, d_u, d_img);
-        ctx->prof_end();
-        hipc(hipMemcpyAsync(h_out + hu_at, d_u, u_total * 8, hipMemcpyDeviceToHost, st), "download combinations");
-        hipc(hipMemcpyAsync(h_out + hcell_at, d_cells, G * 8, hipMemcpyDeviceToHost, st), "download evaluation checks");
-        hipc(hipStreamSynchronize(st), (who + ": sync").c_str());
-        hipc(hipGetLastError(), (who + ": launch").c_str());
-        const double t2 = omp_get_wtime();
-        // the host's share: every member's u_i into its transcript, its column indices out of it, one member a thread
-        hj.assign(G * Q + G, 0);
-        size_t active = 0;
-        for (size_t m = 0; m < G; m++) {
-            mem[m].refused = h_cells[m] != BNPCSV_NONE;
-            hj[G * Q + m] = mem[m].refused ? 0 : 1;
-            active += mem[m].refused ? 0 : 1;
-        }
-#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
-        for (long long mq = 0; mq < (long long)G; mq++) {
-            Member& x = mem[mq];
-            if (x.refused) continue;
-            try {
-                pcs_absorb(x.tr, reinterpret_cast<const Fr*>(h_u + x.u), x.u_words / 4);
-                const std::vector<size_t> js = pcs_squeeze_indices(x.tr, N, Q);
-                for (size_t q = 0; q < Q; q++) hj[(size_t)mq * Q + q] = js[q];
-            } catch (const std::exception& e) { x.error = e.what(); }
-        }
-        for (const Member& x : mem)
-            if (!x.error.empty()) throw Error(who + ": index " + std::to_string(x.idx) + ": " + x.error);
-        const double t3 = omp_get_wtime();
-        if (active) {
-            if (Q) {
-                hipc(hipMemcpyAsync(d_js, hj.data(), hj.size() * 8, hipMemcpyHostToDevice, st), "upload column indices");
-                ctx->prof_begin(cls, (double)active * Q * R * 64);
-                k_bnpcsob_gather<<<bnpcs_blocks(G * Q * R), BNPCS_TPB, 0, st>>>(d_mem, G, Q, R, N, q_words, d_js, d_img);
-                ctx->prof_end();
-            }
-            hipc(hipMemcpyAsync(h_img, d_img, img_total * 8, hipMemcpyDeviceToHost, st), "download openings");
-            hipc(hipStreamSynchronize(st), (who + ": sync").c_str());
-            hipc(hipGetLastError(), (who + ": launch").c_str());
-        }
-        ctx->prof_collect();
-        const double t4 = omp_get_wtime();
-        // the siblings from each handle's tree into the gaps; a refused member's reason
-#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
-        for (long long mq = 0; mq < (long long)G; mq++) {
-            Member& x = mem[mq];
-            try {
-                pcs::Opened& out = res[x.idx];
-                const pcs::Commitment& cm = *items[x.idx].cm;
-                if (x.refused) {
-                    const size_t i = (size_t)h_cells[mq];
-                    out.refused = true;
-                    out.reason = std::string(single) + ": claim " + std::to_string(i) + ": the value is not the evaluation of table " + std::to_string((*items[x.idx].claims)[i].table) +
-                                 " at the point";
-                    continue;
-                }
-                const uint8_t* image = h_img + 8 * x.img;
-                out.bytes.assign(image, image + x.len);
-                for (size_t q = 0; q < Q; q++) {
-                    uint8_t* sib = out.bytes.data() + 8 * (x.u_words + q * q_words + 4 * R);
-                    size_t idx = (size_t)hj[(size_t)mq * Q + q];
-                    for (int l = 0; l < depth; l++, idx >>= 1) memcpy(sib + 32 * l, cm.node(l, idx ^ 1), 32);
-                }
-            } catch (const std::exception& e) { x.error = e.what(); }
-        }
-        for (const Member& x : mem)
-            if (!x.error.empty()) throw Error(who + ": index " + std::to_string(x.idx) + ": " + x.error);
-        if (times)
-            fprintf(stderr, "[hg pcs] bn254 open group %zu of %zu members: transcripts and weights %.2f ms, combine, checks and u back %.2f, hash %.2f, gather and images back %.2f, "
-                            "siblings %.2f\n", g, G, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3, (omp_get_wtime() - t4) * 1e3);
     }
-    return res;
+    static void ob_eval(hg_ctx* ctx, int cls, hipStream_t st, const ObClaim* claim, size_t claims, int c, const Fr* u, const char* stage, u64* cells) {
+        ctx->prof_begin(cls, (double)(claims << c) * 32);
+        k_bnpcsob_eval<<<(unsigned)claims, BNPCS_TPB, 0, st>>>(claim, c, u, stage, cells);
+        ctx->prof_end();
+    }
+    static void emit(hg_ctx* ctx, int cls, hipStream_t st, const ObMember* mem, size_t G, size_t u_words, const u64* u, u64* img) {
+        ctx->prof_begin(cls, (double)u_words * 16);
+        k_bnpcsob_emit<<<(unsigned)std::min<size_t>(bnpcs_blocks(u_words), 4096), BNPCS_TPB, 0, st>>>(mem, (unsigned)G, u_words, u, img);
+        ctx->prof_end();
+    }
+    static void gather(hg_ctx* ctx, int cls, hipStream_t st, const ObMember* mem, size_t G, size_t Q, size_t R, size_t N, size_t q_words, size_t active, const u64* js, u64* img) {
+        ctx->prof_begin(cls, (double)active * Q * R * 64);
+        k_bnpcsob_gather<<<bnpcs_blocks(G * Q * R), BNPCS_TPB, 0, st>>>(mem, G, Q, R, N, q_words, js, img);
+        ctx->prof_end();
+    }
+    static void gather_one(hipStream_t st, const Fr* M, size_t N, size_t R, size_t Q, const u64* js, Fr* cols) {
+        k_bnpcs_gather<<<dim3(bnpcs_blocks(R), (unsigned)Q), BNPCS_TPB, 0, st>>>(M, N, R, js, cols);
+    }
+};
+
+void pcs_combine_device(const pcs::Commitment& cm, const std::vector<PcsJob>& jobs, Fr* u) { pcs::combine_flow<BnPcs>(cm, jobs, u); }
+void pcs_columns_device(const pcs::Commitment& cm, const std::vector<size_t>& js, Fr* cols) { pcs::columns_flow<BnPcs>(cm, js, cols); }
+std::string pcs_verify_device(hg_ctx* ctx, const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof, size_t len) {
+    return pcs::verify_flow<BnPcs>(ctx, sh, root, claims, Q, proof, len);
 }
+std::vector<std::string> pcs_verify_device_batch(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const std::vector<VerifyItem>& items, size_t Q) {
+    return pcs::verify_batch_flow<BnPcs>(who, ctx, sh, items, Q);
+}
+std::vector<pcs::Commitment*> pcs_commit_device_batch(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const u64* const* tables, size_t n, bool words) {
+    return pcs::commit_batch_flow<BnPcs>(who, ctx, sh, tables, n, words);
+}
+std::vector<pcs::Opened> pcs_open_device_batch(const char* who, const char* single, hg_ctx* ctx, const std::vector<PcsOpenItem>& items, size_t Q) {
+    return pcs::open_batch_flow<BnPcs>(who, single, ctx, items, Q);
+}
+
