@@ -57,6 +57,7 @@ EXPORTS = [
     "hg_pcs_verify_device", "hg_claims_verify_device", "hg_pcs_verify_device_batch", "hg_claims_verify_batch",
     "hg_pcs_commit_batch", "hg_secrets_commit_batch", "hg_pcs_open_batch", "hg_claims_open_batch",
     "hg_secrets_commit_values", "hg_prove_encryptions_committed", "hg_prove_encryptions_committed_bn254",
+    "hg_instance_digest", "hg_instance_digest_batch", "hg_values_instance_digest", "hg_bound_seed", "hg_prove_committed_mode", "hg_verify_public_bound", "hg_verify_public_bound_device",
     "hg_pcs_commit_bn254", "hg_pcs_open_bn254", "hg_pcs_verify_bn254", "hg_secrets_commit_bn254", "hg_claims_open_bn254", "hg_claims_verify_bn254",
     "hg_pcs_verify_device_bn254", "hg_claims_verify_device_bn254", "hg_pcs_verify_device_batch_bn254", "hg_claims_verify_batch_bn254",
     "hg_pcs_commit_batch_bn254", "hg_secrets_commit_batch_bn254", "hg_pcs_open_batch_bn254", "hg_claims_open_batch_bn254",
@@ -112,6 +113,14 @@ def _two_field_protos(L):
     L.hg_pcs_commit_batch.argtypes = L.hg_pcs_commit_batch_bn254.argtypes = [vp, C.POINTER(C.POINTER(u64p)), u32p, sz, sz, sz, C.POINTER(vp), u8p]
     L.hg_secrets_commit_batch.argtypes = L.hg_secrets_commit_batch_bn254.argtypes = [vp, C.POINTER(HgParams), C.POINTER(vp), sz, sz, C.POINTER(vp), u8p]
     L.hg_secrets_commit_values.argtypes = [vp, vp, vp, sz, C.POINTER(vp), u8p]   # ctx, key, values, log2_row, handle out, root out
+    # bound proofs: a 32-byte root or digest goes in as bytes and comes out through a u8 array
+    L.hg_instance_digest.argtypes = [vp, vp, u8p]
+    L.hg_instance_digest_batch.argtypes = [vp, C.POINTER(vp), sz, u8p]
+    L.hg_values_instance_digest.argtypes = [vp, vp, vp, u8p]
+    L.hg_bound_seed.argtypes = [C.POINTER(HgParams), ci, cp, cp, u8p, sz, szp]
+    L.hg_prove_committed_mode.argtypes = [vp, vp, vp, ci, sz, vp, sz, szp, C.POINTER(vp), u8p, C.POINTER(HgTimings)]
+    L.hg_verify_public_bound.argtypes = [vp, vp, ci, cp, cp, sz] + room
+    L.hg_verify_public_bound_device.argtypes = [vp, vp, vp, ci, cp, cp, sz] + room
     pp = C.POINTER(i64p)
     L.hg_prove_encryptions_committed.argtypes = L.hg_prove_encryptions_committed_bn254.argtypes = [
         vp, vp, pp, pp, pp, pp, sz, sz, vp, sz, szp, C.POINTER(ci), C.POINTER(vp), u8p, C.POINTER(vp), cp, sz, C.POINTER(HgTimings)]
@@ -1145,6 +1154,61 @@ def verify_public(pk, instance, proof, mode=0, ctx=None, device=False):
     """hg_verify_public (device=True: hg_verify_public_device on ctx): the part of BfvEncrypt::verify that the key, the proof, a_i
     and ct0_i decide. Returns (accepted, reason, InputClaims or None): the claims left on the secret inputs, for claims_settle."""
     return _verify_public(InputClaims, pk, instance, proof, (mode,), ctx, device)
+
+
+def verify_public_bound(pk, instance, proof, root, mode=3, ctx=None, device=False):
+    """hg_verify_public_bound (device=True: hg_verify_public_bound_device on ctx): verify_public for a proof of prove_committed_mode,
+    whose transcript starts from the key's parameters, the digest of `instance` and `root`, the 32-byte root of the commitment to the
+    secret inputs. Returns (accepted, reason, InputClaims or None); HgError for mode 0 or 2."""
+    nc, nco = pk_claim_shape(pk)
+    claims = (HgInputClaim * max(nc, 1))()
+    points = np.zeros(2 * max(nco, 1), dtype=np.uint64)
+    n = C.c_size_t(0)
+    args = (pk.h, instance.h, mode, root, proof, len(proof), claims, nc, _ptr(points), nco, C.byref(n))
+    L = lib()
+    ok, why = _decision(L.hg_verify_public_bound_device(_h(ctx), *args) if device else L.hg_verify_public_bound(*args))
+    return ok, why, (InputClaims(claims, n.value, points) if ok else None)
+
+
+def instance_digest(instance, ctx=None):
+    """hg_instance_digest: the 32-byte statement digest of an Instance (the Keccak tree of include/hg.h over its 2kn signed words);
+    ctx None: the host tree, else the digest kernel."""
+    out = (C.c_uint8 * 32)()
+    _check(lib().hg_instance_digest(_h(ctx), instance.h, out))
+    return bytes(out)
+
+
+def instance_digest_batch(ctx, instances):
+    """hg_instance_digest_batch: the digests of a run of Instances of one parameter set, one launch over all of them."""
+    n = len(instances)
+    hs = (C.c_void_p * max(n, 1))(*[i.h for i in instances])
+    out = (C.c_uint8 * (32 * max(n, 1)))()
+    _check(lib().hg_instance_digest_batch(_h(ctx), hs, n, out))
+    return [bytes(out[32 * i:32 * (i + 1)]) for i in range(n)]
+
+
+def values_instance_digest(ctx, pk, values):
+    """hg_values_instance_digest: the same digest read from the resident ais and ct0is tables of a ResidentValues of this key."""
+    out = (C.c_uint8 * 32)()
+    _check(lib().hg_values_instance_digest(_h(ctx), pk.h, values.h if values is not None else None, out))
+    return bytes(out)
+
+
+def bound_seed(params, mode, digest, root):
+    """hg_bound_seed: the bytes a bound transcript starts from."""
+    out, n = (C.c_uint8 * 256)(), C.c_size_t(0)
+    _check(lib().hg_bound_seed(C.byref(params), mode, digest, root, out, 256, C.byref(n)))
+    return bytes(out[:n.value])
+
+
+def prove_committed_mode(ctx, pk, values, out, mode=3, log2_row=0):
+    """hg_prove_committed_mode: commits to the secret inputs of a ResidentValues (the Commitment of Commitment.from_values), digests
+    its public tables and proves in `mode` (1 or 3) on the transcript seeded with both. Returns (out, Commitment)."""
+    h, root = C.c_void_p(), (C.c_uint8 * 32)()
+    _check(lib().hg_prove_committed_mode(_h(ctx), pk.h, values.h if values is not None else None, mode, log2_row, out.buf, out.cap, C.byref(out.len), C.byref(h), root,
+                                         C.byref(out.tm)))
+    nvars = _secrets_nvars(pk.params)
+    return out, Commitment(h, bytes(root), ctx, nvars, pcs_row_log2(nvars, log2_row))
 
 
 def verify_public_bn254(pk, instance, proof, ctx=None, device=False):

@@ -126,8 +126,10 @@ struct GlAbi {
         for (size_t i = 0; i < nv; i++) pt[i] = elem(point + 2 * i);
         return pt;
     }
-    static std::string verify_public(hg_ctx* ctx, bool device, const hg_pk* pk, const Instance& inst, const uint8_t* proof, size_t len, int mode, std::vector<Open>& open) {
-        return device ? verify_public_device(ctx, pk, inst, proof, len, mode, open) : hg::verify_public(pk->params, pk->lasso, pk->circuit, inst, proof, len, mode, open);
+    // root (hg_verify_public_bound*, else null): the walk of a bound proof
+    static std::string verify_public(hg_ctx* ctx, bool device, const hg_pk* pk, const Instance& inst, const uint8_t* proof, size_t len, int mode, std::vector<Open>& open,
+                                     const uint8_t* root) {
+        return device ? verify_public_device(ctx, pk, inst, proof, len, mode, open, root) : hg::verify_public(pk->params, pk->lasso, pk->circuit, inst, proof, len, mode, open, root);
     }
     static std::string settle(hg_ctx* ctx, const Params& p, const Witness& w, const std::vector<Open>& cl) { return ctx ? claims_settle_device(ctx, p, w, cl) : claims_settle(p, w, cl); }
     static void mle(hg_ctx* ctx, const Params& p, const Instance& inst, int which, int index, const u64* point, size_t nv, u64* out) {
@@ -198,7 +200,8 @@ struct BnAbi {
         memcpy(value, c.value, 32);
         if (!c.point4.empty()) memcpy(point, c.point4.data(), c.point4.size() * 8);
     }
-    static std::string verify_public(hg_ctx* ctx, bool device, const hg_pk* pk, const Instance& inst, const uint8_t* proof, size_t len, int, std::vector<Open>& open) {
+    static std::string verify_public(hg_ctx* ctx, bool device, const hg_pk* pk, const Instance& inst, const uint8_t* proof, size_t len, int, std::vector<Open>& open,
+                                     const uint8_t*) {   // (BN254 has no protocol modes, so no bound proofs)
         return device ? bn::verify_public_device_bn254(ctx, pk, inst, proof, len, open) : verify_public_bn254(pk->params, pk->lasso, pk->circuit, inst, proof, len, open);
     }
     static std::string settle(hg_ctx* ctx, const Params& p, const Witness& w, const std::vector<Open>& cl) { return ctx ? bn::claims_settle_device_bn254(ctx, p, w, cl) : claims_settle_bn254(p, w, cl); }
@@ -345,19 +348,26 @@ static void put_claims(const std::vector<typename A::Open>& open, void* claims, 
     }
 }
 
-// hg_verify_public*, hg_verify_public_device*
+// the entries that bind a proof to its statement (hg.h: "Bound proofs"): modes 1 and 3 only
+static void check_bound_mode(const std::string& who, int mode) {
+    if (mode < 0 || mode > 3) throw Error(who + ": unknown mode bits");
+    if (!(mode & 1)) throw Error(who + ": binding needs the absorbing transcript (mode bit 1)");
+}
+
+// hg_verify_public*, hg_verify_public_device*; bound (hg_verify_public_bound*): the walk of a bound proof against `root`
 template <class A>
 static int verify_public_entry(const char* who, hg_ctx* ctx, bool device, const hg_pk* pk, const void* instance, int mode, const uint8_t* proof, size_t len,
-                               void* claims, size_t claim_cap, uint64_t* points, size_t coord_cap, size_t* n_claims) {
+                               void* claims, size_t claim_cap, uint64_t* points, size_t coord_cap, size_t* n_claims, bool bound = false, const uint8_t* root = nullptr) {
     if (n_claims) *n_claims = 0;
     if (device && (!ctx || !pk || !pk->ctx)) throw Error(std::string(who) + ": needs a device context and a device prover key");
-    if (!pk || !instance || !proof || !n_claims) throw Error(std::string(who) + ": null argument");
+    if (!pk || !instance || !proof || !n_claims || (bound && !root)) throw Error(std::string(who) + ": null argument");
     if (mode < 0 || mode > 3) throw Error(std::string(who) + ": unknown mode bits");
+    if (bound) check_bound_mode(who, mode);
     const hg_instance* in = as_instance(instance);
     check_instance(pk, in, who);
     check_claim_room(who, pk, claims, claim_cap, points, coord_cap, "");
     std::vector<typename A::Open> open;
-    const std::string why = A::verify_public(ctx, device, pk, in->inst, proof, len, mode, open);
+    const std::string why = A::verify_public(ctx, device, pk, in->inst, proof, len, mode, open, bound ? root : nullptr);
     if (!why.empty()) return decision(why);
     check_claim_count<A>(who, open, claim_cap, coord_cap);
     put_claims<A>(open, claims, points);
@@ -584,15 +594,42 @@ static int secrets_commit_entry(const char* who, hg_ctx* ctx, const hg_params* p
     return 0;
 }
 
-// hg_secrets_commit_values: the tables of secrets_commit_entry where hg_witness_gen left them in HBM
-static int secrets_commit_values_entry(const char* who, hg_ctx* ctx, const hg_pk* pk, const hg_values* v, size_t log2_row, void** commitment, uint8_t root[32]) {
-    const std::string w(who);
-    if (commitment) *commitment = nullptr;
-    if (!pk || !v || !commitment || !root) throw Error(w + ": null argument");
+// a values object of this key and this context (hg_secrets_commit_values, hg_values_instance_digest, hg_prove_committed_mode)
+static void check_values_of(const std::string& w, hg_ctx* ctx, const hg_pk* pk, const hg_values* v) {
     if (!ctx) throw Error(w + ": no context");
     if (!pk->ctx) throw Error(w + ": host-only prover key (created without a context)");
     if (v->pk_serial != pk->serial) throw Error(w + ": the values were laid out for another prover key");
     if (v->ctx != ctx || pk->ctx != ctx) throw Error(w + ": the values or the prover key belong to another context");
+}
+
+// where the public tables of a values object lie (the laid-out read of the statement digest): inputs 3 .. 3+k-1 and ct0is
+static pcs::DigestMember values_public_tables(const std::string& w, const hg_pk* pk, const hg_values* v) {
+    const Params& p = pk->params;
+    const std::vector<int>& ids = pk->circuit.input_ids;
+    if (ids.size() != 3 + 2 * (size_t)p.k + 1) throw Error(w + ": unexpected input nodes");
+    pcs::DigestMember mem;
+    memset(&mem, 0, sizeof(mem));
+    for (size_t i = 0; i < (size_t)p.k; i++) {
+        const size_t id = (size_t)ids[3 + i];
+        if (id >= v->d_vals.size() || !v->d_vals[id])
+            throw Error(w + ": input " + std::to_string(3 + i) + " is not resident in these values (a rank's share of hg_witness_gen_shard holds only what the rank reads)");
+        if (v->sizes[id] != p.SZ()) throw Error(w + ": table size mismatch");
+        mem.a[i] = v->d_vals[id];
+    }
+    if (!v->d_ct0is) throw Error(w + ": ct0is is not resident in these values (a rank's share of hg_witness_gen_shard holds only what the rank reads)");
+    if (v->ct0is_len != (size_t)p.k * p.SZ()) throw Error(w + ": table size mismatch");
+    mem.ct0 = v->d_ct0is;
+    return mem;
+}
+
+// hg_secrets_commit_values: the tables of secrets_commit_entry where hg_witness_gen left them in HBM. dg (hg_prove_committed_mode, may be
+// null): the statement digest of the same values object beside the commit
+static int secrets_commit_values_entry(const char* who, hg_ctx* ctx, const hg_pk* pk, const hg_values* v, size_t log2_row, void** commitment, uint8_t root[32],
+                                       pcs::DigestJob* dg = nullptr) {
+    const std::string w(who);
+    if (commitment) *commitment = nullptr;
+    if (!pk || !v || !commitment || !root) throw Error(w + ": null argument");
+    check_values_of(w, ctx, pk, v);
     const Params& p = pk->params;
     const size_t k = (size_t)p.k;
     const std::vector<int>& ids = pk->circuit.input_ids;
@@ -611,11 +648,13 @@ static int secrets_commit_values_entry(const char* who, hg_ctx* ctx, const hg_pk
     }
     const pcs::Shape sh = pcs::make_shape(who, nv.data(), nv.size(), log2_row);
     pcs::Commitment* cm;
+    if (dg) { dg->p = &p; dg->mem = values_public_tables(w, pk, v); }
     try {
-        cm = pcs::commit_device_values(ctx, sh, tabs.data());
+        cm = pcs::commit_device_values(ctx, sh, tabs.data(), dg);
     } catch (const std::exception& e) {
         throw Error(w + ": " + e.what());
     }
+    if (dg && dg->flag) { delete cm; throw Error(w + ": a word of ais or ct0is is not a signed value in [-(q_i-1)/2, (q_i-1)/2]"); }
     memcpy(root, cm->root(), 32);
     *commitment = cm;
     return 0;
@@ -1851,6 +1890,124 @@ int hg_instance_mle(hg_ctx* ctx, const void* instance, int which, int index, con
 
 int hg_instance_mle_batch(hg_ctx* ctx, const void* const* instances, size_t n, int which, int index, const uint64_t* point, size_t nvars, uint64_t* out) {
     HG_ENTRY(instance_mle_entry<GlAbi>("hg_instance_mle_batch", true, ctx, instances, n, which, index, point, nvars, out))
+}
+
+// ---- proofs bound to the secrets' commitment and the ciphertext (hg.h: "Bound proofs") ------------------------------------------
+// hg_instance_digest (batch false: instances is the one handle, ctx may be null: the host tree) and hg_instance_digest_batch
+static int instance_digest_entry(const char* who, bool batch, hg_ctx* ctx, const void* const* instances, size_t n, uint8_t* out) {
+    const std::string w(who);
+    if (batch && !n) return 0;
+    if (!instances || !out) throw Error(w + ": null argument");
+    if (batch && !ctx) throw Error(w + ": no context");
+    std::vector<const Instance*> I(n);
+    for (size_t i = 0; i < n; i++) {
+        if (!instances[i]) throw Error(batch ? w + ": instance " + std::to_string(i) + ": null" : w + ": null argument");
+        const hg_instance* in = as_instance(instances[i]);
+        const hg_params &a = as_instance(instances[0])->params, &b = in->params;
+        if (a.n != b.n || a.k != b.k || memcmp(a.qis, b.qis, sizeof(a.qis[0]) * a.k) != 0) throw Error(w + ": instances of mixed parameters (instance " + std::to_string(i) + ")");
+        I[i] = &in->inst;
+    }
+    const Params p(as_instance(instances[0])->params);
+    std::vector<uint8_t> res(32 * n);   // (an error of the call leaves out alone)
+    if (!ctx) instance_digest_host(p, *I[0], res.data());
+    else {
+        try {
+            pcs::instance_digest_device(ctx, p, I, res.data());
+        } catch (const std::exception& e) {
+            throw Error(w + ": " + e.what());
+        }
+    }
+    memcpy(out, res.data(), res.size());
+    return 0;
+}
+
+int hg_instance_digest(hg_ctx* ctx, const void* instance, uint8_t out32[32]) {
+    HG_ENTRY(instance_digest_entry("hg_instance_digest", false, ctx, &instance, 1, out32))
+}
+
+int hg_instance_digest_batch(hg_ctx* ctx, const void* const* instances, size_t n, uint8_t* out) {
+    HG_ENTRY(instance_digest_entry("hg_instance_digest_batch", true, ctx, instances, n, out))
+}
+
+int hg_values_instance_digest(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, uint8_t out32[32]) {
+    HG_TRY
+    const std::string w = "hg_values_instance_digest";
+    if (!pk || !v || !out32) throw Error(w + ": null argument");
+    check_values_of(w, ctx, pk, v);
+    const pcs::DigestMember mem = values_public_tables(w, pk, v);
+    uint8_t res[32];
+    try {
+        pcs::instance_digest_values(ctx, pk->params, mem, res);
+    } catch (const std::exception& e) {
+        throw Error(w + ": " + e.what());
+    }
+    memcpy(out32, res, 32);
+    return 0;
+    HG_CATCH(-1)
+}
+
+int hg_bound_seed(const hg_params* params, int mode, const uint8_t digest32[32], const uint8_t root32[32], uint8_t* out, size_t cap, size_t* len) {
+    HG_TRY
+    const std::string w = "hg_bound_seed";
+    if (len) *len = 0;
+    if (!params || !digest32 || !root32 || !len) throw Error(w + ": null argument");
+    check_bound_mode(w, mode);
+    try {
+        Params p(*params);
+    } catch (const std::exception& e) {
+        throw Error(w + ": " + e.what());
+    }
+    const std::vector<uint8_t> s = bound_seed(*params, mode, digest32, root32);
+    *len = s.size();
+    if (!out || s.size() > cap) throw Error(w + ": buffer too small (" + std::to_string(s.size()) + " bytes)");
+    memcpy(out, s.data(), s.size());
+    return 0;
+    HG_CATCH(-1)
+}
+
+int hg_prove_committed_mode(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, int mode, size_t log2_row, uint8_t* proof, size_t cap, size_t* len, void** commitment,
+                            uint8_t root[32], hg_timings* timings) {
+    HG_TRY
+    const std::string w = "hg_prove_committed_mode";
+    if (commitment) *commitment = nullptr;
+    if (len) *len = 0;
+    check_bound_mode(w, mode);
+    const double t0 = now_ms_capi();
+    void* h = nullptr;
+    uint8_t rt[32];
+    pcs::DigestJob dg;
+    secrets_commit_values_entry(w.c_str(), ctx, pk, v, log2_row, commitment ? &h : nullptr, root ? rt : nullptr, &dg);
+    std::unique_ptr<pcs::Commitment> cm(static_cast<pcs::Commitment*>(h));   // (an error below drops the handle with it)
+    if (!proof || !len) throw Error(w + ": null argument");
+    const double t1 = now_ms_capi();
+    ProveResult r;
+    try {
+        r = prove_resident_mode(ctx, pk, v, mode, bound_seed(pk->params.raw, mode, dg.digest, rt));
+    } catch (const std::exception& e) {
+        throw Error(w + ": " + e.what());
+    }
+    *len = r.proof.size();
+    if (r.proof.size() > cap) throw Error(w + ": proof buffer too small (" + std::to_string(r.proof.size()) + " bytes)");
+    memcpy(proof, r.proof.data(), r.proof.size());
+    if (timings) {   // as hg_prove_resident_mode; upload_ms: the commit and the digest
+        memset(timings, 0, sizeof(*timings));
+        timings->upload_ms = t1 - t0; timings->prove_ms = r.prove_ms; timings->gpu_ms = r.gpu_ms; timings->total_ms = now_ms_capi() - t0;
+        timings->enqueue_ms = r.enqueue_ms; timings->sync_ms = r.sync_ms; timings->replay_ms = r.replay_ms;
+    }
+    memcpy(root, rt, 32);
+    *commitment = cm.release();
+    return 0;
+    HG_CATCH(-1)
+}
+
+int hg_verify_public_bound(const hg_pk* pk, const void* instance, int mode, const uint8_t root[32], const uint8_t* proof, size_t len, void* claims, size_t claim_cap,
+                           uint64_t* points, size_t coord_cap, size_t* n_claims) {
+    HG_ENTRY(verify_public_entry<GlAbi>("hg_verify_public_bound", nullptr, false, pk, instance, mode, proof, len, claims, claim_cap, points, coord_cap, n_claims, true, root))
+}
+
+int hg_verify_public_bound_device(hg_ctx* ctx, const hg_pk* pk, const void* instance, int mode, const uint8_t root[32], const uint8_t* proof, size_t len, void* claims,
+                                  size_t claim_cap, uint64_t* points, size_t coord_cap, size_t* n_claims) {
+    HG_ENTRY(verify_public_entry<GlAbi>("hg_verify_public_bound_device", ctx, true, pk, instance, mode, proof, len, claims, claim_cap, points, coord_cap, n_claims, true, root))
 }
 
 int hg_verify_bn254(const hg_pk* pk, const hg_witness* w, const uint8_t* proof, size_t len) {

@@ -611,6 +611,46 @@ Instance instance_from_witness(const Params& p, const Witness& w) {
     return out;
 }
 
+// hg_instance_digest on the host (hg.h states the tree byte for byte): the 2kn signed words, a then ct0, in leaves of B = min(128, 2kn)
+// words under the prefix word 2; inner nodes are the commitment's (prefix word 1). The leaves are dealt to the host threads.
+void instance_digest_host(const Params& p, const Instance& inst, uint8_t out[32]) {
+    const size_t kn = (size_t)p.k * p.PZ(), total = 2 * kn, B = std::min<size_t>(DIGEST_LEAF_WORDS, total), leaves = total / B;
+    if (inst.a.size() != kn || inst.ct0.size() != kn) throw Error("hg_instance_digest: the instance does not hold k * n coefficients a table");
+    std::vector<uint8_t> level(32 * leaves);
+    [[maybe_unused]] const int nt = hg_omp_threads();   // (the device pass of hipcc ignores the pragmas)
+#pragma omp parallel for schedule(static) num_threads(nt) if (leaves >= 64)
+    for (long long j = 0; j < (long long)leaves; j++) {
+        int64_t msg[DIGEST_LEAF_WORDS + 1];   // little-endian host: the words are their LE64 encoding
+        msg[0] = 2;
+        for (size_t t = 0; t < B; t++) { const size_t w = (size_t)j * B + t; msg[1 + t] = w < kn ? inst.a[w] : inst.ct0[w - kn]; }
+        keccak256(reinterpret_cast<const uint8_t*>(msg), 8 * (B + 1), level.data() + 32 * j);
+    }
+    for (size_t cnt = leaves / 2; cnt >= 1; cnt /= 2) {
+        std::vector<uint8_t> up(32 * cnt);
+        for (size_t i = 0; i < cnt; i++) {
+            uint8_t msg[72] = {1, 0, 0, 0, 0, 0, 0, 0};
+            memcpy(msg + 8, level.data() + 64 * i, 64);
+            keccak256(msg, 72, up.data() + 32 * i);
+        }
+        level.swap(up);
+    }
+    memcpy(out, level.data(), 32);
+}
+
+// hg_bound_seed: what the transcript of a bound proof starts from - the one place the byte string is built
+std::vector<uint8_t> bound_seed(const hg_params& raw, int mode, const uint8_t digest[32], const uint8_t root[32]) {
+    static const char tag[] = "hg-gkr-bound-1";
+    std::vector<uint8_t> s(tag, tag + sizeof(tag) - 1);
+    auto le = [&](u64 x, int bytes) { for (int i = 0; i < bytes; i++) s.push_back((uint8_t)(x >> (8 * i))); };
+    le(raw.n, 4);
+    le(raw.k, 4);
+    for (uint32_t i = 0; i < raw.k; i++) le(raw.qis[i], 8);
+    le((u64)(uint32_t)mode, 4);
+    s.insert(s.end(), digest, digest + 32);
+    s.insert(s.end(), root, root + 32);
+    return s;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Synthetic witness: the math of scripts/circuit_sk.py:18-140 on seeded integer-only samplers.
 //   s uniform in {-1,0,1}; e centred binomial (eta = 20, variance 10 ~ sigma 3.2) truncated to +-19;

@@ -132,6 +132,13 @@ struct Instance { std::vector<int64_t> a, ct0; };
 Instance instance_from_ciphertext(const Params& p, const int64_t* a, const int64_t* ct0);
 // the layout inverted; an Error if a padding word is nonzero or a word is not a small signed value in that range
 Instance instance_from_witness(const Params& p, const Witness& w);
+// hg_instance_digest: the Keccak tree over the instance's 2kn signed words (hg.h: "The statement digest"); this is the host form,
+// the leaves dealt to the host threads. DIGEST_LEAF_WORDS: the width of a full leaf
+constexpr size_t DIGEST_LEAF_WORDS = 128;
+void instance_digest_host(const Params& p, const Instance& inst, uint8_t out[32]);
+// hg_bound_seed: "hg-gkr-bound-1" || LE32(n) || LE32(k) || LE64(qis[0..k)) || LE32(mode) || digest || root - what FsTranscript::pending
+// of a bound proof starts as, on the prover's side and on every verifier's
+std::vector<uint8_t> bound_seed(const hg_params& raw, int mode, const uint8_t digest[32], const uint8_t root[32]);
 
 // ---------------------------------------------------------------------------------------------
 // Lasso preprocessing (host description; the device copy lives in the prover key)
@@ -237,13 +244,15 @@ template <class E> struct VerifyPendingT {
 };
 typedef VerifyPendingT<E2> VerifyPending;
 // public_only (hg_verify_public_device): claims on the inputs outside 3 .. 3+k-1 are not handed to the backend but returned in `open`
+// seed (hg_verify_public_bound*, may be null): the bytes the transcript's hash state starts as (bound_seed); null or empty: an unbound proof
 VerifyPending verify_walk(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode,
-                          bool public_only = false);
+                          bool public_only = false, const std::vector<uint8_t>* seed = nullptr);
 std::string verify_complete(VerifyPending& v);
 // hg_verify_public on the host: everything the key, the proof, a_i and ct0_i decide; "" = accepted, `open` = the claims left on the
 // secret inputs (inputs ascending, within one input the order in which the walk pushed them), else the reason and no claims
+// root (hg_verify_public_bound, may be null): the walk of a bound proof - the transcript starts from bound_seed over the instance's host digest and this root
 std::string verify_public(const Params& p, const LassoPlan& lp, const HCircuit& c, const Instance& inst, const uint8_t* proof, size_t len, int mode,
-                          std::vector<OpenClaim>& open);
+                          std::vector<OpenClaim>& open, const uint8_t* root = nullptr);
 void claim_shape(const Params& p, const LassoPlan& lp, const HCircuit& c, size_t* n_claims, size_t* n_coords);   // hg_pk_claim_shape
 // table `input` of the handle and its number of variables (an Error for an index past 3+2k)
 const u64* input_table(const Params& p, const Witness& w, size_t input, int* log2_size);

@@ -10,6 +10,8 @@
 // texts and one launch function per kernel step. commit_device and commit_device_values keep a host flow of their own.
 // A commitment to tables that lie in HBM (commit_tables_enqueue: hg_secrets_commit_values, the encryption pipeline) stages them with one
 // kernel of its own and goes on with the encoding, the leaf hash and the tree of commit_device.
+// The statement digest of a bound proof (hg.h: "Bound proofs") lives here as well: its leaves are hashed by a kernel of the same
+// thread-a-sponge form as the column hashes, its levels are the commitment's.
 #include <omp.h>
 #include "pcs.hpp"
 #include "prover.hpp"
@@ -95,6 +97,74 @@ __global__ __launch_bounds__(PCS_TPB) void k_pcsb_merkle_top(u64* __restrict__ t
         below = here;
         count >>= 1;
     }
+}
+
+// ---- the statement digest (pcs.hpp DigestMember; hg.h states the tree): the leaf kernel for a group of G members of one parameter
+// set. Word w < 2kn of a member is coefficient w & (n-1) of modulus (w mod kn) >> log2 n of a (w < kn) or of ct0.
+struct DigestShape {
+    int log2_n, log2_k, log2_leaf, log2_leaves;   // a leaf: 2^log2_leaf = min(128, 2kn) words; 2^log2_leaves leaves a member
+    u64 half[HG_MAX_K];                            // (q_i - 1) / 2
+};
+constexpr int DIGEST_TPB = 64;   // a member has 2kn / 128 leaves (8192 at n=32768 k=16): small workgroups reach more compute units
+// Word w of member M as the signed value the digest hashes (two's complement). Compact: the staged word itself. Laid out: coefficient
+// j of a_i is word n-1-j of input 3+i, of ct0_i word 2n-2-j of block i of ct0is; a field word v stands for v if v <= (p-1)/2, else
+// for -(p-v) = v + 2^32 - 1 mod 2^64. bad: v is not below p or |value| is above (q_i-1)/2
+template <bool LAID>
+__device__ __forceinline__ u64 digest_word(const DigestMember* __restrict__ M, const DigestShape& S, size_t w, bool& bad) {
+    const size_t kn = (size_t)1 << (S.log2_n + S.log2_k), n = (size_t)1 << S.log2_n;
+    const bool c = w >= kn;
+    const size_t r = c ? w - kn : w;
+    if constexpr (!LAID) return (c ? M->ct0 : M->a[0])[r];
+    const size_t i = r >> S.log2_n, j = r & (n - 1);
+    const u64 v = c ? M->ct0[(i << (S.log2_n + 1)) + (2 * n - 2 - j)] : M->a[i][n - 1 - j];
+    const bool neg = v > (GL_P - 1) / 2;
+    const u64 mag = neg ? GL_P - v : v;
+    bad |= v >= GL_P || mag > S.half[i];
+    return neg ? v + 0xFFFFFFFFull : v;
+}
+// The 17 message words of sponge block b of leaf j into nx: message word 0 is LE64(2), word 1 + t is word j 2^log2_leaf + t of the
+// member, word 2^log2_leaf + 1 the first padding byte; every index of nx is a compile-time constant
+template <bool LAID>
+__device__ __forceinline__ void digest_block(const DigestMember* __restrict__ M, const DigestShape& S, size_t j, size_t b, u64 (&nx)[RATE_WORDS], bool& bad) {
+    const size_t words = ((size_t)1 << S.log2_leaf) + 1, first = j << S.log2_leaf;
+#pragma unroll
+    for (int i = 0; i < RATE_WORDS; i++) {
+        const size_t idx = b * RATE_WORDS + i;
+        u64 w = 0;
+        if (idx == 0) w = 2;
+        else if (idx < words) w = digest_word<LAID>(M, S, first + idx - 1, bad);
+        else if (idx == words) w = 0x01;
+        nx[i] = w;
+    }
+}
+// One thread per (member m, leaf j), id = m 2^log2_leaves + j: Keccak256(LE64(2) || the leaf's words) into leaf j of the member's tree
+// at trees + m tree_words. The state stays in registers; the words of the next sponge block are loaded ahead of the permutation of
+// this one, so that their latency passes under it. A lane reads its leaf's 1 KiB with 8-byte loads at a lane stride of 1 KiB: eight
+// whole 128-byte lines that no other lane touches, each fetched from HBM once and found in the cache by the loads that follow. LAID:
+// a member whose word is not a signed value in range sets its flag.
+template <bool LAID>
+__global__ __launch_bounds__(DIGEST_TPB) void k_instance_digest_leaves(const DigestMember* __restrict__ mem, const DigestShape S, size_t G, u64* __restrict__ trees,
+                                                                      size_t tree_words, unsigned* __restrict__ flags) {
+    const size_t id = (size_t)blockIdx.x * DIGEST_TPB + threadIdx.x;
+    if (id >= G << S.log2_leaves) return;
+    const size_t m = id >> S.log2_leaves, j = id & (((size_t)1 << S.log2_leaves) - 1);
+    const DigestMember* M = mem + m;
+    const size_t blocks = (((size_t)1 << S.log2_leaf) + 1) / RATE_WORDS + 1;   // the last block holds the rest (possibly nothing) and the padding
+    bool bad = false;
+    u64 a[25], nx[RATE_WORDS];
+#pragma unroll
+    for (int i = 0; i < 25; i++) a[i] = 0;
+    digest_block<LAID>(M, S, j, 0, nx, bad);
+    for (size_t b = 0; b < blocks; b++) {
+#pragma unroll
+        for (int i = 0; i < RATE_WORDS; i++) a[i] ^= nx[i];
+        if (b + 1 < blocks) digest_block<LAID>(M, S, j, b + 1, nx, bad);
+        else a[RATE_WORDS - 1] ^= 0x8000000000000000ull;
+        keccak_f(a);
+    }
+    u64* out = trees + m * tree_words + 4 * j;
+    out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
+    if (LAID && bad) atomicOr(flags + m, 1u);
 }
 
 // sum_{r < nrows} w[r] * src[r << shift]. Products go into two accumulators (c0 and c1 of the weight) that are reduced every
@@ -438,7 +508,85 @@ std::shared_ptr<void> slab_alloc(size_t bytes, u64** p) {
     return slab;
 }
 
-Commitment* commit_device_values(hg_ctx* ctx, const Shape& sh, const u64* const* d_tables) {
+// ---- the statement digest: host side
+void instance_digest_enqueue(hg_ctx* ctx, hipStream_t st, const Params& p, bool laid, const DigestMember* mem, size_t G, uint8_t* roots, unsigned* flags) {
+    if (!G) return;
+    DigestShape S;
+    S.log2_n = p.n_log2;
+    S.log2_k = p.log2k;
+    S.log2_leaf = std::min(7, p.n_log2 + p.log2k + 1);
+    static_assert(DIGEST_LEAF_WORDS == 128, "2^7 words a full leaf");
+    S.log2_leaves = p.n_log2 + p.log2k + 1 - S.log2_leaf;
+    for (int i = 0; i < HG_MAX_K; i++) S.half[i] = i < p.k ? (p.raw.qis[i] - 1) / 2 : 0;
+    const size_t leaves = (size_t)1 << S.log2_leaves, tree_words = 8 * leaves, bytes = G * sizeof(DigestMember), need = (bytes + 15) & ~(size_t)15;
+    if (ctx->stage_used + need > ctx->stage_cap) throw Error("the staging buffer cannot hold the members of the digest");
+    DigestMember* h_mem = reinterpret_cast<DigestMember*>(ctx->h_stage + ctx->stage_used);
+    ctx->stage_used += need;
+    memcpy(h_mem, mem, bytes);
+    DigestMember* d_mem = ctx->alloc_n<DigestMember>(G);
+    u64* d_trees = ctx->alloc_n<u64>(G * tree_words);
+    unsigned* d_flags = ctx->alloc_n<unsigned>(G + 4);
+    hip_check(hipMemcpyAsync(d_mem, h_mem, bytes, hipMemcpyHostToDevice, st), "instance digest: upload the members");
+    if (laid) hip_check(hipMemsetAsync(d_flags, 0, G * sizeof(unsigned), st), "memset");
+    hipStream_t prof_was = ctx->prof_stream;
+    ctx->prof_stream = st;
+    const unsigned grid = (unsigned)(((G << S.log2_leaves) + DIGEST_TPB - 1) / DIGEST_TPB);
+    ctx->prof_begin(ctx->prof_class("instance_digest_leaves", false), (double)G * (((size_t)16 << (p.n_log2 + p.log2k)) + 32 * leaves));
+    if (laid) k_instance_digest_leaves<true><<<grid, DIGEST_TPB, 0, st>>>(d_mem, S, G, d_trees, tree_words, d_flags);
+    else k_instance_digest_leaves<false><<<grid, DIGEST_TPB, 0, st>>>(d_mem, S, G, d_trees, tree_words, d_flags);
+    ctx->prof_end();
+    if (leaves > 1) {
+        ctx->prof_begin(ctx->prof_class("instance_digest_tree", false), (double)G * leaves * 96);
+        merkle_levels_device_batch(st, d_trees, tree_words, leaves, G);
+        ctx->prof_end();
+    }
+    ctx->prof_stream = prof_was;
+    // the root is the last node of a tree: word 4 (2 leaves - 2)
+    hip_check(hipMemcpy2DAsync(roots, 32, d_trees + 4 * (2 * leaves - 2), tree_words * 8, 32, G, hipMemcpyDeviceToHost, st), "instance digest: download the roots");
+    if (laid && flags) hip_check(hipMemcpyAsync(flags, d_flags, G * sizeof(unsigned), hipMemcpyDeviceToHost, st), "instance digest: download the flags");
+}
+
+void instance_digest_device(hg_ctx* ctx, const Params& p, const std::vector<const Instance*>& insts, uint8_t* out) {
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->arena_reset();
+    hipStream_t st = ctx->stream;
+    DrainOne drain{st};   // (the instances are the caller's: every way out waits for their uploads)
+    const size_t G = insts.size(), kn = (size_t)p.k * p.PZ();
+    std::vector<DigestMember> mem(G);
+    u64* d_words = ctx->alloc_n<u64>(G * 2 * kn);
+    for (size_t m = 0; m < G; m++) {
+        if (insts[m]->a.size() != kn || insts[m]->ct0.size() != kn) throw Error("an instance does not hold k * n coefficients a table");
+        memset(&mem[m], 0, sizeof(DigestMember));
+        u64* at = d_words + m * 2 * kn;
+        hip_check(hipMemcpyAsync(at, insts[m]->a.data(), kn * 8, hipMemcpyHostToDevice, st), "instance digest: upload the instance");
+        hip_check(hipMemcpyAsync(at + kn, insts[m]->ct0.data(), kn * 8, hipMemcpyHostToDevice, st), "instance digest: upload the instance");
+        mem[m].a[0] = at;
+        mem[m].ct0 = at + kn;
+    }
+    std::vector<uint8_t> roots(32 * G);
+    instance_digest_enqueue(ctx, st, p, false, mem.data(), G, roots.data(), nullptr);
+    hip_check(hipStreamSynchronize(st), "instance digest: sync");
+    hip_check(hipGetLastError(), "instance digest: launch");
+    ctx->prof_collect();
+    memcpy(out, roots.data(), roots.size());
+}
+
+void instance_digest_values(hg_ctx* ctx, const Params& p, const DigestMember& mem, uint8_t out[32]) {
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->arena_reset();
+    hipStream_t st = ctx->stream;
+    DrainOne drain{st};
+    uint8_t root[32];
+    unsigned flag = 0;
+    instance_digest_enqueue(ctx, st, p, true, &mem, 1, root, &flag);
+    hip_check(hipStreamSynchronize(st), "instance digest: sync");
+    hip_check(hipGetLastError(), "instance digest: launch");
+    ctx->prof_collect();
+    if (flag) throw Error("a word of ais or ct0is is not a signed value in [-(q_i-1)/2, (q_i-1)/2]");
+    memcpy(out, root, 32);
+}
+
+Commitment* commit_device_values(hg_ctx* ctx, const Shape& sh, const u64* const* d_tables, DigestJob* dg) {
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
     ctx->arena_reset();
     hipStream_t st = ctx->stream;
@@ -455,12 +603,22 @@ Commitment* commit_device_values(hg_ctx* ctx, const Shape& sh, const u64* const*
     unsigned* d_flag = ctx->alloc_n<unsigned>(4);
     unsigned flag = 0;
     DrainOne drain{st};   // (drains on an error; after the synchronisation below its own is one more, on an idle stream)
+    DrainOne drain2{dg ? ctx->stream2 : st};   // (the digest's stream as well, where one is used)
+    if (dg) {   // the second stream starts behind whatever the first one holds by now, not behind the commit
+        hip_check(hipEventRecord(ctx->ev_fork, st), "fork");
+        hip_check(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0), "fork wait");
+    }
     ctx->prof_stream = st;
     commit_tables_enqueue(st, sh, d_tables, cm->d_rows, cm->d_M, scratch, W, d_tree, d_flag, ctx, ctx->prof_class("pcs_commit_values", false));
+    if (dg) {   // the statement digest of the same values object, beside the commit's kernels: both are enqueued ahead of the first copy back
+        dg->flag = 0;
+        instance_digest_enqueue(ctx, ctx->stream2, *dg->p, true, &dg->mem, 1, dg->digest, &dg->flag);
+    }
     cm->tree.resize(32 * (2 * N - 1));
     hip_check(hipMemcpyAsync(cm->tree.data(), d_tree, cm->tree.size(), hipMemcpyDeviceToHost, st), "download tree");
     hip_check(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st), "download flag");
     hip_check(hipStreamSynchronize(st), "sync");
+    if (dg) hip_check(hipStreamSynchronize(ctx->stream2), "sync (statement digest)");
     hip_check(hipGetLastError(), "launch");
     ctx->prof_collect();
     if (flag) throw Error("a table holds a word that is not below p");

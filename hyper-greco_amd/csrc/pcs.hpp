@@ -76,9 +76,33 @@ std::vector<Commitment*> commit_device_batch(const char* who, hg_ctx* ctx, const
 // profiler class cls the launches are counted in (its prof_stream must be st)
 void commit_tables_enqueue(hipStream_t st, const Shape& sh, const u64* const* d_tables, u64* d_rows, u64* d_M, u64* scratch, u64* W, u64* d_tree, unsigned* d_flag,
                            hg_ctx* prof = nullptr, int cls = -1);
+// ---- the statement digest on the device (pcs.hip; hg.h states the tree, instance_digest_host is its host form). One kernel hashes
+// the leaves of a group of members of one parameter set, one thread per (member, leaf); the levels above are the commitment's
+// (merkle_levels_device_batch). A member is where its words lie: compact (an hg_instance as it is uploaded: a[0] = the k n signed
+// words of a, ct0 = those of ct0) or laid out (the resident tables of an hg_values: a[i] = input 3+i, ct0 = ct0is).
+struct DigestMember { const u64* a[HG_MAX_K]; const u64* ct0; };
+struct DigestJob {   // the laid-out digest of one values object beside a commit (commit_device_values): in mem, out digest and flag
+    const Params* p;
+    DigestMember mem;
+    uint8_t digest[32];
+    unsigned flag;   // != 0: a word of ais or ct0is is not a signed value in [-(q_i-1)/2, (q_i-1)/2]
+};
+// Enqueues on st the digests of G members (host copies of their descriptors in mem; staged through the context's pinned buffer into its
+// arena, which is not reset) and the copies of the G roots to roots (32 bytes each) and, laid out, of the G flag words to flags
+// (flags may be null for compact members). Nothing is synchronised: roots and flags are valid once st has been. The launches are
+// counted in the profiler classes instance_digest_leaves and instance_digest_tree (the context's prof_stream is st for their duration).
+void instance_digest_enqueue(hg_ctx* ctx, hipStream_t st, const Params& p, bool laid, const DigestMember* mem, size_t G, uint8_t* roots, unsigned* flags);
+// hg_instance_digest with a context and hg_instance_digest_batch: every instance uploaded as it is, one launch over all of them, one
+// synchronisation; out: 32 bytes an instance
+void instance_digest_device(hg_ctx* ctx, const Params& p, const std::vector<const Instance*>& insts, uint8_t* out);
+// hg_values_instance_digest: the laid-out read; throws if a word is not a signed value in range
+void instance_digest_values(hg_ctx* ctx, const Params& p, const DigestMember& mem, uint8_t out[32]);
+
 // hg_secrets_commit_values: commit_tables_enqueue on the context's stream, the scratch from its arena, one synchronisation; the handle
-// owns d_rows and d_M. Its errors do not carry a name
-Commitment* commit_device_values(hg_ctx* ctx, const Shape& sh, const u64* const* d_tables);
+// owns d_rows and d_M. Its errors do not carry a name. dg (hg_prove_committed_mode, may be null): the statement digest of the same
+// values object as well, enqueued on the context's second stream beside the commit's kernels and waited for with them; the caller
+// reads dg->flag
+Commitment* commit_device_values(hg_ctx* ctx, const Shape& sh, const u64* const* d_tables, DigestJob* dg = nullptr);
 // an allocation of `bytes` that lives until the last copy of the returned owner is dropped (Commitment::owner of handles whose
 // matrices are laid into it by the caller)
 std::shared_ptr<void> slab_alloc(size_t bytes, u64** p);

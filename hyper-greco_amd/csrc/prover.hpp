@@ -274,7 +274,8 @@ void ctx_register(hg_ctx* ctx, bool alive);
 ProveResult prove_resident(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, bool borrow = false);
 // the same in a protocol mode of SURVEY.md 8(f) f-4 (bit 0 absorbing transcript, bit 1 extension-field memory checking):
 // round-by-round prover (prover_seq.hip); mode 0 = prove_resident
-ProveResult prove_resident_mode(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, int mode);
+// seed (hg_prove_committed_mode; modes with bit 0 only): the bytes the transcript's hash state starts as (host.hpp bound_seed)
+ProveResult prove_resident_mode(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, int mode, const std::vector<uint8_t>& seed = {});
 ProveResult prove_resident_mode_sharded(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, int mode, int rank, int world,
                                         int (*reduce)(void*, uint64_t*, size_t), void* user);
 size_t prove_shard_begin(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, int rank, int world);  // -> #E2 slots in ctx->h_res
@@ -319,7 +320,9 @@ void vdot_jobs(hipStream_t st, const DotJob* d_jobs, size_t njobs, E2* partials,
 struct CompactDotJob { const int64_t* c; const E2* eq; u32 log2_n, nblk, lo; };
 void vdot_compact_jobs(hipStream_t st, const CompactDotJob* d_jobs, const DotJob* d_slots, size_t njobs, E2* partials, E2* res);
 // hg_verify_public_device: the public part of the verification; "" = accepted and `open` = the claims left on the secret inputs
-std::string verify_public_device(hg_ctx* ctx, const hg_pk* pk, const Instance& inst, const uint8_t* proof, size_t len, int mode, std::vector<OpenClaim>& open);
+// root (hg_verify_public_bound_device, may be null): the walk of a bound proof, the statement digest by the digest kernel
+std::string verify_public_device(hg_ctx* ctx, const hg_pk* pk, const Instance& inst, const uint8_t* proof, size_t len, int mode, std::vector<OpenClaim>& open,
+                                 const uint8_t* root = nullptr);
 std::string claims_settle_device(hg_ctx* ctx, const Params& p, const Witness& w, const std::vector<OpenClaim>& claims);   // hg_claims_settle with a context
 E2 instance_mle_device(hg_ctx* ctx, const Params& p, const Instance& inst, int which, int index, const std::vector<E2>& pt);   // hg_instance_mle with a context
 // hg_verify_device_batch (verifier_batch.hip): proof i against ws[i], all in `mode`; why[i] = "" accepted, else the reason. An

@@ -645,8 +645,10 @@ struct SeqProver {
         }
     }
 
-    SeqProver(hg_ctx* c, const hg_pk* k, int m) : ctx(c), pk(k), mode(m), st(c->stream) {
+    // seed: what the transcript's hash state starts as (host.hpp bound_seed: a bound proof); empty: the state of every other proof
+    SeqProver(hg_ctx* c, const hg_pk* k, int m, const std::vector<uint8_t>& seed) : ctx(c), pk(k), mode(m), st(c->stream) {
         tr.absorb = (m & 1) != 0;
+        tr.pending = seed;
         chain_cap = 1 << 15;
         d_chain = ctx->alloc_n<E2>(chain_cap);
         hip_check(hipMemsetAsync(d_chain, 0, chain_cap * sizeof(E2), st), "clear challenge table");
@@ -1571,8 +1573,12 @@ struct SeqProver {
 
 // BfvEncrypt::prove on resident node values in a non-default protocol mode; gpu_ms = wall time of the whole walk (the device
 // is synchronised every round, so there is no separate device span)
-ProveResult prove_resident_mode(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, int mode) {
-    return prove_resident_mode_sharded(ctx, pk, v, mode, 0, 1, nullptr, nullptr);
+// seed (hg_prove_committed_mode): the transcript of a bound proof starts from it; an empty one changes no byte of any proof
+static ProveResult prove_seq(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, int mode, int rank, int world, int (*reduce)(void*, uint64_t*, size_t), void* user,
+                             const std::vector<uint8_t>& seed);
+ProveResult prove_resident_mode(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, int mode, const std::vector<uint8_t>& seed) {
+    if (!seed.empty() && !(mode & 1)) throw Error("hg_prove_mode: a seeded transcript needs the absorbing transcript (mode bit 1)");
+    return prove_seq(ctx, pk, v, mode, 0, 1, nullptr, nullptr, seed);
 }
 // The round-by-round prover on `world` ranks. With the whole witness on every rank: rank r evaluates the hypercube sums of the tiles
 // t = r (mod world) of every round kernel and folds everything; one all-reduce (`reduce`) per round completes the sums, after which
@@ -1581,6 +1587,10 @@ ProveResult prove_resident_mode(hg_ctx* ctx, const hg_pk* pk, const hg_values* v
 // SeqProver::own_mode. Every rank returns the same proof, byte for byte the single-rank one.
 ProveResult prove_resident_mode_sharded(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, int mode, int rank, int world,
                                         int (*reduce)(void*, uint64_t*, size_t), void* user) {
+    return prove_seq(ctx, pk, v, mode, rank, world, reduce, user, {});
+}
+static ProveResult prove_seq(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, int mode, int rank, int world, int (*reduce)(void*, uint64_t*, size_t), void* user,
+                             const std::vector<uint8_t>& seed) {
     if (world < 1 || rank < 0 || rank >= world) throw Error("sharded prove: rank out of range");
     if (world > 1 && !reduce) throw Error("sharded prove: no all-reduce given");
     if (mode == 0) {
@@ -1591,7 +1601,7 @@ ProveResult prove_resident_mode_sharded(hg_ctx* ctx, const hg_pk* pk, const hg_v
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
     ctx->arena_reset();
     const double t0 = now_ms();
-    SeqProver P(ctx, pk, mode);
+    SeqProver P(ctx, pk, mode, seed);
     P.shard_rank = rank; P.shard_world = world; P.reduce = reduce; P.reduce_user = user;
     P.d_vals = v->d_vals;
     if (v->shard_rank >= 0) {   // a rank's share of the witness (hg_witness_gen_shard): node reductions run on their owners only

@@ -62,6 +62,7 @@ struct GlField {
         E squeeze() { return t.squeeze(); }
         void absorb(E v) { t.absorb_read(v.c0); t.absorb_read(v.c1); }  // read_felt of an absorbing transcript (transcript.rs:210-222)
         void set_mode(int mode) { t.absorb = (mode & 1) != 0; }
+        void seed(const std::vector<uint8_t>& s) { t.pending = s; }   // a bound proof (host.hpp bound_seed): the state starts as these bytes
     };
 };
 
@@ -108,6 +109,7 @@ struct BnField {  // elements in Montgomery form
         Chal() { keccak256(nullptr, 0, h); }
         void absorb(E) {}
         void set_mode(int mode) { if (mode != 0) throw Reject("bn254: protocol modes are implemented for the Goldilocks family only"); }
+        void seed(const std::vector<uint8_t>& s) { if (!s.empty()) throw Reject("bn254: bound proofs are implemented for the Goldilocks family only"); }
         E squeeze() {
             bn::Fr v;
             memcpy(v.l, h, 32);
@@ -214,6 +216,7 @@ template <class F> struct Verifier {
         E squeeze() { n++; E v = c.squeeze(); if (keep) seq.push_back(v); return v; }
         void absorb(E v) { c.absorb(v); }
         void set_mode(int mode) { c.set_mode(mode); }
+        void seed(const std::vector<uint8_t>* s) { if (s) c.seed(*s); }
     } ch;
     bool ext_memcheck = false;  // mode bit 1: gamma, tau stay in E (prover.rs:36-39 truncates them; README.md:108)
     // the table-sized checks elsewhere: see VerifyBackendT in host.hpp
@@ -563,13 +566,14 @@ template <class F> struct Verifier {
 // `open` (inputs ascending, within one input in the order the walk pushed them); `w` is not read.
 template <class F>
 static std::string verify_impl(const Params& p, const LassoPlan& lp, const HCircuit& c, const Witness& w, const uint8_t* proof, size_t len, int mode,
-                               const Instance* inst = nullptr, std::vector<OpenClaimT<typename F::E>>* open = nullptr) {
+                               const Instance* inst = nullptr, std::vector<OpenClaimT<typename F::E>>* open = nullptr, const std::vector<uint8_t>* seed = nullptr) {
     typedef typename F::E E;
     typedef typename Verifier<F>::Claim Claim;
     try {
         Verifier<F> V;
         V.bytes = ProofBytes{proof, len};
         V.ch.set_mode(mode);
+        V.ch.seed(seed);
         V.ext_memcheck = (mode & 2) != 0;
         double t_kind[3] = {0, 0, 0};
         const double tv0 = omp_get_wtime();
@@ -648,7 +652,7 @@ static std::string verify_impl(const Params& p, const LassoPlan& lp, const HCirc
 // (verifier_batch.hip) - and finish them together. The walk itself opens no OpenMP region.
 template <class F>
 static VerifyPendingT<typename F::E> walk_with_backend(VerifyBackendT<typename F::E>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode,
-                                                       bool public_only = false) {
+                                                       bool public_only = false, const std::vector<uint8_t>* seed = nullptr) {
     typedef typename F::E E;
     typedef typename Verifier<F>::Claim Claim;
     VerifyPendingT<E> out;
@@ -656,6 +660,7 @@ static VerifyPendingT<typename F::E> walk_with_backend(VerifyBackendT<typename F
         Verifier<F> V;
         V.bytes = ProofBytes{proof, len};
         V.ch.set_mode(mode);
+        V.ch.seed(seed);
         V.ext_memcheck = (mode & 2) != 0;
         V.ch.keep = mode != 0;
         V.dev = &dev;
@@ -734,8 +739,9 @@ static std::string verify_with_backend(VerifyBackendT<typename F::E>& dev, const
 std::string verify_proof_with(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode) {
     return verify_with_backend<GlField>(dev, p, lp, c, proof, len, mode);
 }
-VerifyPending verify_walk(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode, bool public_only) {
-    return walk_with_backend<GlField>(dev, p, lp, c, proof, len, mode, public_only);
+VerifyPending verify_walk(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode, bool public_only,
+                          const std::vector<uint8_t>* seed) {
+    return walk_with_backend<GlField>(dev, p, lp, c, proof, len, mode, public_only, seed);
 }
 std::string verify_complete(VerifyPending& v) { return complete_pending(v); }
 std::string verify_proof_with_bn254(VerifyBackendT<bn::Fr>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len) {
@@ -757,10 +763,16 @@ std::string verify_proof_bn254(const Params& p, const LassoPlan& lp, const HCirc
 
 // ---- hg_verify_public / hg_claims_settle: the verifier split where the public data ends -------------------------------------------
 std::string verify_public(const Params& p, const LassoPlan& lp, const HCircuit& c, const Instance& inst, const uint8_t* proof, size_t len, int mode,
-                          std::vector<OpenClaim>& open) {
+                          std::vector<OpenClaim>& open, const uint8_t* root) {
     open.clear();
     const Witness none;
-    std::string why = verify_impl<GlField>(p, lp, c, none, proof, len, mode, &inst, &open);
+    std::vector<uint8_t> seed;
+    if (root) {   // hg_verify_public_bound: the digest by the host tree
+        uint8_t digest[32];
+        instance_digest_host(p, inst, digest);
+        seed = bound_seed(p.raw, mode, digest, root);
+    }
+    std::string why = verify_impl<GlField>(p, lp, c, none, proof, len, mode, &inst, &open, root ? &seed : nullptr);
     if (!why.empty()) open.clear();
     return why;
 }

@@ -384,7 +384,11 @@ const int64_t* upload_coeffs(hg_ctx* ctx, const int64_t* src, size_t n) {
 // The public part of the verification on the device: the instance's 2 k n signed words are uploaded as they are (8 MB at n=32768
 // k=16 against 22 MB of laid-out tables), the walk records compact dot jobs for ct0is and the ais claims and NOTHING for the secret
 // inputs - their claims come back in `open`, value from the walk and point from the challenges it squeezed.
-std::string verify_public_device(hg_ctx* ctx, const hg_pk* pk, const Instance& inst, const uint8_t* proof, size_t len, int mode, std::vector<OpenClaim>& open) {
+// root (hg_verify_public_bound_device, may be null): the proof is a bound one. Its transcript starts from the statement digest, which
+// the digest kernel takes from the words uploaded here; the 32 bytes must be back before the walk's first squeeze, so this form waits
+// once for the uploads and the digest ahead of the walk (the unbound form runs the walk under them).
+std::string verify_public_device(hg_ctx* ctx, const hg_pk* pk, const Instance& inst, const uint8_t* proof, size_t len, int mode, std::vector<OpenClaim>& open,
+                                 const uint8_t* root) {
     const double tv0 = omp_get_wtime();
     struct Total { double t0; ~Total() { if (hg_times("verify")) fprintf(stderr, "[hg] verify_public_device: %.2f ms in all\n", (omp_get_wtime() - t0) * 1e3); } } total{tv0};
     open.clear();
@@ -397,7 +401,20 @@ std::string verify_public_device(hg_ctx* ctx, const hg_pk* pk, const Instance& i
     D.cp = &p;
     D.d_ca = upload_coeffs(ctx, inst.a.data(), inst.a.size());
     D.d_cct0 = upload_coeffs(ctx, inst.ct0.data(), inst.ct0.size());
-    VerifyPending v = verify_walk(D, p, pk->lasso, pk->circuit, proof, len, mode, true);
+    std::vector<uint8_t> seed;
+    if (root) {
+        pcs::DigestMember mem;
+        memset(&mem, 0, sizeof(mem));
+        mem.a[0] = reinterpret_cast<const u64*>(D.d_ca);
+        mem.ct0 = reinterpret_cast<const u64*>(D.d_cct0);
+        uint8_t digest[32];
+        pcs::instance_digest_enqueue(ctx, ctx->stream, p, false, &mem, 1, digest, nullptr);
+        hip_check(hipStreamSynchronize(ctx->stream), "verifier: the statement digest");
+        hip_check(hipGetLastError(), "verifier: the statement digest");
+        ctx->prof_collect();
+        seed = bound_seed(p.raw, mode, digest, root);
+    }
+    VerifyPending v = verify_walk(D, p, pk->lasso, pk->circuit, proof, len, mode, true, root ? &seed : nullptr);
     if (!v.reason.empty()) return v.reason;
     if (mode != 0) D.set_chain(v.chain);
     D.finish();

@@ -316,7 +316,9 @@ int hg_instance_mle_batch(hg_ctx* ctx, const void* const* instances, size_t n, i
  * commitment of the Brakedown / Ligero shape with the reference's hash, Keccak-256. Two things differ from the type the reference
  * names: the linear code is Reed-Solomon of rate 1/4 (the NTT of the zero-padded row; Brakedown's argument needs a linear code, not
  * the expander code of BrakedownSpec6), and evaluation points are E = GoldilocksExt2 points. Not zero knowledge: an opening
- * reveals linear combinations and whole encoded columns of the tables. The root is NOT yet absorbed into the GKR transcript.
+ * reveals linear combinations and whole encoded columns of the tables. A proof of
+ * hg_prove_committed_mode absorbs the root into the GKR transcript ahead of the first challenge ("Bound proofs" below); the other
+ * provers do not.
  *
  * The scheme. Coordinate i of a point belongs to bit i of the table index (the convention of hg_mle_eval and hg_claims_settle).
  *   Rows.   Tables T_0 .. T_{m-1}, table t of 2^{v_t} canonical words. Row length C = 2^c (c = log2_row, c <= v_t for every t).
@@ -538,6 +540,61 @@ int hg_prove_encryptions_committed(hg_ctx* ctx, const hg_pk* pk, const int64_t* 
 int hg_prove_mode(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, int mode, uint8_t* proof, size_t cap, size_t* len, hg_timings* timings);
 int hg_prove_resident_mode(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, int mode, uint8_t* proof, size_t cap, size_t* len, hg_timings* timings);
 int hg_verify_mode(const hg_pk* pk, const hg_witness* w, int mode, const uint8_t* proof, size_t len);
+
+/* ---- Bound proofs: the GKR transcript starts from the statement -----------------------------------------------------------------
+ * With the absorbing transcript (mode bit 1) the challenges depend on the proof bytes. In a BOUND proof they also depend on what the
+ * proof is about and on what its claims are opened against: the transcript's hash state starts, instead of empty, as
+ *     "hg-gkr-bound-1" (14 ASCII bytes) || LE32(n) || LE32(k) || LE64(qis[0]) .. LE64(qis[k-1]) || LE32(mode) || digest || root
+ * (hg_bound_seed), digest = the statement digest of the public instance below, root = the 32-byte root of the commitment to the five
+ * secret inputs (hg_secrets_commit*). Nothing else changes: a bound transcript is the absorbing transcript with that start, on the
+ * prover's side and on the verifier's. mode is 1 or 3; for mode 0 or 2 every entry of this section returns -1 with the text
+ * "<function>: binding needs the absorbing transcript (mode bit 1)" (a mode outside 0..3: "<function>: unknown mode bits").
+ * Goldilocks, one proof per call. Still open: BN254 has no protocol modes and stays unbound; hg_verify_public_batch and the
+ * hg_prove_encryptions_committed pipeline are mode 0 and stay unbound; the sharded prover is unbound; nothing here is zero knowledge.
+ *
+ * The statement digest. The instance is read as 2 k n signed 64-bit words, two's complement, little-endian: the k n words of a, then
+ *   those of ct0, each modulus-major in ascending degree (what hg_instance_from_ciphertext takes). Leaf width B = min(128, 2 k n)
+ *   words; leaf_j = Keccak256(LE64(2) || words[j B .. (j+1) B)), j < 2 k n / B; an inner node is the commitment's,
+ *   Keccak256(LE64(1) || left || right); the digest is the root of the (full binary) tree, with one leaf that leaf. Keccak-256 with
+ *   the original padding. The prefix 2 keeps these leaves apart from the commitment's leaves (prefix 0) and nodes (prefix 1).
+ * hg_instance_digest: ctx == NULL: the host tree, the leaves dealt to the host threads. With a context: the instance is uploaded as
+ *   it is and hashed by one kernel, one thread per leaf with the Keccak-f[1600] state in registers, the levels above by the tree
+ *   kernels of the commitment; one synchronisation. Same 32 bytes. -1: a null argument.
+ * hg_instance_digest_batch: device only; the n instances (one parameter set) go through ONE launch of that kernel as n members; out
+ *   receives 32 bytes an instance. n == 0 returns 0. -1: a null argument or element, no context, instances of mixed parameters.
+ * hg_values_instance_digest: device only; the same 32 bytes from the resident tables of a full hg_values of this key and context (the
+ *   laid-out read: coefficient j of a_i is word n-1-j of input 3+i, of ct0_i word 2n-2-j of block i of ct0is; a field word w stands
+ *   for w if w <= (p-1)/2, else for -(p-w)). Padding words are not read. -1, in this order: a null argument; no context; a host-only
+ *   key; values of another key or context; a rank's share of hg_witness_gen_shard, in which an input (or ct0is) is not resident; a
+ *   word that is not a signed value in [-(q_i-1)/2, (q_i-1)/2].
+ * hg_bound_seed: the byte string above into out (90 + 8 k bytes); *len = its length, also when cap is too small (-1). -1 also:
+ *   a null argument, the mode rule, parameters hg_setup would not take.
+ * hg_prove_committed_mode: on a full resident hg_values - of hg_witness_gen, hg_witness_gen_into or hg_witness_derive_into -, in one call:
+ *   the commitment of hg_secrets_commit_values(ctx, pk, v, log2_row, ..) - handle and root byte for byte that call's; hg_claims_open
+ *   takes the handle -, the statement digest from the same resident tables (the digest kernel on the context's second stream, beside
+ *   the commit's kernels and waited for together with them), the seed, and the round-by-round prover of hg_prove_resident_mode on
+ *   the seeded transcript. No table crosses the bus: only the commitment's tree and the 32 digest bytes come back. -1, in this
+ *   order, after which no handle is alive (*commitment = NULL): the mode rule; the errors of hg_secrets_commit_values under this
+ *   function's name; a null proof or len; the errors of hg_prove_resident_mode; a proof buffer that is too small (*len = the need).
+ *   timings: the fields of hg_prove_resident_mode, upload_ms = the commit and the digest (host clock).
+ * hg_verify_public_bound / hg_verify_public_bound_device: hg_verify_public / hg_verify_public_device for a bound proof, with the
+ *   root the encryptor published as one more argument. The host form computes the digest with the host tree; the device form with
+ *   the kernel, from the instance words it uploads anyway, and waits for the 32 bytes ahead of the walk's first squeeze (one
+ *   synchronisation more than the unbound form). Decisions, claims, points and reasons are otherwise those of the unbound entries; -1
+ *   also for a null root and by the mode rule. A proof made for another root, another instance or another mode, and an unbound
+ *   proof, are rejected: their challenges differ from the first one on. hg_verify_public_bound followed by hg_claims_verify against
+ *   the same root is a verification that needs no secret in which neither the commitment nor the ciphertext can be chosen after the
+ *   challenges. */
+int hg_instance_digest(hg_ctx* ctx, const void* instance, uint8_t out32[32]);
+int hg_instance_digest_batch(hg_ctx* ctx, const void* const* instances, size_t n, uint8_t* out);
+int hg_values_instance_digest(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, uint8_t out32[32]);
+int hg_bound_seed(const hg_params* params, int mode, const uint8_t digest32[32], const uint8_t root32[32], uint8_t* out, size_t cap, size_t* len);
+int hg_prove_committed_mode(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, int mode, size_t log2_row, uint8_t* proof, size_t cap, size_t* len,
+                            void** commitment, uint8_t root[32], hg_timings* timings);
+int hg_verify_public_bound(const hg_pk* pk, const void* instance, int mode, const uint8_t root[32], const uint8_t* proof, size_t len, void* claims,
+                           size_t claim_cap, uint64_t* points, size_t coord_cap, size_t* n_claims);
+int hg_verify_public_bound_device(hg_ctx* ctx, const hg_pk* pk, const void* instance, int mode, const uint8_t root[32], const uint8_t* proof, size_t len,
+                                  void* claims, size_t claim_cap, uint64_t* points, size_t coord_cap, size_t* n_claims);
 
 /* The round-by-round prover (modes 1-3) on several ranks, with ONE all-reduce per sum-check round: the exchange pattern an absorbing
  * transcript leaves [REF bfv-gkr/src/transcript.rs:205-208, 224-233: every round's message is hashed before the next challenge is
@@ -853,7 +910,7 @@ int hg_instance_mle_batch_bn254(hg_ctx* ctx, const void* const* instances, size_
  * The scheme of the Goldilocks block above (hg_pcs_commit ..) with F = E = Fr (r = the order of bn256's scalar field). Shape rules,
  * limits, the log2_row = 0 rule, n_queries = 0 -> 241 and the 65535-row cap of the device commit are unchanged; the 241 is the same
  * (3/4)^Q term, and with a 254-bit field ONE rho is enough for the combination's own error - no more is claimed. Not zero knowledge;
- * the root is not yet absorbed into the GKR transcript. An element crosses the ABI as 4 canonical little-endian u64 limbs, as
+ * BN254 has no protocol modes, so no BN254 proof absorbs the root ("Bound proofs" above is Goldilocks only). An element crosses the ABI as 4 canonical little-endian u64 limbs, as
  * everywhere in the BN254 entries. repr(x) below is the 32-byte little-endian canonical, non-Montgomery form (halo2curves to_repr).
  *   Rows.   Table t has 2^{v_t} elements and is cut into rows of C = 2^c elements; rows are stacked in table order (R rows, off_t).
  *   Code.   Enc(row) = the forward NTT of size N = 4C of the row zero-padded to 4C elements, natural order, root of unity
