@@ -58,6 +58,7 @@ EXPORTS = [
     "hg_pcs_commit_batch", "hg_secrets_commit_batch", "hg_pcs_open_batch", "hg_claims_open_batch",
     "hg_secrets_commit_values", "hg_prove_encryptions_committed", "hg_prove_encryptions_committed_bn254",
     "hg_instance_digest", "hg_instance_digest_batch", "hg_values_instance_digest", "hg_bound_seed", "hg_prove_committed_mode", "hg_verify_public_bound", "hg_verify_public_bound_device",
+    "hg_verify_public_bound_batch", "hg_instance_digest_group",
     "hg_pcs_commit_bn254", "hg_pcs_open_bn254", "hg_pcs_verify_bn254", "hg_secrets_commit_bn254", "hg_claims_open_bn254", "hg_claims_verify_bn254",
     "hg_pcs_verify_device_bn254", "hg_claims_verify_device_bn254", "hg_pcs_verify_device_batch_bn254", "hg_claims_verify_batch_bn254",
     "hg_pcs_commit_batch_bn254", "hg_secrets_commit_batch_bn254", "hg_pcs_open_batch_bn254", "hg_claims_open_batch_bn254",
@@ -121,6 +122,8 @@ def _two_field_protos(L):
     L.hg_prove_committed_mode.argtypes = [vp, vp, vp, ci, sz, vp, sz, szp, C.POINTER(vp), u8p, C.POINTER(HgTimings)]
     L.hg_verify_public_bound.argtypes = [vp, vp, ci, cp, cp, sz] + room
     L.hg_verify_public_bound_device.argtypes = [vp, vp, vp, ci, cp, cp, sz] + room
+    L.hg_verify_public_bound_batch.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(cp), C.POINTER(cp), szp, sz, ci, C.POINTER(ci)] + room + [u8p, cp, sz]
+    L.hg_instance_digest_group.argtypes = [vp, C.POINTER(vp), sz, u8p]
     pp = C.POINTER(i64p)
     L.hg_prove_encryptions_committed.argtypes = L.hg_prove_encryptions_committed_bn254.argtypes = [
         vp, vp, pp, pp, pp, pp, sz, sz, vp, sz, szp, C.POINTER(ci), C.POINTER(vp), u8p, C.POINTER(vp), cp, sz, C.POINTER(HgTimings)]
@@ -1185,6 +1188,47 @@ def instance_digest_batch(ctx, instances):
     out = (C.c_uint8 * (32 * max(n, 1)))()
     _check(lib().hg_instance_digest_batch(_h(ctx), hs, n, out))
     return [bytes(out[32 * i:32 * (i + 1)]) for i in range(n)]
+
+
+def instance_digest_group(ctx, instances):
+    """hg_instance_digest_group: the digests of a run of Instances of one parameter set as verify_public_bound_batch computes them:
+    staged in slices (context option "bound_batch_slice") and hashed out of the staged set."""
+    n = len(instances)
+    hs = (C.c_void_p * max(n, 1))(*[i.h for i in instances])
+    out = (C.c_uint8 * (32 * max(n, 1)))()
+    _check(lib().hg_instance_digest_group(_h(ctx), hs, n, out))
+    return [bytes(out[32 * i:32 * (i + 1)]) for i in range(n)]
+
+
+def verify_public_bound_batch(ctx, pk, instances, roots, proofs, mode=3, reason_cap=256):
+    """hg_verify_public_bound_batch: bound proof i against instances[i] and the 32-byte roots[i] in `mode` (1 or 3), the run verified
+    in device passes of a group of proofs each. Returns (results, digests): results as verify_public_batch returns them - what
+    verify_public_bound(pk, instances[i], proofs[i], roots[i], mode, ctx, device=True) returns for that pair alone -, digests the
+    statement digest of every instance as the device computed it, rejected items included."""
+    if not len(instances) == len(roots) == len(proofs):
+        raise ValueError("verify_public_bound_batch: one instance and one root per proof")
+    nc, nco = pk_claim_shape(pk)
+    n = len(proofs)
+    m, nc1, nco1 = max(n, 1), max(nc, 1), max(nco, 1)
+    hs = (C.c_void_p * m)(*[x.h.value for x in instances])
+    rs = (C.c_char_p * m)(*[bytes(r) for r in roots])
+    ps = (C.c_char_p * m)(*[bytes(p) for p in proofs])
+    lens = (C.c_size_t * m)(*[len(p) for p in proofs])
+    res = (C.c_int * m)()
+    claims = (HgInputClaim * (m * nc1))()
+    points = np.zeros(2 * m * nco1, dtype=np.uint64)
+    counts = (C.c_size_t * m)()
+    dg = (C.c_uint8 * (32 * m))()
+    reasons = C.create_string_buffer(m * reason_cap)
+    if lib().hg_verify_public_bound_batch(_h(ctx), pk.h, hs, rs, ps, lens, n, mode, res, claims, nc1, _ptr(points), nco1, counts, dg, reasons, reason_cap) < 0:
+        raise HgError(lib().hg_last_error().decode())
+    raw = reasons.raw
+    out = []
+    for i in range(n):
+        ok = res[i] == 0
+        cl = InputClaims((HgInputClaim * nc1)(*claims[i * nc1:(i + 1) * nc1]), counts[i], points[2 * i * nco1:2 * (i + 1) * nco1].copy()) if ok else None
+        out.append((ok, raw[i * reason_cap:(i + 1) * reason_cap].split(b"\0", 1)[0].decode(), cl))
+    return out, [bytes(dg[32 * i:32 * (i + 1)]) for i in range(n)]
 
 
 def values_instance_digest(ctx, pk, values):

@@ -380,13 +380,17 @@ static int verify_public_entry(const char* who, hg_ctx* ctx, bool device, const 
 // (handles: hg_witness) or Instance (handles: hg_instance); run(items, P, N, why, open) is the field's device pass.
 // Historical: the witness batches report a missing context as "null argument" and a host-only key second, in words of its own; the
 // public batches report both first, in one message.
+// bound (hg_verify_public_bound_batch): roots[i] is item i's 32-byte root - the array and every element checked here, the mode by
+// check_bound_mode; run reads the array as it is.
 template <class A, class Item, class Run>
 static int batch_entry(const std::string& who, hg_ctx* ctx, const hg_pk* pk, const void* const* handles, const uint8_t* const* proofs, const size_t* lens, size_t n, int mode,
-                       int* results, void* claims, size_t claim_cap_each, uint64_t* points, size_t coord_cap_each, size_t* n_claims, char* reasons, size_t reason_cap, Run run) {
+                       int* results, void* claims, size_t claim_cap_each, uint64_t* points, size_t coord_cap_each, size_t* n_claims, char* reasons, size_t reason_cap, Run run,
+                       bool bound = false, const uint8_t* const* roots = nullptr) {
     constexpr bool pub = std::is_same<Item, Instance>::value;
+    if (bound) check_bound_mode(who, mode);   // (the mode rule comes first, as in hg_prove_committed_mode: its text is part of the contract)
     if (pub) {
         if (!ctx || !pk || !pk->ctx) throw Error(who + ": needs a device context and a device prover key");
-        if (n && (!handles || !proofs || !lens || !results || !n_claims)) throw Error(who + ": null argument");
+        if (n && (!handles || !proofs || !lens || !results || !n_claims || (bound && !roots))) throw Error(who + ": null argument");
     } else {
         if (!ctx || !pk || (n && (!handles || !proofs || !lens || !results))) throw Error(who + ": null argument");
         if (!pk->ctx) throw Error(who + ": needs a device prover key (hg_setup with a context)");
@@ -398,6 +402,7 @@ static int batch_entry(const std::string& who, hg_ctx* ctx, const hg_pk* pk, con
     std::vector<size_t> N(n);
     for (size_t i = 0; i < n; i++) {
         if (!handles[i] || !proofs[i]) throw Error(who + ": null " + (pub ? "instance" : "witness") + " or proof at index " + std::to_string(i));
+        if (bound && !roots[i]) throw Error(who + ": null root at index " + std::to_string(i));
         if constexpr (pub) {
             check_instance(pk, as_instance(handles[i]), (who + ": index " + std::to_string(i)).c_str());
             items[i] = &as_instance(handles[i])->inst;
@@ -999,6 +1004,7 @@ int hg_set_option(hg_ctx* ctx, const char* name, int64_t value) {
     if (n == "one_stream") { if (ctx->one_stream != (value != 0)) ctx->walk_counts.clear(); ctx->one_stream = value != 0; }
     else if (n == "graph") { ctx->use_graph = value != 0; if (!ctx->use_graph) prove_cache_drop(ctx); }
     else if (n == "verify_batch_group") { if (value < 0) throw Error("hg_set_option: verify_batch_group must be >= 0"); ctx->verify_batch_group = value; }
+    else if (n == "bound_batch_slice") { if (value < 0) throw Error("hg_set_option: bound_batch_slice must be >= 0"); ctx->bound_batch_slice = value; }
     else throw Error("hg_set_option: unknown option " + n);
     return 0;
     HG_CATCH(-1)
@@ -1880,6 +1886,20 @@ int hg_verify_public_batch(hg_ctx* ctx, const hg_pk* pk, const void* const* inst
                                         reasons, reason_cap, [&](auto& I, auto& P, auto& N, auto& why, auto& open) { verify_public_batch_device(ctx, pk, I, P, N, mode, why, open); }))
 }
 
+int hg_verify_public_bound_batch(hg_ctx* ctx, const hg_pk* pk, const void* const* instances, const uint8_t* const* roots, const uint8_t* const* proofs, const size_t* lens,
+                                 size_t n, int mode, int* results, void* claims, size_t claim_cap_each, uint64_t* points, size_t coord_cap_each, size_t* n_claims,
+                                 uint8_t* digests, char* reasons, size_t reason_cap) {
+    HG_TRY
+    std::vector<uint8_t> dg;   // (an error of the call leaves digests alone)
+    const int rejected = batch_entry<GlAbi, Instance>("hg_verify_public_bound_batch", ctx, pk, instances, proofs, lens, n, mode, results, claims, claim_cap_each, points,
+                                                      coord_cap_each, n_claims, reasons, reason_cap, [&](auto& I, auto& P, auto& N, auto& why, auto& open) {
+                                                          verify_public_bound_batch_device(ctx, pk, I, std::vector<const uint8_t*>(roots, roots + n), P, N, mode, why, open, dg);
+                                                      }, true, roots);
+    if (digests && !dg.empty()) memcpy(digests, dg.data(), dg.size());
+    return rejected;
+    HG_CATCH(-1)
+}
+
 int hg_claims_settle(hg_ctx* ctx, const hg_params* params, const hg_witness* w, const void* claims, size_t n, const uint64_t* points) {
     HG_ENTRY(claims_settle_entry<GlAbi>("hg_claims_settle", ctx, params, w, claims, n, points))
 }
@@ -1893,8 +1913,9 @@ int hg_instance_mle_batch(hg_ctx* ctx, const void* const* instances, size_t n, i
 }
 
 // ---- proofs bound to the secrets' commitment and the ciphertext (hg.h: "Bound proofs") ------------------------------------------
-// hg_instance_digest (batch false: instances is the one handle, ctx may be null: the host tree) and hg_instance_digest_batch
-static int instance_digest_entry(const char* who, bool batch, hg_ctx* ctx, const void* const* instances, size_t n, uint8_t* out) {
+// hg_instance_digest (batch false: instances is the one handle, ctx may be null: the host tree), hg_instance_digest_batch and
+// hg_instance_digest_group (group: the digest of the bound batch, out of its staged sets)
+static int instance_digest_entry(const char* who, bool batch, hg_ctx* ctx, const void* const* instances, size_t n, uint8_t* out, bool group = false) {
     const std::string w(who);
     if (batch && !n) return 0;
     if (!instances || !out) throw Error(w + ": null argument");
@@ -1912,7 +1933,8 @@ static int instance_digest_entry(const char* who, bool batch, hg_ctx* ctx, const
     if (!ctx) instance_digest_host(p, *I[0], res.data());
     else {
         try {
-            pcs::instance_digest_device(ctx, p, I, res.data());
+            if (group) instance_digest_group_device(ctx, p, I, res.data());
+            else pcs::instance_digest_device(ctx, p, I, res.data());
         } catch (const std::exception& e) {
             throw Error(w + ": " + e.what());
         }
@@ -1927,6 +1949,10 @@ int hg_instance_digest(hg_ctx* ctx, const void* instance, uint8_t out32[32]) {
 
 int hg_instance_digest_batch(hg_ctx* ctx, const void* const* instances, size_t n, uint8_t* out) {
     HG_ENTRY(instance_digest_entry("hg_instance_digest_batch", true, ctx, instances, n, out))
+}
+
+int hg_instance_digest_group(hg_ctx* ctx, const void* const* instances, size_t n, uint8_t* out) {
+    HG_ENTRY(instance_digest_entry("hg_instance_digest_group", true, ctx, instances, n, out, true))
 }
 
 int hg_values_instance_digest(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, uint8_t out32[32]) {

@@ -143,15 +143,9 @@ __device__ __forceinline__ void digest_block(const DigestMember* __restrict__ M,
 // whole 128-byte lines that no other lane touches, each fetched from HBM once and found in the cache by the loads that follow. LAID:
 // a member whose word is not a signed value in range sets its flag.
 template <bool LAID>
-__global__ __launch_bounds__(DIGEST_TPB) void k_instance_digest_leaves(const DigestMember* __restrict__ mem, const DigestShape S, size_t G, u64* __restrict__ trees,
-                                                                      size_t tree_words, unsigned* __restrict__ flags) {
-    const size_t id = (size_t)blockIdx.x * DIGEST_TPB + threadIdx.x;
-    if (id >= G << S.log2_leaves) return;
-    const size_t m = id >> S.log2_leaves, j = id & (((size_t)1 << S.log2_leaves) - 1);
-    const DigestMember* M = mem + m;
+__device__ __forceinline__ void digest_leaf(const DigestMember* __restrict__ M, const DigestShape& S, size_t j, u64 (&a)[25], bool& bad) {
     const size_t blocks = (((size_t)1 << S.log2_leaf) + 1) / RATE_WORDS + 1;   // the last block holds the rest (possibly nothing) and the padding
-    bool bad = false;
-    u64 a[25], nx[RATE_WORDS];
+    u64 nx[RATE_WORDS];
 #pragma unroll
     for (int i = 0; i < 25; i++) a[i] = 0;
     digest_block<LAID>(M, S, j, 0, nx, bad);
@@ -162,9 +156,55 @@ __global__ __launch_bounds__(DIGEST_TPB) void k_instance_digest_leaves(const Dig
         else a[RATE_WORDS - 1] ^= 0x8000000000000000ull;
         keccak_f(a);
     }
+}
+template <bool LAID>
+__global__ __launch_bounds__(DIGEST_TPB) void k_instance_digest_leaves(const DigestMember* __restrict__ mem, const DigestShape S, size_t G, u64* __restrict__ trees,
+                                                                      size_t tree_words, unsigned* __restrict__ flags) {
+    const size_t id = (size_t)blockIdx.x * DIGEST_TPB + threadIdx.x;
+    if (id >= G << S.log2_leaves) return;
+    const size_t m = id >> S.log2_leaves, j = id & (((size_t)1 << S.log2_leaves) - 1);
+    bool bad = false;
+    u64 a[25];
+    digest_leaf<LAID>(mem + m, S, j, a, bad);
     u64* out = trees + m * tree_words + 4 * j;
     out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
     if (LAID && bad) atomicOr(flags + m, 1u);
+}
+
+// The digest of a bound batch (verifier_batch.hip: a slice of a staged set; hg_instance_digest_group). The members are read where the
+// batch staged them: member m's 2kn signed words - a, then ct0 - at set + m stride, the compact read without a descriptor table. One
+// workgroup of DIGEST_TPB = 64 threads per (member, block of 64 leaves): thread t hashes leaf 64 b + t as k_instance_digest_leaves
+// does (digest_leaf: the state in registers, the next sponge block loaded under the permutation of this one), puts its four words into
+// LDS, and the workgroup folds its min(64, leaves) leaves to one node there - the levels one behind the other as in a tree buffer,
+// 4 (64 + 32 + .. + 1) words = 4064 bytes, one merkle_node a thread and one barrier a level, six levels at most. Node b of member m goes
+// to nodes + m tree_words + 4 b: the root where a member has at most 64 leaves (one leaf: that leaf), else leaf b of the small tree that
+// merkle_levels_device_batch finishes. leaves = 2^log2_leaves is a power of two, so a workgroup's leaf count is one as well.
+constexpr int DIGEST_FOLD_WORDS = 4 * (2 * DIGEST_TPB - 1);
+__global__ __launch_bounds__(DIGEST_TPB) void k_instance_digest_group(const u64* __restrict__ set, size_t stride, const DigestShape S, u64* __restrict__ nodes,
+                                                                     size_t tree_words) {
+    __shared__ u64 fold[DIGEST_FOLD_WORDS];
+    const size_t leaves = (size_t)1 << S.log2_leaves, per = leaves > DIGEST_TPB ? leaves / DIGEST_TPB : 1;   // workgroups a member
+    const size_t m = blockIdx.x / per, b = blockIdx.x - m * per, j = b * DIGEST_TPB + threadIdx.x;
+    const size_t mine = leaves < DIGEST_TPB ? leaves : DIGEST_TPB;                                           // leaves of this workgroup
+    if (threadIdx.x < mine) {   // (j < leaves: every word read lies inside the member)
+        DigestMember M;
+        M.a[0] = set + m * stride;
+        M.ct0 = M.a[0] + ((size_t)1 << (S.log2_n + S.log2_k));
+        bool bad = false;
+        u64 a[25];
+        digest_leaf<false>(&M, S, j, a, bad);
+        u64* leaf = fold + 4 * threadIdx.x;
+        leaf[0] = a[0]; leaf[1] = a[1]; leaf[2] = a[2]; leaf[3] = a[3];
+    }
+    __syncthreads();
+    u64* below = fold;
+    for (size_t count = mine / 2; count >= 1; count >>= 1) {
+        u64* here = below + 8 * count;   // `below` has 2 * count nodes of 4 words
+        if (threadIdx.x < count) merkle_node(below, here, threadIdx.x);
+        __syncthreads();
+        below = here;
+    }
+    if (threadIdx.x < 4) nodes[m * tree_words + 4 * b + threadIdx.x] = below[threadIdx.x];
 }
 
 // sum_{r < nrows} w[r] * src[r << shift]. Products go into two accumulators (c0 and c1 of the weight) that are reduced every
@@ -509,8 +549,7 @@ std::shared_ptr<void> slab_alloc(size_t bytes, u64** p) {
 }
 
 // ---- the statement digest: host side
-void instance_digest_enqueue(hg_ctx* ctx, hipStream_t st, const Params& p, bool laid, const DigestMember* mem, size_t G, uint8_t* roots, unsigned* flags) {
-    if (!G) return;
+static DigestShape digest_shape(const Params& p) {
     DigestShape S;
     S.log2_n = p.n_log2;
     S.log2_k = p.log2k;
@@ -518,6 +557,31 @@ void instance_digest_enqueue(hg_ctx* ctx, hipStream_t st, const Params& p, bool 
     static_assert(DIGEST_LEAF_WORDS == 128, "2^7 words a full leaf");
     S.log2_leaves = p.n_log2 + p.log2k + 1 - S.log2_leaf;
     for (int i = 0; i < HG_MAX_K; i++) S.half[i] = i < p.k ? (p.raw.qis[i] - 1) / 2 : 0;
+    return S;
+}
+
+// the subtree nodes of a member and the levels above them: 8 words a node of the lowest level, as in every tree buffer
+static size_t digest_group_per(const DigestShape& S) { return std::max<size_t>(1, ((size_t)1 << S.log2_leaves) / DIGEST_TPB); }
+size_t instance_digest_group_words(const Params& p) { return 8 * digest_group_per(digest_shape(p)); }
+
+void instance_digest_group_enqueue(hg_ctx* ctx, hipStream_t st, const Params& p, const u64* d_set, size_t G, u64* d_nodes, uint8_t* h_roots) {
+    if (!G) return;
+    const DigestShape S = digest_shape(p);
+    const size_t per = digest_group_per(S), tree_words = 8 * per, stride = (size_t)2 << (p.n_log2 + p.log2k);
+    hipStream_t prof_was = ctx->prof_stream;
+    ctx->prof_stream = st;
+    ctx->prof_begin(ctx->prof_class("instance_digest_group", false), (double)G * (8.0 * stride + 32 * per + (per > 1 ? 96.0 * per : 0)));
+    k_instance_digest_group<<<(unsigned)(G * per), DIGEST_TPB, 0, st>>>(d_set, stride, S, d_nodes, tree_words);
+    if (per > 1) merkle_levels_device_batch(st, d_nodes, tree_words, per, G);
+    ctx->prof_end();
+    ctx->prof_stream = prof_was;
+    // the root is the last node of a member's small tree: word 4 (2 per - 2)
+    hip_check(hipMemcpy2DAsync(h_roots, 32, d_nodes + 4 * (2 * per - 2), tree_words * 8, 32, G, hipMemcpyDeviceToHost, st), "instance digest: download the roots");
+}
+
+void instance_digest_enqueue(hg_ctx* ctx, hipStream_t st, const Params& p, bool laid, const DigestMember* mem, size_t G, uint8_t* roots, unsigned* flags) {
+    if (!G) return;
+    const DigestShape S = digest_shape(p);
     const size_t leaves = (size_t)1 << S.log2_leaves, tree_words = 8 * leaves, bytes = G * sizeof(DigestMember), need = (bytes + 15) & ~(size_t)15;
     if (ctx->stage_used + need > ctx->stage_cap) throw Error("the staging buffer cannot hold the members of the digest");
     DigestMember* h_mem = reinterpret_cast<DigestMember*>(ctx->h_stage + ctx->stage_used);

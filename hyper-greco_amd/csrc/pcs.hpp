@@ -92,6 +92,14 @@ struct DigestJob {   // the laid-out digest of one values object beside a commit
 // (flags may be null for compact members). Nothing is synchronised: roots and flags are valid once st has been. The launches are
 // counted in the profiler classes instance_digest_leaves and instance_digest_tree (the context's prof_stream is st for their duration).
 void instance_digest_enqueue(hg_ctx* ctx, hipStream_t st, const Params& p, bool laid, const DigestMember* mem, size_t G, uint8_t* roots, unsigned* flags);
+// The digest of a bound batch (hg_verify_public_bound_batch, hg_instance_digest_group): G members that lie back to back as the batch
+// staged them, member m's 2kn signed words at d_set + 2kn m, hashed by k_instance_digest_group - no descriptor table, neither the
+// context's arena nor its staging buffer. The caller owns the scratch: d_nodes, instance_digest_group_words(p) words a member (the
+// nodes of its blocks of 64 leaves and the levels above them: 8 KB at n=32768 k=16), and h_roots, 32 page-locked bytes a member, valid
+// once st has been waited for. Two launches where a member has more than 64 leaves, else one; nothing is synchronised. Counted in the
+// profiler class instance_digest_group (the context's prof_stream is st for their duration).
+size_t instance_digest_group_words(const Params& p);
+void instance_digest_group_enqueue(hg_ctx* ctx, hipStream_t st, const Params& p, const u64* d_set, size_t G, u64* d_nodes, uint8_t* h_roots);
 // hg_instance_digest with a context and hg_instance_digest_batch: every instance uploaded as it is, one launch over all of them, one
 // synchronisation; out: 32 bytes an instance
 void instance_digest_device(hg_ctx* ctx, const Params& p, const std::vector<const Instance*>& insts, uint8_t* out);

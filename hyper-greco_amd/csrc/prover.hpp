@@ -79,6 +79,7 @@ struct hg_ctx {
     bool one_stream = false;  // keep every launch on `stream` (per-kernel timings without cross-stream interference)
     int mode = 0;             // protocol mode of the next proves: bit 0 absorbing transcript, bit 1 extension-field memory checking
     int64_t verify_batch_group = 0;   // hg_verify_device_batch, hg_verify_public_batch, hg_pcs_verify_device_batch and their _bn254 forms: most proofs or openings per device pass (0: sized from the arena budget)
+    int64_t bound_batch_slice = 0;    // hg_verify_public_bound_batch, hg_instance_digest_group: members of a group staged and digested at a time (0: what fits in 32 MiB of instance words, at least one)
     void* verify_batch = nullptr;     // verifier_batch.hip: VerifyBatchBufs (pinned and device input sets, upload stream), freed with the context
     // bump arena: chunks are kept across proves, offsets reset per prove
     struct Chunk { char* p; size_t cap, used; size_t high = 0; };  // high: largest `used` since the last reset
@@ -336,6 +337,16 @@ void verify_public_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<
 // hg_instance_mle_batch: one public table (which / index as instance_mle_device) of every instance at one point, through the batch's
 // kernel as one work unit; out: one E2 per instance
 void instance_mle_batch_device(hg_ctx* ctx, const Params& p, const std::vector<const Instance*>& insts, int which, int index, const std::vector<E2>& pt, E2* out);
+// hg_verify_public_bound_batch (verifier_batch.hip): verify_public_batch_device for bound proofs - proof i against insts[i] and
+// roots[i] (32 bytes). A group's instances are staged in slices (context option "bound_batch_slice") and each slice's statement
+// digests are taken from the staged set on the upload stream, in the batch's own buffers; a walk starts from bound_seed over its
+// digest and its root. digests: 32 bytes an item, as the device computed them (why and open as above)
+void verify_public_bound_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Instance*>& insts, const std::vector<const uint8_t*>& roots,
+                                      const std::vector<const uint8_t*>& proofs, const std::vector<size_t>& lens, int mode, std::vector<std::string>& why,
+                                      std::vector<std::vector<OpenClaim>>& open, std::vector<uint8_t>& digests);
+// hg_instance_digest_group: the digests of the bound batch alone - the instances staged into set 0 in slices, each slice hashed out of
+// the staged set behind its copy; out: 32 bytes an instance
+void instance_digest_group_device(hg_ctx* ctx, const Params& p, const std::vector<const Instance*>& insts, uint8_t* out);
 void verify_batch_drop(hg_ctx* ctx);   // the context's batch buffers (hg_destroy)
 void prove_cache_drop(hg_ctx* ctx);
 

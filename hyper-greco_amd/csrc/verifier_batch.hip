@@ -15,6 +15,10 @@
 // hg_verify_public_batch is the same pass from the ciphertext (the batch form of verify_public_device, verifier_dev.hip): the walks
 // run with public_only, the recording backend in its compact form, each proof's instance is staged as it is (2 k n signed words),
 // k_vin_compact_dots evaluates ais and ct0is from them, and the claims on the secret inputs come back from each proof's pending state.
+// hg_verify_public_bound_batch is that pass for bound proofs (the batch form of verify_public_device with a root): a third source kind
+// of verify_batch_run. A group's instances are staged in slices, each slice's statement digests are taken out of the staged set on the
+// upload stream, in the batch's own buffers (batch_stage_instances_bound), and a group's walks wait for its digests before they start
+// from bound_seed; launch and complete are the unbound ones.
 #include <algorithm>
 #include <cstring>
 #include <map>
@@ -22,6 +26,7 @@
 #include <omp.h>
 #include "verifier_batch.hpp"
 #include "gl_wide.hpp"
+#include "pcs.hpp"
 
 namespace hg {
 namespace {
@@ -295,6 +300,7 @@ VerifyBatchBufs* batch_bufs(hg_ctx* ctx) {
         b->slabs->cap = VB_PCS_COMMIT_BUDGET_BN254;
         hip_check(hipStreamCreateWithFlags(&b->up, hipStreamNonBlocking), "hipStreamCreate(batch uploads)");
         for (auto& e : b->ev) hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate(batch uploads)");
+        for (auto& e : b->ev_dg) hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate(batch digests)");
     }
     return static_cast<VerifyBatchBufs*>(ctx->verify_batch);
 }
@@ -373,9 +379,12 @@ void stage_table(std::vector<Piece>& pieces, u64*& dst, const u64* src, size_t n
     for (size_t o = 0; o < n; o += PIECE) pieces.push_back(Piece{dst + o, src + o, std::min(PIECE, n - o)});
     dst += n;
 }
-void stage_copy(VerifyBatchBufs* B, int s, const std::vector<Piece>& pieces, size_t total, [[maybe_unused]] int nthr, const std::string& w) {
+void stage_gather(const std::vector<Piece>& pieces, [[maybe_unused]] int nthr) {
 #pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)pieces.size()))
     for (long long q = 0; q < (long long)pieces.size(); q++) memcpy(pieces[q].dst, pieces[q].src, pieces[q].n * sizeof(u64));
+}
+void stage_copy(VerifyBatchBufs* B, int s, const std::vector<Piece>& pieces, size_t total, int nthr, const std::string& w) {
+    stage_gather(pieces, nthr);
     hip_check(hipMemcpyAsync(B->d_in[s], B->h_in[s], total * sizeof(u64), hipMemcpyHostToDevice, B->up), (w + ": upload inputs").c_str());
     hip_check(hipEventRecord(B->ev[s], B->up), "hipEventRecord");
     B->recorded[s] = true;
@@ -413,6 +422,55 @@ void batch_stage_instances(VerifyBatchBufs* B, int s, const std::vector<const In
     stage_copy(B, s, pieces, np * 2 * kn, nthr, w);
 }
 
+// batch_stage_instances for the bound pass (hg_verify_public_bound_batch, hg_instance_digest_group), in slices of `slice` members: the
+// host threads gather a slice, its copy is enqueued on the upload stream, the statement digests of its members behind the copy
+// (pcs::instance_digest_group_enqueue: read out of d_in[s], the nodes in d_dg[s]) and the copy of their 32-byte roots into h_dg[s] behind
+// those - so copies and digests run under the gather of the next slice, and nothing of it touches the context's arena or staging
+// buffer. The set's event is recorded behind the last slice as ever (stage_set waits for it before the set, its node words and its
+// digest block are reused or grown), ev_dg[s] at the same place: the digests of the set are back.
+namespace {
+void batch_stage_instances_bound(hg_ctx* ctx, VerifyBatchBufs* B, int s, const Params& p, const std::vector<const Instance*>& insts, size_t i0, size_t i1,
+                                 size_t kn, size_t slice, int nthr, const char* who) {
+    const size_t np = i1 - i0, dgw = pcs::instance_digest_group_words(p);
+    const std::string w(who);
+    stage_set(B, s, np * 2 * kn, w);
+    if (B->dg_words[s] < np * dgw) {
+        if (B->d_dg[s]) { (void)hipFree(B->d_dg[s]); B->d_dg[s] = nullptr; }
+        B->dg_words[s] = 0;
+        hip_check(hipMalloc((void**)&B->d_dg[s], np * dgw * sizeof(u64)), "hipMalloc(batch digests)");
+        B->dg_words[s] = np * dgw;
+    }
+    if (B->dg_cap[s] < np) {
+        if (B->h_dg[s]) { (void)hipHostFree(B->h_dg[s]); B->h_dg[s] = nullptr; }
+        B->dg_cap[s] = 0;
+        hip_check(hipHostMalloc((void**)&B->h_dg[s], 32 * np, hipHostMallocDefault), "hipHostMalloc(batch digests)");
+        B->dg_cap[s] = np;
+    }
+    for (size_t a = 0; a < np; a += slice) {
+        const size_t b = std::min(np, a + slice);
+        std::vector<Piece> pieces;
+        for (size_t m = a; m < b; m++) {
+            const Instance& x = *insts[i0 + m];
+            u64* dst = B->h_in[s] + m * 2 * kn;
+            stage_table(pieces, dst, reinterpret_cast<const u64*>(x.a.data()), kn);
+            stage_table(pieces, dst, reinterpret_cast<const u64*>(x.ct0.data()), kn);
+        }
+        stage_gather(pieces, nthr);
+        hip_check(hipMemcpyAsync(B->d_in[s] + a * 2 * kn, B->h_in[s] + a * 2 * kn, (b - a) * 2 * kn * sizeof(u64), hipMemcpyHostToDevice, B->up),
+                  (w + ": upload inputs").c_str());
+        pcs::instance_digest_group_enqueue(ctx, B->up, p, B->d_in[s] + a * 2 * kn, b - a, B->d_dg[s] + a * dgw, B->h_dg[s] + 32 * a);
+    }
+    hip_check(hipEventRecord(B->ev[s], B->up), "hipEventRecord");
+    B->recorded[s] = true;
+    hip_check(hipEventRecord(B->ev_dg[s], B->up), "hipEventRecord");
+}
+// members a slice: the option, else what fits in 32 MiB of instance words, at least one (4 at n=32768 k=16)
+size_t bound_slice(const hg_ctx* ctx, size_t kn) {
+    if (ctx->bound_batch_slice > 0) return (size_t)ctx->bound_batch_slice;
+    return std::max<size_t>(1, ((size_t)32 << 20) / (2 * kn * sizeof(u64)));
+}
+}  // namespace
+
 void batch_stage_blobs(VerifyBatchBufs* B, int s, const std::vector<BatchBlob>& blobs, size_t total_words, [[maybe_unused]] int nthr, const char* who) {
     const std::string w(who);
     stage_set(B, s, std::max<size_t>(total_words, 1), w);
@@ -433,8 +491,11 @@ void verify_batch_drop(hg_ctx* ctx) {
     auto* b = static_cast<VerifyBatchBufs*>(ctx->verify_batch);
     if (b->up) { (void)hipStreamSynchronize(b->up); (void)hipStreamDestroy(b->up); }
     for (auto e : b->ev) if (e) (void)hipEventDestroy(e);
+    for (auto e : b->ev_dg) if (e) (void)hipEventDestroy(e);
     for (auto p : b->h_in) if (p) (void)hipHostFree(p);
     for (auto p : b->d_in) if (p) (void)hipFree(p);
+    for (auto p : b->h_dg) if (p) (void)hipHostFree(p);
+    for (auto p : b->d_dg) if (p) (void)hipFree(p);
     if (b->h_desc) (void)hipHostFree(b->h_desc);
     if (b->h_out) (void)hipHostFree(b->h_out);
     if (b->slabs) b->slabs->close();
@@ -459,20 +520,25 @@ void vin_launch(hipStream_t st, bool compact, const VinUnit* units, const VinMem
 
 // What a batch checks its proofs against: witness handles (hg_verify_device_batch: ws) or public instances (hg_verify_public_batch:
 // insts, and open[i] receives the claims an accepted proof i leaves on the secret inputs). `who` prefixes the error messages.
+// roots (hg_verify_public_bound_batch, else null): the proofs are bound ones - proof i's transcript starts from bound_seed over the
+// statement digest of insts[i], taken from the staged set, and roots[i]; digests receives the 32 bytes of every item.
 struct BatchSrc {
     const char* who;
     const std::vector<const Witness*>* ws;
     const std::vector<const Instance*>* insts;
     std::vector<std::vector<OpenClaim>>* open;
+    const std::vector<const uint8_t*>* roots = nullptr;
+    std::vector<uint8_t>* digests = nullptr;
 };
 
 void verify_batch_run(hg_ctx* ctx, const hg_pk* pk, const BatchSrc& src, const std::vector<const uint8_t*>& proofs, const std::vector<size_t>& lens, int mode,
                       std::vector<std::string>& why) {
     const size_t n = proofs.size();
-    const bool pub = src.insts != nullptr;
+    const bool pub = src.insts != nullptr, bound = src.roots != nullptr;
     const std::string who(src.who);
     why.assign(n, std::string());
     if (pub) src.open->assign(n, std::vector<OpenClaim>());
+    if (bound) src.digests->assign(32 * n, 0);
     if (!n) return;
     const bool times = hg_times("verify");
     const double t0 = omp_get_wtime();
@@ -499,21 +565,30 @@ void verify_batch_run(hg_ctx* ctx, const hg_pk* pk, const BatchSrc& src, const s
     std::vector<std::vector<Walked>> groups(ngroups);
     // stage group g: gather its inputs into page-locked set g & 1 (host threads), copy them on the upload stream
     auto stage = [&](size_t g) {
-        if (pub) batch_stage_instances(B, (int)(g & 1), *src.insts, g * G, std::min(n, g * G + G), kn, nthr, src.who);
+        if (bound) batch_stage_instances_bound(ctx, B, (int)(g & 1), p, *src.insts, g * G, std::min(n, g * G + G), kn, bound_slice(ctx, kn), nthr, src.who);
+        else if (pub) batch_stage_instances(B, (int)(g & 1), *src.insts, g * G, std::min(n, g * G + G), kn, nthr, src.who);
         else batch_stage_inputs(B, (int)(g & 1), *src.ws, g * G, std::min(n, g * G + G), L, nthr, src.who);
     };
-    // walk group g on the host threads
+    // walk group g on the host threads (a bound walk cannot squeeze its first challenge before its digest is back: wait for the set's)
     auto walk = [&](size_t g) {
         const size_t i0 = g * G, i1 = std::min(n, i0 + G);
         std::vector<Walked>& W = groups[g];
         W.resize(i1 - i0);
+        const uint8_t* dg = nullptr;
+        if (bound) {
+            hip_check(hipEventSynchronize(B->ev_dg[g & 1]), (who + ": the statement digests").c_str());
+            dg = B->h_dg[g & 1];
+            memcpy(src.digests->data() + 32 * i0, dg, 32 * (i1 - i0));
+        }
 #pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)W.size()))
         for (long long q = 0; q < (long long)W.size(); q++) {
             Walked& x = W[q];
             x.idx = i0 + (size_t)q;
             try {
                 x.rec.reset(new RecBackend(pk, pub));
-                x.pend = verify_walk(*x.rec, p, pk->lasso, pk->circuit, proofs[x.idx], lens[x.idx], mode, pub);
+                std::vector<uint8_t> seed;
+                if (bound) seed = bound_seed(p.raw, mode, dg + 32 * (size_t)q, (*src.roots)[x.idx]);
+                x.pend = verify_walk(*x.rec, p, pk->lasso, pk->circuit, proofs[x.idx], lens[x.idx], mode, pub, bound ? &seed : nullptr);
             } catch (const std::exception& e) { x.error = e.what(); }
         }
         for (auto& x : W)
@@ -765,6 +840,7 @@ void verify_batch_run(hg_ctx* ctx, const hg_pk* pk, const BatchSrc& src, const s
         t_sync += omp_get_wtime() - ts;
         complete(g);
     }
+    if (bound) ctx->prof_collect();   // (the last digests were waited for by the last walk, ahead of the synchronisation above)
     if (times)
         fprintf(stderr, "[hg] verify_batch: %zu proofs in %zu groups of up to %zu: %.2f ms in all (staging and walks %.2f, waiting for the device %.2f)\n", n,
                 ngroups, G, (omp_get_wtime() - t0) * 1e3, t_walk * 1e3, t_sync * 1e3);
@@ -780,6 +856,41 @@ void verify_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const W
 void verify_public_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Instance*>& insts, const std::vector<const uint8_t*>& proofs,
                                 const std::vector<size_t>& lens, int mode, std::vector<std::string>& why, std::vector<std::vector<OpenClaim>>& open) {
     verify_batch_run(ctx, pk, BatchSrc{"hg_verify_public_batch", nullptr, &insts, &open}, proofs, lens, mode, why);
+}
+
+void verify_public_bound_batch_device(hg_ctx* ctx, const hg_pk* pk, const std::vector<const Instance*>& insts, const std::vector<const uint8_t*>& roots,
+                                      const std::vector<const uint8_t*>& proofs, const std::vector<size_t>& lens, int mode, std::vector<std::string>& why,
+                                      std::vector<std::vector<OpenClaim>>& open, std::vector<uint8_t>& digests) {
+    verify_batch_run(ctx, pk, BatchSrc{"hg_verify_public_bound_batch", nullptr, &insts, &open, &roots, &digests}, proofs, lens, mode, why);
+}
+
+// the staging of the bound pass without its walks: groups as that pass cuts them by the option and the input budget, group g in set
+// g & 1, its digests fetched once group g + 1 is enqueued
+void instance_digest_group_device(hg_ctx* ctx, const Params& p, const std::vector<const Instance*>& insts, uint8_t* out) {
+    const size_t n = insts.size(), kn = (size_t)p.k * p.PZ();
+    if (!n) return;
+    const char* who = "hg_instance_digest_group";
+    for (const Instance* x : insts)
+        if (x->a.size() != kn || x->ct0.size() != kn) throw Error("an instance does not hold k * n coefficients a table");
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    VerifyBatchBufs* B = batch_bufs(ctx);
+    Drain drain{ctx->stream, B->up};
+    size_t G = (size_t)std::max<int64_t>(0, ctx->verify_batch_group);
+    if (!G) G = std::min(VB_MAX_GROUP, std::max<size_t>(1, VB_INPUT_BUDGET / (2 * kn * sizeof(u64))));
+    const size_t ngroups = (n + G - 1) / G;
+    const int nthr = std::max(1, hg_omp_threads());
+    auto fetch = [&](size_t g) {
+        hip_check(hipEventSynchronize(B->ev_dg[g & 1]), "hg_instance_digest_group: the statement digests");
+        memcpy(out + 32 * g * G, B->h_dg[g & 1], 32 * (std::min(n, g * G + G) - g * G));
+    };
+    for (size_t g = 0; g < ngroups; g++) {
+        batch_stage_instances_bound(ctx, B, (int)(g & 1), p, insts, g * G, std::min(n, g * G + G), kn, bound_slice(ctx, kn), nthr, who);
+        if (g) fetch(g - 1);
+    }
+    fetch(ngroups - 1);
+    hip_check(hipStreamSynchronize(B->up), "hg_instance_digest_group: synchronise");
+    hip_check(hipGetLastError(), "hg_instance_digest_group: kernels");
+    ctx->prof_collect();
 }
 
 // one eq job, then k_vin_compact_dots as ONE unit whose members are the instances' tables

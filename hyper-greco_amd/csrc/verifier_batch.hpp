@@ -23,6 +23,12 @@ struct VerifyBatchBufs {
     u64* h_in[2] = {nullptr, nullptr};
     u64* d_in[2] = {nullptr, nullptr};
     size_t words[2] = {0, 0};
+    // hg_verify_public_bound_batch: the statement digests of the set's members, hashed out of d_in[s] on the upload stream
+    u64* d_dg[2] = {nullptr, nullptr};       // each member's subtree nodes and the levels above them (pcs::instance_digest_group_words a member)
+    size_t dg_words[2] = {0, 0};
+    uint8_t* h_dg[2] = {nullptr, nullptr};   // page-locked: 32 bytes a member, the digests as they come back
+    size_t dg_cap[2] = {0, 0};               // members h_dg[s] holds
+    hipEvent_t ev_dg[2] = {nullptr, nullptr};   // the digests of set s are back
     char* h_desc = nullptr;                  // page-locked descriptor staging of one group
     size_t desc_cap = 0;
     char* h_out = nullptr;                   // page-locked results of one group (hg_pcs_open_batch: the u vectors and the opening images)

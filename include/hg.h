@@ -77,12 +77,16 @@ void hg_destroy(hg_ctx* ctx);
  *                 addresses only, because every challenge is known up front; a values object refilled by hg_witness_gen_into
  *                 keeps its graph; up to HG_GRAPH_ENTRIES (8) graphs per context, each with a private workspace)
  *   "verify_batch_group"  the most proofs one device pass of hg_verify_device_batch, hg_verify_device_batch_bn254,
- *                 hg_verify_public_batch or hg_verify_public_batch_bn254 holds, and the most openings one of
+ *                 hg_verify_public_batch, hg_verify_public_bound_batch or hg_verify_public_batch_bn254 holds (and
+ *                 hg_instance_digest_group stages), and the most openings one of
  *                 hg_pcs_verify_device_batch, hg_claims_verify_batch, hg_pcs_verify_device_batch_bn254 or
  *                 hg_claims_verify_batch_bn254, the most members one device pass of hg_pcs_commit_batch, hg_secrets_commit_batch,
  *                 hg_pcs_commit_batch_bn254 or hg_secrets_commit_batch_bn254 encodes and the most items one of hg_pcs_open_batch,
  *                 hg_claims_open_batch, hg_pcs_open_batch_bn254 or hg_claims_open_batch_bn254 opens (default 0: sized from the
  *                 memory budget, at most 64)
+ *   "bound_batch_slice"  the members of a group that hg_verify_public_bound_batch and hg_instance_digest_group gather, copy and
+ *                 digest at a time (default 0: as many as fit in 32 MiB of instance words, at least one: 4 at n=32768 k=16); a
+ *                 slice's copy and digests run under the gather of the next one. Results do not depend on it
  * Returns 0, or -1 for an unknown name. */
 int hg_set_option(hg_ctx* ctx, const char* name, int64_t value);
 
@@ -549,8 +553,9 @@ int hg_verify_mode(const hg_pk* pk, const hg_witness* w, int mode, const uint8_t
  * secret inputs (hg_secrets_commit*). Nothing else changes: a bound transcript is the absorbing transcript with that start, on the
  * prover's side and on the verifier's. mode is 1 or 3; for mode 0 or 2 every entry of this section returns -1 with the text
  * "<function>: binding needs the absorbing transcript (mode bit 1)" (a mode outside 0..3: "<function>: unknown mode bits").
- * Goldilocks, one proof per call. Still open: BN254 has no protocol modes and stays unbound; hg_verify_public_batch and the
- * hg_prove_encryptions_committed pipeline are mode 0 and stay unbound; the sharded prover is unbound; nothing here is zero knowledge.
+ * Goldilocks; hg_verify_public_bound_batch verifies a run of bound proofs in one pass. Still open: BN254 has no protocol modes and
+ * stays unbound; the hg_prove_encryptions_committed pipeline is mode 0 and stays unbound; the sharded prover is unbound; nothing here
+ * is zero knowledge.
  *
  * The statement digest. The instance is read as 2 k n signed 64-bit words, two's complement, little-endian: the k n words of a, then
  *   those of ct0, each modulus-major in ascending degree (what hg_instance_from_ciphertext takes). Leaf width B = min(128, 2 k n)
@@ -584,9 +589,30 @@ int hg_verify_mode(const hg_pk* pk, const hg_witness* w, int mode, const uint8_t
  *   also for a null root and by the mode rule. A proof made for another root, another instance or another mode, and an unbound
  *   proof, are rejected: their challenges differ from the first one on. hg_verify_public_bound followed by hg_claims_verify against
  *   the same root is a verification that needs no secret in which neither the commitment nor the ciphertext can be chosen after the
- *   challenges. */
+ *   challenges.
+ * hg_verify_public_bound_batch: hg_verify_public_bound_device for a run of n pairs under one key: proof i (proofs[i], lens[i]) is
+ *   checked against instances[i], roots[i] (32 bytes; the array hg_claims_verify_batch takes) and `mode` (1 or 3). Goldilocks, device
+ *   only. results, reasons, claims, points and n_claims follow hg_verify_public_batch in layout and meaning; for every pair the
+ *   decision, the reason text, the claims and the points are bit for bit those of hg_verify_public_bound_device on that pair alone
+ *   (and so those of hg_verify_public_bound). digests (may be NULL): 32 bytes an item, the statement digest of instances[i] as the
+ *   device computed it - for accepted and rejected items alike, it depends on the instance only. Returns the number of rejected
+ *   proofs; n == 0 returns 0 and writes nothing; -1, after which nothing is written and hg_last_error begins with the function's
+ *   name (and gives "index i" where an item is at fault): everything hg_verify_public_batch returns -1 for, a null roots or
+ *   roots[i], and - checked first - the mode rule above.
+ *   The pass is hg_verify_public_batch's with the digests ordered in. A group's instances are staged in slices (context option
+ *   "bound_batch_slice"): the host threads gather a slice, its copy goes on the upload stream, one kernel behind it hashes the
+ *   slice's members out of the staged set - one workgroup of 64 threads per (member, 64 leaves), a thread a leaf with the state in
+ *   registers, the workgroup's leaves folded to one node in LDS; members of more than 64 leaves finish with the commitment's tree
+ *   kernels over those nodes - and the 32-byte roots come back into a page-locked block of the batch; all of it in the batch's own
+ *   buffers, without the context's arena or staging buffer. The walks of a group wait for its digests (one event a group, under the
+ *   kernels of the group before), build each item's seed and go on as the unbound pass does.
+ * hg_instance_digest_group: part exposed for parity tests: the digests of n instances of one parameter set computed exactly as
+ *   hg_verify_public_bound_batch computes them - gathered into the batch's page-locked sets in slices, copied on the upload stream,
+ *   hashed by that kernel out of the staged set. out receives 32 bytes an instance: hg_instance_digest's. The contract of
+ *   hg_instance_digest_batch: device only, n == 0 returns 0, -1 for a null argument or element, no context, mixed parameters. */
 int hg_instance_digest(hg_ctx* ctx, const void* instance, uint8_t out32[32]);
 int hg_instance_digest_batch(hg_ctx* ctx, const void* const* instances, size_t n, uint8_t* out);
+int hg_instance_digest_group(hg_ctx* ctx, const void* const* instances, size_t n, uint8_t* out);
 int hg_values_instance_digest(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, uint8_t out32[32]);
 int hg_bound_seed(const hg_params* params, int mode, const uint8_t digest32[32], const uint8_t root32[32], uint8_t* out, size_t cap, size_t* len);
 int hg_prove_committed_mode(hg_ctx* ctx, const hg_pk* pk, const hg_values* v, int mode, size_t log2_row, uint8_t* proof, size_t cap, size_t* len,
@@ -595,6 +621,10 @@ int hg_verify_public_bound(const hg_pk* pk, const void* instance, int mode, cons
                            size_t claim_cap, uint64_t* points, size_t coord_cap, size_t* n_claims);
 int hg_verify_public_bound_device(hg_ctx* ctx, const hg_pk* pk, const void* instance, int mode, const uint8_t root[32], const uint8_t* proof, size_t len,
                                   void* claims, size_t claim_cap, uint64_t* points, size_t coord_cap, size_t* n_claims);
+int hg_verify_public_bound_batch(hg_ctx* ctx, const hg_pk* pk, const void* const* instances, const uint8_t* const* roots,
+                                 const uint8_t* const* proofs, const size_t* lens, size_t n, int mode, int* results,
+                                 void* claims, size_t claim_cap_each, uint64_t* points, size_t coord_cap_each,
+                                 size_t* n_claims, uint8_t* digests, char* reasons, size_t reason_cap);
 
 /* The round-by-round prover (modes 1-3) on several ranks, with ONE all-reduce per sum-check round: the exchange pattern an absorbing
  * transcript leaves [REF bfv-gkr/src/transcript.rs:205-208, 224-233: every round's message is hashed before the next challenge is
