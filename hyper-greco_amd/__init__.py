@@ -239,7 +239,8 @@ class Context:
             self.h = None
 
     def set_option(self, name, value):
-        """hg_set_option: "one_stream" (1 = no cross-stream overlap, for per-kernel timings)."""
+        """hg_set_option: "one_stream" (1 = no cross-stream overlap, for per-kernel timings), "gp_claims_device" (0 = the grand
+        products' layer claims in the transcript replay instead of the tail kernel), ... (include/hg.h)."""
         L = lib()
         L.hg_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
         if L.hg_set_option(self.h, name.encode(), int(value)) != 0:

@@ -1003,6 +1003,10 @@ int hg_set_option(hg_ctx* ctx, const char* name, int64_t value) {
     const std::string n(name);
     if (n == "one_stream") { if (ctx->one_stream != (value != 0)) ctx->walk_counts.clear(); ctx->one_stream = value != 0; }
     else if (n == "graph") { ctx->use_graph = value != 0; if (!ctx->use_graph) prove_cache_drop(ctx); }
+    else if (n == "gp_claims_device") {   // (a cached launch graph holds the descriptors and transcript steps of the form it was walked in)
+        if (ctx->gp_claims_device != (value != 0)) { prove_cache_drop(ctx); ctx->walk_counts.clear(); }
+        ctx->gp_claims_device = value != 0;
+    }
     else if (n == "verify_batch_group") { if (value < 0) throw Error("hg_set_option: verify_batch_group must be >= 0"); ctx->verify_batch_group = value; }
     else if (n == "bound_batch_slice") { if (value < 0) throw Error("hg_set_option: bound_batch_slice must be >= 0"); ctx->bound_batch_slice = value; }
     else throw Error("hg_set_option: unknown option " + n);
@@ -2140,7 +2144,7 @@ int hg_sumcheck(hg_ctx* ctx, int kind, size_t nv, size_t ntab, const uint64_t* c
     // everything the kernels cannot do is refused here, on the host, before anything is uploaded or launched
     if (kind < 0 || kind > 2) throw Error("hg_sumcheck: kind must be 0 (collation), 1 (grand product) or 2 (prodsum)");
     if (kind != 0 && (ntab & 1)) throw Error("hg_sumcheck: kinds 1 and 2 take an even number of tables (pairs)");
-    const size_t max_tab = kind == 0 ? (size_t)dev::PW_MAX : kind == 1 ? 2 * (size_t)dev::PW_MAX : 2 * (size_t)dev::PS_MAX_PAIRS;
+    const size_t max_tab = kind == 0 ? (size_t)dev::PW_ENTRY_MAX : kind == 1 ? 2 * (size_t)dev::PW_ENTRY_MAX : 2 * (size_t)dev::PS_MAX_PAIRS;
     if (ntab > max_tab) throw Error("hg_sumcheck: kind " + std::to_string(kind) + " carries at most " + std::to_string(max_tab) + " tables");
     const size_t need_pw = kind == 0 ? ntab : kind == 1 ? ntab / 2 : 0;
     if (npw < need_pw) throw Error("hg_sumcheck: kind " + std::to_string(kind) + " with " + std::to_string(ntab) + " tables needs " + std::to_string(need_pw) + " powers");

@@ -1247,7 +1247,7 @@ static inline size_t sc_lds_bytes(int nv, int bd) { return (SM_SLOTS + (size_t)n
 // ---- LDS-resident tail: ALL remaining rounds of a job in one workgroup ------------------------------------------------------
 // The item's first round (half = 2^h0 pair indices) reads the job's tables from HBM and folds them into LDS; every later round
 // runs LDS -> LDS with the thread mapping of the big rounds (sc_round_body: 2^jb threads along j, the rest along the tables), the
-// last one writes the ntab scalars. How many rounds fit depends on the job's table count (st_tail_h: 12 for the two collation
+// last one leaves the ntab scalars there as well: copied to final_out, or turned into the layer's claims (gp_claim_epilogue). How many rounds fit depends on the job's table count (st_tail_h: 12 for the two collation
 // tables, 7 for the mirrored top layer, 6 for a full grand-product layer, 9-10 for the few tables of a sharded rank), so a small
 // job spends its whole launch-bound second half in ONE launch. Dynamic LDS: [SM_SLOTS][NV * ST_TAIL_THREADS reduction slots][ntab 2^h0][ntab 2^(h0-1)].
 constexpr size_t ST_TAIL_LDS_BYTES = 120 * 1024;   // for the two table regions
@@ -1256,6 +1256,32 @@ int st_tail_h(int ntab, int nvars) {
     int h = 0;
     while (h + 1 <= nvars - 1 && (size_t)ntab * (((size_t)1 << (h + 1)) + ((size_t)1 << h)) * sizeof(E2) <= ST_TAIL_LDS_BYTES) h++;
     return h;
+}
+// Claim epilogue of a grand-product layer (GpClaimEp, kernels.hpp): `fin` = the job's final evaluations as the last round left them
+// in LDS. One pair per thread; the next claim's terms stay unreduced in a W2 per thread (a thread walks at most PW_MAX / 256 + 1
+// pairs, far below WFLUSH_TRIPS) and are reduced once ahead of the sum over the workgroup.
+__device__ __forceinline__ void gp_claim_epilogue(const GpClaimEp* __restrict__ ep, const E2* __restrict__ fin, E2* __restrict__ res, E2* sm) {
+    const int nb = ep->nb, nread = ep->nread;
+    const bool has_next = ep->has_next != 0, has_claims = ep->has_claims != 0;
+    const E2 mu = ep->mu;
+    const u64 c = ep->c;
+    E2* __restrict__ ev = res + ep->evals_slot;
+    W2 w = w2_zero();
+    for (int b = threadIdx.x; b < nb; b += blockDim.x) {
+        const int rb = (nread && b >= nread) ? b - nread : b;   // the pair held for b (mirrored job: the read pair of a write pair)
+        E2 l = fin[2 * rb], r = fin[2 * rb + 1];
+        if (rb > 0) l = e2_mul(l, gload_e2(ep->winv + rb));
+        if (rb != b) { l = e2_add_f(l, c); r = e2_add_f(r, c); }
+        gstore_e2(ev + 2 * b, l);
+        gstore_e2(ev + 2 * b + 1, r);
+        const E2 cl = e2_add(l, e2_mul(mu, e2_sub(r, l)));
+        if (has_claims) gstore_e2(res + ep->claims_slot + b, cl);
+        if (has_next) w2_mac(w, cl, gload_e2(ep->gnext + b));
+    }
+    if (has_next) {
+        const E2 s = block_sum_n(w2_reduce(w), sm);
+        if (threadIdx.x == 0) gstore_e2(res + ep->next_slot, s);
+    }
 }
 template <int KIND>
 __global__ __launch_bounds__(ST_TAIL_THREADS) void k_st_tail(const StJob* __restrict__ jobs, const StItem* __restrict__ items, const E2* __restrict__ chal,
@@ -1299,8 +1325,7 @@ __global__ __launch_bounds__(ST_TAIL_THREADS) void k_st_tail(const StJob* __rest
         const int h_log2 = J.nvars - 1 - rd;
         const size_t half = (size_t)1 << h_log2;
         const int jb_log2 = h_log2 < 8 ? h_log2 : 8;
-        const bool last = rd == J.nvars - 1;
-        E2* out = last ? J.final_out : tab[(rd - I.rd) & 1];
+        E2* out = tab[(rd - I.rd) & 1];   // (the last round's ntab scalars as well: copied out, or turned into claims, below)
         E2 acc[NV];
 #pragma unroll
         for (int t = 0; t < NV; t++) acc[t] = e2_zero();
@@ -1317,6 +1342,10 @@ __global__ __launch_bounds__(ST_TAIL_THREADS) void k_st_tail(const StJob* __rest
         in = out; in_stride = half;
     }
     if ((int)threadIdx.x < (J.nvars - I.rd) * NV) res[J.sums_slot + (size_t)I.rd * NV + threadIdx.x] = keep[threadIdx.x];
+    // the ntab final evaluations (complete in LDS behind the last round's barrier)
+    const E2* fin = reinterpret_cast<const E2*>(in);
+    if (KIND == SC_GRANDPROD && J.ep) gp_claim_epilogue(J.ep, fin, res, sm);
+    else for (int t = threadIdx.x; t < J.ntab; t += blockDim.x) J.final_out[t] = fin[t];
 }
 __global__ void k_gp_slot_regroup(const E2* __restrict__ in, E2* __restrict__ out, const uint8_t* __restrict__ slot_of, const E2* __restrict__ ratio,
                                   int nrows, int nslots, int npairs, int len_log2, int sh, int has_s) {

@@ -15,7 +15,8 @@ constexpr size_t PARTIALS_E2 = (size_t)SC_MAX_BLOCKS * 6 * 64;
 constexpr int PARTIALS_TICKETS = 64 * 32;  // one 128-byte line per job of a launch
 constexpr size_t PARTIALS_BYTES = PARTIALS_E2 * sizeof(E2) + PARTIALS_TICKETS * sizeof(unsigned);
 constexpr int PS_MAX_PAIRS = 32;     // max (input, bookkeeping) table pairs of one PRODSUM sum-check
-constexpr int PW_MAX = 64;           // max batched products / memories carried in kernarg powers
+constexpr int PW_MAX = 128;          // max batched products / memories a job descriptor carries powers for
+constexpr int PW_ENTRY_MAX = 64;     // ... and what hg_sumcheck and the round-by-round prover take (k_mail patches a job's weights with one wave)
 
 struct Powers { E2 v[PW_MAX]; };     // by-value kernarg: gamma^i (grand product) or M^i (collation)
 // by-value kernarg: the output claims of one node. Points and alphas are runs of the (device-resident)
@@ -89,11 +90,31 @@ void gp_slot_regroup(hipStream_t st, const E2* in, E2* out, const uint8_t* slot_
 struct SlotRegroupJob { const E2* in; E2* out; const uint8_t* slot_of; const E2* ratio; int nrows, nslots, npairs, len_log2, sh, has_s; };
 SlotRegroupJob gp_slot_regroup_job(const E2* in, E2* out, const uint8_t* slot_of, const E2* ratio, int nrows, int nslots, int npairs, int len_log2, bool has_s);
 void gp_slot_regroup_jobs(hipStream_t st, const SlotRegroupJob* jobs, int njobs, size_t max_entries);   // every job in one launch
+// Claim epilogue of one grand-product layer (k_st_tail<SC_GRANDPROD>, prover_lasso.inc: grand_product). The workgroup that wrote the
+// layer's final evaluations also forms what the transcript replay would form from them - every factor is a challenge or a function
+// of challenges, known before the proof:
+//   left evaluation of pair b >= 1 times winv[b] = gamma^-b (the first round stored the left tables times gamma^b);
+//   mirrored job: pair nread + b = pair b plus the base-field constant c, for both evaluations (StJob::mirror);
+//   claim_b = L_b + mu (R_b - L_b)                       (layer_down, prover.rs:288-294);
+//   next claim = sum_b claim_b gnext[b]                  (sum_check_claim of the layer below, prover.rs:281-286).
+// Result slots: 2 nb evaluations at evals_slot (in place of StJob::final_out), the next claim at next_slot (has_next), the nb claims at
+// claims_slot (has_claims: the last layer, whose claims the caller reads).
+struct GpClaimEp {
+    E2 mu;
+    u64 c;
+    int nb;            // pairs of the whole batch
+    int nread;         // mirrored job: read pairs held (= nb / 2); 0 otherwise
+    int has_next, has_claims;
+    size_t evals_slot, next_slot, claims_slot;
+    const E2* winv;    // nread ? nread : nb entries (entry 0 unused)
+    const E2* gnext;   // nb entries (has_next)
+};
 struct StJob {
     const void* in;
     size_t in_stride;
     E2* buf[2];        // ping-pong storage for folded tables (ntab * len/2, ntab * len/4)
     E2* final_out;     // ntab folded scalars
+    const GpClaimEp* ep;   // grand product, tail launches: the layer's claim epilogue writes result slots instead of final_out; null: none
     int kind, ntab, nvars, base;
     int p0_only;       // grand product on a subset of the batch (multi-GPU): pair 0 only supplies p_0, its product is not summed
     // Slot form of a layer below the top one (see GpHashSrc::slot_of; prover.hip: grand_product): the job's table pairs are joint

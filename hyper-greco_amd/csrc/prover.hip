@@ -1842,7 +1842,7 @@ void sumcheck_on_tables(hg_ctx* ctx, SumcheckIO& io) {
 // prove_grand_product on caller tables (kernel-level parity entry point, hg_grand_product)
 std::vector<uint8_t> grand_product_on_tables(hg_ctx* ctx, size_t nb, size_t len, const u64* const* tables, size_t chain_skip, std::vector<E2>* claims_out,
                                              std::vector<E2>* point_out) {
-    if (nb == 0 || nb > (size_t)dev::PW_MAX || len < 2 || (len & (len - 1))) throw Error("hg_grand_product: need 1..64 tables of a power-of-two length >= 2");
+    if (nb == 0 || nb > (size_t)dev::PW_MAX || len < 2 || (len & (len - 1))) throw Error("hg_grand_product: need 1.." + std::to_string(dev::PW_MAX) + " tables of a power-of-two length >= 2");
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
     ctx->arena_reset();
     Prover P(ctx, nullptr);

@@ -128,6 +128,13 @@
         defer_write_slots(ev0, 2 * (size_t)nb);
         out.point_off = epos();
         layer_down(ev0, squeeze());
+        // Claim epilogue on the device (GpClaimEp, kernels.hpp): the tail workgroup that writes a layer's final evaluations also
+        // unscales them, completes a mirrored job's write rows, folds them by mu and sums the next layer's claim - the replay then
+        // only reads result slots. One rank holding the whole batch only: a sharded rank's evaluations are partial. Layer 0 has no
+        // sum-check and stays here; the per-pair claims are written by the LAST layer alone (GpOut::claims), no step reads the others'.
+        const bool dev_claims = ctx->gp_claims_device && world == 1 && !local;
+        int prev_ep = -1;        // gp_eps entry of the layer above, which still lacks this layer's gamma^b
+        int ndev = 0, ndev_mirrored = 0, ndev_slot = 0;
         for (int n = 1; n < nv; n++) {
             int k = nv - 1 - n;
             size_t h = (size_t)1 << n;
@@ -138,6 +145,13 @@
             E2 g = e2_one();
             for (int b = 0; b < nb; b++) { pw.v[b] = g; g = e2_mul(g, gamma); }
             Cell claim = cell();
+            if (prev_ep >= 0) {   // sum_check_claim, formed by the epilogue of the layer above
+                GpEpReq& pe = gp_eps[prev_ep];
+                pe.gnext.assign(pw.v, pw.v + nb);
+                pe.ep.has_next = 1;
+                const size_t ns = pe.ep.next_slot = slot(1);
+                push_op([this, ns, claim] { *claim = h_res()[ns]; });
+            } else
             push_op([claims, nb, pw, claim] {  // sum_check_claim (prover.rs:281-286)
                 E2 c = e2_zero();
                 for (int b = 0; b < nb; b++) c = e2_add(c, e2_mul((*claims)[b], pw.v[b]));
@@ -145,6 +159,7 @@
             });
             size_t evals = slot(2 * (size_t)nb);
             ScHandle sc;
+            const size_t jobs_before = st_jobs.size();
             const int seq = n >= nv - emit ? nv - n : 0;                    // first round launched alone, deepest layer first
             u64* nxt = seq ? lev_w[k + 1] : nullptr;                          // ... and writes tree level k + 1
             const dev::GpHashSrc* hs = (hash_src && k == 0) ? hash_src : nullptr;
@@ -196,7 +211,7 @@
                                slotted ? &spl : nullptr);
                 sc.scaled = true; sc.scale = onek;
                 if (slotted) slot_weights(gp_slots.layer[0], pwl, sc.rs[0]);
-                if (run)
+                if (run && !dev_claims)   // (the claim epilogue writes the result slots itself)
                     for (int li = p0_only ? 1 : 0; li < R; li++) {
                         scatter.push_back({fin + 2 * li, evals + 2 * (size_t)rows[li]});
                         scatter.push_back({fin + 2 * li + 1, evals + 2 * (size_t)rows[li] + 1});
@@ -239,8 +254,9 @@
             }
             mark("grand product layer " + std::to_string(n) + ": sum-check, " + std::to_string(n) + " rounds x 4 coefficients [C1 message format, C2 power order, C3 variable order]");
             defer_sumcheck(sc, 3, claim, nullptr);
-            defer_gp_unscale(evals, nb, pw);
-            if (mirrored) {   // the write rows' evaluations: folding is affine with coefficients summing to one, so row + c stays row + c
+            const bool dev_layer = dev_claims && st_jobs.size() == jobs_before + 1;   // (queued here: it ends in the tail launch of flush_stride)
+            if (!dev_layer) defer_gp_unscale(evals, nb, pw);
+            if (mirrored && !dev_layer) {   // the write rows' evaluations: folding is affine with coefficients summing to one, so row + c stays row + c
                 const u64 c = *mirror_c;
                 const int G2 = nb / 2;
                 push_op([this, evals, G2, c] {
@@ -251,8 +267,40 @@
             mark("grand product layer " + std::to_string(n) + ": v_l, v_r evaluations per tree (prover.rs:257)");
             defer_write_slots(evals, 2 * (size_t)nb);  // prover.rs:257
             out.point_off = sc.point_off;
-            layer_down(evals, squeeze());              // mu (prover.rs:259)
+            const E2 mu = squeeze();                   // prover.rs:259
+            prev_ep = -1;
+            if (dev_layer) {
+                GpEpReq e;
+                memset(&e.ep, 0, sizeof(e.ep));
+                e.job = (int)jobs_before;
+                e.ep.mu = mu; e.ep.nb = nb; e.ep.evals_slot = evals;
+                if (mirrored) { e.ep.nread = nb / 2; e.ep.c = *mirror_c; }
+                // gamma^-b: challenge-only, computed during the walk like the host form's (defer_gp_unscale)
+                const int nw = mirrored ? nb / 2 : nb;
+                e.winv.assign(nw, e2_one());
+                if (nw > 1) {
+                    if (pw.v[1].c0 == 0 && pw.v[1].c1 == 0) throw Error("grand product: zero batching weight");
+                    const E2 ginv = e2_inv(pw.v[1]);
+                    E2 w = ginv;
+                    for (int b = 1; b < nw; b++) { e.winv[b] = w; w = e2_mul(w, ginv); }
+                }
+                if (n == nv - 1) {   // the final claims, read by the caller after the replay
+                    const size_t cs = e.ep.claims_slot = slot(nb);
+                    e.ep.has_claims = 1;
+                    push_op([this, claims, nb, cs] { for (int b = 0; b < nb; b++) (*claims)[b] = h_res()[cs + b]; });
+                }
+                prev_ep = (int)gp_eps.size();
+                gp_eps.push_back(std::move(e));
+                ndev++;
+                if (mirrored) ndev_mirrored++;
+                else if (st_slot.back().tail_ntab) ndev_slot++;
+            } else layer_down(evals, mu);
         }
+        // which sum-check layers' claims the device forms: the mirrored top layer, slot-form layers below it, plain ones (a token of
+        // its own: the lines of HG_DEBUG=plan are all numbers and are read as such)
+        if (hg_debug("gpclaims"))
+            fprintf(stderr, "[hg plan] gpclaims nb=%d layers=%d device=%d mirrored=%d slot=%d plain=%d\n", nb, nv - 1, ndev, ndev_mirrored, ndev_slot,
+                    ndev - ndev_mirrored - ndev_slot);
         return out;
     }
 

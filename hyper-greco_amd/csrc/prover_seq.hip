@@ -1281,7 +1281,7 @@ struct SeqProver {
             const E2 gamma = squeeze();  // prover.rs:238
             dev::Powers pw;
             memset(&pw, 0, sizeof(pw));
-            if (nb > dev::PW_MAX) throw Error("grand product: too many batched tables");
+            if (nb > dev::PW_ENTRY_MAX) throw Error("grand product: too many batched tables");
             E2 g = e2_one(), claim = e2_zero();
             for (int b = 0; b < nb; b++) { pw.v[b] = g; claim = e2_add(claim, e2_mul(cl[b], g)); g = e2_mul(g, gamma); }  // prover.rs:281-286
             const size_t evals = slot(2 * (size_t)nb);
@@ -1325,7 +1325,7 @@ struct SeqProver {
         {   // collation sum-check (lasso.rs:271-279), result dropped (:97)
             dev::Powers pw;
             memset(&pw, 0, sizeof(pw));
-            if (A > dev::PW_MAX) throw Error("lasso: too many memories");
+            if (A > dev::PW_ENTRY_MAX) throw Error("lasso: too many memories");
             u64 c = 1;
             for (int i = 0; i < A; i++) { pw.v[i] = e2(c, 0); c = gl_mul(c, M); }
             E2 claim = claimed;

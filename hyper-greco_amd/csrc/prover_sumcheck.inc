@@ -25,6 +25,10 @@
     double pending_fused_model_extra = 0, hash_model_extra = 0;   // ... and what only the reference's traffic model counts of it (E reads)
     std::vector<double> st_fused_model_extra;
     std::vector<dev::ScatterEnt> scatter;  // locally produced scalars -> global result slots (batch-subset grand products)
+    // claim epilogues of the queued grand-product jobs (grand_product, prover_lasso.inc): challenge-only constants, filled during the
+    // walk and uploaded with the job descriptors, which a cached launch graph does not repeat
+    struct GpEpReq { int job = -1; dev::GpClaimEp ep; std::vector<E2> winv, gnext; };
+    std::vector<GpEpReq> gp_eps;
 
     ScHandle sc_stride(int kind, const void* in, bool base, size_t in_stride, int ntab, int nvars, const dev::Powers& pw, E2* final_out,
                        bool enqueue = true, bool p0_only = false, int seq = 0, u64* next_level = nullptr, const dev::GpHashSrc* hash_src = nullptr,
@@ -220,6 +224,28 @@
                 fprintf(stderr, "[hg plan] stride kind=%d base=%d nrounds=%d mode=%d tail=%d hash=%d items=%zu %s=%d..%d\n", L.kind, L.base ? 1 : 0, L.nrounds,
                         L.mode, L.tail ? 1 : 0, L.hash ? 1 : 0, L.items.size(), L.tail ? "rounds" : "h", lo, hi);
             }
+        if (!gp_eps.empty()) {   // the claim epilogues and their weight vectors: one upload each
+            std::vector<E2> wts;
+            std::vector<dev::GpClaimEp> eps;
+            for (const GpEpReq& e : gp_eps) {
+                if (e.job < 0 || e.job >= nj || st_jobs[e.job].kind != dev::SC_GRANDPROD) throw Error("grand product: claim epilogue without its job");
+                wts.insert(wts.end(), e.winv.begin(), e.winv.end());
+                wts.insert(wts.end(), e.gnext.begin(), e.gnext.end());
+            }
+            E2* d_wts = ctx->alloc_n<E2>(wts.size());
+            dev::GpClaimEp* d_eps = ctx->alloc_n<dev::GpClaimEp>(gp_eps.size());
+            size_t o = 0;
+            for (size_t i = 0; i < gp_eps.size(); i++) {
+                dev::GpClaimEp ep = gp_eps[i].ep;
+                ep.winv = d_wts + o; o += gp_eps[i].winv.size();
+                ep.gnext = d_wts + o; o += gp_eps[i].gnext.size();
+                eps.push_back(ep);
+                st_jobs[gp_eps[i].job].ep = d_eps + i;
+            }
+            upload(d_wts, wts.data(), wts.size() * sizeof(E2), "upload claim weights");
+            upload(d_eps, eps.data(), eps.size() * sizeof(dev::GpClaimEp), "upload claim epilogues");
+            gp_eps.clear();
+        }
         dev::StJob* d_jobs = ctx->alloc_n<dev::StJob>(nj);
         upload(d_jobs, st_jobs.data(), (size_t)nj * sizeof(dev::StJob), "upload jobs");
         std::vector<dev::StItem> flat;

@@ -76,6 +76,10 @@ void hg_destroy(hg_ctx* ctx);
  *                 values object the third is captured into a hipGraph and later ones replay it - the launch sequence depends on
  *                 addresses only, because every challenge is known up front; a values object refilled by hg_witness_gen_into
  *                 keeps its graph; up to HG_GRAPH_ENTRIES (8) graphs per context, each with a private workspace)
+ *   "gp_claims_device"  value == 0: the grand products' layer claims (unscaled evaluations, the mu fold, the next layer's claim) are
+ *                 formed by the transcript replay on the host (default 1: by the tail kernel that writes the layer's evaluations;
+ *                 a sharded rank, the sound modes and BN254 always use the host form). Same proof bytes; a change drops the
+ *                 context's cached launch graphs
  *   "verify_batch_group"  the most proofs one device pass of hg_verify_device_batch, hg_verify_device_batch_bn254,
  *                 hg_verify_public_batch, hg_verify_public_bound_batch or hg_verify_public_batch_bn254 holds (and
  *                 hg_instance_digest_group stages), and the most openings one of
@@ -763,7 +767,7 @@ int hg_sumcheck(hg_ctx* ctx, int kind, size_t nv, size_t ntab, const uint64_t* c
                 const uint64_t* pw, size_t npw, const uint64_t* claim2, size_t chain_skip, uint64_t* msgs,
                 uint64_t* point, uint64_t* evals, uint64_t* sums);
 
-/* = prove_grand_product [REF lasso/src/memory_checking/prover.rs:183-266] on nb host tables of len = 2^nv base-field values: product
+/* = prove_grand_product [REF lasso/src/memory_checking/prover.rs:183-266] on nb <= 128 host tables of len = 2^nv base-field values: product
  *   tree on the MSB split, root products, per layer the batched degree-3 sum-check, 2 nb evaluations and the mu fold. The transcript
  *   starts after `chain_skip` E challenges. claims2: nb final claims (E), point2: nv coordinates (E). (Goldilocks counterpart of
  *   hg_grand_product_bn254)
