@@ -526,21 +526,7 @@ __global__ __launch_bounds__(BN_TPB) void k_bn_reduce(const Fr* __restrict__ par
     }
 }
 
-// all rounds of one sum-check in one launch: workgroup rd sums counts.n[rd] per-workgroup partials of round rd
-struct RoundCounts { int n[32]; };
-__global__ __launch_bounds__(BN_TPB) void k_bn_reduce_rounds(const Fr* __restrict__ partials, RoundCounts counts, int nv, Fr* __restrict__ out) {
-    __shared__ Fr sm[BN_TPB];
-    const int rd = blockIdx.x;
-    const Fr* src = partials + (size_t)rd * BN_PART_STRIDE * nv;
-    for (int v = 0; v < nv; v++) {
-        Fr a = fr_zero();
-        for (int b = threadIdx.x; b < counts.n[rd]; b += BN_TPB) a = fr_add(a, src[(size_t)b * nv + v]);
-        a = block_sum_fr(a, sm);
-        if (threadIdx.x == 0) out[rd * nv + v] = fr_from_mont(a);  // canonical for the host
-    }
-}
-
-// the same for many sum-checks: grid (32, jobs)
+// all rounds of many sum-checks in one launch: grid (32, jobs), workgroup (rd, job) sums n[rd] per-workgroup partials of round rd
 struct RedJobDev { const Fr* part; Fr* out; int n[32]; int nrounds, pad; };
 __global__ __launch_bounds__(BN_TPB) void k_bn_reduce_jobs(const RedJobDev* __restrict__ jobs, int nv) {
     __shared__ Fr sm[BN_TPB];
@@ -922,20 +908,11 @@ void field_op_bn254(hg_ctx* ctx, int op, size_t n, const u64* a, const u64* b, u
 }
 
 // ---- prove_grand_product over Fr [REF lasso/src/memory_checking/prover.rs:183-266, 268-294, 297-355] ----------------------
-// lw (optional, with pw): the left half of every output row times the row's weight pw[b] - what the sum-check layer that reads this
-// level wants as its left tables (k_bn_gp_round_jobs), written here instead of by a second pass over the level (k_bn_weight_rows)
-__global__ void k_bn_prod_level(const Fr* __restrict__ in, size_t in_len, Fr* __restrict__ out, int nb, const Fr* __restrict__ pw = nullptr,
-                                Fr* __restrict__ lw = nullptr) {
-    const size_t h = in_len >> 1, total = h * nb;   // (h is a power of two: shift and mask, not a 64-bit division per thread)
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const size_t b = i >> (__ffsll((long long)h) - 1), j = i & (h - 1);
-    const Fr v = lz_mul(in[b * in_len + j], in[b * in_len + j + h]);  // Layer::bottom / Layer::up: v_l * v_r on the MSB split (loose in, loose out)
-    out[b * h + j] = v;
-    if (lw && j < (h >> 1)) lw[b * (h >> 1) + j] = b == 0 ? v : lz_mul(pw[b], v);
-}
-// the same with the row index on grid.y (uniform per workgroup), so that the weight of row b is a LAUNCH-WIDE constant of the
-// workgroup: lw = pw[b] * v runs through fr_fold_const with the row's precomputed constants fk[b] (k_bn_fold_consts)
+// One level of the product tree: out = v_l * v_r on the MSB split (Layer::bottom / Layer::up; loose in, loose out). lw: the left half
+// of every output row times the row's weight pw[b] - what the sum-check layer that reads this level wants as its left tables
+// (k_bn_gp_round_jobs), written here instead of by a second pass over the level. The row index is on grid.y (uniform per workgroup),
+// so that the weight of row b is a LAUNCH-WIDE constant of the workgroup: lw = pw[b] * v runs through fr_fold_const with the row's
+// precomputed constants fk[b] (k_bn_fold_consts)
 // slot_of (optional): `in` holds slot rows - row b's values at entry j are those of slot row slot_of[b * ng + (j >> seg_shift)]
 __global__ void k_bn_prod_level_rows(const Fr* __restrict__ in, size_t in_len, Fr* __restrict__ out, const FoldK* __restrict__ fk, Fr* __restrict__ lw,
                                      const unsigned char* __restrict__ slot_of = nullptr, int ng = 0, int seg_shift = 0) {
@@ -1904,18 +1881,6 @@ static void lasso_prove_bn254_impl(hg_ctx* ctx, const hg_pk* pk, const u64* in4,
 // The limb split and the counters are integer work on the low limb (fe_to_bits_le truncates to at most 63 bits,
 // lasso.rs:381-414, 654-669): the Goldilocks kernels (lasso_split, lasso_counters) are reused as they are; everything
 // that involves challenges runs over Fr.
-__global__ void k_bn_from_u64(const u64* __restrict__ in, Fr* __restrict__ out, size_t n) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = fr_to_mont(fr_make(in[i], 0, 0, 0));
-}
-// eq table by doubling: after step i the first 2^(i+1) entries hold eq(r_0..r_i, .)
-__global__ void k_bn_eq_step(Fr* __restrict__ eq, size_t cur, Fr r) {
-    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= cur) return;
-    const Fr hi = fr_mul(eq[j], r);
-    eq[j + cur] = hi;
-    eq[j] = fr_sub(eq[j], hi);
-}
 // Integer tables meet field constants through "double Montgomery" constants: for a plain integer x and K2 = K R^2 mod r (the raw
 // limbs of fr_to_mont(K~)), the Montgomery reduction of x * K2 is (x K) R, i.e. x K in Montgomery form - one short multiply-
 // accumulate (wcol_mac_u64) per table entry and one reduction per hash / row instead of a conversion and a full product each.

@@ -97,10 +97,6 @@ static void ntt_dev(hipStream_t st, Fr* a, Fr* tmp, const Fr* W, int log2n, bool
     hipc(hipMemcpyAsync(a, tmp, total * sizeof(Fr), hipMemcpyDeviceToDevice, st), "ntt copy");
 }
 
-__global__ void k_bn_fill(Fr* __restrict__ p, Fr v, size_t n) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
-}
 // the table over m <= 8 variables (at most 256 entries) in one workgroup
 struct EqHead { Fr r[8]; };
 __global__ __launch_bounds__(256) void k_bn_eq_head(Fr* __restrict__ eq, EqHead h, int m) {
@@ -135,12 +131,6 @@ static void build_eq_dev(hipStream_t st, Fr* eq, const Fr* pt_canon, int n, Fr* 
     build_eq_dev(st, lo, pt_canon, 8, nullptr);
     build_eq_dev(st, hi, pt_canon + 8, n - 8, hi + ((size_t)1 << (n - 8)));
     k_bn_eq_outer<<<grid_of((size_t)1 << n), 256, 0, st>>>(eq, lo, hi, (size_t)1 << n);
-}
-__global__ void k_bn_axpy(Fr* __restrict__ dst, const Fr* __restrict__ src, Fr a, size_t n, int first) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const Fr v = fr_mul(a, src[i]);
-    dst[i] = first ? v : fr_add(dst[i], v);
 }
 
 // One round of prove_sum_check for g = sum_i a_i b_i (Libra / zkCNN reductions): tables by pointer (round 0 reads the node
@@ -439,18 +429,6 @@ __global__ void k_bn_fft_part(Fr* __restrict__ T, const Fr* __restrict__ W, int 
     Fr acc = one;
     for (int b = b_lo; b < b_hi; b++) acc = fr_mul_wide(acc, bn_fft_factor(W, N, pt.r[b], y, b, one));
     T[y] = acc;
-}
-__global__ void k_bn_fft_tab(Fr* __restrict__ F, const Fr* __restrict__ W, int L, BnPoint pt, Fr coef, int first, const Fr* __restrict__ T1, int s1,
-                             const Fr* __restrict__ T2, int s2) {
-    const size_t N = (size_t)1 << L;
-    size_t x = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (x >= N) return;
-    const Fr one = fr_one_mont();
-    Fr acc = coef;
-    for (int b = 0; b < s1; b++) acc = fr_mul_wide(acc, bn_fft_factor(W, N, pt.r[b], x, b, one));
-    if (T1) acc = fr_mul_wide(acc, T1[x & (((size_t)1 << (L - s1)) - 1)]);
-    if (T2) acc = fr_mul_wide(acc, T2[x & (((size_t)1 << (L - s2)) - 1)]);
-    F[x] = first ? acc : fr_add(F[x], acc);
 }
 
 // ---- the same bookkeeping kernels over job arrays: one launch for all nodes (grid.y / blockIdx.x = job) ------------------------

@@ -329,7 +329,7 @@ pcs::Commitment* pcs_commit_device(const char* who, hg_ctx* ctx, const pcs::Shap
     const int c_stage = ctx->prof_class("pcs_bn254_stage", false), c_ntt = ctx->prof_class("pcs_bn254_ntt", false), c_leaf = ctx->prof_class("pcs_bn254_leaf", false),
               c_tree = ctx->prof_class("pcs_bn254_tree", false);
     ctx->prof_stream = st;
-    pcs::DrainOne drain{st};   // (drains on an error; after the synchronisation below its own is one more, on an idle stream)
+    Drain drain{st};   // (drains on an error; after the synchronisation below its own is one more, on an idle stream)
     hipc(hipMemsetAsync(d_flag, 0, 16, st), "memset");
     for (size_t t = 0; t < sh.nvars.size(); t++) {
         const size_t len = (size_t)1 << sh.nvars[t];

@@ -483,10 +483,7 @@ std::string verify_proof_device_bn254(hg_ctx* ctx, const hg_pk* pk, const Witnes
     // Rejection is a normal outcome and leaves kernels and staged copies queued (the walk returns from the middle of the proof), and
     // an hg::Error may leave from any upload: drain the stream on EVERY way out before the caller may reuse the staging buffer and
     // the arena or free the witness whose uploads may still be pending (verifier_dev.hip: the same guard).
-    struct Drain {
-        hipStream_t st;
-        ~Drain() { (void)hipStreamSynchronize(st); }
-    } drain{ctx->stream};
+    Drain drain{ctx->stream};
     const Params& p = pk->params;
     BnDevBackend D(ctx, pk, pool);
     D.t_begin = tv0;
@@ -511,11 +508,7 @@ std::string verify_proof_device_bn254(hg_ctx* ctx, const hg_pk* pk, const Witnes
 }
 
 // ---- hg_verify_public_device_bn254, hg_claims_settle_bn254, hg_instance_mle_bn254 ------------------------------------------------
-// every way out of an entry drains the stream before the staging buffer, the arena or the caller's arrays are reused (see above)
-struct BnDrain {
-    hipStream_t st;
-    ~BnDrain() { (void)hipStreamSynchronize(st); }
-};
+// (every way out of an entry drains the stream before the staging buffer, the arena or the caller's arrays are reused: see above)
 static const int64_t* bn_upload_coeffs(hg_ctx* ctx, DevPool& pool, const std::vector<int64_t>& src) {
     int64_t* d = pool.get<int64_t>(src.size());
     hipc(hipMemcpyAsync(d, src.data(), src.size() * 8, hipMemcpyHostToDevice, ctx->stream), "verifier: upload the instance");
@@ -534,7 +527,7 @@ std::string verify_public_device_bn254(hg_ctx* ctx, const hg_pk* pk, const Insta
     hipc(hipSetDevice(ctx->device), "hipSetDevice");
     ctx->arena_reset();
     DevPool pool(ctx);
-    BnDrain drain{ctx->stream};
+    Drain drain{ctx->stream};
     const Params& p = pk->params;
     BnDevBackend D(ctx, pk, pool);
     D.t_begin = tv0;
@@ -557,7 +550,7 @@ std::string claims_settle_device_bn254(hg_ctx* ctx, const Params& p, const Witne
     hipc(hipSetDevice(ctx->device), "hipSetDevice");
     ctx->arena_reset();
     DevPool pool(ctx);
-    BnDrain drain{ctx->stream};
+    Drain drain{ctx->stream};
     BnDevBackend D(ctx, nullptr, pool);
     D.own_chain = true;
     std::map<size_t, const u64*> d_tab;   // one upload per table, however many claims it carries
@@ -589,7 +582,7 @@ void instance_mle_device_bn254(hg_ctx* ctx, const Params& p, const Instance& ins
     hipc(hipSetDevice(ctx->device), "hipSetDevice");
     ctx->arena_reset();
     DevPool pool(ctx);
-    BnDrain drain{ctx->stream};
+    Drain drain{ctx->stream};
     BnDevBackend D(ctx, nullptr, pool);
     D.own_chain = true;
     D.cp = &p;

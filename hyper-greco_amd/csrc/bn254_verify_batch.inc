@@ -1,7 +1,9 @@
 // hg_verify_device_batch_bn254: BfvEncrypt::verify::<Fr, Fr> of a run of proofs under one key in one device pass per group [REF
 // bfv-gkr/src/sk_encryption_circuit.rs:462-517, 614-626] - included by bn254.hip behind bn254_verify.inc, inside namespace hg::bn,
 // so that it launches that translation unit's BN254 job kernels. Every proof gets exactly the decision of verify_proof_device_bn254.
-// The BN254 counterpart of verifier_batch.hip, in mode 0 only (every evaluation point is a run of the fixed Fr chain):
+// The BN254 counterpart of verifier_batch.hip, in mode 0 only (every evaluation point is a run of the fixed Fr chain). The host side
+// of the three steps - recorder, merge, input units, the loop over the groups - is verifier_merge.hpp, shared with Goldilocks; this
+// file keeps the group-size rule, the Fr chain in Montgomery form, the lowering of a merged group and the input kernels:
 //   1. The walks (verifier.cpp: verify_walk_bn254) run on the host threads, one proof each, against a backend that only RECORDS the
 //      calls BnDevBackend makes (no device call, no arena or DevPool allocation: the bump allocator is not thread-safe).
 //   2. The jobs of a group are merged. Chain offsets are absolute already, so every eq table, constant-gate sum, Libra phase-1
@@ -14,7 +16,7 @@
 // the Goldilocks batch (verifier_batch.hpp), so group g+1's copies and walks run while group g's kernels do.
 // hg_verify_public_batch_bn254 is the same pass from the ciphertext (the batch form of verify_public_device_bn254, bn254_verify.inc):
 // the walks run with public_only, the recording backend in its compact form, each proof's instance is staged as it is (2 k n signed
-// words), k_bn_vin_compact_dots evaluates ais and ct0is from them, and the claims on the secret inputs come back from each proof's
+// words), k_bn_vin_dots<true> evaluates ais and ct0is from them, and the claims on the secret inputs come back from each proof's
 // pending state.
 
 // ---- the MLE evaluations of the public inputs -------------------------------------------------------------------------------------
@@ -29,10 +31,7 @@
 // 2^12 r^2. The reduction gives value R^-1 = sum z b~ R^-1 = sum z b (b~ = b R: the eq table is in Montgomery form): the PLAIN residue
 // of the thread's sum, so the partials and the slots are plain residues, canonical for the host without a conversion.
 constexpr int VBN_TPB = 256, VBN_ITEMS = 8, VBN_TILE = VBN_TPB * VBN_ITEMS, VBN_WAVES = VBN_TPB / 64;
-// (log2_n, lo: k_bn_vin_compact_dots only - n is then the count of non-padding words, blocks of 2^log2_n, word lo + r of a block's 2^(log2_n+1) eq entries)
-struct BnVinUnit { const Fr* eq; size_t n; int first, P, nblk; u32 log2_n; size_t part0; u32 lo, pad; };   // member p's partial of wave w of workgroup b: part0 + (p * nblk + b) * VBN_WAVES + w
-struct BnVinMember { const u64* a; int unit, slot; };
-struct BnVinBlock { int unit, blk; };
+typedef VinUnitT<Fr> BnVinUnit;   // member p's partial of wave w of workgroup b: part0 + (p * nblk + b) * VBN_WAVES + w
 
 __device__ __forceinline__ Fr vbn_shfl_xor(const Fr& v, int o) {
     Fr t;
@@ -40,16 +39,35 @@ __device__ __forceinline__ Fr vbn_shfl_xor(const Fr& v, int o) {
     for (int i = 0; i < 4; i++) t.l[i] = __shfl_xor(v.l[i], o);
     return t;
 }
-__global__ __launch_bounds__(VBN_TPB) void k_bn_vin_dots(const BnVinUnit* __restrict__ units, const BnVinMember* __restrict__ members,
-                                                         const BnVinBlock* __restrict__ blocks, Fr* __restrict__ partials) {
-    const BnVinBlock B = blocks[blockIdx.x];
+// COMPACT: k_bn_vin_dots over the compact signed coefficients of public instances (hg_verify_public_batch_bn254; k_bn_vdot_compact_jobs,
+// bn254_verify.inc, is the single-proof form and k_vin_dots<true>, verifier_batch.hip, the Goldilocks one). A unit is one eq table
+// (Fr, Montgomery form) and the P members' coefficient blocks evaluated at its point (mode 0: the group's tables of one public input,
+// so P is the group size). A workgroup owns VBN_TILE consecutive WORD indices t of the non-padding range only (U.n = blocks *
+// 2^log2_n of them): with b = t >> log2_n and r = t & (n-1), eq entry b * 2n + lo + r meets coefficient n-1-r of block b, exactly as
+// k_bn_vdot_compact_jobs indexes (ais[i]: one block, lo = 0; ct0is: k blocks, lo = n-1). Both addresses of an item come from one
+// (t, r) pair (vin_at). The eq tile is loaded once into registers; per member the thread reads its VBN_ITEMS int64 words (descending
+// over the same cache lines as the eq loads ascend) and accumulates |z| times eq, or times r - eq for a negative z; a word beyond U.n
+// counts as zero. One lz_reduce / lz_canon per thread and member, one partial per (member, wave): no barrier, and the next member's
+// loads are issued ahead of this member's arithmetic, as in the plain form. k_bn_vin_reduce adds the partials: with b~ = b R the
+// reduction yields plain residues, so the slots are canonical for the host.
+// Bound: |z| <= (q_i-1)/2 < 2^61 (hg_instance_from_ciphertext checks the range), each product is below 2^61 r and a thread's
+// VBN_ITEMS = 8 of them below 2^64 r - far inside lz_reduce's 2^12 r^2.
+// HBM traffic by design: 8 B per coefficient plus 32 / P B of eq, nothing for padding words - the padding half of an eq table is
+// never read. Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): 248 VGPRs, no scratch, 2 waves per SIMD (the plain
+// form: 230 VGPRs).
+template <bool COMPACT>
+__global__ __launch_bounds__(VBN_TPB) void k_bn_vin_dots(const BnVinUnit* __restrict__ units, const VinMember* __restrict__ members,
+                                                         const VinBlock* __restrict__ blocks, Fr* __restrict__ partials) {
+    const VinBlock B = blocks[blockIdx.x];
     const BnVinUnit U = units[B.unit];
-    const size_t base = (size_t)B.blk * VBN_TILE + threadIdx.x;
+    const size_t base = (size_t)B.blk * VBN_TILE + threadIdx.x, nm1 = ((size_t)1 << U.log2_n) - 1;
     Fr eq[VBN_ITEMS];
 #pragma unroll
     for (int j = 0; j < VBN_ITEMS; j++) {
-        const size_t i = base + (size_t)j * VBN_TPB;
-        eq[j] = i < U.n ? U.eq[i] : fr_zero();
+        const size_t t = base + (size_t)j * VBN_TPB;
+        size_t ie, iw;
+        vin_at<COMPACT>(t, nm1, U.lo, ie, iw);
+        eq[j] = t < U.n ? U.eq[ie] : fr_zero();
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     u64 v[VBN_ITEMS];
@@ -57,8 +75,10 @@ __global__ __launch_bounds__(VBN_TPB) void k_bn_vin_dots(const BnVinUnit* __rest
         const u64* __restrict__ a = members[U.first + p].a;
 #pragma unroll
         for (int j = 0; j < VBN_ITEMS; j++) {
-            const size_t i = base + (size_t)j * VBN_TPB;
-            out[j] = i < U.n ? a[i] : 0;
+            const size_t t = base + (size_t)j * VBN_TPB;
+            size_t ie, iw;
+            vin_at<COMPACT>(t, nm1, U.lo, ie, iw);
+            out[j] = t < U.n ? a[iw] : 0;
         }
     };
     load(0, v);
@@ -68,61 +88,12 @@ __global__ __launch_bounds__(VBN_TPB) void k_bn_vin_dots(const BnVinUnit* __rest
         WCol w = wcol_zero();
 #pragma unroll
         for (int j = 0; j < VBN_ITEMS; j++) {
+            // the word's sign and magnitude: a laid-out entry v >= 2^63 is -(GL_P - v), a compact word is the int64 itself
             const bool neg = v[j] >= (1ULL << 63);
-            wcol_mac_u64(w, neg ? GL_P - v[j] : v[j], vd_negate_if(eq[j], neg));
-        }
-        Fr s = lz_canon(lz_reduce(w));
-        for (int o = 32; o > 0; o >>= 1) s = fr_add(s, vbn_shfl_xor(s, o));
-        if (lane == 0) partials[U.part0 + ((size_t)p * U.nblk + B.blk) * VBN_WAVES + wave] = s;   // (one partial per wave: no barrier)
-#pragma unroll
-        for (int j = 0; j < VBN_ITEMS; j++) v[j] = nx[j];
-    }
-}
-// k_bn_vin_dots over the compact signed coefficients of public instances (hg_verify_public_batch_bn254; k_bn_vdot_compact_jobs,
-// bn254_verify.inc, is the single-proof form and k_vin_compact_dots, verifier_batch.hip, the Goldilocks one). A unit is one eq table
-// (Fr, Montgomery form) and the P members' coefficient blocks evaluated at its point (mode 0: the group's tables of one public input,
-// so P is the group size). A workgroup owns VBN_TILE consecutive WORD indices t of the non-padding range only (U.n = blocks *
-// 2^log2_n of them): with b = t >> log2_n and r = t & (n-1), eq entry b * 2n + lo + r meets coefficient n-1-r of block b, exactly as
-// k_bn_vdot_compact_jobs indexes (ais[i]: one block, lo = 0; ct0is: k blocks, lo = n-1). Both addresses of an item come from one
-// (t, r) pair. The eq tile is loaded once into registers; per member the thread reads its VBN_ITEMS int64 words (descending over the
-// same cache lines as the eq loads ascend) and accumulates |z| times eq, or times r - eq for a negative z; a word beyond U.n counts
-// as zero. One lz_reduce / lz_canon per thread and member, one partial per (member, wave): no barrier, and the next member's loads
-// are issued ahead of this member's arithmetic, as in k_bn_vin_dots. k_bn_vin_reduce adds the partials: with b~ = b R the reduction
-// yields plain residues, so the slots are canonical for the host.
-// Bound: |z| <= (q_i-1)/2 < 2^61 (hg_instance_from_ciphertext checks the range), each product is below 2^61 r and a thread's
-// VBN_ITEMS = 8 of them below 2^64 r - far inside lz_reduce's 2^12 r^2.
-// HBM traffic by design: 8 B per coefficient plus 32 / P B of eq, nothing for padding words - the padding half of an eq table is
-// never read. Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): 248 VGPRs, no scratch, 2 waves per SIMD.
-__global__ __launch_bounds__(VBN_TPB) void k_bn_vin_compact_dots(const BnVinUnit* __restrict__ units, const BnVinMember* __restrict__ members,
-                                                                 const BnVinBlock* __restrict__ blocks, Fr* __restrict__ partials) {
-    const BnVinBlock B = blocks[blockIdx.x];
-    const BnVinUnit U = units[B.unit];
-    const size_t base = (size_t)B.blk * VBN_TILE + threadIdx.x, nm1 = ((size_t)1 << U.log2_n) - 1;
-    Fr eq[VBN_ITEMS];
-#pragma unroll
-    for (int j = 0; j < VBN_ITEMS; j++) {
-        const size_t t = base + (size_t)j * VBN_TPB, r = t & nm1;
-        eq[j] = t < U.n ? U.eq[2 * (t - r) + U.lo + r] : fr_zero();
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int64_t v[VBN_ITEMS];
-    auto load = [&](int p, int64_t* out) {
-        const int64_t* __restrict__ c = reinterpret_cast<const int64_t*>(members[U.first + p].a);
-#pragma unroll
-        for (int j = 0; j < VBN_ITEMS; j++) {
-            const size_t t = base + (size_t)j * VBN_TPB, r = t & nm1;
-            out[j] = t < U.n ? c[(t - r) + (nm1 - r)] : 0;
-        }
-    };
-    load(0, v);
-    for (int p = 0; p < U.P; p++) {
-        int64_t nx[VBN_ITEMS];
-        if (p + 1 < U.P) load(p + 1, nx);   // (the next member's loads are in flight under this member's arithmetic)
-        WCol w = wcol_zero();
-#pragma unroll
-        for (int j = 0; j < VBN_ITEMS; j++) {
-            const bool neg = v[j] < 0;
-            wcol_mac_u64(w, neg ? (u64)0 - (u64)v[j] : (u64)v[j], vd_negate_if(eq[j], neg));
+            u64 mag;
+            if constexpr (COMPACT) mag = neg ? (u64)0 - v[j] : v[j];
+            else mag = neg ? GL_P - v[j] : v[j];
+            wcol_mac_u64(w, mag, vd_negate_if(eq[j], neg));
         }
         Fr s = lz_canon(lz_reduce(w));
         for (int o = 32; o > 0; o >>= 1) s = fr_add(s, vbn_shfl_xor(s, o));
@@ -132,9 +103,9 @@ __global__ __launch_bounds__(VBN_TPB) void k_bn_vin_compact_dots(const BnVinUnit
     }
 }
 // one wave per member: its unit's nblk * VBN_WAVES partials into its slot (canonical)
-__global__ __launch_bounds__(64) void k_bn_vin_reduce(const BnVinUnit* __restrict__ units, const BnVinMember* __restrict__ members,
+__global__ __launch_bounds__(64) void k_bn_vin_reduce(const BnVinUnit* __restrict__ units, const VinMember* __restrict__ members,
                                                       const Fr* __restrict__ partials, Fr* __restrict__ res) {
-    const BnVinMember M = members[blockIdx.x];
+    const VinMember M = members[blockIdx.x];
     const BnVinUnit U = units[M.unit];
     const size_t np = (size_t)U.nblk * VBN_WAVES;
     const Fr* part = partials + U.part0 + (size_t)(blockIdx.x - U.first) * np;
@@ -145,155 +116,6 @@ __global__ __launch_bounds__(64) void k_bn_vin_reduce(const BnVinUnit* __restric
 }
 
 namespace {
-
-// ---- the recording backend ----------------------------------------------------------------------------------------------------------
-// The same calls as BnDevBackend, kept as symbolic jobs: tables are indices into the proof's own lists, tickets are local result
-// slots. value() reads the slots the batch copied back (canonical) in Montgomery form, as BnDevBackend::value does.
-struct BnRecBackend : VerifyBackendT<Fr> {
-    const hg_pk* pk;
-    BatchInputs L;
-    struct Eq { int nvars; dev::ClaimSet cs; };
-    struct Const { int node, eqc, slot; };
-    struct Lin { int node, in, eqc; };
-    struct Mul { int node, in, eqc, eqx; size_t u_at; };
-    struct Fft { int node; dev::ClaimSet cs; };
-    enum { D_LIN, D_MUL, D_FFT };
-    struct Dot { int kind, tab, eq, slot; };
-    struct In { int k, eq, slot; };   // k < 0: ct0is
-    std::vector<Eq> eqs;
-    std::vector<Const> consts;
-    std::vector<Lin> lins;
-    std::vector<Mul> muls;
-    std::vector<Fft> ffts;
-    std::vector<Dot> dots;
-    std::vector<In> ins;
-    std::vector<Fr> us;            // phase-1 evaluations of the Vanilla nodes with a phase 2 (Montgomery, as the walk has them)
-    size_t chain_need = 0;         // one past the last chain entry a job reads
-    int nslots = 0;
-    std::vector<Fr> res;           // the results (Montgomery), filled after the group's synchronisation
-    int node = -1, eqc = -1, eqx = -1, eqy = -1;
-    size_t u_at = 0;
-    dev::ClaimSet cs;
-
-    // hg_verify_public_batch_bn254 (the counterpart of BnDevBackend::cp): the public tables are compact signed coefficients, mle_input
-    // for inputs 3 .. 3+k-1 and mle_ct0is record compact input jobs, any other input is refused
-    const Params* cp = nullptr;
-
-    BnRecBackend(const hg_pk* k, bool compact = false) : pk(k), L(k->params), cp(compact ? &k->params : nullptr) { memset(&cs, 0, sizeof(cs)); }
-    int slot() { return nslots++; }
-    void reads_chain(const dev::ClaimSet& c, int nvars) {
-        for (int a = 0; a < c.n; a++) chain_need = std::max(chain_need, c.point_off[a] + (size_t)nvars);
-        if (!c.unit_alpha) chain_need = std::max(chain_need, c.alpha_off + (size_t)c.n);
-    }
-    int eq_of(int nvars, const dev::ClaimSet& c) {
-        reads_chain(c, nvars);
-        eqs.push_back(Eq{nvars, c});
-        return (int)eqs.size() - 1;
-    }
-    int eq_single(int nvars, size_t off) {
-        dev::ClaimSet c;
-        memset(&c, 0, sizeof(c));
-        c.n = 1; c.unit_alpha = 1; c.point_off[0] = off;
-        return eq_of(nvars, c);
-    }
-    int dot(int kind, int tab, int eq) { const int t = slot(); dots.push_back(Dot{kind, tab, eq, t}); return t; }
-
-    void begin_node(int id, const ClaimOffs& cl) override {
-        node = id;
-        const HNode& n = pk->circuit.nodes[id];
-        if (cl.point_off.size() > (size_t)dev::MAX_CLAIMS) throw Error("verifier: too many claims on one node");
-        memset(&cs, 0, sizeof(cs));
-        cs.n = (int)cl.point_off.size();
-        cs.unit_alpha = cl.unit ? 1 : 0;
-        cs.alpha_off = cl.alpha_off;
-        for (int a = 0; a < cs.n; a++) cs.point_off[a] = cl.point_off[a];
-        eqc = n.kind == NK_VANILLA ? eq_of(n.log2_out(), cs) : -1;
-        eqx = eqy = -1;
-    }
-    int const_sum() override { const int t = slot(); consts.push_back(Const{node, eqc, t}); return t; }
-    void set_x(size_t x_off) override {
-        const HNode& n = pk->circuit.nodes[node];
-        eqx = eq_single(n.kind == NK_VANILLA ? n.log2_sub_in + n.log2_reps : n.log2_size, x_off);
-    }
-    std::vector<int> lin_terms() override {
-        const HNode& n = pk->circuit.nodes[node];
-        const hg_pk::NodeDev& nd = pk->node_dev[node];
-        std::vector<int> tk(n.arity, -1);
-        for (int i = 0; i < n.arity; i++) {
-            if (!n.left_use[i] || !nd.lin[i].ptr) continue;
-            lins.push_back(Lin{node, i, eqc});
-            tk[i] = dot(D_LIN, (int)lins.size() - 1, eqx);
-        }
-        return tk;
-    }
-    void set_y(size_t y_off, const std::vector<Fr>& u) override {
-        const HNode& n = pk->circuit.nodes[node];
-        if (n.arity > dev::PS_MAX_PAIRS) throw Error("verifier: arity too large");
-        eqy = eq_single(n.log2_sub_in + n.log2_reps, y_off);
-        u_at = us.size();
-        us.insert(us.end(), u.begin(), u.end());
-    }
-    std::vector<int> mul_terms() override {
-        const HNode& n = pk->circuit.nodes[node];
-        const hg_pk::NodeDev& nd = pk->node_dev[node];
-        std::vector<int> tk(n.arity, -1);
-        for (int i = 0; i < n.arity; i++) {
-            if (!n.right_use[i] || !nd.mulR[i].ptr) continue;
-            muls.push_back(Mul{node, i, eqc, eqx, u_at});
-            tk[i] = dot(D_MUL, (int)muls.size() - 1, eqy);
-        }
-        return tk;
-    }
-    int fft_term() override {
-        const int L2 = pk->circuit.nodes[node].log2_size;
-        if (L2 > 28) throw Error("bn254: two-adicity is 28");
-        reads_chain(cs, L2);
-        ffts.push_back(Fft{node, cs});
-        return dot(D_FFT, (int)ffts.size() - 1, eqx);
-    }
-    void end_node() override { node = -1; }
-    int mle_int(int k, size_t point_off, int nvars) {
-        if (nvars < 0 || nvars > 40 || ((size_t)1 << nvars) != L.length(k)) throw Error("verifier: claim point does not fit the input table");
-        const int t = slot();
-        ins.push_back(In{k, eq_single(nvars, point_off), t});
-        return t;
-    }
-    int mle_compact(int k, int nblk, size_t point_off, int nvars) {
-        int lg = 0;
-        while ((1 << lg) < nblk) lg++;
-        if (nvars != cp->L + lg) throw Error("verifier: a point of the wrong length for a public table");   // (the job reads nblk * 2n eq entries)
-        const int t = slot();
-        ins.push_back(In{k, eq_single(nvars, point_off), t});
-        return t;
-    }
-    int mle_input(size_t k, size_t point_off, int nvars) override {
-        if (cp) {
-            if (k < 3 || k >= 3 + (size_t)cp->k) throw Error("verifier: input " + std::to_string(k) + " is not a public table");
-            return mle_compact((int)k, 1, point_off, nvars);
-        }
-        if (k >= 3 + 2 * L.K + 1) throw Error("verifier: no such input table");
-        return mle_int((int)k, point_off, nvars);
-    }
-    int mle_ct0is(size_t point_off, int nvars) override { return cp ? mle_compact(-1, cp->k, point_off, nvars) : mle_int(-1, point_off, nvars); }
-    void finish() override { throw Error("verifier: a recording backend is finished by its batch"); }
-    Fr value(int t) const override { return res[t]; }
-};
-
-struct BnWalked {   // one proof of a group
-    size_t idx;
-    std::unique_ptr<BnRecBackend> rec;
-    VerifyPendingT<Fr> pend;
-    std::string error;                       // an hg::Error of the walk
-    std::vector<int> gslot;                  // local slot -> the group's result slot
-    const u64* d_in = nullptr;               // its inputs in HBM: s, e, k1, ais, r1is, r2is, ct0is; from the ciphertext: a, ct0
-};
-
-// kernels, descriptor copies and input copies may be queued on any way out (a rejection, an hg::Error): drain both streams before
-// the caller may reuse the arena and the staging or free a witness or an instance
-struct BnBatchDrain {
-    hipStream_t a, b;
-    ~BnBatchDrain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); }
-};
 
 // What a batch checks its proofs against: witness handles (hg_verify_device_batch_bn254: ws) or public instances
 // (hg_verify_public_batch_bn254: insts, and open[i] receives the claims an accepted proof i leaves on the secret inputs). `who`
@@ -317,7 +139,7 @@ void verify_batch_run_bn254(hg_ctx* ctx, const hg_pk* pk, const BnBatchSrc& src,
     const double t0 = omp_get_wtime();
     hipc(hipSetDevice(ctx->device), "hipSetDevice");
     VerifyBatchBufs* B = batch_bufs(ctx);
-    BnBatchDrain drain{ctx->stream, B->up};
+    Drain drain{ctx->stream, B->up};
     hipc(hipStreamSynchronize(ctx->stream), (who + ": synchronise").c_str());   // (the arena is reset below)
     const Params& p = pk->params;
     // one proof's inputs in HBM, in the order of verify_proof_device_bn254: s, e, k1, ais (k), r1is (k), r2is, then ct0is; from the
@@ -338,111 +160,38 @@ void verify_batch_run_bn254(hg_ctx* ctx, const hg_pk* pk, const BnBatchSrc& src,
         for (size_t q = have; q < end; q++) chm[q] = fr_to_mont(chm[q]);
     };
 
-    std::vector<std::vector<BnWalked>> groups(ngroups);
+    std::vector<std::vector<Walked<Fr>>> groups(ngroups);
     auto stage = [&](size_t g) {
         if (pub) batch_stage_instances(B, (int)(g & 1), *src.insts, g * G, std::min(n, g * G + G), kn, nthr, src.who);
         else batch_stage_inputs(B, (int)(g & 1), *src.ws, g * G, std::min(n, g * G + G), L, nthr, src.who);
     };
     auto walk = [&](size_t g) {
-        const size_t i0 = g * G, i1 = std::min(n, i0 + G);
-        std::vector<BnWalked>& W = groups[g];
-        W.resize(i1 - i0);
-#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)W.size()))
-        for (long long q = 0; q < (long long)W.size(); q++) {
-            BnWalked& x = W[q];
-            x.idx = i0 + (size_t)q;
-            try {
-                x.rec.reset(new BnRecBackend(pk, pub));
-                x.pend = verify_walk_bn254(*x.rec, p, pk->lasso, pk->circuit, proofs[x.idx], lens[x.idx], pub);
-            } catch (const std::exception& e) { x.error = e.what(); }
-        }
-        for (auto& x : W)
-            if (!x.error.empty()) throw Error(who + ": proof " + std::to_string(x.idx) + ": " + x.error);
+        walk_group(groups[g], g * G, std::min(n, g * G + G), nthr, who, [&](Walked<Fr>& x) {
+            x.rec.reset(new RecBackendT<Fr>(pk, pub, true));
+            x.pend = verify_walk_bn254(*x.rec, p, pk->lasso, pk->circuit, proofs[x.idx], lens[x.idx], pub);
+        });
     };
     // merge group g's jobs and enqueue them; returns the result slots used
     auto launch = [&](size_t g) -> size_t {
         const int s = (int)(g & 1);
-        std::vector<BnWalked>& W = groups[g];
+        std::vector<Walked<Fr>>& W = groups[g];
         hipStream_t st = ctx->stream;
         ctx->arena_reset();
+        // chain offsets are absolute already: every proof reads the fixed chain
+        MergedGroup<Fr> M = merge_group(W, false);
+        for (Fr& u : M.us) u = fr_from_mont(u);   // canonical: k_bn_gather_B_jobs reads them as the prover's result slots
+        const auto& consts = M.consts;
+        const auto& lins = M.lins;
+        const auto& muls = M.muls;
+        const auto& ffts = M.ffts;
+        const auto& dots = M.dots;
+        const std::vector<Fr>& us = M.us;
+        const int nslot = M.nslot;
+        const size_t chain_need = M.chain_need;
+        typedef RecBackendT<Fr> Rec;
         struct EqG { int n; dev::ClaimSet cs; Fr* out; };
         std::vector<EqG> eqs;
-        struct ConstG { int node, eq, slot; };
-        std::vector<ConstG> consts;
-        struct LinG { int node, in, eq; };
-        std::vector<LinG> lins;
-        struct MulG { int node, in, eqc, eqx; size_t u_at; };
-        std::vector<MulG> muls;
-        struct FftG { int node; dev::ClaimSet cs; };
-        std::vector<FftG> ffts;
-        struct DotG { int kind, tab, eq, slot; };
-        std::vector<DotG> dots;
-        struct InM { int eq; const u64* a; int slot; int ct0; };   // (ct0: the public form's ct0is, k blocks at lo = n-1)
-        std::vector<InM> ins;
-        std::vector<Fr> us;   // canonical: k_bn_gather_B_jobs reads them as the prover's result slots
-        std::map<Key, int> eq_ix, const_ix, lin_ix, fft_ix, dot_ix;
-        int nslot = 0;
-        size_t chain_need = 0;
-        for (BnWalked& x : W) {
-            x.d_in = B->d_in[s] + (x.idx - g * G) * words;
-            if (!x.pend.reason.empty()) continue;   // rejected by the walk: its recorded prefix is not launched
-            BnRecBackend& R = *x.rec;
-            chain_need = std::max(chain_need, R.chain_need);
-            x.gslot.assign(R.nslots, -1);
-            auto new_slot = [&] { return nslot++; };
-            std::vector<int> geq(R.eqs.size());
-            for (size_t e = 0; e < R.eqs.size(); e++) {
-                Key k{(u64)R.eqs[e].nvars};
-                key_cs(k, R.eqs[e].cs, 0);
-                auto it = eq_ix.find(k);
-                if (it == eq_ix.end()) {
-                    eqs.push_back(EqG{R.eqs[e].nvars, R.eqs[e].cs, nullptr});
-                    it = eq_ix.emplace(k, (int)eqs.size() - 1).first;
-                }
-                geq[e] = it->second;
-            }
-            for (auto& c : R.consts) {
-                Key k{(u64)c.node, (u64)geq[c.eqc]};
-                auto it = const_ix.find(k);
-                if (it == const_ix.end()) { consts.push_back(ConstG{c.node, geq[c.eqc], new_slot()}); it = const_ix.emplace(k, (int)consts.size() - 1).first; }
-                x.gslot[c.slot] = consts[it->second].slot;
-            }
-            std::vector<int> glin(R.lins.size()), gmul(R.muls.size()), gfft(R.ffts.size());
-            for (size_t i = 0; i < R.lins.size(); i++) {
-                const auto& l = R.lins[i];
-                Key k{(u64)l.node, (u64)l.in, (u64)geq[l.eqc]};
-                auto it = lin_ix.find(k);
-                if (it == lin_ix.end()) { lins.push_back(LinG{l.node, l.in, geq[l.eqc]}); it = lin_ix.emplace(k, (int)lins.size() - 1).first; }
-                glin[i] = it->second;
-            }
-            for (size_t i = 0; i < R.muls.size(); i++) {   // (never shared: they read the proof's phase-1 evaluations)
-                const auto& m = R.muls[i];
-                muls.push_back(MulG{m.node, m.in, geq[m.eqc], geq[m.eqx], us.size() + m.u_at});
-                gmul[i] = (int)muls.size() - 1;
-            }
-            for (const Fr& u : R.us) us.push_back(fr_from_mont(u));
-            for (size_t i = 0; i < R.ffts.size(); i++) {
-                Key k{(u64)R.ffts[i].node};
-                key_cs(k, R.ffts[i].cs, 0);
-                auto it = fft_ix.find(k);
-                if (it == fft_ix.end()) { ffts.push_back(FftG{R.ffts[i].node, R.ffts[i].cs}); it = fft_ix.emplace(k, (int)ffts.size() - 1).first; }
-                gfft[i] = it->second;
-            }
-            for (auto& d : R.dots) {
-                const int tab = d.kind == BnRecBackend::D_LIN ? glin[d.tab] : d.kind == BnRecBackend::D_MUL ? gmul[d.tab] : gfft[d.tab];
-                if (d.kind == BnRecBackend::D_MUL) { dots.push_back(DotG{d.kind, tab, geq[d.eq], new_slot()}); x.gslot[d.slot] = dots.back().slot; continue; }
-                Key k{(u64)d.kind, (u64)tab, (u64)geq[d.eq]};
-                auto it = dot_ix.find(k);
-                if (it == dot_ix.end()) { dots.push_back(DotG{d.kind, tab, geq[d.eq], new_slot()}); it = dot_ix.emplace(k, (int)dots.size() - 1).first; }
-                x.gslot[d.slot] = dots[it->second].slot;
-            }
-            for (auto& in : R.ins) {   // (never shared: they read the proof's own witness or instance)
-                const int sl = new_slot();
-                if (pub) ins.push_back(InM{geq[in.eq], x.d_in + (in.k < 0 ? kn : (size_t)(in.k - 3) * L.PZ), sl, in.k < 0});
-                else ins.push_back(InM{geq[in.eq], x.d_in + L.offset(in.k), sl, 0});
-                x.gslot[in.slot] = sl;
-            }
-        }
+        for (auto& e : M.eqs) eqs.push_back(EqG{e.n, e.cs, nullptr});
         if ((size_t)nslot > res_cap_fr)
             throw Error(who + ": a group needs " + std::to_string(nslot) + " result slots, the context has " + std::to_string(res_cap_fr) +
                         ": lower verify_batch_group");
@@ -490,7 +239,7 @@ void verify_batch_run_bn254(hg_ctx* ctx, const hg_pk* pk, const BnBatchSrc& src,
         }
         std::vector<BnGatherBJob> gbs(muls.size());
         for (size_t i = 0; i < muls.size(); i++) {
-            const MulG& m = muls[i];
+            const auto& m = muls[i];
             const HNode& nd = pk->circuit.nodes[m.node];
             const size_t SR = (size_t)1 << (nd.log2_sub_in + nd.log2_reps);
             BnGatherBJob& bj = gbs[i];
@@ -548,41 +297,19 @@ void verify_batch_run_bn254(hg_ctx* ctx, const hg_pk* pk, const BnBatchSrc& src,
         std::vector<VdotJob> vdots(dots.size());
         std::vector<int> blk_job;
         for (size_t i = 0; i < dots.size(); i++) {
-            const DotG& d = dots[i];
+            const auto& d = dots[i];
             VdotJob& J = vdots[i];
             memset(&J, 0, sizeof(J));
-            J.a = d.kind == BnRecBackend::D_LIN ? lin_T[d.tab] : d.kind == BnRecBackend::D_MUL ? mul_B[d.tab] : fft_F[d.tab];
+            J.a = d.kind == Rec::D_LIN ? lin_T[d.tab] : d.kind == Rec::D_MUL ? mul_B[d.tab] : fft_F[d.tab];
             J.b = eqs[d.eq].out; J.n = (size_t)1 << eqs[d.eq].n; J.out = res + d.slot; J.a_is_int = 0;
             J.blk0 = (int)blk_job.size();
             J.nblk = (int)((J.n + VD_TILE - 1) / VD_TILE);
             blk_job.insert(blk_job.end(), (size_t)J.nblk, (int)i);
         }
-        std::vector<BnVinUnit> units;
-        std::vector<BnVinMember> members;
-        std::vector<BnVinBlock> blocks;
-        {
-            // (an ais table and ct0is never share a unit, even at one point: their words sit at other places of the eq table)
-            std::vector<std::vector<const InM*>> by_eq(2 * eqs.size());
-            for (auto& m : ins) by_eq[2 * (size_t)m.eq + m.ct0].push_back(&m);
-            size_t part = 0;
-            for (size_t e2x = 0; e2x < by_eq.size(); e2x++) {
-                if (by_eq[e2x].empty()) continue;
-                const size_t e = e2x / 2;
-                BnVinUnit U;
-                memset(&U, 0, sizeof(U));
-                U.eq = eqs[e].out; U.n = (size_t)1 << eqs[e].n; U.first = (int)members.size(); U.P = (int)by_eq[e2x].size();
-                if (pub) {   // the non-padding words only: n of an ais table, k n of ct0is (the walk checked the eq table's size)
-                    U.n = e2x & 1 ? kn : L.PZ; U.log2_n = (u32)p.n_log2; U.lo = e2x & 1 ? (u32)(L.PZ - 1) : 0;
-                }
-                U.nblk = (int)((U.n + VBN_TILE - 1) / VBN_TILE); U.part0 = part;
-                part += (size_t)U.P * U.nblk * VBN_WAVES;
-                for (const InM* m : by_eq[e2x]) members.push_back(BnVinMember{m->a, (int)units.size(), m->slot});
-                for (int b = 0; b < U.nblk; b++) blocks.push_back(BnVinBlock{(int)units.size(), b});
-                units.push_back(U);
-            }
-        }
-        size_t vin_parts = 0, vin_bytes = 0;   // (vin_bytes: what k_bn_vin_dots / k_bn_vin_compact_dots reads, eq tables and input tables)
-        for (auto& U : units) { vin_parts += (size_t)U.P * U.nblk * VBN_WAVES; vin_bytes += U.n * (sizeof(Fr) + (size_t)U.P * sizeof(u64)); }
+        const VinPlan<Fr> V = vin_units(M, [&](size_t e) { return eqs[e].out; }, B->d_in[s], words, p, pub, VBN_TILE, VBN_WAVES);
+        const auto& units = V.units;
+        const auto& members = V.members;
+        const auto& blocks = V.blocks;
         // the chain, the phase-1 evaluations and every descriptor: one page-locked staging, one copy ahead of the launches
         size_t desc_bytes = 0;
         auto place = [&](size_t bytes) { const size_t o = desc_bytes; desc_bytes += (bytes + 255) & ~(size_t)255; return o; };
@@ -591,8 +318,8 @@ void verify_batch_run_bn254(hg_ctx* ctx, const hg_pk* pk, const BnBatchSrc& src,
                      o_gb = place(gbs.size() * sizeof(BnGatherBJob)), o_part = place(fft_parts.size() * sizeof(FftPartJob)),
                      o_claim = place(fft_claims.size() * sizeof(FftTabClaim)), o_tab = place(fft_tabs.size() * sizeof(FftTabJob)),
                      o_dot = place(vdots.size() * sizeof(VdotJob)), o_bj = place(blk_job.size() * sizeof(int)),
-                     o_unit = place(units.size() * sizeof(BnVinUnit)), o_mem = place(members.size() * sizeof(BnVinMember)),
-                     o_blk = place(blocks.size() * sizeof(BnVinBlock));
+                     o_unit = place(units.size() * sizeof(BnVinUnit)), o_mem = place(members.size() * sizeof(VinMember)),
+                     o_blk = place(blocks.size() * sizeof(VinBlock));
         char* d_desc = static_cast<char*>(ctx->alloc(std::max<size_t>(desc_bytes, 1)));
         char* h = batch_desc_host(B, std::max<size_t>(desc_bytes, 1));
         const Fr* d_chal = reinterpret_cast<const Fr*>(d_desc + o_chain);
@@ -615,7 +342,7 @@ void verify_batch_run_bn254(hg_ctx* ctx, const hg_pk* pk, const BnBatchSrc& src,
         });
         if (!consts.empty()) {
             Fr* d_cpart = ctx->alloc_n<Fr>(1024);   // one after the other on the stream: one partials buffer serves them all
-            for (const ConstG& c : consts) {
+            for (const auto& c : consts) {
                 const HNode& nd = pk->circuit.nodes[c.node];
                 const hg_pk::NodeDev& dv = pk->node_dev[c.node];
                 const size_t total = dv.nconst << nd.log2_reps;
@@ -648,53 +375,30 @@ void verify_batch_run_bn254(hg_ctx* ctx, const hg_pk* pk, const BnBatchSrc& src,
         }
         if (!units.empty()) {
             hipc(hipStreamWaitEvent(st, B->ev[s], 0), (who + ": wait for the inputs").c_str());
-            Fr* part = ctx->alloc_n<Fr>(vin_parts);
+            Fr* part = ctx->alloc_n<Fr>(V.parts);
             const auto* d_units = reinterpret_cast<const BnVinUnit*>(d_desc + o_unit);
-            const auto* d_mem = reinterpret_cast<const BnVinMember*>(d_desc + o_mem);
-            const auto* d_blk = reinterpret_cast<const BnVinBlock*>(d_desc + o_blk);
-            if (pub) k_bn_vin_compact_dots<<<(unsigned)blocks.size(), VBN_TPB, 0, st>>>(d_units, d_mem, d_blk, part);
-            else k_bn_vin_dots<<<(unsigned)blocks.size(), VBN_TPB, 0, st>>>(d_units, d_mem, d_blk, part);
+            const auto* d_mem = reinterpret_cast<const VinMember*>(d_desc + o_mem);
+            const auto* d_blk = reinterpret_cast<const VinBlock*>(d_desc + o_blk);
+            if (pub) k_bn_vin_dots<true><<<(unsigned)blocks.size(), VBN_TPB, 0, st>>>(d_units, d_mem, d_blk, part);
+            else k_bn_vin_dots<false><<<(unsigned)blocks.size(), VBN_TPB, 0, st>>>(d_units, d_mem, d_blk, part);
             k_bn_vin_reduce<<<(unsigned)members.size(), 64, 0, st>>>(d_units, d_mem, part, res);
         }
         if (ctx->d_res != ctx->h_res && nslot)
             hipc(hipMemcpyAsync(ctx->h_res, ctx->d_res, (size_t)nslot * sizeof(Fr), hipMemcpyDeviceToHost, st), (who + ": copy results").c_str());
         if (times)
             fprintf(stderr, "[hg] verify_batch_bn254: group %zu (%zu proofs): %zu eq tables, %zu constant sums, %zu + %zu gathers, %zu DFT rows, %zu dots, %zu input evaluations in %zu units (%.1f MB); %d slots\n",
-                    g, W.size(), eqs.size(), consts.size(), lins.size(), muls.size(), ffts.size(), dots.size(), members.size(), units.size(), vin_bytes / 1e6, nslot);
+                    g, W.size(), eqs.size(), consts.size(), lins.size(), muls.size(), ffts.size(), dots.size(), members.size(), units.size(), V.bytes / 1e6, nslot);
         return (size_t)nslot;
     };
     auto complete = [&](size_t g) {
-        std::vector<BnWalked>& W = groups[g];
         const Fr* h_res = reinterpret_cast<const Fr*>(ctx->h_res);
-#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)W.size()))
-        for (long long q = 0; q < (long long)W.size(); q++) {
-            BnWalked& x = W[q];
-            if (x.pend.reason.empty()) {
-                x.rec->res.resize(x.gslot.size());
-                for (size_t t = 0; t < x.gslot.size(); t++) x.rec->res[t] = fr_to_mont(h_res[x.gslot[t]]);
-            }
+        complete_group(groups[g], nthr, [&](int slot) { return fr_to_mont(h_res[slot]); }, [&](Walked<Fr>& x) {
             why[x.idx] = verify_complete_bn254(x.pend);
             if (pub && why[x.idx].empty())
                 for (const auto& cl : x.pend.open) (*src.open)[x.idx].push_back(open_claim_bn254(cl));
-        }
-        W.clear();
+        });
     };
-
-    stage(0);
-    walk(0);
-    double t_walk = omp_get_wtime() - t0, t_sync = 0;
-    for (size_t g = 0; g < ngroups; g++) {
-        launch(g);
-        if (g + 1 < ngroups) { const double tw = omp_get_wtime(); stage(g + 1); walk(g + 1); t_walk += omp_get_wtime() - tw; }
-        const double ts = omp_get_wtime();
-        hipc(hipStreamSynchronize(ctx->stream), (who + ": synchronise").c_str());
-        hipc(hipGetLastError(), (who + ": kernels").c_str());
-        t_sync += omp_get_wtime() - ts;
-        complete(g);
-    }
-    if (times)
-        fprintf(stderr, "[hg] verify_batch_bn254: %zu proofs in %zu groups of up to %zu: %.2f ms in all (staging and walks %.2f, waiting for the device %.2f)\n", n,
-                ngroups, G, (omp_get_wtime() - t0) * 1e3, t_walk * 1e3, t_sync * 1e3);
+    batch_groups(ctx->stream, who, "verify_batch_bn254", times, t0, n, ngroups, G, stage, walk, launch, complete);
 }
 
 }  // namespace
@@ -709,7 +413,7 @@ void verify_public_batch_device_bn254(hg_ctx* ctx, const hg_pk* pk, const std::v
     verify_batch_run_bn254(ctx, pk, BnBatchSrc{"hg_verify_public_batch_bn254", nullptr, &insts, &open}, proofs, lens, why);
 }
 
-// one eq table over the caller's point, then k_bn_vin_compact_dots as ONE unit whose members are the instances' tables
+// one eq table over the caller's point, then k_bn_vin_dots<true> as ONE unit whose members are the instances' tables
 void instance_mle_batch_device_bn254(hg_ctx* ctx, const Params& p, const std::vector<const Instance*>& insts, int which, int index, const u64* point4,
                                      size_t nvars, u64* out4) {
     const size_t np = insts.size();
@@ -717,7 +421,7 @@ void instance_mle_batch_device_bn254(hg_ctx* ctx, const Params& p, const std::ve
     const char* who = "hg_instance_mle_batch_bn254";
     hipc(hipSetDevice(ctx->device), "hipSetDevice");
     VerifyBatchBufs* B = batch_bufs(ctx);
-    BnBatchDrain drain{ctx->stream, B->up};
+    Drain drain{ctx->stream, B->up};
     hipc(hipStreamSynchronize(ctx->stream), "hg_instance_mle_batch_bn254: synchronise");   // (the arena is reset below)
     ctx->arena_reset();
     hipStream_t st = ctx->stream;
@@ -732,26 +436,25 @@ void instance_mle_batch_device_bn254(hg_ctx* ctx, const Params& p, const std::ve
     memset(&P, 0, sizeof(P));
     P.ab = ab; P.n = nv; P.unit = 1;
     const VeqFill F{eq, ab, nv, 1};
-    BnVinUnit U;
-    memset(&U, 0, sizeof(U));
-    U.eq = eq; U.n = which ? kn : n; U.P = (int)np; U.nblk = (int)((U.n + VBN_TILE - 1) / VBN_TILE);
-    U.log2_n = (u32)p.n_log2; U.lo = which ? (u32)(n - 1) : 0;
-    std::vector<BnVinMember> members(np);
-    for (size_t i = 0; i < np; i++) members[i] = BnVinMember{B->d_in[0] + i * 2 * kn + (which ? kn : (size_t)index * n), 0, (int)i};
-    std::vector<BnVinBlock> blocks((size_t)U.nblk);
-    for (int b = 0; b < U.nblk; b++) blocks[b] = BnVinBlock{0, b};
+    std::vector<std::pair<const u64*, int>> tabs(np);
+    for (size_t i = 0; i < np; i++) tabs[i] = {B->d_in[0] + i * 2 * kn + (which ? kn : (size_t)index * n), (int)i};
+    VinPlan<Fr> V;
+    V.add(eq, which ? kn : n, (u32)p.n_log2, which ? (u32)(n - 1) : 0, tabs, VBN_TILE, VBN_WAVES);
+    const BnVinUnit& U = V.units[0];
+    const auto& members = V.members;
+    const auto& blocks = V.blocks;
     size_t desc_bytes = 0;
     auto place = [&](size_t bytes) { const size_t o = desc_bytes; desc_bytes += (bytes + 255) & ~(size_t)255; return o; };
     const size_t o_chain = place(std::max<size_t>(nvars, 1) * sizeof(Fr)), o_prep = place(sizeof(P)), o_fill = place(sizeof(F)), o_unit = place(sizeof(U)),
-                 o_mem = place(np * sizeof(BnVinMember)), o_blk = place(blocks.size() * sizeof(BnVinBlock));
+                 o_mem = place(np * sizeof(VinMember)), o_blk = place(blocks.size() * sizeof(VinBlock));
     char* d_desc = static_cast<char*>(ctx->alloc(desc_bytes));
     char* h = batch_desc_host(B, desc_bytes);
     if (nvars) memcpy(h + o_chain, chm.data(), nvars * sizeof(Fr));
     memcpy(h + o_prep, &P, sizeof(P));
     memcpy(h + o_fill, &F, sizeof(F));
     memcpy(h + o_unit, &U, sizeof(U));
-    memcpy(h + o_mem, members.data(), np * sizeof(BnVinMember));
-    memcpy(h + o_blk, blocks.data(), blocks.size() * sizeof(BnVinBlock));
+    memcpy(h + o_mem, members.data(), np * sizeof(VinMember));
+    memcpy(h + o_blk, blocks.data(), blocks.size() * sizeof(VinBlock));
     hipc(hipMemcpyAsync(d_desc, h, desc_bytes, hipMemcpyHostToDevice, st), "hg_instance_mle_batch_bn254: upload descriptors");
     const size_t high = (size_t)1 << (nv > 8 ? nv - 8 : 0);
     k_bn_veq_prep<<<dim3(1 + (unsigned)((high + 255) / 256), 1), 256, 0, st>>>(reinterpret_cast<const VeqPrep*>(d_desc + o_prep),
@@ -759,10 +462,10 @@ void instance_mle_batch_device_bn254(hg_ctx* ctx, const Params& p, const std::ve
     k_bn_veq_fill<<<dim3((unsigned)std::min<size_t>((((size_t)1 << nv) + 255) / 256, 1024), 1), 256, 0, st>>>(reinterpret_cast<const VeqFill*>(d_desc + o_fill));
     hipc(hipStreamWaitEvent(st, B->ev[0], 0), "hg_instance_mle_batch_bn254: wait for the instances");
     Fr* res = ctx->alloc_n<Fr>(np);
-    Fr* part = ctx->alloc_n<Fr>(np * (size_t)U.nblk * VBN_WAVES);
+    Fr* part = ctx->alloc_n<Fr>(V.parts);
     const auto* d_units = reinterpret_cast<const BnVinUnit*>(d_desc + o_unit);
-    const auto* d_mem = reinterpret_cast<const BnVinMember*>(d_desc + o_mem);
-    k_bn_vin_compact_dots<<<(unsigned)blocks.size(), VBN_TPB, 0, st>>>(d_units, d_mem, reinterpret_cast<const BnVinBlock*>(d_desc + o_blk), part);
+    const auto* d_mem = reinterpret_cast<const VinMember*>(d_desc + o_mem);
+    k_bn_vin_dots<true><<<(unsigned)blocks.size(), VBN_TPB, 0, st>>>(d_units, d_mem, reinterpret_cast<const VinBlock*>(d_desc + o_blk), part);
     k_bn_vin_reduce<<<(unsigned)np, 64, 0, st>>>(d_units, d_mem, part, res);
     static_assert(sizeof(Fr) == 4 * sizeof(u64), "an Fr result slot is 4 limbs");
     hipc(hipMemcpyAsync(out4, res, np * sizeof(Fr), hipMemcpyDeviceToHost, st), "hg_instance_mle_batch_bn254: copy results");

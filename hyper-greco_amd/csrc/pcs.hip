@@ -614,7 +614,7 @@ void instance_digest_device(hg_ctx* ctx, const Params& p, const std::vector<cons
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
     ctx->arena_reset();
     hipStream_t st = ctx->stream;
-    DrainOne drain{st};   // (the instances are the caller's: every way out waits for their uploads)
+    Drain drain{st};   // (the instances are the caller's: every way out waits for their uploads)
     const size_t G = insts.size(), kn = (size_t)p.k * p.PZ();
     std::vector<DigestMember> mem(G);
     u64* d_words = ctx->alloc_n<u64>(G * 2 * kn);
@@ -639,7 +639,7 @@ void instance_digest_values(hg_ctx* ctx, const Params& p, const DigestMember& me
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
     ctx->arena_reset();
     hipStream_t st = ctx->stream;
-    DrainOne drain{st};
+    Drain drain{st};
     uint8_t root[32];
     unsigned flag = 0;
     instance_digest_enqueue(ctx, st, p, true, &mem, 1, root, &flag);
@@ -666,8 +666,8 @@ Commitment* commit_device_values(hg_ctx* ctx, const Shape& sh, const u64* const*
     u64* d_tree = ctx->alloc_n<u64>(4 * 2 * N);
     unsigned* d_flag = ctx->alloc_n<unsigned>(4);
     unsigned flag = 0;
-    DrainOne drain{st};   // (drains on an error; after the synchronisation below its own is one more, on an idle stream)
-    DrainOne drain2{dg ? ctx->stream2 : st};   // (the digest's stream as well, where one is used)
+    Drain drain{st};   // (drains on an error; after the synchronisation below its own is one more, on an idle stream)
+    Drain drain2{dg ? ctx->stream2 : st};   // (the digest's stream as well, where one is used)
     if (dg) {   // the second stream starts behind whatever the first one holds by now, not behind the commit
         hip_check(hipEventRecord(ctx->ev_fork, st), "fork");
         hip_check(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0), "fork wait");

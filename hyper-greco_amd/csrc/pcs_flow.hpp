@@ -158,7 +158,7 @@ std::string verify_flow(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], co
     } catch (const std::exception& e) {
         throw Error(std::string("the context's arena cannot hold the opening (") + e.what() + ")");
     }
-    DrainOne drain{st};   // (drains on an error; after the synchronisation below its own is one more, on an idle stream)
+    Drain drain{st};   // (drains on an error; after the synchronisation below its own is one more, on an idle stream)
     const int cls = ctx->prof_class(F::CLS_VERIFY, false);
     ctx->prof_stream = st;
     const VbGroup vg{1, (u64)Q, (u64)sh.R, (u64)query_stride<F>(sh), sh.c, sh.depth()};
@@ -227,7 +227,7 @@ std::vector<std::string> verify_batch_flow(const char* who_c, hg_ctx* ctx, const
     VerifyBatchBufs* B = batch_bufs(ctx);
     hipStream_t st = ctx->stream;
     std::vector<u64> hj, cells;   // (declared ahead of the guard: copies of them may be queued when it drains)
-    DrainOne drain_up{B->up}, drain{st};   // (the upload stream as well: no kernel on a set left behind)
+    Drain drain_up{B->up}, drain{st};   // (the upload stream as well: no kernel on a set left behind)
     hip_check(hipStreamSynchronize(st), (who + ": synchronise").c_str());   // (the arena is reset below)
     [[maybe_unused]] const int nthr = std::max(1, hg_omp_threads());        // (the device pass of hipcc ignores the pragmas)
     const int cls = ctx->prof_class(F::CLS_VERIFY_BATCH, false);
@@ -363,7 +363,7 @@ std::vector<Commitment*> commit_batch_flow(const char* who_c, hg_ctx* ctx, const
     hipStream_t st = ctx->stream;
     std::vector<std::unique_ptr<Commitment>> made;
     std::vector<u64> h_out;   // (declared ahead of the guard: a copy into it may be queued when it drains)
-    DrainOne drain{st};
+    Drain drain{st};
     hip_check(hipStreamSynchronize(st), (who + ": synchronise").c_str());   // (the arena is reset below)
     const int cls = ctx->prof_class(F::CLS_COMMIT_BATCH, false);
     ctx->prof_stream = st;
@@ -524,7 +524,7 @@ std::vector<Opened> open_batch_flow(const char* who_c, const char* single, hg_ct
     VerifyBatchBufs* B = batch_bufs(ctx);
     hipStream_t st = ctx->stream;
     std::vector<u64> hj;   // (declared ahead of the guard: a copy of it may be queued when it drains)
-    DrainOne drain{st};
+    Drain drain{st};
     hip_check(hipStreamSynchronize(st), (who + ": synchronise").c_str());   // (the arena is reset below)
     [[maybe_unused]] const int nthr = std::max(1, hg_omp_threads());        // (the device pass of hipcc ignores the pragmas)
     const int cls = ctx->prof_class(F::CLS_OPEN_BATCH, false);

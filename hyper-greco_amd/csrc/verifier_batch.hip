@@ -14,11 +14,14 @@
 // and walks run while group g's kernels do.
 // hg_verify_public_batch is the same pass from the ciphertext (the batch form of verify_public_device, verifier_dev.hip): the walks
 // run with public_only, the recording backend in its compact form, each proof's instance is staged as it is (2 k n signed words),
-// k_vin_compact_dots evaluates ais and ct0is from them, and the claims on the secret inputs come back from each proof's pending state.
+// k_vin_dots<true> evaluates ais and ct0is from them, and the claims on the secret inputs come back from each proof's pending state.
 // hg_verify_public_bound_batch is that pass for bound proofs (the batch form of verify_public_device with a root): a third source kind
 // of verify_batch_run. A group's instances are staged in slices, each slice's statement digests are taken out of the staged set on the
 // upload stream, in the batch's own buffers (batch_stage_instances_bound), and a group's walks wait for its digests before they start
 // from bound_seed; launch and complete are the unbound ones.
+// What of this is the same over BN254 - the recording backend, the merge of step 2, the work units of the input evaluations and the
+// loop over the groups - is verifier_merge.hpp. This file keeps what is Goldilocks': the group-size rule, the chain a group reads
+// (the context's, or the proofs' own), the lowering of a merged group into tables, descriptors and launches, and the input kernels.
 #include <algorithm>
 #include <cstring>
 #include <map>
@@ -37,22 +40,32 @@ namespace {
 // of the P tables, eight products per accumulator before one reduction (gl_wide.hpp), one partial per (member, workgroup). A second
 // launch adds every member's partials into its result slot. HBM traffic: 8 B per input entry plus 16 / P B of eq.
 constexpr int VB_TPB = 256, VB_ITEMS = 8, VB_TILE = VB_TPB * VB_ITEMS;
-// (log2_n, lo: k_vin_compact_dots only - n is then the count of non-padding words, blocks of 2^log2_n, word lo + r of a block's 2^(log2_n+1) eq entries)
-struct VinUnit { const E2* eq; size_t n; int first, P, nblk; size_t part0; u32 log2_n, lo; };   // member p's partial of workgroup b: part0 + p * nblk + b
-struct VinMember { const u64* a; int unit, slot; };
-struct VinBlock { int unit, blk; };
+typedef VinUnitT<E2> VinUnit;   // member p's partial of workgroup b: part0 + p * nblk + b
 
+// COMPACT: k_vin_dots over the compact signed coefficients of public instances (hg_verify_public_batch; CompactDotJob, prover.hpp, is
+// the single-proof form). A unit is one eq table and the P members' coefficient blocks evaluated at its point (mode 0: the group's
+// tables of one public input; modes 1-3: one). A workgroup owns VB_TILE consecutive WORD indices t of the non-padding range only
+// (U.n = blocks * 2^log2_n of them): with b = t >> log2_n and r = t & (n-1), eq entry b * 2n + lo + r meets coefficient n-1-r of
+// block b (vin_at), exactly as k_vdot_compact_jobs indexes (ais[i]: one block, lo = 0; ct0is: k blocks, lo = n-1). The eq tile is loaded
+// once into registers; per member the eight int64 words are read (descending over the same cache lines as the eq loads ascend) and
+// the sign becomes the field element in registers, a negative z being GL_P - |z|. Accumulator bound: the plain form's, eight products of
+// canonical operands per accumulator before one reduction - |z| <= (q_i-1)/2 < 2^61 (hg_instance_from_ciphertext checks the range),
+// so the lifted word is canonical, and the eq entries are. One partial per (member, workgroup); k_vin_reduce adds them. HBM traffic
+// by design: 8 B per coefficient plus 16 / P B of eq, nothing for padding words - the padding half of an eq table is never read.
+template <bool COMPACT>
 __global__ __launch_bounds__(VB_TPB) void k_vin_dots(const VinUnit* __restrict__ units, const VinMember* __restrict__ members,
                                                      const VinBlock* __restrict__ blocks, E2* __restrict__ partials) {
     __shared__ E2 sm[2][VB_TPB / 64];
     const VinBlock B = blocks[blockIdx.x];
     const VinUnit U = units[B.unit];
-    const size_t base = (size_t)B.blk * VB_TILE + threadIdx.x;
+    const size_t base = (size_t)B.blk * VB_TILE + threadIdx.x, nm1 = ((size_t)1 << U.log2_n) - 1;
     E2 eq[VB_ITEMS];
 #pragma unroll
     for (int j = 0; j < VB_ITEMS; j++) {
-        const size_t i = base + (size_t)j * VB_TPB;
-        eq[j] = i < U.n ? U.eq[i] : e2_zero();
+        const size_t t = base + (size_t)j * VB_TPB;
+        size_t ie, iw;
+        vin_at<COMPACT>(t, nm1, U.lo, ie, iw);
+        eq[j] = t < U.n ? U.eq[ie] : e2_zero();
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int p = 0; p < U.P; p++) {
@@ -60,8 +73,14 @@ __global__ __launch_bounds__(VB_TPB) void k_vin_dots(const VinUnit* __restrict__
         u64 v[VB_ITEMS];
 #pragma unroll
         for (int j = 0; j < VB_ITEMS; j++) {
-            const size_t i = base + (size_t)j * VB_TPB;
-            v[j] = i < U.n ? a[i] : 0;
+            const size_t t = base + (size_t)j * VB_TPB;
+            size_t ie, iw;
+            vin_at<COMPACT>(t, nm1, U.lo, ie, iw);
+            v[j] = t < U.n ? a[iw] : 0;
+            if constexpr (COMPACT) {
+                const int64_t z = (int64_t)v[j];
+                v[j] = z >= 0 ? (u64)z : GL_P - (u64)(-z);
+            }
         }
         WAcc c0 = wacc_zero(), c1 = wacc_zero();
 #pragma unroll
@@ -74,58 +93,6 @@ __global__ __launch_bounds__(VB_TPB) void k_vin_dots(const VinUnit* __restrict__
             s = e2_add(s, t);
         }
         // (two LDS buffers: member p + 1 writes the other one, and thread 0 has read this one before the next barrier)
-        if (lane == 0) sm[p & 1][wave] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            E2 t = sm[p & 1][0];
-            for (int w = 1; w < VB_TPB / 64; w++) t = e2_add(t, sm[p & 1][w]);
-            partials[U.part0 + (size_t)p * U.nblk + B.blk] = t;
-        }
-    }
-}
-// k_vin_dots over the compact signed coefficients of public instances (hg_verify_public_batch; CompactDotJob, prover.hpp, is the
-// single-proof form). A unit is one eq table and the P members' coefficient blocks evaluated at its point (mode 0: the group's
-// tables of one public input; modes 1-3: one). A workgroup owns VB_TILE consecutive WORD indices t of the non-padding range only
-// (U.n = blocks * 2^log2_n of them): with b = t >> log2_n and r = t & (n-1), eq entry b * 2n + lo + r meets coefficient n-1-r of
-// block b, exactly as k_vdot_compact_jobs indexes (ais[i]: one block, lo = 0; ct0is: k blocks, lo = n-1). The eq tile is loaded
-// once into registers; per member the eight int64 words are read (descending over the same cache lines as the eq loads ascend) and
-// the sign becomes the field element in registers, a negative z being GL_P - |z|. Accumulator bound: k_vin_dots's, eight products of
-// canonical operands per accumulator before one reduction - |z| <= (q_i-1)/2 < 2^61 (hg_instance_from_ciphertext checks the range),
-// so the lifted word is canonical, and the eq entries are. One partial per (member, workgroup); k_vin_reduce adds them. HBM traffic
-// by design: 8 B per coefficient plus 16 / P B of eq, nothing for padding words - the padding half of an eq table is never read.
-__global__ __launch_bounds__(VB_TPB) void k_vin_compact_dots(const VinUnit* __restrict__ units, const VinMember* __restrict__ members,
-                                                             const VinBlock* __restrict__ blocks, E2* __restrict__ partials) {
-    __shared__ E2 sm[2][VB_TPB / 64];
-    const VinBlock B = blocks[blockIdx.x];
-    const VinUnit U = units[B.unit];
-    const size_t base = (size_t)B.blk * VB_TILE + threadIdx.x, nm1 = ((size_t)1 << U.log2_n) - 1;
-    E2 eq[VB_ITEMS];
-#pragma unroll
-    for (int j = 0; j < VB_ITEMS; j++) {
-        const size_t t = base + (size_t)j * VB_TPB, r = t & nm1;
-        eq[j] = t < U.n ? U.eq[2 * (t - r) + U.lo + r] : e2_zero();
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int p = 0; p < U.P; p++) {
-        const int64_t* __restrict__ c = reinterpret_cast<const int64_t*>(members[U.first + p].a);
-        u64 v[VB_ITEMS];
-#pragma unroll
-        for (int j = 0; j < VB_ITEMS; j++) {
-            const size_t t = base + (size_t)j * VB_TPB, r = t & nm1;
-            const int64_t z = t < U.n ? c[(t - r) + (nm1 - r)] : 0;
-            v[j] = z >= 0 ? (u64)z : GL_P - (u64)(-z);
-        }
-        WAcc c0 = wacc_zero(), c1 = wacc_zero();
-#pragma unroll
-        for (int j = 0; j < VB_ITEMS; j++) wmac2(c0, eq[j].c0, v[j], c1, eq[j].c1, v[j]);
-        E2 s = e2(wreduce(c0), wreduce(c1));
-        for (int o = 32; o > 0; o >>= 1) {
-            E2 t;
-            t.c0 = __shfl_xor(s.c0, o);
-            t.c1 = __shfl_xor(s.c1, o);
-            s = e2_add(s, t);
-        }
-        // (two LDS buffers, as in k_vin_dots)
         if (lane == 0) sm[p & 1][wave] = s;
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -151,144 +118,6 @@ __global__ __launch_bounds__(64) void k_vin_reduce(const VinUnit* __restrict__ u
     }
     if (threadIdx.x == 0) res[M.slot] = s;
 }
-
-// ---- the recording backend ----------------------------------------------------------------------------------------------------------
-// The same calls as DevBackend (verifier_dev.hip), kept as symbolic jobs: tables are indices into the proof's own lists, chain
-// offsets are local to the proof's chain, tickets are local result slots. value() reads the slots the batch copied back.
-struct RecBackend : VerifyBackend {
-    const hg_pk* pk;
-    size_t n_inputs;
-    struct Eq { int nvars; dev::ClaimSet cs; };
-    struct Const { int node, eqc, slot; };
-    struct Lin { int node, in, eqc; };
-    struct Mul { int node, in, eqc, eqx; size_t u_at; };
-    struct Fft { int node; dev::ClaimSet cs; };
-    enum { D_LIN, D_MUL, D_FFT };
-    struct Dot { int kind, tab, eq, slot; };
-    struct In { int k, eq, slot; };   // k < 0: ct0is
-    std::vector<Eq> eqs;
-    std::vector<Const> consts;
-    std::vector<Lin> lins;
-    std::vector<Mul> muls;
-    std::vector<Fft> ffts;
-    std::vector<Dot> dots;
-    std::vector<In> ins;
-    std::vector<E2> us;            // phase-1 evaluations of the Vanilla nodes with a phase 2, back to back
-    size_t chain_need = 0;         // one past the last chain entry a job reads
-    int nslots = 0;
-    std::vector<E2> res;           // the results, filled after the group's synchronisation
-    int node = -1, eqc = -1, eqx = -1, eqy = -1;
-    size_t u_at = 0;
-    dev::ClaimSet cs;
-
-    // hg_verify_public_batch (the counterpart of DevBackend::cp): the public tables are compact signed coefficients, mle_input for
-    // inputs 3 .. 3+k-1 and mle_ct0is record compact input jobs, any other input is refused
-    const Params* cp = nullptr;
-
-    RecBackend(const hg_pk* k, bool compact = false) : pk(k), n_inputs(2 * (size_t)k->params.k + 4), cp(compact ? &k->params : nullptr) { memset(&cs, 0, sizeof(cs)); }
-    int slot() { return nslots++; }
-    void reads_chain(const dev::ClaimSet& c, int nvars) {
-        for (int a = 0; a < c.n; a++) chain_need = std::max(chain_need, c.point_off[a] + (size_t)nvars);
-        if (!c.unit_alpha) chain_need = std::max(chain_need, c.alpha_off + (size_t)c.n);
-    }
-    int eq_of(int nvars, const dev::ClaimSet& c) {
-        reads_chain(c, nvars);
-        eqs.push_back(Eq{nvars, c});
-        return (int)eqs.size() - 1;
-    }
-    int eq_single(int nvars, size_t off) {
-        dev::ClaimSet c;
-        memset(&c, 0, sizeof(c));
-        c.n = 1; c.unit_alpha = 1; c.point_off[0] = off;
-        return eq_of(nvars, c);
-    }
-    int dot(int kind, int tab, int eq) { const int t = slot(); dots.push_back(Dot{kind, tab, eq, t}); return t; }
-
-    void begin_node(int id, const ClaimOffs& cl) override {
-        node = id;
-        const HNode& n = pk->circuit.nodes[id];
-        if (cl.point_off.size() > (size_t)dev::MAX_CLAIMS) throw Error("verifier: too many claims on one node");
-        memset(&cs, 0, sizeof(cs));
-        cs.n = (int)cl.point_off.size();
-        cs.unit_alpha = cl.unit ? 1 : 0;
-        cs.alpha_off = cl.alpha_off;
-        for (int a = 0; a < cs.n; a++) cs.point_off[a] = cl.point_off[a];
-        eqc = n.kind == NK_VANILLA ? eq_of(n.log2_out(), cs) : -1;
-        eqx = eqy = -1;
-    }
-    int const_sum() override { const int t = slot(); consts.push_back(Const{node, eqc, t}); return t; }
-    void set_x(size_t x_off) override {
-        const HNode& n = pk->circuit.nodes[node];
-        eqx = eq_single(n.kind == NK_VANILLA ? n.log2_sub_in + n.log2_reps : n.log2_size, x_off);
-    }
-    std::vector<int> lin_terms() override {
-        const HNode& n = pk->circuit.nodes[node];
-        const hg_pk::NodeDev& nd = pk->node_dev[node];
-        std::vector<int> tk(n.arity, -1);
-        for (int i = 0; i < n.arity; i++) {
-            if (!n.left_use[i] || !nd.lin[i].ptr) continue;
-            lins.push_back(Lin{node, i, eqc});
-            tk[i] = dot(D_LIN, (int)lins.size() - 1, eqx);
-        }
-        return tk;
-    }
-    void set_y(size_t y_off, const std::vector<E2>& u) override {
-        const HNode& n = pk->circuit.nodes[node];
-        eqy = eq_single(n.log2_sub_in + n.log2_reps, y_off);
-        u_at = us.size();
-        us.insert(us.end(), u.begin(), u.end());
-    }
-    std::vector<int> mul_terms() override {
-        const HNode& n = pk->circuit.nodes[node];
-        const hg_pk::NodeDev& nd = pk->node_dev[node];
-        std::vector<int> tk(n.arity, -1);
-        for (int i = 0; i < n.arity; i++) {
-            if (!n.right_use[i] || !nd.mulR[i].ptr) continue;
-            muls.push_back(Mul{node, i, eqc, eqx, u_at});
-            tk[i] = dot(D_MUL, (int)muls.size() - 1, eqy);
-        }
-        return tk;
-    }
-    int fft_term() override {
-        reads_chain(cs, pk->circuit.nodes[node].log2_size);
-        ffts.push_back(Fft{node, cs});
-        return dot(D_FFT, (int)ffts.size() - 1, eqx);
-    }
-    void end_node() override { node = -1; }
-    int mle_input(size_t k, size_t point_off, int nvars) override {
-        if (cp) {
-            if (k < 3 || k >= 3 + (size_t)cp->k) throw Error("verifier: input " + std::to_string(k) + " is not a public table");
-            if (nvars != cp->L) throw Error("verifier: a point of the wrong length for a public table");   // (the job reads 2n eq entries)
-        }
-        if (k >= n_inputs) throw Error("verifier: no such input table");
-        const int t = slot();
-        ins.push_back(In{(int)k, eq_single(nvars, point_off), t});
-        return t;
-    }
-    int mle_ct0is(size_t point_off, int nvars) override {
-        if (cp && nvars != cp->ct0is_log2()) throw Error("verifier: a point of the wrong length for a public table");   // (k * 2n eq entries)
-        const int t = slot();
-        ins.push_back(In{-1, eq_single(nvars, point_off), t});
-        return t;
-    }
-    void finish() override { throw Error("verifier: a recording backend is finished by its batch"); }
-    E2 value(int t) const override { return res[t]; }
-};
-
-dev::ClaimSet shift_cs(dev::ClaimSet c, size_t base) {
-    if (!c.unit_alpha) c.alpha_off += base;
-    for (int a = 0; a < c.n; a++) c.point_off[a] += base;
-    return c;
-}
-
-struct Walked {   // one proof of a group
-    size_t idx;
-    std::unique_ptr<RecBackend> rec;
-    VerifyPending pend;
-    std::string error;                       // an hg::Error of the walk
-    std::vector<int> gslot;                  // local slot -> the group's result slot
-    const u64* d_in = nullptr;               // its inputs in HBM: s, e, k1, ais, r1is, r2is, ct0is
-};
 
 }  // namespace
 
@@ -504,17 +333,11 @@ void verify_batch_drop(hg_ctx* ctx) {
 }
 
 namespace {
-// kernels, descriptor copies and input copies may be queued on any way out (a rejection, an hg::Error): drain both streams before
-// the caller may reuse the arena and the staging or free a witness or an instance
-struct Drain {
-    hipStream_t a, b;
-    ~Drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); }
-};
 // the MLE evaluations of the inputs: one partial per (member, workgroup), then every member's partials into its slot
 void vin_launch(hipStream_t st, bool compact, const VinUnit* units, const VinMember* members, size_t nmembers, const VinBlock* blocks, size_t nblocks,
                 E2* part, E2* res) {
-    if (compact) k_vin_compact_dots<<<(unsigned)nblocks, VB_TPB, 0, st>>>(units, members, blocks, part);
-    else k_vin_dots<<<(unsigned)nblocks, VB_TPB, 0, st>>>(units, members, blocks, part);
+    if (compact) k_vin_dots<true><<<(unsigned)nblocks, VB_TPB, 0, st>>>(units, members, blocks, part);
+    else k_vin_dots<false><<<(unsigned)nblocks, VB_TPB, 0, st>>>(units, members, blocks, part);
     k_vin_reduce<<<(unsigned)nmembers, 64, 0, st>>>(units, members, part, res);
 }
 
@@ -562,7 +385,7 @@ void verify_batch_run(hg_ctx* ctx, const hg_pk* pk, const BatchSrc& src, const s
     const size_t ngroups = (n + G - 1) / G;
     [[maybe_unused]] const int nthr = std::max(1, hg_omp_threads());   // (the device pass of hipcc ignores the pragmas)
 
-    std::vector<std::vector<Walked>> groups(ngroups);
+    std::vector<std::vector<Walked<E2>>> groups(ngroups);
     // stage group g: gather its inputs into page-locked set g & 1 (host threads), copy them on the upload stream
     auto stage = [&](size_t g) {
         if (bound) batch_stage_instances_bound(ctx, B, (int)(g & 1), p, *src.insts, g * G, std::min(n, g * G + G), kn, bound_slice(ctx, kn), nthr, src.who);
@@ -572,126 +395,53 @@ void verify_batch_run(hg_ctx* ctx, const hg_pk* pk, const BatchSrc& src, const s
     // walk group g on the host threads (a bound walk cannot squeeze its first challenge before its digest is back: wait for the set's)
     auto walk = [&](size_t g) {
         const size_t i0 = g * G, i1 = std::min(n, i0 + G);
-        std::vector<Walked>& W = groups[g];
-        W.resize(i1 - i0);
         const uint8_t* dg = nullptr;
         if (bound) {
             hip_check(hipEventSynchronize(B->ev_dg[g & 1]), (who + ": the statement digests").c_str());
             dg = B->h_dg[g & 1];
             memcpy(src.digests->data() + 32 * i0, dg, 32 * (i1 - i0));
         }
-#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)W.size()))
-        for (long long q = 0; q < (long long)W.size(); q++) {
-            Walked& x = W[q];
-            x.idx = i0 + (size_t)q;
-            try {
-                x.rec.reset(new RecBackend(pk, pub));
-                std::vector<uint8_t> seed;
-                if (bound) seed = bound_seed(p.raw, mode, dg + 32 * (size_t)q, (*src.roots)[x.idx]);
-                x.pend = verify_walk(*x.rec, p, pk->lasso, pk->circuit, proofs[x.idx], lens[x.idx], mode, pub, bound ? &seed : nullptr);
-            } catch (const std::exception& e) { x.error = e.what(); }
-        }
-        for (auto& x : W)
-            if (!x.error.empty()) throw Error(who + ": proof " + std::to_string(x.idx) + ": " + x.error);
+        walk_group(groups[g], i0, i1, nthr, who, [&](Walked<E2>& x) {
+            x.rec.reset(new RecBackendT<E2>(pk, pub, false));
+            std::vector<uint8_t> seed;
+            if (bound) seed = bound_seed(p.raw, mode, dg + 32 * (x.idx - i0), (*src.roots)[x.idx]);
+            x.pend = verify_walk(*x.rec, p, pk->lasso, pk->circuit, proofs[x.idx], lens[x.idx], mode, pub, bound ? &seed : nullptr);
+        });
     };
     // merge group g's jobs and enqueue them; returns the result slots used
     auto launch = [&](size_t g) -> size_t {
         const int s = (int)(g & 1);
-        std::vector<Walked>& W = groups[g];
+        std::vector<Walked<E2>>& W = groups[g];
         hipStream_t st = ctx->stream;
         ctx->arena_reset();
-        std::vector<dev::EqJob> eqs;
-        int eq_max_n = 0;
-        struct ConstG { int node, eq, slot; };
-        std::vector<ConstG> consts;
-        struct LinG { int node, in, eq; };
-        std::vector<LinG> lins;
-        struct MulG { int node, in, eqc, eqx; size_t u_at; };
-        std::vector<MulG> muls;
-        struct FftG { int node; dev::ClaimSet cs; };
-        std::vector<FftG> ffts;
-        int fft_max_L = 0, fft_max_claims = 0;
-        struct DotG { int kind, tab, eq, slot; };
-        std::vector<DotG> dots;
-        struct InM { int eq; const u64* a; int slot; int ct0; };   // (ct0: the public form's ct0is, k blocks at lo = n-1)
-        std::vector<InM> ins;
-        std::vector<E2> chain, us;
-        std::map<Key, int> eq_ix, const_ix, lin_ix, fft_ix, dot_ix;
-        int nslot = 0;
+        // mode 0 reads the context's fixed chain, modes 1-3 the concatenation of the proofs' own chains
+        for (auto& x : W) {
+            if (!x.pend.reason.empty()) continue;
+            if (mode != 0 && x.rec->chain_need > x.pend.chain.size())
+                throw Error(who + ": proof " + std::to_string(x.idx) + ": verifier: a job reads past the challenges the walk squeezed");
+            if (mode == 0 && x.rec->chain_need > ctx->chal_e) throw Error(who + ": proof " + std::to_string(x.idx) + ": verifier: a job reads past the fixed chain");
+        }
+        const MergedGroup<E2> M = merge_group(W, mode != 0);
+        const auto& consts = M.consts;
+        const auto& lins = M.lins;
+        const auto& muls = M.muls;
+        const auto& ffts = M.ffts;
+        const auto& dots = M.dots;
+        const std::vector<E2>& chain = M.chain;
+        const std::vector<E2>& us = M.us;
+        const int nslot = M.nslot;
+        typedef RecBackendT<E2> Rec;
+        std::vector<dev::EqJob> eqs(M.eqs.size());
+        int eq_max_n = 0, fft_max_L = 0, fft_max_claims = 0;
         size_t gt_max = 0, gb_max = 0;
-        for (Walked& x : W) {
-            x.d_in = B->d_in[s] + (x.idx - g * G) * words;
-            if (!x.pend.reason.empty()) continue;   // rejected by the walk: its recorded prefix is not launched
-            RecBackend& R = *x.rec;
-            size_t base = 0;
-            if (mode != 0) {
-                if (R.chain_need > x.pend.chain.size()) throw Error(who + ": proof " + std::to_string(x.idx) + ": verifier: a job reads past the challenges the walk squeezed");
-                base = chain.size();
-                chain.insert(chain.end(), x.pend.chain.begin(), x.pend.chain.end());
-            } else if (R.chain_need > ctx->chal_e) throw Error(who + ": proof " + std::to_string(x.idx) + ": verifier: a job reads past the fixed chain");
-            x.gslot.assign(R.nslots, -1);
-            auto new_slot = [&] { return nslot++; };
-            std::vector<int> geq(R.eqs.size());
-            for (size_t e = 0; e < R.eqs.size(); e++) {
-                Key k{(u64)R.eqs[e].nvars};
-                key_cs(k, R.eqs[e].cs, base);
-                auto it = eq_ix.find(k);
-                if (it == eq_ix.end()) {
-                    dev::EqJob J;
-                    memset(&J, 0, sizeof(J));
-                    J.n = R.eqs[e].nvars; J.cs = shift_cs(R.eqs[e].cs, base);
-                    eqs.push_back(J);
-                    eq_max_n = std::max(eq_max_n, J.n);
-                    it = eq_ix.emplace(k, (int)eqs.size() - 1).first;
-                }
-                geq[e] = it->second;
-            }
-            for (auto& c : R.consts) {
-                Key k{(u64)c.node, (u64)geq[c.eqc]};
-                auto it = const_ix.find(k);
-                if (it == const_ix.end()) { consts.push_back(ConstG{c.node, geq[c.eqc], new_slot()}); it = const_ix.emplace(k, (int)consts.size() - 1).first; }
-                x.gslot[c.slot] = consts[it->second].slot;
-            }
-            std::vector<int> glin(R.lins.size()), gmul(R.muls.size()), gfft(R.ffts.size());
-            for (size_t i = 0; i < R.lins.size(); i++) {
-                const auto& l = R.lins[i];
-                Key k{(u64)l.node, (u64)l.in, (u64)geq[l.eqc]};
-                auto it = lin_ix.find(k);
-                if (it == lin_ix.end()) { lins.push_back(LinG{l.node, l.in, geq[l.eqc]}); it = lin_ix.emplace(k, (int)lins.size() - 1).first; }
-                glin[i] = it->second;
-            }
-            for (size_t i = 0; i < R.muls.size(); i++) {   // (never shared: they read the proof's phase-1 evaluations)
-                const auto& m = R.muls[i];
-                muls.push_back(MulG{m.node, m.in, geq[m.eqc], geq[m.eqx], us.size() + m.u_at});
-                gmul[i] = (int)muls.size() - 1;
-            }
-            us.insert(us.end(), R.us.begin(), R.us.end());
-            for (size_t i = 0; i < R.ffts.size(); i++) {
-                Key k{(u64)R.ffts[i].node};
-                key_cs(k, R.ffts[i].cs, base);
-                auto it = fft_ix.find(k);
-                if (it == fft_ix.end()) {
-                    ffts.push_back(FftG{R.ffts[i].node, shift_cs(R.ffts[i].cs, base)});
-                    fft_max_L = std::max(fft_max_L, pk->circuit.nodes[R.ffts[i].node].log2_size);
-                    fft_max_claims = std::max(fft_max_claims, R.ffts[i].cs.n);
-                    it = fft_ix.emplace(k, (int)ffts.size() - 1).first;
-                }
-                gfft[i] = it->second;
-            }
-            for (auto& d : R.dots) {
-                const int tab = d.kind == RecBackend::D_LIN ? glin[d.tab] : d.kind == RecBackend::D_MUL ? gmul[d.tab] : gfft[d.tab];
-                if (d.kind == RecBackend::D_MUL) { dots.push_back(DotG{d.kind, tab, geq[d.eq], new_slot()}); x.gslot[d.slot] = dots.back().slot; continue; }
-                Key k{(u64)d.kind, (u64)tab, (u64)geq[d.eq]};
-                auto it = dot_ix.find(k);
-                if (it == dot_ix.end()) { dots.push_back(DotG{d.kind, tab, geq[d.eq], new_slot()}); it = dot_ix.emplace(k, (int)dots.size() - 1).first; }
-                x.gslot[d.slot] = dots[it->second].slot;
-            }
-            for (auto& in : R.ins) {   // (never shared: they read the proof's own witness or instance)
-                const int sl = new_slot();
-                if (pub) ins.push_back(InM{geq[in.eq], x.d_in + (in.k < 0 ? kn : (size_t)(in.k - 3) * L.PZ), sl, in.k < 0});
-                else ins.push_back(InM{geq[in.eq], x.d_in + L.offset(in.k), sl, 0});
-                x.gslot[in.slot] = sl;
-            }
+        for (size_t e = 0; e < eqs.size(); e++) {
+            memset(&eqs[e], 0, sizeof(eqs[e]));
+            eqs[e].n = M.eqs[e].n; eqs[e].cs = M.eqs[e].cs;
+            eq_max_n = std::max(eq_max_n, eqs[e].n);
+        }
+        for (auto& f : ffts) {
+            fft_max_L = std::max(fft_max_L, pk->circuit.nodes[f.node].log2_size);
+            fft_max_claims = std::max(fft_max_claims, f.cs.n);
         }
         if ((size_t)nslot > ctx->res_cap)
             throw Error(who + ": a group needs " + std::to_string(nslot) + " result slots, the context has " + std::to_string(ctx->res_cap) + ": lower verify_batch_group");
@@ -717,32 +467,10 @@ void verify_batch_run(hg_ctx* ctx, const hg_pk* pk, const BatchSrc& src, const s
             fjs[i] = dev::FftJob{fft_F[i] = ctx->alloc_n<E2>(N), (nd.inverse ? pk->w_inv : pk->w_fwd).at(L), nd.inverse ? gl_inv(gl_from_u64(N)) : 1, L, ffts[i].cs};
         }
         // the descriptors, the walks' chains and phase-1 evaluations: one page-locked staging, one copy ahead of the launches
-        std::vector<VinUnit> units;
-        std::vector<VinMember> members;
-        std::vector<VinBlock> blocks;
-        {
-            // (an ais table and ct0is never share a unit, even at one point: their words sit at other places of the eq table)
-            std::vector<std::vector<const InM*>> by_eq(2 * eqs.size());
-            for (auto& m : ins) by_eq[2 * (size_t)m.eq + m.ct0].push_back(&m);
-            size_t part = 0;
-            for (size_t e2x = 0; e2x < by_eq.size(); e2x++) {
-                if (by_eq[e2x].empty()) continue;
-                const size_t e = e2x / 2;
-                VinUnit U;
-                memset(&U, 0, sizeof(U));
-                U.eq = eqs[e].out; U.n = (size_t)1 << eqs[e].n; U.first = (int)members.size(); U.P = (int)by_eq[e2x].size();
-                if (pub) {   // the non-padding words only: n of an ais table, k n of ct0is (the walk checked the eq table's size)
-                    U.n = e2x & 1 ? kn : L.PZ; U.log2_n = (u32)p.n_log2; U.lo = e2x & 1 ? (u32)(L.PZ - 1) : 0;
-                }
-                U.nblk = (int)((U.n + VB_TILE - 1) / VB_TILE); U.part0 = part;
-                part += (size_t)U.P * U.nblk;
-                for (const InM* m : by_eq[e2x]) members.push_back(VinMember{m->a, (int)units.size(), m->slot});
-                for (int b = 0; b < U.nblk; b++) blocks.push_back(VinBlock{(int)units.size(), b});
-                units.push_back(U);
-            }
-        }
-        size_t vin_parts = 0, vin_bytes = 0;   // (vin_bytes: what k_vin_dots / k_vin_compact_dots reads, eq tables and input tables)
-        for (auto& U : units) { vin_parts += (size_t)U.P * U.nblk; vin_bytes += U.n * (sizeof(E2) + (size_t)U.P * sizeof(u64)); }
+        const VinPlan<E2> V = vin_units(M, [&](size_t e) { return eqs[e].out; }, B->d_in[s], words, p, pub, VB_TILE, 1);
+        const auto& units = V.units;
+        const auto& members = V.members;
+        const auto& blocks = V.blocks;
         size_t desc_bytes = 0;
         auto place = [&](size_t bytes) { const size_t o = desc_bytes; desc_bytes += (bytes + 255) & ~(size_t)255; return o; };
         const size_t o_chain = place(chain.size() * sizeof(E2)), o_us = place(us.size() * sizeof(E2)), o_eq = place(eqs.size() * sizeof(dev::EqJob)),
@@ -759,7 +487,7 @@ void verify_batch_run(hg_ctx* ctx, const hg_pk* pk, const BatchSrc& src, const s
         if (!eqs.empty()) memcpy(h + o_eq, eqs.data(), eqs.size() * sizeof(dev::EqJob));
         if (!gts.empty()) memcpy(h + o_gt, gts.data(), gts.size() * sizeof(dev::GatherJob));
         for (size_t i = 0; i < muls.size(); i++) {
-            const MulG& m = muls[i];
+            const auto& m = muls[i];
             const HNode& nd = pk->circuit.nodes[m.node];
             const size_t SR = (size_t)1 << (nd.log2_sub_in + nd.log2_reps);
             mul_B[i] = ctx->alloc_n<E2>(SR);
@@ -769,8 +497,8 @@ void verify_batch_run(hg_ctx* ctx, const hg_pk* pk, const BatchSrc& src, const s
         }
         if (!fjs.empty()) memcpy(h + o_fft, fjs.data(), fjs.size() * sizeof(dev::FftJob));
         for (size_t i = 0; i < dots.size(); i++) {
-            const DotG& d = dots[i];
-            const E2* a = d.kind == RecBackend::D_LIN ? lin_T[d.tab] : d.kind == RecBackend::D_MUL ? mul_B[d.tab] : fft_F[d.tab];
+            const auto& d = dots[i];
+            const E2* a = d.kind == Rec::D_LIN ? lin_T[d.tab] : d.kind == Rec::D_MUL ? mul_B[d.tab] : fft_F[d.tab];
             const DotJob J{a, eqs[d.eq].out, (size_t)1 << eqs[d.eq].n, d.slot, 0};
             memcpy(h + o_dot + i * sizeof(DotJob), &J, sizeof(J));
         }
@@ -784,7 +512,7 @@ void verify_batch_run(hg_ctx* ctx, const hg_pk* pk, const BatchSrc& src, const s
         auto chunks = [](size_t njobs, size_t per, auto fn) { for (size_t q0 = 0; q0 < njobs; q0 += per) fn(q0, std::min(per, njobs - q0)); };
         const auto* d_eqs = reinterpret_cast<const dev::EqJob*>(d_desc + o_eq);
         chunks(eqs.size(), VD_MAX_Y, [&](size_t q0, size_t nq) { dev::eq_jobs(st, d_eqs + q0, (int)nq, eq_max_n, chal); });
-        for (const ConstG& c : consts) {
+        for (const auto& c : consts) {
             const HNode& nd = pk->circuit.nodes[c.node];
             const hg_pk::NodeDev& dv = pk->node_dev[c.node];
             const int grid = dev::vanilla_const_sum(st, dv.const_gate, dv.const_coef, dv.nconst, eqs[c.eq].out, nd.log2_sub_out, nd.log2_reps, ctx->d_partials);
@@ -804,46 +532,23 @@ void verify_batch_run(hg_ctx* ctx, const hg_pk* pk, const BatchSrc& src, const s
         if (!units.empty()) {
             hip_check(hipStreamWaitEvent(st, B->ev[s], 0), (who + ": wait for the inputs").c_str());
             vin_launch(st, pub, reinterpret_cast<const VinUnit*>(d_desc + o_unit), reinterpret_cast<const VinMember*>(d_desc + o_mem), members.size(),
-                       reinterpret_cast<const VinBlock*>(d_desc + o_blk), blocks.size(), ctx->alloc_n<E2>(vin_parts), ctx->d_res);
+                       reinterpret_cast<const VinBlock*>(d_desc + o_blk), blocks.size(), ctx->alloc_n<E2>(V.parts), ctx->d_res);
         }
         if (ctx->d_res != ctx->h_res && nslot)
             hip_check(hipMemcpyAsync(ctx->h_res, ctx->d_res, (size_t)nslot * sizeof(E2), hipMemcpyDeviceToHost, st), (who + ": copy results").c_str());
         if (times)
             fprintf(stderr, "[hg] verify_batch: group %zu (%zu proofs): %zu eq tables, %zu constant sums, %zu + %zu gathers, %zu DFT rows, %zu dots, %zu input evaluations in %zu units (%.1f MB); %d slots\n",
-                    g, W.size(), eqs.size(), consts.size(), lins.size(), muls.size(), ffts.size(), dots.size(), members.size(), units.size(), vin_bytes / 1e6, nslot);
+                    g, W.size(), eqs.size(), consts.size(), lins.size(), muls.size(), ffts.size(), dots.size(), members.size(), units.size(), V.bytes / 1e6, nslot);
         return (size_t)nslot;
     };
     auto complete = [&](size_t g) {
-        std::vector<Walked>& W = groups[g];
-#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)W.size()))
-        for (long long q = 0; q < (long long)W.size(); q++) {
-            Walked& x = W[q];
-            if (x.pend.reason.empty()) {
-                x.rec->res.resize(x.gslot.size());
-                for (size_t t = 0; t < x.gslot.size(); t++) x.rec->res[t] = ctx->h_res[x.gslot[t]];
-            }
+        complete_group(groups[g], nthr, [&](int slot) { return ctx->h_res[slot]; }, [&](Walked<E2>& x) {
             why[x.idx] = verify_complete(x.pend);
             if (pub && why[x.idx].empty()) (*src.open)[x.idx] = std::move(x.pend.open);
-        }
-        W.clear();
+        });
+        if (bound && g + 1 == ngroups) ctx->prof_collect();   // (the last digests were waited for by the last walk, ahead of the last synchronisation)
     };
-
-    stage(0);
-    walk(0);
-    double t_walk = omp_get_wtime() - t0, t_sync = 0;
-    for (size_t g = 0; g < ngroups; g++) {
-        launch(g);
-        if (g + 1 < ngroups) { const double tw = omp_get_wtime(); stage(g + 1); walk(g + 1); t_walk += omp_get_wtime() - tw; }
-        const double ts = omp_get_wtime();
-        hip_check(hipStreamSynchronize(ctx->stream), (who + ": synchronise").c_str());
-        hip_check(hipGetLastError(), (who + ": kernels").c_str());
-        t_sync += omp_get_wtime() - ts;
-        complete(g);
-    }
-    if (bound) ctx->prof_collect();   // (the last digests were waited for by the last walk, ahead of the synchronisation above)
-    if (times)
-        fprintf(stderr, "[hg] verify_batch: %zu proofs in %zu groups of up to %zu: %.2f ms in all (staging and walks %.2f, waiting for the device %.2f)\n", n,
-                ngroups, G, (omp_get_wtime() - t0) * 1e3, t_walk * 1e3, t_sync * 1e3);
+    batch_groups(ctx->stream, who, "verify_batch", times, t0, n, ngroups, G, stage, walk, launch, complete);
 }
 
 }  // namespace
@@ -893,7 +598,7 @@ void instance_digest_group_device(hg_ctx* ctx, const Params& p, const std::vecto
     ctx->prof_collect();
 }
 
-// one eq job, then k_vin_compact_dots as ONE unit whose members are the instances' tables
+// one eq job, then k_vin_dots<true> as ONE unit whose members are the instances' tables
 void instance_mle_batch_device(hg_ctx* ctx, const Params& p, const std::vector<const Instance*>& insts, int which, int index, const std::vector<E2>& pt, E2* out) {
     const size_t np = insts.size();
     if (!np) return;
@@ -910,14 +615,13 @@ void instance_mle_batch_device(hg_ctx* ctx, const Params& p, const std::vector<c
     memset(&J, 0, sizeof(J));
     J.n = (int)pt.size(); J.cs.n = 1; J.cs.unit_alpha = 1;   // (point_off[0] = 0: the point is the whole chain)
     J.out = ctx->alloc_n<E2>((size_t)1 << J.n);
-    VinUnit U;
-    memset(&U, 0, sizeof(U));
-    U.eq = J.out; U.n = which ? kn : n; U.P = (int)np; U.nblk = (int)((U.n + VB_TILE - 1) / VB_TILE);
-    U.log2_n = (u32)p.n_log2; U.lo = which ? (u32)(n - 1) : 0;
-    std::vector<VinMember> members(np);
-    for (size_t i = 0; i < np; i++) members[i] = VinMember{B->d_in[0] + i * 2 * kn + (which ? kn : (size_t)index * n), 0, (int)i};
-    std::vector<VinBlock> blocks((size_t)U.nblk);
-    for (int b = 0; b < U.nblk; b++) blocks[b] = VinBlock{0, b};
+    std::vector<std::pair<const u64*, int>> tabs(np);
+    for (size_t i = 0; i < np; i++) tabs[i] = {B->d_in[0] + i * 2 * kn + (which ? kn : (size_t)index * n), (int)i};
+    VinPlan<E2> V;
+    V.add(J.out, which ? kn : n, (u32)p.n_log2, which ? (u32)(n - 1) : 0, tabs, VB_TILE, 1);
+    const VinUnit& U = V.units[0];
+    const auto& members = V.members;
+    const auto& blocks = V.blocks;
     size_t desc_bytes = 0;
     auto place = [&](size_t bytes) { const size_t o = desc_bytes; desc_bytes += (bytes + 255) & ~(size_t)255; return o; };
     const size_t o_chain = place(pt.size() * sizeof(E2)), o_eq = place(sizeof(J)), o_unit = place(sizeof(U)), o_mem = place(np * sizeof(VinMember)),
@@ -934,7 +638,7 @@ void instance_mle_batch_device(hg_ctx* ctx, const Params& p, const std::vector<c
     hip_check(hipStreamWaitEvent(st, B->ev[0], 0), "hg_instance_mle_batch: wait for the instances");
     E2* res = ctx->alloc_n<E2>(np);
     vin_launch(st, true, reinterpret_cast<const VinUnit*>(d_desc + o_unit), reinterpret_cast<const VinMember*>(d_desc + o_mem), np,
-               reinterpret_cast<const VinBlock*>(d_desc + o_blk), blocks.size(), ctx->alloc_n<E2>(np * (size_t)U.nblk), res);
+               reinterpret_cast<const VinBlock*>(d_desc + o_blk), blocks.size(), ctx->alloc_n<E2>(V.parts), res);
     hip_check(hipMemcpyAsync(out, res, np * sizeof(E2), hipMemcpyDeviceToHost, st), "hg_instance_mle_batch: copy results");
     hip_check(hipStreamSynchronize(st), "hg_instance_mle_batch: synchronise");
     hip_check(hipGetLastError(), "hg_instance_mle_batch: kernels");

@@ -1,6 +1,7 @@
 // What the batched device verifiers share (verifier_batch.hip: hg_verify_device_batch and hg_verify_public_batch over Goldilocks;
-// bn254_verify_batch.inc: hg_verify_device_batch_bn254 over bn256::Fr): the context's input sets and upload stream, the layout of one proof's public inputs
-// in a set, the default group size, and the staging of a group's inputs.
+// bn254_verify_batch.inc: hg_verify_device_batch_bn254 over bn256::Fr): the context's input sets and upload stream, the default
+// group size and the staging of a group's inputs here; the recorder, the group merge, the input units, the loop over the groups, the
+// layout of one proof's public inputs in a set and the stream guard of every device entry in verifier_merge.hpp.
 #pragma once
 #include <algorithm>
 #include <memory>
@@ -10,6 +11,7 @@
 #include <vector>
 #include "kernels.hpp"
 #include "prover.hpp"
+#include "verifier_merge.hpp"
 
 namespace hg {
 
@@ -40,19 +42,6 @@ VerifyBatchBufs* batch_bufs(hg_ctx* ctx);
 char* batch_desc_host(VerifyBatchBufs* B, size_t bytes);
 // the page-locked result buffer, grown to `bytes` (call it only when no copy into it is in flight)
 char* batch_out_host(VerifyBatchBufs* B, size_t bytes);
-
-// one proof's public inputs in a set, in the order of the single-proof verifiers: s, e, k1, ais (k), r1is (k), r2is, then ct0is -
-// the same signed integers in the same layout over both fields
-struct BatchInputs {
-    size_t SZ, PZ, K, words;
-    explicit BatchInputs(const Params& p) : SZ(p.SZ()), PZ(p.PZ()), K((size_t)p.k), words((3 + 3 * K) * SZ + K * PZ) {}
-    size_t offset(int k) const {   // the verifier's input table k (k < 0: ct0is)
-        if (k < 0) return (3 + 2 * K) * SZ + K * PZ;
-        if ((size_t)k < 3 + 2 * K) return (size_t)k * SZ;   // s, e, k1, then ais and r1is, SZ each
-        return (3 + 2 * K) * SZ;                           // r2is
-    }
-    size_t length(int k) const { return k < 0 ? K * SZ : (size_t)k == 3 + 2 * K ? K * PZ : SZ; }
-};
 
 // budget of one group: its inputs in one set (and, in modes 1-3 of the Goldilocks batch, each proof's own node tables in the arena:
 // about five times its inputs, 0.13 GB at n=32768 k=16)
@@ -92,10 +81,6 @@ struct Slab {   // a group's raw and encoded rows; its members' handles share it
         if (home) home->give(p, bytes); else (void)hipFree(p);
     }
 };
-struct DrainOne {   // every way out, an error included: no copy of a dead host buffer and no kernel on the arena left behind
-    hipStream_t st;
-    ~DrainOne() { (void)hipStreamSynchronize(st); }
-};
 // [first, last) of a run cut into groups: at most VB_MAX_GROUP or the option, `bytes_of(i)` summed within `budget`, `rows_each` a
 // member summed within max_rows; a group holds at least one member
 template <class BytesOf>
@@ -116,15 +101,6 @@ std::vector<std::pair<size_t, size_t>> cut_groups(hg_ctx* ctx, size_t n, BytesOf
     return groups;
 }
 }  // namespace pcs
-
-// dedup keys of the group merge: a job's descriptor with absolute chain offsets
-typedef std::vector<u64> Key;
-inline void key_cs(Key& k, const dev::ClaimSet& c, size_t base) {
-    k.push_back((u64)c.n);
-    k.push_back((u64)c.unit_alpha);
-    if (!c.unit_alpha) k.push_back(c.alpha_off + base);
-    for (int a = 0; a < c.n; a++) k.push_back(c.point_off[a] + base);
-}
 
 // gathers the inputs of proofs [i0, i1) into page-locked set `set` on the host threads (at most nthr) and copies them on the
 // upload stream; the set's event marks the copy. `who` prefixes the error messages.

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <omp.h>
 #include "prover.hpp"
+#include "verifier_merge.hpp"
 
 namespace hg {
 namespace {
@@ -343,10 +344,7 @@ std::string verify_proof_device(hg_ctx* ctx, const hg_pk* pk, const Witness& w, 
     // before the caller may reuse the staging buffer and the arena or free the witness whose uploads may still be pending. (The guard
     // stands ahead of the first enqueue. Peak arena use: every node's tables stay until the batched finish - the per-node rewind
     // went with the per-kind launches - about the size of the node tables, 0.13 GB at n=32768 k=16.)
-    struct Drain {
-        hipStream_t st;
-        ~Drain() { (void)hipStreamSynchronize(st); }
-    } drain{ctx->stream};
+    Drain drain{ctx->stream};
     ctx->ensure_chain(16384);
     const Params& p = pk->params;
     DevBackend D(ctx, pk, mode);
@@ -369,11 +367,7 @@ std::string verify_proof_device(hg_ctx* ctx, const hg_pk* pk, const Witness& w, 
 
 // ---- hg_verify_public_device, hg_claims_settle, hg_instance_mle ----------------------------------------------------------------
 namespace {
-// every way out of an entry drains the stream before the staging buffer, the arena or the caller's arrays are reused (see above)
-struct Drain {
-    hipStream_t st;
-    ~Drain() { (void)hipStreamSynchronize(st); }
-};
+// (every way out of an entry drains the stream before the staging buffer, the arena or the caller's arrays are reused: see above)
 const int64_t* upload_coeffs(hg_ctx* ctx, const int64_t* src, size_t n) {
     int64_t* d = ctx->alloc_n<int64_t>(n);
     hip_check(hipMemcpyAsync(d, src, n * 8, hipMemcpyHostToDevice, ctx->stream), "verifier: upload the instance");

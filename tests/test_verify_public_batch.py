@@ -171,7 +171,7 @@ def members(n, k):
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,k,which,index", [(1024, 1, 0, 0), (1024, 1, 1, 0), (4096, 2, 0, 1), (4096, 2, 1, 0)])
 def test_batch_kernel_parity_with_the_host_form_and_hg_mle_eval(ctx, n, k, which, index):
-    """3. one unit of k_vin_compact_dots with P members: half a tile (1024 words), lo = n-1, two coefficient blocks over four tiles"""
+    """3. one unit of k_vin_dots<true> with P members: half a tile (1024 words), lo = n-1, two coefficient blocks over four tiles"""
     all_ = members(n, k)
     nv = n.bit_length() + (k.bit_length() - 1 if which else 0)
     tables = [(m.table(1) if which else m.table(0)[index * 2 * n:(index + 1) * 2 * n]) for m in all_]

@@ -1,7 +1,7 @@
 """hg_verify_public_batch_bn254: a run of (instance, proof) pairs over bn256::Fr under one key verified from the ciphertext in device
 passes of a group of proofs each (bn254_verify_batch.inc). The single entry is the yardstick: every pair of a batch gets the
 decision, the reason, the claims and the points that hg_verify_public_device_bn254 gives it alone. hg_instance_mle_batch_bn254
-exposes the batch's kernel (k_bn_vin_compact_dots) as one work unit."""
+exposes the batch's kernel (k_bn_vin_dots<true>) as one work unit."""
 import ctypes as C
 import os
 import random
@@ -242,7 +242,7 @@ def ctx():
 @pytest.mark.gpu
 @pytest.mark.parametrize("key,which,index", [((1024, 1), 0, 0), ((1024, 1), 1, 0), ("derived", 1, 0), ((4096, 2), 0, 1), ((4096, 2), 1, 0)])
 def test_batch_kernel_parity_with_the_host_form_and_hg_mle_eval_bn254(ctx, key, which, index):
-    """3. one unit of k_bn_vin_compact_dots with P members: half a tile (1024 words) and lo = n-1; one 2048-word tile that holds both
+    """3. one unit of k_bn_vin_dots<true> with P members: half a tile (1024 words) and lo = n-1; one 2048-word tile that holds both
     blocks of the derived (1024,2) set, the block boundary inside a thread's items; two and four tiles at (4096,2)"""
     params, all_ = members(key)
     n, k = int(params.n), int(params.k)
