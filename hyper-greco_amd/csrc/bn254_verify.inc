@@ -536,7 +536,7 @@ std::string verify_public_device_bn254(hg_ctx* ctx, const hg_pk* pk, const Insta
     D.d_ca = bn_upload_coeffs(ctx, pool, inst.a);
     D.d_cct0 = bn_upload_coeffs(ctx, pool, inst.ct0);
     VerifyPendingT<Fr> v = verify_walk_bn254(D, p, pk->lasso, pk->circuit, proof, len, true);
-    if (!v.reason.empty()) return v.reason;
+    if (!v.live()) return v.reason;
     D.finish();
     std::string why = verify_complete_bn254(v);
     if (why.empty()) for (const auto& cl : v.open) open.push_back(open_claim_bn254(cl));

@@ -231,8 +231,12 @@ typedef VerifyBackendT<E2> VerifyBackend;
 std::string verify_proof_with(VerifyBackend& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode);
 // verify_proof_with in two steps (hg_verify_device_batch): the walk, which records its work with the backend and returns the checks
 // that wait for the backend's results, and - after the caller has finished the backend, with `chain` handed over in modes != 0 -
-// the completion, which runs them ("" = accepted, else the rejection reason). A walk that rejects early sets `reason` and leaves
-// nothing pending; the jobs it recorded up to there are not needed.
+// the completion, which runs them ("" = accepted, else the rejection reason). The host verifier makes a Vanilla node's checks while
+// it reads the proof, the walk only afterwards: a walk that rejects early sets `reason` and keeps the checks of the Vanilla nodes it
+// had reached - one of them failing comes first on the host and is the reason to report - so the jobs recorded up to there are
+// still needed (live()); with none pending the rejection stands as it is. The completion runs the checks in the host verifier's
+// order: those of the Vanilla nodes, then the FFT nodes' final evaluations, then the input claims. Decisions and reasons are then
+// the host verifier's, proof for proof.
 // a claim the public variant of the walk leaves open: input `input` (chain_par! order) evaluates to `value` at `point`
 template <class E> struct OpenClaimT { size_t input; std::vector<E> point; E value; };
 typedef OpenClaimT<E2> OpenClaim;
@@ -241,6 +245,7 @@ template <class E> struct VerifyPendingT {
     std::vector<E> chain;                              // modes != 0: every challenge the walk squeezed, in order
     std::vector<std::function<void()>> deferred;       // the comparisons; they read the backend's tickets
     std::vector<OpenClaimT<E>> open;                   // public_only walks: the claims on the secret inputs, in walk order per ascending input
+    bool live() const { return reason.empty() || !deferred.empty(); }   // the backend's results are needed
 };
 typedef VerifyPendingT<E2> VerifyPending;
 // public_only (hg_verify_public_device): claims on the inputs outside 3 .. 3+k-1 are not handed to the backend but returned in `open`

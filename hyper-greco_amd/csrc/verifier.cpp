@@ -221,7 +221,8 @@ template <class F> struct Verifier {
     bool ext_memcheck = false;  // mode bit 1: gamma, tau stay in E (prover.rs:36-39 truncates them; README.md:108)
     // the table-sized checks elsewhere: see VerifyBackendT in host.hpp
     VerifyBackendT<E>* dev = nullptr;
-    std::vector<std::function<void()>> deferred;   // checks that need a ticket: run after dev->finish()
+    std::vector<std::function<void()>> deferred;   // checks that need a ticket: run after dev->finish(). These are the Vanilla nodes' (the host makes them while it reads)
+    std::vector<std::function<void()>> deferred_fft;   // the FFT nodes' final evaluations (the host queues them behind the walk: run_node_checks)
     std::function<E()> late_claim = nullptr;       // a late-bound term of the NEXT node's initial claim (the output evaluation)
     E read_e() { E v = F::read(bytes); ch.absorb(v); return v; }
     std::vector<E> read_es(size_t n) { std::vector<E> v(n); for (auto& x : v) x = read_e(); return v; }
@@ -430,7 +431,7 @@ template <class F> struct Verifier {
         D->set_x(x_off);
         const int t = D->fft_term();
         const E fin = r.first;
-        deferred.push_back([D, t, u, fin] { if (!F::eq(fin, F::mul(u, D->value(t)))) throw Reject("fft node: final evaluation mismatch"); });
+        deferred_fft.push_back([D, t, u, fin] { if (!F::eq(fin, F::mul(u, D->value(t)))) throw Reject("fft node: final evaluation mismatch"); });
         D->end_node();
         return {{Claim{r.second, u, x_off}}};
     }
@@ -656,8 +657,8 @@ static VerifyPendingT<typename F::E> walk_with_backend(VerifyBackendT<typename F
     typedef typename F::E E;
     typedef typename Verifier<F>::Claim Claim;
     VerifyPendingT<E> out;
+    Verifier<F> V;
     try {
-        Verifier<F> V;
         V.bytes = ProofBytes{proof, len};
         V.ch.set_mode(mode);
         V.ch.seed(seed);
@@ -695,6 +696,7 @@ static VerifyPendingT<typename F::E> walk_with_backend(VerifyBackendT<typename F
             for (size_t i = 0; i < n.preds.size(); i++) for (auto& s : sub[i]) claims[n.preds[i]].push_back(s);
         }
         // izip_eq!(inputs, input_claims): input.evaluate(point) == value (:512-516)
+        std::vector<std::function<void()>> input_checks;
         for (size_t k = 0; k < c.input_ids.size(); k++)
             for (auto& cl : claims[c.input_ids[k]]) {
                 if (cl.off == Verifier<F>::NOPOS) throw Reject("verifier: an input claim point is not a run of the challenge chain");
@@ -704,23 +706,27 @@ static VerifyPendingT<typename F::E> walk_with_backend(VerifyBackendT<typename F
                 }
                 const int t = D->mle_input(k, cl.off, (int)cl.point.size());
                 const E want = cl.value;
-                V.deferred.push_back([D, t, want, k] { if (!F::eq(D->value(t), want)) throw Reject("input claim mismatch at input " + std::to_string(k)); });
+                input_checks.push_back([D, t, want, k] { if (!F::eq(D->value(t), want)) throw Reject("input claim mismatch at input " + std::to_string(k)); });
             }
-        if (mode != 0) out.chain = std::move(V.ch.seq);
-        out.deferred = std::move(V.deferred);   // (the checks capture the backend and their own values, never the walk's state)
+        // (the checks capture the backend and their own values, never the walk's state) In the host verifier's order: see VerifyPendingT
+        out.deferred = std::move(V.deferred);
+        for (auto& f : V.deferred_fft) out.deferred.push_back(std::move(f));
+        for (auto& f : input_checks) out.deferred.push_back(std::move(f));
     } catch (const Reject& r) {
+        // the host verifier would have stopped at a failing check of a Vanilla node it had reached before this point: those stay pending
         out.reason = r.what();
-        out.deferred.clear();
+        out.deferred = std::move(V.deferred);
         out.open.clear();
     }
+    if (mode != 0) out.chain = std::move(V.ch.seq);
     return out;
 }
-// the deferred comparisons, in walk order, once the backend's results are in: "" or the first failure
+// the deferred comparisons, in the host verifier's order, once the backend's results are in: "" or the first failure (the walk's own
+// rejection if none of the checks it kept fails)
 template <class E> static std::string complete_pending(VerifyPendingT<E>& v) {
-    if (!v.reason.empty()) return v.reason;
     try {
         for (auto& f : v.deferred) f();
-        return "";
+        return v.reason;   // ("" unless the walk itself rejected)
     } catch (const Reject& r) {
         return r.what();
     }
@@ -728,7 +734,7 @@ template <class E> static std::string complete_pending(VerifyPendingT<E>& v) {
 template <class F>
 static std::string verify_with_backend(VerifyBackendT<typename F::E>& dev, const Params& p, const LassoPlan& lp, const HCircuit& c, const uint8_t* proof, size_t len, int mode) {
     VerifyPendingT<typename F::E> v = walk_with_backend<F>(dev, p, lp, c, proof, len, mode);
-    if (!v.reason.empty()) return v.reason;
+    if (!v.live()) return v.reason;
     if (mode != 0) dev.set_chain(v.chain);
     dev.finish();
     return complete_pending(v);

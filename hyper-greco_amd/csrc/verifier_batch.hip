@@ -416,7 +416,7 @@ void verify_batch_run(hg_ctx* ctx, const hg_pk* pk, const BatchSrc& src, const s
         ctx->arena_reset();
         // mode 0 reads the context's fixed chain, modes 1-3 the concatenation of the proofs' own chains
         for (auto& x : W) {
-            if (!x.pend.reason.empty()) continue;
+            if (!x.pend.live()) continue;
             if (mode != 0 && x.rec->chain_need > x.pend.chain.size())
                 throw Error(who + ": proof " + std::to_string(x.idx) + ": verifier: a job reads past the challenges the walk squeezed");
             if (mode == 0 && x.rec->chain_need > ctx->chal_e) throw Error(who + ": proof " + std::to_string(x.idx) + ": verifier: a job reads past the fixed chain");

@@ -409,7 +409,7 @@ std::string verify_public_device(hg_ctx* ctx, const hg_pk* pk, const Instance& i
         seed = bound_seed(p.raw, mode, digest, root);
     }
     VerifyPending v = verify_walk(D, p, pk->lasso, pk->circuit, proof, len, mode, true, root ? &seed : nullptr);
-    if (!v.reason.empty()) return v.reason;
+    if (!v.live()) return v.reason;
     if (mode != 0) D.set_chain(v.chain);
     D.finish();
     std::string why = verify_complete(v);

@@ -223,8 +223,8 @@ template <class F> struct MergedGroup {
     int nslot = 0;
 };
 
-// Merges the records of a group's proofs, in their order; a proof the walk rejected (pend.reason) contributes nothing - its recorded
-// prefix is not launched. Identical eq tables, constant sums, phase-1 gathers, DFT-row tables and their dot products become one job
+// Merges the records of a group's proofs, in their order; a proof the walk rejected with no check pending (!pend.live()) contributes
+// nothing - its recorded prefix is not launched; one that keeps the checks of the Vanilla nodes it had reached contributes its prefix. Identical eq tables, constant sums, phase-1 gathers, DFT-row tables and their dot products become one job
 // and one slot. Phase-2 gathers and their dots (they read the proof's own phase-1 evaluations) and the input jobs (they read the
 // proof's own witness or instance) are never shared. own_chains: the jobs read the concatenation of the proofs' own chains
 // (pend.chain), each proof's offsets shifted by its base - so two proofs share nothing; else every proof reads one chain at its
@@ -236,7 +236,7 @@ template <class F> MergedGroup<F> merge_group(std::vector<Walked<F>>& W, bool ow
     auto new_slot = [&] { return M.nslot++; };
     for (size_t w = 0; w < W.size(); w++) {
         Walked<F>& x = W[w];
-        if (!x.pend.reason.empty()) continue;
+        if (!x.pend.live()) continue;
         const Rec& R = *x.rec;
         size_t base = 0;
         if (own_chains) {
@@ -377,7 +377,7 @@ template <class F, class Res, class Done> void complete_group(std::vector<Walked
 #pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)W.size()))
     for (long long q = 0; q < (long long)W.size(); q++) {
         Walked<F>& x = W[q];
-        if (x.pend.reason.empty()) {
+        if (x.pend.live()) {
             x.rec->res.resize(x.gslot.size());
             for (size_t t = 0; t < x.gslot.size(); t++) x.rec->res[t] = res(x.gslot[t]);
         }

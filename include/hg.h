@@ -199,22 +199,26 @@ int hg_prove_encryptions(hg_ctx* ctx, const hg_pk* pk, const int64_t* const* s, 
  *   supplies the public inputs and ct0is. Returns 0 = accepted, 1 = rejected (reason via hg_last_error), < 0 = error.
  *   Works with a host-only key (hg_setup(NULL, ..)).
  *   NOTE: "accepted" means what the reference's verifier means, which is NOT soundness: the challenges are a fixed Keccak chain
- *   independent of the proof bytes, gamma / tau are truncated to one base limb, the collation sum-check's final evaluation and
+ *   independent of the proof bytes, gamma / tau are truncated to one base limb, the collation sum-check's final evaluation, the
+ *   final evaluation of every grand-product layer's sum-check (verify_grand_product discards it and keeps the point) and
  *   the multiset relation init * write == read * final between the two grand products are never checked, trailing bytes are
- *   ignored. hg_verify_mode(.., 3, ..) closes the first two. */
+ *   ignored. hg_verify_mode(.., 3, ..) closes the first two. Every single element of the stream is bound all the same: a proof
+ *   with one element changed is rejected in every mode (tests/test_proof_binding.py). */
 int hg_verify(const hg_pk* pk, const hg_witness* w, const uint8_t* proof, size_t len);
 /* The same check with the table-sized work on the device [REF sk_encryption_circuit.rs:462-517; lasso/src/memory_checking/verifier.rs:
  * 130-176]: the host parses the proof and checks the round polynomials and the Lasso scalars; the eq tables, the wiring-predicate
  * sums of the Vanilla nodes, the DFT rows of the FFT nodes and the MLE evaluations of the public inputs run as kernels (one stream,
- * one synchronisation). Same return values and the same accept / reject decisions as hg_verify; Goldilocks, mode 0 (the protocol
- * modes: hg_verify_device_mode). */
+ * one synchronisation). Same return values, the same accept / reject decisions and the same reasons as hg_verify (a proof rejected
+ * while it is read still has the checks of the Vanilla nodes read so far evaluated: hg_verify makes those first); Goldilocks, mode 0
+ * (the protocol modes: hg_verify_device_mode). */
 int hg_verify_device(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, const uint8_t* proof, size_t len);
 /* hg_verify_device in a protocol mode (the mode bits of hg_prove_mode / hg_verify_mode below, 0 to 3), Goldilocks only. Mode 0 is
  * hg_verify_device; modes 1 to 3 make the same accept / reject decision as hg_verify_mode in the same mode. The walk records the
  * challenges it squeezes (with bit 1 they depend on the proof bytes) and the kernels read that record, staged into the context's
  * arena; the fixed chain the mode-0 prover reads is left as it is. Of the gaps listed at hg_verify, bit 1 closes the first (the
  * challenges bind every element read), bit 2 the second (gamma, tau in E); mode 3 closes both. The collation sum-check's final
- * evaluation, the multiset relation and trailing bytes stay unchecked in every mode. Needs a device context and a device key
+ * evaluation, the final evaluation of every grand-product layer's sum-check, the multiset relation and trailing bytes stay
+ * unchecked in every mode. Needs a device context and a device key
  * (hg_setup(ctx, ..)). Returns 0 accept, 1 reject (reason in hg_last_error), -1 error: a null argument, a host-only key, or a mode
  * outside 0..3. */
 int hg_verify_device_mode(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, int mode, const uint8_t* proof, size_t len);

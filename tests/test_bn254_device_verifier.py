@@ -99,15 +99,13 @@ def test_device_verifier_bn254_agrees_with_the_host_verifier(ctx, n, k):
         muts += [(rng.randrange(nel), None), (32 * rng.randrange(nel) + 31, 1 << rng.randrange(8)),
                  (32 * rng.randrange(nel), 0x80), (32 * (nel - 1), 0xff)]
     assert len(muts) >= (8 if n == 32768 else 14)
-    rejected = 0
-    for pos, mask in muts:
+    for pos, mask in muts:   # (every element of the stream is bound: tests/test_proof_binding.py)
         bad = bytearray(proof)
         if mask is None:
             bad[32 * pos] = 0xff
         else:
             bad[pos] ^= mask
-        rejected += not _same_decision(ctx, pk, w, bytes(bad))
-    assert rejected >= len(muts) // 2, (rejected, len(muts))
+        assert not _same_decision(ctx, pk, w, bytes(bad)), (pos, mask)
     assert not _same_decision(ctx, pk, w, proof[:len(proof) // 2])   # truncated
     _same_decision(ctx, pk, w, proof[:-32])
     assert _same_decision(ctx, pk, w, proof + bytes(32))               # a trailing zero element is ignored, as by the host verifier

@@ -137,8 +137,7 @@ def test_batch_matches_the_single_proof_verifier(ctx, n, k):
         (ws[2], ps[2])]
     got = _batch_matches_singles(ctx, pk, [w for w, _ in pairs], [p for _, p in pairs])
     assert got[0] == got[1] == got[-1] == (True, "")
-    assert not got[7][0] and not got[9][0]
-    assert sum(not ok for ok, _ in got) >= 6, got
+    assert [i for i, (ok, _) in enumerate(got) if ok] == [0, 1, 8, 10], got   # the honest pairs and the trailing element; every flip is rejected
     pk.free()
 
 

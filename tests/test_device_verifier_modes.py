@@ -126,12 +126,10 @@ def test_device_verifier_in_a_protocol_mode_agrees_with_hg_verify_mode(ctx, n, k
     # tampering
     flips = _flips(proof, n)
     assert len(flips) >= 12
-    rejected = 0
-    for pos, mask in flips:
+    for pos, mask in flips:   # (every element of the stream is bound: tests/test_proof_binding.py)
         bad = bytearray(proof)
         bad[pos] ^= mask
-        rejected += not _same_decision(ctx, pk, w, bytes(bad), mode)
-    assert rejected >= len(flips) // 2, (rejected, len(flips))
+        assert not _same_decision(ctx, pk, w, bytes(bad), mode), (pos, mask)
     w2 = hg.Witness.synthetic(bfv.params, 0x77 + n + mode)
     assert not _same_decision(ctx, pk, w2, proof, mode)                       # another witness
     assert not _same_decision(ctx, pk, w, proof[:len(proof) // 2], mode)      # truncated
@@ -155,14 +153,10 @@ def test_mode_0_through_the_new_entry_is_hg_verify_device(ctx, n, k):
     w = hg.Witness.synthetic(bfv.params, 0x300 + n)
     proof, _ = bfv.prove(ctx, pk, w)
     assert _dev(ctx, pk, w, proof, 0) and hg.verify_device(ctx, pk, w, proof) == (True, "")
-    rejected = 0
     for pos, mask in _flips(proof, n):
         bad = bytearray(proof)
         bad[pos] ^= mask
-        d0 = hg.verify_device(ctx, pk, w, bytes(bad))[0]
-        assert _dev(ctx, pk, w, bytes(bad), 0) == d0, pos
-        rejected += not d0
-    assert rejected >= 7
+        assert not hg.verify_device(ctx, pk, w, bytes(bad))[0] and not _dev(ctx, pk, w, bytes(bad), 0), pos
     w2 = hg.Witness.synthetic(bfv.params, 0x301 + n)
     assert not _dev(ctx, pk, w2, proof, 0) and not hg.verify_device(ctx, pk, w2, proof)[0]
     pk.free()
