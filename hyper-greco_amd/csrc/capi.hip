@@ -1007,6 +1007,10 @@ int hg_set_option(hg_ctx* ctx, const char* name, int64_t value) {
         if (ctx->gp_claims_device != (value != 0)) { prove_cache_drop(ctx); ctx->walk_counts.clear(); }
         ctx->gp_claims_device = value != 0;
     }
+    else if (n == "graph_const_tables") {   // (a cached launch graph was recorded with or without those launches)
+        if (ctx->graph_const_tables != (value != 0)) { prove_cache_drop(ctx); ctx->walk_counts.clear(); }
+        ctx->graph_const_tables = value != 0;
+    }
     else if (n == "verify_batch_group") { if (value < 0) throw Error("hg_set_option: verify_batch_group must be >= 0"); ctx->verify_batch_group = value; }
     else if (n == "bound_batch_slice") { if (value < 0) throw Error("hg_set_option: bound_batch_slice must be >= 0"); ctx->bound_batch_slice = value; }
     else throw Error("hg_set_option: unknown option " + n);

@@ -3296,6 +3296,7 @@ void fft_jobs(hipStream_t st, const FftJob* jobs, int njobs, int max_L, int max_
         k_fft_tab<<<dim3((unsigned)std::min<size_t>((tab_stride + TPB - 1) / TPB, 64), njobs * max_claims), TPB, 0, st>>>(jobs, chal, tab, tab_stride, max_claims);
     k_fft_jobs<<<dim3((unsigned)std::min<size_t>((N + TPB - 1) / TPB, 1024), njobs), TPB, 0, st>>>(jobs, chal, tab, tab_stride, max_claims);
 }
+int fft_jobs_launches(int max_L) { return max_L > FFT_SPLIT ? 2 : 1; }
 // Libra bookkeeping tables of many (node, input) pairs in one launch (grid.y = job)
 __global__ __launch_bounds__(TPB) void k_gather_jobs(const GatherJob* __restrict__ jobs) {
     const GatherJob& J = jobs[blockIdx.y];

@@ -403,6 +403,7 @@ int vanilla_const_sum(hipStream_t st, const u32* gate, const u64* coef, size_t n
 struct FftJob { E2* out; const u64* W; u64 scale; int L; ClaimSet cs; };
 // `tab`: scratch of njobs * max_claims * 2^(max_L - 4) E2 (the high-bit factor tables)
 void fft_jobs(hipStream_t st, const FftJob* jobs, int njobs, int max_L, int max_claims, const E2* chal, E2* tab);
+int fft_jobs_launches(int max_L);   // kernels one fft_jobs call launches (the factor tables have a launch of their own)
 void powers_table(hipStream_t st, u64* W, u64 w, size_t n);  // W[i] = w^i
 
 // ---- circuit evaluation (witness generation): one Vanilla node, gate-major wiring -------------------------

@@ -1193,6 +1193,11 @@ static std::shared_ptr<ProveCache> prove_capture(hg_ctx* ctx, const hg_pk* pk, c
         C->P.reset(new Prover(ctx, pk, rank, world));
         C->P->d_vals = v->d_vals;
         C->P->defer_uploads = true;   // (descriptor uploads are not graph nodes: Prover::upload)
+        if (world == 1 && ctx->graph_const_tables) {   // ... and neither are the launches that build challenge-only tables (Prover::issue_const)
+            C->P->hoist_consts = true;
+            C->P->key_allocs.assign(pk->owned.begin(), pk->owned.end());
+            std::sort(C->P->key_allocs.begin(), C->P->key_allocs.end(), std::less<const void*>());
+        }
         if (hg_debug("fail_capture")) throw Error("launch-graph capture failed (forced by HG_DEBUG=fail_capture)");
         enqueue_prove(ctx, pk, v, C->P.get(), world, false);   // (the exchange is not part of the graph: prove_from_cache)
         capturing = false;
@@ -1210,8 +1215,24 @@ static std::shared_ptr<ProveCache> prove_capture(hg_ctx* ctx, const hg_pk* pk, c
     restore();
     for (auto& u : C->P->deferred_uploads)   // once, ahead of the first replay on the same stream; their targets live in the private arena
         hip_check(hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, ctx->stream), "descriptor upload");
+    for (auto& f : C->P->hoisted) f(ctx->stream);   // the challenge-only tables: once, in recorded order, behind the descriptors they read
+    hip_check(hipGetLastError(), "challenge-only tables");
     hip_check(hipStreamSynchronize(ctx->stream), "descriptor uploads");   // (the pinned staging they came from is reused by the next prove)
     C->P->deferred_uploads.clear();
+    C->P->hoisted.clear();
+    C->P->hoist_consts = false;
+    if (hg_debug("consts")) {   // (a token of its own: the lines of HG_DEBUG=plan alone are read one by one)
+        size_t nn = 0, kept = 0;
+        hip_check(hipGraphGetNodes(C->graph, nullptr, &nn), "hipGraphGetNodes");
+        std::vector<hipGraphNode_t> nodes(nn);
+        if (nn) hip_check(hipGraphGetNodes(C->graph, nodes.data(), &nn), "hipGraphGetNodes");
+        for (size_t i = 0; i < nn; i++) {
+            hipGraphNodeType ty;
+            hip_check(hipGraphNodeGetType(nodes[i], &ty), "hipGraphNodeGetType");
+            kept += ty == hipGraphNodeTypeKernel;
+        }
+        fprintf(stderr, "[hg plan] consts hoisted=%d kept=%zu bytes=%zu split=%d\n", C->P->n_hoisted, kept, C->P->hoisted_bytes, C->P->n_split);
+    }
     // (Re-issuing the captured nodes from the library on two real streams - kernel parameters and dependencies read back from the
     // graph - was measured against hipGraphLaunch: 3.50-3.59 ms vs 3.52-3.64 ms of GPU time and 0.53 vs 0.40 ms of host time per
     // prove. No gain, not kept: the serialised look of a replay in a rocprofv3 trace is a profiling artefact.)

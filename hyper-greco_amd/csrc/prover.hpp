@@ -79,7 +79,8 @@ struct hg_ctx {
     bool one_stream = false;  // keep every launch on `stream` (per-kernel timings without cross-stream interference)
     int mode = 0;             // protocol mode of the next proves: bit 0 absorbing transcript, bit 1 extension-field memory checking
     bool gp_claims_device = true;   // grand-product layers: unscaling, layer_down and the next layer's claim in the tail kernel (GpClaimEp); 0: in the transcript replay
-    int64_t verify_batch_group = 0;   // hg_verify_device_batch, hg_verify_public_batch, hg_pcs_verify_device_batch and their _bn254 forms: most proofs or openings per device pass (0: sized from the arena budget)
+    bool graph_const_tables = true; // launch graphs: tables of the challenges and the key alone are built once after the capture, not in every replay (prover_sumcheck.inc: issue_const); 0: every launch recorded
+    int64_t verify_batch_group = 0;  // hg_verify_device_batch, hg_verify_public_batch, hg_pcs_verify_device_batch and their _bn254 forms: most proofs or openings per device pass (0: sized from the arena budget)
     int64_t bound_batch_slice = 0;    // hg_verify_public_bound_batch, hg_instance_digest_group: members of a group staged and digested at a time (0: what fits in 32 MiB of instance words, at least one)
     void* verify_batch = nullptr;     // verifier_batch.hip: VerifyBatchBufs (pinned and device input sets, upload stream), freed with the context
     // bump arena: chunks are kept across proves, offsets reset per prove

@@ -447,7 +447,7 @@
         auto do_claim = [&] {
             E2* ab = (lean_e && !lasso_tables()) ? eq_prep_now(nu, r_off) : nullptr;
             claim_ab = ab != nullptr;
-            if (!ab) eq_now(eq_table(), nu, r_off);
+            if (!ab) eq_now(eq_table(), nu, r_off, nullptr, !use_aux);   // (one stream: the opening point's table takes the buffer later)
             int grid = lean_e ? dev::lasso_claim_in(st, L, ab ? ab : eq, d_input, own_mask, partials, ab != nullptr)
                               : dev::lasso_claim(st, L, eq, ep, ep_rows_own, partials);  // sharded: this rank's memories only (partial sum)
             reduce(grid, 1, claim_slot);
@@ -826,7 +826,7 @@
                 if (open_ab) eqx_v = eq_prep_now(nu, p1);
                 else {
                     eqx_v = use_aux ? ctx->alloc_n<E2>(N) : eq_table();  // (one stream: the eq(r,.) table is dead by now)
-                    eq_now(eqx_v, nu, p1);
+                    eq_now(eqx_v, nu, p1, nullptr, !use_aux);
                 }
                 eq_now(eqy_v, 16, p2);
             });

@@ -140,14 +140,20 @@
             else if (own) T = ctx->alloc_n<E2>(SR);
             gt.lin = nd.lin[i];
             gt.mul = nd.mulL[i];
+            // (only a mul part reads the node inputs: a job without one names none, and its table depends on the challenges alone)
+            const bool mul_part = gt.mul.ptr != nullptr;
             if (own && use_seg && sg.alias) {
             } else if (own && use_seg && sg.d) {
                 dev::GatherSegJob sj;
                 memset(&sj, 0, sizeof(sj));
                 sj.segs = sg.d; sj.nseg = sg.nseg; sj.eqc = eqc; sj.log2_S = n.log2_sub_in; sj.log2_G = n.log2_sub_out; sj.log2_R = n.log2_reps; sj.T = T;
-                for (int q = 0; q < n.arity; q++) sj.in_vals[q] = gt.in_vals[q];
+                if (mul_part) for (int q = 0; q < n.arity; q++) sj.in_vals[q] = gt.in_vals[q];
                 gather_seg_queue.push_back(sj);
-            } else if (own) gather_queue.push_back(dev::GatherJob{gt, eqc, n.log2_sub_in, n.log2_sub_out, n.log2_reps, T});
+            } else if (own) {
+                dev::GatherT g = gt;
+                if (!mul_part) memset(g.in_vals, 0, sizeof(g.in_vals));
+                gather_queue.push_back(dev::GatherJob{g, eqc, n.log2_sub_in, n.log2_sub_out, n.log2_reps, T});
+            }
             a.push_back(d_vals[n.preds[i]]);
             b.push_back(T);
             fa.push_back(d_res() + u_base + i);

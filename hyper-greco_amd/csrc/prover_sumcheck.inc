@@ -80,6 +80,13 @@
     void flush_stride() {
         if (st_jobs.empty()) return;
         const int nj = (int)st_jobs.size();
+        if (hoist_consts)   // (as in flush_prodsum: the rounds stay recorded)
+            for (auto& J : st_jobs) {
+                const size_t N = (size_t)1 << J.nvars;
+                kept_writes(crange(J.buf[0], (size_t)J.ntab * std::max<size_t>(N / 2, 1)));
+                kept_writes(crange(J.buf[1], (size_t)J.ntab * std::max<size_t>(N / 4, 1)));
+                kept_writes(crange(J.final_out, (size_t)J.ntab));
+            }
         // launch plan: (kind, base? | fused pair?, h_log2 | tail) -> items (job, where the round reads and writes).
         // Folded tables ping-pong between the job's two buffers; the host tracks where each job's live tables are.
         constexpr int fuse_min_h = 15;   // fused pairs of rounds from half = 2^15 up (13 until the slot form: 1.96-1.99 against 1.99-2.01 ms; round 5: 13 / 11 / 9 = 1.864 / 1.905 / 1.980 against 1.831)
@@ -503,6 +510,17 @@
         for (auto& kv : ps_queue) { jobs.insert(jobs.end(), kv.second.begin(), kv.second.end()); kv.second.clear(); }
         if (jobs.empty()) return;
         const int nj = (int)jobs.size();
+        if (hoist_consts)   // the rounds stay recorded: none of their fold buffers may be a table that was built once
+            for (auto& J : jobs) {
+                const size_t N = (size_t)1 << J.nvars;
+                for (int q = 0; q < 2; q++) {
+                    const size_t len = std::max<size_t>(N >> (q + 1), 1);
+                    kept_writes(crange(J.bufa[q], (size_t)J.npairs * len));
+                    kept_writes(crange(J.bufb[q], (size_t)J.npairs * len));
+                    kept_writes(crange(J.bufA[q], len));
+                }
+                kept_writes(crange(J.eqA0, N));
+            }
         if (hg_debug("eq")) {
             int ne = 0; size_t ee = 0, et = 0;
             for (auto& J : jobs) { const size_t e = (size_t)J.npairs << J.nvars; et += e; if (J.eq_n) { ne++; ee += e; } }
@@ -648,6 +666,54 @@
         if (defer_uploads) { deferred_uploads.push_back(Upload{dst, staged, bytes}); return; }
         hip_check(hipMemcpyAsync(dst, staged, bytes, hipMemcpyHostToDevice, st), what);
     }
+    // Challenge-only tables (DESIGN.md 3.7). In mode 0 the challenges are the fixed chain, so a table built from the chain and the
+    // key's wiring alone is the same for every witness proven under the key. A prove that is being recorded into a launch graph does
+    // not record a launch that reads nothing else and writes such tables only: it is kept as a closure and runs ONCE after the
+    // capture (prove_capture), behind the descriptor uploads it reads; its tables stay in the graph's private arena, a pure bump
+    // allocation. Whether a launch qualifies is decided from its inputs (const_src), and the address ranges written by hoisted
+    // launches are kept: a launch that stays in the graph and writes into one of them ends the capture (plain launches then).
+    bool hoist_consts = false;
+    struct ConstRange { const char* lo; const char* hi; };
+    std::vector<std::function<void(hipStream_t)>> hoisted;
+    std::vector<ConstRange> hoisted_ranges, kept_ranges;   // kept: tables written by launches of the same kinds that stay recorded
+    std::vector<const void*> key_allocs;  // sorted base addresses of the key's device memory (set with hoist_consts)
+    int n_hoisted = 0, n_split = 0;        // launches hoisted; queues flushed as a hoisted and a kept launch
+    size_t hoisted_bytes = 0;
+    template <typename T> static ConstRange crange(const T* p, size_t n) {
+        return ConstRange{reinterpret_cast<const char*>(p), reinterpret_cast<const char*>(p) + n * sizeof(T)};
+    }
+    bool in_hoisted(ConstRange r) const {
+        for (const ConstRange& h : hoisted_ranges) if (r.lo < h.hi && h.lo < r.hi) return true;
+        return false;
+    }
+    // a buffer a hoisted launch may read: absent, the key's, or a table written by an earlier hoisted launch
+    bool const_src(const void* p) const {
+        if (!p) return true;
+        if (std::binary_search(key_allocs.begin(), key_allocs.end(), p, std::less<const void*>())) return true;
+        const char* c = static_cast<const char*>(p);
+        return in_hoisted(ConstRange{c, c + 1});
+    }
+    void kept_writes(ConstRange r) const {
+        if (hoist_consts && r.lo && r.lo < r.hi && in_hoisted(r)) throw Error("launch graph: a recorded launch writes a table that was built once");
+    }
+    // `fn(stream)` issues `nlaunch` kernels that write `writes`; constant: every buffer they read passes const_src
+    template <typename Fn> void issue_const(bool constant, const std::vector<ConstRange>& writes, int nlaunch, Fn fn) {
+        if (!(hoist_consts && constant)) {
+            for (const ConstRange& w : writes) { kept_writes(w); if (hoist_consts && w.lo && w.lo < w.hi) kept_ranges.push_back(w); }
+            fn(st);
+            return;
+        }
+        for (const ConstRange& w : writes) {
+            if (!w.lo || w.lo >= w.hi) continue;
+            bool clash = in_hoisted(w);
+            for (const ConstRange& k : kept_ranges) clash = clash || (w.lo < k.hi && k.lo < w.hi);
+            if (clash) throw Error("launch graph: two launches build one challenge-only table");
+            hoisted_ranges.push_back(w);
+            hoisted_bytes += (size_t)(w.hi - w.lo);
+        }
+        hoisted.push_back(fn);
+        n_hoisted += nlaunch;
+    }
     void* stage(const void* src, size_t bytes) {
         size_t need = (bytes + 63) & ~(size_t)63;
         if (ctx->stage_used + need > ctx->stage_cap) throw Error("staging buffer exhausted");
@@ -713,7 +779,13 @@
     std::vector<dev::GatherBJob> gatherB_queue;
     std::vector<dev::FftJob> fft_queue;
 
-    void eq_now(E2* out, int n, size_t point_off, const E2* point_dev = nullptr) {  // single table, launched in place
+    // tables an eq job writes: its factor tables and, with `fill`, the table itself
+    static void eq_writes(const dev::EqJob& J, bool fill, std::vector<ConstRange>& wr) {
+        if (J.ab) wr.push_back(crange(J.ab, (size_t)J.cs.n * dev::eq_ab_entries(J.n)));
+        if (fill && J.out) wr.push_back(crange(J.out, (size_t)1 << J.n));
+    }
+    // `reused`: another launch of this prove fills the same buffer later (never built once)
+    void eq_now(E2* out, int n, size_t point_off, const E2* point_dev = nullptr, bool reused = false) {  // single table, launched in place
         dev::EqJob J;
         memset(&J, 0, sizeof(J));
         J.out = out; J.n = n; J.point_dev = point_dev;
@@ -723,9 +795,12 @@
         if (two) { J.ab = ctx->alloc_n<E2>(dev::eq_ab_entries(n)); grid = dev::eq_ab_plan(&J, 1); }
         dev::EqJob* d = ctx->alloc_n<dev::EqJob>(1);
         upload(d, &J, sizeof(J), "upload eq job");
+        std::vector<ConstRange> wr;
+        eq_writes(J, true, wr);
+        const E2* chal = ctx->d_chal;
         ctx->prof_begin(cls_aux, 16.0 * ((size_t)1 << n));
-        if (two) dev::eq_jobs_ab(st, d, 1, grid, ctx->d_chal);
-        else dev::eq_jobs(st, d, 1, n, ctx->d_chal);
+        if (two) issue_const(!point_dev && !reused, wr, 2, [d, grid, chal](hipStream_t s) { dev::eq_jobs_ab(s, d, 1, grid, chal); });
+        else issue_const(!point_dev && !reused, wr, 1, [d, n, chal](hipStream_t s) { dev::eq_jobs(s, d, 1, n, chal); });
         ctx->prof_end();
     }
     // The factor tables of the same table alone (k_eq_prep, no fill): for a table with ONE reader that forms A[j & 255] * B[j >> 8] per
@@ -740,8 +815,11 @@
         const dev::EqAbGrid grid = dev::eq_ab_plan(&J, 1);
         dev::EqJob* d = ctx->alloc_n<dev::EqJob>(1);
         upload(d, &J, sizeof(J), "upload eq job");
+        std::vector<ConstRange> wr;
+        eq_writes(J, false, wr);
+        const E2* chal = ctx->d_chal;
         ctx->prof_begin(cls_aux, 16.0 * dev::eq_ab_entries(n), 16.0 * ((size_t)1 << n));   // (reference model: the table is written)
-        dev::eq_jobs_prep(st, d, 1, grid, ctx->d_chal);
+        issue_const(true, wr, 1, [d, grid, chal](hipStream_t s) { dev::eq_jobs_prep(s, d, 1, grid, chal); });
         ctx->prof_end();
         return J.ab;
     }
@@ -771,56 +849,117 @@
             eq_queue.push_back(J);
         }
         const int nc = cs.n;
-        eq_post.push_back([this, out, tmp, nc, N] { dev::sum_tables(st, out, tmp, nc, N); });
+        eq_post.push_back([this, out, tmp, nc, N] {
+            issue_const(const_src(tmp), {crange(out, N)}, 1, [out, tmp, nc, N](hipStream_t s) { dev::sum_tables(s, out, tmp, nc, N); });
+        });
     }
-    template <typename JobT, typename LaunchFn>
-    void flush_jobs(std::vector<JobT>& q, int cls, double bytes, LaunchFn launch) {
-        if (q.empty()) return;
+    template <typename JobT> JobT* put_jobs(const std::vector<JobT>& q) {
         JobT* d = ctx->alloc_n<JobT>(q.size());
         upload(d, q.data(), q.size() * sizeof(JobT), "upload jobs");
-        ctx->prof_begin(cls, bytes);
-        launch(d, (int)q.size());
-        ctx->prof_end();
+        return d;
+    }
+    // Flushes a queue of table-building jobs: each(part, constant) plans, uploads and issues one part. While a launch graph is
+    // recorded, the jobs that read challenge-only inputs (is_const) are one part, built once, and the others stay recorded.
+    template <typename JobT, typename Pred, typename Each>
+    void flush_jobs(std::vector<JobT>& q, Pred is_const, Each each) {
+        if (q.empty()) return;
+        std::vector<JobT> c, k;
+        if (hoist_consts) for (const JobT& J : q) (is_const(J) ? c : k).push_back(J);
+        else k.swap(q);
         q.clear();
+        if (!c.empty() && !k.empty()) n_split++;
+        if (!c.empty()) each(c, true);
+        if (!k.empty()) each(k, false);
+    }
+    static bool no_in_vals(const u64* const* in_vals) {
+        for (int q = 0; q < dev::PS_MAX_PAIRS; q++) if (in_vals[q]) return false;
+        return true;
     }
     void flush_bookkeeping() {
-        if (!eqpt_queue.empty()) {   // factor tables of the eq-factored jobs' points
+        const E2* chal = ctx->d_chal;
+        // factor tables of the eq-factored jobs' points: the chain alone
+        flush_jobs(eqpt_queue, [](const dev::PsEqPoint&) { return true; }, [&](std::vector<dev::PsEqPoint>& part, bool c) {
             double pb = 0;
-            for (auto& p : eqpt_queue) pb += 16.0 * (dev::ps_eq_lo_entries(p.nvars) + dev::ps_eq_suf_entries(p.nvars));
-            flush_jobs(eqpt_queue, cls_aux, pb, [&](dev::PsEqPoint* d, int np) { dev::ps_eq_prep(st, d, np, ctx->d_chal); });
-        }
-        int max_n = 0; double eb = 0;
-        for (auto& J : eq_queue) { max_n = std::max(max_n, J.n); eb += 16.0 * ((size_t)1 << J.n); }
-        {   // jobs of the two-launch form first (queue_eq gives every job of a prove the same form)
-            std::vector<dev::EqJob> ab, old;
-            for (auto& J : eq_queue) (J.ab ? ab : old).push_back(J);
-            if (!ab.empty() && !old.empty()) throw Error("eq tables: mixed job forms in one batch");
-            if (!ab.empty()) {
-                const dev::EqAbGrid grid = dev::eq_ab_plan(ab.data(), (int)ab.size());
-                flush_jobs(ab, cls_aux, eb, [&](dev::EqJob* d, int nj) { dev::eq_jobs_ab(st, d, nj, grid, ctx->d_chal); });
-                eq_queue.clear();
+            std::vector<ConstRange> wr;
+            for (auto& p : part) {
+                pb += 16.0 * (dev::ps_eq_lo_entries(p.nvars) + dev::ps_eq_suf_entries(p.nvars));
+                wr.push_back(crange(p.lo, dev::ps_eq_lo_entries(p.nvars)));
+                wr.push_back(crange(p.suf, dev::ps_eq_suf_entries(p.nvars)));
             }
-        }
-        flush_jobs(eq_queue, cls_aux, eb, [&](dev::EqJob* d, int nj) { dev::eq_jobs(st, d, nj, max_n, ctx->d_chal); });
+            dev::PsEqPoint* d = put_jobs(part);
+            const int np = (int)part.size();
+            ctx->prof_begin(cls_aux, pb);
+            issue_const(c, wr, 1, [d, np, chal](hipStream_t s) { dev::ps_eq_prep(s, d, np, chal); });
+            ctx->prof_end();
+        });
+        // eq tables: a point in the chain (point_dev null) and nothing else
+        flush_jobs(eq_queue, [](const dev::EqJob& J) { return J.point_dev == nullptr; }, [&](std::vector<dev::EqJob>& part, bool c) {
+            int max_n = 0; double eb = 0;
+            bool ab = false, old = false;   // (queue_eq gives every job of a prove the same form)
+            std::vector<ConstRange> wr;
+            for (auto& J : part) { max_n = std::max(max_n, J.n); eb += 16.0 * ((size_t)1 << J.n); (J.ab ? ab : old) = true; eq_writes(J, true, wr); }
+            if (ab && old) throw Error("eq tables: mixed job forms in one batch");
+            const int nj = (int)part.size();
+            dev::EqAbGrid grid{0, 0};
+            if (ab) grid = dev::eq_ab_plan(part.data(), nj);
+            dev::EqJob* d = put_jobs(part);
+            ctx->prof_begin(cls_aux, eb);
+            if (ab) issue_const(c, wr, 2, [d, nj, grid, chal](hipStream_t s) { dev::eq_jobs_ab(s, d, nj, grid, chal); });
+            else issue_const(c, wr, 1, [d, nj, max_n, chal](hipStream_t s) { dev::eq_jobs(s, d, nj, max_n, chal); });
+            ctx->prof_end();
+        });
         for (auto& f : eq_post) f();
         eq_post.clear();
         for (auto& f : after_eq) f();
         after_eq.clear();
-        size_t max_total = 0; double gb = 0;
-        for (auto& J : gather_queue) { size_t t = (size_t)1 << (J.log2_S + J.log2_R); max_total = std::max(max_total, t); gb += 24.0 * t; }
-        flush_jobs(gather_queue, cls_gather, gb, [&](dev::GatherJob* d, int nj) { dev::gather_jobs(st, d, nj, max_total); });
-        if (!gather_seg_queue.empty()) {
+        // Libra phase-1 tables: the key's wiring and the node's eq table; a mul part reads the node inputs (in_vals)
+        flush_jobs(gather_queue, [&](const dev::GatherJob& J) { return no_in_vals(J.g.in_vals) && const_src(J.eqc) && const_src(J.g.lin.ptr) && const_src(J.g.mul.ptr); },
+                   [&](std::vector<dev::GatherJob>& part, bool c) {
+            size_t max_total = 0; double gb = 0;
+            std::vector<ConstRange> wr;
+            for (auto& J : part) { size_t t = (size_t)1 << (J.log2_S + J.log2_R); max_total = std::max(max_total, t); gb += 24.0 * t; wr.push_back(crange(J.T, t)); }
+            dev::GatherJob* d = put_jobs(part);
+            const int nj = (int)part.size();
+            ctx->prof_begin(cls_gather, gb);
+            issue_const(c, wr, 1, [d, nj, max_total](hipStream_t s) { dev::gather_jobs(s, d, nj, max_total); });
+            ctx->prof_end();
+        });
+        flush_jobs(gather_seg_queue, [&](const dev::GatherSegJob& J) { return no_in_vals(J.in_vals) && const_src(J.eqc) && const_src(J.segs); },
+                   [&](std::vector<dev::GatherSegJob>& part, bool c) {
             double sb = 0;
-            for (auto& J : gather_seg_queue) sb += 16.0 * (J.nseg + 1) * ((size_t)1 << (J.log2_S + J.log2_R));
-            const int grid = dev::gather_seg_plan(gather_seg_queue.data(), (int)gather_seg_queue.size());
-            flush_jobs(gather_seg_queue, cls_gather, sb, [&](dev::GatherSegJob* d, int nj) { dev::gather_seg_jobs(st, d, nj, grid); });
-        }
-        size_t maxB = 0; double bb = 0;
-        for (auto& J : gatherB_queue) { size_t t = (size_t)1 << (J.log2_S + J.log2_R); maxB = std::max(maxB, t); bb += 40.0 * t; }
-        flush_jobs(gatherB_queue, cls_gather, bb, [&](dev::GatherBJob* d, int nj) { dev::gather_B_jobs(st, d, nj, maxB); });
-        int max_L = 0, max_claims = 1; double fb = 0;
-        for (auto& J : fft_queue) { max_L = std::max(max_L, J.L); max_claims = std::max(max_claims, J.cs.n); fb += 24.0 * ((size_t)1 << J.L); }
-        E2* fft_tab = fft_queue.empty() ? nullptr : ctx->alloc_n<E2>(fft_queue.size() * (size_t)max_claims * (((size_t)1 << max_L) >> 4) + 1);
-        flush_jobs(fft_queue, cls_aux, fb, [&](dev::FftJob* d, int nj) { dev::fft_jobs(st, d, nj, max_L, max_claims, ctx->d_chal, fft_tab); });
+            std::vector<ConstRange> wr;
+            for (auto& J : part) { size_t t = (size_t)1 << (J.log2_S + J.log2_R); sb += 16.0 * (J.nseg + 1) * t; wr.push_back(crange(J.T, t)); }
+            const int nj = (int)part.size();
+            const int grid = dev::gather_seg_plan(part.data(), nj);
+            dev::GatherSegJob* d = put_jobs(part);
+            ctx->prof_begin(cls_gather, sb);
+            issue_const(c, wr, 1, [d, nj, grid](hipStream_t s) { dev::gather_seg_jobs(s, d, nj, grid); });
+            ctx->prof_end();
+        });
+        // Libra phase-2 tables: built without u (the replay applies it) they read the wiring and two eq tables
+        flush_jobs(gatherB_queue, [&](const dev::GatherBJob& J) { return J.u == nullptr && const_src(J.eqc) && const_src(J.eqx) && const_src(J.m.ptr); },
+                   [&](std::vector<dev::GatherBJob>& part, bool c) {
+            size_t maxB = 0; double bb = 0;
+            std::vector<ConstRange> wr;
+            for (auto& J : part) { size_t t = (size_t)1 << (J.log2_S + J.log2_R); maxB = std::max(maxB, t); bb += 40.0 * t; wr.push_back(crange(J.B, t)); }
+            dev::GatherBJob* d = put_jobs(part);
+            const int nj = (int)part.size();
+            ctx->prof_begin(cls_gather, bb);
+            issue_const(c, wr, 1, [d, nj, maxB](hipStream_t s) { dev::gather_B_jobs(s, d, nj, maxB); });
+            ctx->prof_end();
+        });
+        // DFT-row tables: the key's twiddle table and claim points in the chain
+        flush_jobs(fft_queue, [&](const dev::FftJob& J) { return const_src(J.W); }, [&](std::vector<dev::FftJob>& part, bool c) {
+            int max_L = 0, max_claims = 1; double fb = 0;
+            std::vector<ConstRange> wr;
+            for (auto& J : part) { max_L = std::max(max_L, J.L); max_claims = std::max(max_claims, J.cs.n); fb += 24.0 * ((size_t)1 << J.L); wr.push_back(crange(J.out, (size_t)1 << J.L)); }
+            const size_t tab_entries = part.size() * (size_t)max_claims * (((size_t)1 << max_L) >> 4) + 1;
+            E2* fft_tab = ctx->alloc_n<E2>(tab_entries);
+            wr.push_back(crange(fft_tab, tab_entries));
+            dev::FftJob* d = put_jobs(part);
+            const int nj = (int)part.size();
+            ctx->prof_begin(cls_aux, fb);
+            issue_const(c, wr, dev::fft_jobs_launches(max_L), [d, nj, max_L, max_claims, chal, fft_tab](hipStream_t s) { dev::fft_jobs(s, d, nj, max_L, max_claims, chal, fft_tab); });
+            ctx->prof_end();
+        });
     }
-

@@ -80,6 +80,10 @@ void hg_destroy(hg_ctx* ctx);
  *                 formed by the transcript replay on the host (default 1: by the tail kernel that writes the layer's evaluations;
  *                 a sharded rank, the sound modes and BN254 always use the host form). Same proof bytes; a change drops the
  *                 context's cached launch graphs
+ *   "graph_const_tables"  value == 0: a launch graph records every launch of the prove (default 1: the launches that build tables
+ *                 of the challenge chain and the prover key alone - eq and DFT-row tables, Libra tables without a mul part - run
+ *                 once after the capture and are not part of the replays; one rank, mode 0). Same proof bytes; a change drops
+ *                 the context's cached launch graphs
  *   "verify_batch_group"  the most proofs one device pass of hg_verify_device_batch, hg_verify_device_batch_bn254,
  *                 hg_verify_public_batch, hg_verify_public_bound_batch or hg_verify_public_batch_bn254 holds (and
  *                 hg_instance_digest_group stages), and the most openings one of
