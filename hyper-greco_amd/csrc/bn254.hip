@@ -1673,6 +1673,36 @@ __global__ __launch_bounds__(256) void k_bn_fold_multi(const Fr* __restrict__ in
     }
     if (t == 0) out[blockIdx.x] = to_slot ? fr_from_mont(sm[0]) : lz_canon(sm[0]);
 }
+// The launches of an MLE evaluation by folding, lowest variable first: up to ten variables per launch (k_bn_fold_multi), no launch left
+// with one (the launch before it binds one fewer); nv < 2 through k_bn_fold and a copy. `table` in Montgomery form, `pt_canon` canonical,
+// the value lands canonical in *dst. get(n): n elements for an intermediate table. What BnProver::mle_dev and hg_mle_eval_bn254 both run;
+// ms (the entry's plan line only): the variables bound by each k_bn_fold_multi launch, in order.
+template <class Get>
+static void mle_fold_dev(hipStream_t st, const Fr* table, int nv, const Fr* pt_canon, Get&& get, Fr* dst, std::vector<int>* ms = nullptr) {
+    if (nv < 2) {
+        const Fr* cur = table;
+        Fr* a = get(2);
+        if (nv == 1) { k_bn_fold<<<1, 64, 0, st>>>(cur, a, 1, fr_to_mont(pt_canon[0])); cur = a; }
+        k_bn_copy_from_mont<<<1, 64, 0, st>>>(cur, dst, 1);
+        return;
+    }
+    const Fr* cur = table;
+    int left = nv, at = 0;
+    while (left > 0) {
+        int m = std::min(left, 10);
+        if (left - m == 1) m--;   // (no launch binds fewer than two variables)
+        FoldPoint P;
+        for (int i = 0; i < 10; i++) P.r[i] = i < m ? fr_to_mont(pt_canon[at + i]) : fr_zero();
+        const size_t groups = (size_t)1 << (left - m);
+        const bool last = left == m;
+        Fr* out = last ? dst : get(groups);
+        k_bn_fold_multi<<<(unsigned)groups, 256, 0, st>>>(cur, out, m, P, last ? 1 : 0);
+        if (ms) ms->push_back(m);
+        cur = out;
+        left -= m;
+        at += m;
+    }
+}
 // W[i] = w^i (Montgomery), i < n
 __global__ void k_bn_powers(Fr* __restrict__ W, Fr w, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1772,8 +1802,9 @@ __global__ __launch_bounds__(256) void k_bn_ntt4_rows(const Fr* __restrict__ in,
     }
 }
 // in place on `a` through `tmp` (same size); W[i] = w^i for i < 2^log2n; returns false when the size is outside the four-step range
+static bool ntt4_size(int log2n) { return log2n >= 8 && log2n <= 16; }
 static bool ntt4_dev(hipStream_t st, Fr* a, Fr* tmp, const Fr* W, int log2n, bool scaled, Fr scale, size_t batch, const NttSrc* srcs = nullptr) {
-    if (log2n < 8 || log2n > 16 || (srcs && batch > 64)) return false;
+    if (!ntt4_size(log2n) || (srcs && batch > 64)) return false;
     NttSrc none;
     memset(&none, 0, sizeof(none));
     const int n1 = log2n / 2, n2 = log2n - n1;
@@ -1794,7 +1825,7 @@ __global__ void k_bn_scale_into(const Fr* __restrict__ in, Fr* __restrict__ out,
 }
 void ntt_batch_dev(hipStream_t st, Fr* a, Fr* tmp, const Fr* W, int log2n, size_t batch, const Fr* scale) {
     const Fr sc = scale ? *scale : fr_zero();
-    if (log2n >= 8 && log2n <= 16 && batch > 65535) throw Error("bn254: more than 65535 transforms in one four-step batch");
+    if (ntt4_size(log2n) && batch > 65535) throw Error("bn254: more than 65535 transforms in one four-step batch");
     if (ntt4_dev(st, a, tmp, W, log2n, scale != nullptr, sc, batch)) return;
     const size_t total = batch << log2n, th = total / 2;
     k_bn_bitrev<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(a, tmp, log2n, total);
@@ -1810,26 +1841,43 @@ static Fr fr_root_of_unity(int log2n) {
     return w;
 }
 
+// the kernel-level entries take canonical elements (hg.h): the first one that is not below r refuses the call
+static void require_below_r(const char* entry, const char* what, const u64* v4, size_t n) {
+    for (size_t i = 0; i < n; i++) {
+        Fr v;
+        memcpy(v.l, v4 + 4 * i, 32);
+        if (fr_geq_p(v)) throw Error(std::string(entry) + ": " + what + " not below r (element " + std::to_string(i) + ")");
+    }
+}
+
 // = BoxMultilinearPoly::evaluate over Fr [REF memory_checking/mod.rs:80-93, sk_encryption_circuit.rs:446]
 void mle_eval_bn254(hg_ctx* ctx, const u64* table4, size_t nv, const u64* point4, u64* out4) {
+    if (nv > 28) throw Error("hg_mle_eval_bn254: table size out of range");
+    const size_t N = (size_t)1 << nv;
+    require_below_r("hg_mle_eval_bn254", "point coordinate", point4, nv);
+    require_below_r("hg_mle_eval_bn254", "table entry", table4, N);
     hipc(hipSetDevice(ctx->device), "hipSetDevice");
     hipStream_t st = ctx->stream;
-    const size_t N = (size_t)1 << nv;
+    std::vector<Fr> pt(nv);
+    if (nv) memcpy(pt.data(), point4, nv * sizeof(Fr));
+    // the intermediates of the fold sequence: at most N / 4 elements after the first launch (it binds two variables or more), a quarter
+    // of the one before after every later one, N / 3 in all; nv < 2: two elements. One more element for the value.
+    const size_t inter = std::max<size_t>(N / 2, 2);
     Fr *a = nullptr, *b = nullptr;
     hipc(hipMalloc((void**)&a, N * sizeof(Fr)), "hipMalloc");
-    hipc(hipMalloc((void**)&b, std::max<size_t>(N / 2, 1) * sizeof(Fr)), "hipMalloc");
-    hipError_t e = hipMemcpyAsync(a, table4, N * sizeof(Fr), hipMemcpyHostToDevice, st);
+    hipError_t e = hipMalloc((void**)&b, (inter + 1) * sizeof(Fr));
+    if (e == hipSuccess) e = hipMemcpyAsync(a, table4, N * sizeof(Fr), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
         k_bn_to_mont<<<(unsigned)((N + 255) / 256), 256, 0, st>>>(a, N);
-        Fr *cur = a, *nxt = b;
-        for (size_t v = 0; v < nv; v++) {
-            const size_t half = N >> (v + 1);
-            const Fr r = fr_to_mont(fr_make(point4[4 * v], point4[4 * v + 1], point4[4 * v + 2], point4[4 * v + 3]));
-            k_bn_fold<<<(unsigned)((half + 255) / 256), 256, 0, st>>>(cur, nxt, half, r);
-            std::swap(cur, nxt);
+        size_t used = 0;
+        std::vector<int> ms;
+        mle_fold_dev(st, a, (int)nv, pt.data(), [&](size_t n) { Fr* q = b + used; used += n; return q; }, b + inter, &ms);
+        if (hg_debug("bnplan")) {   // the variables each k_bn_fold_multi launch bound (read at every call: the tests switch it per case)
+            std::string l;
+            for (size_t i = 0; i < ms.size(); i++) l += (i ? "," : "") + std::to_string(ms[i]);
+            fprintf(stderr, "[hg bnplan] mle nv=%zu m=[%s]\n", nv, l.c_str());
         }
-        k_bn_from_mont<<<1, 64, 0, st>>>(cur, 1);
-        e = hipMemcpyAsync(out4, cur, sizeof(Fr), hipMemcpyDeviceToHost, st);
+        e = hipMemcpyAsync(out4, b + inter, sizeof(Fr), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
     }
     (void)hipFree(a); (void)hipFree(b);
@@ -1838,10 +1886,20 @@ void mle_eval_bn254(hg_ctx* ctx, const u64* table4, size_t nv, const u64* point4
 
 // = FftNode evaluate over Fr: out[k] = sum_j in[j] w^(jk), w the 2^log2n-th root of unity (inverse: w^-1 and 1/n);
 // natural order in and out [REF sk_encryption_circuit.rs:224,249,251]
-void ntt_bn254(hg_ctx* ctx, const u64* in4, int log2n, bool inverse, size_t batch, u64* out4) {
+void ntt_bn254(hg_ctx* ctx, const u64* in4, size_t log2n_, bool inverse, size_t batch, u64* out4) {
+    if (log2n_ < 1 || log2n_ > 28) throw Error("hg_ntt_bn254: size out of range");
+    const int log2n = (int)log2n_;
+    if (batch == 0) throw Error("hg_ntt_bn254: empty batch");
+    if (ntt4_size(log2n) && batch > 65535) throw Error("hg_ntt_bn254: more than 65535 transforms in one four-step batch");
+    if (batch > (SIZE_MAX >> 6 >> log2n)) throw Error("hg_ntt_bn254: batch out of range");
+    const size_t n = (size_t)1 << log2n, total = n * batch;
+    require_below_r("hg_ntt_bn254", "input element", in4, total);
     hipc(hipSetDevice(ctx->device), "hipSetDevice");
     hipStream_t st = ctx->stream;
-    const size_t n = (size_t)1 << log2n, total = n * batch;
+    if (hg_debug("bnplan")) {   // the branch ntt4_dev takes below (the same predicate; read at every call: the tests switch it per case)
+        if (ntt4_size(log2n)) fprintf(stderr, "[hg bnplan] ntt log2n=%d batch=%zu path=four n1=%d n2=%d\n", log2n, batch, log2n / 2, log2n - log2n / 2);
+        else fprintf(stderr, "[hg bnplan] ntt log2n=%d batch=%zu path=radix2 grid=%zu\n", log2n, batch, (total / 2 + 255) / 256);
+    }
     Fr w = fr_root_of_unity(log2n);
     if (inverse) w = fr_inv(w);
     Fr *a = nullptr, *b = nullptr, *W = nullptr;

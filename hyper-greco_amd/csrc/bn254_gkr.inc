@@ -1135,28 +1135,7 @@ struct BnProver {
     // by the replay after the synchronisation
     const Fr* mle_dev(const Fr* table, int nv, const Fr* pt_canon) {
         const ResRef out = res_slots(ctx, 1);
-        if (nv < 2) {
-            const Fr* cur = table;
-            Fr* a = pool.get<Fr>(2);
-            if (nv == 1) { k_bn_fold<<<1, 64, 0, st>>>(cur, a, 1, fr_to_mont(pt_canon[0])); cur = a; }
-            k_bn_copy_from_mont<<<1, 64, 0, st>>>(cur, out.dev, 1);
-            return out.host;
-        }
-        const Fr* cur = table;
-        int left = nv, at = 0;
-        while (left > 0) {
-            int m = std::min(left, 10);
-            if (left - m == 1) m--;   // (no launch binds fewer than two variables)
-            FoldPoint P;
-            for (int i = 0; i < 10; i++) P.r[i] = i < m ? fr_to_mont(pt_canon[at + i]) : fr_zero();
-            const size_t groups = (size_t)1 << (left - m);
-            const bool last = left == m;
-            Fr* dst = last ? out.dev : pool.get<Fr>(groups);
-            k_bn_fold_multi<<<(unsigned)groups, 256, 0, st>>>(cur, dst, m, P, last ? 1 : 0);
-            cur = dst;
-            left -= m;
-            at += m;
-        }
+        mle_fold_dev(st, table, nv, pt_canon, [this](size_t n) { return pool.get<Fr>(n); }, out.dev);
         return out.host;
     }
 

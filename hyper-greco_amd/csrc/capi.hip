@@ -5,6 +5,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
+#include <cstdint>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -22,7 +23,7 @@ void prodsum_jobs_bn254(hg_ctx* ctx, size_t njobs, const size_t* nv, const size_
 void field_op_bn254(hg_ctx* ctx, int op, size_t n, const u64* a, const u64* b, u64* out);
 void challenges_bn254_raw(size_t n, uint64_t* out4);
 void mle_eval_bn254(hg_ctx* ctx, const u64* table4, size_t nv, const u64* point4, u64* out4);
-void ntt_bn254(hg_ctx* ctx, const u64* in4, int log2n, bool inverse, size_t batch, u64* out4);
+void ntt_bn254(hg_ctx* ctx, const u64* in4, size_t log2n, bool inverse, size_t batch, u64* out4);
 void grand_product_bn254(hg_ctx* ctx, size_t nb, size_t len, const u64* const* tables, size_t chain_skip, std::vector<uint8_t>& proof,
                          u64* claims_out, u64* point_out);
 void lasso_prove_bn254(hg_ctx* ctx, const hg_pk* pk, const u64* in4, size_t chain_skip, std::vector<uint8_t>& proof, u64* claim_out);
@@ -2190,9 +2191,17 @@ int hg_grand_product(hg_ctx* ctx, size_t nb, size_t len, const uint64_t* const* 
     return 0;
     HG_CATCH(-1)
 }
+// the kernel-level entries take canonical words (hg.h): the first word that is not below p refuses the call
+static void require_canonical(const char* entry, const char* what, const uint64_t* v, size_t words) {
+    for (size_t i = 0; i < words; i++)
+        if (v[i] >= GL_P) throw Error(std::string(entry) + ": non-canonical " + what + " (word " + std::to_string(i) + ")");
+}
 int hg_fold(hg_ctx* ctx, const uint64_t* table, size_t nv, int is_base, const uint64_t r2[2], uint64_t* out) {
     HG_TRY
     if (!ctx || !table || !r2 || !out) throw Error("hg_fold: null argument (a HIP device is required)");
+    if (nv < 1 || nv > 30) throw Error("hg_fold: table size out of range");
+    if (r2[0] >= GL_P || r2[1] >= GL_P) throw Error("hg_fold: non-canonical r");
+    require_canonical("hg_fold", "table entry", table, (is_base ? (size_t)1 : (size_t)2) << nv);
     fold_device(ctx, table, nv, is_base != 0, e2(r2[0], r2[1]), reinterpret_cast<E2*>(out));
     return 0;
     HG_CATCH(-1)
@@ -2208,6 +2217,9 @@ int hg_params_derive(uint32_t n, uint32_t k, const uint64_t* qis, uint64_t t, hg
 int hg_mle_eval(hg_ctx* ctx, const uint64_t* table, size_t nv, const uint64_t* point, uint64_t out2[2]) {
     HG_TRY
     if (!ctx || !table || (nv && !point) || !out2) throw Error("hg_mle_eval: null argument (a HIP device is required)");
+    if (nv > 30) throw Error("hg_mle_eval: table size out of range");
+    require_canonical("hg_mle_eval", "point coordinate", point, 2 * nv);
+    require_canonical("hg_mle_eval", "table entry", table, (size_t)1 << nv);
     std::vector<E2> pt(nv);
     for (size_t i = 0; i < nv; i++) pt[i] = e2(point[2 * i], point[2 * i + 1]);
     E2 v = mle_eval_device(ctx, table, nv, pt.data());
@@ -2220,6 +2232,10 @@ int hg_ntt(hg_ctx* ctx, const uint64_t* in, size_t log2n, int inverse, size_t ba
     HG_TRY
     if (!ctx || !in || !out) throw Error("hg_ntt: null argument (a HIP device is required)");
     if (log2n < 1 || log2n > 32) throw Error("hg_ntt: size out of range");
+    if (batch == 0) throw Error("hg_ntt: empty batch");
+    if (log2n >= 8 && log2n <= 16 && batch > 65535) throw Error("hg_ntt: more than 65535 transforms in one four-step batch");
+    if (batch > (SIZE_MAX >> 4 >> log2n)) throw Error("hg_ntt: batch out of range");
+    require_canonical("hg_ntt", "input word", in, batch << log2n);
     ntt_device(ctx, in, (int)log2n, inverse != 0, batch, out);
     return 0;
     HG_CATCH(-1)
@@ -2326,15 +2342,15 @@ int hg_prove_bn254(hg_ctx* ctx, const hg_pk* pk, const hg_witness* w, uint8_t* p
 }
 int hg_mle_eval_bn254(hg_ctx* ctx, const uint64_t* table4, size_t nv, const uint64_t* point4, uint64_t out4[4]) {
     HG_TRY
-    if (!ctx) throw hg::Error("hg_mle_eval_bn254: no context (a HIP device is required)");
+    if (!ctx || !table4 || (nv && !point4) || !out4) throw hg::Error("hg_mle_eval_bn254: null argument (a HIP device is required)");
     hg::bn::mle_eval_bn254(ctx, table4, nv, point4, out4);
     return 0;
     HG_CATCH(-1)
 }
 int hg_ntt_bn254(hg_ctx* ctx, const uint64_t* in4, size_t log2n, int inverse, size_t batch, uint64_t* out4) {
     HG_TRY
-    if (!ctx) throw hg::Error("hg_ntt_bn254: no context (a HIP device is required)");
-    hg::bn::ntt_bn254(ctx, in4, (int)log2n, inverse != 0, batch, out4);
+    if (!ctx || !in4 || !out4) throw hg::Error("hg_ntt_bn254: null argument (a HIP device is required)");
+    hg::bn::ntt_bn254(ctx, in4, log2n, inverse != 0, batch, out4);
     return 0;
     HG_CATCH(-1)
 }

@@ -35,6 +35,9 @@ const u64* challenge_chain(size_t n_base);  // pointer to >= n_base cached base-
 // Diagnostics on stderr: HG_DEBUG = comma-separated tokens, read at every call (tests set and unset it inside one process).
 //   shard: per-rank times of a sharded prove, the shard plan, failed graph captures    slots: the slot-form layers a prove adopted
 //   eq: how many queued node reductions run eq-factored    launch: host time of every launch-graph replay    fail_capture: makes the next launch-graph capture fail (fallback test)
+//   plan: one line per launch decision, `[hg plan] ..` - the sum-check planners (stride, prodsum) and hg_ntt's path (ntt)
+//   bnplan: the same for the BN254 entries, `[hg bnplan] ..` - staged descriptors (ps, gp), hg_ntt_bn254's path (ntt), the variables each
+//   launch of hg_mle_eval_bn254 binds (mle)    gpclaims, lasso, consts: further `[hg plan]` lines with tokens of their own
 bool hg_debug(const char* token);
 // Timing breakdowns on stderr: HG_TIMES = comma-separated tokens, read at every call.
 //   seq: the round-by-round prover (waits, host steps, drains)    bn: the bn254 prove and its witness generation

@@ -3560,15 +3560,15 @@ __global__ __launch_bounds__(256) void k_ntt4_rows(const u64* __restrict__ in, u
 
 // W must hold w^i for i < N (four-step) — the radix-2 fallback only reads i < N/2.
 void ntt_batch(hipStream_t st, u64* data, int log2n, size_t batch, const u64* W, u64 scale, u64* scratch) {
-    if (log2n >= 8 && log2n <= 16 && scratch) {
+    if (ntt_four_step(log2n, scratch)) {
         const int n1 = log2n / 2, n2 = log2n - n1;
         const size_t lds = (size_t)(1 << (n1 > n2 ? n1 : n2)) * (NTT_TILE + 1) * sizeof(u64);
         k_ntt4_cols<<<dim3(1u << (n2 - 4), (unsigned)batch), 256, lds, st>>>(data, scratch, log2n, n1, W);
         k_ntt4_rows<<<dim3(1u << (n1 - 4), (unsigned)batch), 256, lds, st>>>(scratch, data, log2n, n1, W, scale);
         return;
     }
-    size_t total = batch << (log2n - 1);
-    int grid = (int)std::min<size_t>((total + TPB - 1) / TPB, 4096);
+    static_assert(TPB == 256, "ntt_radix2_grid counts workgroups of 256");
+    const int grid = ntt_radix2_grid(log2n, batch);
     for (int s = log2n - 1; s >= 0; s--) k_ntt_stage<<<grid, TPB, 0, st>>>(data, log2n, s, batch, W);
     k_ntt_bitrev<<<grid * 2, TPB, 0, st>>>(data, log2n, batch, scale);
 }

@@ -2,6 +2,7 @@
 // pointers; every launch goes to the given stream; nothing here synchronises.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include "gl_field.hpp"
 
 namespace hg {
@@ -422,6 +423,10 @@ void gate_eval(hipStream_t st, const EvalNode& n);
 // In place, natural order in and out. 8 <= log2n <= 16 with a scratch buffer of batch*N u64: LDS-resident four-step
 // (two launches); otherwise radix-2 stages in HBM. W = w^i for i < N.
 void ntt_batch(hipStream_t st, u64* data, int log2n, size_t batch, const u64* W, u64 scale, u64* scratch);
+// The branch ntt_batch takes and the grid of its radix-2 launches, for a caller that reports them (hg_ntt's plan line). The four-step
+// grids carry the batch in their y extent: at most 65535 transforms a call on that path (checked by the callers).
+inline bool ntt_four_step(int log2n, const u64* scratch) { return log2n >= 8 && log2n <= 16 && scratch != nullptr; }
+inline int ntt_radix2_grid(int log2n, size_t batch) { return (int)std::min<size_t>(((batch << (log2n - 1)) + 255) / 256, 4096); }   // k_ntt_stage; k_ntt_bitrev: twice that
 
 // ---- witness derivation (hg_witness_derive): ct0is, r2is, r1is from s, e, k1, ais [REF scripts/circuit_sk.py:18-140] -------------
 // The exact integer product a_i * s as 2k+1 Goldilocks NTTs of size 2n: a_i is split as lo + 2^32 hi (lo = low 32 bits, hi the

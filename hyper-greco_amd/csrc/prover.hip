@@ -1944,6 +1944,10 @@ void ntt_device(hg_ctx* ctx, const u64* in_host, int log2n, bool inverse, size_t
     u64* W = ctx->alloc_n<u64>(N);
     u64 w = root_of_unity(log2n);
     if (inverse) w = gl_inv(w);
+    if (hg_debug("plan")) {   // the branch ntt_batch takes below (the same predicate; read at every call: the tests switch it per case)
+        if (dev::ntt_four_step(log2n, scratch)) fprintf(stderr, "[hg plan] ntt log2n=%d batch=%zu path=four n1=%d n2=%d\n", log2n, batch, log2n / 2, log2n - log2n / 2);
+        else fprintf(stderr, "[hg plan] ntt log2n=%d batch=%zu path=radix2 grid=%d\n", log2n, batch, dev::ntt_radix2_grid(log2n, batch));
+    }
     hip_check(hipMemcpyAsync(d, in_host, N * batch * 8, hipMemcpyHostToDevice, ctx->stream), "upload");
     dev::powers_table(ctx->stream, W, w, N);
     dev::ntt_batch(ctx->stream, d, log2n, batch, W, inverse ? gl_inv(gl_from_u64(N)) : 1, scratch);

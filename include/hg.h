@@ -784,14 +784,25 @@ int hg_sumcheck(hg_ctx* ctx, int kind, size_t nv, size_t ntab, const uint64_t* c
 int hg_grand_product(hg_ctx* ctx, size_t nb, size_t len, const uint64_t* const* tables, size_t chain_skip, uint8_t* proof, size_t cap,
                      size_t* proof_len, uint64_t* claims2, uint64_t* point2);
 /* = BoxMultilinearPoly::fix_var on the lowest variable (inside gkr::sum_check::prove_sum_check; SURVEY.md 8(c) convention C3):
- *   out[j] = T[2j] + r (T[2j+1] - T[2j]), j < 2^(nv-1). table: 2^nv base values (is_base) or (c0, c1) pairs; out: 2^(nv-1) pairs. */
+ *   out[j] = T[2j] + r (T[2j+1] - T[2j]), j < 2^(nv-1). table: 2^nv base values (is_base) or (c0, c1) pairs; out: 2^(nv-1) pairs.
+ *   Refused with -1 (hg_last_error names hg_fold), checked on the host before anything is launched: a null argument; nv outside
+ *   1..30 (checked before the table is read); a table word or a coordinate of r that is >= p. */
 int hg_fold(hg_ctx* ctx, const uint64_t* table, size_t nv, int is_base, const uint64_t r2[2], uint64_t* out);
 
 /* = BoxMultilinearPoly::evaluate [REF call sites memory_checking/mod.rs:80-93, sk_encryption_circuit.rs:446]
- *   on a host table of 2^nv base-field values at an E point. */
+ *   on a host table of 2^nv base-field values at an E point (point: nv (c0, c1) pairs, lowest variable first; may be null at nv = 0).
+ *   Refused with -1 (hg_last_error names hg_mle_eval), checked on the host before anything is launched: a null argument; nv > 30
+ *   (checked before the table is read); a table word or a point coordinate that is >= p. */
 int hg_mle_eval(hg_ctx* ctx, const uint64_t* table, size_t nv, const uint64_t* point, uint64_t out2[2]);
 
-/* = FftNode evaluate (size-2^log2n NTT, natural order in/out) [REF sk_encryption_circuit.rs:224,249,251]. Device. */
+/* = FftNode evaluate (size-2^log2n NTT, natural order in/out) [REF sk_encryption_circuit.rs:224,249,251]. Device.
+ *   in, out: batch rows of 2^log2n canonical words. 8 <= log2n <= 16 runs the LDS-resident four-step kernels (2^n1 x 2^n2,
+ *   n1 = log2n / 2), every other size radix-2 stages in HBM.
+ *   Refused with -1 (hg_last_error names hg_ntt), checked on the host before anything is launched: a null argument; log2n outside
+ *   1..32; batch == 0; batch > 65535 when 8 <= log2n <= 16 (the four-step grids carry the batch in their y extent); a batch whose
+ *   byte count does not fit size_t - all of these before `in` is read; an input word >= p.
+ *   HG_DEBUG=plan prints the path taken, one line per call: `[hg plan] ntt log2n=.. batch=.. path=four n1=.. n2=..` or
+ *   `[hg plan] ntt log2n=.. batch=.. path=radix2 grid=..` (grid: workgroups of a stage launch; the bit reversal has twice as many). */
 int hg_ntt(hg_ctx* ctx, const uint64_t* in, size_t log2n, int inverse, size_t batch, uint64_t* out);
 
 /* Fiat-Shamir challenge chain [REF bfv-gkr/src/transcript.rs:146-157,198-203]: first n base-field challenges. */
@@ -842,10 +853,21 @@ int hg_grand_product_bn254(hg_ctx* ctx, size_t nb, size_t len, const uint64_t* c
  *   products and the openings run over Fr. proof: 32-byte big-endian elements. claim_out4: nu coordinates of r, then the claimed sum. */
 int hg_lasso_prove_bn254(hg_ctx* ctx, const hg_pk* pk, const uint64_t* lasso_in4, size_t chain_skip, uint8_t* proof, size_t cap, size_t* len,
                          uint64_t* claim_out4);
-/* = BoxMultilinearPoly::evaluate over Fr [REF memory_checking/mod.rs:80-93]: table of 2^nv elements at a point of nv elements */
+/* = BoxMultilinearPoly::evaluate over Fr [REF memory_checking/mod.rs:80-93]: table of 2^nv elements at a point of nv elements,
+ *   lowest variable first. Runs the fold sequence of hg_prove_bn254's own evaluation: up to ten variables bound per launch, no launch
+ *   left with a single one (11 variables: 9 then 2); nv < 2 without such a launch.
+ *   Refused with -1 (hg_last_error names hg_mle_eval_bn254), checked on the host before anything is launched: a null context or
+ *   pointer (point4 may be null at nv = 0); nv > 28 (checked before the table is read); a table or point element >= r.
+ *   HG_DEBUG=bnplan prints `[hg bnplan] mle nv=.. m=[..]`: the variables bound by each launch, in order (m=[] for nv < 2). */
 int hg_mle_eval_bn254(hg_ctx* ctx, const uint64_t* table4, size_t nv, const uint64_t* point4, uint64_t out4[4]);
 /* = FftNode evaluate over Fr [REF sk_encryption_circuit.rs:224,249,251]: size-2^log2n NTT with the root of unity
- *   7^((r-1)/2^log2n) (halo2curves ROOT_OF_UNITY, two-adicity 28), natural order in / out; inverse scales by 1/n */
+ *   7^((r-1)/2^log2n) (halo2curves ROOT_OF_UNITY, two-adicity 28), natural order in / out; inverse scales by 1/n.
+ *   8 <= log2n <= 16 runs the LDS-resident four-step kernels (n1 = log2n / 2), every other size radix-2 stages in HBM.
+ *   Refused with -1 (hg_last_error names hg_ntt_bn254), checked on the host before anything is launched: a null context or pointer;
+ *   log2n outside 1..28; batch == 0; batch > 65535 when 8 <= log2n <= 16; a batch whose byte count does not fit size_t - all of
+ *   these before in4 is read; an element >= r.
+ *   HG_DEBUG=bnplan prints the path taken: `[hg bnplan] ntt log2n=.. batch=.. path=four n1=.. n2=..` or `.. path=radix2 grid=..`
+ *   (grid: workgroups of a stage launch). */
 int hg_ntt_bn254(hg_ctx* ctx, const uint64_t* in4, size_t log2n, int inverse, size_t batch, uint64_t* out4);
 
 /* = BfvSkEncryptArgs from one of the reference's bn254 fixtures [REF bfv-gkr/src/data/bn254/ *.json, sk_encryption_circuit.rs:365-415]:

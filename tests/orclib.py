@@ -47,7 +47,13 @@ def ptr(a):
 
 # ---- kernel-level sum-check helpers shared by test_gpu_parity.py and test_launch_plans.py ----------------------------------
 def rand_f(rng, n):
+    """n random canonical words with the edges planted; rng: random.Random, or a numpy Generator (long tables: no Python loop)"""
     edge = [0, 1, P - 1, P - 2, 0xFFFFFFFF, 0x100000000, 0xFFFFFFFF00000000]
+    if isinstance(rng, np.random.Generator):
+        v = rng.integers(0, P, size=n, dtype=np.uint64)
+        k = min(n, len(edge))
+        v[rng.choice(n, size=k, replace=False)] = np.array(edge[:k], dtype=np.uint64)
+        return v
     v = [rng.randrange(P) for _ in range(n)]
     for i, e in enumerate(edge[:n]):
         v[rng.randrange(n)] = e
@@ -60,6 +66,8 @@ EDGE_POOL = [0, 1, 2, P - 1, P - 2, 0xFFFFFFFF, 0x100000000, 0x100000001, 0xFFFF
 
 
 def edge_f(rng, n):
+    if isinstance(rng, np.random.Generator):
+        return np.array(EDGE_POOL, dtype=np.uint64)[rng.integers(0, len(EDGE_POOL), size=n)]
     return np.array(rng.choices(EDGE_POOL, k=n), dtype=np.uint64)
 
 
@@ -435,9 +443,69 @@ def mle_eval_f(field, table, point):
     fl, el = limbs_of(field)
     nv = (len(table) - 1).bit_length()
     out = np.zeros(el, dtype=np.uint64)
-    pt = to_limbs(list(point), el) if len(point) else np.zeros(el, dtype=np.uint64)
+    pt = to_limbs(point if isinstance(point, np.ndarray) else list(point), el) if len(point) else np.zeros(el, dtype=np.uint64)   # ((nv, el) limbs as they are)
     _sym(field, "mle_eval_f")(ptr(to_limbs(table, fl)), C.c_size_t(nv), ptr(pt), ptr(out))
     return from_limbs(out, el)[0]
+
+
+# ---- transforms and folds on limb arrays (tests/test_transform_paths.py; pinned in tests/test_oracle_kats.py) ---------------------
+def ntt_f(field, limbs, log2n, inverse=False):
+    """ntt of the C++ oracle on one row: 2^log2n elements as limbs ((N,) words for goldilocks, (N, 4) for bn254) -> the same shape"""
+    a = np.ascontiguousarray(limbs, dtype=np.uint64)
+    assert a.size == limbs_of(field)[0] << log2n, (a.shape, log2n)
+    out = np.zeros_like(a)
+    _sym(field, "ntt")(ptr(a), C.c_size_t(log2n), 1 if inverse else 0, ptr(out))
+    return out
+
+
+def binop_limbs(field, ext, op, a, b):
+    """f_binop (ext = False) / e_binop of the C++ oracle on limb arrays of equal shape; op: 0 add, 1 sub, 2 mul"""
+    a, b = np.ascontiguousarray(a, dtype=np.uint64), np.ascontiguousarray(b, dtype=np.uint64)
+    nl = limbs_of(field)[1 if ext else 0]
+    assert a.shape == b.shape and a.size % nl == 0
+    out = np.zeros_like(a)
+    _sym(field, "e_binop" if ext else "f_binop")(op, C.c_size_t(a.size // nl), ptr(a), ptr(b), ptr(out))
+    return out
+
+
+def fold_f(field, table, is_base, r):
+    """fix_var on the lowest variable, out[j] = x + r (y - x) with x = T[2j], y = T[2j + 1], from the oracle's binops. table: 2^nv
+    base-field elements (is_base) or extension elements as limbs, r: one extension element as limbs -> (2^(nv-1), e_limbs)"""
+    fl, el = limbs_of(field)
+    t = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1, fl if is_base else el)
+    x, y = np.ascontiguousarray(t[0::2]), np.ascontiguousarray(t[1::2])
+    if is_base:   # y - x in the base field, then both lifted (the higher coordinate zero)
+        d, xe = np.zeros((len(x), el), dtype=np.uint64), np.zeros((len(x), el), dtype=np.uint64)
+        d[:, :fl] = binop_limbs(field, False, 1, y, x)
+        xe[:, :fl] = x
+    else:
+        d, xe = binop_limbs(field, True, 1, y, x), x
+    rr = np.ascontiguousarray(np.broadcast_to(np.asarray(r, dtype=np.uint64).reshape(1, el), (len(x), el)))
+    return binop_limbs(field, True, 0, xe, binop_limbs(field, True, 2, rr, d))
+
+
+def field_modulus(field):
+    return R_BN if field == "bn254" else P
+
+
+def ints_to_limbs(vals, nl):
+    """Python ints -> (n, nl) limbs ((n,) for nl = 1) through their bytes (long lists: no per-limb Python loop)"""
+    a = np.frombuffer(b"".join(int(v).to_bytes(8 * nl, "little") for v in vals), dtype=np.uint64).copy()
+    return a if nl == 1 else a.reshape(-1, nl)
+
+
+def ntt_impulse(field, log2n, j, c, inverse=False):
+    """The transform of the row that holds c at position j and zero elsewhere, without the oracle's ntt: out[k] = c w^(jk), filled by a
+    running product with g = w^j in Python integers (the inverse: w^-1 and the factor 1 / N). -> limbs, the shape ntt_f returns"""
+    q, N = field_modulus(field), 1 << log2n
+    w = root_of_unity_f(field, log2n)
+    if inverse:
+        w, c = pow(w, q - 2, q), c * pow(N, q - 2, q) % q
+    g, v, out = pow(w, j, q), c % q, []
+    for _ in range(N):
+        out.append(v)
+        v = v * g % q
+    return ints_to_limbs(out, limbs_of(field)[0])
 
 
 # ---- long bn254 tables as (n, 4) uint64 limb arrays: no Python loop over the elements ---------------------------------------------

@@ -24,6 +24,8 @@ import pytest
 import orclib
 from orclib import P, ptr, rand_f, edge_f, oracle_sumcheck
 from hglib import hg
+import planlib
+from planlib import plan_lines, show_plans   # noqa: F401  (show_plans: the autouse fixture that prints what each test read)
 
 pytestmark = pytest.mark.gpu
 
@@ -41,31 +43,6 @@ def ctx():
 
 
 # ---- the plan lines -----------------------------------------------------------------------------------------------------------
-
-def _val(v):
-    if v.startswith("["):
-        return [int(x) for x in v[1:-1].split(",") if x]
-    if ".." in v:
-        lo, hi = v.split("..")
-        return (int(lo), int(hi))
-    return int(v)
-
-
-def plan_lines(err):
-    """The `[hg plan]` lines of a captured stderr as dicts: what = "stride" | "prodsum", the line's fields, `ptail` for the prodsum tail."""
-    out = []
-    for ln in err.splitlines():
-        if not ln.startswith("[hg plan] "):
-            continue
-        w = ln.split()[2:]
-        d = {"what": w[0], "ptail": len(w) > 1 and w[1] == "tail", "line": ln}
-        for tok in w[1:]:
-            if "=" in tok:
-                k, v = tok.split("=", 1)
-                d[k] = _val(v)
-        out.append(d)
-    return out
-
 
 def _rng(lo_hi):
     lo, hi = lo_hi
@@ -96,28 +73,9 @@ def signature(plan):
     return " ".join(sig)
 
 
-_SEEN = []
-
-
-@pytest.fixture(autouse=True)
-def show_plans():
-    """Prints every plan the test read, once it no longer captures (pytest -rA shows them: which launches each row ran)."""
-    _SEEN.clear()
-    yield
-    print("\n".join(_SEEN))
-
-
 def planned(capfd, monkeypatch, fn, label=""):
-    """Runs fn() with HG_DEBUG=plan and returns (its result, the plan lines it printed)."""
-    monkeypatch.setenv("HG_DEBUG", "plan")
-    capfd.readouterr()
-    try:
-        res = fn()
-    finally:
-        monkeypatch.delenv("HG_DEBUG")
-    plan = plan_lines(capfd.readouterr().err)
-    _SEEN.extend(["-- %s: %s" % (label, signature(plan))] + [l["line"] for l in plan])
-    return res, plan
+    """Runs fn() with HG_DEBUG=plan and returns (its result, the plan lines it printed); the signature is shown next to the label."""
+    return planlib.planned(capfd, monkeypatch, fn, label, describe=signature)
 
 
 # ---- operands -----------------------------------------------------------------------------------------------------------------

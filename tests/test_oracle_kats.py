@@ -586,3 +586,86 @@ def test_joint_classes_of_the_product_tree_layers_share_their_rows():
                             assert (lev[m][g * n:(g + 1) * n] == lev[members[0]][g * n:(g + 1) * n]).all(), (n, d, g, members)
                     found = max(found, len(groups))
                 assert found < A or d > 0, (n, d, found)   # (the top layer always has something to share)
+
+
+# ---- the references of tests/test_transform_paths.py, pinned to something that does not go through them -------------------------------
+FIELDS = ("goldilocks", "bn254")
+
+
+def _ints(field, limbs):
+    return orclib.from_limbs(np.asarray(limbs).reshape(-1), orclib.limbs_of(field)[0])
+
+
+@pytest.mark.parametrize("field", FIELDS)
+def test_ntt_f_matches_the_definition(field):
+    """orclib.ntt_f (the C++ oracle's ntt) against out[k] = sum_j a[j] w^(jk) in Python integers (the inverse: w^-1 and 1 / N), at
+    log2n 1..6, on random rows that carry the edge values."""
+    q, nl = orclib.field_modulus(field), orclib.limbs_of(field)[0]
+    rng = random.Random(0x4e5454)
+    edges = orclib.EDGE_POOL_FR if field == "bn254" else orclib.EDGE_POOL
+    for log2n in range(1, 7):
+        N = 1 << log2n
+        w = orclib.root_of_unity_f(field, log2n)
+        assert pow(w, N, q) == 1 and pow(w, N // 2, q) == q - 1   # a primitive N-th root
+        a = [rng.randrange(q) for _ in range(N)]
+        for e in rng.sample(edges, min(N // 2, len(edges))):
+            a[rng.randrange(N)] = e
+        for inverse in (False, True):
+            ww, sc = (pow(w, q - 2, q), pow(N, q - 2, q)) if inverse else (w, 1)
+            want = [sum(a[j] * pow(ww, j * k, q) for j in range(N)) * sc % q for k in range(N)]
+            assert _ints(field, orclib.ntt_f(field, orclib.ints_to_limbs(a, nl), log2n, inverse)) == want, (log2n, inverse)
+
+
+@pytest.mark.parametrize("field", FIELDS)
+def test_ntt_f_and_the_impulse_closed_form_agree_at_2_17(field):
+    """At 2^17 the definition is out of reach: the transform of c at position j, zero elsewhere, is c w^(jk) (orclib.ntt_impulse, a running
+    product in Python integers). Both directions; and the closed form itself against the definition's terms at a few k."""
+    q, nl, log2n = orclib.field_modulus(field), orclib.limbs_of(field)[0], 17
+    N = 1 << log2n
+    w = orclib.root_of_unity_f(field, log2n)
+    rng = random.Random(0x494d50)
+    for inverse in (False, True):
+        for j, c in ((0, q - 1), (1, 2), (N - 1, q - 2), (rng.randrange(N), rng.randrange(q))):
+            row = [0] * N
+            row[j] = c
+            closed = orclib.ntt_impulse(field, log2n, j, c, inverse)
+            assert (orclib.ntt_f(field, orclib.ints_to_limbs(row, nl), log2n, inverse) == closed).all(), (inverse, j)
+            ww, sc = (pow(w, q - 2, q), pow(N, q - 2, q)) if inverse else (w, 1)
+            for k in (0, 1, 2, N // 2, N - 1, rng.randrange(N)):
+                assert _ints(field, closed[k]) == [c * sc * pow(ww, j * k, q) % q], (inverse, j, k)
+
+
+@pytest.mark.parametrize("field", FIELDS)
+def test_fold_f_matches_python_integers(field):
+    """orclib.fold_f = x + r (y - x) on the lowest variable, against Python integers: base-field and extension tables (goldilocks: pairs
+    with X^2 = 7; bn254: the field itself), r with both coordinates set, edge values in the table."""
+    q = orclib.field_modulus(field)
+    fl, el = orclib.limbs_of(field)
+    rng = random.Random(0x464f4c)
+    edges = orclib.EDGE_POOL_FR if field == "bn254" else orclib.EDGE_POOL
+    deg = el // fl   # coordinates of an extension element
+    def mul(a, b):
+        return ((a[0] * b[0] + 7 * a[1] * b[1]) % q, (a[0] * b[1] + a[1] * b[0]) % q) if deg == 2 else (a[0] * b[0] % q,)
+    for is_base in (True, False):
+        width = 1 if is_base else deg
+        tab = [tuple(rng.choice(edges) if rng.random() < 0.4 else rng.randrange(q) for _ in range(width)) for _ in range(32)]
+        for r in (tuple(rng.randrange(q) for _ in range(deg)), (q - 1,) * deg, (0,) * deg, (1,) + (0,) * (deg - 1)):
+            lift = [t + (0,) * (deg - len(t)) for t in tab]
+            want = []
+            for x, y in zip(lift[0::2], lift[1::2]):
+                d = mul(r, tuple((b - a) % q for a, b in zip(x, y)))
+                want += [(a + b) % q for a, b in zip(x, d)]
+            flat = orclib.ints_to_limbs([c for t in tab for c in t], fl)
+            got = orclib.fold_f(field, flat, is_base, orclib.ints_to_limbs(list(r), fl).reshape(-1))
+            assert got.shape == (16, el) and _ints(field, got) == want, (is_base, r)
+
+
+def test_numpy_forms_of_rand_f_and_edge_f():
+    """rand_f / edge_f on a numpy Generator (long tables): canonical words, every edge planted / nothing but edges."""
+    rng = np.random.default_rng(7)
+    a = orclib.rand_f(rng, 1 << 12)
+    assert a.dtype == np.uint64 and a.shape == (1 << 12,) and int(a.max()) < P and len(set(a.tolist())) > 4000
+    assert {0, 1, P - 1, P - 2, 0xFFFFFFFF, 0x100000000, 0xFFFFFFFF00000000} <= set(a.tolist())
+    assert len(orclib.rand_f(rng, 2)) == 2
+    e = orclib.edge_f(rng, 1 << 12)
+    assert e.dtype == np.uint64 and set(e.tolist()) == set(orclib.EDGE_POOL)
