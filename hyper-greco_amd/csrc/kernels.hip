@@ -302,7 +302,7 @@ __device__ __forceinline__ GpItemE2 gp_item_any() {   // "no value yet" without 
 // MODE (grand product, later rounds on Ext2 tables only; round 6): 0 = the round; 1 = its folds only (the next round needs nothing else: the
 // challenges are known before the proof), 2 = its sums only - a small round is one workgroup's dependent chain, and the chain of a
 // fold-only launch is a third of the whole round's; the sums of every split round then run in one launch beside the rounds that follow
-template <int KIND, typename T, bool FIRST, bool SLOT = false, bool GIO = true, int MODE = 0>   // SLOT: first round of a slot-form job (StJob::slotw), passed as `mirror`; GIO = false: tables behind generic pointers (k_st_tail: LDS)
+template <int KIND, typename T, bool FIRST, bool SLOT = false, bool GIO = true, int MODE = 0, bool GOUT = GIO>   // SLOT: first round of a slot-form job (StJob::slotw), passed as `mirror`; GIO = false: tables behind generic pointers (k_st_tail: LDS); GOUT: the same for the folded tables alone (grand product, later rounds: the tail's first round reads HBM and writes LDS)
 __device__ __forceinline__ void sc_round_body(const T* __restrict__ in, size_t in_stride, E2* __restrict__ out,
                                               size_t out_stride, int ntab, size_t half, E2 r, const E2* __restrict__ pw, const E2* __restrict__ pwr,
                                               int jb_log2, E2* __restrict__ red, E2* acc, size_t first_tile, size_t tile_step,
@@ -361,8 +361,8 @@ __device__ __forceinline__ void sc_round_body(const T* __restrict__ in, size_t i
                         we2_mac(wi, dl, dr);
                     }
                     if (MODE != 2) {
-                        store_e2<GIO>(out + (size_t)(2 * i) * out_stride + jo, e2_fold_wide(xl, dl, fr));
-                        store_e2<GIO>(out + (size_t)(2 * i + 1) * out_stride + jo, e2_fold_wide(xr, dr, fr));
+                        store_e2<GOUT>(out + (size_t)(2 * i) * out_stride + jo, e2_fold_wide(xl, dl, fr));
+                        store_e2<GOUT>(out + (size_t)(2 * i + 1) * out_stride + jo, e2_fold_wide(xr, dr, fr));
                     }
                     gp_cur = nxt;
                 }
@@ -374,7 +374,7 @@ __device__ __forceinline__ void sc_round_body(const T* __restrict__ in, size_t i
                         s0 = e2_add(s0, e2_add(e2_mul(mirror->mk1, x), mirror->mk2));
                         s2 = e2_add(s2, e2_add(e2_mul(mirror->mk1, y), mirror->mk2));
                     }
-                    if (MODE != 2) store_e2<GIO>(out + (size_t)(2 * nb) * out_stride + jo, e2_fold_wide(x, e2_sub(y, x), fr));
+                    if (MODE != 2) store_e2<GOUT>(out + (size_t)(2 * nb) * out_stride + jo, e2_fold_wide(x, e2_sub(y, x), fr));
                 }
             } else {
             for (int i = g; i < nb; i += G) {
@@ -620,6 +620,13 @@ __device__ __forceinline__ int find_item(const StItem* __restrict__ items, int n
     const int b0 = l < nitems ? items[l].blk0 : 0x7fffffff;
     const unsigned long long m = __ballot(b0 <= blk);
     return __builtin_amdgcn_readfirstlane(__popcll(m) - 1);
+}
+// the same for a launch of up to 128 items (st_sums): two loads and two ballots
+__device__ __forceinline__ int find_item128(const StItem* __restrict__ items, int nitems, int blk) {
+    const int l = threadIdx.x & 63;
+    const int b0 = l < nitems ? items[l].blk0 : 0x7fffffff, b1 = l + 64 < nitems ? items[l + 64].blk0 : 0x7fffffff;
+    const unsigned long long m0 = __ballot(b0 <= blk), m1 = __ballot(b1 <= blk);
+    return __builtin_amdgcn_readfirstlane(__popcll(m0) + __popcll(m1) - 1);
 }
 // one step: every item runs its job's round with half = 2^item.h_log2
 template <int KIND, typename T, bool SLOT = false, int MODE = 0>   // SLOT: the first round of ONE slot-form job (StJob::slotw); MODE: sc_round_body
@@ -1059,12 +1066,42 @@ __device__ __forceinline__ E2 gp_combine(E2 P0, E2 P1, E2 Pi, E2 p0, E2 p2, E2 p
     a2 = e2_add(a2, e2_mul(q3, p3));
     return q2;
 }
+// SUMS (the split rounds' sums, round 7): the same pass without a table store - an item with nrounds == 2 sums rounds (h, h - 1) of its
+// job from round h's input alone, which the fold-only launches left in a buffer of its own; any other item of such a launch is one
+// round's sums as k_st_step<.., MODE = 2> forms them. A launch holds up to ST_SUMS_MAX_ITEMS items (find_item128); every item's
+// partials are six slots per workgroup apart, whichever form it takes.
+template <bool SUMS = false>
 __global__ __launch_bounds__(256) void k_st_step2(const StJob* __restrict__ jobs, const StItem* __restrict__ items, int nitems,
                                                   const E2* __restrict__ chal, E2* __restrict__ partials, E2* __restrict__ res) {
-    const int y = find_item(items, nitems, blockIdx.x);
+    const int y = SUMS ? find_item128(items, nitems, blockIdx.x) : find_item(items, nitems, blockIdx.x);
     const StItem& I = items[y];
     const StJob& J = jobs[I.job];
     const int h_log2 = I.h_log2;
+    // (SUMS: up to ST_SUMS_MAX_ITEMS = 128 items share the partials buffer and its tickets - half the slots and half a ticket line each)
+    constexpr size_t PSTRIDE = SUMS ? (size_t)ST_SUMS_PART_BLOCKS * 6 : (size_t)SC_MAX_BLOCKS * 6;
+    constexpr int TSTRIDE = SUMS ? 16 : 32;
+    if constexpr (SUMS) {
+        if (I.nrounds != 2) {   // (uniform over the workgroup)
+            const int rd1 = J.nvars - 1 - h_log2;
+            const size_t half1 = (size_t)1 << h_log2;
+            const int nblk1 = I.nblk, bx1 = (int)blockIdx.x - I.blk0;
+            E2* sm1 = dyn_lds;
+            E2 acc1[3] = {e2_zero(), e2_zero(), e2_zero()};
+            sc_round_body<SC_GRANDPROD, E2, false, false, true, 2>(reinterpret_cast<const E2*>(I.in), I.in_stride, I.out, half1, J.ntab, half1, chal[J.r_off + rd1], J.pw, J.pwr, I.jb_log2,
+                                                                   dyn_lds + SM_SLOTS, acc1, bx1, nblk1, J.p0_only != 0, nullptr, J.mirror ? &J : nullptr);
+            E2* part1 = partials + (size_t)y * PSTRIDE;
+            block_sum_multi<3>(acc1, sm1);
+            if (threadIdx.x == 0) {
+#pragma unroll
+                for (int t = 0; t < 3; t++) {
+                    if (nblk1 == 1) res[J.sums_slot + (size_t)rd1 * 3 + t] = acc1[t];
+                    else part_store(part1 + (size_t)bx1 * 3 + t, acc1[t]);
+                }
+            }
+            if (nblk1 > 1) finish_partials(part1, 3, tickets_of(partials) + y * TSTRIDE, res + J.sums_slot + (size_t)rd1 * 3, sm1, nblk1);
+            return;
+        }
+    }
     const int rd = J.nvars - 1 - h_log2;
     const size_t half = (size_t)1 << h_log2, half2 = half >> 1;
     const size_t ntiles = half >> 8;
@@ -1110,8 +1147,10 @@ __global__ __launch_bounds__(256) void k_st_step2(const StJob* __restrict__ jobs
             w0.A.L = c0.c0; w0.C.L = c0.c1;
             w1.A.L = c1.c0; w1.C.L = c1.c1;
             vm.c0.L = cm.c0; vm.c1.L = cm.c1;
-            const E2 fs = e2_fold_wide(ms, es, fb);
-            if (!odd) store_e2(out + (size_t)(2 * nb) * half2 + jo2, fs);
+            if constexpr (!SUMS) {
+                const E2 fs = e2_fold_wide(ms, es, fb);
+                if (!odd) store_e2(out + (size_t)(2 * nb) * half2 + jo2, fs);
+            }
         }
         // software pipeline over the workgroup's whole (tile, pair) stream (two waves per SIMD cannot hide an HBM round trip behind
         // ~800 instructions otherwise): the next item's four loads go out before this one is computed on, into registers of their
@@ -1145,8 +1184,10 @@ __global__ __launch_bounds__(256) void k_st_step2(const StJob* __restrict__ jobs
                 const u64 c = odd ? el.c1 : gl_mul7_lazy(el.c1);
                 wmac_pair(vi, el.c0, b, c, d);
             }
-            const E2 fx = odd ? mr : ml, fd = odd ? er : el;
-            store_e2(out + (size_t)(2 * i + (odd ? 1 : 0)) * half2 + jo2, e2_fold_wide(fx, fd, fb));
+            if constexpr (!SUMS) {
+                const E2 fx = odd ? mr : ml, fd = odd ? er : el;
+                store_e2(out + (size_t)(2 * i + (odd ? 1 : 0)) * half2 + jo2, e2_fold_wide(fx, fd, fb));
+            }
             cur = nxt;
         }
         gp_combine(we2_reduce(w0), we2_reduce(w1), we2_reduce(wi), p0, p2, p3, acc[0], acc[1], acc[2]);
@@ -1155,7 +1196,7 @@ __global__ __launch_bounds__(256) void k_st_step2(const StJob* __restrict__ jobs
         if (!odd) gp_combine(mine, other, e2(ip, iq), q0, q2, q3, acc[3], acc[4], acc[5]);
     }
     E2* sm = dyn_lds;
-    E2* part = partials + (size_t)y * SC_MAX_BLOCKS * 6;
+    E2* part = partials + (size_t)y * PSTRIDE;
     block_sum_multi<6>(acc, sm);
     if (threadIdx.x == 0) {
 #pragma unroll
@@ -1164,7 +1205,7 @@ __global__ __launch_bounds__(256) void k_st_step2(const StJob* __restrict__ jobs
             else part_store(part + (size_t)bx * 6 + t, acc[t]);
         }
     }
-    if (nblocks > 1) finish_partials(part, 6, tickets_of(partials) + y * 32, res + J.sums_slot + (size_t)rd * 3, sm, nblocks);
+    if (nblocks > 1) finish_partials(part, 6, tickets_of(partials) + y * TSTRIDE, res + J.sums_slot + (size_t)rd * 3, sm, nblocks);
 }
 // Collation shape, two rounds per pass (folded Ext2 tables, weights already in the tables): the round sums are plain
 // sums over the tables; the lane pair (2j', 2j'+1) shares round t+1 as in k_st_step2 - each lane adds up its own folded
@@ -1249,7 +1290,8 @@ static inline size_t sc_lds_bytes(int nv, int bd) { return (SM_SLOTS + (size_t)n
 // runs LDS -> LDS with the thread mapping of the big rounds (sc_round_body: 2^jb threads along j, the rest along the tables), the
 // last one leaves the ntab scalars there as well: copied to final_out, or turned into the layer's claims (gp_claim_epilogue). How many rounds fit depends on the job's table count (st_tail_h: 12 for the two collation
 // tables, 7 for the mirrored top layer, 6 for a full grand-product layer, 9-10 for the few tables of a sharded rank), so a small
-// job spends its whole launch-bound second half in ONE launch. Dynamic LDS: [SM_SLOTS][NV * ST_TAIL_THREADS reduction slots][ntab 2^h0][ntab 2^(h0-1)].
+// job spends its whole launch-bound second half in ONE launch. Dynamic LDS: [SM_SLOTS][NV * ST_TAIL_THREADS reduction slots][ntab 2^h0][ntab 2^(h0-1)]
+// (fold-first form, k_st_tail<.., FF>: [ntab 2^h0][every later level, < ntab 2^h0] where that fits; st_tail_table_bytes).
 constexpr size_t ST_TAIL_LDS_BYTES = 120 * 1024;   // for the two table regions
 constexpr int ST_TAIL_THREADS = 256;               // (512: 92.8 against 84 us for the grand-product tail - the per-round chain is the same and the sums cross more waves)
 int st_tail_h(int ntab, int nvars) {
@@ -1283,7 +1325,18 @@ __device__ __forceinline__ void gp_claim_epilogue(const GpClaimEp* __restrict__ 
         if (threadIdx.x == 0) gstore_e2(res + ep->next_slot, s);
     }
 }
-template <int KIND>
+// FF (grand product; round 7): fold first, sum once. The challenges are known, so round t + 1 needs round t's folds and nothing
+// else (sc_round_body's MODE 1 / 2 on the scale of one workgroup). The item's first round runs whole - it reads HBM, through the global
+// address space here - and so does the second one where every level behind the first does not fit beside it (st_tail_whole_rounds).
+// Then (1) the folds of all remaining rounds, LDS -> LDS with one barrier per round and every level kept: level k (the output of the
+// item's round k, ntab 2^(h0-k) entries) sits behind level k - 1, the first of them behind level 0 or, after two whole rounds, in
+// level 0's place; (2) the sums of all those rounds in one pass without a barrier: a round with half >= 64 takes one pair index per
+// thread, a smaller one spreads the table pairs over the 256 >> h thread groups and adds the groups of a wave up with butterflies,
+// one partial per wave and pair index in `red` (4 (2^h - 1) + 4 2^h slots of three up to h = 5: 756 of the 768); (3) behind ONE
+// barrier thread 2^h + j adds the four waves' partials of (round h, j) - BEFORE the scaling by p_0, p_2, p_3, and with the mirrored
+// job's K1 S + K2 - and a segmented butterfly over wave 0 leaves every small round's three sums; wave 1 adds the wave sums of the
+// larger rounds. Every sum goes to keep[] and from there to the result slots as before.
+template <int KIND, bool FF = false>
 __global__ __launch_bounds__(ST_TAIL_THREADS) void k_st_tail(const StJob* __restrict__ jobs, const StItem* __restrict__ items, const E2* __restrict__ chal,
                                                  E2* __restrict__ res) {
     constexpr int NV = KIND == SC_GRANDPROD ? 3 : 2;
@@ -1320,8 +1373,12 @@ __global__ __launch_bounds__(ST_TAIL_THREADS) void k_st_tail(const StJob* __rest
     __shared__ E2 keep[3 * 32], rch[32];
     if ((int)threadIdx.x < J.nvars - I.rd) rch[threadIdx.x] = chal[J.r_off + I.rd + threadIdx.x];
     __syncthreads();
+    const int R = J.nvars - I.rd;   // rounds of this item
+    int whole = R;
+    if constexpr (FF) whole = ((size_t)(2 * J.ntab) << h0) * sizeof(E2) <= ST_TAIL_LDS_BYTES ? 1 : 2;   // (= st_tail_whole_rounds)
+    if (whole > R) whole = R;
 #pragma unroll 1
-    for (int rd = I.rd; rd < J.nvars; rd++) {
+    for (int rd = I.rd; rd < I.rd + whole; rd++) {
         const int h_log2 = J.nvars - 1 - rd;
         const size_t half = (size_t)1 << h_log2;
         const int jb_log2 = h_log2 < 8 ? h_log2 : 8;
@@ -1332,7 +1389,10 @@ __global__ __launch_bounds__(ST_TAIL_THREADS) void k_st_tail(const StJob* __rest
         const E2 r = rch[rd - I.rd];
         if (rd == 0 && J.base) sc_round_body<KIND, u64, true, false, false>(reinterpret_cast<const u64*>(in), in_stride, out, half, J.ntab, half, r, J.pw, J.pwr, jb_log2, red, acc, 0, 1, p0_only);
         else if (rd == 0) sc_round_body<KIND, E2, true, false, false>(reinterpret_cast<const E2*>(in), in_stride, out, half, J.ntab, half, r, J.pw, J.pwr, jb_log2, red, acc, 0, 1, p0_only);
-        else sc_round_body<KIND, E2, false, false, false>(reinterpret_cast<const E2*>(in), in_stride, out, half, J.ntab, half, r, J.pw, J.pwr, jb_log2, red, acc, 0, 1, p0_only, nullptr, mirror);
+        else if constexpr (FF) {   // (the item's first round reads HBM: loads in the global address space, counted by vmcnt alone)
+            if (rd == I.rd) sc_round_body<KIND, E2, false, false, true, 0, false>(reinterpret_cast<const E2*>(in), in_stride, out, half, J.ntab, half, r, J.pw, J.pwr, jb_log2, red, acc, 0, 1, p0_only, nullptr, mirror);
+            else sc_round_body<KIND, E2, false, false, false>(reinterpret_cast<const E2*>(in), in_stride, out, half, J.ntab, half, r, J.pw, J.pwr, jb_log2, red, acc, 0, 1, p0_only, nullptr, mirror);
+        } else sc_round_body<KIND, E2, false, false, false>(reinterpret_cast<const E2*>(in), in_stride, out, half, J.ntab, half, r, J.pw, J.pwr, jb_log2, red, acc, 0, 1, p0_only, nullptr, mirror);
         block_sum_multi<NV>(acc, sm);
         if (threadIdx.x == 0) {
 #pragma unroll
@@ -1340,6 +1400,125 @@ __global__ __launch_bounds__(ST_TAIL_THREADS) void k_st_tail(const StJob* __rest
         }
         __syncthreads();   // the folded tables of this round are complete in LDS
         in = out; in_stride = half;
+    }
+    if constexpr (FF && KIND == SC_GRANDPROD) if (whole < R) {
+        const int ntab = J.ntab, nb = ntab >> 1, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+        E2* const ffb = whole == 1 ? tab[1] : tab[0];
+        auto lvl = [&](int k) -> E2* {
+            return k < whole ? tab[k & 1] : ffb + (size_t)ntab * (((size_t)2 << (h0 - whole)) - ((size_t)2 << (h0 - k)));
+        };
+        // (1) the folds
+#pragma unroll 1
+        for (int k = whole; k < R; k++) {
+            const int hl = h0 - k;
+            const size_t half = (size_t)1 << hl;
+            const E2* __restrict__ src = lvl(k - 1);
+            E2* __restrict__ dst = lvl(k);
+            const FoldR fr = fold_r(rch[k]);
+            for (size_t e = tid; e < ((size_t)ntab << hl); e += ST_TAIL_THREADS) {
+                const size_t i = e >> hl, j = e & (half - 1);
+                const E2 x = src[i * 2 * half + j], y = src[i * 2 * half + half + j];
+                dst[i * half + dpos(j, half)] = e2_fold_wide(x, e2_sub(y, x), fr);
+            }
+            __syncthreads();
+        }
+        // (2) the sums
+        const bool mir = mirror != nullptr;
+        const E2 mk1 = J.mk1, mk2 = J.mk2;
+#pragma unroll 1
+        for (int k = whole; k < R; k++) {
+            const int hl = h0 - k;
+            const size_t half = (size_t)1 << hl, ts = 2 * half;
+            const E2* __restrict__ src = lvl(k - 1);
+            if (hl >= 6) {
+                E2 a[3] = {e2_zero(), e2_zero(), e2_zero()};
+                for (size_t j = tid; j < half; j += ST_TAIL_THREADS) {
+                    WE2 w0 = we2_zero(), w1 = we2_zero(), wi = we2_zero();
+                    E2 p0 = e2_zero(), p2 = e2_zero(), p3 = e2_zero();
+                    for (int i = 0; i < nb; i++) {
+                        const E2* tl = src + (size_t)(2 * i) * ts + j;
+                        const E2 xl = tl[0], yl = tl[half], xr = tl[ts], yr = tl[ts + half];
+                        const E2 dl = e2_sub(yl, xl), dr = e2_sub(yr, xr);
+                        if (i == 0) { p0 = xl; p2 = e2_add(yl, dl); p3 = e2_add(p2, dl); }
+                        if (!(p0_only && i == 0)) { we2_mac(w0, xl, xr); we2_mac(w1, yl, yr); we2_mac(wi, dl, dr); }
+                    }
+                    E2 s0 = we2_reduce(w0), s2 = we2_reduce(w1);
+                    if (mir) {
+                        const E2* tl = src + (size_t)(2 * nb) * ts + j;
+                        s0 = e2_add(s0, e2_add(e2_mul(mk1, tl[0]), mk2));
+                        s2 = e2_add(s2, e2_add(e2_mul(mk1, tl[half]), mk2));
+                    }
+                    gp_combine(s0, s2, we2_reduce(wi), p0, p2, p3, a[0], a[1], a[2]);
+                }
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    a[c] = wave_sum(a[c]);
+                    if (lane == 0) sm[((hl - 6) * 4 + wave) * 3 + c] = a[c];
+                }
+            } else {
+                const int JB = 1 << hl, jj = tid & (JB - 1), g = tid >> hl, G = ST_TAIL_THREADS >> hl;
+                WE2 w0 = we2_zero(), w1 = we2_zero(), wi = we2_zero();
+                for (int i = g; i < nb; i += G) {
+                    const E2* tl = src + (size_t)(2 * i) * ts + jj;
+                    const E2 xl = tl[0], yl = tl[half], xr = tl[ts], yr = tl[ts + half];
+                    if (!(p0_only && i == 0)) { we2_mac(w0, xl, xr); we2_mac(w1, yl, yr); we2_mac(wi, e2_sub(yl, xl), e2_sub(yr, xr)); }
+                }
+                E2 s[3] = {we2_reduce(w0), we2_reduce(w1), we2_reduce(wi)};
+                for (int m = 32; m >= JB; m >>= 1) {   // the groups of this wave that share a pair index
+#pragma unroll
+                    for (int c = 0; c < 3; c++) s[c] = e2_add(s[c], e2(__shfl_xor((unsigned long long)s[c].c0, m, 64), __shfl_xor((unsigned long long)s[c].c1, m, 64)));
+                }
+                if ((lane >> hl) == 0) {
+#pragma unroll
+                    for (int c = 0; c < 3; c++) red[(4 * (JB - 1) + wave * JB + jj) * 3 + c] = s[c];
+                }
+            }
+        }
+        __syncthreads();
+        // (3) one (round, pair index) per thread of wave 0; the larger rounds' wave sums in wave 1
+        if (tid < 64) {
+            const int hl = tid ? 31 - __clz(tid) : 0;
+            const int JB = 1 << hl, jj = tid - JB, k = h0 - hl;
+            const bool on = tid > 0 && k >= whole;   // (hl <= 5, and k < R as hl >= 0)
+            E2 v[3] = {e2_zero(), e2_zero(), e2_zero()};
+            if (on) {
+                E2 s[3] = {e2_zero(), e2_zero(), e2_zero()};
+                for (int w = 0; w < ST_TAIL_THREADS / 64; w++) {
+#pragma unroll
+                    for (int c = 0; c < 3; c++) s[c] = e2_add(s[c], red[(4 * (JB - 1) + w * JB + jj) * 3 + c]);
+                }
+                const size_t half = (size_t)JB, ts = 2 * half;
+                const E2* __restrict__ src = lvl(k - 1);
+                const E2 xl = src[jj], yl = src[half + jj], dl = e2_sub(yl, xl);
+                const E2 p2 = e2_add(yl, dl);
+                if (mir) {
+                    const E2* tl = src + (size_t)(2 * nb) * ts + jj;
+                    s[0] = e2_add(s[0], e2_add(e2_mul(mk1, tl[0]), mk2));
+                    s[1] = e2_add(s[1], e2_add(e2_mul(mk1, tl[half]), mk2));
+                }
+                gp_combine(s[0], s[1], s[2], xl, p2, e2_add(p2, dl), v[0], v[1], v[2]);
+            }
+            for (int b = 0; b < 5; b++) {   // round h owns lanes [2^h, 2^(h+1)): sums over its 2^h pair indices
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    const E2 o = e2(__shfl_xor((unsigned long long)v[c].c0, 1 << b, 64), __shfl_xor((unsigned long long)v[c].c1, 1 << b, 64));
+                    if (b < hl) v[c] = e2_add(v[c], o);
+                }
+            }
+            if (on && jj == 0) {
+#pragma unroll
+                for (int c = 0; c < 3; c++) keep[k * 3 + c] = v[c];
+            }
+        } else if (tid < 64 + 15) {
+            const int hb = (tid - 64) / 3, c = (tid - 64) % 3, k = h0 - (hb + 6);
+            if (k >= whole) {
+                E2 s = e2_zero();
+                for (int w = 0; w < ST_TAIL_THREADS / 64; w++) s = e2_add(s, sm[(hb * 4 + w) * 3 + c]);
+                keep[k * 3 + c] = s;
+            }
+        }
+        __syncthreads();
+        in = lvl(R - 1);
     }
     if ((int)threadIdx.x < (J.nvars - I.rd) * NV) res[J.sums_slot + (size_t)I.rd * NV + threadIdx.x] = keep[threadIdx.x];
     // the ntab final evaluations (complete in LDS behind the last round's barrier)
@@ -1395,12 +1574,19 @@ void gp_slot_regroup(hipStream_t st, const E2* in, E2* out, const uint8_t* slot_
     const size_t n = ((size_t)nrows + (has_s ? 1 : 0)) << len_log2;
     k_gp_slot_regroup<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(in, out, slot_of, ratio, nrows, nslots, npairs, len_log2, len_log2 - np_log2, has_s ? 1 : 0);
 }
-void st_tail(hipStream_t st, int kind, const StJob* jobs, const StItem* items, int nitems, size_t table_bytes, const E2* chal, E2* res) {
+int st_tail_whole_rounds(int ntab, int h0) { return ((size_t)(2 * ntab) << h0) * sizeof(E2) <= ST_TAIL_LDS_BYTES ? 1 : 2; }
+size_t st_tail_table_bytes(int ntab, int h0, bool fold_first) {
+    const size_t l0 = (size_t)ntab << h0;
+    return (fold_first && h0 >= 1 && st_tail_whole_rounds(ntab, h0) == 1 ? 2 * l0 : l0 + (l0 >> 1)) * sizeof(E2);
+}
+void st_tail(hipStream_t st, int kind, const StJob* jobs, const StItem* items, int nitems, size_t table_bytes, const E2* chal, E2* res, bool fold_first) {
     const size_t lds = (SM_SLOTS + 3 * ST_TAIL_THREADS) * sizeof(E2) + table_bytes;
     static const hipError_t a1 = hipFuncSetAttribute((const void*)k_st_tail<SC_GRANDPROD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((SM_SLOTS + 3 * ST_TAIL_THREADS) * sizeof(E2) + ST_TAIL_LDS_BYTES));
     static const hipError_t a2 = hipFuncSetAttribute((const void*)k_st_tail<SC_COLLATION>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((SM_SLOTS + 3 * ST_TAIL_THREADS) * sizeof(E2) + ST_TAIL_LDS_BYTES));
-    (void)a1; (void)a2;
-    if (kind == SC_GRANDPROD) k_st_tail<SC_GRANDPROD><<<nitems, ST_TAIL_THREADS, lds, st>>>(jobs, items, chal, res);
+    static const hipError_t a3 = hipFuncSetAttribute((const void*)k_st_tail<SC_GRANDPROD, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((SM_SLOTS + 3 * ST_TAIL_THREADS) * sizeof(E2) + ST_TAIL_LDS_BYTES));
+    (void)a1; (void)a2; (void)a3;
+    if (kind == SC_GRANDPROD && fold_first) k_st_tail<SC_GRANDPROD, true><<<nitems, ST_TAIL_THREADS, lds, st>>>(jobs, items, chal, res);
+    else if (kind == SC_GRANDPROD) k_st_tail<SC_GRANDPROD><<<nitems, ST_TAIL_THREADS, lds, st>>>(jobs, items, chal, res);
     else k_st_tail<SC_COLLATION><<<nitems, ST_TAIL_THREADS, lds, st>>>(jobs, items, chal, res);
 }
 
@@ -1412,7 +1598,7 @@ int st_plan_blocks(StItem* items, int nitems, bool rounds2) {
     for (int q = 0; q < nitems; q++) {
         StItem& I = items[q];
         int jb = 8;
-        if (!rounds2) while (jb > 2 && (total << (8 - jb)) < st_min_threads()) jb--;
+        if (!rounds2 && I.nrounds != 2) while (jb > 2 && (total << (8 - jb)) < st_min_threads()) jb--;   // (nrounds == 2: a pair of rounds inside a sums launch, st_sums)
         if (jb > I.h_log2) jb = I.h_log2;
         const size_t ntiles = ((size_t)1 << I.h_log2) >> jb;
         I.jb_log2 = jb;
@@ -1444,8 +1630,14 @@ void st_step(hipStream_t st, int kind, bool base, const StJob* jobs, const StIte
     }
 }
 void st_step2(hipStream_t st, int kind, const StJob* jobs, const StItem* items, int nitems, int grid, const E2* chal, E2* partials, E2* res) {
-    if (kind == SC_GRANDPROD) k_st_step2<<<grid, 256, sc_lds_bytes(0, 256), st>>>(jobs, items, nitems, chal, partials, res);
+    if (kind == SC_GRANDPROD) k_st_step2<false><<<grid, 256, sc_lds_bytes(0, 256), st>>>(jobs, items, nitems, chal, partials, res);
     else k_col_step2<<<grid, 256, sc_lds_bytes(0, 256), st>>>(jobs, items, nitems, chal, partials, res);
+}
+static_assert(HG_TEST_ST_MAX_BLOCKS <= ST_SUMS_PART_BLOCKS && (size_t)ST_SUMS_MAX_ITEMS * ST_SUMS_PART_BLOCKS * 6 <= PARTIALS_E2 && ST_SUMS_MAX_ITEMS * 16 <= PARTIALS_TICKETS,
+              "st_sums: the items of a launch share one partials buffer");
+void st_sums(hipStream_t st, const StJob* jobs, const StItem* items, int nitems, int grid, const E2* chal, E2* partials, E2* res) {
+    if (nitems > ST_SUMS_MAX_ITEMS) throw std::runtime_error("st_sums: too many items in one launch");
+    k_st_step2<true><<<grid, 256, sc_lds_bytes(3, 256), st>>>(jobs, items, nitems, chal, partials, res);
 }
 // ---- PRODSUM: g = sum_i a_i * b_i (Libra / zkCNN reductions), batched over independent instances -----
 // Round rd of job J: inputs are a[i]/b[i] (rd = 0; a in the base field) or the ping-pong buffers; table i of

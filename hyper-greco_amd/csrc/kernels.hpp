@@ -168,11 +168,28 @@ void st_step(hipStream_t st, int kind, bool base, const StJob* jobs, const StIte
 void st_first_hash(hipStream_t st, const StJob* job, const StItem* item, int grid, bool mirror, bool recomp, const E2* chal, E2* partials, E2* res, bool slot = false);
 // fused step (folded Ext2 inputs; grand-product or collation shape): every item runs its job's rounds with half = 2^h_log2 and 2^(h_log2-1)
 void st_step2(hipStream_t st, int kind, const StJob* jobs, const StItem* items, int nitems, int grid, const E2* chal, E2* partials, E2* res);
+// the split rounds' sums in one launch (grand product, folded Ext2 tables; no table is written): an item with nrounds == 2 sums rounds
+// (h_log2, h_log2 - 1) of its job from the first one's input (h_log2 >= ST_STEP2_MIN_H), any other item sums its one round as
+// st_step(.., mode = 2) does. Plan the items with st_plan_blocks(.., false): it gives the pairs one pair index per thread.
+// One launch takes up to ST_SUMS_MAX_ITEMS items (every other step launch: 64): the sums of a prove's split rounds, 108 items at n=32768 k=16,
+// are one launch, not a full one and a short one behind it on the same stream. An item has at most ST_SUMS_PART_BLOCKS workgroups.
+constexpr int ST_SUMS_MAX_ITEMS = 128, ST_SUMS_PART_BLOCKS = 512;
+void st_sums(hipStream_t st, const StJob* jobs, const StItem* items, int nitems, int grid, const E2* chal, E2* partials, E2* res);
 // LDS-resident tail (st_tail): every item runs ALL rounds from its `rd` on in one workgroup; st_tail_h(ntab, nvars) = log2 of the
 // largest half length whose tables fit, i.e. the rounds with half <= 2^st_tail_h belong to the tail; table_bytes = max over the
 // items of ntab * (2^h0 + 2^(h0-1)) * sizeof(E2), h0 = nvars - 1 - rd
 int st_tail_h(int ntab, int nvars);
-void st_tail(hipStream_t st, int kind, const StJob* jobs, const StItem* items, int nitems, size_t table_bytes, const E2* chal, E2* res);
+// fold_first (grand product): the item's first round runs whole - and its second one too where st_tail_whole_rounds(ntab, h0) = 2: the
+// levels behind the first do not fit beside it - then the folds of every remaining round, then all their sums in one pass
+// (kernels.hip: k_st_tail<.., FF>). table_bytes = max over the items of st_tail_table_bytes(ntab, h0, fold_first): never more than
+// the regions st_tail_h sizes the tails for.
+int st_tail_whole_rounds(int ntab, int h0);
+size_t st_tail_table_bytes(int ntab, int h0, bool fold_first);
+void st_tail(hipStream_t st, int kind, const StJob* jobs, const StItem* items, int nitems, size_t table_bytes, const E2* chal, E2* res, bool fold_first = false);
+// the split rounds' sums pair two rounds of a job with at most this many table pairs (n=32768 k=16, 8 proves, 64 items per launch, the
+// two sums launches together: no pairs 926-944 us, pairs up to 24 / 27 / 36 / all table pairs 878-896 / 873-921 / 937 / 1424-1431; one
+// item per round in fold order, the parent's pass, 1071-1100)
+constexpr int ST_SUMS_PAIR_MAX_NB = 24;
 constexpr int ST_STEP2_MIN_H = 9;  // fused steps need 2^h_log2 >= 2 * 256 (one pair index per thread, lane pairs share the second round)
 
 // PRODSUM sum-check instance (g = sum_i a_i b_i), device-visible descriptor; instances of equal nvars are

@@ -92,7 +92,9 @@
         constexpr int fuse_min_h = 15;   // fused pairs of rounds from half = 2^15 up (13 until the slot form: 1.96-1.99 against 1.99-2.01 ms; round 5: 13 / 11 / 9 = 1.864 / 1.905 / 1.980 against 1.831)
         struct Launch { int kind; bool base; int h_log2; bool tail; int nrounds; std::vector<dev::StItem> items; bool hash = false; bool after_seq = false;
                         int mode = 0;   // 1: a split round's folds (main stream), 2: the split rounds' sums (side stream) - kernels.hip: sc_round_body
+                        std::vector<dev::StItem> run;   // mode 2: what is launched for `items` - job-major, consecutive rounds of a job as one item (st_sums); empty: `items`
         };
+        int n_tail_ff = 0, n_tail_whole = 0, n_sum_pairs = 0, n_sum_singles = 0;   // (HG_DEBUG=endgame)
         std::vector<Launch> plan;
         struct Regroup { int job; const E2* in; E2* out; int len_log2; };
         std::vector<Regroup> regroups;
@@ -198,7 +200,25 @@
                     plan.push_back(le);
                 }
             }
-            if (!lsum.items.empty()) plan.push_back(lsum);
+            if (!lsum.items.empty()) {
+                // Rounds (h, h - 1) of one job are summed from round h's input alone (the fused pass folds round h in registers): a third
+                // of the reads less - for a job of few table pairs. The fused pass walks a job's pairs serially in every thread, and
+                // with many pairs that chain, not the bytes, is what the launch waits for (kernels.hpp: ST_SUMS_PAIR_MAX_NB). A job's
+                // rounds follow each other, largest first; a pair is ONE launched item, so none straddles two launches.
+                // HG_SUMS_SINGLE=1: one item per round, in fold order, through st_step.
+                if (!hg_env_on("HG_SUMS_SINGLE")) {
+                    std::vector<dev::StItem> byjob = lsum.items;
+                    std::stable_sort(byjob.begin(), byjob.end(), [](const dev::StItem& a, const dev::StItem& b) { return a.job < b.job; });
+                    for (size_t k = 0; k < byjob.size(); k++) {
+                        dev::StItem it = byjob[k];
+                        if (k + 1 < byjob.size() && byjob[k + 1].job == it.job && byjob[k + 1].h_log2 == it.h_log2 - 1 && it.h_log2 >= dev::ST_STEP2_MIN_H &&
+                            st_jobs[it.job].ntab / 2 <= dev::ST_SUMS_PAIR_MAX_NB) { it.nrounds = 2; k++; n_sum_pairs++; }
+                        else n_sum_singles++;
+                        lsum.run.push_back(it);
+                    }
+                } else n_sum_singles += (int)lsum.items.size();
+                plan.push_back(lsum);
+            }
             // the tail launch: every job's remaining rounds
             {
                 Launch lc{kind, false, 0, true, 0, {}};
@@ -260,11 +280,13 @@
         std::vector<std::vector<int>> grids(plan.size());
         for (size_t li = 0; li < plan.size(); li++) {
             Launch& L = plan[li];
+            std::vector<dev::StItem>& its = L.run.empty() ? L.items : L.run;
+            const size_t batch = L.run.empty() ? MAX_BATCH : (size_t)dev::ST_SUMS_MAX_ITEMS;
             if (!L.tail && !L.after_seq)
-                for (size_t o = 0; o < L.items.size(); o += MAX_BATCH)
-                    grids[li].push_back(dev::st_plan_blocks(L.items.data() + o, (int)std::min<size_t>(MAX_BATCH, L.items.size() - o), L.nrounds == 2));
+                for (size_t o = 0; o < its.size(); o += batch)
+                    grids[li].push_back(dev::st_plan_blocks(its.data() + o, (int)std::min<size_t>(batch, its.size() - o), L.nrounds == 2));
             offs.push_back(flat.size());
-            flat.insert(flat.end(), L.items.begin(), L.items.end());
+            flat.insert(flat.end(), its.begin(), its.end());
         }
         dev::StItem* d_items = ctx->alloc_n<dev::StItem>(flat.size());
         upload(d_items, flat.data(), flat.size() * sizeof(dev::StItem), "upload step items");
@@ -296,11 +318,13 @@
                 if (st_before_gp2) { st_before_gp2(); st_before_gp2 = nullptr; }   // the launches from here on contain grand product #2's jobs
                 continue;
             }
-            for (size_t o = 0; o < L.items.size(); o += MAX_BATCH) {
-                const int cnt = (int)std::min<size_t>(MAX_BATCH, L.items.size() - o);
+            const std::vector<dev::StItem>& its = L.run.empty() ? L.items : L.run;   // (mode 2: the launched form of the items)
+            const size_t batch = L.run.empty() ? MAX_BATCH : (size_t)dev::ST_SUMS_MAX_ITEMS;
+            for (size_t o = 0; o < its.size(); o += batch) {
+                const int cnt = (int)std::min<size_t>(batch, its.size() - o);
                 double bytes = 0, model = 0;
                 if (L.hash) {
-                    const dev::StItem& it = L.items[o];
+                    const dev::StItem& it = its[o];
                     // algorithmic bytes (SURVEY.md 8(d)): the sum-check round plus the passes this launch absorbs - the hash build
                     // (dims, read_ts per chunk; E read, read / write hashes written per memory) and product-tree level 1
                     bytes = round_bytes(it.job, 0, false) + st_fused_bytes[it.job];
@@ -314,15 +338,19 @@
                 if (L.tail) {
                     size_t table_bytes = 0;
                     double design = 0;
+                    // the grand-product tail folds first and sums once (kernels.hip: k_st_tail<.., FF>); HG_TAIL_WHOLE_ROUNDS=1: round by round
+                    const bool tail_ff = L.kind == dev::SC_GRANDPROD && !hg_env_on("HG_TAIL_WHOLE_ROUNDS");
                     std::vector<dev::SlotRegroupJob> rg_jobs;
                     size_t rg_max = 0;
                     for (int q = 0; q < cnt; q++) {
-                        const dev::StItem& it = L.items[o + q];
+                        const dev::StItem& it = its[o + q];
                         const dev::StJob& J = st_jobs[it.job];
                         for (int k = 0; k < it.nrounds; k++) { bytes += round_bytes(it.job, it.rd + k, false); model += round_bytes(it.job, it.rd + k, true); }
                         design += (double)(it.ntab > 0 ? it.ntab : J.ntab) * 2.0 * (double)((size_t)1 << (J.nvars - 1 - it.rd)) * ((J.base && it.rd == 0) ? 8 : 16);
-                        const int h0 = J.nvars - 1 - it.rd;
-                        table_bytes = std::max(table_bytes, (size_t)(it.ntab > 0 ? it.ntab : J.ntab) * (((size_t)1 << h0) + (((size_t)1 << h0) >> 1)) * sizeof(E2));
+                        const int h0 = J.nvars - 1 - it.rd, tn = it.ntab > 0 ? it.ntab : J.ntab;
+                        table_bytes = std::max(table_bytes, dev::st_tail_table_bytes(tn, h0, tail_ff));
+                        if (tail_ff && it.nrounds > dev::st_tail_whole_rounds(tn, h0)) n_tail_ff++;   // (a tail of one or two whole rounds has nothing to fold first)
+                        else if (L.kind == dev::SC_GRANDPROD) n_tail_whole++;
                         for (const Regroup& g : regroups) if (g.job == it.job) {
                             const SlotPlan& sp = st_slot[it.job];
                             rg_jobs.push_back(dev::gp_slot_regroup_job(g.in, g.out, sp.d_slot_of, sp.d_ratio, sp.nrows, sp.nslots, sp.npairs, g.len_log2, (sp.tail_ntab & 1) != 0));
@@ -335,12 +363,12 @@
                         dev::gp_slot_regroup_jobs(st, d_rg, (int)rg_jobs.size(), rg_max);
                     }
                     ctx->prof_begin(cls_tail, bytes, model, design);
-                    dev::st_tail(st, L.kind, d_jobs, d_items + offs[li] + o, cnt, table_bytes, ctx->d_chal, d_res());
+                    dev::st_tail(st, L.kind, d_jobs, d_items + offs[li] + o, cnt, table_bytes, ctx->d_chal, d_res(), tail_ff);
                     ctx->prof_end();
                 } else {
                     double design = 0;
                     for (int q = 0; q < cnt; q++) {
-                        const dev::StItem& it = L.items[o + q];
+                        const dev::StItem& it = its[o + q];
                         const dev::StJob& J = st_jobs[it.job];
                         design += design_bytes(it.job, J.nvars - 1 - it.h_log2, L.nrounds, false);
                         // algorithmic bytes in the per-round accounting of SURVEY.md 8(d): a fused launch is credited with both of
@@ -348,7 +376,7 @@
                         for (int k = 0; k < L.nrounds; k++) { bytes += round_bytes(it.job, J.nvars - 1 - it.h_log2 + k, false); model += round_bytes(it.job, J.nvars - 1 - it.h_log2 + k, true); }
                         if (L.base && it.h_log2 == J.nvars - 1) { bytes += st_fused_bytes[it.job]; model += st_fused_bytes[it.job]; }  // the tree level a first round also writes
                     }
-                    const int grid = grids[li][o / MAX_BATCH];
+                    const int grid = grids[li][o / batch];
                     int cls = L.kind == dev::SC_GRANDPROD ? (L.base ? cls_gp_base : (L.nrounds == 2 ? cls_gp_ext2 : cls_gp_ext)) : (L.base ? cls_col_base : (L.nrounds == 2 ? cls_col_ext2 : cls_col_ext));
                     if (L.mode == 2) {   // the split rounds' sums: beside whatever the main stream does next, joined at the end of the prove
                         if (o == 0) {
@@ -357,10 +385,11 @@
                         }
                         ctx->prof_stream = ctx->stream_sum;
                         ctx->prof_begin(cls_gp_sums, 0, 0, design);
-                        dev::st_step(ctx->stream_sum, L.kind, false, d_jobs, d_items + offs[li] + o, cnt, grid, ctx->d_chal, ctx->d_partials4, d_res(), false, 2);
+                        if (!L.run.empty()) dev::st_sums(ctx->stream_sum, d_jobs, d_items + offs[li] + o, cnt, grid, ctx->d_chal, ctx->d_partials4, d_res());
+                        else dev::st_step(ctx->stream_sum, L.kind, false, d_jobs, d_items + offs[li] + o, cnt, grid, ctx->d_chal, ctx->d_partials4, d_res(), false, 2);
                         ctx->prof_end();
                         ctx->prof_stream = st;
-                        if (o + MAX_BATCH >= L.items.size()) {
+                        if (o + batch >= its.size()) {
                             hip_check(hipEventRecord(ctx->ev_sum[1], ctx->stream_sum), "split rounds: sums done");
                             ctx->sum_pending = true;
                         }
@@ -369,11 +398,13 @@
                     ctx->prof_begin(cls, bytes, model, design);
                     if (L.nrounds == 2) dev::st_step2(st, L.kind, d_jobs, d_items + offs[li] + o, cnt, grid, ctx->d_chal, partials, d_res());
                     else dev::st_step(st, L.kind, L.base, d_jobs, d_items + offs[li] + o, cnt, grid, ctx->d_chal, partials, d_res(),
-                                      L.base && st_jobs[L.items[o].job].slotw != nullptr, L.mode);
+                                      L.base && st_jobs[its[o].job].slotw != nullptr, L.mode);
                     ctx->prof_end();
                 }
             }
         }
+        if (hg_debug("endgame") && (n_tail_ff || n_tail_whole || n_sum_pairs || n_sum_singles))   // what the end of the grand products ran as
+            fprintf(stderr, "[hg endgame] stride tail_fold_first=%d tail_whole=%d sums_pairs=%d sums_singles=%d\n", n_tail_ff, n_tail_whole, n_sum_pairs, n_sum_singles);
         if (st_before_gp) { st_before_gp(); st_before_gp = nullptr; }
         if (st_before_gp2) { st_before_gp2(); st_before_gp2 = nullptr; }
         st_jobs.clear();
