@@ -2177,6 +2177,31 @@ int hg_sumcheck(hg_ctx* ctx, int kind, size_t nv, size_t ntab, const uint64_t* c
     HG_CATCH(-1)
 }
 
+int hg_prodsum_jobs(hg_ctx* ctx, size_t njobs, const size_t* nv, const size_t* npairs, const uint64_t* const* tables, const size_t* eq4,
+                    const uint64_t* kappa2, size_t chain_skip, uint64_t* sums2, uint64_t* evals2) {
+    HG_TRY
+    if (!ctx) throw Error("hg_prodsum_jobs: null argument (a HIP device is required)");
+    prodsum_jobs(ctx, njobs, nv, npairs, tables, eq4, kappa2, chain_skip, sums2, evals2);
+    return 0;
+    HG_CATCH(-1)
+}
+int hg_claim_tables_eq(hg_ctx* ctx, size_t njobs, const size_t* n, const size_t* nclaims, const size_t* point_off, const size_t* alpha_off,
+                       uint64_t* const* out) {
+    HG_TRY
+    if (!ctx) throw Error("hg_claim_tables_eq: null argument (a HIP device is required)");
+    claim_tables_eq(ctx, njobs, n, nclaims, point_off, alpha_off, out);
+    return 0;
+    HG_CATCH(-1)
+}
+int hg_claim_tables_fft(hg_ctx* ctx, size_t njobs, const size_t* L, const int* inverse, const size_t* nclaims, const size_t* point_off,
+                        const size_t* alpha_off, uint64_t* const* out) {
+    HG_TRY
+    if (!ctx) throw Error("hg_claim_tables_fft: null argument (a HIP device is required)");
+    claim_tables_fft(ctx, njobs, L, inverse, nclaims, point_off, alpha_off, out);
+    return 0;
+    HG_CATCH(-1)
+}
+
 int hg_grand_product(hg_ctx* ctx, size_t nb, size_t len, const uint64_t* const* tables, size_t chain_skip, uint8_t* proof, size_t cap,
                      size_t* proof_len, uint64_t* claims2, uint64_t* point2) {
     HG_TRY

@@ -1860,6 +1860,184 @@ void sumcheck_on_tables(hg_ctx* ctx, SumcheckIO& io) {
     }
 }
 
+// hg_prodsum_jobs: the node reductions' PRODSUM flush on caller tables, for kernel-level tests. Every job is queued through
+// sc_prodsum / sc_prodsum_eq and the batch runs as ONE flush_bookkeeping (the eq-factored jobs' point tables) and ONE flush_prodsum,
+// so it takes the launches a prove takes. Everything is checked before anything is uploaded or launched.
+constexpr size_t ENTRY_MAX_CHAIN = (size_t)1 << 20;   // chain positions the kernel-level entries accept
+void prodsum_jobs(hg_ctx* ctx, size_t njobs, const size_t* nv, const size_t* npairs, const u64* const* tables, const size_t* eq4, const u64* kappa2,
+                  size_t chain_skip, u64* sums2, u64* evals2) {
+    const std::string who = "hg_prodsum_jobs: ";
+    if (!nv || !npairs || !tables || !eq4 || !sums2 || !evals2) throw Error(who + "null argument");
+    if (njobs < 1 || njobs > 128) throw Error(who + "njobs must be 1 .. 128");
+    if (chain_skip > ENTRY_MAX_CHAIN) throw Error(who + "chain_skip out of range");
+    size_t total_nv = 0, chain_need = 0;
+    bool any_eq = false;
+    for (size_t q = 0; q < njobs; q++) {
+        const std::string job = " (job " + std::to_string(q) + ")";
+        if (nv[q] < 1 || nv[q] > (size_t)dev::PS_EQ_MAX_VARS) throw Error(who + "nv must be 1 .. " + std::to_string(dev::PS_EQ_MAX_VARS) + job);
+        if (npairs[q] < 1 || npairs[q] > (size_t)dev::PS_MAX_PAIRS) throw Error(who + "npairs must be 1 .. " + std::to_string(dev::PS_MAX_PAIRS) + job);
+        total_nv += nv[q];
+        const size_t form = eq4[4 * q], z_off = eq4[4 * q + 1], w = eq4[4 * q + 2], hib = eq4[4 * q + 3];
+        if (form > 1) throw Error(who + "form must be 0 (plain) or 1 (eq-factored)" + job);
+        if (!form) continue;
+        any_eq = true;
+        if (w > nv[q]) throw Error(who + "w > nv" + job);
+        if (hib >= ((size_t)1 << (nv[q] - w))) throw Error(who + "hib is not below 2^(nv - w)" + job);
+        if (z_off > ENTRY_MAX_CHAIN) throw Error(who + "z_off out of range" + job);
+        if (Prover::eq_tail_rd((int)npairs[q], (int)nv[q]) < 0)
+            throw Error(who + "a job of " + std::to_string(npairs[q]) + " pairs and " + std::to_string(nv[q]) + " variables does not take the eq-factored form" + job);
+        chain_need = std::max(chain_need, z_off + w);
+    }
+    if (any_eq && !kappa2) throw Error(who + "null argument (kappa2 with an eq-factored job)");
+    for (size_t q = 0, t0 = 0, k0 = 0; q < njobs; q++) {
+        const bool eq = eq4[4 * q] != 0;
+        const size_t N = (size_t)1 << nv[q], nt = (eq ? 1 : 2) * npairs[q];
+        for (size_t t = 0; t < nt; t++) {
+            const u64* tab = tables[t0 + t];
+            if (!tab) throw Error(who + "null table (job " + std::to_string(q) + ")");
+            const size_t words = !eq && (t & 1) ? 2 * N : N;
+            for (size_t i = 0; i < words; i++)
+                if (tab[i] >= GL_P) throw Error(who + "non-canonical table word (job " + std::to_string(q) + ", table " + std::to_string(t) + ")");
+        }
+        if (eq) {
+            for (size_t i = 0; i < 2 * npairs[q]; i++) if (kappa2[k0 + i] >= GL_P) throw Error(who + "non-canonical kappa (job " + std::to_string(q) + ")");
+            k0 += 2 * npairs[q];
+        }
+        t0 += nt;
+    }
+    chain_need = std::max(chain_need, chain_skip + total_nv);
+    // the points' coordinates, copied out before anything else asks for the chain
+    std::vector<E2> chain(chain_need);
+    {
+        const u64* c = challenge_chain(2 * chain_need);
+        for (size_t i = 0; i < chain_need; i++) chain[i] = e2(c[2 * i], c[2 * i + 1]);
+    }
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->arena_reset();
+    Prover P(ctx, nullptr);
+    ctx->ensure_chain(chain_need);
+    P.ch.pos = 2 * chain_skip;
+    std::vector<ScHandle> hs;
+    std::vector<size_t> ev_slot;
+    for (size_t q = 0, t0 = 0, k0 = 0; q < njobs; q++) {
+        const bool eq = eq4[4 * q] != 0;
+        const size_t N = (size_t)1 << nv[q], np = npairs[q];
+        const size_t evals = P.slot(2 * np);
+        std::vector<const u64*> a;
+        std::vector<const E2*> b;
+        std::vector<E2*> fa, fb;
+        for (size_t i = 0; i < np; i++) {
+            u64* da = ctx->alloc_n<u64>(N);
+            hip_check(hipMemcpyAsync(da, tables[t0 + (eq ? i : 2 * i)], N * 8, hipMemcpyHostToDevice, ctx->stream), "upload");
+            a.push_back(da);
+            if (!eq) {
+                E2* db = ctx->alloc_n<E2>(N);
+                hip_check(hipMemcpyAsync(db, tables[t0 + 2 * i + 1], N * 16, hipMemcpyHostToDevice, ctx->stream), "upload");
+                b.push_back(db);
+            }
+            fa.push_back(ctx->d_res + evals + 2 * i); fb.push_back(ctx->d_res + evals + 2 * i + 1);
+        }
+        if (eq) {   // z' = (chain[z_off .. z_off + w), bits of hib): what vanilla_node hands to sc_prodsum_eq
+            const size_t z_off = eq4[4 * q + 1], w = eq4[4 * q + 2], hib = eq4[4 * q + 3];
+            std::vector<E2> zp(nv[q]), kappa(np);
+            for (size_t k = 0; k < nv[q]; k++) zp[k] = k < w ? chain[z_off + k] : e2((hib >> (k - w)) & 1u, 0);
+            for (size_t i = 0; i < np; i++) kappa[i] = e2(kappa2[k0 + 2 * i], kappa2[k0 + 2 * i + 1]);
+            hs.push_back(P.sc_prodsum_eq(a, kappa, zp, z_off, (int)w, (unsigned)hib, (int)nv[q], Prover::eq_tail_rd((int)np, (int)nv[q]), fa, fb, true));
+            k0 += 2 * np;
+        } else hs.push_back(P.sc_prodsum(a, b, (int)nv[q], fa, fb));
+        ev_slot.push_back(evals);
+        t0 += (eq ? 1 : 2) * np;
+    }
+    P.flush_bookkeeping();
+    P.flush_prodsum();
+    P.finish();
+    for (size_t q = 0; q < njobs; q++) {
+        memcpy(sums2, ctx->h_res + hs[q].sums_slot, nv[q] * 2 * sizeof(E2));
+        memcpy(evals2, ctx->h_res + ev_slot[q], 2 * npairs[q] * sizeof(E2));
+        sums2 += nv[q] * 2 * 2; evals2 += 2 * npairs[q] * 2;
+    }
+}
+
+// hg_claim_tables_eq / hg_claim_tables_fft: the challenge-only tables of a batch of claims. Every job is queued as a node queues it
+// (queue_eq / fft_queue) and the batch runs as ONE flush_bookkeeping: one eq_ab_plan with its prep and fill launch, one fft_jobs call.
+static dev::ClaimSet entry_claim_set(const std::string& who, size_t q, size_t coords, size_t nclaims, const size_t* point_off, size_t alpha_off, size_t* chain_need) {
+    const std::string job = " (job " + std::to_string(q) + ")";
+    if (nclaims < 1 || nclaims > (size_t)dev::MAX_CLAIMS) throw Error(who + "nclaims must be 1 .. " + std::to_string(dev::MAX_CLAIMS) + job);
+    const bool unit = alpha_off == (size_t)-1;
+    if (unit && nclaims != 1) throw Error(who + "a unit alpha needs a job of one claim" + job);
+    if (!unit && alpha_off > ENTRY_MAX_CHAIN) throw Error(who + "alpha_off out of range" + job);
+    dev::ClaimSet cs;
+    memset(&cs, 0, sizeof(cs));
+    cs.n = (int)nclaims; cs.unit_alpha = unit ? 1 : 0; cs.alpha_off = unit ? 0 : alpha_off;
+    if (!unit) *chain_need = std::max(*chain_need, alpha_off + nclaims);
+    for (size_t a = 0; a < nclaims; a++) {
+        if (point_off[a] > ENTRY_MAX_CHAIN) throw Error(who + "point_off out of range" + job);
+        cs.point_off[a] = point_off[a];
+        *chain_need = std::max(*chain_need, point_off[a] + coords);
+    }
+    return cs;
+}
+void claim_tables_eq(hg_ctx* ctx, size_t njobs, const size_t* n, const size_t* nclaims, const size_t* point_off, const size_t* alpha_off, u64* const* out) {
+    const std::string who = "hg_claim_tables_eq: ";
+    if (!n || !nclaims || !point_off || !alpha_off || !out) throw Error(who + "null argument");
+    if (njobs < 1 || njobs > 64) throw Error(who + "njobs must be 1 .. 64");
+    std::vector<dev::ClaimSet> sets;
+    size_t chain_need = 1;
+    for (size_t q = 0, c0 = 0; q < njobs; q++) {
+        if (n[q] < 1 || n[q] > 24) throw Error(who + "n must be 1 .. 24 (job " + std::to_string(q) + ")");
+        if (!out[q]) throw Error(who + "null output table (job " + std::to_string(q) + ")");
+        sets.push_back(entry_claim_set(who, q, n[q], nclaims[q], point_off + c0, alpha_off[q], &chain_need));
+        c0 += nclaims[q];
+    }
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->arena_reset();
+    Prover P(ctx, nullptr);
+    ctx->ensure_chain(chain_need);
+    std::vector<E2*> tabs;
+    for (size_t q = 0; q < njobs; q++) {
+        tabs.push_back(ctx->alloc_n<E2>((size_t)1 << n[q]));
+        P.queue_eq(tabs[q], (int)n[q], sets[q]);
+    }
+    P.flush_bookkeeping();
+    P.finish();   // (no transcript: the synchronisation and the profile bookkeeping of every entry)
+    for (size_t q = 0; q < njobs; q++)
+        hip_check(hipMemcpyAsync(out[q], tabs[q], sizeof(E2) << n[q], hipMemcpyDeviceToHost, ctx->stream), "download");
+    hip_check(hipStreamSynchronize(ctx->stream), "hg_claim_tables_eq: sync");
+}
+void claim_tables_fft(hg_ctx* ctx, size_t njobs, const size_t* L, const int* inverse, const size_t* nclaims, const size_t* point_off, const size_t* alpha_off,
+                      u64* const* out) {
+    const std::string who = "hg_claim_tables_fft: ";
+    if (!L || !inverse || !nclaims || !point_off || !alpha_off || !out) throw Error(who + "null argument");
+    if (njobs < 1 || njobs > 64) throw Error(who + "njobs must be 1 .. 64");
+    std::vector<dev::ClaimSet> sets;
+    size_t chain_need = 1;
+    for (size_t q = 0, c0 = 0; q < njobs; q++) {
+        if (L[q] < 1 || L[q] > 24) throw Error(who + "L must be 1 .. 24 (job " + std::to_string(q) + ")");
+        if (!out[q]) throw Error(who + "null output table (job " + std::to_string(q) + ")");
+        sets.push_back(entry_claim_set(who, q, L[q], nclaims[q], point_off + c0, alpha_off[q], &chain_need));
+        c0 += nclaims[q];
+    }
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->arena_reset();
+    Prover P(ctx, nullptr);
+    ctx->ensure_chain(chain_need);
+    std::vector<E2*> tabs;
+    for (size_t q = 0; q < njobs; q++) {   // W and scale as hg_ntt builds them
+        const size_t N = (size_t)1 << L[q];
+        u64* W = ctx->alloc_n<u64>(N);
+        u64 w = root_of_unity((int)L[q]);
+        if (inverse[q]) w = gl_inv(w);
+        dev::powers_table(ctx->stream, W, w, N);
+        tabs.push_back(ctx->alloc_n<E2>(N));
+        P.fft_queue.push_back(dev::FftJob{tabs[q], W, inverse[q] ? gl_inv(gl_from_u64(N)) : 1, (int)L[q], sets[q]});
+    }
+    P.flush_bookkeeping();
+    P.finish();   // (no transcript: the synchronisation and the profile bookkeeping of every entry)
+    for (size_t q = 0; q < njobs; q++)
+        hip_check(hipMemcpyAsync(out[q], tabs[q], sizeof(E2) << L[q], hipMemcpyDeviceToHost, ctx->stream), "download");
+    hip_check(hipStreamSynchronize(ctx->stream), "hg_claim_tables_fft: sync");
+}
+
 // prove_grand_product on caller tables (kernel-level parity entry point, hg_grand_product)
 std::vector<uint8_t> grand_product_on_tables(hg_ctx* ctx, size_t nb, size_t len, const u64* const* tables, size_t chain_skip, std::vector<E2>* claims_out,
                                              std::vector<E2>* point_out) {

@@ -301,6 +301,13 @@ struct SumcheckIO {
     std::vector<E2> msgs, point, evals, sums;
 };
 void sumcheck_on_tables(hg_ctx* ctx, SumcheckIO& io);
+// the prover's PRODSUM flush on caller tables, plain and eq-factored jobs in one flush (hg_prodsum_jobs; arguments as in hg.h)
+void prodsum_jobs(hg_ctx* ctx, size_t njobs, const size_t* nv, const size_t* npairs, const u64* const* tables, const size_t* eq4, const u64* kappa2,
+                  size_t chain_skip, u64* sums2, u64* evals2);
+// the challenge-only tables of a batch of claims through flush_bookkeeping (hg_claim_tables_eq, hg_claim_tables_fft)
+void claim_tables_eq(hg_ctx* ctx, size_t njobs, const size_t* n, const size_t* nclaims, const size_t* point_off, const size_t* alpha_off, u64* const* out);
+void claim_tables_fft(hg_ctx* ctx, size_t njobs, const size_t* L, const int* inverse, const size_t* nclaims, const size_t* point_off, const size_t* alpha_off,
+                      u64* const* out);
 E2 mle_eval_device(hg_ctx* ctx, const u64* table_host, size_t nv, const E2* point_host);
 std::vector<uint8_t> grand_product_on_tables(hg_ctx* ctx, size_t nb, size_t len, const u64* const* tables, size_t chain_skip, std::vector<E2>* claims_out,
                                              std::vector<E2>* point_out);

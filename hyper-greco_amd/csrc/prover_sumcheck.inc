@@ -630,13 +630,20 @@
         if (hg_debug("plan")) {   // one line per launch, in launch order, then the tail's
             for (const PsLaunch& L : launches) {
                 int lo = INT_MAX, hi = INT_MIN;
-                std::string hs;
+                std::string hs, gs, ws, ts;
                 for (int q = 0; q < L.cnt; q++) {
                     const dev::PsItem& it = all_items[L.off + q];
                     lo = std::min(lo, it.rd); hi = std::max(hi, it.rd);
                     hs += (q ? "," : "") + std::to_string(jobs[it.job].nvars - 1 - it.rd);
+                    if (L.eq) {
+                        gs += (q ? "," : "") + std::to_string(it.jb_log2);
+                        ws += (q ? "," : "") + std::to_string(it.nblk / it.jb_log2);
+                        ts += (q ? "," : "") + std::to_string(it.pad);
+                    }
                 }
-                fprintf(stderr, "[hg plan] prodsum two=%d eq=%d cnt=%d rd=%d..%d h=[%s]\n", L.two ? 1 : 0, L.eq ? 1 : 0, L.cnt, lo, hi, hs.c_str());
+                // (an eq-factored launch also shows each item's table groups and the workgroups of one group: ps_plan_blocks)
+                fprintf(stderr, "[hg plan] prodsum two=%d eq=%d cnt=%d rd=%d..%d h=[%s]%s\n", L.two ? 1 : 0, L.eq ? 1 : 0, L.cnt, lo, hi, hs.c_str(),
+                        L.eq ? (" grp=[" + gs + "] wg=[" + ws + "] out_tail=[" + ts + "]").c_str() : "");
             }
             int lo = INT_MAX, hi = INT_MIN;
             for (auto& J : jobs) { lo = std::min(lo, J.tail_rd); hi = std::max(hi, J.tail_rd); }
@@ -919,6 +926,7 @@
             }
             dev::PsEqPoint* d = put_jobs(part);
             const int np = (int)part.size();
+            if (hg_debug("plan")) fprintf(stderr, "[hg plan] eqprep points=%d\n", np);
             ctx->prof_begin(cls_aux, pb);
             issue_const(c, wr, 1, [d, np, chal](hipStream_t s) { dev::ps_eq_prep(s, d, np, chal); });
             ctx->prof_end();
@@ -933,6 +941,7 @@
             const int nj = (int)part.size();
             dev::EqAbGrid grid{0, 0};
             if (ab) grid = dev::eq_ab_plan(part.data(), nj);
+            if (hg_debug("plan")) fprintf(stderr, "[hg plan] eqtab jobs=%d ab=%d max_n=%d prep=%d fill=%d rows=%d\n", nj, ab ? 1 : 0, max_n, grid.prep, grid.fill, ab ? part[0].rows : 0);
             dev::EqJob* d = put_jobs(part);
             ctx->prof_begin(cls_aux, eb);
             if (ab) issue_const(c, wr, 2, [d, nj, grid, chal](hipStream_t s) { dev::eq_jobs_ab(s, d, nj, grid, chal); });
@@ -989,6 +998,7 @@
             wr.push_back(crange(fft_tab, tab_entries));
             dev::FftJob* d = put_jobs(part);
             const int nj = (int)part.size();
+            if (hg_debug("plan")) fprintf(stderr, "[hg plan] fftrows jobs=%d max_L=%d max_claims=%d launches=%d\n", nj, max_L, max_claims, dev::fft_jobs_launches(max_L));
             ctx->prof_begin(cls_aux, fb);
             issue_const(c, wr, dev::fft_jobs_launches(max_L), [d, nj, max_L, max_claims, chal, fft_tab](hipStream_t s) { dev::fft_jobs(s, d, nj, max_L, max_claims, chal, fft_tab); });
             ctx->prof_end();

@@ -775,6 +775,47 @@ int hg_sumcheck(hg_ctx* ctx, int kind, size_t nv, size_t ntab, const uint64_t* c
                 const uint64_t* pw, size_t npw, const uint64_t* claim2, size_t chain_skip, uint64_t* msgs,
                 uint64_t* point, uint64_t* evals, uint64_t* sums);
 
+/* The prover's own PRODSUM flush (the Vanilla / FFT node reductions of hg_prove) on caller tables, for kernel-level tests; the
+ *   Goldilocks counterpart of hg_prodsum_jobs_bn254, with its conventions. Job q is a sum-check over 2^nv[q] entries with npairs[q]
+ *   pairs; all jobs go through one prover, one bookkeeping flush and ONE round-synchronised PRODSUM flush, so jobs of different sizes
+ *   and forms share the step launches and the tail launch exactly as in a prove. Job q takes its nv[q] round challenges from the
+ *   chain at chain_skip + sum_{q' < q} nv[q'] (E challenges).
+ *   eq4[4q .. 4q+3] = (form, z_off, w, hib):
+ *     form 0, plain: g = sum_i a_i b_i on tables a_i (2^nv words) and b_i (2^nv (c0, c1) pairs); tables holds a_0, b_0, a_1, b_1, ..;
+ *       the other three words are not read.
+ *     form 1, eq-factored: every b_i = kappa_i eq(z', .) with z' = (chain[z_off .. z_off + w), bits of hib, lowest first) - a table
+ *       that is zero outside block hib of 2^w entries - and no b table exists before the tail; tables holds a_0, a_1, .. only, and
+ *       kappa2 the job's npairs (c0, c1) pairs (the eq-factored jobs' kappas, concatenated in job order; may be null without such a
+ *       job). The job is queued with the first tail round the prover plans for its shape. HG_NO_PS_EQ is not read here.
+ *   sums2: per job nv[q] x (g(0), g(2)) raw round sums, concatenated; evals2: per job the 2 npairs[q] folded values (a_0(r), b_0(r),
+ *   a_1(r), ..), concatenated - b_i(r) = kappa_i eq(z', r) for an eq-factored job.
+ *   HG_DEBUG=plan prints `[hg plan] eqprep points=..` (the point tables' launch), one `[hg plan] prodsum two= eq= cnt= rd= h=[..]` line
+ *   per step launch (an eq-factored launch adds grp=[..] table groups, wg=[..] workgroups per group and out_tail=[..] per item) and the
+ *   `prodsum tail jobs= tail_rd=` line.
+ *   -1 before any launch (hg_last_error names hg_prodsum_jobs) for: a null argument; njobs outside 1..128; nv outside 1..26; npairs
+ *   outside 1..32; a form above 1; a table word or a kappa coordinate >= p (the points' coordinates come from the chain); w > nv;
+ *   hib >= 2^(nv - w); chain_skip or z_off above 2^20; an eq-factored job whose shape does not take the form (the message says
+ *   "does not take the eq-factored form": fewer than two rounds ahead of the tail, or a last pass below 2^9 pairs). */
+int hg_prodsum_jobs(hg_ctx* ctx, size_t njobs, const size_t* nv, const size_t* npairs, const uint64_t* const* tables, const size_t* eq4,
+                    const uint64_t* kappa2, size_t chain_skip, uint64_t* sums2, uint64_t* evals2);
+/* The challenge-only tables of a batch of claims as the prover builds them for the plain node reductions, for kernel-level tests:
+ *   all jobs of a call are queued as a node queues them and run in ONE bookkeeping flush. Claim a of job q has its point at
+ *   chain[point_off[c0 + a] ..] (c0 = sum_{q' < q} nclaims[q'], E challenges) and the weight chain[alpha_off[q] + a];
+ *   alpha_off[q] = SIZE_MAX: unit weight, one claim only. out[q]: host, 2^n[q] (2^L[q]) (c0, c1) pairs.
+ *   hg_claim_tables_eq: out[q] = sum_a alpha_a eq(r_a, .) over n[q] variables (coordinate i belongs to bit i of the index): one plan,
+ *     one factor-table launch and one fill launch for the batch (`[hg plan] eqtab jobs= ab= max_n= prep= fill= rows=`). n <= 24: the
+ *     one-launch form the prover keeps for larger tables (with its summing pass) is not reachable here - no parameter set builds
+ *     such a table.
+ *   hg_claim_tables_fft: the DFT-row tables of FFT nodes, out[q][x] = scale sum_a alpha_a prod_b (1 + r_{a,b} (W[(x 2^b) mod N] - 1)),
+ *     N = 2^L[q], W the powers of the N-th root of unity of hg_ntt (inverse[q]: of its inverse, and scale = 1 / N, else 1): one call
+ *     of the batch kernel for all jobs (`[hg plan] fftrows jobs= max_L= max_claims= launches=`).
+ *   -1 before any launch (hg_last_error names the entry) for: a null argument or output; njobs outside 1..64; n or L outside 1..24;
+ *   nclaims outside 1..32; a unit weight with several claims; point_off or alpha_off above 2^20. */
+int hg_claim_tables_eq(hg_ctx* ctx, size_t njobs, const size_t* n, const size_t* nclaims, const size_t* point_off, const size_t* alpha_off,
+                       uint64_t* const* out);
+int hg_claim_tables_fft(hg_ctx* ctx, size_t njobs, const size_t* L, const int* inverse, const size_t* nclaims, const size_t* point_off,
+                        const size_t* alpha_off, uint64_t* const* out);
+
 /* = prove_grand_product [REF lasso/src/memory_checking/prover.rs:183-266] on nb <= 128 host tables of len = 2^nv base-field values: product
  *   tree on the MSB split, root products, per layer the batched degree-3 sum-check, 2 nb evaluations and the mu fold. The transcript
  *   starts after `chain_skip` E challenges. claims2: nb final claims (E), point2: nv coordinates (E). (Goldilocks counterpart of

@@ -555,3 +555,101 @@ def bn254_fixture_inputs(n=1024, k=1, bits=27):
 
 def elems_be(proof, nbytes):
     return [int.from_bytes(proof[i:i + nbytes], "big") for i in range(0, len(proof), nbytes)]
+
+
+# ---- node reductions and claim tables (tests/test_node_reductions.py; pinned in tests/test_oracle_kats.py) ----------------------------
+# Goldilocks only. Extension elements are (c0, c1) rows of uint64; every table operation is an O(N) call of the oracle's binops.
+def e_chain(n):
+    """The first n E challenges as an (n, 2) limb array (E challenge i = base challenges 2i, 2i + 1)."""
+    return np.array(challenge_chain("goldilocks", 2 * n), dtype=np.uint64).reshape(n, 2)
+
+
+def _e_rows(v, n):
+    """One extension element broadcast to n rows."""
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.uint64).reshape(1, 2), (n, 2)))
+
+
+def e_scale(table, v):
+    """table (n, 2) times the extension element v"""
+    return binop_limbs("goldilocks", True, 2, table, _e_rows(v, len(table)))
+
+
+def eq_table_limbs(point):
+    """eq(point, .) over len(point) variables, coordinate i on bit i of the index, by doubling: the half with bit i set is t z_i, the
+    other half t - t z_i. point: (k, 2) limbs -> (2^k, 2)"""
+    t = np.array([[1, 0]], dtype=np.uint64)
+    for z in np.asarray(point, dtype=np.uint64).reshape(-1, 2):
+        hi = e_scale(t, z)
+        t = np.concatenate([binop_limbs("goldilocks", True, 1, t, hi), hi])
+    return t
+
+
+def windowed_point(chain, z_off, w, hib, nv):
+    """z' of an eq-factored job: the chain run (z_off .. z_off + w), then the bits of hib (lowest first) as field elements. -> (nv, 2)"""
+    z = np.zeros((nv, 2), dtype=np.uint64)
+    z[:w] = chain[z_off:z_off + w]
+    for k in range(w, nv):
+        z[k, 0] = (hib >> (k - w)) & 1
+    return z
+
+
+def eq_factored_b_tables(chain, z_off, w, hib, nv, kappas):
+    """The tables an eq-factored job stands for, materialised: b_i = kappa_i eq(z', .), each as the flat (2 * 2^nv,) array a plain job takes."""
+    eq = eq_table_limbs(windowed_point(chain, z_off, w, hib, nv))
+    return [e_scale(eq, k).reshape(-1) for k in np.asarray(kappas, dtype=np.uint64).reshape(-1, 2)]
+
+
+def eq_claims_table(chain, n, point_offs, alpha_off):
+    """sum_a alpha_a eq(r_a, .): r_a = chain[point_offs[a] .. + n), alpha_a = chain[alpha_off + a] (alpha_off None: one claim, weight 1)"""
+    acc = None
+    for a, po in enumerate(point_offs):
+        t = eq_table_limbs(chain[po:po + n])
+        if alpha_off is not None:
+            t = e_scale(t, chain[alpha_off + a])
+        acc = t if acc is None else binop_limbs("goldilocks", True, 0, acc, t)
+    return acc
+
+
+def powers_limbs(w, n_log2):
+    """w^0 .. w^(2^n_log2 - 1) as words, by doubling (the upper half is the lower half times w^(half))"""
+    t = np.array([1], dtype=np.uint64)
+    for k in range(n_log2):
+        step = np.full(len(t), pow(w, 1 << k, P), dtype=np.uint64)
+        t = np.concatenate([t, binop_limbs("goldilocks", False, 2, t, step)])
+    return t
+
+
+def fft_rows_table(chain, L, inverse, point_offs, alpha_off):
+    """The DFT-row table of an FFT node: F(x) = scale sum_a alpha_a prod_b (1 + r_{a,b} (W[(x 2^b) mod N] - 1)), W the powers of the
+    2^L-th root of unity (inverse: of its inverse, scale = 1 / N, else 1); claims as in eq_claims_table. -> (2^L, 2)"""
+    N = 1 << L
+    w = root_of_unity_f("goldilocks", L)
+    scale = 1
+    if inverse:
+        w, scale = pow(w, P - 2, P), pow(N, P - 2, P)
+    W = powers_limbs(w, L)
+    wm1 = binop_limbs("goldilocks", False, 1, W, np.ones(N, dtype=np.uint64))   # W - 1
+    x = np.arange(N, dtype=np.uint64)
+    one = _e_rows([1, 0], N)
+    acc = None
+    for a, po in enumerate(point_offs):
+        p = _e_rows([scale, 0], N)
+        if alpha_off is not None:
+            p = e_scale(p, chain[alpha_off + a])
+        for b in range(L):
+            d = np.zeros((N, 2), dtype=np.uint64)
+            d[:, 0] = wm1[(x << np.uint64(b)) & np.uint64(N - 1)]
+            p = binop_limbs("goldilocks", True, 2, p, binop_limbs("goldilocks", True, 0, one, e_scale(d, chain[po + b])))
+        acc = p if acc is None else binop_limbs("goldilocks", True, 0, acc, p)
+    return acc
+
+
+def oracle_prodsum(a_tables, b_tables, chain_skip, threads=4):
+    """oracle_sumcheck(2, ..) on the pairs (a_i, b_i) with the job's chain position -> (sums nv x (g(0), g(2)), evals (a_0(r), b_0(r), ..)),
+    both as flat word arrays, the layout hg_prodsum_jobs returns per job"""
+    tabs, flags = [], []
+    for a, b in zip(a_tables, b_tables):
+        tabs += [a, b]
+        flags += [True, False]
+    _, _, evals, sums = oracle_sumcheck(2, tabs, flags, np.zeros((0, 2), dtype=np.uint64), np.array([3, 4], dtype=np.uint64), chain_skip, threads=threads)
+    return sums, evals

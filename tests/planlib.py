@@ -1,5 +1,5 @@
 """Reading the launch-plan lines the library prints on stderr (HG_DEBUG=plan: `[hg plan] ..`, HG_DEBUG=bnplan: `[hg bnplan] ..`), shared
-by the kernel-level suites (test_launch_plans.py, test_transform_paths.py): a case runs its call through `planned`, asserts the
+by the kernel-level suites (test_launch_plans.py, test_transform_paths.py, test_node_reductions.py): a case runs its call through `planned`, asserts the
 lines it got back, and `show_plans` prints them once the test no longer captures (pytest -rA: which launches each row ran)."""
 import re
 

@@ -669,3 +669,111 @@ def test_numpy_forms_of_rand_f_and_edge_f():
     assert len(orclib.rand_f(rng, 2)) == 2
     e = orclib.edge_f(rng, 1 << 12)
     assert e.dtype == np.uint64 and set(e.tolist()) == set(orclib.EDGE_POOL)
+
+
+# ---- the references of tests/test_node_reductions.py against Python integers over GoldilocksExt2 (X^2 = 7) ------------------------------
+def _e2_mul(a, b):
+    return ((a[0] * b[0] + 7 * a[1] * b[1]) % P, (a[0] * b[1] + a[1] * b[0]) % P)
+
+
+def _e2_add(a, b):
+    return ((a[0] + b[0]) % P, (a[1] + b[1]) % P)
+
+
+def _e2_sub(a, b):
+    return ((a[0] - b[0]) % P, (a[1] - b[1]) % P)
+
+
+def _eq_py(z, idx):
+    """eq(z, idx) = prod_i (bit i of idx ? z_i : 1 - z_i)"""
+    acc = (1, 0)
+    for i, zi in enumerate(z):
+        acc = _e2_mul(acc, zi if (idx >> i) & 1 else _e2_sub((1, 0), zi))
+    return acc
+
+
+def _rows(t):
+    return [tuple(int(c) for c in r) for r in np.asarray(t).reshape(-1, 2)]
+
+
+def _kat_points(rng, n):
+    """random points, and points whose coordinates are edge values (0 and 1 among them: Boolean coordinates)"""
+    yield [(rng.randrange(P), rng.randrange(P)) for _ in range(n)]
+    yield [(rng.choice(orclib.EDGE_POOL), rng.choice(orclib.EDGE_POOL)) for _ in range(n)]
+    yield [(rng.choice((0, 1)), 0) for _ in range(n)]
+
+
+def test_eq_table_limbs_matches_python_integers():
+    rng = random.Random(0x4551)
+    for n in range(0, 7):
+        for z in _kat_points(rng, n):
+            got = _rows(orclib.eq_table_limbs(np.array(z, dtype=np.uint64).reshape(n, 2)))
+            assert got == [_eq_py(z, i) for i in range(1 << n)], (n, z)
+
+
+def test_windowed_point_and_the_eq_factored_b_tables():
+    """b_i = kappa_i eq(z', .), z' = (chain run, bits of hib): zero outside block hib of 2^w entries, kappa_i eq(chain run, .) inside;
+    at w = 0 the table is kappa_i at index hib and zero elsewhere."""
+    rng = random.Random(0x57494e)
+    chain = orclib.e_chain(64)
+    ch = _rows(chain)
+    for nv in (1, 3, 6):
+        for w in range(0, nv + 1):
+            for hib in sorted({0, (1 << (nv - w)) - 1, rng.randrange(1 << (nv - w))}):
+                z_off = rng.randrange(40)
+                kappas = [(rng.randrange(P), rng.randrange(P)), (P - 1, 0), (0, 1)]
+                zp = _rows(orclib.windowed_point(chain, z_off, w, hib, nv))
+                assert zp == ch[z_off:z_off + w] + [((hib >> k) & 1, 0) for k in range(nv - w)]
+                tabs = orclib.eq_factored_b_tables(chain, z_off, w, hib, nv, np.array(kappas, dtype=np.uint64))
+                for kap, t in zip(kappas, tabs):
+                    assert t.shape == (2 << nv,)
+                    rows = _rows(t)
+                    for idx in range(1 << nv):
+                        inside = idx >> w == hib
+                        want = _e2_mul(kap, _eq_py(ch[z_off:z_off + w], idx & ((1 << w) - 1))) if inside else (0, 0)
+                        assert rows[idx] == want, (nv, w, hib, idx)
+                        assert rows[idx] == _e2_mul(kap, _eq_py(zp, idx))
+                    if w == 0:
+                        assert [i for i, r in enumerate(rows) if r != (0, 0)] == [hib] and rows[hib] == kap
+
+
+def test_eq_claims_table_matches_python_integers():
+    rng = random.Random(0x434c)
+    chain = orclib.e_chain(128)
+    ch = _rows(chain)
+    for n in (1, 4, 6):
+        for nclaims, unit in ((1, True), (1, False), (2, False), (5, False)):
+            offs = [rng.randrange(100) for _ in range(nclaims)]
+            a_off = None if unit else rng.randrange(100)
+            got = _rows(orclib.eq_claims_table(chain, n, offs, a_off))
+            for i in range(1 << n):
+                want = (0, 0)
+                for a, po in enumerate(offs):
+                    want = _e2_add(want, _e2_mul((1, 0) if unit else ch[a_off + a], _eq_py(ch[po:po + n], i)))
+                assert got[i] == want, (n, nclaims, i)
+
+
+def test_fft_rows_table_matches_python_integers():
+    """F(x) = scale sum_a alpha_a prod_b (1 + r_{a,b} (w^((x 2^b) mod N) - 1)) at L = 1 .. 5, both directions, from pow() alone."""
+    rng = random.Random(0x464654)
+    chain = orclib.e_chain(128)
+    ch = _rows(chain)
+    for L_ in range(1, 6):
+        N = 1 << L_
+        w = orclib.root_of_unity_f("goldilocks", L_)
+        assert [int(v) for v in orclib.powers_limbs(w, L_)] == [pow(w, i, P) for i in range(N)]
+        for inverse in (False, True):
+            ww, sc = (pow(w, P - 2, P), pow(N, P - 2, P)) if inverse else (w, 1)
+            for nclaims, unit in ((1, True), (2, False), (3, False)):
+                offs = [rng.randrange(100) for _ in range(nclaims)]
+                a_off = None if unit else rng.randrange(100)
+                got = _rows(orclib.fft_rows_table(chain, L_, inverse, offs, a_off))
+                for x in range(N):
+                    want = (0, 0)
+                    for a, po in enumerate(offs):
+                        p = (sc, 0) if unit else _e2_mul(ch[a_off + a], (sc, 0))
+                        for b in range(L_):
+                            wx = pow(ww, (x << b) % N, P)
+                            p = _e2_mul(p, _e2_add((1, 0), _e2_mul(ch[po + b], ((wx - 1) % P, 0))))
+                        want = _e2_add(want, p)
+                    assert got[x] == want, (L_, inverse, nclaims, x)
