@@ -56,6 +56,7 @@ EXPORTS = [
     "hg_pcs_commit", "hg_pcs_free", "hg_pcs_open", "hg_pcs_verify", "hg_secrets_commit", "hg_claims_open", "hg_claims_verify",
     "hg_pcs_verify_device", "hg_claims_verify_device", "hg_pcs_verify_device_batch", "hg_claims_verify_batch",
     "hg_pcs_commit_batch", "hg_secrets_commit_batch", "hg_pcs_open_batch", "hg_claims_open_batch",
+    "hg_pcs_open_folded", "hg_pcs_verify_folded", "hg_pcs_verify_folded_device", "hg_claims_open_folded", "hg_claims_verify_folded", "hg_claims_verify_folded_device",
     "hg_secrets_commit_values", "hg_prove_encryptions_committed", "hg_prove_encryptions_committed_bn254",
     "hg_instance_digest", "hg_instance_digest_batch", "hg_values_instance_digest", "hg_bound_seed", "hg_prove_committed_mode", "hg_verify_public_bound", "hg_verify_public_bound_device",
     "hg_verify_public_bound_batch", "hg_instance_digest_group",
@@ -107,6 +108,10 @@ def _two_field_protos(L):
         getattr(L, "hg_claims_verify" + sfx).argtypes = [C.POINTER(HgParams), cp, sz, vp, sz, u64p, sz, cp, sz]
         getattr(L, "hg_pcs_verify_device" + sfx).argtypes = [vp] + getattr(L, "hg_pcs_verify" + sfx).argtypes
         getattr(L, "hg_claims_verify_device" + sfx).argtypes = [vp] + getattr(L, "hg_claims_verify" + sfx).argtypes
+    for name in ("hg_pcs_open", "hg_pcs_verify", "hg_claims_open", "hg_claims_verify"):   # the folded forms take what the unfolded ones take
+        getattr(L, name + "_folded").argtypes = getattr(L, name).argtypes
+    L.hg_pcs_verify_folded_device.argtypes = L.hg_pcs_verify_device.argtypes
+    L.hg_claims_verify_folded_device.argtypes = L.hg_claims_verify_device.argtypes
     L.hg_pcs_free.argtypes, L.hg_pcs_free.restype = [vp], None
     tail = [szp, sz, C.POINTER(cp), szp, sz, C.POINTER(ci), cp, sz]   # claim counts, n_queries, openings, lengths, n, results, reasons, reason_cap
     L.hg_pcs_verify_device_batch.argtypes = L.hg_pcs_verify_device_batch_bn254.argtypes = [vp, C.POINTER(cp), u32p, sz, sz, C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u64p)] + tail
@@ -1360,6 +1365,11 @@ def pcs_opening_bytes_bn254(nvars, n_claims, n_queries=0, log2_row=0):
     return _opening_bytes(32, 32, nvars, n_claims, n_queries, log2_row)
 
 
+def pcs_folded_opening_bytes(nvars, n_queries=0, log2_row=0):
+    """16 (3 V + m) + 32 C + Q (8 R + 32 (c+2)): the exact length of a folded opening, whatever the number of claims."""
+    return 16 * (3 * max(nvars) + len(nvars)) + pcs_opening_bytes(nvars, 1, n_queries, log2_row)
+
+
 def _pcs_protos():
     """the library: the prototypes of the commitment entries are assigned with the others when it is loaded"""
     return lib()
@@ -1499,10 +1509,15 @@ class Commitment:
         lifted into Fr by the signed rule."""
         return cls._secrets_batch("bn254", ctx, params, witnesses, log2_row)
 
-    def _open(self, entry, head, n_claims, tail, n_queries):
+    def _open(self, entry, head, n_claims, tail, n_queries, folded=False):
         """entry(ctx, *head, n_claims, *tail, n_queries, buffer, its size, length out) of the handle's field -> the opening bytes"""
         bn = self.field == "bn254"
-        cap = (pcs_opening_bytes_bn254 if bn else pcs_opening_bytes)(self.nvars, n_claims, n_queries, self.log2_row)
+        if folded:
+            if bn:
+                raise ValueError("folded openings are Goldilocks only")
+            entry, cap = entry + "_folded", pcs_folded_opening_bytes(self.nvars, n_queries, self.log2_row)
+        else:
+            cap = (pcs_opening_bytes_bn254 if bn else pcs_opening_bytes)(self.nvars, n_claims, n_queries, self.log2_row)
         buf, ln = (C.c_uint8 * cap)(), C.c_size_t(0)
         _check(getattr(lib(), entry + ("_bn254" if bn else ""))(_h(self.ctx), *head, n_claims, *tail, n_queries, buf, cap, C.byref(ln)))
         return bytes(memoryview(buf)[:ln.value])
@@ -1517,6 +1532,15 @@ class Commitment:
         """hg_claims_open: the opening of an InputClaims (what verify_public returns) against a Commitment.secrets handle. On a BN254
         handle hg_claims_open_bn254 of an InputClaimsBn254 (what verify_public_bn254 returns)."""
         return self._open("hg_claims_open", (C.byref(params), self.h, claims.claims), claims.n, (_ptr(claims.points),), n_queries)
+
+    def open_folded(self, claims, n_queries=0):
+        """hg_pcs_open_folded: open's claims (at least one) -> a folded opening, whose length does not grow with the claims."""
+        table, pts, vals = _pcs_claim_arrays(claims)
+        return self._open("hg_pcs_open", (self.h, table, _ptr(pts), _ptr(vals)), len(claims), (), n_queries, folded=True)
+
+    def open_claims_folded(self, params, claims, n_queries=0):
+        """hg_claims_open_folded: open_claims as a folded opening."""
+        return self._open("hg_claims_open", (C.byref(params), self.h, claims.claims), claims.n, (_ptr(claims.points),), n_queries, folded=True)
 
     def free(self):
         if self.h:
@@ -1594,18 +1618,19 @@ def claims_open_batch_bn254(ctx, params, cms, claims_list, n_queries=0, reason_c
     return _claims_open_batch_of(InputClaimsBn254, pcs_opening_bytes_bn254, ctx, params, cms, claims_list, n_queries, reason_cap)
 
 
-def _pcs_verify(sfx, arrays, root, nvars, claims, proof, n_queries, log2_row, ctx):
+def _pcs_verify(sfx, arrays, root, nvars, claims, proof, n_queries, log2_row, ctx, form=""):
+    """form "_folded": the folded verifiers"""
     nv = (C.c_uint32 * len(nvars))(*nvars)
     table, pts, vals = arrays(claims)
     args = (bytes(root), nv, len(nvars), log2_row, table, _ptr(pts), _ptr(vals), len(claims), n_queries, bytes(proof), len(proof))
     L = lib()
-    return _decision(getattr(L, "hg_pcs_verify" + sfx)(*args) if ctx is None else getattr(L, "hg_pcs_verify_device" + sfx)(ctx.h, *args))
+    return _decision(getattr(L, "hg_pcs_verify" + form + sfx)(*args) if ctx is None else getattr(L, "hg_pcs_verify" + form + "_device" + sfx)(ctx.h, *args))
 
 
-def _claims_verify(sfx, params, root, claims, opening, n_queries, log2_row, ctx):
+def _claims_verify(sfx, params, root, claims, opening, n_queries, log2_row, ctx, form=""):
     args = (C.byref(params), bytes(root), log2_row, claims.claims, claims.n, _ptr(claims.points), n_queries, bytes(opening), len(opening))
     L = lib()
-    return _decision(getattr(L, "hg_claims_verify" + sfx)(*args) if ctx is None else getattr(L, "hg_claims_verify_device" + sfx)(ctx.h, *args))
+    return _decision(getattr(L, "hg_claims_verify" + form + sfx)(*args) if ctx is None else getattr(L, "hg_claims_verify" + form + "_device" + sfx)(ctx.h, *args))
 
 
 def pcs_verify(root, nvars, claims, proof, n_queries=0, log2_row=0, ctx=None):
@@ -1616,6 +1641,16 @@ def pcs_verify(root, nvars, claims, proof, n_queries=0, log2_row=0, ctx=None):
 def claims_verify(params, root, claims, opening, n_queries=0, log2_row=0, ctx=None):
     """hg_claims_verify, with a context hg_claims_verify_device: an InputClaims against the root of hg_secrets_commit: (accepted, reason)."""
     return _claims_verify("", params, root, claims, opening, n_queries, log2_row, ctx)
+
+
+def pcs_verify_folded(root, nvars, claims, proof, n_queries=0, log2_row=0, ctx=None):
+    """hg_pcs_verify_folded, with a context hg_pcs_verify_folded_device: (accepted, reason) for a folded opening."""
+    return _pcs_verify("", _pcs_claim_arrays, root, nvars, claims, proof, n_queries, log2_row, ctx, "_folded")
+
+
+def claims_verify_folded(params, root, claims, opening, n_queries=0, log2_row=0, ctx=None):
+    """hg_claims_verify_folded, with a context hg_claims_verify_folded_device: claims_verify for a folded opening."""
+    return _claims_verify("", params, root, claims, opening, n_queries, log2_row, ctx, "_folded")
 
 
 def _pcs_verify_batch(call, roots, proofs, reason_cap):

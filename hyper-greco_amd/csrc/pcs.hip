@@ -12,6 +12,8 @@
 // kernel of its own and goes on with the encoding, the leaf hash and the tree of commit_device.
 // The statement digest of a bound proof (hg.h: "Bound proofs") lives here as well: its leaves are hashed by a kernel of the same
 // thread-a-sponge form as the column hashes, its levels are the commitment's.
+// The prover's side of a folded opening (pcs.hpp FoldSource) is here too: the kernel that builds g, the round kernels of the reduction
+// sum-check and their host driver FoldDev, and the device verifier of a folded opening, which reuses the verifier's kernels.
 #include <omp.h>
 #include "pcs.hpp"
 #include "prover.hpp"
@@ -689,6 +691,300 @@ Commitment* commit_device_values(hg_ctx* ctx, const Shape& sh, const u64* const*
     return cm.release();
 }
 
+// ---- the reduction sum-check of a folded opening (pcs.hpp FoldSource; hg.h "Folded openings"): the prover's table-sized work.
+// The raw rows of a handle are its tables, contiguous in table order: table t starts at word s_t = off_t C. g lies in an E array parallel
+// to them. Round 0 reads the rows as they are; the kernel of round j >= 1 folds every live table and its g by r_{j-1} into buffers of
+// half the size and forms round j's sums from the folded entries while it holds them, so a table is read once and written once a round.
+// After j folds table t lies at entry s_t >> j of its buffer: two live tables never overlap there, since s_t' >= s_t + 2^{v_t} and
+// 2^{v_t - j} is whole. The two buffer pairs alternate; the rows are never written. A table of two entries is folded to its two scalars
+// T_t(rho[..v_t)) and g_t(rho[..v_t)) - the first is Y_t - which go to the host with the round's sums; from then on the table is host
+// arithmetic. Hand-off: the sums of a round (48 bytes) and the scalars of the tables that retired come back with ONE SYNCHRONISATION A
+// ROUND (the challenge of round j is hashed from round j's sums, so V round trips are inherent; the rounds on small tables are
+// single-workgroup launches). Every round runs on the device: there is no host finish.
+// Geometry: blockIdx.y = a live table, its units grid-strided over blockIdx.x; at most fold_max_blocks() workgroups in all. A thread
+// keeps the three sums unreduced (gl_wide.hpp), restarted every WFLUSH_TRIPS units, reduces them once, then the wave adds by lane
+// exchange and the workgroup through 192 bytes of LDS; one small workgroup adds the workgroups' partials. Field addition is exact: the
+// order changes no byte.
+constexpr int FOLD_TPB = 256;
+constexpr unsigned FOLD_MAX_BLOCKS = 2048;
+// HG_PCS_FOLD_BLOCKS (tests set it): another bound on the workgroups of a launch, so that a thread's units cross WFLUSH_TRIPS at a small size
+static unsigned fold_max_blocks() {
+    const char* e = getenv("HG_PCS_FOLD_BLOCKS");
+    const long v = e && *e ? atol(e) : (long)FOLD_MAX_BLOCKS;
+    return (unsigned)std::max(1L, std::min(65535L, v));
+}
+struct FoldClaim { u64 lo_at, hi_at; u32 lo_bits, pad; };   // its two factor tables (elements of the staged factors): eq(z, x) = lo[x & (2^lo_bits - 1)] hi[x >> lo_bits]
+struct FoldGTables {
+    u32 nt;
+    u32 lg[MAX_TABLES], claim0[MAX_TABLES + 1];   // v_t; the claims of table t are claim0[t] .. claim0[t+1] of the staged list
+    u64 at[MAX_TABLES];                           // s_t
+};
+struct FoldTables {
+    u32 nt, vec;                                  // vec: every `in` of the rows is even, a pair of words is one 16-byte load
+    u32 lg[MAX_TABLES], id[MAX_TABLES];           // log2 of a live table's entries at the input; its number t
+    u64 in[MAX_TABLES], out[MAX_TABLES];          // where it lies in the input and where it goes in the output (entries)
+};
+__device__ __forceinline__ E2 ld_e2(const E2* p) { const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(p); return e2(v.x, v.y); }
+__device__ __forceinline__ void st_e2(E2* p, E2 v) { *reinterpret_cast<ulonglong2*>(p) = make_ulonglong2(v.c0, v.c1); }
+__device__ __forceinline__ void ld_pair(const u64* p, bool vec, u64& a, u64& b) {
+    if (vec) { const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(p); a = v.x; b = v.y; }
+    else { a = p[0]; b = p[1]; }
+}
+// g_t[x] = sum_{i on t} beta^i eq(z_i, x), every entry written once: a thread owns entry x and walks the table's claims, each a product of
+// two staged factors (beta^i lies in the low one)
+__global__ __launch_bounds__(FOLD_TPB) void k_pcsfold_g(const FoldGTables A, const char* __restrict__ stage, size_t fac_at, E2* __restrict__ g) {
+    const unsigned t = blockIdx.y;
+    const size_t len = (size_t)1 << A.lg[t];
+    const FoldClaim* cl = reinterpret_cast<const FoldClaim*>(stage);
+    const E2* fac = reinterpret_cast<const E2*>(stage + fac_at);
+    for (size_t x = (size_t)blockIdx.x * FOLD_TPB + threadIdx.x; x < len; x += (size_t)gridDim.x * FOLD_TPB) {
+        WE2 acc = we2_zero();
+        E2 sum = e2_zero();
+        int trips = 0;
+        for (unsigned i = A.claim0[t]; i < A.claim0[t + 1]; i++) {
+            const FoldClaim d = cl[i];
+            we2_mac(acc, ld_e2(fac + d.lo_at + (x & (((size_t)1 << d.lo_bits) - 1))), ld_e2(fac + d.hi_at + (x >> d.lo_bits)));
+            if (++trips == WFLUSH_TRIPS) { sum = e2_add(sum, we2_reduce(acc)); acc = we2_zero(); trips = 0; }
+        }
+        st_e2(g + A.at[t] + x, e2_add(sum, we2_reduce(acc)));
+    }
+}
+// the three sums of a thread -> those of its workgroup at out[3 b .. 3 b + 3), b = its number in the grid; every thread calls it
+__device__ __forceinline__ void fold_block_sums(E2 (&s)[3], E2* __restrict__ out) {
+    __shared__ E2 part[FOLD_TPB / 64][3];
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+        for (int m = 32; m >= 1; m >>= 1)
+            s[k] = e2_add(s[k], e2((u64)__shfl_xor((unsigned long long)s[k].c0, m, 64), (u64)__shfl_xor((unsigned long long)s[k].c1, m, 64)));
+    if ((threadIdx.x & 63) == 0)
+        for (int k = 0; k < 3; k++) part[threadIdx.x >> 6][k] = s[k];
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        E2 v = part[0][threadIdx.x];
+        for (int w = 1; w < FOLD_TPB / 64; w++) v = e2_add(v, part[w][threadIdx.x]);
+        out[3 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x) + threadIdx.x] = v;
+    }
+}
+// Round 0: nothing to fold, the table entries are base-field words. A unit is a pair (T0, T1), (g0, g1):
+// s(0) += g0 T0, s(1) += g1 T1, c2 += (g1 - g0) (T1 - T0), an E x F product each
+__global__ __launch_bounds__(FOLD_TPB) void k_pcsfold_round0(const FoldTables A, const u64* __restrict__ rows, const E2* __restrict__ g, E2* __restrict__ partial) {
+    const unsigned t = blockIdx.y;
+    const size_t pairs = (size_t)1 << (A.lg[t] - 1);
+    const u64* T = rows + A.in[t];
+    const E2* G = g + A.in[t];
+    W2 a = w2_zero(), b = w2_zero(), c = w2_zero();
+    int trips = 0;
+    for (size_t u = (size_t)blockIdx.x * FOLD_TPB + threadIdx.x; u < pairs; u += (size_t)gridDim.x * FOLD_TPB) {
+        u64 t0, t1;
+        ld_pair(T + 2 * u, A.vec, t0, t1);
+        const E2 g0 = ld_e2(G + 2 * u), g1 = ld_e2(G + 2 * u + 1);
+        w2_mac_f(a, g0, t0);
+        w2_mac_f(b, g1, t1);
+        w2_mac_f(c, e2_sub(g1, g0), gl_sub(t1, t0));
+        if (++trips == WFLUSH_TRIPS) { a = w2_from(w2_reduce(a)); b = w2_from(w2_reduce(b)); c = w2_from(w2_reduce(c)); trips = 0; }
+    }
+    E2 s[3] = {w2_reduce(a), w2_reduce(b), w2_reduce(c)};
+    fold_block_sums(s, partial);
+}
+// Round j >= 1. A unit is four adjacent entries of T and of g: folded by r = r_{j-1} into two of each, which are stored and enter the sums
+// of round j as E x E products. BASE (round 1): the entries of T are the words of the raw rows. A table of two entries is folded into its
+// two scalars at scal[2 id], scal[2 id + 1] by one thread and enters no sum.
+template <bool BASE>
+__global__ __launch_bounds__(FOLD_TPB) void k_pcsfold_round(const FoldTables A, const u64* __restrict__ rows, const E2* __restrict__ tin, const E2* __restrict__ gin,
+                                                            E2* __restrict__ tout, E2* __restrict__ gout, const E2 r, E2* __restrict__ scal, E2* __restrict__ partial) {
+    const unsigned t = blockIdx.y, lg = A.lg[t];
+    const FoldR f = fold_r(r);
+    const E2* G = gin + A.in[t];
+    // T[2i] + r (T[2i+1] - T[2i])
+    auto fold_t = [&](size_t i) {
+        if constexpr (BASE) {
+            u64 t0, t1;
+            ld_pair(rows + A.in[t] + 2 * i, A.vec, t0, t1);
+            const u64 d = gl_sub(t1, t0);
+            return e2(wreduce(wacc_mul_init(t0, f.r0, d)), gl_mul(f.r1, d));
+        } else {
+            const E2 t0 = ld_e2(tin + A.in[t] + 2 * i);
+            return e2_fold_wide(t0, e2_sub(ld_e2(tin + A.in[t] + 2 * i + 1), t0), f);
+        }
+    };
+    auto fold_g = [&](size_t i) {
+        const E2 g0 = ld_e2(G + 2 * i);
+        return e2_fold_wide(g0, e2_sub(ld_e2(G + 2 * i + 1), g0), f);
+    };
+    WE2 a = we2_zero(), b = we2_zero(), c = we2_zero();
+    E2 s[3] = {e2_zero(), e2_zero(), e2_zero()};
+    if (lg == 1) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            st_e2(scal + 2 * A.id[t], fold_t(0));
+            st_e2(scal + 2 * A.id[t] + 1, fold_g(0));
+        }
+    } else {
+        const size_t units = (size_t)1 << (lg - 2);
+        E2* To = tout + A.out[t];
+        E2* Go = gout + A.out[t];
+        int trips = 0;
+        for (size_t u = (size_t)blockIdx.x * FOLD_TPB + threadIdx.x; u < units; u += (size_t)gridDim.x * FOLD_TPB) {
+            const E2 t0 = fold_t(2 * u), t1 = fold_t(2 * u + 1), g0 = fold_g(2 * u), g1 = fold_g(2 * u + 1);
+            st_e2(To + 2 * u, t0);
+            st_e2(To + 2 * u + 1, t1);
+            st_e2(Go + 2 * u, g0);
+            st_e2(Go + 2 * u + 1, g1);
+            we2_mac(a, g0, t0);
+            we2_mac(b, g1, t1);
+            we2_mac(c, e2_sub(g1, g0), e2_sub(t1, t0));
+            if (++trips == WFLUSH_TRIPS) {
+                s[0] = e2_add(s[0], we2_reduce(a)); s[1] = e2_add(s[1], we2_reduce(b)); s[2] = e2_add(s[2], we2_reduce(c));
+                a = we2_zero(); b = we2_zero(); c = we2_zero();
+                trips = 0;
+            }
+        }
+    }
+    s[0] = e2_add(s[0], we2_reduce(a)); s[1] = e2_add(s[1], we2_reduce(b)); s[2] = e2_add(s[2], we2_reduce(c));
+    fold_block_sums(s, partial);
+}
+// one workgroup: out[k] = sum_b partial[3 b + k]
+__global__ __launch_bounds__(FOLD_TPB) void k_pcsfold_sum(const E2* __restrict__ partial, size_t blocks, E2* __restrict__ out) {
+    E2 s[3] = {e2_zero(), e2_zero(), e2_zero()};
+    for (size_t b = threadIdx.x; b < blocks; b += FOLD_TPB)
+        for (int k = 0; k < 3; k++) s[k] = e2_add(s[k], ld_e2(partial + 3 * b + k));
+    fold_block_sums(s, out);
+}
+
+// The device form of FoldSource. Scratch from the context's arena (reset here; the handle's matrices are its own): g (16 bytes a table
+// entry), the two buffer pairs (a half and a quarter of that for T and for g each), the partials, the sums and the scalars.
+struct FoldDev : FoldSource {
+    const Commitment& cm;
+    hg_ctx* ctx;
+    hipStream_t st;
+    int cls;
+    size_t n_claims;
+    unsigned max_blocks;
+    E2 *d_g, *d_t[2], *d_gg[2], *d_scal, *d_partial, *d_sums;
+    std::vector<E2> h_scal;
+    E2 h_sums[3];
+
+    FoldDev(const Commitment& cm_, const std::vector<Claim>& claims, const std::vector<E2>& bpow) : cm(cm_), ctx(cm_.ctx), n_claims(claims.size()) {
+        const Shape& sh = cm.sh;
+        const size_t m = sh.nvars.size(), W = sh.R << sh.c;
+        hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+        ctx->arena_reset();
+        st = ctx->stream;
+        cls = ctx->prof_class("pcs_fold", false);
+        ctx->prof_stream = st;
+        max_blocks = fold_max_blocks();
+        T.assign(m, e2_zero());
+        G.assign(m, e2_zero());
+        h_scal.assign(2 * m, e2_zero());
+        // the claims in table order; per claim the two factor tables, beta^i in the low one
+        FoldGTables A;
+        memset(&A, 0, sizeof(A));
+        std::vector<FoldClaim> list;
+        std::vector<E2> fac;
+        size_t max_len = 0;
+        for (size_t t = 0; t < m; t++) {
+            const size_t v = (size_t)sh.nvars[t], lo_bits = (v + 1) / 2;
+            if (v == 0) {   // a table of one word is a scalar from the start: T_t() is the word, g_t() = sum beta^i
+                u64 word = 0;
+                hip_check(hipMemcpyAsync(&word, cm.d_rows + (sh.off[t] << sh.c), 8, hipMemcpyDeviceToHost, st), "download a one-word table");
+                hip_check(hipStreamSynchronize(st), "hg_pcs_open_folded: sync");
+                T[t] = e2(word, 0);
+                for (size_t i = 0; i < claims.size(); i++)
+                    if (claims[i].table == t) G[t] = e2_add(G[t], bpow[i]);
+                continue;
+            }
+            for (size_t i = 0; i < claims.size(); i++) {
+                if (claims[i].table != t) continue;
+                std::vector<E2> lo = eq_table(claims[i].point.data(), lo_bits);
+                const std::vector<E2> hi = eq_table(claims[i].point.data() + lo_bits, v - lo_bits);
+                for (E2& x : lo) x = e2_mul(x, bpow[i]);
+                list.push_back(FoldClaim{(u64)fac.size(), (u64)(fac.size() + lo.size()), (u32)lo_bits, 0});
+                fac.insert(fac.end(), lo.begin(), lo.end());
+                fac.insert(fac.end(), hi.begin(), hi.end());
+            }
+            A.lg[A.nt] = (u32)v;
+            A.at[A.nt] = (u64)(sh.off[t] << sh.c);
+            A.nt++;   // (the kernel's table number, which skips the one-word tables; claim0[0] = 0)
+            A.claim0[A.nt] = (u32)list.size();
+            max_len = std::max(max_len, (size_t)1 << v);
+        }
+        const size_t fac_at = (list.size() * sizeof(FoldClaim) + 15) & ~(size_t)15;
+        std::vector<char> stage(fac_at + fac.size() * sizeof(E2) + 16);
+        if (!list.empty()) memcpy(stage.data(), list.data(), list.size() * sizeof(FoldClaim));
+        if (!fac.empty()) memcpy(stage.data() + fac_at, fac.data(), fac.size() * sizeof(E2));
+        try {
+            d_g = ctx->alloc_n<E2>(W);
+            d_t[0] = ctx->alloc_n<E2>(W / 2 + 1);
+            d_gg[0] = ctx->alloc_n<E2>(W / 2 + 1);
+            d_t[1] = ctx->alloc_n<E2>(W / 4 + 1);
+            d_gg[1] = ctx->alloc_n<E2>(W / 4 + 1);
+            d_scal = ctx->alloc_n<E2>(2 * m);
+            d_partial = ctx->alloc_n<E2>(3 * ((size_t)max_blocks + MAX_TABLES));
+            d_sums = ctx->alloc_n<E2>(3);
+        } catch (const std::exception& e) {
+            throw Error(std::string("the context's arena cannot hold the reduction (") + e.what() + ")");
+        }
+        if (!A.nt) return;
+        char* d_stage = ctx->alloc_n<char>(stage.size());
+        hip_check(hipMemcpyAsync(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, st), "upload factor tables");
+        ctx->prof_begin(cls, (double)W * 16 + (double)fac.size() * 16);
+        k_pcsfold_g<<<dim3(blocks_of(max_len, A.nt), A.nt), FOLD_TPB, 0, st>>>(A, d_stage, fac_at, d_g);
+        ctx->prof_end();
+        hip_check(hipStreamSynchronize(st), "hg_pcs_open_folded: sync");   // (the staged copy is a local)
+        hip_check(hipGetLastError(), "hg_pcs_open_folded: launch");
+    }
+    // the workgroups a table of a launch over nt tables whose largest has `units` units
+    unsigned blocks_of(size_t units, unsigned nt) const {
+        const size_t cap = std::max<size_t>(1, max_blocks / nt);
+        return (unsigned)std::max<size_t>(1, std::min(cap, (units + FOLD_TPB - 1) / FOLD_TPB));
+    }
+    void step(size_t j, E2 r, E2 s[3]) override {
+        const Shape& sh = cm.sh;
+        const size_t m = sh.nvars.size(), V = fold_rounds(sh);
+        FoldTables A;
+        memset(&A, 0, sizeof(A));
+        A.vec = sh.c >= 1;
+        bool retire = false;
+        size_t max_units = 1, entries = 0;
+        for (size_t t = 0; t < m; t++) {
+            const size_t v = (size_t)sh.nvars[t], at = sh.off[t] << sh.c;
+            if (v == 0 || v < j) continue;   // a scalar already
+            const size_t lg = j == 0 ? v : v - (j - 1);
+            A.lg[A.nt] = (u32)lg;
+            A.id[A.nt] = (u32)t;
+            A.in[A.nt] = j == 0 ? at : at >> (j - 1);
+            A.out[A.nt] = at >> j;
+            A.nt++;
+            retire |= j > 0 && lg == 1;
+            max_units = std::max(max_units, j == 0 ? (size_t)1 << (lg - 1) : lg == 1 ? 1 : (size_t)1 << (lg - 2));
+            entries += (size_t)1 << lg;
+        }
+        if (s) s[0] = s[1] = s[2] = e2_zero();
+        if (!A.nt) return;
+        const dim3 grid(blocks_of(max_units, A.nt), A.nt);
+        ctx->prof_stream = st;
+        // round 0 reads 8 + 16 bytes an entry, round 1 reads them and writes 16 + 16 for every two, a later round reads 32 and writes 16
+        ctx->prof_begin(cls, (double)entries * (j == 0 ? 24 : j == 1 ? 40 : 48));
+        if (j == 0) k_pcsfold_round0<<<grid, FOLD_TPB, 0, st>>>(A, cm.d_rows, d_g, d_partial);
+        else if (j == 1) k_pcsfold_round<true><<<grid, FOLD_TPB, 0, st>>>(A, cm.d_rows, nullptr, d_g, d_t[0], d_gg[0], r, d_scal, d_partial);
+        else k_pcsfold_round<false><<<grid, FOLD_TPB, 0, st>>>(A, nullptr, d_t[j & 1], d_gg[j & 1], d_t[(j - 1) & 1], d_gg[(j - 1) & 1], r, d_scal, d_partial);
+        if (s) k_pcsfold_sum<<<1, FOLD_TPB, 0, st>>>(d_partial, (size_t)grid.x * grid.y, d_sums);
+        ctx->prof_end();
+        if (s) hip_check(hipMemcpyAsync(h_sums, d_sums, sizeof(h_sums), hipMemcpyDeviceToHost, st), "download the round's sums");
+        if (retire) hip_check(hipMemcpyAsync(h_scal.data(), d_scal, 2 * m * sizeof(E2), hipMemcpyDeviceToHost, st), "download the retired tables' scalars");
+        hip_check(hipStreamSynchronize(st), "hg_pcs_open_folded: sync");
+        hip_check(hipGetLastError(), "hg_pcs_open_folded: launch");
+        ctx->prof_collect();
+        if (s) memcpy(s, h_sums, sizeof(h_sums));
+        for (size_t t = 0; t < m; t++)
+            if (j > 0 && (size_t)sh.nvars[t] == j) { T[t] = h_scal[2 * t]; G[t] = h_scal[2 * t + 1]; }
+        if (j == V && hg_debug("plan"))   // (read at every call: the tests switch it per case)
+            fprintf(stderr, "[hg plan] pcsfold V=%zu dev_rounds=%zu host_rounds=0 tables=%zu claims=%zu\n", V, V, m, n_claims);
+    }
+};
+std::unique_ptr<FoldSource> fold_source_device(const Commitment& cm, const std::vector<Claim>& claims, const std::vector<E2>& bpow) {
+    return std::unique_ptr<FoldSource>(new FoldDev(cm, claims, bpow));
+}
+
 // ---- the Goldilocks policy of the flows of pcs_flow.hpp. A row element is one word, an element of u and a weight an E2: a u vector
 // is encoded as two rows (c0, c1) and a row offset in Row units is a word offset.
 struct GlPcs {
@@ -806,6 +1102,64 @@ void combine_device(const Commitment& cm, const std::vector<CombineJob>& jobs, E
 void columns_device(const Commitment& cm, const std::vector<size_t>& js, u64* cols) { columns_flow<GlPcs>(cm, js, cols); }
 std::string verify_device(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof, size_t len) {
     return verify_flow<GlPcs>(ctx, sh, root, claims, Q, proof, len);
+}
+// The device verifier of a folded opening. The header is host scalar work (folded_header); its body is an opening of one claim -
+// all R rows under the combined weights, at rho[..c), with the value sum_t delta^t Y_t - and goes through verify_flow's kernels as a
+// group of one member whose opening starts behind the header. The kernels run whatever the header's checks gave: a word of the body
+// that is not below p is reported ahead of a failing round, as the host verifier does.
+std::string verify_folded_device(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof, size_t len) {
+    typedef GlPcs F;
+    const size_t C = sh.C(), N = sh.N(), R = sh.R, hb = folded_header_bytes(sh);
+    const std::string who("hg_pcs_verify_folded_device");
+    const std::string bad_len = length_reason(len, folded_opening_bytes(sh, Q));
+    if (!bad_len.empty()) return bad_len;
+    FoldedHeader H = folded_header(sh, root, claims, Q, proof);
+    if (H.noncanonical != ~(size_t)0) return reason_noncanonical(H.noncanonical);
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->arena_reset();
+    hipStream_t st = ctx->stream;
+    const size_t nw = 2 * R, u_units = F::U_ROWS * C * 2;
+    const VerifyTotals t{1, u_units, u_units + Q * R, F::U_ROWS * 2, 1, 2, nw};
+    VbMember desc{};
+    desc.n = 1;
+    desc.proof = hb / 8;
+    std::vector<char> stage(member_block_layout<F>(desc, sh, 1, nw, sizeof(VbMember)));
+    memcpy(stage.data(), &desc, sizeof(VbMember));
+    memcpy(stage.data() + desc.root_at, root, 32);
+    CombineDesc* hd = reinterpret_cast<CombineDesc*>(stage.data() + desc.jobs_at);
+    hd[0].row0 = 0; hd[0].nrows = R; hd[0].woff = 0;
+    hd[1].row0 = 0; hd[1].nrows = R; hd[1].woff = R;
+    memcpy(stage.data() + desc.y_at, &H.y, sizeof(E2));
+    if (sh.c) memcpy(stage.data() + desc.z_at, H.lo.data(), (size_t)sh.c * sizeof(E2));
+    memcpy(stage.data() + desc.w_at, H.rho_pw.data(), R * sizeof(E2));
+    memcpy(stage.data() + desc.w_at + R * sizeof(E2), H.w.data(), R * sizeof(E2));
+    u64* d_proof;
+    VerifyDev<F> d;
+    try {
+        d_proof = ctx->alloc_n<u64>(len / 8);
+        d = verify_alloc<F>(ctx, sh, Q, stage.size(), t, 4);
+    } catch (const std::exception& e) {
+        throw Error(std::string("the context's arena cannot hold the opening (") + e.what() + ")");
+    }
+    Drain drain{st};   // (drains on an error; after the synchronisation below its own is one more, on an idle stream)
+    const int cls = ctx->prof_class(F::CLS_VERIFY, false);
+    ctx->prof_stream = st;
+    const VbGroup vg{1, (u64)Q, (u64)R, (u64)query_stride<F>(sh), sh.c, sh.depth()};
+    hip_check(hipMemcpyAsync(d_proof, proof, len, hipMemcpyHostToDevice, st), "upload opening");
+    hip_check(hipMemcpyAsync(d.stage, stage.data(), stage.size(), hipMemcpyHostToDevice, st), "upload claims");
+    verify_enqueue<F>(ctx, cls, st, 4096, d_proof, d, vg, t, 4);
+    F::absorb_opening(H.tr, proof + hb, 2 * C);
+    const std::vector<size_t> js = F::squeeze_indices(H.tr, N, Q);
+    const std::vector<u64> hj(js.begin(), js.end());
+    verify_enqueue_query<F>(ctx, cls, st, d_proof, d, vg, t, hj.data());
+    u64 cells[4];
+    hip_check(hipMemcpyAsync(cells, d.cells, 32, hipMemcpyDeviceToHost, st), "download verdict");
+    hip_check(hipStreamSynchronize(st), (who + ": sync").c_str());
+    hip_check(hipGetLastError(), (who + ": launch").c_str());
+    ctx->prof_collect();
+    if (cells[0] != PCSV_NONE) return reason_noncanonical(hb + (size_t)cells[0]);
+    if (!H.reason.empty()) return H.reason;
+    return cells_reason(cells, 1);
 }
 std::vector<std::string> verify_device_batch(const char* who, hg_ctx* ctx, const Shape& sh, const std::vector<VerifyItem>& items, size_t Q) {
     return verify_batch_flow<GlPcs>(who, ctx, sh, items, Q);

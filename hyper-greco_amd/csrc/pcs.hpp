@@ -146,10 +146,49 @@ std::string verify_device(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], 
 struct VerifyItem { const uint8_t* root; const std::vector<Claim>* claims; const uint8_t* proof; size_t len; };
 std::vector<std::string> verify_device_batch(const char* who, hg_ctx* ctx, const Shape& sh, const std::vector<VerifyItem>& items, size_t Q);
 
+// ---- folded openings (hg.h "Folded openings"): a sum-check over the committed tables reduces the n claims to one value Y_t a table at
+// the prefixes of one point, which one combined row opens. The opening is a header - 3 coefficients a round, V = max_t v_t rounds,
+// then the m values Y_t - followed by the body of an opening of one claim. Goldilocks only.
+inline size_t fold_rounds(const Shape& sh) { int V = 0; for (int v : sh.nvars) V = v > V ? v : V; return (size_t)V; }
+inline size_t folded_header_bytes(const Shape& sh) { return 16 * (3 * fold_rounds(sh) + sh.nvars.size()); }
+inline size_t folded_opening_bytes(const Shape& sh, size_t Q) { return folded_header_bytes(sh) + opening_bytes(sh, 1, Q); }
+// The prover's side of the reduction, one object an opening. step(j, r, s), j = 0 .. V in turn: the tables still live are folded by r
+// (the challenge of round j - 1; j = 0 folds nothing); a table left with one entry retires - T[t] and G[t] receive the entries of T_t and
+// g_t, the evaluations at rho[..v_t) - and for j < V s = the sums over the tables that stay live of g(0,x') T(0,x'), of g(1,x') T(1,x')
+// and of (g(1,x') - g(0,x')) (T(1,x') - T(0,x')): s_j's value at 0, its value at 1 and its coefficient c2, without the retired tables.
+struct FoldSource {
+    std::vector<E2> T, G;   // per table, valid once it has retired (v_t <= j after step j)
+    virtual void step(size_t j, E2 r, E2 s[3]) = 0;
+    virtual ~FoldSource() {}
+};
+// bpow[i] = beta^i. The host form reads cm.rows; the device form (pcs.hip) builds g and runs every round on the context's stream
+std::unique_ptr<FoldSource> fold_source_host(const Commitment& cm, const std::vector<Claim>& claims, const std::vector<E2>& bpow);
+std::unique_ptr<FoldSource> fold_source_device(const Commitment& cm, const std::vector<Claim>& claims, const std::vector<E2>& bpow);
+// hg_pcs_open_folded: the opening bytes; an Error naming `who` if there is no claim and - naming the lowest failing claim - if a value
+// is not its table's evaluation (round 0 shows that one is wrong, the claims are then evaluated one by one)
+std::vector<uint8_t> open_folded(const char* who, const Commitment& cm, const std::vector<Claim>& claims, size_t Q);
+// hg_pcs_verify_folded: "" = accepted, else the reason
+std::string verify_folded(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof, size_t len);
+// hg_pcs_verify_folded_device (pcs.hip): the same decision and reason; the header on the host, the body through verify_device's kernels
+std::string verify_folded_device(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof, size_t len);
+// What the two folded verifiers share: everything the header decides. The header's words are read (`noncanonical`: the lowest byte
+// offset of one that is not below p, else ~0; the walk then stops), the rounds and the final evaluation checked (`reason`: the first
+// that fails, the walk goes on regardless so that the body's challenges exist) and the body's one claim formed: the transcript with
+// delta and rho squeezed, the R powers of rho, the combined weights over all R rows, the value sum_t delta^t Y_t and the point rho[..c)
+struct FoldedHeader {
+    size_t noncanonical = ~(size_t)0;
+    std::string reason;
+    FsTranscript tr;
+    std::vector<E2> rho_pw, w, lo;
+    E2 y;
+};
+FoldedHeader folded_header(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof);
+
 // ---- what both forms of the verifier share (pcs.cpp): the length check, the transcript up to the column indices, the reasons
 std::string length_reason(const Shape& sh, size_t n_claims, size_t Q, size_t len);   // "" if the length is the opening's
 std::string length_reason(size_t len, size_t want);                                   // the same for a length worked out by the caller
-FsTranscript start_transcript(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q);
+// tag: "hg-pcs-1", or "hg-pcs-fold-1" for a folded opening
+FsTranscript start_transcript(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const char* tag = "hg-pcs-1");
 std::vector<E2> rho_powers(E2 rho, size_t R);
 void absorb_words(FsTranscript& tr, const u64* words, size_t count);                 // the u_i as read: c0, c1 of every element
 std::vector<size_t> squeeze_indices(FsTranscript& tr, size_t N, size_t Q);           // j_q = a squeezed word & (N - 1)

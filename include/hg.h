@@ -413,6 +413,73 @@ int hg_claims_verify(const hg_params* params, const uint8_t root[32], size_t log
 int hg_claims_verify_device(hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n,
                             const uint64_t* points, size_t n_queries, const uint8_t* opening, size_t len);
 
+/* ---- Folded openings: all claims reduced to one point by a sum-check ------------------------------------------------------------
+ * An opening above carries one combined row u_i a claim. All claims of one proof are claims on tables of the same commitment, so the
+ * usual multi-point batch opening of multilinear commitments applies: a sum-check over the committed tables reduces the n claims to
+ * one value Y_t a table at the prefixes of a single point rho, and because those points share their low c coordinates the m values
+ * are opened by ONE combined row. A folded opening carries two rows (proximity and combined) and 3 V + m field elements whatever n
+ * is: 1 832 816 bytes against 3 338 912 for the 47 claims of n=32768 k=16, and the transcript hashes 64 KB of u instead of 1.5 MB.
+ * A second set of entries with its own transcript tag; hg_pcs_open and its neighbours, their bytes and "hg-pcs-1" are unchanged.
+ *
+ * The scheme, in the notation of the section above; V = max_t v_t, n >= 1 claims (t_i, z_i, y_i), challenges are E elements.
+ *   Transcript. Absorbing; its hash state starts as the 13 ASCII bytes "hg-pcs-fold-1" followed by exactly what "hg-pcs-1" appends
+ *     after its tag: the root, c, m, v_0 .. v_{m-1}, Q, n (4-byte LE), per claim t_i, the point's words and the value's words. Every
+ *     element written below is absorbed (its two words, 8-byte LE, c0 first) and appears in the opening big-endian.
+ *   1. beta = a squeezed E challenge. S = sum_i beta^i y_i. For every table g_t(x) = sum_{i: t_i = t} beta^i eq(z_i, x) on v_t
+ *      variables (zero for a table without a claim): sum_t sum_x g_t(x) T_t(x) = S.
+ *   2. V rounds, the lowest variable first; folding by r is hg_fold's T'[j] = T[2j] + r (T[2j+1] - T[2j]). In round j the prover
+ *      writes the coefficients c0, c1, c2 of s_j(X) = sum_t s_{j,t}(X), then r_j is squeezed. For v_t > j, s_{j,t}(X) = sum_{x'}
+ *      g_t^(j)(X, x') T_t^(j)(X, x') over the tables folded by r_0 .. r_{j-1}. For v_t <= j, s_{j,t}(X) = K_t prod_{v_t <= j' < j}
+ *      (1 - r_j') (1 - X) with K_t = g_t(rho[..v_t)) T_t(rho[..v_t)): a table that has run out of variables counts as extended by zero
+ *      over the remaining ones. rho = (r_0 .. r_{V-1}).
+ *   3. The prover writes Y_t = T_t(rho[0..v_t)), t = 0 .. m-1.
+ *   4. delta, then rho' are squeezed. u_0[j] = sum_{r<R} rho'^r row_r[j]; u_1[j] = sum_t delta^t sum_{r < 2^{v_t-c}}
+ *      eq(rho[c..v_t))[r] row_{off_t+r}[j]. u_0, then u_1 are written.
+ *   5. Q column indices and 6. per query the R column words and the c+2 siblings, exactly as in "hg-pcs-1".
+ *   Layout: a header of 16 (3 V + m) bytes - the round coefficients, then the Y_t - followed by a body that has exactly the layout of
+ *     an "hg-pcs-1" opening with one claim: u_0, u_1, Q x (8 R + 32 (c+2)). Length: exactly 16 (3 V + m) + 32 C + Q (8 R + 32 (c+2)).
+ *   Verification (hg_pcs_verify_folded on the host, hg_pcs_verify_folded_device on a context), in this order, the first failure is
+ *     the reason:  1. the exact length ("pcs: the opening has .. bytes, .. expected", with the folded length);  2. every element and
+ *     column word below p ("pcs: non-canonical word at byte ..", the lowest offset, counted from the start of the folded opening);
+ *     3. for j ascending 2 c0 + c1 + c2 == claim_j, claim_0 = S, claim_{j+1} = s_j(r_j) ("pcs: fold round j does not match the
+ *     running claim");  4. claim_V == sum_t Y_t g_t(rho[..v_t)) prod_{j >= v_t} (1 - rho_j), g_t evaluated from the claims in n V
+ *     products ("pcs: fold final evaluation mismatch");  5. <u_1, eq(rho[..c))> == sum_t delta^t Y_t ("pcs: evaluation mismatch at
+ *     claim 0");  6. per query, ascending: the Merkle path, proximity, then sum_t delta^t sum_r eq(rho[c..v_t))[r] col[off_t + r] ==
+ *     Enc(u_1)[j_q] ("pcs: claim 0 inconsistent at query q"), the first two with the texts of hg_pcs_verify.
+ *   Soundness is the beta and delta combinations plus the sum-check over E, on top of what the opening above claims; no more is
+ *   claimed. Still not zero knowledge.
+ * Contracts are those of the unfolded entries unless stated. Goldilocks only, single calls only: there are no batch forms, no BN254
+ * forms, and hg_prove_encryptions_committed does not fold.
+ * hg_pcs_open_folded: hg_pcs_open's arguments. n_claims == 0 is -1 ("<function>: a folded opening needs a claim"; the proximity
+ *   test alone is hg_pcs_open). *len = the length also when cap is too small. A value that is not its table's evaluation is refused
+ *   with hg_pcs_open's text under this name, naming the lowest failing claim: the prover sees that round 0's s(0) + s(1) is not S
+ *   and only then evaluates the claims one by one. A BN254 handle or a handle of another context is -1. The host form (ctx == NULL)
+ *   is the byte reference. The device form builds g in HBM (16 bytes a table entry, 28 MB at n=32768 k=16) with one kernel from
+ *   per-claim factor tables staged in one copy, then runs one launch a round on the context's stream with scratch from its arena:
+ *   every live table pair is folded by the previous challenge and enters the round's sums in the same pass (round 0 reads the
+ *   handle's raw rows, which are never written); the three sums come back once a round (one synchronisation a round), a table that
+ *   has run out of variables continues as two scalars on the host, the Y_t come out of the last fold. u_0 and u_1 are two row
+ *   combinations of R rows through hg_pcs_open's kernel, the columns through its gather. Profiler class pcs_fold. Not concurrently
+ *   with another call on the same context.
+ * hg_pcs_verify_folded: hg_pcs_verify's arguments and -1 cases, and n_claims == 0 as above. Host only.
+ * hg_pcs_verify_folded_device: the same decision and reason on every input, also where several checks fail at once (a non-canonical
+ *   column word together with a failing round reports the word). The header's checks are host scalar work; the body goes through
+ *   the kernels of hg_pcs_verify_device as an opening of one claim that starts behind the header.
+ * hg_claims_open_folded / hg_claims_verify_folded / hg_claims_verify_folded_device: the same under the mapping of hg_claims_open /
+ *   hg_claims_verify, on an hg_input_claim array as hg_verify_public* returns it. */
+int hg_pcs_open_folded(hg_ctx* ctx, const void* commitment, const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n_claims,
+                       size_t n_queries, uint8_t* proof, size_t cap, size_t* len);
+int hg_pcs_verify_folded(const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table, const uint64_t* points,
+                         const uint64_t* values, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len);
+int hg_pcs_verify_folded_device(hg_ctx* ctx, const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table,
+                                const uint64_t* points, const uint64_t* values, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len);
+int hg_claims_open_folded(hg_ctx* ctx, const hg_params* params, const void* commitment, const void* claims, size_t n, const uint64_t* points,
+                          size_t n_queries, uint8_t* opening, size_t cap, size_t* len);
+int hg_claims_verify_folded(const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points,
+                            size_t n_queries, const uint8_t* opening, size_t len);
+int hg_claims_verify_folded_device(hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n,
+                                   const uint64_t* points, size_t n_queries, const uint8_t* opening, size_t len);
+
 /* hg_pcs_verify_device_batch: hg_pcs_verify_device for a run of n openings of ONE shape (nvars, n_tables, log2_row) and one n_queries.
  *   Item i has its own root roots[i] (32 bytes), its own claims - n_claims[i] of them, 0 allowed; tables[i], points[i], values[i]
  *   laid out as hg_pcs_verify_device takes them, and may be NULL where n_claims[i] == 0 - and its opening proofs[i] of lens[i] bytes.
