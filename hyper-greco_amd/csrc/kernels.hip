@@ -615,7 +615,8 @@ __device__ __forceinline__ void st_io(const StJob& J, int rd, const void*& in, s
 // The items of a launch share a 1-D grid: item y owns workgroups [blk0, blk0 + nblk).
 // (a launch holds at most 64 items: ONE 64-lane load of the items' first workgroups and a ballot, instead of a binary search whose six
 // dependent loads stood at the head of every workgroup of every round launch)
-__device__ __forceinline__ int find_item(const StItem* __restrict__ items, int nitems, int blk) {
+template <typename Item>   // (StItem, StFoldRun)
+__device__ __forceinline__ int find_item(const Item* __restrict__ items, int nitems, int blk) {
     const int l = threadIdx.x & 63;
     const int b0 = l < nitems ? items[l].blk0 : 0x7fffffff;
     const unsigned long long m = __ballot(b0 <= blk);
@@ -661,6 +662,69 @@ __global__ __launch_bounds__(256) void k_st_step(const StJob* __restrict__ jobs,
         }
     }
     if (nblocks > 1) finish_partials(part, NV, tickets_of(partials) + y * 32, res + J.sums_slot + (size_t)rd * NV, sm, nblocks);
+}
+// ---- runs of fold-only rounds (kernels.hpp: StFoldRun) ---------------------------------------------------------------------
+// A workgroup walks (table, tile) units of its item. The tile's P pair indices of round h0 are folded from HBM (two 16-byte loads per
+// pair index, contiguous across the wave: load_xy) into LDS in logical order; level k + 1 then reads its pair (2t, 2t + 1) of level
+// k from LDS, WRITES that pair to level k's buffer - position t of the lower and of the upper half (dpos of 2t, 2t + 1), both
+// contiguous across the wave - and folds it with round h0 - k - 1's challenge. The run's last level goes out from registers at dpos.
+// The two LDS levels ping-pong, one barrier a round; the next unit's loads are requested ahead of the level loop (a conditional
+// request: hipcc waits for it with the current unit's values, DESIGN.md 5d - measured as it is, 109 us per prove at n=32768 k=16).
+__global__ __launch_bounds__(256) void k_st_fold_runs(const StJob* __restrict__ jobs, const StFoldRun* __restrict__ items, int nitems, const E2* __restrict__ chal) {
+    constexpr int NL = (1 << ST_FOLD_TILE_MAX_LOG2) / 256 > 0 ? (1 << ST_FOLD_TILE_MAX_LOG2) / 256 : 1;   // pair indices per thread at level 0
+    static_assert((1 << ST_FOLD_TILE_MAX_LOG2) <= 2 * 256, "k_st_fold_runs: level 1 of a tile is one entry per thread");
+    __shared__ E2 lv0[1 << ST_FOLD_TILE_MAX_LOG2], lv1[1 << (ST_FOLD_TILE_MAX_LOG2 - 1)];
+    const int y = find_item(items, nitems, blockIdx.x);
+    const StFoldRun& I = items[y];
+    const StJob& J = jobs[I.job];
+    const int h0 = I.h0, nr = I.nrounds, p = I.tile_log2, P = 1 << p, tid = threadIdx.x;
+    const int nblk = I.nblk, bx = (int)blockIdx.x - I.blk0;
+    const size_t half0 = (size_t)1 << h0, units = (size_t)J.ntab << (h0 - p);
+    const E2* rch = chal + J.r_off + (J.nvars - 1 - h0);   // the challenge of round h0 - k at rch[k]
+    const E2* in = I.in; const size_t in_stride = I.in_stride;
+    auto fetch = [&](size_t u, E2* x, E2* yv) {
+        const size_t tab = u >> (h0 - p), j0 = (u & ((half0 >> p) - 1)) << p;
+#pragma unroll
+        for (int q = 0; q < NL; q++) if (tid + q * 256 < P) load_xy<E2, false>(in + tab * in_stride, j0 + tid + q * 256, half0, x[q], yv[q]);
+    };
+    E2 cx[NL], cy[NL];
+    if ((size_t)bx < units) fetch(bx, cx, cy);
+    for (size_t u = bx; u < units; u += nblk) {
+        const size_t tab = u >> (h0 - p), j0 = (u & ((half0 >> p) - 1)) << p;
+        E2 nx[NL], ny[NL];
+        if (u + nblk < units) fetch(u + nblk, nx, ny);
+        {
+            const FoldR fr = fold_r(rch[0]);
+#pragma unroll
+            for (int q = 0; q < NL; q++) {
+                const int l = tid + q * 256;
+                if (l < P) {
+                    const E2 v = e2_fold_wide(cx[q], e2_sub(cy[q], cx[q]), fr);
+                    if (nr == 1) store_e2(I.out[0] + tab * half0 + dpos(j0 + l, half0), v);
+                    else lv0[l] = v;
+                }
+            }
+        }
+        for (int k = 1; k < nr; k++) {
+            __syncthreads();
+            const E2* src = (k & 1) ? lv0 : lv1;
+            E2* dst = (k & 1) ? lv1 : lv0;
+            const size_t hk = half0 >> k;   // level k's length: half the length of level k - 1
+            if (tid < (P >> k)) {
+                const size_t jk = (j0 >> k) + tid;
+                const E2 x = src[2 * tid], yv = src[2 * tid + 1];
+                E2* lo = I.out[k - 1] + tab * (2 * hk);
+                store_e2(lo + jk, x);
+                store_e2(lo + hk + jk, yv);
+                const E2 v = e2_fold_wide(x, e2_sub(yv, x), fold_r(rch[k]));
+                if (k == nr - 1) store_e2(I.out[k] + tab * hk + dpos(jk, hk), v);
+                else dst[tid] = v;
+            }
+        }
+        __syncthreads();   // (the next unit's level 0 overwrites what the last level may still be reading)
+#pragma unroll
+        for (int q = 0; q < NL; q++) { cx[q] = nx[q]; cy[q] = ny[q]; }
+    }
 }
 // ---- limbs without the limb table (kernels.hpp: LimbSrc) -----------------------------------------------------------------
 // the four limbs of row j in one word: the node input masked to its lookup's width, 0 beyond `rows`; limb c of it
@@ -1628,6 +1692,23 @@ void st_step(hipStream_t st, int kind, bool base, const StJob* jobs, const StIte
         if (base) k_st_step<SC_COLLATION, u64><<<grid, 256, lds, st>>>(jobs, items, nitems, chal, partials, res);
         else k_st_step<SC_COLLATION, E2><<<grid, 256, lds, st>>>(jobs, items, nitems, chal, partials, res);
     }
+}
+int st_plan_fold_blocks(StFoldRun* items, int nitems, const StJob* host_jobs, int tile_log2) {
+    if (nitems > 64 || tile_log2 < 1 || tile_log2 > ST_FOLD_TILE_MAX_LOG2) throw std::runtime_error("st_plan_fold_blocks: items or tile out of range");
+    int blk = 0;
+    for (int q = 0; q < nitems; q++) {
+        StFoldRun& I = items[q];
+        I.tile_log2 = std::min(tile_log2, I.h0);
+        if (I.h0 < 0 || I.nrounds < 1 || I.nrounds > I.tile_log2 + 1) throw std::runtime_error("st_plan_fold_blocks: a run longer than its tile holds");
+        const size_t units = (size_t)host_jobs[I.job].ntab << (I.h0 - I.tile_log2);
+        I.blk0 = blk;
+        I.nblk = (int)std::min<size_t>(units, (size_t)st_max_blocks());
+        blk += I.nblk;
+    }
+    return blk;
+}
+void st_fold_runs(hipStream_t st, const StJob* jobs, const StFoldRun* items, int nitems, int grid, const E2* chal) {
+    k_st_fold_runs<<<grid, 256, 0, st>>>(jobs, items, nitems, chal);
 }
 void st_step2(hipStream_t st, int kind, const StJob* jobs, const StItem* items, int nitems, int grid, const E2* chal, E2* partials, E2* res) {
     if (kind == SC_GRANDPROD) k_st_step2<false><<<grid, 256, sc_lds_bytes(0, 256), st>>>(jobs, items, nitems, chal, partials, res);

@@ -174,6 +174,25 @@ void st_step2(hipStream_t st, int kind, const StJob* jobs, const StItem* items, 
 // One launch takes up to ST_SUMS_MAX_ITEMS items (every other step launch: 64): the sums of a prove's split rounds, 108 items at n=32768 k=16,
 // are one launch, not a full one and a short one behind it on the same stream. An item has at most ST_SUMS_PART_BLOCKS workgroups.
 constexpr int ST_SUMS_MAX_ITEMS = 128, ST_SUMS_PART_BLOCKS = 512;
+// A run of fold-only rounds of one grand-product job (folded Ext2 tables) in ONE launch: rounds h0, h0 - 1, .., h0 - nrounds + 1.
+// Round t + 1 folds the logical pairs (2j, 2j + 1) of what round t wrote, so a workgroup that holds P = 2^tile_log2 consecutive pair
+// indices of round h0 of one table folds that tile log2(P) + 1 rounds deep on its own: no sums, no partials, no tickets. Every level
+// is written to its round's own buffer exactly as st_step(.., mode = 1) writes it (de-interleaved, stride = the round's half length):
+// the sums pass and the tail read them from there.
+constexpr int ST_FOLD_TILE_MAX_LOG2 = 9, ST_FOLD_MAX_ROUNDS = ST_FOLD_TILE_MAX_LOG2 + 1;
+constexpr int ST_FOLD_TILE_LOG2 = 9;   // (12 KB of levels per workgroup; the workload's longest run, 9 rounds, is one launch)
+struct StFoldRun {
+    int job;
+    int h0, nrounds;   // first round's half length (log2); nrounds <= min(tile_log2, h0) + 1
+    int tile_log2;     // log2 of the tile's pair indices: min(the launch's tile, h0)
+    int blk0, nblk;    // this item's workgroups (st_plan_fold_blocks); a workgroup walks (table, tile) units blk, blk + nblk, ..
+    const E2* in;      // the first round's input: tables of length 2^(h0+1), de-interleaved, at stride in_stride
+    size_t in_stride;
+    E2* out[ST_FOLD_MAX_ROUNDS];   // round h0 - k writes out[k], stride 2^(h0-k)
+};
+// Fills tile_log2 / blk0 / nblk of the items of one launch (at most 64) from each job's table count; returns the grid size.
+int st_plan_fold_blocks(StFoldRun* items, int nitems, const StJob* host_jobs, int tile_log2);
+void st_fold_runs(hipStream_t st, const StJob* jobs, const StFoldRun* items, int nitems, int grid, const E2* chal);
 void st_sums(hipStream_t st, const StJob* jobs, const StItem* items, int nitems, int grid, const E2* chal, E2* partials, E2* res);
 // LDS-resident tail (st_tail): every item runs ALL rounds from its `rd` on in one workgroup; st_tail_h(ntab, nvars) = log2 of the
 // largest half length whose tables fit, i.e. the rounds with half <= 2^st_tail_h belong to the tail; table_bytes = max over the

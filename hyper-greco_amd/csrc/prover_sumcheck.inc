@@ -243,7 +243,49 @@
                 if (!lc.items.empty()) plan.push_back(lc);
             }
         }
-        if (hg_debug("plan"))   // one line per launch, in launch order (read at every call: the tests switch it per case)
+        // The fold-only rounds (mode 1) of one job are consecutive rounds, each reading what the one before it wrote: a run, issued as ONE
+        // item of the fold-run launch (kernels.hpp: StFoldRun) at the position of the plan's LAST mode-1 entry - every run's input was
+        // written by a launch planned ahead of its first fold-only round. A run longer than a tile holds is cut: piece c of every run
+        // shares launch c. HG_FOLD_ROUNDS=1: one launch per round, where it stands (st_step, mode 1). HG_FOLD_TILE_LOG2=<1..9>: a
+        // smaller tile, so that small shapes reach the cut and the many-tiles paths. Both are read at every flush.
+        int fold_at = -1, fold_tile = dev::ST_FOLD_TILE_LOG2, fold_rounds = 0, fold_max_run = 0;
+        struct FoldLaunch { size_t off; int cnt, grid; double bytes, model, design; };
+        std::vector<FoldLaunch> fold_launches;
+        std::vector<dev::StFoldRun> fold_items;
+        if (!hg_env_on("HG_FOLD_ROUNDS")) {
+            if (const char* e = getenv("HG_FOLD_TILE_LOG2")) { const int v = atoi(e); if (v >= 1 && v <= dev::ST_FOLD_TILE_MAX_LOG2) fold_tile = v; }
+            std::vector<std::vector<dev::StItem>> runs(nj);
+            for (size_t li = 0; li < plan.size(); li++)
+                if (plan[li].mode == 1) { fold_at = (int)li; for (const dev::StItem& it : plan[li].items) runs[it.job].push_back(it); }
+            std::vector<std::vector<dev::StFoldRun>> pieces;   // [c]: piece c of every run that has one
+            for (int q = 0; q < nj; q++) {
+                const std::vector<dev::StItem>& run = runs[q];
+                for (size_t k = 1; k < run.size(); k++)
+                    if (run[k].h_log2 != run[k - 1].h_log2 - 1 || run[k].in != (const void*)run[k - 1].out || run[k].in_stride != (size_t)1 << run[k - 1].h_log2)
+                        throw Error("fold-only rounds of a job that do not follow each other");
+                fold_rounds += (int)run.size();
+                fold_max_run = std::max(fold_max_run, (int)run.size());
+                size_t c = 0;
+                for (size_t pos = 0; pos < run.size(); c++) {
+                    dev::StFoldRun F;
+                    memset(&F, 0, sizeof(F));
+                    F.job = q; F.h0 = run[pos].h_log2; F.in = (const E2*)run[pos].in; F.in_stride = run[pos].in_stride;
+                    F.nrounds = (int)std::min<size_t>((size_t)std::min(fold_tile, F.h0) + 1, run.size() - pos);
+                    for (int k = 0; k < F.nrounds; k++) F.out[k] = run[pos + k].out;
+                    if (pieces.size() <= c) pieces.emplace_back();
+                    pieces[c].push_back(F);
+                    pos += (size_t)F.nrounds;
+                }
+            }
+            for (const auto& pc : pieces)
+                for (size_t o = 0; o < pc.size(); o += MAX_BATCH) {
+                    FoldLaunch FL{fold_items.size(), (int)std::min<size_t>(MAX_BATCH, pc.size() - o), 0, 0, 0, 0};
+                    fold_items.insert(fold_items.end(), pc.begin() + o, pc.begin() + o + FL.cnt);
+                    FL.grid = dev::st_plan_fold_blocks(fold_items.data() + FL.off, FL.cnt, st_jobs.data(), fold_tile);
+                    fold_launches.push_back(FL);
+                }
+        }
+        if (hg_debug("plan"))   // one line per plan entry, in launch order (read at every call: the tests switch it per case); a mode=1 line is a round of the fold-run launch, which is issued where the last of them stands
             for (const Launch& L : plan) {
                 if (L.after_seq) { fprintf(stderr, "[hg plan] stride kind=%d after_seq=1\n", L.kind); continue; }
                 int lo = INT_MAX, hi = INT_MIN;
@@ -309,9 +351,33 @@
             if (rd == 0) b += st_level_design[q];
             return b;
         };
+        dev::StFoldRun* d_fold = nullptr;
+        if (!fold_items.empty()) {
+            d_fold = ctx->alloc_n<dev::StFoldRun>(fold_items.size());
+            upload(d_fold, fold_items.data(), fold_items.size() * sizeof(dev::StFoldRun), "upload fold runs");
+            for (FoldLaunch& FL : fold_launches)   // credited round by round as the per-round launches are; by design: the first level read once, every level written once
+                for (int q = 0; q < FL.cnt; q++) {
+                    const dev::StFoldRun& F = fold_items[FL.off + q];
+                    const dev::StJob& J = st_jobs[F.job];
+                    FL.design += (double)J.ntab * 2.0 * (double)((size_t)1 << F.h0) * 16.0;
+                    for (int k = 0; k < F.nrounds; k++) {
+                        FL.bytes += round_bytes(F.job, J.nvars - 1 - F.h0 + k, false); FL.model += round_bytes(F.job, J.nvars - 1 - F.h0 + k, true);
+                        FL.design += (double)J.ntab * (double)((size_t)1 << (F.h0 - k)) * 16.0;
+                    }
+                }
+        }
         for (size_t li = 0; li < plan.size(); li++) {
             const Launch& L = plan[li];
             if (L.kind == dev::SC_GRANDPROD && st_before_gp) { stamp("collation done"); st_before_gp(); st_before_gp = nullptr; stamp("grand products may start"); }
+            if (L.mode == 1 && fold_at >= 0) {   // a fold-only round of the runs: all of them go where the last one stands
+                if ((int)li == fold_at)
+                    for (const FoldLaunch& FL : fold_launches) {
+                        ctx->prof_begin(cls_gp_ext, FL.bytes, FL.model, FL.design);
+                        dev::st_fold_runs(st, d_jobs, d_fold + FL.off, FL.cnt, FL.grid, ctx->d_chal);
+                        ctx->prof_end();
+                    }
+                continue;
+            }
             if (L.after_seq) {
                 for (auto& f : st_after_seq) f();
                 st_after_seq.clear();
@@ -405,6 +471,8 @@
         }
         if (hg_debug("endgame") && (n_tail_ff || n_tail_whole || n_sum_pairs || n_sum_singles))   // what the end of the grand products ran as
             fprintf(stderr, "[hg endgame] stride tail_fold_first=%d tail_whole=%d sums_pairs=%d sums_singles=%d\n", n_tail_ff, n_tail_whole, n_sum_pairs, n_sum_singles);
+        if (hg_debug("folds") && !fold_launches.empty())   // the fold-only rounds as they were issued: `rounds` = the items of the plan's mode=1 lines
+            fprintf(stderr, "[hg folds] stride launches=%zu items=%zu rounds=%d max_run=%d tile_log2=%d\n", fold_launches.size(), fold_items.size(), fold_rounds, fold_max_run, fold_tile);
         if (st_before_gp) { st_before_gp(); st_before_gp = nullptr; }
         if (st_before_gp2) { st_before_gp2(); st_before_gp2 = nullptr; }
         st_jobs.clear();
