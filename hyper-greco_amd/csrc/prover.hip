@@ -262,6 +262,72 @@ struct SlotPlan {
     const E2* job_slotw = nullptr; const u64* job_emit = nullptr;   // layers below the top one: StJob::slotw / emit_mask (the top layer's are in its GpHashSrc)
 };
 struct MirrorSpec { E2 k1, k2; int credit_ntab; };  // StJob::mk1 / mk2; the table count the launch is credited with (the unmirrored batch)
+// What a stride-layout sum-check may set beside its tables (Prover::sc_stride).
+struct StrideArgs {
+    bool enqueue = true;                        // false: another rank runs this job, transcript bookkeeping only
+    bool p0_only = false;
+    int seq = 0;                                // > 0: the first round is launched alone, in ascending seq (StQueued::seq)
+    u64* next_level = nullptr;                  // ... and writes this product-tree level
+    const dev::GpHashSrc* hash_src = nullptr;   // the first round recomputes its input rows (k_gp_first_hash)
+    const MirrorSpec* mirror = nullptr;
+    int model_ntab = 0;                         // table count of the reference's batch, 0: ntab
+    const SlotPlan* slots = nullptr;
+    // traffic of the passes the job's first round absorbs (hash build, tree level): algorithmic bytes, what only the reference's
+    // model counts of them (E reads); and by design (hg_kernel_stat::hbm_bytes): the tree level written (rows actually written x
+    // their length), the integer tables a hash-source job reads INSTEAD of its input rows (-1: it reads its rows)
+    double fused_bytes = 0, fused_model_extra = 0, level_design = 0, hash_reads = -1;
+};
+// One queued stride-layout job (Prover::st_queue). Grand-product jobs whose FIRST round also produces a product-tree level (or reads
+// recomputed hashes) must run one after the other, deepest layer first: a job with seq = s > 0 gets its own first-round launch, in
+// ascending s, before the shared first-round launch of everything else.
+struct StQueued {
+    dev::StJob J;
+    int seq;
+    SlotPlan slot;
+    int credit_ntab;   // table count of the reference's batch (traffic model of SURVEY.md 8(d)); = ntab without a shortcut
+    double fused_bytes, fused_model_extra, level_design, hash_reads;   // StrideArgs; fused_bytes with the tree level a first round writes
+};
+// The switches of a stride plan (Prover::stride_opts fills them, Prover::plan_stride reads them).
+struct StrideOpts {
+    bool may_split;           // small grand-product rounds run as folds and sums; HG_NO_SPLIT=1, one stream, a sharded prove: whole rounds
+    bool sums_single;         // HG_SUMS_SINGLE=1: the split rounds' sums one item per round, in fold order, through st_step
+    bool fold_per_round;      // HG_FOLD_ROUNDS=1: one launch per fold-only round, where it stands (st_step, mode 1)
+    int fold_tile_log2;       // HG_FOLD_TILE_LOG2=<1..9>: a smaller tile, so that small shapes reach the cut and the many-tiles paths
+    bool tail_whole_rounds;   // HG_TAIL_WHOLE_ROUNDS=1: the grand-product tail round by round
+};
+// One kernel launch or callback of a stride flush, with everything its issue needs.
+struct StLaunch {
+    enum Tag { SeqFirst,   // a sequenced first round alone: the hash first round (`hash`) or a base first round that writes a tree level
+               AfterSeq,   // the st_after_seq callbacks (the remaining tree levels), then st_before_gp2
+               First,      // every other first round on base-field rows
+               Step, Step2,   // one round / a fused pair of rounds of every job that has one; Step with mode = 1: the round's folds only
+               FoldRuns,   // runs of fold-only rounds, one item per run (kernels.hpp: StFoldRun)
+               Sums,       // the split rounds' sums, on the sums stream
+               Regroup,    // the per-memory tables of the next Tail's slot-form jobs, gathered in one launch
+               Tail } tag; // every job's remaining rounds, one workgroup per job
+    int kind;
+    size_t off; int cnt, grid;       // items [off, off + cnt) of StridePlan::items (FoldRuns: ::fold_runs, Regroup: ::regroups), cut at the launch's batch size; its workgroups
+    int cls; double bytes, model, design;   // profile class; algorithmic bytes, those of the reference's batch, bytes moved by design
+    bool side;                       // on the sums stream with its partials (otherwise: the stream the flush enqueues to)
+    bool base, hash, slot;           // first rounds: base-field rows; SeqFirst: the hash round; a base round on slot rows
+    int mode;                        // st_step's mode (Sums: 2 = one item per round through st_step, 0 = st_sums items)
+    bool first, last;                // Sums: the first / last sums launch of the flush (the event operations around them)
+    size_t table_bytes; bool fold_first;   // Tail (st_tail)
+    size_t rg_max;                   // Regroup: entries of its longest job
+};
+struct StLine { int kind, base, nrounds, mode, tail, hash, after_seq; size_t items; int lo, hi; };   // one `[hg plan] stride` line
+struct StridePlan {
+    std::vector<dev::StJob> jobs;             // the queued descriptors, contiguous as they are uploaded
+    std::vector<StLaunch> launches;           // exactly what is issued, in issue order
+    std::vector<dev::StItem> items;           // the launches' items - and, as the record of a FoldRuns launch, the rounds it stands for, where they stood
+    std::vector<dev::StFoldRun> fold_runs;
+    std::vector<dev::SlotRegroupJob> regroups;
+    // HG_DEBUG=plan: one line per planned ROUND group, in plan order - a mode=1 line is a round of the fold-run launches (issued where
+    // the last of them stands), the mode=2 line counts the rounds whose sums the Sums launches hold
+    std::vector<StLine> lines;
+    int n_tail_ff = 0, n_tail_whole = 0, n_sum_pairs = 0, n_sum_singles = 0;          // HG_DEBUG=endgame: what the end of the grand products runs as
+    int fold_launches = 0, fold_rounds = 0, fold_max_run = 0, fold_tile_log2 = 0;     // HG_DEBUG=folds
+};
 
 struct Prover {
     hg_ctx* ctx;

@@ -159,14 +159,16 @@
             });
             size_t evals = slot(2 * (size_t)nb);
             ScHandle sc;
-            const size_t jobs_before = st_jobs.size();
-            const int seq = n >= nv - emit ? nv - n : 0;                    // first round launched alone, deepest layer first
-            u64* nxt = seq ? lev_w[k + 1] : nullptr;                          // ... and writes tree level k + 1
+            const size_t jobs_before = st_queue.size();
+            StrideArgs sa;   // what every form of the layer's sum-check sets; the forms below add their own
+            sa.seq = n >= nv - emit ? nv - n : 0;                           // first round launched alone, deepest layer first
+            sa.next_level = sa.seq ? lev_w[k + 1] : nullptr;                  // ... and writes tree level k + 1
             const dev::GpHashSrc* hs = (hash_src && k == 0) ? hash_src : nullptr;
-            if (hs) { pending_fused_bytes = hash_fused_bytes; pending_fused_model_extra = hash_model_extra; pending_hash_reads = hash_design_reads; }
-            if (nxt) {   // rows of level k + 1 this first round writes: the next layer's slot rows in slot form, one per row held otherwise
+            sa.hash_src = hs;
+            if (hs) { sa.fused_bytes = hash_fused_bytes; sa.fused_model_extra = hash_model_extra; sa.hash_reads = hash_design_reads; }
+            if (sa.next_level) {   // rows of level k + 1 this first round writes: the next layer's slot rows in slot form, one per row held otherwise
                 const bool next_slots = hash_src && !local && k + 1 < (int)gp_slots.layer.size();
-                pending_level_design = (double)(next_slots ? gp_slots.layer[k + 1].V : nl) * (double)(len >> (k + 1)) * 8.0;
+                sa.level_design = (double)(next_slots ? gp_slots.layer[k + 1].V : nl) * (double)(len >> (k + 1)) * 8.0;
             }
             const bool mirrored = hs && mirror_c;
             if (mirrored) {
@@ -207,8 +209,8 @@
                     spl.tail_ntab = 2 * R + 1; spl.d_slot_of = sl.d_slot_of; spl.d_ratio = sl.d_ratio;
                     spl.nrows = R; spl.nslots = sl.V; spl.npairs = sl.ng; spl.max_rd = gp_slots.seg_shift;
                 }
-                sc = sc_stride(dev::SC_GRANDPROD, lev[k], true, h, slotted ? 2 * gp_slots.layer[0].V + 1 : 2 * R + 1, n, pwl, fin, run, p0_only, seq, nxt, hs, &ms, 0,
-                               slotted ? &spl : nullptr);
+                sa.enqueue = run; sa.p0_only = p0_only; sa.mirror = &ms; sa.slots = slotted ? &spl : nullptr;
+                sc = sc_stride(dev::SC_GRANDPROD, lev[k], true, h, slotted ? 2 * gp_slots.layer[0].V + 1 : 2 * R + 1, n, pwl, fin, sa);
                 sc.scaled = true; sc.scale = onek;
                 if (slotted) slot_weights(gp_slots.layer[0], pwl, sc.rs[0]);
                 if (run && !dev_claims)   // (the claim epilogue writes the result slots itself)
@@ -220,15 +222,18 @@
                 // slot form below the top layer: the input rows are this layer's slot rows (written by the layer above), the tail runs
                 // on the 2 nb per-row tables again
                 const SlotLayer& sl = gp_slots.layer[k];
-                if (sl.nrows != nb || !mine(owner[n]) || !seq) throw Error("grand product: slot form on a partial batch");
+                if (sl.nrows != nb || !mine(owner[n]) || !sa.seq) throw Error("grand product: slot form on a partial batch");
                 SlotPlan spl;
                 spl.tail_ntab = 2 * nb; spl.d_slot_of = sl.d_slot_of; spl.d_ratio = sl.d_ratio;
                 spl.nrows = nb; spl.nslots = sl.V; spl.npairs = sl.ng; spl.max_rd = gp_slots.seg_shift;
                 spl.job_slotw = sl.d_slotw; spl.job_emit = sl.d_emit;
-                sc = sc_stride(dev::SC_GRANDPROD, lev[k], true, h, 2 * sl.V, n, pw, d_res() + evals, true, false, seq, nxt, nullptr, nullptr, 2 * nb, &spl);
+                sa.model_ntab = 2 * nb; sa.slots = &spl;
+                sc = sc_stride(dev::SC_GRANDPROD, lev[k], true, h, 2 * sl.V, n, pw, d_res() + evals, sa);
                 slot_weights(sl, pw, sc.rs[0]);
-            } else if (!local) sc = sc_stride(dev::SC_GRANDPROD, lev[k], true, h, 2 * nb, n, pw, d_res() + evals, mine(owner[n]), false, seq, nxt, hs);
-            else {
+            } else if (!local) {
+                sa.enqueue = mine(owner[n]);
+                sc = sc_stride(dev::SC_GRANDPROD, lev[k], true, h, 2 * nb, n, pw, d_res() + evals, sa);
+            } else {
                 // this rank's share of the batch: local pair li is global pair b = local[li], weight gamma^b
                 dev::Powers pwl;
                 memset(&pwl, 0, sizeof(pwl));
@@ -236,15 +241,18 @@
                 E2* fin = nl ? ctx->alloc_n<E2>(2 * (size_t)nl) : nullptr;
                 if (hash_src && k >= 1 && k < (int)gp_slots.layer.size()) {   // slot form below the top layer, on the rows this rank holds
                     const SlotLayer& sl = gp_slots.layer[k];
-                    if (sl.nrows != nl || !mine(owner[n]) || !seq || nl <= (p0_only ? 1 : 0)) throw Error("grand product: the slot plan does not fit the rows held");
+                    if (sl.nrows != nl || !mine(owner[n]) || !sa.seq || nl <= (p0_only ? 1 : 0)) throw Error("grand product: the slot plan does not fit the rows held");
                     SlotPlan spl;
                     spl.tail_ntab = 2 * nl; spl.d_slot_of = sl.d_slot_of; spl.d_ratio = sl.d_ratio;
                     spl.nrows = nl; spl.nslots = sl.V; spl.npairs = sl.ng; spl.max_rd = gp_slots.seg_shift;
                     spl.job_slotw = sl.d_slotw; spl.job_emit = sl.d_emit;
-                    sc = sc_stride(dev::SC_GRANDPROD, lev[k], true, h, 2 * sl.V, n, pwl, fin, true, p0_only, seq, nxt, nullptr, nullptr, 2 * nl, &spl);
+                    sa.p0_only = p0_only; sa.model_ntab = 2 * nl; sa.slots = &spl;
+                    sc = sc_stride(dev::SC_GRANDPROD, lev[k], true, h, 2 * sl.V, n, pwl, fin, sa);
                     slot_weights(sl, pwl, sc.rs[0]);
-                } else
-                sc = sc_stride(dev::SC_GRANDPROD, lev[k], true, h, 2 * nl, n, pwl, fin, mine(owner[n]) && nl > (p0_only ? 1 : 0), p0_only, seq, nxt, hs);
+                } else {
+                    sa.enqueue = mine(owner[n]) && nl > (p0_only ? 1 : 0); sa.p0_only = p0_only;
+                    sc = sc_stride(dev::SC_GRANDPROD, lev[k], true, h, 2 * nl, n, pwl, fin, sa);
+                }
                 if (mine(owner[n]))
                     for (int li = p0_only ? 1 : 0; li < nl; li++) {
                         int b = (*local)[li];
@@ -254,7 +262,7 @@
             }
             mark("grand product layer " + std::to_string(n) + ": sum-check, " + std::to_string(n) + " rounds x 4 coefficients [C1 message format, C2 power order, C3 variable order]");
             defer_sumcheck(sc, 3, claim, nullptr);
-            const bool dev_layer = dev_claims && st_jobs.size() == jobs_before + 1;   // (queued here: it ends in the tail launch of flush_stride)
+            const bool dev_layer = dev_claims && st_queue.size() == jobs_before + 1;   // (queued here: it ends in the tail launch of flush_stride)
             if (!dev_layer) defer_gp_unscale(evals, nb, pw);
             if (mirrored && !dev_layer) {   // the write rows' evaluations: folding is affine with coefficients summing to one, so row + c stays row + c
                 const u64 c = *mirror_c;
@@ -293,7 +301,7 @@
                 gp_eps.push_back(std::move(e));
                 ndev++;
                 if (mirrored) ndev_mirrored++;
-                else if (st_slot.back().tail_ntab) ndev_slot++;
+                else if (st_queue.back().slot.tail_ntab) ndev_slot++;
             } else layer_down(evals, mu);
         }
         // which sum-check layers' claims the device forms: the mirrored top layer, slot-form layers below it, plain ones (a token of
@@ -465,8 +473,9 @@
             if (A > dev::PW_MAX) throw Error("lasso: too many memories");
             pw.v[0] = e2_one(); pw.v[1] = e2_one();
             const bool col_run = do_col && (int)col_mems.size() > (col_p0_only ? 1 : 0);
-            ScHandle sc = sc_stride(dev::SC_COLLATION, ep, true, (size_t)ep_count * N, 2, nu, pw, nullptr, col_run, true, 0, nullptr, nullptr, nullptr,
-                                    (int)col_mems.size());
+            StrideArgs sa;
+            sa.enqueue = col_run; sa.p0_only = true; sa.model_ntab = (int)col_mems.size();
+            ScHandle sc = sc_stride(dev::SC_COLLATION, ep, true, (size_t)ep_count * N, 2, nu, pw, nullptr, sa);
             mark("lasso: collation sum-check, " + std::to_string(nu) + " rounds x 3 coefficients (lasso.rs:271-279) [C1, C3; poly(0) quirk]");
             defer_sumcheck(sc, 2, claimed, nullptr);
         }

@@ -1,4 +1,4 @@
-// Part of struct Prover (prover.hip includes this file inside the class body): the sum-check drivers - stride-layout jobs (collation, grand-product layers) and PRODSUM jobs (Libra / zkCNN node reductions, eq-factored or with tables), their round-synchronised launch plans, descriptor uploads, the transcript side of a sum-check - and the batched bookkeeping kernels (eq tables, DFT rows, Libra gathers).
+// Part of struct Prover (prover.hip includes this file inside the class body): the sum-check drivers - stride-layout jobs (collation, grand-product layers) and PRODSUM jobs (Libra / zkCNN node reductions, eq-factored or with tables), their round-synchronised launch plans (stride jobs: plan_stride() lists every launch with its items, grid, class and credit, flush_stride() uploads and issues that list; PRODSUM jobs: flush_prodsum(), plan then issue in one function), descriptor uploads, the transcript side of a sum-check - and the batched bookkeeping kernels (eq tables, DFT rows, Libra gathers).
 
     // ---- sum-check drivers ---------------------------------------------------------------------
     // A sum-check whose remaining work is this small ((table pairs) x (pairs per table) items) finishes all
@@ -7,23 +7,13 @@
 
     // Stride-layout sum-checks (collation, every grand-product layer) are queued as jobs and executed by
     // flush_stride() in a round-synchronised schedule (launch k = every job's next round(s)): they are independent on the device.
+    // flush_stride() = plan_stride(), which turns the queue into the list of launches and touches no device, stream or profile, then
+    // one loop that issues that list entry by entry.
     bool hash_recomp = false;   // the queued hash-source job recomputes its E values (lasso_node: lean form)
-    std::vector<dev::StJob> st_jobs;
-    // Grand-product jobs whose FIRST round also produces a product-tree level (or reads recomputed hashes) must run one after
-    // the other, deepest layer first: job q with st_seq[q] = s > 0 gets its own first-round launch, in ascending s, before
-    // the shared first-round launch of everything else; `st_after_seq` then builds the remaining (small) tree levels.
-    std::vector<int> st_seq;
-    std::vector<SlotPlan> st_slot;     // per queued job
-    std::vector<int> st_credit_ntab;   // per queued job: table count of the reference's batch (traffic model of SURVEY.md 8(d)); = ntab without a shortcut
-    std::vector<double> st_fused_bytes;  // algorithmic bytes of the passes a job's first round absorbs (hash build, tree level)
-    std::vector<std::function<void()>> st_after_seq;
-    // what a job's first round moves to or from HBM beside its own tables (hg_kernel_stat::hbm_bytes): the tree level it writes
-    // (rows actually written x their length) and, for the hash-source job, the integer tables it reads INSTEAD of its input rows
-    double pending_level_design = 0, pending_hash_reads = -1, hash_design_reads = 0;
-    std::vector<double> st_level_design, st_hash_reads;
-    double pending_fused_bytes = 0;      // set by the caller right before sc_stride (the hash build a hash-source job absorbs)
-    double pending_fused_model_extra = 0, hash_model_extra = 0;   // ... and what only the reference's traffic model counts of it (E reads)
-    std::vector<double> st_fused_model_extra;
+    // (the types of the queue and of the plan - StQueued, StrideOpts, StLaunch, StridePlan - are in prover.hip, beside SlotPlan)
+    std::vector<StQueued> st_queue;
+    std::vector<std::function<void()>> st_after_seq;   // the remaining (small) tree levels, behind the sequenced first rounds (StQueued::seq)
+    double hash_design_reads = 0, hash_model_extra = 0;   // lasso_node -> grand_product: StrideArgs::hash_reads / fused_model_extra of the hash-source job
     std::vector<dev::ScatterEnt> scatter;  // locally produced scalars -> global result slots (batch-subset grand products)
     // claim epilogues of the queued grand-product jobs (grand_product, prover_lasso.inc): challenge-only constants, filled during the
     // walk and uploaded with the job descriptors, which a cached launch graph does not repeat
@@ -31,16 +21,14 @@
     std::vector<GpEpReq> gp_eps;
 
     ScHandle sc_stride(int kind, const void* in, bool base, size_t in_stride, int ntab, int nvars, const dev::Powers& pw, E2* final_out,
-                       bool enqueue = true, bool p0_only = false, int seq = 0, u64* next_level = nullptr, const dev::GpHashSrc* hash_src = nullptr,
-                       const MirrorSpec* mirror = nullptr, int model_ntab = 0, const SlotPlan* slots = nullptr) {
+                       const StrideArgs& a = StrideArgs()) {
         ScHandle h;
         h.nv = kind == dev::SC_GRANDPROD ? 3 : 2;
         h.nvars = nvars;
         h.point_off = epos();
         h.sums_slot = slot((size_t)nvars * h.nv);
         const size_t N = (size_t)1 << nvars;
-        if (!enqueue) {  // another rank runs this job: transcript bookkeeping only
-            pending_fused_bytes = 0; pending_fused_model_extra = 0; pending_level_design = 0; pending_hash_reads = -1;
+        if (!a.enqueue) {  // another rank runs this job: transcript bookkeeping only
             for (int i = 0; i < nvars; i++) h.rs.push_back(squeeze());
             return h;
         }
@@ -50,254 +38,342 @@
         J.buf[0] = ctx->alloc_n<E2>((size_t)ntab * std::max<size_t>(N / 2, 1));
         J.buf[1] = ctx->alloc_n<E2>((size_t)ntab * std::max<size_t>(N / 4, 1));
         J.final_out = final_out ? final_out : ctx->alloc_n<E2>(ntab);
-        J.kind = kind; J.ntab = ntab; J.nvars = nvars; J.base = base ? 1 : 0; J.p0_only = p0_only ? 1 : 0;
+        J.kind = kind; J.ntab = ntab; J.nvars = nvars; J.base = base ? 1 : 0; J.p0_only = a.p0_only ? 1 : 0;
         J.r_off = h.point_off; J.sums_slot = h.sums_slot;
-        J.next_level = next_level; J.hash_src = hash_src;
-        if (mirror) { J.mirror = 1; J.mk1 = mirror->k1; J.mk2 = mirror->k2; }
-        if (slots && slots->job_slotw) { J.slotw = slots->job_slotw; J.emit_mask = slots->job_emit; J.slot_ng = slots->npairs; J.slot_shift = slots->max_rd; }
+        J.next_level = a.next_level; J.hash_src = a.hash_src;
+        if (a.mirror) { J.mirror = 1; J.mk1 = a.mirror->k1; J.mk2 = a.mirror->k2; }
+        if (a.slots && a.slots->job_slotw) { J.slotw = a.slots->job_slotw; J.emit_mask = a.slots->job_emit; J.slot_ng = a.slots->npairs; J.slot_shift = a.slots->max_rd; }
         memcpy(J.pw, pw.v, sizeof(J.pw));
         for (int i = 0; i < nvars; i++) h.rs.push_back(squeeze());
         if (nvars > 0)  // weight * r_0: the first round stores the weighted fold (kernels.hip)
             for (int i = 0; i < dev::PW_MAX; i++) J.pwr[i] = e2_mul(pw.v[i], h.rs[0]);
         if (nvars > 0) {
-            st_slot.push_back(slots ? *slots : SlotPlan());
-            st_jobs.push_back(J); st_seq.push_back(seq); st_credit_ntab.push_back(mirror ? mirror->credit_ntab : (model_ntab ? model_ntab : ntab));
+            const int credit_ntab = a.mirror ? a.mirror->credit_ntab : (a.model_ntab ? a.model_ntab : ntab);
             // a level-writing first round replaces prod_level on its input level: (nb rows of 2N entries) x 8 B x 1.5 (read +
             // write), as prod_level is credited; the hash-source job's level 1 is credited with its write only, as the hash kernel
             // it replaces was (round-1 accounting: the totals stay comparable)
-            double fused = next_level ? (double)(st_credit_ntab.back() / 2) * (double)(2 * N) * 8.0 * (hash_src ? 0.5 : 1.5) : 0.0;
-            st_fused_bytes.push_back(fused + pending_fused_bytes);
-            st_fused_model_extra.push_back(pending_fused_model_extra);
-            st_level_design.push_back(next_level ? pending_level_design : 0.0);
-            st_hash_reads.push_back(hash_src ? pending_hash_reads : -1.0);
-            pending_fused_bytes = 0; pending_fused_model_extra = 0; pending_level_design = 0; pending_hash_reads = -1;
+            const double fused = a.next_level ? (double)(credit_ntab / 2) * (double)(2 * N) * 8.0 * (a.hash_src ? 0.5 : 1.5) : 0.0;
+            st_queue.push_back(StQueued{J, a.seq, a.slots ? *a.slots : SlotPlan(), credit_ntab, fused + a.fused_bytes, a.fused_model_extra,
+                                        a.next_level ? a.level_design : 0.0, a.hash_src ? a.hash_reads : -1.0});
         }
         return h;
     }
 
     // half-length (log2) at which a slot-form job's tail starts: what its PER-MEMORY tables allow (HG_TAIL_H does not apply)
     static int slot_tail_h(int tail_ntab, int nvars) { return std::min(dev::st_tail_h(tail_ntab, nvars), nvars - 2); }
-    void flush_stride() {
-        if (st_jobs.empty()) return;
-        const int nj = (int)st_jobs.size();
-        if (hoist_consts)   // (as in flush_prodsum: the rounds stay recorded)
-            for (auto& J : st_jobs) {
-                const size_t N = (size_t)1 << J.nvars;
-                kept_writes(crange(J.buf[0], (size_t)J.ntab * std::max<size_t>(N / 2, 1)));
-                kept_writes(crange(J.buf[1], (size_t)J.ntab * std::max<size_t>(N / 4, 1)));
-                kept_writes(crange(J.final_out, (size_t)J.ntab));
-            }
-        // launch plan: (kind, base? | fused pair?, h_log2 | tail) -> items (job, where the round reads and writes).
-        // Folded tables ping-pong between the job's two buffers; the host tracks where each job's live tables are.
+    // ---- the plan of a flush: what is launched, in issue order ---------------------------------------------------------------------
+    // The switches of a plan are read here and nowhere else: HG_NO_SPLIT once per process, the others at every flush (the tests
+    // switch them per case).
+    StrideOpts stride_opts() const {
+        static const bool no_split = hg_env_on("HG_NO_SPLIT");
+        StrideOpts o;
+        o.may_split = !no_split && st == ctx->stream && fork_recorded && world == 1;
+        o.sums_single = hg_env_on("HG_SUMS_SINGLE");
+        o.fold_per_round = hg_env_on("HG_FOLD_ROUNDS");
+        o.fold_tile_log2 = dev::ST_FOLD_TILE_LOG2;
+        if (const char* e = getenv("HG_FOLD_TILE_LOG2")) { const int v = atoi(e); if (v >= 1 && v <= dev::ST_FOLD_TILE_MAX_LOG2) o.fold_tile_log2 = v; }
+        o.tail_whole_rounds = hg_env_on("HG_TAIL_WHOLE_ROUNDS");
+        return o;
+    }
+    // Plans a flush: (kind, base? | fused pair?, h_log2 | tail) -> items (job, where the round reads and writes). Folded tables
+    // ping-pong between the job's two buffers; the plan tracks where each job's live tables are. No device, stream or profile call:
+    // `alloc_e2` hands out the arena buffers of split rounds' folds and slot-form tails.
+    StridePlan plan_stride(const std::vector<StQueued>& Q, const StrideOpts& o, const std::function<E2*(size_t)>& alloc_e2) const {
         constexpr int fuse_min_h = 15;   // fused pairs of rounds from half = 2^15 up (13 until the slot form: 1.96-1.99 against 1.99-2.01 ms; round 5: 13 / 11 / 9 = 1.864 / 1.905 / 1.980 against 1.831)
-        struct Launch { int kind; bool base; int h_log2; bool tail; int nrounds; std::vector<dev::StItem> items; bool hash = false; bool after_seq = false;
-                        int mode = 0;   // 1: a split round's folds (main stream), 2: the split rounds' sums (side stream) - kernels.hip: sc_round_body
-                        std::vector<dev::StItem> run;   // mode 2: what is launched for `items` - job-major, consecutive rounds of a job as one item (st_sums); empty: `items`
-        };
-        int n_tail_ff = 0, n_tail_whole = 0, n_sum_pairs = 0, n_sum_singles = 0;   // (HG_DEBUG=endgame)
-        std::vector<Launch> plan;
-        struct Regroup { int job; const E2* in; E2* out; int len_log2; };
-        std::vector<Regroup> regroups;
+        constexpr int split_h = 14;      // split rounds from half = 2^14 down (every single-round launch of Ext2 tables: pairs of rounds are fused from 2^15 up; 12 / 10 measured the same)
+        StridePlan P;
+        const int nj = (int)Q.size();
+        for (const StQueued& q : Q) P.jobs.push_back(q.J);
+        const std::vector<dev::StJob>& jobs = P.jobs;
         std::vector<const void*> cur_in(nj);
         std::vector<size_t> cur_stride(nj);
         std::vector<int> next_h(nj);  // half-length (log2) of the job's next unscheduled round
-        for (int q = 0; q < nj; q++) { cur_in[q] = st_jobs[q].in; cur_stride[q] = st_jobs[q].in_stride; next_h[q] = st_jobs[q].nvars - 1; }
-        auto next_out = [&](int q) { return cur_in[q] == (const void*)st_jobs[q].buf[0] ? st_jobs[q].buf[1] : st_jobs[q].buf[0]; };
+        for (int q = 0; q < nj; q++) { cur_in[q] = jobs[q].in; cur_stride[q] = jobs[q].in_stride; next_h[q] = jobs[q].nvars - 1; }
+        auto next_out = [&](int q) { return cur_in[q] == (const void*)jobs[q].buf[0] ? jobs[q].buf[1] : jobs[q].buf[0]; };
+        // the item of job q's next round (or fused pair of rounds), written to `out`; the job moves on
+        auto take = [&](int q, E2* out, int nrounds) {
+            dev::StItem it;
+            memset(&it, 0, sizeof(it));
+            it.job = q; it.h_log2 = next_h[q]; it.in = cur_in[q]; it.in_stride = cur_stride[q]; it.out = out;
+            cur_in[q] = out; cur_stride[q] = (size_t)1 << (it.h_log2 - (nrounds - 1)); next_h[q] -= nrounds;
+            return it;
+        };
         // The rounds with half <= 2^h_small[q] of job q run in ONE single-workgroup launch with the folded tables in LDS (st_tail);
         // how many fit depends on the job's table count (12 rounds for the two collation tables, 6 for a full grand-product layer).
         std::vector<int> h_small(nj);
         for (int q = 0; q < nj; q++) {
-            const SlotPlan& sp = st_slot[q];
-            h_small[q] = sp.tail_ntab ? slot_tail_h(sp.tail_ntab, st_jobs[q].nvars) : dev::st_tail_h(st_jobs[q].ntab, st_jobs[q].nvars);
-            if (st_seq[q] > 0) h_small[q] = std::min(h_small[q], st_jobs[q].nvars - 2);   // a sequenced first round has its own kernel
-            if (sp.tail_ntab && st_jobs[q].nvars - 1 - h_small[q] > sp.max_rd) throw Error("slot-form job: the tail starts below the segment pairs");
+            const SlotPlan& sp = Q[q].slot;
+            h_small[q] = sp.tail_ntab ? slot_tail_h(sp.tail_ntab, jobs[q].nvars) : dev::st_tail_h(jobs[q].ntab, jobs[q].nvars);
+            if (Q[q].seq > 0) h_small[q] = std::min(h_small[q], jobs[q].nvars - 2);   // a sequenced first round has its own kernel
+            if (sp.tail_ntab && jobs[q].nvars - 1 - h_small[q] > sp.max_rd) throw Error("slot-form job: the tail starts below the segment pairs");
         }
+        // algorithmic bytes of one round of job q (SURVEY.md 8(d)): every live table read once, every folded table written once.
+        // model = true: the tables of the reference's batch (a mirrored grand product is modelled with its read AND write tables, the
+        // collation sum-check with its alpha tables), false: the tables this implementation streams
+        auto round_bytes = [&](int q, int rd, bool model) {
+            const dev::StJob& J = jobs[q];
+            size_t half = (size_t)1 << (J.nvars - 1 - rd);
+            return (double)(model ? Q[q].credit_ntab : J.ntab) * (2.0 * half * ((J.base && rd == 0) ? 8 : 16) + half * 16.0);
+        };
+        // bytes moved to or from HBM by design (hg_kernel_stat::hbm_bytes): `ntab` tables of round rd read once; the folds of half 2^h written once
+        auto reads = [&](int q, int rd, int ntab) { return (double)ntab * 2.0 * (double)((size_t)1 << (jobs[q].nvars - 1 - rd)) * ((jobs[q].base && rd == 0) ? 8 : 16); };
+        auto writes = [&](int q, int h) { return (double)jobs[q].ntab * (double)((size_t)1 << h) * 16.0; };
+        // a launch of rounds rd .. rd + nrounds - 1: the tables of round rd read (the hash-source job's first round: its integer tables
+        // instead), the folds of the last round written, plus the tree level a first round emits
+        auto design_bytes = [&](int q, int rd, int nrounds) {
+            double b = reads(q, rd, jobs[q].ntab);
+            if (rd == 0 && Q[q].hash_reads >= 0) b = Q[q].hash_reads;
+            b += writes(q, jobs[q].nvars - 1 - rd - (nrounds - 1));
+            if (rd == 0) b += Q[q].level_design;
+            return b;
+        };
+        auto line = [&](int kind, bool base, int nrounds, int mode, bool tail, bool hash, const std::vector<dev::StItem>& its) {
+            StLine l{kind, base, nrounds, mode, tail, hash, 0, its.size(), INT_MAX, INT_MIN};
+            for (const dev::StItem& it : its) { const int v = tail ? it.nrounds : it.h_log2; l.lo = std::min(l.lo, v); l.hi = std::max(l.hi, v); }
+            P.lines.push_back(l);
+        };
+        auto launch = [](StLaunch::Tag tag, int kind) { StLaunch L; memset(&L, 0, sizeof(L)); L.tag = tag; L.kind = kind; return L; };
+        // The launches of one round group: `its` cut at the batch size, each piece with its grid, class and credit - per round, as
+        // SURVEY.md 8(d) accounts: a fused launch is credited with both of its rounds although the intermediate folded tables never
+        // reach HBM (DESIGN.md 6), a base first round also with the passes it absorbs (the tree level it writes, the hash build).
+        // The sums are credited with nothing: their rounds' bytes are the folds'. launched = false: the items only, as a record.
+        auto emit = [&](StLaunch::Tag tag, int kind, bool base, int nrounds, int mode, std::vector<dev::StItem>& its, bool launched = true) {
+            const size_t batch = tag == StLaunch::Sums && mode == 0 ? (size_t)dev::ST_SUMS_MAX_ITEMS : MAX_BATCH;
+            for (size_t at = 0; at < its.size(); at += batch) {
+                StLaunch L = launch(tag, kind);
+                L.off = P.items.size() + at; L.cnt = (int)std::min<size_t>(batch, its.size() - at);
+                L.grid = dev::st_plan_blocks(its.data() + at, L.cnt, nrounds == 2);
+                L.base = base; L.mode = mode; L.slot = base && jobs[its[at].job].slotw != nullptr;
+                L.cls = tag == StLaunch::Sums ? cls_gp_sums : kind == dev::SC_GRANDPROD ? (base ? cls_gp_base : (nrounds == 2 ? cls_gp_ext2 : cls_gp_ext)) : (base ? cls_col_base : (nrounds == 2 ? cls_col_ext2 : cls_col_ext));
+                L.side = tag == StLaunch::Sums; L.first = at == 0; L.last = at + batch >= its.size();
+                for (int k = 0; k < L.cnt; k++) {
+                    const dev::StItem& it = its[at + k];
+                    const int q = it.job, rd = jobs[q].nvars - 1 - it.h_log2;
+                    L.design += design_bytes(q, rd, nrounds);
+                    if (tag == StLaunch::Sums) continue;
+                    for (int r = 0; r < nrounds; r++) { L.bytes += round_bytes(q, rd + r, false); L.model += round_bytes(q, rd + r, true); }
+                    if (base && rd == 0) { L.bytes += Q[q].fused_bytes; L.model += Q[q].fused_bytes; }
+                }
+                if (launched) P.launches.push_back(L);
+            }
+            P.items.insert(P.items.end(), its.begin(), its.end());
+        };
         for (int kind : {dev::SC_COLLATION, dev::SC_GRANDPROD}) {
             int max_h = -1;
-            for (auto& J : st_jobs) if (J.kind == kind) max_h = std::max(max_h, J.nvars - 1);
+            for (auto& J : jobs) if (J.kind == kind) max_h = std::max(max_h, J.nvars - 1);
             if (max_h < 0) continue;
             // sequenced first rounds (each produces the tree level the next one reads), then the remaining tree levels
             if (kind == dev::SC_GRANDPROD) {
                 int max_seq = 0;
-                for (int q = 0; q < nj; q++) max_seq = std::max(max_seq, st_seq[q]);
+                for (int q = 0; q < nj; q++) max_seq = std::max(max_seq, Q[q].seq);
                 for (int sq = 1; sq <= max_seq; sq++)
                     for (int q = 0; q < nj; q++) {
-                        const dev::StJob& J = st_jobs[q];
-                        if (st_seq[q] != sq || J.kind != kind) continue;
+                        const dev::StJob& J = jobs[q];
+                        if (Q[q].seq != sq || J.kind != kind) continue;
                         if (!J.base || next_h[q] <= h_small[q]) throw Error("sequenced first round on a job that has none");
-                        Launch ls{kind, true, -1, false, 1, {}};
-                        ls.hash = J.hash_src != nullptr;
-                        dev::StItem it;
-                        memset(&it, 0, sizeof(it));
-                        it.job = q; it.h_log2 = next_h[q]; it.in = cur_in[q]; it.in_stride = cur_stride[q]; it.out = J.buf[0];
-                        ls.items.push_back(it);
-                        cur_in[q] = it.out; cur_stride[q] = (size_t)1 << next_h[q];
-                        next_h[q]--;
-                        plan.push_back(ls);
+                        std::vector<dev::StItem> one{take(q, J.buf[0], 1)};
+                        line(kind, true, 1, 0, false, J.hash_src != nullptr, one);
+                        emit(StLaunch::SeqFirst, kind, true, 1, 0, one);
+                        if (J.hash_src) {   // ... and what only the reference's traffic model counts of the hash build (E reads)
+                            StLaunch& L = P.launches.back();
+                            L.hash = true; L.cls = cls_gp_hash; L.model += Q[q].fused_model_extra;
+                        }
                     }
-                if (max_seq > 0 || !st_after_seq.empty()) { Launch la{kind, true, -1, false, 0, {}}; la.after_seq = true; plan.push_back(la); }
+                if (max_seq > 0 || !st_after_seq.empty()) {
+                    P.lines.push_back(StLine{kind, 0, 0, 0, 0, 0, 1, 0, 0, 0});
+                    P.launches.push_back(launch(StLaunch::AfterSeq, kind));
+                }
             }
             // the first rounds on base-field rows only read finished tree levels / node tables: one launch for all of them
             {
-                Launch lall{kind, true, -1, false, 1, {}};
+                std::vector<dev::StItem> all;
                 for (int q = 0; q < nj; q++) {
-                    const dev::StJob& J = st_jobs[q];
+                    const dev::StJob& J = jobs[q];
                     if (J.kind != kind || !J.base || next_h[q] <= h_small[q] || next_h[q] != J.nvars - 1) continue;  // (sequenced jobs are past their first round)
-                    dev::StItem it;
-                    memset(&it, 0, sizeof(it));
-                    it.job = q; it.h_log2 = next_h[q]; it.in = cur_in[q]; it.in_stride = cur_stride[q]; it.out = J.buf[0];
-                    lall.items.push_back(it);
-                    cur_in[q] = it.out; cur_stride[q] = (size_t)1 << next_h[q];
-                    next_h[q]--;
+                    all.push_back(take(q, J.buf[0], 1));
                 }
-                if (!lall.items.empty()) plan.push_back(lall);
+                if (!all.empty()) { line(kind, true, 1, 0, false, false, all); emit(StLaunch::First, kind, true, 1, 0, all); }
             }
             // then round-synchronised: launch k runs every job's next round (or, grand product with a long enough table,
             // its next TWO rounds) whatever the sizes; the jobs only depend on their own previous launch
             // Small grand-product rounds are split (round 6): a launch whose items all have half <= 2^split_h runs the FOLDS only, into
             // buffers of the round's own (so that its input outlives the rounds after it); the sums of all such rounds follow in
             // launches of their own on a side stream, beside the remaining fold-only rounds' successor - the tail. HG_NO_SPLIT=1: whole rounds.
-            static const bool no_split = hg_env_on("HG_NO_SPLIT");
-            constexpr int split_h = 14;   // (every single-round launch of Ext2 tables: pairs of rounds are fused from 2^15 up; 12 / 10 measured the same)
-            const bool may_split = kind == dev::SC_GRANDPROD && !no_split && st == ctx->stream && fork_recorded && world == 1;
-            Launch lsum{kind, false, -1, false, 1, {}};
-            lsum.mode = 2;
+            const bool may_split = kind == dev::SC_GRANDPROD && o.may_split;
+            std::vector<dev::StItem> split;              // the fold-only rounds' items, in fold order
+            std::vector<std::vector<dev::StItem>> runs(nj);   // ... by job
+            size_t fold_at = 0;                          // launches ahead of the fold-run launches: all that were planned ahead of the LAST fold-only round
             for (;;) {
-                Launch le{kind, false, -1, false, 1, {}}, l2{kind, false, -1, false, 2, {}};
+                std::vector<dev::StItem> le, l2;
                 bool le_small = may_split;
                 for (int q = 0; q < nj; q++) {
-                    const dev::StJob& J = st_jobs[q];
+                    const dev::StJob& J = jobs[q];
                     const int h = next_h[q];
                     if (J.kind != kind || h <= h_small[q]) continue;
                     const bool first = J.nvars - 1 == h;
                     if (first && J.hash_src) throw Error("hash-source job without a sequenced first round");
-                    dev::StItem it;
-                    memset(&it, 0, sizeof(it));
-                    it.job = q; it.h_log2 = h; it.in = cur_in[q]; it.in_stride = cur_stride[q];
-                    it.out = first ? J.buf[0] : next_out(q);
                     // (fusing the SMALL rounds as well - pairs from 2^12 / 2^11 / 2^10 down - to save launches: 2.10 / 2.19 / 2.22 against 1.79 ms:
                     // the fused kernel walks a job's tables serially per thread and has too few workgroups there; with the table pairs split
                     // over thread groups as the single rounds are, pairs from 2^13 / 2^11 / 2^9: 1.663 / 1.694 / 1.759 against 1.670 - those
                     // rounds are bound by the dependent chain inside a pass, not by the launches)
                     const bool pair = !first && h - 1 > h_small[q] && h >= std::max(dev::ST_STEP2_MIN_H, fuse_min_h);
-                    (pair ? l2 : le).items.push_back(it);
                     if (!pair && (first || h > split_h)) le_small = false;
-                    next_h[q] = h - (pair ? 2 : 1);
-                    cur_in[q] = it.out; cur_stride[q] = (size_t)1 << (pair ? h - 1 : h);
+                    (pair ? l2 : le).push_back(take(q, first ? J.buf[0] : next_out(q), pair ? 2 : 1));
                 }
-                if (le.items.empty() && l2.items.empty()) break;
-                if (!l2.items.empty()) plan.push_back(l2);
-                if (!le.items.empty()) {
-                    if (le_small) {
-                        le.mode = 1;
-                        for (auto& it : le.items) {   // (cur_in[] already points at it.out: repoint both)
-                            E2* fresh = ctx->alloc_n<E2>((size_t)st_jobs[it.job].ntab << it.h_log2);
-                            it.out = fresh;
-                            cur_in[it.job] = fresh;
-                            lsum.items.push_back(it);
-                        }
+                if (le.empty() && l2.empty()) break;
+                if (!l2.empty()) { line(kind, false, 2, 0, false, false, l2); emit(StLaunch::Step2, kind, false, 2, 0, l2); }
+                if (le.empty()) continue;
+                if (le_small)
+                    for (auto& it : le) {   // (the job already points at it.out: repoint both)
+                        it.out = alloc_e2((size_t)jobs[it.job].ntab << it.h_log2);
+                        cur_in[it.job] = it.out;
+                        split.push_back(it);
+                        runs[it.job].push_back(it);
                     }
-                    plan.push_back(le);
-                }
+                line(kind, false, 1, le_small ? 1 : 0, false, false, le);
+                emit(StLaunch::Step, kind, false, 1, le_small ? 1 : 0, le, !le_small || o.fold_per_round);
+                if (le_small) fold_at = P.launches.size();
             }
-            if (!lsum.items.empty()) {
+            // The fold-only rounds of one job are consecutive rounds, each reading what the one before it wrote: a run, issued as ONE item
+            // of a fold-run launch (kernels.hpp: StFoldRun) where the LAST fold-only round stands - every run's input was written by a
+            // launch planned ahead of its first fold-only round. A run longer than a tile holds is cut: piece c of every run shares launch c.
+            if (!split.empty() && !o.fold_per_round) {
+                std::vector<std::vector<dev::StFoldRun>> pieces;   // [c]: piece c of every run that has one
+                for (int q = 0; q < nj; q++) {
+                    const std::vector<dev::StItem>& run = runs[q];
+                    for (size_t k = 1; k < run.size(); k++)
+                        if (run[k].h_log2 != run[k - 1].h_log2 - 1 || run[k].in != (const void*)run[k - 1].out || run[k].in_stride != (size_t)1 << run[k - 1].h_log2)
+                            throw Error("fold-only rounds of a job that do not follow each other");
+                    P.fold_rounds += (int)run.size();
+                    P.fold_max_run = std::max(P.fold_max_run, (int)run.size());
+                    size_t c = 0;
+                    for (size_t pos = 0; pos < run.size(); c++) {
+                        dev::StFoldRun F;
+                        memset(&F, 0, sizeof(F));
+                        F.job = q; F.h0 = run[pos].h_log2; F.in = (const E2*)run[pos].in; F.in_stride = run[pos].in_stride;
+                        F.nrounds = (int)std::min<size_t>((size_t)std::min(o.fold_tile_log2, F.h0) + 1, run.size() - pos);
+                        for (int k = 0; k < F.nrounds; k++) F.out[k] = run[pos + k].out;
+                        if (pieces.size() <= c) pieces.emplace_back();
+                        pieces[c].push_back(F);
+                        pos += (size_t)F.nrounds;
+                    }
+                }
+                std::vector<StLaunch> fl;
+                for (const auto& pc : pieces)
+                    for (size_t at = 0; at < pc.size(); at += MAX_BATCH) {
+                        StLaunch L = launch(StLaunch::FoldRuns, kind);
+                        L.off = P.fold_runs.size(); L.cnt = (int)std::min<size_t>(MAX_BATCH, pc.size() - at);
+                        P.fold_runs.insert(P.fold_runs.end(), pc.begin() + at, pc.begin() + at + L.cnt);
+                        L.grid = dev::st_plan_fold_blocks(P.fold_runs.data() + L.off, L.cnt, jobs.data(), o.fold_tile_log2);
+                        L.cls = cls_gp_ext;
+                        for (int k = 0; k < L.cnt; k++) {   // credited round by round as the per-round launches are; by design: the first level read once, every level written once
+                            const dev::StFoldRun& F = P.fold_runs[L.off + k];
+                            const int rd = jobs[F.job].nvars - 1 - F.h0;
+                            L.design += reads(F.job, rd, jobs[F.job].ntab);
+                            for (int r = 0; r < F.nrounds; r++) {
+                                L.bytes += round_bytes(F.job, rd + r, false); L.model += round_bytes(F.job, rd + r, true);
+                                L.design += writes(F.job, F.h0 - r);
+                            }
+                        }
+                        fl.push_back(L);
+                    }
+                P.launches.insert(P.launches.begin() + fold_at, fl.begin(), fl.end());
+                P.fold_launches = (int)fl.size(); P.fold_tile_log2 = o.fold_tile_log2;
+            }
+            if (!split.empty()) {
                 // Rounds (h, h - 1) of one job are summed from round h's input alone (the fused pass folds round h in registers): a third
                 // of the reads less - for a job of few table pairs. The fused pass walks a job's pairs serially in every thread, and
                 // with many pairs that chain, not the bytes, is what the launch waits for (kernels.hpp: ST_SUMS_PAIR_MAX_NB). A job's
                 // rounds follow each other, largest first; a pair is ONE launched item, so none straddles two launches.
-                // HG_SUMS_SINGLE=1: one item per round, in fold order, through st_step.
-                if (!hg_env_on("HG_SUMS_SINGLE")) {
-                    std::vector<dev::StItem> byjob = lsum.items;
-                    std::stable_sort(byjob.begin(), byjob.end(), [](const dev::StItem& a, const dev::StItem& b) { return a.job < b.job; });
-                    for (size_t k = 0; k < byjob.size(); k++) {
-                        dev::StItem it = byjob[k];
-                        if (k + 1 < byjob.size() && byjob[k + 1].job == it.job && byjob[k + 1].h_log2 == it.h_log2 - 1 && it.h_log2 >= dev::ST_STEP2_MIN_H &&
-                            st_jobs[it.job].ntab / 2 <= dev::ST_SUMS_PAIR_MAX_NB) { it.nrounds = 2; k++; n_sum_pairs++; }
-                        else n_sum_singles++;
-                        lsum.run.push_back(it);
+                line(kind, false, 1, 2, false, false, split);
+                std::vector<dev::StItem> sums;   // what is launched for `split`: job-major, consecutive rounds of a job as one item (st_sums)
+                if (!o.sums_single) {
+                    std::stable_sort(split.begin(), split.end(), [](const dev::StItem& a, const dev::StItem& b) { return a.job < b.job; });
+                    for (size_t k = 0; k < split.size(); k++) {
+                        dev::StItem it = split[k];
+                        if (k + 1 < split.size() && split[k + 1].job == it.job && split[k + 1].h_log2 == it.h_log2 - 1 && it.h_log2 >= dev::ST_STEP2_MIN_H &&
+                            jobs[it.job].ntab / 2 <= dev::ST_SUMS_PAIR_MAX_NB) { it.nrounds = 2; k++; P.n_sum_pairs++; }
+                        else P.n_sum_singles++;
+                        sums.push_back(it);
                     }
-                } else n_sum_singles += (int)lsum.items.size();
-                plan.push_back(lsum);
+                } else { sums = split; P.n_sum_singles += (int)split.size(); }
+                emit(StLaunch::Sums, kind, false, 1, o.sums_single ? 2 : 0, sums);
             }
-            // the tail launch: every job's remaining rounds
-            {
-                Launch lc{kind, false, 0, true, 0, {}};
-                for (int q = 0; q < nj; q++) {
-                    const dev::StJob& J = st_jobs[q];
-                    if (J.kind != kind || next_h[q] < 0) continue;
-                    const int hs = next_h[q];
-                    dev::StItem it;
-                    memset(&it, 0, sizeof(it));
-                    it.job = q; it.in = cur_in[q]; it.in_stride = cur_stride[q];
-                    it.rd = J.nvars - 1 - hs; it.nrounds = hs + 1; it.out = J.final_out;
-                    if (st_slot[q].tail_ntab) {   // the tail reads the per-memory tables (gathered right before it is launched)
-                        const SlotPlan& sp = st_slot[q];
-                        if (cur_stride[q] != (size_t)2 << hs) throw Error("slot-form job: unexpected table length at the tail");
-                        E2* rg = ctx->alloc_n<E2>((size_t)sp.tail_ntab << (hs + 1));
-                        regroups.push_back(Regroup{q, (const E2*)cur_in[q], rg, hs + 1});
-                        it.in = rg; it.ntab = sp.tail_ntab;
-                    }
-                    lc.items.push_back(it);
-                    next_h[q] = -1;
-                }
-                if (!lc.items.empty()) plan.push_back(lc);
-            }
-        }
-        // The fold-only rounds (mode 1) of one job are consecutive rounds, each reading what the one before it wrote: a run, issued as ONE
-        // item of the fold-run launch (kernels.hpp: StFoldRun) at the position of the plan's LAST mode-1 entry - every run's input was
-        // written by a launch planned ahead of its first fold-only round. A run longer than a tile holds is cut: piece c of every run
-        // shares launch c. HG_FOLD_ROUNDS=1: one launch per round, where it stands (st_step, mode 1). HG_FOLD_TILE_LOG2=<1..9>: a
-        // smaller tile, so that small shapes reach the cut and the many-tiles paths. Both are read at every flush.
-        int fold_at = -1, fold_tile = dev::ST_FOLD_TILE_LOG2, fold_rounds = 0, fold_max_run = 0;
-        struct FoldLaunch { size_t off; int cnt, grid; double bytes, model, design; };
-        std::vector<FoldLaunch> fold_launches;
-        std::vector<dev::StFoldRun> fold_items;
-        if (!hg_env_on("HG_FOLD_ROUNDS")) {
-            if (const char* e = getenv("HG_FOLD_TILE_LOG2")) { const int v = atoi(e); if (v >= 1 && v <= dev::ST_FOLD_TILE_MAX_LOG2) fold_tile = v; }
-            std::vector<std::vector<dev::StItem>> runs(nj);
-            for (size_t li = 0; li < plan.size(); li++)
-                if (plan[li].mode == 1) { fold_at = (int)li; for (const dev::StItem& it : plan[li].items) runs[it.job].push_back(it); }
-            std::vector<std::vector<dev::StFoldRun>> pieces;   // [c]: piece c of every run that has one
+            // the tail launch: every job's remaining rounds. The grand-product tail folds first and sums once (kernels.hip: k_st_tail<.., FF>)
+            const bool tail_ff = kind == dev::SC_GRANDPROD && !o.tail_whole_rounds;
+            std::vector<dev::StItem> tail;
             for (int q = 0; q < nj; q++) {
-                const std::vector<dev::StItem>& run = runs[q];
-                for (size_t k = 1; k < run.size(); k++)
-                    if (run[k].h_log2 != run[k - 1].h_log2 - 1 || run[k].in != (const void*)run[k - 1].out || run[k].in_stride != (size_t)1 << run[k - 1].h_log2)
-                        throw Error("fold-only rounds of a job that do not follow each other");
-                fold_rounds += (int)run.size();
-                fold_max_run = std::max(fold_max_run, (int)run.size());
-                size_t c = 0;
-                for (size_t pos = 0; pos < run.size(); c++) {
-                    dev::StFoldRun F;
-                    memset(&F, 0, sizeof(F));
-                    F.job = q; F.h0 = run[pos].h_log2; F.in = (const E2*)run[pos].in; F.in_stride = run[pos].in_stride;
-                    F.nrounds = (int)std::min<size_t>((size_t)std::min(fold_tile, F.h0) + 1, run.size() - pos);
-                    for (int k = 0; k < F.nrounds; k++) F.out[k] = run[pos + k].out;
-                    if (pieces.size() <= c) pieces.emplace_back();
-                    pieces[c].push_back(F);
-                    pos += (size_t)F.nrounds;
+                const dev::StJob& J = jobs[q];
+                if (J.kind != kind || next_h[q] < 0) continue;
+                const int hs = next_h[q];
+                dev::StItem it;
+                memset(&it, 0, sizeof(it));
+                it.job = q; it.in = cur_in[q]; it.in_stride = cur_stride[q];
+                it.rd = J.nvars - 1 - hs; it.nrounds = hs + 1; it.out = J.final_out;
+                if (Q[q].slot.tail_ntab) {   // the tail reads the per-memory tables, gathered right before it is launched (Regroup) from cur_in[q]
+                    if (cur_stride[q] != (size_t)2 << hs) throw Error("slot-form job: unexpected table length at the tail");
+                    it.in = alloc_e2((size_t)Q[q].slot.tail_ntab << (hs + 1)); it.ntab = Q[q].slot.tail_ntab;
                 }
+                tail.push_back(it);
+                next_h[q] = -1;
             }
-            for (const auto& pc : pieces)
-                for (size_t o = 0; o < pc.size(); o += MAX_BATCH) {
-                    FoldLaunch FL{fold_items.size(), (int)std::min<size_t>(MAX_BATCH, pc.size() - o), 0, 0, 0, 0};
-                    fold_items.insert(fold_items.end(), pc.begin() + o, pc.begin() + o + FL.cnt);
-                    FL.grid = dev::st_plan_fold_blocks(fold_items.data() + FL.off, FL.cnt, st_jobs.data(), fold_tile);
-                    fold_launches.push_back(FL);
+            if (!tail.empty()) line(kind, false, 0, 0, true, false, tail);
+            for (size_t at = 0; at < tail.size(); at += MAX_BATCH) {
+                StLaunch R = launch(StLaunch::Regroup, kind), T = launch(StLaunch::Tail, kind);
+                R.off = P.regroups.size();
+                T.off = P.items.size() + at; T.cnt = (int)std::min<size_t>(MAX_BATCH, tail.size() - at);
+                T.cls = cls_tail; T.fold_first = tail_ff;
+                for (int k = 0; k < T.cnt; k++) {
+                    const dev::StItem& it = tail[at + k];
+                    const int h0 = jobs[it.job].nvars - 1 - it.rd, tn = it.ntab > 0 ? it.ntab : jobs[it.job].ntab;
+                    for (int r = 0; r < it.nrounds; r++) { T.bytes += round_bytes(it.job, it.rd + r, false); T.model += round_bytes(it.job, it.rd + r, true); }
+                    T.design += reads(it.job, it.rd, tn);   // (nothing written)
+                    T.table_bytes = std::max(T.table_bytes, dev::st_tail_table_bytes(tn, h0, tail_ff));
+                    if (tail_ff && it.nrounds > dev::st_tail_whole_rounds(tn, h0)) P.n_tail_ff++;   // (a tail of one or two whole rounds has nothing to fold first)
+                    else if (kind == dev::SC_GRANDPROD) P.n_tail_whole++;
+                    if (it.ntab > 0) {   // (a slot-form job: its tables are one round longer than the tail's first half, 2^(h0 + 1))
+                        const SlotPlan& sp = Q[it.job].slot;
+                        P.regroups.push_back(dev::gp_slot_regroup_job((const E2*)cur_in[it.job], (E2*)it.in, sp.d_slot_of, sp.d_ratio, sp.nrows, sp.nslots, sp.npairs, h0 + 1, (sp.tail_ntab & 1) != 0));
+                        R.cnt++;
+                        R.rg_max = std::max(R.rg_max, ((size_t)sp.nrows + (sp.tail_ntab & 1)) << (h0 + 1));
+                    }
                 }
+                if (R.cnt) P.launches.push_back(R);
+                P.launches.push_back(T);
+            }
+            P.items.insert(P.items.end(), tail.begin(), tail.end());
         }
-        if (hg_debug("plan"))   // one line per plan entry, in launch order (read at every call: the tests switch it per case); a mode=1 line is a round of the fold-run launch, which is issued where the last of them stands
-            for (const Launch& L : plan) {
-                if (L.after_seq) { fprintf(stderr, "[hg plan] stride kind=%d after_seq=1\n", L.kind); continue; }
-                int lo = INT_MAX, hi = INT_MIN;
-                for (const dev::StItem& it : L.items) { const int v = L.tail ? it.nrounds : it.h_log2; lo = std::min(lo, v); hi = std::max(hi, v); }
-                fprintf(stderr, "[hg plan] stride kind=%d base=%d nrounds=%d mode=%d tail=%d hash=%d items=%zu %s=%d..%d\n", L.kind, L.base ? 1 : 0, L.nrounds,
-                        L.mode, L.tail ? 1 : 0, L.hash ? 1 : 0, L.items.size(), L.tail ? "rounds" : "h", lo, hi);
+        return P;
+    }
+    void print_stride_plan(const StridePlan& P) const {   // (the tokens are read at every call: the tests switch them per case)
+        if (hg_debug("plan"))
+            for (const StLine& l : P.lines) {
+                if (l.after_seq) { fprintf(stderr, "[hg plan] stride kind=%d after_seq=1\n", l.kind); continue; }
+                fprintf(stderr, "[hg plan] stride kind=%d base=%d nrounds=%d mode=%d tail=%d hash=%d items=%zu %s=%d..%d\n", l.kind, l.base, l.nrounds,
+                        l.mode, l.tail, l.hash, l.items, l.tail ? "rounds" : "h", l.lo, l.hi);
             }
+        if (hg_debug("endgame") && (P.n_tail_ff || P.n_tail_whole || P.n_sum_pairs || P.n_sum_singles))
+            fprintf(stderr, "[hg endgame] stride tail_fold_first=%d tail_whole=%d sums_pairs=%d sums_singles=%d\n", P.n_tail_ff, P.n_tail_whole, P.n_sum_pairs, P.n_sum_singles);
+        if (hg_debug("folds") && P.fold_launches)   // `rounds` = the items of the plan's mode=1 lines
+            fprintf(stderr, "[hg folds] stride launches=%d items=%zu rounds=%d max_run=%d tile_log2=%d\n", P.fold_launches, P.fold_runs.size(), P.fold_rounds, P.fold_max_run, P.fold_tile_log2);
+    }
+    void flush_stride() {
+        if (st_queue.empty()) return;
+        const int nj = (int)st_queue.size();
+        if (hoist_consts)   // (as in flush_prodsum: the rounds stay recorded)
+            for (const StQueued& q : st_queue) {
+                const size_t N = (size_t)1 << q.J.nvars;
+                kept_writes(crange(q.J.buf[0], (size_t)q.J.ntab * std::max<size_t>(N / 2, 1)));
+                kept_writes(crange(q.J.buf[1], (size_t)q.J.ntab * std::max<size_t>(N / 4, 1)));
+                kept_writes(crange(q.J.final_out, (size_t)q.J.ntab));
+            }
+        StridePlan P = plan_stride(st_queue, stride_opts(), [this](size_t n) { return ctx->alloc_n<E2>(n); });
+        print_stride_plan(P);
         if (!gp_eps.empty()) {   // the claim epilogues and their weight vectors: one upload each
             std::vector<E2> wts;
             std::vector<dev::GpClaimEp> eps;
             for (const GpEpReq& e : gp_eps) {
-                if (e.job < 0 || e.job >= nj || st_jobs[e.job].kind != dev::SC_GRANDPROD) throw Error("grand product: claim epilogue without its job");
+                if (e.job < 0 || e.job >= nj || P.jobs[e.job].kind != dev::SC_GRANDPROD) throw Error("grand product: claim epilogue without its job");
                 wts.insert(wts.end(), e.winv.begin(), e.winv.end());
                 wts.insert(wts.end(), e.gnext.begin(), e.gnext.end());
             }
@@ -309,180 +385,82 @@
                 ep.winv = d_wts + o; o += gp_eps[i].winv.size();
                 ep.gnext = d_wts + o; o += gp_eps[i].gnext.size();
                 eps.push_back(ep);
-                st_jobs[gp_eps[i].job].ep = d_eps + i;
+                P.jobs[gp_eps[i].job].ep = d_eps + i;
             }
             upload(d_wts, wts.data(), wts.size() * sizeof(E2), "upload claim weights");
             upload(d_eps, eps.data(), eps.size() * sizeof(dev::GpClaimEp), "upload claim epilogues");
             gp_eps.clear();
         }
         dev::StJob* d_jobs = ctx->alloc_n<dev::StJob>(nj);
-        upload(d_jobs, st_jobs.data(), (size_t)nj * sizeof(dev::StJob), "upload jobs");
-        std::vector<dev::StItem> flat;
-        std::vector<size_t> offs;
-        std::vector<std::vector<int>> grids(plan.size());
-        for (size_t li = 0; li < plan.size(); li++) {
-            Launch& L = plan[li];
-            std::vector<dev::StItem>& its = L.run.empty() ? L.items : L.run;
-            const size_t batch = L.run.empty() ? MAX_BATCH : (size_t)dev::ST_SUMS_MAX_ITEMS;
-            if (!L.tail && !L.after_seq)
-                for (size_t o = 0; o < its.size(); o += batch)
-                    grids[li].push_back(dev::st_plan_blocks(its.data() + o, (int)std::min<size_t>(batch, its.size() - o), L.nrounds == 2));
-            offs.push_back(flat.size());
-            flat.insert(flat.end(), its.begin(), its.end());
-        }
-        dev::StItem* d_items = ctx->alloc_n<dev::StItem>(flat.size());
-        upload(d_items, flat.data(), flat.size() * sizeof(dev::StItem), "upload step items");
-        // algorithmic bytes of one round of job q (SURVEY.md 8(d)): every live table read once, every folded table written once.
-        // model = true: the tables of the reference's batch (a mirrored grand product is modelled with its read AND write tables, the
-        // collation sum-check with its alpha tables), false: the tables this implementation streams
-        auto round_bytes = [&](int q, int rd, bool model) {
-            const dev::StJob& J = st_jobs[q];
-            size_t half = (size_t)1 << (J.nvars - 1 - rd);
-            return (double)(model ? st_credit_ntab[q] : J.ntab) * (2.0 * half * ((J.base && rd == 0) ? 8 : 16) + half * 16.0);
-        };
-        // the same launch in bytes moved to or from HBM by design (hg_kernel_stat::hbm_bytes): the tables of round rd read once, the
-        // folds of round rd + nrounds - 1 written once (the tail: nothing written), plus the tree level a first round emits
-        auto design_bytes = [&](int q, int rd, int nrounds, bool tail) {
-            const dev::StJob& J = st_jobs[q];
-            const size_t half = (size_t)1 << (J.nvars - 1 - rd);
-            double b = (double)J.ntab * 2.0 * half * ((J.base && rd == 0) ? 8 : 16);
-            if (rd == 0 && st_hash_reads[q] >= 0) b = st_hash_reads[q];
-            if (!tail) b += (double)J.ntab * (double)(half >> (nrounds - 1)) * 16.0;
-            if (rd == 0) b += st_level_design[q];
-            return b;
-        };
+        upload(d_jobs, P.jobs.data(), (size_t)nj * sizeof(dev::StJob), "upload jobs");
+        dev::StItem* d_items = ctx->alloc_n<dev::StItem>(P.items.size());
+        upload(d_items, P.items.data(), P.items.size() * sizeof(dev::StItem), "upload step items");
         dev::StFoldRun* d_fold = nullptr;
-        if (!fold_items.empty()) {
-            d_fold = ctx->alloc_n<dev::StFoldRun>(fold_items.size());
-            upload(d_fold, fold_items.data(), fold_items.size() * sizeof(dev::StFoldRun), "upload fold runs");
-            for (FoldLaunch& FL : fold_launches)   // credited round by round as the per-round launches are; by design: the first level read once, every level written once
-                for (int q = 0; q < FL.cnt; q++) {
-                    const dev::StFoldRun& F = fold_items[FL.off + q];
-                    const dev::StJob& J = st_jobs[F.job];
-                    FL.design += (double)J.ntab * 2.0 * (double)((size_t)1 << F.h0) * 16.0;
-                    for (int k = 0; k < F.nrounds; k++) {
-                        FL.bytes += round_bytes(F.job, J.nvars - 1 - F.h0 + k, false); FL.model += round_bytes(F.job, J.nvars - 1 - F.h0 + k, true);
-                        FL.design += (double)J.ntab * (double)((size_t)1 << (F.h0 - k)) * 16.0;
-                    }
-                }
+        if (!P.fold_runs.empty()) {
+            d_fold = ctx->alloc_n<dev::StFoldRun>(P.fold_runs.size());
+            upload(d_fold, P.fold_runs.data(), P.fold_runs.size() * sizeof(dev::StFoldRun), "upload fold runs");
         }
-        for (size_t li = 0; li < plan.size(); li++) {
-            const Launch& L = plan[li];
+        for (const StLaunch& L : P.launches) {
             if (L.kind == dev::SC_GRANDPROD && st_before_gp) { stamp("collation done"); st_before_gp(); st_before_gp = nullptr; stamp("grand products may start"); }
-            if (L.mode == 1 && fold_at >= 0) {   // a fold-only round of the runs: all of them go where the last one stands
-                if ((int)li == fold_at)
-                    for (const FoldLaunch& FL : fold_launches) {
-                        ctx->prof_begin(cls_gp_ext, FL.bytes, FL.model, FL.design);
-                        dev::st_fold_runs(st, d_jobs, d_fold + FL.off, FL.cnt, FL.grid, ctx->d_chal);
-                        ctx->prof_end();
-                    }
-                continue;
-            }
-            if (L.after_seq) {
+            hipStream_t s = L.side ? ctx->stream_sum : st;
+            E2* part = L.side ? ctx->d_partials4 : partials;
+            switch (L.tag) {
+            case StLaunch::AfterSeq:
                 for (auto& f : st_after_seq) f();
                 st_after_seq.clear();
                 if (st_before_gp2) { st_before_gp2(); st_before_gp2 = nullptr; }   // the launches from here on contain grand product #2's jobs
-                continue;
-            }
-            const std::vector<dev::StItem>& its = L.run.empty() ? L.items : L.run;   // (mode 2: the launched form of the items)
-            const size_t batch = L.run.empty() ? MAX_BATCH : (size_t)dev::ST_SUMS_MAX_ITEMS;
-            for (size_t o = 0; o < its.size(); o += batch) {
-                const int cnt = (int)std::min<size_t>(batch, its.size() - o);
-                double bytes = 0, model = 0;
+                break;
+            case StLaunch::SeqFirst: case StLaunch::First: case StLaunch::Step:
+                ctx->prof_begin(L.cls, L.bytes, L.model, L.design);
                 if (L.hash) {
-                    const dev::StItem& it = its[o];
-                    // algorithmic bytes (SURVEY.md 8(d)): the sum-check round plus the passes this launch absorbs - the hash build
-                    // (dims, read_ts per chunk; E read, read / write hashes written per memory) and product-tree level 1
-                    bytes = round_bytes(it.job, 0, false) + st_fused_bytes[it.job];
-                    model = round_bytes(it.job, 0, true) + st_fused_bytes[it.job] + st_fused_model_extra[it.job];
-                    ctx->prof_begin(cls_gp_hash, bytes, model, design_bytes(it.job, 0, 1, false));
-                    dev::st_first_hash(st, d_jobs + it.job, d_items + offs[li] + o, grids[li][0], st_jobs[it.job].mirror != 0, hash_recomp, ctx->d_chal, partials, d_res(), st_slot[it.job].tail_ntab != 0);
-                    ctx->prof_end();
-                    stamp("first hash round done");
-                    continue;
+                    const int q = P.items[L.off].job;
+                    dev::st_first_hash(s, d_jobs + q, d_items + L.off, L.grid, P.jobs[q].mirror != 0, hash_recomp, ctx->d_chal, part, d_res(), st_queue[q].slot.tail_ntab != 0);
+                } else dev::st_step(s, L.kind, L.base, d_jobs, d_items + L.off, L.cnt, L.grid, ctx->d_chal, part, d_res(), L.slot, L.mode);
+                ctx->prof_end();
+                if (L.hash) stamp("first hash round done");
+                break;
+            case StLaunch::Step2:
+                ctx->prof_begin(L.cls, L.bytes, L.model, L.design);
+                dev::st_step2(s, L.kind, d_jobs, d_items + L.off, L.cnt, L.grid, ctx->d_chal, part, d_res());
+                ctx->prof_end();
+                break;
+            case StLaunch::FoldRuns:
+                ctx->prof_begin(L.cls, L.bytes, L.model, L.design);
+                dev::st_fold_runs(s, d_jobs, d_fold + L.off, L.cnt, L.grid, ctx->d_chal);
+                ctx->prof_end();
+                break;
+            case StLaunch::Sums:   // beside whatever the main stream does next, joined at the end of the prove
+                if (L.first) {
+                    hip_check(hipEventRecord(ctx->ev_sum[0], st), "split rounds: folds done");
+                    hip_check(hipStreamWaitEvent(s, ctx->ev_sum[0], 0), "split rounds: wait for the folds");
                 }
-                if (L.tail) {
-                    size_t table_bytes = 0;
-                    double design = 0;
-                    // the grand-product tail folds first and sums once (kernels.hip: k_st_tail<.., FF>); HG_TAIL_WHOLE_ROUNDS=1: round by round
-                    const bool tail_ff = L.kind == dev::SC_GRANDPROD && !hg_env_on("HG_TAIL_WHOLE_ROUNDS");
-                    std::vector<dev::SlotRegroupJob> rg_jobs;
-                    size_t rg_max = 0;
-                    for (int q = 0; q < cnt; q++) {
-                        const dev::StItem& it = its[o + q];
-                        const dev::StJob& J = st_jobs[it.job];
-                        for (int k = 0; k < it.nrounds; k++) { bytes += round_bytes(it.job, it.rd + k, false); model += round_bytes(it.job, it.rd + k, true); }
-                        design += (double)(it.ntab > 0 ? it.ntab : J.ntab) * 2.0 * (double)((size_t)1 << (J.nvars - 1 - it.rd)) * ((J.base && it.rd == 0) ? 8 : 16);
-                        const int h0 = J.nvars - 1 - it.rd, tn = it.ntab > 0 ? it.ntab : J.ntab;
-                        table_bytes = std::max(table_bytes, dev::st_tail_table_bytes(tn, h0, tail_ff));
-                        if (tail_ff && it.nrounds > dev::st_tail_whole_rounds(tn, h0)) n_tail_ff++;   // (a tail of one or two whole rounds has nothing to fold first)
-                        else if (L.kind == dev::SC_GRANDPROD) n_tail_whole++;
-                        for (const Regroup& g : regroups) if (g.job == it.job) {
-                            const SlotPlan& sp = st_slot[it.job];
-                            rg_jobs.push_back(dev::gp_slot_regroup_job(g.in, g.out, sp.d_slot_of, sp.d_ratio, sp.nrows, sp.nslots, sp.npairs, g.len_log2, (sp.tail_ntab & 1) != 0));
-                            rg_max = std::max(rg_max, ((size_t)sp.nrows + (sp.tail_ntab & 1)) << g.len_log2);
-                        }
-                    }
-                    if (!rg_jobs.empty()) {   // the slot-form jobs' per-memory tables, gathered in ONE launch
-                        dev::SlotRegroupJob* d_rg = ctx->alloc_n<dev::SlotRegroupJob>(rg_jobs.size());
-                        upload(d_rg, rg_jobs.data(), rg_jobs.size() * sizeof(dev::SlotRegroupJob), "upload regroup jobs");
-                        dev::gp_slot_regroup_jobs(st, d_rg, (int)rg_jobs.size(), rg_max);
-                    }
-                    ctx->prof_begin(cls_tail, bytes, model, design);
-                    dev::st_tail(st, L.kind, d_jobs, d_items + offs[li] + o, cnt, table_bytes, ctx->d_chal, d_res(), tail_ff);
-                    ctx->prof_end();
-                } else {
-                    double design = 0;
-                    for (int q = 0; q < cnt; q++) {
-                        const dev::StItem& it = its[o + q];
-                        const dev::StJob& J = st_jobs[it.job];
-                        design += design_bytes(it.job, J.nvars - 1 - it.h_log2, L.nrounds, false);
-                        // algorithmic bytes in the per-round accounting of SURVEY.md 8(d): a fused launch is credited with both of
-                        // its rounds although the intermediate folded tables never reach HBM (DESIGN.md 6)
-                        for (int k = 0; k < L.nrounds; k++) { bytes += round_bytes(it.job, J.nvars - 1 - it.h_log2 + k, false); model += round_bytes(it.job, J.nvars - 1 - it.h_log2 + k, true); }
-                        if (L.base && it.h_log2 == J.nvars - 1) { bytes += st_fused_bytes[it.job]; model += st_fused_bytes[it.job]; }  // the tree level a first round also writes
-                    }
-                    const int grid = grids[li][o / batch];
-                    int cls = L.kind == dev::SC_GRANDPROD ? (L.base ? cls_gp_base : (L.nrounds == 2 ? cls_gp_ext2 : cls_gp_ext)) : (L.base ? cls_col_base : (L.nrounds == 2 ? cls_col_ext2 : cls_col_ext));
-                    if (L.mode == 2) {   // the split rounds' sums: beside whatever the main stream does next, joined at the end of the prove
-                        if (o == 0) {
-                            hip_check(hipEventRecord(ctx->ev_sum[0], st), "split rounds: folds done");
-                            hip_check(hipStreamWaitEvent(ctx->stream_sum, ctx->ev_sum[0], 0), "split rounds: wait for the folds");
-                        }
-                        ctx->prof_stream = ctx->stream_sum;
-                        ctx->prof_begin(cls_gp_sums, 0, 0, design);
-                        if (!L.run.empty()) dev::st_sums(ctx->stream_sum, d_jobs, d_items + offs[li] + o, cnt, grid, ctx->d_chal, ctx->d_partials4, d_res());
-                        else dev::st_step(ctx->stream_sum, L.kind, false, d_jobs, d_items + offs[li] + o, cnt, grid, ctx->d_chal, ctx->d_partials4, d_res(), false, 2);
-                        ctx->prof_end();
-                        ctx->prof_stream = st;
-                        if (o + batch >= its.size()) {
-                            hip_check(hipEventRecord(ctx->ev_sum[1], ctx->stream_sum), "split rounds: sums done");
-                            ctx->sum_pending = true;
-                        }
-                        continue;
-                    }
-                    ctx->prof_begin(cls, bytes, model, design);
-                    if (L.nrounds == 2) dev::st_step2(st, L.kind, d_jobs, d_items + offs[li] + o, cnt, grid, ctx->d_chal, partials, d_res());
-                    else dev::st_step(st, L.kind, L.base, d_jobs, d_items + offs[li] + o, cnt, grid, ctx->d_chal, partials, d_res(),
-                                      L.base && st_jobs[its[o].job].slotw != nullptr, L.mode);
-                    ctx->prof_end();
+                ctx->prof_stream = s;
+                ctx->prof_begin(L.cls, L.bytes, L.model, L.design);
+                if (L.mode == 0) dev::st_sums(s, d_jobs, d_items + L.off, L.cnt, L.grid, ctx->d_chal, part, d_res());
+                else dev::st_step(s, L.kind, false, d_jobs, d_items + L.off, L.cnt, L.grid, ctx->d_chal, part, d_res(), false, L.mode);
+                ctx->prof_end();
+                ctx->prof_stream = st;
+                if (L.last) {
+                    hip_check(hipEventRecord(ctx->ev_sum[1], s), "split rounds: sums done");
+                    ctx->sum_pending = true;
                 }
+                break;
+            case StLaunch::Regroup: {
+                dev::SlotRegroupJob* d_rg = ctx->alloc_n<dev::SlotRegroupJob>(L.cnt);
+                upload(d_rg, P.regroups.data() + L.off, (size_t)L.cnt * sizeof(dev::SlotRegroupJob), "upload regroup jobs");
+                dev::gp_slot_regroup_jobs(s, d_rg, L.cnt, L.rg_max);
+                break;
+            }
+            case StLaunch::Tail:
+                ctx->prof_begin(L.cls, L.bytes, L.model, L.design);
+                dev::st_tail(s, L.kind, d_jobs, d_items + L.off, L.cnt, L.table_bytes, ctx->d_chal, d_res(), L.fold_first);
+                ctx->prof_end();
+                break;
             }
         }
-        if (hg_debug("endgame") && (n_tail_ff || n_tail_whole || n_sum_pairs || n_sum_singles))   // what the end of the grand products ran as
-            fprintf(stderr, "[hg endgame] stride tail_fold_first=%d tail_whole=%d sums_pairs=%d sums_singles=%d\n", n_tail_ff, n_tail_whole, n_sum_pairs, n_sum_singles);
-        if (hg_debug("folds") && !fold_launches.empty())   // the fold-only rounds as they were issued: `rounds` = the items of the plan's mode=1 lines
-            fprintf(stderr, "[hg folds] stride launches=%zu items=%zu rounds=%d max_run=%d tile_log2=%d\n", fold_launches.size(), fold_items.size(), fold_rounds, fold_max_run, fold_tile);
         if (st_before_gp) { st_before_gp(); st_before_gp = nullptr; }
         if (st_before_gp2) { st_before_gp2(); st_before_gp2 = nullptr; }
-        st_jobs.clear();
-        st_seq.clear();
-        st_credit_ntab.clear();
-        st_slot.clear();
-        st_fused_bytes.clear();
-        st_fused_model_extra.clear();
-        st_level_design.clear();
-        st_hash_reads.clear();
+        st_queue.clear();
         for (auto& f : st_after_seq) f();  // (no grand-product job was queued: nothing can depend on these, but keep the order)
         st_after_seq.clear();
         if (!scatter.empty()) {
@@ -528,14 +506,19 @@
     // HG_NO_PS_EQ=1: every Libra table materialised (the general form, which small or non-affine nodes take anyway)
     static bool ps_eq_on() { static const bool v = !hg_env_on("HG_NO_PS_EQ"); return v; }
     static size_t ps_tail_items() { return std::min<size_t>(TAIL_ITEMS, dev::ps_tail_items_max()); }   // (the tail keeps a job's folds in LDS)
+    // first round whose work fits the tail
+    static int ps_tail_rd(int npairs, int nvars) {
+        const size_t N = (size_t)1 << nvars;
+        int rd = 0;
+        while (rd < nvars && ((N >> rd) / 2) * (size_t)npairs > ps_tail_items()) rd++;
+        return rd;
+    }
     // First tail round of an eq-factored job, -1: the job is too small for the form. Every round ahead of the tail runs in a fused
     // pair (the tail may start one round later than TAIL_ITEMS says), the last pair at half >= 2^9, and the table handed to the
     // tail must be one of the point's stored suffix tables.
     static int eq_tail_rd(int npairs, int nvars) {
         if (npairs < 1 || npairs > dev::PS_MAX_PAIRS || nvars > dev::PS_EQ_MAX_VARS) return -1;
-        const size_t N = (size_t)1 << nvars;
-        int rd = 0;
-        while (rd < nvars && ((N >> rd) / 2) * (size_t)npairs > ps_tail_items()) rd++;
+        int rd = ps_tail_rd(npairs, nvars);
         if (rd & 1) rd++;
         if (rd < 2 || rd > nvars - 8 || rd < dev::ps_eq_kmin(nvars)) return -1;
         return rd;
@@ -631,15 +614,8 @@
             for (auto& J : jobs) if (J.eq_n) J.eq_scal = d_scal + reinterpret_cast<size_t>(J.eq_scal) / sizeof(E2);
             eq_scal_host.clear();
         }
-        int max_rd = 0;
-        for (auto& J : jobs) {
-            const size_t N = (size_t)1 << J.nvars;
-            int rd = 0;
-            if (J.eq_n) rd = J.tail_rd;   // (planned when the job was queued: eq_tail_rd)
-            else while (rd < J.nvars && ((N >> rd) / 2) * (size_t)J.npairs > ps_tail_items()) rd++;
-            J.tail_rd = rd;
-            max_rd = std::max(max_rd, rd);
-        }
+        for (auto& J : jobs)
+            if (!J.eq_n) J.tail_rd = ps_tail_rd(J.npairs, J.nvars);   // (an eq-factored job's was planned when it was queued: eq_tail_rd)
         auto round_bytes = [&](const dev::PsJob& J, int rd) {
             size_t half = ((size_t)1 << J.nvars) >> (rd + 1);
             if (J.eq_n && rd < J.tail_rd)   // no b tables; the folded A beside the a_i (formed in round 0, not read)
