@@ -62,6 +62,8 @@ EXPORTS = [
     "hg_verify_public_bound_batch", "hg_instance_digest_group",
     "hg_pcs_commit_bn254", "hg_pcs_open_bn254", "hg_pcs_verify_bn254", "hg_secrets_commit_bn254", "hg_claims_open_bn254", "hg_claims_verify_bn254",
     "hg_pcs_verify_device_bn254", "hg_claims_verify_device_bn254", "hg_pcs_verify_device_batch_bn254", "hg_claims_verify_batch_bn254",
+    "hg_pcs_open_folded_bn254", "hg_pcs_verify_folded_bn254", "hg_pcs_verify_folded_device_bn254", "hg_claims_open_folded_bn254", "hg_claims_verify_folded_bn254",
+    "hg_claims_verify_folded_device_bn254",
     "hg_pcs_commit_batch_bn254", "hg_secrets_commit_batch_bn254", "hg_pcs_open_batch_bn254", "hg_claims_open_batch_bn254",
     "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_prodsum_jobs", "hg_claim_tables_eq", "hg_claim_tables_fft", "hg_mle_eval",
     "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_prodsum_jobs_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_verify_public_bn254", "hg_verify_public_device_bn254", "hg_verify_public_batch_bn254", "hg_claims_settle_bn254", "hg_instance_mle_bn254", "hg_instance_mle_batch_bn254", "hg_prove_encryptions_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
@@ -108,10 +110,10 @@ def _two_field_protos(L):
         getattr(L, "hg_claims_verify" + sfx).argtypes = [C.POINTER(HgParams), cp, sz, vp, sz, u64p, sz, cp, sz]
         getattr(L, "hg_pcs_verify_device" + sfx).argtypes = [vp] + getattr(L, "hg_pcs_verify" + sfx).argtypes
         getattr(L, "hg_claims_verify_device" + sfx).argtypes = [vp] + getattr(L, "hg_claims_verify" + sfx).argtypes
-    for name in ("hg_pcs_open", "hg_pcs_verify", "hg_claims_open", "hg_claims_verify"):   # the folded forms take what the unfolded ones take
-        getattr(L, name + "_folded").argtypes = getattr(L, name).argtypes
-    L.hg_pcs_verify_folded_device.argtypes = L.hg_pcs_verify_device.argtypes
-    L.hg_claims_verify_folded_device.argtypes = L.hg_claims_verify_device.argtypes
+    for sfx in ("", "_bn254"):   # the folded forms take what the unfolded ones take
+        for name in ("hg_pcs_open", "hg_pcs_verify", "hg_claims_open", "hg_claims_verify", "hg_pcs_verify_device", "hg_claims_verify_device"):
+            folded = name.replace("_device", "") + "_folded" + ("_device" if name.endswith("_device") else "") + sfx
+            getattr(L, folded).argtypes = getattr(L, name + sfx).argtypes
     L.hg_pcs_free.argtypes, L.hg_pcs_free.restype = [vp], None
     tail = [szp, sz, C.POINTER(cp), szp, sz, C.POINTER(ci), cp, sz]   # claim counts, n_queries, openings, lengths, n, results, reasons, reason_cap
     L.hg_pcs_verify_device_batch.argtypes = L.hg_pcs_verify_device_batch_bn254.argtypes = [vp, C.POINTER(cp), u32p, sz, sz, C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u64p)] + tail
@@ -1370,6 +1372,11 @@ def pcs_folded_opening_bytes(nvars, n_queries=0, log2_row=0):
     return 16 * (3 * max(nvars) + len(nvars)) + pcs_opening_bytes(nvars, 1, n_queries, log2_row)
 
 
+def pcs_folded_opening_bytes_bn254(nvars, n_queries=0, log2_row=0):
+    """32 (3 V + m) + 64 C + Q (32 R + 32 (c+2)): the exact length of a folded opening over BN254, whatever the number of claims."""
+    return 32 * (3 * max(nvars) + len(nvars)) + pcs_opening_bytes_bn254(nvars, 1, n_queries, log2_row)
+
+
 def _pcs_protos():
     """the library: the prototypes of the commitment entries are assigned with the others when it is loaded"""
     return lib()
@@ -1513,9 +1520,7 @@ class Commitment:
         """entry(ctx, *head, n_claims, *tail, n_queries, buffer, its size, length out) of the handle's field -> the opening bytes"""
         bn = self.field == "bn254"
         if folded:
-            if bn:
-                raise ValueError("folded openings are Goldilocks only")
-            entry, cap = entry + "_folded", pcs_folded_opening_bytes(self.nvars, n_queries, self.log2_row)
+            entry, cap = entry + "_folded", (pcs_folded_opening_bytes_bn254 if bn else pcs_folded_opening_bytes)(self.nvars, n_queries, self.log2_row)
         else:
             cap = (pcs_opening_bytes_bn254 if bn else pcs_opening_bytes)(self.nvars, n_claims, n_queries, self.log2_row)
         buf, ln = (C.c_uint8 * cap)(), C.c_size_t(0)
@@ -1534,12 +1539,13 @@ class Commitment:
         return self._open("hg_claims_open", (C.byref(params), self.h, claims.claims), claims.n, (_ptr(claims.points),), n_queries)
 
     def open_folded(self, claims, n_queries=0):
-        """hg_pcs_open_folded: open's claims (at least one) -> a folded opening, whose length does not grow with the claims."""
-        table, pts, vals = _pcs_claim_arrays(claims)
+        """hg_pcs_open_folded, on a BN254 handle hg_pcs_open_folded_bn254: open's claims (at least one) -> a folded opening, whose
+        length does not grow with the claims."""
+        table, pts, vals = (_pcs_claim_arrays_bn254 if self.field == "bn254" else _pcs_claim_arrays)(claims)
         return self._open("hg_pcs_open", (self.h, table, _ptr(pts), _ptr(vals)), len(claims), (), n_queries, folded=True)
 
     def open_claims_folded(self, params, claims, n_queries=0):
-        """hg_claims_open_folded: open_claims as a folded opening."""
+        """hg_claims_open_folded, on a BN254 handle hg_claims_open_folded_bn254: open_claims as a folded opening."""
         return self._open("hg_claims_open", (C.byref(params), self.h, claims.claims), claims.n, (_ptr(claims.points),), n_queries, folded=True)
 
     def free(self):
@@ -1754,6 +1760,16 @@ def claims_verify_bn254(params, root, claims, opening, n_queries=0, log2_row=0, 
     """hg_claims_verify_bn254, with a context hg_claims_verify_device_bn254: an InputClaimsBn254 against the root of
     hg_secrets_commit_bn254: (accepted, reason)."""
     return _claims_verify("_bn254", params, root, claims, opening, n_queries, log2_row, ctx)
+
+
+def pcs_verify_folded_bn254(root, nvars, claims, proof, n_queries=0, log2_row=0, ctx=None):
+    """hg_pcs_verify_folded_bn254, with a context hg_pcs_verify_folded_device_bn254: (accepted, reason) for a folded BN254 opening."""
+    return _pcs_verify("_bn254", _pcs_claim_arrays_bn254, root, nvars, claims, proof, n_queries, log2_row, ctx, "_folded")
+
+
+def claims_verify_folded_bn254(params, root, claims, opening, n_queries=0, log2_row=0, ctx=None):
+    """hg_claims_verify_folded_bn254, with a context hg_claims_verify_folded_device_bn254: claims_verify_bn254 for a folded opening."""
+    return _claims_verify("_bn254", params, root, claims, opening, n_queries, log2_row, ctx, "_folded")
 
 
 class LassoNode:

@@ -10,6 +10,8 @@
 // The host flows of the verifiers, the batch opener, the batch committer, pcs_combine_device and pcs_columns_device are the templates
 // of pcs_flow.hpp, written once for both fields; this file gives them BnPcs, the BN254 policy: the types, the transcript calls, the
 // texts and one launch function per kernel step. pcs_commit_device and pcs_commit_words_enqueue keep a host flow of their own.
+// The prover's side of a folded opening (pcs_bn254.hpp PcsFoldSource) is at the end: the kernel that builds g, the round kernels of the
+// reduction sum-check and their host driver BnFoldDev.
 
 constexpr int BNPCS_TPB = 256;
 static unsigned bnpcs_blocks(size_t n) { return (unsigned)((n + BNPCS_TPB - 1) / BNPCS_TPB); }
@@ -455,6 +457,13 @@ struct BnPcs {
     static constexpr const char *VERIFY_NAME = "hg_pcs_verify_device_bn254", *OPEN_NAME = "hg_pcs_open_bn254", *TIMES_TAG = "bn254 ",
                                 *NOT_BELOW = "a table holds an element that is not below r";
     static size_t opening_bytes(const pcs::Shape& sh, size_t n, size_t Q) { return pcs_opening_bytes(sh, n, Q); }
+    // the folded opening (verify_folded_flow)
+    static constexpr const char* VERIFY_FOLDED_NAME = "hg_pcs_verify_folded_device_bn254";
+    static size_t folded_header_bytes(const pcs::Shape& sh) { return pcs_folded_header_bytes(sh); }
+    static size_t folded_opening_bytes(const pcs::Shape& sh, size_t Q) { return pcs_folded_opening_bytes(sh, Q); }
+    static PcsFoldedHeader folded_header(const pcs::Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof) {
+        return pcs_folded_header(sh, root, claims, Q, proof);
+    }
     // the transcript
     static FsTranscript start_transcript(const pcs::Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q) { return pcs_start_transcript(sh, root, claims, Q); }
     static std::vector<Fr> rho_powers(FsTranscript& tr, size_t R) { return pcs_rho_powers(pcs_squeeze(tr), R); }
@@ -573,5 +582,301 @@ std::vector<pcs::Commitment*> pcs_commit_device_batch(const char* who, hg_ctx* c
 }
 std::vector<pcs::Opened> pcs_open_device_batch(const char* who, const char* single, hg_ctx* ctx, const std::vector<PcsOpenItem>& items, size_t Q) {
     return pcs::open_batch_flow<BnPcs>(who, single, ctx, items, Q);
+}
+std::string pcs_verify_folded_device(hg_ctx* ctx, const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof, size_t len) {
+    return pcs::verify_folded_flow<BnPcs>(ctx, sh, root, claims, Q, proof, len);
+}
+
+// ---- the reduction sum-check of a folded opening (pcs_bn254.hpp PcsFoldSource; hg.h "Folded openings over BN254"): the prover's
+// table-sized work, the structure of FoldDev in pcs.hip over Fr. The raw rows of a handle are its tables, contiguous in table order:
+// table t starts at element s_t = off_t C, plain canonical words that are never written. g lies in an Fr array parallel to them, in
+// Montgomery form. Round 0 reads both as they are; the kernel of round j >= 1 folds every live table and its g by r_{j-1} into buffers of
+// half the size and forms round j's sums from the folded entries while it holds them. After j folds table t lies at entry s_t >> j of
+// its buffer (two live tables never overlap there); the two buffer pairs alternate. A fold x + r d is lz_fold with the launch's
+// fold_consts(r) (r in Montgomery form): the constants are r 2^(32 i) as plain integers, so a plain table stays plain and g stays in
+// Montgomery form; a Montgomery reduction of a product g T is the plain value. A table of two entries is folded to its two scalars, which go
+// to the host with the round's sums: ONE SYNCHRONISATION A ROUND (the challenge of round j is hashed from round j's sums). Every round
+// runs on the device.
+// Numbers: the buffers hold loose residues in [0, 2p); what reaches the host - the three sums, the retired scalars (the first of which
+// is Y_t) - is canonical (lz_canon), so the device's bytes are the host's. A thread keeps the three sums as unreduced column
+// accumulators and restarts them every BNFOLD_TRIPS units: lz_reduce takes a value below 2^12 p^2. The largest product of a unit is
+// the c2 term, two lz_sub results in (0, 4p): below 16 p^2 (g T of loose residues is below 4 p^2), so an interval of up to 256 units is
+// inside the bound. 64 is chosen: a quarter of that, the reductions are already 1/64 of the multiply-adds, and a test crosses it twice
+// with one workgroup a table at 2^17 entries. The g builder multiplies two canonical staged factors (below p^2 a product) and
+// restarts every BNFOLD_G_TRIPS = 1024 claims, a quarter of its bound of 4096.
+// Geometry: blockIdx.y = a live table, its units grid-strided over blockIdx.x; at most HG_PCS_FOLD_BLOCKS (2048) workgroups in all.
+constexpr int BNFOLD_TPB = 256;
+constexpr unsigned BNFOLD_MAX_BLOCKS = 2048;
+constexpr int BNFOLD_TRIPS = 64, BNFOLD_G_TRIPS = 1024;
+static_assert(BNFOLD_TRIPS <= 64 && BNFOLD_TRIPS * 16 <= 4096, "lz_reduce takes a value below 2^12 p^2; a unit adds less than 16 p^2 to a sum");
+static_assert(BNFOLD_G_TRIPS <= 4096, "lz_reduce takes a value below 2^12 p^2; a claim adds less than p^2");
+static unsigned bnfold_max_blocks() {   // HG_PCS_FOLD_BLOCKS (tests set it): another bound on the workgroups of a launch
+    const char* e = getenv("HG_PCS_FOLD_BLOCKS");
+    const long v = e && *e ? atol(e) : (long)BNFOLD_MAX_BLOCKS;
+    return (unsigned)std::max(1L, std::min(65535L, v));
+}
+struct BnFoldClaim { u64 lo_at, hi_at; u32 lo_bits, pad; };   // its two factor tables (elements of the staged factors): eq(z, x) = lo[x & (2^lo_bits - 1)] hi[x >> lo_bits]
+struct BnFoldGTables {
+    u32 nt;
+    u32 lg[pcs::MAX_TABLES], claim0[pcs::MAX_TABLES + 1];   // v_t; the claims of table t are claim0[t] .. claim0[t+1] of the staged list
+    u64 at[pcs::MAX_TABLES];                                // s_t
+};
+struct BnFoldTables {
+    u32 nt, pad;
+    u32 lg[pcs::MAX_TABLES], id[pcs::MAX_TABLES];           // log2 of a live table's entries at the input; its number t
+    u64 in[pcs::MAX_TABLES], out[pcs::MAX_TABLES];          // where it lies in the input and where it goes in the output (entries)
+};
+// g_t[x] = sum_{i on t} beta^i eq(z_i, x), every entry written once: a thread owns entry x and walks the table's claims, each a product of
+// two staged factors (Montgomery form, canonical; beta^i lies in the low one). Loose on the way out.
+__global__ __launch_bounds__(BNFOLD_TPB) void k_bnpcsfold_g(const BnFoldGTables A, const char* __restrict__ stage, size_t fac_at, Fr* __restrict__ g) {
+    const unsigned t = blockIdx.y;
+    const size_t len = (size_t)1 << A.lg[t];
+    const BnFoldClaim* cl = reinterpret_cast<const BnFoldClaim*>(stage);
+    const Fr* fac = reinterpret_cast<const Fr*>(stage + fac_at);
+    for (size_t x = (size_t)blockIdx.x * BNFOLD_TPB + threadIdx.x; x < len; x += (size_t)gridDim.x * BNFOLD_TPB) {
+        WCol acc = wcol_zero();
+        Fr sum = fr_zero();
+        int trips = 0;
+        for (unsigned i = A.claim0[t]; i < A.claim0[t + 1]; i++) {
+            const BnFoldClaim d = cl[i];
+            wcol_mac(acc, lz_gload(fac + d.lo_at + (x & (((size_t)1 << d.lo_bits) - 1))), lz_gload(fac + d.hi_at + (x >> d.lo_bits)));
+            if (++trips == BNFOLD_G_TRIPS) { sum = lz_add(sum, lz_reduce(acc)); acc = wcol_zero(); trips = 0; }
+        }
+        lz_gstore(g + A.at[t] + x, lz_add(sum, lz_reduce(acc)));
+    }
+}
+// the three sums of a thread (loose) -> those of its workgroup at out[3 b .. 3 b + 3), b = its number in the grid, canonical if `canon`;
+// every thread calls it
+__device__ __forceinline__ void bnfold_block_sums(const Fr (&s)[3], Fr* __restrict__ out, bool canon) {
+    __shared__ Fr part[3][BNFOLD_TPB];
+#pragma unroll
+    for (int k = 0; k < 3; k++) part[k][threadIdx.x] = s[k];
+    __syncthreads();
+    for (int h = BNFOLD_TPB / 2; h >= 1; h >>= 1) {
+        if (threadIdx.x < h)
+            for (int k = 0; k < 3; k++) part[k][threadIdx.x] = lz_add(part[k][threadIdx.x], part[k][threadIdx.x + h]);
+        __syncthreads();
+    }
+    if (threadIdx.x < 3) {
+        const Fr v = part[threadIdx.x][0];
+        lz_gstore(out + 3 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x) + threadIdx.x, canon ? lz_canon(v) : v);
+    }
+}
+// the accumulators of a unit's three products, restarted every BNFOLD_TRIPS units into the loose sums s
+struct BnFoldAcc {
+    WCol a, b, c;
+    int trips;
+};
+__device__ __forceinline__ void bnfold_acc_unit(BnFoldAcc& w, Fr (&s)[3], const Fr& t0, const Fr& t1, const Fr& g0, const Fr& g1) {
+    wcol_mac(w.a, g0, t0);
+    wcol_mac(w.b, g1, t1);
+    wcol_mac(w.c, lz_sub(g1, g0), lz_sub(t1, t0));
+    if (++w.trips == BNFOLD_TRIPS) {
+        s[0] = lz_add(s[0], lz_reduce(w.a)); s[1] = lz_add(s[1], lz_reduce(w.b)); s[2] = lz_add(s[2], lz_reduce(w.c));
+        w.a = wcol_zero(); w.b = wcol_zero(); w.c = wcol_zero();
+        w.trips = 0;
+    }
+}
+__device__ __forceinline__ void bnfold_acc_finish(BnFoldAcc& w, Fr (&s)[3]) {
+    s[0] = lz_add(s[0], lz_reduce(w.a)); s[1] = lz_add(s[1], lz_reduce(w.b)); s[2] = lz_add(s[2], lz_reduce(w.c));
+}
+// Round 0: nothing to fold. A unit is a pair (T0, T1) of the raw rows, (g0, g1) of g:
+// s(0) += g0 T0, s(1) += g1 T1, c2 += (g1 - g0) (T1 - T0)
+__global__ __launch_bounds__(BNFOLD_TPB) void k_bnpcsfold_round0(const BnFoldTables A, const Fr* __restrict__ rows, const Fr* __restrict__ g, Fr* __restrict__ partial) {
+    const unsigned t = blockIdx.y;
+    const size_t pairs = (size_t)1 << (A.lg[t] - 1);
+    const Fr* T = rows + A.in[t];
+    const Fr* G = g + A.in[t];
+    BnFoldAcc w{wcol_zero(), wcol_zero(), wcol_zero(), 0};
+    Fr s[3] = {fr_zero(), fr_zero(), fr_zero()};
+    for (size_t u = (size_t)blockIdx.x * BNFOLD_TPB + threadIdx.x; u < pairs; u += (size_t)gridDim.x * BNFOLD_TPB)
+        bnfold_acc_unit(w, s, lz_gload(T + 2 * u), lz_gload(T + 2 * u + 1), lz_gload(G + 2 * u), lz_gload(G + 2 * u + 1));
+    bnfold_acc_finish(w, s);
+    bnfold_block_sums(s, partial, false);
+}
+// Round j >= 1. A unit is four adjacent entries of T and of g: folded by r_{j-1} (fk = its fold_consts) into two of each, which are
+// stored and enter the sums of round j while they are in registers. Round 1 reads T from the raw rows, later rounds from the other buffer
+// pair. A table of two entries is folded into its two scalars at scal[2 id], scal[2 id + 1] (canonical) by one thread and enters no sum.
+__global__ __launch_bounds__(BNFOLD_TPB) void k_bnpcsfold_round(const BnFoldTables A, const Fr* __restrict__ tin, const Fr* __restrict__ gin, Fr* __restrict__ tout,
+                                                                Fr* __restrict__ gout, const FoldK fk, Fr* __restrict__ scal, Fr* __restrict__ partial) {
+    const unsigned t = blockIdx.y, lg = A.lg[t];
+    const Fr* T = tin + A.in[t];
+    const Fr* G = gin + A.in[t];
+    // X[2i] + r (X[2i+1] - X[2i])
+    auto fold = [&](const Fr* X, size_t i) {
+        const Fr x0 = lz_gload(X + 2 * i);
+        return lz_fold(x0, lz_sub(lz_gload(X + 2 * i + 1), x0), fk.k);
+    };
+    BnFoldAcc w{wcol_zero(), wcol_zero(), wcol_zero(), 0};
+    Fr s[3] = {fr_zero(), fr_zero(), fr_zero()};
+    if (lg == 1) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            lz_gstore(scal + 2 * A.id[t], lz_canon(fold(T, 0)));
+            lz_gstore(scal + 2 * A.id[t] + 1, lz_canon(fold(G, 0)));
+        }
+    } else {
+        const size_t units = (size_t)1 << (lg - 2);
+        Fr* To = tout + A.out[t];
+        Fr* Go = gout + A.out[t];
+        for (size_t u = (size_t)blockIdx.x * BNFOLD_TPB + threadIdx.x; u < units; u += (size_t)gridDim.x * BNFOLD_TPB) {
+            const Fr t0 = fold(T, 2 * u), t1 = fold(T, 2 * u + 1), g0 = fold(G, 2 * u), g1 = fold(G, 2 * u + 1);
+            lz_gstore(To + 2 * u, t0);
+            lz_gstore(To + 2 * u + 1, t1);
+            lz_gstore(Go + 2 * u, g0);
+            lz_gstore(Go + 2 * u + 1, g1);
+            bnfold_acc_unit(w, s, t0, t1, g0, g1);
+        }
+    }
+    bnfold_acc_finish(w, s);
+    bnfold_block_sums(s, partial, false);
+}
+// one workgroup: out[k] = sum_b partial[3 b + k], canonical
+__global__ __launch_bounds__(BNFOLD_TPB) void k_bnpcsfold_sum(const Fr* __restrict__ partial, size_t blocks, Fr* __restrict__ out) {
+    Fr s[3] = {fr_zero(), fr_zero(), fr_zero()};
+    for (size_t b = threadIdx.x; b < blocks; b += BNFOLD_TPB)
+        for (int k = 0; k < 3; k++) s[k] = lz_add(s[k], lz_gload(partial + 3 * b + k));
+    bnfold_block_sums(s, out, true);
+}
+
+// The device form of PcsFoldSource. Scratch from the context's arena (reset here; the handle's matrices are its own): g (32 bytes a table
+// entry), the two buffer pairs (a half and a quarter of that for T and for g each), the partials, the sums and the scalars.
+struct BnFoldDev : PcsFoldSource {
+    const pcs::Commitment& cm;
+    hg_ctx* ctx;
+    hipStream_t st;
+    int cls;
+    size_t n_claims;
+    unsigned max_blocks;
+    std::string me;
+    Fr *d_g, *d_t[2], *d_gg[2], *d_scal, *d_partial, *d_sums;
+    std::vector<Fr> h_scal;
+    Fr h_sums[3];
+
+    BnFoldDev(const char* who, const pcs::Commitment& cm_, const std::vector<PcsClaim>& claims, const std::vector<Fr>& bpow)
+        : cm(cm_), ctx(cm_.ctx), n_claims(claims.size()), me(who) {
+        const pcs::Shape& sh = cm.sh;
+        const size_t m = sh.nvars.size(), W = sh.R << sh.c;
+        const Fr* d_rows = reinterpret_cast<const Fr*>(cm.d_rows);
+        hipc(hipSetDevice(ctx->device), "hipSetDevice");
+        ctx->arena_reset();
+        st = ctx->stream;
+        cls = ctx->prof_class("pcs_fold_bn254", false);
+        ctx->prof_stream = st;
+        max_blocks = bnfold_max_blocks();
+        T.assign(m, fr_zero());
+        G.assign(m, fr_zero());
+        h_scal.assign(2 * m, fr_zero());
+        // the claims in table order; per claim the two factor tables, beta^i in the low one
+        BnFoldGTables A;
+        memset(&A, 0, sizeof(A));
+        std::vector<BnFoldClaim> list;
+        std::vector<Fr> fac;
+        size_t max_len = 0;
+        for (size_t t = 0; t < m; t++) {
+            const size_t v = (size_t)sh.nvars[t], lo_bits = (v + 1) / 2;
+            if (v == 0) {   // a table of one element is a scalar from the start: T_t() is the element, g_t() = sum beta^i
+                hipc(hipMemcpyAsync(&T[t], d_rows + (sh.off[t] << sh.c), sizeof(Fr), hipMemcpyDeviceToHost, st), "download a one-element table");
+                hipc(hipStreamSynchronize(st), (me + ": sync").c_str());
+                for (size_t i = 0; i < claims.size(); i++)
+                    if (claims[i].table == t) G[t] = fr_add(G[t], bpow[i]);
+                continue;
+            }
+            for (size_t i = 0; i < claims.size(); i++) {
+                if (claims[i].table != t) continue;
+                std::vector<Fr> lo = pcs_eq_table(claims[i].point.data(), lo_bits);
+                const std::vector<Fr> hi = pcs_eq_table(claims[i].point.data() + lo_bits, v - lo_bits);
+                for (Fr& x : lo) x = fr_mul(x, bpow[i]);
+                list.push_back(BnFoldClaim{(u64)fac.size(), (u64)(fac.size() + lo.size()), (u32)lo_bits, 0});
+                fac.insert(fac.end(), lo.begin(), lo.end());
+                fac.insert(fac.end(), hi.begin(), hi.end());
+            }
+            A.lg[A.nt] = (u32)v;
+            A.at[A.nt] = (u64)(sh.off[t] << sh.c);
+            A.nt++;   // (the kernel's table number, which skips the one-element tables; claim0[0] = 0)
+            A.claim0[A.nt] = (u32)list.size();
+            max_len = std::max(max_len, (size_t)1 << v);
+        }
+        const size_t fac_at = (list.size() * sizeof(BnFoldClaim) + 31) & ~(size_t)31;
+        std::vector<char> stage(fac_at + fac.size() * sizeof(Fr) + 32);
+        if (!list.empty()) memcpy(stage.data(), list.data(), list.size() * sizeof(BnFoldClaim));
+        if (!fac.empty()) memcpy(stage.data() + fac_at, fac.data(), fac.size() * sizeof(Fr));
+        char* d_stage;
+        try {
+            d_g = ctx->alloc_n<Fr>(W);
+            d_t[0] = ctx->alloc_n<Fr>(W / 2 + 1);
+            d_gg[0] = ctx->alloc_n<Fr>(W / 2 + 1);
+            d_t[1] = ctx->alloc_n<Fr>(W / 4 + 1);
+            d_gg[1] = ctx->alloc_n<Fr>(W / 4 + 1);
+            d_scal = ctx->alloc_n<Fr>(2 * m);
+            d_partial = ctx->alloc_n<Fr>(3 * ((size_t)max_blocks + pcs::MAX_TABLES));
+            d_sums = ctx->alloc_n<Fr>(3);
+            d_stage = ctx->alloc_n<char>(stage.size());
+        } catch (const std::exception& e) {
+            throw Error(std::string("the context's arena cannot hold the reduction (") + e.what() + ")");
+        }
+        if (!A.nt) return;
+        hipc(hipMemcpyAsync(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, st), "upload factor tables");
+        ctx->prof_begin(cls, (double)W * 32 + (double)fac.size() * 32);
+        k_bnpcsfold_g<<<dim3(blocks_of(max_len, A.nt), A.nt), BNFOLD_TPB, 0, st>>>(A, d_stage, fac_at, d_g);
+        ctx->prof_end();
+        hipc(hipStreamSynchronize(st), (me + ": sync").c_str());   // (the staged copy is a local)
+        hipc(hipGetLastError(), (me + ": launch").c_str());
+    }
+    // the workgroups a table of a launch over nt tables whose largest has `units` units
+    unsigned blocks_of(size_t units, unsigned nt) const {
+        const size_t cap = std::max<size_t>(1, max_blocks / nt);
+        return (unsigned)std::max<size_t>(1, std::min(cap, (units + BNFOLD_TPB - 1) / BNFOLD_TPB));
+    }
+    void step(size_t j, const Fr& r, Fr s[3]) override {
+        const pcs::Shape& sh = cm.sh;
+        const size_t m = sh.nvars.size(), V = pcs::fold_rounds(sh);
+        BnFoldTables A;
+        memset(&A, 0, sizeof(A));
+        bool retire = false;
+        size_t max_units = 1, entries = 0;
+        for (size_t t = 0; t < m; t++) {
+            const size_t v = (size_t)sh.nvars[t], at = sh.off[t] << sh.c;
+            if (v == 0 || v < j) continue;   // a scalar already
+            const size_t lg = j == 0 ? v : v - (j - 1);
+            A.lg[A.nt] = (u32)lg;
+            A.id[A.nt] = (u32)t;
+            A.in[A.nt] = j == 0 ? at : at >> (j - 1);
+            A.out[A.nt] = at >> j;
+            A.nt++;
+            retire |= j > 0 && lg == 1;
+            max_units = std::max(max_units, j == 0 ? (size_t)1 << (lg - 1) : lg == 1 ? 1 : (size_t)1 << (lg - 2));
+            entries += (size_t)1 << lg;
+        }
+        if (s) s[0] = s[1] = s[2] = fr_zero();
+        if (!A.nt) return;
+        const dim3 grid(blocks_of(max_units, A.nt), A.nt);
+        ctx->prof_stream = st;
+        // round 0 reads 32 + 32 bytes an entry, a later round reads them and writes 32 + 32 for every two
+        ctx->prof_begin(cls, (double)entries * (j == 0 ? 64 : 96));
+        if (j == 0) {
+            k_bnpcsfold_round0<<<grid, BNFOLD_TPB, 0, st>>>(A, reinterpret_cast<const Fr*>(cm.d_rows), d_g, d_partial);
+        } else {
+            FoldK fk;
+            fold_consts(fr_to_mont(r), &fk);
+            const Fr* tin = j == 1 ? reinterpret_cast<const Fr*>(cm.d_rows) : d_t[j & 1];
+            const Fr* gin = j == 1 ? d_g : d_gg[j & 1];
+            k_bnpcsfold_round<<<grid, BNFOLD_TPB, 0, st>>>(A, tin, gin, d_t[(j - 1) & 1], d_gg[(j - 1) & 1], fk, d_scal, d_partial);
+        }
+        if (s) k_bnpcsfold_sum<<<1, BNFOLD_TPB, 0, st>>>(d_partial, (size_t)grid.x * grid.y, d_sums);
+        ctx->prof_end();
+        if (s) hipc(hipMemcpyAsync(h_sums, d_sums, sizeof(h_sums), hipMemcpyDeviceToHost, st), "download the round's sums");
+        if (retire) hipc(hipMemcpyAsync(h_scal.data(), d_scal, 2 * m * sizeof(Fr), hipMemcpyDeviceToHost, st), "download the retired tables' scalars");
+        hipc(hipStreamSynchronize(st), (me + ": sync").c_str());
+        hipc(hipGetLastError(), (me + ": launch").c_str());
+        ctx->prof_collect();
+        if (s) memcpy(s, h_sums, sizeof(h_sums));
+        for (size_t t = 0; t < m; t++)
+            if (j > 0 && (size_t)sh.nvars[t] == j) { T[t] = h_scal[2 * t]; G[t] = h_scal[2 * t + 1]; }
+        if (j == V && hg_debug("plan"))   // (read at every call: the tests switch it per case)
+            fprintf(stderr, "[hg plan] bnpcsfold V=%zu dev_rounds=%zu host_rounds=0 tables=%zu claims=%zu\n", V, V, m, n_claims);
+    }
+};
+std::unique_ptr<PcsFoldSource> pcs_fold_source_device(const char* who, const pcs::Commitment& cm, const std::vector<PcsClaim>& claims, const std::vector<Fr>& bpow) {
+    return std::unique_ptr<PcsFoldSource>(new BnFoldDev(who, cm, claims, bpow));
 }
 

@@ -164,6 +164,11 @@ struct GlAbi {
     static std::vector<std::string> pcs_verify_batch(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const std::vector<PcsItem>& items, size_t Q) {
         return pcs::verify_device_batch(who, ctx, sh, items, Q);
     }
+    // folded openings; ctx: the device form of the verifier
+    static std::vector<uint8_t> pcs_open_folded(const char* who, const pcs::Commitment& cm, const std::vector<PcsClaim>& cl, size_t Q) { return pcs::open_folded(who, cm, cl, Q); }
+    static std::string pcs_verify_folded(hg_ctx* ctx, const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& cl, size_t Q, const uint8_t* proof, size_t len) {
+        return ctx ? pcs::verify_folded_device(ctx, sh, root, cl, Q, proof, len) : pcs::verify_folded(sh, root, cl, Q, proof, len);
+    }
     // the batch forms of commit and open (device only): tabs[i * m + t] = table t of member i
     typedef pcs::OpenItem PcsOpenItem;
     static size_t opening_bytes(const pcs::Shape& sh, size_t n_claims, size_t Q) { return pcs::opening_bytes(sh, n_claims, Q); }
@@ -231,6 +236,11 @@ struct BnAbi {
     }
     static std::vector<std::string> pcs_verify_batch(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const std::vector<PcsItem>& items, size_t Q) {
         return bn::pcs_verify_device_batch(who, ctx, sh, items, Q);
+    }
+    // folded openings; ctx: the device form of the verifier
+    static std::vector<uint8_t> pcs_open_folded(const char* who, const pcs::Commitment& cm, const std::vector<PcsClaim>& cl, size_t Q) { return bn::pcs_open_folded(who, cm, cl, Q); }
+    static std::string pcs_verify_folded(hg_ctx* ctx, const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& cl, size_t Q, const uint8_t* proof, size_t len) {
+        return ctx ? bn::pcs_verify_folded_device(ctx, sh, root, cl, Q, proof, len) : bn::pcs_verify_folded(sh, root, cl, Q, proof, len);
     }
     // the batch forms of commit and open (device only): `secrets` says that the tables are witness words, lifted by the signed rule
     typedef bn::PcsOpenItem PcsOpenItem;
@@ -666,36 +676,39 @@ static int secrets_commit_values_entry(const char* who, hg_ctx* ctx, const hg_pk
     return 0;
 }
 
-// ---- folded openings (pcs.hpp; Goldilocks only). hg_pcs_open_folded after its null checks, and the tail of hg_claims_open_folded
+// ---- folded openings (pcs.hpp, pcs_bn254.hpp). hg_pcs_open_folded* after its null checks, and the tail of hg_claims_open_folded*
+template <class A>
 static int pcs_open_folded_entry(const char* who, hg_ctx* ctx, const pcs::Commitment* cm, const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n_claims,
                                  size_t n_queries, uint8_t* proof, size_t cap, size_t* len) {
     const std::string w(who);
-    if (cm->field != pcs::GOLDILOCKS) throw Error(w + ": the commitment is over BN254: folded openings are Goldilocks only");
+    if (cm->field != A::FIELD) throw Error(w + ": " + A::other_field(who));
     if (cm->ctx != ctx) throw Error(w + ": the commitment was made " + (cm->ctx ? "on a device context: pass that context" : "by the host form: pass no context"));
     if (!n_claims) throw Error(w + ": a folded opening needs a claim");
-    const std::vector<pcs::Claim> cl = pcs_claims<GlAbi>(who, cm->sh, table, points, values, n_claims);
-    pcs_emit(who, pcs::open_folded(who, *cm, cl, pcs_queries(who, n_queries)), proof, cap, len);
+    const std::vector<typename A::PcsClaim> cl = pcs_claims<A>(who, cm->sh, table, points, values, n_claims);
+    pcs_emit(who, A::pcs_open_folded(who, *cm, cl, pcs_queries(who, n_queries)), proof, cap, len);
     return 0;
 }
+template <class A>
 static int pcs_open_folded_api(const char* who, hg_ctx* ctx, const void* commitment, const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n_claims,
                                size_t n_queries, uint8_t* proof, size_t cap, size_t* len) {
     if (len) *len = 0;
     if (!commitment || !proof || !len || (n_claims && (!table || !points || !values))) throw Error(std::string(who) + ": null argument");
-    return pcs_open_folded_entry(who, ctx, static_cast<const pcs::Commitment*>(commitment), table, points, values, n_claims, n_queries, proof, cap, len);
+    return pcs_open_folded_entry<A>(who, ctx, static_cast<const pcs::Commitment*>(commitment), table, points, values, n_claims, n_queries, proof, cap, len);
 }
-// hg_pcs_verify_folded (device == false) and hg_pcs_verify_folded_device: pcs_verify_entry's checks in its order, then the form's verifier
+// hg_pcs_verify_folded* (device == false) and hg_pcs_verify_folded_device*: pcs_verify_entry's checks in its order, then the form's verifier
+template <class A>
 static int pcs_verify_folded_entry(const char* who, bool device, hg_ctx* ctx, const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row,
                                    const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
     const std::string w(who);
     if (!root || !nvars || (len && !proof) || (n_claims && (!table || !points || !values))) throw Error(w + ": null argument");
     const pcs::Shape sh = pcs::make_shape(who, nvars, n_tables, log2_row);
     if (!n_claims) throw Error(w + ": a folded opening needs a claim");
-    const std::vector<pcs::Claim> cl = pcs_claims<GlAbi>(who, sh, table, points, values, n_claims);
+    const std::vector<typename A::PcsClaim> cl = pcs_claims<A>(who, sh, table, points, values, n_claims);
     const size_t Q = pcs_queries(who, n_queries);
-    if (!device) return decision(pcs::verify_folded(sh, root, cl, Q, proof, len));
+    if (!device) return decision(A::pcs_verify_folded(nullptr, sh, root, cl, Q, proof, len));
     if (!ctx) throw Error(w + ": no context");
     try {
-        return decision(pcs::verify_folded_device(ctx, sh, root, cl, Q, proof, len));
+        return decision(A::pcs_verify_folded(ctx, sh, root, cl, Q, proof, len));
     } catch (const std::exception& e) {
         throw Error(w + ": " + e.what());
     }
@@ -716,7 +729,7 @@ static int claims_open_entry(const char* who, const char* mine, hg_ctx* ctx, con
     std::vector<uint32_t> table;
     std::vector<uint64_t> pts, vals;
     secrets_claims<A>(who, p, claims, n, points, table, pts, vals);
-    if (folded) return pcs_open_folded_entry(who, ctx, cm, table.data(), pts.data(), vals.data(), n, n_queries, opening, cap, len);
+    if (folded) return pcs_open_folded_entry<A>(who, ctx, cm, table.data(), pts.data(), vals.data(), n, n_queries, opening, cap, len);
     return pcs_open_entry<A>(who, ctx, cm, table.data(), pts.data(), vals.data(), n, n_queries, opening, cap, len);
 }
 
@@ -731,7 +744,7 @@ static int claims_verify_entry(const char* who, bool device, hg_ctx* ctx, const 
     std::vector<uint64_t> pts, vals;
     (void)pcs::make_shape(who, nv.data(), nv.size(), log2_row);   // a shape error is reported ahead of a claim's
     secrets_claims<A>(who, p, claims, n, points, table, pts, vals);
-    if (folded) return pcs_verify_folded_entry(who, device, ctx, root, nv.data(), nv.size(), log2_row, table.data(), pts.data(), vals.data(), n, n_queries, opening, len);
+    if (folded) return pcs_verify_folded_entry<A>(who, device, ctx, root, nv.data(), nv.size(), log2_row, table.data(), pts.data(), vals.data(), n, n_queries, opening, len);
     return pcs_verify_entry<A>(who, device, ctx, root, nv.data(), nv.size(), log2_row, table.data(), pts.data(), vals.data(), n, n_queries, opening, len);
 }
 
@@ -2469,15 +2482,15 @@ int hg_claims_verify_device(hg_ctx* ctx, const hg_params* params, const uint8_t 
 
 int hg_pcs_open_folded(hg_ctx* ctx, const void* commitment, const uint32_t* table, const uint64_t* points, const uint64_t* values, size_t n_claims, size_t n_queries,
                        uint8_t* proof, size_t cap, size_t* len) {
-    HG_ENTRY(pcs_open_folded_api("hg_pcs_open_folded", ctx, commitment, table, points, values, n_claims, n_queries, proof, cap, len))
+    HG_ENTRY(pcs_open_folded_api<GlAbi>("hg_pcs_open_folded", ctx, commitment, table, points, values, n_claims, n_queries, proof, cap, len))
 }
 int hg_pcs_verify_folded(const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table, const uint64_t* points,
                          const uint64_t* values, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
-    HG_ENTRY(pcs_verify_folded_entry("hg_pcs_verify_folded", false, nullptr, root, nvars, n_tables, log2_row, table, points, values, n_claims, n_queries, proof, len))
+    HG_ENTRY(pcs_verify_folded_entry<GlAbi>("hg_pcs_verify_folded", false, nullptr, root, nvars, n_tables, log2_row, table, points, values, n_claims, n_queries, proof, len))
 }
 int hg_pcs_verify_folded_device(hg_ctx* ctx, const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table, const uint64_t* points,
                                 const uint64_t* values, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
-    HG_ENTRY(pcs_verify_folded_entry("hg_pcs_verify_folded_device", true, ctx, root, nvars, n_tables, log2_row, table, points, values, n_claims, n_queries, proof, len))
+    HG_ENTRY(pcs_verify_folded_entry<GlAbi>("hg_pcs_verify_folded_device", true, ctx, root, nvars, n_tables, log2_row, table, points, values, n_claims, n_queries, proof, len))
 }
 int hg_claims_open_folded(hg_ctx* ctx, const hg_params* params, const void* commitment, const void* claims, size_t n, const uint64_t* points, size_t n_queries,
                           uint8_t* opening, size_t cap, size_t* len) {
@@ -2576,6 +2589,31 @@ int hg_claims_verify_bn254(const hg_params* params, const uint8_t root[32], size
 int hg_claims_verify_device_bn254(hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points4,
                                   size_t n_queries, const uint8_t* opening, size_t len) {
     HG_ENTRY(claims_verify_entry<BnAbi>("hg_claims_verify_device_bn254", true, ctx, params, root, log2_row, claims, n, points4, n_queries, opening, len))
+}
+
+int hg_pcs_open_folded_bn254(hg_ctx* ctx, const void* commitment, const uint32_t* table, const uint64_t* points4, const uint64_t* values4, size_t n_claims, size_t n_queries,
+                             uint8_t* proof, size_t cap, size_t* len) {
+    HG_ENTRY(pcs_open_folded_api<BnAbi>("hg_pcs_open_folded_bn254", ctx, commitment, table, points4, values4, n_claims, n_queries, proof, cap, len))
+}
+int hg_pcs_verify_folded_bn254(const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table, const uint64_t* points4,
+                               const uint64_t* values4, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
+    HG_ENTRY(pcs_verify_folded_entry<BnAbi>("hg_pcs_verify_folded_bn254", false, nullptr, root, nvars, n_tables, log2_row, table, points4, values4, n_claims, n_queries, proof, len))
+}
+int hg_pcs_verify_folded_device_bn254(hg_ctx* ctx, const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table, const uint64_t* points4,
+                                      const uint64_t* values4, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len) {
+    HG_ENTRY(pcs_verify_folded_entry<BnAbi>("hg_pcs_verify_folded_device_bn254", true, ctx, root, nvars, n_tables, log2_row, table, points4, values4, n_claims, n_queries, proof, len))
+}
+int hg_claims_open_folded_bn254(hg_ctx* ctx, const hg_params* params, const void* commitment, const void* claims, size_t n, const uint64_t* points4, size_t n_queries,
+                                uint8_t* opening, size_t cap, size_t* len) {
+    HG_ENTRY(claims_open_entry<BnAbi>("hg_claims_open_folded_bn254", "hg_secrets_commit_bn254", ctx, params, commitment, claims, n, points4, n_queries, opening, cap, len, true))
+}
+int hg_claims_verify_folded_bn254(const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points4,
+                                  size_t n_queries, const uint8_t* opening, size_t len) {
+    HG_ENTRY(claims_verify_entry<BnAbi>("hg_claims_verify_folded_bn254", false, nullptr, params, root, log2_row, claims, n, points4, n_queries, opening, len, true))
+}
+int hg_claims_verify_folded_device_bn254(hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points4,
+                                         size_t n_queries, const uint8_t* opening, size_t len) {
+    HG_ENTRY(claims_verify_entry<BnAbi>("hg_claims_verify_folded_device_bn254", true, ctx, params, root, log2_row, claims, n, points4, n_queries, opening, len, true))
 }
 
 int hg_pcs_verify_device_batch_bn254(hg_ctx* ctx, const uint8_t* const* roots, const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* const* tables,

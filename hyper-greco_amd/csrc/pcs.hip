@@ -13,7 +13,7 @@
 // The statement digest of a bound proof (hg.h: "Bound proofs") lives here as well: its leaves are hashed by a kernel of the same
 // thread-a-sponge form as the column hashes, its levels are the commitment's.
 // The prover's side of a folded opening (pcs.hpp FoldSource) is here too: the kernel that builds g, the round kernels of the reduction
-// sum-check and their host driver FoldDev, and the device verifier of a folded opening, which reuses the verifier's kernels.
+// sum-check and their host driver FoldDev; the device verifier of a folded opening is verify_folded_flow of pcs_flow.hpp.
 #include <omp.h>
 #include "pcs.hpp"
 #include "prover.hpp"
@@ -1001,6 +1001,13 @@ struct GlPcs {
                                 *CLS_COMBINE = nullptr;
     static constexpr const char *VERIFY_NAME = "hg_pcs_verify_device", *OPEN_NAME = "hg_pcs_open", *TIMES_TAG = "", *NOT_BELOW = "a table holds a word that is not below p";
     static size_t opening_bytes(const Shape& sh, size_t n, size_t Q) { return pcs::opening_bytes(sh, n, Q); }
+    // the folded opening (verify_folded_flow)
+    static constexpr const char* VERIFY_FOLDED_NAME = "hg_pcs_verify_folded_device";
+    static size_t folded_header_bytes(const Shape& sh) { return pcs::folded_header_bytes(sh); }
+    static size_t folded_opening_bytes(const Shape& sh, size_t Q) { return pcs::folded_opening_bytes(sh, Q); }
+    static FoldedHeader folded_header(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof) {
+        return pcs::folded_header(sh, root, claims, Q, proof);
+    }
     // the transcript
     static FsTranscript start_transcript(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q) { return pcs::start_transcript(sh, root, claims, Q); }
     static std::vector<E2> rho_powers(FsTranscript& tr, size_t R) { return pcs::rho_powers(tr.squeeze(), R); }
@@ -1103,63 +1110,9 @@ void columns_device(const Commitment& cm, const std::vector<size_t>& js, u64* co
 std::string verify_device(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof, size_t len) {
     return verify_flow<GlPcs>(ctx, sh, root, claims, Q, proof, len);
 }
-// The device verifier of a folded opening. The header is host scalar work (folded_header); its body is an opening of one claim -
-// all R rows under the combined weights, at rho[..c), with the value sum_t delta^t Y_t - and goes through verify_flow's kernels as a
-// group of one member whose opening starts behind the header. The kernels run whatever the header's checks gave: a word of the body
-// that is not below p is reported ahead of a failing round, as the host verifier does.
+// the device verifier of a folded opening: verify_folded_flow of pcs_flow.hpp
 std::string verify_folded_device(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof, size_t len) {
-    typedef GlPcs F;
-    const size_t C = sh.C(), N = sh.N(), R = sh.R, hb = folded_header_bytes(sh);
-    const std::string who("hg_pcs_verify_folded_device");
-    const std::string bad_len = length_reason(len, folded_opening_bytes(sh, Q));
-    if (!bad_len.empty()) return bad_len;
-    FoldedHeader H = folded_header(sh, root, claims, Q, proof);
-    if (H.noncanonical != ~(size_t)0) return reason_noncanonical(H.noncanonical);
-    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
-    ctx->arena_reset();
-    hipStream_t st = ctx->stream;
-    const size_t nw = 2 * R, u_units = F::U_ROWS * C * 2;
-    const VerifyTotals t{1, u_units, u_units + Q * R, F::U_ROWS * 2, 1, 2, nw};
-    VbMember desc{};
-    desc.n = 1;
-    desc.proof = hb / 8;
-    std::vector<char> stage(member_block_layout<F>(desc, sh, 1, nw, sizeof(VbMember)));
-    memcpy(stage.data(), &desc, sizeof(VbMember));
-    memcpy(stage.data() + desc.root_at, root, 32);
-    CombineDesc* hd = reinterpret_cast<CombineDesc*>(stage.data() + desc.jobs_at);
-    hd[0].row0 = 0; hd[0].nrows = R; hd[0].woff = 0;
-    hd[1].row0 = 0; hd[1].nrows = R; hd[1].woff = R;
-    memcpy(stage.data() + desc.y_at, &H.y, sizeof(E2));
-    if (sh.c) memcpy(stage.data() + desc.z_at, H.lo.data(), (size_t)sh.c * sizeof(E2));
-    memcpy(stage.data() + desc.w_at, H.rho_pw.data(), R * sizeof(E2));
-    memcpy(stage.data() + desc.w_at + R * sizeof(E2), H.w.data(), R * sizeof(E2));
-    u64* d_proof;
-    VerifyDev<F> d;
-    try {
-        d_proof = ctx->alloc_n<u64>(len / 8);
-        d = verify_alloc<F>(ctx, sh, Q, stage.size(), t, 4);
-    } catch (const std::exception& e) {
-        throw Error(std::string("the context's arena cannot hold the opening (") + e.what() + ")");
-    }
-    Drain drain{st};   // (drains on an error; after the synchronisation below its own is one more, on an idle stream)
-    const int cls = ctx->prof_class(F::CLS_VERIFY, false);
-    ctx->prof_stream = st;
-    const VbGroup vg{1, (u64)Q, (u64)R, (u64)query_stride<F>(sh), sh.c, sh.depth()};
-    hip_check(hipMemcpyAsync(d_proof, proof, len, hipMemcpyHostToDevice, st), "upload opening");
-    hip_check(hipMemcpyAsync(d.stage, stage.data(), stage.size(), hipMemcpyHostToDevice, st), "upload claims");
-    verify_enqueue<F>(ctx, cls, st, 4096, d_proof, d, vg, t, 4);
-    F::absorb_opening(H.tr, proof + hb, 2 * C);
-    const std::vector<size_t> js = F::squeeze_indices(H.tr, N, Q);
-    const std::vector<u64> hj(js.begin(), js.end());
-    verify_enqueue_query<F>(ctx, cls, st, d_proof, d, vg, t, hj.data());
-    u64 cells[4];
-    hip_check(hipMemcpyAsync(cells, d.cells, 32, hipMemcpyDeviceToHost, st), "download verdict");
-    hip_check(hipStreamSynchronize(st), (who + ": sync").c_str());
-    hip_check(hipGetLastError(), (who + ": launch").c_str());
-    ctx->prof_collect();
-    if (cells[0] != PCSV_NONE) return reason_noncanonical(hb + (size_t)cells[0]);
-    if (!H.reason.empty()) return H.reason;
-    return cells_reason(cells, 1);
+    return verify_folded_flow<GlPcs>(ctx, sh, root, claims, Q, proof, len);
 }
 std::vector<std::string> verify_device_batch(const char* who, hg_ctx* ctx, const Shape& sh, const std::vector<VerifyItem>& items, size_t Q) {
     return verify_batch_flow<GlPcs>(who, ctx, sh, items, Q);

@@ -148,7 +148,7 @@ std::vector<std::string> verify_device_batch(const char* who, hg_ctx* ctx, const
 
 // ---- folded openings (hg.h "Folded openings"): a sum-check over the committed tables reduces the n claims to one value Y_t a table at
 // the prefixes of one point, which one combined row opens. The opening is a header - 3 coefficients a round, V = max_t v_t rounds,
-// then the m values Y_t - followed by the body of an opening of one claim. Goldilocks only.
+// then the m values Y_t - followed by the body of an opening of one claim. The forms over bn256::Fr: pcs_bn254.hpp.
 inline size_t fold_rounds(const Shape& sh) { int V = 0; for (int v : sh.nvars) V = v > V ? v : V; return (size_t)V; }
 inline size_t folded_header_bytes(const Shape& sh) { return 16 * (3 * fold_rounds(sh) + sh.nvars.size()); }
 inline size_t folded_opening_bytes(const Shape& sh, size_t Q) { return folded_header_bytes(sh) + opening_bytes(sh, 1, Q); }
@@ -169,7 +169,8 @@ std::unique_ptr<FoldSource> fold_source_device(const Commitment& cm, const std::
 std::vector<uint8_t> open_folded(const char* who, const Commitment& cm, const std::vector<Claim>& claims, size_t Q);
 // hg_pcs_verify_folded: "" = accepted, else the reason
 std::string verify_folded(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof, size_t len);
-// hg_pcs_verify_folded_device (pcs.hip): the same decision and reason; the header on the host, the body through verify_device's kernels
+// hg_pcs_verify_folded_device (pcs.hip, verify_folded_flow of pcs_flow.hpp): the same decision and reason; the header on the host, the body through
+// verify_device's kernels
 std::string verify_folded_device(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof, size_t len);
 // What the two folded verifiers share: everything the header decides. The header's words are read (`noncanonical`: the lowest byte
 // offset of one that is not below p, else ~0; the walk then stops), the rounds and the final evaluation checked (`reason`: the first

@@ -1,5 +1,6 @@
 // Host side of the polynomial commitment over bn256::Fr (pcs_bn254.hpp): the host form of commit, the opening's transcript and byte
-// layout (shared by both forms) and the verifier. Elements at rest are canonical plain words; weights and twiddles are in Montgomery
+// layout (shared by both forms) and the verifier; the folded opening's host flow (both forms), its host reduction, its host verifier
+// and the header walk both folded verifiers share. Elements at rest are canonical plain words; weights and twiddles are in Montgomery
 // form, so fr_mul(weight, element) is the plain product.
 #include "pcs_bn254.hpp"
 #include <algorithm>
@@ -174,11 +175,10 @@ Fr pcs_squeeze(FsTranscript& tr) {   // LE(hash) mod r, the state re-hashed: hg_
     while (fr_geq_p(v)) v = fr_sub_p(v);   // 2^256 / r < 6
     return v;
 }
-FsTranscript pcs_start_transcript(const Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q) {
+FsTranscript pcs_start_transcript(const Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const char* tag) {
     FsTranscript tr;
     tr.absorb = true;
-    static const char tag[] = "hg-pcs-bn254-1";
-    tr.pending.assign(tag, tag + sizeof(tag) - 1);
+    tr.pending.assign(tag, tag + strlen(tag));
     tr.pending.insert(tr.pending.end(), root, root + 32);
     put_le32(tr.pending, (uint32_t)sh.c);
     put_le32(tr.pending, (uint32_t)sh.nvars.size());
@@ -211,9 +211,31 @@ Fr pcs_read_be32(const uint8_t* p) {
     return v;
 }
 
+// the end of an opening, folded or not: the u vectors written and absorbed, the Q column indices squeezed, then per query the R column
+// elements and the siblings of the path. `total`: the bytes of the finished opening
+static void write_u_and_queries(FsTranscript& tr, const Commitment& cm, const std::vector<Fr>& u, size_t Q, size_t total) {
+    const Shape& sh = cm.sh;
+    const size_t N = sh.N(), R = sh.R;
+    std::vector<uint8_t>& out = tr.bytes;
+    out.reserve(total);
+    for (const Fr& x : u) write_be32(out, x);
+    pcs_absorb(tr, u.data(), u.size());
+    const std::vector<size_t> js = pcs_squeeze_indices(tr, N, Q);
+    std::vector<Fr> cols(Q * R);
+    if (Q) { if (cm.ctx) pcs_columns_device(cm, js, cols.data()); else pcs_columns_host(cm, js, cols.data()); }
+    for (size_t q = 0; q < Q; q++) {
+        for (size_t r = 0; r < R; r++) write_be32(out, cols[q * R + r]);
+        size_t idx = js[q];
+        for (int l = 0; l < sh.depth(); l++, idx >>= 1) {
+            const uint8_t* sib = cm.node(l, idx ^ 1);
+            out.insert(out.end(), sib, sib + 32);
+        }
+    }
+}
+
 std::vector<uint8_t> pcs_open(const char* who, const Commitment& cm, const std::vector<PcsClaim>& claims, size_t Q) {
     const Shape& sh = cm.sh;
-    const size_t C = sh.C(), N = sh.N(), R = sh.R, n = claims.size();
+    const size_t C = sh.C(), R = sh.R, n = claims.size();
     FsTranscript tr = pcs_start_transcript(sh, cm.root(), claims, Q);
     std::vector<PcsJob> jobs(n + 1);
     jobs[0].row0 = 0; jobs[0].nrows = R; jobs[0].w = pcs_rho_powers(pcs_squeeze(tr), R);
@@ -230,58 +252,47 @@ std::vector<uint8_t> pcs_open(const char* who, const Commitment& cm, const std::
         if (!fr_eq(dot_fr(lo.data(), u.data() + (i + 1) * C, C), claims[i].value))
             throw Error(std::string(who) + ": claim " + std::to_string(i) + ": the value is not the evaluation of table " + std::to_string(claims[i].table) + " at the point");
     }
-    std::vector<uint8_t>& out = tr.bytes;
-    out.reserve(pcs_opening_bytes(sh, n, Q));
-    for (const Fr& x : u) write_be32(out, x);
-    pcs_absorb(tr, u.data(), u.size());
-    const std::vector<size_t> js = pcs_squeeze_indices(tr, N, Q);
-    std::vector<Fr> cols(Q * R);
-    if (Q) { if (cm.ctx) pcs_columns_device(cm, js, cols.data()); else pcs_columns_host(cm, js, cols.data()); }
-    for (size_t q = 0; q < Q; q++) {
-        for (size_t r = 0; r < R; r++) write_be32(out, cols[q * R + r]);
-        size_t idx = js[q];
-        for (int l = 0; l < sh.depth(); l++, idx >>= 1) {
-            const uint8_t* sib = cm.node(l, idx ^ 1);
-            out.insert(out.end(), sib, sib + 32);
-        }
-    }
-    if (out.size() != pcs_opening_bytes(sh, n, Q)) throw Error(std::string(who) + ": internal: opening length");
+    write_u_and_queries(tr, cm, u, Q, pcs_opening_bytes(sh, n, Q));
+    if (tr.bytes.size() != pcs_opening_bytes(sh, n, Q)) throw Error(std::string(who) + ": internal: opening length");
     return std::move(tr.bytes);
 }
 
-std::string pcs_verify(const Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof, size_t len) {
-    const size_t C = sh.C(), N = sh.N(), R = sh.R, n = claims.size();
-    const int depth = sh.depth();
-    // 1. exact length
-    const std::string bad_len = pcs::length_reason(len, pcs_opening_bytes(sh, n, Q));
-    if (!bad_len.empty()) return bad_len;
-    // 2. every element below r
-    const size_t u_bytes = 32 * C * (n + 1), q_bytes = 32 * R + 32 * (size_t)depth;
-    std::vector<Fr> u((n + 1) * C);
+
+// ---- the body of an opening - n + 1 u vectors, then Q queries - as pcs_verify and pcs_verify_folded check it
+// Reads the u vectors and the Q R column elements of a body that starts at byte `base` of its opening -> "" or the reason of the lowest
+// element that is not below r
+static std::string read_body(const Shape& sh, size_t n, size_t Q, const uint8_t* body, size_t base, std::vector<Fr>& u, std::vector<Fr>& cols) {
+    const size_t C = sh.C(), R = sh.R;
+    const size_t u_bytes = 32 * C * (n + 1), q_bytes = 32 * R + 32 * (size_t)sh.depth();
+    u.resize((n + 1) * C);
     for (size_t i = 0; i < u.size(); i++) {
-        u[i] = pcs_read_be32(proof + 32 * i);
-        if (fr_geq_p(u[i])) return pcs::reason_noncanonical(32 * i);
+        u[i] = pcs_read_be32(body + 32 * i);
+        if (fr_geq_p(u[i])) return pcs::reason_noncanonical(base + 32 * i);
     }
-    std::vector<Fr> cols(Q * R);
+    cols.resize(Q * R);
     for (size_t q = 0; q < Q; q++)
         for (size_t r = 0; r < R; r++) {
             const size_t at = u_bytes + q * q_bytes + 32 * r;
-            cols[q * R + r] = pcs_read_be32(proof + at);
-            if (fr_geq_p(cols[q * R + r])) return pcs::reason_noncanonical(at);
+            cols[q * R + r] = pcs_read_be32(body + at);
+            if (fr_geq_p(cols[q * R + r])) return pcs::reason_noncanonical(base + at);
         }
-    // 3. <u_i, eq(z_i[..c])> == y_i
-    for (size_t i = 0; i < n; i++) {
-        const std::vector<Fr> lo = pcs_eq_table(claims[i].point.data(), (size_t)sh.c);
-        if (!fr_eq(dot_fr(lo.data(), u.data() + (i + 1) * C, C), claims[i].value)) return pcs::reason_evaluation(i);
-    }
-    // the challenges
-    FsTranscript tr = pcs_start_transcript(sh, root, claims, Q);
-    const std::vector<Fr> rho = pcs_rho_powers(pcs_squeeze(tr), R);
+    return "";
+}
+// a claim as the queries see it: its weights (Montgomery form) over the rows from row0 on
+struct RowWeights { size_t row0; std::vector<Fr> w; };
+// The u vectors into the transcript, the column indices out of it, then per query: path, proximity (rho: the R powers), claims.
+// weights(i): claim i's, called once and only if there is a query
+template <class Weights>
+static std::string check_queries(const Shape& sh, const uint8_t root[32], FsTranscript& tr, const std::vector<Fr>& rho, size_t n, Weights weights, const std::vector<Fr>& u,
+                                 const std::vector<Fr>& cols, size_t Q, const uint8_t* body) {
+    const size_t C = sh.C(), N = sh.N(), R = sh.R;
+    const int depth = sh.depth();
+    const size_t u_bytes = 32 * C * (n + 1), q_bytes = 32 * R + 32 * (size_t)depth;
     pcs_absorb(tr, u.data(), u.size());
     const std::vector<size_t> js = pcs_squeeze_indices(tr, N, Q);
     // Enc(u_i)
     std::vector<Fr> enc((n + 1) * N, fr_zero());
-    std::vector<std::vector<Fr>> w(n);
+    std::vector<RowWeights> w(n);
     if (Q) {
         const std::vector<Fr> W = root_powers(depth, N / 2);
         [[maybe_unused]] const int nt = hg_omp_threads();
@@ -290,12 +301,11 @@ std::string pcs_verify(const Shape& sh, const uint8_t root[32], const std::vecto
             memcpy(enc.data() + i * N, u.data() + i * C, 32 * C);
             ntt_host_fr(enc.data() + i * N, depth, W.data());
         }
-        for (size_t i = 0; i < n; i++) w[i] = pcs_eq_table(claims[i].point.data() + sh.c, (size_t)(sh.nvars[claims[i].table] - sh.c));
+        for (size_t i = 0; i < n; i++) w[i] = weights(i);
     }
-    // 4. per query: path, proximity, claims
     for (size_t q = 0; q < Q; q++) {
         const Fr* col = cols.data() + q * R;
-        const uint8_t* sib = proof + u_bytes + q * q_bytes + 32 * R;
+        const uint8_t* sib = body + u_bytes + q * q_bytes + 32 * R;
         uint8_t h[32], nx[32];
         leaf_hash_fr(col, R, h);
         size_t idx = js[q];
@@ -306,9 +316,267 @@ std::string pcs_verify(const Shape& sh, const uint8_t root[32], const std::vecto
         if (memcmp(h, root, 32) != 0) return pcs::reason_merkle(q);
         if (!fr_eq(dot_fr(rho.data(), col, R), enc[js[q]])) return pcs::reason_proximity(q);
         for (size_t i = 0; i < n; i++)
-            if (!fr_eq(dot_fr(w[i].data(), col + sh.off[claims[i].table], w[i].size()), enc[(i + 1) * N + js[q]])) return pcs::reason_claim(i, q);
+            if (!fr_eq(dot_fr(w[i].w.data(), col + w[i].row0, w[i].w.size()), enc[(i + 1) * N + js[q]])) return pcs::reason_claim(i, q);
     }
     return "";
+}
+
+std::string pcs_verify(const Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof, size_t len) {
+    const size_t C = sh.C(), R = sh.R, n = claims.size();
+    // 1. exact length
+    const std::string bad_len = pcs::length_reason(len, pcs_opening_bytes(sh, n, Q));
+    if (!bad_len.empty()) return bad_len;
+    // 2. every element below r
+    std::vector<Fr> u, cols;
+    const std::string bad_word = read_body(sh, n, Q, proof, 0, u, cols);
+    if (!bad_word.empty()) return bad_word;
+    // 3. <u_i, eq(z_i[..c])> == y_i
+    for (size_t i = 0; i < n; i++) {
+        const std::vector<Fr> lo = pcs_eq_table(claims[i].point.data(), (size_t)sh.c);
+        if (!fr_eq(dot_fr(lo.data(), u.data() + (i + 1) * C, C), claims[i].value)) return pcs::reason_evaluation(i);
+    }
+    // the challenges, then 4. per query: path, proximity, claims
+    FsTranscript tr = pcs_start_transcript(sh, root, claims, Q);
+    const std::vector<Fr> rho = pcs_rho_powers(pcs_squeeze(tr), R);
+    auto weights = [&](size_t i) { return RowWeights{sh.off[claims[i].table], pcs_eq_table(claims[i].point.data() + sh.c, (size_t)(sh.nvars[claims[i].table] - sh.c))}; };
+    return check_queries(sh, root, tr, rho, n, weights, u, cols, Q, proof);
+}
+
+// ---- folded openings (hg.h "Folded openings over BN254"): pcs.cpp's with F = E = Fr. Table entries, the round's sums, the Y_t and every
+// element written are plain canonical words; beta^i, the challenges as multipliers, g and the tails are in Montgomery form, so a
+// Montgomery product of one of each is the plain product.
+static const char FOLD_TAG[] = "hg-pcs-bn254-fold-1";
+// eq(z, r) for one coordinate: z r + (1 - z) (1 - r), all in Montgomery form
+static Fr eq1(const Fr& z, const Fr& r) {
+    const Fr zr = fr_mul(z, r);
+    return fr_sub(fr_add(fr_add(zr, zr), fr_one_mont()), fr_add(z, r));
+}
+// the weights of the combined row over all R rows: w[off_t + r] = delta^t eq(rho[c..v_t))[r]
+static std::vector<Fr> combined_weights(const Shape& sh, const std::vector<Fr>& rho_canon, const Fr& delta_canon) {
+    std::vector<Fr> w(sh.R);
+    const Fr delta = fr_to_mont(delta_canon);
+    Fr d = fr_one_mont();
+    for (size_t t = 0; t < sh.nvars.size(); t++, d = fr_mul(d, delta)) {
+        const std::vector<Fr> eq = pcs_eq_table(rho_canon.data() + sh.c, (size_t)(sh.nvars[t] - sh.c));
+        for (size_t r = 0; r < eq.size(); r++) w[sh.off[t] + r] = fr_mul(d, eq[r]);
+    }
+    return w;
+}
+static void write_fr(FsTranscript& tr, const Fr& x) {   // an element of the header: into the opening and into the transcript
+    write_be32(tr.bytes, x);
+    pcs_absorb(tr, &x, 1);
+}
+
+// The host form of the reduction: every table (plain) and its g (Montgomery) as vectors, folded in place
+struct FoldHost : PcsFoldSource {
+    std::vector<std::vector<Fr>> t, g;
+    void step(size_t j, const Fr& r, Fr s[3]) override {
+        [[maybe_unused]] const int nt = hg_omp_threads();
+        const Fr rm = fr_to_mont(r);
+        for (size_t x = 0; x < t.size(); x++) {
+            std::vector<Fr>&a = t[x], &b = g[x];
+            if (a.empty()) continue;   // retired
+            if (j > 0) {
+                const long long h = (long long)(a.size() / 2);
+                std::vector<Fr> a2((size_t)h), b2((size_t)h);
+#pragma omp parallel for schedule(static) num_threads(nt) if (h >= 4096)
+                for (long long i = 0; i < h; i++) {
+                    a2[i] = fr_add(a[2 * i], fr_mul(rm, fr_sub(a[2 * i + 1], a[2 * i])));
+                    b2[i] = fr_add(b[2 * i], fr_mul(rm, fr_sub(b[2 * i + 1], b[2 * i])));
+                }
+                a.swap(a2);
+                b.swap(b2);
+            }
+            if (a.size() == 1) {
+                T[x] = a[0];
+                G[x] = b[0];
+                a.clear();
+                b.clear();
+            }
+        }
+        if (!s) return;
+        s[0] = s[1] = s[2] = fr_zero();
+        for (size_t x = 0; x < t.size(); x++) {
+            const std::vector<Fr>&a = t[x], &b = g[x];
+            const long long h = (long long)(a.size() / 2);
+            const int parts = h >= 4096 ? nt : 1;
+            std::vector<Fr> part(3 * (size_t)parts, fr_zero());
+#pragma omp parallel for schedule(static) num_threads(parts)
+            for (int q = 0; q < parts; q++) {
+                Fr s0 = fr_zero(), s1 = fr_zero(), s2 = fr_zero();
+                for (long long i = h * q / parts; i < h * (q + 1) / parts; i++) {
+                    s0 = fr_add(s0, fr_mul(b[2 * i], a[2 * i]));
+                    s1 = fr_add(s1, fr_mul(b[2 * i + 1], a[2 * i + 1]));
+                    s2 = fr_add(s2, fr_mul(fr_sub(b[2 * i + 1], b[2 * i]), fr_sub(a[2 * i + 1], a[2 * i])));
+                }
+                part[3 * q] = s0; part[3 * q + 1] = s1; part[3 * q + 2] = s2;
+            }
+            for (int q = 0; q < parts; q++)
+                for (int k = 0; k < 3; k++) s[k] = fr_add(s[k], part[3 * q + k]);
+        }
+    }
+};
+std::unique_ptr<PcsFoldSource> pcs_fold_source_host(const Commitment& cm, const std::vector<PcsClaim>& claims, const std::vector<Fr>& bpow) {
+    const Shape& sh = cm.sh;
+    const size_t m = sh.nvars.size(), C = sh.C();
+    std::unique_ptr<FoldHost> f(new FoldHost());
+    f->T.assign(m, fr_zero());
+    f->G.assign(m, fr_zero());
+    f->t.resize(m);
+    f->g.resize(m);
+    const Fr* rows = reinterpret_cast<const Fr*>(cm.rows.data());
+    for (size_t x = 0; x < m; x++) {
+        const size_t len = (size_t)1 << sh.nvars[x];
+        f->t[x].assign(rows + sh.off[x] * C, rows + sh.off[x] * C + len);
+        f->g[x].assign(len, fr_zero());
+    }
+    [[maybe_unused]] const int nt = hg_omp_threads();
+    for (size_t i = 0; i < claims.size(); i++) {
+        const std::vector<Fr> eq = pcs_eq_table(claims[i].point.data(), claims[i].point.size());
+        std::vector<Fr>& g = f->g[claims[i].table];
+        const Fr b = bpow[i];
+#pragma omp parallel for schedule(static) num_threads(nt) if (eq.size() >= 4096)
+        for (long long k = 0; k < (long long)eq.size(); k++) g[k] = fr_add(g[k], fr_mul(b, eq[k]));
+    }
+    return f;
+}
+
+std::vector<uint8_t> pcs_open_folded(const char* who, const Commitment& cm, const std::vector<PcsClaim>& claims, size_t Q) {
+    const Shape& sh = cm.sh;
+    const size_t C = sh.C(), R = sh.R, n = claims.size(), m = sh.nvars.size(), V = pcs::fold_rounds(sh);
+    const std::string w(who);
+    if (!n) throw Error(w + ": a folded opening needs a claim");
+    FsTranscript tr = pcs_start_transcript(sh, cm.root(), claims, Q, FOLD_TAG);
+    const std::vector<Fr> bpow = pcs_rho_powers(pcs_squeeze(tr), n);
+    Fr claim = fr_zero();
+    for (size_t i = 0; i < n; i++) claim = fr_add(claim, fr_mul(bpow[i], claims[i].value));
+    // a running claim the sums do not meet: a value is wrong. The claims one by one, as pcs_open checks them, to name the lowest
+    auto refuse = [&]() {
+        for (size_t i = 0; i < n; i++) {
+            const PcsClaim& cl = claims[i];
+            std::vector<PcsJob> job(1);
+            job[0].row0 = sh.off[cl.table];
+            job[0].nrows = (size_t)1 << (sh.nvars[cl.table] - sh.c);
+            job[0].w = pcs_eq_table(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
+            std::vector<Fr> u(C);
+            if (cm.ctx) pcs_combine_device(cm, job, u.data()); else pcs_combine_host(cm, job, u.data());
+            const std::vector<Fr> lo = pcs_eq_table(cl.point.data(), (size_t)sh.c);
+            if (!fr_eq(dot_fr(lo.data(), u.data(), C), cl.value))
+                throw Error(w + ": claim " + std::to_string(i) + ": the value is not the evaluation of table " + std::to_string(cl.table) + " at the point");
+        }
+        throw Error(w + ": internal: the reduction does not meet its claim");
+    };
+    std::unique_ptr<PcsFoldSource> src;
+    try {
+        src = cm.ctx ? pcs_fold_source_device(who, cm, claims, bpow) : pcs_fold_source_host(cm, claims, bpow);
+    } catch (const std::exception& e) {
+        throw Error(w + ": " + e.what());
+    }
+    std::vector<Fr> tail(m, fr_one_mont()), rho(V);
+    auto retired = [&](size_t t) { return fr_mul(fr_mul(src->G[t], tail[t]), src->T[t]); };   // K_t prod (1 - r_j'), plain
+    Fr r = fr_zero();
+    for (size_t j = 0; j < V; j++) {
+        Fr s[3];
+        src->step(j, r, s);
+        Fr k = fr_zero();   // the retired tables: K_t prod (1 - r_j') (1 - X)
+        for (size_t t = 0; t < m; t++)
+            if ((size_t)sh.nvars[t] <= j) k = fr_add(k, retired(t));
+        const Fr c0 = fr_add(s[0], k), c2 = s[2], c1 = fr_sub(fr_sub(s[1], s[0]), fr_add(s[2], k));
+        if (!fr_eq(fr_add(fr_add(c0, c0), fr_add(c1, c2)), claim)) refuse();   // (round 0 is where a wrong value shows)
+        write_fr(tr, c0);
+        write_fr(tr, c1);
+        write_fr(tr, c2);
+        r = rho[j] = pcs_squeeze(tr);
+        const Fr rm = fr_to_mont(r);
+        claim = fr_add(c0, fr_mul(rm, fr_add(c1, fr_mul(rm, c2))));
+        for (size_t t = 0; t < m; t++)
+            if ((size_t)sh.nvars[t] <= j) tail[t] = fr_mul(tail[t], fr_sub(fr_one_mont(), rm));
+    }
+    src->step(V, r, nullptr);
+    Fr fin = fr_zero();
+    for (size_t t = 0; t < m; t++) fin = fr_add(fin, retired(t));
+    if (!fr_eq(fin, claim)) refuse();
+    for (size_t t = 0; t < m; t++) write_fr(tr, src->T[t]);
+    src.reset();   // (the device form's scratch is the context's arena, which the row combinations take next)
+    const Fr delta = pcs_squeeze(tr);
+    std::vector<PcsJob> jobs(2);
+    jobs[0].row0 = 0; jobs[0].nrows = R; jobs[0].w = pcs_rho_powers(pcs_squeeze(tr), R);
+    jobs[1].row0 = 0; jobs[1].nrows = R; jobs[1].w = combined_weights(sh, rho, delta);
+    std::vector<Fr> u(2 * C);
+    if (cm.ctx) pcs_combine_device(cm, jobs, u.data()); else pcs_combine_host(cm, jobs, u.data());
+    write_u_and_queries(tr, cm, u, Q, pcs_folded_opening_bytes(sh, Q));
+    if (tr.bytes.size() != pcs_folded_opening_bytes(sh, Q)) throw Error(w + ": internal: opening length");
+    return std::move(tr.bytes);
+}
+
+PcsFoldedHeader pcs_folded_header(const Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof) {
+    const size_t R = sh.R, n = claims.size(), m = sh.nvars.size(), V = pcs::fold_rounds(sh);
+    PcsFoldedHeader H;
+    std::vector<Fr> el(3 * V + m);
+    for (size_t i = 0; i < el.size(); i++) {
+        el[i] = pcs_read_be32(proof + 32 * i);
+        if (fr_geq_p(el[i])) { H.noncanonical = 32 * i; return H; }
+    }
+    H.tr = pcs_start_transcript(sh, root, claims, Q, FOLD_TAG);
+    const std::vector<Fr> bpow = pcs_rho_powers(pcs_squeeze(H.tr), n);
+    Fr claim = fr_zero();
+    for (size_t i = 0; i < n; i++) claim = fr_add(claim, fr_mul(bpow[i], claims[i].value));
+    std::vector<Fr> rho(V), rm(V);
+    for (size_t j = 0; j < V; j++) {
+        const Fr c0 = el[3 * j], c1 = el[3 * j + 1], c2 = el[3 * j + 2];
+        if (H.reason.empty() && !fr_eq(fr_add(fr_add(c0, c0), fr_add(c1, c2)), claim)) H.reason = "pcs: fold round " + std::to_string(j) + " does not match the running claim";
+        pcs_absorb(H.tr, &el[3 * j], 3);
+        rho[j] = pcs_squeeze(H.tr);
+        rm[j] = fr_to_mont(rho[j]);
+        claim = fr_add(c0, fr_mul(rm[j], fr_add(c1, fr_mul(rm[j], c2))));
+    }
+    const Fr* Y = el.data() + 3 * V;
+    pcs_absorb(H.tr, Y, m);
+    // sum_t Y_t g_t(rho[..v_t)) prod_{j >= v_t} (1 - rho_j), g_t from the claims: n V products
+    std::vector<Fr> gt(m, fr_zero());
+    for (size_t i = 0; i < n; i++) {
+        Fr e = bpow[i];
+        for (size_t b = 0; b < claims[i].point.size(); b++) e = fr_mul(e, eq1(fr_to_mont(claims[i].point[b]), rm[b]));
+        gt[claims[i].table] = fr_add(gt[claims[i].table], e);
+    }
+    Fr fin = fr_zero();
+    for (size_t t = 0; t < m; t++) {
+        Fr e = gt[t];
+        for (size_t j = (size_t)sh.nvars[t]; j < V; j++) e = fr_mul(e, fr_sub(fr_one_mont(), rm[j]));
+        fin = fr_add(fin, fr_mul(e, Y[t]));
+    }
+    if (H.reason.empty() && !fr_eq(fin, claim)) H.reason = "pcs: fold final evaluation mismatch";
+    // the body's one claim
+    const Fr delta = pcs_squeeze(H.tr);
+    H.rho_pw = pcs_rho_powers(pcs_squeeze(H.tr), R);
+    H.w = combined_weights(sh, rho, delta);
+    H.lo.assign(rho.begin(), rho.begin() + sh.c);
+    H.y = fr_zero();
+    const Fr dm = fr_to_mont(delta);
+    Fr d = fr_one_mont();
+    for (size_t t = 0; t < m; t++, d = fr_mul(d, dm)) H.y = fr_add(H.y, fr_mul(d, Y[t]));
+    return H;
+}
+
+std::string pcs_verify_folded(const Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof, size_t len) {
+    const size_t C = sh.C(), hb = pcs_folded_header_bytes(sh);
+    // 1. exact length
+    const std::string bad_len = pcs::length_reason(len, pcs_folded_opening_bytes(sh, Q));
+    if (!bad_len.empty()) return bad_len;
+    // 2. every element below r, the header's first
+    PcsFoldedHeader H = pcs_folded_header(sh, root, claims, Q, proof);
+    if (H.noncanonical != ~(size_t)0) return pcs::reason_noncanonical(H.noncanonical);
+    std::vector<Fr> u, cols;
+    const std::string bad_word = read_body(sh, 1, Q, proof + hb, hb, u, cols);
+    if (!bad_word.empty()) return bad_word;
+    // 3., 4. the rounds and the final evaluation
+    if (!H.reason.empty()) return H.reason;
+    // 5. <u_1, eq(rho[..c))> == sum_t delta^t Y_t
+    const std::vector<Fr> lo = pcs_eq_table(H.lo.data(), (size_t)sh.c);
+    if (!fr_eq(dot_fr(lo.data(), u.data() + C, C), H.y)) return pcs::reason_evaluation(0);
+    // 6. per query: path, proximity, the combined claim
+    auto weights = [&](size_t) { return RowWeights{0, H.w}; };
+    return check_queries(sh, root, H.tr, H.rho_pw, 1, weights, u, cols, Q, proof + hb);
 }
 
 }  // namespace bn

@@ -58,8 +58,42 @@ std::string pcs_verify_device(hg_ctx* ctx, const pcs::Shape& sh, const uint8_t r
 struct VerifyItem { const uint8_t* root; const std::vector<PcsClaim>* claims; const uint8_t* proof; size_t len; };
 std::vector<std::string> pcs_verify_device_batch(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const std::vector<VerifyItem>& items, size_t Q);
 
+// ---- folded openings (hg.h "Folded openings over BN254"): the folded openings of pcs.hpp with F = E = Fr. The header is 3 coefficients a
+// round, V = max_t v_t rounds, then the m values Y_t, 32 bytes big-endian each; the body is that of an opening of one claim.
+inline size_t pcs_folded_header_bytes(const pcs::Shape& sh) { return 32 * (3 * pcs::fold_rounds(sh) + sh.nvars.size()); }
+inline size_t pcs_folded_opening_bytes(const pcs::Shape& sh, size_t Q) { return pcs_folded_header_bytes(sh) + pcs_opening_bytes(sh, 1, Q); }
+// The prover's side of the reduction: pcs::FoldSource over Fr. r is the canonical challenge of round j - 1; T[t] (plain) and G[t]
+// (Montgomery form) are canonical once table t has retired; s = the three sums as plain canonical elements
+struct PcsFoldSource {
+    std::vector<Fr> T, G;
+    virtual void step(size_t j, const Fr& r, Fr s[3]) = 0;
+    virtual ~PcsFoldSource() {}
+};
+// bpow[i] = beta^i in Montgomery form. The host form reads cm.rows; the device form (bn254_pcs.inc) builds g and runs every round on the
+// context's stream (`who` names the entry in the texts of its device calls)
+std::unique_ptr<PcsFoldSource> pcs_fold_source_host(const pcs::Commitment& cm, const std::vector<PcsClaim>& claims, const std::vector<Fr>& bpow);
+std::unique_ptr<PcsFoldSource> pcs_fold_source_device(const char* who, const pcs::Commitment& cm, const std::vector<PcsClaim>& claims, const std::vector<Fr>& bpow);
+// hg_pcs_open_folded_bn254: the opening bytes; an Error naming `who` if there is no claim and - naming the lowest failing claim - if a
+// value is not its table's evaluation
+std::vector<uint8_t> pcs_open_folded(const char* who, const pcs::Commitment& cm, const std::vector<PcsClaim>& claims, size_t Q);
+// hg_pcs_verify_folded_bn254: "" = accepted, else the reason
+std::string pcs_verify_folded(const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof, size_t len);
+// hg_pcs_verify_folded_device_bn254 (bn254_pcs.inc): the same decision and reason; the header on the host, the body through
+// pcs_verify_device's kernels
+std::string pcs_verify_folded_device(hg_ctx* ctx, const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof, size_t len);
+// What the two folded verifiers share (pcs::FoldedHeader over Fr): rho_pw and w in Montgomery form, lo and y canonical
+struct PcsFoldedHeader {
+    size_t noncanonical = ~(size_t)0;
+    std::string reason;
+    FsTranscript tr;
+    std::vector<Fr> rho_pw, w, lo;
+    Fr y;
+};
+PcsFoldedHeader pcs_folded_header(const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof);
+
 // ---- what the opening and both forms of the verifier share (pcs_bn254.cpp): the transcript up to the column indices, the weights
-FsTranscript pcs_start_transcript(const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q);
+// tag: "hg-pcs-bn254-1", or "hg-pcs-bn254-fold-1" for a folded opening
+FsTranscript pcs_start_transcript(const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const char* tag = "hg-pcs-bn254-1");
 Fr pcs_squeeze(FsTranscript& tr);                                                    // a challenge, canonical (rho is the first)
 std::vector<Fr> pcs_rho_powers(const Fr& rho_canon, size_t R);                       // rho^r, r < R, Montgomery form
 void pcs_absorb(FsTranscript& tr, const Fr* x, size_t count);                        // canonical elements as their 32 bytes

@@ -178,6 +178,66 @@ std::string verify_flow(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], co
     return cells_reason(cells, n);
 }
 
+// The device verifier of a folded opening. The header is host scalar work (the field's folded_header); its body is an opening of one
+// claim - all R rows under the combined weights, at rho[..c), with the value sum_t delta^t Y_t - and goes through verify_flow's kernels
+// as a group of one member whose opening starts behind the header. The kernels run whatever the header's checks gave: an element of the
+// body that is not canonical is reported ahead of a failing round, as the host verifier does.
+template <class F>
+std::string verify_folded_flow(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], const std::vector<typename F::Claim>& claims, size_t Q, const uint8_t* proof, size_t len) {
+    typedef typename F::W W;
+    const size_t C = sh.C(), N = sh.N(), R = sh.R, hb = F::folded_header_bytes(sh);
+    const std::string who(F::VERIFY_FOLDED_NAME);
+    const std::string bad_len = length_reason(len, F::folded_opening_bytes(sh, Q));
+    if (!bad_len.empty()) return bad_len;
+    auto H = F::folded_header(sh, root, claims, Q, proof);
+    if (H.noncanonical != ~(size_t)0) return reason_noncanonical(H.noncanonical);
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->arena_reset();
+    hipStream_t st = ctx->stream;
+    const size_t nw = 2 * R, u_units = F::U_ROWS * C * 2;
+    const VerifyTotals t{1, u_units, u_units + Q * R, F::U_ROWS * 2, 1, 2, nw};
+    VbMember desc{};
+    desc.n = 1;
+    desc.proof = hb / 8;
+    std::vector<char> stage(member_block_layout<F>(desc, sh, 1, nw, sizeof(VbMember)));
+    memcpy(stage.data(), &desc, sizeof(VbMember));
+    memcpy(stage.data() + desc.root_at, root, 32);
+    CombineDesc* hd = reinterpret_cast<CombineDesc*>(stage.data() + desc.jobs_at);
+    hd[0].row0 = 0; hd[0].nrows = R; hd[0].woff = 0;
+    hd[1].row0 = 0; hd[1].nrows = R; hd[1].woff = R;
+    memcpy(stage.data() + desc.y_at, &H.y, sizeof(W));
+    if (sh.c) F::store_low(reinterpret_cast<W*>(stage.data() + desc.z_at), H.lo.data(), sh.c);
+    memcpy(stage.data() + desc.w_at, H.rho_pw.data(), R * sizeof(W));
+    memcpy(stage.data() + desc.w_at + R * sizeof(W), H.w.data(), R * sizeof(W));
+    u64* d_proof;
+    VerifyDev<F> d;
+    try {
+        d_proof = ctx->alloc_n<u64>(len / 8);
+        d = verify_alloc<F>(ctx, sh, Q, stage.size(), t, 4);
+    } catch (const std::exception& e) {
+        throw Error(std::string("the context's arena cannot hold the opening (") + e.what() + ")");
+    }
+    Drain drain{st};   // (drains on an error; after the synchronisation below its own is one more, on an idle stream)
+    const int cls = ctx->prof_class(F::CLS_VERIFY, false);
+    ctx->prof_stream = st;
+    const VbGroup vg{1, (u64)Q, (u64)R, (u64)query_stride<F>(sh), sh.c, sh.depth()};
+    hip_check(hipMemcpyAsync(d_proof, proof, len, hipMemcpyHostToDevice, st), "upload opening");
+    hip_check(hipMemcpyAsync(d.stage, stage.data(), stage.size(), hipMemcpyHostToDevice, st), "upload claims");
+    verify_enqueue<F>(ctx, cls, st, 4096, d_proof, d, vg, t, 4);
+    F::absorb_opening(H.tr, proof + hb, 2 * C);
+    const std::vector<size_t> js = F::squeeze_indices(H.tr, N, Q);
+    const std::vector<u64> hj(js.begin(), js.end());
+    verify_enqueue_query<F>(ctx, cls, st, d_proof, d, vg, t, hj.data());
+    u64 cells[4];
+    hip_check(hipMemcpyAsync(cells, d.cells, 32, hipMemcpyDeviceToHost, st), "download verdict");
+    hip_check(hipStreamSynchronize(st), (who + ": sync").c_str());
+    hip_check(hipGetLastError(), (who + ": launch").c_str());
+    ctx->prof_collect();
+    if (cells[0] != PCSV_NONE) return reason_noncanonical(hb + (size_t)cells[0]);
+    if (!H.reason.empty()) return H.reason;
+    return cells_reason(cells, 1);
+}
+
 // The device verifier of a run of openings. The items whose length is right are cut into groups (the option verify_batch_group,
 // VB_PCS_BUDGET over what a member takes, the rows the field's NTT takes on its four-step path, the field's limit of one inner-product
 // launch). A group: its openings gathered into a page-locked set on the host threads and copied on the upload stream; every member's

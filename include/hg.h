@@ -448,12 +448,13 @@ int hg_claims_verify_device(hg_ctx* ctx, const hg_params* params, const uint8_t 
  *     Enc(u_1)[j_q] ("pcs: claim 0 inconsistent at query q"), the first two with the texts of hg_pcs_verify.
  *   Soundness is the beta and delta combinations plus the sum-check over E, on top of what the opening above claims; no more is
  *   claimed. Still not zero knowledge.
- * Contracts are those of the unfolded entries unless stated. Goldilocks only, single calls only: there are no batch forms, no BN254
- * forms, and hg_prove_encryptions_committed does not fold.
+ * Contracts are those of the unfolded entries unless stated. Single calls only: there are no batch forms, and
+ * hg_prove_encryptions_committed does not fold. The forms over bn256::Fr are hg_pcs_open_folded_bn254 and its neighbours ("Folded
+ * openings over BN254" below).
  * hg_pcs_open_folded: hg_pcs_open's arguments. n_claims == 0 is -1 ("<function>: a folded opening needs a claim"; the proximity
  *   test alone is hg_pcs_open). *len = the length also when cap is too small. A value that is not its table's evaluation is refused
  *   with hg_pcs_open's text under this name, naming the lowest failing claim: the prover sees that round 0's s(0) + s(1) is not S
- *   and only then evaluates the claims one by one. A BN254 handle or a handle of another context is -1. The host form (ctx == NULL)
+ *   and only then evaluates the claims one by one. A BN254 handle (open it with hg_pcs_open_folded_bn254) or a handle of another context is -1. The host form (ctx == NULL)
  *   is the byte reference. The device form builds g in HBM (16 bytes a table entry, 28 MB at n=32768 k=16) with one kernel from
  *   per-claim factor tables staged in one copy, then runs one launch a round on the context's stream with scratch from its arena:
  *   every live table pair is folded by the previous challenge and enters the round's sums in the same pass (round 0 reads the
@@ -1156,6 +1157,74 @@ int hg_claims_verify_bn254(const hg_params* params, const uint8_t root[32], size
                            const uint64_t* points4, size_t n_queries, const uint8_t* opening, size_t len);
 int hg_claims_verify_device_bn254(hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n,
                                   const uint64_t* points4, size_t n_queries, const uint8_t* opening, size_t len);
+
+/* ---- Folded openings over BN254: "Folded openings" above with F = E = Fr ---------------------------------------------------------
+ * The six folded entries over bn256::Fr, with the element conventions of the BN254 commitment above: 4 canonical little-endian limbs
+ * across the ABI, 32-byte big-endian elements in the opening, repr absorbed, claims as hg_input_claim_bn254 with points4. An element is
+ * four times a Goldilocks word, so folding saves most here: for the 47 claims of n=32768 k=16 (m = 20, V = 19, c = 11, C = 2048,
+ * R = 864, Q = 241) a folded opening is 2464 + 131072 + 6763424 = 6 896 960 bytes against 9 909 152, the transcript hashes 128 KB of u
+ * instead of 3.1 MB, and prover and verifiers form 2 row combinations instead of 48.
+ *
+ * The scheme; V = max_t v_t, n >= 1 claims (t_i, z_i, y_i); one squeezed element is one challenge, there is no extension field.
+ *   Transcript. That of "hg-pcs-bn254-1": absorbing, challenge = LE(Keccak256(state)) mod r, the state becomes the hash. It starts as
+ *     the 19 ASCII bytes "hg-pcs-bn254-fold-1" followed by exactly what "hg-pcs-bn254-1" appends after its tag: the root, c, m,
+ *     v_0 .. v_{m-1}, Q, n (4-byte LE), per claim t_i (4-byte LE), repr of the point's coordinates and of the value. Every element
+ *     written below is absorbed as repr (32 bytes little-endian, canonical) and appears in the opening as 32 bytes big-endian.
+ *   1. beta is squeezed. S = sum_i beta^i y_i. For every table g_t(x) = sum_{i: t_i = t} beta^i eq(z_i, x) on v_t variables (zero for
+ *      a table without a claim): sum_t sum_x g_t(x) T_t(x) = S.
+ *   2. V rounds, the lowest variable first; folding by r is T'[j] = T[2j] + r (T[2j+1] - T[2j]). In round j the prover writes the
+ *      coefficients c0, c1, c2 of s_j(X) = sum_t s_{j,t}(X), then r_j is squeezed. For v_t > j, s_{j,t}(X) = sum_{x'} g_t^(j)(X, x')
+ *      T_t^(j)(X, x') over the tables folded by r_0 .. r_{j-1}. For v_t <= j, s_{j,t}(X) = K_t prod_{v_t <= j' < j} (1 - r_j') (1 - X)
+ *      with K_t = g_t(rho[..v_t)) T_t(rho[..v_t)). rho = (r_0 .. r_{V-1}).
+ *   3. The prover writes Y_t = T_t(rho[0..v_t)), t = 0 .. m-1.
+ *   4. delta, then rho' are squeezed. u_0[j] = sum_{r<R} rho'^r row_r[j]; u_1[j] = sum_t delta^t sum_{r < 2^{v_t-c}}
+ *      eq(rho[c..v_t))[r] row_{off_t+r}[j]. u_0, then u_1 are written.
+ *   5. Q column indices, each the low 64 bits of a squeezed element & (4C - 1), and 6. per query the R column elements and the c+2
+ *      siblings, exactly as in "hg-pcs-bn254-1".
+ *   Layout: a header of 32 (3 V + m) bytes - the round coefficients, then the Y_t - followed by a body that has exactly the layout of
+ *     an "hg-pcs-bn254-1" opening of one claim: u_0, u_1, Q x (32 R + 32 (c+2)). Length: exactly 32 (3 V + m) + 64 C + Q (32 R + 32 (c+2)).
+ *   Verification (hg_pcs_verify_folded_bn254 on the host, hg_pcs_verify_folded_device_bn254 on a context), in this order, the first
+ *     failure is the reason:  1. the exact length ("pcs: the opening has .. bytes, .. expected", with the folded length);  2. every
+ *     element below r ("pcs: non-canonical word at byte B", B = the offset of the first byte of the first element that is not below
+ *     r, counted from the start of the folded opening: the header first, then u, then the columns query by query);  3. for j
+ *     ascending 2 c0 + c1 + c2 == claim_j, claim_0 = S, claim_{j+1} = s_j(r_j) ("pcs: fold round j does not match the running
+ *     claim");  4. claim_V == sum_t Y_t g_t(rho[..v_t)) prod_{j >= v_t} (1 - rho_j) ("pcs: fold final evaluation mismatch");
+ *     5. <u_1, eq(rho[..c))> == sum_t delta^t Y_t ("pcs: evaluation mismatch at claim 0");  6. per query, ascending: the Merkle path,
+ *     proximity, then the combined claim ("pcs: claim 0 inconsistent at query q"), the first two with the texts of hg_pcs_verify_bn254.
+ *   Soundness is what "Folded openings" claims, over Fr. Still not zero knowledge.
+ * Contracts are those of the Goldilocks folded entries. Single calls only: no batch forms, and hg_prove_encryptions_committed_bn254
+ * does not fold. hg_pcs_open and its BN254 neighbours, their bytes and "hg-pcs-bn254-1" are unchanged.
+ * hg_pcs_open_folded_bn254: hg_pcs_open_bn254's arguments. n_claims == 0 is -1 ("<function>: a folded opening needs a claim").
+ *   *len = the length also when cap is too small. A value that is not its table's evaluation is refused with hg_pcs_open_bn254's text
+ *   under this name, naming the lowest failing claim. A Goldilocks handle or a handle of another context is -1. The host form
+ *   (ctx == NULL) is the byte reference. The device form builds g in HBM beside the handle's raw rows (Montgomery form, 32 bytes a
+ *   table entry, 57 MB at n=32768 k=16) with one kernel from per-claim factor tables staged in one copy, then runs one launch a round
+ *   over all live tables on the context's stream with scratch from its arena ("the context's arena cannot hold the reduction" when
+ *   it does not fit): four adjacent entries of a table and of g are folded by the previous challenge into two of each and enter the
+ *   round's sums in the same pass (round 0 reads the raw rows, which are never written); the three sums come back once a round (one
+ *   synchronisation a round), a table of two entries retires into two scalars, a table of one element is a scalar from the start.
+ *   Everything that reaches the host is canonical, so device bytes equal host bytes. u_0 and u_1 are two row combinations of R rows
+ *   through hg_pcs_open_bn254's kernel, the columns through its gather. Profiler class pcs_fold_bn254. HG_PCS_FOLD_BLOCKS bounds the
+ *   workgroups of a launch as it does over Goldilocks. Not concurrently with another call on the same context.
+ * hg_pcs_verify_folded_bn254: hg_pcs_verify_bn254's arguments and -1 cases, and n_claims == 0 as above. Host only.
+ * hg_pcs_verify_folded_device_bn254: the same decision and reason on every input, also where several checks fail at once (a
+ *   non-canonical body element together with a failing round reports the element). ctx == NULL is -1 ("<function>: no context").
+ *   The header's checks are host scalar work; the body goes through the kernels of hg_pcs_verify_device_bn254 as an opening of one
+ *   claim that starts behind the header.
+ * hg_claims_open_folded_bn254 / hg_claims_verify_folded_bn254 / hg_claims_verify_folded_device_bn254: the same under the mapping and
+ *   the -1 cases of hg_claims_open_bn254 / hg_claims_verify_bn254, on an hg_input_claim_bn254 array as hg_verify_public_bn254 returns it. */
+int hg_pcs_open_folded_bn254(hg_ctx* ctx, const void* commitment, const uint32_t* table, const uint64_t* points4, const uint64_t* values4,
+                             size_t n_claims, size_t n_queries, uint8_t* proof, size_t cap, size_t* len);
+int hg_pcs_verify_folded_bn254(const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table,
+                               const uint64_t* points4, const uint64_t* values4, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len);
+int hg_pcs_verify_folded_device_bn254(hg_ctx* ctx, const uint8_t root[32], const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* table,
+                                      const uint64_t* points4, const uint64_t* values4, size_t n_claims, size_t n_queries, const uint8_t* proof, size_t len);
+int hg_claims_open_folded_bn254(hg_ctx* ctx, const hg_params* params, const void* commitment, const void* claims, size_t n, const uint64_t* points4,
+                                size_t n_queries, uint8_t* opening, size_t cap, size_t* len);
+int hg_claims_verify_folded_bn254(const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n,
+                                  const uint64_t* points4, size_t n_queries, const uint8_t* opening, size_t len);
+int hg_claims_verify_folded_device_bn254(hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n,
+                                         const uint64_t* points4, size_t n_queries, const uint8_t* opening, size_t len);
 
 /* hg_pcs_verify_device_batch_bn254 / hg_claims_verify_batch_bn254: hg_pcs_verify_device_batch / hg_claims_verify_batch over bn256::Fr,
  *   the same contract word for word with a coordinate or value of 4 canonical limbs: a run of n openings of ONE shape and one

@@ -7,7 +7,9 @@ witness and the claims hg_verify_public_device leaves on its hg_prove proof, dev
   verify_host / verify_host_folded    hg_claims_verify / hg_claims_verify_folded
 Prints the bytes of both openings, median and range per leg, per pair whether the whole range of the folded form lies below that of the
 unfolded form, then the kernel time of one more folded open under hg_profile (class pcs_fold: the g table, the rounds, their sums).
-Usage: pcs_fold_times.py [n k] [--reps 5]"""
+--bn254: the same legs over bn256::Fr - the claims of hg_verify_public_device_bn254 on an hg_prove_bn254 proof, the hg_claims_*_bn254
+entries, class pcs_fold_bn254.
+Usage: pcs_fold_times.py [n k] [--reps 5] [--bn254]"""
 import argparse
 import os
 import statistics
@@ -25,20 +27,28 @@ def main():
     ap.add_argument("n", type=int, nargs="?", default=32768)
     ap.add_argument("k", type=int, nargs="?", default=16)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--bn254", action="store_true")
     a = ap.parse_args()
     ctx = hg.Context(0)
     bfv = hg.BfvEncrypt.new(a.n, a.k)
     pk = bfv.setup(ctx)
     w = hg.Witness.synthetic(bfv.params, 0x4752454330 + a.n)
-    proof, _ = bfv.prove(ctx, pk, w, cap=1 << 25)
-    ok, why, claims = hg.verify_public(pk, hg.Instance.from_witness(w), proof, 0, ctx=ctx, device=True)
+    if a.bn254:
+        proof = ctx.prove_bn254(pk, w, cap=1 << 25)[0]
+        ok, why, claims = hg.verify_public_bn254(pk, hg.Instance.from_witness(w), proof, ctx=ctx, device=True)
+        cm = hg.Commitment.secrets_bn254(ctx, bfv.params, w) if ok else None
+        verify, verify_folded, cls = hg.claims_verify_bn254, hg.claims_verify_folded_bn254, "pcs_fold_bn254"
+    else:
+        proof, _ = bfv.prove(ctx, pk, w, cap=1 << 25)
+        ok, why, claims = hg.verify_public(pk, hg.Instance.from_witness(w), proof, 0, ctx=ctx, device=True)
+        cm = hg.Commitment.secrets(ctx, bfv.params, w) if ok else None
+        verify, verify_folded, cls = hg.claims_verify, hg.claims_verify_folded, "pcs_fold"
     assert ok, why
-    cm = hg.Commitment.secrets(ctx, bfv.params, w)
     params, root = bfv.params, cm.root
     plain, folded = cm.open_claims(params, claims), cm.open_claims_folded(params, claims)
     pairs = [("open", lambda: cm.open_claims(params, claims), lambda: cm.open_claims_folded(params, claims)),
-             ("verify_dev", lambda: hg.claims_verify(params, root, claims, plain, ctx=ctx), lambda: hg.claims_verify_folded(params, root, claims, folded, ctx=ctx)),
-             ("verify_host", lambda: hg.claims_verify(params, root, claims, plain), lambda: hg.claims_verify_folded(params, root, claims, folded))]
+             ("verify_dev", lambda: verify(params, root, claims, plain, ctx=ctx), lambda: verify_folded(params, root, claims, folded, ctx=ctx)),
+             ("verify_host", lambda: verify(params, root, claims, plain), lambda: verify_folded(params, root, claims, folded))]
     legs = [(name + sfx, fn) for name, f0, f1 in pairs for sfx, fn in (("", f0), ("_folded", f1))]
     times = {name: [] for name, _ in legs}
     for rep in range(a.reps + 1):   # rep 0: the warm-up call of each leg
@@ -52,8 +62,8 @@ def main():
                 assert out == (folded if name.endswith("_folded") else plain)
             if rep:
                 times[name].append(dt)
-    print("n=%d k=%d: %d tables, log2_row %d, %d rows; %d claims, 241 queries, opening %d bytes, folded %d bytes; legs alternated, %d timed calls each after "
-          "one warm-up call, one process" % (a.n, a.k, len(cm.nvars), cm.log2_row, sum(1 << (v - cm.log2_row) for v in cm.nvars), claims.n, len(plain), len(folded), a.reps))
+    print("%sn=%d k=%d: %d tables, log2_row %d, %d rows; %d claims, 241 queries, opening %d bytes, folded %d bytes; legs alternated, %d timed calls each after "
+          "one warm-up call, one process" % ("bn254 " if a.bn254 else "", a.n, a.k, len(cm.nvars), cm.log2_row, sum(1 << (v - cm.log2_row) for v in cm.nvars), claims.n, len(plain), len(folded), a.reps))
     for name, _ in legs:
         t = times[name]
         print("%-19s median %.2f ms, range %.2f .. %.2f ms (%s)" % (name, statistics.median(t), min(t), max(t), " ".join("%.2f" % x for x in t)))
@@ -69,8 +79,8 @@ def main():
     ctx.profile_reset()
     assert cm.open_claims_folded(params, claims) == folded
     for st in ctx.profile_get(256):
-        if st["name"] == "pcs_fold":
-            print("%-10s %3d launches %8.3f ms  %7.1f MB by the algorithm" % (st["name"], st["launches"], st["total_ms"], st["algo_bytes"] / 1e6))
+        if st["name"] == cls:
+            print("%-14s %3d launches %8.3f ms  %7.1f MB by the algorithm" % (st["name"], st["launches"], st["total_ms"], st["algo_bytes"] / 1e6))
     ctx.profile(0)
     cm.free()
     pk.free()
