@@ -57,6 +57,7 @@ EXPORTS = [
     "hg_pcs_verify_device", "hg_claims_verify_device", "hg_pcs_verify_device_batch", "hg_claims_verify_batch",
     "hg_pcs_commit_batch", "hg_secrets_commit_batch", "hg_pcs_open_batch", "hg_claims_open_batch",
     "hg_pcs_open_folded", "hg_pcs_verify_folded", "hg_pcs_verify_folded_device", "hg_claims_open_folded", "hg_claims_verify_folded", "hg_claims_verify_folded_device",
+    "hg_pcs_open_folded_batch", "hg_claims_open_folded_batch", "hg_pcs_verify_folded_device_batch", "hg_claims_verify_folded_batch",
     "hg_secrets_commit_values", "hg_prove_encryptions_committed", "hg_prove_encryptions_committed_bn254",
     "hg_instance_digest", "hg_instance_digest_batch", "hg_values_instance_digest", "hg_bound_seed", "hg_prove_committed_mode", "hg_verify_public_bound", "hg_verify_public_bound_device",
     "hg_verify_public_bound_batch", "hg_instance_digest_group",
@@ -137,6 +138,9 @@ def _two_field_protos(L):
     opened = [szp, sz, sz, u8p, sz, szp, C.POINTER(ci), cp, sz]   # claim counts, n_queries, n, openings, cap_each, lengths, status, reasons, reason_cap
     L.hg_pcs_open_batch.argtypes = L.hg_pcs_open_batch_bn254.argtypes = [vp, C.POINTER(vp), C.POINTER(u32p), C.POINTER(u64p), C.POINTER(u64p)] + opened
     L.hg_claims_open_batch.argtypes = L.hg_claims_open_batch_bn254.argtypes = [vp, C.POINTER(HgParams), C.POINTER(vp), vp, sz, u64p, sz] + opened
+    # the batch forms of the folded openings take what the unfolded batch forms take
+    L.hg_pcs_open_folded_batch.argtypes, L.hg_claims_open_folded_batch.argtypes = L.hg_pcs_open_batch.argtypes, L.hg_claims_open_batch.argtypes
+    L.hg_pcs_verify_folded_device_batch.argtypes, L.hg_claims_verify_folded_batch.argtypes = L.hg_pcs_verify_device_batch.argtypes, L.hg_claims_verify_batch.argtypes
 
 
 _lib = None
@@ -1576,8 +1580,8 @@ def _open_batch(call, cms, counts, n_queries, reason_cap, opening_bytes=pcs_open
     return [(None if status[i] else buf[i * cap:i * cap + lens[i]].tobytes(), raw[i * reason_cap:(i + 1) * reason_cap].split(b"\0", 1)[0].decode()) for i in range(n)]
 
 
-def _pcs_open_batch_of(sfx, arrays_of, opening_bytes, ctx, cms, claims_list, n_queries, reason_cap):
-    """hg_pcs_open_batch + sfx on claim lists that arrays_of turns into (table, points, values)"""
+def _pcs_open_batch_of(sfx, arrays_of, opening_bytes, ctx, cms, claims_list, n_queries, reason_cap, entry="hg_pcs_open_batch"):
+    """hg_pcs_open_batch + sfx (or the `entry` of its argument list) on claim lists that arrays_of turns into (table, points, values)"""
     if len(cms) != len(claims_list):
         raise ValueError(f"pcs_open_batch{sfx}: one claim list per commitment")
     m = max(len(cms), 1)
@@ -1585,16 +1589,16 @@ def _pcs_open_batch_of(sfx, arrays_of, opening_bytes, ctx, cms, claims_list, n_q
     tabs = (u32p * m)(*[C.cast(a[0], u32p) for a in arrays])
     pts = (u64p * m)(*[_ptr(a[1]) for a in arrays])
     vals = (u64p * m)(*[_ptr(a[2]) for a in arrays])
-    fn = getattr(lib(), "hg_pcs_open_batch" + sfx)
+    fn = getattr(lib(), entry + sfx)
     return _open_batch(lambda hs, nc, *rest: fn(_h(ctx), hs, tabs, pts, vals, nc, *rest), cms, [len(c) for c in claims_list], n_queries, reason_cap, opening_bytes)
 
 
-def _claims_open_batch_of(F, opening_bytes, ctx, params, cms, claims_list, n_queries, reason_cap):
-    """hg_claims_open_batch of field F"""
+def _claims_open_batch_of(F, opening_bytes, ctx, params, cms, claims_list, n_queries, reason_cap, entry="hg_claims_open_batch"):
+    """hg_claims_open_batch of field F (or the `entry` of its argument list)"""
     if len(cms) != len(claims_list):
         raise ValueError(f"claims_open_batch{F.SFX}: one {F.__name__} per commitment")
     claims, nc1, points, nco1, counts = _claims_batch_arrays(claims_list, F)
-    fn = getattr(lib(), "hg_claims_open_batch" + F.SFX)
+    fn = getattr(lib(), entry + F.SFX)
     return _open_batch(lambda hs, nc, *rest: fn(_h(ctx), C.byref(params), hs, claims, nc1, _ptr(points), nco1, nc, *rest), cms, list(counts)[:len(cms)], n_queries, reason_cap,
                        opening_bytes)
 
@@ -1610,6 +1614,23 @@ def claims_open_batch(ctx, params, cms, claims_list, n_queries=0, reason_cap=256
     """hg_claims_open_batch: the InputClaims claims_list[i] (what verify_public_batch returns; None stands for no claims) opened
     against the Commitment.secrets / secrets_batch handle cms[i]: [(bytes or None, reason)]."""
     return _claims_open_batch_of(InputClaims, pcs_opening_bytes, ctx, params, cms, claims_list, n_queries, reason_cap)
+
+
+def _folded_bytes(nvars, n_claims, n_queries, log2_row):
+    """pcs_folded_opening_bytes with the argument list of pcs_opening_bytes: the length does not depend on the claims"""
+    return pcs_folded_opening_bytes(nvars, n_queries, log2_row)
+
+
+def pcs_open_folded_batch(ctx, cms, claims_list, n_queries=0, reason_cap=256):
+    """hg_pcs_open_folded_batch: pcs_open_batch for folded openings (every claim list holds a claim): [(bytes or None, reason)] - the
+    bytes of cms[i].open_folded(claims_list[i]), or None and the text of its error where a value is not the evaluation."""
+    return _pcs_open_batch_of("", _pcs_claim_arrays, _folded_bytes, ctx, cms, claims_list, n_queries, reason_cap, "hg_pcs_open_folded_batch")
+
+
+def claims_open_folded_batch(ctx, params, cms, claims_list, n_queries=0, reason_cap=256):
+    """hg_claims_open_folded_batch: claims_open_batch for folded openings: [(bytes or None, reason)] - the bytes of
+    cms[i].open_claims_folded(params, claims_list[i])."""
+    return _claims_open_batch_of(InputClaims, _folded_bytes, ctx, params, cms, claims_list, n_queries, reason_cap, "hg_claims_open_folded_batch")
 
 
 def pcs_open_batch_bn254(ctx, cms, claims_list, n_queries=0, reason_cap=256):
@@ -1674,8 +1695,8 @@ def _pcs_verify_batch(call, roots, proofs, reason_cap):
     return [(res[i] == 0, raw[i * reason_cap:(i + 1) * reason_cap].split(b"\0", 1)[0].decode()) for i in range(n)]
 
 
-def _pcs_verify_batch_of(sfx, arrays_of, ctx, roots, nvars, claims_list, proofs, n_queries, log2_row, reason_cap):
-    """hg_pcs_verify_device_batch + sfx on claim lists that arrays_of turns into (table, points, values)"""
+def _pcs_verify_batch_of(sfx, arrays_of, ctx, roots, nvars, claims_list, proofs, n_queries, log2_row, reason_cap, entry="hg_pcs_verify_device_batch"):
+    """hg_pcs_verify_device_batch + sfx (or the `entry` of its argument list) on claim lists that arrays_of turns into (table, points, values)"""
     if not (len(roots) == len(claims_list) == len(proofs)):
         raise ValueError(f"pcs_verify_batch{sfx}: one root and one claim list per opening")
     m = max(len(proofs), 1)
@@ -1685,7 +1706,7 @@ def _pcs_verify_batch_of(sfx, arrays_of, ctx, roots, nvars, claims_list, proofs,
     pts = (u64p * m)(*[_ptr(a[1]) for a in arrays])
     vals = (u64p * m)(*[_ptr(a[2]) for a in arrays])
     counts = (C.c_size_t * m)(*[len(c) for c in claims_list])
-    fn = getattr(lib(), "hg_pcs_verify_device_batch" + sfx)
+    fn = getattr(lib(), entry + sfx)
     return _pcs_verify_batch(lambda rs, ps, lens, n, res, reasons, cap: fn(_h(ctx), rs, nv, len(nvars), log2_row, tabs, pts, vals, counts, n_queries, ps, lens, n,
                                                                             res, reasons, cap), roots, proofs, reason_cap)
 
@@ -1721,12 +1742,12 @@ def _claims_batch_arrays(claims_list, F=InputClaims):
     return claims, nc1, points, nco1, counts
 
 
-def _claims_verify_batch_of(F, ctx, params, roots, claims_list, openings, n_queries, log2_row, reason_cap):
-    """hg_claims_verify_batch of field F"""
+def _claims_verify_batch_of(F, ctx, params, roots, claims_list, openings, n_queries, log2_row, reason_cap, entry="hg_claims_verify_batch"):
+    """hg_claims_verify_batch of field F (or the `entry` of its argument list)"""
     if not (len(roots) == len(claims_list) == len(openings)):
         raise ValueError(f"claims_verify_batch{F.SFX}: one root and one {F.__name__} per opening")
     claims, nc1, points, nco1, counts = _claims_batch_arrays(claims_list, F)
-    fn = getattr(lib(), "hg_claims_verify_batch" + F.SFX)
+    fn = getattr(lib(), entry + F.SFX)
     return _pcs_verify_batch(lambda rs, ps, lens, n, res, reasons, cap: fn(_h(ctx), C.byref(params), rs, log2_row, claims, nc1, _ptr(points), nco1, counts, n_queries,
                                                                             ps, lens, n, res, reasons, cap), roots, openings, reason_cap)
 
@@ -1736,6 +1757,18 @@ def claims_verify_batch(ctx, params, roots, claims_list, openings, n_queries=0, 
     stands for no claims), packed into the layout hg_verify_public_batch writes: a list of (accepted, reason), the decisions of
     claims_verify for each item alone."""
     return _claims_verify_batch_of(InputClaims, ctx, params, roots, claims_list, openings, n_queries, log2_row, reason_cap)
+
+
+def pcs_verify_folded_batch(ctx, roots, nvars, claims_list, proofs, n_queries=0, log2_row=0, reason_cap=256):
+    """hg_pcs_verify_folded_device_batch: pcs_verify_batch for folded openings (every claim list holds a claim): a list of (accepted,
+    reason), the decisions of pcs_verify_folded for each item alone."""
+    return _pcs_verify_batch_of("", _pcs_claim_arrays, ctx, roots, nvars, claims_list, proofs, n_queries, log2_row, reason_cap, "hg_pcs_verify_folded_device_batch")
+
+
+def claims_verify_folded_batch(ctx, params, roots, claims_list, openings, n_queries=0, log2_row=0, reason_cap=256):
+    """hg_claims_verify_folded_batch: claims_verify_batch for folded openings: a list of (accepted, reason), the decisions of
+    claims_verify_folded for each item alone; an item without claims (None) is rejected, not an error."""
+    return _claims_verify_batch_of(InputClaims, ctx, params, roots, claims_list, openings, n_queries, log2_row, reason_cap, "hg_claims_verify_folded_batch")
 
 
 def pcs_verify_batch_bn254(ctx, roots, nvars, claims_list, proofs, n_queries=0, log2_row=0, reason_cap=256):

@@ -178,6 +178,15 @@ struct GlAbi {
     static std::vector<pcs::Opened> pcs_open_batch(const char* who, const char* single, hg_ctx* ctx, const std::vector<PcsOpenItem>& items, size_t Q) {
         return pcs::open_device_batch(who, single, ctx, items, Q);
     }
+    // the batch forms of the folded openings
+    static constexpr bool FOLDED_BATCH = true;
+    static size_t folded_opening_bytes(const pcs::Shape& sh, size_t Q) { return pcs::folded_opening_bytes(sh, Q); }
+    static std::vector<pcs::Opened> pcs_open_folded_batch(const char* who, const char* single, hg_ctx* ctx, const std::vector<PcsOpenItem>& items, size_t Q) {
+        return pcs::open_folded_device_batch(who, single, ctx, items, Q);
+    }
+    static std::vector<std::string> pcs_verify_folded_batch(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const std::vector<PcsItem>& items, size_t Q) {
+        return pcs::verify_folded_device_batch(who, ctx, sh, items, Q);
+    }
 };
 
 struct BnAbi {
@@ -251,6 +260,7 @@ struct BnAbi {
     static std::vector<pcs::Opened> pcs_open_batch(const char* who, const char* single, hg_ctx* ctx, const std::vector<PcsOpenItem>& items, size_t Q) {
         return bn::pcs_open_device_batch(who, single, ctx, items, Q);
     }
+    static constexpr bool FOLDED_BATCH = false;   // (folded openings have no batch forms over BN254 yet: the folded switches below are never set)
 };
 }  // namespace
 
@@ -752,19 +762,25 @@ static int claims_verify_entry(const char* who, bool device, hg_ctx* ctx, const 
 // error of the call writes no output): the device pass with its errors given the entry's name, results and reasons
 template <class A>
 static int pcs_verify_batch_tail(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const uint8_t* const* roots, const std::vector<std::vector<typename A::PcsClaim>>& cl,
-                                 size_t Q, const uint8_t* const* proofs, const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap) {
+                                 size_t Q, const uint8_t* const* proofs, const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap, bool folded = false) {
     const std::string w(who);
     if (!n) return 0;
     if (!ctx) throw Error(w + ": no context");
-    std::vector<typename A::PcsItem> items(n);
-    for (size_t i = 0; i < n; i++) items[i] = typename A::PcsItem{roots[i], &cl[i], proofs[i], lens[i]};
-    std::vector<std::string> why;
+    // folded: an item without a claim (hg_claims_verify_folded_batch lets it through) is rejected here and never reaches the device
+    std::vector<size_t> at;
+    for (size_t i = 0; i < n; i++)
+        if (!folded || !cl[i].empty()) at.push_back(i);
+    std::vector<typename A::PcsItem> items(at.size());
+    for (size_t k = 0; k < at.size(); k++) items[k] = typename A::PcsItem{roots[at[k]], &cl[at[k]], proofs[at[k]], lens[at[k]]};
+    std::vector<std::string> got, why(n, folded ? w + ": a folded opening needs a claim" : std::string());
     try {
-        why = A::pcs_verify_batch(who, ctx, sh, items, Q);
+        if constexpr (A::FOLDED_BATCH) got = folded ? A::pcs_verify_folded_batch(who, ctx, sh, items, Q) : A::pcs_verify_batch(who, ctx, sh, items, Q);
+        else got = A::pcs_verify_batch(who, ctx, sh, items, Q);
     } catch (const std::exception& e) {
         const std::string m = e.what();
         throw Error(m.rfind(w, 0) == 0 ? m : w + ": " + m);
     }
+    for (size_t k = 0; k < at.size(); k++) why[at[k]] = std::move(got[k]);
     return write_results(why, results, reasons, reason_cap);
 }
 
@@ -772,7 +788,7 @@ static int pcs_verify_batch_tail(const char* who, hg_ctx* ctx, const pcs::Shape&
 template <class A>
 static int pcs_verify_batch_entry(const char* who, hg_ctx* ctx, const uint8_t* const* roots, const uint32_t* nvars, size_t n_tables, size_t log2_row,
                                   const uint32_t* const* tables, const uint64_t* const* points, const uint64_t* const* values, const size_t* n_claims, size_t n_queries,
-                                  const uint8_t* const* proofs, const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap) {
+                                  const uint8_t* const* proofs, const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap, bool folded = false) {
     const std::string w(who);
     if (!nvars || (n && (!roots || !n_claims || !proofs || !lens || !results))) throw Error(w + ": null argument");
     const pcs::Shape sh = pcs::make_shape(who, nvars, n_tables, log2_row);
@@ -782,16 +798,17 @@ static int pcs_verify_batch_entry(const char* who, hg_ctx* ctx, const uint8_t* c
         const std::string at = w + ": index " + std::to_string(i);
         const bool has = n_claims[i] != 0;
         if (!roots[i] || (lens[i] && !proofs[i]) || (has && (!tables || !points || !values || !tables[i] || !points[i] || !values[i]))) throw Error(at + ": null argument");
+        if (folded && !has) throw Error(at + ": a folded opening needs a claim");
         cl[i] = pcs_claims<A>(at.c_str(), sh, has ? tables[i] : nullptr, has ? points[i] : nullptr, has ? values[i] : nullptr, n_claims[i]);
     }
-    return pcs_verify_batch_tail<A>(who, ctx, sh, roots, cl, Q, proofs, lens, n, results, reasons, reason_cap);
+    return pcs_verify_batch_tail<A>(who, ctx, sh, roots, cl, Q, proofs, lens, n, results, reasons, reason_cap, folded);
 }
 
 // hg_claims_verify_batch*: the claim and point blocks as hg_verify_public_batch* writes them, item i's under claims_verify_entry's mapping
 template <class A>
 static int claims_verify_batch_entry(const char* who, hg_ctx* ctx, const hg_params* params, const uint8_t* const* roots, size_t log2_row, const void* claims,
                                      size_t claim_cap_each, const uint64_t* points, size_t coord_cap_each, const size_t* n_claims, size_t n_queries,
-                                     const uint8_t* const* openings, const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap) {
+                                     const uint8_t* const* openings, const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap, bool folded = false) {
     const std::string w(who);
     if (!params || (n && (!roots || !n_claims || !openings || !lens || !results))) throw Error(w + ": null argument");
     Params p(*params);
@@ -812,7 +829,7 @@ static int claims_verify_batch_entry(const char* who, hg_ctx* ctx, const hg_para
         secrets_claims<A>(at.c_str(), p, in, n_claims[i], points ? points + A::WORDS * i * coord_cap_each : nullptr, table, pts, vals);
         cl[i] = pcs_claims<A>(at.c_str(), sh, table.data(), pts.data(), vals.data(), n_claims[i]);
     }
-    return pcs_verify_batch_tail<A>(who, ctx, sh, roots, cl, Q, openings, lens, n, results, reasons, reason_cap);
+    return pcs_verify_batch_tail<A>(who, ctx, sh, roots, cl, Q, openings, lens, n, results, reasons, reason_cap, folded);
 }
 
 // ---- the batch forms of commit and open (device only). An error of the call writes nothing: every item is checked before anything
@@ -900,12 +917,15 @@ static const pcs::Commitment* open_batch_handle(const char* who, const std::stri
 template <class A>
 static int pcs_open_batch_tail(const char* who, const char* single, hg_ctx* ctx, const std::vector<const pcs::Commitment*>& cms,
                                const std::vector<std::vector<typename A::PcsClaim>>& cl, size_t Q, uint8_t* openings, size_t cap_each, size_t* lens, int* status,
-                               char* reasons, size_t reason_cap) {
+                               char* reasons, size_t reason_cap, bool folded = false) {
     const std::string w(who);
     const size_t n = cms.size();
     if (!n) return 0;
     size_t need = 0;
-    for (size_t i = 0; i < n; i++) need = std::max(need, A::opening_bytes(cms[i]->sh, cl[i].size(), Q));
+    for (size_t i = 0; i < n; i++) {
+        if constexpr (A::FOLDED_BATCH) need = std::max(need, folded ? A::folded_opening_bytes(cms[i]->sh, Q) : A::opening_bytes(cms[i]->sh, cl[i].size(), Q));
+        else need = std::max(need, A::opening_bytes(cms[i]->sh, cl[i].size(), Q));
+    }
     if (cap_each < need) throw Error(w + ": the largest opening of the run has " + std::to_string(need) + " bytes, cap_each is " + std::to_string(cap_each));
     if (!ctx) throw Error(w + ": no context");
     std::vector<typename A::PcsOpenItem> items(n);
@@ -915,7 +935,8 @@ static int pcs_open_batch_tail(const char* who, const char* single, hg_ctx* ctx,
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = now();
     try {
-        got = A::pcs_open_batch(who, single, ctx, items, Q);
+        if constexpr (A::FOLDED_BATCH) got = folded ? A::pcs_open_folded_batch(who, single, ctx, items, Q) : A::pcs_open_batch(who, single, ctx, items, Q);
+        else got = A::pcs_open_batch(who, single, ctx, items, Q);
     } catch (const std::exception& e) {
         const std::string m = e.what();
         throw Error(m.rfind(w, 0) == 0 ? m : w + ": " + m);
@@ -944,7 +965,7 @@ static int pcs_open_batch_tail(const char* who, const char* single, hg_ctx* ctx,
 template <class A>
 static int pcs_open_batch_entry(const char* who, const char* single, hg_ctx* ctx, const void* const* commitments, const uint32_t* const* tables, const uint64_t* const* points,
                                 const uint64_t* const* values, const size_t* n_claims, size_t n_queries, size_t n, uint8_t* openings, size_t cap_each, size_t* lens,
-                                int* status, char* reasons, size_t reason_cap) {
+                                int* status, char* reasons, size_t reason_cap, bool folded = false) {
     const std::string w(who);
     if (n && (!commitments || !n_claims || !openings || !lens || !status)) throw Error(w + ": null argument");
     const size_t Q = pcs_queries(who, n_queries);
@@ -955,9 +976,10 @@ static int pcs_open_batch_entry(const char* who, const char* single, hg_ctx* ctx
         const bool has = n_claims[i] != 0;
         if (has && (!tables || !points || !values || !tables[i] || !points[i] || !values[i])) throw Error(at + ": null argument");
         cms[i] = open_batch_handle<A>(who, at, ctx, commitments[i], i ? cms[0] : nullptr);
+        if (folded && !has) throw Error(at + ": a folded opening needs a claim");
         cl[i] = pcs_claims<A>(at.c_str(), cms[i]->sh, has ? tables[i] : nullptr, has ? points[i] : nullptr, has ? values[i] : nullptr, n_claims[i]);
     }
-    return pcs_open_batch_tail<A>(who, single, ctx, cms, cl, Q, openings, cap_each, lens, status, reasons, reason_cap);
+    return pcs_open_batch_tail<A>(who, single, ctx, cms, cl, Q, openings, cap_each, lens, status, reasons, reason_cap, folded);
 }
 
 // hg_claims_open_batch*: the claim and point blocks as hg_verify_public_batch* writes them, item i's under claims_open_entry's mapping;
@@ -965,7 +987,7 @@ static int pcs_open_batch_entry(const char* who, const char* single, hg_ctx* ctx
 template <class A>
 static int claims_open_batch_entry(const char* who, const char* single, const char* mine, hg_ctx* ctx, const hg_params* params, const void* const* commitments,
                                    const void* claims, size_t claim_cap_each, const uint64_t* points, size_t coord_cap_each, const size_t* n_claims, size_t n_queries,
-                                   size_t n, uint8_t* openings, size_t cap_each, size_t* lens, int* status, char* reasons, size_t reason_cap) {
+                                   size_t n, uint8_t* openings, size_t cap_each, size_t* lens, int* status, char* reasons, size_t reason_cap, bool folded = false) {
     const std::string w(who);
     if (!params || (n && (!commitments || !n_claims || !openings || !lens || !status))) throw Error(w + ": null argument");
     Params p(*params);
@@ -979,6 +1001,7 @@ static int claims_open_batch_entry(const char* who, const char* single, const ch
         cms[i] = open_batch_handle<A>(who, at, ctx, commitments[i], i ? cms[0] : nullptr);
         if (cms[i]->sh.nvars.size() != nv.size() || !std::equal(nv.begin(), nv.end(), cms[i]->sh.nvars.begin(), [](uint32_t a, int b) { return (int)a == b; }))
             throw Error(at + ": the commitment is not " + mine + "'s for these parameters");
+        if (folded && !n_claims[i]) throw Error(at + ": a folded opening needs a claim");
         if (n_claims[i] > claim_cap_each) throw Error(at + ": " + std::to_string(n_claims[i]) + " claims in a block of " + std::to_string(claim_cap_each));
         const typename A::Wire* in = static_cast<const typename A::Wire*>(claims) + i * claim_cap_each;
         for (size_t j = 0; j < n_claims[i]; j++)
@@ -989,7 +1012,7 @@ static int claims_open_batch_entry(const char* who, const char* single, const ch
         secrets_claims<A>(at.c_str(), p, in, n_claims[i], points ? points + A::WORDS * i * coord_cap_each : nullptr, table, pts, vals);
         cl[i] = pcs_claims<A>(at.c_str(), cms[i]->sh, table.data(), pts.data(), vals.data(), n_claims[i]);
     }
-    return pcs_open_batch_tail<A>(who, single, ctx, cms, cl, Q, openings, cap_each, lens, status, reasons, reason_cap);
+    return pcs_open_batch_tail<A>(who, single, ctx, cms, cl, Q, openings, cap_each, lens, status, reasons, reason_cap, folded);
 }
 
 extern "C" {
@@ -2503,6 +2526,30 @@ int hg_claims_verify_folded(const hg_params* params, const uint8_t root[32], siz
 int hg_claims_verify_folded_device(hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points,
                                    size_t n_queries, const uint8_t* opening, size_t len) {
     HG_ENTRY(claims_verify_entry<GlAbi>("hg_claims_verify_folded_device", true, ctx, params, root, log2_row, claims, n, points, n_queries, opening, len, true))
+}
+
+int hg_pcs_open_folded_batch(hg_ctx* ctx, const void* const* commitments, const uint32_t* const* tables, const uint64_t* const* points, const uint64_t* const* values,
+                             const size_t* n_claims, size_t n_queries, size_t n, uint8_t* openings, size_t cap_each, size_t* lens, int* status, char* reasons, size_t reason_cap) {
+    HG_ENTRY(pcs_open_batch_entry<GlAbi>("hg_pcs_open_folded_batch", "hg_pcs_open_folded", ctx, commitments, tables, points, values, n_claims, n_queries, n, openings, cap_each, lens,
+                                         status, reasons, reason_cap, true))
+}
+int hg_claims_open_folded_batch(hg_ctx* ctx, const hg_params* params, const void* const* commitments, const void* claims, size_t claim_cap_each, const uint64_t* points,
+                                size_t coord_cap_each, const size_t* n_claims, size_t n_queries, size_t n, uint8_t* openings, size_t cap_each, size_t* lens, int* status,
+                                char* reasons, size_t reason_cap) {
+    HG_ENTRY(claims_open_batch_entry<GlAbi>("hg_claims_open_folded_batch", "hg_claims_open_folded", "hg_secrets_commit", ctx, params, commitments, claims, claim_cap_each, points,
+                                            coord_cap_each, n_claims, n_queries, n, openings, cap_each, lens, status, reasons, reason_cap, true))
+}
+int hg_pcs_verify_folded_device_batch(hg_ctx* ctx, const uint8_t* const* roots, const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* const* tables,
+                                      const uint64_t* const* points, const uint64_t* const* values, const size_t* n_claims, size_t n_queries, const uint8_t* const* proofs,
+                                      const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap) {
+    HG_ENTRY(pcs_verify_batch_entry<GlAbi>("hg_pcs_verify_folded_device_batch", ctx, roots, nvars, n_tables, log2_row, tables, points, values, n_claims, n_queries, proofs, lens, n,
+                                           results, reasons, reason_cap, true))
+}
+int hg_claims_verify_folded_batch(hg_ctx* ctx, const hg_params* params, const uint8_t* const* roots, size_t log2_row, const void* claims, size_t claim_cap_each,
+                                  const uint64_t* points, size_t coord_cap_each, const size_t* n_claims, size_t n_queries, const uint8_t* const* openings, const size_t* lens,
+                                  size_t n, int* results, char* reasons, size_t reason_cap) {
+    HG_ENTRY(claims_verify_batch_entry<GlAbi>("hg_claims_verify_folded_batch", ctx, params, roots, log2_row, claims, claim_cap_each, points, coord_cap_each, n_claims, n_queries,
+                                              openings, lens, n, results, reasons, reason_cap, true))
 }
 
 int hg_pcs_verify_device_batch(hg_ctx* ctx, const uint8_t* const* roots, const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* const* tables,

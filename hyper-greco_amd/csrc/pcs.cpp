@@ -404,15 +404,49 @@ std::unique_ptr<FoldSource> fold_source_host(const Commitment& cm, const std::ve
     return f;
 }
 
+FoldProver::FoldProver(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q)
+    : tr(start_transcript(sh, root, claims, Q, FOLD_TAG)), tail(sh.nvars.size(), e2_one()), rho(fold_rounds(sh)), claim(e2_zero()), r(e2_zero()) {
+    bpow = rho_powers(tr.squeeze(), claims.size());
+    for (size_t i = 0; i < claims.size(); i++) claim = e2_add(claim, e2_mul(bpow[i], claims[i].value));
+}
+bool FoldProver::round(const Shape& sh, size_t j, const E2 s[3], const std::vector<E2>& T, const std::vector<E2>& G) {
+    const size_t m = sh.nvars.size();
+    E2 k = e2_zero();   // the retired tables: K_t prod (1 - r_j') (1 - X)
+    for (size_t t = 0; t < m; t++)
+        if ((size_t)sh.nvars[t] <= j) k = e2_add(k, e2_mul(e2_mul(T[t], G[t]), tail[t]));
+    const E2 c0 = e2_add(s[0], k), c2 = s[2], c1 = e2_sub(e2_sub(s[1], s[0]), e2_add(s[2], k));
+    if (!e2_eq(e2_add(e2_add(c0, c0), e2_add(c1, c2)), claim)) return false;   // (round 0 is where a wrong value shows)
+    tr.write_e(c0);
+    tr.write_e(c1);
+    tr.write_e(c2);
+    r = rho[j] = tr.squeeze();
+    claim = e2_add(c0, e2_mul(r, e2_add(c1, e2_mul(r, c2))));
+    for (size_t t = 0; t < m; t++)
+        if ((size_t)sh.nvars[t] <= j) tail[t] = e2_mul(tail[t], e2_sub(e2_one(), r));
+    return true;
+}
+bool FoldProver::finish(const Shape& sh, const std::vector<E2>& T, const std::vector<E2>& G) {
+    const size_t m = sh.nvars.size();
+    E2 fin = e2_zero();
+    for (size_t t = 0; t < m; t++) fin = e2_add(fin, e2_mul(e2_mul(T[t], G[t]), tail[t]));
+    if (!e2_eq(fin, claim)) return false;
+    for (size_t t = 0; t < m; t++) tr.write_e(T[t]);
+    return true;
+}
+std::vector<CombineJob> FoldProver::body_jobs(const Shape& sh) {
+    const E2 delta = tr.squeeze();
+    std::vector<CombineJob> jobs(2);
+    jobs[0].row0 = 0; jobs[0].nrows = sh.R; jobs[0].w = rho_powers(tr.squeeze(), sh.R);
+    jobs[1].row0 = 0; jobs[1].nrows = sh.R; jobs[1].w = combined_weights(sh, rho, delta);
+    return jobs;
+}
+
 std::vector<uint8_t> open_folded(const char* who, const Commitment& cm, const std::vector<Claim>& claims, size_t Q) {
     const Shape& sh = cm.sh;
-    const size_t C = sh.C(), R = sh.R, n = claims.size(), m = sh.nvars.size(), V = fold_rounds(sh);
+    const size_t C = sh.C(), n = claims.size(), V = fold_rounds(sh);
     const std::string w(who);
     if (!n) throw Error(w + ": a folded opening needs a claim");
-    FsTranscript tr = start_transcript(sh, cm.root(), claims, Q, FOLD_TAG);
-    const std::vector<E2> bpow = rho_powers(tr.squeeze(), n);
-    E2 claim = e2_zero();
-    for (size_t i = 0; i < n; i++) claim = e2_add(claim, e2_mul(bpow[i], claims[i].value));
+    FoldProver P(sh, cm.root(), claims, Q);
     // a running claim the sums do not meet: a value is wrong. The claims one by one, as open checks them, to name the lowest
     auto refuse = [&]() {
         for (size_t i = 0; i < n; i++) {
@@ -431,43 +465,24 @@ std::vector<uint8_t> open_folded(const char* who, const Commitment& cm, const st
     };
     std::unique_ptr<FoldSource> src;
     try {
-        src = cm.ctx ? fold_source_device(cm, claims, bpow) : fold_source_host(cm, claims, bpow);
+        src = cm.ctx ? fold_source_device(cm, claims, P.bpow) : fold_source_host(cm, claims, P.bpow);
     } catch (const std::exception& e) {
         throw Error(w + ": " + e.what());
     }
-    std::vector<E2> tail(m, e2_one()), rho(V);
-    E2 r = e2_zero();
     for (size_t j = 0; j < V; j++) {
         E2 s[3];
-        src->step(j, r, s);
-        E2 k = e2_zero();   // the retired tables: K_t prod (1 - r_j') (1 - X)
-        for (size_t t = 0; t < m; t++)
-            if ((size_t)sh.nvars[t] <= j) k = e2_add(k, e2_mul(e2_mul(src->T[t], src->G[t]), tail[t]));
-        const E2 c0 = e2_add(s[0], k), c2 = s[2], c1 = e2_sub(e2_sub(s[1], s[0]), e2_add(s[2], k));
-        if (!e2_eq(e2_add(e2_add(c0, c0), e2_add(c1, c2)), claim)) refuse();   // (round 0 is where a wrong value shows)
-        tr.write_e(c0);
-        tr.write_e(c1);
-        tr.write_e(c2);
-        r = rho[j] = tr.squeeze();
-        claim = e2_add(c0, e2_mul(r, e2_add(c1, e2_mul(r, c2))));
-        for (size_t t = 0; t < m; t++)
-            if ((size_t)sh.nvars[t] <= j) tail[t] = e2_mul(tail[t], e2_sub(e2_one(), r));
+        src->step(j, P.r, s);
+        if (!P.round(sh, j, s, src->T, src->G)) refuse();
     }
-    src->step(V, r, nullptr);
-    E2 fin = e2_zero();
-    for (size_t t = 0; t < m; t++) fin = e2_add(fin, e2_mul(e2_mul(src->T[t], src->G[t]), tail[t]));
-    if (!e2_eq(fin, claim)) refuse();
-    for (size_t t = 0; t < m; t++) tr.write_e(src->T[t]);
+    src->step(V, P.r, nullptr);
+    if (!P.finish(sh, src->T, src->G)) refuse();
     src.reset();   // (the device form's scratch is the context's arena, which the row combinations take next)
-    const E2 delta = tr.squeeze();
-    std::vector<CombineJob> jobs(2);
-    jobs[0].row0 = 0; jobs[0].nrows = R; jobs[0].w = rho_powers(tr.squeeze(), R);
-    jobs[1].row0 = 0; jobs[1].nrows = R; jobs[1].w = combined_weights(sh, rho, delta);
+    const std::vector<CombineJob> jobs = P.body_jobs(sh);
     std::vector<E2> u(2 * C);
     if (cm.ctx) combine_device(cm, jobs, u.data()); else combine_host(cm, jobs, u.data());
-    write_u_and_queries(tr, cm, u, Q);
-    if (tr.bytes.size() != folded_opening_bytes(sh, Q)) throw Error(w + ": internal: opening length");
-    return std::move(tr.bytes);
+    write_u_and_queries(P.tr, cm, u, Q);
+    if (P.tr.bytes.size() != folded_opening_bytes(sh, Q)) throw Error(w + ": internal: opening length");
+    return std::move(P.tr.bytes);
 }
 
 FoldedHeader folded_header(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof) {

@@ -13,7 +13,8 @@
 // The statement digest of a bound proof (hg.h: "Bound proofs") lives here as well: its leaves are hashed by a kernel of the same
 // thread-a-sponge form as the column hashes, its levels are the commitment's.
 // The prover's side of a folded opening (pcs.hpp FoldSource) is here too: the kernel that builds g, the round kernels of the reduction
-// sum-check and their host driver FoldDev; the device verifier of a folded opening is verify_folded_flow of pcs_flow.hpp.
+// sum-check - written for a group of members, the single call a group of one - with their host drivers FoldDev (one opening) and
+// open_folded_device_batch (a run); the device verifiers of folded openings are verify_folded_flow and verify_batch_flow of pcs_flow.hpp.
 #include <omp.h>
 #include "pcs.hpp"
 #include "prover.hpp"
@@ -713,17 +714,33 @@ static unsigned fold_max_blocks() {
     const long v = e && *e ? atol(e) : (long)FOLD_MAX_BLOCKS;
     return (unsigned)std::max(1L, std::min(65535L, v));
 }
-struct FoldClaim { u64 lo_at, hi_at; u32 lo_bits, pad; };   // its two factor tables (elements of the staged factors): eq(z, x) = lo[x & (2^lo_bits - 1)] hi[x >> lo_bits]
+struct FoldClaim { u64 lo_at, hi_at; u32 lo_bits, pad; };   // its two factor tables (elements of its member's staged factors): eq(z, x) = lo[x & (2^lo_bits - 1)] hi[x >> lo_bits]
+// What a shape fixes for the g kernel of every member: the tables of two entries or more (the kernel's table numbers) and the one-word
+// tables, whose word goes to the scalars as it is
 struct FoldGTables {
-    u32 nt;
-    u32 lg[MAX_TABLES], claim0[MAX_TABLES + 1];   // v_t; the claims of table t are claim0[t] .. claim0[t+1] of the staged list
-    u64 at[MAX_TABLES];                           // s_t
+    u32 nt, n1;
+    u32 lg[MAX_TABLES], id1[MAX_TABLES];          // v_t; the number t of a one-word table
+    u64 at[MAX_TABLES], at1[MAX_TABLES];          // s_t; where a one-word table lies in the rows
 };
+// A member's block of the g kernel's staged copy (byte offsets): claim0[nt + 1] (the claims of kernel table t are claim0[t] .. claim0[t+1]
+// of its list: members differ in their claim counts, and a table may have none), its FoldClaim list, its factor tables
+struct FoldGMember { u64 claim0_at, claims_at, fac_at, pad; };
 struct FoldTables {
     u32 nt, vec;                                  // vec: every `in` of the rows is even, a pair of words is one 16-byte load
     u32 lg[MAX_TABLES], id[MAX_TABLES];           // log2 of a live table's entries at the input; its number t
     u64 in[MAX_TABLES], out[MAX_TABLES];          // where it lies in the input and where it goes in the output (entries)
 };
+// What differs by member (blockIdx.z) of a launch: where its raw rows lie (a handle may live in any slab), its challenge, and a fixed
+// stride into the group's g, buffer pairs and scalars. A group of one - the single call - carries its row base and its challenge in
+// the kernel arguments (rows == null, r == null): its launches need no table and no upload.
+struct FoldMembers {
+    const u64* const* rows;
+    const u64* rows0;
+    const E2* r;
+    E2 r0;
+    u64 g_stride, in_stride, out_stride, scal_stride;   // entries from a member to the next: g, the input pair, the output pair, the scalars
+};
+__device__ __forceinline__ const u64* fold_rows(const FoldMembers& M) { return M.rows ? M.rows[blockIdx.z] : M.rows0; }
 __device__ __forceinline__ E2 ld_e2(const E2* p) { const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(p); return e2(v.x, v.y); }
 __device__ __forceinline__ void st_e2(E2* p, E2 v) { *reinterpret_cast<ulonglong2*>(p) = make_ulonglong2(v.c0, v.c1); }
 __device__ __forceinline__ void ld_pair(const u64* p, bool vec, u64& a, u64& b) {
@@ -731,25 +748,33 @@ __device__ __forceinline__ void ld_pair(const u64* p, bool vec, u64& a, u64& b) 
     else { a = p[0]; b = p[1]; }
 }
 // g_t[x] = sum_{i on t} beta^i eq(z_i, x), every entry written once: a thread owns entry x and walks the table's claims, each a product of
-// two staged factors (beta^i lies in the low one)
-__global__ __launch_bounds__(FOLD_TPB) void k_pcsfold_g(const FoldGTables A, const char* __restrict__ stage, size_t fac_at, E2* __restrict__ g) {
+// two staged factors (beta^i lies in the low one). stage: G FoldGMember, then the members' blocks. The first workgroup of a member
+// also copies the words of its one-word tables to scal[2 t].
+__global__ __launch_bounds__(FOLD_TPB) void k_pcsfold_g(const FoldGTables A, const FoldMembers M, const char* __restrict__ stage, E2* __restrict__ g, E2* __restrict__ scal) {
     const unsigned t = blockIdx.y;
+    if (blockIdx.x == 0 && t == 0 && threadIdx.x < A.n1)
+        st_e2(scal + (size_t)blockIdx.z * M.scal_stride + 2 * A.id1[threadIdx.x], e2(fold_rows(M)[A.at1[threadIdx.x]], 0));
+    if (t >= A.nt) return;
     const size_t len = (size_t)1 << A.lg[t];
-    const FoldClaim* cl = reinterpret_cast<const FoldClaim*>(stage);
-    const E2* fac = reinterpret_cast<const E2*>(stage + fac_at);
+    const FoldGMember D = reinterpret_cast<const FoldGMember*>(stage)[blockIdx.z];
+    const u32* claim0 = reinterpret_cast<const u32*>(stage + D.claim0_at);
+    const FoldClaim* cl = reinterpret_cast<const FoldClaim*>(stage + D.claims_at);
+    const E2* fac = reinterpret_cast<const E2*>(stage + D.fac_at);
+    const unsigned first = claim0[t], last = claim0[t + 1];
+    E2* G = g + (size_t)blockIdx.z * M.g_stride + A.at[t];
     for (size_t x = (size_t)blockIdx.x * FOLD_TPB + threadIdx.x; x < len; x += (size_t)gridDim.x * FOLD_TPB) {
         WE2 acc = we2_zero();
         E2 sum = e2_zero();
         int trips = 0;
-        for (unsigned i = A.claim0[t]; i < A.claim0[t + 1]; i++) {
+        for (unsigned i = first; i < last; i++) {
             const FoldClaim d = cl[i];
             we2_mac(acc, ld_e2(fac + d.lo_at + (x & (((size_t)1 << d.lo_bits) - 1))), ld_e2(fac + d.hi_at + (x >> d.lo_bits)));
             if (++trips == WFLUSH_TRIPS) { sum = e2_add(sum, we2_reduce(acc)); acc = we2_zero(); trips = 0; }
         }
-        st_e2(g + A.at[t] + x, e2_add(sum, we2_reduce(acc)));
+        st_e2(G + x, e2_add(sum, we2_reduce(acc)));
     }
 }
-// the three sums of a thread -> those of its workgroup at out[3 b .. 3 b + 3), b = its number in the grid; every thread calls it
+// the three sums of a thread -> those of its workgroup at out[3 b .. 3 b + 3), b = its number in the grid (members outermost); every thread calls it
 __device__ __forceinline__ void fold_block_sums(E2 (&s)[3], E2* __restrict__ out) {
     __shared__ E2 part[FOLD_TPB / 64][3];
 #pragma unroll
@@ -762,16 +787,16 @@ __device__ __forceinline__ void fold_block_sums(E2 (&s)[3], E2* __restrict__ out
     if (threadIdx.x < 3) {
         E2 v = part[0][threadIdx.x];
         for (int w = 1; w < FOLD_TPB / 64; w++) v = e2_add(v, part[w][threadIdx.x]);
-        out[3 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x) + threadIdx.x] = v;
+        out[3 * (((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) + threadIdx.x] = v;
     }
 }
 // Round 0: nothing to fold, the table entries are base-field words. A unit is a pair (T0, T1), (g0, g1):
 // s(0) += g0 T0, s(1) += g1 T1, c2 += (g1 - g0) (T1 - T0), an E x F product each
-__global__ __launch_bounds__(FOLD_TPB) void k_pcsfold_round0(const FoldTables A, const u64* __restrict__ rows, const E2* __restrict__ g, E2* __restrict__ partial) {
+__global__ __launch_bounds__(FOLD_TPB) void k_pcsfold_round0(const FoldTables A, const FoldMembers M, const E2* __restrict__ g, E2* __restrict__ partial) {
     const unsigned t = blockIdx.y;
     const size_t pairs = (size_t)1 << (A.lg[t] - 1);
-    const u64* T = rows + A.in[t];
-    const E2* G = g + A.in[t];
+    const u64* T = fold_rows(M) + A.in[t];
+    const E2* G = g + (size_t)blockIdx.z * M.g_stride + A.in[t];
     W2 a = w2_zero(), b = w2_zero(), c = w2_zero();
     int trips = 0;
     for (size_t u = (size_t)blockIdx.x * FOLD_TPB + threadIdx.x; u < pairs; u += (size_t)gridDim.x * FOLD_TPB) {
@@ -787,24 +812,26 @@ __global__ __launch_bounds__(FOLD_TPB) void k_pcsfold_round0(const FoldTables A,
     fold_block_sums(s, partial);
 }
 // Round j >= 1. A unit is four adjacent entries of T and of g: folded by r = r_{j-1} into two of each, which are stored and enter the sums
-// of round j as E x E products. BASE (round 1): the entries of T are the words of the raw rows. A table of two entries is folded into its
-// two scalars at scal[2 id], scal[2 id + 1] by one thread and enters no sum.
+// of round j as E x E products. BASE (round 1): the entries of T are the words of the raw rows and gin is g (in_stride = g_stride). A
+// table of two entries is folded into its two scalars at scal[2 id], scal[2 id + 1] of its member by one thread and enters no sum.
 template <bool BASE>
-__global__ __launch_bounds__(FOLD_TPB) void k_pcsfold_round(const FoldTables A, const u64* __restrict__ rows, const E2* __restrict__ tin, const E2* __restrict__ gin,
-                                                            E2* __restrict__ tout, E2* __restrict__ gout, const E2 r, E2* __restrict__ scal, E2* __restrict__ partial) {
+__global__ __launch_bounds__(FOLD_TPB) void k_pcsfold_round(const FoldTables A, const FoldMembers M, const E2* __restrict__ tin, const E2* __restrict__ gin,
+                                                            E2* __restrict__ tout, E2* __restrict__ gout, E2* __restrict__ scal, E2* __restrict__ partial) {
     const unsigned t = blockIdx.y, lg = A.lg[t];
-    const FoldR f = fold_r(r);
-    const E2* G = gin + A.in[t];
+    const FoldR f = fold_r(M.r ? M.r[blockIdx.z] : M.r0);
+    const size_t in_at = (size_t)blockIdx.z * M.in_stride + A.in[t];
+    const u64* rows = BASE ? fold_rows(M) + A.in[t] : nullptr;
+    const E2* G = gin + in_at;
     // T[2i] + r (T[2i+1] - T[2i])
     auto fold_t = [&](size_t i) {
         if constexpr (BASE) {
             u64 t0, t1;
-            ld_pair(rows + A.in[t] + 2 * i, A.vec, t0, t1);
+            ld_pair(rows + 2 * i, A.vec, t0, t1);
             const u64 d = gl_sub(t1, t0);
             return e2(wreduce(wacc_mul_init(t0, f.r0, d)), gl_mul(f.r1, d));
         } else {
-            const E2 t0 = ld_e2(tin + A.in[t] + 2 * i);
-            return e2_fold_wide(t0, e2_sub(ld_e2(tin + A.in[t] + 2 * i + 1), t0), f);
+            const E2 t0 = ld_e2(tin + in_at + 2 * i);
+            return e2_fold_wide(t0, e2_sub(ld_e2(tin + in_at + 2 * i + 1), t0), f);
         }
     };
     auto fold_g = [&](size_t i) {
@@ -815,13 +842,14 @@ __global__ __launch_bounds__(FOLD_TPB) void k_pcsfold_round(const FoldTables A, 
     E2 s[3] = {e2_zero(), e2_zero(), e2_zero()};
     if (lg == 1) {
         if (blockIdx.x == 0 && threadIdx.x == 0) {
-            st_e2(scal + 2 * A.id[t], fold_t(0));
-            st_e2(scal + 2 * A.id[t] + 1, fold_g(0));
+            E2* sc = scal + (size_t)blockIdx.z * M.scal_stride + 2 * A.id[t];
+            st_e2(sc, fold_t(0));
+            st_e2(sc + 1, fold_g(0));
         }
     } else {
-        const size_t units = (size_t)1 << (lg - 2);
-        E2* To = tout + A.out[t];
-        E2* Go = gout + A.out[t];
+        const size_t units = (size_t)1 << (lg - 2), out_at = (size_t)blockIdx.z * M.out_stride + A.out[t];
+        E2* To = tout + out_at;
+        E2* Go = gout + out_at;
         int trips = 0;
         for (size_t u = (size_t)blockIdx.x * FOLD_TPB + threadIdx.x; u < units; u += (size_t)gridDim.x * FOLD_TPB) {
             const E2 t0 = fold_t(2 * u), t1 = fold_t(2 * u + 1), g0 = fold_g(2 * u), g1 = fold_g(2 * u + 1);
@@ -842,16 +870,144 @@ __global__ __launch_bounds__(FOLD_TPB) void k_pcsfold_round(const FoldTables A, 
     s[0] = e2_add(s[0], we2_reduce(a)); s[1] = e2_add(s[1], we2_reduce(b)); s[2] = e2_add(s[2], we2_reduce(c));
     fold_block_sums(s, partial);
 }
-// one workgroup: out[k] = sum_b partial[3 b + k]
+// one workgroup a member (blockIdx.x): out[3 member + k] = sum_b partial[3 (member blocks + b) + k]
 __global__ __launch_bounds__(FOLD_TPB) void k_pcsfold_sum(const E2* __restrict__ partial, size_t blocks, E2* __restrict__ out) {
+    const E2* mine = partial + 3 * blocks * blockIdx.x;
     E2 s[3] = {e2_zero(), e2_zero(), e2_zero()};
     for (size_t b = threadIdx.x; b < blocks; b += FOLD_TPB)
-        for (int k = 0; k < 3; k++) s[k] = e2_add(s[k], ld_e2(partial + 3 * b + k));
+        for (int k = 0; k < 3; k++) s[k] = e2_add(s[k], ld_e2(mine + 3 * b + k));
     fold_block_sums(s, out);
 }
 
-// The device form of FoldSource. Scratch from the context's arena (reset here; the handle's matrices are its own): g (16 bytes a table
-// entry), the two buffer pairs (a half and a quarter of that for T and for g each), the partials, the sums and the scalars.
+// ---- what the single call (FoldDev) and the pass over a group (open_folded_device_batch) share on the host: the geometry a shape
+// fixes, a member's block of the g kernel's staged copy, the launches of the g kernel and of a round
+static FoldGTables fold_g_tables(const Shape& sh, size_t* max_len) {
+    FoldGTables A;
+    memset(&A, 0, sizeof(A));
+    *max_len = 1;
+    for (size_t t = 0; t < sh.nvars.size(); t++) {
+        const size_t v = (size_t)sh.nvars[t], at = sh.off[t] << sh.c;
+        if (v == 0) { A.id1[A.n1] = (u32)t; A.at1[A.n1] = (u64)at; A.n1++; continue; }   // a scalar from the start: T_t() is the word, g_t() = sum beta^i
+        A.lg[A.nt] = (u32)v;
+        A.at[A.nt] = (u64)at;
+        A.nt++;
+        *max_len = std::max(*max_len, (size_t)1 << v);
+    }
+    return A;
+}
+// the bytes of a member's block, a multiple of 16
+static size_t fold_gblock_bytes(const Shape& sh, const FoldGTables& A, const std::vector<Claim>& claims) {
+    size_t nc = 0, fac = 0;
+    for (const Claim& cl : claims) {
+        const size_t v = (size_t)sh.nvars[cl.table], lo_bits = (v + 1) / 2;
+        if (v == 0) continue;
+        nc++;
+        fac += ((size_t)1 << lo_bits) + ((size_t)1 << (v - lo_bits));
+    }
+    auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    return up((A.nt + 1) * sizeof(u32)) + up(nc * sizeof(FoldClaim)) + fac * sizeof(E2);
+}
+// writes the block at byte `at` (a multiple of 16) of the staged copy and its descriptor; G1[t] = g_t() of the one-word tables
+static void fold_gblock_fill(char* stage, FoldGMember& d, size_t at, const Shape& sh, const FoldGTables& A, const std::vector<Claim>& claims, const std::vector<E2>& bpow,
+                             std::vector<E2>& G1) {
+    auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    size_t nc = 0;
+    for (const Claim& cl : claims) nc += sh.nvars[cl.table] != 0;
+    d.claim0_at = at;
+    d.claims_at = d.claim0_at + up((A.nt + 1) * sizeof(u32));
+    d.fac_at = d.claims_at + up(nc * sizeof(FoldClaim));
+    d.pad = 0;
+    u32* claim0 = reinterpret_cast<u32*>(stage + d.claim0_at);
+    FoldClaim* list = reinterpret_cast<FoldClaim*>(stage + d.claims_at);
+    E2* fac = reinterpret_cast<E2*>(stage + d.fac_at);
+    size_t k = 0, f = 0, kt = 0;   // claims and factors written; the kernel's table number
+    claim0[0] = 0;
+    G1.assign(sh.nvars.size(), e2_zero());
+    for (size_t t = 0; t < sh.nvars.size(); t++) {
+        const size_t v = (size_t)sh.nvars[t], lo_bits = (v + 1) / 2;
+        for (size_t i = 0; i < claims.size(); i++) {
+            if (claims[i].table != t) continue;
+            if (v == 0) { G1[t] = e2_add(G1[t], bpow[i]); continue; }
+            std::vector<E2> lo = eq_table(claims[i].point.data(), lo_bits);
+            const std::vector<E2> hi = eq_table(claims[i].point.data() + lo_bits, v - lo_bits);
+            for (E2& x : lo) x = e2_mul(x, bpow[i]);
+            list[k++] = FoldClaim{(u64)f, (u64)(f + lo.size()), (u32)lo_bits, 0};
+            memcpy(fac + f, lo.data(), lo.size() * sizeof(E2));
+            memcpy(fac + f + lo.size(), hi.data(), hi.size() * sizeof(E2));
+            f += lo.size() + hi.size();
+        }
+        if (v != 0) claim0[++kt] = (u32)k;
+    }
+}
+// the workgroups a table of a launch over nt tables of G members whose largest has `units` units: max_blocks bounds the launch as a whole
+static unsigned fold_blocks_of(unsigned max_blocks, size_t units, size_t nt, size_t G) {
+    const size_t cap = std::max<size_t>(1, max_blocks / (nt * G));
+    return (unsigned)std::max<size_t>(1, std::min(cap, (units + FOLD_TPB - 1) / FOLD_TPB));
+}
+// the tables live in step j and where they lie; retire: one of them is folded to its scalars; units: those of the largest; entries: in all
+static FoldTables fold_tables(const Shape& sh, size_t j, bool* retire, size_t* max_units, size_t* entries) {
+    FoldTables A;
+    memset(&A, 0, sizeof(A));
+    A.vec = sh.c >= 1;
+    *retire = false;
+    *max_units = 1;
+    *entries = 0;
+    for (size_t t = 0; t < sh.nvars.size(); t++) {
+        const size_t v = (size_t)sh.nvars[t], at = sh.off[t] << sh.c;
+        if (v == 0 || v < j) continue;   // a scalar already
+        const size_t lg = j == 0 ? v : v - (j - 1);
+        A.lg[A.nt] = (u32)lg;
+        A.id[A.nt] = (u32)t;
+        A.in[A.nt] = j == 0 ? at : at >> (j - 1);
+        A.out[A.nt] = at >> j;
+        A.nt++;
+        *retire |= j > 0 && lg == 1;
+        *max_units = std::max(*max_units, j == 0 ? (size_t)1 << (lg - 1) : lg == 1 ? 1 : (size_t)1 << (lg - 2));
+        *entries += (size_t)1 << lg;
+    }
+    return A;
+}
+// the arena buffers of G reductions: g (16 bytes a table entry), the two buffer pairs (a half and a quarter of that for T and for g
+// each, member after member), the partials, the sums and the scalars
+struct FoldBufs {
+    E2 *g, *t[2], *gg[2], *scal, *partial, *sums;
+    size_t stride[2];   // entries a member of pair 0 and of pair 1
+};
+static FoldBufs fold_alloc(hg_ctx* ctx, const Shape& sh, size_t G, unsigned max_blocks) {
+    const size_t W = sh.R << sh.c, m = sh.nvars.size();
+    FoldBufs b;
+    b.stride[0] = W / 2 + 1;
+    b.stride[1] = W / 4 + 1;
+    b.g = ctx->alloc_n<E2>(G * W);
+    for (int p = 0; p < 2; p++) {
+        b.t[p] = ctx->alloc_n<E2>(G * b.stride[p]);
+        b.gg[p] = ctx->alloc_n<E2>(G * b.stride[p]);
+    }
+    b.scal = ctx->alloc_n<E2>(G * 2 * m);
+    b.partial = ctx->alloc_n<E2>(3 * ((size_t)max_blocks + MAX_TABLES * G));
+    b.sums = ctx->alloc_n<E2>(3 * G);
+    return b;
+}
+// the launch of step j over G members (A.nt >= 1) and, `sums`, of the workgroup a member that adds its partials
+static void fold_launch(hipStream_t st, unsigned max_blocks, const Shape& sh, size_t j, const FoldTables& A, size_t max_units, size_t G, FoldMembers M, const FoldBufs& b,
+                        bool sums) {
+    const size_t W = sh.R << sh.c;
+    const dim3 grid(fold_blocks_of(max_blocks, max_units, A.nt, G), A.nt, (unsigned)G);
+    M.g_stride = W;
+    M.scal_stride = 2 * sh.nvars.size();
+    M.in_stride = j <= 1 ? W : b.stride[j & 1];
+    M.out_stride = j == 0 ? 0 : b.stride[(j - 1) & 1];
+    if (j == 0) k_pcsfold_round0<<<grid, FOLD_TPB, 0, st>>>(A, M, b.g, b.partial);
+    else if (j == 1) k_pcsfold_round<true><<<grid, FOLD_TPB, 0, st>>>(A, M, nullptr, b.g, b.t[0], b.gg[0], b.scal, b.partial);
+    else k_pcsfold_round<false><<<grid, FOLD_TPB, 0, st>>>(A, M, b.t[j & 1], b.gg[j & 1], b.t[(j - 1) & 1], b.gg[(j - 1) & 1], b.scal, b.partial);
+    if (sums) k_pcsfold_sum<<<(unsigned)G, FOLD_TPB, 0, st>>>(b.partial, (size_t)grid.x * grid.y, b.sums);
+}
+// the bytes step j moves over `entries` table entries: round 0 reads 8 + 16 an entry, round 1 reads them and writes 16 + 16 for every
+// two, a later round reads 32 and writes 16
+static double fold_step_bytes(size_t j, size_t entries) { return (double)entries * (j == 0 ? 24 : j == 1 ? 40 : 48); }
+
+// The device form of FoldSource: a group of one through the kernels above. Scratch from the context's arena (reset here; the handle's
+// matrices are its own).
 struct FoldDev : FoldSource {
     const Commitment& cm;
     hg_ctx* ctx;
@@ -859,8 +1015,10 @@ struct FoldDev : FoldSource {
     int cls;
     size_t n_claims;
     unsigned max_blocks;
-    E2 *d_g, *d_t[2], *d_gg[2], *d_scal, *d_partial, *d_sums;
-    std::vector<E2> h_scal;
+    FoldBufs buf;
+    FoldMembers mem;
+    bool one_word;          // the shape has one-word tables: their words come back with step 0
+    std::vector<E2> h_scal, G1;
     E2 h_sums[3];
 
     FoldDev(const Commitment& cm_, const std::vector<Claim>& claims, const std::vector<E2>& bpow) : cm(cm_), ctx(cm_.ctx), n_claims(claims.size()) {
@@ -875,108 +1033,57 @@ struct FoldDev : FoldSource {
         T.assign(m, e2_zero());
         G.assign(m, e2_zero());
         h_scal.assign(2 * m, e2_zero());
-        // the claims in table order; per claim the two factor tables, beta^i in the low one
-        FoldGTables A;
-        memset(&A, 0, sizeof(A));
-        std::vector<FoldClaim> list;
-        std::vector<E2> fac;
-        size_t max_len = 0;
-        for (size_t t = 0; t < m; t++) {
-            const size_t v = (size_t)sh.nvars[t], lo_bits = (v + 1) / 2;
-            if (v == 0) {   // a table of one word is a scalar from the start: T_t() is the word, g_t() = sum beta^i
-                u64 word = 0;
-                hip_check(hipMemcpyAsync(&word, cm.d_rows + (sh.off[t] << sh.c), 8, hipMemcpyDeviceToHost, st), "download a one-word table");
-                hip_check(hipStreamSynchronize(st), "hg_pcs_open_folded: sync");
-                T[t] = e2(word, 0);
-                for (size_t i = 0; i < claims.size(); i++)
-                    if (claims[i].table == t) G[t] = e2_add(G[t], bpow[i]);
-                continue;
-            }
-            for (size_t i = 0; i < claims.size(); i++) {
-                if (claims[i].table != t) continue;
-                std::vector<E2> lo = eq_table(claims[i].point.data(), lo_bits);
-                const std::vector<E2> hi = eq_table(claims[i].point.data() + lo_bits, v - lo_bits);
-                for (E2& x : lo) x = e2_mul(x, bpow[i]);
-                list.push_back(FoldClaim{(u64)fac.size(), (u64)(fac.size() + lo.size()), (u32)lo_bits, 0});
-                fac.insert(fac.end(), lo.begin(), lo.end());
-                fac.insert(fac.end(), hi.begin(), hi.end());
-            }
-            A.lg[A.nt] = (u32)v;
-            A.at[A.nt] = (u64)(sh.off[t] << sh.c);
-            A.nt++;   // (the kernel's table number, which skips the one-word tables; claim0[0] = 0)
-            A.claim0[A.nt] = (u32)list.size();
-            max_len = std::max(max_len, (size_t)1 << v);
-        }
-        const size_t fac_at = (list.size() * sizeof(FoldClaim) + 15) & ~(size_t)15;
-        std::vector<char> stage(fac_at + fac.size() * sizeof(E2) + 16);
-        if (!list.empty()) memcpy(stage.data(), list.data(), list.size() * sizeof(FoldClaim));
-        if (!fac.empty()) memcpy(stage.data() + fac_at, fac.data(), fac.size() * sizeof(E2));
+        size_t max_len;
+        const FoldGTables A = fold_g_tables(sh, &max_len);
+        one_word = A.n1 != 0;
+        memset(&mem, 0, sizeof(mem));
+        mem.rows0 = cm.d_rows;
+        mem.g_stride = W;
+        mem.scal_stride = 2 * m;
+        std::vector<char> stage(sizeof(FoldGMember) + fold_gblock_bytes(sh, A, claims) + 16);
+        static_assert(sizeof(FoldGMember) % 16 == 0, "a member's block starts at a multiple of 16");
+        FoldGMember d;
+        fold_gblock_fill(stage.data(), d, sizeof(FoldGMember), sh, A, claims, bpow, G1);
+        memcpy(stage.data(), &d, sizeof(d));
         try {
-            d_g = ctx->alloc_n<E2>(W);
-            d_t[0] = ctx->alloc_n<E2>(W / 2 + 1);
-            d_gg[0] = ctx->alloc_n<E2>(W / 2 + 1);
-            d_t[1] = ctx->alloc_n<E2>(W / 4 + 1);
-            d_gg[1] = ctx->alloc_n<E2>(W / 4 + 1);
-            d_scal = ctx->alloc_n<E2>(2 * m);
-            d_partial = ctx->alloc_n<E2>(3 * ((size_t)max_blocks + MAX_TABLES));
-            d_sums = ctx->alloc_n<E2>(3);
+            buf = fold_alloc(ctx, sh, 1, max_blocks);
         } catch (const std::exception& e) {
             throw Error(std::string("the context's arena cannot hold the reduction (") + e.what() + ")");
         }
-        if (!A.nt) return;
         char* d_stage = ctx->alloc_n<char>(stage.size());
         hip_check(hipMemcpyAsync(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, st), "upload factor tables");
-        ctx->prof_begin(cls, (double)W * 16 + (double)fac.size() * 16);
-        k_pcsfold_g<<<dim3(blocks_of(max_len, A.nt), A.nt), FOLD_TPB, 0, st>>>(A, d_stage, fac_at, d_g);
+        ctx->prof_begin(cls, (double)W * 16 + (double)stage.size());
+        k_pcsfold_g<<<dim3(fold_blocks_of(max_blocks, max_len, std::max<size_t>(A.nt, 1), 1), std::max<unsigned>(A.nt, 1)), FOLD_TPB, 0, st>>>(A, mem, d_stage, buf.g, buf.scal);
         ctx->prof_end();
         hip_check(hipStreamSynchronize(st), "hg_pcs_open_folded: sync");   // (the staged copy is a local)
         hip_check(hipGetLastError(), "hg_pcs_open_folded: launch");
     }
-    // the workgroups a table of a launch over nt tables whose largest has `units` units
-    unsigned blocks_of(size_t units, unsigned nt) const {
-        const size_t cap = std::max<size_t>(1, max_blocks / nt);
-        return (unsigned)std::max<size_t>(1, std::min(cap, (units + FOLD_TPB - 1) / FOLD_TPB));
-    }
     void step(size_t j, E2 r, E2 s[3]) override {
         const Shape& sh = cm.sh;
         const size_t m = sh.nvars.size(), V = fold_rounds(sh);
-        FoldTables A;
-        memset(&A, 0, sizeof(A));
-        A.vec = sh.c >= 1;
-        bool retire = false;
-        size_t max_units = 1, entries = 0;
-        for (size_t t = 0; t < m; t++) {
-            const size_t v = (size_t)sh.nvars[t], at = sh.off[t] << sh.c;
-            if (v == 0 || v < j) continue;   // a scalar already
-            const size_t lg = j == 0 ? v : v - (j - 1);
-            A.lg[A.nt] = (u32)lg;
-            A.id[A.nt] = (u32)t;
-            A.in[A.nt] = j == 0 ? at : at >> (j - 1);
-            A.out[A.nt] = at >> j;
-            A.nt++;
-            retire |= j > 0 && lg == 1;
-            max_units = std::max(max_units, j == 0 ? (size_t)1 << (lg - 1) : lg == 1 ? 1 : (size_t)1 << (lg - 2));
-            entries += (size_t)1 << lg;
-        }
+        bool retire;
+        size_t max_units, entries;
+        const FoldTables A = fold_tables(sh, j, &retire, &max_units, &entries);
+        retire |= j == 0 && one_word;
         if (s) s[0] = s[1] = s[2] = e2_zero();
-        if (!A.nt) return;
-        const dim3 grid(blocks_of(max_units, A.nt), A.nt);
+        if (!A.nt && !retire) return;
         ctx->prof_stream = st;
-        // round 0 reads 8 + 16 bytes an entry, round 1 reads them and writes 16 + 16 for every two, a later round reads 32 and writes 16
-        ctx->prof_begin(cls, (double)entries * (j == 0 ? 24 : j == 1 ? 40 : 48));
-        if (j == 0) k_pcsfold_round0<<<grid, FOLD_TPB, 0, st>>>(A, cm.d_rows, d_g, d_partial);
-        else if (j == 1) k_pcsfold_round<true><<<grid, FOLD_TPB, 0, st>>>(A, cm.d_rows, nullptr, d_g, d_t[0], d_gg[0], r, d_scal, d_partial);
-        else k_pcsfold_round<false><<<grid, FOLD_TPB, 0, st>>>(A, nullptr, d_t[j & 1], d_gg[j & 1], d_t[(j - 1) & 1], d_gg[(j - 1) & 1], r, d_scal, d_partial);
-        if (s) k_pcsfold_sum<<<1, FOLD_TPB, 0, st>>>(d_partial, (size_t)grid.x * grid.y, d_sums);
-        ctx->prof_end();
-        if (s) hip_check(hipMemcpyAsync(h_sums, d_sums, sizeof(h_sums), hipMemcpyDeviceToHost, st), "download the round's sums");
-        if (retire) hip_check(hipMemcpyAsync(h_scal.data(), d_scal, 2 * m * sizeof(E2), hipMemcpyDeviceToHost, st), "download the retired tables' scalars");
+        if (A.nt) {
+            mem.r0 = r;
+            ctx->prof_begin(cls, fold_step_bytes(j, entries));
+            fold_launch(st, max_blocks, sh, j, A, max_units, 1, mem, buf, s != nullptr);
+            ctx->prof_end();
+            if (s) hip_check(hipMemcpyAsync(h_sums, buf.sums, sizeof(h_sums), hipMemcpyDeviceToHost, st), "download the round's sums");
+        }
+        if (retire) hip_check(hipMemcpyAsync(h_scal.data(), buf.scal, 2 * m * sizeof(E2), hipMemcpyDeviceToHost, st), "download the retired tables' scalars");
         hip_check(hipStreamSynchronize(st), "hg_pcs_open_folded: sync");
         hip_check(hipGetLastError(), "hg_pcs_open_folded: launch");
         ctx->prof_collect();
-        if (s) memcpy(s, h_sums, sizeof(h_sums));
-        for (size_t t = 0; t < m; t++)
+        if (s && A.nt) memcpy(s, h_sums, sizeof(h_sums));
+        for (size_t t = 0; t < m; t++) {
+            if (j == 0 && sh.nvars[t] == 0) { T[t] = h_scal[2 * t]; G[t] = G1[t]; }
             if (j > 0 && (size_t)sh.nvars[t] == j) { T[t] = h_scal[2 * t]; G[t] = h_scal[2 * t + 1]; }
+        }
         if (j == V && hg_debug("plan"))   // (read at every call: the tests switch it per case)
             fprintf(stderr, "[hg plan] pcsfold V=%zu dev_rounds=%zu host_rounds=0 tables=%zu claims=%zu\n", V, V, m, n_claims);
     }
@@ -1122,6 +1229,325 @@ std::vector<Commitment*> commit_device_batch(const char* who, hg_ctx* ctx, const
 }
 std::vector<Opened> open_device_batch(const char* who, const char* single, hg_ctx* ctx, const std::vector<OpenItem>& items, size_t Q) {
     return open_batch_flow<GlPcs>(who, single, ctx, items, Q);
+}
+
+std::vector<std::string> verify_folded_device_batch(const char* who, hg_ctx* ctx, const Shape& sh, const std::vector<VerifyItem>& items, size_t Q) {
+    return verify_batch_flow<GlPcs>(who, ctx, sh, items, Q, true);
+}
+
+// ---- hg_pcs_open_folded_batch: the device opener of a run of folded openings. A group (cut_groups over what a member takes: its g, its
+// two buffer pairs, its blocks of the staged copy and its image): the host threads start every member's transcript and write its claim
+// rows and factor tables into one staged copy, one member a task; ONE launch builds all members' g; then, for every step of the
+// reduction, ONE launch folds the live tables of all members (the member is the grid's z), one workgroup a member adds its partials,
+// the 3 G sums and - where tables retire - the scalars come back in one copy each, and ONE SYNCHRONISATION serves the group; the host
+// threads do every member's transcript arithmetic (FoldProver, open_folded's) and the G challenges go up in one copy ahead of the next
+// launch. A member whose running claim is not met is refused: it rides on in the launches - its buffers are its own, so no other
+// member's bytes depend on it - and its results are ignored. The tail is open_device_batch's on two jobs a member: the combinations,
+// the u vectors back, the host threads hash them and squeeze the indices, the gather writes the columns into images whose body starts
+// behind the header, the host writes header, u vectors and siblings. The lowest failing claim of the refused members comes from the
+// combine and evaluation kernels over their claims, one cell a member.
+std::vector<Opened> open_folded_device_batch(const char* who_c, const char* single, hg_ctx* ctx, const std::vector<OpenItem>& items, size_t Q) {
+    typedef GlPcs F;
+    const std::string who(who_c);
+    std::vector<Opened> res(items.size());
+    if (items.empty()) return res;
+    const Shape& sh = items[0].cm->sh;
+    const size_t C = sh.C(), N = sh.N(), R = sh.R, m = sh.nvars.size(), V = fold_rounds(sh), W = R << sh.c;
+    const int depth = sh.depth();
+    const size_t hb = folded_header_bytes(sh), len = folded_opening_bytes(sh, Q), q_words = query_stride<F>(sh), body_at = hb / 8 + 4 * C;   // (words)
+    size_t max_len;
+    const FoldGTables GA = fold_g_tables(sh, &max_len);
+    const unsigned max_blocks = fold_max_blocks();
+    auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    // what a member takes: g, the buffer pairs (a half and a quarter of g for T and for g each), its blocks of the staged copy, its u
+    // vectors, its image and its indices
+    const size_t tail_block = sizeof(ObMember<u64>) + 2 * sizeof(ObJob<u64>) + 2 * R * sizeof(E2);
+    auto bytes_of = [&](size_t i) {
+        return sizeof(E2) * (W + 2 * (W / 2 + 1) + 2 * (W / 4 + 1) + 2 * m + 3 + 1 + 2 * C) + sizeof(FoldGMember) + 8 + fold_gblock_bytes(sh, GA, *items[i].claims) + tail_block +
+               len + 8 * Q + 64;
+    };
+    const std::vector<std::pair<size_t, size_t>> groups = cut_groups(ctx, items.size(), bytes_of, 0, 0);
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    VerifyBatchBufs* B = batch_bufs(ctx);
+    hipStream_t st = ctx->stream;
+    Drain drain{st};
+    hip_check(hipStreamSynchronize(st), (who + ": synchronise").c_str());   // (the arena is reset below)
+    [[maybe_unused]] const int nthr = std::max(1, hg_omp_threads());        // (the device pass of hipcc ignores the pragmas)
+    const int cls = ctx->prof_class("pcs_fold_batch", false);
+    ctx->prof_stream = st;
+    const bool times = hg_times("pcs");   // HG_TIMES=pcs: where a group's wall clock goes, on stderr
+
+    struct Member {
+        size_t idx, block_at;
+        std::unique_ptr<FoldProver> P;
+        std::vector<E2> T, Gs, G1;
+        bool refused = false;
+        size_t failing = 0;
+        std::string error;
+    };
+    auto rethrow = [&](const std::vector<Member>& mem) {
+        for (const Member& x : mem)
+            if (!x.error.empty()) throw Error(who + ": index " + std::to_string(x.idx) + ": " + x.error);
+    };
+    for (size_t g = 0; g < groups.size(); g++) {
+        const double t0 = omp_get_wtime();
+        const size_t G = groups[g].second - groups[g].first;
+        std::vector<Member> mem(G);
+        // the staged copy: the g kernel's member table, the row pointers, the challenges, the members' blocks; then the tail's member and
+        // job tables, its weights, and the indices with the members' flags behind them
+        const size_t rows_at = up(G * sizeof(FoldGMember)), r_at = rows_at + up(G * 8);
+        size_t at = r_at + G * sizeof(E2), claims_total = 0;
+        for (size_t k = 0; k < G; k++) {
+            mem[k].idx = groups[g].first + k;
+            mem[k].block_at = at;
+            at += fold_gblock_bytes(sh, GA, *items[mem[k].idx].claims);
+            claims_total += items[mem[k].idx].claims->size();
+        }
+        const size_t g_bytes = at, tmem_at = at, tjob_at = tmem_at + up(G * sizeof(ObMember<u64>)), tw_at = tjob_at + up(2 * G * sizeof(ObJob<u64>)),
+                     js_at = tw_at + 2 * G * R * sizeof(E2), stage_bytes = js_at + (G * Q + G) * 8;
+        char* h_stage = batch_desc_host(B, stage_bytes);   // (the previous group's copies of it were waited for)
+        // results of the group, page-locked: the sums, the scalars, the u vectors, the images
+        const size_t hsum_at = 0, hscal_at = hsum_at + 3 * G * sizeof(E2), hu_at = hscal_at + 2 * m * G * sizeof(E2), himg_at = hu_at + 2 * C * G * sizeof(E2);
+        char* h_out = batch_out_host(B, himg_at + G * len);
+        const E2* h_sums = reinterpret_cast<const E2*>(h_out + hsum_at);
+        const E2* h_scal = reinterpret_cast<const E2*>(h_out + hscal_at);
+        const E2* h_u = reinterpret_cast<const E2*>(h_out + hu_at);
+        const uint8_t* h_img = reinterpret_cast<const uint8_t*>(h_out + himg_at);
+        E2* h_r = reinterpret_cast<E2*>(h_stage + r_at);
+        u64* h_js = reinterpret_cast<u64*>(h_stage + js_at);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
+        for (long long k = 0; k < (long long)G; k++) {
+            Member& x = mem[k];
+            try {
+                const Commitment& cm = *items[x.idx].cm;
+                const std::vector<Claim>& claims = *items[x.idx].claims;
+                x.P.reset(new FoldProver(sh, cm.root(), claims, Q));
+                x.T.assign(m, e2_zero());
+                x.Gs.assign(m, e2_zero());
+                fold_gblock_fill(h_stage, reinterpret_cast<FoldGMember*>(h_stage)[k], x.block_at, sh, GA, claims, x.P->bpow, x.G1);
+                reinterpret_cast<const u64**>(h_stage + rows_at)[k] = cm.d_rows;
+                h_r[k] = e2_zero();
+            } catch (const std::exception& e) { x.error = e.what(); }
+        }
+        rethrow(mem);
+        const double t1 = omp_get_wtime();
+        ctx->arena_reset();
+        char* d_stage;
+        FoldBufs buf;
+        E2* d_u;
+        u64* d_img;
+        try {
+            d_stage = ctx->alloc_n<char>(stage_bytes);
+            buf = fold_alloc(ctx, sh, G, max_blocks);
+            d_u = ctx->alloc_n<E2>(G * 2 * C);
+            d_img = ctx->alloc_n<u64>(G * len / 8);
+        } catch (const std::exception& e) {
+            throw Error(who + ": the context's arena cannot hold a group of " + std::to_string(G) + " reductions: lower verify_batch_group (" + e.what() + ")");
+        }
+        FoldMembers M;
+        memset(&M, 0, sizeof(M));
+        M.rows = reinterpret_cast<const u64* const*>(d_stage + rows_at);
+        M.r = reinterpret_cast<const E2*>(d_stage + r_at);
+        M.g_stride = W;
+        M.scal_stride = 2 * m;
+        hip_check(hipMemcpyAsync(d_stage, h_stage, g_bytes, hipMemcpyHostToDevice, st), "upload claims");
+        ctx->prof_begin(cls, (double)G * W * 16 + (double)g_bytes);
+        k_pcsfold_g<<<dim3(fold_blocks_of(max_blocks, max_len, std::max<size_t>(GA.nt, 1), G), std::max<unsigned>(GA.nt, 1), (unsigned)G), FOLD_TPB, 0, st>>>(GA, M, d_stage, buf.g,
+                                                                                                                                                            buf.scal);
+        ctx->prof_end();
+        // the steps of the reduction: every member is in the same one at the same time
+        size_t round_launches = 0, round_syncs = 0;
+        double t_host = 0;
+        for (size_t j = 0; j <= V; j++) {
+            bool retire;
+            size_t max_units, entries;
+            const FoldTables A = fold_tables(sh, j, &retire, &max_units, &entries);
+            retire |= j == 0 && GA.n1 != 0;   // the words of the one-word tables come back with step 0
+            if (A.nt) {
+                if (j > 0) hip_check(hipMemcpyAsync(d_stage + r_at, h_r, G * sizeof(E2), hipMemcpyHostToDevice, st), "upload the round's challenges");
+                ctx->prof_begin(cls, (double)G * fold_step_bytes(j, entries));
+                fold_launch(st, max_blocks, sh, j, A, max_units, G, M, buf, j < V);
+                ctx->prof_end();
+                round_launches++;
+                if (j < V) hip_check(hipMemcpyAsync(h_out + hsum_at, buf.sums, 3 * G * sizeof(E2), hipMemcpyDeviceToHost, st), "download the round's sums");
+            }
+            if (retire) hip_check(hipMemcpyAsync(h_out + hscal_at, buf.scal, 2 * m * G * sizeof(E2), hipMemcpyDeviceToHost, st), "download the retired tables' scalars");
+            if (A.nt || retire) {
+                hip_check(hipStreamSynchronize(st), (who + ": sync").c_str());
+                hip_check(hipGetLastError(), (who + ": launch").c_str());
+                round_syncs++;
+            }
+            const double th = omp_get_wtime();
+#pragma omp parallel for schedule(static) num_threads(std::min<int>(nthr, (int)G))
+            for (long long k = 0; k < (long long)G; k++) {
+                Member& x = mem[k];
+                if (x.refused) continue;
+                try {
+                    const E2* sc = h_scal + 2 * m * (size_t)k;
+                    for (size_t t = 0; t < m; t++) {
+                        if (j == 0 && sh.nvars[t] == 0) { x.T[t] = sc[2 * t]; x.Gs[t] = x.G1[t]; }
+                        if (j > 0 && (size_t)sh.nvars[t] == j) { x.T[t] = sc[2 * t]; x.Gs[t] = sc[2 * t + 1]; }
+                    }
+                    E2 s[3] = {e2_zero(), e2_zero(), e2_zero()};
+                    if (A.nt && j < V) memcpy(s, h_sums + 3 * (size_t)k, sizeof(s));
+                    x.refused = j < V ? !x.P->round(sh, j, s, x.T, x.Gs) : !x.P->finish(sh, x.T, x.Gs);
+                    h_r[k] = x.P->r;
+                } catch (const std::exception& e) { x.error = e.what(); }
+            }
+            rethrow(mem);
+            t_host += omp_get_wtime() - th;
+        }
+        ctx->prof_collect();
+        if (hg_debug("plan"))   // (read at every call: the tests switch it per case)
+            fprintf(stderr, "[hg plan] pcsfoldb members=%zu V=%zu round_launches=%zu round_syncs=%zu tables=%zu claims=%zu\n", G, V, round_launches, round_syncs, m, claims_total);
+        const double t2 = omp_get_wtime();
+        // the refused members: their claims through the row combinations and the evaluation checks, the lowest failing one in a cell a member
+        std::vector<size_t> bad;
+        for (size_t k = 0; k < G; k++)
+            if (mem[k].refused) bad.push_back(k);
+        if (!bad.empty()) {
+            size_t nc = 0, nw = 0;
+            for (size_t k : bad) {
+                nc += items[mem[k].idx].claims->size();
+                nw += weights_of<F>(sh, *items[mem[k].idx].claims) - R;
+            }
+            const size_t rc_at = up(nc * sizeof(ObJob<u64>)), ry_at = rc_at + up(nc * sizeof(ObClaim)), rz_at = ry_at + nc * sizeof(E2), rw_at = rz_at + nc * (size_t)sh.c * sizeof(E2);
+            std::vector<char> rs(rw_at + nw * sizeof(E2) + 16);
+            ObJob<u64>* hd = reinterpret_cast<ObJob<u64>*>(rs.data());
+            ObClaim* hc = reinterpret_cast<ObClaim*>(rs.data() + rc_at);
+            E2* hy = reinterpret_cast<E2*>(rs.data() + ry_at);
+            E2* hz = reinterpret_cast<E2*>(rs.data() + rz_at);
+            E2* hw = reinterpret_cast<E2*>(rs.data() + rw_at);
+            size_t q = 0, off = 0;
+            for (size_t b = 0; b < bad.size(); b++) {
+                const Commitment& cm = *items[mem[bad[b]].idx].cm;
+                const std::vector<Claim>& claims = *items[mem[bad[b]].idx].claims;
+                for (size_t i = 0; i < claims.size(); i++, q++) {
+                    const Claim& cl = claims[i];
+                    const std::vector<E2> w = eq_table(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
+                    hd[q].src = cm.d_rows + (sh.off[cl.table] << sh.c); hd[q].nrows = w.size(); hd[q].w_at = rw_at + off * sizeof(E2); hd[q].u_at = q * C;
+                    memcpy(hw + off, w.data(), w.size() * sizeof(E2));
+                    off += w.size();
+                    hy[q] = cl.value;
+                    F::store_low(hz + q * (size_t)sh.c, cl.point.data(), sh.c);
+                    hc[q].u_at = q * C; hc[q].z_at = rz_at + q * (size_t)sh.c * sizeof(E2); hc[q].y_at = ry_at + q * sizeof(E2); hc[q].member = (u64)b; hc[q].claim = (u64)i;
+                }
+            }
+            char* d_rs;
+            E2* d_ru;
+            u64* d_cells;
+            try {
+                d_rs = ctx->alloc_n<char>(rs.size());
+                d_ru = ctx->alloc_n<E2>(nc * C);
+                d_cells = ctx->alloc_n<u64>(bad.size());
+            } catch (const std::exception& e) {
+                throw Error(who + ": the context's arena cannot hold the claims of the refused members: lower verify_batch_group (" + e.what() + ")");
+            }
+            if (nc * ((C + F::TPB - 1) / F::TPB) > 0x7fffffffull) throw Error(who + ": the refused members have too many claims for one launch: lower verify_batch_group");
+            std::vector<u64> cells(bad.size());
+            hip_check(hipMemcpyAsync(d_rs, rs.data(), rs.size(), hipMemcpyHostToDevice, st), "upload claims");
+            hip_check(hipMemsetAsync(d_cells, 0xff, bad.size() * 8, st), "memset");
+            F::combine(ctx, cls, st, sh.c, nc, nw, 0, reinterpret_cast<const ObJob<u64>*>(d_rs), d_rs, d_ru);
+            F::ob_eval(ctx, cls, st, reinterpret_cast<const ObClaim*>(d_rs + rc_at), nc, sh.c, d_ru, d_rs, d_cells);
+            hip_check(hipMemcpyAsync(cells.data(), d_cells, bad.size() * 8, hipMemcpyDeviceToHost, st), "download evaluation checks");
+            hip_check(hipStreamSynchronize(st), (who + ": sync").c_str());   // (the staged copy and the cells are locals)
+            hip_check(hipGetLastError(), (who + ": launch").c_str());
+            for (size_t b = 0; b < bad.size(); b++) {
+                if (cells[b] == PCSV_NONE) throw Error(who + ": index " + std::to_string(mem[bad[b]].idx) + ": internal: the reduction does not meet its claim");
+                mem[bad[b]].failing = (size_t)cells[b];
+            }
+        }
+        const size_t active = G - bad.size();
+        const double t3 = omp_get_wtime();
+        if (active) {
+            // the tail: two row combinations a member that was not refused
+            ObMember<u64>* hm = reinterpret_cast<ObMember<u64>*>(h_stage + tmem_at);
+            ObJob<u64>* hd = reinterpret_cast<ObJob<u64>*>(h_stage + tjob_at);
+            std::vector<size_t> live;
+            for (size_t k = 0; k < G; k++)
+                if (!mem[k].refused) live.push_back(k);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
+            for (long long k = 0; k < (long long)G; k++) {
+                Member& x = mem[k];
+                try {
+                    const Commitment& cm = *items[x.idx].cm;
+                    hm[k].M = cm.d_M; hm[k].img = (size_t)k * (len / 8); hm[k].u = 0; hm[k].u_words = body_at;
+                    h_js[G * Q + k] = x.refused ? 0 : 1;
+                    if (x.refused) continue;
+                    const size_t a = std::lower_bound(live.begin(), live.end(), (size_t)k) - live.begin();   // its number among the members that go on
+                    const std::vector<CombineJob> jobs = x.P->body_jobs(sh);
+                    for (size_t i = 0; i < 2; i++) {
+                        ObJob<u64>& d = hd[2 * a + i];
+                        d.src = cm.d_rows; d.nrows = R; d.w_at = tw_at + (2 * (size_t)k + i) * R * sizeof(E2); d.u_at = (2 * (size_t)k + i) * C;
+                        memcpy(h_stage + d.w_at, jobs[i].w.data(), R * sizeof(E2));
+                    }
+                } catch (const std::exception& e) { x.error = e.what(); }
+            }
+            rethrow(mem);
+            hip_check(hipMemcpyAsync(d_stage + tmem_at, h_stage + tmem_at, js_at - tmem_at, hipMemcpyHostToDevice, st), "upload weights");
+            F::combine(ctx, cls, st, sh.c, 2 * active, 2 * active * R, 0, reinterpret_cast<const ObJob<u64>*>(d_stage + tjob_at), d_stage, d_u);
+            hip_check(hipMemcpyAsync(h_out + hu_at, d_u, G * 2 * C * sizeof(E2), hipMemcpyDeviceToHost, st), "download combinations");
+            hip_check(hipStreamSynchronize(st), (who + ": sync").c_str());
+            hip_check(hipGetLastError(), (who + ": launch").c_str());
+        }
+        const double t4 = omp_get_wtime();
+        if (active) {
+            // the host's share: every member's u vectors into its transcript (and behind its header), its column indices out of it
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
+            for (long long k = 0; k < (long long)G; k++) {
+                Member& x = mem[k];
+                for (size_t q = 0; q < Q; q++) h_js[(size_t)k * Q + q] = 0;
+                if (x.refused) continue;
+                try {
+                    for (size_t i = 0; i < 2 * C; i++) x.P->tr.write_e(h_u[2 * C * (size_t)k + i]);
+                    const std::vector<size_t> js = squeeze_indices(x.P->tr, N, Q);
+                    for (size_t q = 0; q < Q; q++) h_js[(size_t)k * Q + q] = js[q];
+                } catch (const std::exception& e) { x.error = e.what(); }
+            }
+            rethrow(mem);
+        }
+        const double t5 = omp_get_wtime();
+        if (active) {
+            hip_check(hipMemcpyAsync(d_stage + js_at, h_js, (G * Q + G) * 8, hipMemcpyHostToDevice, st), "upload column indices");
+            F::gather(ctx, cls, st, reinterpret_cast<const ObMember<u64>*>(d_stage + tmem_at), G, Q, R, N, q_words, active, reinterpret_cast<const u64*>(d_stage + js_at), d_img);
+            hip_check(hipMemcpyAsync(h_out + himg_at, d_img, G * len, hipMemcpyDeviceToHost, st), "download openings");
+            hip_check(hipStreamSynchronize(st), (who + ": sync").c_str());
+            hip_check(hipGetLastError(), (who + ": launch").c_str());
+        }
+        ctx->prof_collect();
+        const double t6 = omp_get_wtime();
+        // header and u vectors from each transcript, the siblings from each handle's tree into the gaps; a refused member's reason
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
+        for (long long k = 0; k < (long long)G; k++) {
+            Member& x = mem[k];
+            try {
+                Opened& out = res[x.idx];
+                const Commitment& cm = *items[x.idx].cm;
+                if (x.refused) {
+                    out.refused = true;
+                    out.reason = std::string(single) + ": claim " + std::to_string(x.failing) + ": the value is not the evaluation of table " +
+                                 std::to_string((*items[x.idx].claims)[x.failing].table) + " at the point";
+                    continue;
+                }
+                const std::vector<uint8_t>& head = x.P->tr.bytes;
+                if (head.size() != 8 * body_at) throw Error("internal: opening length");
+                const uint8_t* image = h_img + (size_t)k * len;
+                out.bytes.assign(image, image + len);
+                memcpy(out.bytes.data(), head.data(), head.size());
+                for (size_t q = 0; q < Q; q++) {
+                    uint8_t* sib = out.bytes.data() + 8 * (body_at + q * q_words + R);
+                    size_t idx = (size_t)h_js[(size_t)k * Q + q];
+                    for (int l = 0; l < depth; l++, idx >>= 1) memcpy(sib + 32 * l, cm.node(l, idx ^ 1), 32);
+                }
+            } catch (const std::exception& e) { x.error = e.what(); }
+        }
+        rethrow(mem);
+        if (times)
+            fprintf(stderr, "[hg pcs] folded open group %zu of %zu members: transcripts and factor tables %.2f ms, g and %zu rounds %.2f (host arithmetic %.2f), refusals %.2f, "
+                            "combine and u back %.2f, hash %.2f, gather and images back %.2f, header and siblings %.2f\n", g, G, (t1 - t0) * 1e3, V, (t2 - t1) * 1e3, t_host * 1e3,
+                    (t3 - t2) * 1e3, (t4 - t3) * 1e3, (t5 - t4) * 1e3, (t6 - t5) * 1e3, (omp_get_wtime() - t6) * 1e3);
+    }
+    return res;
 }
 
 }  // namespace pcs

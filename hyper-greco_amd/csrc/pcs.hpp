@@ -164,9 +164,30 @@ struct FoldSource {
 // bpow[i] = beta^i. The host form reads cm.rows; the device form (pcs.hip) builds g and runs every round on the context's stream
 std::unique_ptr<FoldSource> fold_source_host(const Commitment& cm, const std::vector<Claim>& claims, const std::vector<E2>& bpow);
 std::unique_ptr<FoldSource> fold_source_device(const Commitment& cm, const std::vector<Claim>& claims, const std::vector<E2>& bpow);
+// The prover's arithmetic of one reduction, which open_folded and the batch form (pcs.hip) share: the transcript, the running claim and
+// the factors prod (1 - r_j') of the retired tables. T, G are a FoldSource's, or what a group pass brought back for the member.
+struct FoldProver {
+    FsTranscript tr;
+    std::vector<E2> bpow, tail, rho;
+    E2 claim, r;   // r: the challenge the next step folds by (zero ahead of round 0)
+    FoldProver(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q);
+    // round j < V from the sums of step(j): false, with nothing written, if they do not meet the running claim (a value is wrong); else
+    // c0, c1, c2 are written and r = rho[j] is squeezed
+    bool round(const Shape& sh, size_t j, const E2 s[3], const std::vector<E2>& T, const std::vector<E2>& G);
+    // after step(V): false if the final evaluation misses the claim; else the Y_t are written
+    bool finish(const Shape& sh, const std::vector<E2>& T, const std::vector<E2>& G);
+    // delta and rho' squeezed -> the two row combinations of the body: the R powers of rho', the combined weights
+    std::vector<CombineJob> body_jobs(const Shape& sh);
+};
 // hg_pcs_open_folded: the opening bytes; an Error naming `who` if there is no claim and - naming the lowest failing claim - if a value
 // is not its table's evaluation (round 0 shows that one is wrong, the claims are then evaluated one by one)
 std::vector<uint8_t> open_folded(const char* who, const Commitment& cm, const std::vector<Claim>& claims, size_t Q);
+// hg_pcs_open_folded_batch (pcs.hip): open_device_batch for folded openings (every item has a claim): a group's reductions run as one
+// launch a round over all members, with one synchronisation a round. refused / bytes as there, the reason is open_folded's under `single`
+std::vector<Opened> open_folded_device_batch(const char* who, const char* single, hg_ctx* ctx, const std::vector<OpenItem>& items, size_t Q);
+// hg_pcs_verify_folded_device_batch (pcs.hip): verify_device_batch for folded openings: why[i] is what verify_folded_device returns for
+// item i alone; the headers on the host threads, the bodies through verify_device_batch's pass as openings of one claim
+std::vector<std::string> verify_folded_device_batch(const char* who, hg_ctx* ctx, const Shape& sh, const std::vector<VerifyItem>& items, size_t Q);
 // hg_pcs_verify_folded: "" = accepted, else the reason
 std::string verify_folded(const Shape& sh, const uint8_t root[32], const std::vector<Claim>& claims, size_t Q, const uint8_t* proof, size_t len);
 // hg_pcs_verify_folded_device (pcs.hip, verify_folded_flow of pcs_flow.hpp): the same decision and reason; the header on the host, the body through

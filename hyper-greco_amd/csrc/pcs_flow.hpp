@@ -178,13 +178,27 @@ std::string verify_flow(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], co
     return cells_reason(cells, n);
 }
 
+// The block of a folded opening's body, whose layout is that of a member of one claim and 2 R weights: the root, two jobs over all R
+// rows (the powers of rho', the combined weights), the value sum_t delta^t Y_t and the point rho[..c), all from the header H
+template <class F, class Header> void folded_block_fill(char* h_stage, const VbMember& d, const Shape& sh, const uint8_t root[32], const Header& H) {
+    typedef typename F::W W;
+    const size_t R = sh.R;
+    memcpy(h_stage + d.root_at, root, 32);
+    CombineDesc* hd = reinterpret_cast<CombineDesc*>(h_stage + d.jobs_at);
+    hd[0].row0 = 0; hd[0].nrows = R; hd[0].woff = 0;
+    hd[1].row0 = 0; hd[1].nrows = R; hd[1].woff = R;
+    memcpy(h_stage + d.y_at, &H.y, sizeof(W));
+    if (sh.c) F::store_low(reinterpret_cast<W*>(h_stage + d.z_at), H.lo.data(), sh.c);
+    memcpy(h_stage + d.w_at, H.rho_pw.data(), R * sizeof(W));
+    memcpy(h_stage + d.w_at + R * sizeof(W), H.w.data(), R * sizeof(W));
+}
+
 // The device verifier of a folded opening. The header is host scalar work (the field's folded_header); its body is an opening of one
 // claim - all R rows under the combined weights, at rho[..c), with the value sum_t delta^t Y_t - and goes through verify_flow's kernels
 // as a group of one member whose opening starts behind the header. The kernels run whatever the header's checks gave: an element of the
 // body that is not canonical is reported ahead of a failing round, as the host verifier does.
 template <class F>
 std::string verify_folded_flow(hg_ctx* ctx, const Shape& sh, const uint8_t root[32], const std::vector<typename F::Claim>& claims, size_t Q, const uint8_t* proof, size_t len) {
-    typedef typename F::W W;
     const size_t C = sh.C(), N = sh.N(), R = sh.R, hb = F::folded_header_bytes(sh);
     const std::string who(F::VERIFY_FOLDED_NAME);
     const std::string bad_len = length_reason(len, F::folded_opening_bytes(sh, Q));
@@ -201,14 +215,7 @@ std::string verify_folded_flow(hg_ctx* ctx, const Shape& sh, const uint8_t root[
     desc.proof = hb / 8;
     std::vector<char> stage(member_block_layout<F>(desc, sh, 1, nw, sizeof(VbMember)));
     memcpy(stage.data(), &desc, sizeof(VbMember));
-    memcpy(stage.data() + desc.root_at, root, 32);
-    CombineDesc* hd = reinterpret_cast<CombineDesc*>(stage.data() + desc.jobs_at);
-    hd[0].row0 = 0; hd[0].nrows = R; hd[0].woff = 0;
-    hd[1].row0 = 0; hd[1].nrows = R; hd[1].woff = R;
-    memcpy(stage.data() + desc.y_at, &H.y, sizeof(W));
-    if (sh.c) F::store_low(reinterpret_cast<W*>(stage.data() + desc.z_at), H.lo.data(), sh.c);
-    memcpy(stage.data() + desc.w_at, H.rho_pw.data(), R * sizeof(W));
-    memcpy(stage.data() + desc.w_at + R * sizeof(W), H.w.data(), R * sizeof(W));
+    folded_block_fill<F>(stage.data(), desc, sh, root, H);
     u64* d_proof;
     VerifyDev<F> d;
     try {
@@ -245,8 +252,12 @@ std::string verify_folded_flow(hg_ctx* ctx, const Shape& sh, const uint8_t root[
 // each over all members; the members' u_i hashed on the host threads meanwhile; all indices up, the query kernel, three cells a
 // member down: one synchronisation a group. The next group's openings are gathered and copied into the other set before that
 // synchronisation, under this group's kernels.
+// `folded`: the items are folded openings. A member's block is then prepared from its header - the field's folded_header on the host
+// threads, one member a task - as that of an opening of one claim that starts behind the header (folded_block_fill: what
+// verify_folded_flow writes for its one member); everything else is the same pass. A member whose header holds a word that is not
+// canonical rides along on a block of zeros and is given the header's reason.
 template <class F>
-std::vector<std::string> verify_batch_flow(const char* who_c, hg_ctx* ctx, const Shape& sh, const std::vector<typename F::VerifyItem>& items, size_t Q) {
+std::vector<std::string> verify_batch_flow(const char* who_c, hg_ctx* ctx, const Shape& sh, const std::vector<typename F::VerifyItem>& items, size_t Q, bool folded = false) {
     typedef typename F::Row Row;
     typedef typename F::W W;
     typedef typename F::VerifyItem Item;
@@ -254,10 +265,12 @@ std::vector<std::string> verify_batch_flow(const char* who_c, hg_ctx* ctx, const
     const size_t C = sh.C(), N = sh.N(), R = sh.R;
     const int depth = sh.depth();
     const bool four_step = depth >= 8 && depth <= 16;
+    const size_t hb = folded ? F::folded_header_bytes(sh) : 0;   // where a member's body starts in its opening
+    auto claims_of = [&](const Item& it) { return folded ? (size_t)1 : it.claims->size(); };   // the claims of the body
     std::vector<std::string> why(items.size());
     std::vector<size_t> good;   // the items that reach the device
     for (size_t i = 0; i < items.size(); i++) {
-        why[i] = length_reason(items[i].len, F::opening_bytes(sh, items[i].claims->size(), Q));
+        why[i] = length_reason(items[i].len, folded ? F::folded_opening_bytes(sh, Q) : F::opening_bytes(sh, items[i].claims->size(), Q));
         if (why[i].empty()) good.push_back(i);
     }
     if (good.empty()) return why;
@@ -274,7 +287,7 @@ std::vector<std::string> verify_batch_flow(const char* who_c, hg_ctx* ctx, const
     for (size_t a = 0; a < good.size();) {
         size_t b = a, bytes = 0, rows = 0;
         while (b < good.size() && b - a < cap) {
-            const size_t n = items[good[b]].claims->size();
+            const size_t n = claims_of(items[good[b]]);
             if (b > a && (bytes + bytes_of(n, items[good[b]].len) > VB_PCS_BUDGET || (four_step && rows + rows_of(n) > NTT_ROWS) || rows + rows_of(n) > dots_rows)) break;
             bytes += bytes_of(n, items[good[b]].len);
             rows += rows_of(n);
@@ -293,7 +306,8 @@ std::vector<std::string> verify_batch_flow(const char* who_c, hg_ctx* ctx, const
     const int cls = ctx->prof_class(F::CLS_VERIFY_BATCH, false);
     ctx->prof_stream = st;
 
-    struct Member { size_t idx, n, nw; FsTranscript tr; std::string error; };
+    typedef decltype(F::folded_header(sh, nullptr, *items[0].claims, Q, nullptr)) Header;
+    struct Member { size_t idx, n, nw; FsTranscript tr; std::string error, header_reason; size_t noncanonical = ~(size_t)0; };
     auto rethrow = [&](const std::vector<Member>& mem) {
         for (const Member& x : mem)
             if (!x.error.empty()) throw Error(who + ": index " + std::to_string(x.idx) + ": " + x.error);
@@ -330,10 +344,10 @@ std::vector<std::string> verify_batch_flow(const char* who_c, hg_ctx* ctx, const
             Member& x = mem[m];
             const Item& it = items[good[groups[g].first + m]];
             x.idx = good[groups[g].first + m];
-            x.n = it.claims->size();
-            x.nw = weights_of<F>(sh, *it.claims);
+            x.n = claims_of(it);
+            x.nw = folded ? 2 * R : weights_of<F>(sh, *it.claims);
             VbMember& d = desc[m];
-            d.proof = poff[m]; d.u = t.u_total; d.cols = m * Q * R; d.enc_row = t.rows;
+            d.proof = poff[m] + hb / 8; d.u = t.u_total; d.cols = m * Q * R; d.enc_row = t.rows;
             d.n = x.n; d.claim0 = t.claims; d.job0 = t.claims + m;
             at = member_block_layout<F>(d, sh, x.n, x.nw, at);
             const size_t u_units = F::U_ROWS * C * (x.n + 1);
@@ -352,7 +366,13 @@ std::vector<std::string> verify_batch_flow(const char* who_c, hg_ctx* ctx, const
             Member& x = mem[mq];
             try {
                 const Item& it = items[x.idx];
-                x.tr = member_block_fill<F>(h_stage, desc[mq], sh, it.root, *it.claims, Q);
+                if (!folded) { x.tr = member_block_fill<F>(h_stage, desc[mq], sh, it.root, *it.claims, Q); continue; }
+                Header H = F::folded_header(sh, it.root, *it.claims, Q, it.proof);
+                x.noncanonical = H.noncanonical;
+                if (H.noncanonical != ~(size_t)0) { memset(h_stage + desc[mq].root_at, 0, desc[mq].w_at + x.nw * sizeof(W) - desc[mq].root_at); continue; }
+                folded_block_fill<F>(h_stage, desc[mq], sh, it.root, H);
+                x.header_reason = std::move(H.reason);
+                x.tr = std::move(H.tr);
             } catch (const std::exception& e) { x.error = e.what(); }
         }
         rethrow(mem);
@@ -377,7 +397,8 @@ std::vector<std::string> verify_batch_flow(const char* who_c, hg_ctx* ctx, const
         for (long long mq = 0; mq < (long long)G; mq++) {
             Member& x = mem[mq];
             try {
-                F::absorb_opening(x.tr, items[x.idx].proof, C * (x.n + 1));
+                if (x.noncanonical != ~(size_t)0) continue;   // (its indices stay 0: its cells are not read)
+                F::absorb_opening(x.tr, items[x.idx].proof + hb, C * (x.n + 1));
                 const std::vector<size_t> js = F::squeeze_indices(x.tr, N, Q);
                 for (size_t q = 0; q < Q; q++) hj[(size_t)mq * Q + q] = js[q];
             } catch (const std::exception& e) { x.error = e.what(); }
@@ -398,7 +419,15 @@ std::vector<std::string> verify_batch_flow(const char* who_c, hg_ctx* ctx, const
         t_stage = t5 - t4;
         hip_check(hipGetLastError(), (who + ": launch").c_str());
         ctx->prof_collect();
-        for (size_t m = 0; m < G; m++) why[mem[m].idx] = cells_reason(cells.data() + 3 * m, mem[m].n);
+        for (size_t m = 0; m < G; m++) {
+            const Member& x = mem[m];
+            const u64* cell = cells.data() + 3 * m;
+            // a folded opening in the single call's order: a header word, a body word, the header's checks, the body's
+            if (x.noncanonical != ~(size_t)0) why[x.idx] = reason_noncanonical(x.noncanonical);
+            else if (folded && cell[0] != PCSV_NONE) why[x.idx] = reason_noncanonical(hb + (size_t)cell[0]);
+            else if (!x.header_reason.empty()) why[x.idx] = x.header_reason;
+            else why[x.idx] = cells_reason(cell, x.n);
+        }
     }
     return why;
 }
