@@ -65,6 +65,7 @@ EXPORTS = [
     "hg_pcs_verify_device_bn254", "hg_claims_verify_device_bn254", "hg_pcs_verify_device_batch_bn254", "hg_claims_verify_batch_bn254",
     "hg_pcs_open_folded_bn254", "hg_pcs_verify_folded_bn254", "hg_pcs_verify_folded_device_bn254", "hg_claims_open_folded_bn254", "hg_claims_verify_folded_bn254",
     "hg_claims_verify_folded_device_bn254",
+    "hg_pcs_open_folded_batch_bn254", "hg_claims_open_folded_batch_bn254", "hg_pcs_verify_folded_device_batch_bn254", "hg_claims_verify_folded_batch_bn254",
     "hg_pcs_commit_batch_bn254", "hg_secrets_commit_batch_bn254", "hg_pcs_open_batch_bn254", "hg_claims_open_batch_bn254",
     "hg_prove_mode", "hg_prove_resident_mode", "hg_verify_mode", "hg_group_local", "hg_group_external", "hg_group_free", "hg_prove_resident_mode_sharded", "hg_witness_gen", "hg_witness_gen_into", "hg_witness_gen_shard", "hg_values_info", "hg_values_peak_bytes", "hg_values_free", "hg_values_get", "hg_comm_unique_id", "hg_comm_init", "hg_comm_destroy", "hg_comm_count", "hg_comm_selftest", "hg_prove_sharded", "hg_prove_shard_begin", "hg_prove_shard_combine", "hg_prove_shard_finish", "hg_shard_combine_host", "hg_prove_resident", "hg_circuit_eval", "hg_lasso_prove", "hg_lasso_prove_at", "hg_lasso_num_challenges", "hg_sumcheck", "hg_prodsum_jobs", "hg_claim_tables_eq", "hg_claim_tables_fft", "hg_mle_eval",
     "hg_ntt", "hg_challenges", "hg_challenges_bn254", "hg_bn254_field_op", "hg_sumcheck_bn254", "hg_prodsum_jobs_bn254", "hg_grand_product_bn254", "hg_lasso_prove_bn254", "hg_witness_from_json_bn254", "hg_circuit_eval_bn254", "hg_prove_bn254", "hg_verify_bn254", "hg_verify_device_bn254", "hg_verify_device_batch_bn254", "hg_verify_public_bn254", "hg_verify_public_device_bn254", "hg_verify_public_batch_bn254", "hg_claims_settle_bn254", "hg_instance_mle_bn254", "hg_instance_mle_batch_bn254", "hg_prove_encryptions_bn254", "hg_mle_eval_bn254", "hg_ntt_bn254", "hg_profile", "hg_profile_select", "hg_profile_reset", "hg_profile_get",
@@ -141,6 +142,8 @@ def _two_field_protos(L):
     # the batch forms of the folded openings take what the unfolded batch forms take
     L.hg_pcs_open_folded_batch.argtypes, L.hg_claims_open_folded_batch.argtypes = L.hg_pcs_open_batch.argtypes, L.hg_claims_open_batch.argtypes
     L.hg_pcs_verify_folded_device_batch.argtypes, L.hg_claims_verify_folded_batch.argtypes = L.hg_pcs_verify_device_batch.argtypes, L.hg_claims_verify_batch.argtypes
+    L.hg_pcs_open_folded_batch_bn254.argtypes, L.hg_claims_open_folded_batch_bn254.argtypes = L.hg_pcs_open_batch.argtypes, L.hg_claims_open_batch.argtypes
+    L.hg_pcs_verify_folded_device_batch_bn254.argtypes, L.hg_claims_verify_folded_batch_bn254.argtypes = L.hg_pcs_verify_device_batch.argtypes, L.hg_claims_verify_batch.argtypes
 
 
 _lib = None
@@ -1645,6 +1648,23 @@ def claims_open_batch_bn254(ctx, params, cms, claims_list, n_queries=0, reason_c
     return _claims_open_batch_of(InputClaimsBn254, pcs_opening_bytes_bn254, ctx, params, cms, claims_list, n_queries, reason_cap)
 
 
+def _folded_bytes_bn254(nvars, n_claims, n_queries, log2_row):
+    """pcs_folded_opening_bytes_bn254 with the argument list of pcs_opening_bytes_bn254"""
+    return pcs_folded_opening_bytes_bn254(nvars, n_queries, log2_row)
+
+
+def pcs_open_folded_batch_bn254(ctx, cms, claims_list, n_queries=0, reason_cap=256):
+    """hg_pcs_open_folded_batch_bn254: pcs_open_batch_bn254 for folded openings (every claim list holds a claim): [(bytes or None,
+    reason)] - the bytes of cms[i].open_folded(claims_list[i]), or None and the text of its error where a value is not the evaluation."""
+    return _pcs_open_batch_of("_bn254", _pcs_claim_arrays_bn254, _folded_bytes_bn254, ctx, cms, claims_list, n_queries, reason_cap, "hg_pcs_open_folded_batch")
+
+
+def claims_open_folded_batch_bn254(ctx, params, cms, claims_list, n_queries=0, reason_cap=256):
+    """hg_claims_open_folded_batch_bn254: claims_open_batch_bn254 for folded openings: [(bytes or None, reason)] - the bytes of
+    cms[i].open_claims_folded(params, claims_list[i])."""
+    return _claims_open_batch_of(InputClaimsBn254, _folded_bytes_bn254, ctx, params, cms, claims_list, n_queries, reason_cap, "hg_claims_open_folded_batch")
+
+
 def _pcs_verify(sfx, arrays, root, nvars, claims, proof, n_queries, log2_row, ctx, form=""):
     """form "_folded": the folded verifiers"""
     nv = (C.c_uint32 * len(nvars))(*nvars)
@@ -1781,6 +1801,18 @@ def claims_verify_batch_bn254(ctx, params, roots, claims_list, openings, n_queri
     """hg_claims_verify_batch_bn254: claims_verify_batch on InputClaimsBn254 objects (what verify_public_batch_bn254 returns; None
     stands for no claims): a list of (accepted, reason), the decisions of claims_verify_bn254 for each item alone."""
     return _claims_verify_batch_of(InputClaimsBn254, ctx, params, roots, claims_list, openings, n_queries, log2_row, reason_cap)
+
+
+def pcs_verify_folded_batch_bn254(ctx, roots, nvars, claims_list, proofs, n_queries=0, log2_row=0, reason_cap=256):
+    """hg_pcs_verify_folded_device_batch_bn254: pcs_verify_batch_bn254 for folded openings (every claim list holds a claim): a list of
+    (accepted, reason), the decisions of pcs_verify_folded_bn254 for each item alone."""
+    return _pcs_verify_batch_of("_bn254", _pcs_claim_arrays_bn254, ctx, roots, nvars, claims_list, proofs, n_queries, log2_row, reason_cap, "hg_pcs_verify_folded_device_batch")
+
+
+def claims_verify_folded_batch_bn254(ctx, params, roots, claims_list, openings, n_queries=0, log2_row=0, reason_cap=256):
+    """hg_claims_verify_folded_batch_bn254: claims_verify_batch_bn254 for folded openings: a list of (accepted, reason), the decisions
+    of claims_verify_folded_bn254 for each item alone; an item without claims (None) is rejected, not an error."""
+    return _claims_verify_batch_of(InputClaimsBn254, ctx, params, roots, claims_list, openings, n_queries, log2_row, reason_cap, "hg_claims_verify_folded_batch")
 
 
 def pcs_verify_bn254(root, nvars, claims, proof, n_queries=0, log2_row=0, ctx=None):

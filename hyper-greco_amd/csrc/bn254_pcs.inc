@@ -11,7 +11,8 @@
 // of pcs_flow.hpp, written once for both fields; this file gives them BnPcs, the BN254 policy: the types, the transcript calls, the
 // texts and one launch function per kernel step. pcs_commit_device and pcs_commit_words_enqueue keep a host flow of their own.
 // The prover's side of a folded opening (pcs_bn254.hpp PcsFoldSource) is at the end: the kernel that builds g, the round kernels of the
-// reduction sum-check and their host driver BnFoldDev.
+// reduction sum-check - written for a group of members, the single call a group of one - their host driver for one opening,
+// BnFoldDev, and BnFoldPcs, through which open_folded_batch_flow of pcs_flow.hpp drives them for a run.
 
 constexpr int BNPCS_TPB = 256;
 static unsigned bnpcs_blocks(size_t n) { return (unsigned)((n + BNPCS_TPB - 1) / BNPCS_TPB); }
@@ -604,7 +605,8 @@ std::string pcs_verify_folded_device(hg_ctx* ctx, const pcs::Shape& sh, const ui
 // inside the bound. 64 is chosen: a quarter of that, the reductions are already 1/64 of the multiply-adds, and a test crosses it twice
 // with one workgroup a table at 2^17 entries. The g builder multiplies two canonical staged factors (below p^2 a product) and
 // restarts every BNFOLD_G_TRIPS = 1024 claims, a quarter of its bound of 4096.
-// Geometry: blockIdx.y = a live table, its units grid-strided over blockIdx.x; at most HG_PCS_FOLD_BLOCKS (2048) workgroups in all.
+// Geometry: blockIdx.z = the member of a group (the single call is a group of one), blockIdx.y = a live table, its units grid-strided over
+// blockIdx.x; at most HG_PCS_FOLD_BLOCKS (2048) workgroups in all, but at least one a table and member.
 constexpr int BNFOLD_TPB = 256;
 constexpr unsigned BNFOLD_MAX_BLOCKS = 2048;
 constexpr int BNFOLD_TRIPS = 64, BNFOLD_G_TRIPS = 1024;
@@ -615,38 +617,66 @@ static unsigned bnfold_max_blocks() {   // HG_PCS_FOLD_BLOCKS (tests set it): an
     const long v = e && *e ? atol(e) : (long)BNFOLD_MAX_BLOCKS;
     return (unsigned)std::max(1L, std::min(65535L, v));
 }
-struct BnFoldClaim { u64 lo_at, hi_at; u32 lo_bits, pad; };   // its two factor tables (elements of the staged factors): eq(z, x) = lo[x & (2^lo_bits - 1)] hi[x >> lo_bits]
+struct BnFoldClaim { u64 lo_at, hi_at; u32 lo_bits, pad; };   // its two factor tables (elements of its member's staged factors): eq(z, x) = lo[x & (2^lo_bits - 1)] hi[x >> lo_bits]
+// What a shape fixes for the g kernel of every member: the tables of two entries or more (the kernel's table numbers) and the
+// one-element tables, whose element goes to the scalars as it is
 struct BnFoldGTables {
-    u32 nt;
-    u32 lg[pcs::MAX_TABLES], claim0[pcs::MAX_TABLES + 1];   // v_t; the claims of table t are claim0[t] .. claim0[t+1] of the staged list
-    u64 at[pcs::MAX_TABLES];                                // s_t
+    u32 nt, n1;
+    u32 lg[pcs::MAX_TABLES], id1[pcs::MAX_TABLES];          // v_t; the number t of a one-element table
+    u64 at[pcs::MAX_TABLES], at1[pcs::MAX_TABLES];          // s_t; where a one-element table lies in the rows
 };
+// A member's block of the g kernel's staged copy (byte offsets, multiples of 32): claim0[nt + 1] (the claims of kernel table t are
+// claim0[t] .. claim0[t+1] of its list: members differ in their claim counts, and a table may have none), its BnFoldClaim list, its
+// factor tables
+struct BnFoldGMember { u64 claim0_at, claims_at, fac_at, pad; };
 struct BnFoldTables {
     u32 nt, pad;
     u32 lg[pcs::MAX_TABLES], id[pcs::MAX_TABLES];           // log2 of a live table's entries at the input; its number t
     u64 in[pcs::MAX_TABLES], out[pcs::MAX_TABLES];          // where it lies in the input and where it goes in the output (entries)
 };
+// What differs by member (blockIdx.z) of a launch: where its raw rows lie (a handle may live in any slab, and may appear twice), the
+// fold constants of its challenge, and a fixed stride into the group's g, buffer pairs and scalars. A group of one - the single call -
+// carries its row base and its fold constants in the kernel arguments (rows == null, fk == null): its launches need no table and no
+// upload.
+struct BnFoldMembers {
+    const Fr* const* rows;
+    const Fr* rows0;
+    const FoldK* fk;
+    FoldK fk0;
+    u64 g_stride, in_stride, out_stride, scal_stride;   // entries from a member to the next: g, the input pair, the output pair, the scalars
+};
+__device__ __forceinline__ const Fr* bnfold_rows(const BnFoldMembers& M) { return M.rows ? M.rows[blockIdx.z] : M.rows0; }
 // g_t[x] = sum_{i on t} beta^i eq(z_i, x), every entry written once: a thread owns entry x and walks the table's claims, each a product of
-// two staged factors (Montgomery form, canonical; beta^i lies in the low one). Loose on the way out.
-__global__ __launch_bounds__(BNFOLD_TPB) void k_bnpcsfold_g(const BnFoldGTables A, const char* __restrict__ stage, size_t fac_at, Fr* __restrict__ g) {
+// two staged factors (Montgomery form, canonical; beta^i lies in the low one). Loose on the way out. stage: G BnFoldGMember, then the
+// members' blocks. The first workgroup of a member also copies the elements of its one-element tables (canonical, as the rows hold
+// them) to scal[2 t].
+__global__ __launch_bounds__(BNFOLD_TPB) void k_bnpcsfold_g(const BnFoldGTables A, const BnFoldMembers M, const char* __restrict__ stage, Fr* __restrict__ g,
+                                                            Fr* __restrict__ scal) {
     const unsigned t = blockIdx.y;
+    if (blockIdx.x == 0 && t == 0 && threadIdx.x == 0)
+        for (unsigned i = 0; i < A.n1; i++) lz_gstore(scal + (size_t)blockIdx.z * M.scal_stride + 2 * A.id1[i], lz_gload(bnfold_rows(M) + A.at1[i]));
+    if (t >= A.nt) return;
     const size_t len = (size_t)1 << A.lg[t];
-    const BnFoldClaim* cl = reinterpret_cast<const BnFoldClaim*>(stage);
-    const Fr* fac = reinterpret_cast<const Fr*>(stage + fac_at);
+    const BnFoldGMember D = reinterpret_cast<const BnFoldGMember*>(stage)[blockIdx.z];
+    const u32* claim0 = reinterpret_cast<const u32*>(stage + D.claim0_at);
+    const BnFoldClaim* cl = reinterpret_cast<const BnFoldClaim*>(stage + D.claims_at);
+    const Fr* fac = reinterpret_cast<const Fr*>(stage + D.fac_at);
+    const unsigned first = claim0[t], last = claim0[t + 1];
+    Fr* G = g + (size_t)blockIdx.z * M.g_stride + A.at[t];
     for (size_t x = (size_t)blockIdx.x * BNFOLD_TPB + threadIdx.x; x < len; x += (size_t)gridDim.x * BNFOLD_TPB) {
         WCol acc = wcol_zero();
         Fr sum = fr_zero();
         int trips = 0;
-        for (unsigned i = A.claim0[t]; i < A.claim0[t + 1]; i++) {
+        for (unsigned i = first; i < last; i++) {
             const BnFoldClaim d = cl[i];
             wcol_mac(acc, lz_gload(fac + d.lo_at + (x & (((size_t)1 << d.lo_bits) - 1))), lz_gload(fac + d.hi_at + (x >> d.lo_bits)));
             if (++trips == BNFOLD_G_TRIPS) { sum = lz_add(sum, lz_reduce(acc)); acc = wcol_zero(); trips = 0; }
         }
-        lz_gstore(g + A.at[t] + x, lz_add(sum, lz_reduce(acc)));
+        lz_gstore(G + x, lz_add(sum, lz_reduce(acc)));
     }
 }
-// the three sums of a thread (loose) -> those of its workgroup at out[3 b .. 3 b + 3), b = its number in the grid, canonical if `canon`;
-// every thread calls it
+// the three sums of a thread (loose) -> those of its workgroup at out[3 b .. 3 b + 3), b = its number in the grid (members outermost),
+// canonical if `canon`; every thread calls it
 __device__ __forceinline__ void bnfold_block_sums(const Fr (&s)[3], Fr* __restrict__ out, bool canon) {
     __shared__ Fr part[3][BNFOLD_TPB];
 #pragma unroll
@@ -659,7 +689,7 @@ __device__ __forceinline__ void bnfold_block_sums(const Fr (&s)[3], Fr* __restri
     }
     if (threadIdx.x < 3) {
         const Fr v = part[threadIdx.x][0];
-        lz_gstore(out + 3 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x) + threadIdx.x, canon ? lz_canon(v) : v);
+        lz_gstore(out + 3 * (((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) + threadIdx.x, canon ? lz_canon(v) : v);
     }
 }
 // the accumulators of a unit's three products, restarted every BNFOLD_TRIPS units into the loose sums s
@@ -682,11 +712,11 @@ __device__ __forceinline__ void bnfold_acc_finish(BnFoldAcc& w, Fr (&s)[3]) {
 }
 // Round 0: nothing to fold. A unit is a pair (T0, T1) of the raw rows, (g0, g1) of g:
 // s(0) += g0 T0, s(1) += g1 T1, c2 += (g1 - g0) (T1 - T0)
-__global__ __launch_bounds__(BNFOLD_TPB) void k_bnpcsfold_round0(const BnFoldTables A, const Fr* __restrict__ rows, const Fr* __restrict__ g, Fr* __restrict__ partial) {
+__global__ __launch_bounds__(BNFOLD_TPB) void k_bnpcsfold_round0(const BnFoldTables A, const BnFoldMembers M, const Fr* __restrict__ g, Fr* __restrict__ partial) {
     const unsigned t = blockIdx.y;
     const size_t pairs = (size_t)1 << (A.lg[t] - 1);
-    const Fr* T = rows + A.in[t];
-    const Fr* G = g + A.in[t];
+    const Fr* T = bnfold_rows(M) + A.in[t];
+    const Fr* G = g + (size_t)blockIdx.z * M.g_stride + A.in[t];
     BnFoldAcc w{wcol_zero(), wcol_zero(), wcol_zero(), 0};
     Fr s[3] = {fr_zero(), fr_zero(), fr_zero()};
     for (size_t u = (size_t)blockIdx.x * BNFOLD_TPB + threadIdx.x; u < pairs; u += (size_t)gridDim.x * BNFOLD_TPB)
@@ -694,14 +724,30 @@ __global__ __launch_bounds__(BNFOLD_TPB) void k_bnpcsfold_round0(const BnFoldTab
     bnfold_acc_finish(w, s);
     bnfold_block_sums(s, partial, false);
 }
-// Round j >= 1. A unit is four adjacent entries of T and of g: folded by r_{j-1} (fk = its fold_consts) into two of each, which are
-// stored and enter the sums of round j while they are in registers. Round 1 reads T from the raw rows, later rounds from the other buffer
-// pair. A table of two entries is folded into its two scalars at scal[2 id], scal[2 id + 1] (canonical) by one thread and enters no sum.
-__global__ __launch_bounds__(BNFOLD_TPB) void k_bnpcsfold_round(const BnFoldTables A, const Fr* __restrict__ tin, const Fr* __restrict__ gin, Fr* __restrict__ tout,
-                                                                Fr* __restrict__ gout, const FoldK fk, Fr* __restrict__ scal, Fr* __restrict__ partial) {
+// Round j >= 1. A unit is four adjacent entries of T and of g: folded by the member's r_{j-1} (its fold_consts) into two of each,
+// which are stored and enter the sums of round j while they are in registers. Round 1 (tin == null) reads T from the member's raw
+// rows and gin is g (in_stride = g_stride), later rounds read the other buffer pair. A table of two entries is folded into its two
+// scalars at scal[2 id], scal[2 id + 1] of its member (canonical) by one thread and enters no sum.
+// The 64 fold constants stay in SGPRs for the whole kernel in either instantiation. GROUP: the member's set is read from the table
+// at blockIdx.z, an index that is uniform over the wavefront, so the reads are scalar loads (lz_load_k's readfirstlane folds away).
+// !GROUP, the single call: the set comes with the kernel arguments and there is one member, as before the kernels took a group. Two
+// instantiations, not one kernel that chooses at run time: merging the two sources after a branch cost the allocator its SGPRs
+// (the constants were spilled to VGPR lanes and read back in the loop).
+template <bool GROUP>
+__global__ __launch_bounds__(BNFOLD_TPB) void k_bnpcsfold_round(const BnFoldTables A, const BnFoldMembers M, const Fr* __restrict__ tin, const Fr* __restrict__ gin,
+                                                                Fr* __restrict__ tout, Fr* __restrict__ gout, Fr* __restrict__ scal, Fr* __restrict__ partial) {
     const unsigned t = blockIdx.y, lg = A.lg[t];
-    const Fr* T = tin + A.in[t];
-    const Fr* G = gin + A.in[t];
+    const size_t z = GROUP ? blockIdx.z : 0;
+    LzK fk;
+    if constexpr (GROUP) {
+        fk = lz_load_k(M.fk[z].k);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 64; i++) fk.k[i] = M.fk0.k[i];
+    }
+    const size_t in_at = z * M.in_stride + A.in[t];
+    const Fr* T = tin ? tin + in_at : (GROUP ? M.rows[z] : M.rows0) + A.in[t];
+    const Fr* G = gin + in_at;
     // X[2i] + r (X[2i+1] - X[2i])
     auto fold = [&](const Fr* X, size_t i) {
         const Fr x0 = lz_gload(X + 2 * i);
@@ -711,13 +757,14 @@ __global__ __launch_bounds__(BNFOLD_TPB) void k_bnpcsfold_round(const BnFoldTabl
     Fr s[3] = {fr_zero(), fr_zero(), fr_zero()};
     if (lg == 1) {
         if (blockIdx.x == 0 && threadIdx.x == 0) {
-            lz_gstore(scal + 2 * A.id[t], lz_canon(fold(T, 0)));
-            lz_gstore(scal + 2 * A.id[t] + 1, lz_canon(fold(G, 0)));
+            Fr* sc = scal + z * M.scal_stride + 2 * A.id[t];
+            lz_gstore(sc, lz_canon(fold(T, 0)));
+            lz_gstore(sc + 1, lz_canon(fold(G, 0)));
         }
     } else {
-        const size_t units = (size_t)1 << (lg - 2);
-        Fr* To = tout + A.out[t];
-        Fr* Go = gout + A.out[t];
+        const size_t units = (size_t)1 << (lg - 2), out_at = z * M.out_stride + A.out[t];
+        Fr* To = tout + out_at;
+        Fr* Go = gout + out_at;
         for (size_t u = (size_t)blockIdx.x * BNFOLD_TPB + threadIdx.x; u < units; u += (size_t)gridDim.x * BNFOLD_TPB) {
             const Fr t0 = fold(T, 2 * u), t1 = fold(T, 2 * u + 1), g0 = fold(G, 2 * u), g1 = fold(G, 2 * u + 1);
             lz_gstore(To + 2 * u, t0);
@@ -730,16 +777,159 @@ __global__ __launch_bounds__(BNFOLD_TPB) void k_bnpcsfold_round(const BnFoldTabl
     bnfold_acc_finish(w, s);
     bnfold_block_sums(s, partial, false);
 }
-// one workgroup: out[k] = sum_b partial[3 b + k], canonical
+// one workgroup a member (blockIdx.x): out[3 member + k] = sum_b partial[3 (member blocks + b) + k], canonical
 __global__ __launch_bounds__(BNFOLD_TPB) void k_bnpcsfold_sum(const Fr* __restrict__ partial, size_t blocks, Fr* __restrict__ out) {
+    const Fr* mine = partial + 3 * blocks * blockIdx.x;
     Fr s[3] = {fr_zero(), fr_zero(), fr_zero()};
     for (size_t b = threadIdx.x; b < blocks; b += BNFOLD_TPB)
-        for (int k = 0; k < 3; k++) s[k] = lz_add(s[k], lz_gload(partial + 3 * b + k));
+        for (int k = 0; k < 3; k++) s[k] = lz_add(s[k], lz_gload(mine + 3 * b + k));
     bnfold_block_sums(s, out, true);
 }
 
-// The device form of PcsFoldSource. Scratch from the context's arena (reset here; the handle's matrices are its own): g (32 bytes a table
-// entry), the two buffer pairs (a half and a quarter of that for T and for g each), the partials, the sums and the scalars.
+// ---- what the single call (BnFoldDev) and the pass over a group (open_folded_batch_flow of pcs_flow.hpp) share on the host: the
+// geometry a shape fixes, a member's block of the g kernel's staged copy, the launches of the g kernel and of a round
+static BnFoldGTables bnfold_g_tables(const pcs::Shape& sh, size_t* max_len) {
+    BnFoldGTables A;
+    memset(&A, 0, sizeof(A));
+    *max_len = 1;
+    for (size_t t = 0; t < sh.nvars.size(); t++) {
+        const size_t v = (size_t)sh.nvars[t], at = sh.off[t] << sh.c;
+        if (v == 0) { A.id1[A.n1] = (u32)t; A.at1[A.n1] = (u64)at; A.n1++; continue; }   // a scalar from the start: T_t() is the element, g_t() = sum beta^i
+        A.lg[A.nt] = (u32)v;
+        A.at[A.nt] = (u64)at;
+        A.nt++;
+        *max_len = std::max(*max_len, (size_t)1 << v);
+    }
+    return A;
+}
+static size_t bnfold_up(size_t x) { return (x + 31) & ~(size_t)31; }
+// the bytes of a member's block, a multiple of 32
+static size_t bnfold_gblock_bytes(const pcs::Shape& sh, const BnFoldGTables& A, const std::vector<PcsClaim>& claims) {
+    size_t nc = 0, fac = 0;
+    for (const PcsClaim& cl : claims) {
+        const size_t v = (size_t)sh.nvars[cl.table], lo_bits = (v + 1) / 2;
+        if (v == 0) continue;
+        nc++;
+        fac += ((size_t)1 << lo_bits) + ((size_t)1 << (v - lo_bits));
+    }
+    return bnfold_up((A.nt + 1) * sizeof(u32)) + bnfold_up(nc * sizeof(BnFoldClaim)) + fac * sizeof(Fr);
+}
+// writes the block at byte `at` (a multiple of 32) of the staged copy and its descriptor: the claims in table order, per claim the two
+// factor tables, beta^i in the low one; G1[t] = g_t() of the one-element tables (Montgomery form)
+static void bnfold_gblock_fill(char* stage, BnFoldGMember& d, size_t at, const pcs::Shape& sh, const BnFoldGTables& A, const std::vector<PcsClaim>& claims,
+                               const std::vector<Fr>& bpow, std::vector<Fr>& G1) {
+    size_t nc = 0;
+    for (const PcsClaim& cl : claims) nc += sh.nvars[cl.table] != 0;
+    d.claim0_at = at;
+    d.claims_at = d.claim0_at + bnfold_up((A.nt + 1) * sizeof(u32));
+    d.fac_at = d.claims_at + bnfold_up(nc * sizeof(BnFoldClaim));
+    d.pad = 0;
+    u32* claim0 = reinterpret_cast<u32*>(stage + d.claim0_at);
+    BnFoldClaim* list = reinterpret_cast<BnFoldClaim*>(stage + d.claims_at);
+    Fr* fac = reinterpret_cast<Fr*>(stage + d.fac_at);
+    size_t k = 0, f = 0, kt = 0;   // claims and factors written; the kernel's table number
+    claim0[0] = 0;
+    G1.assign(sh.nvars.size(), fr_zero());
+    for (size_t t = 0; t < sh.nvars.size(); t++) {
+        const size_t v = (size_t)sh.nvars[t], lo_bits = (v + 1) / 2;
+        for (size_t i = 0; i < claims.size(); i++) {
+            if (claims[i].table != t) continue;
+            if (v == 0) { G1[t] = fr_add(G1[t], bpow[i]); continue; }
+            std::vector<Fr> lo = pcs_eq_table(claims[i].point.data(), lo_bits);
+            const std::vector<Fr> hi = pcs_eq_table(claims[i].point.data() + lo_bits, v - lo_bits);
+            for (Fr& x : lo) x = fr_mul(x, bpow[i]);
+            list[k++] = BnFoldClaim{(u64)f, (u64)(f + lo.size()), (u32)lo_bits, 0};
+            memcpy(fac + f, lo.data(), lo.size() * sizeof(Fr));
+            memcpy(fac + f + lo.size(), hi.data(), hi.size() * sizeof(Fr));
+            f += lo.size() + hi.size();
+        }
+        if (v != 0) claim0[++kt] = (u32)k;
+    }
+}
+// the workgroups a table of a launch over nt tables of G members whose largest has `units` units: max_blocks bounds the launch as a
+// whole, and a table of a member always gets at least one
+static unsigned bnfold_blocks_of(unsigned max_blocks, size_t units, size_t nt, size_t G) {
+    const size_t cap = std::max<size_t>(1, max_blocks / (nt * G));
+    return (unsigned)std::max<size_t>(1, std::min(cap, (units + BNFOLD_TPB - 1) / BNFOLD_TPB));
+}
+// the tables live in step j and where they lie; retire: one of them is folded to its scalars; units: those of the largest; entries: in all
+static BnFoldTables bnfold_tables(const pcs::Shape& sh, size_t j, bool* retire, size_t* max_units, size_t* entries) {
+    BnFoldTables A;
+    memset(&A, 0, sizeof(A));
+    *retire = false;
+    *max_units = 1;
+    *entries = 0;
+    for (size_t t = 0; t < sh.nvars.size(); t++) {
+        const size_t v = (size_t)sh.nvars[t], at = sh.off[t] << sh.c;
+        if (v == 0 || v < j) continue;   // a scalar already
+        const size_t lg = j == 0 ? v : v - (j - 1);
+        A.lg[A.nt] = (u32)lg;
+        A.id[A.nt] = (u32)t;
+        A.in[A.nt] = j == 0 ? at : at >> (j - 1);
+        A.out[A.nt] = at >> j;
+        A.nt++;
+        *retire |= j > 0 && lg == 1;
+        *max_units = std::max(*max_units, j == 0 ? (size_t)1 << (lg - 1) : lg == 1 ? 1 : (size_t)1 << (lg - 2));
+        *entries += (size_t)1 << lg;
+    }
+    return A;
+}
+// the arena buffers of G reductions: g (32 bytes a table entry), the two buffer pairs (a half and a quarter of that for T and for g
+// each, member after member), the partials (3 a workgroup: max_blocks bounds a launch, but a table of a member has at least one), the
+// sums and the scalars
+struct BnFoldBufs {
+    Fr *g, *t[2], *gg[2], *scal, *partial, *sums;
+    size_t stride[2];   // entries a member of pair 0 and of pair 1
+};
+static BnFoldBufs bnfold_alloc(hg_ctx* ctx, const pcs::Shape& sh, size_t G, unsigned max_blocks) {
+    const size_t W = sh.R << sh.c, m = sh.nvars.size();
+    BnFoldBufs b;
+    b.stride[0] = W / 2 + 1;
+    b.stride[1] = W / 4 + 1;
+    b.g = ctx->alloc_n<Fr>(G * W);
+    for (int p = 0; p < 2; p++) {
+        b.t[p] = ctx->alloc_n<Fr>(G * b.stride[p]);
+        b.gg[p] = ctx->alloc_n<Fr>(G * b.stride[p]);
+    }
+    b.scal = ctx->alloc_n<Fr>(G * 2 * m);
+    b.partial = ctx->alloc_n<Fr>(3 * ((size_t)max_blocks + pcs::MAX_TABLES * G));
+    b.sums = ctx->alloc_n<Fr>(3 * G);
+    return b;
+}
+// a member table: rows and fk null for a group of one, which sets rows0 and fk0
+static BnFoldMembers bnfold_members(const pcs::Shape& sh, const Fr* const* rows, const FoldK* fk) {
+    BnFoldMembers M;
+    memset(&M, 0, sizeof(M));
+    M.rows = rows;
+    M.fk = fk;
+    M.g_stride = sh.R << sh.c;
+    M.scal_stride = 2 * sh.nvars.size();
+    return M;
+}
+static void bnfold_g_launch(hipStream_t st, unsigned max_blocks, const BnFoldGTables& A, size_t max_len, size_t G, const BnFoldMembers& M, const char* d_stage,
+                            const BnFoldBufs& b) {
+    const size_t nt = std::max<size_t>(A.nt, 1);   // (a shape of one-element tables alone: the first workgroup of a member copies them)
+    k_bnpcsfold_g<<<dim3(bnfold_blocks_of(max_blocks, max_len, nt, G), (unsigned)nt, (unsigned)G), BNFOLD_TPB, 0, st>>>(A, M, d_stage, b.g, b.scal);
+}
+// the launch of step j over G members (A.nt >= 1) and, `sums`, of the workgroup a member that adds its partials
+static void bnfold_launch(hipStream_t st, unsigned max_blocks, const pcs::Shape& sh, size_t j, const BnFoldTables& A, size_t max_units, size_t G, BnFoldMembers M,
+                          const BnFoldBufs& b, bool sums) {
+    const size_t W = sh.R << sh.c;
+    const dim3 grid(bnfold_blocks_of(max_blocks, max_units, A.nt, G), A.nt, (unsigned)G);
+    M.in_stride = j <= 1 ? W : b.stride[j & 1];
+    M.out_stride = j == 0 ? 0 : b.stride[(j - 1) & 1];
+    const Fr *tin = j == 1 ? nullptr : b.t[j & 1], *gin = j == 1 ? b.g : b.gg[j & 1];
+    if (j == 0) k_bnpcsfold_round0<<<grid, BNFOLD_TPB, 0, st>>>(A, M, b.g, b.partial);
+    else if (M.fk) k_bnpcsfold_round<true><<<grid, BNFOLD_TPB, 0, st>>>(A, M, tin, gin, b.t[(j - 1) & 1], b.gg[(j - 1) & 1], b.scal, b.partial);
+    else k_bnpcsfold_round<false><<<grid, BNFOLD_TPB, 0, st>>>(A, M, tin, gin, b.t[(j - 1) & 1], b.gg[(j - 1) & 1], b.scal, b.partial);
+    if (sums) k_bnpcsfold_sum<<<(unsigned)G, BNFOLD_TPB, 0, st>>>(b.partial, (size_t)grid.x * grid.y, b.sums);
+}
+// the bytes step j moves over `entries` table entries: round 0 reads 32 + 32 an entry, a later round reads them and writes 32 + 32 for
+// every two
+static double bnfold_step_bytes(size_t j, size_t entries) { return (double)entries * (j == 0 ? 64 : 96); }
+
+// The device form of PcsFoldSource: a group of one through the kernels above. Scratch from the context's arena (reset here; the
+// handle's matrices are its own).
 struct BnFoldDev : PcsFoldSource {
     const pcs::Commitment& cm;
     hg_ctx* ctx;
@@ -748,15 +938,16 @@ struct BnFoldDev : PcsFoldSource {
     size_t n_claims;
     unsigned max_blocks;
     std::string me;
-    Fr *d_g, *d_t[2], *d_gg[2], *d_scal, *d_partial, *d_sums;
-    std::vector<Fr> h_scal;
+    BnFoldBufs buf;
+    BnFoldMembers mem;
+    bool one_element;       // the shape has one-element tables: their elements come back with step 0
+    std::vector<Fr> h_scal, G1;
     Fr h_sums[3];
 
     BnFoldDev(const char* who, const pcs::Commitment& cm_, const std::vector<PcsClaim>& claims, const std::vector<Fr>& bpow)
         : cm(cm_), ctx(cm_.ctx), n_claims(claims.size()), me(who) {
         const pcs::Shape& sh = cm.sh;
         const size_t m = sh.nvars.size(), W = sh.R << sh.c;
-        const Fr* d_rows = reinterpret_cast<const Fr*>(cm.d_rows);
         hipc(hipSetDevice(ctx->device), "hipSetDevice");
         ctx->arena_reset();
         st = ctx->stream;
@@ -766,112 +957,56 @@ struct BnFoldDev : PcsFoldSource {
         T.assign(m, fr_zero());
         G.assign(m, fr_zero());
         h_scal.assign(2 * m, fr_zero());
-        // the claims in table order; per claim the two factor tables, beta^i in the low one
-        BnFoldGTables A;
-        memset(&A, 0, sizeof(A));
-        std::vector<BnFoldClaim> list;
-        std::vector<Fr> fac;
-        size_t max_len = 0;
-        for (size_t t = 0; t < m; t++) {
-            const size_t v = (size_t)sh.nvars[t], lo_bits = (v + 1) / 2;
-            if (v == 0) {   // a table of one element is a scalar from the start: T_t() is the element, g_t() = sum beta^i
-                hipc(hipMemcpyAsync(&T[t], d_rows + (sh.off[t] << sh.c), sizeof(Fr), hipMemcpyDeviceToHost, st), "download a one-element table");
-                hipc(hipStreamSynchronize(st), (me + ": sync").c_str());
-                for (size_t i = 0; i < claims.size(); i++)
-                    if (claims[i].table == t) G[t] = fr_add(G[t], bpow[i]);
-                continue;
-            }
-            for (size_t i = 0; i < claims.size(); i++) {
-                if (claims[i].table != t) continue;
-                std::vector<Fr> lo = pcs_eq_table(claims[i].point.data(), lo_bits);
-                const std::vector<Fr> hi = pcs_eq_table(claims[i].point.data() + lo_bits, v - lo_bits);
-                for (Fr& x : lo) x = fr_mul(x, bpow[i]);
-                list.push_back(BnFoldClaim{(u64)fac.size(), (u64)(fac.size() + lo.size()), (u32)lo_bits, 0});
-                fac.insert(fac.end(), lo.begin(), lo.end());
-                fac.insert(fac.end(), hi.begin(), hi.end());
-            }
-            A.lg[A.nt] = (u32)v;
-            A.at[A.nt] = (u64)(sh.off[t] << sh.c);
-            A.nt++;   // (the kernel's table number, which skips the one-element tables; claim0[0] = 0)
-            A.claim0[A.nt] = (u32)list.size();
-            max_len = std::max(max_len, (size_t)1 << v);
-        }
-        const size_t fac_at = (list.size() * sizeof(BnFoldClaim) + 31) & ~(size_t)31;
-        std::vector<char> stage(fac_at + fac.size() * sizeof(Fr) + 32);
-        if (!list.empty()) memcpy(stage.data(), list.data(), list.size() * sizeof(BnFoldClaim));
-        if (!fac.empty()) memcpy(stage.data() + fac_at, fac.data(), fac.size() * sizeof(Fr));
+        size_t max_len;
+        const BnFoldGTables A = bnfold_g_tables(sh, &max_len);
+        one_element = A.n1 != 0;
+        mem = bnfold_members(sh, nullptr, nullptr);
+        mem.rows0 = reinterpret_cast<const Fr*>(cm.d_rows);
+        std::vector<char> stage(sizeof(BnFoldGMember) + bnfold_gblock_bytes(sh, A, claims) + 32);
+        static_assert(sizeof(BnFoldGMember) % 32 == 0, "a member's block starts at a multiple of 32");
+        BnFoldGMember d;
+        bnfold_gblock_fill(stage.data(), d, sizeof(BnFoldGMember), sh, A, claims, bpow, G1);
+        memcpy(stage.data(), &d, sizeof(d));
         char* d_stage;
         try {
-            d_g = ctx->alloc_n<Fr>(W);
-            d_t[0] = ctx->alloc_n<Fr>(W / 2 + 1);
-            d_gg[0] = ctx->alloc_n<Fr>(W / 2 + 1);
-            d_t[1] = ctx->alloc_n<Fr>(W / 4 + 1);
-            d_gg[1] = ctx->alloc_n<Fr>(W / 4 + 1);
-            d_scal = ctx->alloc_n<Fr>(2 * m);
-            d_partial = ctx->alloc_n<Fr>(3 * ((size_t)max_blocks + pcs::MAX_TABLES));
-            d_sums = ctx->alloc_n<Fr>(3);
+            buf = bnfold_alloc(ctx, sh, 1, max_blocks);
             d_stage = ctx->alloc_n<char>(stage.size());
         } catch (const std::exception& e) {
             throw Error(std::string("the context's arena cannot hold the reduction (") + e.what() + ")");
         }
-        if (!A.nt) return;
         hipc(hipMemcpyAsync(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, st), "upload factor tables");
-        ctx->prof_begin(cls, (double)W * 32 + (double)fac.size() * 32);
-        k_bnpcsfold_g<<<dim3(blocks_of(max_len, A.nt), A.nt), BNFOLD_TPB, 0, st>>>(A, d_stage, fac_at, d_g);
+        ctx->prof_begin(cls, (double)W * 32 + (double)stage.size());
+        bnfold_g_launch(st, max_blocks, A, max_len, 1, mem, d_stage, buf);
         ctx->prof_end();
         hipc(hipStreamSynchronize(st), (me + ": sync").c_str());   // (the staged copy is a local)
         hipc(hipGetLastError(), (me + ": launch").c_str());
     }
-    // the workgroups a table of a launch over nt tables whose largest has `units` units
-    unsigned blocks_of(size_t units, unsigned nt) const {
-        const size_t cap = std::max<size_t>(1, max_blocks / nt);
-        return (unsigned)std::max<size_t>(1, std::min(cap, (units + BNFOLD_TPB - 1) / BNFOLD_TPB));
-    }
     void step(size_t j, const Fr& r, Fr s[3]) override {
         const pcs::Shape& sh = cm.sh;
         const size_t m = sh.nvars.size(), V = pcs::fold_rounds(sh);
-        BnFoldTables A;
-        memset(&A, 0, sizeof(A));
-        bool retire = false;
-        size_t max_units = 1, entries = 0;
-        for (size_t t = 0; t < m; t++) {
-            const size_t v = (size_t)sh.nvars[t], at = sh.off[t] << sh.c;
-            if (v == 0 || v < j) continue;   // a scalar already
-            const size_t lg = j == 0 ? v : v - (j - 1);
-            A.lg[A.nt] = (u32)lg;
-            A.id[A.nt] = (u32)t;
-            A.in[A.nt] = j == 0 ? at : at >> (j - 1);
-            A.out[A.nt] = at >> j;
-            A.nt++;
-            retire |= j > 0 && lg == 1;
-            max_units = std::max(max_units, j == 0 ? (size_t)1 << (lg - 1) : lg == 1 ? 1 : (size_t)1 << (lg - 2));
-            entries += (size_t)1 << lg;
-        }
+        bool retire;
+        size_t max_units, entries;
+        const BnFoldTables A = bnfold_tables(sh, j, &retire, &max_units, &entries);
+        retire |= j == 0 && one_element;
         if (s) s[0] = s[1] = s[2] = fr_zero();
-        if (!A.nt) return;
-        const dim3 grid(blocks_of(max_units, A.nt), A.nt);
+        if (!A.nt && !retire) return;
         ctx->prof_stream = st;
-        // round 0 reads 32 + 32 bytes an entry, a later round reads them and writes 32 + 32 for every two
-        ctx->prof_begin(cls, (double)entries * (j == 0 ? 64 : 96));
-        if (j == 0) {
-            k_bnpcsfold_round0<<<grid, BNFOLD_TPB, 0, st>>>(A, reinterpret_cast<const Fr*>(cm.d_rows), d_g, d_partial);
-        } else {
-            FoldK fk;
-            fold_consts(fr_to_mont(r), &fk);
-            const Fr* tin = j == 1 ? reinterpret_cast<const Fr*>(cm.d_rows) : d_t[j & 1];
-            const Fr* gin = j == 1 ? d_g : d_gg[j & 1];
-            k_bnpcsfold_round<<<grid, BNFOLD_TPB, 0, st>>>(A, tin, gin, d_t[(j - 1) & 1], d_gg[(j - 1) & 1], fk, d_scal, d_partial);
+        if (A.nt) {
+            if (j > 0) fold_consts(fr_to_mont(r), &mem.fk0);
+            ctx->prof_begin(cls, bnfold_step_bytes(j, entries));
+            bnfold_launch(st, max_blocks, sh, j, A, max_units, 1, mem, buf, s != nullptr);
+            ctx->prof_end();
+            if (s) hipc(hipMemcpyAsync(h_sums, buf.sums, sizeof(h_sums), hipMemcpyDeviceToHost, st), "download the round's sums");
         }
-        if (s) k_bnpcsfold_sum<<<1, BNFOLD_TPB, 0, st>>>(d_partial, (size_t)grid.x * grid.y, d_sums);
-        ctx->prof_end();
-        if (s) hipc(hipMemcpyAsync(h_sums, d_sums, sizeof(h_sums), hipMemcpyDeviceToHost, st), "download the round's sums");
-        if (retire) hipc(hipMemcpyAsync(h_scal.data(), d_scal, 2 * m * sizeof(Fr), hipMemcpyDeviceToHost, st), "download the retired tables' scalars");
+        if (retire) hipc(hipMemcpyAsync(h_scal.data(), buf.scal, 2 * m * sizeof(Fr), hipMemcpyDeviceToHost, st), "download the retired tables' scalars");
         hipc(hipStreamSynchronize(st), (me + ": sync").c_str());
         hipc(hipGetLastError(), (me + ": launch").c_str());
         ctx->prof_collect();
-        if (s) memcpy(s, h_sums, sizeof(h_sums));
-        for (size_t t = 0; t < m; t++)
+        if (s && A.nt) memcpy(s, h_sums, sizeof(h_sums));
+        for (size_t t = 0; t < m; t++) {
+            if (j == 0 && sh.nvars[t] == 0) { T[t] = h_scal[2 * t]; G[t] = G1[t]; }
             if (j > 0 && (size_t)sh.nvars[t] == j) { T[t] = h_scal[2 * t]; G[t] = h_scal[2 * t + 1]; }
+        }
         if (j == V && hg_debug("plan"))   // (read at every call: the tests switch it per case)
             fprintf(stderr, "[hg plan] bnpcsfold V=%zu dev_rounds=%zu host_rounds=0 tables=%zu claims=%zu\n", V, V, m, n_claims);
     }
@@ -880,3 +1015,45 @@ std::unique_ptr<PcsFoldSource> pcs_fold_source_device(const char* who, const pcs
     return std::unique_ptr<PcsFoldSource>(new BnFoldDev(who, cm, claims, bpow));
 }
 
+// ---- the batch forms of the folded openings. The verifier is verify_batch_flow with the member blocks prepared from the folded
+// headers; the opener is open_folded_batch_flow over the reduction's kernels and helpers above. A challenge goes up as its 64 fold
+// constants (G x 256 bytes a round), which the round kernel reads at blockIdx.z.
+struct BnFoldPcs : BnPcs {
+    typedef PcsFoldProver FoldProver;
+    typedef BnFoldGTables FoldGTables;
+    typedef BnFoldGMember FoldGMember;
+    typedef BnFoldTables FoldTables;
+    typedef BnFoldMembers FoldMembers;
+    typedef BnFoldBufs FoldBufs;
+    typedef FoldK FoldChal;
+    static constexpr const char *CLS_FOLD_BATCH = "pcs_fold_batch_bn254", *PLAN_FOLD_BATCH = "bnpcsfoldb";
+    static unsigned fold_max_blocks() { return bnfold_max_blocks(); }
+    static FoldGTables fold_g_tables(const pcs::Shape& sh, size_t* max_len) { return bnfold_g_tables(sh, max_len); }
+    static size_t fold_gblock_bytes(const pcs::Shape& sh, const FoldGTables& A, const std::vector<PcsClaim>& claims) { return bnfold_gblock_bytes(sh, A, claims); }
+    static void fold_gblock_fill(char* stage, FoldGMember& d, size_t at, const pcs::Shape& sh, const FoldGTables& A, const std::vector<PcsClaim>& claims, const std::vector<Fr>& bpow,
+                                 std::vector<Fr>& G1) {
+        bnfold_gblock_fill(stage, d, at, sh, A, claims, bpow, G1);
+    }
+    static FoldBufs fold_alloc(hg_ctx* ctx, const pcs::Shape& sh, size_t G, unsigned max_blocks) { return bnfold_alloc(ctx, sh, G, max_blocks); }
+    static FoldTables fold_tables(const pcs::Shape& sh, size_t j, bool* retire, size_t* max_units, size_t* entries) { return bnfold_tables(sh, j, retire, max_units, entries); }
+    static FoldK fold_chal(const Fr& r) {   // r canonical
+        FoldK k;
+        fold_consts(fr_to_mont(r), &k);
+        return k;
+    }
+    static FoldMembers fold_members(const pcs::Shape& sh, const Fr* const* rows, const FoldK* fk) { return bnfold_members(sh, rows, fk); }
+    static void fold_g_launch(hipStream_t st, unsigned max_blocks, const FoldGTables& A, size_t max_len, size_t G, const FoldMembers& M, const char* d_stage, const FoldBufs& b) {
+        bnfold_g_launch(st, max_blocks, A, max_len, G, M, d_stage, b);
+    }
+    static void fold_launch(hipStream_t st, unsigned max_blocks, const pcs::Shape& sh, size_t j, const FoldTables& A, size_t max_units, size_t G, const FoldMembers& M,
+                            const FoldBufs& b, bool sums) {
+        bnfold_launch(st, max_blocks, sh, j, A, max_units, G, M, b, sums);
+    }
+    static double fold_step_bytes(size_t j, size_t entries) { return bnfold_step_bytes(j, entries); }
+};
+std::vector<std::string> pcs_verify_folded_device_batch(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const std::vector<VerifyItem>& items, size_t Q) {
+    return pcs::verify_batch_flow<BnPcs>(who, ctx, sh, items, Q, true);
+}
+std::vector<pcs::Opened> pcs_open_folded_device_batch(const char* who, const char* single, hg_ctx* ctx, const std::vector<PcsOpenItem>& items, size_t Q) {
+    return pcs::open_folded_batch_flow<BnFoldPcs>(who, single, ctx, items, Q);
+}

@@ -179,7 +179,6 @@ struct GlAbi {
         return pcs::open_device_batch(who, single, ctx, items, Q);
     }
     // the batch forms of the folded openings
-    static constexpr bool FOLDED_BATCH = true;
     static size_t folded_opening_bytes(const pcs::Shape& sh, size_t Q) { return pcs::folded_opening_bytes(sh, Q); }
     static std::vector<pcs::Opened> pcs_open_folded_batch(const char* who, const char* single, hg_ctx* ctx, const std::vector<PcsOpenItem>& items, size_t Q) {
         return pcs::open_folded_device_batch(who, single, ctx, items, Q);
@@ -260,7 +259,14 @@ struct BnAbi {
     static std::vector<pcs::Opened> pcs_open_batch(const char* who, const char* single, hg_ctx* ctx, const std::vector<PcsOpenItem>& items, size_t Q) {
         return bn::pcs_open_device_batch(who, single, ctx, items, Q);
     }
-    static constexpr bool FOLDED_BATCH = false;   // (folded openings have no batch forms over BN254 yet: the folded switches below are never set)
+    // the batch forms of the folded openings
+    static size_t folded_opening_bytes(const pcs::Shape& sh, size_t Q) { return bn::pcs_folded_opening_bytes(sh, Q); }
+    static std::vector<pcs::Opened> pcs_open_folded_batch(const char* who, const char* single, hg_ctx* ctx, const std::vector<PcsOpenItem>& items, size_t Q) {
+        return bn::pcs_open_folded_device_batch(who, single, ctx, items, Q);
+    }
+    static std::vector<std::string> pcs_verify_folded_batch(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const std::vector<PcsItem>& items, size_t Q) {
+        return bn::pcs_verify_folded_device_batch(who, ctx, sh, items, Q);
+    }
 };
 }  // namespace
 
@@ -774,8 +780,7 @@ static int pcs_verify_batch_tail(const char* who, hg_ctx* ctx, const pcs::Shape&
     for (size_t k = 0; k < at.size(); k++) items[k] = typename A::PcsItem{roots[at[k]], &cl[at[k]], proofs[at[k]], lens[at[k]]};
     std::vector<std::string> got, why(n, folded ? w + ": a folded opening needs a claim" : std::string());
     try {
-        if constexpr (A::FOLDED_BATCH) got = folded ? A::pcs_verify_folded_batch(who, ctx, sh, items, Q) : A::pcs_verify_batch(who, ctx, sh, items, Q);
-        else got = A::pcs_verify_batch(who, ctx, sh, items, Q);
+        got = folded ? A::pcs_verify_folded_batch(who, ctx, sh, items, Q) : A::pcs_verify_batch(who, ctx, sh, items, Q);
     } catch (const std::exception& e) {
         const std::string m = e.what();
         throw Error(m.rfind(w, 0) == 0 ? m : w + ": " + m);
@@ -922,10 +927,7 @@ static int pcs_open_batch_tail(const char* who, const char* single, hg_ctx* ctx,
     const size_t n = cms.size();
     if (!n) return 0;
     size_t need = 0;
-    for (size_t i = 0; i < n; i++) {
-        if constexpr (A::FOLDED_BATCH) need = std::max(need, folded ? A::folded_opening_bytes(cms[i]->sh, Q) : A::opening_bytes(cms[i]->sh, cl[i].size(), Q));
-        else need = std::max(need, A::opening_bytes(cms[i]->sh, cl[i].size(), Q));
-    }
+    for (size_t i = 0; i < n; i++) need = std::max(need, folded ? A::folded_opening_bytes(cms[i]->sh, Q) : A::opening_bytes(cms[i]->sh, cl[i].size(), Q));
     if (cap_each < need) throw Error(w + ": the largest opening of the run has " + std::to_string(need) + " bytes, cap_each is " + std::to_string(cap_each));
     if (!ctx) throw Error(w + ": no context");
     std::vector<typename A::PcsOpenItem> items(n);
@@ -935,8 +937,7 @@ static int pcs_open_batch_tail(const char* who, const char* single, hg_ctx* ctx,
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = now();
     try {
-        if constexpr (A::FOLDED_BATCH) got = folded ? A::pcs_open_folded_batch(who, single, ctx, items, Q) : A::pcs_open_batch(who, single, ctx, items, Q);
-        else got = A::pcs_open_batch(who, single, ctx, items, Q);
+        got = folded ? A::pcs_open_folded_batch(who, single, ctx, items, Q) : A::pcs_open_batch(who, single, ctx, items, Q);
     } catch (const std::exception& e) {
         const std::string m = e.what();
         throw Error(m.rfind(w, 0) == 0 ? m : w + ": " + m);
@@ -2661,6 +2662,31 @@ int hg_claims_verify_folded_bn254(const hg_params* params, const uint8_t root[32
 int hg_claims_verify_folded_device_bn254(hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n, const uint64_t* points4,
                                          size_t n_queries, const uint8_t* opening, size_t len) {
     HG_ENTRY(claims_verify_entry<BnAbi>("hg_claims_verify_folded_device_bn254", true, ctx, params, root, log2_row, claims, n, points4, n_queries, opening, len, true))
+}
+
+int hg_pcs_open_folded_batch_bn254(hg_ctx* ctx, const void* const* commitments, const uint32_t* const* tables, const uint64_t* const* points4, const uint64_t* const* values4,
+                                   const size_t* n_claims, size_t n_queries, size_t n, uint8_t* openings, size_t cap_each, size_t* lens, int* status, char* reasons,
+                                   size_t reason_cap) {
+    HG_ENTRY(pcs_open_batch_entry<BnAbi>("hg_pcs_open_folded_batch_bn254", "hg_pcs_open_folded_bn254", ctx, commitments, tables, points4, values4, n_claims, n_queries, n, openings,
+                                         cap_each, lens, status, reasons, reason_cap, true))
+}
+int hg_claims_open_folded_batch_bn254(hg_ctx* ctx, const hg_params* params, const void* const* commitments, const void* claims, size_t claim_cap_each, const uint64_t* points4,
+                                      size_t coord_cap_each, const size_t* n_claims, size_t n_queries, size_t n, uint8_t* openings, size_t cap_each, size_t* lens, int* status,
+                                      char* reasons, size_t reason_cap) {
+    HG_ENTRY(claims_open_batch_entry<BnAbi>("hg_claims_open_folded_batch_bn254", "hg_claims_open_folded_bn254", "hg_secrets_commit_bn254", ctx, params, commitments, claims,
+                                            claim_cap_each, points4, coord_cap_each, n_claims, n_queries, n, openings, cap_each, lens, status, reasons, reason_cap, true))
+}
+int hg_pcs_verify_folded_device_batch_bn254(hg_ctx* ctx, const uint8_t* const* roots, const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* const* tables,
+                                            const uint64_t* const* points4, const uint64_t* const* values4, const size_t* n_claims, size_t n_queries,
+                                            const uint8_t* const* proofs, const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap) {
+    HG_ENTRY(pcs_verify_batch_entry<BnAbi>("hg_pcs_verify_folded_device_batch_bn254", ctx, roots, nvars, n_tables, log2_row, tables, points4, values4, n_claims, n_queries, proofs,
+                                           lens, n, results, reasons, reason_cap, true))
+}
+int hg_claims_verify_folded_batch_bn254(hg_ctx* ctx, const hg_params* params, const uint8_t* const* roots, size_t log2_row, const void* claims, size_t claim_cap_each,
+                                        const uint64_t* points4, size_t coord_cap_each, const size_t* n_claims, size_t n_queries, const uint8_t* const* openings,
+                                        const size_t* lens, size_t n, int* results, char* reasons, size_t reason_cap) {
+    HG_ENTRY(claims_verify_batch_entry<BnAbi>("hg_claims_verify_folded_batch_bn254", ctx, params, roots, log2_row, claims, claim_cap_each, points4, coord_cap_each, n_claims,
+                                              n_queries, openings, lens, n, results, reasons, reason_cap, true))
 }
 
 int hg_pcs_verify_device_batch_bn254(hg_ctx* ctx, const uint8_t* const* roots, const uint32_t* nvars, size_t n_tables, size_t log2_row, const uint32_t* const* tables,

@@ -441,6 +441,10 @@ std::vector<CombineJob> FoldProver::body_jobs(const Shape& sh) {
     return jobs;
 }
 
+void FoldProver::write_u(const E2* u, size_t n) {
+    for (size_t i = 0; i < n; i++) tr.write_e(u[i]);
+}
+
 std::vector<uint8_t> open_folded(const char* who, const Commitment& cm, const std::vector<Claim>& claims, size_t Q) {
     const Shape& sh = cm.sh;
     const size_t C = sh.C(), n = claims.size(), V = fold_rounds(sh);

@@ -178,6 +178,8 @@ struct FoldProver {
     bool finish(const Shape& sh, const std::vector<E2>& T, const std::vector<E2>& G);
     // delta and rho' squeezed -> the two row combinations of the body: the R powers of rho', the combined weights
     std::vector<CombineJob> body_jobs(const Shape& sh);
+    // the u vectors behind the header and into the transcript
+    void write_u(const E2* u, size_t n);
 };
 // hg_pcs_open_folded: the opening bytes; an Error naming `who` if there is no claim and - naming the lowest failing claim - if a value
 // is not its table's evaluation (round 0 shows that one is wrong, the claims are then evaluated one by one)

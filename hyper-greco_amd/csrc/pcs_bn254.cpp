@@ -441,15 +441,54 @@ std::unique_ptr<PcsFoldSource> pcs_fold_source_host(const Commitment& cm, const 
     return f;
 }
 
+PcsFoldProver::PcsFoldProver(const Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q)
+    : tr(pcs_start_transcript(sh, root, claims, Q, FOLD_TAG)), tail(sh.nvars.size(), fr_one_mont()), rho(pcs::fold_rounds(sh)), claim(fr_zero()), r(fr_zero()) {
+    bpow = pcs_rho_powers(pcs_squeeze(tr), claims.size());
+    for (size_t i = 0; i < claims.size(); i++) claim = fr_add(claim, fr_mul(bpow[i], claims[i].value));
+}
+bool PcsFoldProver::round(const Shape& sh, size_t j, const Fr s[3], const std::vector<Fr>& T, const std::vector<Fr>& G) {
+    const size_t m = sh.nvars.size();
+    Fr k = fr_zero();   // the retired tables: K_t prod (1 - r_j') (1 - X), plain
+    for (size_t t = 0; t < m; t++)
+        if ((size_t)sh.nvars[t] <= j) k = fr_add(k, fr_mul(fr_mul(G[t], tail[t]), T[t]));
+    const Fr c0 = fr_add(s[0], k), c2 = s[2], c1 = fr_sub(fr_sub(s[1], s[0]), fr_add(s[2], k));
+    if (!fr_eq(fr_add(fr_add(c0, c0), fr_add(c1, c2)), claim)) return false;   // (round 0 is where a wrong value shows)
+    write_fr(tr, c0);
+    write_fr(tr, c1);
+    write_fr(tr, c2);
+    r = rho[j] = pcs_squeeze(tr);
+    const Fr rm = fr_to_mont(r);
+    claim = fr_add(c0, fr_mul(rm, fr_add(c1, fr_mul(rm, c2))));
+    for (size_t t = 0; t < m; t++)
+        if ((size_t)sh.nvars[t] <= j) tail[t] = fr_mul(tail[t], fr_sub(fr_one_mont(), rm));
+    return true;
+}
+bool PcsFoldProver::finish(const Shape& sh, const std::vector<Fr>& T, const std::vector<Fr>& G) {
+    const size_t m = sh.nvars.size();
+    Fr fin = fr_zero();
+    for (size_t t = 0; t < m; t++) fin = fr_add(fin, fr_mul(fr_mul(G[t], tail[t]), T[t]));
+    if (!fr_eq(fin, claim)) return false;
+    for (size_t t = 0; t < m; t++) write_fr(tr, T[t]);
+    return true;
+}
+std::vector<PcsJob> PcsFoldProver::body_jobs(const Shape& sh) {
+    const Fr delta = pcs_squeeze(tr);
+    std::vector<PcsJob> jobs(2);
+    jobs[0].row0 = 0; jobs[0].nrows = sh.R; jobs[0].w = pcs_rho_powers(pcs_squeeze(tr), sh.R);
+    jobs[1].row0 = 0; jobs[1].nrows = sh.R; jobs[1].w = combined_weights(sh, rho, delta);
+    return jobs;
+}
+void PcsFoldProver::write_u(const Fr* u, size_t n) {
+    for (size_t i = 0; i < n; i++) write_be32(tr.bytes, u[i]);
+    pcs_absorb(tr, u, n);
+}
+
 std::vector<uint8_t> pcs_open_folded(const char* who, const Commitment& cm, const std::vector<PcsClaim>& claims, size_t Q) {
     const Shape& sh = cm.sh;
-    const size_t C = sh.C(), R = sh.R, n = claims.size(), m = sh.nvars.size(), V = pcs::fold_rounds(sh);
+    const size_t C = sh.C(), n = claims.size(), V = pcs::fold_rounds(sh);
     const std::string w(who);
     if (!n) throw Error(w + ": a folded opening needs a claim");
-    FsTranscript tr = pcs_start_transcript(sh, cm.root(), claims, Q, FOLD_TAG);
-    const std::vector<Fr> bpow = pcs_rho_powers(pcs_squeeze(tr), n);
-    Fr claim = fr_zero();
-    for (size_t i = 0; i < n; i++) claim = fr_add(claim, fr_mul(bpow[i], claims[i].value));
+    PcsFoldProver P(sh, cm.root(), claims, Q);
     // a running claim the sums do not meet: a value is wrong. The claims one by one, as pcs_open checks them, to name the lowest
     auto refuse = [&]() {
         for (size_t i = 0; i < n; i++) {
@@ -468,45 +507,24 @@ std::vector<uint8_t> pcs_open_folded(const char* who, const Commitment& cm, cons
     };
     std::unique_ptr<PcsFoldSource> src;
     try {
-        src = cm.ctx ? pcs_fold_source_device(who, cm, claims, bpow) : pcs_fold_source_host(cm, claims, bpow);
+        src = cm.ctx ? pcs_fold_source_device(who, cm, claims, P.bpow) : pcs_fold_source_host(cm, claims, P.bpow);
     } catch (const std::exception& e) {
         throw Error(w + ": " + e.what());
     }
-    std::vector<Fr> tail(m, fr_one_mont()), rho(V);
-    auto retired = [&](size_t t) { return fr_mul(fr_mul(src->G[t], tail[t]), src->T[t]); };   // K_t prod (1 - r_j'), plain
-    Fr r = fr_zero();
     for (size_t j = 0; j < V; j++) {
         Fr s[3];
-        src->step(j, r, s);
-        Fr k = fr_zero();   // the retired tables: K_t prod (1 - r_j') (1 - X)
-        for (size_t t = 0; t < m; t++)
-            if ((size_t)sh.nvars[t] <= j) k = fr_add(k, retired(t));
-        const Fr c0 = fr_add(s[0], k), c2 = s[2], c1 = fr_sub(fr_sub(s[1], s[0]), fr_add(s[2], k));
-        if (!fr_eq(fr_add(fr_add(c0, c0), fr_add(c1, c2)), claim)) refuse();   // (round 0 is where a wrong value shows)
-        write_fr(tr, c0);
-        write_fr(tr, c1);
-        write_fr(tr, c2);
-        r = rho[j] = pcs_squeeze(tr);
-        const Fr rm = fr_to_mont(r);
-        claim = fr_add(c0, fr_mul(rm, fr_add(c1, fr_mul(rm, c2))));
-        for (size_t t = 0; t < m; t++)
-            if ((size_t)sh.nvars[t] <= j) tail[t] = fr_mul(tail[t], fr_sub(fr_one_mont(), rm));
+        src->step(j, P.r, s);
+        if (!P.round(sh, j, s, src->T, src->G)) refuse();
     }
-    src->step(V, r, nullptr);
-    Fr fin = fr_zero();
-    for (size_t t = 0; t < m; t++) fin = fr_add(fin, retired(t));
-    if (!fr_eq(fin, claim)) refuse();
-    for (size_t t = 0; t < m; t++) write_fr(tr, src->T[t]);
+    src->step(V, P.r, nullptr);
+    if (!P.finish(sh, src->T, src->G)) refuse();
     src.reset();   // (the device form's scratch is the context's arena, which the row combinations take next)
-    const Fr delta = pcs_squeeze(tr);
-    std::vector<PcsJob> jobs(2);
-    jobs[0].row0 = 0; jobs[0].nrows = R; jobs[0].w = pcs_rho_powers(pcs_squeeze(tr), R);
-    jobs[1].row0 = 0; jobs[1].nrows = R; jobs[1].w = combined_weights(sh, rho, delta);
+    const std::vector<PcsJob> jobs = P.body_jobs(sh);
     std::vector<Fr> u(2 * C);
     if (cm.ctx) pcs_combine_device(cm, jobs, u.data()); else pcs_combine_host(cm, jobs, u.data());
-    write_u_and_queries(tr, cm, u, Q, pcs_folded_opening_bytes(sh, Q));
-    if (tr.bytes.size() != pcs_folded_opening_bytes(sh, Q)) throw Error(w + ": internal: opening length");
-    return std::move(tr.bytes);
+    write_u_and_queries(P.tr, cm, u, Q, pcs_folded_opening_bytes(sh, Q));
+    if (P.tr.bytes.size() != pcs_folded_opening_bytes(sh, Q)) throw Error(w + ": internal: opening length");
+    return std::move(P.tr.bytes);
 }
 
 PcsFoldedHeader pcs_folded_header(const Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof) {

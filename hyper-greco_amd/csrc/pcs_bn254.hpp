@@ -73,9 +73,35 @@ struct PcsFoldSource {
 // context's stream (`who` names the entry in the texts of its device calls)
 std::unique_ptr<PcsFoldSource> pcs_fold_source_host(const pcs::Commitment& cm, const std::vector<PcsClaim>& claims, const std::vector<Fr>& bpow);
 std::unique_ptr<PcsFoldSource> pcs_fold_source_device(const char* who, const pcs::Commitment& cm, const std::vector<PcsClaim>& claims, const std::vector<Fr>& bpow);
+// The prover's arithmetic of one reduction, which pcs_open_folded and the batch form (bn254_pcs.inc) share: pcs::FoldProver over Fr. The
+// transcript, the running claim (plain) and the factors prod (1 - r_j') of the retired tables (Montgomery form). T, G are a
+// PcsFoldSource's, or what a group pass brought back for the member.
+struct PcsFoldProver {
+    FsTranscript tr;
+    std::vector<Fr> bpow, tail, rho;   // bpow, tail in Montgomery form; rho canonical
+    Fr claim, r;                       // r: the canonical challenge the next step folds by (zero ahead of round 0)
+    PcsFoldProver(const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q);
+    // round j < V from the sums of step(j): false, with nothing written, if they do not meet the running claim (a value is wrong); else
+    // c0, c1, c2 are written and r = rho[j] is squeezed
+    bool round(const pcs::Shape& sh, size_t j, const Fr s[3], const std::vector<Fr>& T, const std::vector<Fr>& G);
+    // after step(V): false if the final evaluation misses the claim; else the Y_t are written
+    bool finish(const pcs::Shape& sh, const std::vector<Fr>& T, const std::vector<Fr>& G);
+    // delta and rho' squeezed -> the two row combinations of the body: the R powers of rho', the combined weights
+    std::vector<PcsJob> body_jobs(const pcs::Shape& sh);
+    // the u vectors (canonical) behind the header and into the transcript
+    void write_u(const Fr* u, size_t n);
+};
 // hg_pcs_open_folded_bn254: the opening bytes; an Error naming `who` if there is no claim and - naming the lowest failing claim - if a
 // value is not its table's evaluation
 std::vector<uint8_t> pcs_open_folded(const char* who, const pcs::Commitment& cm, const std::vector<PcsClaim>& claims, size_t Q);
+// hg_pcs_open_folded_batch_bn254 (bn254_pcs.inc): pcs_open_device_batch for folded openings (every item has a claim): a group's reductions
+// run as one launch a round over all members, with one synchronisation a round. refused / bytes as there, the reason is
+// pcs_open_folded's under `single`
+std::vector<pcs::Opened> pcs_open_folded_device_batch(const char* who, const char* single, hg_ctx* ctx, const std::vector<PcsOpenItem>& items, size_t Q);
+// hg_pcs_verify_folded_device_batch_bn254 (bn254_pcs.inc): pcs_verify_device_batch for folded openings: why[i] is what
+// pcs_verify_folded_device returns for item i alone; the headers on the host threads, the bodies through pcs_verify_device_batch's pass
+// as openings of one claim
+std::vector<std::string> pcs_verify_folded_device_batch(const char* who, hg_ctx* ctx, const pcs::Shape& sh, const std::vector<VerifyItem>& items, size_t Q);
 // hg_pcs_verify_folded_bn254: "" = accepted, else the reason
 std::string pcs_verify_folded(const pcs::Shape& sh, const uint8_t root[32], const std::vector<PcsClaim>& claims, size_t Q, const uint8_t* proof, size_t len);
 // hg_pcs_verify_folded_device_bn254 (bn254_pcs.inc): the same decision and reason; the header on the host, the body through

@@ -777,5 +777,326 @@ std::vector<Opened> open_batch_flow(const char* who_c, const char* single, hg_ct
     return res;
 }
 
+// The device opener of a run of folded openings (hg_pcs_open_folded_batch*). A group (cut_groups over what a member takes: its g, its
+// two buffer pairs, its blocks of the staged copy and its image): the host threads start every member's transcript and write its claim
+// rows and factor tables into one staged copy, one member a task; ONE launch builds all members' g; then, for every step of the
+// reduction, ONE launch folds the live tables of all members (the member is the grid's z), one workgroup a member adds its partials,
+// the 3 G sums and - where tables retire - the scalars come back in one copy each, and ONE SYNCHRONISATION serves the group; the host
+// threads do every member's transcript arithmetic (the field's FoldProver, the single call's) and the G challenges - in the form the
+// round kernel takes them, F::FoldChal - go up in one copy ahead of the next launch. A member whose running claim is not met is
+// refused: it rides on in the launches - its buffers are its own, so no other member's bytes depend on it - and its results are
+// ignored. The tail is open_batch_flow's on two jobs a member: the combinations, the u vectors back, the host threads hash them and
+// squeeze the indices, the gather writes the columns into images whose body starts behind the header, the host writes header, u
+// vectors and siblings. The lowest failing claim of the refused members comes from the combine and evaluation kernels over their
+// claims, one cell a member.
+// What the field gives beside the policy of the other flows: FoldProver (round / finish / body_jobs / write_u), the geometry a shape
+// fixes (fold_g_tables, fold_tables), a member's block of the g kernel's staged copy (fold_gblock_bytes, fold_gblock_fill), the arena
+// buffers (fold_alloc), the member table (fold_members), the launches (fold_g_launch, fold_launch) and their bytes.
+template <class F>
+std::vector<Opened> open_folded_batch_flow(const char* who_c, const char* single, hg_ctx* ctx, const std::vector<typename F::OpenItem>& items, size_t Q) {
+    typedef typename F::Row Row;
+    typedef typename F::W W;
+    typedef typename F::Claim Claim;
+    typedef typename F::FoldProver Prover;
+    typedef typename F::FoldChal Chal;
+    typedef typename F::FoldGMember GMember;
+    constexpr size_t RW = sizeof(Row) / 8, WW = sizeof(W) / 8;   // words of a row element and of a u element
+    const std::string who(who_c);
+    std::vector<Opened> res(items.size());
+    if (items.empty()) return res;
+    const Shape& sh = items[0].cm->sh;
+    const size_t C = sh.C(), N = sh.N(), R = sh.R, m = sh.nvars.size(), V = fold_rounds(sh), Wd = R << sh.c;
+    const int depth = sh.depth();
+    const size_t hb = F::folded_header_bytes(sh), len = F::folded_opening_bytes(sh, Q), q_words = RW * query_stride<F>(sh), body_at = hb / 8 + 2 * C * WW;   // (words)
+    size_t max_len;
+    const typename F::FoldGTables GA = F::fold_g_tables(sh, &max_len);
+    const unsigned max_blocks = F::fold_max_blocks();
+    // what a member takes: g, the buffer pairs (a half and a quarter of g for T and for g each), its sums, its challenge and its row
+    // pointer, its blocks of the staged copy, its u vectors, its image and its indices
+    const size_t tail_block = sizeof(ObMember<Row>) + 2 * sizeof(ObJob<Row>) + 2 * R * sizeof(W);
+    auto bytes_of = [&](size_t i) {
+        return sizeof(W) * (Wd + 2 * (Wd / 2 + 1) + 2 * (Wd / 4 + 1) + 2 * m + 3 + 2 * C) + sizeof(Chal) + sizeof(GMember) + 8 + F::fold_gblock_bytes(sh, GA, *items[i].claims) +
+               tail_block + len + 8 * Q + 64;
+    };
+    const std::vector<std::pair<size_t, size_t>> groups = cut_groups(ctx, items.size(), bytes_of, 0, 0);
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    VerifyBatchBufs* B = batch_bufs(ctx);
+    hipStream_t st = ctx->stream;
+    Drain drain{st};
+    hip_check(hipStreamSynchronize(st), (who + ": synchronise").c_str());   // (the arena is reset below)
+    [[maybe_unused]] const int nthr = std::max(1, hg_omp_threads());        // (the device pass of hipcc ignores the pragmas)
+    const int cls = ctx->prof_class(F::CLS_FOLD_BATCH, false);
+    ctx->prof_stream = st;
+    const bool times = hg_times("pcs");   // HG_TIMES=pcs: where a group's wall clock goes, on stderr
+
+    struct Member {
+        size_t idx, block_at;
+        std::unique_ptr<Prover> P;
+        std::vector<W> T, Gs, G1;
+        bool refused = false;
+        size_t failing = 0;
+        std::string error;
+    };
+    auto rethrow = [&](const std::vector<Member>& mem) {
+        for (const Member& x : mem)
+            if (!x.error.empty()) throw Error(who + ": index " + std::to_string(x.idx) + ": " + x.error);
+    };
+    for (size_t g = 0; g < groups.size(); g++) {
+        const double t0 = omp_get_wtime();
+        const size_t G = groups[g].second - groups[g].first;
+        std::vector<Member> mem(G);
+        // the staged copy: the g kernel's member table, the row pointers, the challenges, the members' blocks; then the tail's member and
+        // job tables, its weights, and the indices with the members' flags behind them
+        const size_t rows_at = align_up<F>(G * sizeof(GMember)), r_at = rows_at + align_up<F>(G * 8);
+        size_t at = r_at + align_up<F>(G * sizeof(Chal)), claims_total = 0;
+        for (size_t k = 0; k < G; k++) {
+            mem[k].idx = groups[g].first + k;
+            mem[k].block_at = at;
+            at += F::fold_gblock_bytes(sh, GA, *items[mem[k].idx].claims);
+            claims_total += items[mem[k].idx].claims->size();
+        }
+        const size_t g_bytes = at, tmem_at = at, tjob_at = tmem_at + align_up<F>(G * sizeof(ObMember<Row>)), tw_at = tjob_at + align_up<F>(2 * G * sizeof(ObJob<Row>)),
+                     js_at = tw_at + 2 * G * R * sizeof(W), stage_bytes = js_at + (G * Q + G) * 8;
+        char* h_stage = batch_desc_host(B, stage_bytes);   // (the previous group's copies of it were waited for)
+        // results of the group, page-locked: the sums, the scalars, the u vectors, the images
+        const size_t hsum_at = 0, hscal_at = hsum_at + 3 * G * sizeof(W), hu_at = hscal_at + 2 * m * G * sizeof(W), himg_at = hu_at + 2 * C * G * sizeof(W);
+        char* h_out = batch_out_host(B, himg_at + G * len);
+        const W* h_sums = reinterpret_cast<const W*>(h_out + hsum_at);
+        const W* h_scal = reinterpret_cast<const W*>(h_out + hscal_at);
+        const W* h_u = reinterpret_cast<const W*>(h_out + hu_at);
+        const uint8_t* h_img = reinterpret_cast<const uint8_t*>(h_out + himg_at);
+        Chal* h_r = reinterpret_cast<Chal*>(h_stage + r_at);
+        u64* h_js = reinterpret_cast<u64*>(h_stage + js_at);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
+        for (long long k = 0; k < (long long)G; k++) {
+            Member& x = mem[k];
+            try {
+                const Commitment& cm = *items[x.idx].cm;
+                const std::vector<Claim>& claims = *items[x.idx].claims;
+                x.P.reset(new Prover(sh, cm.root(), claims, Q));
+                x.T.assign(m, W());
+                x.Gs.assign(m, W());
+                F::fold_gblock_fill(h_stage, reinterpret_cast<GMember*>(h_stage)[k], x.block_at, sh, GA, claims, x.P->bpow, x.G1);
+                reinterpret_cast<const Row**>(h_stage + rows_at)[k] = reinterpret_cast<const Row*>(cm.d_rows);
+                h_r[k] = F::fold_chal(x.P->r);
+            } catch (const std::exception& e) { x.error = e.what(); }
+        }
+        rethrow(mem);
+        const double t1 = omp_get_wtime();
+        ctx->arena_reset();
+        char* d_stage;
+        typename F::FoldBufs buf;
+        W* d_u;
+        u64* d_img;
+        try {
+            d_stage = ctx->alloc_n<char>(stage_bytes);
+            buf = F::fold_alloc(ctx, sh, G, max_blocks);
+            d_u = ctx->alloc_n<W>(G * 2 * C);
+            d_img = ctx->alloc_n<u64>(G * len / 8);
+        } catch (const std::exception& e) {
+            throw Error(who + ": the context's arena cannot hold a group of " + std::to_string(G) + " reductions: lower verify_batch_group (" + e.what() + ")");
+        }
+        const typename F::FoldMembers M = F::fold_members(sh, reinterpret_cast<const Row* const*>(d_stage + rows_at), reinterpret_cast<const Chal*>(d_stage + r_at));
+        hip_check(hipMemcpyAsync(d_stage, h_stage, g_bytes, hipMemcpyHostToDevice, st), "upload claims");
+        ctx->prof_begin(cls, (double)G * Wd * sizeof(W) + (double)g_bytes);
+        F::fold_g_launch(st, max_blocks, GA, max_len, G, M, d_stage, buf);
+        ctx->prof_end();
+        // the steps of the reduction: every member is in the same one at the same time
+        size_t round_launches = 0, round_syncs = 0;
+        double t_host = 0;
+        for (size_t j = 0; j <= V; j++) {
+            bool retire;
+            size_t max_units, entries;
+            const typename F::FoldTables A = F::fold_tables(sh, j, &retire, &max_units, &entries);
+            retire |= j == 0 && GA.n1 != 0;   // the elements of the one-element tables come back with step 0
+            if (A.nt) {
+                if (j > 0) hip_check(hipMemcpyAsync(d_stage + r_at, h_r, G * sizeof(Chal), hipMemcpyHostToDevice, st), "upload the round's challenges");
+                ctx->prof_begin(cls, (double)G * F::fold_step_bytes(j, entries));
+                F::fold_launch(st, max_blocks, sh, j, A, max_units, G, M, buf, j < V);
+                ctx->prof_end();
+                round_launches++;
+                if (j < V) hip_check(hipMemcpyAsync(h_out + hsum_at, buf.sums, 3 * G * sizeof(W), hipMemcpyDeviceToHost, st), "download the round's sums");
+            }
+            if (retire) hip_check(hipMemcpyAsync(h_out + hscal_at, buf.scal, 2 * m * G * sizeof(W), hipMemcpyDeviceToHost, st), "download the retired tables' scalars");
+            if (A.nt || retire) {
+                hip_check(hipStreamSynchronize(st), (who + ": sync").c_str());
+                hip_check(hipGetLastError(), (who + ": launch").c_str());
+                round_syncs++;
+            }
+            const double th = omp_get_wtime();
+#pragma omp parallel for schedule(static) num_threads(std::min<int>(nthr, (int)G))
+            for (long long k = 0; k < (long long)G; k++) {
+                Member& x = mem[k];
+                if (x.refused) continue;
+                try {
+                    const W* sc = h_scal + 2 * m * (size_t)k;
+                    for (size_t t = 0; t < m; t++) {
+                        if (j == 0 && sh.nvars[t] == 0) { x.T[t] = sc[2 * t]; x.Gs[t] = x.G1[t]; }
+                        if (j > 0 && (size_t)sh.nvars[t] == j) { x.T[t] = sc[2 * t]; x.Gs[t] = sc[2 * t + 1]; }
+                    }
+                    W s[3] = {W(), W(), W()};
+                    if (A.nt && j < V) memcpy(s, h_sums + 3 * (size_t)k, sizeof(s));
+                    x.refused = j < V ? !x.P->round(sh, j, s, x.T, x.Gs) : !x.P->finish(sh, x.T, x.Gs);
+                    h_r[k] = F::fold_chal(x.P->r);
+                } catch (const std::exception& e) { x.error = e.what(); }
+            }
+            rethrow(mem);
+            t_host += omp_get_wtime() - th;
+        }
+        ctx->prof_collect();
+        if (hg_debug("plan"))   // (read at every call: the tests switch it per case)
+            fprintf(stderr, "[hg plan] %s members=%zu V=%zu round_launches=%zu round_syncs=%zu tables=%zu claims=%zu\n", F::PLAN_FOLD_BATCH, G, V, round_launches, round_syncs, m,
+                    claims_total);
+        const double t2 = omp_get_wtime();
+        // the refused members: their claims through the row combinations and the evaluation checks, the lowest failing one in a cell a member
+        std::vector<size_t> bad;
+        for (size_t k = 0; k < G; k++)
+            if (mem[k].refused) bad.push_back(k);
+        if (!bad.empty()) {
+            size_t nc = 0, nw = 0;
+            for (size_t k : bad) {
+                nc += items[mem[k].idx].claims->size();
+                nw += weights_of<F>(sh, *items[mem[k].idx].claims) - R;
+            }
+            const size_t rc_at = align_up<F>(nc * sizeof(ObJob<Row>)), ry_at = rc_at + align_up<F>(nc * sizeof(ObClaim)), rz_at = ry_at + nc * sizeof(W),
+                         rw_at = rz_at + nc * (size_t)sh.c * sizeof(W);
+            std::vector<char> rs(rw_at + nw * sizeof(W) + F::ALIGN);
+            ObJob<Row>* hd = reinterpret_cast<ObJob<Row>*>(rs.data());
+            ObClaim* hc = reinterpret_cast<ObClaim*>(rs.data() + rc_at);
+            W* hy = reinterpret_cast<W*>(rs.data() + ry_at);
+            W* hz = reinterpret_cast<W*>(rs.data() + rz_at);
+            W* hw = reinterpret_cast<W*>(rs.data() + rw_at);
+            size_t q = 0, off = 0;
+            for (size_t b = 0; b < bad.size(); b++) {
+                const Commitment& cm = *items[mem[bad[b]].idx].cm;
+                const std::vector<Claim>& claims = *items[mem[bad[b]].idx].claims;
+                for (size_t i = 0; i < claims.size(); i++, q++) {
+                    const Claim& cl = claims[i];
+                    const std::vector<W> w = F::eq_table(cl.point.data() + sh.c, (size_t)(sh.nvars[cl.table] - sh.c));
+                    hd[q].src = reinterpret_cast<const Row*>(cm.d_rows) + (sh.off[cl.table] << sh.c); hd[q].nrows = w.size(); hd[q].w_at = rw_at + off * sizeof(W); hd[q].u_at = q * C;
+                    memcpy(hw + off, w.data(), w.size() * sizeof(W));
+                    off += w.size();
+                    hy[q] = cl.value;
+                    F::store_low(hz + q * (size_t)sh.c, cl.point.data(), sh.c);
+                    hc[q].u_at = q * C; hc[q].z_at = rz_at + q * (size_t)sh.c * sizeof(W); hc[q].y_at = ry_at + q * sizeof(W); hc[q].member = (u64)b; hc[q].claim = (u64)i;
+                }
+            }
+            char* d_rs;
+            W* d_ru;
+            u64* d_cells;
+            try {
+                d_rs = ctx->alloc_n<char>(rs.size());
+                d_ru = ctx->alloc_n<W>(nc * C);
+                d_cells = ctx->alloc_n<u64>(bad.size());
+            } catch (const std::exception& e) {
+                throw Error(who + ": the context's arena cannot hold the claims of the refused members: lower verify_batch_group (" + e.what() + ")");
+            }
+            if (nc * ((C + F::TPB - 1) / F::TPB) > 0x7fffffffull) throw Error(who + ": the refused members have too many claims for one launch: lower verify_batch_group");
+            std::vector<u64> cells(bad.size());
+            hip_check(hipMemcpyAsync(d_rs, rs.data(), rs.size(), hipMemcpyHostToDevice, st), "upload claims");
+            hip_check(hipMemsetAsync(d_cells, 0xff, bad.size() * 8, st), "memset");
+            F::combine(ctx, cls, st, sh.c, nc, nw, 0, reinterpret_cast<const ObJob<Row>*>(d_rs), d_rs, d_ru);
+            F::ob_eval(ctx, cls, st, reinterpret_cast<const ObClaim*>(d_rs + rc_at), nc, sh.c, d_ru, d_rs, d_cells);
+            hip_check(hipMemcpyAsync(cells.data(), d_cells, bad.size() * 8, hipMemcpyDeviceToHost, st), "download evaluation checks");
+            hip_check(hipStreamSynchronize(st), (who + ": sync").c_str());   // (the staged copy and the cells are locals)
+            hip_check(hipGetLastError(), (who + ": launch").c_str());
+            for (size_t b = 0; b < bad.size(); b++) {
+                if (cells[b] == PCSV_NONE) throw Error(who + ": index " + std::to_string(mem[bad[b]].idx) + ": internal: the reduction does not meet its claim");
+                mem[bad[b]].failing = (size_t)cells[b];
+            }
+        }
+        const size_t active = G - bad.size();
+        const double t3 = omp_get_wtime();
+        if (active) {
+            // the tail: two row combinations a member that was not refused
+            ObMember<Row>* hm = reinterpret_cast<ObMember<Row>*>(h_stage + tmem_at);
+            ObJob<Row>* hd = reinterpret_cast<ObJob<Row>*>(h_stage + tjob_at);
+            std::vector<size_t> live;
+            for (size_t k = 0; k < G; k++)
+                if (!mem[k].refused) live.push_back(k);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
+            for (long long k = 0; k < (long long)G; k++) {
+                Member& x = mem[k];
+                try {
+                    const Commitment& cm = *items[x.idx].cm;
+                    hm[k].M = reinterpret_cast<const Row*>(cm.d_M); hm[k].img = (size_t)k * (len / 8); hm[k].u = 0; hm[k].u_words = body_at;
+                    h_js[G * Q + k] = x.refused ? 0 : 1;
+                    if (x.refused) continue;
+                    const size_t a = std::lower_bound(live.begin(), live.end(), (size_t)k) - live.begin();   // its number among the members that go on
+                    const auto jobs = x.P->body_jobs(sh);
+                    for (size_t i = 0; i < 2; i++) {
+                        ObJob<Row>& d = hd[2 * a + i];
+                        d.src = reinterpret_cast<const Row*>(cm.d_rows); d.nrows = R; d.w_at = tw_at + (2 * (size_t)k + i) * R * sizeof(W); d.u_at = (2 * (size_t)k + i) * C;
+                        memcpy(h_stage + d.w_at, jobs[i].w.data(), R * sizeof(W));
+                    }
+                } catch (const std::exception& e) { x.error = e.what(); }
+            }
+            rethrow(mem);
+            hip_check(hipMemcpyAsync(d_stage + tmem_at, h_stage + tmem_at, js_at - tmem_at, hipMemcpyHostToDevice, st), "upload weights");
+            F::combine(ctx, cls, st, sh.c, 2 * active, 2 * active * R, 0, reinterpret_cast<const ObJob<Row>*>(d_stage + tjob_at), d_stage, d_u);
+            hip_check(hipMemcpyAsync(h_out + hu_at, d_u, G * 2 * C * sizeof(W), hipMemcpyDeviceToHost, st), "download combinations");
+            hip_check(hipStreamSynchronize(st), (who + ": sync").c_str());
+            hip_check(hipGetLastError(), (who + ": launch").c_str());
+        }
+        const double t4 = omp_get_wtime();
+        if (active) {
+            // the host's share: every member's u vectors into its transcript (and behind its header), its column indices out of it
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
+            for (long long k = 0; k < (long long)G; k++) {
+                Member& x = mem[k];
+                for (size_t q = 0; q < Q; q++) h_js[(size_t)k * Q + q] = 0;
+                if (x.refused) continue;
+                try {
+                    x.P->write_u(h_u + 2 * C * (size_t)k, 2 * C);
+                    const std::vector<size_t> js = F::squeeze_indices(x.P->tr, N, Q);
+                    for (size_t q = 0; q < Q; q++) h_js[(size_t)k * Q + q] = js[q];
+                } catch (const std::exception& e) { x.error = e.what(); }
+            }
+            rethrow(mem);
+        }
+        const double t5 = omp_get_wtime();
+        if (active) {
+            hip_check(hipMemcpyAsync(d_stage + js_at, h_js, (G * Q + G) * 8, hipMemcpyHostToDevice, st), "upload column indices");
+            F::gather(ctx, cls, st, reinterpret_cast<const ObMember<Row>*>(d_stage + tmem_at), G, Q, R, N, q_words, active, reinterpret_cast<const u64*>(d_stage + js_at), d_img);
+            hip_check(hipMemcpyAsync(h_out + himg_at, d_img, G * len, hipMemcpyDeviceToHost, st), "download openings");
+            hip_check(hipStreamSynchronize(st), (who + ": sync").c_str());
+            hip_check(hipGetLastError(), (who + ": launch").c_str());
+        }
+        ctx->prof_collect();
+        const double t6 = omp_get_wtime();
+        // header and u vectors from each transcript, the siblings from each handle's tree into the gaps; a refused member's reason
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::min<int>(nthr, (int)G))
+        for (long long k = 0; k < (long long)G; k++) {
+            Member& x = mem[k];
+            try {
+                Opened& out = res[x.idx];
+                const Commitment& cm = *items[x.idx].cm;
+                if (x.refused) {
+                    out.refused = true;
+                    out.reason = std::string(single) + ": claim " + std::to_string(x.failing) + ": the value is not the evaluation of table " +
+                                 std::to_string((*items[x.idx].claims)[x.failing].table) + " at the point";
+                    continue;
+                }
+                const std::vector<uint8_t>& head = x.P->tr.bytes;
+                if (head.size() != 8 * body_at) throw Error("internal: opening length");
+                const uint8_t* image = h_img + (size_t)k * len;
+                out.bytes.assign(image, image + len);
+                memcpy(out.bytes.data(), head.data(), head.size());
+                for (size_t q = 0; q < Q; q++) {
+                    uint8_t* sib = out.bytes.data() + 8 * (body_at + q * q_words + RW * R);
+                    size_t idx = (size_t)h_js[(size_t)k * Q + q];
+                    for (int l = 0; l < depth; l++, idx >>= 1) memcpy(sib + 32 * l, cm.node(l, idx ^ 1), 32);
+                }
+            } catch (const std::exception& e) { x.error = e.what(); }
+        }
+        rethrow(mem);
+        if (times)
+            fprintf(stderr, "[hg pcs] %sfolded open group %zu of %zu members: transcripts and factor tables %.2f ms, g and %zu rounds %.2f (host arithmetic %.2f), refusals %.2f, "
+                            "combine and u back %.2f, hash %.2f, gather and images back %.2f, header and siblings %.2f\n", F::TIMES_TAG, g, G, (t1 - t0) * 1e3, V, (t2 - t1) * 1e3,
+                    t_host * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3, (t5 - t4) * 1e3, (t6 - t5) * 1e3, (omp_get_wtime() - t6) * 1e3);
+    }
+    return res;
+}
+
 }  // namespace pcs
 }  // namespace hg

@@ -90,9 +90,9 @@ void hg_destroy(hg_ctx* ctx);
  *                 hg_pcs_verify_device_batch, hg_claims_verify_batch, hg_pcs_verify_device_batch_bn254 or
  *                 hg_claims_verify_batch_bn254, the most members one device pass of hg_pcs_commit_batch, hg_secrets_commit_batch,
  *                 hg_pcs_commit_batch_bn254 or hg_secrets_commit_batch_bn254 encodes and the most items one of hg_pcs_open_batch,
- *                 hg_claims_open_batch, hg_pcs_open_batch_bn254, hg_claims_open_batch_bn254, hg_pcs_open_folded_batch or
- *                 hg_claims_open_folded_batch opens (default 0: sized from the
- *                 memory budget, at most 64)
+ *                 hg_claims_open_batch, hg_pcs_open_batch_bn254, hg_claims_open_batch_bn254, hg_pcs_open_folded_batch,
+ *                 hg_claims_open_folded_batch, hg_pcs_open_folded_batch_bn254 or hg_claims_open_folded_batch_bn254 opens (default 0:
+ *                 sized from the memory budget, at most 64)
  *   "bound_batch_slice"  the members of a group that hg_verify_public_bound_batch and hg_instance_digest_group gather, copy and
  *                 digest at a time (default 0: as many as fit in 32 MiB of instance words, at least one: 4 at n=32768 k=16); a
  *                 slice's copy and digests run under the gather of the next one. Results do not depend on it
@@ -1253,8 +1253,9 @@ int hg_claims_verify_device_bn254(hg_ctx* ctx, const hg_params* params, const ui
  *     5. <u_1, eq(rho[..c))> == sum_t delta^t Y_t ("pcs: evaluation mismatch at claim 0");  6. per query, ascending: the Merkle path,
  *     proximity, then the combined claim ("pcs: claim 0 inconsistent at query q"), the first two with the texts of hg_pcs_verify_bn254.
  *   Soundness is what "Folded openings" claims, over Fr. Still not zero knowledge.
- * Contracts are those of the Goldilocks folded entries. Single calls only: no batch forms, and hg_prove_encryptions_committed_bn254
- * does not fold. hg_pcs_open and its BN254 neighbours, their bytes and "hg-pcs-bn254-1" are unchanged.
+ * Contracts are those of the Goldilocks folded entries. The forms for a run are hg_pcs_open_folded_batch_bn254,
+ * hg_claims_open_folded_batch_bn254, hg_pcs_verify_folded_device_batch_bn254 and hg_claims_verify_folded_batch_bn254, below the single
+ * calls; hg_prove_encryptions_committed_bn254 does not fold. hg_pcs_open and its BN254 neighbours, their bytes and "hg-pcs-bn254-1" are unchanged.
  * hg_pcs_open_folded_bn254: hg_pcs_open_bn254's arguments. n_claims == 0 is -1 ("<function>: a folded opening needs a claim").
  *   *len = the length also when cap is too small. A value that is not its table's evaluation is refused with hg_pcs_open_bn254's text
  *   under this name, naming the lowest failing claim. A Goldilocks handle or a handle of another context is -1. The host form
@@ -1286,6 +1287,74 @@ int hg_claims_verify_folded_bn254(const hg_params* params, const uint8_t root[32
                                   const uint64_t* points4, size_t n_queries, const uint8_t* opening, size_t len);
 int hg_claims_verify_folded_device_bn254(hg_ctx* ctx, const hg_params* params, const uint8_t root[32], size_t log2_row, const void* claims, size_t n,
                                          const uint64_t* points4, size_t n_queries, const uint8_t* opening, size_t len);
+
+/* hg_pcs_open_folded_batch_bn254 / hg_claims_open_folded_batch_bn254: hg_pcs_open_folded_bn254 / hg_claims_open_folded_bn254 for a run,
+ *   with the argument lists and the outputs of hg_pcs_open_batch_bn254 / hg_claims_open_batch_bn254 (declared with the BN254 batch
+ *   forms of commit and open, below). Item i opens its own claims, n_claims[i] >= 1, against commitments[i]; all handles are BN254
+ *   device handles of this context and of one shape, a handle may appear twice; one n_queries for the run. Opening i is byte for byte
+ *   what hg_pcs_open_folded_bn254 returns for that item alone - so also what the host form gives on a host commitment of the same
+ *   tables. n == 0 returns 0 and writes nothing.
+ *   status[i] = 0 opened; 1 REFUSED: lens[i] = 0, the item's buffer untouched, the reason slot holds exactly the text
+ *   hg_pcs_open_folded_bn254 (hg_claims_open_folded_bn254) leaves for that item, the single entry's name and the lowest failing claim.
+ *   The run continues after a refusal and the other items' bytes are what they would be without the refused item. Returns the number
+ *   of refused items.
+ *   -1, nothing written, the text beginning with this function's name and giving "index i" where an item is at fault, every item
+ *   checked before anything is enqueued: the cases of hg_pcs_open_batch_bn254 (a Goldilocks handle: "the commitment is over
+ *   Goldilocks: open it with <this function without _bn254>"), and an item without a claim ("<function>: index i: a folded opening
+ *   needs a claim"); "<function>: no context" after the argument checks; cap_each below the folded length (the text gives the bytes
+ *   needed).
+ *   The pass is hg_pcs_open_folded_batch's, one host flow for both fields: groups of at most 64 or "verify_batch_group" members
+ *   within 2 GiB of scratch - a member takes its g (32 bytes a table entry), the two buffer pairs of the rounds (48 bytes a table
+ *   entry), its staged claims and its image: about 149 MB at n=32768 k=16, 14 members a group (a run of 64 ran as 5 groups:
+ *   DESIGN.md 6; "the context's arena cannot hold a group of G reductions: lower verify_batch_group" when the arena is smaller). Per group the host threads start every
+ *   member's transcript and write its claim rows and factor tables into one staged copy, one member a task; one launch builds all
+ *   members' g and copies the elements of one-element tables to the scalars; then every step of the reduction is ONE launch over all
+ *   members (the member is the grid's third dimension; its raw rows through a table of G pointers, the 64 fold constants of its
+ *   challenge - 256 bytes, computed by the host - from an array of G sets that is uploaded once a round and read at the member's
+ *   index, which is uniform over a wavefront, so the constants stay in scalar registers), one workgroup a member adds its partial
+ *   sums, the 3 G sums and the scalars of the tables that retire come back in one copy each, canonical, and ONE synchronisation
+ *   serves the group: V + 1 launches of the round kernels and V + 1 synchronisations a group, whatever its size. The single call runs
+ *   the same kernels as a group of one, with its row base and its fold constants in the kernel arguments. A member whose running
+ *   claim is not met is refused; it rides on in the launches, its results ignored (its buffers are its own; raw rows are never
+ *   written). The lowest failing claim of the refused members comes from the combine and evaluation kernels of
+ *   hg_pcs_open_batch_bn254 over their claims, one cell a member; a refused member of which no claim fails is -1 (internal). u_0 and
+ *   u_1 are two jobs a member through the combine kernel, the u vectors come back (128 KB a member where the unfolded batch hashes
+ *   3.1 MB), the host threads hash them and squeeze the indices, the gather writes the columns into images whose body starts behind
+ *   the header; the host writes header, u vectors and siblings. Profiler class pcs_fold_batch_bn254; HG_TIMES=pcs prints a line a
+ *   group; HG_DEBUG=plan prints "[hg plan] bnpcsfoldb members=.. V=.. round_launches=.. round_syncs=.. tables=.. claims=.." a group.
+ *   HG_PCS_FOLD_BLOCKS bounds the workgroups of a launch as a whole; a table of a member always has at least one. Not concurrently
+ *   with another call on the same context.
+ * hg_pcs_verify_folded_device_batch_bn254 / hg_claims_verify_folded_batch_bn254: hg_pcs_verify_folded_device_bn254 /
+ *   hg_claims_verify_folded_device_bn254 for a run, with the argument lists and the outputs of hg_pcs_verify_device_batch_bn254 /
+ *   hg_claims_verify_batch_bn254. results[i] and the reason are exactly what hg_pcs_verify_folded_device_bn254 (so
+ *   hg_pcs_verify_folded_bn254) gives for that item alone, also where several checks fail at once; byte offsets count from the start
+ *   of the item's folded opening; a wrong length is rejected per item and never reaches the device. The order of reasons is the
+ *   single call's: the length; a header element that is not below r (host); a body element that is not below r; the header's rounds
+ *   and final evaluation; the body's checks. Returns the number of rejected items. -1 as hg_pcs_verify_device_batch_bn254, and in
+ *   hg_pcs_verify_folded_device_batch_bn254 an item with n_claims[i] == 0 ("<function>: index i: a folded opening needs a claim").
+ *   THE ONE EXCEPTION: hg_claims_verify_folded_batch_bn254 gives an item with n_claims[i] == 0 - a proof the public batch verifier
+ *   rejected - results[i] = 1 with the reason "hg_claims_verify_folded_batch_bn254: a folded opening needs a claim", so that a
+ *   service can pass the arrays of hg_verify_public_batch_bn254 through unchanged; such an item never reaches the device.
+ *   The pass is hg_pcs_verify_device_batch_bn254's: per group the host threads run the header of every member and write its block of
+ *   the staged copy as that of an opening of one claim that starts behind the header - what hg_pcs_verify_folded_device_bn254
+ *   writes for its one member; the index-free kernels run once over the group, the host threads hash each member's 2 C elements of u
+ *   meanwhile, one copy of indices, the query kernel, the cells back: one synchronisation a group. A member whose header holds an
+ *   element that is not below r rides along on a block of zeros and gets the header's reason. No kernel of its own. Profiler class
+ *   pcs_bn254_verify_batch. */
+int hg_pcs_open_folded_batch_bn254(hg_ctx* ctx, const void* const* commitments, const uint32_t* const* tables, const uint64_t* const* points4,
+                                   const uint64_t* const* values4, const size_t* n_claims, size_t n_queries, size_t n, uint8_t* openings,
+                                   size_t cap_each, size_t* lens, int* status, char* reasons, size_t reason_cap);
+int hg_claims_open_folded_batch_bn254(hg_ctx* ctx, const hg_params* params, const void* const* commitments, const void* claims, size_t claim_cap_each,
+                                      const uint64_t* points4, size_t coord_cap_each, const size_t* n_claims, size_t n_queries, size_t n,
+                                      uint8_t* openings, size_t cap_each, size_t* lens, int* status, char* reasons, size_t reason_cap);
+int hg_pcs_verify_folded_device_batch_bn254(hg_ctx* ctx, const uint8_t* const* roots, const uint32_t* nvars, size_t n_tables, size_t log2_row,
+                                            const uint32_t* const* tables, const uint64_t* const* points4, const uint64_t* const* values4,
+                                            const size_t* n_claims, size_t n_queries, const uint8_t* const* proofs, const size_t* lens, size_t n,
+                                            int* results, char* reasons, size_t reason_cap);
+int hg_claims_verify_folded_batch_bn254(hg_ctx* ctx, const hg_params* params, const uint8_t* const* roots, size_t log2_row, const void* claims,
+                                        size_t claim_cap_each, const uint64_t* points4, size_t coord_cap_each, const size_t* n_claims,
+                                        size_t n_queries, const uint8_t* const* openings, const size_t* lens, size_t n, int* results, char* reasons,
+                                        size_t reason_cap);
 
 /* hg_pcs_verify_device_batch_bn254 / hg_claims_verify_batch_bn254: hg_pcs_verify_device_batch / hg_claims_verify_batch over bn256::Fr,
  *   the same contract word for word with a coordinate or value of 4 canonical limbs: a run of n openings of ONE shape and one
